@@ -8,7 +8,9 @@ sub-pixel/median, and the results (keypoints, descriptors, uRight, depth) copied
 Multi-GPU: independent image streams, one process per GPU, no data-path collective (weak scaling).
 
 `--config` selects another BASELINE.json configuration (mono / fisheye / rgbd: parity cases, not the headline metric).
-Prints ONE JSON line (rank 0).  See DESIGN.md §Measurement for the roofline / cpu_baseline definitions.
+Prints ONE JSON line (rank 0).  A plain run times exactly --steps steps after --warmup untimed ones and reports the headline;
+`--full` adds the parity check, the roofline, the PCIe-inclusive and latency figures, the other configurations and the CPU baseline
+(DESIGN.md §Measurement has their definitions).  `--dump-outputs DIR` saves the last timed step's outputs as .npy files.
 """
 import argparse
 import json
@@ -318,7 +320,7 @@ def other_configs(seconds=2.5):
         # stereo_natural: the headline's configuration on the second generator (--workload natural: camera-like imagery, 1-5 % FAST corner density
         # instead of the corner field's 23.5 %) - no EuRoC frame can be had offline, this is the closest the run can get to one
         cmd = [sys.executable, os.path.abspath(__file__), "--config", "stereo" if name == "stereo_natural" else name, "--steps", "20", "--warmup", "5", "--min-seconds", str(seconds),
-               "--no-cpu-baseline", "--no-h2d", "--no-other-configs", "--no-latency", "--no-live-traffic"] + (["--workload", "natural"] if name == "stereo_natural" else [])
+               "--full", "--no-cpu-baseline", "--no-h2d", "--no-other-configs", "--no-latency", "--no-live-traffic"] + (["--workload", "natural"] if name == "stereo_natural" else [])
         t0 = time.time()
         try:
             pr = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
@@ -337,6 +339,54 @@ def other_configs(seconds=2.5):
         except Exception as e:
             out[name] = {"value": None, "error": repr(e)}
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, kind, P, o):
+    """--dump-outputs: one handle's output buffers after the last timed step, as float32 .npy files under `path`, unit (stereo pair or frame)
+    first.  The buffers hold `cap` entries per image; entries past an image's keypoint count are written as 0, so that equal results give equal
+    files.  When all units exceed DUMP_LIMIT_BYTES a fixed sample of them (seed 0) is written; units.npy says which.  A directory without a
+    .gitignore gets one naming the files written here, so that a dump inside a checkout leaves `git status` clean."""
+    from orb_slam3_detailed_comments_amd import KP_DTYPE
+    paired = kind in ("stereo", "fisheye")
+    cap = o["k"].shape[1]
+    n = o["n"].astype(np.int64)
+    valid = np.arange(cap)[None, :] < n[:, None]                                  # [images, cap]
+    kp = np.ascontiguousarray(o["k"]).view(KP_DTYPE)[..., 0]
+    f32 = lambda a, mask: np.where(mask, a.astype(np.float32), np.float32(0))    # (stale entries may hold NaN or -0.0: not a product)
+    kp = f32(np.stack([kp[f].astype(np.float32) for f in KP_DTYPE.names], axis=-1), valid[..., None])
+    per_image = {"keypoints": kp, "descriptors": f32(o["d"], valid[..., None]), "keypoint_counts": n.astype(np.float32),
+                 "monocular_counts": o["m"].astype(np.float32)}
+    if paired:                                                                    # images [lefts, rights] -> [pair, side]
+        arrays = {k: np.stack([v[:P], v[P:]], axis=1) for k, v in per_image.items()}
+    else:
+        arrays = per_image
+    left, right = valid[:P], valid[P:] if paired else None
+    if kind in ("stereo", "rgbd"):
+        arrays["u_right"] = f32(o["u"], left)
+        arrays["depth"] = f32(o["z"], left)
+    if kind == "stereo":
+        arrays["stereo_matches"] = o["nm"].astype(np.float32)
+    elif kind == "fisheye":
+        arrays.update(left_to_right=f32(o["l2r"], left), right_to_left=f32(o["r2l"], right), depth=f32(o["z"], left), points3d=f32(o["p3"], left[..., None]),
+                      stereo_matches=o["nm"].astype(np.float32))
+    elif kind == "rgbd":
+        arrays.update(local_point_assignments=f32(o["lp_asg"], left), local_point_matches=o["lp_nm"].astype(np.float32))
+    arrays["units"] = np.arange(P, dtype=np.float32)
+    per_unit = sum(a[0].nbytes for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrays)                                # room for every file's .npy header
+    units = np.arange(P)
+    if per_unit * P > budget:
+        units = np.sort(np.random.default_rng(0).choice(P, budget // per_unit, replace=False))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a[units]))
+    ignore = os.path.join(path, ".gitignore")
+    if not os.path.exists(ignore):
+        with open(ignore, "w") as f:
+            f.write("# written by bench.py --dump-outputs\n.gitignore\n" + "".join(name + ".npy\n" for name in sorted(arrays)))
 
 
 def launch_ranks(n):
@@ -374,9 +424,17 @@ def main():
     ap.add_argument("--allgather", action="store_true", help="BASELINE.json configs[4]: after every batch all-gather the descriptor blocks [B, cap, 32] + counts "
                     "of all ranks (RCCL over xGMI) inside the timed region, on a side stream beside the next extraction; the line then also carries the "
                     "collective's own time per batch")
-    ap.add_argument("--min-seconds", type=float, default=6.0, help="the timed region repeats whole blocks of --steps steps until it lasts at least this long "
-                    "(`repeats` in the output; value = all timed units / the whole timed region).  6 s by default: long enough for an outside observer "
-                    "sampling GPU activity every 5 s (the round driver's rocm-smi sampler) to see the device busy")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="the timed region repeats whole blocks of --steps steps until it lasts at least this long "
+                    "(`repeats` in the output; value = all timed units / the whole timed region).  0 by default: exactly --steps steps are timed.  6 gives "
+                    "the region of at least 6 s the full line timed before --full existed, long enough for an outside observer sampling GPU activity every 5 s "
+                    "to see the device busy")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure and check everything else this file knows (each part can still be "
+                    "left out with its --no-* option): the parity check against the reference, the roofline of the dominant kernel (serial steps of its own, "
+                    "live counter passes), the PCIe-inclusive variant, single-pair latency, the other BASELINE.json configurations, the CPU baseline, and "
+                    "the all-gather alone.  Without it a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last timed step computed (keypoints, "
+                    "descriptors, counts, stereo / fisheye / RGB-D association results) as DIR/<name>.npy in float32, at most 64 MB in all: a fixed, "
+                    "seeded sample of the units when the whole batch is larger.  The inputs are seeded, so two builds can be compared output for output")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the `other_configs` block (mono / fisheye / rgbd = BASELINE.json configs 0, 2, 3, each "
                     "measured for >= 1 s by this same file in a child process after the headline)")
     ap.add_argument("--import-copy", action="store_true", help="keep the resident inputs in a separate linear device buffer and copy them into the pyramid inside "
@@ -391,8 +449,8 @@ def main():
                     help="how the host thread waits for the GPU (orbx_set_host_wait): spin = the HIP default, lowest latency, one core per waiting thread; block = sleep on the "
                          "completion interrupt. auto = spin for one rank, block for --gpus N > 1, where N ranks share the host's cores (8 ranks x 2 spinning threads on a "
                          "16-core grant is the whole grant)")
-    ap.add_argument("--no-live-traffic", action="store_true", help="do not measure roofline.traffic with two short rocprofv3 --pmc passes inside this run (keep the tracked figure); the passes belong to the full "
-                    "default line and are also left out with --no-other-configs and under a profiler")
+    ap.add_argument("--no-live-traffic", action="store_true", help="do not measure roofline.traffic with two short rocprofv3 --pmc passes inside this run (keep the tracked figure); the passes belong to the --full "
+                    "line and are also left out with --no-other-configs and under a profiler")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)        # one pair stream of cpu_baseline's all-core setting (internal)
     args = ap.parse_args()
     if args.cpu_worker:
@@ -713,6 +771,8 @@ def main():
     if args.h2d:
         setup_h2d()
     dt, per_step, repeats = timed(args.steps, args.h2d, args.min_seconds)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, kind, P, out[(args.steps * repeats - 1) % NH])     # the handle of the last timed step
     own_cpu_s = timed_cpu[0]
     own_threads = timed_cpu[1] if len(timed_cpu) > 1 else None
 
@@ -769,7 +829,7 @@ def main():
                 "what": "outputs of the last timed step of every handle, fetched inside the timed region", "mismatches": mism[:8], "seconds": round(time.time() - t0, 2)}
 
     parity = None
-    if rank == 0 and not args.no_parity_check and not args.h2d:
+    if rank == 0 and args.full and not args.no_parity_check and not args.h2d:
         try:
             parity = parity_check()
         except Exception as e:
@@ -790,7 +850,7 @@ def main():
         dt = float(t.item())
 
     ag_alone = None
-    if args.allgather:
+    if args.allgather and args.full:
         # the exchange by itself: snapshot + both collectives + wait, nothing else running, barrier-bracketed (max over ranks)
         import torch
         nrep = 20
@@ -822,95 +882,6 @@ def main():
         stage_ms = {k: v / max(stage_cnt[0], 1) for k, v in stage_sum.items()}
         n_timed_records = stage_cnt[0]
         avg_matches = nmatch[0] / max(nmatch[1], 1)
-        # average FAST candidates per image (for the algorithmic-byte model): probe the last batch
-        ncand = 0
-        for l in range(NLEVELS):
-            ncand += len(handles[0].debug_candidates(l, 0))
-        ab = algorithmic_bytes(W, H, avg_kp, ncand)
-        if zero_copy and not args.h2d:
-            ab["import"] = 0                                   # level 0 is read where the producer wrote it
-        if kind == "rgbd":
-            # M4 = 5000 map points x (32 B descriptor + 20 candidates x 32 B) = 3.36 MB per frame.  (Rounds 3-4 priced this
-            # kernel on what the batched search actually moves - 5000 x (88 + 64) + 4 x 5000 x (64 + 16) = 2.36 MB - the survey's figure is the contract.)
-            ab["match"] = 5000 * (32 + 20 * 32)
-        units = {k: NIMG for k in ab}
-        units["match"] = P
-        # Which kernel dominates is decided on a clean schedule: a few extra steps on ONE handle with every kernel alone on one
-        # stream (with several handles in flight an event pair also brackets the time a launch waits for CUs that another
-        # handle's kernels occupy, which inflates short latency-bound stages).  The reported launch duration of that kernel is
-        # its HIP-event average over the TIMED region (what rocprofv3 --kernel-trace sees under the same command).
-        h0 = handles[0]
-        h0.profile(True, serial=True)
-        serial_sum = {}
-        for _ in range(3):
-            enqueue(0)
-            if kind in ("stereo", "fisheye"):
-                fetch(0, False, gather=False)
-            h0.sync()
-            for k, v in h0.stage_ms().items():
-                serial_sum[k] = serial_sum.get(k, 0.0) + v / 3.0
-        ext_stages = ("import", "pyramid", "fast_cells", "quadtree", "blur", "layout", "orient_brief")
-        dom = max((k for k in serial_sum if serial_sum[k] > 0 and k in ab), key=lambda k: serial_sum[k])
-        achieved = ab[dom] * units[dom] / (stage_ms[dom] * 1e-3) / 1e9
-        # ... and the other view: the stage with the largest launch duration UNDER THE TIMED SCHEDULE (several handles in flight: an event pair then also brackets
-        # the time a launch's workgroups wait for CUs other handles' kernels hold - the quadtree's few long workgroups stretch most)
-        dom_wall = max((k for k in stage_ms if stage_ms[k] > 0 and k in ab), key=lambda k: stage_ms[k])
-        # HBM traffic of that kernel: NOT measured in this run (counter collection needs rocprofv3 --pmc passes of their own) but read from the
-        # tracked summary of the last such passes and scaled to this launch size; `traffic_source` says which file, which collection and
-        # whether the kernel sources have changed since (then the figure is stale and says so)
-        traffic = None; traffic_source = None
-        pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(pmc) and kind == "stereo":
-            try:
-                pj = json.load(open(pmc))
-                traffic = pj.get(dom)
-                if traffic is not None:
-                    traffic = int(traffic * NIMG / 128.0)          # the PMC passes ran at 128 images per launch
-                now = kernel_sources_sha()
-                traffic_source = {"file": "profiles/pmc_traffic.json", "collected": pj.get("_source", "round 3 (profiles/r03_final/), before sources carried a stamp"),
-                                  "kernel_sources_sha_then": pj.get("_kernel_sources_sha"), "kernel_sources_sha_now": now,
-                                  "stale": pj.get("_kernel_sources_sha") != now, "measured_in_this_run": False}
-            except Exception:
-                traffic = None
-        # ... and, in the default run on one GPU, MEASURED in this run: two rocprofv3 --pmc passes of their own (FETCH_SIZE, WRITE_SIZE; never combined with
-        # a trace) over a short child run of this file at 128 images per launch, summed over the dominant kernel's dispatches.  The file above stays the
-        # fallback (no rocprofv3, a pass that times out) and the cross-check (`traffic_file`).
-        under_profiler = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprofiler" in os.environ.get("LD_PRELOAD", "")
-        if (kind == "stereo" and world == 1 and dist is None and not args.no_live_traffic and not args.no_other_configs and not args.h2d and not under_profiler
-                and not os.environ.get("ORBX_BENCH_LIB")):
-            live = live_traffic(dom)
-            if live is not None:
-                traffic_source = dict(traffic_source or {}, traffic_file=traffic, measured_in_this_run=True, live=live)
-                traffic = int(live["bytes_per_launch_128_images"] * NIMG / 128.0)
-        # VALU issue view of the same kernel (the HBM fraction says little for a compute-heavy integer kernel): wave-instructions per launch
-        # from the SQ counter pass (profiles/pmc_valu.json, scaled to this launch size) against the SIMD-32 issue peak of one wave64
-        # instruction per 2 clk (1024 SIMDs x 2.4 GHz / 2 = 1228.8 G wave-instr/s; profiles/r02/valu_survey.txt: only the VOP2 integer forms
-        # reach ~2.5 clk, every VOP3 form takes ~4.4 clk, so a kernel built from both classes sits between 45 % and 80 % of that peak at best)
-        valu = None
-        pv = os.path.join(ROOT, "profiles", "pmc_valu.json")
-        if os.path.exists(pv) and kind == "stereo":
-            try:
-                n_instr = json.load(open(pv)).get(dom, 0) * NIMG / 128.0
-                if n_instr > 0:
-                    valu = {"wave_instr_per_launch": int(n_instr), "peak_wave_instr_per_s": VALU_PEAK_WAVE_INSTR_PER_S,
-                            "achieved_wave_instr_per_s": round(n_instr / (stage_ms[dom] * 1e-3), 0), "alone_wave_instr_per_s": round(n_instr / (serial_sum[dom] * 1e-3), 0),
-                            "frac": round(n_instr / (stage_ms[dom] * 1e-3) / VALU_PEAK_WAVE_INSTR_PER_S, 4),
-                            "alone_frac": round(n_instr / (serial_sum[dom] * 1e-3) / VALU_PEAK_WAVE_INSTR_PER_S, 4)}
-            except Exception:
-                valu = None
-        # the whole step in the same units: every kernel's wave-instructions per step / ms_per_step
-        step_valu = None
-        try:
-            if os.path.exists(pv) and kind == "stereo":
-                pvj = json.load(open(pv))
-                tot = sum(float(v) for k, v in pvj.items() if not k.startswith("_")) * NIMG / 128.0
-                step_ms_now = dt / (args.steps * repeats) * 1e3
-                step_valu = {"wave_instr_per_step": int(tot), "achieved_wave_instr_per_s": round(tot / (step_ms_now * 1e-3), 0),
-                             "frac": round(tot / (step_ms_now * 1e-3) / VALU_PEAK_WAVE_INSTR_PER_S, 4), "kernel_sources_sha_of_counts": pvj.get("_kernel_sources_sha"),
-                             "stale": pvj.get("_kernel_sources_sha") != kernel_sources_sha()}
-        except Exception:
-            step_valu = None
-        per_unit_bytes = (2 if paired else 1) * sum(v for k, v in ab.items() if k not in ("match", "fast_cells_with_candidates")) + (ab["match"] if kind == "stereo" else 0)
         pct = lambda a, q: float(np.percentile(a, q)) if len(a) else None
         res = {
             "metric": cfg["metric"], "value": round(value, 1),
@@ -932,28 +903,6 @@ def main():
                              "max": max(block_values) if block_values else None},
             # per-step completion intervals of the timed region (rank 0; with several handles in flight a step completes every ms_per_step on average)
             "step_ms": {"median": round(pct(per_step, 50), 4), "p10": round(pct(per_step, 10), 4), "p90": round(pct(per_step, 90), 4), "n": int(len(per_step))},
-            # achieved / peak / frac: the kernel's ALGORITHMIC bytes (SURVEY.md 8d) per launch over its HIP-event launch duration in the timed region, against the 8 TB/s
-            # of HBM - the figure the contract asks for.  `bound` says what actually limits that kernel: for k_fast_cells the vector and LDS issue ports (valu_issue:
-            # instruction counts from the SQ counter passes; its HBM traffic is 0.95 x algorithmic - nothing is re-read - and a small fraction of the link)
-            "roofline": {"bound": "valu_lds_issue" if (valu is not None and valu["frac"] > achieved / HBM_PEAK_GBS) else "hbm",
-                         "kernel": dom, "kernel_chosen_by": "largest launch duration alone on one stream (stage_ms_alone)",
-                         "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_source,
-                         "algorithmic_bytes_per_launch": int(ab[dom] * units[dom]), "avg_launch_ms": round(stage_ms[dom], 4),
-                         "alone_launch_ms": round(serial_sum[dom], 4), "alone_GBps": round(ab[dom] * units[dom] / (serial_sum[dom] * 1e-3) / 1e9, 2),
-                         "with_candidate_output": None if dom != "fast_cells" else {
-                             "algorithmic_bytes_per_launch": int(ab["fast_cells_with_candidates"] * units[dom]),
-                             "achieved": round(ab["fast_cells_with_candidates"] * units[dom] / (stage_ms[dom] * 1e-3) / 1e9, 2),
-                             "frac": round(ab["fast_cells_with_candidates"] * units[dom] / (stage_ms[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                             "what": "pixels read + the 4-byte record of every FAST candidate written (the figure rounds 1-5 printed as `frac`)"},
-                         "by_wall": {"kernel": dom_wall, "kernel_chosen_by": "largest launch duration in the timed region, %d handles in flight (stage_ms_per_step)" % NH,
-                                     "avg_launch_ms": round(stage_ms[dom_wall], 4), "alone_launch_ms": round(serial_sum.get(dom_wall, 0.0), 4),
-                                     "algorithmic_bytes_per_launch": int(ab[dom_wall] * units[dom_wall]),
-                                     "achieved": round(ab[dom_wall] * units[dom_wall] / (stage_ms[dom_wall] * 1e-3) / 1e9, 2),
-                                     "frac": round(ab[dom_wall] * units[dom_wall] / (stage_ms[dom_wall] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                                     "bound": "latency (one workgroup per tree; its launch duration beside other handles' kernels is mostly waiting)" if dom_wall == "quadtree" else None},
-                         "end_to_end_GBps": round(per_unit_bytes * value / world / 1e9, 2),
-                         "end_to_end_frac": round(per_unit_bytes * value / world / 1e9 / HBM_PEAK_GBS, 5), "valu_issue": valu, "step_valu_issue": step_valu},
             "parity_check": parity,
             # each rank's own rate over the same barrier-bracketed region (its units / its own clock): `value` uses the slowest rank's time
             "per_rank": None if per_rank_dt is None else {
@@ -968,11 +917,123 @@ def main():
                          "rank0_busiest_threads_cpu_s": own_threads, "timed_seconds": round(dt, 3), "host_wait": host_wait_mode},
             "allgather": ag_alone,
             "stage_ms_per_step": {k: round(v, 4) for k, v in stage_ms.items()},
-            "stage_ms_alone": {k: round(v, 4) for k, v in serial_sum.items()},
-            # the reference's two instrumented regions (src/Frame.cc:132-146 / :158-170, printed by Tracking::PrintTimeStats), per step, each kernel alone
-            "reference_stage_ms_alone": {"ORB Extraction": round(sum(serial_sum.get(k, 0.0) for k in ext_stages), 4), "Stereo Matching": round(serial_sum.get("match", 0.0), 4)},
         }
-        if kind == "stereo" and not args.h2d and not args.no_h2d and world == 1 and dist is None:
+        if args.full:
+            # average FAST candidates per image (for the algorithmic-byte model): probe the last batch
+            ncand = 0
+            for l in range(NLEVELS):
+                ncand += len(handles[0].debug_candidates(l, 0))
+            ab = algorithmic_bytes(W, H, avg_kp, ncand)
+            if zero_copy and not args.h2d:
+                ab["import"] = 0                                   # level 0 is read where the producer wrote it
+            if kind == "rgbd":
+                # M4 = 5000 map points x (32 B descriptor + 20 candidates x 32 B) = 3.36 MB per frame.  (Rounds 3-4 priced this
+                # kernel on what the batched search actually moves - 5000 x (88 + 64) + 4 x 5000 x (64 + 16) = 2.36 MB - the survey's figure is the contract.)
+                ab["match"] = 5000 * (32 + 20 * 32)
+            units = {k: NIMG for k in ab}
+            units["match"] = P
+            # Which kernel dominates is decided on a clean schedule: a few extra steps on ONE handle with every kernel alone on one
+            # stream (with several handles in flight an event pair also brackets the time a launch waits for CUs that another
+            # handle's kernels occupy, which inflates short latency-bound stages).  The reported launch duration of that kernel is
+            # its HIP-event average over the TIMED region (what rocprofv3 --kernel-trace sees under the same command).
+            h0 = handles[0]
+            h0.profile(True, serial=True)
+            serial_sum = {}
+            for _ in range(3):
+                enqueue(0)
+                if kind in ("stereo", "fisheye"):
+                    fetch(0, False, gather=False)
+                h0.sync()
+                for k, v in h0.stage_ms().items():
+                    serial_sum[k] = serial_sum.get(k, 0.0) + v / 3.0
+            ext_stages = ("import", "pyramid", "fast_cells", "quadtree", "blur", "layout", "orient_brief")
+            dom = max((k for k in serial_sum if serial_sum[k] > 0 and k in ab), key=lambda k: serial_sum[k])
+            achieved = ab[dom] * units[dom] / (stage_ms[dom] * 1e-3) / 1e9
+            # ... and the other view: the stage with the largest launch duration UNDER THE TIMED SCHEDULE (several handles in flight: an event pair then also brackets
+            # the time a launch's workgroups wait for CUs other handles' kernels hold - the quadtree's few long workgroups stretch most)
+            dom_wall = max((k for k in stage_ms if stage_ms[k] > 0 and k in ab), key=lambda k: stage_ms[k])
+            # HBM traffic of that kernel: NOT measured in this run (counter collection needs rocprofv3 --pmc passes of their own) but read from the
+            # tracked summary of the last such passes and scaled to this launch size; `traffic_source` says which file, which collection and
+            # whether the kernel sources have changed since (then the figure is stale and says so)
+            traffic = None; traffic_source = None
+            pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(pmc) and kind == "stereo":
+                try:
+                    pj = json.load(open(pmc))
+                    traffic = pj.get(dom)
+                    if traffic is not None:
+                        traffic = int(traffic * NIMG / 128.0)          # the PMC passes ran at 128 images per launch
+                    now = kernel_sources_sha()
+                    traffic_source = {"file": "profiles/pmc_traffic.json", "collected": pj.get("_source", "round 3 (profiles/r03_final/), before sources carried a stamp"),
+                                      "kernel_sources_sha_then": pj.get("_kernel_sources_sha"), "kernel_sources_sha_now": now,
+                                      "stale": pj.get("_kernel_sources_sha") != now, "measured_in_this_run": False}
+                except Exception:
+                    traffic = None
+            # ... and, in a --full run on one GPU, MEASURED in this run: two rocprofv3 --pmc passes of their own (FETCH_SIZE, WRITE_SIZE; never combined with
+            # a trace) over a short child run of this file at 128 images per launch, summed over the dominant kernel's dispatches.  The file above stays the
+            # fallback (no rocprofv3, a pass that times out) and the cross-check (`traffic_file`).
+            under_profiler = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprofiler" in os.environ.get("LD_PRELOAD", "")
+            if (kind == "stereo" and world == 1 and dist is None and not args.no_live_traffic and not args.no_other_configs and not args.h2d and not under_profiler
+                    and not os.environ.get("ORBX_BENCH_LIB")):
+                live = live_traffic(dom)
+                if live is not None:
+                    traffic_source = dict(traffic_source or {}, traffic_file=traffic, measured_in_this_run=True, live=live)
+                    traffic = int(live["bytes_per_launch_128_images"] * NIMG / 128.0)
+            # VALU issue view of the same kernel (the HBM fraction says little for a compute-heavy integer kernel): wave-instructions per launch
+            # from the SQ counter pass (profiles/pmc_valu.json, scaled to this launch size) against the SIMD-32 issue peak of one wave64
+            # instruction per 2 clk (1024 SIMDs x 2.4 GHz / 2 = 1228.8 G wave-instr/s; profiles/r02/valu_survey.txt: only the VOP2 integer forms
+            # reach ~2.5 clk, every VOP3 form takes ~4.4 clk, so a kernel built from both classes sits between 45 % and 80 % of that peak at best)
+            valu = None
+            pv = os.path.join(ROOT, "profiles", "pmc_valu.json")
+            if os.path.exists(pv) and kind == "stereo":
+                try:
+                    n_instr = json.load(open(pv)).get(dom, 0) * NIMG / 128.0
+                    if n_instr > 0:
+                        valu = {"wave_instr_per_launch": int(n_instr), "peak_wave_instr_per_s": VALU_PEAK_WAVE_INSTR_PER_S,
+                                "achieved_wave_instr_per_s": round(n_instr / (stage_ms[dom] * 1e-3), 0), "alone_wave_instr_per_s": round(n_instr / (serial_sum[dom] * 1e-3), 0),
+                                "frac": round(n_instr / (stage_ms[dom] * 1e-3) / VALU_PEAK_WAVE_INSTR_PER_S, 4),
+                                "alone_frac": round(n_instr / (serial_sum[dom] * 1e-3) / VALU_PEAK_WAVE_INSTR_PER_S, 4)}
+                except Exception:
+                    valu = None
+            # the whole step in the same units: every kernel's wave-instructions per step / ms_per_step
+            step_valu = None
+            try:
+                if os.path.exists(pv) and kind == "stereo":
+                    pvj = json.load(open(pv))
+                    tot = sum(float(v) for k, v in pvj.items() if not k.startswith("_")) * NIMG / 128.0
+                    step_ms_now = dt / (args.steps * repeats) * 1e3
+                    step_valu = {"wave_instr_per_step": int(tot), "achieved_wave_instr_per_s": round(tot / (step_ms_now * 1e-3), 0),
+                                 "frac": round(tot / (step_ms_now * 1e-3) / VALU_PEAK_WAVE_INSTR_PER_S, 4), "kernel_sources_sha_of_counts": pvj.get("_kernel_sources_sha"),
+                                 "stale": pvj.get("_kernel_sources_sha") != kernel_sources_sha()}
+            except Exception:
+                step_valu = None
+            per_unit_bytes = (2 if paired else 1) * sum(v for k, v in ab.items() if k not in ("match", "fast_cells_with_candidates")) + (ab["match"] if kind == "stereo" else 0)
+            # achieved / peak / frac: the kernel's ALGORITHMIC bytes (SURVEY.md 8d) per launch over its HIP-event launch duration in the timed region, against the 8 TB/s
+            # of HBM - the figure the contract asks for.  `bound` says what actually limits that kernel: for k_fast_cells the vector and LDS issue ports (valu_issue:
+            # instruction counts from the SQ counter passes; its HBM traffic is 0.95 x algorithmic - nothing is re-read - and a small fraction of the link)
+            res["roofline"] = {"bound": "valu_lds_issue" if (valu is not None and valu["frac"] > achieved / HBM_PEAK_GBS) else "hbm",
+                               "kernel": dom, "kernel_chosen_by": "largest launch duration alone on one stream (stage_ms_alone)",
+                               "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_source,
+                               "algorithmic_bytes_per_launch": int(ab[dom] * units[dom]), "avg_launch_ms": round(stage_ms[dom], 4),
+                               "alone_launch_ms": round(serial_sum[dom], 4), "alone_GBps": round(ab[dom] * units[dom] / (serial_sum[dom] * 1e-3) / 1e9, 2),
+                               "with_candidate_output": None if dom != "fast_cells" else {
+                                   "algorithmic_bytes_per_launch": int(ab["fast_cells_with_candidates"] * units[dom]),
+                                   "achieved": round(ab["fast_cells_with_candidates"] * units[dom] / (stage_ms[dom] * 1e-3) / 1e9, 2),
+                                   "frac": round(ab["fast_cells_with_candidates"] * units[dom] / (stage_ms[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                                   "what": "pixels read + the 4-byte record of every FAST candidate written (the figure rounds 1-5 printed as `frac`)"},
+                               "by_wall": {"kernel": dom_wall, "kernel_chosen_by": "largest launch duration in the timed region, %d handles in flight (stage_ms_per_step)" % NH,
+                                           "avg_launch_ms": round(stage_ms[dom_wall], 4), "alone_launch_ms": round(serial_sum.get(dom_wall, 0.0), 4),
+                                           "algorithmic_bytes_per_launch": int(ab[dom_wall] * units[dom_wall]),
+                                           "achieved": round(ab[dom_wall] * units[dom_wall] / (stage_ms[dom_wall] * 1e-3) / 1e9, 2),
+                                           "frac": round(ab[dom_wall] * units[dom_wall] / (stage_ms[dom_wall] * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                                           "bound": "latency (one workgroup per tree; its launch duration beside other handles' kernels is mostly waiting)" if dom_wall == "quadtree" else None},
+                               "end_to_end_GBps": round(per_unit_bytes * value / world / 1e9, 2),
+                               "end_to_end_frac": round(per_unit_bytes * value / world / 1e9 / HBM_PEAK_GBS, 5), "valu_issue": valu, "step_valu_issue": step_valu}
+            res["stage_ms_alone"] = {k: round(v, 4) for k, v in serial_sum.items()}
+            # the reference's two instrumented regions (src/Frame.cc:132-146 / :158-170, printed by Tracking::PrintTimeStats), per step, each kernel alone
+            res["reference_stage_ms_alone"] = {"ORB Extraction": round(sum(serial_sum.get(k, 0.0) for k in ext_stages), 4), "Stereo Matching": round(serial_sum.get("match", 0.0), 4)}
+        if args.full and kind == "stereo" and not args.h2d and not args.no_h2d and world == 1 and dist is None:
             # second measurement, never `value`: the same steps with every input batch uploaded from page-locked host memory inside the timed
             # region, on each handle's copy stream, double-buffered (upload of batch i + 1 beside the kernels of batch i)
             try:
@@ -1002,7 +1063,7 @@ def main():
                 res["value_host_fed"] = res["h2d_inclusive"]["value"]
             except Exception as e:
                 res["h2d_inclusive"] = {"value": None, "error": repr(e)}
-        if kind == "stereo" and world == 1 and not args.no_latency and not os.environ.get("ORBX_BENCH_LIB"):
+        if args.full and kind == "stereo" and world == 1 and not args.no_latency and not os.environ.get("ORBX_BENCH_LIB"):
             # reported beside the throughput, never `value`: one stereo pair per call on one fresh handle, synchronised after every pair
             # (Tracking's rhythm: extract L + R, ComputeStereoMatches, wait), the frames written into pyramid level 0 by the producer
             try:
@@ -1052,11 +1113,11 @@ def main():
                                       "what": "orbx_extract / orbx_extract_batch from pageable host memory, results copied back to caller arrays, host waits after every call (Python ctypes caller)"}
             except Exception as e:
                 res["latency"] = {"single_pair_ms": None, "error": repr(e)}
-        if kind == "stereo" and world == 1 and dist is None and not args.no_other_configs and not args.h2d and not os.environ.get("ORBX_BENCH_LIB"):
+        if args.full and kind == "stereo" and world == 1 and dist is None and not args.no_other_configs and not args.h2d and not os.environ.get("ORBX_BENCH_LIB"):
             for h in handles:
                 h.sync()
             res["other_configs"] = other_configs()
-        if kind == "stereo" and not args.no_cpu_baseline and world == 1:
+        if args.full and kind == "stereo" and not args.no_cpu_baseline and world == 1:
             try:
                 res["cpu_baseline"] = cpu_baseline()
             except Exception as e:   # the baseline is reporting only; never fail the bench on it

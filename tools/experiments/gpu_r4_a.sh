@@ -3,7 +3,7 @@
 O=gpurun_out/r04_a
 mkdir -p $O
 python -m pytest tests -x -q -m gpu > $O/pytest_gpu.log 2>&1; tail -5 $O/pytest_gpu.log
-python bench.py > $O/bench_n1.json 2> $O/bench.err; tail -3 $O/bench.err
+python bench.py --full --min-seconds 6 > $O/bench_n1.json 2> $O/bench.err; tail -3 $O/bench.err
 python - <<'PY'
 import json
 r = json.load(open("gpurun_out/r04_a/bench_n1.json"))

@@ -9,5 +9,5 @@ r = json.load(open("gpurun_out/r04_b/next_rows.json"))
 for k, v in r.items():
     if "batched on the device" in k or "SearchLocalPoints" in k: print(k[:90], v)
 PY
-python bench.py --allgather --steps 60 --warmup 10 --min-seconds 2 --no-cpu-baseline --no-other-configs 2>> $O/bench.err | grep "^{" > $O/bench_allgather_n1.json; python -c "import json; r=json.load(open('$O/bench_allgather_n1.json')); print('allgather', r['value'], r['allgather'])"; tail -2 $O/bench.err
-python bench.py --config rgbd --steps 40 --warmup 6 --min-seconds 2 --no-cpu-baseline > $O/bench_rgbd.json 2>> $O/bench.err; python -c "import json; r=json.load(open('$O/bench_rgbd.json')); print('rgbd', r['value'], r['stage_ms_alone'])"
+python bench.py --full --allgather --steps 60 --warmup 10 --min-seconds 2 --no-cpu-baseline --no-other-configs 2>> $O/bench.err | grep "^{" > $O/bench_allgather_n1.json; python -c "import json; r=json.load(open('$O/bench_allgather_n1.json')); print('allgather', r['value'], r['allgather'])"; tail -2 $O/bench.err
+python bench.py --full --config rgbd --steps 40 --warmup 6 --min-seconds 2 --no-cpu-baseline > $O/bench_rgbd.json 2>> $O/bench.err; python -c "import json; r=json.load(open('$O/bench_rgbd.json')); print('rgbd', r['value'], r['stage_ms_alone'])"

@@ -5,7 +5,7 @@ mkdir -p $O
 AB="--steps 200 --warmup 20 --min-seconds 3 --no-cpu-baseline --no-h2d --no-other-configs --no-latency"
 run() { # name, env...
   name=$1; shift
-  env "$@" python bench.py $AB > $O/sweep_$name.json 2>> $O/ab.err
+  env "$@" python bench.py --full $AB > $O/sweep_$name.json 2>> $O/ab.err
   python -c "import json; r=json.load(open('$O/sweep_$name.json')); print('$name', r['value'], r['ms_per_step'], r['parity_check']['identical'], 'blur alone', r['stage_ms_alone']['blur'], 'in flight', r['stage_ms_per_step']['blur'])"
 }
 for rep in 1 2; do

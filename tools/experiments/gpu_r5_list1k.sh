@@ -8,7 +8,7 @@ A="--no-cpu-baseline --no-h2d --no-other-configs --no-latency --no-live-traffic 
 for rep in 1 2; do
   for v in base ${VARIANTS:-list1k}; do
     if [ $v = base ]; then unset ORBX_BENCH_LIB; else export ORBX_BENCH_LIB=$PWD/build/variants/liborbx_hip_$v.so; fi
-    python bench.py $A 2>> $O/err.txt | python -c "
+    python bench.py --full $A 2>> $O/err.txt | python -c "
 import json,sys
 r=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('$v', r['value'], r['ms_per_step'], r['parity_check']['identical'], r['stage_ms_alone']['fast_cells'], r['stage_ms_per_step']['fast_cells'], r['config']['library'])" | tee -a $O/ab.txt

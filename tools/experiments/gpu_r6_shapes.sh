@@ -2,4 +2,4 @@
 # step shapes: pairs per step x handles in flight (the default is 128 x 4)
 O=gpurun_out/r06_shapes; mkdir -p $O
 show='import sys,json; r=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith("{")][-1]); print(r["value"], r["ms_per_step"], r["parity_check"]["identical"])'
-for shape in "128 4" "256 4" "256 3" "256 2" "192 4" "384 3" "512 2" "96 4" "128 4"; do set -- $shape; echo -n "pairs $1 handles $2: "; python bench.py --pairs $1 --handles $2 --steps 60 --warmup 10 --min-seconds 3 --no-cpu-baseline --no-h2d --no-other-configs --no-latency --no-live-traffic 2>/dev/null | python -c "$show"; done | tee $O/shapes.txt
+for shape in "128 4" "256 4" "256 3" "256 2" "192 4" "384 3" "512 2" "96 4" "128 4"; do set -- $shape; echo -n "pairs $1 handles $2: "; python bench.py --full --pairs $1 --handles $2 --steps 60 --warmup 10 --min-seconds 3 --no-cpu-baseline --no-h2d --no-other-configs --no-latency --no-live-traffic 2>/dev/null | python -c "$show"; done | tee $O/shapes.txt
