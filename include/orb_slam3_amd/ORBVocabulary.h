@@ -31,6 +31,7 @@ public:
     }
     unsigned int size() const { return (unsigned int)orbv_words(v_); }
     bool empty() const { return v_ == nullptr || orbv_words(v_) == 0; }
+    orbv_vocabulary* Handle() const { return v_; }                                  // the device vocabulary (KeyFrameDatabase.h)
 
     // TemplatedVocabulary::transform(features, BowVector&, FeatureVector&, levelsup), TemplatedVocabulary.h:1127-1195
     void transform(const std::vector<cv::Mat>& features, DBoW2::BowVector& v, DBoW2::FeatureVector& fv, int levelsup) const {

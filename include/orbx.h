@@ -729,6 +729,41 @@ int orbv_fetch(orbv_vocabulary* v, orbx_extractor* h, int b, uint32_t* word_id, 
 int orbm_search_by_bow_frames_batch(orbx_extractor* h, const orbv_vocabulary* v, int first, int B, orbm_keyframe* const* KFs,
                                     const uint8_t* const* has_map_point, float nnratio, int check_orientation, int* const* matches12, int* nmatches);
 
+/* ---- Key frame database (KeyFrameDatabase, src/KeyFrameDatabase.cc): the inverted-file part of place
+ * recognition on the device.  One record per add, keyed by a caller key (a KeyFrame* or its mnId), in add order; every query walks all
+ * records at once: the words each shares with the query (a key added twice counts twice, like the reference's duplicated list entries),
+ * maxCommonWords over the keys left after the exclusions, minCommonWords = (int)(max * 0.8f), the score (TemplatedVocabulary::score,
+ * bit-exact in fp64) of every key with more words than that, and the sharing keys in the order the reference's walk first meets them
+ * (ascending query word, then each word's list in add order).  The per-KeyFrame fields, the covisibility accumulation and the map
+ * filters stay with the caller (include/orb_slam3_amd/KeyFrameDatabase.h).  The database owns a stream of its own; it lives on the
+ * vocabulary's device and may be used from any thread, one call at a time. ---- */
+typedef struct orbv_database orbv_database;
+
+/* KeyFrameDatabase(voc): the word count and the scoring type come from v; KL scoring is refused (ORBX_E_ARG).  h: an extractor handle of v's
+ * device (only its device is used; the database does not keep it). */
+int orbv_db_create(orbv_vocabulary* v, orbx_extractor* h, orbv_database** out);
+void orbv_db_destroy(orbv_database* db);
+/* add(pKF): the BowVector as ascending word ids < orbv_words(v) and values.  A key added again must carry the same vector (n and a checksum are
+ * compared: ORBX_E_ARG otherwise). */
+int orbv_db_add(orbv_database* db, uint64_t key, const uint32_t* bow_id, const double* bow_val, int n);
+/* the same with image b of the last vocabulary transform (orbv_transform_extracted / orbv_transform; b relative to its first image) */
+int orbv_db_add_extracted(orbv_database* db, uint64_t key, orbx_extractor* h, int b);
+/* erase(pKF): drops the earliest surviving add of key; an absent key is a no-op */
+int orbv_db_erase(orbv_database* db, uint64_t key);
+/* every add of each of the n keys (clearMap(pMap) with the keys whose GetMap() == pMap) */
+int orbv_db_erase_keys(orbv_database* db, const uint64_t* keys, int n);
+int orbv_db_clear(orbv_database* db);
+int orbv_db_size(const orbv_database* db);                                      /* surviving adds */
+/* Q queries in one pass.  Query q's BowVector: q_ids / q_vals [q_start[q], q_start[q+1]) (ascending ids).  x_start (Q+1) / x_keys: keys query q
+ * ignores (Detect*'s connected key frames; x_start NULL = none).  score_all != 0 scores every sharing key.  Results of query q at [q * cap ..):
+ * keys, words (shared words), scored (words > min_common[q] or score_all), score (score(query, key), 0 where not scored), in first-appearance
+ * order; n_out[q] of them.  Any result array may be NULL.  ORBX_E_CAPACITY when some n_out[q] > cap (n_out still holds the sizes needed). */
+int orbv_db_query(orbv_database* db, int Q, const int* q_start, const uint32_t* q_ids, const double* q_vals, const int* x_start, const uint64_t* x_keys,
+                  int score_all, int cap, uint64_t* keys, int* words, uint8_t* scored, double* score, int* n_out, int* min_common);
+/* the same for images [first, first + Q) of the last vocabulary transform, whose BowVectors are read where it left them (no copy) */
+int orbv_db_query_extracted(orbv_database* db, orbx_extractor* h, int first, int Q, const int* x_start, const uint64_t* x_keys, int score_all, int cap,
+                            uint64_t* keys, int* words, uint8_t* scored, double* score, int* n_out, int* min_common);
+
 const char* orbx_last_error(void);
 
 #ifdef __cplusplus

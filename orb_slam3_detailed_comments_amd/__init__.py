@@ -4,6 +4,6 @@ from ._lib import KP_DTYPE, OrbxError, load_hip  # noqa: F401
 from .extractor import ORBextractor  # noqa: F401
 from .matcher import (ORBmatcher, ComputeStereoMatches, StereoFishEyeKnn, GetFeaturesInArea, AreaSearchBatch,  # noqa: F401
                       ComputeDistinctiveDescriptors)
-from .vocabulary import ORBVocabulary  # noqa: F401
+from .vocabulary import ORBVocabulary, KeyFrameDatabase  # noqa: F401
 from . import views, sophus  # noqa: F401
 from .sophus import SE3f, Sim3f  # noqa: F401

@@ -33,6 +33,8 @@ SYMBOLS = [
     "orbm_project_points", "orbm_search_by_projection_sim3", "orbm_search_by_projection_keyframe", "orbm_fuse_candidates", "orbm_search_by_sim3", "orbm_distinctive_descriptors",
     "orbm_search_by_projection_mappoints_fisheye", "orbm_search_by_projection_frame_fisheye", "orbm_search_for_triangulation_batch",
     "orbv_create", "orbv_load_text", "orbv_destroy", "orbv_words", "orbv_transform", "orbv_transform_extracted", "orbv_fetch", "orbm_search_by_bow_frames_batch",
+    "orbv_db_create", "orbv_db_destroy", "orbv_db_add", "orbv_db_add_extracted", "orbv_db_erase", "orbv_db_erase_keys", "orbv_db_clear", "orbv_db_size",
+    "orbv_db_query", "orbv_db_query_extracted",
     "orbx_comm_unique_id", "orbx_comm_create", "orbx_comm_adopt", "orbx_comm_destroy", "orbx_comm_world", "orbx_comm_rank", "orbx_allgather_descriptors", "orbx_comm_wait",
     "orbx_comm_fetch",
     "orbx_last_error",
@@ -151,6 +153,17 @@ class OrbxLib:
         L.orbv_transform_extracted.argtypes = [vp, vp, i, i, i]
         L.orbv_fetch.argtypes = [vp, vp, i, vp, vp, i, vp, vp, ip, vp, vp, vp, ip]
         L.orbm_search_by_bow_frames_batch.argtypes = [vp, vp, i, i, vp, vp, f, i, vp, vp]
+        u64 = C.c_uint64
+        L.orbv_db_create.argtypes = [vp, vp, C.POINTER(vp)]
+        L.orbv_db_destroy.argtypes = [vp]; L.orbv_db_destroy.restype = None
+        L.orbv_db_add.argtypes = [vp, u64, vp, vp, i]
+        L.orbv_db_add_extracted.argtypes = [vp, u64, vp, i]
+        L.orbv_db_erase.argtypes = [vp, u64]
+        L.orbv_db_erase_keys.argtypes = [vp, vp, i]
+        L.orbv_db_clear.argtypes = [vp]
+        L.orbv_db_size.argtypes = [vp]
+        L.orbv_db_query.argtypes = [vp, i, vp, vp, vp, vp, vp, i, i, vp, vp, vp, vp, vp, vp]
+        L.orbv_db_query_extracted.argtypes = [vp, vp, i, i, vp, vp, i, i, vp, vp, vp, vp, vp, vp]
         L.orbx_comm_unique_id.argtypes = [vp]
         L.orbx_comm_create.argtypes = [C.POINTER(vp), i, i, vp, i]
         L.orbx_comm_adopt.argtypes = [C.POINTER(vp), vp, i, i, i]

@@ -11,6 +11,16 @@
 //                   (std::map<NodeId, vector<unsigned>>: ascending node ids, feature indices in insertion order) as sorted
 //                   arrays; bitonic sort of (id << 16 | feature) keys in LDS, run detection with a workgroup scan, and the
 //                   order-dependent double-precision sums done sequentially by one thread exactly as the map iteration does.
+// Key frame database (KeyFrameDatabase, src/KeyFrameDatabase.cc; host side in orbv_api.cpp: orbv_db_*): one record per add, in add order,
+// with its sorted BowVector in a CSR arena.  Three launches per batch of Q queries:
+//   k_kfdb_count    one wave per (record, query): the words the record shares with the query (binary search in the query's sorted ids in
+//                   LDS) times the record's multiplicity (duplicate adds fold into the earliest; the others carry 0), and the position in
+//                   the query of the first shared word.  This is what the inverted-file walk of Detect*Candidates counts per key frame.
+//   k_kfdb_order    one workgroup per query: drops excluded keys, the maximum and minCommonWords = (int)(max * 0.8f), and a stable
+//                   counting sort of the sharing records on the first shared position (records are in add order, so this is the order in
+//                   which the walk first meets them: word by word, each word's list in add order).
+//   k_kfdb_score    one wave per scored key: ScoringObject::score (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp), one term per common word, added
+//                   in ascending word order in fp64 exactly as the reference's loop does (no reassociation, no contraction).
 #include "orbx_types.h"
 #include "orbx_block.h"
 
@@ -173,6 +183,184 @@ __global__ void __launch_bounds__(256) k_voc_assemble(const unsigned* __restrict
             if (tid == 0) n_out[2 * b + 1] = nu;
         }
         __syncthreads();
+    }
+}
+
+// ---- key frame database ----
+// position of w in the ascending ids qw[0, nq), or -1
+__device__ __forceinline__ int kfdb_find(const unsigned* qw, int nq, unsigned w) {
+    int lo = 0, hi = nq;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (qw[mid] < w) lo = mid + 1; else hi = mid; }
+    return (lo < nq && qw[lo] == w) ? lo : -1;
+}
+
+// grid (ceil(R / 32), Q), 256 threads, dynamic LDS = 4 * (largest query) bytes.  cnt / firstpos [Q][R]: 0 / 0xFFFFFFFF for a record that
+// shares nothing, is erased or is a later duplicate (rmult 0)
+__global__ void __launch_bounds__(256) k_kfdb_count(const unsigned* __restrict__ ids, const long long* __restrict__ rstart, const int* __restrict__ rn,
+                                                    const int* __restrict__ rmult, int R, KfdbQuerySet qs, int* __restrict__ cnt, int* __restrict__ firstpos) {
+    ORBX_DYN_SMEM(smem);
+    unsigned* qw = (unsigned*)smem;
+    const int tid = (int)threadIdx.x, lane = lane_id(), wave = tid >> 6, q = (int)blockIdx.y;
+    const int nq = qs.n[(size_t)q * qs.n_step];
+    const unsigned* src = qs.ids + (qs.start ? (size_t)qs.start[q] : (size_t)q * qs.stride);
+    for (int i = tid; i < nq; i += 256) qw[i] = src[i];
+    __syncthreads();
+    const int rb = (int)blockIdx.x * kKfdbRecsPerBlock, re = imin(R, rb + kKfdbRecsPerBlock);
+    for (int r = rb + wave; r < re; r += 4) {
+        const int m = rmult[r];
+        int c = 0;
+        unsigned f = 0xFFFFFFFFu;
+        if (m > 0 && nq > 0) {
+            const long long s = rstart[r];
+            const int n = rn[r];
+            for (int i0 = 0; i0 < n; i0 += 64) {
+                const int i = i0 + lane;
+                if (i < n) {
+                    const int p = kfdb_find(qw, nq, ids[s + i]);
+                    if (p >= 0) { c++; f = (unsigned)p < f ? (unsigned)p : f; }
+                }
+            }
+            c = wave_sum(c);
+            f = wave_min_u32(f);
+        }
+        if (lane == 0) { cnt[(size_t)q * R + r] = c * m; firstpos[(size_t)q * R + r] = (int)f; }
+    }
+}
+
+// grid (Q), nw * 64 threads (nw <= 16), dynamic LDS = 4 * nw * (largest query) bytes: one row of bin counters per wave.
+// Excluded records (xrec[xstart[q] .. xstart[q+1])) are zeroed in cnt first.  Wave w owns records [w * seg, (w + 1) * seg): it counts
+// their first positions into its row, the rows become exclusive offsets (bin-major, then wave), and every wave places its records in
+// record order, 64 at a time, ranking equal bins by lane.  head[4q] = sharing keys, head[4q + 1] = minCommonWords, head[4q + 2] = scored.
+__global__ void __launch_bounds__(1024) k_kfdb_order(int* __restrict__ cnt, const int* __restrict__ firstpos, const unsigned long long* __restrict__ rkey, int R,
+                                                     const int* __restrict__ qn, int qn_step, const int* __restrict__ xstart, const int* __restrict__ xrec,
+                                                     int score_all, int* __restrict__ order, KfdbHit* __restrict__ hits, int* __restrict__ slist,
+                                                     int* __restrict__ head) {
+    ORBX_DYN_SMEM(smem);
+    __shared__ int s_red[16];
+    __shared__ int s_scan[20];
+    __shared__ int s_nscored;
+    int* hist = (int*)smem;
+    const int tid = (int)threadIdx.x, nt = (int)blockDim.x, nw = nt >> 6, wave = tid >> 6, lane = lane_id(), q = (int)blockIdx.x;
+    const int nq = qn[(size_t)q * qn_step];
+    int* c = cnt + (size_t)q * R;
+    const int* fp = firstpos + (size_t)q * R;
+    if (xstart) for (int i = xstart[q] + tid; i < xstart[q + 1]; i += nt) c[xrec[i]] = 0;
+    for (int i = tid; i < nw * nq; i += nt) hist[i] = 0;
+    if (tid == 0) s_nscored = 0;
+    __syncthreads();
+    const int seg = (R + nw - 1) / nw, r0 = imin(R, wave * seg), r1 = imin(R, r0 + seg);
+    int* row = hist + (size_t)wave * nq;
+    int mx = 0;
+    for (int r = r0 + lane; r < r1; r += 64) {
+        const int v = c[r];
+        if (v > 0) { atomicAdd(&row[fp[r]], 1); mx = v > mx ? v : mx; }
+    }
+    for (int d = 32; d >= 1; d >>= 1) { const int o2 = __shfl_xor(mx, d); mx = o2 > mx ? o2 : mx; }
+    if (lane == 0) s_red[wave] = mx;
+    __syncthreads();
+    mx = 0;
+    for (int w = 0; w < nw; w++) mx = s_red[w] > mx ? s_red[w] : mx;
+    int carry = 0;
+    for (int b0 = 0; b0 < nq; b0 += nt) {
+        const int b = b0 + tid;
+        int tot = 0;
+        if (b < nq) for (int w = 0; w < nw; w++) tot += hist[(size_t)w * nq + b];
+        int total;
+        const int ex = block_excl_scan<int>(tot, &total, s_scan);
+        if (b < nq) {
+            int run = carry + ex;
+            for (int w = 0; w < nw; w++) { const int t = hist[(size_t)w * nq + b]; hist[(size_t)w * nq + b] = run; run += t; }
+        }
+        carry += total;
+    }
+    __syncthreads();
+    const int minc = (int)((float)mx * 0.8f);          // "int minCommonWords = maxCommonWords * 0.8f"
+    if (tid == 0) { head[4 * q] = carry; head[4 * q + 1] = minc; }
+    int* o = order + (size_t)q * R;
+    KfdbHit* hq = hits + (size_t)q * R;
+    int* sl = slist + (size_t)q * R;
+    for (int base = r0; base < r1; base += 64) {
+        const int r = base + lane;
+        const int v = r < r1 ? c[r] : 0;
+        const int bin = v > 0 ? fp[r] : -1;
+        unsigned long long act = __ballot(v > 0 ? 1 : 0);
+        if (act == 0ull) continue;
+        int rank = 0;
+        bool last = true;
+        while (act) {
+            const int j = __ffsll((unsigned long long)act) - 1;
+            act &= act - 1ull;
+            const int bj = __shfl(bin, j);
+            if (bin >= 0 && bj == bin) { if (j < lane) rank++; else if (j > lane) last = false; }
+        }
+        int pos = 0;
+        if (bin >= 0) pos = row[bin] + rank;
+        ORBX_WAVE_SYNC();
+        if (bin >= 0 && last) row[bin] = pos + 1;
+        ORBX_WAVE_SYNC();
+        if (bin >= 0) {
+            o[pos] = r;
+            const int sc = (score_all || v > minc) ? 1 : 0;
+            KfdbHit h; h.key = rkey[r]; h.score = 0.0; h.words = v; h.scored = sc;
+            hq[pos] = h;
+            if (sc) sl[atomicAdd(&s_nscored, 1)] = pos;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) head[4 * q + 2] = s_nscored;
+}
+
+// grid (S, Q), 256 threads, dynamic LDS = 12 * (largest query) bytes.  scoring = DBoW2::ScoringType (KL is refused by the host).
+// Products and sums are written as __dmul_rn / __dadd_rn / __dsub_rn so that nothing is contracted into an FMA; the divisions and square
+// roots are the correctly rounded IEEE operations the host's are.
+__global__ void __launch_bounds__(256) k_kfdb_score(const unsigned* __restrict__ ids, const double* __restrict__ vals, const long long* __restrict__ rstart,
+                                                    const int* __restrict__ rn, KfdbQuerySet qs, const int* __restrict__ order, const int* __restrict__ slist,
+                                                    const int* __restrict__ head, KfdbHit* __restrict__ hits, int R, int scoring) {
+    ORBX_DYN_SMEM(smem);
+    const int tid = (int)threadIdx.x, lane = lane_id(), wave = tid >> 6, q = (int)blockIdx.y;
+    const int ns = head[4 * q + 2];
+    if ((int)blockIdx.x * 4 >= ns) return;                 // the whole workgroup leaves together
+    const int nq = qs.n[(size_t)q * qs.n_step];
+    const size_t qo = qs.start ? (size_t)qs.start[q] : (size_t)q * qs.stride;
+    double* qv = (double*)smem;
+    unsigned* qw = (unsigned*)(qv + nq);
+    for (int i = tid; i < nq; i += 256) { qw[i] = qs.ids[qo + i]; qv[i] = qs.vals[qo + i]; }
+    __syncthreads();
+    for (int k = (int)blockIdx.x * 4 + wave; k < ns; k += (int)gridDim.x * 4) {
+        const int pos = slist[(size_t)q * R + k], r = order[(size_t)q * R + pos];
+        const long long s = rstart[r];
+        const int n = rn[r];
+        double acc = 0.0;
+        for (int i0 = 0; i0 < n; i0 += 64) {
+            const int i = i0 + lane;
+            int hit = 0;
+            double t = 0.0;
+            if (i < n) {
+                const int p = kfdb_find(qw, nq, ids[s + i]);
+                if (p >= 0) {
+                    const double vi = qv[p], wi = vals[s + i];
+                    hit = 1;
+                    switch (scoring) {
+                        case 0: t = __dsub_rn(__dsub_rn(fabs(__dsub_rn(vi, wi)), fabs(vi)), fabs(wi)); break;     // L1: fabs(vi - wi) - fabs(vi) - fabs(wi)
+                        case 2: { const double sv = __dadd_rn(vi, wi);                                          // chi^2: vi * wi / (vi + wi), if vi + wi != 0
+                                  if (sv != 0.0) t = __dmul_rn(vi, wi) / sv; else hit = 0; } break;
+                        case 4: t = sqrt(__dmul_rn(vi, wi)); break;                                             // Bhattacharyya: sqrt(vi * wi)
+                        default: t = __dmul_rn(vi, wi); break;                                                  // L2, dot product: vi * wi
+                    }
+                }
+            }
+            unsigned long long m = __ballot(hit);
+            while (m) {                                    // the terms of this chunk in ascending word order, one after the other
+                const int j = __ffsll((unsigned long long)m) - 1;
+                m &= m - 1ull;
+                acc = __dadd_rn(acc, __shfl(t, j));
+            }
+        }
+        double score = acc;
+        if (scoring == 0) score = -acc / 2.0;                                         // "score = -score/2.0"
+        else if (scoring == 1) score = acc >= 1.0 ? 1.0 : __dsub_rn(1.0, sqrt(__dsub_rn(1.0, acc)));   // rounding errors; 1 - sqrt(1 - score)
+        else if (scoring == 2) score = __dmul_rn(2.0, acc);                           // "score = 2. * score"
+        if (lane == 0) hits[(size_t)q * R + pos].score = score;
     }
 }
 

@@ -1,9 +1,13 @@
 // orbv_api.cpp — host side of the vocabulary transform (include/orbx.h "Vocabulary"): flattens an ORBVocabulary
 // (DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>, include/ORBVocabulary.h:28-29) into slot arrays whose children are
 // contiguous, uploads them once, and runs k_voc_descend + k_voc_assemble (csrc/k_vocab.hip) per batch of descriptors.
+// Also the key frame database (include/orbx.h "Key frame database", orbv_db_*): the records live in host vectors in add order and are
+// mirrored to the device before a query (the appended tail, or everything after a compaction or growth); k_kfdb_count / _order / _score.
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
+#include <deque>
+#include <unordered_map>
 #include "orbx_internal.h"
 
 using namespace orbx;
@@ -216,6 +220,308 @@ int orbv_transform(orbv_vocabulary* v, orbx_extractor* h, const uint8_t* desc, i
     if (n > 0 && rt::copy_h2d(v->d_fdesc.p, desc, 32 * (size_t)n, h->s0)) return fail(ORBX_E_DEVICE, "upload failed");
     int rc = run(v, h, v->d_fdesc.p, nullptr, n, cap, 1, levelsup); if (rc) return rc;
     return orbv_fetch(v, h, 0, word_id, node_id, n, bow_id, bow_val, n_bow, fv_node, fv_start, fv_feat, n_fv);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// Key frame database
+struct orbv_database {
+    orbv_vocabulary* voc = nullptr;
+    int device = 0, scoring = 0, n_words = 0;
+    rt::stream_t s = 0;
+    // records in add order: the BowVector of record r is ids / vals [rstart[r], rstart[r] + rn[r])
+    std::vector<uint32_t> ids; std::vector<double> vals;
+    std::vector<long long> rstart; std::vector<int> rn; std::vector<unsigned long long> rkey; std::vector<uint8_t> rlive;
+    struct Key { std::deque<int> recs; int n = 0; uint64_t sum = 0; };   // surviving records of a key, in add order; its vector's size and checksum
+    std::unordered_map<unsigned long long, Key> keys;
+    long long live = 0, dead_words = 0;
+    // device mirror: the arena prefix [0, up_words) and the record tables are current unless dirty
+    DevBuf<uint32_t> d_ids; DevBuf<double> d_vals; DevBuf<long long> d_rstart; DevBuf<int> d_rn, d_mult; DevBuf<unsigned long long> d_rkey;
+    size_t up_words = 0; bool meta_dirty = true;
+    // per-query scratch and results
+    DevBuf<uint32_t> d_qid; DevBuf<double> d_qval; DevBuf<int> d_qstart, d_qn, d_xstart, d_xrec, d_cnt, d_first, d_order, d_slist, d_head;
+    DevBuf<KfdbHit> d_hits; HostBuf<KfdbHit> h_hits; HostBuf<int> h_head;
+};
+
+namespace {
+
+uint64_t bow_checksum(const uint32_t* id, const double* val, int n) {       // FNV-1a over the ids and the bit patterns of the values
+    uint64_t h = 1469598103934665603ull;
+    auto mix = [&](uint64_t x) { for (int k = 0; k < 8; k++) { h ^= (x >> (8 * k)) & 0xFFu; h *= 1099511628211ull; } };
+    for (int i = 0; i < n; i++) { uint64_t b; memcpy(&b, &val[i], 8); mix(id[i]); mix(b); }
+    return h;
+}
+
+int db_add_host(orbv_database* db, unsigned long long key, const uint32_t* id, const double* val, int n) {
+    for (int i = 0; i < n; i++) {
+        if ((int)id[i] >= db->n_words || id[i] >= (uint32_t)db->n_words) return fail(ORBX_E_ARG, "word id %u is not a word of the vocabulary (%d words)", id[i], db->n_words);
+        if (i > 0 && id[i] <= id[i - 1]) return fail(ORBX_E_ARG, "BowVector word ids must ascend (entry %d)", i);
+    }
+    const uint64_t sum = bow_checksum(id, val, n);
+    auto it = db->keys.find(key);
+    if (it != db->keys.end() && (it->second.n != n || it->second.sum != sum))
+        return fail(ORBX_E_ARG, "key %llu was added before with another BowVector (%d words then, %d now)", key, it->second.n, n);
+    orbv_database::Key& k = db->keys[key];
+    k.n = n; k.sum = sum; k.recs.push_back((int)db->rn.size());
+    db->rstart.push_back((long long)db->ids.size()); db->rn.push_back(n); db->rkey.push_back(key); db->rlive.push_back(1);
+    db->ids.insert(db->ids.end(), id, id + n); db->vals.insert(db->vals.end(), val, val + n);
+    db->live++; db->meta_dirty = true;
+    return ORBX_OK;
+}
+
+void db_kill(orbv_database* db, int r) { db->rlive[r] = 0; db->live--; db->dead_words += db->rn[r]; db->meta_dirty = true; }
+
+// drops the erased records, keeping the order of the others
+void db_compact(orbv_database* db) {
+    std::vector<int> remap(db->rn.size(), -1);
+    size_t w = 0; int nr = 0;
+    for (size_t r = 0; r < db->rn.size(); r++) {
+        if (!db->rlive[r]) continue;
+        const long long s = db->rstart[r]; const int n = db->rn[r];
+        if ((long long)w != s) { memmove(&db->ids[w], &db->ids[s], 4 * (size_t)n); memmove(&db->vals[w], &db->vals[s], 8 * (size_t)n); }
+        db->rstart[nr] = (long long)w; db->rn[nr] = n; db->rkey[nr] = db->rkey[r]; db->rlive[nr] = 1;
+        remap[r] = nr++; w += n;
+    }
+    db->ids.resize(w); db->vals.resize(w); db->rstart.resize(nr); db->rn.resize(nr); db->rkey.resize(nr); db->rlive.resize(nr);
+    for (auto& kv : db->keys) for (int& r : kv.second.recs) r = remap[r];
+    db->dead_words = 0; db->up_words = 0; db->meta_dirty = true;
+}
+
+// brings the device mirror up to date: compacts when the arena must grow (or erased words outnumber live ones), uploads the appended tail
+// or - after a compaction or growth - everything, and the record tables with the multiplicities (the earliest surviving record of a key
+// carries the number of its surviving adds, the others 0)
+int db_sync(orbv_database* db) {
+    if (!db->meta_dirty && db->up_words == db->ids.size()) return 0;
+    const size_t live_words = db->ids.size() - (size_t)db->dead_words;
+    if (db->dead_words > 0 && (db->ids.size() > db->d_ids.n || (size_t)db->dead_words > live_words)) db_compact(db);
+    const size_t nw = db->ids.size(), R = db->rn.size();
+    if (nw > db->d_ids.n) {
+        const size_t c = std::max<size_t>(nw + nw / 2, 4096);
+        if (db->d_ids.ensure(c) || db->d_vals.ensure(c)) return fail(ORBX_E_DEVICE, "key frame database: arena allocation failed");
+        db->up_words = 0;
+    }
+    if (R > db->d_rn.n) {
+        const size_t c = std::max<size_t>(R + R / 2, 256);
+        if (db->d_rstart.ensure(c) || db->d_rn.ensure(c) || db->d_mult.ensure(c) || db->d_rkey.ensure(c)) return fail(ORBX_E_DEVICE, "key frame database: allocation failed");
+    }
+    int e = 0;
+    if (nw > db->up_words) {
+        e |= rt::copy_h2d(db->d_ids.p + db->up_words, db->ids.data() + db->up_words, 4 * (nw - db->up_words), db->s);
+        e |= rt::copy_h2d(db->d_vals.p + db->up_words, db->vals.data() + db->up_words, 8 * (nw - db->up_words), db->s);
+    }
+    std::vector<int> mult(R, 0);
+    for (auto& kv : db->keys) if (!kv.second.recs.empty()) mult[kv.second.recs.front()] = (int)kv.second.recs.size();
+    if (R > 0) {
+        e |= rt::copy_h2d(db->d_rstart.p, db->rstart.data(), 8 * R, db->s) | rt::copy_h2d(db->d_rn.p, db->rn.data(), 4 * R, db->s) |
+             rt::copy_h2d(db->d_mult.p, mult.data(), 4 * R, db->s) | rt::copy_h2d(db->d_rkey.p, db->rkey.data(), 8 * R, db->s);
+    }
+    // the host vectors are the copies' sources: wait before they can change again
+    e |= rt::stream_sync(db->s);
+    if (e) return fail(ORBX_E_DEVICE, "key frame database upload failed: %s", rt::last_error());
+    db->up_words = nw; db->meta_dirty = false;
+    return 0;
+}
+
+// the three launches and the copy-back of Q queries whose vectors are described by qs (device pointers); nq_max bounds every query's size
+int db_run(orbv_database* db, int Q, KfdbQuerySet qs, int nq_max, const int* x_start, const uint64_t* x_keys, int score_all, int cap,
+           uint64_t* keys, int* words, uint8_t* scored, double* score, int* n_out, int* min_common) {
+    const int R = (int)db->rn.size();
+    // exclusions -> record indices of the keys' earliest surviving records (the only ones that carry a count)
+    std::vector<int> xs((size_t)Q + 1, 0), xr;
+    if (x_start) {
+        for (int q = 0; q < Q; q++) {
+            for (int i = x_start[q]; i < x_start[q + 1]; i++) {
+                auto it = db->keys.find(x_keys[i]);
+                if (it != db->keys.end() && !it->second.recs.empty()) xr.push_back(it->second.recs.front());
+            }
+            xs[q + 1] = (int)xr.size();
+        }
+    }
+    const size_t lds = rt::lds_limit(db->device);
+    if ((size_t)nq_max * 12 + 64 > lds) return fail(ORBX_E_CAPACITY, "a query of %d words needs %zu bytes of LDS, the device allows %zu", nq_max, (size_t)nq_max * 12 + 64, lds);
+    int nw = 16;                                               // k_kfdb_order: one row of bin counters per wave
+    while (nw > 1 && (size_t)nw * 4 * std::max(nq_max, 1) + 512 > lds) nw--;
+    const size_t QR = (size_t)Q * std::max(R, 1);
+    int e = db->d_cnt.ensure(QR) | db->d_first.ensure(QR) | db->d_order.ensure(QR) | db->d_slist.ensure(QR) | db->d_hits.ensure(QR) |
+            db->d_head.ensure(4 * (size_t)Q) | db->h_head.ensure(4 * (size_t)Q);
+    if (x_start) e |= db->d_xstart.ensure((size_t)Q + 1) | db->d_xrec.ensure(std::max<size_t>(xr.size(), 1));
+    if (e) return fail(ORBX_E_DEVICE, "key frame database: query scratch allocation failed");
+    if (x_start) {
+        e |= rt::copy_h2d(db->d_xstart.p, xs.data(), 4 * ((size_t)Q + 1), db->s);
+        if (!xr.empty()) e |= rt::copy_h2d(db->d_xrec.p, xr.data(), 4 * xr.size(), db->s);
+    }
+    if (R > 0) {
+        dim3 blk(256, 1, 1), g1((unsigned)((R + kKfdbRecsPerBlock - 1) / kKfdbRecsPerBlock), (unsigned)Q, 1);
+        ORBX_LAUNCH(k_kfdb_count, g1, blk, (size_t)nq_max * 4, db->s, (const unsigned*)db->d_ids.p, (const long long*)db->d_rstart.p, (const int*)db->d_rn.p,
+                    (const int*)db->d_mult.p, R, qs, db->d_cnt.p, db->d_first.p);
+    }
+    dim3 g2((unsigned)Q, 1, 1), blk2((unsigned)(64 * nw), 1, 1);
+    ORBX_LAUNCH(k_kfdb_order, g2, blk2, (size_t)nw * 4 * std::max(nq_max, 1), db->s, db->d_cnt.p, (const int*)db->d_first.p,
+                (const unsigned long long*)db->d_rkey.p, R, qs.n, qs.n_step, x_start ? (const int*)db->d_xstart.p : (const int*)nullptr,
+                (const int*)db->d_xrec.p, score_all, db->d_order.p, db->d_hits.p, db->d_slist.p, db->d_head.p);
+    if (R > 0) {
+        dim3 g3((unsigned)std::min(64, (R + 3) / 4), (unsigned)Q, 1), blk(256, 1, 1);
+        ORBX_LAUNCH(k_kfdb_score, g3, blk, (size_t)nq_max * 12, db->s, (const unsigned*)db->d_ids.p, (const double*)db->d_vals.p, (const long long*)db->d_rstart.p,
+                    (const int*)db->d_rn.p, qs, (const int*)db->d_order.p, (const int*)db->d_slist.p, (const int*)db->d_head.p, db->d_hits.p, R, db->scoring);
+    }
+    if (rt::check_launch()) return fail(ORBX_E_DEVICE, "key frame database kernels failed to launch: %s", rt::last_error());
+    e = rt::copy_d2h(db->h_head.p, db->d_head.p, 16 * (size_t)Q, db->s) | rt::stream_sync(db->s);
+    if (e) return fail(ORBX_E_DEVICE, "key frame database query failed: %s", rt::last_error());
+    int too_small = 0;
+    size_t total = 0;
+    for (int q = 0; q < Q; q++) {
+        const int n = db->h_head.p[4 * q];
+        if (n_out) n_out[q] = n;
+        if (min_common) min_common[q] = db->h_head.p[4 * q + 1];
+        if (n > cap) too_small = 1;
+        total += (size_t)n;
+    }
+    if (too_small) return fail(ORBX_E_CAPACITY, "a query shares words with more keys than cap = %d (n_out holds the sizes needed)", cap);
+    if (db->h_hits.ensure(std::max<size_t>(total, 1))) return fail(ORBX_E_DEVICE, "key frame database: staging allocation failed");
+    size_t o = 0;
+    for (int q = 0; q < Q; q++) {
+        const int n = db->h_head.p[4 * q];
+        if (n > 0) e |= rt::copy_d2h(db->h_hits.p + o, db->d_hits.p + (size_t)q * R, sizeof(KfdbHit) * (size_t)n, db->s);
+        o += (size_t)n;
+    }
+    e |= rt::stream_sync(db->s);
+    if (e) return fail(ORBX_E_DEVICE, "key frame database query failed: %s", rt::last_error());
+    o = 0;
+    for (int q = 0; q < Q; q++) {
+        const int n = db->h_head.p[4 * q];
+        for (int i = 0; i < n; i++) {
+            const KfdbHit& h = db->h_hits.p[o + i];
+            const size_t d = (size_t)q * cap + i;
+            if (keys) keys[d] = h.key;
+            if (words) words[d] = h.words;
+            if (scored) scored[d] = (uint8_t)h.scored;
+            if (score) score[d] = h.score;
+        }
+        o += (size_t)n;
+    }
+    return ORBX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbv_db_create(orbv_vocabulary* v, orbx_extractor* h, orbv_database** out) {
+    if (!v || !h || !out) return fail(ORBX_E_ARG, "null");
+    if (v->device != h->device) return fail(ORBX_E_ARG, "vocabulary and extractor live on different devices");
+    if (v->scoring == 3) return fail(ORBX_E_ARG, "KL scoring is not supported by the key frame database (its score needs the fp64 log of the host's libm)");
+    rt::set_device(v->device);
+    orbv_database* db = new orbv_database();
+    db->voc = v; db->device = v->device; db->scoring = v->scoring; db->n_words = v->n_words;
+    if (rt::stream_create(&db->s)) { delete db; return fail(ORBX_E_DEVICE, "stream creation failed: %s", rt::last_error()); }
+    *out = db;
+    return ORBX_OK;
+}
+
+void orbv_db_destroy(orbv_database* db) {
+    if (!db) return;
+    rt::set_device(db->device);
+    rt::stream_sync(db->s);
+    db->d_ids.release(); db->d_vals.release(); db->d_rstart.release(); db->d_rn.release(); db->d_mult.release(); db->d_rkey.release();
+    db->d_qid.release(); db->d_qval.release(); db->d_qstart.release(); db->d_qn.release(); db->d_xstart.release(); db->d_xrec.release();
+    db->d_cnt.release(); db->d_first.release(); db->d_order.release(); db->d_slist.release(); db->d_head.release(); db->d_hits.release();
+    db->h_hits.release(); db->h_head.release();
+    rt::stream_destroy(db->s);
+    delete db;
+}
+
+int orbv_db_add(orbv_database* db, uint64_t key, const uint32_t* bow_id, const double* bow_val, int n) {
+    if (!db || n < 0 || (n > 0 && (!bow_id || !bow_val))) return fail(ORBX_E_ARG, "null");
+    return db_add_host(db, key, bow_id, bow_val, n);
+}
+
+int orbv_db_add_extracted(orbv_database* db, uint64_t key, orbx_extractor* h, int b) {
+    if (!db || !h) return fail(ORBX_E_ARG, "null");
+    orbv_vocabulary* v = db->voc;
+    if (h->device != db->device) return fail(ORBX_E_ARG, "extractor and database live on different devices");
+    if (b < 0 || b >= v->lastB) return fail(ORBX_E_ARG, "image %d is not in the last transformed batch of %d", b, v->lastB);
+    if (v->run_handle && v->run_handle != (const void*)h) return fail(ORBX_E_ARG, "the last vocabulary transform ran on another extractor handle");
+    rt::set_device(db->device);
+    int n = 0;
+    if (rt::copy_d2h(&n, v->d_nout.p + 2 * b, sizeof n, h->s0) || rt::stream_sync(h->s0)) return fail(ORBX_E_DEVICE, "fetch failed: %s", rt::last_error());
+    std::vector<uint32_t> id(std::max(n, 1)); std::vector<double> val(std::max(n, 1));
+    const size_t off = (size_t)b * v->run_cap;
+    if (n > 0 && (rt::copy_d2h(id.data(), v->d_bow_id.p + off, 4 * (size_t)n, h->s0) || rt::copy_d2h(val.data(), v->d_bow_val.p + off, 8 * (size_t)n, h->s0) ||
+                  rt::stream_sync(h->s0)))
+        return fail(ORBX_E_DEVICE, "fetch failed: %s", rt::last_error());
+    return db_add_host(db, key, id.data(), val.data(), n);
+}
+
+int orbv_db_erase(orbv_database* db, uint64_t key) {
+    if (!db) return fail(ORBX_E_ARG, "null");
+    auto it = db->keys.find(key);
+    if (it == db->keys.end()) return ORBX_OK;
+    db_kill(db, it->second.recs.front());
+    it->second.recs.pop_front();
+    if (it->second.recs.empty()) db->keys.erase(it);
+    return ORBX_OK;
+}
+
+int orbv_db_erase_keys(orbv_database* db, const uint64_t* keys, int n) {
+    if (!db || n < 0 || (n > 0 && !keys)) return fail(ORBX_E_ARG, "null");
+    for (int i = 0; i < n; i++) {
+        auto it = db->keys.find(keys[i]);
+        if (it == db->keys.end()) continue;
+        for (int r : it->second.recs) db_kill(db, r);
+        db->keys.erase(it);
+    }
+    return ORBX_OK;
+}
+
+int orbv_db_clear(orbv_database* db) {
+    if (!db) return fail(ORBX_E_ARG, "null");
+    db->ids.clear(); db->vals.clear(); db->rstart.clear(); db->rn.clear(); db->rkey.clear(); db->rlive.clear(); db->keys.clear();
+    db->live = 0; db->dead_words = 0; db->up_words = 0; db->meta_dirty = true;
+    return ORBX_OK;
+}
+
+int orbv_db_size(const orbv_database* db) { return db ? (int)db->live : 0; }
+
+int orbv_db_query(orbv_database* db, int Q, const int* q_start, const uint32_t* q_ids, const double* q_vals, const int* x_start, const uint64_t* x_keys,
+                  int score_all, int cap, uint64_t* keys, int* words, uint8_t* scored, double* score, int* n_out, int* min_common) {
+    if (!db || Q <= 0 || !q_start || cap < 0 || (x_start && !x_keys && x_start[Q] > 0)) return fail(ORBX_E_ARG, "null");
+    const int total = q_start[Q];
+    if (q_start[0] != 0 || total < 0 || (total > 0 && (!q_ids || !q_vals))) return fail(ORBX_E_ARG, "q_start must run from 0 to the number of words");
+    std::vector<int> qn(Q);
+    int nq_max = 0;
+    for (int q = 0; q < Q; q++) {
+        qn[q] = q_start[q + 1] - q_start[q];
+        if (qn[q] < 0) return fail(ORBX_E_ARG, "q_start must not descend");
+        nq_max = std::max(nq_max, qn[q]);
+        for (int i = q_start[q] + 1; i < q_start[q + 1]; i++) if (q_ids[i] <= q_ids[i - 1]) return fail(ORBX_E_ARG, "query %d: word ids must ascend", q);
+    }
+    if (x_start) for (int q = 0; q < Q; q++) if (x_start[q + 1] < x_start[q] || x_start[0] != 0) return fail(ORBX_E_ARG, "x_start must run from 0 and not descend");
+    rt::set_device(db->device);
+    if (db_sync(db)) return ORBX_E_DEVICE;
+    int e = db->d_qid.ensure(std::max(total, 1)) | db->d_qval.ensure(std::max(total, 1)) | db->d_qstart.ensure((size_t)Q + 1) | db->d_qn.ensure(Q);
+    if (e) return fail(ORBX_E_DEVICE, "key frame database: query allocation failed");
+    if (total > 0) e |= rt::copy_h2d(db->d_qid.p, q_ids, 4 * (size_t)total, db->s) | rt::copy_h2d(db->d_qval.p, q_vals, 8 * (size_t)total, db->s);
+    e |= rt::copy_h2d(db->d_qstart.p, q_start, 4 * ((size_t)Q + 1), db->s) | rt::copy_h2d(db->d_qn.p, qn.data(), 4 * (size_t)Q, db->s);
+    if (e) return fail(ORBX_E_DEVICE, "key frame database: query upload failed: %s", rt::last_error());
+    KfdbQuerySet qs = {db->d_qid.p, db->d_qval.p, db->d_qstart.p, 0, db->d_qn.p, 1};
+    return db_run(db, Q, qs, nq_max, x_start, x_keys, score_all, cap, keys, words, scored, score, n_out, min_common);
+}
+
+int orbv_db_query_extracted(orbv_database* db, orbx_extractor* h, int first, int Q, const int* x_start, const uint64_t* x_keys, int score_all, int cap,
+                            uint64_t* keys, int* words, uint8_t* scored, double* score, int* n_out, int* min_common) {
+    if (!db || !h || Q <= 0 || cap < 0 || (x_start && !x_keys && x_start[Q] > 0)) return fail(ORBX_E_ARG, "null");
+    orbv_vocabulary* v = db->voc;
+    if (h->device != db->device) return fail(ORBX_E_ARG, "extractor and database live on different devices");
+    if (first < 0 || first + Q > v->lastB) return fail(ORBX_E_ARG, "images [%d, %d) are not in the last transformed batch of %d", first, first + Q, v->lastB);
+    if (v->run_handle && v->run_handle != (const void*)h) return fail(ORBX_E_ARG, "the last vocabulary transform ran on another extractor handle");
+    if (x_start) for (int q = 0; q < Q; q++) if (x_start[q + 1] < x_start[q] || x_start[0] != 0) return fail(ORBX_E_ARG, "x_start must run from 0 and not descend");
+    rt::set_device(db->device);
+    if (db_sync(db)) return ORBX_E_DEVICE;
+    if (rt::stream_sync(h->s0)) return fail(ORBX_E_DEVICE, "vocabulary transform failed: %s", rt::last_error());   // the BowVectors are written on h's stream
+    const int cap_v = v->run_cap;
+    KfdbQuerySet qs = {v->d_bow_id.p + (size_t)first * cap_v, v->d_bow_val.p + (size_t)first * cap_v, nullptr, cap_v, v->d_nout.p + 2 * first, 2};
+    return db_run(db, Q, qs, cap_v, x_start, x_keys, score_all, cap, keys, words, scored, score, n_out, min_common);
 }
 
 }  // extern "C"

@@ -182,6 +182,14 @@ __global__ void k_voc_assemble(const unsigned* __restrict__ word, const unsigned
                                unsigned* __restrict__ bow_id, double* __restrict__ bow_val, int* __restrict__ bow_start,
                                unsigned* __restrict__ fv_node, int* __restrict__ fv_start, unsigned* __restrict__ fv_feat,
                                int* __restrict__ n_out);
+__global__ void k_kfdb_count(const unsigned* __restrict__ ids, const long long* __restrict__ rstart, const int* __restrict__ rn,
+                             const int* __restrict__ rmult, int R, KfdbQuerySet qs, int* __restrict__ cnt, int* __restrict__ firstpos);
+__global__ void k_kfdb_order(int* __restrict__ cnt, const int* __restrict__ firstpos, const unsigned long long* __restrict__ rkey, int R,
+                             const int* __restrict__ qn, int qn_step, const int* __restrict__ xstart, const int* __restrict__ xrec, int score_all,
+                             int* __restrict__ order, KfdbHit* __restrict__ hits, int* __restrict__ slist, int* __restrict__ head);
+__global__ void k_kfdb_score(const unsigned* __restrict__ ids, const double* __restrict__ vals, const long long* __restrict__ rstart,
+                             const int* __restrict__ rn, KfdbQuerySet qs, const int* __restrict__ order, const int* __restrict__ slist,
+                             const int* __restrict__ head, KfdbHit* __restrict__ hits, int R, int scoring);
 
 __global__ void k_input_remap(const uint8_t* __restrict__ src, int sw, int sh, int sstride, size_t simg, int C, const float* __restrict__ mapx,
                               const float* __restrict__ mapy, int out_w, int out_h, uint8_t* __restrict__ dst, int dst_pitch, size_t dst_stride);

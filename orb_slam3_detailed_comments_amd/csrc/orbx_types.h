@@ -93,6 +93,12 @@ struct ProjectParams {
     float bf;
 };
 struct VocSlot { int node_id, child_start, child_cnt, word_id; };   // one vocabulary node; children occupy consecutive slots
+// Key frame database (orbv_db_*): where the BowVectors of queries sit - query q's sorted word ids / values at ids + start[q] (start == nullptr:
+// q * stride), its word count at n[q * n_step] (a host CSR, or the results of the vocabulary transform left on the device)
+struct KfdbQuerySet { const uint32_t* ids; const double* vals; const int* start; int stride; const int* n; int n_step; };
+// one sharing key of one query, in first-appearance order: its word count, whether it is scored, its score (TemplatedVocabulary::score)
+constexpr int kKfdbRecsPerBlock = 32;       // k_kfdb_count: records per workgroup (4 waves, 8 records each): the query's ids are loaded once per 32
+struct KfdbHit { unsigned long long key; double score; int words, scored; };
 struct BowItem { int idx1, start2, cnt2, out_off; };
 struct BowParams {
     float F12[9];            // fundamental matrix, row-major (Pinhole::epipolarConstrain)

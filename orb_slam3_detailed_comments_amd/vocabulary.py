@@ -83,3 +83,88 @@ class ORBVocabulary:
         self._lib.check(self._lib.L.orbv_fetch(self._v, ext._h, int(b), a[5].ctypes.data, a[6].ctypes.data, int(n_features), a[0].ctypes.data,
                                                a[1].ctypes.data, C.byref(nb), a[2].ctypes.data, a[3].ctypes.data, a[4].ctypes.data, C.byref(nf)))
         return self._pack(a, n_features, nb.value, nf.value)
+
+
+class KeyFrameDatabase:
+    """KeyFrameDatabase (src/KeyFrameDatabase.cc) on the device: add / erase / clear / clearMap over caller keys, and batched queries that return,
+    per query, the keys sharing words with it in the order the reference's inverted-file walk first meets them, their shared word counts,
+    minCommonWords, which keys are scored and their scores (TemplatedVocabulary::score, bit-exact).  The per-KeyFrame bookkeeping of
+    Detect*Candidates is the caller's (include/orb_slam3_amd/KeyFrameDatabase.h)."""
+
+    def __init__(self, voc, ext):
+        self._lib, self._voc = voc._lib, voc
+        h = C.c_void_p()
+        self._lib.check(self._lib.L.orbv_db_create(voc._v, ext._h, C.byref(h)))
+        self._db = h
+
+    def close(self):
+        if self._db:
+            self._lib.L.orbv_db_destroy(self._db)
+            self._db = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def add(self, key, bow_id, bow_val):
+        i = np.ascontiguousarray(bow_id, np.uint32); v = np.ascontiguousarray(bow_val, np.float64)
+        self._lib.check(self._lib.L.orbv_db_add(self._db, int(key), i.ctypes.data, v.ctypes.data, len(i)))
+
+    def add_extracted(self, key, ext, b):
+        self._lib.check(self._lib.L.orbv_db_add_extracted(self._db, int(key), ext._h, int(b)))
+
+    def erase(self, key):
+        self._lib.check(self._lib.L.orbv_db_erase(self._db, int(key)))
+
+    def erase_keys(self, keys):
+        k = np.ascontiguousarray(keys, np.uint64)
+        self._lib.check(self._lib.L.orbv_db_erase_keys(self._db, k.ctypes.data, len(k)))
+
+    def clear(self):
+        self._lib.check(self._lib.L.orbv_db_clear(self._db))
+
+    def size(self):
+        return self._lib.L.orbv_db_size(self._db)
+
+    @staticmethod
+    def _exclusions(Q, exclude):
+        if exclude is None:
+            return None, None
+        xs = np.zeros(Q + 1, np.int32)
+        for q in range(Q):
+            xs[q + 1] = xs[q] + len(exclude[q])
+        xk = np.ascontiguousarray(np.concatenate([np.asarray(e, np.uint64) for e in exclude]) if xs[-1] else np.zeros(1, np.uint64), np.uint64)
+        return xs, xk
+
+    def _run(self, call, Q, cap, exclude, score_all):
+        cap = max(self.size(), 1) if cap is None else int(cap)
+        xs, xk = self._exclusions(Q, exclude)
+        keys = np.zeros((Q, max(cap, 1)), np.uint64); words = np.zeros((Q, max(cap, 1)), np.int32)
+        scored = np.zeros((Q, max(cap, 1)), np.uint8); score = np.zeros((Q, max(cap, 1)), np.float64)
+        n_out = np.zeros(Q, np.int32); minc = np.zeros(Q, np.int32)
+        rc = call(None if xs is None else xs.ctypes.data, None if xk is None else xk.ctypes.data, int(bool(score_all)), cap, keys.ctypes.data,
+                  words.ctypes.data, scored.ctypes.data, score.ctypes.data, n_out.ctypes.data, minc.ctypes.data)
+        if rc != 0:
+            err = self._lib.L.orbx_last_error().decode()
+            from ._lib import OrbxError
+            e = OrbxError(rc, err)
+            e.n_out = n_out
+            raise e
+        return [dict(keys=keys[q, :n_out[q]].copy(), words=words[q, :n_out[q]].copy(), scored=scored[q, :n_out[q]].astype(bool),
+                     score=score[q, :n_out[q]].copy(), min_common=int(minc[q])) for q in range(Q)]
+
+    def query(self, bows, exclude=None, cap=None, score_all=False):
+        """bows: list of (ids, values) BowVectors; exclude: per query an iterable of keys it ignores.  One dict per query."""
+        Q = len(bows)
+        start = np.zeros(Q + 1, np.int32)
+        for q, (i, _) in enumerate(bows):
+            start[q + 1] = start[q] + len(i)
+        ids = np.ascontiguousarray(np.concatenate([np.asarray(b[0], np.uint32) for b in bows]) if start[-1] else np.zeros(1, np.uint32), np.uint32)
+        vals = np.ascontiguousarray(np.concatenate([np.asarray(b[1], np.float64) for b in bows]) if start[-1] else np.zeros(1, np.float64), np.float64)
+        return self._run(lambda *a: self._lib.L.orbv_db_query(self._db, Q, start.ctypes.data, ids.ctypes.data, vals.ctypes.data, *a), Q, cap, exclude, score_all)
+
+    def query_extracted(self, ext, first, Q, exclude=None, cap=None, score_all=False):
+        """The same for images [first, first + Q) of the last vocabulary transform, read where it left them on the device."""
+        return self._run(lambda *a: self._lib.L.orbv_db_query_extracted(self._db, ext._h, int(first), int(Q), *a), Q, cap, exclude, score_all)
