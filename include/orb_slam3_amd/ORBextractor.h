@@ -4,9 +4,12 @@
  * link liborbx_hip.so; Frame.cc / Tracking.cc compile unchanged.
  *
  * Differences a caller can observe:
- *  - mvImagePyramid is refreshed after every call by copying the levels back from the GPU (each level is, like in the
- *    reference, a view into a buffer with a 19-px BORDER_REFLECT_101 frame).  SetExportPyramid(false) skips that copy when
- *    the stereo association also runs on the GPU (orbm_stereo_match reads the device-resident pyramid).
+ *  - mvImagePyramid is refreshed after every call: the library frames every level on the device (19-px BORDER_REFLECT_101, the
+ *    reference's layout) and copies the frames into page-locked memory of the handle while the rest of the extraction runs
+ *    (orbx_set_pyramid_export).  Each level is, like in the reference, a view into a framed buffer - but that buffer belongs to the
+ *    handle: the Mats stay valid for the next call as well (a ring of two slots), not for ever.  The reference's only reader is
+ *    Frame.cc, inside the constructor that made them.  Keep a level longer with clone().  SetExportPyramid(false) switches the device
+ *    export off when the stereo association also runs on the GPU (orbm_stereo_match reads the device-resident pyramid).
  *  - failures of the device (no GPU, out of memory) throw std::runtime_error; the reference cannot fail that way.
  */
 #ifndef ORB_SLAM3_AMD_ORBEXTRACTOR_H
@@ -45,6 +48,11 @@ public:
         orbx_get_level_tables(mpHandle, mvScaleFactor.data(), mvInvScaleFactor.data(), mvLevelSigma2.data(), mvInvLevelSigma2.data(),
                               mnFeaturesPerLevel.data(), umax);
         mvImagePyramid.resize(nlevels);
+        if (orbx_set_pyramid_export(mpHandle, EDGE, RING) != ORBX_OK) {
+            const std::string err = orbx_last_error();
+            orbx_destroy(mpHandle);
+            throw std::runtime_error("ORBextractor (HIP): " + err);
+        }
     }
     ~ORBextractor() { orbx_destroy(mpHandle); }
     ORBextractor(const ORBextractor&) = delete;
@@ -97,29 +105,27 @@ public:
     std::vector<cv::Mat> mvImagePyramid;
 
     // ---- additions ----
-    void SetExportPyramid(bool b) { mbExportPyramid = b; }
+    void SetExportPyramid(bool b)
+    {
+        if (orbx_set_pyramid_export(mpHandle, b ? EDGE : 0, RING) != ORBX_OK)
+            throw std::runtime_error(std::string("ORBextractor (HIP): ") + orbx_last_error());
+        mbExportPyramid = b;
+    }
     void SetGaussianTaps(int variant) { orbx_set_gaussian_taps(mpHandle, variant); }   // 0: OpenCV >= 3.4/4.x, 1: OpenCV 3.2
     orbx_extractor* Handle() { return mpHandle; }    // for the orbm_* matchers (device-resident pyramid / descriptors)
 
 protected:
+    enum { EDGE = 19, RING = 2 };     // EDGE_THRESHOLD (src/ORBextractor.cc:78); export slots: this call's and the previous call's levels
+    // mvImagePyramid[l]: the level inside its frame in the handle's export slot (src/ORBextractor.cc:1696-1700) - no copy, no border work here
     void ExportPyramid()
     {
-        const int EDGE_THRESHOLD = 19;
-        std::vector<uint8_t*> dst(mnLevels); std::vector<int> stride(mnLevels);
-        std::vector<cv::Mat> framed(mnLevels);
-        for (int level = 0; level < mnLevels; ++level) {
-            int w = 0, h = 0;
-            orbx_pyramid_level(mpHandle, 0, level, 0, nullptr, 0, &w, &h);           // sizes only (no copy)
-            framed[level] = cv::Mat(cv::Size(w + EDGE_THRESHOLD*2, h + EDGE_THRESHOLD*2), CV_8UC1);
-            mvImagePyramid[level] = framed[level](cv::Rect(EDGE_THRESHOLD, EDGE_THRESHOLD, w, h));
-            dst[level] = mvImagePyramid[level].data; stride[level] = (int)mvImagePyramid[level].step;
-        }
-        // one device-to-host copy for the whole pyramid, then the reference's borders (src/ORBextractor.cc:1712-1736)
-        if (orbx_pyramid_fetch(mpHandle, 0, 0, dst.data(), stride.data()) != ORBX_OK)
+        const uint8_t* base = nullptr;
+        std::vector<size_t> off(mnLevels); std::vector<int> step(mnLevels), w(mnLevels), h(mnLevels);
+        if (orbx_pyramid_exported(mpHandle, 0, &base, off.data(), step.data(), w.data(), h.data()) != ORBX_OK)
             throw std::runtime_error(std::string("ORBextractor (HIP): ") + orbx_last_error());
         for (int level = 0; level < mnLevels; ++level)
-            cv::copyMakeBorder(mvImagePyramid[level], framed[level], EDGE_THRESHOLD, EDGE_THRESHOLD, EDGE_THRESHOLD, EDGE_THRESHOLD,
-                               cv::BORDER_REFLECT_101+cv::BORDER_ISOLATED);
+            mvImagePyramid[level] = cv::Mat(h[level] + 2 * EDGE, w[level] + 2 * EDGE, CV_8UC1, (void*)(base + off[level]), (size_t)step[level])
+                                        (cv::Rect(EDGE, EDGE, w[level], h[level]));
     }
 
     orbx_extractor* mpHandle;

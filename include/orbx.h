@@ -104,6 +104,16 @@ int orbx_pyramid_level(orbx_extractor* h, int image_index, int level, int blurre
                        int dst_stride, int* width, int* height);
 /* all levels of one image with a single device-to-host copy: dst[l] receives level l (width x height of orbx_pyramid_level) with row pitch dst_stride[l] */
 int orbx_pyramid_fetch(orbx_extractor* h, int image_index, int blurred, uint8_t* const* dst, const int* dst_stride);
+/* Bordered pyramid export (ORB-SLAM3's mvImagePyramid, src/ORBextractor.cc:1687-1738).  edge > 0: every later extraction also writes each
+   level of each image as a (w + 2*edge) x (h + 2*edge) frame, level at (edge, edge), BORDER_REFLECT_101 around it, into page-locked memory
+   of the handle, overlapped with the rest of the extraction.  What extraction k exported stays valid until extraction k + depth is enqueued
+   (or the geometry changes, or a larger batch than any before grows the slots).  edge = 0 turns the export off and frees the slots.
+   edge <= 256, depth 1..8; the border repeats its reflection where edge exceeds a level's size.  orbx_fetch does not wait for the export,
+   orbx_sync does.  Under orbx_set_graph_replay the export runs behind the replayed graph instead of beside it. */
+int orbx_set_pyramid_export(orbx_extractor* h, int edge, int depth);
+/* Waits for image b of the last extraction; level l's frame starts at base + offset[l], pitch step[l], level size width[l] x height[l]
+   (arrays of orbx_get_levels(h) entries; every output may be NULL).  Refused when the last extraction exported nothing. */
+int orbx_pyramid_exported(orbx_extractor* h, int b, const uint8_t** base, size_t* offset, int* step, int* width, int* height);
 
 /* device memory helpers so a caller can keep inputs resident (bench, multi-camera rigs) */
 int orbx_device_alloc(orbx_extractor* h, size_t bytes, void** dptr);

@@ -24,7 +24,7 @@ ORBX_OK, ORBX_E_EMPTY, ORBX_E_ARG, ORBX_E_DEVICE, ORBX_E_CAPACITY, ORBX_E_INTERN
 SYMBOLS = [
     "orbx_device_count", "orbx_create", "orbx_destroy", "orbx_set_gaussian_taps", "orbx_reserve",
     "orbx_get_levels", "orbx_get_scale_factor", "orbx_get_level_tables", "orbx_max_keypoints",
-    "orbx_extract", "orbx_extract_batch", "orbx_set_input", "orbx_fetch", "orbx_sync", "orbx_pyramid_level", "orbx_pyramid_fetch",
+    "orbx_extract", "orbx_extract_batch", "orbx_set_input", "orbx_fetch", "orbx_sync", "orbx_pyramid_level", "orbx_pyramid_fetch", "orbx_set_pyramid_export", "orbx_pyramid_exported",
     "orbx_device_alloc", "orbx_device_free", "orbx_device_upload", "orbx_device_upload_async", "orbx_set_undistort", "orbx_fetch_undistorted", "orbx_undistorted_bounds", "orbx_input_buffer", "orbx_input_upload", "orbx_device_outputs", "orbx_device_snapshot", "orbx_device_id", "orbx_host_alloc", "orbx_host_free", "orbx_set_graph_replay", "orbx_set_pyramid_mode", "orbx_set_small_batch_forms", "orbx_profile_enable",
     "orbx_profile_get", "orbx_stage_name", "orbx_debug_candidates", "orbx_debug_level_keys", "orbx_debug_quadtree_profile", "orbx_set_host_wait", "orbx_debug_quadtree_lds_nodes", "orbx_debug_quadtree_pool_levels", "orbx_debug_simd_selftest", "orbx_debug_stereo_flags", "orbx_debug_live_resources",
     "orbm_hamming_matrix", "orbm_stereo_match", "orbm_stereo_fetch", "orbm_knn2", "orbm_knn2_fetch", "orbm_stereo_fisheye", "orbm_stereo_fisheye_fetch", "orbm_search_for_triangulation_kb8", "orbm_is_in_frustum", "orbm_is_in_frustum_rig", "orbm_search_local_points_fisheye", "orbm_search_local_points",
@@ -73,6 +73,8 @@ class OrbxLib:
         L.orbx_sync.argtypes = [vp]
         L.orbx_pyramid_level.argtypes = [vp, i, i, i, vp, i, ip, ip]
         L.orbx_pyramid_fetch.argtypes = [vp, i, i, vp, vp]
+        L.orbx_set_pyramid_export.argtypes = [vp, i, i]
+        L.orbx_pyramid_exported.argtypes = [vp, i, C.POINTER(vp), vp, vp, vp, vp]
         L.orbx_device_alloc.argtypes = [vp, sz, C.POINTER(vp)]
         L.orbx_device_free.argtypes = [vp, vp]
         L.orbx_device_upload.argtypes = [vp, vp, vp, sz]

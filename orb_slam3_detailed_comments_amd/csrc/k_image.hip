@@ -2,6 +2,7 @@
 //   k_resize      pyramid level l from level l-1   (reference ComputePyramid, src/ORBextractor.cc:1687-1738,
 //                                                    arithmetic of cv::resize INTER_LINEAR 8U)
 //   k_blur        7x7 sigma=2 Gaussian, REFLECT_101, 8-bit fixed point        (:1629-1637, cv::GaussianBlur)
+//   k_frame_pyramid  every level in the reference's framed layout, copyMakeBorder REFLECT_101 (:1712-1736; orbx_set_pyramid_export)
 // All are HBM/LDS-bound integer kernels: no MFMA.  One launch covers every image of the batch.
 #include "orbx_types.h"
 #include "orbx_block.h"
@@ -380,6 +381,57 @@ __global__ void __launch_bounds__(256) k_simd_selftest(const uint32_t* __restric
     out[19 * (size_t)n + i] = wave_or_u32((y & 7u) == 0u ? 1u << (x & 31u) : 0u);
     out[20 * (size_t)n + i] = mulhi_u24(x, y);
     out[21 * (size_t)n + i] = add3_u32(x, y, z);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Bordered pyramid export: level l of image b -> out + b * out_stride + fl.off[l], a (w + 2e) x (h + 2e) frame with the level at (e, e) and
+// cv::borderInterpolate(BORDER_REFLECT_101) around it, rows and columns independently (copyMakeBorder(..., BORDER_REFLECT_101 + BORDER_ISOLATED)).
+// grid (fl.band[nlevels], B): one workgroup per band of kFrameRows framed rows of one level, every level and image in one launch.  A lane writes
+// one 16-byte chunk of a framed row per trip; chunks that lie inside the level take their bytes from 5 aligned dwords of the source row (the
+// pyramid was written just before: L2), border chunks gather byte by byte through the reflected column.
+__device__ __forceinline__ int reflect101(int p, int len) {
+    if (len == 1) return 0;
+    while ((unsigned)p >= (unsigned)len) p = p < 0 ? -p : 2 * len - 2 - p;      // repeats while the border is wider than the level
+    return p;
+}
+__global__ void __launch_bounds__(256) k_frame_pyramid(const LevelInfo* __restrict__ lv, int nlevels, const uint8_t* __restrict__ pyr, size_t pyr_stride,
+                                                       uint8_t* __restrict__ out, size_t out_stride, FrameLayout fl) {
+    const int g = (int)blockIdx.x, b = (int)blockIdx.y, tid = (int)threadIdx.x;
+    int l = 0;
+    while (l + 1 < nlevels && g >= fl.band[l + 1]) l++;
+    const LevelInfo L = lv[l];
+    const int e = fl.edge, step = fl.step[l], fh = L.h + 2 * e;
+    const int y0 = (g - fl.band[l]) * kFrameRows, rows = imin(kFrameRows, fh - y0);
+    const int chunks = step >> 4;                        // step = (w + 2e) rounded up to 16: the last chunk's tail is padding (written, never read)
+    const uint8_t* src = pyr + (size_t)b * pyr_stride + L.off;
+    uint8_t* dst = out + (size_t)b * out_stride + fl.off[l];
+    for (int i = tid; i < rows * chunks; i += 256) {
+        const int r = i / chunks, c = i - r * chunks;
+        const int fy = y0 + r, sx0 = c * 16 - e;
+        const uint8_t* row = src + (size_t)reflect101(fy - e, L.h) * L.pitch;
+        uint32_t v[4];
+        if (sx0 >= 0 && sx0 + 16 <= L.w) {
+            // interior: dwords a .. a + 4 (a + 4 ends at most 3 bytes past the level's last pixel: inside the row pitch or the 256 bytes behind
+            // the last image's pyramid block)
+            const uint32_t* p = (const uint32_t*)(row + (sx0 & ~3));
+            const uint32_t sh = (uint32_t)(sx0 & 3);
+            uint32_t d[5];
+#pragma unroll
+            for (int k = 0; k < 5; k++) d[k] = p[k];
+#pragma unroll
+            for (int k = 0; k < 4; k++) v[k] = align_byte(d[k + 1], d[k], sh);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                uint32_t w = 0;
+#pragma unroll
+                for (int j = 0; j < 4; j++) w |= (uint32_t)row[reflect101(sx0 + 4 * k + j, L.w)] << (8 * j);
+                v[k] = w;
+            }
+        }
+        int4 o; o.x = (int)v[0]; o.y = (int)v[1]; o.z = (int)v[2]; o.w = (int)v[3];
+        *(int4*)(dst + (size_t)fy * step + c * 16) = o;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -153,12 +153,72 @@ QuadtreePlan quadtree_plan(const orbx_extractor* h, int counter_bytes) {
     return p;
 }
 
+// ---- bordered pyramid export (orbx_set_pyramid_export) ---------------------------------------------------
+// frames of one image: level after level at 64-byte offsets, rows rounded up to 16 bytes (k_frame_pyramid stores 16 bytes per lane)
+void export_layout(orbx_extractor* h) {
+    FrameLayout& fl = h->exp_fl;
+    memset(&fl, 0, sizeof fl);
+    fl.edge = h->exp_edge;
+    size_t off = 0; int bands = 0;
+    for (int l = 0; l < h->nlevels; l++) {
+        const int fw = h->lv[l].w + 2 * fl.edge, fh = h->lv[l].h + 2 * fl.edge;
+        fl.step[l] = (int)align_up((size_t)fw, 16);
+        fl.off[l] = (int)off; off = align_up(off + (size_t)fl.step[l] * fh, 64);
+        fl.band[l] = bands; bands += (fh + kFrameRows - 1) / kFrameRows;
+    }
+    for (int l = h->nlevels; l <= kMaxLevels; l++) fl.band[l] = bands;
+    h->exp_stride = align_up(off, 256);
+}
+// waits for every export in flight (their copies land in the slots, their kernels read the pyramid)
+int export_drain(orbx_extractor* h) { return h->have_exp_stream ? rt::stream_sync(h->s_exp) : 0; }
+// device staging + the ring slots for a batch of maxB images of the configured geometry: called when the export is switched on and when
+// configure() changes the geometry or grows the batch - never per extraction.  Slots that move or whose layout changes are no longer valid.
+int export_prepare(orbx_extractor* h) {
+    if (h->exp_edge <= 0 || h->W <= 0 || h->maxB <= 0) return ORBX_OK;
+    if (export_drain(h)) return fail(ORBX_E_DEVICE, "export stream sync failed: %s", rt::last_error());
+    export_layout(h);
+    const size_t bytes = (size_t)h->maxB * h->exp_stride;
+    if (bytes != h->exp_cap) h->exp_slot = -1;
+    int e = h->d_exp.ensure(bytes);
+    for (int k = 0; k < h->exp_depth; k++) e |= h->h_exp[k].ensure(bytes);
+    if (e) return fail(ORBX_E_DEVICE, "allocation of the pyramid export (%d slots of %zu bytes) failed", h->exp_depth, bytes);
+    h->exp_cap = bytes;
+    return ORBX_OK;
+}
+// everything of the export: the handle is then as if it had never been switched on
+void export_release(orbx_extractor* h) {
+    export_drain(h);
+    h->d_exp.release();
+    for (auto& x : h->h_exp) x.release();
+    for (auto& ev : h->ev_exp_slot) { rt::event_destroy(ev); ev = 0; }
+    rt::event_destroy(h->ev_exp_fork); rt::event_destroy(h->ev_exp_read); h->ev_exp_fork = h->ev_exp_read = 0;
+    if (h->have_exp_stream) rt::stream_destroy(h->s_exp);
+    h->s_exp = 0; h->have_exp_stream = false;
+    h->exp_edge = h->exp_depth = 0; h->exp_slot = -1; h->exp_B = 0; h->exp_cap = 0; h->exp_count = 0; h->exp_pending = h->exp_guard = false;
+}
+// the export of the batch just enqueued on s0 (its pyramid is complete there): k_frame_pyramid on s_exp, then one copy into the next ring slot
+int export_enqueue(orbx_extractor* h, int B) {
+    if (h->d_exp.n < (size_t)B * h->exp_stride) return fail(ORBX_E_INTERNAL, "pyramid export staging not allocated");
+    const int slot = (int)(h->exp_count % (uint64_t)h->exp_depth);
+    int e = rt::event_record(h->ev_exp_fork, h->s0) | rt::stream_wait_event(h->s_exp, h->ev_exp_fork);
+    ORBX_LAUNCH(k_frame_pyramid, dim3(h->exp_fl.band[h->nlevels], B, 1), dim3(256, 1, 1), 0, h->s_exp, (const LevelInfo*)h->d_lv.p, h->nlevels,
+                (const uint8_t*)h->d_pyr.p, h->pyr_stride, h->d_exp.p, h->exp_stride, h->exp_fl);
+    e |= rt::event_record(h->ev_exp_read, h->s_exp);
+    e |= rt::copy_d2h(h->h_exp[slot].p, h->d_exp.p, (size_t)B * h->exp_stride, h->s_exp);
+    e |= rt::event_record(h->ev_exp_slot[slot], h->s_exp);
+    if (e || rt::check_launch()) return fail(ORBX_E_DEVICE, "pyramid export failed: %s", rt::last_error());
+    h->exp_slot = slot; h->exp_B = B; h->exp_count++; h->exp_pending = h->exp_guard = true;
+    return ORBX_OK;
+}
+
 int configure(orbx_extractor* h, int W, int H, int B) {
     if (W <= 0 || H <= 0 || B <= 0) return fail(ORBX_E_ARG, "bad size %dx%d batch %d", W, H, B);
     const bool same_geom = (W == h->W && H == h->H);
     if (same_geom && B <= h->maxB && h->cfg_qt_lds_nodes == h->qt_lds_nodes) return ORBX_OK;
     if (rt::set_device(h->device)) return fail(ORBX_E_DEVICE, "hipSetDevice(%d) failed", h->device);
+    if (export_drain(h)) return fail(ORBX_E_DEVICE, "export stream sync failed: %s", rt::last_error());    // its kernel reads the buffers that may move
     if (!same_geom) {
+        h->exp_slot = -1;
         if (W - 2 * kBorder > 4095 || H - 2 * kBorder > 4095) return fail(ORBX_E_ARG, "image larger than 4127 px is not supported");
         // the tables below are rebuilt in place; until they are complete (and uploaded) the handle has no geometry, so a rejected size
         // cannot leave host tables of one resolution beside device tables of another
@@ -306,7 +366,7 @@ int configure(orbx_extractor* h, int W, int H, int B) {
         rt::memset_async(h->d_pyr.p, 0, b * h->pyr_stride + 256, h->s0);     // defined row padding for frames written in place (orbx_input_buffer)
         h->maxB = B;
     }
-    return ORBX_OK;
+    return export_prepare(h);
 }
 
 void stage_begin(orbx_extractor* h, int st, rt::stream_t s) { if (h->profile) rt::event_record(h->ev_stage[st][0], s); }
@@ -341,7 +401,8 @@ void enqueue_input(orbx_extractor* h, int B, const uint8_t* d_images, int sw, in
                 lvl0, L0.pitch, h->pyr_stride);
 }
 
-int enqueue_extract(orbx_extractor* h, int B, const uint8_t* d_images, int src_w, int src_h, int stride, size_t image_stride, int lap0, int lap1) {
+// with_export: the bordered pyramid export forks from s0 behind the pyramid (eager path; a captured graph leaves it out, orbx_extract_batch)
+int enqueue_extract(orbx_extractor* h, int B, const uint8_t* d_images, int src_w, int src_h, int stride, size_t image_stride, int lap0, int lap1, bool with_export) {
     const int nl = h->nlevels;
     const dim3 blk2(64, 4, 1), blk1(256, 1, 1);
     // (no fill launches in front of the chain: the quadtree's capacity flag is cleared by k_fast_cells, and the descriptor rows beyond n[b] -
@@ -390,6 +451,7 @@ int enqueue_extract(orbx_extractor* h, int B, const uint8_t* d_images, int src_w
                     (const ResizeTap*)h->d_ytab.p, h->d_pyr.p, h->pyr_stride, lds_pitch, lds_rows);
     }
     stage_end(h, ST_PYRAMID, h->s0);
+    if (with_export && h->exp_edge > 0) { const int rc = export_enqueue(h, B); if (rc) return rc; }
     BlurTaps taps;
     {
         static const int A[7] = {18, 34, 48, 56, 48, 34, 18}, Bt[7] = {18, 34, 49, 55, 49, 34, 18};
@@ -528,6 +590,7 @@ int orbx_create(orbx_extractor** out, int nfeatures, float scale_factor, int nle
 void orbx_destroy(orbx_extractor* h) {
     if (!h) return;
     rt::set_device(h->device);
+    export_release(h);
     if (h->have_streams) {
         rt::stream_sync(h->s0); rt::stream_sync(h->s1);
 #ifndef ORBX_EMU
@@ -551,6 +614,7 @@ void orbx_destroy(orbx_extractor* h) {
     h->d_lp.release(); h->d_depth_in.release(); h->h_lp_in.release(); h->h_lp_out.release();
     h->d_aux.release(); h->d_qtprof.release(); h->d_qtpool.release(); h->d_rowstart.release(); h->d_rowitems.release();
     h->d_mapx.release(); h->d_mapy.release(); h->d_in_xt.release(); h->d_in_yt.release(); h->d_frame.release();
+    h->d_exp.release(); for (auto& x : h->h_exp) x.release();     // (export_release above gave them back already)
     delete h;
 }
 
@@ -603,6 +667,11 @@ int orbx_extract_batch(orbx_extractor* h, int B, const uint8_t* images, int widt
         }
         if (geom && C > 1 && h->d_frame.ensure((size_t)B * h->W * h->H * C + 16)) return fail(ORBX_E_DEVICE, "allocation failed");
     }
+    // the previous batch's export may still be reading the pyramid that this one rewrites
+    if (h->exp_guard) {
+        if (rt::stream_wait_event(h->s0, h->ev_exp_read)) return fail(ORBX_E_DEVICE, "extraction could not be ordered behind the pyramid export: %s", rt::last_error());
+        h->exp_guard = false;
+    }
     const uint8_t* d_images = images;
     if (!on_device) {
         const size_t bytes = (size_t)(B - 1) * image_stride + (size_t)stride * (height - 1) + row_bytes;
@@ -621,21 +690,23 @@ int orbx_extract_batch(orbx_extractor* h, int B, const uint8_t* images, int widt
     // is baked into the kernel arguments and re-captured when any of it changes.
     if (h->use_graph && !h->profile && !h->in_active) {
         const bool same = h->graph_exec && h->g_B == B && h->g_images == d_images && h->g_stride == stride && h->g_image_stride == image_stride &&
-                          h->g_lap0 == lap0 && h->g_lap1 == lap1 && h->g_W == h->W && h->g_H == h->H && h->g_pyr == h->d_pyr.p && h->g_gauss == h->gauss_variant && h->g_undist_gen == h->undist_gen && h->g_pyramid_mode == h->pyramid_mode && h->g_small_forms == h->small_forms;
+                          h->g_lap0 == lap0 && h->g_lap1 == lap1 && h->g_W == h->W && h->g_H == h->H && h->g_pyr == h->d_pyr.p && h->g_gauss == h->gauss_variant && h->g_undist_gen == h->undist_gen && h->g_pyramid_mode == h->pyramid_mode && h->g_small_forms == h->small_forms && h->g_exp_edge == h->exp_edge;
         if (!same) {
             if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
             if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
             if (hipStreamBeginCapture(h->s0, hipStreamCaptureModeThreadLocal) != hipSuccess) return fail(ORBX_E_DEVICE, "graph capture failed to start");
-            rc = enqueue_extract(h, B, d_images, width, height, stride, image_stride, lap0, lap1);
+            rc = enqueue_extract(h, B, d_images, width, height, stride, image_stride, lap0, lap1, false);
             const hipError_t e = hipStreamEndCapture(h->s0, &h->graph);
             if (rc || e != hipSuccess || hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0) != hipSuccess) {
                 h->graph_exec = nullptr;
                 return fail(ORBX_E_DEVICE, "graph capture/instantiate failed: %s", rt::last_error());
             }
             h->g_B = B; h->g_images = d_images; h->g_stride = stride; h->g_image_stride = image_stride; h->g_lap0 = lap0; h->g_lap1 = lap1;
-            h->g_W = h->W; h->g_H = h->H; h->g_pyr = h->d_pyr.p; h->g_gauss = h->gauss_variant; h->g_undist_gen = h->undist_gen; h->g_pyramid_mode = h->pyramid_mode; h->g_small_forms = h->small_forms;
+            h->g_W = h->W; h->g_H = h->H; h->g_pyr = h->d_pyr.p; h->g_gauss = h->gauss_variant; h->g_undist_gen = h->undist_gen; h->g_pyramid_mode = h->pyramid_mode; h->g_small_forms = h->small_forms; h->g_exp_edge = h->exp_edge;
         }
         if (hipGraphLaunch(h->graph_exec, h->s0) != hipSuccess) return fail(ORBX_E_DEVICE, "graph launch failed: %s", rt::last_error());
+        // the pyramid export is not part of the graph (its ring slot changes from call to call): it forks from s0 behind the whole replay
+        if (h->exp_edge > 0 && (rc = export_enqueue(h, B))) return rc;
         // the records inside the capture belong to the graph; these are the ones other streams can wait on (an upload into the input buffer
         // waits for ev_import: after a replay that is the end of the whole graph, which is later than needed but never too early)
         h->import_lazy = true; h->done_lazy = true;
@@ -643,7 +714,7 @@ int orbx_extract_batch(orbx_extractor* h, int B, const uint8_t* images, int widt
         return ORBX_OK;
     }
 #endif
-    return enqueue_extract(h, B, d_images, width, height, stride, image_stride, lap0, lap1);
+    return enqueue_extract(h, B, d_images, width, height, stride, image_stride, lap0, lap1, true);
 }
 
 int orbx_set_input(orbx_extractor* h, const OrbxInputSpec* spec) {
@@ -671,6 +742,7 @@ int orbx_sync(orbx_extractor* h) {
     rt::set_device(h->device);
     if (rt::stream_sync(h->s0) || rt::stream_sync(h->s1)) return fail(ORBX_E_DEVICE, "stream sync failed: %s", rt::last_error());
     if (h->copy_pending && rt::stream_sync(h->s_copy)) return fail(ORBX_E_DEVICE, "copy stream sync failed: %s", rt::last_error());   // uploads nobody has consumed yet
+    if (export_drain(h)) return fail(ORBX_E_DEVICE, "export stream sync failed: %s", rt::last_error());
     if (h->profile) for (int i = 0; i < ORBX_NSTAGES; i++) if (i != ST_MATCH) h->stage_ms[i] = rt::event_elapsed_ms(h->ev_stage[i][0], h->ev_stage[i][1]);
     return ORBX_OK;
 }
@@ -744,6 +816,40 @@ int orbx_pyramid_fetch(orbx_extractor* h, int b, int blurred, uint8_t* const* ds
     return ORBX_OK;
 }
 
+int orbx_set_pyramid_export(orbx_extractor* h, int edge, int depth) {
+    if (!h) return fail(ORBX_E_ARG, "null handle");
+    if (edge < 0 || edge > kExportMaxEdge || (edge > 0 && (depth < 1 || depth > kExportMaxDepth)))
+        return fail(ORBX_E_ARG, "pyramid export: edge 0 (off) .. %d, depth 1 .. %d", kExportMaxEdge, kExportMaxDepth);
+    if (edge == h->exp_edge && (edge == 0 || depth == h->exp_depth)) return ORBX_OK;      // unchanged: the ring stays as it is
+    rt::set_device(h->device);
+    export_release(h);
+    if (edge == 0) return ORBX_OK;
+    int e = rt::stream_create(&h->s_exp);
+    h->have_exp_stream = e == 0;
+    e |= rt::event_create(&h->ev_exp_fork) | rt::event_create(&h->ev_exp_read);
+    for (int k = 0; k < depth; k++) e |= rt::event_create(&h->ev_exp_slot[k]);
+    if (e) { export_release(h); return fail(ORBX_E_DEVICE, "pyramid export: stream/event creation failed"); }
+    h->exp_edge = edge; h->exp_depth = depth;
+    const int rc = export_prepare(h);                     // slots for the batch size configured so far (configure() grows them later)
+    if (rc) export_release(h);
+    return rc;
+}
+
+int orbx_pyramid_exported(orbx_extractor* h, int b, const uint8_t** base, size_t* offset, int* step, int* width, int* height) {
+    if (!h || h->exp_slot < 0 || b < 0 || b >= h->exp_B || b >= h->lastB)
+        return fail(ORBX_E_ARG, "no exported pyramid for image %d of the last extraction (export off, switched on since, or the geometry changed)", b);
+    rt::set_device(h->device);
+    if (rt::event_sync(h->ev_exp_slot[h->exp_slot])) return fail(ORBX_E_DEVICE, "pyramid export failed: %s", rt::last_error());
+    if (base) *base = h->h_exp[h->exp_slot].p + (size_t)b * h->exp_stride;
+    for (int l = 0; l < h->nlevels; l++) {
+        if (offset) offset[l] = (size_t)h->exp_fl.off[l];
+        if (step) step[l] = h->exp_fl.step[l];
+        if (width) width[l] = h->lv[l].w;
+        if (height) height[l] = h->lv[l].h;
+    }
+    return ORBX_OK;
+}
+
 int orbx_device_alloc(orbx_extractor* h, size_t bytes, void** dptr) {
     if (!h || !dptr) return fail(ORBX_E_ARG, "null");
     rt::set_device(h->device);
@@ -766,6 +872,7 @@ int orbx_device_upload_async(orbx_extractor* h, void* dptr, const void* host, si
     rt::set_device(h->device);
     record_import_if_pending(h);
     if (h->lastB > 0 && rt::stream_wait_event(h->s_copy, h->ev_import)) return fail(ORBX_E_DEVICE, "upload could not be ordered behind the previous extraction: %s", rt::last_error());
+    if (h->exp_pending && rt::stream_wait_event(h->s_copy, h->ev_exp_read)) return fail(ORBX_E_DEVICE, "upload could not be ordered behind the pyramid export: %s", rt::last_error());
     if (rt::copy_h2d(dptr, host, bytes, h->s_copy) || rt::event_record(h->ev_copy, h->s_copy)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
     h->copy_pending = true;
     return ORBX_OK;
@@ -865,6 +972,8 @@ int orbx_input_buffer(orbx_extractor* h, int width, int height, int B, void** dp
     if (!h || !dptr) return fail(ORBX_E_ARG, "null");
     if (h->in_active && (h->in_channels != 1 || h->in_geometry != 0)) return fail(ORBX_E_ARG, "zero-copy input needs plain 8-bit grey frames (an input pre-step is set)");
     const int rc = configure(h, width, height, B); if (rc) return rc;
+    // the caller writes level 0 by any means once this returns: the last export must have read it
+    if (h->exp_pending && rt::event_sync(h->ev_exp_read)) return fail(ORBX_E_DEVICE, "pyramid export failed: %s", rt::last_error());
     *dptr = h->d_pyr.p + h->lv[0].off;
     if (stride) *stride = h->lv[0].pitch;
     if (image_stride) *image_stride = h->pyr_stride;

@@ -20,6 +20,8 @@ inline int round_half_even_f(float v) { return (int)lrintf(v); }    // cvRound u
 inline int round_half_even_d(double v) { return (int)lrint(v); }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+constexpr int kExportMaxDepth = 8, kExportMaxEdge = 256;     // orbx_set_pyramid_export
+
 enum Stage { ST_IMPORT = 0, ST_PYRAMID, ST_FAST, ST_QUADTREE, ST_BLUR, ST_LAYOUT, ST_DESCRIBE, ST_MATCH };
 
 template <typename T> struct DevBuf {
@@ -128,6 +130,18 @@ struct orbx_extractor {
     // not the live `undist` - orbx_set_undistort between an extraction and a search would otherwise point them at stale or unallocated keypoints
     int ex_undist_gen = 0; bool ex_undist_active = false;
     orbx::DevBuf<int> d_aux;     // int4 per keypoint: stereo row band / x / octave (k_orient_brief -> k_stereo_match)
+    // bordered pyramid export (orbx_set_pyramid_export; nothing of it exists while exp_edge == 0).  k_frame_pyramid writes the framed levels of a batch
+    // into d_exp on s_exp, forked from s0 when the pyramid is complete; one D2H copy moves them into ring slot exp_count % exp_depth.  exp_slot: the
+    // slot of the last extraction (-1: it exported nothing that is still valid), exp_B its batch
+    int exp_edge = 0, exp_depth = 0, exp_slot = -1, exp_B = 0, g_exp_edge = 0;
+    uint64_t exp_count = 0;
+    size_t exp_stride = 0, exp_cap = 0;        // bytes per image (levels at 64-byte offsets, 256-byte multiple); bytes of every slot
+    orbx::FrameLayout exp_fl = {};
+    orbx::rt::stream_t s_exp = 0;
+    orbx::rt::event_t ev_exp_fork = 0, ev_exp_read = 0, ev_exp_slot[orbx::kExportMaxDepth] = {};
+    bool have_exp_stream = false;
+    bool exp_pending = false, exp_guard = false;  // an export was enqueued (ev_exp_read: its kernel's reads of d_pyr); s0 has not waited for that yet
+    orbx::DevBuf<uint8_t> d_exp; orbx::HostBuf<uint8_t> h_exp[orbx::kExportMaxDepth];
 };
 // mvKeysUn of the last extraction no longer matches the undistortion model of the handle (orbx_set_undistort was called in between)
 inline void record_done_if_pending(orbx_extractor* h) { if (h->done_lazy) { orbx::rt::event_record(h->ev_done, h->s0); h->done_lazy = false; } }

@@ -34,6 +34,11 @@ __global__ void k_fast_cells(const LevelInfo* __restrict__ lv, const CellInfo* _
                              const uint8_t* __restrict__ pyr, size_t pyr_stride, int iniTh, int minTh,
                              uint32_t* __restrict__ slots, size_t slots_stride, int* __restrict__ cell_count,
                              int tile_bytes, int list_bytes, int* __restrict__ status);
+// bordered copy of every level (ORB-SLAM3's mvImagePyramid layout, BORDER_REFLECT_101): grid (fl.band[nlevels], B), block 256; a workgroup writes
+// kFrameRows framed rows of one level, a lane 16 bytes per store
+constexpr int kFrameRows = 8;
+__global__ void k_frame_pyramid(const LevelInfo* __restrict__ lv, int nlevels, const uint8_t* __restrict__ pyr, size_t pyr_stride,
+                                uint8_t* __restrict__ out, size_t out_stride, FrameLayout fl);
 constexpr int kResizeRows = 8;         // output rows per k_resize tile (256 columns wide)
 // Output rows per k_blur wave (a block covers 256 columns x 4 strips of that many rows).  A strip reads 6 halo rows on top of its own: large batches
 // run strips of 32 rows (the horizontal pass of 38 input rows per 32 outputs instead of 22 per 16: +1.0 % on the headline, profiles/r06/ab_experiments.txt),

@@ -55,6 +55,9 @@ struct KeyPointRec { float x, y, size, angle, response; int32_t octave, class_id
 
 struct BlurTaps { int k[7]; };                       // 7-tap Gaussian, 8-bit fixed point
 struct BlurTiles { int begin[kMaxLevels + 1]; };         // first tile (256 cols x 64 rows) of each level in k_blur's grid
+// k_frame_pyramid (orbx_set_pyramid_export): level l's (w + 2 edge) x (h + 2 edge) frame at byte `off` of an image's export block, rows `step` bytes
+// apart (a multiple of 16), and the first row band of each level in the launch's grid
+struct FrameLayout { int off[kMaxLevels], step[kMaxLevels], band[kMaxLevels + 1], edge; };
 struct UmaxTab { int u[16]; };                        // circular patch half-widths (src/ORBextractor.cc:542-570)
 struct StereoParams { float mbf, mb; int th_high, th_orb; int debug_flags; };   // ORBmatcher::TH_HIGH, (TH_HIGH+TH_LOW)/2
 

@@ -163,6 +163,31 @@ class ORBextractor:
     def mvImagePyramid(self):
         return [self.pyramid_level(l) for l in range(self.nlevels)]
 
+    def pyramid_export(self, edge=19, depth=2):
+        """From the next extraction on, every image's levels are also exported as framed planes (the level at (edge, edge) inside a
+        (w + 2 edge) x (h + 2 edge) frame, BORDER_REFLECT_101 around it: the reference's mvImagePyramid layout) into a ring of `depth`
+        page-locked slots of the handle, overlapped with the rest of the extraction (orbx_set_pyramid_export).  edge=0 turns it off."""
+        self._lib.check(self._lib.L.orbx_set_pyramid_export(self._h, int(edge), int(depth)))
+        self._export_edge = int(edge)
+
+    def exported_pyramid(self, image_index=0):
+        """The framed levels of image `image_index` of the last extraction, waiting for their export: read-only numpy VIEWS into the
+        handle's ring slot (no copy), valid until `depth` further extractions have been enqueued, the geometry or the batch grows, the
+        export is switched off or the extractor is closed.  Copy them (np.array(v)) to keep them longer."""
+        nl, e = self.nlevels, getattr(self, "_export_edge", 0)
+        base = C.c_void_p()
+        off = np.zeros(nl, np.uint64); step = np.zeros(nl, np.int32); w = np.zeros(nl, np.int32); h = np.zeros(nl, np.int32)
+        self._lib.check(self._lib.L.orbx_pyramid_exported(self._h, int(image_index), C.byref(base), off.ctypes.data, step.ctypes.data,
+                                                          w.ctypes.data, h.ctypes.data))
+        out = []
+        for l in range(nl):
+            fw, fh, st = int(w[l]) + 2 * e, int(h[l]) + 2 * e, int(step[l])
+            buf = (C.c_uint8 * (st * fh)).from_address(base.value + int(off[l]))
+            a = np.frombuffer(buf, np.uint8).reshape(fh, st)[:, :fw]
+            a.flags.writeable = False
+            out.append(a)
+        return out
+
     # ---- stage probes / profiling ----
     def debug_candidates(self, level, image_index=0):
         cap = 1 << 18

@@ -1,0 +1,33 @@
+"""The drop-in ORBextractor.h's mvImagePyramid over the device pyramid export (tests/cpp/pyramid_export_facade_test.cpp): views into the handle's
+export ring, bytes equal to the former fetch + copyMakeBorder path, the previous call's Mats intact - on the emulator build and on the GPU."""
+import os
+import subprocess
+
+import pytest
+
+import oracle_lib as ol
+from orb_slam3_detailed_comments_amd import synth, _lib
+
+ROOT = ol.ROOT
+
+
+def _run(tmp_path, libdir, libname, w, h, calls):
+    raws = []
+    for s in range(3):
+        img = synth.corner_field(w, h, seed=30 + s, nrect=800 if w < 500 else 3000) if s < 2 else synth.natural(w, h, seed=30 + s)
+        p = tmp_path / ("im%d.raw" % s); p.write_bytes(img.tobytes()); raws.append(str(p))
+    exe = tmp_path / "pyramid_export_facade_test"
+    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + os.path.join(ROOT, "include", "orb_slam3_amd"), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
+                    os.path.join(ROOT, "tests", "cpp", "pyramid_export_facade_test.cpp"), "-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-lpthread",
+                    "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe), str(w), str(h), str(calls)] + raws, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and r.stdout.startswith("ok"), r.stdout + r.stderr
+
+
+def test_facade_pyramid_export_emulated(tmp_path, emu_lib):
+    _run(tmp_path, os.path.join(ROOT, "tests", "emu"), "orbx_emu", 376, 240, 5)
+
+
+@pytest.mark.gpu
+def test_facade_pyramid_export_gpu(tmp_path, hip_lib):
+    _run(tmp_path, os.path.dirname(_lib.HIP_LIB_PATH), "orbx_hip", 752, 480, 12)
