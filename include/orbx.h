@@ -568,6 +568,35 @@ int orbm_search_by_projection_frame_fisheye(orbx_extractor* h, const OrbmFisheye
                                             const float* proj_ur, const float* proj_vr, float th, int forward, int backward,
                                             int check_orientation, int* assigned, int* nmatches);
 
+/* The two searches above for a BATCH of rig frames without leaving the device.  Frame b = left image lf + b of L's last extraction (camera 1:
+ * mvKeys, its descriptors) and right image rf + b of R's last extraction (camera 2: mvKeysRight), linked by the mvLeftToRightMatch /
+ * mvRightToLeftMatch that the last orbm_stereo_fisheye(L, lf, R, rf, B, ...) left on the device.  L == R is allowed (lf = 0, rf = B for a batch
+ * extracted as [L0 .. L(B-1), R0 .. R(B-1)]).  Refused (ORBX_E_ARG) when L has no such orbm_stereo_fisheye call, when that call covered other
+ * frames, when either handle has extracted since, when the handles differ in orbx_max_keypoints, levels, scale factor or device.  One grid per
+ * camera per frame over the extracted keypoints (not mvKeysUn, as Frame::AssignFeaturesToGrid for Nleft != -1), with the bounds of frames[0]:
+ * every frame must have the same bounds.  occupied: [B][2 * orbx_max_keypoints()] bytes in the slot layout of `assigned` (NULL = none).
+ * Asynchronous on L's stream; the results are fetched with orbm_search_rig_batch_fetch.  Both calls share L's one pending batch with the
+ * single-camera batch searches: any enqueue discards a batch that has not been fetched, and a refused enqueue leaves nothing to fetch. */
+/* Tracking::SearchLocalPoints for B rig frames (src/Tracking.cc:3979-4067 with Nleft != -1): per frame the result of
+ * orbm_search_local_points_fisheye.  frames[b]: pose (mRcw for the frustum test), cameras and bounds as in orbm_is_in_frustum_rig; the local map
+ * is resident; is_bad / has_obs as in orbm_search_local_points_batch. */
+int orbm_search_local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* frames,
+                                       const orbm_points* points, const uint8_t* is_bad, const uint8_t* has_obs, const uint8_t* occupied,
+                                       float viewing_cos_limit, float th, int far_points, float th_far, float nnratio, int want_in_view);
+/* SearchByProjection(CurrentFrame, LastFrame, th, bMono) for B rig frames (src/ORBmatcher.cc:1950-2184 incl. :2089-2152): per frame the result of
+ * orbm_search_by_projection_frame_fisheye.  cur[b].left: pose (the quaternion qcw), camera 1 and bounds as in orbm_search_by_projection_lastframe_batch;
+ * `last` as there.  Camera 2's projections are made on the device as the reference makes them: x3Dr = CurrentFrame.GetRelativePoseTrl() * x3Dc
+ * (Sophus' quaternion action), then CurrentFrame.mpCamera->project(x3Dr) - camera 1's model - and no bounds test.  trl = mTrl: unit quaternion
+ * coefficients (x, y, z, w) then the translation, 7 floats for the whole batch. */
+int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* cur,
+                                                  const float* trl, const OrbmLastFrameBatch* last, float th, const uint8_t* forward,
+                                                  const uint8_t* backward, int check_orientation, const uint8_t* occupied);
+/* Results of the last rig batch of L: assigned [B][cap] indexed like F.mvpMapPoints (camera 1 at [0, Nleft), camera 2 at [Nleft, Nleft + Nright);
+ * -1 untouched, -2 reset by the rotation check), cap >= 2 * orbx_max_keypoints(); nmatches [B]; in_view / in_view_r [B][M] (mbTrackInView /
+ * mbTrackInViewR: local-map form with want_in_view only).  Every output may be NULL.  ORBX_E_CAPACITY = the candidate pool was too small for
+ * this scene: it has been enlarged, enqueue the same call again.  orbm_search_local_points_fetch refuses a rig batch, this call a single-camera one. */
+int orbm_search_rig_batch_fetch(orbx_extractor* L, int* assigned, int cap, int* nmatches, uint8_t* in_view, uint8_t* in_view_r);
+
 /* ---- the geometry in front of the projection-type searches, on the device ----
  * SearchByProjection(Frame, LastFrame) (src/ORBmatcher.cc:1993-2010), (Frame, KeyFrame) (:2228-2256), (KeyFrame, Sim3, ...) x2 (:525-560, :640-690),
  * Fuse x2 (:1388-1430, :1590-1625) and SearchBySim3 (:1745-1790, :1830-1875) all start with the same per-map-point chain: transform, depth test,

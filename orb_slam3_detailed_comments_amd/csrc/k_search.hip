@@ -675,6 +675,251 @@ __global__ void __launch_bounds__(64) k_lastframe_accept(int M, int cap, const i
     local_accept_body<true>(M, cap, n_per_frame, q_start, q_count, entries, occupied0, has_obs, 0.0f, th_high, assigned, nmatches, last_angle, cur_kps, check_ori);
 }
 
+// ---- two-camera rig frames (Frame::Nleft != -1) in a batch ----
+// Frame::isInFrustum with two cameras (src/Frame.cc:754-766 -> isInFrustumChecks :1592-1650, once per camera) and the window queries of both passes
+// of SearchByProjection(Frame, MapPoints) for B rig frames.  Fb = [B][2]: camera 1 and camera 2 of frame b, both in rig_mode.  Camera 1's query is
+// the one frustum_body writes (the search runs with the right-coordinate gate off: a rig frame has no mvuRight).  Camera 2's (src/ORBmatcher.cc:
+// 170-176): the point is alive (in view of either camera, not far by camera 1's depth, not bad), in camera 2's view with a level; radius
+// RadiusByViewingCos(mTrackViewCosR) WITHOUT th; levels [level - 1, level].  Every output of camera c of frame b sits at b * M (track: b * 5 * M).
+__global__ void __launch_bounds__(256) k_frustum_rig(const FrustumParams* __restrict__ Fb, int M, const float* __restrict__ pos, const float* __restrict__ normal,
+                                                     const float* __restrict__ min_dist, const float* __restrict__ max_dist, const uint8_t* __restrict__ is_bad,
+                                                     uint8_t* in_view1, uint8_t* in_view2, float* track1, float* track2, int* level1, int* level2,
+                                                     AreaQuery* __restrict__ q1, AreaQuery* __restrict__ q2, int* __restrict__ zero4) {
+    const size_t b = blockIdx.y;
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (zero4 && i < 4 && b == 0) zero4[i] = 0;
+    if (i >= M) return;
+    const FrustumParams& F1 = Fb[2 * b];
+    const FrustumParams& F2 = Fb[2 * b + 1];
+    const size_t o = b * (size_t)M, ot = 5 * o, Ms = (size_t)M;
+    frustum_body(F1, i, M, pos, normal, min_dist, max_dist, is_bad, in_view1 + o, track1 + ot, level1 + o, q1 + o);
+    frustum_body(F2, i, M, pos, normal, min_dist, max_dist, is_bad, in_view2 + o, track2 + ot, level2 + o, nullptr);
+    // (this thread's own stores, read back)
+    const bool inl = in_view1[o + i] != 0, inr = in_view2[o + i] != 0;
+    const int lvl = level2[o + i];
+    AreaQuery q; q.x = 0; q.y = 0; q.r = 0; q.ur = 0; q.min_level = 0; q.max_level = 0; q.active = 0; q.gate = 0;
+    const bool alive = (inl || inr) && !(F1.far_points && track1[ot + 3 * Ms + i] > F1.th_far) && !(is_bad && is_bad[i]);
+    if (alive && inr && lvl >= 0 && lvl < F2.nlevels) {
+        const float r = (double)track2[ot + 4 * Ms + i] > 0.998 ? 2.5f : 4.0f;
+        q.x = track2[ot + i]; q.y = track2[ot + Ms + i]; q.r = __fmul_rn(r, pick(F2.scale_factors, lvl));
+        q.min_level = lvl - 1; q.max_level = lvl; q.active = 1;
+    }
+    q2[o + i] = q;
+}
+
+// The head of SearchByProjection(CurrentFrame, LastFrame) for B rig frames: camera 1 exactly as k_lastframe_queries; camera 2 (src/ORBmatcher.cc:
+// 2089-2100) for every point whose camera-1 query exists: x3Dr = mTrl * x3Dc (Sophus' quaternion action), projected with CurrentFrame.mpCamera
+// (camera 1's model - the reference's own choice), no depth or image test, the same radius and level window, no right-coordinate gate.
+__global__ void __launch_bounds__(256) k_lastframe_queries_rig(const FrustumParams* __restrict__ Fb, int capL, const int* __restrict__ n_last,
+                                                               const float* __restrict__ pos, const uint8_t* __restrict__ valid, const int* __restrict__ octave,
+                                                               RigRelPose trl, AreaQuery* q1, AreaQuery* __restrict__ q2, int* __restrict__ zero4) {
+    projection_queries_body<false>(Fb, capL, n_last, pos, valid, octave, nullptr, nullptr, q1, zero4);
+    const size_t b = blockIdx.y;
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= capL) return;
+    const size_t o = b * (size_t)capL + i;
+    const AreaQuery A = q1[o];                                     // (this thread's own store)
+    AreaQuery q; q.x = 0; q.y = 0; q.r = 0; q.ur = 0; q.min_level = 0; q.max_level = 0; q.active = 0; q.gate = 0;
+    if (A.active) {
+        const FrustumParams& F = Fb[b];
+        const float P0 = pos[3 * o], P1 = pos[3 * o + 1], P2 = pos[3 * o + 2];
+        float pc[3];
+        if (F.debug_flags & 16) se3_act_matrix_form(F.qcw, F.tcw, P0, P1, P2, pc);
+        else se3_act(F.qcw, F.tcw, P0, P1, P2, pc);
+        se3_act(trl.q, trl.t, pc[0], pc[1], pc[2], pc);
+        const float x = pc[0], y = pc[1], z = pc[2];
+        float u, v;
+        if (F.kb8) { KB8Cam c; for (int k = 0; k < 8; k++) c.p[k] = F.cam[k]; const float pcc[3] = {x, y, z}; float uv[2]; kb8_project(c, pcc, uv); u = uv[0]; v = uv[1]; }
+        else { u = __fadd_rn(__fdiv_rn(__fmul_rn(F.cam[0], x), z), F.cam[2]); v = __fadd_rn(__fdiv_rn(__fmul_rn(F.cam[1], y), z), F.cam[3]); }
+        q.x = u; q.y = v; q.r = A.r; q.min_level = A.min_level; q.max_level = A.max_level; q.active = 1;
+    }
+    q2[o] = q;
+}
+
+// The accept loops of both searches for rig frames, one wave per frame, in the joint slot space of F.mvpMapPoints: camera 1's keypoint i at slot i,
+// camera 2's keypoint j at slot Nleft + j.  The optimistic scheme of local_accept_body, per map point (lane) in point order:
+//   camera-1 pass against the current occupancy; MapPoints form (src/ORBmatcher.cc:62-168): a ratio-test rejection ends the point (`continue`),
+//   an accept writes the best slot AND its stereo partner Nleft + mvLeftToRightMatch[best] (partner writes ignore occupancy, as the reference's do);
+//   camera-2 pass (:170-236) against the occupancy with this point's own camera-1 writes applied; an accept writes Nleft + best and
+//   mvRightToLeftMatch[best].  LastFrame form (:2025-2152): best only, an empty camera-1 window ends the point, no partners, every accept is an
+//   event of ONE rotation histogram over both cameras.
+// Every write sets the slot's occupancy to the point's has_obs (F.mvpMapPoints[slot] = pMP: a partner write of a point without observations frees an
+// occupied slot).  A lane claims the slots whose occupancy its writes change; it is dirty when an earlier lane of the round claims a candidate of
+// either of its windows; lanes before the first dirty one commit.  The sequential last writer of a slot is the largest point index (atomicMax on
+// assigned); among the lanes committing in one round, the largest lane writing a slot sets its occupancy.
+// occupied0: [B][2 cap] bytes in the joint slot layout or NULL; has_obs: [M] (MapPoints form) or [B][M] (LastFrame form) or NULL; l2r / r2l: [B][cap];
+// assigned: [B][2 cap]; nmatches: [B].  dynamic LDS: claim word per slot (2 cap words) | occupancy byte per slot (2 cap, 16-byte multiple) | LastFrame:
+// two events per query (2 M words, slot * 32 + bin).
+template <bool LASTFRAME>
+__device__ __forceinline__ void rig_accept_body(int M, int cap, const int* __restrict__ n1, const int* __restrict__ n2, const int* __restrict__ qs1,
+                                                const int* __restrict__ qc1, const int* __restrict__ qs2, const int* __restrict__ qc2,
+                                                const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0, const uint8_t* __restrict__ has_obs,
+                                                const int* __restrict__ l2r, const int* __restrict__ r2l, float nnratio, int th_high, int* __restrict__ assigned,
+                                                int* __restrict__ nmatches, const float* __restrict__ last_angle, const KeyPointRec* __restrict__ kps1,
+                                                const KeyPointRec* __restrict__ kps2, int check_ori) {
+    ORBX_DYN_SMEM(smem);
+    const int S = 2 * cap;
+    unsigned* s_claim = (unsigned*)smem;
+    uint8_t* s_occ = smem + 4 * (size_t)S;                        // one byte per slot: the last writer of a slot stores its has_obs, set or clear
+    int* events = LASTFRAME ? (int*)(s_occ + (((size_t)S + 15) & ~(size_t)15)) : nullptr;
+    __shared__ int s_hist[32];
+    const int lane = lane_id();
+    const size_t b = blockIdx.x;
+    const int NL = n1[b], NR = n2[b], NS = NL + NR;
+    qs1 += b * (size_t)M; qc1 += b * (size_t)M; qs2 += b * (size_t)M; qc2 += b * (size_t)M; assigned += b * (size_t)S;
+    if (LASTFRAME) {
+        if (has_obs) has_obs += b * (size_t)M;
+        last_angle += b * (size_t)M; kps1 += b * (size_t)cap; kps2 += b * (size_t)cap;
+        if (lane < 32) s_hist[lane] = 0;
+    } else { l2r += b * (size_t)cap; r2l += b * (size_t)cap; }
+    for (int i = lane; i < S; i += 64) {
+        assigned[i] = -1; s_claim[i] = 0xFFu;
+        s_occ[i] = (occupied0 && i < NS && occupied0[b * (size_t)S + i]) ? 1 : 0;
+    }
+    ORBX_WAVE_SYNC();
+    int nm = 0;
+    for (int i0 = 0; i0 < M; i0 += 64) {
+        const int qi = i0 + lane;
+        const int c1 = qi < M ? qc1[qi] : 0, st1 = qi < M ? qs1[qi] : 0, c2 = qi < M ? qc2[qi] : 0, st2 = qi < M ? qs2[qi] : 0;
+        const bool obs = qi < M && (!has_obs || has_obs[qi]);
+        bool pending = LASTFRAME ? c1 > 0 : (c1 > 0 || c2 > 0);
+        if (LASTFRAME && qi < M) { events[2 * qi] = -1; events[2 * qi + 1] = -1; }
+        while (__ballot(pending) != 0ull) {
+            // 1. this point's decision against the current occupancy: the slots it writes (camera-1 best, its partner, camera-2 best, its partner)
+            int w0 = -1, w1 = -1, w2 = -1, w3 = -1;
+            if (pending) {
+                bool end = false;
+                unsigned k1 = 0xFFFFFFFFu, k2 = 0xFFFFFFFFu; int e1 = 0, e2 = 0, best = -1;
+                for (int k = 0; k < c1; k++) {
+                    const int2 e = entries[st1 + k];
+                    if (s_occ[e.x]) continue;
+                    const unsigned key = ((unsigned)(e.y & 0xFFFF) << 16) | (unsigned)k;
+                    if (key < k1) { k2 = k1; e2 = e1; k1 = key; e1 = e.y; best = e.x; } else if (key < k2) { k2 = key; e2 = e.y; }
+                }
+                if (k1 != 0xFFFFFFFFu && (e1 & 0xFFFF) <= th_high) {
+                    const int bestDist = e1 & 0xFFFF, bestLevel = e1 >> 16;
+                    const int bestDist2 = k2 != 0xFFFFFFFFu ? (e2 & 0xFFFF) : 256, bestLevel2 = k2 != 0xFFFFFFFFu ? (e2 >> 16) : -1;
+                    if (!LASTFRAME && bestLevel == bestLevel2 && (float)bestDist > __fmul_rn(nnratio, (float)bestDist2)) end = true;
+                    else {
+                        w0 = best;
+                        if (!LASTFRAME) { const int j = l2r[best]; if ((unsigned)j < (unsigned)NR) w1 = NL + j; }
+                    }
+                }
+                if (!end && c2 > 0) {
+                    k1 = 0xFFFFFFFFu; k2 = 0xFFFFFFFFu; e1 = 0; e2 = 0; best = -1;
+                    for (int k = 0; k < c2; k++) {
+                        const int2 e = entries[st2 + k];
+                        const int s = NL + e.x;
+                        if (s == w1 ? obs : s_occ[s] != 0) continue;
+                        const unsigned key = ((unsigned)(e.y & 0xFFFF) << 16) | (unsigned)k;
+                        if (key < k1) { k2 = k1; e2 = e1; k1 = key; e1 = e.y; best = e.x; } else if (key < k2) { k2 = key; e2 = e.y; }
+                    }
+                    if (k1 != 0xFFFFFFFFu && (e1 & 0xFFFF) <= th_high) {
+                        const int bestDist = e1 & 0xFFFF, bestLevel = e1 >> 16;
+                        const int bestDist2 = k2 != 0xFFFFFFFFu ? (e2 & 0xFFFF) : 256, bestLevel2 = k2 != 0xFFFFFFFFu ? (e2 >> 16) : -1;
+                        if (LASTFRAME || !(bestLevel == bestLevel2 && (float)bestDist > __fmul_rn(nnratio, (float)bestDist2))) {
+                            w2 = NL + best;
+                            if (!LASTFRAME) { const int j = r2l[best]; if ((unsigned)j < (unsigned)NL) w3 = j; }
+                        }
+                    }
+                }
+            }
+            const int ws[4] = {w0, w1, w2, w3};
+            // 2. claims: the slots whose occupancy this point's writes change
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int s = ws[k];
+                if (s >= 0 && (s_occ[s] != 0) != obs) atomicMin(&s_claim[s], (unsigned)lane);
+            }
+            ORBX_WAVE_SYNC();
+            // 3. dirty: an earlier lane claims a candidate of either window
+            bool dirty = false;
+            if (pending) {
+                for (int k = 0; k < c1 && !dirty; k++) if (s_claim[entries[st1 + k].x] < (unsigned)lane) dirty = true;
+                for (int k = 0; k < c2 && !dirty; k++) if (s_claim[NL + entries[st2 + k].x] < (unsigned)lane) dirty = true;
+            }
+            const unsigned long long dmask = __ballot(dirty);
+            const int first_dirty = dmask ? __ffsll(dmask) - 1 : 64;
+            ORBX_WAVE_SYNC();
+#pragma unroll
+            for (int k = 0; k < 4; k++) if (ws[k] >= 0) s_claim[ws[k]] = 0xFFu;
+            ORBX_WAVE_SYNC();
+            // 4. commit the lanes before the first dirty one; the largest committing lane that writes a slot decides its occupancy
+            const bool commit = pending && lane < first_dirty;
+            if (commit) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) if (ws[k] >= 0) { atomicMax(&assigned[ws[k]], qi); atomicMin(&s_claim[ws[k]], (unsigned)(63 - lane)); }
+            }
+            ORBX_WAVE_SYNC();
+            if (commit) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const int s = ws[k];
+                    if (s >= 0 && s_claim[s] == (unsigned)(63 - lane)) s_occ[s] = obs ? 1 : 0;
+                }
+            }
+            ORBX_WAVE_SYNC();
+            if (commit) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) if (ws[k] >= 0) s_claim[ws[k]] = 0xFFu;
+                if (LASTFRAME && check_ori) {                          // rot = angle(last) - angle(current), bin = round(rot / 30) (:2118-2125)
+#pragma unroll
+                    for (int c = 0; c < 2; c++) {
+                        const int s = c == 0 ? w0 : w2;
+                        if (s < 0) continue;
+                        float rot = __fsub_rn(last_angle[qi], c == 0 ? kps1[s].angle : kps2[s - NL].angle);
+                        if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
+                        int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
+                        if (bin == 30) bin = 0;
+                        atomicAdd(&s_hist[bin & 31], 1);
+                        events[2 * qi + c] = s * 32 + (bin & 31);
+                    }
+                }
+            }
+            nm += wave_sum(commit ? (int)(w0 >= 0) + (int)(w1 >= 0) + (int)(w2 >= 0) + (int)(w3 >= 0) : 0);
+            if (commit) pending = false;
+            ORBX_WAVE_SYNC();
+        }
+    }
+    if (LASTFRAME && check_ori) {
+        ORBX_WAVE_SYNC();
+        // ComputeThreeMaxima (src/ORBmatcher.cc:2335-2377) over the 30 bin sizes, every lane alike
+        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+        for (int i = 0; i < 30; i++) {
+            const int sz = s_hist[i];
+            if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
+            else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
+            else if (sz > max3) { max3 = sz; ind3 = i; }
+        }
+        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
+        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
+        int taken_back = 0;
+        for (int e = lane; e < 2 * M; e += 64) {
+            const int ev = events[e];
+            if (ev < 0) continue;
+            const int bin = ev & 31;
+            if (bin != ind1 && bin != ind2 && bin != ind3) { assigned[ev >> 5] = -2; taken_back++; }
+        }
+        nm -= wave_sum(taken_back);
+    }
+    if (lane == 0) nmatches[b] = nm;
+}
+
+__global__ void __launch_bounds__(64) k_rig_local_accept(int M, int cap, const int* __restrict__ n1, const int* __restrict__ n2, const int* __restrict__ qs1,
+                                                         const int* __restrict__ qc1, const int* __restrict__ qs2, const int* __restrict__ qc2,
+                                                         const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0, const uint8_t* __restrict__ has_obs,
+                                                         const int* __restrict__ l2r, const int* __restrict__ r2l, float nnratio, int th_high,
+                                                         int* __restrict__ assigned, int* __restrict__ nmatches) {
+    rig_accept_body<false>(M, cap, n1, n2, qs1, qc1, qs2, qc2, entries, occupied0, has_obs, l2r, r2l, nnratio, th_high, assigned, nmatches, nullptr, nullptr, nullptr, 0);
+}
+__global__ void __launch_bounds__(64) k_rig_lastframe_accept(int M, int cap, const int* __restrict__ n1, const int* __restrict__ n2, const int* __restrict__ qs1,
+                                                             const int* __restrict__ qc1, const int* __restrict__ qs2, const int* __restrict__ qc2,
+                                                             const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0, const uint8_t* __restrict__ has_obs,
+                                                             int th_high, int* __restrict__ assigned, int* __restrict__ nmatches, const float* __restrict__ last_angle,
+                                                             const KeyPointRec* __restrict__ kps1, const KeyPointRec* __restrict__ kps2, int check_ori) {
+    rig_accept_body<true>(M, cap, n1, n2, qs1, qc1, qs2, qc2, entries, occupied0, has_obs, nullptr, nullptr, 0.0f, th_high, assigned, nmatches, last_angle, kps1, kps2, check_ori);
+}
+
 // Frame::ComputeStereoFromRGBD (src/Frame.cc:1361-1391) for B frames: mvDepth[i] = imDepth.at<float>(v, u) at the (distorted) keypoint, truncated
 // to integers like cv::Mat::at(int, int) with float arguments, and mvuRight[i] = kpU.pt.x - mbf / d where d > 0, else both -1.  keys_un == NULL:
 // no distortion (mvKeysUn = mvKeys).  depth image b at depth + b * image_stride (floats), rows `stride` floats apart.

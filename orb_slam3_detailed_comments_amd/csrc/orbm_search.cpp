@@ -564,7 +564,7 @@ int orbm_stereo_from_depth(orbx_extractor* h, int first, int B, const float* dep
 int orbm_search_local_points_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView* frames, const orbm_points* points, const uint8_t* is_bad,
                                    const uint8_t* has_obs, const uint8_t* occupied, int use_u_right, float cos_limit, float th, int far_points, float th_far,
                                    float nnratio, int want_in_view) {
-    if (h) h->lp_B = 0;            // a new enqueue - accepted or refused - ends the previous batch: a refused call leaves nothing to fetch
+    if (h) { h->lp_B = 0; h->lp_rig = false; }     // a new enqueue - accepted or refused - ends the previous batch: a refused call leaves nothing to fetch
     if (!h || !frames || !points || B <= 0 || first < 0 || first + B > h->lastB) return fail(ORBX_E_ARG, "bad frame range / null");
     if (points->device != h->device) return fail(ORBX_E_ARG, "map points live on another device");
     for (int b = 0; b < B; b++) {
@@ -747,7 +747,7 @@ int projection_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView*
 
 int orbm_search_by_projection_lastframe_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView* cur, const OrbmLastFrameBatch* last, float th,
                                               const uint8_t* forward, const uint8_t* backward, int check_ori, const uint8_t* occupied, int use_u_right) {
-    if (h) h->lp_B = 0;
+    if (h) { h->lp_B = 0; h->lp_rig = false; }
     if (!h || !cur || !last || B <= 0 || first < 0 || first + B > h->lastB) return fail(ORBX_E_ARG, "bad frame range / null");
     if (last->cap_last <= 0 || !last->n || !last->pos || !last->valid || !last->octave || !last->angle || !last->desc) return fail(ORBX_E_ARG, "bad last-frame batch");
     const PointRows R = {last->cap_last, last->n, last->pos, last->valid, last->octave, last->angle, last->has_obs, last->desc, nullptr, nullptr};
@@ -756,7 +756,7 @@ int orbm_search_by_projection_lastframe_batch(orbx_extractor* h, int first, int 
 
 int orbm_search_by_projection_keyframe_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView* cur, const OrbmKeyFramePointBatch* kf, float th, int orb_dist,
                                              int check_ori, const uint8_t* occupied) {
-    if (h) h->lp_B = 0;
+    if (h) { h->lp_B = 0; h->lp_rig = false; }
     if (!h || !cur || !kf || B <= 0 || first < 0 || first + B > h->lastB) return fail(ORBX_E_ARG, "bad frame range / null");
     if (kf->cap_kf <= 0 || !kf->n || !kf->pos || !kf->valid || !kf->min_distance || !kf->max_distance || !kf->angle || !kf->desc) return fail(ORBX_E_ARG, "bad key-frame batch");
     if (orb_dist < 0 || orb_dist > 256) return fail(ORBX_E_ARG, "ORBdist out of range");
@@ -767,6 +767,7 @@ int orbm_search_by_projection_keyframe_batch(orbx_extractor* h, int first, int B
 
 int orbm_search_local_points_fetch(orbx_extractor* h, int* assigned, int cap, int* nmatches, uint8_t* in_view) {
     if (!h || h->lp_B <= 0) return fail(ORBX_E_ARG, "no batched local point search is pending");
+    if (h->lp_rig) return fail(ORBX_E_ARG, "the pending batch is a rig batch: fetch it with orbm_search_rig_batch_fetch");
     if (assigned && cap < h->kp_total_cap) return fail(ORBX_E_CAPACITY, "assigned rows need %d entries", h->kp_total_cap);
     rt::set_device(h->device);
     const size_t B1 = h->lp_B, M1 = h->lp_M > 0 ? h->lp_M : 1, C1 = h->kp_total_cap;
@@ -1869,6 +1870,237 @@ int orbm_search_by_projection_frame_fisheye(orbx_extractor* h, const OrbmFisheye
                 for (int idx : rotHist[i]) { assigned[idx] = -2; nmatches--; }
     }
     if (nmatches_out) *nmatches_out = nmatches;
+    return ORBX_OK;
+}
+
+
+// ---- the batched rig forms (Tracking::SearchLocalPoints / TrackWithMotionModel with Nleft != -1) ----------------------------------------------
+// Frame b = left image lf + b of L's last extraction (camera 1: mvKeys, its descriptors) and right image rf + b of R's (camera 2: mvKeysRight), linked by
+// the mvLeftToRightMatch / mvRightToLeftMatch that L's last orbm_stereo_fisheye(L, lf, R, rf, B) left in d_l2r / d_r2l.  One grid per camera per frame
+// (Frame::AssignFeaturesToGrid over mvKeys / mvKeysRight, src/Frame.cc:469-504), a window search per camera, the two-camera accept loop of
+// k_search.hip (rig_accept_body) one wave per frame; results in L's one pending batch: assigned [B][2 cap] in the slot layout of F.mvpMapPoints.
+}  // extern "C"
+namespace {
+int rig_pair_check(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B) {
+    if (!R || B <= 0 || lf < 0 || rf < 0) return fail(ORBX_E_ARG, "bad frame range / null");
+    if (lf + B > L->lastB || rf + B > R->lastB)
+        return fail(ORBX_E_ARG, "frames [%d, %d) of the left handle / [%d, %d) of the right one exceed their last extractions (%d / %d images)", lf, lf + B, rf, rf + B, L->lastB, R->lastB);
+    if (L->kp_total_cap != R->kp_total_cap || L->nlevels != R->nlevels || L->scaleFactor != R->scaleFactor)
+        return fail(ORBX_E_ARG, "the two handles differ in orbx_max_keypoints, levels or scale factor");
+    if (L->device != R->device) return fail(ORBX_E_ARG, "the two handles sit on different devices");
+    if (L->fe_B == 0) return fail(ORBX_E_ARG, "no orbm_stereo_fisheye with this handle on the left: the stereo links of the rig frames are missing");
+    if (L->fe_R != R || L->fe_lf != lf || L->fe_rf != rf || L->fe_B != B)
+        return fail(ORBX_E_ARG, "the last orbm_stereo_fisheye covered other frames (left %d, right %d, %d pairs)", L->fe_lf, L->fe_rf, L->fe_B);
+    if (L->fe_gen_L != L->extract_gen || L->fe_gen_R != R->extract_gen) return fail(ORBX_E_ARG, "a handle has extracted since the last orbm_stereo_fisheye: run it again");
+    return ORBX_OK;
+}
+int rig_frames_check(const OrbmFrustumRigView* f, int B) {
+    for (int b = 0; b < B; b++) {
+        const OrbmFrustumView& v = f[b].left;
+        if (v.nlevels < 1 || v.nlevels > kMaxLevels || !v.scale_factors) return fail(ORBX_E_ARG, "bad scale levels (frame %d)", b);
+        if (v.min_x != f[0].left.min_x || v.max_x != f[0].left.max_x || v.min_y != f[0].left.min_y || v.max_y != f[0].left.max_y)
+            return fail(ORBX_E_ARG, "frame %d has other image bounds than frame 0", b);
+    }
+    if (!(f[0].left.max_x > f[0].left.min_x) || !(f[0].left.max_y > f[0].left.min_y)) return fail(ORBX_E_ARG, "empty image bounds");
+    return ORBX_OK;
+}
+// the device block of a rig batch behind the upload: two grids, two query sets and CSRs, the result, the entry pool
+struct RigBlock {
+    size_t cof1, cst1, cit1, cof2, cst2, cit2, q1, q2, qs1, qc1, qs2, qc2, res, res_bytes, pool;
+    RigBlock(size_t o, size_t B1, size_t M1, size_t C1, size_t extra, size_t* o_extra) {
+        cof1 = o; o += al16(4 * B1 * C1); cst1 = o; o += al16(4 * B1 * kGridCellStride); cit1 = o; o += al16(4 * B1 * C1);
+        cof2 = o; o += al16(4 * B1 * C1); cst2 = o; o += al16(4 * B1 * kGridCellStride); cit2 = o; o += al16(4 * B1 * C1);
+        q1 = o; o += al16(sizeof(AreaQuery) * B1 * M1); q2 = o; o += al16(sizeof(AreaQuery) * B1 * M1);
+        qs1 = o; o += al16(4 * B1 * M1); qc1 = o; o += al16(4 * B1 * M1); qs2 = o; o += al16(4 * B1 * M1); qc2 = o; o += al16(4 * B1 * M1);
+        *o_extra = o; o += al16(extra);
+        res = o; res_bytes = 16 + al16(4 * B1) + 4 * B1 * 2 * C1; o += al16(res_bytes);
+        pool = o;
+    }
+};
+// grids of both cameras, then the window searches of both query sets into one entry pool (the right-coordinate gate off: a rig frame has no mvuRight)
+// queries(): the launch that writes both query sets (and zeroes the pool counter)
+template <typename Queries>
+void rig_searches(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, int M, const RigBlock& K, uint8_t* dp, const GridParams& g,
+                  const unsigned long long* qdesc, int qdesc_per_frame, size_t pool, const Queries& queries) {
+    const int cap = L->kp_total_cap;
+    const KeyPointRec* kps1 = L->d_kps.p + (size_t)lf * cap; const KeyPointRec* kps2 = R->d_kps.p + (size_t)rf * cap;
+    int* d_counter = (int*)(dp + K.res);
+    {
+        dim3 grid(B, 1, 1), blkg(kGridThreads, 1, 1);
+        ORBX_LAUNCH(k_grid_build, grid, blkg, 0, L->s0, kps1, 0, g, (int*)(dp + K.cof1), (int*)(dp + K.cst1), (int*)(dp + K.cit1), (const int*)(L->d_nm.p + lf), cap);
+        ORBX_LAUNCH(k_grid_build, grid, blkg, 0, L->s0, kps2, 0, g, (int*)(dp + K.cof2), (int*)(dp + K.cst2), (int*)(dp + K.cit2), (const int*)(R->d_nm.p + rf), cap);
+    }
+    if (M <= 0) { rt::memset_async(d_counter, 0, 16, L->s0); return; }
+    queries();
+    const float* no_ur = (const float*)dp;                       // never read: gate_right = 0
+    dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
+    ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, L->s0, (const AreaQuery*)(dp + K.q1), qdesc, M, kps1, no_ur, L->d_desc.p + (size_t)lf * cap * 4, g,
+                (const int*)(dp + K.cst1), (const int*)(dp + K.cit1), 0, d_counter, (int)pool, (int*)(dp + K.qs1), (int*)(dp + K.qc1), (int2*)(dp + K.pool), cap, qdesc_per_frame);
+    ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, L->s0, (const AreaQuery*)(dp + K.q2), qdesc, M, kps2, no_ur, R->d_desc.p + (size_t)rf * cap * 4, g,
+                (const int*)(dp + K.cst2), (const int*)(dp + K.cit2), 0, d_counter, (int)pool, (int*)(dp + K.qs2), (int*)(dp + K.qc2), (int2*)(dp + K.pool), cap, qdesc_per_frame);
+}
+GridParams rig_grid(const OrbmFrustumView& v) {
+    GridParams g; memset(&g, 0, sizeof g);
+    g.min_x = v.min_x; g.min_y = v.min_y;
+    g.gw_inv = (float)kGridColsHost / (v.max_x - v.min_x); g.gh_inv = (float)kGridRowsHost / (v.max_y - v.min_y);   // src/Frame.cc:190-191
+    return g;
+}
+size_t rig_accept_lds(int cap, int events) { const size_t S = 2 * (size_t)cap; return 4 * S + al16(S) + 4 * (size_t)events + 64; }
+}  // namespace
+extern "C" {
+
+int orbm_search_local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* frames, const orbm_points* points,
+                                       const uint8_t* is_bad, const uint8_t* has_obs, const uint8_t* occupied, float cos_limit, float th, int far_points,
+                                       float th_far, float nnratio, int want_in_view) {
+    if (L) { L->lp_B = 0; L->lp_rig = false; }                     // a new enqueue ends the previous batch; a refused one leaves nothing to fetch
+    if (!L || !frames || !points) return fail(ORBX_E_ARG, "null");
+    int rc = rig_pair_check(L, lf, R, rf, B); if (rc) return rc;
+    if ((rc = rig_frames_check(frames, B))) return rc;
+    if (points->device != L->device) return fail(ORBX_E_ARG, "map points live on another device");
+    rt::set_device(L->device);
+    const int M = points->M, cap = L->kp_total_cap;
+    const size_t B1 = B, M1 = M > 0 ? M : 1, C1 = cap, S1 = 2 * C1;
+    const size_t smem_accept = rig_accept_lds(cap, 0);
+    if (smem_accept + 1024 > rt::lds_limit(L->device)) return fail(ORBX_E_CAPACITY, "%d keypoints per camera need %zu bytes of LDS in the rig accept kernel", cap, smem_accept);
+    if (L->lp_pending) rt::event_sync(L->ev_lp);               // the staging block of the previous enqueue has been consumed
+    // upload: [camera 1, camera 2] parameters per frame | bad flags | has-observation flags | occupancy [B][2 cap]
+    const size_t u_f = 0, u_bad = u_f + al16(sizeof(FrustumParams) * 2 * B1), u_obs = u_bad + al16(M1), u_occ = u_obs + al16(M1), u_total = u_occ + (occupied ? al16(B1 * S1) : 0);
+    // behind the common block: per camera track [B][5 M] | level [B][M] | in_view [B][M]
+    const size_t o_trk1 = 0, o_trk2 = al16(20 * B1 * M1), o_lvl1 = 2 * o_trk2, o_lvl2 = o_lvl1 + al16(4 * B1 * M1), o_view1 = o_lvl2 + al16(4 * B1 * M1),
+                 o_view2 = o_view1 + al16(B1 * M1), track_total = o_view2 + al16(B1 * M1);
+    size_t ox = 0;
+    const RigBlock K(al16(u_total), B1, M1, C1, track_total, &ox);
+    size_t pool = std::max<size_t>(L->lp_pool, B1 * M1 * 12 + 4096);
+    if (pool > 0x7fffffff / 2) pool = 0x7fffffff / 2;
+    if (L->d_lp.ensure(K.pool + pool * 8 + 64) || L->h_lp_in.ensure(u_total + 16) || L->h_lp_out.ensure(al16(K.res_bytes) + (want_in_view ? 2 * B1 * M1 : 0) + 64))
+        return fail(ORBX_E_DEVICE, "allocation failed (batched rig local point search, %d frames x %d points)", B, M);
+    L->lp_pool = pool;
+    uint8_t* hp = L->h_lp_in.p; uint8_t* dp = L->d_lp.p;
+    FrustumParams* Fp = (FrustumParams*)(hp + u_f);
+    for (int b = 0; b < B; b++) {
+        fill_frustum_params(&frames[b].left, cos_limit, th, far_points, th_far, &Fp[2 * b]); Fp[2 * b].rig_mode = 1;
+        right_camera_params(&frames[b], cos_limit, &Fp[2 * b + 1]);
+    }
+    if (is_bad) memcpy(hp + u_bad, is_bad, M1); else memset(hp + u_bad, 0, M1);
+    if (has_obs) memcpy(hp + u_obs, has_obs, M1); else memset(hp + u_obs, 1, M1);
+    if (occupied) memcpy(hp + u_occ, occupied, B1 * S1);
+    if (rt::copy_h2d(dp, hp, u_total, L->s0) || rt::event_record(L->ev_lp, L->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
+    L->lp_pending = true;
+    if (L != R) { record_done_if_pending(R); rt::stream_wait_event(L->s0, R->ev_done); }
+    uint8_t* dx = dp + ox;
+    if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][0], L->s0);
+    rig_searches(L, lf, R, rf, B, M, K, dp, rig_grid(frames[0].left), points->desc, 0, pool, [&]() {
+        dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
+        ORBX_LAUNCH(k_frustum_rig, grid, blk, 0, L->s0, (const FrustumParams*)(dp + u_f), M, points->pos, points->normal, points->min_d, points->max_d,
+                    (const uint8_t*)(dp + u_bad), dx + o_view1, dx + o_view2, (float*)(dx + o_trk1), (float*)(dx + o_trk2), (int*)(dx + o_lvl1), (int*)(dx + o_lvl2),
+                    (AreaQuery*)(dp + K.q1), (AreaQuery*)(dp + K.q2), (int*)(dp + K.res));
+    });
+    {
+        dim3 grid(B, 1, 1), blk(64, 1, 1);
+        ORBX_LAUNCH(k_rig_local_accept, grid, blk, smem_accept, L->s0, M, cap, (const int*)(L->d_nm.p + lf), (const int*)(R->d_nm.p + rf), (const int*)(dp + K.qs1),
+                    (const int*)(dp + K.qc1), (const int*)(dp + K.qs2), (const int*)(dp + K.qc2), (const int2*)(dp + K.pool),
+                    occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr, (const uint8_t*)(dp + u_obs), (const int*)L->d_l2r.p, (const int*)L->d_r2l.p,
+                    nnratio, TH_HIGH, (int*)(dp + K.res + 16 + al16(4 * B1)), (int*)(dp + K.res + 16));
+    }
+    if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][1], L->s0);
+    if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
+    L->lp_B = B; L->lp_M = M; L->lp_first = lf; L->lp_o_counter = K.res; L->lp_o_view = ox + o_view1; L->lp_o_view_r = ox + o_view2;
+    L->lp_want_view = want_in_view != 0; L->lp_rig = true;
+    return ORBX_OK;
+}
+
+int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* cur, const float* trl,
+                                                  const OrbmLastFrameBatch* last, float th, const uint8_t* forward, const uint8_t* backward, int check_ori,
+                                                  const uint8_t* occupied) {
+    if (L) { L->lp_B = 0; L->lp_rig = false; }
+    if (!L || !cur || !trl || !last) return fail(ORBX_E_ARG, "null");
+    if (last->cap_last <= 0 || !last->n || !last->pos || !last->valid || !last->octave || !last->angle || !last->desc) return fail(ORBX_E_ARG, "bad last-frame batch");
+    int rc = rig_pair_check(L, lf, R, rf, B); if (rc) return rc;
+    if ((rc = rig_frames_check(cur, B))) return rc;
+    const int M = last->cap_last, cap = L->kp_total_cap;
+    for (int b = 0; b < B; b++) if (last->n[b] < 0 || last->n[b] > M) return fail(ORBX_E_ARG, "frame %d: %d points in %d rows", b, last->n[b], M);
+    rt::set_device(L->device);
+    const size_t B1 = B, M1 = M, C1 = cap, S1 = 2 * C1;
+    const size_t smem_accept = rig_accept_lds(cap, 2 * M);     // grows with cap_last: checked before anything is enqueued
+    if (smem_accept + 1024 > rt::lds_limit(L->device))
+        return fail(ORBX_E_CAPACITY, "%d keypoints per camera and %d last-frame points per frame need %zu bytes of LDS in the rig accept kernel", cap, M, smem_accept);
+    if (L->lp_pending) rt::event_sync(L->ev_lp);
+    // upload: camera-1 parameters per frame | n_last | pos | valid | octave | angle | has_obs | descriptors | occupancy [B][2 cap]
+    const size_t u_f = 0, u_n = u_f + al16(sizeof(FrustumParams) * B1), u_pos = u_n + al16(4 * B1), u_val = u_pos + al16(12 * B1 * M1), u_oct = u_val + al16(B1 * M1),
+                 u_ang = u_oct + al16(4 * B1 * M1), u_obs = u_ang + al16(4 * B1 * M1), u_desc = u_obs + al16(B1 * M1), u_occ = u_desc + al16(32 * B1 * M1),
+                 u_total = u_occ + (occupied ? al16(B1 * S1) : 0);
+    size_t ox = 0;
+    const RigBlock K(al16(u_total), B1, M1, C1, 0, &ox);
+    size_t pool = std::max<size_t>(L->lp_pool, B1 * M1 * 32 + 4096);          // th = 7 .. 15 px windows, two cameras
+    if (pool > 0x7fffffff / 2) pool = 0x7fffffff / 2;
+    if (L->d_lp.ensure(K.pool + pool * 8 + 64) || L->h_lp_in.ensure(u_total + 16) || L->h_lp_out.ensure(al16(K.res_bytes) + 64))
+        return fail(ORBX_E_DEVICE, "allocation failed (batched rig last-frame search, %d frames x %d points)", B, M);
+    L->lp_pool = pool;
+    uint8_t* hp = L->h_lp_in.p; uint8_t* dp = L->d_lp.p;
+    FrustumParams* Fp = (FrustumParams*)(hp + u_f);
+    for (int b = 0; b < B; b++) {
+        fill_frustum_params(&cur[b].left, 0.0f, th, 0, 0.0f, &Fp[b]);
+        Fp[b].forward = forward ? forward[b] != 0 : 0; Fp[b].backward = backward ? backward[b] != 0 : 0; Fp[b].debug_flags = L->debug_stereo_flags;
+    }
+    memcpy(hp + u_n, last->n, 4 * B1); memcpy(hp + u_pos, last->pos, 12 * B1 * M1); memcpy(hp + u_val, last->valid, B1 * M1);
+    memcpy(hp + u_oct, last->octave, 4 * B1 * M1); memcpy(hp + u_ang, last->angle, 4 * B1 * M1);
+    if (last->has_obs) memcpy(hp + u_obs, last->has_obs, B1 * M1); else memset(hp + u_obs, 1, B1 * M1);
+    memcpy(hp + u_desc, last->desc, 32 * B1 * M1);
+    if (occupied) memcpy(hp + u_occ, occupied, B1 * S1);
+    if (rt::copy_h2d(dp, hp, u_total, L->s0) || rt::event_record(L->ev_lp, L->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
+    L->lp_pending = true;
+    if (L != R) { record_done_if_pending(R); rt::stream_wait_event(L->s0, R->ev_done); }
+    RigRelPose T; memcpy(T.q, trl, sizeof T.q); memcpy(T.t, trl + 4, sizeof T.t);
+    if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][0], L->s0);
+    rig_searches(L, lf, R, rf, B, M, K, dp, rig_grid(cur[0].left), (const unsigned long long*)(dp + u_desc), 1, pool, [&]() {
+        dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
+        ORBX_LAUNCH(k_lastframe_queries_rig, grid, blk, 0, L->s0, (const FrustumParams*)(dp + u_f), M, (const int*)(dp + u_n), (const float*)(dp + u_pos),
+                    (const uint8_t*)(dp + u_val), (const int*)(dp + u_oct), T, (AreaQuery*)(dp + K.q1), (AreaQuery*)(dp + K.q2), (int*)(dp + K.res));
+    });
+    {
+        dim3 grid(B, 1, 1), blk(64, 1, 1);
+        ORBX_LAUNCH(k_rig_lastframe_accept, grid, blk, smem_accept, L->s0, M, cap, (const int*)(L->d_nm.p + lf), (const int*)(R->d_nm.p + rf), (const int*)(dp + K.qs1),
+                    (const int*)(dp + K.qc1), (const int*)(dp + K.qs2), (const int*)(dp + K.qc2), (const int2*)(dp + K.pool),
+                    occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr, (const uint8_t*)(dp + u_obs), TH_HIGH, (int*)(dp + K.res + 16 + al16(4 * B1)),
+                    (int*)(dp + K.res + 16), (const float*)(dp + u_ang), (const KeyPointRec*)(L->d_kps.p + (size_t)lf * cap), (const KeyPointRec*)(R->d_kps.p + (size_t)rf * cap),
+                    check_ori);
+    }
+    if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][1], L->s0);
+    if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
+    L->lp_B = B; L->lp_M = M; L->lp_first = lf; L->lp_o_counter = K.res; L->lp_o_view = 0; L->lp_o_view_r = 0; L->lp_want_view = false; L->lp_rig = true;
+    return ORBX_OK;
+}
+
+int orbm_search_rig_batch_fetch(orbx_extractor* L, int* assigned, int cap, int* nmatches, uint8_t* in_view, uint8_t* in_view_r) {
+    if (!L || L->lp_B <= 0 || !L->lp_rig) return fail(ORBX_E_ARG, "no batched rig search is pending");
+    if (assigned && cap < 2 * L->kp_total_cap) return fail(ORBX_E_ARG, "assigned rows need %d entries (2 x orbx_max_keypoints)", 2 * L->kp_total_cap);
+    if ((in_view || in_view_r) && !L->lp_want_view) return fail(ORBX_E_ARG, "in_view was not requested at enqueue time");
+    rt::set_device(L->device);
+    const size_t B1 = L->lp_B, M1 = L->lp_M > 0 ? L->lp_M : 0, S1 = 2 * (size_t)L->kp_total_cap;
+    const size_t res_bytes = 16 + al16(4 * B1) + 4 * B1 * S1;
+    uint8_t* hp = L->h_lp_out.p;
+    int e = rt::copy_d2h(hp, L->d_lp.p + L->lp_o_counter, res_bytes, L->s0);
+    if (L->lp_want_view && M1 > 0) {
+        e |= rt::copy_d2h(hp + al16(res_bytes), L->d_lp.p + L->lp_o_view, B1 * M1, L->s0);
+        e |= rt::copy_d2h(hp + al16(res_bytes) + B1 * M1, L->d_lp.p + L->lp_o_view_r, B1 * M1, L->s0);
+    }
+    if (e || rt::stream_sync(L->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "batched rig search failed: %s", rt::last_error());
+    L->lp_pending = false;
+    if (L->profile) L->stage_ms[ST_MATCH] = rt::event_elapsed_ms(L->ev_stage[ST_MATCH][0], L->ev_stage[ST_MATCH][1]);
+    const int total = *(const int*)hp;
+    if (L->lp_M > 0 && (size_t)total > L->lp_pool) {               // the candidate pool was too small: the caller enqueues again (the pool has grown)
+        L->lp_pool = (size_t)total + (size_t)total / 8 + 4096;
+        return fail(ORBX_E_CAPACITY, "candidate pool overflow (%d entries): enqueue the search again, the pool has been enlarged", total);
+    }
+    if (nmatches) memcpy(nmatches, hp + 16, 4 * B1);
+    if (assigned) {
+        const int* src = (const int*)(hp + 16 + al16(4 * B1));
+        for (size_t b = 0; b < B1; b++) memcpy(assigned + b * (size_t)cap, src + b * S1, 4 * S1);
+    }
+    if (M1 > 0) {
+        if (in_view) memcpy(in_view, hp + al16(res_bytes), B1 * M1);
+        if (in_view_r) memcpy(in_view_r, hp + al16(res_bytes) + B1 * M1, B1 * M1);
+    }
     return ORBX_OK;
 }
 

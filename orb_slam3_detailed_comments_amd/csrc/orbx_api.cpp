@@ -1171,6 +1171,7 @@ int orbm_knn2(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B) {
 // Frame::ComputeStereoFishEyeMatches (src/Frame.cc:1530-1587) for B fisheye pairs: 2-NN + ratio test (k_knn2), then the triangulation gate
 // KannalaBrandt8::TriangulateMatches (src/CameraModels/KannalaBrandt8.cpp:439-523) on the device.
 int orbm_stereo_fisheye(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmKB8Stereo* S) {
+    if (L) L->fe_B = 0;                                    // the links are being replaced: until this call succeeds they describe no frames
     if (!S) return fail(ORBX_E_ARG, "null camera parameters");
     int rc = orbm_knn2(L, lf, R, rf, B); if (rc) return rc;
     const int cap = L->kp_total_cap; const size_t bc = (size_t)L->maxB * cap;
@@ -1188,6 +1189,8 @@ int orbm_stereo_fisheye(orbx_extractor* L, int lf, orbx_extractor* R, int rf, in
                 L->d_l2r.p, L->d_r2l.p, L->d_depth.p, L->d_p3d.p, L->d_nmatch.p);
     if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][1], L->s0);
     if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
+    // what the links describe, for the rig batch searches that read them in place (orbm_search_local_points_rig_batch, ..._lastframe_rig_batch)
+    L->fe_R = R; L->fe_lf = lf; L->fe_rf = rf; L->fe_B = B; L->fe_gen_L = L->extract_gen; L->fe_gen_R = R->extract_gen;
     return ORBX_OK;
 }
 

@@ -123,6 +123,9 @@ struct orbx_extractor {
     // batched SearchLocalPoints (orbm_search_local_points_batch): one device block, one pinned result block, the size of the last enqueue
     orbx::DevBuf<uint8_t> d_lp, d_depth_in; orbx::HostBuf<uint8_t> h_lp_in, h_lp_out;
     size_t lp_pool = 0; int lp_B = 0, lp_M = 0, lp_first = 0; size_t lp_o_counter = 0, lp_o_view = 0; bool lp_pending = false, lp_want_view = false;
+    bool lp_rig = false; size_t lp_o_view_r = 0;     // the pending batch is a rig batch (orbm_search_rig_batch_fetch; [B][2 cap] assignments, mbTrackInViewR)
+    // the last orbm_stereo_fisheye with this handle on the left: the right handle, frames and extractions that d_l2r / d_r2l describe (fe_B == 0: none)
+    const orbx_extractor* fe_R = nullptr; int fe_lf = 0, fe_rf = 0, fe_B = 0; uint64_t fe_gen_L = 0, fe_gen_R = 0;
     orbx::rt::event_t ev_lp = 0;
     // Frame::UndistortKeyPoints on the device (orbx_set_undistort): mvKeysUn of the last batch
     orbx::UndistortParams undist = {}; int undist_gen = 0, g_undist_gen = 0; orbx::DevBuf<orbx::KeyPointRec> d_kps_un;

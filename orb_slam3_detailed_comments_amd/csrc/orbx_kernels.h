@@ -155,6 +155,22 @@ __global__ void k_lastframe_accept(int M, int cap, const int* __restrict__ n_per
 __global__ void k_local_accept(int M, int cap, const int* __restrict__ n_per_frame, const int* __restrict__ q_start, const int* __restrict__ q_count,
                                const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0, const uint8_t* __restrict__ has_obs, float nnratio,
                                int th_high, int* __restrict__ assigned, int* __restrict__ nmatches);
+__global__ void k_frustum_rig(const FrustumParams* __restrict__ Fb, int M, const float* __restrict__ pos, const float* __restrict__ normal,
+                              const float* __restrict__ min_dist, const float* __restrict__ max_dist, const uint8_t* __restrict__ is_bad,
+                              uint8_t* in_view1, uint8_t* in_view2, float* track1, float* track2, int* level1, int* level2,
+                              AreaQuery* __restrict__ q1, AreaQuery* __restrict__ q2, int* __restrict__ zero4);
+__global__ void k_lastframe_queries_rig(const FrustumParams* __restrict__ Fb, int capL, const int* __restrict__ n_last, const float* __restrict__ pos,
+                                        const uint8_t* __restrict__ valid, const int* __restrict__ octave, RigRelPose trl, AreaQuery* q1,
+                                        AreaQuery* __restrict__ q2, int* __restrict__ zero4);
+__global__ void k_rig_local_accept(int M, int cap, const int* __restrict__ n1, const int* __restrict__ n2, const int* __restrict__ qs1,
+                                   const int* __restrict__ qc1, const int* __restrict__ qs2, const int* __restrict__ qc2, const int2* __restrict__ entries,
+                                   const uint8_t* __restrict__ occupied0, const uint8_t* __restrict__ has_obs, const int* __restrict__ l2r,
+                                   const int* __restrict__ r2l, float nnratio, int th_high, int* __restrict__ assigned, int* __restrict__ nmatches);
+__global__ void k_rig_lastframe_accept(int M, int cap, const int* __restrict__ n1, const int* __restrict__ n2, const int* __restrict__ qs1,
+                                       const int* __restrict__ qc1, const int* __restrict__ qs2, const int* __restrict__ qc2, const int2* __restrict__ entries,
+                                       const uint8_t* __restrict__ occupied0, const uint8_t* __restrict__ has_obs, int th_high, int* __restrict__ assigned,
+                                       int* __restrict__ nmatches, const float* __restrict__ last_angle, const KeyPointRec* __restrict__ kps1,
+                                       const KeyPointRec* __restrict__ kps2, int check_ori);
 __global__ void k_stereo_from_depth(const KeyPointRec* __restrict__ kps, const KeyPointRec* __restrict__ kps_un, const int* __restrict__ n_per_frame, int cap,
                                     const float* __restrict__ depth, int stride, size_t image_stride, int w, int h, float mbf, float* __restrict__ u_right,
                                     float* __restrict__ depth_out, int* __restrict__ n_valid);

@@ -95,6 +95,7 @@ struct ProjectParams {
     int distance_test, angle_test;
     float bf;
 };
+struct RigRelPose { float q[4], t[3]; };                          // mTrl of a two-camera Frame: unit quaternion coeffs (x, y, z, w), translation
 struct VocSlot { int node_id, child_start, child_cnt, word_id; };   // one vocabulary node; children occupy consecutive slots
 // Key frame database (orbv_db_*): where the BowVectors of queries sit - query q's sorted word ids / values at ids + start[q] (start == nullptr:
 // q * stride), its word count at n[q * n_step] (a host CSR, or the results of the vocabulary transform left on the device)

@@ -287,6 +287,24 @@ class _TrackOutRight(C.Structure):
     _fields_ = [("in_view_r", C.c_void_p), ("proj_xr", C.c_void_p), ("proj_yr", C.c_void_p), ("depth_r", C.c_void_p), ("view_cos_r", C.c_void_p), ("scale_level_r", C.c_void_p)]
 
 
+def rig_frustum_view(pose, cam1, cam2, bounds, scale_factors, into=None):
+    """OrbmFrustumRigView of one rig frame: pose = dict(Rcw, tcw, Ow, Rwc, Rrl, trl, tlr) exactly as the Frame holds them (camera 1 takes Rcw / tcw /
+    Ow untouched; camera 2 is derived on the device), cam1 / cam2 = the two cameras' parameters.  Returns (view, the float32 scale-factor array the
+    view points into - keep it alive)."""
+    f32 = lambda a: np.ascontiguousarray(a, np.float32)
+    sf = f32(scale_factors)
+    V = into if into is not None else _FrustumRigView()
+    frustum_view(SE3f(), None, cam1, bounds, 0.0, sf, into=V.left)
+    V.left.Rcw[:] = f32(pose["Rcw"]).ravel().tolist(); V.left.tcw[:] = f32(pose["tcw"]).tolist()       # the Frame's own members, untouched
+    V.left.Ow[:] = [float(v) for v in f32(pose["Ow"])]
+    V.left.scale_factors = sf.ctypes.data
+    V.Rrl[:] = f32(pose["Rrl"]).ravel().tolist(); V.trl[:] = f32(pose["trl"]).tolist(); V.tlr[:] = f32(pose["tlr"]).tolist(); V.Rwc[:] = f32(pose["Rwc"]).ravel().tolist()
+    cam2 = [float(v) for v in cam2]
+    V.camera2_type = 1 if len(cam2) == 8 else 0
+    V.cam2[:] = cam2 + [0.0] * (8 - len(cam2))
+    return V, sf
+
+
 def SearchLocalPointsRig(ext, frame2, pose, cam1, cam2, bounds, scale_factors, pos, normal, min_distance, max_distance, is_bad=None, has_obs=None, desc=None,
                          viewing_cos_limit=0.5, th=1.0, far_points=False, th_far=50.0, nnratio=0.8, search=True):
     """Tracking::SearchLocalPoints for a two-camera (fisheye rig) frame: Frame::isInFrustum with Nleft != -1 (src/Frame.cc:754-766 ->
@@ -296,15 +314,7 @@ def SearchLocalPointsRig(ext, frame2, pose, cam1, cam2, bounds, scale_factors, p
     f32 = lambda a: np.ascontiguousarray(a, np.float32)
     pos, normal, mn, mx, sf = f32(pos).reshape(-1, 3), f32(normal).reshape(-1, 3), f32(min_distance), f32(max_distance), f32(scale_factors)
     M = len(pos)
-    V = _FrustumRigView()
-    frustum_view(SE3f(), None, cam1, bounds, 0.0, sf, into=V.left)
-    V.left.Rcw[:] = f32(pose["Rcw"]).ravel().tolist(); V.left.tcw[:] = f32(pose["tcw"]).tolist()       # the Frame's own members, untouched
-    V.left.Ow[:] = [float(v) for v in f32(pose["Ow"])]
-    V.left.scale_factors = sf.ctypes.data
-    V.Rrl[:] = f32(pose["Rrl"]).ravel().tolist(); V.trl[:] = f32(pose["trl"]).tolist(); V.tlr[:] = f32(pose["tlr"]).tolist(); V.Rwc[:] = f32(pose["Rwc"]).ravel().tolist()
-    cam2 = [float(v) for v in cam2]
-    V.camera2_type = 1 if len(cam2) == 8 else 0
-    V.cam2[:] = cam2 + [0.0] * (8 - len(cam2))
+    V, sf = rig_frustum_view(pose, cam1, cam2, bounds, sf)
     P = _WorldPointView()
     bad = None if is_bad is None else np.ascontiguousarray(is_bad, np.uint8); obs = None if has_obs is None else np.ascontiguousarray(has_obs, np.uint8)
     d = None if desc is None else np.ascontiguousarray(desc, np.uint8)
@@ -554,6 +564,97 @@ class LocalPointsBatch:
             rc = L.L.orbm_search_local_points_fetch(self.ext._h, self.assigned.ctypes.data, self.cap, self.nm.ctypes.data, self.in_view.ctypes.data if self._want else None)
         L.check(rc)
         return self.assigned, self.nm, (self.in_view if self._want else None)
+
+
+class LocalPointsRigBatch:
+    """Tracking::SearchLocalPoints for a batch of rig frames that stay on the device (orbm_search_local_points_rig_batch): frame b = left image
+    left_first + b of `left`'s last extraction and right image right_first + b of `right`'s (right_first defaults to B when both are one handle,
+    the layout [L0 .. L(B-1), R0 .. R(B-1)], else to 0), linked by the last ComputeStereoFishEyeMatches over exactly these frames; the local map is a
+    ResidentPoints.  set_poses() takes B pose dicts as SearchLocalPointsRig does.  enqueue() is asynchronous, fetch() returns (assigned [B, 2 cap]
+    in the slot layout of F.mvpMapPoints, nmatches [B], in_view [B, M] or None, in_view_r [B, M] or None)."""
+
+    def __init__(self, left, right, resident, B, cam1, cam2, bounds, scale_factors, left_first=0, right_first=None):
+        self.ext, self.right, self.res, self.B = left, right, resident, B
+        self.lf, self.rf = int(left_first), int((B if right is left else 0) if right_first is None else right_first)
+        self.cam1, self.cam2, self.bounds = cam1, cam2, bounds
+        self.sf = np.ascontiguousarray(scale_factors, np.float32)
+        self.views = (_FrustumRigView * B)()
+        self.cap = 2 * left.max_keypoints()
+        self.assigned = np.full((B, self.cap), -1, np.int32); self.nm = np.zeros(B, np.int32)
+        self.in_view = np.zeros((B, max(resident.M, 1)), np.uint8); self.in_view_r = np.zeros((B, max(resident.M, 1)), np.uint8)
+
+    def set_poses(self, poses):
+        for b, pose in enumerate(poses):
+            rig_frustum_view(pose, self.cam1, self.cam2, self.bounds, self.sf, into=self.views[b])
+
+    def enqueue(self, is_bad=None, has_obs=None, occupied=None, viewing_cos_limit=0.5, th=1.0, far_points=False, th_far=50.0, nnratio=0.8, want_in_view=False):
+        L = self.ext._lib
+        u8 = lambda a: None if a is None else np.ascontiguousarray(a, np.uint8)
+        self._again = lambda: self.enqueue(is_bad, has_obs, occupied, viewing_cos_limit, th, far_points, th_far, nnratio, want_in_view)
+        self._keep = (u8(is_bad), u8(has_obs), u8(occupied))
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._want = bool(want_in_view)
+        L.check(L.L.orbm_search_local_points_rig_batch(self.ext._h, self.lf, self.right._h, self.rf, self.B, self.views, self.res._p, ptr(self._keep[0]),
+                                                       ptr(self._keep[1]), ptr(self._keep[2]), float(viewing_cos_limit), float(th), int(far_points), float(th_far),
+                                                       float(nnratio), int(self._want)))
+
+    def _fetch(self):
+        iv = lambda a: a.ctypes.data if self._want else None
+        return self.ext._lib.L.orbm_search_rig_batch_fetch(self.ext._h, self.assigned.ctypes.data, self.cap, self.nm.ctypes.data, iv(self.in_view), iv(self.in_view_r))
+
+    def fetch(self):
+        rc = self._fetch()
+        if rc == -4:                 # ORBX_E_CAPACITY: the candidate pool was too small for this scene and has been enlarged - run the batch again
+            self._again()
+            rc = self._fetch()
+        self.ext._lib.check(rc)
+        return self.assigned, self.nm, (self.in_view if self._want else None), (self.in_view_r if self._want else None)
+
+
+class LastFrameRigBatch:
+    """SearchByProjection(CurrentFrame, LastFrame, th, bMono) for a batch of rig frames on the device (orbm_search_by_projection_lastframe_rig_batch):
+    frames as LocalPointsRigBatch, per frame the map points of its last frame (rows indexed like LastFrame.mvpMapPoints).  set_poses(poses, Trl): B
+    camera-1 poses (SE3f or (R, t)) and the rig's mTrl; camera 2's projections are made on the device.  enqueue() is asynchronous, fetch() returns
+    (assigned [B, 2 cap], nmatches [B])."""
+
+    def __init__(self, left, right, B, cam1, bounds, scale_factors, left_first=0, right_first=None):
+        self.ext, self.right, self.B = left, right, B
+        self.lf, self.rf = int(left_first), int((B if right is left else 0) if right_first is None else right_first)
+        self.cam1, self.bounds = cam1, bounds
+        self.sf = np.ascontiguousarray(scale_factors, np.float32)
+        self.views = (_FrustumRigView * B)()
+        self.cap = 2 * left.max_keypoints()
+        self.assigned = np.full((B, self.cap), -1, np.int32); self.nm = np.zeros(B, np.int32)
+        self.trl = np.zeros(7, np.float32)
+
+    def set_poses(self, poses, Trl):
+        for b, pose in enumerate(poses):
+            frustum_view(as_se3(pose), None, self.cam1, self.bounds, 0.0, self.sf, into=self.views[b].left)
+            self.views[b].left.scale_factors = self.sf.ctypes.data
+        T = as_se3(Trl)
+        self.trl[:] = [float(v) for v in T.unit_quaternion()] + [float(v) for v in T.translation()]
+
+    def enqueue(self, n, pos, valid, octave, angle, has_obs, desc, th, forward=None, backward=None, check_orientation=True, occupied=None):
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        u8 = lambda a: None if a is None else np.ascontiguousarray(a, np.uint8)
+        self._again = lambda: self.enqueue(n, pos, valid, octave, angle, has_obs, desc, th, forward, backward, check_orientation, occupied)
+        pos = f32(pos); capL = pos.shape[1]
+        self._keep = (np.ascontiguousarray(n, np.int32), pos, u8(valid), np.ascontiguousarray(octave, np.int32), f32(angle), u8(has_obs), u8(desc), u8(forward), u8(backward), u8(occupied))
+        k = self._keep
+        ptr = lambda a: None if a is None else a.ctypes.data
+        lb = _LastFrameBatch(capL, ptr(k[0]), ptr(k[1]), ptr(k[2]), ptr(k[3]), ptr(k[4]), ptr(k[5]), ptr(k[6]))
+        L = self.ext._lib
+        L.check(L.L.orbm_search_by_projection_lastframe_rig_batch(self.ext._h, self.lf, self.right._h, self.rf, self.B, self.views, self.trl.ctypes.data, C.byref(lb),
+                                                                  float(th), ptr(k[7]), ptr(k[8]), int(bool(check_orientation)), ptr(k[9])))
+
+    def fetch(self):
+        L = self.ext._lib
+        rc = L.L.orbm_search_rig_batch_fetch(self.ext._h, self.assigned.ctypes.data, self.cap, self.nm.ctypes.data, None, None)
+        if rc == -4:                 # ORBX_E_CAPACITY: pool enlarged, run the batch again
+            self._again()
+            rc = L.L.orbm_search_rig_batch_fetch(self.ext._h, self.assigned.ctypes.data, self.cap, self.nm.ctypes.data, None, None)
+        L.check(rc)
+        return self.assigned, self.nm
 
 
 def SearchLocalPoints(ext, frame, Rcw, tcw, cam, bounds, mbf, scale_factors, pos, normal, min_distance, max_distance, is_bad=None, has_obs=None, desc=None,

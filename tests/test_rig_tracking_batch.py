@@ -1,0 +1,379 @@
+"""The batched tracking searches for two-camera (fisheye rig, Frame::Nleft != -1) frames: orbm_search_local_points_rig_batch
+(Tracking::SearchLocalPoints) and orbm_search_by_projection_lastframe_rig_batch (SearchByProjection(CurrentFrame, LastFrame) with its
+camera-2 branch), read where extraction and orbm_stereo_fisheye left the frames, with the two-camera accept loop on the device
+(k_frustum_rig / k_lastframe_queries_rig, k_area_search_threads per camera, k_rig_local_accept / k_rig_lastframe_accept).
+
+Bar, for every frame of a batch: assignments over both cameras, match counts, mbTrackInView / mbTrackInViewR identical to the reference's own
+Frame.cc + ORBmatcher.cc (oracle/_ref/libref_frame.so: ReferenceRigFrame; the oracle restatement of the LastFrame search) and to the
+single-frame product calls (orbm_search_local_points_fisheye, orbm_search_by_projection_frame_fisheye behind orbm_project_points, as the
+facade calls them).  Scenes with duplicated map points, stereo partners that collide, points without observations, bad points and occupied
+keypoints in both cameras; then the refusals and the one-pending-batch rule."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import oracle_lib as ol
+from orb_slam3_detailed_comments_amd import ORBextractor, sophus, views
+from orb_slam3_detailed_comments_amd import matcher as M
+from test_kb8 import CAM1, CAM2, MRLR, RLR, TLR, _fisheye_pair
+from test_local_points import _rot
+from test_local_points_rig import _kb8_unproject, _scene
+
+pytestmark = pytest.mark.skipif(ol.reference_frame_lib() is None, reason="oracle/_ref/libref_frame.so not built (needs /root/reference)")
+TRL = sophus.SE3f(RLR, TLR).inverse()          # mTrl = mTlr.inverse() (src/Frame.cc:1498-1501)
+E_ARG = -2
+
+
+class World:
+    """B rig frames over `nscenes` image pairs (frame b shows scene b % nscenes under its own pose), extracted and stereo-matched on the product
+    library: one handle holding [L0 .. L(B-1), R0 .. R(B-1)], or (two_handles) a left handle with one extra image in front and a right handle."""
+
+    def __init__(self, lib, w, h, nf, lap, B, nscenes, two_handles=False, seed=0):
+        self.lib, self.w, self.h, self.nf, self.B = lib, w, h, nf, B
+        self.rng = np.random.default_rng(4100 + B + 17 * seed + (5 if two_handles else 0))
+        pairs = [_fisheye_pair(60 + s + 11 * seed, w, h) for s in range(nscenes)]
+        self.refs = [ol.ReferenceRigFrame(L, R, lap, lap, nf, (CAM1, CAM2, RLR, TLR)) for L, R in pairs]
+        self.scene = [b % nscenes for b in range(B)]
+        Ls = [pairs[s][0] for s in self.scene]; Rs = [pairs[s][1] for s in self.scene]
+        if two_handles:
+            self.exL = ORBextractor(nf, 1.2, 8, 20, 7, lib=lib); self.exR = ORBextractor(nf, 1.2, 8, 20, 7, lib=lib)
+            resL = self.exL.extract_batch(np.stack([pairs[-1][1]] + Ls), lap)[1:]
+            resR = self.exR.extract_batch(np.stack(Rs), lap)
+            self.lf, self.rf = 1, 0
+        else:
+            self.exL = self.exR = ORBextractor(nf, 1.2, 8, 20, 7, lib=lib)
+            res = self.exL.extract_batch(np.stack(Ls + Rs), lap)
+            resL, resR = res[:B], res[B:]
+            self.lf, self.rf = 0, B
+        st = M.ComputeStereoFishEyeMatches(self.exL, self.exR, CAM1, CAM2, MRLR, TLR, self.lf, self.rf, B)
+        self.kL = [r[1] for r in resL]; self.dL = [r[2] for r in resL]; self.kR = [r[1] for r in resR]; self.dR = [r[2] for r in resR]
+        self.l2r, self.r2l = [], []
+        for b in range(B):
+            F = self.refs[self.scene[b]]
+            assert self.kL[b].tobytes() == F.keys.tobytes() and self.kR[b].tobytes() == F.keys_right.tobytes()
+            assert np.array_equal(st["l2r"][b, :F.nl], F.l2r) and np.array_equal(st["r2l"][b, :F.nr], F.r2l)
+            self.l2r.append(F.l2r); self.r2l.append(F.r2l)
+        self.sfs = self.exL.GetScaleFactors()
+        self.cap = self.exL.max_keypoints()
+        self.bounds = (0.0, float(w), 0.0, float(h))
+        base = [(_rot(*(self.rng.normal(0, 0.015, 3))), self.rng.normal(0, 0.1, 3).astype(np.float32)) for _ in range(nscenes)]
+        self.base = base
+        self.poses = [base[s] if b < nscenes else (_rot(*(self.rng.normal(0, 0.003, 3))) @ base[s][0], (base[s][1] + self.rng.normal(0, 0.01, 3)).astype(np.float32))
+                      for b, s in enumerate(self.scene)]
+
+    def n(self, b):
+        F = self.refs[self.scene[b]]
+        return F.nl, F.nr
+
+    def frame2(self, b, occupied=None):
+        nl, nr = self.n(b)
+        o = (None, None) if occupied is None else (occupied[b, :nl], occupied[b, nl:nl + nr])
+        left = views.frame_view(self.kL[b], self.dL[b], self.sfs, self.w, self.h, occupied=o[0])
+        right = views.frame_view(self.kR[b], self.dR[b], self.sfs, self.w, self.h, occupied=o[1])
+        return views.fisheye_frame_view(left, right, self.l2r[b], self.r2l[b])
+
+    def occupied(self):
+        occ = np.zeros((self.B, 2 * self.cap), np.uint8)
+        for b in range(self.B):
+            nl, nr = self.n(b)
+            occ[b, self.rng.choice(nl, nl // 8, replace=False)] = 1
+            occ[b, nl + self.rng.choice(nr, nr // 8, replace=False)] = 1
+        return occ
+
+    def close(self):
+        self.exL.close()
+        if self.exR is not self.exL:
+            self.exR.close()
+
+
+def _map_points(W, npts):
+    """points of every scene (test_local_points_rig._scene) + contention: duplicates inside and across groups of 64, and stereo pairs (a, l2r[a])
+    offered to both cameras by two points, the camera-1 one first and the other way round"""
+    rng = W.rng
+    per = npts // len(W.refs)
+    parts = [_scene(W.refs[s], rng, W.base[s][0], W.base[s][1], per) for s in range(len(W.refs))]
+    pos, normal, mind, maxd, bad, obs, desc = [np.concatenate([p[k] for p in parts]) for k in range(7)]
+    F = W.refs[0]; R, t = W.base[0]
+    Rw, tw = R.astype(np.float64), t.astype(np.float64)
+    stereo = np.nonzero(F.l2r >= 0)[0]
+    for a in rng.choice(stereo, min(len(stereo), max(8, npts // 60)), replace=False):
+        c = int(F.l2r[a])
+        z = rng.uniform(1.0, 6.0)
+        Xc = _kb8_unproject(CAM1, np.array([F.keys["x"][a]]), np.array([F.keys["y"][a]]))[0] * z
+        Xw = Rw.T @ (Xc - tw)
+        d = np.linalg.norm(Xw + Rw.T @ tw)
+        i = int(rng.integers(0, len(pos) - 70))
+        gap = int(rng.choice([1, 3, 70 % (len(pos) - i) or 1]))
+        first_left = rng.uniform() < 0.5
+        for k, src in ((i, a if first_left else F.nl + c), (i + gap, F.nl + c if first_left else a)):
+            pos[k] = Xw; normal[k] = (Xw + Rw.T @ tw) / d; maxd[k] = d * 1.2 ** 3; mind[k] = maxd[k] / 1.2 ** 7
+            desc[k] = F.desc[src]; bad[k] = False; obs[k] = True
+    dups = []
+    for i in rng.choice(len(pos) - 70, len(pos) // 6, replace=False):
+        j = int(i + rng.choice([1, 2, 5, 63, 64, 65]))
+        pos[j] = pos[i]; normal[j] = normal[i]; mind[j] = mind[i]; maxd[j] = maxd[i]; desc[j] = desc[i]
+        if rng.uniform() < 0.3:
+            desc[j, int(rng.integers(0, 32))] ^= np.uint8(1 << int(rng.integers(0, 8)))
+        dups.append(j)
+    return pos, normal, mind, maxd, bad, obs, desc, np.array(sorted(set(dups)))
+
+
+def _check_local(W, npts, params=((1.0, False), (3.0, True)), with_occupied=True):
+    ex = W.exL
+    pos, normal, mind, maxd, bad, obs, desc, dups = _map_points(W, npts)
+    rp = M.ResidentPoints(ex, pos, normal, mind, maxd, desc)
+    lp = M.LocalPointsRigBatch(W.exL, W.exR, rp, W.B, CAM1, CAM2, W.bounds, W.sfs, W.lf, W.rf)
+    collided = False
+    poses = None
+    for th, far in params:
+        refs = [W.refs[W.scene[b]].search_local_points(W.poses[b][0], W.poses[b][1], pos, normal, mind, maxd, bad, obs, desc, 0.5, True, th, far, 9.0, 0.8)
+                for b in range(W.B)]
+        poses = [r[4] for r in refs]
+        lp.set_poses(poses)
+        lp.enqueue(is_bad=bad, has_obs=obs, th=th, far_points=far, th_far=9.0, nnratio=0.8, want_in_view=True)
+        asg, nm, iv, ivr = lp.fetch()
+        total = 0
+        for b in range(W.B):
+            rl, rr, ref_as, ref_n, pose = refs[b]
+            nl, nr = W.n(b)
+            assert np.array_equal(iv[b].astype(bool), rl["in_view"]) and np.array_equal(ivr[b].astype(bool), rr["in_view_r"]), "mbTrackInView(R), frame %d" % b
+            assert nm[b] == ref_n and np.array_equal(asg[b, :nl + nr], ref_as), "frame %d (th %g): %d vs %d matches" % (b, th, nm[b], ref_n)
+            assert (asg[b, nl + nr:] == -1).all()
+            _, _, one_as, one_n = M.SearchLocalPointsRig(ex, W.frame2(b), pose, CAM1, CAM2, W.bounds, W.sfs, pos, normal, mind, maxd, bad, obs, desc, 0.5, th, far, 9.0, 0.8)
+            assert one_n == ref_n and np.array_equal(one_as, ref_as), "frame %d: single-frame call vs the reference" % b
+            total += ref_n
+            if not collided and b < 3:                          # the duplicates really compete: without them the result is another one
+                bad2 = bad.copy(); bad2[dups] = True
+                _, _, as2, _ = M.SearchLocalPointsRig(ex, W.frame2(b), pose, CAM1, CAM2, W.bounds, W.sfs, pos, normal, mind, maxd, bad2, obs, desc, 0.5, th, far, 9.0, 0.8)
+                keep = ~np.isin(ref_as, dups)
+                collided = not np.array_equal(as2[keep], ref_as[keep]) or not np.array_equal(as2 >= 0, ref_as >= 0)
+        assert total > W.B * npts // 40
+    assert collided
+    if with_occupied:                                           # occupied keypoints in both cameras: the single-frame call (pinned above) is the checker
+        occ = W.occupied()
+        lp.enqueue(is_bad=bad, has_obs=obs, occupied=occ, th=3.0, want_in_view=False)
+        asg, nm, iv, ivr = lp.fetch()
+        assert iv is None and ivr is None
+        for b in range(W.B):
+            nl, nr = W.n(b)
+            _, _, one_as, one_n = M.SearchLocalPointsRig(ex, W.frame2(b, occ), poses[b], CAM1, CAM2, W.bounds, W.sfs, pos, normal, mind, maxd, bad, obs, desc, 0.5, 3.0)
+            assert nm[b] == one_n and np.array_equal(asg[b, :nl + nr], one_as), "frame %d with occupied keypoints" % b
+    rp.close()
+
+
+def _last_frames(W):
+    """per frame, its last frame's map points: on the rays of the current frame's left AND right keypoints (rows indexed like mvpMapPoints),
+    valid / octave / angle / observations / descriptors perturbed, rotated pairs, duplicates inside and across groups of 64"""
+    rng = W.rng
+    capL = 2 * W.cap + 3
+    B = W.B
+    n = np.zeros(B, np.int32); pos = np.zeros((B, capL, 3), np.float32); valid = np.zeros((B, capL), np.uint8); octave = np.zeros((B, capL), np.int32)
+    angle = np.zeros((B, capL), np.float32); has_obs = np.ones((B, capL), np.uint8); desc = np.zeros((B, capL, 32), np.uint8)
+    Tlr = sophus.SE3f(RLR, TLR)
+    Rlr, tlr = Tlr.rotationMatrix().astype(np.float64), np.asarray(Tlr.translation(), np.float64)
+    for b in range(B):
+        F = W.refs[W.scene[b]]
+        nl, nr = F.nl, F.nr; N = nl + nr; n[b] = N
+        R, t = W.poses[b]
+        k = np.concatenate([F.keys, F.keys_right])
+        z = rng.uniform(1.0, 8.0, N)
+        u = k["x"] + rng.normal(0, 0.7, N); v = k["y"] + rng.normal(0, 0.7, N)
+        XcL = _kb8_unproject(CAM1, u[:nl], v[:nl]) * z[:nl, None]
+        XcR = (Rlr @ (_kb8_unproject(CAM2, u[nl:], v[nl:]) * z[nl:, None]).T).T + tlr
+        Xc = np.concatenate([XcL, XcR])
+        pos[b, :N] = (R.astype(np.float64).T @ (Xc - t.astype(np.float64)).T).T
+        valid[b, :N] = rng.uniform(size=N) < 0.8
+        octave[b, :N] = np.clip(k["octave"] + rng.integers(-1, 2, N), 0, 7)
+        ang = k["angle"] + rng.normal(0, 4.0, N); ang[rng.uniform(size=N) < 0.15] += rng.uniform(40, 300)
+        angle[b, :N] = np.mod(ang, 360.0)
+        has_obs[b, :N] = rng.uniform(size=N) < 0.85
+        dd = F.desc.copy()
+        fl = rng.integers(0, 256, (N, 12))
+        for j in range(12):
+            dd[np.arange(N), fl[:, j] >> 3] ^= (1 << (fl[:, j] & 7)).astype(np.uint8)
+        desc[b, :N] = dd
+        for i in rng.choice(N - 70, N // 5, replace=False):
+            j = i + int(rng.choice([1, 2, 63, 64, 65]))
+            pos[b, j] = pos[b, i]; desc[b, j] = desc[b, i]; octave[b, j] = octave[b, i]; valid[b, j] = valid[b, i]
+    return n, pos, valid, octave, angle, has_obs, desc
+
+
+def _check_lastframe(W, runs=((1, 0, True), (0, 1, True), (0, 0, True), (0, 0, False)), th=7.0, with_oracle=True):
+    ex = W.exL
+    n, pos, valid, octave, angle, has_obs, desc = _last_frames(W)
+    lf = M.LastFrameRigBatch(W.exL, W.exR, W.B, CAM1, W.bounds, W.sfs, W.lf, W.rf)
+    lf.set_poses(W.poses, TRL)
+    occ = W.occupied()
+    resets, resets_right, total = 0, 0, 0
+    for fw, bw, ori in runs:
+        fwd = np.full(W.B, fw, np.uint8); bwd = np.full(W.B, bw, np.uint8)
+        use_occ = not (fw or bw) and ori
+        lf.enqueue(n, pos, valid, octave, angle, has_obs, desc, th, fwd, bwd, ori, occ if use_occ else None)
+        asg, nm = lf.fetch()
+        matcher = M.ORBmatcher(0.9, ori)
+        for b in range(W.B):
+            N = int(n[b]); nl, nr = W.n(b)
+            sk = 1 - valid[b, :N]
+            pr = M.ProjectPoints(ex, W.poses[b], CAM1, W.bounds, pos[b, :N], skip=sk, depth_test=2, bounds_mode=0)
+            p2 = M.ProjectPoints(ex, W.poses[b], CAM1, W.bounds, pos[b, :N], skip=sk, second=TRL, depth_test=0, bounds_mode=2)
+            last = views.last_frame_view(pr["valid"], pr["u"], pr["v"], pr["inv_z"], octave[b, :N], angle[b, :N], has_obs[b, :N], desc[b, :N])
+            cur2 = W.frame2(b, occ if use_occ else None)
+            one_n, one_as = matcher.SearchByProjectionFrameFisheye(ex, cur2, last, p2["u"], p2["v"], th, bool(fw), bool(bw))
+            assert nm[b] == one_n and np.array_equal(asg[b, :nl + nr], one_as), "frame %d (fw %d bw %d ori %d): %d vs %d" % (b, fw, bw, ori, nm[b], one_n)
+            assert (asg[b, nl + nr:] == -1).all()
+            if with_oracle:
+                o_n, o_as = ol.oracle_search_by_projection_frame_fisheye(cur2, last, p2["u"], p2["v"], th, fw, bw, ori)
+                assert o_n == one_n and np.array_equal(o_as, one_as), "frame %d: oracle" % b
+            total += one_n; resets += int((one_as == -2).sum()); resets_right += int((one_as[nl:] == -2).sum())
+    assert total > 50 * W.B * len(runs) and resets > 0 and resets_right > 0
+
+
+def test_rig_batch_local_points_emulated(emu_lib):
+    W = World(emu_lib, 376, 376, 500, (0, 375), 3, 2)
+    try:
+        _check_local(W, 1200)
+    finally:
+        W.close()
+
+
+def test_rig_batch_local_points_two_handles_emulated(emu_lib):
+    """frames from two handles, the left one with an image in front (lf = 1), and a lapping area over part of the image (feature order != FAST order)"""
+    W = World(emu_lib, 376, 376, 500, (40, 300), 3, 2, two_handles=True, seed=1)
+    try:
+        _check_local(W, 1000, params=((3.0, True),))
+    finally:
+        W.close()
+
+
+def test_rig_batch_lastframe_emulated(emu_lib):
+    W = World(emu_lib, 376, 376, 500, (0, 375), 3, 2)
+    try:
+        _check_lastframe(W)
+    finally:
+        W.close()
+
+
+def test_rig_batch_lastframe_two_handles_emulated(emu_lib):
+    W = World(emu_lib, 376, 376, 500, (40, 300), 3, 2, two_handles=True, seed=1)
+    try:
+        _check_lastframe(W, runs=((0, 0, True), (1, 0, False)))
+    finally:
+        W.close()
+
+
+def _fetch(lib, h, cap, B):
+    a = np.zeros((B, cap), np.int32); nm = np.zeros(B, np.int32)
+    return lib.L.orbm_search_rig_batch_fetch(h, a.ctypes.data, cap, nm.ctypes.data, None, None)
+
+
+def _live(lib):
+    a = (C.c_longlong * 4)()
+    lib.check(lib.L.orbx_debug_live_resources(a))
+    return list(a)
+
+
+def test_rig_batch_refusals_emulated(emu_lib):
+    lib = emu_lib
+    w = h = 320; nf = 300; lap = (0, 319); B = 2
+    pairs = [_fisheye_pair(70 + b, w, h) for b in range(B)]
+    live0 = _live(lib)
+    ex = ORBextractor(nf, 1.2, 8, 20, 7, lib=lib)
+    ex.extract_batch(np.stack([p[0] for p in pairs] + [p[1] for p in pairs]), lap)
+    cap2 = 2 * ex.max_keypoints()
+    sfs = ex.GetScaleFactors(); bounds = (0.0, float(w), 0.0, float(h))
+    rng = np.random.default_rng(5)
+    pos = rng.uniform(-2, 2, (50, 3)).astype(np.float32); pos[:, 2] += 4
+    normal = (pos / np.linalg.norm(pos, axis=1)[:, None]).astype(np.float32)
+    dist = np.linalg.norm(pos, axis=1).astype(np.float32)
+    rp = M.ResidentPoints(ex, pos, normal, dist / 3, dist * 2, rng.integers(0, 256, (50, 32), dtype=np.uint8))
+    pose = dict(Rcw=np.eye(3, dtype=np.float32), tcw=np.zeros(3, np.float32), Ow=np.zeros(3, np.float32), Rwc=np.eye(3, dtype=np.float32),
+                Rrl=TRL.rotationMatrix(), trl=np.asarray(TRL.translation(), np.float32), tlr=TLR)
+
+    def local(ext_l=ex, ext_r=ex, lf=0, rf=B, n=B, bounds_b=None):
+        views_ = (M._FrustumRigView * n)()
+        for b in range(n):
+            M.rig_frustum_view(pose, CAM1, CAM2, bounds if (bounds_b is None or b == 0) else bounds_b, sfs, into=views_[b])
+        return lib.L.orbm_search_local_points_rig_batch(ext_l._h, lf, ext_r._h, rf, n, views_, rp._p, None, None, None, 0.5, 1.0, 0, 0.0, 0.8, 0)
+
+    def nothing_pending():
+        return _fetch(lib, ex._h, cap2, B) == E_ARG
+
+    assert local() == E_ARG and nothing_pending()                                          # no orbm_stereo_fisheye yet
+    M.ComputeStereoFishEyeMatches(ex, ex, CAM1, CAM2, MRLR, TLR, 0, B, 1)
+    assert local() == E_ARG and nothing_pending()                                          # the call covered one pair only
+    M.ComputeStereoFishEyeMatches(ex, ex, CAM1, CAM2, MRLR, TLR, 0, B, B)
+    assert local() == 0 and _fetch(lib, ex._h, cap2, B) == 0                              # accepted
+    assert local(bounds_b=(0.0, float(w) - 1, 0.0, float(h))) == E_ARG and nothing_pending()      # other bounds in the batch
+    assert local(lf=1, rf=1) == E_ARG and nothing_pending()                               # other frames than the stereo call
+    assert local(lf=B + 1) == E_ARG and nothing_pending()                                 # lf + B beyond the extraction
+    # a small assigned row, the wrong fetch for the form of the pending batch
+    assert local() == 0
+    assert _fetch(lib, ex._h, cap2 - 1, B) == E_ARG
+    a = np.zeros((B, cap2), np.int32)
+    assert lib.L.orbm_search_local_points_fetch(ex._h, a.ctypes.data, cap2, None, None) == E_ARG
+    assert _fetch(lib, ex._h, cap2, B) == 0
+    # a pinhole batch after the rig batch: the rig fetch refuses it, the pinhole batch gives what it gives on a fresh handle
+    lpb = M.LocalPointsBatch(ex, rp, B, CAM1, bounds, 0.0, sfs)
+    lpb.set_poses([(np.eye(3, dtype=np.float32), np.zeros(3, np.float32))] * B)
+    lpb.enqueue(0, use_u_right=False, th=3.0)
+    assert _fetch(lib, ex._h, cap2, B) == E_ARG
+    asg1, nm1, _ = lpb.fetch(); asg1, nm1 = asg1.copy(), nm1.copy()
+    fresh = ORBextractor(nf, 1.2, 8, 20, 7, lib=lib)
+    fresh.extract_batch(np.stack([p[0] for p in pairs] + [p[1] for p in pairs]), lap)
+    lpb2 = M.LocalPointsBatch(fresh, rp, B, CAM1, bounds, 0.0, sfs)
+    lpb2.set_poses([(np.eye(3, dtype=np.float32), np.zeros(3, np.float32))] * B)
+    lpb2.enqueue(0, use_u_right=False, th=3.0)
+    asg2, nm2, _ = lpb2.fetch()
+    assert np.array_equal(asg1, asg2) and np.array_equal(nm1, nm2)
+    # an extraction after the stereo call
+    assert local() == 0 and _fetch(lib, ex._h, cap2, B) == 0
+    ex.extract_batch(np.stack([p[0] for p in pairs] + [p[1] for p in pairs]), lap)
+    assert local() == E_ARG and nothing_pending()
+    # two handles with different feature counts
+    other = ORBextractor(nf + 100, 1.2, 8, 20, 7, lib=lib)
+    other.extract_batch(np.stack([p[1] for p in pairs]), lap)
+    M.ComputeStereoFishEyeMatches(ex, ex, CAM1, CAM2, MRLR, TLR, 0, B, B)
+    assert local(ext_r=other, rf=0) == E_ARG and nothing_pending()
+    # the last-frame form refuses alike, and leaves nothing
+    last = M.LastFrameRigBatch(ex, other, B, CAM1, bounds, sfs, 0, 0)
+    last.set_poses([(np.eye(3, dtype=np.float32), np.zeros(3, np.float32))] * B, TRL)
+    z = np.zeros((B, 4), np.float32)
+    with pytest.raises(Exception):
+        last.enqueue(np.zeros(B, np.int32), np.zeros((B, 4, 3), np.float32), np.zeros((B, 4), np.uint8), np.zeros((B, 4), np.int32), z, None,
+                     np.zeros((B, 4, 32), np.uint8), 7.0)
+    assert nothing_pending()
+    for o in (other, fresh):
+        o.close()
+    rp.close(); ex.close()
+    assert _live(lib) == live0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", [8, 64])
+def test_rig_batch_local_points_gpu(hip_lib, B):
+    W = World(hip_lib, 512, 512, 1500, (0, 511), B, 4)
+    try:
+        _check_local(W, 5000)
+    finally:
+        W.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", [8, 64])
+def test_rig_batch_lastframe_gpu(hip_lib, B):
+    W = World(hip_lib, 512, 512, 1500, (0, 511), B, 4)
+    try:
+        _check_lastframe(W, with_oracle=B == 8)
+    finally:
+        W.close()
+
+
+@pytest.mark.gpu
+def test_rig_batch_two_handles_gpu(hip_lib):
+    W = World(hip_lib, 512, 512, 1500, (0, 511), 8, 3, two_handles=True, seed=2)
+    try:
+        _check_local(W, 5000, params=((3.0, True),))
+        _check_lastframe(W, runs=((0, 0, True),), with_oracle=False)
+    finally:
+        W.close()
