@@ -768,6 +768,31 @@ int orbv_fetch(orbv_vocabulary* v, orbx_extractor* h, int b, uint32_t* word_id, 
 int orbm_search_by_bow_frames_batch(orbx_extractor* h, const orbv_vocabulary* v, int first, int B, orbm_keyframe* const* KFs,
                                     const uint8_t* const* has_map_point, float nnratio, int check_orientation, int* const* matches12, int* nmatches);
 
+/* Frame::ComputeBoW for B fisheye-rig frames (Nleft != -1, src/Frame.cc:984-997 over the rig Frame's mDescriptors, :1514): frame b = left image
+ * lf + b of L's last extraction (camera 1: features [0, Nleft)) followed by right image rf + b of R's (camera 2: features [Nleft, Nleft + Nright)),
+ * transformed as ONE set of Nleft + Nright rows - BowVector and FeatureVector equal to transform() on the joined rows.  L == R is allowed (lf = 0,
+ * rf = B for a batch extracted as [L0 .. L(B-1), R0 .. R(B-1)]); the handles must match in orbx_max_keypoints, levels, scale factor and device (no
+ * orbm_stereo_fisheye is needed).  Asynchronous on L's stream, after R's extraction.  The results then serve as those of orbv_transform_extracted on
+ * L: orbv_fetch(v, L, b, ..) (up to Nleft + Nright words and nodes: capacities 2 x orbx_max_keypoints), orbv_db_add_extracted(db, key, L, b),
+ * orbv_db_query_extracted(db, L, first, Q, ..); orbm_search_by_bow_frames_batch refuses them.  ORBX_E_CAPACITY when 2 x orbx_max_keypoints
+ * exceeds what one transform workgroup can sort (16384 features, or the LDS of the device). */
+int orbv_transform_rig_extracted(orbv_vocabulary* v, orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, int levelsup);
+
+/* ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vpMapPointMatches) for rig frames (F.Nleft != -1, src/ORBmatcher.cc:259-493 incl. :343-372 and
+ * :414-446; Tracking::TrackReferenceKeyFrame and Relocalization with two cameras) for P (frame, key frame) pairs on the device: frame[p] in [0, B)
+ * names a rig frame of the last orbv_transform_rig_extracted(v, L, lf, R, rf, B, levelsup) (same handles and ranges, neither handle extracted
+ * since), KFs[p] a resident key frame - a rig key frame (views listing mvKeys followed by mvKeysRight, as for the *_resident_kb8 searches) or a
+ * one-camera one - and has_map_point[p] [KFs[p]->N] its features with a good map point (NULL = none).  TrackReferenceKeyFrame: P = B, frame[p] = p;
+ * Relocalization: one frame against each of its candidates.  Per vocabulary node the frame's camera-1 and camera-2 features keep a best / second
+ * best each; camera 1 takes its best at <= TH_LOW within the ratio, camera 2 its best at <= TH_LOW without a ratio test, only when camera 1's best
+ * passed TH_LOW; one rotation histogram covers both (key-frame keypoint angle minus the frame's extracted keypoint angle).  assigned[p]
+ * [2 x orbx_max_keypoints] = key-frame feature whose map point goes to vpMapPointMatches[j] (j < Nleft + Nright), or -1 - the form of
+ * orbm_search_by_bow_fisheye; nmatches[p] = the reference's return value.  ORBX_E_CAPACITY when a vocabulary node holds more than 2048 features of
+ * one frame.  Blocking. */
+int orbm_search_by_bow_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const orbv_vocabulary* v, int P, const int* frame,
+                                 orbm_keyframe* const* KFs, const uint8_t* const* has_map_point, float nnratio, int check_orientation,
+                                 int* const* assigned, int* nmatches);
+
 /* ---- Key frame database (KeyFrameDatabase, src/KeyFrameDatabase.cc): the inverted-file part of place
  * recognition on the device.  One record per add, keyed by a caller key (a KeyFrame* or its mnId), in add order; every query walks all
  * records at once: the words each shares with the query (a key added twice counts twice, like the reference's duplicated list entries),

@@ -34,6 +34,7 @@ SYMBOLS = [
     "orbm_search_by_projection_mappoints_fisheye", "orbm_search_by_projection_frame_fisheye", "orbm_search_for_triangulation_batch",
     "orbm_search_local_points_rig_batch", "orbm_search_by_projection_lastframe_rig_batch", "orbm_search_rig_batch_fetch",
     "orbv_create", "orbv_load_text", "orbv_destroy", "orbv_words", "orbv_transform", "orbv_transform_extracted", "orbv_fetch", "orbm_search_by_bow_frames_batch",
+    "orbv_transform_rig_extracted", "orbm_search_by_bow_rig_batch",
     "orbv_db_create", "orbv_db_destroy", "orbv_db_add", "orbv_db_add_extracted", "orbv_db_erase", "orbv_db_erase_keys", "orbv_db_clear", "orbv_db_size",
     "orbv_db_query", "orbv_db_query_extracted",
     "orbx_comm_unique_id", "orbx_comm_create", "orbx_comm_adopt", "orbx_comm_destroy", "orbx_comm_world", "orbx_comm_rank", "orbx_allgather_descriptors", "orbx_comm_wait",
@@ -159,6 +160,8 @@ class OrbxLib:
         L.orbv_transform_extracted.argtypes = [vp, vp, i, i, i]
         L.orbv_fetch.argtypes = [vp, vp, i, vp, vp, i, vp, vp, ip, vp, vp, vp, ip]
         L.orbm_search_by_bow_frames_batch.argtypes = [vp, vp, i, i, vp, vp, f, i, vp, vp]
+        L.orbv_transform_rig_extracted.argtypes = [vp, vp, i, vp, i, i, i]
+        L.orbm_search_by_bow_rig_batch.argtypes = [vp, i, vp, i, i, vp, i, vp, vp, vp, f, i, vp, vp]
         u64 = C.c_uint64
         L.orbv_db_create.argtypes = [vp, vp, C.POINTER(vp)]
         L.orbv_db_destroy.argtypes = [vp]; L.orbv_db_destroy.restype = None

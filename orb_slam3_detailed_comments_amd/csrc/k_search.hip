@@ -1081,14 +1081,13 @@ __global__ void __launch_bounds__(256) k_sft_resident_kb8(ResidentKF k1, const u
 // loop included: a target taken by an earlier feature is skipped (:331, :948), and since a feature of K2 belongs to exactly one vocabulary
 // node, that dependence never leaves a node - one wave per (node of K1, pair) walks the node's K1 features in order.
 // A lane owns the candidates (positions in K2's list of the node) lane, lane + 64, ..; bit r of `taken` = position lane + 64 r is taken.
-// m12[p * N1cap + idx1] = matched index in K2 (pre-set to -1).  Nodes with more than 2048 features in K2 set status bit 2.
-// grid (ceil(max fv_nodes / 4), n)
-__global__ void __launch_bounds__(256) k_bow_match_resident(const BowPairResident* __restrict__ pairs, const uint8_t* __restrict__ flags,
-                                                            float nnratio, int th_low, int th_inclusive, int* __restrict__ m12, int N1cap,
-                                                            int* __restrict__ status) {
+// RIG: K2 is a rig frame (F.Nleft != -1, :343-372 and :414-446): its features below nleft are camera 1's, the others camera 2's; camera 1 keeps best
+// and second best, camera 2 only its best (its ratio test is `|| true`, :419) and is considered only when camera 1's best passed TH_LOW (:384).
+// out: K2 index by K1 feature (out[idx1]), or for RIG the K1 feature by K2 index (out[idx2]) - every K2 feature is taken at most once.
+template <bool RIG>
+__device__ __forceinline__ void bow_match_node(const BowPairResident& B, int a, const uint8_t* __restrict__ flags, float nnratio, int th_low,
+                                               int th_inclusive, int nleft, int* __restrict__ out, int* __restrict__ status) {
     const int lane = lane_id();
-    const int a = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), p = (int)blockIdx.y;
-    const BowPairResident& B = pairs[p];
     if (a >= B.k1.fv_nodes || B.mp1_off < 0) return;
     const int b = wave_find_node(B.k2.node_id, B.k2_nodes_dev ? *B.k2_nodes_dev : B.k2.fv_nodes, B.k1.node_id[a]);
     if (b < 0) return;
@@ -1103,7 +1102,7 @@ __global__ void __launch_bounds__(256) k_bow_match_resident(const BowPairResiden
         if (!mp1[idx1]) continue;                                                      // !pMP || pMP->isBad()
         const unsigned long long* da = B.k1.desc + 4 * (size_t)idx1;
         const unsigned long long a0 = da[0], a1 = da[1], a2 = da[2], a3 = da[3];
-        unsigned k1key = (256u << 16) | 0xFFFFu, k2key = k1key;                        // this lane's two smallest (distance << 16 | position)
+        unsigned k1key = (256u << 16) | 0xFFFFu, k2key = k1key, r1key = k1key;        // this lane's two smallest (distance << 16 | position); camera 2's smallest
         for (int j = lane, r = 0; j < c2; j += 64, r++) {
             if ((taken >> r) & 1u) continue;
             const int idx2 = B.k2.fv_feat[s2 + j];
@@ -1111,7 +1110,8 @@ __global__ void __launch_bounds__(256) k_bow_match_resident(const BowPairResiden
             const unsigned long long* db = B.k2.desc + 4 * (size_t)idx2;
             const unsigned d = (unsigned)(__popcll(a0 ^ db[0]) + __popcll(a1 ^ db[1]) + __popcll(a2 ^ db[2]) + __popcll(a3 ^ db[3]));
             const unsigned key = (d << 16) | (unsigned)j;
-            if (key < k1key) { k2key = k1key; k1key = key; } else if (key < k2key) k2key = key;
+            if (!RIG || idx2 < nleft) { if (key < k1key) { k2key = k1key; k1key = key; } else if (key < k2key) k2key = key; }
+            else if (key < r1key) r1key = key;
         }
         // sequential rule: bestDist1 = smallest distance (first position that attains it), bestDist2 = second smallest of the multiset
         const unsigned m1 = wave_min_u32(k1key);
@@ -1120,31 +1120,49 @@ __global__ void __launch_bounds__(256) k_bow_match_resident(const BowPairResiden
         const bool pass = th_inclusive ? bestDist1 <= th_low : bestDist1 < th_low;
         if (pass && (float)bestDist1 < __fmul_rn(nnratio, (float)bestDist2)) {
             const int j1 = (int)(m1 & 0xFFFFu);
-            if (lane == (j1 & 63)) { taken |= 1u << (j1 >> 6); m12[(size_t)p * N1cap + idx1] = B.k2.fv_feat[s2 + j1]; }
+            if (lane == (j1 & 63)) {
+                taken |= 1u << (j1 >> 6);
+                if (RIG) out[B.k2.fv_feat[s2 + j1]] = idx1; else out[idx1] = B.k2.fv_feat[s2 + j1];
+            }
+        }
+        if (RIG && pass) {                                                             // uniform: m1 is the wave's
+            const unsigned mr = wave_min_u32(r1key);
+            if ((int)(mr >> 16) <= th_low) {
+                const int jr = (int)(mr & 0xFFFFu);
+                if (lane == (jr & 63)) { taken |= 1u << (jr >> 6); out[B.k2.fv_feat[s2 + jr]] = idx1; }
+            }
         }
     }
 }
 
+// m12[p * N1cap + idx1] = matched index in K2 (pre-set to -1).  Nodes with more than 2048 features in K2 set status bit 2.
+// grid (ceil(max fv_nodes / 4), n)
+__global__ void __launch_bounds__(256) k_bow_match_resident(const BowPairResident* __restrict__ pairs, const uint8_t* __restrict__ flags,
+                                                            float nnratio, int th_low, int th_inclusive, int* __restrict__ m12, int N1cap,
+                                                            int* __restrict__ status) {
+    const int a = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), p = (int)blockIdx.y;
+    bow_match_node<false>(pairs[p], a, flags, nnratio, th_low, th_inclusive, 0, m12 + (size_t)p * N1cap, status);
+}
+
+// SearchByBoW(pKF, F) with a rig frame F (orbm_search_by_bow_rig_batch): assigned[p * S + j] = key-frame feature whose map point goes to
+// F.mvpMapPoints[j] (pre-set to -1), j < Nleft + Nright.  TH_LOW inclusive (:378).  grid (ceil(max fv_nodes of the key frames / 4), pairs)
+__global__ void __launch_bounds__(256) k_bow_match_rig(const BowPairRig* __restrict__ pairs, const uint8_t* __restrict__ flags, float nnratio, int th_low,
+                                                       int* __restrict__ assigned, int S, int* __restrict__ status) {
+    const int a = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), p = (int)blockIdx.y;
+    const BowPairRig& R = pairs[p];
+    bow_match_node<true>(R.m, a, flags, nnratio, th_low, 1, *R.nleft, assigned + (size_t)p * S, status);
+}
+
 // The rotation-consistency pruning behind SearchByBoW (src/ORBmatcher.cc:396-412 fill, :457-479 prune; ComputeThreeMaxima :2335-2377) on the device, one
 // wave per pair: histogram of round((angle1 - angle2 [+ 360]) / 30) over the matches, entries outside the three strongest bins (the second / third
-// only while they hold at least 10 % of the first) are reset to -1; nmatches[p] = matches left.  m12 as written by k_bow_match_resident.
-__global__ void __launch_bounds__(64) k_bow_rotation_prune(const BowPairResident* __restrict__ pairs, int* __restrict__ m12, int N1cap, int check_ori,
-                                                           int* __restrict__ nmatches) {
-    __shared__ int s_hist[32];
-    const int lane = lane_id(), p = (int)blockIdx.x;
-    const BowPairResident& B = pairs[p];
-    const int N1 = B.k1.N;
-    int* m = m12 + (size_t)p * N1cap;
+// only while they hold at least 10 % of the first) are reset to -1; returns the matches left (on every lane).  m [n]: one pair's results, bin_of(i, m[i]).
+template <typename BinOf>
+__device__ __forceinline__ int bow_prune_body(int* __restrict__ m, int n, int check_ori, int* s_hist, const BinOf& bin_of) {
+    const int lane = lane_id();
     if (lane < 32) s_hist[lane] = 0;
     ORBX_WAVE_SYNC();
-    auto bin_of = [&](int i, int j) {
-        float rot = __fsub_rn(B.k1.kps[i].angle, B.k2.kps[j].angle);
-        if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-        int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-        return bin == 30 ? 0 : bin;
-    };
     int nm = 0;
-    for (int i = lane; i < N1; i += 64) {
+    for (int i = lane; i < n; i += 64) {
         const int j = m[i];
         if (j < 0) continue;
         nm++;
@@ -1161,15 +1179,45 @@ __global__ void __launch_bounds__(64) k_bow_rotation_prune(const BowPairResident
         }
         if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
         else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
-        for (int i = lane; i < N1; i += 64) {
+        for (int i = lane; i < n; i += 64) {
             const int j = m[i];
             if (j < 0) continue;
             const int bin = bin_of(i, j);
             if (bin != ind1 && bin != ind2 && bin != ind3) { m[i] = -1; nm--; }
         }
     }
-    nm = wave_sum(nm);
-    if (lane == 0) nmatches[p] = nm;
+    return wave_sum(nm);
+}
+__device__ __forceinline__ int bow_rot_bin(float angle1, float angle2) {
+    float rot = __fsub_rn(angle1, angle2);
+    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
+    const int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
+    return bin == 30 ? 0 : bin;
+}
+
+// m12 as written by k_bow_match_resident; nmatches[p] = matches left
+__global__ void __launch_bounds__(64) k_bow_rotation_prune(const BowPairResident* __restrict__ pairs, int* __restrict__ m12, int N1cap, int check_ori,
+                                                           int* __restrict__ nmatches) {
+    __shared__ int s_hist[32];
+    const int p = (int)blockIdx.x;
+    const BowPairResident& B = pairs[p];
+    const int nm = bow_prune_body(m12 + (size_t)p * N1cap, B.k1.N, check_ori, s_hist,
+                                  [&](int i, int j) { return bow_rot_bin(B.k1.kps[i].angle, B.k2.kps[j].angle); });
+    if (lane_id() == 0) nmatches[p] = nm;
+}
+
+// the same over k_bow_match_rig's frame-indexed rows: one histogram for both cameras; the key frame's keypoint minus the frame's (mvKeys below
+// Nleft, mvKeysRight above, :391-395 and :425-429); nmatches[p] = matches left, as the reference counts them (each match enters the histogram once)
+__global__ void __launch_bounds__(64) k_bow_rotation_prune_rig(const BowPairRig* __restrict__ pairs, int* __restrict__ assigned, int S, int check_ori,
+                                                               int* __restrict__ nmatches) {
+    __shared__ int s_hist[32];
+    const int p = (int)blockIdx.x;
+    const BowPairRig& R = pairs[p];
+    const int nleft = *R.nleft;
+    const int nm = bow_prune_body(assigned + (size_t)p * S, S, check_ori, s_hist, [&](int j, int i) {
+        return bow_rot_bin(R.m.k1.kps[i].angle, j < nleft ? R.m.k2.kps[j].angle : R.kps_r[j - nleft].angle);
+    });
+    if (lane_id() == 0) nmatches[p] = nm;
 }
 
 __global__ void __launch_bounds__(256) k_bow_search(const BowItem* __restrict__ items, int nitems, const KeyPointRec* __restrict__ kps1,

@@ -119,6 +119,21 @@ __device__ __forceinline__ int emit_runs(const unsigned long long* key, int nval
 // weighting: 0 TF_IDF, 1 TF, 2 IDF, 3 BINARY;  norm: 0 none, 1 L1, 2 L2  (BowVector.h:29-50, ScoringObject.h:74-89)
 // Per image b (regions of `cap` entries): bow_id/bow_val/[n_out[2b]], fv_node/fv_start(cap+1)/fv_feat/[n_out[2b+1]];
 // bow_start: scratch, cap+1 ints per image.
+// orbv_transform_rig_extracted: the rows of rig frame b as the rig Frame's mDescriptors holds them (src/Frame.cc:1514, cv::vconcat): the descriptors
+// of left image b (camera 1) then those of right image b (camera 2), at out[(b * 2 cap + i) * 4]; n_out[b] = Nleft + Nright.  grid (ceil(2 cap / 256), B).
+__global__ void __launch_bounds__(256) k_voc_gather_rig(const unsigned long long* __restrict__ desc_l, const int* __restrict__ n_l,
+                                                        const unsigned long long* __restrict__ desc_r, const int* __restrict__ n_r, int cap, int B,
+                                                        unsigned long long* __restrict__ out, int* __restrict__ n_out) {
+    const int b = (int)blockIdx.y, i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (b >= B) return;
+    const int nl = imin(n_l[b], cap), nr = imin(n_r[b], cap);
+    if (i == 0) n_out[b] = nl + nr;
+    if (i >= nl + nr) return;
+    const unsigned long long* s = i < nl ? desc_l + 4 * ((size_t)b * cap + i) : desc_r + 4 * ((size_t)b * cap + (i - nl));
+    unsigned long long* d = out + 4 * ((size_t)b * 2 * cap + i);
+    d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3];
+}
+
 __global__ void __launch_bounds__(256) k_voc_assemble(const unsigned* __restrict__ word, const unsigned* __restrict__ node,
                                                       const double* __restrict__ weight, const int* __restrict__ n_feat, int n_fixed, int cap,
                                                       int P, int weighting, int norm, unsigned* __restrict__ bow_id,

@@ -1271,6 +1271,8 @@ int orbm_search_by_bow_frames_batch(orbx_extractor* h, const orbv_vocabulary* v,
                                     float nnratio, int check_ori, int* const* matches12, int* nmatches_out) {
     if (!h || !v || B <= 0 || !KFs || !has_mp1 || !matches12) return fail(ORBX_E_ARG, "null");
     VocFrameArrays V;
+    if (orbv_frame_arrays(v, &V) == 0 && V.rig)
+        return fail(ORBX_E_ARG, "the last vocabulary transform was a rig transform (orbv_transform_rig_extracted): search its frames with orbm_search_by_bow_rig_batch");
     if (orbv_frame_arrays(v, &V) || V.handle != (const void*)h || V.first != first || V.lastB != B || V.cap != h->kp_total_cap || first < 0 || first + B > h->lastB)
         return fail(ORBX_E_ARG, "run orbv_transform_extracted(v, h, %d, %d, levelsup) on this extraction first: the FeatureVectors of these frames are read where it leaves them", first, B);
     if (V.extract_gen != h->extract_gen)
@@ -1319,6 +1321,74 @@ int orbm_search_by_bow_frames_batch(orbx_extractor* h, const orbv_vocabulary* v,
         const int N1 = KFs[b]->N;
         if (N1 > 0) memcpy(matches12[b], &res[(size_t)b * N1cap], sizeof(int) * (size_t)N1);
         if (nmatches_out) nmatches_out[b] = res[nout + 4 + b];
+    }
+    return ORBX_OK;
+}
+
+// SearchByBoW(pKF, F) for rig frames (F.Nleft != -1, src/ORBmatcher.cc:259-493 incl. :343-372 and :414-446), P (frame, key frame) pairs: rig frame
+// frame[p] of the last orbv_transform_rig_extracted(v, L, lf, R, rf, B, .) - its rows and FeatureVector where the transform left them, camera 1's
+// keypoints in L, camera 2's in R - against the resident key frame KFs[p].  k_bow_match_rig (the two-camera accept loop per vocabulary node) and
+// k_bow_rotation_prune_rig (one histogram over both cameras' matches) for all pairs; assigned[p] is frame-indexed, as orbm_search_by_bow_fisheye's.
+int orbm_search_by_bow_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const orbv_vocabulary* v, int P, const int* frame,
+                                 orbm_keyframe* const* KFs, const uint8_t* const* has_map_point, float nnratio, int check_ori, int* const* assigned,
+                                 int* nmatches_out) {
+    if (!L || !R || !v || B <= 0 || P <= 0 || !frame || !KFs || !has_map_point || !assigned) return fail(ORBX_E_ARG, "null");
+    VocFrameArrays V;
+    if (orbv_frame_arrays(v, &V) || !V.rig)
+        return fail(ORBX_E_ARG, "no rig transform: run orbv_transform_rig_extracted(v, L, %d, R, %d, %d, levelsup) first - the rig frames' rows and FeatureVectors are read where it leaves them",
+                    lf, rf, B);
+    if (V.handle != (const void*)L || V.handle_r != (const void*)R || V.first != lf || V.first_r != rf || V.lastB != B)
+        return fail(ORBX_E_ARG, "the last rig transform covered other handles or frames (left %d, right %d, %d frames)", V.first, V.first_r, V.lastB);
+    if (V.extract_gen != L->extract_gen || V.extract_gen_r != R->extract_gen)
+        return fail(ORBX_E_ARG, "a handle has extracted since orbv_transform_rig_extracted ran: its FeatureVectors index the keypoints of the previous batch - transform again");
+    if (V.device != L->device || R->device != L->device) return fail(ORBX_E_ARG, "vocabulary and extractors live on different devices");
+    const int cap = L->kp_total_cap, S = V.cap;
+    if (S != 2 * cap || lf + B > L->lastB || rf + B > R->lastB) return fail(ORBX_E_ARG, "the rig transform does not match the handles' extractions");
+    rt::set_device(L->device);
+    size_t ftotal = 0; int maxnodes = 1;
+    std::vector<BowPairRig> pairs(P);
+    for (int p = 0; p < P; p++) {
+        const int b = frame[p];
+        if (b < 0 || b >= B) return fail(ORBX_E_ARG, "pair %d names frame %d, the rig transform holds %d", p, b, B);
+        const orbm_keyframe* K = KFs[p];
+        if (!K || !assigned[p]) return fail(ORBX_E_ARG, "pair %d: null key frame or output row", p);
+        if (K->device != L->device) return fail(ORBX_E_ARG, "pair %d: the key frame lives on another device", p);
+        BowPairRig& Q = pairs[p];
+        memset(&Q, 0, sizeof Q);
+        BowPairResident& M = Q.m;
+        M.k1 = K->dev;
+        M.k2.kps = L->d_kps.p + (size_t)(lf + b) * cap;                                   // mvKeys; camera 2's mvKeysRight below
+        M.k2.desc = V.desc + (size_t)b * S * 4; M.k2.ur = nullptr;
+        M.k2.node_id = V.fv_node + (size_t)b * S; M.k2.fv_start = V.fv_start + (size_t)b * (S + 1); M.k2.fv_feat = V.fv_feat + (size_t)b * S;
+        M.k2.node_of_feat = nullptr; M.k2.N = S; M.k2.fv_nodes = 0;
+        M.k2_nodes_dev = V.nout + 2 * b + 1;
+        M.mp1_off = -1; M.elig2_off = -1;
+        if (has_map_point[p] && K->N > 0) { M.mp1_off = (int)ftotal; ftotal += al16((size_t)K->N); }
+        Q.kps_r = R->d_kps.p + (size_t)(rf + b) * cap;
+        Q.nleft = L->d_nm.p + lf + b;
+        maxnodes = std::max(maxnodes, K->fv_nodes);
+    }
+    std::vector<uint8_t> flags(std::max<size_t>(ftotal, 16), 0);
+    for (int p = 0; p < P; p++) if (pairs[p].m.mp1_off >= 0) memcpy(&flags[pairs[p].m.mp1_off], has_map_point[p], (size_t)KFs[p]->N);
+    Packer pk(L);
+    const size_t pf = pk.add(flags.data(), flags.size()), pp = pk.add(pairs.data(), sizeof(BowPairRig) * pairs.size());
+    const size_t nout = (size_t)P * S, ntot = nout + 4 + (size_t)P;                  // assigned | status | nmatches
+    if (pk.flush() || L->d_si[SI_BEST].ensure(ntot)) return fail(ORBX_E_DEVICE, "upload/allocation failed");
+    if (rt::memset_async(L->d_si[SI_BEST].p, 0xFF, sizeof(int) * nout, L->s0) || rt::memset_async(L->d_si[SI_BEST].p + nout, 0, sizeof(int) * (4 + (size_t)P), L->s0))
+        return fail(ORBX_E_DEVICE, "memset failed");
+    if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][0], L->s0);
+    dim3 grid((maxnodes + 3) / 4, P, 1), blk(256, 1, 1);
+    ORBX_LAUNCH(k_bow_match_rig, grid, blk, 0, L->s0, pk.dev<BowPairRig>(pp), pk.dev<uint8_t>(pf), nnratio, TH_LOW, L->d_si[SI_BEST].p, S, L->d_si[SI_BEST].p + nout);
+    dim3 gridp(P, 1, 1), blkp(64, 1, 1);
+    ORBX_LAUNCH(k_bow_rotation_prune_rig, gridp, blkp, 0, L->s0, pk.dev<BowPairRig>(pp), L->d_si[SI_BEST].p, S, check_ori, L->d_si[SI_BEST].p + nout + 4);
+    if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][1], L->s0);
+    std::vector<int> res(ntot);
+    if (fetch_sync(L, res.data(), L->d_si[SI_BEST].p, sizeof(int) * ntot) || rt::check_launch())
+        return fail(ORBX_E_DEVICE, "batched rig bow search failed: %s", rt::last_error());
+    if (res[nout] & 4) return fail(ORBX_E_CAPACITY, "a vocabulary node holds more than 2048 features of one rig frame");
+    for (int p = 0; p < P; p++) {
+        memcpy(assigned[p], &res[(size_t)p * S], sizeof(int) * (size_t)S);
+        if (nmatches_out) nmatches_out[p] = res[nout + 4 + p];
     }
     return ORBX_OK;
 }

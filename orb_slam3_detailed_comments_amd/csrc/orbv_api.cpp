@@ -21,6 +21,8 @@ struct orbv_vocabulary {
     // per-call scratch / results (sized by reserve())
     int cap = 0, maxB = 0, lastB = 0, run_cap = 0;      // run_cap: per-image stride of the results of the last run
     int run_first = -1; const void* run_handle = nullptr; uint64_t run_extract_gen = 0;   // orbv_transform_extracted: which images of which extractor the results belong to
+    // orbv_transform_rig_extracted: the right handle, its first image and extraction; the frames' rows are in d_fdesc
+    bool run_rig = false; int run_first_r = -1; const void* run_handle_r = nullptr; uint64_t run_extract_gen_r = 0;
     DevBuf<unsigned long long> d_fdesc;
     DevBuf<unsigned> d_word, d_node, d_bow_id, d_fv_node, d_fv_feat;
     DevBuf<double> d_wt, d_bow_val;
@@ -45,14 +47,21 @@ int reserve(orbv_vocabulary* v, int cap, int B) {
     return 0;
 }
 
+// the limits of run() on the features per image, checked before anything is enqueued; *P = the key slots k_voc_assemble sorts
+int check_capacity(const orbx_extractor* h, int cap, int* P) {
+    if (cap > 16384) return fail(ORBX_E_CAPACITY, "more than 16384 features per image");
+    *P = 64; while (*P < cap) *P <<= 1;
+    // k_voc_assemble sorts one image's (id, feature) keys in LDS: 8 bytes per key slot (+ its static scan scratch)
+    if ((size_t)*P * 8 + 1024 > rt::lds_limit(h->device))
+        return fail(ORBX_E_CAPACITY, "%d features per image need %zu bytes of LDS for the vocabulary transform, the device allows %zu per workgroup", cap, (size_t)*P * 8 + 1024, rt::lds_limit(h->device));
+    return ORBX_OK;
+}
+
 // launches the two kernels over B images whose descriptors sit at fdesc[(b*cap + i)*4]; n_feat: device counts or nullptr (n_fixed)
 int run(orbv_vocabulary* v, orbx_extractor* h, const unsigned long long* fdesc, const int* n_feat, int n_fixed, int cap, int B, int levelsup) {
-    if (cap > 16384) return fail(ORBX_E_CAPACITY, "more than 16384 features per image");
+    int P = 0;
+    if (int rc = check_capacity(h, cap, &P)) return rc;
     if (reserve(v, cap, B)) return fail(ORBX_E_DEVICE, "vocabulary scratch allocation failed");
-    int P = 64; while (P < cap) P <<= 1;
-    // k_voc_assemble sorts one image's (id, feature) keys in LDS: 8 bytes per key slot (+ its static scan scratch)
-    if ((size_t)P * 8 + 1024 > rt::lds_limit(h->device))
-        return fail(ORBX_E_CAPACITY, "%d features per image need %zu bytes of LDS for the vocabulary transform, the device allows %zu per workgroup", cap, (size_t)P * 8 + 1024, rt::lds_limit(h->device));
     const long groups = (long)cap * B;
     dim3 g1((unsigned)((groups * 16 + 255) / 256), 1, 1), blk(256, 1, 1);
     ORBX_LAUNCH(k_voc_descend, g1, blk, 0, h->s0, fdesc, n_feat, n_fixed, cap, B, (const unsigned long long*)v->d_desc.p,
@@ -63,6 +72,7 @@ int run(orbv_vocabulary* v, orbx_extractor* h, const unsigned long long* fdesc, 
                 v->d_fv_start.p, v->d_fv_feat.p, v->d_nout.p);
     if (rt::check_launch()) return fail(ORBX_E_DEVICE, "vocabulary kernels failed to launch: %s", rt::last_error());
     v->lastB = B; v->run_cap = cap; v->run_first = -1; v->run_handle = nullptr;
+    v->run_rig = false; v->run_first_r = -1; v->run_handle_r = nullptr;
     return ORBX_OK;
 }
 
@@ -73,6 +83,8 @@ int orbv_frame_arrays(const orbv_vocabulary* v, VocFrameArrays* out) {
     if (!v || v->lastB <= 0) return -1;
     out->fv_node = (const uint32_t*)v->d_fv_node.p; out->fv_start = v->d_fv_start.p; out->fv_feat = (const int*)v->d_fv_feat.p; out->nout = v->d_nout.p;
     out->cap = v->run_cap; out->lastB = v->lastB; out->device = v->device; out->first = v->run_first; out->handle = v->run_handle; out->extract_gen = v->run_extract_gen;
+    out->rig = v->run_rig ? 1 : 0; out->first_r = v->run_first_r; out->handle_r = v->run_handle_r; out->extract_gen_r = v->run_extract_gen_r;
+    out->desc = v->run_rig ? (const unsigned long long*)v->d_fdesc.p : nullptr;
     return 0;
 }
 }  // namespace orbx
@@ -177,6 +189,34 @@ int orbv_transform_extracted(orbv_vocabulary* v, orbx_extractor* h, int first, i
     const int cap = h->kp_total_cap;
     const int rc = run(v, h, (const unsigned long long*)(h->d_desc.p + (size_t)first * cap * 4), (const int*)(h->d_nm.p + first), 0, cap, B, levelsup);
     if (rc == ORBX_OK) { v->run_first = first; v->run_handle = h; v->run_extract_gen = h->extract_gen; }
+    return rc;
+}
+
+// Frame::ComputeBoW of B rig frames (src/Frame.cc:984-997 over the rig Frame's mDescriptors, :1514): k_voc_gather_rig joins each frame's camera-1 and
+// camera-2 rows into d_fdesc, then the transform of orbv_transform_extracted runs on them with 2 x orbx_max_keypoints features per frame.
+int orbv_transform_rig_extracted(orbv_vocabulary* v, orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, int levelsup) {
+    if (!v || !L || !R) return fail(ORBX_E_ARG, "null");
+    if (B <= 0 || lf < 0 || rf < 0 || lf + B > L->lastB || rf + B > R->lastB)
+        return fail(ORBX_E_ARG, "frames [%d, %d) of the left handle / [%d, %d) of the right one are not in their last extractions (%d / %d images)", lf, lf + B, rf, rf + B,
+                    L->lastB, R->lastB);
+    if (L->kp_total_cap != R->kp_total_cap || L->nlevels != R->nlevels || L->scaleFactor != R->scaleFactor)
+        return fail(ORBX_E_ARG, "the two handles differ in orbx_max_keypoints, levels or scale factor");
+    if (L->device != R->device || v->device != L->device) return fail(ORBX_E_ARG, "vocabulary and extractors live on different devices");
+    rt::set_device(L->device);
+    const int cap = L->kp_total_cap, cap2 = 2 * cap;
+    int P = 0;
+    if (int rc = check_capacity(L, cap2, &P)) return rc;                 // refused before the gather overwrites the rows of an earlier rig run
+    v->lastB = 0; v->run_rig = false; v->run_handle = nullptr; v->run_handle_r = nullptr;
+    if (v->d_fdesc.ensure((size_t)B * cap2 * 4) || reserve(v, cap2, B)) return fail(ORBX_E_DEVICE, "vocabulary scratch allocation failed");
+    if (L != R) { record_done_if_pending(R); rt::stream_wait_event(L->s0, R->ev_done); }          // R's extraction runs on R's stream
+    dim3 grid((unsigned)((cap2 + 255) / 256), (unsigned)B, 1), blk(256, 1, 1);
+    ORBX_LAUNCH(k_voc_gather_rig, grid, blk, 0, L->s0, (const unsigned long long*)(L->d_desc.p + (size_t)lf * cap * 4), (const int*)(L->d_nm.p + lf),
+                (const unsigned long long*)(R->d_desc.p + (size_t)rf * cap * 4), (const int*)(R->d_nm.p + rf), cap, B, v->d_fdesc.p, v->d_nfeat.p);
+    const int rc = run(v, L, v->d_fdesc.p, v->d_nfeat.p, 0, cap2, B, levelsup);
+    if (rc == ORBX_OK) {
+        v->run_first = lf; v->run_handle = L; v->run_extract_gen = L->extract_gen;
+        v->run_rig = true; v->run_first_r = rf; v->run_handle_r = R; v->run_extract_gen_r = R->extract_gen;
+    }
     return rc;
 }
 

@@ -45,8 +45,12 @@ template <typename T> struct HostBuf {
 
 // where the vocabulary transform of the last orbv_transform_extracted left the FeatureVectors of its frames (orbv_api.cpp), for the searches that
 // read them in place (orbm_search_by_bow_frames_batch): frame b's sorted node ids at fv_node + b * cap, CSR offsets at fv_start + b * (cap + 1),
-// feature indices at fv_feat + b * cap, its node count at nout[2 * b + 1]
-struct VocFrameArrays { const uint32_t* fv_node; const int* fv_start; const int* fv_feat; const int* nout; int cap, lastB, device, first; const void* handle; uint64_t extract_gen; };
+// feature indices at fv_feat + b * cap, its node count at nout[2 * b + 1].  A rig run (orbv_transform_rig_extracted, rig != 0) also names its right
+// handle and range, and desc holds the rows it transformed: frame b's Nleft + Nright descriptors at desc + b * cap * 4 (cap = 2 x orbx_max_keypoints)
+struct VocFrameArrays {
+    const uint32_t* fv_node; const int* fv_start; const int* fv_feat; const int* nout; int cap, lastB, device, first; const void* handle; uint64_t extract_gen;
+    int rig, first_r; const void* handle_r; uint64_t extract_gen_r; const unsigned long long* desc;
+};
 }  // namespace orbx
 struct orbv_vocabulary;
 namespace orbx { int orbv_frame_arrays(const orbv_vocabulary* v, VocFrameArrays* out); }

@@ -189,6 +189,9 @@ __global__ void k_sft_resident_kb8(ResidentKF k1, const uint8_t* __restrict__ fl
 __global__ void k_bow_match_resident(const BowPairResident* __restrict__ pairs, const uint8_t* __restrict__ flags, float nnratio, int th_low,
                                      int th_inclusive, int* __restrict__ m12, int N1cap, int* __restrict__ status);
 __global__ void k_bow_rotation_prune(const BowPairResident* __restrict__ pairs, int* __restrict__ m12, int N1cap, int check_ori, int* __restrict__ nmatches);
+__global__ void k_bow_match_rig(const BowPairRig* __restrict__ pairs, const uint8_t* __restrict__ flags, float nnratio, int th_low,
+                                int* __restrict__ assigned, int S, int* __restrict__ status);
+__global__ void k_bow_rotation_prune_rig(const BowPairRig* __restrict__ pairs, int* __restrict__ assigned, int S, int check_ori, int* __restrict__ nmatches);
 __global__ void k_bow_dists(const BowItem* __restrict__ items, int nitems, const unsigned long long* __restrict__ desc1,
                             const unsigned long long* __restrict__ desc2, const uint8_t* __restrict__ eligible2,
                             const int* __restrict__ feat2, int* __restrict__ out);
@@ -198,6 +201,8 @@ __global__ void k_voc_descend(const unsigned long long* __restrict__ fdesc, cons
                               const unsigned long long* __restrict__ slot_desc, const VocSlot* __restrict__ slots,
                               const double* __restrict__ slot_weight, int root_children, int nid_level, unsigned* __restrict__ out_word,
                               unsigned* __restrict__ out_node, double* __restrict__ out_weight);
+__global__ void k_voc_gather_rig(const unsigned long long* __restrict__ desc_l, const int* __restrict__ n_l, const unsigned long long* __restrict__ desc_r,
+                                 const int* __restrict__ n_r, int cap, int B, unsigned long long* __restrict__ out, int* __restrict__ n_out);
 __global__ void k_voc_assemble(const unsigned* __restrict__ word, const unsigned* __restrict__ node, const double* __restrict__ weight,
                                const int* __restrict__ n_feat, int n_fixed, int cap, int P, int weighting, int norm,
                                unsigned* __restrict__ bow_id, double* __restrict__ bow_val, int* __restrict__ bow_start,

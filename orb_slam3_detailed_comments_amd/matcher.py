@@ -115,6 +115,25 @@ class ORBmatcher:
         ext._lib.check(ext._lib.L.orbm_search_by_bow_frames_batch(ext._h, voc._v, int(first), B, p1, q1, self.mfNNratio, int(self.mbCheckOrientation), po, nm.ctypes.data))
         return [(int(nm[b]), outs[b][:kfs[b].N]) for b in range(B)]
 
+    def SearchByBoWRigBatch(self, exL, lf, exR, rf, voc, frames, kfs, mps, n_frame=None):
+        """ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) for fisheye-rig frames on the device (orbm_search_by_bow_rig_batch): voc = the
+        ORBVocabulary whose transform_rig_extracted(exL, lf, exR, rf, B, levelsup) ran last; pair p = rig frame frames[p] of that transform against the
+        ResidentKeyFrame kfs[p] (rig or one camera), mps[p] = uint8 flags "feature of kfs[p] has a good map point".  Returns [(nmatches, assigned)]
+        with assigned[j] = key-frame feature whose map point goes to vpMapPointMatches[j] or -1: Nleft + Nright entries when n_frame[b] gives them
+        per frame, else the whole row of 2 x max_keypoints."""
+        P = len(kfs)
+        fr = np.ascontiguousarray(frames, np.int32)
+        assert len(fr) == P and len(mps) == P
+        S = 2 * exL.max_keypoints()
+        p1 = (C.c_void_p * max(P, 1))(*[k._kf for k in kfs])
+        a1 = [np.ascontiguousarray(m, np.uint8) for m in mps]
+        q1 = (C.c_void_p * max(P, 1))(*[m.ctypes.data for m in a1])
+        outs = [np.full(S, -1, np.int32) for _ in range(P)]
+        po = (C.c_void_p * max(P, 1))(*[o.ctypes.data for o in outs]); nm = np.zeros(max(P, 1), np.int32)
+        exL._lib.check(exL._lib.L.orbm_search_by_bow_rig_batch(exL._h, int(lf), exR._h, int(rf), int(getattr(voc, "_rig_B", 0)), voc._v, P, fr.ctypes.data, p1, q1,
+                                                               self.mfNNratio, int(self.mbCheckOrientation), po, nm.ctypes.data))
+        return [(int(nm[p]), outs[p] if n_frame is None else outs[p][:int(n_frame[fr[p]])]) for p in range(P)]
+
     def SearchByBoWFisheye(self, ext, kf, frame, nleft):
         """SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) for a fisheye-rig frame (F.Nleft = nleft != -1), src/ORBmatcher.cc:259-493.
         Both views list all features by index (camera 1 first).  Returns (nmatches, assigned[N_frame] = key-frame feature or -1)."""

@@ -77,8 +77,16 @@ class ORBVocabulary:
         B = ext._B - first if B is None else B
         self._lib.check(self._lib.L.orbv_transform_extracted(self._v, ext._h, int(first), int(B), int(levelsup)))
 
+    def transform_rig_extracted(self, exL, lf, exR, rf, B, levelsup=4):
+        """Frame::ComputeBoW of B fisheye-rig frames on the device (orbv_transform_rig_extracted): frame b = left image lf + b of exL's last batch
+        (camera 1) followed by right image rf + b of exR's (camera 2), transformed as one set of Nleft + Nright rows (asynchronous).  fetch(exL, b, ..),
+        KeyFrameDatabase.add_extracted(key, exL, b) / query_extracted(exL, ..) and ORBmatcher.SearchByBoWRigBatch read the results."""
+        self._rig_B = 0
+        self._lib.check(self._lib.L.orbv_transform_rig_extracted(self._v, exL._h, int(lf), exR._h, int(rf), int(B), int(levelsup)))
+        self._rig_B = int(B)
+
     def fetch(self, ext, b, n_features):
-        a = self._alloc(max(ext.max_keypoints(), 1))
+        a = self._alloc(max(2 * ext.max_keypoints(), n_features, 1))           # a rig transform holds up to 2 x max_keypoints features per frame
         nb, nf = C.c_int(), C.c_int()
         self._lib.check(self._lib.L.orbv_fetch(self._v, ext._h, int(b), a[5].ctypes.data, a[6].ctypes.data, int(n_features), a[0].ctypes.data,
                                                a[1].ctypes.data, C.byref(nb), a[2].ctypes.data, a[3].ctypes.data, a[4].ctypes.data, C.byref(nf)))
