@@ -1,11 +1,16 @@
-// orbm_search.cpp — host side of the guided searches (include/orbx.h "Guided searches"): uploads the SoA views,
-// launches k_grid_build / k_area_search / k_bow_search, and replays the reference's *order-dependent* acceptance loops
-// over the device-computed candidate lists:
-//   SearchByProjection(Frame, MapPoints)   src/ORBmatcher.cc:45-239
-//   SearchByProjection(Frame, Frame)       src/ORBmatcher.cc:1950-2184 (+ ComputeThreeMaxima :2335-2377)
-//   SearchForTriangulation                 src/ORBmatcher.cc:1045-1323
-// All Hamming distances and all window / level / gate / epipolar tests run on the GPU; the replay below only compares
-// precomputed integers in the reference's sequence (an assignment for one map point changes the candidate set of the next).
+// orbm_search.cpp — host side of the guided searches (include/orbx.h "Guided searches").  All Hamming distances and all window / level / gate /
+// epipolar tests run on the GPU; the host uploads the SoA views, launches the kernels of k_search.hip and - where the reference's acceptance loop is
+// order-dependent (an assignment for one map point changes the candidate set of the next) - replays it over the device-computed candidate lists,
+// comparing precomputed integers in the reference's sequence.  Map of the file:
+//   shared pieces           Bump / Packer (block layout, one staged upload), upload_frame, the window search with its candidate pool (pooled_area_search), the replay
+//                           helpers (Cands, scan_best, scan_best2, RotHist, for_each_common_node, fill_kb8)
+//   single-frame searches   GetFeaturesInArea, SearchByProjection(Frame, MapPoints), isInFrustum (one camera and rig), SearchLocalPoints,
+//                           SearchByProjection(Frame, Frame), SearchForTriangulation, SearchByBoW, SearchForInitialization, the projected-point searches
+//                           (Sim3, key frame, Fuse, SearchBySim3), DistinctiveDescriptors, the two-camera (fisheye) forms
+//   resident objects        orbm_points (map points), orbm_keyframe (key frames) and the searches that read them
+//   batched routes          frames of the last extraction: SearchLocalPoints, SearchByProjection(last frame / key frame), SearchByBoW; one fetch
+//   rig routes              the same for two-camera frames (two handles), fetched through the same core
+// The line numbers in the comments point into the reference's src/ORBmatcher.cc unless another file is named.
 #include "orbx_internal.h"
 
 using namespace orbx;
@@ -34,34 +39,54 @@ int upload(orbx_extractor* h, int slot, const void* src, size_t bytes) {
 // dozen small pageable copies the driver calls cost more than the kernels).
 inline size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-// several host arrays -> one pinned staging buffer -> one async copy into d_sr[SR_KPS]; add() returns the device address
-struct Packer {
-    orbx_extractor* h; std::vector<std::pair<const void*, size_t>> parts; std::vector<size_t> offs; size_t total = 0;
-    explicit Packer(orbx_extractor* hh) : h(hh) {}
-    size_t add(const void* src, size_t bytes) { offs.push_back(total); parts.emplace_back(src, bytes); total += al16(bytes ? bytes : 1); return offs.size() - 1; }
-    int flush() {
-        if (h->h_packA.ensure(total + 16) || h->d_sr[SR_KPS].ensure(total + 16)) return -1;
-        for (size_t i = 0; i < parts.size(); i++) if (parts[i].second) memcpy(h->h_packA.p + offs[i], parts[i].first, parts[i].second);
-        return rt::copy_h2d(h->d_sr[SR_KPS].p, h->h_packA.p, total, h->s0);
-    }
-    template <typename T> const T* dev(size_t part) const { return (const T*)(h->d_sr[SR_KPS].p + offs[part]); }
+// lays 16-byte aligned parts out one behind the other: take() returns the offset of the next one
+struct Bump {
+    size_t o;
+    explicit Bump(size_t start = 0) : o(start) {}
+    size_t take(size_t bytes) { const size_t at = o; o += al16(bytes); return at; }
 };
 
-int upload_frame(orbx_extractor* h, const OrbmFrameView* F, DeviceFrame* D) {
+// several host arrays -> one pinned staging buffer -> one async copy into a scratch slot (h_packA -> d_sr[SR_KPS] unless the caller chooses others).
+// add() copies an array, fill() writes `bytes` of one value, room() reserves device space behind the upload (after the last add / fill);
+// each returns the part whose device address dev() / out() gives after flush()
+struct Packer {
+    struct Part { const void* src; size_t bytes; int value; size_t off; };
+    orbx_extractor* h; HostBuf<uint8_t>& stage; int slot; std::vector<Part> parts; Bump lay; size_t uploaded = 0;
+    explicit Packer(orbx_extractor* hh) : h(hh), stage(hh->h_packA), slot(SR_KPS) {}
+    Packer(orbx_extractor* hh, HostBuf<uint8_t>& st, int sl) : h(hh), stage(st), slot(sl) {}
+    size_t part(const void* src, size_t bytes, int value) { parts.push_back({src, bytes, value, lay.take(bytes ? bytes : 1)}); uploaded = lay.o; return parts.size() - 1; }
+    size_t add(const void* src, size_t bytes) { return part(src, bytes, 0); }
+    size_t fill(int value, size_t bytes) { return part(nullptr, bytes, value); }
+    size_t room(size_t bytes) { parts.push_back({nullptr, 0, 0, lay.take(bytes)}); return parts.size() - 1; }
+    int flush() {                                                   // -1: an allocation failed, -2: the copy
+        if (stage.ensure(uploaded + 16) || h->d_sr[slot].ensure(lay.o + 16)) return -1;
+        for (const Part& p : parts) { if (p.src) memcpy(stage.p + p.off, p.src, p.bytes); else if (p.bytes) memset(stage.p + p.off, p.value, p.bytes); }
+        return rt::copy_h2d(h->d_sr[slot].p, stage.p, uploaded, h->s0) ? -2 : 0;
+    }
+    template <typename T> const T* dev(size_t part) const { return (const T*)(h->d_sr[slot].p + parts[part].off); }
+    template <typename T> T* out(size_t part) const { return (T*)(h->d_sr[slot].p + parts[part].off); }
+};
+const char* upload_error(int e) { return e == -1 ? "upload/allocation failed" : "upload failed"; }
+
+int frame_check(const OrbmFrameView* F) {
     if (!F || F->N < 0 || (F->N > 0 && (!F->keys_un || !F->desc))) return fail(ORBX_E_ARG, "bad frame view");
     if (F->N >= 65535) return fail(ORBX_E_ARG, "too many keypoints");
-    const int N = F->N, N1 = N > 0 ? N : 1;
-    const size_t okp = 0, odesc = al16(sizeof(KeyPointRec) * (size_t)N1), our = odesc + al16(32 * (size_t)N1), total = our + al16(sizeof(float) * (size_t)N1);
-    int e = h->h_packA.ensure(total + 16) | h->d_sr[SR_KPS].ensure(total + 16);
-    e |= h->d_si[SI_CELLOF].ensure(N + 1) | h->d_si[SI_CELLSTART].ensure(64 * 48 + 2) | h->d_si[SI_CELLITEMS].ensure(N + 1) | h->d_si[SI_COUNTER].ensure(4);
-    if (e) return fail(ORBX_E_DEVICE, "upload/allocation failed");
-    uint8_t* hp = h->h_packA.p;
-    if (N > 0) { memcpy(hp + okp, F->keys_un, sizeof(KeyPointRec) * (size_t)N); memcpy(hp + odesc, F->desc, 32 * (size_t)N); }
-    float* ur = (float*)(hp + our);
-    if (F->u_right) memcpy(ur, F->u_right, sizeof(float) * (size_t)N); else for (int i = 0; i < N1; i++) ur[i] = -1.0f;
-    if (rt::copy_h2d(h->d_sr[SR_KPS].p, hp, total, h->s0)) return fail(ORBX_E_DEVICE, "upload failed");
-    const uint8_t* dp = h->d_sr[SR_KPS].p;
-    D->kps = (const KeyPointRec*)(dp + okp); D->desc = (const unsigned long long*)(dp + odesc); D->ur = (const float*)(dp + our);
+    return ORBX_OK;
+}
+// the frame (keypoints | descriptors | uRight, -1 where the frame has none) and what more() adds to pk behind it go up in one copy; then the frame's grid is built
+template <typename More>
+int upload_frame(orbx_extractor* h, const OrbmFrameView* F, DeviceFrame* D, Packer& pk, const More& more) {
+    int rc = frame_check(F); if (rc) return rc;
+    const int N = F->N;
+    std::vector<float> mono;
+    if (!F->u_right) mono.assign(N > 0 ? N : 1, -1.0f);
+    const size_t pkp = pk.add(F->keys_un, sizeof(KeyPointRec) * (size_t)N), pdesc = pk.add(F->desc, 32 * (size_t)N),
+                 pur = F->u_right ? pk.add(F->u_right, sizeof(float) * (size_t)N) : pk.add(mono.data(), sizeof(float) * mono.size());
+    more();
+    if (h->d_si[SI_CELLOF].ensure(N + 1) | h->d_si[SI_CELLSTART].ensure(64 * 48 + 2) | h->d_si[SI_CELLITEMS].ensure(N + 1) | h->d_si[SI_COUNTER].ensure(4))
+        return fail(ORBX_E_DEVICE, "upload/allocation failed");
+    if (int e = pk.flush()) return fail(ORBX_E_DEVICE, "%s", upload_error(e));
+    D->kps = pk.dev<KeyPointRec>(pkp); D->desc = pk.dev<unsigned long long>(pdesc); D->ur = pk.dev<float>(pur);
     memset(&D->g, 0, sizeof D->g);
     D->g.min_x = F->min_x; D->g.min_y = F->min_y; D->g.gw_inv = F->grid_w_inv; D->g.gh_inv = F->grid_h_inv;
     const dim3 one(1, 1, 1), blkg(kGridThreads, 1, 1);
@@ -69,8 +94,8 @@ int upload_frame(orbx_extractor* h, const OrbmFrameView* F, DeviceFrame* D) {
     D->cell_start = h->d_si[SI_CELLSTART].p; D->cell_items = h->d_si[SI_CELLITEMS].p;
     return ORBX_OK;
 }
+int upload_frame(orbx_extractor* h, const OrbmFrameView* F, DeviceFrame* D) { Packer pk(h); return upload_frame(h, F, D, pk, [] {}); }
 
-struct Csr { std::vector<int> start, count; std::vector<int> ent; };   // ent: 2 ints per candidate {idx, dist | octave << 16}
 void fill_frustum_params(const OrbmFrustumView* V, float cos_limit, float th, int far_points, float th_far, FrustumParams* Fp) {
     memset(Fp, 0, sizeof *Fp);
     memcpy(Fp->Rcw, V->Rcw, sizeof Fp->Rcw); memcpy(Fp->tcw, V->tcw, sizeof Fp->tcw); memcpy(Fp->Ow, V->Ow, sizeof Fp->Ow); memcpy(Fp->qcw, V->qcw, sizeof Fp->qcw);
@@ -80,82 +105,177 @@ void fill_frustum_params(const OrbmFrustumView* V, float cos_limit, float th, in
     Fp->cos_limit = cos_limit; Fp->th = th; Fp->th_far = th_far; Fp->far_points = far_points;
 }
 
-// runs k_area_search for Q queries.  Results come back in one copy: [total, -, -, -][start Q][count Q][entries]; the number of
-// entries fetched with the header is a guess from the previous call, a second copy follows only if it was too small, and the pool is
-// grown and the search repeated if the pool itself overflowed.
-int run_area_search_dev(orbx_extractor* h, const DeviceFrame& D, int Q, const AreaQuery* dq, const unsigned long long* dqd, Csr* out, const void* extra_src = nullptr,
-                        size_t extra_bytes = 0, const uint8_t** extra_host = nullptr);
-int run_area_search(orbx_extractor* h, const DeviceFrame& D, const std::vector<AreaQuery>& qs, const uint8_t* qdesc, Csr* out) {
-    const int Q = (int)qs.size();
-    out->start.assign(Q, 0); out->count.assign(Q, 0); out->ent.clear();
-    if (Q == 0) return ORBX_OK;
-    const size_t oq = 0, oqd = al16(sizeof(AreaQuery) * (size_t)Q), qtotal = oqd + al16(32 * (size_t)Q);
-    if (h->h_packB.ensure(qtotal + 16) || h->d_sr[SR_QUERY].ensure(qtotal + 16)) return fail(ORBX_E_DEVICE, "upload/allocation failed");
-    memcpy(h->h_packB.p + oq, qs.data(), sizeof(AreaQuery) * (size_t)Q); memcpy(h->h_packB.p + oqd, qdesc, 32 * (size_t)Q);
-    if (rt::copy_h2d(h->d_sr[SR_QUERY].p, h->h_packB.p, qtotal, h->s0)) return fail(ORBX_E_DEVICE, "upload failed");
-    return run_area_search_dev(h, D, Q, (const AreaQuery*)(h->d_sr[SR_QUERY].p + oq), (const unsigned long long*)(h->d_sr[SR_QUERY].p + oqd), out);
+// ---- the candidate lists of a window search, and the pieces of the replays over them ----
+// query q owns `count[q]` entries from `start[q]` on, two ints each: {keypoint, dist | octave << 16}, in the order of the reference's GetFeaturesInArea
+struct Csr;
+struct Cands {
+    const int *start = nullptr, *count = nullptr, *ent = nullptr; int total = 0;
+    Cands() {}
+    Cands(const int* s, const int* c, const int* e, int t) : start(s), count(c), ent(e), total(t) {}     // the pinned block a search came back in
+    Cands(const Csr& c);
+    int idx(int q, int k) const { return ent[2 * ((size_t)start[q] + k)]; }
+    int dist(int q, int k) const { return ent[2 * ((size_t)start[q] + k) + 1] & 0xFFFF; }
+    int level(int q, int k) const { return ent[2 * ((size_t)start[q] + k) + 1] >> 16; }
+};
+// a copy of the lists, for the replays that hold two searches at a time (the pinned block is overwritten by the handle's next search)
+struct Csr {
+    std::vector<int> start, count, ent;
+    void copy(const Cands& c, int Q) { start.assign(c.start, c.start + Q); count.assign(c.count, c.count + Q); ent.assign(c.ent, c.ent + 2 * (size_t)c.total); ent.resize(ent.size() + 2); }
+};
+Cands::Cands(const Csr& c) : start(c.start.data()), count(c.count.data()), ent(c.ent.data()), total((int)c.ent.size() / 2 - 1) {}
+
+// the nearest candidate of query q on a free keypoint (occ == nullptr: on any).  off: the candidates are camera 2's, whose slots follow camera 1's Nleft
+struct Best { int dist, idx; };
+Best scan_best(const Cands& c, int q, const uint8_t* occ, int off = 0, int init = 256) {
+    Best b = {init, -1};
+    for (int k = 0; k < c.count[q]; k++) {
+        const int idx = c.idx(q, k), dist = c.dist(q, k);
+        if (occ && occ[idx + off]) continue;
+        if (dist < b.dist) { b.dist = dist; b.idx = idx; }
+    }
+    return b;
 }
-// the same with the queries and their descriptors already on the device.  extra_src / extra_bytes: another device block to bring back with the
-// same synchronisation (the tracking fields of SearchLocalPoints); *extra_host points at its pinned copy afterwards.
-int run_area_search_dev(orbx_extractor* h, const DeviceFrame& D, int Q, const AreaQuery* dq, const unsigned long long* dqd, Csr* out, const void* extra_src,
-                        size_t extra_bytes, const uint8_t** extra_host) {
-    out->start.assign(Q, 0); out->count.assign(Q, 0); out->ent.clear();
-    if (Q == 0) return ORBX_OK;
-    const size_t hdr = 16 + 8 * (size_t)Q;                          // bytes in front of the entries
+// the two nearest with their pyramid levels, as the scan of SearchByProjection(Frame, MapPoints) keeps them (:101-140)
+struct Best2 { int bestDist, bestLevel, bestDist2, bestLevel2, bestIdx; };
+Best2 scan_best2(const Cands& c, int q, const uint8_t* occ, int off = 0) {
+    int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
+    for (int k = 0; k < c.count[q]; k++) {
+        const int idx = c.idx(q, k);
+        if (occ && occ[idx + off]) continue;
+        const int dist = c.dist(q, k), level = c.level(q, k);
+        if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = level; bestIdx = idx; }
+        else if (dist < bestDist2) { bestLevel2 = level; bestDist2 = dist; }
+    }
+    return {bestDist, bestLevel, bestDist2, bestLevel2, bestIdx};
+}
+
+// the rotation-consistency check: matches vote with their angle difference, those outside the three strongest bins are reset (:2118-2123, :2161-2176)
+class RotHist {
+    std::vector<int> rotHist[HISTO_LENGTH];
+    // ORBmatcher::ComputeThreeMaxima, src/ORBmatcher.cc:2335-2377
+    static void three_maxima(const std::vector<int>* histo, int L, int& ind1, int& ind2, int& ind3) {
+        int max1 = 0, max2 = 0, max3 = 0;
+        for (int i = 0; i < L; i++) {
+            const int s = (int)histo[i].size();
+            if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
+            else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
+            else if (s > max3) { max3 = s; ind3 = i; }
+        }
+        if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
+        else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
+    }
+    static int rot_bin(float a1, float a2) {    // :2118-2123; the 1/HISTO_LENGTH factor is the reference's (kept on purpose)
+        const float factor = 1.0f / HISTO_LENGTH;
+        float rot = a1 - a2;
+        if (rot < 0.0) rot += 360.0f;
+        int bin = (int)round(rot * factor);
+        if (bin == HISTO_LENGTH) bin = 0;
+        return bin;
+    }
+public:
+    void add(float angle1, float angle2, int id) { rotHist[rot_bin(angle1, angle2)].push_back(id); }
+    // reset(id) for every id outside the three strongest bins, in bin order
+    template <typename Reset> void prune(const Reset& reset) const {
+        int ind1 = -1, ind2 = -1, ind3 = -1;
+        three_maxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
+        for (int i = 0; i < HISTO_LENGTH; i++) {
+            if (i == ind1 || i == ind2 || i == ind3) continue;
+            for (int id : rotHist[i]) reset(id);
+        }
+    }
+};
+
+// merge-join of two FeatureVectors by node id (:1105-1286, :300-474, :917-1021): fn(a, b) for every vocabulary node that both key frames hold
+template <typename Fn> void for_each_common_node(const OrbmKeyFrameView* K1, const OrbmKeyFrameView* K2, const Fn& fn) {
+    int a = 0, b = 0;
+    while (a < K1->fv_nodes && b < K2->fv_nodes) {
+        const uint32_t na = K1->fv_node_id[a], nb = K2->fv_node_id[b];
+        if (na == nb) { fn(a, b); a++; b++; }
+        else if (na < nb) { while (a < K1->fv_nodes && K1->fv_node_id[a] < nb) a++; }
+        else { while (b < K2->fv_nodes && K2->fv_node_id[b] < na) b++; }
+    }
+}
+// the Kannala-Brandt half of BowParams: the camera pair of one neighbour and KF1's level variances
+void fill_kb8(BowParams& P, const OrbmKB8Pair& C, const float* sigma2_1, int nlevels) {
+    P.kb8 = 1; P.nleft1 = C.nleft1; P.nleft2 = C.nleft2;
+    memcpy(P.cam1, C.cam1, sizeof P.cam1); memcpy(P.cam2, C.cam2, sizeof P.cam2); memcpy(P.R, C.R, sizeof P.R); memcpy(P.t, C.t, sizeof P.t);
+    for (int l = 0; l < nlevels && l < kMaxLevels; l++) P.sigma2_1[l] = sigma2_1[l];
+}
+
+// the ordered loop of SearchByProjection(Frame, MapPoints) over one camera's candidates, :62-166 (a map point that is not in view, far, bad or
+// on a level the frame does not have got no window: count 0); returns nmatches
+int replay_mappoints(const Cands& c, int M, float nnratio, const uint8_t* has_obs, uint8_t* occ, int* assigned) {
+    int nmatches = 0;
+    for (int i = 0; i < M; i++) {
+        if (c.count[i] == 0) continue;
+        const Best2 b = scan_best2(c, i, occ);
+        if (b.bestDist <= TH_HIGH) {
+            if (b.bestLevel == b.bestLevel2 && b.bestDist > nnratio * b.bestDist2) continue;
+            if (b.bestLevel != b.bestLevel2 || b.bestDist <= nnratio * b.bestDist2) {
+                assigned[b.bestIdx] = i;
+                occ[b.bestIdx] = has_obs ? has_obs[i] : 1;
+                nmatches++;
+            }
+        }
+    }
+    return nmatches;
+}
+
+// ---- the window search of one frame ----
+// the result block in d_sr[SR_ENTRIES] and its pinned copy in h_out: [counter 16 | start Q | count Q] | `mid` bytes of the caller's | entry pool
+struct AreaBlock {
+    int* counter; int* start; int* count; uint8_t* mid; int2* ent;
+    AreaBlock(uint8_t* p, size_t Q, size_t mid_bytes) : counter((int*)p), start((int*)(p + 16)), count(start + Q), mid(p + al16(16 + 8 * Q)), ent((int2*)(mid + mid_bytes)) {}
+};
+void launch_area_search(orbx_extractor* h, const DeviceFrame& D, int Q, const AreaQuery* dq, const unsigned long long* dqd, const AreaBlock& o, size_t pool) {
+    dim3 grid((Q + kAreaWaves - 1) / kAreaWaves, 1, 1), blk(64 * kAreaWaves, 1, 1);
+    ORBX_LAUNCH(k_area_search, grid, blk, 0, h->s0, dq, dqd, Q, D.kps, D.ur, D.desc, D.g, D.cell_start, D.cell_items, 1, o.counter, (int)pool, o.start, o.count, o.ent, 0);
+}
+// The candidate-pool protocol of the single-frame searches.  launch(block, pool) enqueues the kernels that zero the counter and fill the block
+// for Q queries.  Results come back in one copy: the number of entries fetched with the header (and the caller's `mid` bytes, *mid_host
+// afterwards) is a guess from the previous call, a second copy follows only if it was too small, and the pool is grown and the launch
+// repeated if the pool itself overflowed (the first call of a much denser scene).  *out reads the pinned block: valid until the handle's next search.
+template <typename Launch>
+int pooled_area_search(orbx_extractor* h, int Q, size_t mid_bytes, const char* what, const Launch& launch, Cands* out, const uint8_t** mid_host = nullptr) {
+    const size_t oent = al16(16 + 8 * (size_t)Q) + mid_bytes;       // bytes in front of the entries
     size_t pool = std::max<size_t>(h->area_pool, (size_t)Q * 48 + 1024);
     for (int attempt = 0; attempt < 2; attempt++) {
-        if (h->d_sr[SR_ENTRIES].ensure(hdr + pool * 8 + 16)) return fail(ORBX_E_DEVICE, "entry pool allocation failed");
+        if (h->d_sr[SR_ENTRIES].ensure(oent + pool * 8 + 16)) return fail(ORBX_E_DEVICE, "entry pool allocation failed");
+        if (h->h_out.ensure(oent + pool * 8 + 16)) return fail(ORBX_E_DEVICE, "pinned allocation failed");
         h->area_pool = pool;
         uint8_t* dout = h->d_sr[SR_ENTRIES].p;
-        int* d_counter = (int*)dout; int* d_start = (int*)(dout + 16); int* d_count = d_start + Q; int2* d_ent = (int2*)(dout + hdr);
-        rt::memset_async(d_counter, 0, 16, h->s0);
-        dim3 grid((Q + kAreaWaves - 1) / kAreaWaves, 1, 1), blk(64 * kAreaWaves, 1, 1);
-        ORBX_LAUNCH(k_area_search, grid, blk, 0, h->s0, dq, dqd, Q, D.kps, D.ur, D.desc, D.g, D.cell_start, D.cell_items, 1, d_counter, (int)pool,
-                    d_start, d_count, d_ent, 0);
+        launch(AreaBlock(dout, Q, mid_bytes), pool);
         const size_t guess = std::min(pool, std::max<size_t>(h->area_last_total + h->area_last_total / 4 + 256, 1024));
-        const size_t oextra = al16(hdr + pool * 8 + 16);
-        if (h->h_out.ensure(oextra + extra_bytes + 16)) return fail(ORBX_E_DEVICE, "pinned allocation failed");
-        rt::copy_d2h(h->h_out.p, dout, hdr + guess * 8, h->s0);
-        if (extra_bytes) { rt::copy_d2h(h->h_out.p + oextra, extra_src, extra_bytes, h->s0); if (extra_host) *extra_host = h->h_out.p + oextra; }
-        if (rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "area search failed: %s", rt::last_error());
+        rt::copy_d2h(h->h_out.p, dout, oent + guess * 8, h->s0);
+        if (rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "%s failed: %s", what, rt::last_error());
         const int total = *(const int*)h->h_out.p;
         if ((size_t)total <= pool) {
             if ((size_t)total > guess) {
-                rt::copy_d2h(h->h_out.p + hdr + guess * 8, dout + hdr + guess * 8, ((size_t)total - guess) * 8, h->s0);
-                if (rt::stream_sync(h->s0)) return fail(ORBX_E_DEVICE, "area search download failed: %s", rt::last_error());
+                rt::copy_d2h(h->h_out.p + oent + guess * 8, dout + oent + guess * 8, ((size_t)total - guess) * 8, h->s0);
+                if (rt::stream_sync(h->s0)) return fail(ORBX_E_DEVICE, "%s download failed: %s", what, rt::last_error());
             }
             h->area_last_total = (size_t)total;
-            memcpy(out->start.data(), h->h_out.p + 16, sizeof(int) * (size_t)Q);
-            memcpy(out->count.data(), h->h_out.p + 16 + sizeof(int) * (size_t)Q, sizeof(int) * (size_t)Q);
-            out->ent.resize(2 * (size_t)total + 2);
-            if (total > 0) memcpy(out->ent.data(), h->h_out.p + hdr, 8 * (size_t)total);
+            const AreaBlock host(h->h_out.p, Q, mid_bytes);
+            *out = Cands(host.start, host.count, (const int*)host.ent, total);
+            if (mid_host) *mid_host = host.mid;
             return ORBX_OK;
         }
         pool = (size_t)total + 1024;
     }
     return fail(ORBX_E_INTERNAL, "entry pool overflow after retry");
 }
-
-// ORBmatcher::ComputeThreeMaxima, src/ORBmatcher.cc:2335-2377
-void three_maxima(const std::vector<int>* histo, int L, int& ind1, int& ind2, int& ind3) {
-    int max1 = 0, max2 = 0, max3 = 0;
-    for (int i = 0; i < L; i++) {
-        const int s = (int)histo[i].size();
-        if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-        else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-        else if (s > max3) { max3 = s; ind3 = i; }
-    }
-    if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-    else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-}
-
-int rot_bin(float a1, float a2) {    // :2118-2123; the 1/HISTO_LENGTH factor is the reference's (kept on purpose)
-    const float factor = 1.0f / HISTO_LENGTH;
-    float rot = a1 - a2;
-    if (rot < 0.0) rot += 360.0f;
-    int bin = (int)round(rot * factor);
-    if (bin == HISTO_LENGTH) bin = 0;
-    return bin;
+// k_area_search for host queries: they and their descriptors go up in one copy (h_packB -> d_sr[SR_QUERY])
+int run_area_search(orbx_extractor* h, const DeviceFrame& D, const std::vector<AreaQuery>& qs, const uint8_t* qdesc, Cands* out) {
+    const int Q = (int)qs.size();
+    *out = Cands();
+    if (Q == 0) return ORBX_OK;
+    Packer pq(h, h->h_packB, SR_QUERY);
+    const size_t pqs = pq.add(qs.data(), sizeof(AreaQuery) * (size_t)Q), pqd = pq.add(qdesc, 32 * (size_t)Q);
+    if (int e = pq.flush()) return fail(ORBX_E_DEVICE, "%s", upload_error(e));
+    return pooled_area_search(h, Q, 0, "area search", [&](const AreaBlock& o, size_t pool) {
+        rt::memset_async(o.counter, 0, 16, h->s0);
+        launch_area_search(h, D, Q, pq.dev<AreaQuery>(pqs), pq.dev<unsigned long long>(pqd), o, pool);
+    }, out);
 }
 
 }  // namespace
@@ -170,9 +290,9 @@ int orbm_get_features_in_area(orbx_extractor* h, const OrbmFrameView* F, float x
     std::vector<AreaQuery> qs(1);
     qs[0].x = x; qs[0].y = y; qs[0].r = r; qs[0].ur = 0; qs[0].min_level = min_level; qs[0].max_level = max_level; qs[0].active = 1; qs[0].gate = 0;
     uint8_t zero[32] = {0};
-    Csr c;
+    Cands c;
     rc = run_area_search(h, D, qs, zero, &c); if (rc) return rc;
-    for (int k = 0; k < c.count[0] && k < cap; k++) indices[k] = c.ent[2 * (size_t)(c.start[0] + k)];
+    for (int k = 0; k < c.count[0] && k < cap; k++) indices[k] = c.idx(0, k);
     return c.count[0];
 }
 
@@ -188,12 +308,13 @@ int orbm_area_search_batch(orbx_extractor* h, const OrbmFrameView* F, const Orbm
         q.x = queries[i].x; q.y = queries[i].y; q.r = queries[i].r; q.min_level = queries[i].min_level; q.max_level = queries[i].max_level;
         q.active = 1; q.gate = 0;
     }
-    Csr c;
+    Cands c;
     rc = run_area_search(h, D, qs, query_desc, &c); if (rc) return rc;
     int total = 0;
     for (int i = 0; i < Q; i++) { start[i] = c.start[i]; count[i] = c.count[i]; total = std::max(total, c.start[i] + c.count[i]); }
-    if (total <= cap && idx && dist && level)
-        for (int k = 0; k < total; k++) { idx[k] = c.ent[2 * (size_t)k]; dist[k] = c.ent[2 * (size_t)k + 1] & 0xFFFF; level[k] = c.ent[2 * (size_t)k + 1] >> 16; }
+    if (total <= cap && idx && dist && level)               // (the queries' spans tile the pool: every entry belongs to one of them)
+        for (int i = 0; i < Q; i++)
+            for (int k = 0; k < c.count[i]; k++) { const int e = c.start[i] + k; idx[e] = c.idx(i, k); dist[e] = c.dist(i, k); level[e] = c.level(i, k); }
     return total;
 }
 
@@ -219,32 +340,12 @@ int orbm_search_by_projection_mappoints(orbx_extractor* h, const OrbmFrameView* 
         q.x = P->proj_x[i]; q.y = P->proj_y[i]; q.r = r * F->scale_factors[lvl]; q.ur = P->proj_xr[i];
         q.min_level = lvl - 1; q.max_level = lvl; q.active = 1; q.gate = 1;
     }
-    Csr c;
+    Cands c;
     rc = run_area_search(h, D, qs, P->desc, &c); if (rc) return rc;
-    // ---- sequential replay of :62-166 ----
     std::vector<uint8_t> occ(N > 0 ? N : 1, 0);
     if (F->occupied) memcpy(occ.data(), F->occupied, N);
     for (int i = 0; i < N; i++) assigned[i] = -1;
-    int nmatches = 0;
-    for (int i = 0; i < M; i++) {
-        if (!qs[i].active || c.count[i] == 0) continue;
-        int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
-        for (int k = 0; k < c.count[i]; k++) {
-            const int idx = c.ent[2 * (size_t)(c.start[i] + k)], dl = c.ent[2 * (size_t)(c.start[i] + k) + 1];
-            if (occ[idx]) continue;
-            const int dist = dl & 0xFFFF, level = dl >> 16;
-            if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = level; bestIdx = idx; }
-            else if (dist < bestDist2) { bestLevel2 = level; bestDist2 = dist; }
-        }
-        if (bestDist <= TH_HIGH) {
-            if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) continue;
-            if (bestLevel != bestLevel2 || bestDist <= nnratio * bestDist2) {
-                assigned[bestIdx] = i;
-                occ[bestIdx] = P->has_obs ? P->has_obs[i] : 1;
-                nmatches++;
-            }
-        }
-    }
+    const int nmatches = replay_mappoints(c, M, nnratio, P->has_obs, occ.data(), assigned);      // (an inactive query has no candidates)
     if (nmatches_out) *nmatches_out = nmatches;
     return ORBX_OK;
 }
@@ -252,68 +353,62 @@ int orbm_search_by_projection_mappoints(orbx_extractor* h, const OrbmFrameView* 
 // ---- C1 on the device: Frame::isInFrustum + MapPoint::PredictScale (k_frustum), alone or in front of SearchByProjection(Frame, MapPoints) ----
 namespace {
 struct FrustumDev { uint8_t* in_view; float* track; int* level; AreaQuery* queries; const unsigned long long* qdesc; };
+// what k_frustum writes for M points, one block per camera: [track 5 M][level M][in_view M]
+struct TrackBlock {
+    size_t level, in_view, bytes;
+    explicit TrackBlock(int M) { Bump b; b.take(20 * (size_t)std::max(M, 1)); level = b.take(4 * (size_t)std::max(M, 1)); in_view = b.take((size_t)std::max(M, 1)); bytes = b.o; }
+};
+void launch_frustum(orbx_extractor* h, const FrustumParams& F, int M, const float* pos, const float* normal, const float* min_d, const float* max_d, const uint8_t* bad,
+                    uint8_t* track, AreaQuery* queries, int* counter) {
+    const TrackBlock T(M);
+    dim3 grid((M + 255) / 256, 1, 1), blk(256, 1, 1);
+    ORBX_LAUNCH(k_frustum, grid, blk, 0, h->s0, F, M, pos, normal, min_d, max_d, bad, track + T.in_view, (float*)track, (int*)(track + T.level), queries, counter,
+                (const FrustumParams*)nullptr);
+}
 int enqueue_frustum(orbx_extractor* h, const OrbmFrustumView* V, const OrbmWorldPointView* P, float cos_limit, bool with_queries, float th, int far_points, float th_far,
                     FrustumDev* out, const FrustumParams* second = nullptr, FrustumDev* out2 = nullptr) {
     if (!V || !P || P->M < 0 || (P->M > 0 && (!P->pos || !P->normal || !P->min_distance || !P->max_distance))) return fail(ORBX_E_ARG, "bad frustum arguments");
     if (V->nlevels < 1 || V->nlevels > kMaxLevels || !V->scale_factors) return fail(ORBX_E_ARG, "bad scale levels");
-    const int M = P->M; const size_t M1 = M > 0 ? M : 1;
-    // inputs -> d_sr[SR_QUERY]: [queries][descriptors][pos][normal][min][max][bad]; outputs -> d_sr[SR_SPARE]: [track 5 M][level M][in_view M]
-    const size_t oq = 0, od = oq + al16(sizeof(AreaQuery) * M1), op = od + al16(32 * M1), on = op + al16(12 * M1), omn = on + al16(12 * M1), omx = omn + al16(4 * M1),
-                 ob = omx + al16(4 * M1), total = ob + al16(M1);
-    const size_t ot = 0, ol = ot + al16(20 * M1), ov = ol + al16(4 * M1), ototal = ov + al16(M1);
-    if (h->h_packB.ensure(total + 16) || h->d_sr[SR_QUERY].ensure(total + 16) || h->d_sr[SR_SPARE].ensure(2 * ototal + 16)) return fail(ORBX_E_DEVICE, "upload/allocation failed");
-    uint8_t* hp = h->h_packB.p;
-    if (M > 0) {
-        if (P->desc) memcpy(hp + od, P->desc, 32 * (size_t)M); else if (with_queries) return fail(ORBX_E_ARG, "map point descriptors missing");
-        memcpy(hp + op, P->pos, 12 * (size_t)M); memcpy(hp + on, P->normal, 12 * (size_t)M);
-        memcpy(hp + omn, P->min_distance, 4 * (size_t)M); memcpy(hp + omx, P->max_distance, 4 * (size_t)M);
-        if (P->is_bad) memcpy(hp + ob, P->is_bad, M); else memset(hp + ob, 0, M);
-    }
-    if (rt::copy_h2d(h->d_sr[SR_QUERY].p + od, hp + od, total - od, h->s0)) return fail(ORBX_E_DEVICE, "upload failed");
-    FrustumParams F; memset(&F, 0, sizeof F);
-    memcpy(F.Rcw, V->Rcw, sizeof F.Rcw); memcpy(F.tcw, V->tcw, sizeof F.tcw); memcpy(F.Ow, V->Ow, sizeof F.Ow);
-    memcpy(F.cam, V->cam, sizeof F.cam); F.kb8 = V->camera_type == 1;
-    F.min_x = V->min_x; F.max_x = V->max_x; F.min_y = V->min_y; F.max_y = V->max_y; F.mbf = V->mbf; F.log_scale_factor = V->log_scale_factor; F.nlevels = V->nlevels;
-    for (int l = 0; l < V->nlevels; l++) F.scale_factors[l] = V->scale_factors[l];
-    F.cos_limit = cos_limit; F.th = th; F.th_far = th_far; F.far_points = far_points;
+    const int M = P->M; const size_t M1 = M > 0 ? M : 1, Mn = M;
+    if (M > 0 && !P->desc && with_queries) return fail(ORBX_E_ARG, "map point descriptors missing");
+    // inputs -> d_sr[SR_QUERY]: [descriptors][pos][normal][min][max][bad], the queries behind them; outputs -> d_sr[SR_SPARE]: one TrackBlock per camera
+    Packer pk(h, h->h_packB, SR_QUERY);
+    const size_t pd = pk.add(P->desc, P->desc ? 32 * Mn : 0), pp = pk.add(P->pos, 12 * Mn), pn = pk.add(P->normal, 12 * Mn), pmn = pk.add(P->min_distance, 4 * Mn),
+                 pmx = pk.add(P->max_distance, 4 * Mn), pb = P->is_bad ? pk.add(P->is_bad, Mn) : pk.fill(0, Mn), pq = pk.room(sizeof(AreaQuery) * M1);
+    const TrackBlock T(M);
+    if (h->d_sr[SR_SPARE].ensure(2 * T.bytes + 16)) return fail(ORBX_E_DEVICE, "upload/allocation failed");
+    if (int e = pk.flush()) return fail(ORBX_E_DEVICE, "%s", upload_error(e));
+    FrustumParams F; fill_frustum_params(V, cos_limit, th, far_points, th_far, &F);     // (k_frustum does not read qcw)
     F.rig_mode = second ? 1 : 0;
-    uint8_t* di = h->d_sr[SR_QUERY].p; uint8_t* dout = h->d_sr[SR_SPARE].p;
-    out->in_view = dout + ov; out->track = (float*)(dout + ot); out->level = (int*)(dout + ol);
-    out->queries = with_queries ? (AreaQuery*)(di + oq) : nullptr; out->qdesc = (const unsigned long long*)(di + od);
-    if (M > 0) {
-        dim3 grid((M + 255) / 256, 1, 1), blk(256, 1, 1);
-        ORBX_LAUNCH(k_frustum, grid, blk, 0, h->s0, F, M, (const float*)(di + op), (const float*)(di + on), (const float*)(di + omn), (const float*)(di + omx),
-                    (const uint8_t*)(di + ob), out->in_view, out->track, out->level, out->queries, (int*)nullptr, (const FrustumParams*)nullptr);
-    }
+    uint8_t* dout = h->d_sr[SR_SPARE].p;
+    out->in_view = dout + T.in_view; out->track = (float*)dout; out->level = (int*)(dout + T.level);
+    out->queries = with_queries ? pk.out<AreaQuery>(pq) : nullptr; out->qdesc = pk.dev<unsigned long long>(pd);
+    if (M > 0) launch_frustum(h, F, M, pk.dev<float>(pp), pk.dev<float>(pn), pk.dev<float>(pmn), pk.dev<float>(pmx), pk.dev<uint8_t>(pb), dout, out->queries, nullptr);
     if (second && out2) {                                           // the second camera of a rig: the same points, its own block behind the first one
-        F.rig_mode = 1;                                             // (both cameras of a rig store nothing for a rejected point; the caller passed V with rig semantics)
-        out2->in_view = dout + ototal + ov; out2->track = (float*)(dout + ototal + ot); out2->level = (int*)(dout + ototal + ol); out2->queries = nullptr; out2->qdesc = out->qdesc;
-        if (M > 0) {
-            dim3 grid((M + 255) / 256, 1, 1), blk(256, 1, 1);
-            ORBX_LAUNCH(k_frustum, grid, blk, 0, h->s0, *second, M, (const float*)(di + op), (const float*)(di + on), (const float*)(di + omn), (const float*)(di + omx),
-                        (const uint8_t*)(di + ob), out2->in_view, out2->track, out2->level, (AreaQuery*)nullptr, (int*)nullptr, (const FrustumParams*)nullptr);
-        }
+        uint8_t* dout2 = dout + T.bytes;                            // (both cameras of a rig store nothing for a rejected point; the caller passed V with rig semantics)
+        out2->in_view = dout2 + T.in_view; out2->track = (float*)dout2; out2->level = (int*)(dout2 + T.level); out2->queries = nullptr; out2->qdesc = out->qdesc;
+        if (M > 0) launch_frustum(h, *second, M, pk.dev<float>(pp), pk.dev<float>(pn), pk.dev<float>(pmn), pk.dev<float>(pmx), pk.dev<uint8_t>(pb), dout2, nullptr, nullptr);
     }
     return ORBX_OK;
 }
-// hands the tracking fields (host copy of the frustum kernel's output block: [track 5 M][level M][in_view M]) to the caller's arrays
+// hands the tracking fields (host copy of one TrackBlock) to the caller's arrays
 void scatter_track(const uint8_t* blk, int M, const OrbmTrackOut* out) {
     if (!out || M <= 0) return;
-    const size_t M1 = M, ol = al16(20 * M1), ov = ol + al16(4 * M1);
+    const TrackBlock T(M);
+    const size_t M1 = M;
     const float* tr = (const float*)blk;
-    if (out->in_view) memcpy(out->in_view, blk + ov, M1);
+    if (out->in_view) memcpy(out->in_view, blk + T.in_view, M1);
     if (out->proj_x) memcpy(out->proj_x, tr, 4 * M1);
     if (out->proj_y) memcpy(out->proj_y, tr + M1, 4 * M1);
     if (out->proj_xr) memcpy(out->proj_xr, tr + 2 * M1, 4 * M1);
     if (out->depth) memcpy(out->depth, tr + 3 * M1, 4 * M1);
     if (out->view_cos) memcpy(out->view_cos, tr + 4 * M1, 4 * M1);
-    if (out->scale_level) memcpy(out->scale_level, blk + ol, 4 * M1);
+    if (out->scale_level) memcpy(out->scale_level, blk + T.level, 4 * M1);
 }
-size_t track_block_bytes(int M) { const size_t M1 = M > 0 ? M : 1; return al16(20 * M1) + al16(4 * M1) + al16(M1); }
 // brings the block back (one copy into pinned memory) and scatters it
 int fetch_frustum(orbx_extractor* h, int M, const FrustumDev& D, const OrbmTrackOut* out) {
     if (M <= 0) return ORBX_OK;
-    const size_t n = track_block_bytes(M);
+    const size_t n = TrackBlock(M).bytes;
     if (h->h_out.ensure(n + 16)) return fail(ORBX_E_DEVICE, "pinned allocation failed");
     if (rt::copy_d2h(h->h_out.p, D.track, n, h->s0) || rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "frustum kernel failed: %s", rt::last_error());
     scatter_track(h->h_out.p, M, out);
@@ -345,14 +440,15 @@ void right_camera_params(const OrbmFrustumRigView* V, float cos_limit, FrustumPa
 }
 void scatter_track_right(const uint8_t* blk, int M, const OrbmTrackOutRight* out) {
     if (!out || M <= 0) return;
-    const size_t M1 = M, ol = al16(20 * M1), ov = ol + al16(4 * M1);
+    const TrackBlock T(M);
+    const size_t M1 = M;
     const float* tr = (const float*)blk;
-    if (out->in_view_r) memcpy(out->in_view_r, blk + ov, M1);
+    if (out->in_view_r) memcpy(out->in_view_r, blk + T.in_view, M1);
     if (out->proj_xr) memcpy(out->proj_xr, tr, 4 * M1);
     if (out->proj_yr) memcpy(out->proj_yr, tr + M1, 4 * M1);
     if (out->depth_r) memcpy(out->depth_r, tr + 3 * M1, 4 * M1);
     if (out->view_cos_r) memcpy(out->view_cos_r, tr + 4 * M1, 4 * M1);
-    if (out->scale_level_r) memcpy(out->scale_level_r, blk + ol, 4 * M1);
+    if (out->scale_level_r) memcpy(out->scale_level_r, blk + T.level, 4 * M1);
 }
 }  // namespace
 
@@ -364,7 +460,7 @@ int orbm_is_in_frustum_rig(orbx_extractor* h, const OrbmFrustumRigView* V, const
     int rc = enqueue_frustum(h, &V->left, P, cos_limit, false, 1.0f, 0, 0.0f, &D, &Fr, &D2); if (rc) return rc;
     const int M = P->M;
     if (M <= 0) return ORBX_OK;
-    const size_t n = track_block_bytes(M);
+    const size_t n = TrackBlock(M).bytes;
     if (h->h_out.ensure(2 * n + 16)) return fail(ORBX_E_DEVICE, "pinned allocation failed");
     if (rt::copy_d2h(h->h_out.p, D.track, 2 * n, h->s0) || rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "frustum kernel failed: %s", rt::last_error());
     scatter_track(h->h_out.p, M, left);
@@ -413,105 +509,38 @@ namespace {
 int search_local_points_core(orbx_extractor* h, const OrbmFrameView* F, const OrbmFrustumView* V, int M, const OrbmWorldPointView* P, const orbm_points* R,
                              const uint8_t* is_bad, const uint8_t* has_obs, float cos_limit, float th, int far_points, float th_far, float nnratio,
                              const OrbmTrackOut* out, int* assigned, int* nmatches_out) {
-    if (!F || F->N < 0 || (F->N > 0 && (!F->keys_un || !F->desc))) return fail(ORBX_E_ARG, "bad frame view");
-    if (F->N >= 65535) return fail(ORBX_E_ARG, "too many keypoints");
+    int rc = frame_check(F); if (rc) return rc;
     if (!V || V->nlevels < 1 || V->nlevels > kMaxLevels || !V->scale_factors) return fail(ORBX_E_ARG, "bad scale levels");
     const int N = F->N;
     for (int i = 0; i < N; i++) assigned[i] = -1;
     if (nmatches_out) *nmatches_out = 0;
     if (M <= 0) return ORBX_OK;
-    const size_t N1 = N > 0 ? N : 1, M1 = M;
+    const size_t M1 = M;
+    if (h->d_sr[SR_QUERY].ensure(sizeof(AreaQuery) * M1 + 16)) return fail(ORBX_E_DEVICE, "upload/allocation failed");
     // input block: frame [keys | descriptors | uRight] | bad flags | (host points: descriptors | pos | normal | min | max)
-    const size_t okp = 0, odesc = okp + al16(sizeof(KeyPointRec) * N1), our = odesc + al16(32 * N1), ob = our + al16(4 * N1), opd = ob + al16(M1),
-                 opp = opd + (R ? 0 : al16(32 * M1)), opn = opp + (R ? 0 : al16(12 * M1)), opmn = opn + (R ? 0 : al16(12 * M1)), opmx = opmn + (R ? 0 : al16(4 * M1)),
-                 in_total = opmx + (R ? 0 : al16(4 * M1));
-    // output block: [counter 16 | start M | count M] | tracking fields | candidate entries
-    const size_t hdr = al16(16 + 8 * M1), trk = track_block_bytes(M), oent = hdr + trk;
-    const size_t pool = std::max<size_t>(h->area_pool, M1 * 48 + 1024);
-    int e = h->h_packA.ensure(in_total + 16) | h->d_sr[SR_KPS].ensure(in_total + 16) | h->d_sr[SR_QUERY].ensure(sizeof(AreaQuery) * M1 + 16) |
-            h->d_sr[SR_ENTRIES].ensure(oent + pool * 8 + 16) | h->h_out.ensure(oent + pool * 8 + 16);
-    e |= h->d_si[SI_CELLOF].ensure(N + 1) | h->d_si[SI_CELLSTART].ensure(64 * 48 + 2) | h->d_si[SI_CELLITEMS].ensure(N + 1);
-    if (e) return fail(ORBX_E_DEVICE, "upload/allocation failed");
-    h->area_pool = pool;
-    uint8_t* hp = h->h_packA.p;
-    if (N > 0) { memcpy(hp + okp, F->keys_un, sizeof(KeyPointRec) * (size_t)N); memcpy(hp + odesc, F->desc, 32 * (size_t)N); }
-    float* ur = (float*)(hp + our);
-    if (F->u_right) memcpy(ur, F->u_right, sizeof(float) * (size_t)N); else for (size_t i = 0; i < N1; i++) ur[i] = -1.0f;
-    if (is_bad) memcpy(hp + ob, is_bad, M1); else memset(hp + ob, 0, M1);
-    if (!R) {
-        memcpy(hp + opd, P->desc, 32 * M1); memcpy(hp + opp, P->pos, 12 * M1); memcpy(hp + opn, P->normal, 12 * M1);
-        memcpy(hp + opmn, P->min_distance, 4 * M1); memcpy(hp + opmx, P->max_distance, 4 * M1);
-    }
-    if (rt::copy_h2d(h->d_sr[SR_KPS].p, hp, in_total, h->s0)) return fail(ORBX_E_DEVICE, "upload failed");
-    const uint8_t* di = h->d_sr[SR_KPS].p;
+    Packer pk(h);
+    size_t pb = 0, pd = 0, pp = 0, pn = 0, pmn = 0, pmx = 0;
     DeviceFrame D;
-    D.kps = (const KeyPointRec*)(di + okp); D.desc = (const unsigned long long*)(di + odesc); D.ur = (const float*)(di + our);
-    memset(&D.g, 0, sizeof D.g);
-    D.g.min_x = F->min_x; D.g.min_y = F->min_y; D.g.gw_inv = F->grid_w_inv; D.g.gh_inv = F->grid_h_inv;
-    D.cell_start = h->d_si[SI_CELLSTART].p; D.cell_items = h->d_si[SI_CELLITEMS].p;
-    const dim3 one(1, 1, 1), blkg(kGridThreads, 1, 1), blk(256, 1, 1);
-    ORBX_LAUNCH(k_grid_build, one, blkg, 0, h->s0, D.kps, N, D.g, h->d_si[SI_CELLOF].p, h->d_si[SI_CELLSTART].p, h->d_si[SI_CELLITEMS].p, (const int*)nullptr, 0);
-    FrustumParams Fp; memset(&Fp, 0, sizeof Fp);
-    memcpy(Fp.Rcw, V->Rcw, sizeof Fp.Rcw); memcpy(Fp.tcw, V->tcw, sizeof Fp.tcw); memcpy(Fp.Ow, V->Ow, sizeof Fp.Ow);
-    memcpy(Fp.cam, V->cam, sizeof Fp.cam); Fp.kb8 = V->camera_type == 1;
-    Fp.min_x = V->min_x; Fp.max_x = V->max_x; Fp.min_y = V->min_y; Fp.max_y = V->max_y; Fp.mbf = V->mbf; Fp.log_scale_factor = V->log_scale_factor; Fp.nlevels = V->nlevels;
-    for (int l = 0; l < V->nlevels; l++) Fp.scale_factors[l] = V->scale_factors[l];
-    Fp.cos_limit = cos_limit; Fp.th = th; Fp.th_far = th_far; Fp.far_points = far_points;
-    uint8_t* dout = h->d_sr[SR_ENTRIES].p;
-    int* d_counter = (int*)dout; int* d_start = (int*)(dout + 16); int* d_count = d_start + M; int2* d_ent = (int2*)(dout + oent);
-    uint8_t* dtrk = dout + hdr;
-    const size_t ol = al16(20 * M1), ov = ol + al16(4 * M1);                        // track block: [track 5 M][level M][in_view M] (scatter_track)
+    rc = upload_frame(h, F, &D, pk, [&] {
+        pb = is_bad ? pk.add(is_bad, M1) : pk.fill(0, M1);
+        if (!R) { pd = pk.add(P->desc, 32 * M1); pp = pk.add(P->pos, 12 * M1); pn = pk.add(P->normal, 12 * M1); pmn = pk.add(P->min_distance, 4 * M1); pmx = pk.add(P->max_distance, 4 * M1); }
+    });
+    if (rc) return rc;
+    FrustumParams Fp; fill_frustum_params(V, cos_limit, th, far_points, th_far, &Fp);     // (k_frustum does not read qcw)
     AreaQuery* dq = (AreaQuery*)h->d_sr[SR_QUERY].p;
-    const unsigned long long* dqd = R ? R->desc : (const unsigned long long*)(di + opd);
-    {
-        dim3 grid((M + 255) / 256, 1, 1);
-        ORBX_LAUNCH(k_frustum, grid, blk, 0, h->s0, Fp, M, R ? R->pos : (const float*)(di + opp), R ? R->normal : (const float*)(di + opn),
-                    R ? R->min_d : (const float*)(di + opmn), R ? R->max_d : (const float*)(di + opmx), (const uint8_t*)(di + ob),
-                    dtrk + ov, (float*)dtrk, (int*)(dtrk + ol), dq, d_counter, (const FrustumParams*)nullptr);
-    }
-    {
-        dim3 grid((M + kAreaWaves - 1) / kAreaWaves, 1, 1), blka(64 * kAreaWaves, 1, 1);
-        ORBX_LAUNCH(k_area_search, grid, blka, 0, h->s0, (const AreaQuery*)dq, dqd, M, D.kps, D.ur, D.desc, D.g, D.cell_start, D.cell_items, 1, d_counter, (int)pool,
-                    d_start, d_count, d_ent, 0);
-    }
-    const size_t guess = std::min(pool, std::max<size_t>(h->area_last_total + h->area_last_total / 4 + 256, 1024));
-    rt::copy_d2h(h->h_out.p, dout, oent + guess * 8, h->s0);
-    if (rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "local point search failed: %s", rt::last_error());
-    const int total = *(const int*)h->h_out.p;
-    if ((size_t)total > pool) {                                     // pool overflow (the first call of a much denser scene): grow and run again
-        h->area_pool = (size_t)total + 1024;
-        return search_local_points_core(h, F, V, M, P, R, is_bad, has_obs, cos_limit, th, far_points, th_far, nnratio, out, assigned, nmatches_out);
-    }
-    if ((size_t)total > guess) {
-        rt::copy_d2h(h->h_out.p + oent + guess * 8, dout + oent + guess * 8, ((size_t)total - guess) * 8, h->s0);
-        if (rt::stream_sync(h->s0)) return fail(ORBX_E_DEVICE, "local point search download failed: %s", rt::last_error());
-    }
-    h->area_last_total = (size_t)total;
-    scatter_track(h->h_out.p + hdr, M, out);
-    const int* q_start = (const int*)(h->h_out.p + 16); const int* q_count = q_start + M; const int* ent = (const int*)(h->h_out.p + oent);
-    // ---- sequential replay of src/ORBmatcher.cc:62-166 (a query without candidates - not in view, far, bad - has count 0) ----
-    std::vector<uint8_t> occ(N1, 0);
+    const unsigned long long* dqd = R ? R->desc : pk.dev<unsigned long long>(pd);
+    // output block: [counter 16 | start M | count M] | tracking fields | candidate entries
+    Cands c; const uint8_t* track = nullptr;
+    rc = pooled_area_search(h, M, TrackBlock(M).bytes, "local point search", [&](const AreaBlock& o, size_t pool) {
+        launch_frustum(h, Fp, M, R ? R->pos : pk.dev<float>(pp), R ? R->normal : pk.dev<float>(pn), R ? R->min_d : pk.dev<float>(pmn), R ? R->max_d : pk.dev<float>(pmx),
+                       pk.dev<uint8_t>(pb), o.mid, dq, o.counter);
+        launch_area_search(h, D, M, dq, dqd, o, pool);
+    }, &c, &track);
+    if (rc) return rc;
+    scatter_track(track, M, out);
+    std::vector<uint8_t> occ(N > 0 ? N : 1, 0);
     if (F->occupied) memcpy(occ.data(), F->occupied, N);
-    int nmatches = 0;
-    for (int i = 0; i < M; i++) {
-        if (q_count[i] == 0) continue;
-        int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
-        for (int k = 0; k < q_count[i]; k++) {
-            const int idx = ent[2 * (size_t)(q_start[i] + k)], dl = ent[2 * (size_t)(q_start[i] + k) + 1];
-            if (occ[idx]) continue;
-            const int dist = dl & 0xFFFF, level = dl >> 16;
-            if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = level; bestIdx = idx; }
-            else if (dist < bestDist2) { bestLevel2 = level; bestDist2 = dist; }
-        }
-        if (bestDist <= TH_HIGH) {
-            if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) continue;
-            if (bestLevel != bestLevel2 || bestDist <= nnratio * bestDist2) {
-                assigned[bestIdx] = i;
-                occ[bestIdx] = has_obs ? has_obs[i] : 1;
-                nmatches++;
-            }
-        }
-    }
+    const int nmatches = replay_mappoints(c, M, nnratio, has_obs, occ.data(), assigned);
     if (nmatches_out) *nmatches_out = nmatches;
     return ORBX_OK;
 }
@@ -561,19 +590,97 @@ int orbm_stereo_from_depth(orbx_extractor* h, int first, int B, const float* dep
     return ORBX_OK;
 }
 
+}  // extern "C"
+namespace {
+// ---- pieces that the batched routes (one camera and rig) share ----
+// the poses of a batch, `stride` bytes apart (a rig batch passes &f[0].left): scale levels, and one grid geometry per batch
+int frames_check(const OrbmFrustumView* f0, size_t stride, int B) {
+    for (int b = 0; b < B; b++) {
+        const OrbmFrustumView& v = *(const OrbmFrustumView*)((const uint8_t*)f0 + (size_t)b * stride);
+        if (v.nlevels < 1 || v.nlevels > kMaxLevels || !v.scale_factors) return fail(ORBX_E_ARG, "bad scale levels (frame %d)", b);
+        // (the frames of a batch come from one extraction: one image size)
+        if (v.min_x != f0->min_x || v.max_x != f0->max_x || v.min_y != f0->min_y || v.max_y != f0->max_y) return fail(ORBX_E_ARG, "frame %d has other image bounds than frame 0", b);
+    }
+    if (!(f0->max_x > f0->min_x) || !(f0->max_y > f0->min_y)) return fail(ORBX_E_ARG, "empty image bounds");
+    return ORBX_OK;
+}
+GridParams grid_from_view(const OrbmFrustumView& v) {
+    GridParams g; memset(&g, 0, sizeof g);
+    g.min_x = v.min_x; g.min_y = v.min_y;
+    g.gw_inv = (float)kGridColsHost / (v.max_x - v.min_x); g.gh_inv = (float)kGridRowsHost / (v.max_y - v.min_y);   // src/Frame.cc:190-191
+    return g;
+}
+// entries of the candidate pool: what the last batch grew it to, or `expected` for this one; the kernels count entries in an int
+size_t batch_pool(const orbx_extractor* h, size_t expected) { return std::min<size_t>(std::max(h->lp_pool, expected), 0x7fffffff / 2); }
+// the grid of one camera for B frames (k_grid_build: cell_of, cell_start, cell_items)
+struct GridBlock {
+    size_t cof, cst, cit;
+    GridBlock(Bump& d, size_t B1, size_t C1) { cof = d.take(4 * B1 * C1); cst = d.take(4 * B1 * kGridCellStride); cit = d.take(4 * B1 * C1); }
+};
+// the result of a batch, [counter 16 | nmatches B | assigned B x slots]: laid out by the enqueue, read back by the fetch
+struct ResultBlock {
+    size_t nmatches, assigned, bytes;
+    ResultBlock(size_t B1, size_t slots) : nmatches(16), assigned(16 + al16(4 * B1)), bytes(assigned + 4 * B1 * slots) {}
+};
+// one record per frame of map points seen from somewhere else: the LastFrame's (octave of its keypoint, has_obs) or a key frame's (distance limits)
+struct PointRows {
+    int cap; const int* n; const float* pos; const uint8_t* valid; const int* octave; const float* angle; const uint8_t* has_obs; const uint8_t* desc;
+    const float* min_distance; const float* max_distance;          // key-frame form only
+};
+PointRows last_frame_rows(const OrbmLastFrameBatch* last) {
+    return {last->cap_last, last->n, last->pos, last->valid, last->octave, last->angle, last->has_obs, last->desc, nullptr, nullptr};
+}
+// their place in the upload block, n_last | pos | valid | octave | angle | has_obs | descriptors, and the copy into the staging buffer
+struct PointRowsUpload {
+    size_t u_n, u_pos, u_val, u_oct, u_ang, u_obs, u_desc;
+    PointRowsUpload(Bump& u, size_t B1, size_t M1) {
+        u_n = u.take(4 * B1); u_pos = u.take(12 * B1 * M1); u_val = u.take(B1 * M1); u_oct = u.take(4 * B1 * M1); u_ang = u.take(4 * B1 * M1); u_obs = u.take(B1 * M1);
+        u_desc = u.take(32 * B1 * M1);
+    }
+    void stage(uint8_t* hp, const PointRows& last, size_t B1, size_t M1) const {
+        memcpy(hp + u_n, last.n, 4 * B1); memcpy(hp + u_pos, last.pos, 12 * B1 * M1); memcpy(hp + u_val, last.valid, B1 * M1);
+        if (last.octave) memcpy(hp + u_oct, last.octave, 4 * B1 * M1); else memcpy(hp + u_oct, last.min_distance, 4 * B1 * M1);      // (a key frame's octave rows carry mfMinDistance)
+        memcpy(hp + u_ang, last.angle, 4 * B1 * M1);
+        if (last.has_obs) memcpy(hp + u_obs, last.has_obs, B1 * M1); else memset(hp + u_obs, 1, B1 * M1);
+        memcpy(hp + u_desc, last.desc, 32 * B1 * M1);
+    }
+};
+// the fetch of the handle's pending batch: `slots` assignments per frame, `nviews` mbTrackInView arrays (fetched when fetch_views says so)
+int batch_fetch(orbx_extractor* h, size_t slots, const char* what, int* assigned, int cap, int* nmatches, int nviews, bool fetch_views, uint8_t* const* views) {
+    rt::set_device(h->device);
+    const size_t B1 = h->lp_B, M1 = h->lp_M > 0 ? h->lp_M : 0;
+    const ResultBlock res(B1, slots);
+    const size_t view_off[2] = {h->lp_o_view, h->lp_o_view_r};
+    uint8_t* hp = h->h_lp_out.p;
+    int e = rt::copy_d2h(hp, h->d_lp.p + h->lp_o_counter, res.bytes, h->s0);
+    if (fetch_views) for (int v = 0; v < nviews; v++) e |= rt::copy_d2h(hp + al16(res.bytes) + v * B1 * M1, h->d_lp.p + view_off[v], B1 * M1, h->s0);
+    if (e || rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "%s failed: %s", what, rt::last_error());
+    h->lp_pending = false;
+    if (h->profile) h->stage_ms[ST_MATCH] = rt::event_elapsed_ms(h->ev_stage[ST_MATCH][0], h->ev_stage[ST_MATCH][1]);
+    const int total = *(const int*)hp;
+    if (h->lp_M > 0 && (size_t)total > h->lp_pool) {                // the candidate pool was too small: the caller enqueues again (the pool has grown)
+        h->lp_pool = (size_t)total + (size_t)total / 8 + 4096;
+        return fail(ORBX_E_CAPACITY, "candidate pool overflow (%d entries): enqueue the search again, the pool has been enlarged", total);
+    }
+    if (nmatches) memcpy(nmatches, hp + res.nmatches, 4 * B1);
+    if (assigned) {
+        const int* src = (const int*)(hp + res.assigned);
+        if ((size_t)cap == slots) memcpy(assigned, src, 4 * B1 * slots);
+        else for (size_t b = 0; b < B1; b++) memcpy(assigned + b * (size_t)cap, src + b * slots, 4 * slots);
+    }
+    if (fetch_views) for (int v = 0; v < nviews; v++) if (views[v]) memcpy(views[v], hp + al16(res.bytes) + v * B1 * M1, B1 * M1);
+    return ORBX_OK;
+}
+}  // namespace
+extern "C" {
+
 int orbm_search_local_points_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView* frames, const orbm_points* points, const uint8_t* is_bad,
                                    const uint8_t* has_obs, const uint8_t* occupied, int use_u_right, float cos_limit, float th, int far_points, float th_far,
                                    float nnratio, int want_in_view) {
     if (h) { h->lp_B = 0; h->lp_rig = false; }     // a new enqueue - accepted or refused - ends the previous batch: a refused call leaves nothing to fetch
     if (!h || !frames || !points || B <= 0 || first < 0 || first + B > h->lastB) return fail(ORBX_E_ARG, "bad frame range / null");
     if (points->device != h->device) return fail(ORBX_E_ARG, "map points live on another device");
-    for (int b = 0; b < B; b++) {
-        if (frames[b].nlevels < 1 || frames[b].nlevels > kMaxLevels || !frames[b].scale_factors) return fail(ORBX_E_ARG, "bad scale levels (frame %d)", b);
-        // one grid geometry per batch (the frames of a batch come from one extraction: one image size)
-        if (frames[b].min_x != frames[0].min_x || frames[b].max_x != frames[0].max_x || frames[b].min_y != frames[0].min_y || frames[b].max_y != frames[0].max_y)
-            return fail(ORBX_E_ARG, "frame %d has other image bounds than frame 0", b);
-    }
-    if (!(frames[0].max_x > frames[0].min_x) || !(frames[0].max_y > frames[0].min_y)) return fail(ORBX_E_ARG, "empty image bounds");
+    if (int rc = frames_check(frames, sizeof *frames, B)) return rc;
     if (undistort_stale(h)) return fail(ORBX_E_ARG, "orbx_set_undistort was called after the last extraction: extract again before searching its frames");
     rt::set_device(h->device);
     const int M = points->M, cap = h->kp_total_cap;
@@ -584,25 +691,18 @@ int orbm_search_local_points_batch(orbx_extractor* h, int first, int B, const Or
     h->lp_B = 0;                                                // the block is about to be overwritten: a previous, unfetched batch is gone
     if (h->lp_pending) { rt::event_sync(h->ev_lp); }            // the staging block of the previous enqueue has been consumed
     // upload block: poses | bad flags | has-observation flags | occupancy
-    const size_t u_f = 0, u_bad = u_f + al16(sizeof(FrustumParams) * B1), u_obs = u_bad + al16(M1), u_occ = u_obs + al16(M1), u_total = u_occ + (occupied ? al16(B1 * C1) : 0);
-    // device block: upload | uRight of "no stereo" | grid (cell_of, cell_start, cell_items) | queries | track | level | in_view | q_start | q_count |
-    // result [counter 16 | nmatches B | assigned B * cap] | entry pool
-    size_t o = al16(u_total);
-    const size_t o_ur = o; o += use_u_right ? 0 : al16(4 * B1 * C1);
-    const size_t o_cof = o; o += al16(4 * B1 * C1);
-    const size_t o_cst = o; o += al16(4 * B1 * kGridCellStride);
-    const size_t o_cit = o; o += al16(4 * B1 * C1);
-    const size_t o_q = o; o += al16(sizeof(AreaQuery) * B1 * M1);
-    const size_t o_trk = o; o += al16(20 * B1 * M1);
-    const size_t o_lvl = o; o += al16(4 * B1 * M1);
-    const size_t o_view = o; o += al16(B1 * M1);
-    const size_t o_qs = o; o += al16(4 * B1 * M1);
-    const size_t o_qc = o; o += al16(4 * B1 * M1);
-    const size_t o_res = o; const size_t res_bytes = 16 + al16(4 * B1) + 4 * B1 * C1; o += al16(res_bytes);
-    const size_t o_pool = o;
-    size_t pool = std::max<size_t>(h->lp_pool, B1 * M1 * 6 + 4096);
-    if (pool > 0x7fffffff / 2) pool = 0x7fffffff / 2;
-    if (h->d_lp.ensure(o_pool + pool * 8 + 64) || h->h_lp_in.ensure(u_total + 16) || h->h_lp_out.ensure(al16(res_bytes) + (want_in_view ? B1 * M1 : 0) + 64))
+    Bump u;
+    const size_t u_f = u.take(sizeof(FrustumParams) * B1), u_bad = u.take(M1), u_obs = u.take(M1), u_occ = u.take(occupied ? B1 * C1 : 0), u_total = u.o;
+    // device block: upload | uRight of "no stereo" | grid | queries | track | level | in_view | q_start | q_count | result | entry pool
+    Bump d(u_total);
+    const size_t o_ur = d.take(use_u_right ? 0 : 4 * B1 * C1);
+    const GridBlock G(d, B1, C1);
+    const size_t o_q = d.take(sizeof(AreaQuery) * B1 * M1), o_trk = d.take(20 * B1 * M1), o_lvl = d.take(4 * B1 * M1), o_view = d.take(B1 * M1), o_qs = d.take(4 * B1 * M1),
+                 o_qc = d.take(4 * B1 * M1);
+    const ResultBlock res(B1, C1);
+    const size_t o_res = d.take(res.bytes), o_pool = d.o;
+    const size_t pool = batch_pool(h, B1 * M1 * 6 + 4096);
+    if (h->d_lp.ensure(o_pool + pool * 8 + 64) || h->h_lp_in.ensure(u_total + 16) || h->h_lp_out.ensure(al16(res.bytes) + (want_in_view ? B1 * M1 : 0) + 64))
         return fail(ORBX_E_DEVICE, "allocation failed (batched local point search, %d frames x %d points)", B, M);
     h->lp_pool = pool;
     uint8_t* hp = h->h_lp_in.p; uint8_t* dp = h->d_lp.p;
@@ -618,14 +718,12 @@ int orbm_search_local_points_batch(orbx_extractor* h, int first, int B, const Or
     const int* nper = h->d_nm.p + first;
     const float* ur = h->d_uRight.p;
     if (!use_u_right) { rt::memset_async(dp + o_ur, 0xBF, 4 * B1 * C1, h->s0); ur = (const float*)(dp + o_ur); }   // 0xBFBFBFBF = -1.498...: a negative uRight = monocular keypoint
-    GridParams g; memset(&g, 0, sizeof g);
-    g.min_x = frames[0].min_x; g.min_y = frames[0].min_y;
-    g.gw_inv = (float)kGridColsHost / (frames[0].max_x - frames[0].min_x); g.gh_inv = (float)kGridRowsHost / (frames[0].max_y - frames[0].min_y);   // src/Frame.cc:190-191
-    int* d_counter = (int*)(dp + o_res); int* d_nmatch = (int*)(dp + o_res + 16); int* d_assigned = (int*)(dp + o_res + 16 + al16(4 * B1));
+    const GridParams g = grid_from_view(frames[0]);
+    int* d_counter = (int*)(dp + o_res); int* d_nmatch = (int*)(dp + o_res + res.nmatches); int* d_assigned = (int*)(dp + o_res + res.assigned);
     if (h->profile) rt::event_record(h->ev_stage[ST_MATCH][0], h->s0);
     {
         dim3 grid(B, 1, 1), blkg(kGridThreads, 1, 1);
-        ORBX_LAUNCH(k_grid_build, grid, blkg, 0, h->s0, kps, 0, g, (int*)(dp + o_cof), (int*)(dp + o_cst), (int*)(dp + o_cit), nper, cap);
+        ORBX_LAUNCH(k_grid_build, grid, blkg, 0, h->s0, kps, 0, g, (int*)(dp + G.cof), (int*)(dp + G.cst), (int*)(dp + G.cit), nper, cap);
     }
     if (M > 0) {
         FrustumParams dummy; memset(&dummy, 0, sizeof dummy);
@@ -633,7 +731,7 @@ int orbm_search_local_points_batch(orbx_extractor* h, int first, int B, const Or
         ORBX_LAUNCH(k_frustum, grid, blk, 0, h->s0, dummy, M, points->pos, points->normal, points->min_d, points->max_d, (const uint8_t*)(dp + u_bad),
                     dp + o_view, (float*)(dp + o_trk), (int*)(dp + o_lvl), (AreaQuery*)(dp + o_q), d_counter, (const FrustumParams*)(dp + u_f));
         dim3 grida((M + 255) / 256, B, 1);
-        ORBX_LAUNCH(k_area_search_threads, grida, blk, 0, h->s0, (const AreaQuery*)(dp + o_q), points->desc, M, kps, ur, fdesc, g, (const int*)(dp + o_cst), (const int*)(dp + o_cit), 1,
+        ORBX_LAUNCH(k_area_search_threads, grida, blk, 0, h->s0, (const AreaQuery*)(dp + o_q), points->desc, M, kps, ur, fdesc, g, (const int*)(dp + G.cst), (const int*)(dp + G.cit), 1,
                     d_counter, (int)pool, (int*)(dp + o_qs), (int*)(dp + o_qc), (int2*)(dp + o_pool), cap, 0);
     } else rt::memset_async(d_counter, 0, 16, h->s0);
     {
@@ -649,22 +747,12 @@ int orbm_search_local_points_batch(orbx_extractor* h, int first, int B, const Or
 }
 
 namespace {
-// one record per frame of map points seen from somewhere else: the LastFrame's (octave of its keypoint, has_obs) or a key frame's (distance limits)
-struct PointRows {
-    int cap; const int* n; const float* pos; const uint8_t* valid; const int* octave; const float* angle; const uint8_t* has_obs; const uint8_t* desc;
-    const float* min_distance; const float* max_distance;          // key-frame form only
-};
 // SearchByProjection(CurrentFrame, LastFrame) (keyframe = false) or (CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (keyframe = true) for B frames
 int projection_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView* cur, const PointRows* last, float th, const uint8_t* forward, const uint8_t* backward,
                      int check_ori, const uint8_t* occupied, int use_u_right, bool keyframe, int th_accept) {
     const int M = last->cap;
-    for (int b = 0; b < B; b++) {
-        if (cur[b].nlevels < 1 || cur[b].nlevels > kMaxLevels || !cur[b].scale_factors) return fail(ORBX_E_ARG, "bad scale levels (frame %d)", b);
-        if (cur[b].min_x != cur[0].min_x || cur[b].max_x != cur[0].max_x || cur[b].min_y != cur[0].min_y || cur[b].max_y != cur[0].max_y)
-            return fail(ORBX_E_ARG, "frame %d has other image bounds than frame 0", b);
-        if (last->n[b] < 0 || last->n[b] > M) return fail(ORBX_E_ARG, "frame %d: %d points in %d rows", b, last->n[b], M);
-    }
-    if (!(cur[0].max_x > cur[0].min_x) || !(cur[0].max_y > cur[0].min_y)) return fail(ORBX_E_ARG, "empty image bounds");
+    if (int rc = frames_check(cur, sizeof *cur, B)) return rc;
+    for (int b = 0; b < B; b++) if (last->n[b] < 0 || last->n[b] > M) return fail(ORBX_E_ARG, "frame %d: %d points in %d rows", b, last->n[b], M);
     if (undistort_stale(h)) return fail(ORBX_E_ARG, "orbx_set_undistort was called after the last extraction: extract again before searching its frames");
     rt::set_device(h->device);
     const int cap = h->kp_total_cap;
@@ -673,23 +761,19 @@ int projection_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView*
     if (smem_accept + 1024 > rt::lds_limit(h->device)) { h->lp_B = 0; return fail(ORBX_E_CAPACITY, "%d keypoints and %d last-frame points per frame need %zu bytes of LDS in the accept kernel", cap, M, smem_accept); }
     h->lp_B = 0;
     if (h->lp_pending) rt::event_sync(h->ev_lp);
-    // upload block: poses | n_last | pos | valid | octave | angle | has_obs | descriptors | occupancy
-    const size_t u_f = 0, u_n = u_f + al16(sizeof(FrustumParams) * B1), u_pos = u_n + al16(4 * B1), u_val = u_pos + al16(12 * B1 * M1), u_oct = u_val + al16(B1 * M1),
-                 u_ang = u_oct + al16(4 * B1 * M1), u_obs = u_ang + al16(4 * B1 * M1), u_desc = u_obs + al16(B1 * M1), u_occ = u_desc + al16(32 * B1 * M1),
-                 u_mxd = u_occ + (occupied ? al16(B1 * C1) : 0), u_total = u_mxd + (keyframe ? al16(4 * B1 * M1) : 0);
-    size_t o = al16(u_total);
-    const size_t o_ur = o; o += use_u_right ? 0 : al16(4 * B1 * C1);
-    const size_t o_cof = o; o += al16(4 * B1 * C1);
-    const size_t o_cst = o; o += al16(4 * B1 * kGridCellStride);
-    const size_t o_cit = o; o += al16(4 * B1 * C1);
-    const size_t o_q = o; o += al16(sizeof(AreaQuery) * B1 * M1);
-    const size_t o_qs = o; o += al16(4 * B1 * M1);
-    const size_t o_qc = o; o += al16(4 * B1 * M1);
-    const size_t o_res = o; const size_t res_bytes = 16 + al16(4 * B1) + 4 * B1 * C1; o += al16(res_bytes);
-    const size_t o_pool = o;
-    size_t pool = std::max<size_t>(h->lp_pool, B1 * M1 * 16 + 4096);           // th = 7 .. 15 px windows: a dozen candidates per point
-    if (pool > 0x7fffffff / 2) pool = 0x7fffffff / 2;
-    if (h->d_lp.ensure(o_pool + pool * 8 + 64) || h->h_lp_in.ensure(u_total + 16) || h->h_lp_out.ensure(al16(res_bytes) + 64))
+    // upload block: poses | the rows (n_last .. descriptors) | occupancy | a key frame's mfMaxDistance rows
+    Bump u;
+    const size_t u_f = u.take(sizeof(FrustumParams) * B1);
+    const PointRowsUpload U(u, B1, M1);
+    const size_t u_occ = u.take(occupied ? B1 * C1 : 0), u_mxd = u.take(keyframe ? 4 * B1 * M1 : 0), u_total = u.o;
+    Bump d(u_total);
+    const size_t o_ur = d.take(use_u_right ? 0 : 4 * B1 * C1);
+    const GridBlock G(d, B1, C1);
+    const size_t o_q = d.take(sizeof(AreaQuery) * B1 * M1), o_qs = d.take(4 * B1 * M1), o_qc = d.take(4 * B1 * M1);
+    const ResultBlock res(B1, C1);
+    const size_t o_res = d.take(res.bytes), o_pool = d.o;
+    const size_t pool = batch_pool(h, B1 * M1 * 16 + 4096);                     // th = 7 .. 15 px windows: a dozen candidates per point
+    if (h->d_lp.ensure(o_pool + pool * 8 + 64) || h->h_lp_in.ensure(u_total + 16) || h->h_lp_out.ensure(al16(res.bytes) + 64))
         return fail(ORBX_E_DEVICE, "allocation failed (batched last-frame search, %d frames x %d points)", B, M);
     h->lp_pool = pool;
     uint8_t* hp = h->h_lp_in.p; uint8_t* dp = h->d_lp.p;
@@ -698,12 +782,8 @@ int projection_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView*
         fill_frustum_params(&cur[b], 0.0f, th, 0, 0.0f, &Fp[b]);
         Fp[b].forward = forward ? forward[b] != 0 : 0; Fp[b].backward = backward ? backward[b] != 0 : 0; Fp[b].debug_flags = h->debug_stereo_flags;
     }
-    memcpy(hp + u_n, last->n, 4 * B1); memcpy(hp + u_pos, last->pos, 12 * B1 * M1); memcpy(hp + u_val, last->valid, B1 * M1);
-    if (keyframe) { memcpy(hp + u_oct, last->min_distance, 4 * B1 * M1); memcpy(hp + u_mxd, last->max_distance, 4 * B1 * M1); }     // (the octave rows carry mfMinDistance)
-    else memcpy(hp + u_oct, last->octave, 4 * B1 * M1);
-    memcpy(hp + u_ang, last->angle, 4 * B1 * M1);
-    if (last->has_obs) memcpy(hp + u_obs, last->has_obs, B1 * M1); else memset(hp + u_obs, 1, B1 * M1);
-    memcpy(hp + u_desc, last->desc, 32 * B1 * M1);
+    U.stage(hp, *last, B1, M1);
+    if (keyframe) memcpy(hp + u_mxd, last->max_distance, 4 * B1 * M1);
     if (occupied) memcpy(hp + u_occ, occupied, B1 * C1);
     if (rt::copy_h2d(dp, hp, u_total, h->s0) || rt::event_record(h->ev_lp, h->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
     h->lp_pending = true;
@@ -712,31 +792,29 @@ int projection_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView*
     const int* nper = h->d_nm.p + first;
     const float* ur = h->d_uRight.p;
     if (!use_u_right) { rt::memset_async(dp + o_ur, 0xBF, 4 * B1 * C1, h->s0); ur = (const float*)(dp + o_ur); }
-    GridParams g; memset(&g, 0, sizeof g);
-    g.min_x = cur[0].min_x; g.min_y = cur[0].min_y;
-    g.gw_inv = (float)kGridColsHost / (cur[0].max_x - cur[0].min_x); g.gh_inv = (float)kGridRowsHost / (cur[0].max_y - cur[0].min_y);
-    int* d_counter = (int*)(dp + o_res); int* d_nmatch = (int*)(dp + o_res + 16); int* d_assigned = (int*)(dp + o_res + 16 + al16(4 * B1));
+    const GridParams g = grid_from_view(cur[0]);
+    int* d_counter = (int*)(dp + o_res); int* d_nmatch = (int*)(dp + o_res + res.nmatches); int* d_assigned = (int*)(dp + o_res + res.assigned);
     if (h->profile) rt::event_record(h->ev_stage[ST_MATCH][0], h->s0);
     const dim3 blk(256, 1, 1);
     {
         dim3 grid(B, 1, 1), blkg(kGridThreads, 1, 1);
-        ORBX_LAUNCH(k_grid_build, grid, blkg, 0, h->s0, kps, 0, g, (int*)(dp + o_cof), (int*)(dp + o_cst), (int*)(dp + o_cit), nper, cap);
+        ORBX_LAUNCH(k_grid_build, grid, blkg, 0, h->s0, kps, 0, g, (int*)(dp + G.cof), (int*)(dp + G.cst), (int*)(dp + G.cit), nper, cap);
     }
     {
         dim3 grid((M + 255) / 256, B, 1);
-        if (keyframe) ORBX_LAUNCH(k_keyframe_queries, grid, blk, 0, h->s0, (const FrustumParams*)(dp + u_f), M, (const int*)(dp + u_n), (const float*)(dp + u_pos),
-                                  (const uint8_t*)(dp + u_val), (const float*)(dp + u_oct), (const float*)(dp + u_mxd), (AreaQuery*)(dp + o_q), d_counter);
-        else ORBX_LAUNCH(k_lastframe_queries, grid, blk, 0, h->s0, (const FrustumParams*)(dp + u_f), M, (const int*)(dp + u_n), (const float*)(dp + u_pos), (const uint8_t*)(dp + u_val),
-                    (const int*)(dp + u_oct), (AreaQuery*)(dp + o_q), d_counter);
-        ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, h->s0, (const AreaQuery*)(dp + o_q), (const unsigned long long*)(dp + u_desc), M, kps, ur, fdesc, g, (const int*)(dp + o_cst),
-                    (const int*)(dp + o_cit), keyframe ? 0 : 1, d_counter, (int)pool, (int*)(dp + o_qs), (int*)(dp + o_qc), (int2*)(dp + o_pool), cap, 1);
+        if (keyframe) ORBX_LAUNCH(k_keyframe_queries, grid, blk, 0, h->s0, (const FrustumParams*)(dp + u_f), M, (const int*)(dp + U.u_n), (const float*)(dp + U.u_pos),
+                                  (const uint8_t*)(dp + U.u_val), (const float*)(dp + U.u_oct), (const float*)(dp + u_mxd), (AreaQuery*)(dp + o_q), d_counter);
+        else ORBX_LAUNCH(k_lastframe_queries, grid, blk, 0, h->s0, (const FrustumParams*)(dp + u_f), M, (const int*)(dp + U.u_n), (const float*)(dp + U.u_pos),
+                         (const uint8_t*)(dp + U.u_val), (const int*)(dp + U.u_oct), (AreaQuery*)(dp + o_q), d_counter);
+        ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, h->s0, (const AreaQuery*)(dp + o_q), (const unsigned long long*)(dp + U.u_desc), M, kps, ur, fdesc, g, (const int*)(dp + G.cst),
+                    (const int*)(dp + G.cit), keyframe ? 0 : 1, d_counter, (int)pool, (int*)(dp + o_qs), (int*)(dp + o_qc), (int2*)(dp + o_pool), cap, 1);
     }
     {
         dim3 grid(B, 1, 1), blka(64, 1, 1);
         const size_t smem = smem_accept;
         ORBX_LAUNCH(k_lastframe_accept, grid, blka, smem, h->s0, M, cap, nper, (const int*)(dp + o_qs), (const int*)(dp + o_qc), (const int2*)(dp + o_pool),
-                    occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr, (const uint8_t*)(dp + u_obs), th_accept, d_assigned, d_nmatch,
-                    (const float*)(dp + u_ang), kps, check_ori);
+                    occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr, (const uint8_t*)(dp + U.u_obs), th_accept, d_assigned, d_nmatch,
+                    (const float*)(dp + U.u_ang), kps, check_ori);
     }
     if (h->profile) rt::event_record(h->ev_stage[ST_MATCH][1], h->s0);
     if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
@@ -750,7 +828,7 @@ int orbm_search_by_projection_lastframe_batch(orbx_extractor* h, int first, int 
     if (h) { h->lp_B = 0; h->lp_rig = false; }
     if (!h || !cur || !last || B <= 0 || first < 0 || first + B > h->lastB) return fail(ORBX_E_ARG, "bad frame range / null");
     if (last->cap_last <= 0 || !last->n || !last->pos || !last->valid || !last->octave || !last->angle || !last->desc) return fail(ORBX_E_ARG, "bad last-frame batch");
-    const PointRows R = {last->cap_last, last->n, last->pos, last->valid, last->octave, last->angle, last->has_obs, last->desc, nullptr, nullptr};
+    const PointRows R = last_frame_rows(last);
     return projection_batch(h, first, B, cur, &R, th, forward, backward, check_ori, occupied, use_u_right, false, TH_HIGH);
 }
 
@@ -769,27 +847,10 @@ int orbm_search_local_points_fetch(orbx_extractor* h, int* assigned, int cap, in
     if (!h || h->lp_B <= 0) return fail(ORBX_E_ARG, "no batched local point search is pending");
     if (h->lp_rig) return fail(ORBX_E_ARG, "the pending batch is a rig batch: fetch it with orbm_search_rig_batch_fetch");
     if (assigned && cap < h->kp_total_cap) return fail(ORBX_E_CAPACITY, "assigned rows need %d entries", h->kp_total_cap);
-    rt::set_device(h->device);
-    const size_t B1 = h->lp_B, M1 = h->lp_M > 0 ? h->lp_M : 1, C1 = h->kp_total_cap;
-    const size_t res_bytes = 16 + al16(4 * B1) + 4 * B1 * C1;
-    uint8_t* hp = h->h_lp_out.p;
-    int e = rt::copy_d2h(hp, h->d_lp.p + h->lp_o_counter, res_bytes, h->s0);
-    if (in_view && h->lp_want_view && h->lp_M > 0) e |= rt::copy_d2h(hp + al16(res_bytes), h->d_lp.p + h->lp_o_view, B1 * M1, h->s0);
-    if (e || rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "batched local point search failed: %s", rt::last_error());
-    h->lp_pending = false;
-    if (h->profile) h->stage_ms[ST_MATCH] = rt::event_elapsed_ms(h->ev_stage[ST_MATCH][0], h->ev_stage[ST_MATCH][1]);
-    const int total = *(const int*)hp;
-    if (h->lp_M > 0 && (size_t)total > h->lp_pool) {                // the candidate pool was too small: the caller enqueues again (the pool has grown)
-        h->lp_pool = (size_t)total + (size_t)total / 8 + 4096;
-        return fail(ORBX_E_CAPACITY, "candidate pool overflow (%d entries): enqueue the search again, the pool has been enlarged", total);
-    }
-    if (nmatches) memcpy(nmatches, hp + 16, 4 * B1);
-    if (assigned) {
-        const int* src = (const int*)(hp + 16 + al16(4 * B1));
-        if ((size_t)cap == C1) memcpy(assigned, src, 4 * B1 * C1);
-        else for (size_t b = 0; b < B1; b++) memcpy(assigned + b * (size_t)cap, src + b * C1, 4 * C1);
-    }
-    if (in_view) { if (h->lp_want_view && h->lp_M > 0) memcpy(in_view, hp + al16(res_bytes), B1 * M1); else return fail(ORBX_E_ARG, "in_view was not requested at enqueue time"); }
+    const bool fetch_view = in_view && h->lp_want_view && h->lp_M > 0;
+    const int rc = batch_fetch(h, h->kp_total_cap, "batched local point search", assigned, cap, nmatches, 1, fetch_view, &in_view);
+    if (rc) return rc;
+    if (in_view && !fetch_view) return fail(ORBX_E_ARG, "in_view was not requested at enqueue time");
     return ORBX_OK;
 }
 
@@ -816,35 +877,24 @@ int orbm_search_by_projection_frame(orbx_extractor* h, const OrbmFrameView* Cur,
         else { q.min_level = oct - 1; q.max_level = oct + 1; }
         q.active = 1; q.gate = 1;
     }
-    Csr c;
+    Cands c;
     rc = run_area_search(h, D, qs, Last->desc, &c); if (rc) return rc;
     std::vector<uint8_t> occ(N > 0 ? N : 1, 0);
     if (Cur->occupied) memcpy(occ.data(), Cur->occupied, N);
     for (int i = 0; i < N; i++) assigned[i] = -1;
-    std::vector<int> rotHist[HISTO_LENGTH];
+    RotHist hist;
     int nmatches = 0;
     for (int i = 0; i < NL; i++) {
         if (!qs[i].active || c.count[i] == 0) continue;
-        int bestDist = 256, bestIdx2 = -1;
-        for (int k = 0; k < c.count[i]; k++) {
-            const int i2 = c.ent[2 * (size_t)(c.start[i] + k)], dist = c.ent[2 * (size_t)(c.start[i] + k) + 1] & 0xFFFF;
-            if (occ[i2]) continue;
-            if (dist < bestDist) { bestDist = dist; bestIdx2 = i2; }
-        }
-        if (bestDist <= TH_HIGH) {
-            assigned[bestIdx2] = i;
-            occ[bestIdx2] = Last->has_obs ? Last->has_obs[i] : 1;
+        const Best b = scan_best(c, i, occ.data());
+        if (b.dist <= TH_HIGH) {
+            assigned[b.idx] = i;
+            occ[b.idx] = Last->has_obs ? Last->has_obs[i] : 1;
             nmatches++;
-            if (check_ori) rotHist[rot_bin(Last->angle[i], Cur->keys_un[bestIdx2].angle)].push_back(bestIdx2);
+            if (check_ori) hist.add(Last->angle[i], Cur->keys_un[b.idx].angle, b.idx);
         }
     }
-    if (check_ori) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        three_maxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int i = 0; i < HISTO_LENGTH; i++)
-            if (i != ind1 && i != ind2 && i != ind3)
-                for (int idx : rotHist[i]) { assigned[idx] = -2; nmatches--; }
-    }
+    if (check_ori) hist.prune([&](int idx) { assigned[idx] = -2; nmatches--; });
     if (nmatches_out) *nmatches_out = nmatches;
     return ORBX_OK;
 }
@@ -868,23 +918,19 @@ static int search_for_triangulation_impl(orbx_extractor* h, const OrbmKeyFrameVi
         if (!K2 || K2->N >= 65535 || K2->nlevels > kMaxLevels) return fail(ORBX_E_ARG, "bad neighbour key frame %d", j);
         base2[j + 1] = base2[j] + K2->N; fbase[j + 1] = fbase[j] + K2->fv_start[K2->fv_nodes];
         first_item[j] = (int)items.size();
-        int a = 0, b = 0;
-        while (a < K1->fv_nodes && b < K2->fv_nodes) {
-            const uint32_t na = K1->fv_node_id[a], nb = K2->fv_node_id[b];
-            if (na == nb) {
-                for (int k = K1->fv_start[a]; k < K1->fv_start[a + 1]; k++) {
-                    const int idx1 = (int)K1->fv_feat[k];
-                    if (K1->has_map_point && K1->has_map_point[idx1]) continue;
-                    const bool stereo1 = K1->u_right && K1->u_right[idx1] >= 0;
-                    if (only_stereo && !stereo1) continue;
-                    BowItem it; it.idx1 = idx1; it.start2 = fbase[j] + K2->fv_start[b]; it.cnt2 = K2->fv_start[b + 1] - K2->fv_start[b]; it.out_off = j;
-                    if (it.cnt2 > 0xFFFF) return fail(ORBX_E_ARG, "vocabulary node with more than 65535 features");
-                    items.push_back(it);
-                }
-                a++; b++;
-            } else if (na < nb) { while (a < K1->fv_nodes && K1->fv_node_id[a] < nb) a++; }
-            else { while (b < K2->fv_nodes && K2->fv_node_id[b] < na) b++; }
-        }
+        bool node_too_large = false;
+        for_each_common_node(K1, K2, [&](int a, int b) {
+            for (int k = K1->fv_start[a]; k < K1->fv_start[a + 1]; k++) {
+                const int idx1 = (int)K1->fv_feat[k];
+                if (K1->has_map_point && K1->has_map_point[idx1]) continue;
+                const bool stereo1 = K1->u_right && K1->u_right[idx1] >= 0;
+                if (only_stereo && !stereo1) continue;
+                BowItem it; it.idx1 = idx1; it.start2 = fbase[j] + K2->fv_start[b]; it.cnt2 = K2->fv_start[b + 1] - K2->fv_start[b]; it.out_off = j;
+                node_too_large |= it.cnt2 > 0xFFFF;
+                items.push_back(it);
+            }
+        });
+        if (node_too_large) return fail(ORBX_E_ARG, "vocabulary node with more than 65535 features");
     }
     first_item[n2] = (int)items.size();
     if (items.empty()) return ORBX_OK;
@@ -905,12 +951,7 @@ static int search_for_triangulation_impl(orbx_extractor* h, const OrbmKeyFrameVi
         for (int k = 0; k < nf; k++) feat2[fbase[j] + k] = (int)K2->fv_feat[k] + o;
         BowParams& P = Ps[j]; memset(&P, 0, sizeof P);
         if (F12s) for (int i = 0; i < 9; i++) P.F12[i] = F12s[9 * (size_t)j + i];
-        if (kb8) {                               // Kannala-Brandt cameras: one OrbmKB8Pair per neighbour
-            const OrbmKB8Pair& C = kb8[j];
-            P.kb8 = 1; P.nleft1 = C.nleft1; P.nleft2 = C.nleft2;
-            memcpy(P.cam1, C.cam1, sizeof P.cam1); memcpy(P.cam2, C.cam2, sizeof P.cam2); memcpy(P.R, C.R, sizeof P.R); memcpy(P.t, C.t, sizeof P.t);
-            for (int l = 0; l < K1->nlevels && l < kMaxLevels; l++) P.sigma2_1[l] = K1->level_sigma2[l];
-        }
+        if (kb8) fill_kb8(P, kb8[j], K1->level_sigma2, K1->nlevels);         // Kannala-Brandt cameras: one OrbmKB8Pair per neighbour
         P.ep[0] = eps[2 * (size_t)j]; P.ep[1] = eps[2 * (size_t)j + 1];
         for (int l = 0; l < K2->nlevels; l++) { P.scale2[l] = K2->scale_factors[l]; P.sigma2_2[l] = K2->level_sigma2[l]; }
         P.only_stereo = only_stereo; P.coarse = coarse; P.th_low = TH_LOW;
@@ -939,22 +980,15 @@ static int search_for_triangulation_impl(orbx_extractor* h, const OrbmKeyFrameVi
         const OrbmKeyFrameView* K2 = K2s[j];
         int* m12 = matches12 + (size_t)j * N1;
         int nmatches = 0;
-        std::vector<int> rotHist[HISTO_LENGTH];
+        RotHist hist;
         for (int k = first_item[j]; k < first_item[j + 1]; k++) {
             if (best[k] < 0) continue;
             const int idx1 = items[k].idx1, idx2 = best[k] - base2[j];
             m12[idx1] = idx2;
             nmatches++;
-            if (check_ori) rotHist[rot_bin(K1->keys_un[idx1].angle, K2->keys_un[idx2].angle)].push_back(idx1);
+            if (check_ori) hist.add(K1->keys_un[idx1].angle, K2->keys_un[idx2].angle, idx1);
         }
-        if (check_ori) {
-            int ind1 = -1, ind2 = -1, ind3 = -1;
-            three_maxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-            for (int i = 0; i < HISTO_LENGTH; i++) {
-                if (i == ind1 || i == ind2 || i == ind3) continue;
-                for (int idx1 : rotHist[i]) { m12[idx1] = -1; nmatches--; }
-            }
-        }
+        if (check_ori) hist.prune([&](int idx1) { m12[idx1] = -1; nmatches--; });           // :1270-1286
         if (nmatches_out) nmatches_out[j] = nmatches;
     }
     return ORBX_OK;
@@ -998,21 +1032,15 @@ int orbm_search_by_bow_batch(orbx_extractor* h, int n, const OrbmKeyFrameView* c
         if (nmatches_out) nmatches_out[p] = 0;
         first_item[p] = (int)items.size(); obase[p] = total;
         base1[p + 1] = base1[p] + K1->N; base2[p + 1] = base2[p] + K2->N; fbase2[p + 1] = fbase2[p] + K2->fv_start[K2->fv_nodes];
-        int a = 0, b = 0;
-        while (a < K1->fv_nodes && b < K2->fv_nodes) {
-            const uint32_t na = K1->fv_node_id[a], nb = K2->fv_node_id[b];
-            if (na == nb) {
-                for (int k = K1->fv_start[a]; k < K1->fv_start[a + 1]; k++) {
-                    const int idx1 = (int)K1->fv_feat[k];
-                    if (!K1->has_map_point || !K1->has_map_point[idx1]) continue;     // !pMP || pMP->isBad()
-                    BowItem it; it.idx1 = base1[p] + idx1; it.start2 = fbase2[p] + K2->fv_start[b]; it.cnt2 = K2->fv_start[b + 1] - K2->fv_start[b]; it.out_off = total;
-                    total += it.cnt2;
-                    items.push_back(it);
-                }
-                a++; b++;
-            } else if (na < nb) { while (a < K1->fv_nodes && K1->fv_node_id[a] < nb) a++; }
-            else { while (b < K2->fv_nodes && K2->fv_node_id[b] < na) b++; }
-        }
+        for_each_common_node(K1, K2, [&](int a, int b) {
+            for (int k = K1->fv_start[a]; k < K1->fv_start[a + 1]; k++) {
+                const int idx1 = (int)K1->fv_feat[k];
+                if (!K1->has_map_point || !K1->has_map_point[idx1]) continue;     // !pMP || pMP->isBad()
+                BowItem it; it.idx1 = base1[p] + idx1; it.start2 = fbase2[p] + K2->fv_start[b]; it.cnt2 = K2->fv_start[b + 1] - K2->fv_start[b]; it.out_off = total;
+                total += it.cnt2;
+                items.push_back(it);
+            }
+        });
     }
     first_item[n] = (int)items.size(); obase[n] = total;
     if (items.empty() || total == 0) return ORBX_OK;
@@ -1044,7 +1072,7 @@ int orbm_search_by_bow_batch(orbx_extractor* h, int n, const OrbmKeyFrameView* c
         int nmatches = 0;
         // sequential replay: a target taken by an earlier feature is skipped (:331 vpMapPointMatches[realIdxF], :948 vbMatched2[idx2])
         std::vector<uint8_t> taken(N2 > 0 ? N2 : 1, 0);
-        std::vector<int> rotHist[HISTO_LENGTH];
+        RotHist hist;
         for (int q = first_item[p]; q < first_item[p + 1]; q++) {
             const BowItem& it = items[q];
             const int idx1 = it.idx1 - base1[p];
@@ -1061,17 +1089,10 @@ int orbm_search_by_bow_batch(orbx_extractor* h, int n, const OrbmKeyFrameView* c
                 m12[idx1] = bestIdx2;
                 taken[bestIdx2] = 1;
                 nmatches++;
-                if (check_ori) rotHist[rot_bin(K1->keys_un[idx1].angle, K2->keys_un[bestIdx2].angle)].push_back(idx1);
+                if (check_ori) hist.add(K1->keys_un[idx1].angle, K2->keys_un[bestIdx2].angle, idx1);
             }
         }
-        if (check_ori) {
-            int ind1 = -1, ind2 = -1, ind3 = -1;
-            three_maxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-            for (int i = 0; i < HISTO_LENGTH; i++) {
-                if (i == ind1 || i == ind2 || i == ind3) continue;
-                for (int idx1 : rotHist[i]) { m12[idx1] = -1; nmatches--; }
-            }
-        }
+        if (check_ori) hist.prune([&](int idx1) { m12[idx1] = -1; nmatches--; });
         if (nmatches_out) nmatches_out[p] = nmatches;
     }
     return ORBX_OK;
@@ -1141,20 +1162,13 @@ void orbm_keyframe_destroy(orbm_keyframe* kf) {
 // histogram are reset (src/ORBmatcher.cc:1270-1286); returns the number of matches left
 static int prune_by_rotation(const orbm_keyframe* K1, const orbm_keyframe* K2, int* m12, bool check_ori) {
     int nmatches = 0;
-    std::vector<int> rotHist[HISTO_LENGTH];
+    RotHist hist;
     for (int i = 0; i < K1->N; i++) {
         if (m12[i] < 0) continue;
         nmatches++;
-        if (check_ori) rotHist[rot_bin(K1->angle[i], K2->angle[m12[i]])].push_back(i);
+        if (check_ori) hist.add(K1->angle[i], K2->angle[m12[i]], i);
     }
-    if (check_ori) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        three_maxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int i = 0; i < HISTO_LENGTH; i++) {
-            if (i == ind1 || i == ind2 || i == ind3) continue;
-            for (int idx1 : rotHist[i]) { m12[idx1] = -1; nmatches--; }
-        }
-    }
+    if (check_ori) hist.prune([&](int idx1) { m12[idx1] = -1; nmatches--; });
     return nmatches;
 }
 
@@ -1179,12 +1193,7 @@ static int sft_resident_impl(orbx_extractor* h, orbm_keyframe* K1, const uint8_t
         P.ep[0] = eps[2 * (size_t)j]; P.ep[1] = eps[2 * (size_t)j + 1];
         for (int l = 0; l < kMaxLevels; l++) { P.scale2[l] = K2->scale[l]; P.sigma2_2[l] = K2->sigma2[l]; }
         P.only_stereo = only_stereo; P.coarse = coarse; P.th_low = TH_LOW; P.nleft1 = P.nleft2 = -1;
-        if (kb8) {                               // Kannala-Brandt cameras: one OrbmKB8Pair per neighbour (as orbm_search_for_triangulation_kb8)
-            const OrbmKB8Pair& C = kb8[j];
-            P.kb8 = 1; P.nleft1 = C.nleft1; P.nleft2 = C.nleft2;
-            memcpy(P.cam1, C.cam1, sizeof P.cam1); memcpy(P.cam2, C.cam2, sizeof P.cam2); memcpy(P.R, C.R, sizeof P.R); memcpy(P.t, C.t, sizeof P.t);
-            for (int l = 0; l < kMaxLevels; l++) P.sigma2_1[l] = K1->sigma2[l];
-        }
+        if (kb8) fill_kb8(P, kb8[j], K1->sigma2, kMaxLevels);                // Kannala-Brandt cameras: one OrbmKB8Pair per neighbour (as orbm_search_for_triangulation_kb8)
     }
     std::vector<uint8_t> flags(ftotal, 0);
     if (has_mp1) memcpy(flags.data(), has_mp1, (size_t)N1);
@@ -1414,21 +1423,16 @@ int orbm_search_by_bow_fisheye(orbx_extractor* h, const OrbmKeyFrameView* K1, co
     const int N1 = K1->N, N2 = K2->N;
     for (int i = 0; i < N2; i++) assigned2[i] = -1;
     std::vector<BowItem> items;
-    int a = 0, b = 0, total = 0;
-    while (a < K1->fv_nodes && b < K2->fv_nodes) {
-        const uint32_t na = K1->fv_node_id[a], nb = K2->fv_node_id[b];
-        if (na == nb) {
-            for (int k = K1->fv_start[a]; k < K1->fv_start[a + 1]; k++) {
-                const int idx1 = (int)K1->fv_feat[k];
-                if (!K1->has_map_point || !K1->has_map_point[idx1]) continue;     // !pMP || pMP->isBad()
-                BowItem it; it.idx1 = idx1; it.start2 = K2->fv_start[b]; it.cnt2 = K2->fv_start[b + 1] - K2->fv_start[b]; it.out_off = total;
-                total += it.cnt2;
-                items.push_back(it);
-            }
-            a++; b++;
-        } else if (na < nb) { while (a < K1->fv_nodes && K1->fv_node_id[a] < nb) a++; }
-        else { while (b < K2->fv_nodes && K2->fv_node_id[b] < na) b++; }
-    }
+    int total = 0;
+    for_each_common_node(K1, K2, [&](int a, int b) {
+        for (int k = K1->fv_start[a]; k < K1->fv_start[a + 1]; k++) {
+            const int idx1 = (int)K1->fv_feat[k];
+            if (!K1->has_map_point || !K1->has_map_point[idx1]) continue;     // !pMP || pMP->isBad()
+            BowItem it; it.idx1 = idx1; it.start2 = K2->fv_start[b]; it.cnt2 = K2->fv_start[b + 1] - K2->fv_start[b]; it.out_off = total;
+            total += it.cnt2;
+            items.push_back(it);
+        }
+    });
     int nmatches = 0;
     if (!items.empty() && total > 0) {
         std::vector<uint8_t> elig(N2 > 0 ? N2 : 1, 1);
@@ -1443,7 +1447,7 @@ int orbm_search_by_bow_fisheye(orbx_extractor* h, const OrbmKeyFrameView* K1, co
         std::vector<int> dist((size_t)total);
         if (fetch_sync(h, dist.data(), h->d_si[SI_BEST].p, sizeof(int) * (size_t)total) || rt::check_launch())
             return fail(ORBX_E_DEVICE, "bow distances failed: %s", rt::last_error());
-        std::vector<int> rotHist[HISTO_LENGTH];
+        RotHist hist;
         for (const BowItem& it : items) {
             int bestDist1 = 256, bestIdxF = -1, bestDist2 = 256, bestDist1R = 256, bestIdxFR = -1, bestDist2R = 256;
             for (int j = 0; j < it.cnt2; j++) {
@@ -1462,23 +1466,16 @@ int orbm_search_by_bow_fisheye(orbx_extractor* h, const OrbmKeyFrameView* K1, co
                 if (static_cast<float>(bestDist1) < nnratio * static_cast<float>(bestDist2)) {
                     assigned2[bestIdxF] = it.idx1;
                     nmatches++;
-                    if (check_ori) rotHist[rot_bin(K1->keys_un[it.idx1].angle, K2->keys_un[bestIdxF].angle)].push_back(bestIdxF);
+                    if (check_ori) hist.add(K1->keys_un[it.idx1].angle, K2->keys_un[bestIdxF].angle, bestIdxF);
                 }
                 if (bestDist1R <= TH_LOW) {
                     assigned2[bestIdxFR] = it.idx1;
                     nmatches++;
-                    if (check_ori) rotHist[rot_bin(K1->keys_un[it.idx1].angle, K2->keys_un[bestIdxFR].angle)].push_back(bestIdxFR);
+                    if (check_ori) hist.add(K1->keys_un[it.idx1].angle, K2->keys_un[bestIdxFR].angle, bestIdxFR);
                 }
             }
         }
-        if (check_ori) {
-            int ind1 = -1, ind2 = -1, ind3 = -1;
-            three_maxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-            for (int i = 0; i < HISTO_LENGTH; i++) {
-                if (i == ind1 || i == ind2 || i == ind3) continue;
-                for (int idx2 : rotHist[i]) { assigned2[idx2] = -1; nmatches--; }
-            }
-        }
+        if (check_ori) hist.prune([&](int idx2) { assigned2[idx2] = -1; nmatches--; });
     }
     if (nmatches_out) *nmatches_out = nmatches;
     return ORBX_OK;
@@ -1499,18 +1496,18 @@ int orbm_search_for_initialization(orbx_extractor* h, const OrbmFrameView* F1, c
         if (level1 > 0) continue;                                   // :755-757 only level-0 keypoints
         q.x = prev[2 * i]; q.y = prev[2 * i + 1]; q.r = (float)window_size; q.min_level = level1; q.max_level = level1; q.active = 1; q.gate = 0;
     }
-    Csr c;
+    Cands c;
     rc = run_area_search(h, D, qs, F1->desc, &c); if (rc) return rc;
     for (int i = 0; i < N1; i++) matches12[i] = -1;
     std::vector<int> matched_dist(N2 > 0 ? N2 : 1, 0x7FFFFFFF), matches21(N2 > 0 ? N2 : 1, -1);
-    std::vector<int> rotHist[HISTO_LENGTH];
+    RotHist hist;
     int nmatches = 0;
     for (int i1 = 0; i1 < N1; i1++) {
         if (!qs[i1].active || c.count[i1] == 0) continue;
         int bestDist = 0x7FFFFFFF, bestDist2 = 0x7FFFFFFF, bestIdx2 = -1;
         for (int k = 0; k < c.count[i1]; k++) {
-            const int i2 = c.ent[2 * (size_t)(c.start[i1] + k)], dist = c.ent[2 * (size_t)(c.start[i1] + k) + 1] & 0xFFFF;
-            if (matched_dist[i2] <= dist) continue;
+            const int i2 = c.idx(i1, k), dist = c.dist(i1, k);
+            if (matched_dist[i2] <= dist) continue;                    // :790 (not the occupancy skip of the other scans)
             if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestIdx2 = i2; }
             else if (dist < bestDist2) bestDist2 = dist;
         }
@@ -1519,18 +1516,11 @@ int orbm_search_for_initialization(orbx_extractor* h, const OrbmFrameView* F1, c
                 if (matches21[bestIdx2] >= 0) { matches12[matches21[bestIdx2]] = -1; nmatches--; }
                 matches12[i1] = bestIdx2; matches21[bestIdx2] = i1; matched_dist[bestIdx2] = bestDist;
                 nmatches++;
-                if (check_ori) rotHist[rot_bin(F1->keys_un[i1].angle, F2->keys_un[bestIdx2].angle)].push_back(i1);
+                if (check_ori) hist.add(F1->keys_un[i1].angle, F2->keys_un[bestIdx2].angle, i1);
             }
         }
     }
-    if (check_ori) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        three_maxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int i = 0; i < HISTO_LENGTH; i++) {
-            if (i == ind1 || i == ind2 || i == ind3) continue;
-            for (int idx1 : rotHist[i]) if (matches12[idx1] >= 0) { matches12[idx1] = -1; nmatches--; }
-        }
-    }
+    if (check_ori) hist.prune([&](int idx1) { if (matches12[idx1] >= 0) { matches12[idx1] = -1; nmatches--; } });
     for (int i1 = 0; i1 < N1; i1++) if (matches12[i1] >= 0) { prev[2 * i1] = F2->keys_un[matches12[i1]].x; prev[2 * i1 + 1] = F2->keys_un[matches12[i1]].y; }
     if (nmatches_out) *nmatches_out = nmatches;
     return ORBX_OK;
@@ -1546,7 +1536,7 @@ namespace {
 
 // one k_area_search over P's valid points: window radius th * scale[pred], levels [pred-1, pred+hi]
 int projected_candidates(orbx_extractor* h, const OrbmFrameView* F, const OrbmProjectedPointView* P, float th, int hi, int gate,
-                         const float* inv_sigma2, std::vector<AreaQuery>* qs, Csr* c) {
+                         const float* inv_sigma2, std::vector<AreaQuery>* qs, Cands* c) {
     if (!P || P->M < 0 || (P->M > 0 && (!P->valid || !P->u || !P->v || !P->pred_level || !P->desc))) return fail(ORBX_E_ARG, "bad point view");
     if (F && F->nlevels > kMaxLevels) return fail(ORBX_E_ARG, "too many levels");
     DeviceFrame D;
@@ -1612,7 +1602,7 @@ int orbm_search_by_projection_sim3(orbx_extractor* h, const OrbmFrameView* KF, c
                                    int* assigned, int* nmatches_out) {
     if (!h || !KF || !P || !assigned) return fail(ORBX_E_ARG, "null");
     rt::set_device(h->device);
-    std::vector<AreaQuery> qs; Csr c;
+    std::vector<AreaQuery> qs; Cands c;
     int rc = projected_candidates(h, KF, P, th, 0, 0, nullptr, &qs, &c); if (rc) return rc;
     const int N = KF->N;
     std::vector<uint8_t> occ(N > 0 ? N : 1, 0);
@@ -1621,13 +1611,8 @@ int orbm_search_by_projection_sim3(orbx_extractor* h, const OrbmFrameView* KF, c
     int nmatches = 0;
     for (int i = 0; i < P->M; i++) {                                 // src/ORBmatcher.cc:519-606 / :640-727
         if (!qs[i].active || c.count[i] == 0) continue;
-        int bestDist = 256, bestIdx = -1;
-        for (int k = 0; k < c.count[i]; k++) {
-            const int idx = c.ent[2 * (size_t)(c.start[i] + k)], dist = c.ent[2 * (size_t)(c.start[i] + k) + 1] & 0xFFFF;
-            if (occ[idx]) continue;
-            if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
-        }
-        if (bestIdx >= 0 && bestDist <= TH_LOW * ratio_hamming) { assigned[bestIdx] = i; occ[bestIdx] = 1; nmatches++; }
+        const Best b = scan_best(c, i, occ.data());
+        if (b.idx >= 0 && b.dist <= TH_LOW * ratio_hamming) { assigned[b.idx] = i; occ[b.idx] = 1; nmatches++; }
     }
     if (nmatches_out) *nmatches_out = nmatches;
     return ORBX_OK;
@@ -1638,34 +1623,23 @@ int orbm_search_by_projection_keyframe(orbx_extractor* h, const OrbmFrameView* C
     if (!h || !Cur || !P || !assigned) return fail(ORBX_E_ARG, "null");
     if (check_ori && P->M > 0 && !P->angle) return fail(ORBX_E_ARG, "orientation check without key-frame angles");
     rt::set_device(h->device);
-    std::vector<AreaQuery> qs; Csr c;
+    std::vector<AreaQuery> qs; Cands c;
     int rc = projected_candidates(h, Cur, P, th, 1, 0, nullptr, &qs, &c); if (rc) return rc;
     const int N = Cur->N;
     std::vector<uint8_t> occ(N > 0 ? N : 1, 0);
     if (Cur->occupied) memcpy(occ.data(), Cur->occupied, N);        // CurrentFrame.mvpMapPoints[i2] != NULL
     for (int i = 0; i < N; i++) assigned[i] = -1;
-    std::vector<int> rotHist[HISTO_LENGTH];
+    RotHist hist;
     int nmatches = 0;
     for (int i = 0; i < P->M; i++) {                                 // src/ORBmatcher.cc:2213-2290
         if (!qs[i].active || c.count[i] == 0) continue;
-        int bestDist = 256, bestIdx2 = -1;
-        for (int k = 0; k < c.count[i]; k++) {
-            const int i2 = c.ent[2 * (size_t)(c.start[i] + k)], dist = c.ent[2 * (size_t)(c.start[i] + k) + 1] & 0xFFFF;
-            if (occ[i2]) continue;
-            if (dist < bestDist) { bestDist = dist; bestIdx2 = i2; }
-        }
-        if (bestIdx2 >= 0 && bestDist <= orb_dist) {
-            assigned[bestIdx2] = i; occ[bestIdx2] = 1; nmatches++;
-            if (check_ori) rotHist[rot_bin(P->angle[i], Cur->keys_un[bestIdx2].angle)].push_back(bestIdx2);
+        const Best b = scan_best(c, i, occ.data());
+        if (b.idx >= 0 && b.dist <= orb_dist) {
+            assigned[b.idx] = i; occ[b.idx] = 1; nmatches++;
+            if (check_ori) hist.add(P->angle[i], Cur->keys_un[b.idx].angle, b.idx);
         }
     }
-    if (check_ori) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        three_maxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int i = 0; i < HISTO_LENGTH; i++)
-            if (i != ind1 && i != ind2 && i != ind3)
-                for (int idx : rotHist[i]) { assigned[idx] = -2; nmatches--; }
-    }
+    if (check_ori) hist.prune([&](int idx) { assigned[idx] = -2; nmatches--; });
     if (nmatches_out) *nmatches_out = nmatches;
     return ORBX_OK;
 }
@@ -1675,18 +1649,13 @@ int orbm_fuse_candidates(orbx_extractor* h, const OrbmFrameView* KF, const OrbmP
     if (!h || !KF || !P || !best_idx) return fail(ORBX_E_ARG, "null");
     if (chi2_gate && P->M > 0 && !P->ur) return fail(ORBX_E_ARG, "chi-square gate without projected right coordinates");
     rt::set_device(h->device);
-    std::vector<AreaQuery> qs; Csr c;
+    std::vector<AreaQuery> qs; Cands c;
     int rc = projected_candidates(h, KF, P, th, 0, chi2_gate ? 2 : 0, inv_level_sigma2, &qs, &c); if (rc) return rc;
     for (int i = 0; i < P->M; i++) {                                 // src/ORBmatcher.cc:1421-1490 / :1601-1640
-        int bestDist = 256, bestIdx = -1;
-        if (qs[i].active)
-            for (int k = 0; k < c.count[i]; k++) {
-                const int idx = c.ent[2 * (size_t)(c.start[i] + k)], dist = c.ent[2 * (size_t)(c.start[i] + k) + 1] & 0xFFFF;
-                if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
-            }
-        if (bestDist > TH_LOW) bestIdx = -1;                         // :1493 / :1643
+        const Best b = scan_best(c, i, nullptr);                     // no occupancy here; an inactive query has no candidates
+        const int bestIdx = b.dist > TH_LOW ? -1 : b.idx;            // :1493 / :1643
         best_idx[i] = bestIdx;
-        if (best_dist) best_dist[i] = bestIdx >= 0 ? bestDist : -1;
+        if (best_dist) best_dist[i] = bestIdx >= 0 ? b.dist : -1;
     }
     return ORBX_OK;
 }
@@ -1700,17 +1669,13 @@ int orbm_search_by_sim3(orbx_extractor* h, const OrbmFrameView* KF1, const OrbmF
     std::vector<int> vnMatch1(N1 > 0 ? N1 : 1, -1), vnMatch2(N2 > 0 ? N2 : 1, -1);
     for (int dir = 0; dir < 2; dir++) {                              // src/ORBmatcher.cc:1735-1826 and :1829-1915
         const OrbmProjectedPointView* P = dir == 0 ? P1in2 : P2in1;
-        std::vector<AreaQuery> qs; Csr c;
+        std::vector<AreaQuery> qs; Cands c;
         int rc = projected_candidates(h, dir == 0 ? KF2 : KF1, P, th, 0, 0, nullptr, &qs, &c); if (rc) return rc;
         std::vector<int>& out = dir == 0 ? vnMatch1 : vnMatch2;
         for (int i = 0; i < P->M; i++) {
             if (!qs[i].active) continue;
-            int bestDist = 0x7fffffff, bestIdx = -1;
-            for (int k = 0; k < c.count[i]; k++) {
-                const int idx = c.ent[2 * (size_t)(c.start[i] + k)], dist = c.ent[2 * (size_t)(c.start[i] + k) + 1] & 0xFFFF;
-                if (dist < bestDist) { bestDist = dist; bestIdx = idx; }
-            }
-            if (bestDist <= TH_HIGH) out[i] = bestIdx;
+            const Best b = scan_best(c, i, nullptr, 0, 0x7fffffff);
+            if (b.dist <= TH_HIGH) out[i] = b.idx;
         }
     }
     int nfound = 0;
@@ -1746,10 +1711,11 @@ namespace {
 int camera_candidates(orbx_extractor* h, const OrbmFrameView* F, const std::vector<AreaQuery>& qs, const uint8_t* qdesc, Csr* c) {
     DeviceFrame D;
     int rc = upload_frame(h, F, &D); if (rc) return rc;
-    return run_area_search(h, D, qs, qdesc, c);
+    Cands v;
+    rc = run_area_search(h, D, qs, qdesc, &v); if (rc) return rc;
+    c->copy(v, (int)qs.size());
+    return ORBX_OK;
 }
-inline int cand_idx(const Csr& c, int q, int k) { return c.ent[2 * (size_t)(c.start[q] + k)]; }
-inline int cand_dl(const Csr& c, int q, int k) { return c.ent[2 * (size_t)(c.start[q] + k) + 1]; }
 }  // namespace
 
 int orbm_search_by_projection_mappoints_fisheye(orbx_extractor* h, const OrbmFisheyeFrameView* F, const OrbmMapPointView* P,
@@ -1786,9 +1752,10 @@ int orbm_search_by_projection_mappoints_fisheye(orbx_extractor* h, const OrbmFis
             }
         }
     }
-    Csr cl, cr;
-    int rc = camera_candidates(h, &F->left, ql, P->desc, &cl); if (rc) return rc;
-    rc = camera_candidates(h, &F->right, qr, P->desc, &cr); if (rc) return rc;
+    Csr csl, csr;
+    int rc = camera_candidates(h, &F->left, ql, P->desc, &csl); if (rc) return rc;
+    rc = camera_candidates(h, &F->right, qr, P->desc, &csr); if (rc) return rc;
+    const Cands cl(csl), cr(csr);
     std::vector<uint8_t> occ((size_t)NL + NR + 1, 0);
     if (F->left.occupied) memcpy(occ.data(), F->left.occupied, NL);
     if (F->right.occupied) memcpy(occ.data() + NL, F->right.occupied, NR);
@@ -1799,19 +1766,12 @@ int orbm_search_by_projection_mappoints_fisheye(orbx_extractor* h, const OrbmFis
         const uint8_t obs = P->has_obs ? P->has_obs[i] : 1;
         bool skip_right = false;
         if (ql[i].active && cl.count[i] > 0) {                               // :62-166
-            int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
-            for (int k = 0; k < cl.count[i]; k++) {
-                const int idx = cand_idx(cl, i, k), dl = cand_dl(cl, i, k);
-                if (occ[idx]) continue;
-                const int dist = dl & 0xFFFF, level = dl >> 16;
-                if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = level; bestIdx = idx; }
-                else if (dist < bestDist2) { bestLevel2 = level; bestDist2 = dist; }
-            }
-            if (bestDist <= TH_HIGH) {
-                if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) skip_right = true;     // `continue` of the reference: next map point
-                else if (bestLevel != bestLevel2 || bestDist <= nnratio * bestDist2) {
-                    assigned[bestIdx] = i; occ[bestIdx] = obs;
-                    const int ltr = F->left_to_right ? F->left_to_right[bestIdx] : -1;
+            const Best2 b = scan_best2(cl, i, occ.data());
+            if (b.bestDist <= TH_HIGH) {
+                if (b.bestLevel == b.bestLevel2 && b.bestDist > nnratio * b.bestDist2) skip_right = true;     // `continue` of the reference: next map point
+                else if (b.bestLevel != b.bestLevel2 || b.bestDist <= nnratio * b.bestDist2) {
+                    assigned[b.bestIdx] = i; occ[b.bestIdx] = obs;
+                    const int ltr = F->left_to_right ? F->left_to_right[b.bestIdx] : -1;
                     if (ltr != -1) { assigned[ltr + NL] = i; occ[ltr + NL] = obs; nmatches++; }
                     nmatches++;
                 }
@@ -1820,19 +1780,12 @@ int orbm_search_by_projection_mappoints_fisheye(orbx_extractor* h, const OrbmFis
         if (skip_right) continue;
         if (qr[i].active) {                                                  // :170-236
             if (cr.count[i] == 0) continue;
-            int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
-            for (int k = 0; k < cr.count[i]; k++) {
-                const int idx = cand_idx(cr, i, k), dl = cand_dl(cr, i, k);
-                if (occ[idx + NL]) continue;
-                const int dist = dl & 0xFFFF, level = dl >> 16;
-                if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2 = bestLevel; bestLevel = level; bestIdx = idx; }
-                else if (dist < bestDist2) { bestLevel2 = level; bestDist2 = dist; }
-            }
-            if (bestDist <= TH_HIGH) {
-                if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) continue;
-                const int rtl = F->right_to_left ? F->right_to_left[bestIdx] : -1;
+            const Best2 b = scan_best2(cr, i, occ.data(), NL);
+            if (b.bestDist <= TH_HIGH) {
+                if (b.bestLevel == b.bestLevel2 && b.bestDist > nnratio * b.bestDist2) continue;
+                const int rtl = F->right_to_left ? F->right_to_left[b.bestIdx] : -1;
                 if (rtl != -1) { assigned[rtl] = i; occ[rtl] = obs; nmatches++; }
-                assigned[bestIdx + NL] = i; occ[bestIdx + NL] = obs;
+                assigned[b.bestIdx + NL] = i; occ[b.bestIdx + NL] = obs;
                 nmatches++;
             }
         }
@@ -1846,30 +1799,24 @@ int orbm_search_local_points_fisheye(orbx_extractor* h, const OrbmFisheyeFrameVi
     if (!h || !F || !V || !P || !assigned) return fail(ORBX_E_ARG, "null");
     if (P->M < 0 || (P->M > 0 && (!P->pos || !P->normal || !P->min_distance || !P->max_distance || !P->desc))) return fail(ORBX_E_ARG, "bad map point view");
     const size_t M1 = P->M > 0 ? P->M : 1;
-    // the tracking fields of both cameras come back once (they are the reference's MapPoint members; the searches read them as views)
+    // the tracking fields of both cameras come back once (they are the reference's MapPoint members; the searches read them as views): into the
+    // caller's arrays where they are given, into scratch where not
     std::vector<uint8_t> inl(M1), inr(M1), zero(M1, 0), one(M1, 1);
     std::vector<float> f(9 * M1);
     std::vector<int> ll(M1), lr(M1);
-    OrbmTrackOut L = {inl.data(), f.data(), f.data() + M1, f.data() + 2 * M1, f.data() + 3 * M1, f.data() + 4 * M1, ll.data()};
-    OrbmTrackOutRight R = {inr.data(), f.data() + 5 * M1, f.data() + 6 * M1, f.data() + 7 * M1, f.data() + 8 * M1, lr.data()};
+    const OrbmTrackOut l0 = left ? *left : OrbmTrackOut{};
+    const OrbmTrackOutRight r0 = right ? *right : OrbmTrackOutRight{};
+    const auto or_own = [](auto* given, auto* own) { return given ? given : own; };
+    const OrbmTrackOut L = {or_own(l0.in_view, inl.data()), or_own(l0.proj_x, f.data()), or_own(l0.proj_y, f.data() + M1), or_own(l0.proj_xr, f.data() + 2 * M1),
+                            or_own(l0.depth, f.data() + 3 * M1), or_own(l0.view_cos, f.data() + 4 * M1), or_own(l0.scale_level, ll.data())};
+    const OrbmTrackOutRight R = {or_own(r0.in_view_r, inr.data()), or_own(r0.proj_xr, f.data() + 5 * M1), or_own(r0.proj_yr, f.data() + 6 * M1),
+                                 or_own(r0.depth_r, f.data() + 7 * M1), or_own(r0.view_cos_r, f.data() + 8 * M1), or_own(r0.scale_level_r, lr.data())};
     int rc = orbm_is_in_frustum_rig(h, V, P, cos_limit, &L, &R); if (rc) return rc;
     OrbmMapPointView PV; memset(&PV, 0, sizeof PV);
     PV.M = P->M; PV.in_view = L.in_view; PV.proj_x = L.proj_x; PV.proj_y = L.proj_y; PV.proj_xr = L.proj_xr; PV.scale_level = L.scale_level; PV.view_cos = L.view_cos;
     PV.track_depth = L.depth; PV.is_bad = P->is_bad ? P->is_bad : zero.data(); PV.has_obs = P->has_obs ? P->has_obs : one.data(); PV.desc = P->desc;
     OrbmMapPointRightView PR; PR.in_view_r = R.in_view_r; PR.proj_xr = R.proj_xr; PR.proj_yr = R.proj_yr; PR.scale_level_r = R.scale_level_r; PR.view_cos_r = R.view_cos_r;
-    rc = orbm_search_by_projection_mappoints_fisheye(h, F, &PV, &PR, th, far_points, th_far, nnratio, assigned, nmatches_out); if (rc) return rc;
-    const size_t n = (size_t)(P->M > 0 ? P->M : 0);
-    if (left) {
-        if (left->in_view) memcpy(left->in_view, L.in_view, n); if (left->proj_x) memcpy(left->proj_x, L.proj_x, 4 * n); if (left->proj_y) memcpy(left->proj_y, L.proj_y, 4 * n);
-        if (left->depth) memcpy(left->depth, L.depth, 4 * n); if (left->view_cos) memcpy(left->view_cos, L.view_cos, 4 * n); if (left->scale_level) memcpy(left->scale_level, L.scale_level, 4 * n);
-        if (left->proj_xr) memcpy(left->proj_xr, L.proj_xr, 4 * n);
-    }
-    if (right) {
-        if (right->in_view_r) memcpy(right->in_view_r, R.in_view_r, n); if (right->proj_xr) memcpy(right->proj_xr, R.proj_xr, 4 * n); if (right->proj_yr) memcpy(right->proj_yr, R.proj_yr, 4 * n);
-        if (right->depth_r) memcpy(right->depth_r, R.depth_r, 4 * n); if (right->view_cos_r) memcpy(right->view_cos_r, R.view_cos_r, 4 * n);
-        if (right->scale_level_r) memcpy(right->scale_level_r, R.scale_level_r, 4 * n);
-    }
-    return ORBX_OK;
+    return orbm_search_by_projection_mappoints_fisheye(h, F, &PV, &PR, th, far_points, th_far, nnratio, assigned, nmatches_out);
 }
 
 int orbm_search_by_projection_frame_fisheye(orbx_extractor* h, const OrbmFisheyeFrameView* Cur, const OrbmLastFrameView* Last, const float* proj_ur,
@@ -1895,50 +1842,31 @@ int orbm_search_by_projection_frame_fisheye(orbx_extractor* h, const OrbmFisheye
             q.active = 1;
         }
     }
-    Csr cl, cr;
-    int rc = camera_candidates(h, &Cur->left, ql, Last->desc, &cl); if (rc) return rc;
-    rc = camera_candidates(h, &Cur->right, qr, Last->desc, &cr); if (rc) return rc;
+    Csr csl, csr;
+    int rc = camera_candidates(h, &Cur->left, ql, Last->desc, &csl); if (rc) return rc;
+    rc = camera_candidates(h, &Cur->right, qr, Last->desc, &csr); if (rc) return rc;
+    const Cands cl(csl), cr(csr);
     std::vector<uint8_t> occ((size_t)NL + NR + 1, 0);
     if (Cur->left.occupied) memcpy(occ.data(), Cur->left.occupied, NL);
     if (Cur->right.occupied) memcpy(occ.data() + NL, Cur->right.occupied, NR);
     for (int i = 0; i < NL + NR; i++) assigned[i] = -1;
-    std::vector<int> rotHist[HISTO_LENGTH];
+    RotHist hist;
     int nmatches = 0;
     for (int i = 0; i < NLast; i++) {
         if (!ql[i].active || cl.count[i] == 0) continue;                   // an empty left window also skips the right camera (:2025-2026)
         const uint8_t obs = Last->has_obs ? Last->has_obs[i] : 1;
-        {
-            int bestDist = 256, bestIdx2 = -1;
-            for (int k = 0; k < cl.count[i]; k++) {
-                const int i2 = cand_idx(cl, i, k), dist = cand_dl(cl, i, k) & 0xFFFF;
-                if (occ[i2]) continue;
-                if (dist < bestDist) { bestDist = dist; bestIdx2 = i2; }
-            }
-            if (bestDist <= TH_HIGH) {
-                assigned[bestIdx2] = i; occ[bestIdx2] = obs; nmatches++;
-                if (check_ori) rotHist[rot_bin(Last->angle[i], Cur->left.keys_un[bestIdx2].angle)].push_back(bestIdx2);
-            }
+        const Best bl = scan_best(cl, i, occ.data());
+        if (bl.dist <= TH_HIGH) {
+            assigned[bl.idx] = i; occ[bl.idx] = obs; nmatches++;
+            if (check_ori) hist.add(Last->angle[i], Cur->left.keys_un[bl.idx].angle, bl.idx);
         }
-        {
-            int bestDist = 256, bestIdx2 = -1;
-            for (int k = 0; k < cr.count[i]; k++) {
-                const int i2 = cand_idx(cr, i, k), dist = cand_dl(cr, i, k) & 0xFFFF;
-                if (occ[i2 + NL]) continue;
-                if (dist < bestDist) { bestDist = dist; bestIdx2 = i2; }
-            }
-            if (bestDist <= TH_HIGH) {
-                assigned[bestIdx2 + NL] = i; occ[bestIdx2 + NL] = obs; nmatches++;
-                if (check_ori) rotHist[rot_bin(Last->angle[i], Cur->right.keys_un[bestIdx2].angle)].push_back(bestIdx2 + NL);
-            }
+        const Best br = scan_best(cr, i, occ.data(), NL);
+        if (br.dist <= TH_HIGH) {
+            assigned[br.idx + NL] = i; occ[br.idx + NL] = obs; nmatches++;
+            if (check_ori) hist.add(Last->angle[i], Cur->right.keys_un[br.idx].angle, br.idx + NL);
         }
     }
-    if (check_ori) {
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        three_maxima(rotHist, HISTO_LENGTH, ind1, ind2, ind3);
-        for (int i = 0; i < HISTO_LENGTH; i++)
-            if (i != ind1 && i != ind2 && i != ind3)
-                for (int idx : rotHist[i]) { assigned[idx] = -2; nmatches--; }
-    }
+    if (check_ori) hist.prune([&](int idx) { assigned[idx] = -2; nmatches--; });
     if (nmatches_out) *nmatches_out = nmatches;
     return ORBX_OK;
 }
@@ -1964,27 +1892,13 @@ int rig_pair_check(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B) 
     if (L->fe_gen_L != L->extract_gen || L->fe_gen_R != R->extract_gen) return fail(ORBX_E_ARG, "a handle has extracted since the last orbm_stereo_fisheye: run it again");
     return ORBX_OK;
 }
-int rig_frames_check(const OrbmFrustumRigView* f, int B) {
-    for (int b = 0; b < B; b++) {
-        const OrbmFrustumView& v = f[b].left;
-        if (v.nlevels < 1 || v.nlevels > kMaxLevels || !v.scale_factors) return fail(ORBX_E_ARG, "bad scale levels (frame %d)", b);
-        if (v.min_x != f[0].left.min_x || v.max_x != f[0].left.max_x || v.min_y != f[0].left.min_y || v.max_y != f[0].left.max_y)
-            return fail(ORBX_E_ARG, "frame %d has other image bounds than frame 0", b);
-    }
-    if (!(f[0].left.max_x > f[0].left.min_x) || !(f[0].left.max_y > f[0].left.min_y)) return fail(ORBX_E_ARG, "empty image bounds");
-    return ORBX_OK;
-}
-// the device block of a rig batch behind the upload: two grids, two query sets and CSRs, the result, the entry pool
+// the device block of a rig batch behind the upload: two grids, two query sets and CSRs, `extra` bytes of the caller's, the result, the entry pool
 struct RigBlock {
-    size_t cof1, cst1, cit1, cof2, cst2, cit2, q1, q2, qs1, qc1, qs2, qc2, res, res_bytes, pool;
-    RigBlock(size_t o, size_t B1, size_t M1, size_t C1, size_t extra, size_t* o_extra) {
-        cof1 = o; o += al16(4 * B1 * C1); cst1 = o; o += al16(4 * B1 * kGridCellStride); cit1 = o; o += al16(4 * B1 * C1);
-        cof2 = o; o += al16(4 * B1 * C1); cst2 = o; o += al16(4 * B1 * kGridCellStride); cit2 = o; o += al16(4 * B1 * C1);
-        q1 = o; o += al16(sizeof(AreaQuery) * B1 * M1); q2 = o; o += al16(sizeof(AreaQuery) * B1 * M1);
-        qs1 = o; o += al16(4 * B1 * M1); qc1 = o; o += al16(4 * B1 * M1); qs2 = o; o += al16(4 * B1 * M1); qc2 = o; o += al16(4 * B1 * M1);
-        *o_extra = o; o += al16(extra);
-        res = o; res_bytes = 16 + al16(4 * B1) + 4 * B1 * 2 * C1; o += al16(res_bytes);
-        pool = o;
+    Bump d; GridBlock g1, g2; size_t q1, q2, qs1, qc1, qs2, qc2, extra; ResultBlock r; size_t res, pool;
+    RigBlock(size_t o, size_t B1, size_t M1, size_t C1, size_t extra_bytes) : d(o), g1(d, B1, C1), g2(d, B1, C1), r(B1, 2 * C1) {
+        q1 = d.take(sizeof(AreaQuery) * B1 * M1); q2 = d.take(sizeof(AreaQuery) * B1 * M1);
+        qs1 = d.take(4 * B1 * M1); qc1 = d.take(4 * B1 * M1); qs2 = d.take(4 * B1 * M1); qc2 = d.take(4 * B1 * M1);
+        extra = d.take(extra_bytes); res = d.take(r.bytes); pool = d.o;
     }
 };
 // grids of both cameras, then the window searches of both query sets into one entry pool (the right-coordinate gate off: a rig frame has no mvuRight)
@@ -1997,23 +1911,17 @@ void rig_searches(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, i
     int* d_counter = (int*)(dp + K.res);
     {
         dim3 grid(B, 1, 1), blkg(kGridThreads, 1, 1);
-        ORBX_LAUNCH(k_grid_build, grid, blkg, 0, L->s0, kps1, 0, g, (int*)(dp + K.cof1), (int*)(dp + K.cst1), (int*)(dp + K.cit1), (const int*)(L->d_nm.p + lf), cap);
-        ORBX_LAUNCH(k_grid_build, grid, blkg, 0, L->s0, kps2, 0, g, (int*)(dp + K.cof2), (int*)(dp + K.cst2), (int*)(dp + K.cit2), (const int*)(R->d_nm.p + rf), cap);
+        ORBX_LAUNCH(k_grid_build, grid, blkg, 0, L->s0, kps1, 0, g, (int*)(dp + K.g1.cof), (int*)(dp + K.g1.cst), (int*)(dp + K.g1.cit), (const int*)(L->d_nm.p + lf), cap);
+        ORBX_LAUNCH(k_grid_build, grid, blkg, 0, L->s0, kps2, 0, g, (int*)(dp + K.g2.cof), (int*)(dp + K.g2.cst), (int*)(dp + K.g2.cit), (const int*)(R->d_nm.p + rf), cap);
     }
     if (M <= 0) { rt::memset_async(d_counter, 0, 16, L->s0); return; }
     queries();
     const float* no_ur = (const float*)dp;                       // never read: gate_right = 0
     dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
     ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, L->s0, (const AreaQuery*)(dp + K.q1), qdesc, M, kps1, no_ur, L->d_desc.p + (size_t)lf * cap * 4, g,
-                (const int*)(dp + K.cst1), (const int*)(dp + K.cit1), 0, d_counter, (int)pool, (int*)(dp + K.qs1), (int*)(dp + K.qc1), (int2*)(dp + K.pool), cap, qdesc_per_frame);
+                (const int*)(dp + K.g1.cst), (const int*)(dp + K.g1.cit), 0, d_counter, (int)pool, (int*)(dp + K.qs1), (int*)(dp + K.qc1), (int2*)(dp + K.pool), cap, qdesc_per_frame);
     ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, L->s0, (const AreaQuery*)(dp + K.q2), qdesc, M, kps2, no_ur, R->d_desc.p + (size_t)rf * cap * 4, g,
-                (const int*)(dp + K.cst2), (const int*)(dp + K.cit2), 0, d_counter, (int)pool, (int*)(dp + K.qs2), (int*)(dp + K.qc2), (int2*)(dp + K.pool), cap, qdesc_per_frame);
-}
-GridParams rig_grid(const OrbmFrustumView& v) {
-    GridParams g; memset(&g, 0, sizeof g);
-    g.min_x = v.min_x; g.min_y = v.min_y;
-    g.gw_inv = (float)kGridColsHost / (v.max_x - v.min_x); g.gh_inv = (float)kGridRowsHost / (v.max_y - v.min_y);   // src/Frame.cc:190-191
-    return g;
+                (const int*)(dp + K.g2.cst), (const int*)(dp + K.g2.cit), 0, d_counter, (int)pool, (int*)(dp + K.qs2), (int*)(dp + K.qc2), (int2*)(dp + K.pool), cap, qdesc_per_frame);
 }
 size_t rig_accept_lds(int cap, int events) { const size_t S = 2 * (size_t)cap; return 4 * S + al16(S) + 4 * (size_t)events + 64; }
 }  // namespace
@@ -2025,7 +1933,7 @@ int orbm_search_local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor
     if (L) { L->lp_B = 0; L->lp_rig = false; }                     // a new enqueue ends the previous batch; a refused one leaves nothing to fetch
     if (!L || !frames || !points) return fail(ORBX_E_ARG, "null");
     int rc = rig_pair_check(L, lf, R, rf, B); if (rc) return rc;
-    if ((rc = rig_frames_check(frames, B))) return rc;
+    if ((rc = frames_check(&frames[0].left, sizeof *frames, B))) return rc;
     if (points->device != L->device) return fail(ORBX_E_ARG, "map points live on another device");
     rt::set_device(L->device);
     const int M = points->M, cap = L->kp_total_cap;
@@ -2034,15 +1942,15 @@ int orbm_search_local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor
     if (smem_accept + 1024 > rt::lds_limit(L->device)) return fail(ORBX_E_CAPACITY, "%d keypoints per camera need %zu bytes of LDS in the rig accept kernel", cap, smem_accept);
     if (L->lp_pending) rt::event_sync(L->ev_lp);               // the staging block of the previous enqueue has been consumed
     // upload: [camera 1, camera 2] parameters per frame | bad flags | has-observation flags | occupancy [B][2 cap]
-    const size_t u_f = 0, u_bad = u_f + al16(sizeof(FrustumParams) * 2 * B1), u_obs = u_bad + al16(M1), u_occ = u_obs + al16(M1), u_total = u_occ + (occupied ? al16(B1 * S1) : 0);
+    Bump u;
+    const size_t u_f = u.take(sizeof(FrustumParams) * 2 * B1), u_bad = u.take(M1), u_obs = u.take(M1), u_occ = u.take(occupied ? B1 * S1 : 0), u_total = u.o;
     // behind the common block: per camera track [B][5 M] | level [B][M] | in_view [B][M]
-    const size_t o_trk1 = 0, o_trk2 = al16(20 * B1 * M1), o_lvl1 = 2 * o_trk2, o_lvl2 = o_lvl1 + al16(4 * B1 * M1), o_view1 = o_lvl2 + al16(4 * B1 * M1),
-                 o_view2 = o_view1 + al16(B1 * M1), track_total = o_view2 + al16(B1 * M1);
-    size_t ox = 0;
-    const RigBlock K(al16(u_total), B1, M1, C1, track_total, &ox);
-    size_t pool = std::max<size_t>(L->lp_pool, B1 * M1 * 12 + 4096);
-    if (pool > 0x7fffffff / 2) pool = 0x7fffffff / 2;
-    if (L->d_lp.ensure(K.pool + pool * 8 + 64) || L->h_lp_in.ensure(u_total + 16) || L->h_lp_out.ensure(al16(K.res_bytes) + (want_in_view ? 2 * B1 * M1 : 0) + 64))
+    Bump t;
+    const size_t o_trk1 = t.take(20 * B1 * M1), o_trk2 = t.take(20 * B1 * M1), o_lvl1 = t.take(4 * B1 * M1), o_lvl2 = t.take(4 * B1 * M1), o_view1 = t.take(B1 * M1),
+                 o_view2 = t.take(B1 * M1);
+    const RigBlock K(u_total, B1, M1, C1, t.o);
+    const size_t ox = K.extra, pool = batch_pool(L, B1 * M1 * 12 + 4096);
+    if (L->d_lp.ensure(K.pool + pool * 8 + 64) || L->h_lp_in.ensure(u_total + 16) || L->h_lp_out.ensure(al16(K.r.bytes) + (want_in_view ? 2 * B1 * M1 : 0) + 64))
         return fail(ORBX_E_DEVICE, "allocation failed (batched rig local point search, %d frames x %d points)", B, M);
     L->lp_pool = pool;
     uint8_t* hp = L->h_lp_in.p; uint8_t* dp = L->d_lp.p;
@@ -2059,7 +1967,7 @@ int orbm_search_local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor
     if (L != R) { record_done_if_pending(R); rt::stream_wait_event(L->s0, R->ev_done); }
     uint8_t* dx = dp + ox;
     if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][0], L->s0);
-    rig_searches(L, lf, R, rf, B, M, K, dp, rig_grid(frames[0].left), points->desc, 0, pool, [&]() {
+    rig_searches(L, lf, R, rf, B, M, K, dp, grid_from_view(frames[0].left), points->desc, 0, pool, [&]() {
         dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
         ORBX_LAUNCH(k_frustum_rig, grid, blk, 0, L->s0, (const FrustumParams*)(dp + u_f), M, points->pos, points->normal, points->min_d, points->max_d,
                     (const uint8_t*)(dp + u_bad), dx + o_view1, dx + o_view2, (float*)(dx + o_trk1), (float*)(dx + o_trk2), (int*)(dx + o_lvl1), (int*)(dx + o_lvl2),
@@ -2070,7 +1978,7 @@ int orbm_search_local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor
         ORBX_LAUNCH(k_rig_local_accept, grid, blk, smem_accept, L->s0, M, cap, (const int*)(L->d_nm.p + lf), (const int*)(R->d_nm.p + rf), (const int*)(dp + K.qs1),
                     (const int*)(dp + K.qc1), (const int*)(dp + K.qs2), (const int*)(dp + K.qc2), (const int2*)(dp + K.pool),
                     occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr, (const uint8_t*)(dp + u_obs), (const int*)L->d_l2r.p, (const int*)L->d_r2l.p,
-                    nnratio, TH_HIGH, (int*)(dp + K.res + 16 + al16(4 * B1)), (int*)(dp + K.res + 16));
+                    nnratio, TH_HIGH, (int*)(dp + K.res + K.r.assigned), (int*)(dp + K.res + K.r.nmatches));
     }
     if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][1], L->s0);
     if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
@@ -2086,7 +1994,7 @@ int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orb
     if (!L || !cur || !trl || !last) return fail(ORBX_E_ARG, "null");
     if (last->cap_last <= 0 || !last->n || !last->pos || !last->valid || !last->octave || !last->angle || !last->desc) return fail(ORBX_E_ARG, "bad last-frame batch");
     int rc = rig_pair_check(L, lf, R, rf, B); if (rc) return rc;
-    if ((rc = rig_frames_check(cur, B))) return rc;
+    if ((rc = frames_check(&cur[0].left, sizeof *cur, B))) return rc;
     const int M = last->cap_last, cap = L->kp_total_cap;
     for (int b = 0; b < B; b++) if (last->n[b] < 0 || last->n[b] > M) return fail(ORBX_E_ARG, "frame %d: %d points in %d rows", b, last->n[b], M);
     rt::set_device(L->device);
@@ -2096,14 +2004,13 @@ int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orb
         return fail(ORBX_E_CAPACITY, "%d keypoints per camera and %d last-frame points per frame need %zu bytes of LDS in the rig accept kernel", cap, M, smem_accept);
     if (L->lp_pending) rt::event_sync(L->ev_lp);
     // upload: camera-1 parameters per frame | n_last | pos | valid | octave | angle | has_obs | descriptors | occupancy [B][2 cap]
-    const size_t u_f = 0, u_n = u_f + al16(sizeof(FrustumParams) * B1), u_pos = u_n + al16(4 * B1), u_val = u_pos + al16(12 * B1 * M1), u_oct = u_val + al16(B1 * M1),
-                 u_ang = u_oct + al16(4 * B1 * M1), u_obs = u_ang + al16(4 * B1 * M1), u_desc = u_obs + al16(B1 * M1), u_occ = u_desc + al16(32 * B1 * M1),
-                 u_total = u_occ + (occupied ? al16(B1 * S1) : 0);
-    size_t ox = 0;
-    const RigBlock K(al16(u_total), B1, M1, C1, 0, &ox);
-    size_t pool = std::max<size_t>(L->lp_pool, B1 * M1 * 32 + 4096);          // th = 7 .. 15 px windows, two cameras
-    if (pool > 0x7fffffff / 2) pool = 0x7fffffff / 2;
-    if (L->d_lp.ensure(K.pool + pool * 8 + 64) || L->h_lp_in.ensure(u_total + 16) || L->h_lp_out.ensure(al16(K.res_bytes) + 64))
+    Bump u;
+    const size_t u_f = u.take(sizeof(FrustumParams) * B1);
+    const PointRowsUpload U(u, B1, M1);
+    const size_t u_occ = u.take(occupied ? B1 * S1 : 0), u_total = u.o;
+    const RigBlock K(u_total, B1, M1, C1, 0);
+    const size_t pool = batch_pool(L, B1 * M1 * 32 + 4096);                    // th = 7 .. 15 px windows, two cameras
+    if (L->d_lp.ensure(K.pool + pool * 8 + 64) || L->h_lp_in.ensure(u_total + 16) || L->h_lp_out.ensure(al16(K.r.bytes) + 64))
         return fail(ORBX_E_DEVICE, "allocation failed (batched rig last-frame search, %d frames x %d points)", B, M);
     L->lp_pool = pool;
     uint8_t* hp = L->h_lp_in.p; uint8_t* dp = L->d_lp.p;
@@ -2112,27 +2019,24 @@ int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orb
         fill_frustum_params(&cur[b].left, 0.0f, th, 0, 0.0f, &Fp[b]);
         Fp[b].forward = forward ? forward[b] != 0 : 0; Fp[b].backward = backward ? backward[b] != 0 : 0; Fp[b].debug_flags = L->debug_stereo_flags;
     }
-    memcpy(hp + u_n, last->n, 4 * B1); memcpy(hp + u_pos, last->pos, 12 * B1 * M1); memcpy(hp + u_val, last->valid, B1 * M1);
-    memcpy(hp + u_oct, last->octave, 4 * B1 * M1); memcpy(hp + u_ang, last->angle, 4 * B1 * M1);
-    if (last->has_obs) memcpy(hp + u_obs, last->has_obs, B1 * M1); else memset(hp + u_obs, 1, B1 * M1);
-    memcpy(hp + u_desc, last->desc, 32 * B1 * M1);
+    U.stage(hp, last_frame_rows(last), B1, M1);
     if (occupied) memcpy(hp + u_occ, occupied, B1 * S1);
     if (rt::copy_h2d(dp, hp, u_total, L->s0) || rt::event_record(L->ev_lp, L->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
     L->lp_pending = true;
     if (L != R) { record_done_if_pending(R); rt::stream_wait_event(L->s0, R->ev_done); }
     RigRelPose T; memcpy(T.q, trl, sizeof T.q); memcpy(T.t, trl + 4, sizeof T.t);
     if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][0], L->s0);
-    rig_searches(L, lf, R, rf, B, M, K, dp, rig_grid(cur[0].left), (const unsigned long long*)(dp + u_desc), 1, pool, [&]() {
+    rig_searches(L, lf, R, rf, B, M, K, dp, grid_from_view(cur[0].left), (const unsigned long long*)(dp + U.u_desc), 1, pool, [&]() {
         dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
-        ORBX_LAUNCH(k_lastframe_queries_rig, grid, blk, 0, L->s0, (const FrustumParams*)(dp + u_f), M, (const int*)(dp + u_n), (const float*)(dp + u_pos),
-                    (const uint8_t*)(dp + u_val), (const int*)(dp + u_oct), T, (AreaQuery*)(dp + K.q1), (AreaQuery*)(dp + K.q2), (int*)(dp + K.res));
+        ORBX_LAUNCH(k_lastframe_queries_rig, grid, blk, 0, L->s0, (const FrustumParams*)(dp + u_f), M, (const int*)(dp + U.u_n), (const float*)(dp + U.u_pos),
+                    (const uint8_t*)(dp + U.u_val), (const int*)(dp + U.u_oct), T, (AreaQuery*)(dp + K.q1), (AreaQuery*)(dp + K.q2), (int*)(dp + K.res));
     });
     {
         dim3 grid(B, 1, 1), blk(64, 1, 1);
         ORBX_LAUNCH(k_rig_lastframe_accept, grid, blk, smem_accept, L->s0, M, cap, (const int*)(L->d_nm.p + lf), (const int*)(R->d_nm.p + rf), (const int*)(dp + K.qs1),
                     (const int*)(dp + K.qc1), (const int*)(dp + K.qs2), (const int*)(dp + K.qc2), (const int2*)(dp + K.pool),
-                    occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr, (const uint8_t*)(dp + u_obs), TH_HIGH, (int*)(dp + K.res + 16 + al16(4 * B1)),
-                    (int*)(dp + K.res + 16), (const float*)(dp + u_ang), (const KeyPointRec*)(L->d_kps.p + (size_t)lf * cap), (const KeyPointRec*)(R->d_kps.p + (size_t)rf * cap),
+                    occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr, (const uint8_t*)(dp + U.u_obs), TH_HIGH, (int*)(dp + K.res + K.r.assigned),
+                    (int*)(dp + K.res + K.r.nmatches), (const float*)(dp + U.u_ang), (const KeyPointRec*)(L->d_kps.p + (size_t)lf * cap), (const KeyPointRec*)(R->d_kps.p + (size_t)rf * cap),
                     check_ori);
     }
     if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][1], L->s0);
@@ -2145,33 +2049,8 @@ int orbm_search_rig_batch_fetch(orbx_extractor* L, int* assigned, int cap, int* 
     if (!L || L->lp_B <= 0 || !L->lp_rig) return fail(ORBX_E_ARG, "no batched rig search is pending");
     if (assigned && cap < 2 * L->kp_total_cap) return fail(ORBX_E_ARG, "assigned rows need %d entries (2 x orbx_max_keypoints)", 2 * L->kp_total_cap);
     if ((in_view || in_view_r) && !L->lp_want_view) return fail(ORBX_E_ARG, "in_view was not requested at enqueue time");
-    rt::set_device(L->device);
-    const size_t B1 = L->lp_B, M1 = L->lp_M > 0 ? L->lp_M : 0, S1 = 2 * (size_t)L->kp_total_cap;
-    const size_t res_bytes = 16 + al16(4 * B1) + 4 * B1 * S1;
-    uint8_t* hp = L->h_lp_out.p;
-    int e = rt::copy_d2h(hp, L->d_lp.p + L->lp_o_counter, res_bytes, L->s0);
-    if (L->lp_want_view && M1 > 0) {
-        e |= rt::copy_d2h(hp + al16(res_bytes), L->d_lp.p + L->lp_o_view, B1 * M1, L->s0);
-        e |= rt::copy_d2h(hp + al16(res_bytes) + B1 * M1, L->d_lp.p + L->lp_o_view_r, B1 * M1, L->s0);
-    }
-    if (e || rt::stream_sync(L->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "batched rig search failed: %s", rt::last_error());
-    L->lp_pending = false;
-    if (L->profile) L->stage_ms[ST_MATCH] = rt::event_elapsed_ms(L->ev_stage[ST_MATCH][0], L->ev_stage[ST_MATCH][1]);
-    const int total = *(const int*)hp;
-    if (L->lp_M > 0 && (size_t)total > L->lp_pool) {               // the candidate pool was too small: the caller enqueues again (the pool has grown)
-        L->lp_pool = (size_t)total + (size_t)total / 8 + 4096;
-        return fail(ORBX_E_CAPACITY, "candidate pool overflow (%d entries): enqueue the search again, the pool has been enlarged", total);
-    }
-    if (nmatches) memcpy(nmatches, hp + 16, 4 * B1);
-    if (assigned) {
-        const int* src = (const int*)(hp + 16 + al16(4 * B1));
-        for (size_t b = 0; b < B1; b++) memcpy(assigned + b * (size_t)cap, src + b * S1, 4 * S1);
-    }
-    if (M1 > 0) {
-        if (in_view) memcpy(in_view, hp + al16(res_bytes), B1 * M1);
-        if (in_view_r) memcpy(in_view_r, hp + al16(res_bytes) + B1 * M1, B1 * M1);
-    }
-    return ORBX_OK;
+    uint8_t* const views[2] = {in_view, in_view_r};
+    return batch_fetch(L, 2 * (size_t)L->kp_total_cap, "batched rig search", assigned, cap, nmatches, 2, L->lp_want_view && L->lp_M > 0, views);
 }
 
 }  // extern "C"

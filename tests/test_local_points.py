@@ -89,6 +89,60 @@ def test_local_points_emulated(emu_lib):
     _check(emu_lib, (3,), npts=1500)
 
 
+def test_single_frame_candidate_pool_overflow_is_retried(emu_lib):
+    """The first window search of a handle gets a candidate pool of Q * 48 + 1024 entries; a search that finds more has to enlarge the pool and run
+    again (the batched routes: test_local_points_batch.py::test_candidate_pool_overflow_is_retried).  Whole-image windows on fresh handles: once through
+    orbm_area_search_batch, once through orbm_search_local_points (host points and resident points), results against the oracles as above."""
+    rng = np.random.default_rng(11)
+    w, h, nf, Q = 752, 480, 1200, 32
+    L, R = synth.stereo_pair(w, h, seed=11)
+    F = ol.ReferenceFrame(L, R, nf, fx=FX, fy=FY, cx=CX, cy=CY, bf=BF)
+    ex = ORBextractor(nf, 1.2, 8, 20, 7, lib=emu_lib)
+    (_, kL, dL), _ = ex.extract_batch(np.stack([L, R]))
+    u, _, _ = ComputeStereoMatches(ex, ex, BF, F.mb, 0, 1, 1)
+    assert kL.tobytes() == F.keys.tobytes() and F.N >= 200
+    sfs = ex.GetScaleFactors()
+    fv = views.frame_view(kL, dL, sfs, w, h, u_right=u[0, :F.N], mbf=BF)
+    # the window search alone: Q windows that hold every keypoint
+    qs = [(float(rng.uniform(0, w)), float(rng.uniform(0, h)), 2000.0, -1, -1) for _ in range(Q)]
+    qd = rng.integers(0, 256, (Q, 32), dtype=np.uint8)
+    res = M.AreaSearchBatch(ex, fv, qs, qd)
+    assert sum(len(lst) for lst in res) == Q * F.N > Q * 48 + 1024
+    for (x, y, r, mn, mx), dq, lst in zip(qs, qd, res):
+        exp_idx = ol.oracle_features_in_area(fv, x, y, r, mn, mx)
+        assert len(exp_idx) == F.N and [e[0] for e in lst] == exp_idx.tolist()
+        assert [e[1] for e in lst] == [int(np.unpackbits(dq ^ dL[i]).sum()) for i in exp_idx]
+        assert [e[2] for e in lst] == kL["octave"][exp_idx].tolist()
+    # SearchLocalPoints: th so large that the window of every point in view covers the image (r = 2.5 th or 4 th, times the level's scale)
+    npts, th = 64, 400.0
+    Rcw = _rot(0.02, -0.03, 0.01); tcw = np.array([0.3, -0.1, 0.25], np.float32)
+    pos, normal, mind, maxd, bad, obs, desc = _scene(F, rng, Rcw, tcw, npts)
+    ref_tr, ref_as, ref_n = F.search_local_points(Rcw, tcw, pos, normal, mind, maxd, bad, obs, desc, 0.5, True, th, False, 9.0, 0.8)
+    searched = ref_tr["in_view"] & ~bad
+    lvl = ref_tr["scale_level"][searched]
+    assert np.all((lvl >= 0) & (lvl < 8))
+    octave = kL["octave"].astype(np.int64)
+    total = sum(int(((octave >= l - 1) & (octave <= l)).sum()) for l in lvl)          # candidates: the keypoints of levels [l - 1, l]
+    assert total > npts * 48 + 1024, "the scene does not overflow the initial pool (%d candidates)" % total
+    for resident in (False, True):
+        ex2 = ORBextractor(nf, 1.2, 8, 20, 7, lib=emu_lib)                            # a handle that has not searched yet
+        rp = M.ResidentPoints(ex2, pos, normal, mind, maxd, desc) if resident else None
+        tr, asg, n = M.SearchLocalPoints(ex2, fv, Rcw, tcw, (FX, FY, CX, CY), (0.0, float(w), 0.0, float(h)), BF, sfs, pos, normal, mind, maxd, bad, obs, desc,
+                                         0.5, th, False, 9.0, 0.8, resident=rp)
+        inv = ref_tr["in_view"]
+        assert np.array_equal(tr["in_view"].astype(bool), inv), "mbTrackInView"
+        for k in ("proj_x", "proj_y"):
+            assert tr[k].tobytes() == ref_tr[k].tobytes(), k
+        for k in ("proj_xr", "depth", "view_cos"):
+            assert tr[k][inv].tobytes() == ref_tr[k][inv].tobytes(), k
+        assert np.array_equal(tr["scale_level"][inv], ref_tr["scale_level"][inv]), "mnTrackScaleLevel"
+        assert n == ref_n and ref_n > 0 and np.array_equal(asg, ref_as), "SearchByProjection assignment differs (%d vs %d matches)" % (n, ref_n)
+        if rp is not None:
+            rp.close()
+        ex2.close()
+    ex.close()
+
+
 @pytest.mark.gpu
 def test_local_points_gpu(hip_lib):
     _check(hip_lib, (3, 4, 5, 6))
