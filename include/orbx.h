@@ -397,6 +397,26 @@ int orbm_search_local_points_batch(orbx_extractor* h, int first, int B, const Or
                                    float viewing_cos_limit, float th, int far_points, float th_far, float nnratio, int want_in_view);
 int orbm_search_local_points_fetch(orbx_extractor* h, int* assigned, int cap, int* nmatches, uint8_t* in_view);
 
+/* The same for frames that each bring their OWN local map - independent streams tracked side by side, one frame of every stream per batch.
+ * maps[b] is the local map of frame b: a resident set (one set may serve several frames; NULL or an empty set = empty map: the frame gets
+ * nmatches = 0 and every assigned entry -1) and that frame's call-time flags over the points of ITS set.  Frame b's results are those of
+ * orbm_search_local_points_resident with maps[b]: assigned[b][i] indexes frame b's own set.  Everything else - frames, occupied, the parameters,
+ * the one pending batch per handle, the candidate pool (ORBX_E_CAPACITY from the fetch, then enqueue again) - as orbm_search_local_points_batch;
+ * also refused (ORBX_E_ARG, nothing enqueued, nothing to fetch): maps == NULL, a set that lives on another device than the handle.
+ * orbm_search_local_points_fetch returns mbTrackInView as [B][M_max], M_max = the largest orbm_points_count of the batch: row b holds frame
+ * b's M_b flags, then zeros.  (The struct is declared apart from its typedef - the same C type - because tests/test_struct_layout.py keeps a fixed
+ * list of the header's `typedef struct X { .. } X;` records; this one's Python mirror is checked by tests/test_local_points_maps.py.) */
+struct OrbmFrameMap {
+    const orbm_points* points;             /* resident set; one set may serve many frames; NULL or M == 0 = empty map */
+    const uint8_t* is_bad;                 /* [M of that set] call-time flags, NULL = none bad */
+    const uint8_t* has_obs;                /* [M of that set], NULL = all observed */
+};
+typedef struct OrbmFrameMap OrbmFrameMap;  /* the local map of ONE frame of a batch */
+int orbm_search_local_points_batch_maps(orbx_extractor* h, int first, int B, const OrbmFrustumView* frames, const OrbmFrameMap* maps /*[B]*/,
+                                        const uint8_t* occupied, int use_u_right, float viewing_cos_limit, float th, int far_points, float th_far,
+                                        float nnratio, int want_in_view);
+int orbm_points_count(const orbm_points* p);     /* M of a resident set (0 for NULL) */
+
 /* ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (src/ORBmatcher.cc:1950-2184, one camera) - the search of
  * Tracking::TrackWithMotionModel - for a BATCH of frames on the device: current frames = images [first, first + B) of the handle's last
  * extraction (mvKeysUn, mDescriptors, mvuRight as in orbm_search_local_points_batch); cur[b] = pose, camera, bounds, mbf and scale factors of
@@ -583,6 +603,12 @@ int orbm_search_by_projection_frame_fisheye(orbx_extractor* h, const OrbmFisheye
 int orbm_search_local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* frames,
                                        const orbm_points* points, const uint8_t* is_bad, const uint8_t* has_obs, const uint8_t* occupied,
                                        float viewing_cos_limit, float th, int far_points, float th_far, float nnratio, int want_in_view);
+/* The same for rig frames that each bring their own local map (OrbmFrameMap, as orbm_search_local_points_batch_maps): per frame the result of
+ * orbm_search_local_points_fisheye with maps[b].  Refused like the call above (no / other / outdated orbm_stereo_fisheye links, differing handles),
+ * and for maps == NULL or a set on another device.  orbm_search_rig_batch_fetch returns in_view / in_view_r as [B][M_max], zeros beyond M_b. */
+int orbm_search_local_points_rig_batch_maps(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* frames,
+                                            const OrbmFrameMap* maps /*[B]*/, const uint8_t* occupied, float viewing_cos_limit, float th, int far_points,
+                                            float th_far, float nnratio, int want_in_view);
 /* SearchByProjection(CurrentFrame, LastFrame, th, bMono) for B rig frames (src/ORBmatcher.cc:1950-2184 incl. :2089-2152): per frame the result of
  * orbm_search_by_projection_frame_fisheye.  cur[b].left: pose (the quaternion qcw), camera 1 and bounds as in orbm_search_by_projection_lastframe_batch;
  * `last` as there.  Camera 2's projections are made on the device as the reference makes them: x3Dr = CurrentFrame.GetRelativePoseTrl() * x3Dc
@@ -593,7 +619,7 @@ int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orb
                                                   const uint8_t* backward, int check_orientation, const uint8_t* occupied);
 /* Results of the last rig batch of L: assigned [B][cap] indexed like F.mvpMapPoints (camera 1 at [0, Nleft), camera 2 at [Nleft, Nleft + Nright);
  * -1 untouched, -2 reset by the rotation check), cap >= 2 * orbx_max_keypoints(); nmatches [B]; in_view / in_view_r [B][M] (mbTrackInView /
- * mbTrackInViewR: local-map form with want_in_view only).  Every output may be NULL.  ORBX_E_CAPACITY = the candidate pool was too small for
+ * mbTrackInViewR: local-map form with want_in_view only; after orbm_search_local_points_rig_batch_maps M = M_max, rows padded with zeros).  Every output may be NULL.  ORBX_E_CAPACITY = the candidate pool was too small for
  * this scene: it has been enlarged, enqueue the same call again.  orbm_search_local_points_fetch refuses a rig batch, this call a single-camera one. */
 int orbm_search_rig_batch_fetch(orbx_extractor* L, int* assigned, int cap, int* nmatches, uint8_t* in_view, uint8_t* in_view_r);
 

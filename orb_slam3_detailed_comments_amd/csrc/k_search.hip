@@ -329,6 +329,22 @@ __global__ void __launch_bounds__(256) k_frustum(FrustumParams F, int M, const f
     } else frustum_body(F, i, M, pos, normal, min_dist, max_dist, is_bad, in_view, track, scale_level, queries);
 }
 
+// The batched form for frames that bring their OWN local maps (orbm_search_local_points_batch_maps): blockIdx.y = frame, frame b reads the set
+// maps[b] names and writes at maps[b].offset - its place in everything laid out by the prefix sums of M_b (is_bad, in_view, level, queries;
+// track at 5 x offset).  grid ((max M_b + 255) / 256, B): the blocks beyond a frame's M_b leave at once.  The table entry is the same for the
+// whole block (an address made of blockIdx.y alone): one scalar load, not one per lane.
+__global__ void __launch_bounds__(256) k_frustum_maps(const FrustumParams* __restrict__ Fb, const FrameMapRec* __restrict__ maps, const uint8_t* __restrict__ is_bad,
+                                                      uint8_t* __restrict__ in_view, float* __restrict__ track, int* __restrict__ scale_level,
+                                                      AreaQuery* __restrict__ queries, int* __restrict__ zero4) {
+    const size_t b = blockIdx.y;
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (zero4 && i < 4 && b == 0) zero4[i] = 0;
+    const FrameMapRec T = maps[b];
+    if (i >= T.M) return;
+    const size_t o = (size_t)T.offset;
+    frustum_body(Fb[b], i, T.M, T.pos, T.normal, T.min_d, T.max_d, is_bad + o, in_view + o, track + 5 * o, scale_level + o, queries + o);
+}
+
 // The head of the projection-type searches of ORBmatcher (SearchByProjection(Frame, LastFrame) src/ORBmatcher.cc:1993-2010, (Frame, KeyFrame)
 // :2228-2256, (KeyFrame, Sim3, ...) :525-560 / :640-690, Fuse :1388-1430 / :1590-1625, SearchBySim3 :1745-1790 / :1830-1875): transform the map
 // point, depth test, projection, image test, distance range, viewing angle - one thread per point, the reference's fp32 operation order
@@ -451,24 +467,19 @@ __global__ void __launch_bounds__(256) k_keyframe_queries(const FrustumParams* _
 // reference's order (ix-major, iy-minor, items in insertion order), counts, the workgroup reserves its span of the entry pool with one
 // atomicAdd, and a second walk writes {idx, dist | octave << 16} at the thread's offset.  Same gates as k_area_search.  blockIdx.y = frame.
 // On pool overflow nothing is written and the counts are 0 (the host sees the counter, enlarges the pool and repeats).
-__global__ void __launch_bounds__(256) k_area_search_threads(const AreaQuery* __restrict__ queries, const unsigned long long* __restrict__ qdesc, int Q,
-                                                             const KeyPointRec* __restrict__ kps, const float* __restrict__ u_right,
-                                                             const unsigned long long* __restrict__ fdesc, GridParams g, const int* __restrict__ cell_start,
-                                                             const int* __restrict__ cell_items, int gate_right, int* __restrict__ pool_counter, int pool_cap,
-                                                             int* __restrict__ q_start, int* __restrict__ q_count, int2* __restrict__ entries, int frame_stride,
-                                                             int qdesc_per_frame) {
+// (the body: queries / q_start / q_count / qdesc / the frame's keypoints and grid are THIS frame's, Q its number of queries)
+__device__ __forceinline__ void area_search_threads_body(const AreaQuery* __restrict__ queries, const unsigned long long* __restrict__ qdesc, int Q,
+                                                         const KeyPointRec* __restrict__ kps, const float* __restrict__ u_right,
+                                                         const unsigned long long* __restrict__ fdesc, const GridParams& g, const int* __restrict__ cell_start,
+                                                         const int* __restrict__ cell_items, int gate_right, int* __restrict__ pool_counter, int pool_cap,
+                                                         int* __restrict__ q_start, int* __restrict__ q_count, int2* __restrict__ entries) {
     __shared__ int s_scan[20];
     __shared__ int s_base;
     // the first kAreaKeep accepted keypoints of every query (index | octave << 16), [slot][thread]: the second pass - Hamming distances and the
     // writes - then reads them back instead of walking the window, its cells, keypoint records and gates again (round 4; most queries accept fewer)
     constexpr int kAreaKeep = 12;
     __shared__ uint32_t s_keep[kAreaKeep * 256];
-    const size_t b = blockIdx.y;
     const int q = (int)(blockIdx.x * 256 + threadIdx.x);
-    queries += b * (size_t)Q; q_start += b * (size_t)Q; q_count += b * (size_t)Q;
-    if (qdesc_per_frame) qdesc += 4 * b * (size_t)Q;               // every frame brings its own query descriptors (the map points of ITS last frame)
-    kps += b * (size_t)frame_stride; u_right += b * (size_t)frame_stride; fdesc += 4 * b * (size_t)frame_stride;
-    cell_start += b * (size_t)kGridCellStride; cell_items += b * (size_t)frame_stride;
     AreaQuery A{};
     if (q < Q) A = queries[q];
     const int nMinX = imax(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(A.x, g.min_x), A.r), g.gw_inv)));
@@ -527,6 +538,31 @@ __global__ void __launch_bounds__(256) k_area_search_threads(const AreaQuery* __
     }
     if (q < Q) { q_start[q] = fits ? start : 0; q_count[q] = fits ? cnt : 0; }
 }
+__global__ void __launch_bounds__(256) k_area_search_threads(const AreaQuery* __restrict__ queries, const unsigned long long* __restrict__ qdesc, int Q,
+                                                             const KeyPointRec* __restrict__ kps, const float* __restrict__ u_right,
+                                                             const unsigned long long* __restrict__ fdesc, GridParams g, const int* __restrict__ cell_start,
+                                                             const int* __restrict__ cell_items, int gate_right, int* __restrict__ pool_counter, int pool_cap,
+                                                             int* __restrict__ q_start, int* __restrict__ q_count, int2* __restrict__ entries, int frame_stride,
+                                                             int qdesc_per_frame) {
+    const size_t b = blockIdx.y, o = b * (size_t)Q, f = b * (size_t)frame_stride;
+    // qdesc_per_frame: every frame brings its own query descriptors (the map points of ITS last frame)
+    area_search_threads_body(queries + o, qdesc_per_frame ? qdesc + 4 * o : qdesc, Q, kps + f, u_right + f, fdesc + 4 * f, g, cell_start + b * (size_t)kGridCellStride,
+                             cell_items + f, gate_right, pool_counter, pool_cap, q_start + o, q_count + o, entries);
+}
+// The same for frames with their own local maps: frame b's M_b queries sit at maps[b].offset, their descriptors are those of the set maps[b] names.
+// grid ((max M_b + 255) / 256, B); a block beyond its frame's M_b leaves before the first barrier.
+__global__ void __launch_bounds__(256) k_area_search_threads_maps(const AreaQuery* __restrict__ queries, const FrameMapRec* __restrict__ maps,
+                                                                  const KeyPointRec* __restrict__ kps, const float* __restrict__ u_right,
+                                                                  const unsigned long long* __restrict__ fdesc, GridParams g, const int* __restrict__ cell_start,
+                                                                  const int* __restrict__ cell_items, int gate_right, int* __restrict__ pool_counter, int pool_cap,
+                                                                  int* __restrict__ q_start, int* __restrict__ q_count, int2* __restrict__ entries, int frame_stride) {
+    const size_t b = blockIdx.y, f = b * (size_t)frame_stride;
+    const FrameMapRec T = maps[b];
+    if ((int)(blockIdx.x * 256) >= T.M) return;
+    const size_t o = (size_t)T.offset;
+    area_search_threads_body(queries + o, T.desc, T.M, kps + f, u_right + f, fdesc + 4 * f, g, cell_start + b * (size_t)kGridCellStride, cell_items + f, gate_right,
+                             pool_counter, pool_cap, q_start + o, q_count + o, entries);
+}
 
 // ORBmatcher::SearchByProjection(Frame, MapPoints) accept loop (src/ORBmatcher.cc:62-166) on the device, one wave per frame of a batch.
 // The loop is sequential over the map points: a keypoint that has received a map point WITH observations is skipped by every later point.
@@ -545,12 +581,14 @@ __global__ void __launch_bounds__(256) k_area_search_threads(const AreaQuery* __
 // (bestDist <= TH_HIGH, no ratio test), has_obs / the query arrays are per frame, and every accepted pair goes into the rotation histogram
 // (:2118-2126, ComputeThreeMaxima :2335-2377): after the loop the pairs outside the three fullest bins are taken back (assigned = -2 = reset to
 // NULL, nmatches--) - per accept EVENT, as the reference's rotHist lists are (a keypoint that was given twice has two entries).
-template <bool LASTFRAME>
+// MAPS = the frames bring their own local maps (k_local_accept_maps): frame b has maps[b].M points, its q_start / q_count / has_obs rows start at
+// maps[b].offset (prefix sums of M_b) instead of b * M.
+template <bool LASTFRAME, bool MAPS = false>
 __device__ __forceinline__ void local_accept_body(int M, int cap, const int* __restrict__ n_per_frame, const int* __restrict__ q_start,
                                                   const int* __restrict__ q_count, const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0,
                                                   const uint8_t* __restrict__ has_obs, float nnratio, int th_high, int* __restrict__ assigned,
                                                   int* __restrict__ nmatches, const float* __restrict__ last_angle, const KeyPointRec* __restrict__ cur_kps,
-                                                  int check_ori) {
+                                                  int check_ori, const FrameMapRec* __restrict__ maps = nullptr) {
     int* events = nullptr;
     ORBX_DYN_SMEM(smem);
     const int nwords = (cap + 31) / 32;
@@ -560,7 +598,10 @@ __device__ __forceinline__ void local_accept_body(int M, int cap, const int* __r
     const int lane = lane_id();
     const size_t b = blockIdx.x;
     const int N = n_per_frame[b];
-    q_start += b * (size_t)M; q_count += b * (size_t)M; assigned += b * (size_t)cap;
+    if (MAPS) M = maps[b].M;
+    const size_t qo = MAPS ? (size_t)maps[b].offset : b * (size_t)M;
+    q_start += qo; q_count += qo; assigned += b * (size_t)cap;
+    if (MAPS && has_obs) has_obs += qo;
     if (LASTFRAME) {
         if (has_obs) has_obs += b * (size_t)M;
         last_angle += b * (size_t)M; cur_kps += b * (size_t)cap;
@@ -668,6 +709,12 @@ __global__ void __launch_bounds__(64) k_local_accept(int M, int cap, const int* 
                                                      int* __restrict__ nmatches) {
     local_accept_body<false>(M, cap, n_per_frame, q_start, q_count, entries, occupied0, has_obs, nnratio, th_high, assigned, nmatches, nullptr, nullptr, 0);
 }
+__global__ void __launch_bounds__(64) k_local_accept_maps(const FrameMapRec* __restrict__ maps, int cap, const int* __restrict__ n_per_frame, const int* __restrict__ q_start,
+                                                          const int* __restrict__ q_count, const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0,
+                                                          const uint8_t* __restrict__ has_obs, float nnratio, int th_high, int* __restrict__ assigned,
+                                                          int* __restrict__ nmatches) {
+    local_accept_body<false, true>(0, cap, n_per_frame, q_start, q_count, entries, occupied0, has_obs, nnratio, th_high, assigned, nmatches, nullptr, nullptr, 0, maps);
+}
 __global__ void __launch_bounds__(64) k_lastframe_accept(int M, int cap, const int* __restrict__ n_per_frame, const int* __restrict__ q_start,
                                                          const int* __restrict__ q_count, const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0,
                                                          const uint8_t* __restrict__ has_obs, int th_high, int* __restrict__ assigned, int* __restrict__ nmatches,
@@ -681,6 +728,26 @@ __global__ void __launch_bounds__(64) k_lastframe_accept(int M, int cap, const i
 // the one frustum_body writes (the search runs with the right-coordinate gate off: a rig frame has no mvuRight).  Camera 2's (src/ORBmatcher.cc:
 // 170-176): the point is alive (in view of either camera, not far by camera 1's depth, not bad), in camera 2's view with a level; radius
 // RadiusByViewingCos(mTrackViewCosR) WITHOUT th; levels [level - 1, level].  Every output of camera c of frame b sits at b * M (track: b * 5 * M).
+// (the body, point i of a frame: every array is THAT frame's - M rows, track 5 M)
+__device__ __forceinline__ void frustum_rig_body(const FrustumParams& F1, const FrustumParams& F2, int i, int M, const float* __restrict__ pos,
+                                                 const float* __restrict__ normal, const float* __restrict__ min_dist, const float* __restrict__ max_dist,
+                                                 const uint8_t* __restrict__ is_bad, uint8_t* in_view1, uint8_t* in_view2, float* track1, float* track2, int* level1,
+                                                 int* level2, AreaQuery* __restrict__ q1, AreaQuery* __restrict__ q2) {
+    const size_t Ms = (size_t)M;
+    frustum_body(F1, i, M, pos, normal, min_dist, max_dist, is_bad, in_view1, track1, level1, q1);
+    frustum_body(F2, i, M, pos, normal, min_dist, max_dist, is_bad, in_view2, track2, level2, nullptr);
+    // (this thread's own stores, read back)
+    const bool inl = in_view1[i] != 0, inr = in_view2[i] != 0;
+    const int lvl = level2[i];
+    AreaQuery q; q.x = 0; q.y = 0; q.r = 0; q.ur = 0; q.min_level = 0; q.max_level = 0; q.active = 0; q.gate = 0;
+    const bool alive = (inl || inr) && !(F1.far_points && track1[3 * Ms + i] > F1.th_far) && !(is_bad && is_bad[i]);
+    if (alive && inr && lvl >= 0 && lvl < F2.nlevels) {
+        const float r = (double)track2[4 * Ms + i] > 0.998 ? 2.5f : 4.0f;
+        q.x = track2[i]; q.y = track2[Ms + i]; q.r = __fmul_rn(r, pick(F2.scale_factors, lvl));
+        q.min_level = lvl - 1; q.max_level = lvl; q.active = 1;
+    }
+    q2[i] = q;
+}
 __global__ void __launch_bounds__(256) k_frustum_rig(const FrustumParams* __restrict__ Fb, int M, const float* __restrict__ pos, const float* __restrict__ normal,
                                                      const float* __restrict__ min_dist, const float* __restrict__ max_dist, const uint8_t* __restrict__ is_bad,
                                                      uint8_t* in_view1, uint8_t* in_view2, float* track1, float* track2, int* level1, int* level2,
@@ -689,22 +756,23 @@ __global__ void __launch_bounds__(256) k_frustum_rig(const FrustumParams* __rest
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
     if (zero4 && i < 4 && b == 0) zero4[i] = 0;
     if (i >= M) return;
-    const FrustumParams& F1 = Fb[2 * b];
-    const FrustumParams& F2 = Fb[2 * b + 1];
-    const size_t o = b * (size_t)M, ot = 5 * o, Ms = (size_t)M;
-    frustum_body(F1, i, M, pos, normal, min_dist, max_dist, is_bad, in_view1 + o, track1 + ot, level1 + o, q1 + o);
-    frustum_body(F2, i, M, pos, normal, min_dist, max_dist, is_bad, in_view2 + o, track2 + ot, level2 + o, nullptr);
-    // (this thread's own stores, read back)
-    const bool inl = in_view1[o + i] != 0, inr = in_view2[o + i] != 0;
-    const int lvl = level2[o + i];
-    AreaQuery q; q.x = 0; q.y = 0; q.r = 0; q.ur = 0; q.min_level = 0; q.max_level = 0; q.active = 0; q.gate = 0;
-    const bool alive = (inl || inr) && !(F1.far_points && track1[ot + 3 * Ms + i] > F1.th_far) && !(is_bad && is_bad[i]);
-    if (alive && inr && lvl >= 0 && lvl < F2.nlevels) {
-        const float r = (double)track2[ot + 4 * Ms + i] > 0.998 ? 2.5f : 4.0f;
-        q.x = track2[ot + i]; q.y = track2[ot + Ms + i]; q.r = __fmul_rn(r, pick(F2.scale_factors, lvl));
-        q.min_level = lvl - 1; q.max_level = lvl; q.active = 1;
-    }
-    q2[o + i] = q;
+    const size_t o = b * (size_t)M, ot = 5 * o;
+    frustum_rig_body(Fb[2 * b], Fb[2 * b + 1], i, M, pos, normal, min_dist, max_dist, is_bad, in_view1 + o, in_view2 + o, track1 + ot, track2 + ot, level1 + o, level2 + o,
+                     q1 + o, q2 + o);
+}
+// The same for rig frames with their own local maps (orbm_search_local_points_rig_batch_maps): frame b reads the set maps[b] names and writes at
+// maps[b].offset (track: 5 x offset), as k_frustum_maps does.
+__global__ void __launch_bounds__(256) k_frustum_rig_maps(const FrustumParams* __restrict__ Fb, const FrameMapRec* __restrict__ maps, const uint8_t* __restrict__ is_bad,
+                                                          uint8_t* in_view1, uint8_t* in_view2, float* track1, float* track2, int* level1, int* level2,
+                                                          AreaQuery* __restrict__ q1, AreaQuery* __restrict__ q2, int* __restrict__ zero4) {
+    const size_t b = blockIdx.y;
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (zero4 && i < 4 && b == 0) zero4[i] = 0;
+    const FrameMapRec T = maps[b];
+    if (i >= T.M) return;
+    const size_t o = (size_t)T.offset, ot = 5 * o;
+    frustum_rig_body(Fb[2 * b], Fb[2 * b + 1], i, T.M, T.pos, T.normal, T.min_d, T.max_d, is_bad + o, in_view1 + o, in_view2 + o, track1 + ot, track2 + ot, level1 + o,
+                     level2 + o, q1 + o, q2 + o);
 }
 
 // The head of SearchByProjection(CurrentFrame, LastFrame) for B rig frames: camera 1 exactly as k_lastframe_queries; camera 2 (src/ORBmatcher.cc:
@@ -750,13 +818,14 @@ __global__ void __launch_bounds__(256) k_lastframe_queries_rig(const FrustumPara
 // occupied0: [B][2 cap] bytes in the joint slot layout or NULL; has_obs: [M] (MapPoints form) or [B][M] (LastFrame form) or NULL; l2r / r2l: [B][cap];
 // assigned: [B][2 cap]; nmatches: [B].  dynamic LDS: claim word per slot (2 cap words) | occupancy byte per slot (2 cap, 16-byte multiple) | LastFrame:
 // two events per query (2 M words, slot * 32 + bin).
-template <bool LASTFRAME>
+// MAPS (k_rig_local_accept_maps): frame b has maps[b].M points; its query rows and has_obs start at maps[b].offset.
+template <bool LASTFRAME, bool MAPS = false>
 __device__ __forceinline__ void rig_accept_body(int M, int cap, const int* __restrict__ n1, const int* __restrict__ n2, const int* __restrict__ qs1,
                                                 const int* __restrict__ qc1, const int* __restrict__ qs2, const int* __restrict__ qc2,
                                                 const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0, const uint8_t* __restrict__ has_obs,
                                                 const int* __restrict__ l2r, const int* __restrict__ r2l, float nnratio, int th_high, int* __restrict__ assigned,
                                                 int* __restrict__ nmatches, const float* __restrict__ last_angle, const KeyPointRec* __restrict__ kps1,
-                                                const KeyPointRec* __restrict__ kps2, int check_ori) {
+                                                const KeyPointRec* __restrict__ kps2, int check_ori, const FrameMapRec* __restrict__ maps = nullptr) {
     ORBX_DYN_SMEM(smem);
     const int S = 2 * cap;
     unsigned* s_claim = (unsigned*)smem;
@@ -766,7 +835,10 @@ __device__ __forceinline__ void rig_accept_body(int M, int cap, const int* __res
     const int lane = lane_id();
     const size_t b = blockIdx.x;
     const int NL = n1[b], NR = n2[b], NS = NL + NR;
-    qs1 += b * (size_t)M; qc1 += b * (size_t)M; qs2 += b * (size_t)M; qc2 += b * (size_t)M; assigned += b * (size_t)S;
+    if (MAPS) M = maps[b].M;
+    const size_t qo = MAPS ? (size_t)maps[b].offset : b * (size_t)M;
+    qs1 += qo; qc1 += qo; qs2 += qo; qc2 += qo; assigned += b * (size_t)S;
+    if (MAPS && has_obs) has_obs += qo;
     if (LASTFRAME) {
         if (has_obs) has_obs += b * (size_t)M;
         last_angle += b * (size_t)M; kps1 += b * (size_t)cap; kps2 += b * (size_t)cap;
@@ -911,6 +983,14 @@ __global__ void __launch_bounds__(64) k_rig_local_accept(int M, int cap, const i
                                                          const int* __restrict__ l2r, const int* __restrict__ r2l, float nnratio, int th_high,
                                                          int* __restrict__ assigned, int* __restrict__ nmatches) {
     rig_accept_body<false>(M, cap, n1, n2, qs1, qc1, qs2, qc2, entries, occupied0, has_obs, l2r, r2l, nnratio, th_high, assigned, nmatches, nullptr, nullptr, nullptr, 0);
+}
+__global__ void __launch_bounds__(64) k_rig_local_accept_maps(const FrameMapRec* __restrict__ maps, int cap, const int* __restrict__ n1, const int* __restrict__ n2,
+                                                              const int* __restrict__ qs1, const int* __restrict__ qc1, const int* __restrict__ qs2,
+                                                              const int* __restrict__ qc2, const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0,
+                                                              const uint8_t* __restrict__ has_obs, const int* __restrict__ l2r, const int* __restrict__ r2l, float nnratio,
+                                                              int th_high, int* __restrict__ assigned, int* __restrict__ nmatches) {
+    rig_accept_body<false, true>(0, cap, n1, n2, qs1, qc1, qs2, qc2, entries, occupied0, has_obs, l2r, r2l, nnratio, th_high, assigned, nmatches, nullptr, nullptr, nullptr, 0,
+                                 maps);
 }
 __global__ void __launch_bounds__(64) k_rig_lastframe_accept(int M, int cap, const int* __restrict__ n1, const int* __restrict__ n2, const int* __restrict__ qs1,
                                                              const int* __restrict__ qc1, const int* __restrict__ qs2, const int* __restrict__ qc2,

@@ -612,6 +612,50 @@ GridParams grid_from_view(const OrbmFrustumView& v) {
 }
 // entries of the candidate pool: what the last batch grew it to, or `expected` for this one; the kernels count entries in an int
 size_t batch_pool(const orbx_extractor* h, size_t expected) { return std::min<size_t>(std::max(h->lp_pool, expected), 0x7fffffff / 2); }
+// The local maps of a batched SearchLocalPoints: ONE resident set and one pair of flag arrays for every frame (maps == nullptr: frame b's scratch rows at
+// b * M), or one OrbmFrameMap per frame (frame b's rows at the prefix sum of M_b, flags uploaded per frame, the table of the k_*_maps kernels in the upload)
+struct BatchMaps {
+    const orbm_points* one; const uint8_t *is_bad, *has_obs; const OrbmFrameMap* maps; int B;
+    int m_max = 0; size_t rows = 1, flags = 1;     // largest map; scratch rows of the batch; bytes of ONE uploaded flag array
+    std::vector<int> M;                            // per frame (per-frame form)
+    size_t table_bytes() const { return maps ? sizeof(FrameMapRec) * (size_t)B : 0; }
+    int plan(int device) {
+        if (!maps) {
+            if (one->device != device) return fail(ORBX_E_ARG, "map points live on another device");
+            m_max = one->M; flags = m_max > 0 ? m_max : 1; rows = (size_t)B * flags;
+            return ORBX_OK;
+        }
+        size_t sum = 0;
+        M.resize(B);
+        for (int b = 0; b < B; b++) {
+            const orbm_points* s = maps[b].points;
+            if (s && s->device != device) return fail(ORBX_E_ARG, "frame %d: its map points live on another device", b);
+            M[b] = s && s->M > 0 ? s->M : 0; sum += (size_t)M[b]; m_max = std::max(m_max, M[b]);
+        }
+        if (sum > 0x7fffffff / 32) return fail(ORBX_E_CAPACITY, "%zu map points in one batch", sum);      // (offsets are ints; 5 floats of track per row)
+        rows = flags = sum > 0 ? sum : 1;
+        return ORBX_OK;
+    }
+    void stage(uint8_t* tab, uint8_t* bad, uint8_t* obs) const {
+        if (!maps) {
+            if (is_bad) memcpy(bad, is_bad, flags); else memset(bad, 0, flags);
+            if (has_obs) memcpy(obs, has_obs, flags); else memset(obs, 1, flags);
+            return;
+        }
+        FrameMapRec* T = (FrameMapRec*)tab;
+        size_t o = 0;
+        for (int b = 0; b < B; b++) {
+            const orbm_points* s = maps[b].points; const size_t m = (size_t)M[b];
+            FrameMapRec r; memset(&r, 0, sizeof r);
+            if (m) { r.pos = s->pos; r.normal = s->normal; r.min_d = s->min_d; r.max_d = s->max_d; r.desc = s->desc; }
+            r.M = (int)m; r.offset = (int)o;
+            T[b] = r;
+            if (maps[b].is_bad) memcpy(bad + o, maps[b].is_bad, m); else memset(bad + o, 0, m);
+            if (maps[b].has_obs) memcpy(obs + o, maps[b].has_obs, m); else memset(obs + o, 1, m);
+            o += m;
+        }
+    }
+};
 // the grid of one camera for B frames (k_grid_build: cell_of, cell_start, cell_items)
 struct GridBlock {
     size_t cof, cst, cit;
@@ -651,9 +695,13 @@ int batch_fetch(orbx_extractor* h, size_t slots, const char* what, int* assigned
     const size_t B1 = h->lp_B, M1 = h->lp_M > 0 ? h->lp_M : 0;
     const ResultBlock res(B1, slots);
     const size_t view_off[2] = {h->lp_o_view, h->lp_o_view_r};
+    // mbTrackInView on the device: [B][M], or - frames with their own maps - frame b's M_b bytes at the prefix sum; the caller's rows are M = max M_b apart
+    const std::vector<int>& Mb = h->lp_maps_M;
+    size_t vb = B1 * M1;
+    if (!Mb.empty()) { vb = 0; for (int m : Mb) vb += (size_t)m; }
     uint8_t* hp = h->h_lp_out.p;
     int e = rt::copy_d2h(hp, h->d_lp.p + h->lp_o_counter, res.bytes, h->s0);
-    if (fetch_views) for (int v = 0; v < nviews; v++) e |= rt::copy_d2h(hp + al16(res.bytes) + v * B1 * M1, h->d_lp.p + view_off[v], B1 * M1, h->s0);
+    if (fetch_views) for (int v = 0; v < nviews; v++) e |= rt::copy_d2h(hp + al16(res.bytes) + v * vb, h->d_lp.p + view_off[v], vb, h->s0);
     if (e || rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "%s failed: %s", what, rt::last_error());
     h->lp_pending = false;
     if (h->profile) h->stage_ms[ST_MATCH] = rt::event_elapsed_ms(h->ev_stage[ST_MATCH][0], h->ev_stage[ST_MATCH][1]);
@@ -668,48 +716,55 @@ int batch_fetch(orbx_extractor* h, size_t slots, const char* what, int* assigned
         if ((size_t)cap == slots) memcpy(assigned, src, 4 * B1 * slots);
         else for (size_t b = 0; b < B1; b++) memcpy(assigned + b * (size_t)cap, src + b * slots, 4 * slots);
     }
-    if (fetch_views) for (int v = 0; v < nviews; v++) if (views[v]) memcpy(views[v], hp + al16(res.bytes) + v * B1 * M1, B1 * M1);
+    if (fetch_views) for (int v = 0; v < nviews; v++) if (views[v]) {
+        const uint8_t* src = hp + al16(res.bytes) + v * vb;
+        if (Mb.empty()) { memcpy(views[v], src, vb); continue; }
+        for (size_t b = 0; b < B1; b++) {
+            const size_t m = (size_t)Mb[b];
+            memcpy(views[v] + b * M1, src, m); memset(views[v] + b * M1 + m, 0, M1 - m);
+            src += m;
+        }
+    }
     return ORBX_OK;
 }
-}  // namespace
-extern "C" {
-
-int orbm_search_local_points_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView* frames, const orbm_points* points, const uint8_t* is_bad,
-                                   const uint8_t* has_obs, const uint8_t* occupied, int use_u_right, float cos_limit, float th, int far_points, float th_far,
-                                   float nnratio, int want_in_view) {
+// orbm_search_local_points_batch (one resident set, `maps` == NULL) and orbm_search_local_points_batch_maps (maps[b] = frame b's own)
+int local_points_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView* frames, const orbm_points* points, const uint8_t* is_bad, const uint8_t* has_obs,
+                       const OrbmFrameMap* maps, const uint8_t* occupied, int use_u_right, float cos_limit, float th, int far_points, float th_far, float nnratio,
+                       int want_in_view) {
     if (h) { h->lp_B = 0; h->lp_rig = false; }     // a new enqueue - accepted or refused - ends the previous batch: a refused call leaves nothing to fetch
-    if (!h || !frames || !points || B <= 0 || first < 0 || first + B > h->lastB) return fail(ORBX_E_ARG, "bad frame range / null");
-    if (points->device != h->device) return fail(ORBX_E_ARG, "map points live on another device");
+    if (!h || !frames || (!points && !maps) || B <= 0 || first < 0 || first + B > h->lastB) return fail(ORBX_E_ARG, "bad frame range / null");
+    BatchMaps P{points, is_bad, has_obs, maps, B};
+    if (int rc = P.plan(h->device)) return rc;
     if (int rc = frames_check(frames, sizeof *frames, B)) return rc;
     if (undistort_stale(h)) return fail(ORBX_E_ARG, "orbx_set_undistort was called after the last extraction: extract again before searching its frames");
     rt::set_device(h->device);
-    const int M = points->M, cap = h->kp_total_cap;
-    const size_t B1 = B, M1 = M > 0 ? M : 1, C1 = cap;
+    const int M = P.m_max, cap = h->kp_total_cap;
+    const size_t B1 = B, C1 = cap, rows = P.rows;
     // every refusal comes BEFORE anything is enqueued into the shared block, and leaves no batch to fetch
     const size_t smem_accept = 4 * (size_t)((cap + 31) / 32) + 4 * (size_t)cap + 64;
     if (smem_accept + 1024 > rt::lds_limit(h->device)) { h->lp_B = 0; return fail(ORBX_E_CAPACITY, "%d keypoints per frame need %zu bytes of LDS in the accept kernel", cap, smem_accept); }
     h->lp_B = 0;                                                // the block is about to be overwritten: a previous, unfetched batch is gone
     if (h->lp_pending) { rt::event_sync(h->ev_lp); }            // the staging block of the previous enqueue has been consumed
-    // upload block: poses | bad flags | has-observation flags | occupancy
+    // upload block: poses | the table of per-frame maps | bad flags | has-observation flags | occupancy
     Bump u;
-    const size_t u_f = u.take(sizeof(FrustumParams) * B1), u_bad = u.take(M1), u_obs = u.take(M1), u_occ = u.take(occupied ? B1 * C1 : 0), u_total = u.o;
+    const size_t u_f = u.take(sizeof(FrustumParams) * B1), u_tab = u.take(P.table_bytes()), u_bad = u.take(P.flags), u_obs = u.take(P.flags),
+                 u_occ = u.take(occupied ? B1 * C1 : 0), u_total = u.o;
     // device block: upload | uRight of "no stereo" | grid | queries | track | level | in_view | q_start | q_count | result | entry pool
+    // (`rows` of each: B x M, or the sum of the frames' own M_b)
     Bump d(u_total);
     const size_t o_ur = d.take(use_u_right ? 0 : 4 * B1 * C1);
     const GridBlock G(d, B1, C1);
-    const size_t o_q = d.take(sizeof(AreaQuery) * B1 * M1), o_trk = d.take(20 * B1 * M1), o_lvl = d.take(4 * B1 * M1), o_view = d.take(B1 * M1), o_qs = d.take(4 * B1 * M1),
-                 o_qc = d.take(4 * B1 * M1);
+    const size_t o_q = d.take(sizeof(AreaQuery) * rows), o_trk = d.take(20 * rows), o_lvl = d.take(4 * rows), o_view = d.take(rows), o_qs = d.take(4 * rows), o_qc = d.take(4 * rows);
     const ResultBlock res(B1, C1);
     const size_t o_res = d.take(res.bytes), o_pool = d.o;
-    const size_t pool = batch_pool(h, B1 * M1 * 6 + 4096);
-    if (h->d_lp.ensure(o_pool + pool * 8 + 64) || h->h_lp_in.ensure(u_total + 16) || h->h_lp_out.ensure(al16(res.bytes) + (want_in_view ? B1 * M1 : 0) + 64))
-        return fail(ORBX_E_DEVICE, "allocation failed (batched local point search, %d frames x %d points)", B, M);
+    const size_t pool = batch_pool(h, rows * 6 + 4096);
+    if (h->d_lp.ensure(o_pool + pool * 8 + 64) || h->h_lp_in.ensure(u_total + 16) || h->h_lp_out.ensure(al16(res.bytes) + (want_in_view ? rows : 0) + 64))
+        return fail(ORBX_E_DEVICE, "allocation failed (batched local point search, %d frames, %zu points)", B, rows);
     h->lp_pool = pool;
     uint8_t* hp = h->h_lp_in.p; uint8_t* dp = h->d_lp.p;
     FrustumParams* Fp = (FrustumParams*)(hp + u_f);
     for (int b = 0; b < B; b++) fill_frustum_params(&frames[b], cos_limit, th, far_points, th_far, &Fp[b]);
-    if (is_bad) memcpy(hp + u_bad, is_bad, M1); else memset(hp + u_bad, 0, M1);
-    if (has_obs) memcpy(hp + u_obs, has_obs, M1); else memset(hp + u_obs, 1, M1);
+    P.stage(hp + u_tab, hp + u_bad, hp + u_obs);
     if (occupied) memcpy(hp + u_occ, occupied, B1 * C1);
     if (rt::copy_h2d(dp, hp, u_total, h->s0) || rt::event_record(h->ev_lp, h->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
     h->lp_pending = true;
@@ -725,26 +780,52 @@ int orbm_search_local_points_batch(orbx_extractor* h, int first, int B, const Or
         dim3 grid(B, 1, 1), blkg(kGridThreads, 1, 1);
         ORBX_LAUNCH(k_grid_build, grid, blkg, 0, h->s0, kps, 0, g, (int*)(dp + G.cof), (int*)(dp + G.cst), (int*)(dp + G.cit), nper, cap);
     }
-    if (M > 0) {
+    const FrameMapRec* d_tab = (const FrameMapRec*)(dp + u_tab);
+    const dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);              // M: of the one set, or the largest of the frames' own
+    if (M <= 0) rt::memset_async(d_counter, 0, 16, h->s0);
+    else if (maps) {
+        ORBX_LAUNCH(k_frustum_maps, grid, blk, 0, h->s0, (const FrustumParams*)(dp + u_f), d_tab, (const uint8_t*)(dp + u_bad), dp + o_view, (float*)(dp + o_trk),
+                    (int*)(dp + o_lvl), (AreaQuery*)(dp + o_q), d_counter);
+        ORBX_LAUNCH(k_area_search_threads_maps, grid, blk, 0, h->s0, (const AreaQuery*)(dp + o_q), d_tab, kps, ur, fdesc, g, (const int*)(dp + G.cst), (const int*)(dp + G.cit), 1,
+                    d_counter, (int)pool, (int*)(dp + o_qs), (int*)(dp + o_qc), (int2*)(dp + o_pool), cap);
+    } else {
         FrustumParams dummy; memset(&dummy, 0, sizeof dummy);
-        dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
         ORBX_LAUNCH(k_frustum, grid, blk, 0, h->s0, dummy, M, points->pos, points->normal, points->min_d, points->max_d, (const uint8_t*)(dp + u_bad),
                     dp + o_view, (float*)(dp + o_trk), (int*)(dp + o_lvl), (AreaQuery*)(dp + o_q), d_counter, (const FrustumParams*)(dp + u_f));
-        dim3 grida((M + 255) / 256, B, 1);
-        ORBX_LAUNCH(k_area_search_threads, grida, blk, 0, h->s0, (const AreaQuery*)(dp + o_q), points->desc, M, kps, ur, fdesc, g, (const int*)(dp + G.cst), (const int*)(dp + G.cit), 1,
+        ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, h->s0, (const AreaQuery*)(dp + o_q), points->desc, M, kps, ur, fdesc, g, (const int*)(dp + G.cst), (const int*)(dp + G.cit), 1,
                     d_counter, (int)pool, (int*)(dp + o_qs), (int*)(dp + o_qc), (int2*)(dp + o_pool), cap, 0);
-    } else rt::memset_async(d_counter, 0, 16, h->s0);
+    }
     {
-        dim3 grid(B, 1, 1), blk(64, 1, 1);
+        dim3 grida(B, 1, 1), blka(64, 1, 1);
         const size_t smem = smem_accept;
-        ORBX_LAUNCH(k_local_accept, grid, blk, smem, h->s0, M, cap, nper, (const int*)(dp + o_qs), (const int*)(dp + o_qc), (const int2*)(dp + o_pool),
-                    occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr, (const uint8_t*)(dp + u_obs), nnratio, TH_HIGH, d_assigned, d_nmatch);
+        const uint8_t* d_occ = occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr;
+        if (maps) ORBX_LAUNCH(k_local_accept_maps, grida, blka, smem, h->s0, d_tab, cap, nper, (const int*)(dp + o_qs), (const int*)(dp + o_qc), (const int2*)(dp + o_pool), d_occ,
+                              (const uint8_t*)(dp + u_obs), nnratio, TH_HIGH, d_assigned, d_nmatch);
+        else ORBX_LAUNCH(k_local_accept, grida, blka, smem, h->s0, M, cap, nper, (const int*)(dp + o_qs), (const int*)(dp + o_qc), (const int2*)(dp + o_pool), d_occ,
+                         (const uint8_t*)(dp + u_obs), nnratio, TH_HIGH, d_assigned, d_nmatch);
     }
     if (h->profile) rt::event_record(h->ev_stage[ST_MATCH][1], h->s0);
     if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
-    h->lp_B = B; h->lp_M = M; h->lp_first = first; h->lp_o_counter = o_res; h->lp_o_view = o_view; h->lp_want_view = want_in_view != 0;
+    h->lp_B = B; h->lp_M = M; h->lp_first = first; h->lp_o_counter = o_res; h->lp_o_view = o_view; h->lp_want_view = want_in_view != 0; h->lp_maps_M = P.M;
     return ORBX_OK;
 }
+}  // namespace
+extern "C" {
+
+int orbm_search_local_points_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView* frames, const orbm_points* points, const uint8_t* is_bad,
+                                   const uint8_t* has_obs, const uint8_t* occupied, int use_u_right, float cos_limit, float th, int far_points, float th_far,
+                                   float nnratio, int want_in_view) {
+    if (h && !points) { h->lp_B = 0; h->lp_rig = false; return fail(ORBX_E_ARG, "bad frame range / null"); }
+    return local_points_batch(h, first, B, frames, points, is_bad, has_obs, nullptr, occupied, use_u_right, cos_limit, th, far_points, th_far, nnratio, want_in_view);
+}
+
+int orbm_search_local_points_batch_maps(orbx_extractor* h, int first, int B, const OrbmFrustumView* frames, const OrbmFrameMap* maps, const uint8_t* occupied,
+                                        int use_u_right, float cos_limit, float th, int far_points, float th_far, float nnratio, int want_in_view) {
+    if (h && !maps) { h->lp_B = 0; h->lp_rig = false; return fail(ORBX_E_ARG, "null table of per-frame maps"); }
+    return local_points_batch(h, first, B, frames, nullptr, nullptr, nullptr, maps, occupied, use_u_right, cos_limit, th, far_points, th_far, nnratio, want_in_view);
+}
+
+int orbm_points_count(const orbm_points* p) { return p ? p->M : 0; }
 
 namespace {
 // SearchByProjection(CurrentFrame, LastFrame) (keyframe = false) or (CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (keyframe = true) for B frames
@@ -1895,17 +1976,18 @@ int rig_pair_check(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B) 
 // the device block of a rig batch behind the upload: two grids, two query sets and CSRs, `extra` bytes of the caller's, the result, the entry pool
 struct RigBlock {
     Bump d; GridBlock g1, g2; size_t q1, q2, qs1, qc1, qs2, qc2, extra; ResultBlock r; size_t res, pool;
-    RigBlock(size_t o, size_t B1, size_t M1, size_t C1, size_t extra_bytes) : d(o), g1(d, B1, C1), g2(d, B1, C1), r(B1, 2 * C1) {
-        q1 = d.take(sizeof(AreaQuery) * B1 * M1); q2 = d.take(sizeof(AreaQuery) * B1 * M1);
-        qs1 = d.take(4 * B1 * M1); qc1 = d.take(4 * B1 * M1); qs2 = d.take(4 * B1 * M1); qc2 = d.take(4 * B1 * M1);
+    RigBlock(size_t o, size_t B1, size_t rows, size_t C1, size_t extra_bytes) : d(o), g1(d, B1, C1), g2(d, B1, C1), r(B1, 2 * C1) {       // rows: query rows of the whole batch
+        q1 = d.take(sizeof(AreaQuery) * rows); q2 = d.take(sizeof(AreaQuery) * rows);
+        qs1 = d.take(4 * rows); qc1 = d.take(4 * rows); qs2 = d.take(4 * rows); qc2 = d.take(4 * rows);
         extra = d.take(extra_bytes); res = d.take(r.bytes); pool = d.o;
     }
 };
 // grids of both cameras, then the window searches of both query sets into one entry pool (the right-coordinate gate off: a rig frame has no mvuRight)
-// queries(): the launch that writes both query sets (and zeroes the pool counter)
+// queries(): the launch that writes both query sets (and zeroes the pool counter).  maps (device) != NULL: the frames bring their own local maps - M is the
+// largest, the query rows and descriptors come from the table
 template <typename Queries>
 void rig_searches(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, int M, const RigBlock& K, uint8_t* dp, const GridParams& g,
-                  const unsigned long long* qdesc, int qdesc_per_frame, size_t pool, const Queries& queries) {
+                  const unsigned long long* qdesc, int qdesc_per_frame, const FrameMapRec* maps, size_t pool, const Queries& queries) {
     const int cap = L->kp_total_cap;
     const KeyPointRec* kps1 = L->d_kps.p + (size_t)lf * cap; const KeyPointRec* kps2 = R->d_kps.p + (size_t)rf * cap;
     int* d_counter = (int*)(dp + K.res);
@@ -1918,40 +2000,46 @@ void rig_searches(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, i
     queries();
     const float* no_ur = (const float*)dp;                       // never read: gate_right = 0
     dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
+    if (maps) {
+        ORBX_LAUNCH(k_area_search_threads_maps, grid, blk, 0, L->s0, (const AreaQuery*)(dp + K.q1), maps, kps1, no_ur, L->d_desc.p + (size_t)lf * cap * 4, g,
+                    (const int*)(dp + K.g1.cst), (const int*)(dp + K.g1.cit), 0, d_counter, (int)pool, (int*)(dp + K.qs1), (int*)(dp + K.qc1), (int2*)(dp + K.pool), cap);
+        ORBX_LAUNCH(k_area_search_threads_maps, grid, blk, 0, L->s0, (const AreaQuery*)(dp + K.q2), maps, kps2, no_ur, R->d_desc.p + (size_t)rf * cap * 4, g,
+                    (const int*)(dp + K.g2.cst), (const int*)(dp + K.g2.cit), 0, d_counter, (int)pool, (int*)(dp + K.qs2), (int*)(dp + K.qc2), (int2*)(dp + K.pool), cap);
+        return;
+    }
     ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, L->s0, (const AreaQuery*)(dp + K.q1), qdesc, M, kps1, no_ur, L->d_desc.p + (size_t)lf * cap * 4, g,
                 (const int*)(dp + K.g1.cst), (const int*)(dp + K.g1.cit), 0, d_counter, (int)pool, (int*)(dp + K.qs1), (int*)(dp + K.qc1), (int2*)(dp + K.pool), cap, qdesc_per_frame);
     ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, L->s0, (const AreaQuery*)(dp + K.q2), qdesc, M, kps2, no_ur, R->d_desc.p + (size_t)rf * cap * 4, g,
                 (const int*)(dp + K.g2.cst), (const int*)(dp + K.g2.cit), 0, d_counter, (int)pool, (int*)(dp + K.qs2), (int*)(dp + K.qc2), (int2*)(dp + K.pool), cap, qdesc_per_frame);
 }
 size_t rig_accept_lds(int cap, int events) { const size_t S = 2 * (size_t)cap; return 4 * S + al16(S) + 4 * (size_t)events + 64; }
-}  // namespace
-extern "C" {
-
-int orbm_search_local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* frames, const orbm_points* points,
-                                       const uint8_t* is_bad, const uint8_t* has_obs, const uint8_t* occupied, float cos_limit, float th, int far_points,
-                                       float th_far, float nnratio, int want_in_view) {
+// orbm_search_local_points_rig_batch (one resident set, `maps` == NULL) and orbm_search_local_points_rig_batch_maps (maps[b] = frame b's own)
+int local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* frames, const orbm_points* points,
+                           const uint8_t* is_bad, const uint8_t* has_obs, const OrbmFrameMap* maps, const uint8_t* occupied, float cos_limit, float th, int far_points,
+                           float th_far, float nnratio, int want_in_view) {
     if (L) { L->lp_B = 0; L->lp_rig = false; }                     // a new enqueue ends the previous batch; a refused one leaves nothing to fetch
-    if (!L || !frames || !points) return fail(ORBX_E_ARG, "null");
+    if (!L || !frames || (!points && !maps)) return fail(ORBX_E_ARG, "null");
     int rc = rig_pair_check(L, lf, R, rf, B); if (rc) return rc;
     if ((rc = frames_check(&frames[0].left, sizeof *frames, B))) return rc;
-    if (points->device != L->device) return fail(ORBX_E_ARG, "map points live on another device");
+    BatchMaps P{points, is_bad, has_obs, maps, B};
+    if ((rc = P.plan(L->device))) return rc;
     rt::set_device(L->device);
-    const int M = points->M, cap = L->kp_total_cap;
-    const size_t B1 = B, M1 = M > 0 ? M : 1, C1 = cap, S1 = 2 * C1;
+    const int M = P.m_max, cap = L->kp_total_cap;
+    const size_t B1 = B, C1 = cap, S1 = 2 * C1, rows = P.rows;
     const size_t smem_accept = rig_accept_lds(cap, 0);
     if (smem_accept + 1024 > rt::lds_limit(L->device)) return fail(ORBX_E_CAPACITY, "%d keypoints per camera need %zu bytes of LDS in the rig accept kernel", cap, smem_accept);
     if (L->lp_pending) rt::event_sync(L->ev_lp);               // the staging block of the previous enqueue has been consumed
-    // upload: [camera 1, camera 2] parameters per frame | bad flags | has-observation flags | occupancy [B][2 cap]
+    // upload: [camera 1, camera 2] parameters per frame | the table of per-frame maps | bad flags | has-observation flags | occupancy [B][2 cap]
     Bump u;
-    const size_t u_f = u.take(sizeof(FrustumParams) * 2 * B1), u_bad = u.take(M1), u_obs = u.take(M1), u_occ = u.take(occupied ? B1 * S1 : 0), u_total = u.o;
-    // behind the common block: per camera track [B][5 M] | level [B][M] | in_view [B][M]
+    const size_t u_f = u.take(sizeof(FrustumParams) * 2 * B1), u_tab = u.take(P.table_bytes()), u_bad = u.take(P.flags), u_obs = u.take(P.flags),
+                 u_occ = u.take(occupied ? B1 * S1 : 0), u_total = u.o;
+    // behind the common block: per camera track [5 rows] | level [rows] | in_view [rows]   (rows: B x M, or the sum of the frames' own M_b)
     Bump t;
-    const size_t o_trk1 = t.take(20 * B1 * M1), o_trk2 = t.take(20 * B1 * M1), o_lvl1 = t.take(4 * B1 * M1), o_lvl2 = t.take(4 * B1 * M1), o_view1 = t.take(B1 * M1),
-                 o_view2 = t.take(B1 * M1);
-    const RigBlock K(u_total, B1, M1, C1, t.o);
-    const size_t ox = K.extra, pool = batch_pool(L, B1 * M1 * 12 + 4096);
-    if (L->d_lp.ensure(K.pool + pool * 8 + 64) || L->h_lp_in.ensure(u_total + 16) || L->h_lp_out.ensure(al16(K.r.bytes) + (want_in_view ? 2 * B1 * M1 : 0) + 64))
-        return fail(ORBX_E_DEVICE, "allocation failed (batched rig local point search, %d frames x %d points)", B, M);
+    const size_t o_trk1 = t.take(20 * rows), o_trk2 = t.take(20 * rows), o_lvl1 = t.take(4 * rows), o_lvl2 = t.take(4 * rows), o_view1 = t.take(rows), o_view2 = t.take(rows);
+    const RigBlock K(u_total, B1, rows, C1, t.o);
+    const size_t ox = K.extra, pool = batch_pool(L, rows * 12 + 4096);
+    if (L->d_lp.ensure(K.pool + pool * 8 + 64) || L->h_lp_in.ensure(u_total + 16) || L->h_lp_out.ensure(al16(K.r.bytes) + (want_in_view ? 2 * rows : 0) + 64))
+        return fail(ORBX_E_DEVICE, "allocation failed (batched rig local point search, %d frames, %zu points)", B, rows);
     L->lp_pool = pool;
     uint8_t* hp = L->h_lp_in.p; uint8_t* dp = L->d_lp.p;
     FrustumParams* Fp = (FrustumParams*)(hp + u_f);
@@ -1959,32 +2047,54 @@ int orbm_search_local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor
         fill_frustum_params(&frames[b].left, cos_limit, th, far_points, th_far, &Fp[2 * b]); Fp[2 * b].rig_mode = 1;
         right_camera_params(&frames[b], cos_limit, &Fp[2 * b + 1]);
     }
-    if (is_bad) memcpy(hp + u_bad, is_bad, M1); else memset(hp + u_bad, 0, M1);
-    if (has_obs) memcpy(hp + u_obs, has_obs, M1); else memset(hp + u_obs, 1, M1);
+    P.stage(hp + u_tab, hp + u_bad, hp + u_obs);
     if (occupied) memcpy(hp + u_occ, occupied, B1 * S1);
     if (rt::copy_h2d(dp, hp, u_total, L->s0) || rt::event_record(L->ev_lp, L->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
     L->lp_pending = true;
     if (L != R) { record_done_if_pending(R); rt::stream_wait_event(L->s0, R->ev_done); }
     uint8_t* dx = dp + ox;
+    const FrameMapRec* d_tab = maps ? (const FrameMapRec*)(dp + u_tab) : nullptr;
     if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][0], L->s0);
-    rig_searches(L, lf, R, rf, B, M, K, dp, grid_from_view(frames[0].left), points->desc, 0, pool, [&]() {
+    rig_searches(L, lf, R, rf, B, M, K, dp, grid_from_view(frames[0].left), points ? points->desc : nullptr, 0, d_tab, pool, [&]() {
         dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
-        ORBX_LAUNCH(k_frustum_rig, grid, blk, 0, L->s0, (const FrustumParams*)(dp + u_f), M, points->pos, points->normal, points->min_d, points->max_d,
-                    (const uint8_t*)(dp + u_bad), dx + o_view1, dx + o_view2, (float*)(dx + o_trk1), (float*)(dx + o_trk2), (int*)(dx + o_lvl1), (int*)(dx + o_lvl2),
-                    (AreaQuery*)(dp + K.q1), (AreaQuery*)(dp + K.q2), (int*)(dp + K.res));
+        if (maps) ORBX_LAUNCH(k_frustum_rig_maps, grid, blk, 0, L->s0, (const FrustumParams*)(dp + u_f), d_tab, (const uint8_t*)(dp + u_bad), dx + o_view1, dx + o_view2,
+                              (float*)(dx + o_trk1), (float*)(dx + o_trk2), (int*)(dx + o_lvl1), (int*)(dx + o_lvl2), (AreaQuery*)(dp + K.q1), (AreaQuery*)(dp + K.q2),
+                              (int*)(dp + K.res));
+        else ORBX_LAUNCH(k_frustum_rig, grid, blk, 0, L->s0, (const FrustumParams*)(dp + u_f), M, points->pos, points->normal, points->min_d, points->max_d,
+                         (const uint8_t*)(dp + u_bad), dx + o_view1, dx + o_view2, (float*)(dx + o_trk1), (float*)(dx + o_trk2), (int*)(dx + o_lvl1), (int*)(dx + o_lvl2),
+                         (AreaQuery*)(dp + K.q1), (AreaQuery*)(dp + K.q2), (int*)(dp + K.res));
     });
     {
         dim3 grid(B, 1, 1), blk(64, 1, 1);
-        ORBX_LAUNCH(k_rig_local_accept, grid, blk, smem_accept, L->s0, M, cap, (const int*)(L->d_nm.p + lf), (const int*)(R->d_nm.p + rf), (const int*)(dp + K.qs1),
-                    (const int*)(dp + K.qc1), (const int*)(dp + K.qs2), (const int*)(dp + K.qc2), (const int2*)(dp + K.pool),
-                    occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr, (const uint8_t*)(dp + u_obs), (const int*)L->d_l2r.p, (const int*)L->d_r2l.p,
-                    nnratio, TH_HIGH, (int*)(dp + K.res + K.r.assigned), (int*)(dp + K.res + K.r.nmatches));
+        const uint8_t* d_occ = occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr;
+        if (maps) ORBX_LAUNCH(k_rig_local_accept_maps, grid, blk, smem_accept, L->s0, d_tab, cap, (const int*)(L->d_nm.p + lf), (const int*)(R->d_nm.p + rf),
+                              (const int*)(dp + K.qs1), (const int*)(dp + K.qc1), (const int*)(dp + K.qs2), (const int*)(dp + K.qc2), (const int2*)(dp + K.pool), d_occ,
+                              (const uint8_t*)(dp + u_obs), (const int*)L->d_l2r.p, (const int*)L->d_r2l.p, nnratio, TH_HIGH, (int*)(dp + K.res + K.r.assigned),
+                              (int*)(dp + K.res + K.r.nmatches));
+        else ORBX_LAUNCH(k_rig_local_accept, grid, blk, smem_accept, L->s0, M, cap, (const int*)(L->d_nm.p + lf), (const int*)(R->d_nm.p + rf), (const int*)(dp + K.qs1),
+                         (const int*)(dp + K.qc1), (const int*)(dp + K.qs2), (const int*)(dp + K.qc2), (const int2*)(dp + K.pool), d_occ, (const uint8_t*)(dp + u_obs),
+                         (const int*)L->d_l2r.p, (const int*)L->d_r2l.p, nnratio, TH_HIGH, (int*)(dp + K.res + K.r.assigned), (int*)(dp + K.res + K.r.nmatches));
     }
     if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][1], L->s0);
     if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
     L->lp_B = B; L->lp_M = M; L->lp_first = lf; L->lp_o_counter = K.res; L->lp_o_view = ox + o_view1; L->lp_o_view_r = ox + o_view2;
-    L->lp_want_view = want_in_view != 0; L->lp_rig = true;
+    L->lp_want_view = want_in_view != 0; L->lp_rig = true; L->lp_maps_M = P.M;
     return ORBX_OK;
+}
+}  // namespace
+extern "C" {
+
+int orbm_search_local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* frames, const orbm_points* points,
+                                       const uint8_t* is_bad, const uint8_t* has_obs, const uint8_t* occupied, float cos_limit, float th, int far_points,
+                                       float th_far, float nnratio, int want_in_view) {
+    if (L && !points) { L->lp_B = 0; L->lp_rig = false; return fail(ORBX_E_ARG, "null"); }
+    return local_points_rig_batch(L, lf, R, rf, B, frames, points, is_bad, has_obs, nullptr, occupied, cos_limit, th, far_points, th_far, nnratio, want_in_view);
+}
+
+int orbm_search_local_points_rig_batch_maps(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* frames, const OrbmFrameMap* maps,
+                                            const uint8_t* occupied, float cos_limit, float th, int far_points, float th_far, float nnratio, int want_in_view) {
+    if (L && !maps) { L->lp_B = 0; L->lp_rig = false; return fail(ORBX_E_ARG, "null table of per-frame maps"); }
+    return local_points_rig_batch(L, lf, R, rf, B, frames, nullptr, nullptr, nullptr, maps, occupied, cos_limit, th, far_points, th_far, nnratio, want_in_view);
 }
 
 int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* cur, const float* trl,
@@ -2008,7 +2118,7 @@ int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orb
     const size_t u_f = u.take(sizeof(FrustumParams) * B1);
     const PointRowsUpload U(u, B1, M1);
     const size_t u_occ = u.take(occupied ? B1 * S1 : 0), u_total = u.o;
-    const RigBlock K(u_total, B1, M1, C1, 0);
+    const RigBlock K(u_total, B1, B1 * M1, C1, 0);
     const size_t pool = batch_pool(L, B1 * M1 * 32 + 4096);                    // th = 7 .. 15 px windows, two cameras
     if (L->d_lp.ensure(K.pool + pool * 8 + 64) || L->h_lp_in.ensure(u_total + 16) || L->h_lp_out.ensure(al16(K.r.bytes) + 64))
         return fail(ORBX_E_DEVICE, "allocation failed (batched rig last-frame search, %d frames x %d points)", B, M);
@@ -2026,7 +2136,7 @@ int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orb
     if (L != R) { record_done_if_pending(R); rt::stream_wait_event(L->s0, R->ev_done); }
     RigRelPose T; memcpy(T.q, trl, sizeof T.q); memcpy(T.t, trl + 4, sizeof T.t);
     if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][0], L->s0);
-    rig_searches(L, lf, R, rf, B, M, K, dp, grid_from_view(cur[0].left), (const unsigned long long*)(dp + U.u_desc), 1, pool, [&]() {
+    rig_searches(L, lf, R, rf, B, M, K, dp, grid_from_view(cur[0].left), (const unsigned long long*)(dp + U.u_desc), 1, nullptr, pool, [&]() {
         dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
         ORBX_LAUNCH(k_lastframe_queries_rig, grid, blk, 0, L->s0, (const FrustumParams*)(dp + u_f), M, (const int*)(dp + U.u_n), (const float*)(dp + U.u_pos),
                     (const uint8_t*)(dp + U.u_val), (const int*)(dp + U.u_oct), T, (AreaQuery*)(dp + K.q1), (AreaQuery*)(dp + K.q2), (int*)(dp + K.res));

@@ -95,6 +95,10 @@ struct ProjectParams {
     int distance_test, angle_test;
     float bf;
 };
+// The local map of ONE frame of a batch whose frames bring their own maps (orbm_search_local_points_batch_maps / _rig_batch_maps): the arrays of the
+// resident set the frame names, its size, and where the frame's rows start in everything that is laid out by the prefix sums of M_b (call-time flags,
+// queries, track x 5, level, in_view, q_start / q_count)
+struct FrameMapRec { const float *pos, *normal, *min_d, *max_d; const unsigned long long* desc; int M, offset; };
 struct RigRelPose { float q[4], t[3]; };                          // mTrl of a two-camera Frame: unit quaternion coeffs (x, y, z, w), translation
 struct VocSlot { int node_id, child_start, child_cnt, word_id; };   // one vocabulary node; children occupy consecutive slots
 // Key frame database (orbv_db_*): where the BowVectors of queries sit - query q's sorted word ids / values at ids + start[q] (start == nullptr:

@@ -499,6 +499,53 @@ class ResidentPoints:
             pass
 
 
+class _FrameMap(C.Structure):
+    _fields_ = [("points", C.c_void_p), ("is_bad", C.c_void_p), ("has_obs", C.c_void_p)]
+
+
+class _FrameMaps:
+    """The OrbmFrameMap table of B frames with their own local maps: residents = B ResidentPoints (or None = empty map).  table(is_bad, has_obs)
+    fills it for one enqueue: None or B arrays (or None) over the points of each frame's set.  The table is a [B, 3] array of addresses laid
+    out as B _FrameMap records; each kind of flag is gathered into ONE array first, so that the table takes two base addresses plus offsets
+    (asking 2 B arrays for their addresses costs more than the search itself at B = 64)."""
+
+    def __init__(self, residents):
+        assert C.sizeof(_FrameMap) == 24
+        self.B = len(residents)
+        self.sizes = [r.M if r is not None else 0 for r in residents]
+        sz = np.array(self.sizes, np.int64)
+        self.offsets = np.cumsum(sz) - sz
+        self.points = np.array([(r._p.value or 0) if r is not None else 0 for r in residents], np.uint64)
+        self.width = max(self.sizes + [1])
+
+    def table(self, is_bad, has_obs):
+        B, sizes = self.B, self.sizes
+        table = np.zeros((B, 3), np.uint64); keep = []
+        table[:, 0] = self.points
+        for col, name, flags, default in ((1, "is_bad", is_bad, 0), (2, "has_obs", has_obs, 1)):
+            if flags is None:
+                continue
+            if len(flags) != B:
+                raise ValueError("%s: %d arrays for %d frames" % (name, len(flags), B))
+            parts = [np.full(sizes[b], default, np.uint8) if a is None else (a if type(a) is np.ndarray else np.asarray(a)) for b, a in enumerate(flags)]
+            if [a.size for a in parts] != sizes:
+                raise ValueError("%s: %s flags for maps of %s points" % (name, [a.size for a in parts], sizes))
+            buf = np.ascontiguousarray(np.concatenate(parts, axis=None), np.uint8)
+            keep.append(buf)
+            table[:, col] = buf.ctypes.data + self.offsets
+        return table, keep
+
+
+def _maps_of(resident, B):
+    """the per-frame form of a batch's `resident` argument (None: it is ONE ResidentPoints), and the width of its in_view rows"""
+    if not isinstance(resident, (list, tuple)):
+        return None, max(resident.M, 1)
+    if len(resident) != B:
+        raise ValueError("%d local maps for %d frames" % (len(resident), B))
+    fm = _FrameMaps(list(resident))
+    return fm, fm.width
+
+
 def frustum_view(Rcw, tcw, cam, bounds, mbf, scale_factors, into=None):
     """OrbmFrustumView of one frame.  The pose is a sophus.SE3f (pass it as Rcw, tcw = None) or (Rcw, tcw), which enters through Sophus' SE3(R, t)
     constructor as in Frame::SetPose(Sophus::SE3f(R, t)); the view then holds what Frame::UpdatePoseMatrices derives (src/Frame.cc:594-598):
@@ -548,7 +595,10 @@ def StereoFetch(ext, B):
 class LocalPointsBatch:
     """Tracking::SearchLocalPoints for a batch of frames that stay on the device (orbm_search_local_points_batch): the frames are images
     [first, first + B) of ext's last extraction, the local map is a ResidentPoints, poses = B x (Rcw, tcw).  enqueue() is asynchronous, fetch()
-    returns (assigned [B, cap], nmatches [B], in_view [B, M] or None)."""
+    returns (assigned [B, cap], nmatches [B], in_view [B, M] or None).
+    Independent streams: `resident` = a list of B ResidentPoints (or None = empty map), frame b is searched against its own
+    (orbm_search_local_points_batch_maps); is_bad / has_obs of enqueue() are then lists of B arrays (or None), assigned[b] indexes frame b's set and
+    in_view is [B, M_max], zero beyond M_b."""
 
     def __init__(self, ext, resident, B, cam, bounds, mbf, scale_factors):
         self.ext, self.res, self.B = ext, resident, B
@@ -557,7 +607,8 @@ class LocalPointsBatch:
         self.views = (_FrustumView * B)()
         self.cap = ext.max_keypoints()
         self.assigned = np.full((B, self.cap), -1, np.int32); self.nm = np.zeros(B, np.int32)
-        self.in_view = np.zeros((B, max(resident.M, 1)), np.uint8)
+        self.maps, width = _maps_of(resident, B)
+        self.in_view = np.zeros((B, width), np.uint8)
 
     def set_poses(self, poses):
         for b, pose in enumerate(poses):
@@ -569,9 +620,15 @@ class LocalPointsBatch:
         L = self.ext._lib
         u8 = lambda a: None if a is None else np.ascontiguousarray(a, np.uint8)
         self._again = lambda: self.enqueue(first, is_bad, has_obs, occupied, use_u_right, viewing_cos_limit, th, far_points, th_far, nnratio, want_in_view)
-        self._keep = (u8(is_bad), u8(has_obs), u8(occupied))
         ptr = lambda a: None if a is None else a.ctypes.data
         self._want = bool(want_in_view)
+        if self.maps is not None:
+            table, flags = self.maps.table(is_bad, has_obs)
+            self._keep = (table, flags, u8(occupied))
+            L.check(L.L.orbm_search_local_points_batch_maps(self.ext._h, int(first), self.B, self.views, table.ctypes.data, ptr(self._keep[2]), int(bool(use_u_right)),
+                                                            float(viewing_cos_limit), float(th), int(far_points), float(th_far), float(nnratio), int(self._want)))
+            return
+        self._keep = (u8(is_bad), u8(has_obs), u8(occupied))
         L.check(L.L.orbm_search_local_points_batch(self.ext._h, int(first), self.B, self.views, self.res._p, ptr(self._keep[0]), ptr(self._keep[1]), ptr(self._keep[2]),
                                                    int(bool(use_u_right)), float(viewing_cos_limit), float(th), int(far_points), float(th_far), float(nnratio), int(self._want)))
 
@@ -590,7 +647,9 @@ class LocalPointsRigBatch:
     left_first + b of `left`'s last extraction and right image right_first + b of `right`'s (right_first defaults to B when both are one handle,
     the layout [L0 .. L(B-1), R0 .. R(B-1)], else to 0), linked by the last ComputeStereoFishEyeMatches over exactly these frames; the local map is a
     ResidentPoints.  set_poses() takes B pose dicts as SearchLocalPointsRig does.  enqueue() is asynchronous, fetch() returns (assigned [B, 2 cap]
-    in the slot layout of F.mvpMapPoints, nmatches [B], in_view [B, M] or None, in_view_r [B, M] or None)."""
+    in the slot layout of F.mvpMapPoints, nmatches [B], in_view [B, M] or None, in_view_r [B, M] or None).
+    Independent streams: `resident` = a list of B ResidentPoints (or None), is_bad / has_obs lists of B arrays (or None), as LocalPointsBatch
+    (orbm_search_local_points_rig_batch_maps); in_view / in_view_r are then [B, M_max]."""
 
     def __init__(self, left, right, resident, B, cam1, cam2, bounds, scale_factors, left_first=0, right_first=None):
         self.ext, self.right, self.res, self.B = left, right, resident, B
@@ -600,7 +659,8 @@ class LocalPointsRigBatch:
         self.views = (_FrustumRigView * B)()
         self.cap = 2 * left.max_keypoints()
         self.assigned = np.full((B, self.cap), -1, np.int32); self.nm = np.zeros(B, np.int32)
-        self.in_view = np.zeros((B, max(resident.M, 1)), np.uint8); self.in_view_r = np.zeros((B, max(resident.M, 1)), np.uint8)
+        self.maps, width = _maps_of(resident, B)
+        self.in_view = np.zeros((B, width), np.uint8); self.in_view_r = np.zeros((B, width), np.uint8)
 
     def set_poses(self, poses):
         for b, pose in enumerate(poses):
@@ -610,9 +670,15 @@ class LocalPointsRigBatch:
         L = self.ext._lib
         u8 = lambda a: None if a is None else np.ascontiguousarray(a, np.uint8)
         self._again = lambda: self.enqueue(is_bad, has_obs, occupied, viewing_cos_limit, th, far_points, th_far, nnratio, want_in_view)
-        self._keep = (u8(is_bad), u8(has_obs), u8(occupied))
         ptr = lambda a: None if a is None else a.ctypes.data
         self._want = bool(want_in_view)
+        if self.maps is not None:
+            table, flags = self.maps.table(is_bad, has_obs)
+            self._keep = (table, flags, u8(occupied))
+            L.check(L.L.orbm_search_local_points_rig_batch_maps(self.ext._h, self.lf, self.right._h, self.rf, self.B, self.views, table.ctypes.data, ptr(self._keep[2]),
+                                                                float(viewing_cos_limit), float(th), int(far_points), float(th_far), float(nnratio), int(self._want)))
+            return
+        self._keep = (u8(is_bad), u8(has_obs), u8(occupied))
         L.check(L.L.orbm_search_local_points_rig_batch(self.ext._h, self.lf, self.right._h, self.rf, self.B, self.views, self.res._p, ptr(self._keep[0]),
                                                        ptr(self._keep[1]), ptr(self._keep[2]), float(viewing_cos_limit), float(th), int(far_points), float(th_far),
                                                        float(nnratio), int(self._want)))

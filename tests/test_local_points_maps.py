@@ -1,0 +1,401 @@
+"""Batched Tracking::SearchLocalPoints for frames that each bring their OWN local map - independent streams side by side
+(orbm_search_local_points_batch_maps: k_frustum_maps / k_area_search_threads_maps / k_local_accept_maps read frame b's resident set through a
+per-frame table; scratch and call-time flags are laid out by the prefix sums of M_b).
+
+Checker: the reference's own Frame.cc + ORBmatcher.cc, called once per frame with THAT frame's map (oracle/_ref/libref_frame.so); where the
+reference has no input (keypoints occupied beforehand, monocular frames of a stereo Frame) the single-frame product call that
+tests/test_local_points.py pins to the reference.  Bar for every frame: assignments, match counts and mbTrackInView identical; assigned is -1
+beyond N.  So that equality cannot pass on empty results, the reference alone has to find at least M_b / 8 matches in every non-empty map
+(th = 1, no occupancy); a frame searched against another frame's map finds a few per cent of that."""
+import ctypes as C
+import functools
+import os
+import subprocess
+import types
+
+import numpy as np
+import pytest
+
+import oracle_lib as ol
+from orb_slam3_detailed_comments_amd import ORBextractor, synth, views
+from orb_slam3_detailed_comments_amd import matcher as M
+from test_local_points import _rot, _scene, FX, FY, CX, CY, BF
+from test_local_points_batch import BASE, PARAM_SETS
+
+pytestmark = pytest.mark.skipif(ol.reference_frame_lib() is None, reason="oracle/_ref/libref_frame.so is not built")
+CAM = (FX, FY, CX, CY)
+E_ARG, E_CAPACITY = -2, -4
+EMU_SHAPE = (376, 240, 500, (900, 0, 37, 300))          # an empty map inside the batch, one smaller than a wave, sizes that are multiples of neither 64 nor 256
+GPU_SHAPE = (640, 480, 1000, (5000, 0, 37, 1300, 64, 65, 256, 2049))     # the wave edge, the block edge, one past each, the workload's own 5000
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _duplicates(rng, m):
+    """rows that get a copy of another row 1, 2, 5, 63, 64 or 65 rows in front of them (as far as the map is long): the copies compete for one keypoint"""
+    pairs = []
+    for i in rng.choice(m - 1, max(m // 4, 1), replace=False):
+        gaps = [g for g in (1, 2, 5, 63, 64, 65) if i + g < m]
+        pairs.append((int(i), int(i + rng.choice(gaps))))
+    return pairs
+
+
+@functools.lru_cache(maxsize=None)
+def _streams(w, h, nf, sizes):
+    """B independent streams: frame b = stereo pair of image seed 60 + b under its own pose, with a local map of sizes[b] points built from ITS
+    keypoints (rng seed 100 + b), and what the reference finds: `expect[k][b]` = (mbTrackInView, assigned, nmatches) of frame b against its own map
+    for the k-th parameter set without occupancy, `cross` = (frame, other frame, matches of the frame against the OTHER frame's map).
+    Independent of the library under test: built once, shared, never modified.  The reference runs HERE, while its frames are the last ones
+    constructed (Frame keeps image bounds and grid constants in static members: a frame of another size built later would change them), and
+    only plain arrays are kept."""
+    B = len(sizes)
+    pairs = [synth.stereo_pair(w, h, seed=60 + b, nrect=int(3000 * w * h / (752 * 480))) for b in range(B)]
+    refs = [ol.ReferenceFrame(l, r, nf, fx=FX, fy=FY, cx=CX, cy=CY, bf=BF) for l, r in pairs]
+    poses, maps = [], []
+    for b in range(B):
+        rng = np.random.default_rng(100 + b)
+        R, t = _rot(*rng.normal(0, 0.02, 3)), rng.normal(0, 0.2, 3).astype(np.float32)
+        poses.append((R, t))
+        m = sizes[b]
+        if m == 0:
+            maps.append(None)
+            continue
+        pos, normal, mind, maxd, bad, obs, desc = _scene(refs[b], rng, R, t, m)
+        for i, j in _duplicates(rng, m):
+            pos[j] = pos[i]; normal[j] = normal[i]; mind[j] = mind[i]; maxd[j] = maxd[i]; desc[j] = desc[i]
+            if rng.uniform() < 0.5:
+                desc[j, int(rng.integers(0, 32))] ^= np.uint8(1 << int(rng.integers(0, 8)))
+        maps.append(dict(pos=pos, normal=normal, mind=mind, maxd=maxd, bad=bad, obs=obs, desc=desc))
+
+    def search(b, m, th, far, cosl, thfar, ratio):
+        tr, asg, n = refs[b].search_local_points(poses[b][0], poses[b][1], m["pos"], m["normal"], m["mind"], m["maxd"], m["bad"], m["obs"], m["desc"], cosl, True, th, far, thfar, ratio)
+        return tr["in_view"].copy(), asg.copy(), n
+    expect = {k: [None if m is None else search(b, m, th, far, cosl, thfar, ratio) for b, m in enumerate(maps)]
+              for k, (th, far, use_occ, cosl, thfar, ratio) in enumerate(PARAM_SETS) if not use_occ}
+    full = [b for b, m in enumerate(maps) if m is not None]
+    cross = [(b, o, search(b, maps[o], 1.0, False, 0.5, 50.0, 0.8)[2]) for b, o in zip(full, full[1:] + full[:1]) if o != b]
+    frames = [types.SimpleNamespace(N=F.N, keys=F.keys.copy(), u_right=F.u_right.copy()) for F in refs]
+    return pairs, frames, poses, maps, expect, cross
+
+
+class World:
+    """the streams of _streams() extracted and stereo-matched on the library under test, their maps resident"""
+
+    def __init__(self, lib, shape):
+        w, h, nf, sizes = shape
+        self.lib, self.w, self.h, self.sizes, self.B = lib, w, h, sizes, len(sizes)
+        self.pairs, self.refs, self.poses, self.maps, self.expect, _ = _streams(w, h, nf, sizes)
+        B = self.B
+        self.ex = ORBextractor(nf, 1.2, 8, 20, 7, lib=lib)
+        self.res = self.ex.extract_batch(np.stack([l for l, _ in self.pairs] + [r for _, r in self.pairs]))
+        lib.check(lib.L.orbm_stereo_match(self.ex._h, 0, self.ex._h, B, B, BF, BASE))
+        self.u, _, _ = M.StereoFetch(self.ex, B)
+        for b in range(B):
+            assert self.res[b][1].tobytes() == self.refs[b].keys.tobytes() and self.u[b, :self.refs[b].N].tobytes() == self.refs[b].u_right.tobytes()
+        self.sfs = self.ex.GetScaleFactors()
+        self.cap = self.ex.max_keypoints()
+        self.bounds = (0.0, float(w), 0.0, float(h))
+        self.rps = [None if m is None else M.ResidentPoints(self.ex, m["pos"], m["normal"], m["mind"], m["maxd"], m["desc"]) for m in self.maps]
+        rng = np.random.default_rng(4242)
+        self.occupied = np.zeros((B, self.cap), np.uint8)
+        for b in range(B):
+            self.occupied[b, rng.choice(self.refs[b].N, self.refs[b].N // 6, replace=False)] = 1
+
+    def batch(self, rps=None):
+        lp = M.LocalPointsBatch(self.ex, list(self.rps if rps is None else rps), self.B, CAM, self.bounds, BF, self.sfs)
+        lp.set_poses(self.poses)
+        return lp
+
+    def flags(self, name):
+        return [None if m is None else m[name] for m in self.maps]
+
+    def single(self, b, m, bad, obs, pose=None, occ=None, stereo=True, th=1.0, far=False, thfar=50.0, ratio=0.8, cosl=0.5):
+        """the single-frame product call (pinned to the reference by tests/test_local_points.py) for frame b against map m"""
+        n = self.refs[b].N
+        fv = views.frame_view(self.res[b][1], self.res[b][2], self.sfs, self.w, self.h, u_right=self.u[b, :n] if stereo else None, mbf=BF if stereo else 0.0,
+                              occupied=None if occ is None else occ[b, :n])
+        R, t = pose or self.poses[b]
+        tr, asg, nm = M.SearchLocalPoints(self.ex, fv, R, t, CAM, self.bounds, BF, self.sfs, m["pos"], m["normal"], m["mind"], m["maxd"], bad, obs, m["desc"], cosl, th, far, thfar, ratio)
+        return tr["in_view"].astype(bool), asg, nm
+
+    def close(self):
+        for r in self.rps:
+            if r is not None:
+                r.close()
+        self.ex.close()
+
+
+def _check_frame(W, b, asg, nm, inv, ref_as, ref_n, ref_inv, what):
+    N, m = W.refs[b].N, W.sizes[b]
+    print("frame %d (%s): M %d, %d matches (expected %d)" % (b, what, m, nm[b], ref_n))
+    assert nm[b] == ref_n and np.array_equal(asg[b, :N], ref_as), "frame %d (%s): %d vs %d matches" % (b, what, nm[b], ref_n)
+    assert (asg[b, N:] == -1).all()
+    if inv is not None:
+        assert np.array_equal(inv[b, :m].astype(bool), ref_inv), "mbTrackInView, frame %d (%s)" % (b, what)
+        assert not inv[b, m:].any(), "in_view of frame %d is not zero beyond its %d points" % (b, m)
+
+
+def _ragged(lib, shape):
+    W = World(lib, shape)
+    try:
+        lp = W.batch()
+        assert lp.in_view.shape == (W.B, max(W.sizes))
+        for k, (th, far, use_occ, cosl, thfar, ratio) in enumerate(PARAM_SETS):
+            occ = W.occupied if use_occ else None
+            lp.enqueue(0, is_bad=W.flags("bad"), has_obs=W.flags("obs"), occupied=occ, use_u_right=True, viewing_cos_limit=cosl, th=th, far_points=far, th_far=thfar, nnratio=ratio,
+                       want_in_view=True)
+            asg, nm, inv = lp.fetch()
+            for b, m in enumerate(W.maps):
+                if m is None:
+                    assert nm[b] == 0 and (asg[b] == -1).all() and not inv[b].any(), "frame %d has an empty map" % b
+                    continue
+                if occ is None:           # the reference itself
+                    ref_inv, ref_as, ref_n = W.expect[k][b]
+                    if th == 1.0:         # the equality is about something: the reference alone finds an eighth of the map
+                        assert ref_n >= W.sizes[b] // 8 and ref_n >= W.sizes[b] / 8.0, "frame %d: the reference finds %d of %d points" % (b, ref_n, W.sizes[b])
+                else:
+                    ref_inv, ref_as, ref_n = W.single(b, m, m["bad"], m["obs"], occ=occ, th=th, far=far, thfar=thfar, ratio=ratio, cosl=cosl)
+                _check_frame(W, b, asg, nm, inv, ref_as, ref_n, ref_inv, "th %g" % th)
+        # monocular frames (no uRight): the right-coordinate gate is off
+        lp.enqueue(0, is_bad=W.flags("bad"), has_obs=W.flags("obs"), use_u_right=False, th=3.0)
+        asg, nm, none = lp.fetch()
+        assert none is None
+        for b, m in enumerate(W.maps):
+            if m is None:
+                assert nm[b] == 0 and (asg[b] == -1).all()
+                continue
+            _, ref_as, ref_n = W.single(b, m, m["bad"], m["obs"], stereo=False, th=3.0)
+            _check_frame(W, b, asg, nm, None, ref_as, ref_n, None, "monocular")
+    finally:
+        W.close()
+
+
+def test_ragged_maps_emulated(emu_lib):
+    _ragged(emu_lib, EMU_SHAPE)
+
+
+@pytest.mark.gpu
+def test_ragged_maps_gpu(hip_lib):
+    _ragged(hip_lib, GPU_SHAPE)
+
+
+@pytest.mark.gpu
+def test_ragged_maps_emulator_shape_gpu(hip_lib):
+    _ragged(hip_lib, EMU_SHAPE)
+
+
+def test_wrong_map_would_be_noticed():
+    """the premise of the equality checks: a frame searched against ANOTHER frame's map finds next to nothing, so reading the wrong map cannot
+    reproduce the expected assignments"""
+    for shape in (EMU_SHAPE,):
+        maps, cross = _streams(*shape)[3], _streams(*shape)[5]
+        assert len(cross) >= 3
+        for b, o, n in cross:
+            assert n <= 0.03 * len(maps[o]["pos"]) + 1, "frame %d finds %d of frame %d's %d points" % (b, n, o, len(maps[o]["pos"]))
+
+
+def _shared_set(lib):
+    """frames 0 and 1 name ONE resident set with different flags and different poses; frame 2 names another set"""
+    W = World(lib, (EMU_SHAPE[0], EMU_SHAPE[1], EMU_SHAPE[2], (900, 0, 37)))
+    try:
+        m0, m2 = W.maps[0], W.maps[2]
+        rng = np.random.default_rng(9)
+        bad1 = rng.uniform(size=900) < 0.3; obs1 = rng.uniform(size=900) < 0.5
+        # frame 1 = another look at stream 0's scene: the images of frame 0 again would need another extraction, so frame 1 (its own image) sees
+        # stream 0's map from stream 0's pose, slightly moved - few matches, but its flags and pose are its own
+        pose1 = (_rot(0.001, -0.002, 0.0005) @ W.poses[0][0], (W.poses[0][1] + np.array([0.01, 0.0, -0.01], np.float32)).astype(np.float32))
+        lp = M.LocalPointsBatch(W.ex, [W.rps[0], W.rps[0], W.rps[2]], 3, CAM, W.bounds, BF, W.sfs)
+        lp.set_poses([W.poses[0], pose1, W.poses[2]])
+        lp.enqueue(0, is_bad=[m0["bad"], bad1, None], has_obs=[m0["obs"], obs1, m2["obs"]], th=3.0, want_in_view=True)
+        asg, nm, inv = lp.fetch()
+        expect = [W.single(0, m0, m0["bad"], m0["obs"], th=3.0), W.single(1, m0, bad1, obs1, pose=pose1, th=3.0), W.single(2, m2, None, m2["obs"], th=3.0)]
+        for b, (ref_inv, ref_as, ref_n) in enumerate(expect):
+            N, m = W.refs[b].N, (900, 900, 37)[b]
+            assert nm[b] == ref_n and np.array_equal(asg[b, :N], ref_as) and (asg[b, N:] == -1).all(), "frame %d: %d vs %d" % (b, nm[b], ref_n)
+            assert np.array_equal(inv[b, :m].astype(bool), ref_inv) and not inv[b, m:].any()
+        # the same frame and pose under the two flag sets: the flags are per frame, not per set
+        lp.set_poses([W.poses[0], W.poses[0], W.poses[2]])
+        lp.enqueue(0, is_bad=[m0["bad"], bad1, None], has_obs=[m0["obs"], obs1, m2["obs"]], th=3.0)
+        asg, nm, _ = lp.fetch()
+        _, as_a, n_a = W.single(0, m0, m0["bad"], m0["obs"], th=3.0)
+        assert nm[0] == n_a and np.array_equal(asg[0, :W.refs[0].N], as_a) and n_a > 900 // 8
+    finally:
+        W.close()
+
+
+def test_shared_set_different_flags_emulated(emu_lib):
+    _shared_set(emu_lib)
+
+
+@pytest.mark.gpu
+def test_shared_set_different_flags_gpu(hip_lib):
+    _shared_set(hip_lib)
+
+
+def _in_view_layout(lib):
+    """the C fetch writes rows M_max apart and zeroes the padding itself (the buffer is handed over full of 0xFF)"""
+    W = World(lib, EMU_SHAPE)
+    try:
+        L = lib.L
+        assert [L.orbm_points_count(r._p) if r is not None else L.orbm_points_count(None) for r in W.rps] == list(W.sizes)
+        lp = W.batch()
+        lp.enqueue(0, is_bad=W.flags("bad"), has_obs=W.flags("obs"), want_in_view=True)
+        m_max = max(W.sizes)
+        buf = np.full(W.B * m_max + 64, 0xFF, np.uint8)
+        asg = np.zeros((W.B, W.cap), np.int32); nm = np.zeros(W.B, np.int32)
+        lib.check(L.orbm_search_local_points_fetch(W.ex._h, asg.ctypes.data, W.cap, nm.ctypes.data, buf.ctypes.data))
+        assert (buf[W.B * m_max:] == 0xFF).all()
+        rows = buf[:W.B * m_max].reshape(W.B, m_max)
+        for b, m in enumerate(W.maps):
+            n = W.sizes[b]
+            assert not rows[b, n:].any()
+            if m is not None:
+                ref_inv, _, _ = W.single(b, m, m["bad"], m["obs"])
+                assert np.array_equal(rows[b, :n].astype(bool), ref_inv) and ref_inv.any()
+    finally:
+        W.close()
+
+
+def test_in_view_layout_emulated(emu_lib):
+    _in_view_layout(emu_lib)
+
+
+@pytest.mark.gpu
+def test_in_view_layout_gpu(hip_lib):
+    _in_view_layout(hip_lib)
+
+
+def test_pool_overflow_with_ragged_maps(emu_lib):
+    """windows so wide that the candidate pool of a fresh handle (sized from the sum of the M_b) overflows: one ORBX_E_CAPACITY from the fetch, then
+    the re-enqueued batch equals the single-frame calls"""
+    W = World(emu_lib, EMU_SHAPE)
+    try:
+        lp = W.batch()
+        lp.enqueue(0, use_u_right=False, th=30.0)
+        assert emu_lib.L.orbm_search_local_points_fetch(W.ex._h, lp.assigned.ctypes.data, lp.cap, lp.nm.ctypes.data, None) == E_CAPACITY
+        lp.enqueue(0, use_u_right=False, th=30.0)
+        assert emu_lib.L.orbm_search_local_points_fetch(W.ex._h, lp.assigned.ctypes.data, lp.cap, lp.nm.ctypes.data, None) == 0
+        for b, m in enumerate(W.maps):
+            if m is None:
+                assert lp.nm[b] == 0 and (lp.assigned[b] == -1).all()
+                continue
+            _, ref_as, ref_n = W.single(b, m, None, None, stereo=False, th=30.0)
+            assert lp.nm[b] == ref_n and np.array_equal(lp.assigned[b, :W.refs[b].N], ref_as), "frame %d" % b
+        assert lp.nm[0] > 50
+    finally:
+        W.close()
+
+
+def _live(lib):
+    a = (C.c_longlong * 4)()
+    lib.check(lib.L.orbx_debug_live_resources(a))
+    return list(a)
+
+
+def _refusals(lib, two_devices):
+    L = lib.L
+    live0 = _live(lib)
+    w, h, nf, B = 320, 240, 300, 2
+    ex = ORBextractor(nf, 1.2, 8, 20, 7, lib=lib)
+    ex.extract_batch(np.stack([synth.corner_field(w, h, seed=40 + b, nrect=700) for b in range(B)]))
+    cap = ex.max_keypoints(); sfs = ex.GetScaleFactors(); bounds = (0.0, float(w), 0.0, float(h))
+    rng = np.random.default_rng(5)
+    pos = rng.uniform(-2, 2, (50, 3)).astype(np.float32); pos[:, 2] += 4
+    dist = np.linalg.norm(pos, axis=1).astype(np.float32)
+    mk = lambda e: M.ResidentPoints(e, pos, (pos / dist[:, None]).astype(np.float32), dist / 3, dist * 2, rng.integers(0, 256, (50, 32), dtype=np.uint8))
+    rp = mk(ex)
+    fv = (M._FrustumView * B)()
+    for b in range(B):
+        M.frustum_view(np.eye(3, dtype=np.float32), np.zeros(3, np.float32), CAM, bounds, 0.0, sfs, into=fv[b])
+    table = (M._FrameMap * B)()
+    table[0].points = rp._p; table[1].points = rp._p
+    a = np.zeros((B, 2 * cap), np.int32); nm = np.zeros(B, np.int32)
+    fetch = lambda: L.orbm_search_local_points_fetch(ex._h, a.ctypes.data, 2 * cap, nm.ctypes.data, None)
+    enqueue = lambda t, first=0, n=B: L.orbm_search_local_points_batch_maps(ex._h, first, n, fv, t, None, 0, 0.5, 1.0, 0, 0.0, 0.8, 0)
+    assert fetch() == E_ARG                                             # nothing yet
+    assert enqueue(table) == 0 and fetch() == 0                         # accepted
+    assert enqueue(None) == E_ARG and fetch() == E_ARG                  # a NULL table ends the pending batch and leaves nothing
+    assert enqueue(table) == 0
+    assert enqueue(table, first=1) == E_ARG and fetch() == E_ARG        # frames beyond the extraction
+    assert L.orbm_search_local_points_batch_maps(None, 0, B, fv, table, None, 0, 0.5, 1.0, 0, 0.0, 0.8, 0) == E_ARG
+    # the rig fetch refuses a one-camera maps batch
+    assert enqueue(table) == 0
+    assert L.orbm_search_rig_batch_fetch(ex._h, a.ctypes.data, 2 * cap, nm.ctypes.data, None, None) == E_ARG
+    assert fetch() == 0
+    # in_view that was not requested
+    iv = np.zeros((B, 50), np.uint8)
+    assert enqueue(table) == 0 and L.orbm_search_local_points_fetch(ex._h, a.ctypes.data, 2 * cap, nm.ctypes.data, iv.ctypes.data) == E_ARG
+    # every map empty
+    empty = (M._FrameMap * B)()
+    assert enqueue(empty) == 0 and fetch() == 0 and (nm == 0).all() and (a[:, :cap] == -1).all()
+    other = rp2 = None
+    if two_devices:
+        other = ORBextractor(nf, 1.2, 8, 20, 7, lib=lib, device_id=1)
+        rp2 = mk(other)
+        table[1].points = rp2._p
+        assert enqueue(table) == E_ARG and b"frame 1" in L.orbx_last_error()       # the message names the frame
+        assert fetch() == E_ARG
+        table[1].points = rp._p
+    assert enqueue(table) == 0 and fetch() == 0
+    for o in (rp2, other, rp, ex):
+        if o is not None:
+            o.close()
+    assert _live(lib) == live0
+
+
+def test_refusals_emulated(emu_lib, monkeypatch):
+    monkeypatch.setenv("ORBX_EMU_DEVICES", "2")
+    assert emu_lib.L.orbx_device_count() == 2
+    _refusals(emu_lib, True)
+
+
+@pytest.mark.gpu
+def test_refusals_gpu(hip_lib):
+    _refusals(hip_lib, False)
+
+
+def _identical_entries(lib, shape, B):
+    """B table entries naming one set with one pair of flag arrays = the one-map call on the same batch: both forms give the same outputs (and
+    the one-map entry point gives what the reference gives)"""
+    W = World(lib, shape)
+    try:
+        m, rp = W.maps[0], W.rps[0]
+        one = M.LocalPointsBatch(W.ex, rp, B, CAM, W.bounds, BF, W.sfs); one.set_poses(W.poses[:B])
+        many = M.LocalPointsBatch(W.ex, [rp] * B, B, CAM, W.bounds, BF, W.sfs); many.set_poses(W.poses[:B])
+        th, far, _, cosl, thfar, ratio = PARAM_SETS[0]
+        for occ in (None, W.occupied[:B]):
+            one.enqueue(0, is_bad=m["bad"], has_obs=m["obs"], occupied=occ, viewing_cos_limit=cosl, th=th, far_points=far, th_far=thfar, nnratio=ratio, want_in_view=True)
+            a1, n1, v1 = [x.copy() for x in one.fetch()]
+            many.enqueue(0, is_bad=[m["bad"]] * B, has_obs=[m["obs"]] * B, occupied=occ, viewing_cos_limit=cosl, th=th, far_points=far, th_far=thfar, nnratio=ratio, want_in_view=True)
+            a2, n2, v2 = many.fetch()
+            assert np.array_equal(a1, a2) and np.array_equal(n1, n2) and np.array_equal(v1, v2)
+            if occ is None:               # frame 0 against its own map: the reference's result, and not an empty one
+                ref_inv, ref_as, ref_n = W.expect[0][0]
+                assert n1[0] == ref_n and np.array_equal(a1[0, :W.refs[0].N], ref_as) and np.array_equal(v1[0].astype(bool), ref_inv) and ref_n >= W.sizes[0] / 8.0
+    finally:
+        W.close()
+
+
+def test_identical_entries_equal_the_one_map_call_emulated(emu_lib):
+    _identical_entries(emu_lib, EMU_SHAPE, 4)
+
+
+@pytest.mark.gpu
+def test_identical_entries_equal_the_one_map_call_gpu(hip_lib):
+    _identical_entries(hip_lib, GPU_SHAPE, 8)
+
+
+def test_frame_map_mirror_has_the_header_layout(tmp_path):
+    """OrbmFrameMap of include/orbx.h against its ctypes mirror: same fields, offsets and sizes"""
+    fields = [f[0] for f in M._FrameMap._fields_]
+    assert fields == ["points", "is_bad", "has_obs"]
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "orbx.h"', 'int main(void) {', 'printf("%zu\\n", sizeof(OrbmFrameMap));']
+    lines += ['printf("%%zu %%zu\\n", offsetof(OrbmFrameMap, %s), sizeof(((OrbmFrameMap*)0)->%s));' % (f, f) for f in fields]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines + ["return 0; }"]))
+    exe = str(tmp_path / "layout")
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()
+    assert int(out[0]) == C.sizeof(M._FrameMap)
+    for k, f in enumerate(fields):
+        d = getattr(M._FrameMap, f)
+        assert (d.offset, d.size) == (int(out[1 + 2 * k]), int(out[2 + 2 * k])), f

@@ -1,0 +1,369 @@
+"""Batched Tracking::SearchLocalPoints for two-camera (fisheye rig) frames that each bring their OWN local map
+(orbm_search_local_points_rig_batch_maps: k_frustum_rig_maps / k_area_search_threads_maps per camera / k_rig_local_accept_maps read frame b's
+resident set through a per-frame table; scratch and call-time flags laid out by the prefix sums of M_b).
+
+Checker: the reference's own Frame.cc + ORBmatcher.cc (ReferenceRigFrame.search_local_points, oracle/_ref/libref_frame.so), called once per
+frame with THAT frame's map; with keypoints occupied beforehand - an input the reference does not have - the single-frame product call
+orbm_search_local_points_fisheye, which tests/test_local_points_rig.py pins to the reference.  Bar for every frame: assignments over both
+cameras, match counts, mbTrackInView and mbTrackInViewR identical; assigned is -1 beyond Nleft + Nright.  The reference alone has to find at
+least M_b / 4 matches in every non-empty map (th = 1, no occupancy), so equality cannot pass on empty results."""
+import ctypes as C
+import functools
+import types
+
+import numpy as np
+import pytest
+
+import oracle_lib as ol
+from orb_slam3_detailed_comments_amd import ORBextractor, sophus, views
+from orb_slam3_detailed_comments_amd import matcher as M
+from test_kb8 import CAM1, CAM2, MRLR, RLR, TLR, _fisheye_pair
+from test_local_points import _rot
+from test_local_points_rig import _scene
+from test_local_points_maps import _duplicates, _live, E_ARG, E_CAPACITY
+
+pytestmark = pytest.mark.skipif(ol.reference_frame_lib() is None, reason="oracle/_ref/libref_frame.so is not built")
+EMU_SHAPE = (376, 376, 500, (0, 375), (700, 0, 45, 260))
+GPU_SHAPE = (512, 512, 1500, (0, 511), (5000, 0, 37, 1300, 64, 65, 256, 2049))
+PARAMS = ((1.0, False), (3.0, True))              # (th, bFarPoints) with thFarPoints = 9, as tests/test_rig_tracking_batch.py
+
+
+def _rig_pose(R, t):
+    """what a rig Frame holds after SetPose(SE3f(R, t)) (src/Frame.cc:594-598, :1498-1501), for poses the reference frames of _streams() were not asked about"""
+    T = sophus.SE3f(R, t); Tlr = sophus.SE3f(RLR, TLR); Trl = Tlr.inverse()
+    Rm = T.rotationMatrix().astype(np.float32)
+    return dict(Rcw=Rm, tcw=np.asarray(T.translation(), np.float32), Ow=np.asarray(T.inverse().translation(), np.float32), Rwc=Rm.T.copy(),
+                Rrl=Trl.rotationMatrix().astype(np.float32), trl=np.asarray(Trl.translation(), np.float32), tlr=np.asarray(Tlr.translation(), np.float32))
+
+
+@functools.lru_cache(maxsize=None)
+def _streams(w, h, nf, lap, sizes):
+    """B independent rig streams: frame b = fisheye pair of image seed 60 + b under its own pose, with a local map of sizes[b] points on the rays
+    of ITS keypoints (rng seed 200 + b), and what the reference finds: expect[k][b] = (mbTrackInView, mbTrackInViewR, assigned, nmatches) of frame b
+    against its own map under PARAMS[k], cross = (frame, other frame, matches against the OTHER frame's map).  Independent of the library under
+    test: built once, shared, never modified.  The reference runs HERE, while its frames are the last ones constructed (Frame keeps image bounds
+    and grid constants in static members: a frame of another size built later would change them); only plain arrays are kept."""
+    B = len(sizes)
+    pairs = [_fisheye_pair(60 + b, w, h) for b in range(B)]
+    refs = [ol.ReferenceRigFrame(L, R, lap, lap, nf, (CAM1, CAM2, RLR, TLR)) for L, R in pairs]
+    poses, rig_poses, maps = [], [], []
+    for b in range(B):
+        rng = np.random.default_rng(200 + b)
+        R, t = _rot(*rng.normal(0, 0.015, 3)), rng.normal(0, 0.1, 3).astype(np.float32)
+        poses.append((R, t))
+        m = sizes[b]
+        one = _scene(refs[b], np.random.default_rng(1), R, t, 1)
+        rig_poses.append(refs[b].search_local_points(R, t, *one, 0.5, False)[4])          # the pose as the Frame holds it after SetPose
+        if m == 0:
+            maps.append(None)
+            continue
+        pos, normal, mind, maxd, bad, obs, desc = _scene(refs[b], rng, R, t, m)
+        for i, j in _duplicates(rng, m):
+            pos[j] = pos[i]; normal[j] = normal[i]; mind[j] = mind[i]; maxd[j] = maxd[i]; desc[j] = desc[i]
+            if rng.uniform() < 0.3:
+                desc[j, int(rng.integers(0, 32))] ^= np.uint8(1 << int(rng.integers(0, 8)))
+        maps.append(dict(pos=pos, normal=normal, mind=mind, maxd=maxd, bad=bad, obs=obs, desc=desc))
+
+    def search(b, m, th, far):
+        rl, rr, asg, n, _ = refs[b].search_local_points(poses[b][0], poses[b][1], m["pos"], m["normal"], m["mind"], m["maxd"], m["bad"], m["obs"], m["desc"], 0.5, True, th, far, 9.0, 0.8)
+        return rl["in_view"].copy(), rr["in_view_r"].copy(), asg.copy(), n
+    expect = [[None if m is None else search(b, m, th, far) for b, m in enumerate(maps)] for th, far in PARAMS]
+    full = [b for b, m in enumerate(maps) if m is not None]
+    cross = [(b, o, search(b, maps[o], 1.0, False)[3]) for b, o in zip(full, full[1:] + full[:1]) if o != b]
+    frames = [types.SimpleNamespace(nl=F.nl, nr=F.nr, keys=F.keys.copy(), keys_right=F.keys_right.copy(), l2r=F.l2r.copy(), r2l=F.r2l.copy()) for F in refs]
+    return pairs, frames, poses, rig_poses, maps, expect, cross
+
+
+class World:
+    """the streams of _streams() extracted as [L0 .. L(B-1), R0 .. R(B-1)] and stereo-linked on the library under test, their maps resident"""
+
+    def __init__(self, lib, shape):
+        w, h, nf, lap, sizes = shape
+        self.lib, self.w, self.h, self.lap, self.sizes, self.B = lib, w, h, lap, sizes, len(sizes)
+        self.pairs, self.refs, self.poses, self.rig_poses, self.maps, self.expect, _ = _streams(w, h, nf, lap, sizes)
+        B = self.B
+        self.ex = ORBextractor(nf, 1.2, 8, 20, 7, lib=lib)
+        self.images = np.stack([p[0] for p in self.pairs] + [p[1] for p in self.pairs])
+        res = self.ex.extract_batch(self.images, lap)
+        self.kL = [r[1] for r in res[:B]]; self.dL = [r[2] for r in res[:B]]; self.kR = [r[1] for r in res[B:]]; self.dR = [r[2] for r in res[B:]]
+        self.link()
+        for b, F in enumerate(self.refs):
+            assert self.kL[b].tobytes() == F.keys.tobytes() and self.kR[b].tobytes() == F.keys_right.tobytes()
+        self.sfs = self.ex.GetScaleFactors()
+        self.cap = self.ex.max_keypoints()
+        self.bounds = (0.0, float(w), 0.0, float(h))
+        self.rps = [None if m is None else M.ResidentPoints(self.ex, m["pos"], m["normal"], m["mind"], m["maxd"], m["desc"]) for m in self.maps]
+        rng = np.random.default_rng(4343)
+        self.occupied = np.zeros((B, 2 * self.cap), np.uint8)
+        for b, F in enumerate(self.refs):
+            self.occupied[b, rng.choice(F.nl, F.nl // 8, replace=False)] = 1
+            self.occupied[b, F.nl + rng.choice(F.nr, F.nr // 8, replace=False)] = 1
+
+    def link(self):
+        st = M.ComputeStereoFishEyeMatches(self.ex, self.ex, CAM1, CAM2, MRLR, TLR, 0, self.B, self.B)
+        for b, F in enumerate(self.refs):
+            assert np.array_equal(st["l2r"][b, :F.nl], F.l2r) and np.array_equal(st["r2l"][b, :F.nr], F.r2l)
+
+    def batch(self, rps=None, poses=None):
+        rps = list(self.rps if rps is None else rps)
+        lp = M.LocalPointsRigBatch(self.ex, self.ex, rps, len(rps), CAM1, CAM2, self.bounds, self.sfs, 0, self.B)
+        lp.set_poses(self.rig_poses[:len(rps)] if poses is None else poses)
+        return lp
+
+    def flags(self, name):
+        return [None if m is None else m[name] for m in self.maps]
+
+    def reference(self, b, th, far):
+        """(mbTrackInView, mbTrackInViewR, assigned, nmatches) of the reference for frame b against its own map"""
+        return self.expect[PARAMS.index((th, far))][b]
+
+    def single(self, b, m, bad, obs, pose=None, occ=None, th=1.0, far=False):
+        """the single-frame product call (pinned to the reference by tests/test_local_points_rig.py) for frame b against map m"""
+        F = self.refs[b]
+        o = (None, None) if occ is None else (occ[b, :F.nl], occ[b, F.nl:F.nl + F.nr])
+        f2 = views.fisheye_frame_view(views.frame_view(self.kL[b], self.dL[b], self.sfs, self.w, self.h, occupied=o[0]),
+                                      views.frame_view(self.kR[b], self.dR[b], self.sfs, self.w, self.h, occupied=o[1]), F.l2r, F.r2l)
+        tl, tr, asg, n = M.SearchLocalPointsRig(self.ex, f2, pose or self.rig_poses[b], CAM1, CAM2, self.bounds, self.sfs, m["pos"], m["normal"], m["mind"], m["maxd"], bad, obs,
+                                                m["desc"], 0.5, th, far, 9.0, 0.8)
+        return tl["in_view"].astype(bool), tr["in_view_r"].astype(bool), asg, n
+
+    def close(self):
+        for r in self.rps:
+            if r is not None:
+                r.close()
+        self.ex.close()
+
+
+def _check_frame(W, b, m_b, asg, nm, iv, ivr, expect, what):
+    il, ir, ref_as, ref_n = expect
+    F = W.refs[b]; ns = F.nl + F.nr
+    print("frame %d (%s): M %d, %d matches (expected %d)" % (b, what, m_b, nm[b], ref_n))
+    assert nm[b] == ref_n and np.array_equal(asg[b, :ns], ref_as), "frame %d (%s): %d vs %d matches" % (b, what, nm[b], ref_n)
+    assert (asg[b, ns:] == -1).all()
+    if iv is not None:
+        assert np.array_equal(iv[b, :m_b].astype(bool), il) and np.array_equal(ivr[b, :m_b].astype(bool), ir), "mbTrackInView(R), frame %d (%s)" % (b, what)
+        assert not iv[b, m_b:].any() and not ivr[b, m_b:].any(), "in_view of frame %d is not zero beyond its %d points" % (b, m_b)
+
+
+def _ragged(lib, shape):
+    W = World(lib, shape)
+    try:
+        lp = W.batch()
+        assert lp.in_view.shape == (W.B, max(W.sizes)) and lp.in_view_r.shape == (W.B, max(W.sizes))
+        for th, far in PARAMS:
+            lp.enqueue(is_bad=W.flags("bad"), has_obs=W.flags("obs"), th=th, far_points=far, th_far=9.0, nnratio=0.8, want_in_view=True)
+            asg, nm, iv, ivr = lp.fetch()
+            for b, m in enumerate(W.maps):
+                if m is None:
+                    assert nm[b] == 0 and (asg[b] == -1).all() and not iv[b].any() and not ivr[b].any(), "frame %d has an empty map" % b
+                    continue
+                expect = W.reference(b, th, far)
+                if th == 1.0:             # the equality is about something: the reference alone finds a quarter of the map
+                    assert expect[3] >= W.sizes[b] / 4.0, "frame %d: the reference finds %d of %d points" % (b, expect[3], W.sizes[b])
+                _check_frame(W, b, W.sizes[b], asg, nm, iv, ivr, expect, "th %g" % th)
+        # occupied keypoints in both cameras, per frame
+        lp.enqueue(is_bad=W.flags("bad"), has_obs=W.flags("obs"), occupied=W.occupied, th=3.0, want_in_view=False)
+        asg, nm, iv, ivr = lp.fetch()
+        assert iv is None and ivr is None
+        for b, m in enumerate(W.maps):
+            if m is None:
+                assert nm[b] == 0 and (asg[b] == -1).all()
+                continue
+            _check_frame(W, b, W.sizes[b], asg, nm, None, None, W.single(b, m, m["bad"], m["obs"], occ=W.occupied, th=3.0), "occupied")
+    finally:
+        W.close()
+
+
+def test_rig_ragged_maps_emulated(emu_lib):
+    _ragged(emu_lib, EMU_SHAPE)
+
+
+@pytest.mark.gpu
+def test_rig_ragged_maps_gpu(hip_lib):
+    _ragged(hip_lib, GPU_SHAPE)
+
+
+@pytest.mark.gpu
+def test_rig_ragged_maps_emulator_shape_gpu(hip_lib):
+    _ragged(hip_lib, EMU_SHAPE)
+
+
+def test_rig_wrong_map_would_be_noticed():
+    """a frame searched against ANOTHER frame's map finds less than the floor of a quarter: reading the wrong map cannot reproduce the expected assignments"""
+    st = _streams(*EMU_SHAPE)
+    maps, cross = st[4], st[6]
+    assert len(cross) >= 3
+    for b, o, n in cross:
+        assert n <= 0.22 * len(maps[o]["pos"]), "frame %d finds %d of frame %d's %d points" % (b, n, o, len(maps[o]["pos"]))
+
+
+def _shared_set(lib):
+    """frames 0 and 1 name ONE resident set with different flags and poses; frame 2 names another set"""
+    W = World(lib, EMU_SHAPE[:4] + ((700, 0, 45),))
+    try:
+        m0, m2 = W.maps[0], W.maps[2]
+        rng = np.random.default_rng(9)
+        bad1 = rng.uniform(size=700) < 0.3; obs1 = rng.uniform(size=700) < 0.5
+        R1 = _rot(0.001, -0.002, 0.0005) @ W.poses[0][0]; t1 = (W.poses[0][1] + np.array([0.01, 0.0, -0.01], np.float32)).astype(np.float32)
+        pose1 = _rig_pose(R1, t1)
+        for poses in ([W.rig_poses[0], pose1, W.rig_poses[2]], [W.rig_poses[0], W.rig_poses[0], W.rig_poses[2]]):
+            lp = W.batch([W.rps[0], W.rps[0], W.rps[2]], poses)
+            lp.enqueue(is_bad=[m0["bad"], bad1, None], has_obs=[m0["obs"], obs1, m2["obs"]], th=3.0, want_in_view=True)
+            asg, nm, iv, ivr = lp.fetch()
+            expect = [W.single(0, m0, m0["bad"], m0["obs"], pose=poses[0], th=3.0), W.single(1, m0, bad1, obs1, pose=poses[1], th=3.0),
+                      W.single(2, m2, None, m2["obs"], pose=poses[2], th=3.0)]
+            for b in range(3):
+                _check_frame(W, b, (700, 700, 45)[b], asg, nm, iv, ivr, expect[b], "shared set")
+            assert expect[0][3] > 700 // 4
+    finally:
+        W.close()
+
+
+def test_rig_shared_set_different_flags_emulated(emu_lib):
+    _shared_set(emu_lib)
+
+
+@pytest.mark.gpu
+def test_rig_shared_set_different_flags_gpu(hip_lib):
+    _shared_set(hip_lib)
+
+
+def _in_view_layout(lib):
+    """the C fetch writes rows M_max apart and zeroes the padding itself (both buffers are handed over full of 0xFF)"""
+    W = World(lib, EMU_SHAPE)
+    try:
+        lp = W.batch()
+        lp.enqueue(is_bad=W.flags("bad"), has_obs=W.flags("obs"), want_in_view=True)
+        m_max = max(W.sizes)
+        bufs = [np.full(W.B * m_max + 64, 0xFF, np.uint8) for _ in range(2)]
+        asg = np.zeros((W.B, 2 * W.cap), np.int32); nm = np.zeros(W.B, np.int32)
+        lib.check(lib.L.orbm_search_rig_batch_fetch(W.ex._h, asg.ctypes.data, 2 * W.cap, nm.ctypes.data, bufs[0].ctypes.data, bufs[1].ctypes.data))
+        rows = [x[:W.B * m_max].reshape(W.B, m_max) for x in bufs]
+        assert all((x[W.B * m_max:] == 0xFF).all() for x in bufs)
+        for b, m in enumerate(W.maps):
+            n = W.sizes[b]
+            assert not rows[0][b, n:].any() and not rows[1][b, n:].any()
+            if m is not None:
+                il, ir, _, _ = W.reference(b, 1.0, False)
+                assert np.array_equal(rows[0][b, :n].astype(bool), il) and np.array_equal(rows[1][b, :n].astype(bool), ir) and il.any() and ir.any()
+    finally:
+        W.close()
+
+
+def test_rig_in_view_layout_emulated(emu_lib):
+    _in_view_layout(emu_lib)
+
+
+@pytest.mark.gpu
+def test_rig_in_view_layout_gpu(hip_lib):
+    _in_view_layout(hip_lib)
+
+
+def test_rig_pool_overflow_with_ragged_maps(emu_lib):
+    """th = 30 on a fresh handle: one ORBX_E_CAPACITY from the fetch (the pool, sized from the sum of the M_b, is enlarged), then the re-enqueued
+    batch equals the single-frame calls"""
+    W = World(emu_lib, EMU_SHAPE)
+    try:
+        lp = W.batch()
+        lp.enqueue(th=30.0)
+        assert lp._fetch() == E_CAPACITY
+        lp.enqueue(th=30.0)
+        assert lp._fetch() == 0
+        for b, m in enumerate(W.maps):
+            if m is None:
+                assert lp.nm[b] == 0 and (lp.assigned[b] == -1).all()
+                continue
+            _check_frame(W, b, W.sizes[b], lp.assigned, lp.nm, None, None, W.single(b, m, None, None, th=30.0), "th 30")
+        assert lp.nm[0] > 50
+    finally:
+        W.close()
+
+
+def _refusals(lib, two_devices):
+    L = lib.L
+    live0 = _live(lib)
+    W = World(lib, EMU_SHAPE[:4] + ((50, 0),))
+    ex, B, cap2 = W.ex, 2, 2 * W.cap
+    rv = (M._FrustumRigView * B)()
+    for b in range(B):
+        M.rig_frustum_view(W.rig_poses[b], CAM1, CAM2, W.bounds, W.sfs, into=rv[b])
+    table = (M._FrameMap * B)()
+    table[0].points = W.rps[0]._p
+    a = np.zeros((B, cap2), np.int32); nm = np.zeros(B, np.int32)
+    fetch = lambda h=ex: L.orbm_search_rig_batch_fetch(h._h, a.ctypes.data, cap2, nm.ctypes.data, None, None)
+    enqueue = lambda t, l=ex, r=ex, lf=0, rf=B: L.orbm_search_local_points_rig_batch_maps(l._h, lf, r._h, rf, B, rv, t, None, 0.5, 1.0, 0, 0.0, 0.8, 0)
+    assert enqueue(table) == 0 and fetch() == 0                                   # accepted
+    assert enqueue(None) == E_ARG and fetch() == E_ARG                            # a NULL table: refused, and the pending batch is gone
+    assert enqueue(table) == 0
+    assert enqueue(table, lf=1, rf=1) == E_ARG and fetch() == E_ARG               # other frames than the stereo call linked
+    assert L.orbm_search_local_points_rig_batch_maps(None, 0, ex._h, B, B, rv, table, None, 0.5, 1.0, 0, 0.0, 0.8, 0) == E_ARG
+    assert L.orbm_search_local_points_rig_batch_maps(ex._h, 0, None, B, B, rv, table, None, 0.5, 1.0, 0, 0.0, 0.8, 0) == E_ARG
+    # the wrong fetch for the form of the pending batch, both ways
+    assert enqueue(table) == 0
+    assert L.orbm_search_local_points_fetch(ex._h, a.ctypes.data, cap2, None, None) == E_ARG
+    assert fetch() == 0
+    fv = (M._FrustumView * B)()
+    for b in range(B):
+        M.frustum_view(W.poses[b][0], W.poses[b][1], CAM1, W.bounds, 0.0, W.sfs, into=fv[b])
+    assert L.orbm_search_local_points_batch_maps(ex._h, 0, B, fv, table, None, 0, 0.5, 1.0, 0, 0.0, 0.8, 0) == 0
+    assert fetch() == E_ARG                                                       # a one-camera maps batch is pending
+    assert L.orbm_search_local_points_fetch(ex._h, a.ctypes.data, cap2, nm.ctypes.data, None) == 0
+    if two_devices:
+        other = ORBextractor(300, 1.2, 8, 20, 7, lib=lib, device_id=1)
+        m = W.maps[0]
+        rp2 = M.ResidentPoints(other, m["pos"], m["normal"], m["mind"], m["maxd"], m["desc"])
+        table[1].points = rp2._p
+        assert enqueue(table) == E_ARG and b"frame 1" in L.orbx_last_error()      # the message names the frame
+        assert fetch() == E_ARG
+        table[1].points = None
+        rp2.close(); other.close()
+    # stale stereo links: a handle has extracted since orbm_stereo_fisheye
+    assert enqueue(table) == 0 and fetch() == 0
+    ex.extract_batch(W.images, W.lap)
+    assert enqueue(table) == E_ARG and fetch() == E_ARG
+    W.link()
+    assert enqueue(table) == 0 and fetch() == 0 and nm[1] == 0
+    W.close()
+    assert _live(lib) == live0
+
+
+def test_rig_refusals_emulated(emu_lib, monkeypatch):
+    monkeypatch.setenv("ORBX_EMU_DEVICES", "2")
+    assert emu_lib.L.orbx_device_count() == 2
+    _refusals(emu_lib, True)
+
+
+@pytest.mark.gpu
+def test_rig_refusals_gpu(hip_lib):
+    _refusals(hip_lib, False)
+
+
+def _identical_entries(lib, shape):
+    """B table entries naming one set with one pair of flag arrays = the one-map rig call on the same batch: equal outputs from both forms (and
+    frame 0 of the one-map call gives what the reference gives)"""
+    W = World(lib, shape)
+    try:
+        m, rp, B = W.maps[0], W.rps[0], W.B
+        one = M.LocalPointsRigBatch(W.ex, W.ex, rp, B, CAM1, CAM2, W.bounds, W.sfs, 0, B); one.set_poses(W.rig_poses)
+        many = W.batch([rp] * B)
+        for occ in (None, W.occupied):
+            one.enqueue(is_bad=m["bad"], has_obs=m["obs"], occupied=occ, th=1.0, far_points=False, th_far=9.0, want_in_view=True)
+            r1 = [x.copy() for x in one.fetch()]
+            many.enqueue(is_bad=[m["bad"]] * B, has_obs=[m["obs"]] * B, occupied=occ, th=1.0, far_points=False, th_far=9.0, want_in_view=True)
+            r2 = many.fetch()
+            assert all(np.array_equal(x, y) for x, y in zip(r1, r2))
+            if occ is None:
+                il, ir, ref_as, ref_n = W.reference(0, 1.0, False)
+                F = W.refs[0]
+                assert r1[1][0] == ref_n and np.array_equal(r1[0][0, :F.nl + F.nr], ref_as) and np.array_equal(r1[2][0].astype(bool), il) and ref_n >= W.sizes[0] / 4.0
+    finally:
+        W.close()
+
+
+def test_rig_identical_entries_equal_the_one_map_call_emulated(emu_lib):
+    _identical_entries(emu_lib, EMU_SHAPE)
+
+
+@pytest.mark.gpu
+def test_rig_identical_entries_equal_the_one_map_call_gpu(hip_lib):
+    _identical_entries(hip_lib, GPU_SHAPE)
