@@ -165,18 +165,10 @@ __global__ void __launch_bounds__(64 * kAreaWaves) k_area_search(const AreaQuery
                                                      const unsigned long long* __restrict__ fdesc, GridParams g,
                                                      const int* __restrict__ cell_start, const int* __restrict__ cell_items,
                                                      int gate_right, int* __restrict__ pool_counter, int pool_cap,
-                                                     int* __restrict__ q_start, int* __restrict__ q_count, int2* __restrict__ entries, int frame_stride) {
+                                                     int* __restrict__ q_start, int* __restrict__ q_count, int2* __restrict__ entries) {
     __shared__ int s_cnt[kAreaWaves], s_base;
     const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
     const int q = (int)blockIdx.x * kAreaWaves + wave;
-    if (frame_stride > 0) {
-        // batched form: blockIdx.y = frame; every frame has its own Q queries against its own keypoints / grid; the query descriptors (map
-        // points) and the entry pool are shared
-        const size_t b = blockIdx.y;
-        queries += b * (size_t)Q; q_start += b * (size_t)Q; q_count += b * (size_t)Q;
-        kps += b * (size_t)frame_stride; u_right += b * (size_t)frame_stride; fdesc += 4 * b * (size_t)frame_stride;
-        cell_start += b * (size_t)kGridCellStride; cell_items += b * (size_t)frame_stride;
-    }
     AreaQuery A{};
     if (q < Q) A = queries[q];
     int cnt_total = 0, start = 0;

@@ -229,7 +229,7 @@ struct AreaBlock {
 };
 void launch_area_search(orbx_extractor* h, const DeviceFrame& D, int Q, const AreaQuery* dq, const unsigned long long* dqd, const AreaBlock& o, size_t pool) {
     dim3 grid((Q + kAreaWaves - 1) / kAreaWaves, 1, 1), blk(64 * kAreaWaves, 1, 1);
-    ORBX_LAUNCH(k_area_search, grid, blk, 0, h->s0, dq, dqd, Q, D.kps, D.ur, D.desc, D.g, D.cell_start, D.cell_items, 1, o.counter, (int)pool, o.start, o.count, o.ent, 0);
+    ORBX_LAUNCH(k_area_search, grid, blk, 0, h->s0, dq, dqd, Q, D.kps, D.ur, D.desc, D.g, D.cell_start, D.cell_items, 1, o.counter, (int)pool, o.start, o.count, o.ent);
 }
 // The candidate-pool protocol of the single-frame searches.  launch(block, pool) enqueues the kernels that zero the counter and fill the block
 // for Q queries.  Results come back in one copy: the number of entries fetched with the header (and the caller's `mid` bytes, *mid_host

@@ -5,7 +5,7 @@ import oracle_lib as ol
 from cases import FULL_CASES
 from orb_slam3_detailed_comments_amd import _lib
 from orb_slam3_detailed_comments_amd.extractor import ORBextractor
-emu = _lib.OrbxLib(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'emu', 'liborbx_emu.so'))
+emu = _lib.OrbxLib(ol.emu_lib_path())
 ok = True
 for name, factory, nf, lap in FULL_CASES:
     img = factory()

@@ -11,6 +11,18 @@ KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4
 assert KP_DTYPE.itemsize == 28
 
 
+def emu_lib_path():
+    """the emulator build of the kernel sources the tests run: ORBX_EMU_LIB (the sanitizer / coverage builds of tools/) or tests/emu/liborbx_emu.so"""
+    return os.path.abspath(os.environ.get("ORBX_EMU_LIB") or os.path.join(ROOT, "tests", "emu", "liborbx_emu.so"))
+
+
+def emu_link():
+    """(directory, name) of emu_lib_path() for -L / -l / -rpath"""
+    d, f = os.path.split(emu_lib_path())
+    assert f.startswith("lib") and f.endswith(".so"), f
+    return d, f[3:-3]
+
+
 def build():
     subprocess.run(["make", "-j8", "-C", ORACLE_DIR, "-s"], check=True, stdout=subprocess.DEVNULL)
 

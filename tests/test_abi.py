@@ -69,7 +69,7 @@ def test_null_arguments_are_refused_not_dereferenced(emu_lib):
     """~280 calls with null pointers and zero sizes (tests/null_argument_runner.py), on the emulator build of the same host code."""
     import subprocess
     import sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "null_argument_runner.py"), os.path.join(ROOT, "tests", "emu", "liborbx_emu.so"), ROOT],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "null_argument_runner.py"), ol.emu_lib_path(), ROOT],
                        capture_output=True, text=True)
     lines = r.stdout.strip().splitlines()
     assert r.returncode == 0 and lines and lines[-1].startswith("DONE"), "crashed in: %s (rc %d)\n%s" % (lines[-1] if lines else "?", r.returncode, r.stderr[-500:])

@@ -10,6 +10,7 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EMU_SO = os.environ.get("ORBX_EMU_LIB") or os.path.join(ROOT, "tests", "emu", "liborbx_emu.so")
 
 
 def _free_port():
@@ -18,7 +19,7 @@ def _free_port():
 
 def test_bench_two_ranks_gloo(emu_lib):
     env = dict(os.environ)
-    env.update(ORBX_BENCH_BACKEND="gloo", ORBX_BENCH_LIB=os.path.join(ROOT, "tests", "emu", "liborbx_emu.so"), OMP_NUM_THREADS="1")
+    env.update(ORBX_BENCH_BACKEND="gloo", ORBX_BENCH_LIB=EMU_SO, OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "1", "--handles", "1", "--full", "--no-cpu-baseline", "--min-seconds", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
@@ -43,7 +44,7 @@ def test_bench_launches_its_own_ranks(emu_lib):
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    env.update(ORBX_BENCH_BACKEND="gloo", ORBX_BENCH_LIB=os.path.join(ROOT, "tests", "emu", "liborbx_emu.so"), OMP_NUM_THREADS="1")
+    env.update(ORBX_BENCH_BACKEND="gloo", ORBX_BENCH_LIB=EMU_SO, OMP_NUM_THREADS="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "1", "--handles", "1", "--full", "--no-cpu-baseline",
            "--allgather", "--min-seconds", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
@@ -136,7 +137,7 @@ def test_bench_eight_ranks_gloo(emu_lib):
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    env.update(ORBX_BENCH_BACKEND="gloo", ORBX_BENCH_LIB=os.path.join(ROOT, "tests", "emu", "liborbx_emu.so"), OMP_NUM_THREADS="1")
+    env.update(ORBX_BENCH_BACKEND="gloo", ORBX_BENCH_LIB=EMU_SO, OMP_NUM_THREADS="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--pairs", "1", "--handles", "1", "--full", "--no-cpu-baseline",
            "--allgather"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
@@ -159,7 +160,7 @@ def test_bench_plain_run_times_its_steps_and_dumps_outputs(emu_lib, tmp_path):
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "ORBX_BENCH_BACKEND"):
         env.pop(k, None)
-    env.update(ORBX_BENCH_LIB=os.path.join(ROOT, "tests", "emu", "liborbx_emu.so"), OMP_NUM_THREADS="1")
+    env.update(ORBX_BENCH_LIB=EMU_SO, OMP_NUM_THREADS="1")
     dumps = []
     for run in range(2):
         d = tmp_path / str(run)
@@ -246,7 +247,7 @@ def test_bench_dump_other_configs(config, emu_lib, tmp_path):
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "ORBX_BENCH_BACKEND"):
         env.pop(k, None)
-    env.update(ORBX_BENCH_LIB=os.path.join(ROOT, "tests", "emu", "liborbx_emu.so"), OMP_NUM_THREADS="1")
+    env.update(ORBX_BENCH_LIB=EMU_SO, OMP_NUM_THREADS="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", config, "--steps", "2", "--warmup", "1", "--pairs", "1", "--handles", "1",
            "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)

@@ -1,0 +1,203 @@
+"""The sub-pixel tail of Frame::ComputeStereoMatches (reference src/Frame.cc:1305-1336, csrc/k_match.hip: the parabola, the negative-disparity rejection and the
+`disparity <= 0` clamp to 0.01 with bestuR = uL - 0.01 evaluated in double) on inputs made for those branches, small enough for the emulator (where the sanitizer
+and coverage builds run): an identical pair (disparity exactly 0), the right image shifted one and two pixels the WRONG way (the descriptor search only admits
+right keypoints at or left of uL, the SAD refinement then walks to the right of it), and one-pixel stripes added to the right image.
+
+mvuRight / mvDepth must be bit-equal to the reference's own Frame constructor (oracle/_ref/libref_frame.so).  A sequential numpy restatement of the function, in
+float32 where the reference computes in float, must give the same bits too, and it counts how many keypoints enter each branch: every case asserts that its own
+branch was entered.
+
+Disparity exactly 0 needs deltaR == 0, i.e. equal SADs one pixel left and right of the best shift: on a noisy texture that next to never happens (an identical
+pair of synth.corner_field images: one keypoint of 510), on flat rectangles without noise it is common.  And in a wholly identical pair every SAD is 0, so is the
+median, and the outlier removal (:1343-1357, `SAD < 2.1 * median` keeps) erases EVERY match, the clamped ones included: "identical" pins that, "identical_upper"
+(noise of +-3 grey levels below row 80, so that the median is not 0) is the case whose clamped mvuRight / mvDepth survive into the output.
+
+The third gate, `deltaR < -1 || deltaR > 1`, cannot be entered by any input: bestincR is the FIRST minimum of the eleven SADs and is not at either end, so
+dist1 > dist2 <= dist3, the denominator 2 (dist1 + dist3 - 2 dist2) is positive and |dist1 - dist3| <= dist1 + dist3 - 2 dist2, i.e. |deltaR| <= 0.5 (the SADs
+are integers below 2^15: every operation is exact up to the division).  The striped pair is the attempt the gate's comment suggests; the restatement asserts the
+bound instead of an entry (profiles/emu_coverage/README.md lists the branch as unreachable)."""
+import numpy as np
+import pytest
+
+import oracle_lib as ol
+from orb_slam3_detailed_comments_amd import ORBextractor, ComputeStereoMatches, synth
+
+pytestmark = pytest.mark.skipif(ol.reference_frame_lib() is None, reason="oracle/_ref/libref_frame.so not built (needs /root/reference)")
+W, H, NF = 376, 240, 500
+FX = 458.654
+BF = FX * 0.110074
+f32 = np.float32
+
+
+def _round_half_away(x):                   # round() of <cmath> on a non-negative float
+    return f32(np.floor(np.float64(x) + 0.5))
+
+
+def restated_stereo(kL, dL, kR, dR, pyrL, pyrR, mbf, mb):
+    """Frame::ComputeStereoMatches, src/Frame.cc:1102-1358, one keypoint after the other.  Returns (mvuRight, mvDepth, counts of the keypoints per branch)."""
+    N, Nr = len(kL), len(kR)
+    sf = np.ones(8, f32)
+    for i in range(1, 8):
+        sf[i] = sf[i - 1] * f32(1.2)
+    inv = (f32(1.0) / sf).astype(f32)
+    u_right = np.full(N, -1, f32); depth = np.full(N, -1, f32)
+    rows = [[] for _ in range(pyrL[0].shape[0])]
+    for iR in range(Nr):
+        y = f32(kR["y"][iR]); r = f32(2.0) * sf[kR["octave"][iR]]
+        lo, hi = int(np.floor(y - r)), int(np.ceil(y + r))
+        assert 0 <= lo and hi < len(rows), "a band outside the image: the reference indexes vRowIndices out of range there (:1153), not an input for this test"
+        for yi in range(lo, hi + 1):
+            rows[yi].append(iR)
+    bitsL = np.unpackbits(dL, axis=1).astype(np.int16); bitsR = np.unpackbits(dR, axis=1).astype(np.int16)
+    minD, maxD = f32(0), f32(mbf) / f32(mb)
+    entered = dict(clamp=0, negative=0, too_far=0, delta=0, max_abs_delta=0.0)
+    dist_idx = []
+    for iL in range(N):
+        lvl = int(kL["octave"][iL]); uL = f32(kL["x"][iL]); vL = f32(kL["y"][iL])
+        cands = rows[int(vL)]
+        minU, maxU = uL - maxD, uL - minD
+        if not cands or maxU < 0:
+            continue
+        best, bestR = 100, 0
+        for iR in cands:
+            if kR["octave"][iR] < lvl - 1 or kR["octave"][iR] > lvl + 1:
+                continue
+            uR = f32(kR["x"][iR])
+            if uR >= minU and uR <= maxU:
+                d = int(np.abs(bitsL[iL] - bitsR[iR]).sum())
+                if d < best:
+                    best, bestR = d, iR
+        if not best < 75:
+            continue
+        uR0 = f32(kR["x"][bestR])
+        su, sv, sr = _round_half_away(uL * inv[lvl]), _round_half_away(vL * inv[lvl]), _round_half_away(uR0 * inv[lvl])
+        w = L = 5
+        IL = pyrL[lvl][int(sv) - w:int(sv) + w + 1, int(su) - w:int(su) + w + 1].astype(np.int32)
+        if sr + f32(L - w) < 0 or sr + f32(L + w + 1) >= pyrR[lvl].shape[1]:
+            continue
+        sads = []
+        for inc in range(-L, L + 1):
+            IR = pyrR[lvl][int(sv) - w:int(sv) + w + 1, int(sr) + inc - w:int(sr) + inc + w + 1].astype(np.int32)
+            sads.append(int(np.abs(IL - IR).sum()))
+        bi = int(np.argmin(sads))                                     # the first minimum: `dist < bestDist` while incR ascends
+        if bi == 0 or bi == 2 * L:
+            continue
+        d1, d2, d3 = f32(sads[bi - 1]), f32(sads[bi]), f32(sads[bi + 1])
+        delta = (d1 - d3) / (f32(2.0) * (d1 + d3 - f32(2.0) * d2))
+        entered["max_abs_delta"] = max(entered["max_abs_delta"], abs(float(delta)))
+        if delta < -1 or delta > 1:
+            entered["delta"] += 1
+            continue
+        best_u = sf[lvl] * ((sr + f32(bi - L)) + delta)
+        disparity = uL - best_u
+        if not disparity >= minD:
+            entered["negative"] += 1
+            continue
+        if not disparity < maxD:
+            entered["too_far"] += 1
+            continue
+        if disparity <= 0:
+            entered["clamp"] += 1
+            disparity = f32(0.01); best_u = f32(np.float64(uL) - 0.01)
+        depth[iL] = f32(mbf) / disparity; u_right[iL] = best_u
+        dist_idx.append((sads[bi], iL))
+    dist_idx.sort()
+    if dist_idx:                                                     # (the reference reads vDistIdx[0] of an empty vector otherwise; no such input here)
+        th = f32(1.5) * f32(1.4) * f32(dist_idx[len(dist_idx) // 2][0])
+        for s, iL in reversed(dist_idx):
+            if f32(s) < th:
+                break
+            u_right[iL] = -1; depth[iL] = -1
+    return u_right, depth, entered
+
+
+def _shift_right(img, px):
+    """the content px pixels further RIGHT than in the left image: the disparity of every point is -px"""
+    out = img.copy()
+    out[:, px:] = img[:, :-px]
+    return out
+
+
+def _flat_rectangles(seed, n=500):
+    rng = np.random.default_rng(seed)
+    img = np.full((H, W), 128, np.uint8)
+    for _ in range(n):
+        x, y, w, h = rng.integers(0, W - 8), rng.integers(0, H - 8), rng.integers(8, 48), rng.integers(8, 48)
+        img[y:y + h, x:x + w] = rng.integers(0, 256)
+    return img
+
+
+def _noisy_below(img, row, seed):
+    out = img.astype(np.int32)
+    out[row:] += np.random.default_rng(seed).integers(-3, 4, out[row:].shape)
+    return np.clip(out, 0, 255).astype(np.uint8)
+
+
+def _striped(img, seed):
+    rng = np.random.default_rng(seed)
+    out = img.astype(np.int32)
+    cols = rng.random(img.shape[1]) < 0.3
+    out[:, cols] += rng.integers(-60, 61, int(cols.sum()))[None, :]
+    return np.clip(out, 0, 255).astype(np.uint8)
+
+
+_CASES = {}
+
+
+def _case(name):
+    """(left, right, reference Frame, restated mvuRight, mvDepth, branch counts), made once per session and shared by the emulator and the GPU form"""
+    if name not in _CASES:
+        L = _flat_rectangles(1) if name.startswith("identical") else synth.corner_field(W, H, seed=60, nrect=800)
+        R = {"identical": lambda: L.copy(), "identical_upper": lambda: _noisy_below(L, 80, 99), "wrong_way_1": lambda: _shift_right(L, 1), "wrong_way_2": lambda: _shift_right(L, 2), "stripes": lambda: _striped(L, 7)}[name]()
+        F = ol.ReferenceFrame(L, R, NF, 1.2, 8, 20, 7, 0, fx=FX, bf=BF)
+        oL, oR = ol.OracleExtractor(NF), ol.OracleExtractor(NF)
+        oL.extract(L); oR.extract(R)
+        pyrL = [oL.level_image(l) for l in range(8)]; pyrR = [oR.level_image(l) for l in range(8)]
+        u, d, entered = restated_stereo(F.keys, F.desc, F.keys_right, F.desc_right, pyrL, pyrR, F.mbf, F.mb)
+        for a in (F.u_right, F.depth, u, d):
+            a.setflags(write=False)
+        _CASES[name] = (L, R, F, u, d, entered)
+    return _CASES[name]
+
+
+def _check(lib, name):
+    L, R, F, u_re, d_re, entered = _case(name)
+    print(name, "keypoints", F.N, "matched", int((F.u_right >= 0).sum()), entered)
+    # the restatement is the reference, bit for bit: its branch counts are the reference's
+    assert u_re.tobytes() == F.u_right.tobytes() and d_re.tobytes() == F.depth.tobytes(), "the numpy restatement differs from the reference Frame"
+    assert F.N > 300
+    assert entered["delta"] == 0 and entered["max_abs_delta"] <= 0.5              # see the module docstring
+    if name == "identical":
+        assert entered["clamp"] > 10 and (F.u_right >= 0).sum() == 0
+    elif name == "identical_upper":
+        clamped = F.depth == f32(F.mbf) / f32(0.01)
+        assert entered["clamp"] > 10 and clamped.sum() > 10
+        assert np.array_equal(F.u_right[clamped], (F.keys["x"][clamped].astype(np.float64) - 0.01).astype(f32))
+    elif name.startswith("wrong_way"):
+        assert entered["negative"] > 20
+    else:
+        assert (F.u_right >= 0).sum() > 20
+    ex = ORBextractor(NF, 1.2, 8, 20, 7, lib=lib)
+    (_, kL, dL), (_, kR, dR) = ex.extract_batch(np.stack([L, R]))
+    assert kL.tobytes() == F.keys.tobytes() and dL.tobytes() == F.desc.tobytes() and kR.tobytes() == F.keys_right.tobytes() and dR.tobytes() == F.desc_right.tobytes()
+    u, d, n = ComputeStereoMatches(ex, ex, BF, F.mb, 0, 1, 1)
+    ex.close()
+    N = F.N
+    bad = np.flatnonzero(u[0, :N].view(np.uint32) != F.u_right.view(np.uint32))
+    assert len(bad) == 0, "%s: mvuRight differs at %d keypoints, first %d: %r vs the reference's %r" % (name, len(bad), bad[0], u[0, bad[0]], F.u_right[bad[0]])
+    assert d[0, :N].tobytes() == F.depth.tobytes(), "%s: mvDepth differs from the reference Frame" % name
+    assert int(n[0]) == int((F.u_right >= 0).sum())
+
+
+CASES = ["identical", "identical_upper", "wrong_way_1", "wrong_way_2", "stripes"]
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_stereo_subpixel_edges_emulated(emu_lib, name):
+    _check(emu_lib, name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", CASES)
+def test_stereo_subpixel_edges_gpu(hip_lib, name):
+    _check(hip_lib, name)

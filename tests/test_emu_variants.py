@@ -19,10 +19,14 @@ SOURCES = ("k_image.hip", "k_fast.hip", "k_quadtree.hip", "k_describe.hip", "k_m
 
 
 def build_emu_variant(so, defines):
-    """the kernel sources for the CPU SIMT emulator with extra -D switches; the translation units are compiled side by side"""
+    """the kernel sources for the CPU SIMT emulator with extra -D switches; the translation units are compiled side by side.  ORBX_EMU_EXTRA_FLAGS: further compile and
+    link flags (tools/emu_coverage.sh: --coverage; a sanitizer run: -fsanitize=...)"""
+    import shlex
     from concurrent.futures import ThreadPoolExecutor
     d = os.path.dirname(so)
     flags = ["-O2", "-std=c++17", "-ffp-contract=off", "-fwrapv", "-fno-gnu-unique", "-DORBX_EMU"] + list(defines) + ["-I" + os.path.join(ROOT, "tests", "emu"), "-I" + CSRC, "-fPIC", "-w"]
+    extra = shlex.split(os.environ.get("ORBX_EMU_EXTRA_FLAGS", ""))
+    flags += extra
 
     def one(f):
         o = os.path.join(d, f + ".o")
@@ -30,7 +34,7 @@ def build_emu_variant(so, defines):
         return o
     with ThreadPoolExecutor(6) as ex:
         objs = list(ex.map(one, SOURCES))
-    subprocess.run(["g++", "-shared"] + objs + ["-o", so, "-lpthread"], check=True)
+    subprocess.run(["g++", "-shared"] + extra + objs + ["-o", so, "-lpthread"], check=True)
 
 
 @pytest.mark.parametrize("presort_max,bigspan,wave_sort_range,big_pixels,u16_max", [(1, 80, 16, 0, 65535), (0, 1024, 100000, 150000, 0), (5, 1024, 40, 0, 0)])

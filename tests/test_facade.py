@@ -33,7 +33,7 @@ def _run_pair(tmp_path, libdir, libname, extra_env=None):
 
 @pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref/facade_driver_ref not built (needs /root/reference)")
 def test_facade_dropin_emulated(tmp_path, emu_lib):
-    _run_pair(tmp_path, os.path.join(ROOT, "tests", "emu"), "orbx_emu")
+    _run_pair(tmp_path, *ol.emu_link())
 
 
 @pytest.mark.gpu
@@ -67,7 +67,7 @@ def _run_matcher_threads(tmp_path, libdir, libname):
 
 
 def test_matcher_facade_three_threads_emulated(tmp_path, emu_lib):
-    exe = _run_matcher_threads(tmp_path, os.path.join(ROOT, "tests", "emu"), "orbx_emu")
+    exe = _run_matcher_threads(tmp_path, *ol.emu_link())
     # a multi-GPU C++ host: two "GPUs" (the emulator reports as many as ORBX_EMU_DEVICES says), extractor + matcher handles per device, and the
     # descriptor all-gather of BASELINE.json configs[4] through the C ABI alone (orbx_comm_*, orbx_allgather_descriptors)
     r = subprocess.run([str(exe), str(tmp_path / "t.raw"), "376", "240", "2"], capture_output=True, text=True, timeout=600, env=dict(os.environ, ORBX_EMU_DEVICES="2"))
@@ -83,7 +83,7 @@ def test_matcher_facade_three_threads_gpu(tmp_path, hip_lib):
 
 
 def test_matcher_facade_emulated(tmp_path, emu_lib):
-    _run_matcher_facade(tmp_path, os.path.join(ROOT, "tests", "emu"), "orbx_emu")
+    _run_matcher_facade(tmp_path, *ol.emu_link())
 
 
 @pytest.mark.gpu
@@ -103,12 +103,12 @@ def test_vocabulary_facade_emulated(tmp_path, emu_lib):
     voc = tmp_path / "voc.txt"
     vs.write_text(voc, header, parent, leaf, desc, weight)
     exe = tmp_path / "vocabulary_facade_test"
-    libdir = os.path.join(ROOT, "tests", "emu")
+    libdir, libname = ol.emu_link()
     srcs = [os.path.join(DBOW2, "DBoW2", f) for f in ("FORB.cpp", "BowVector.cpp", "FeatureVector.cpp", "ScoringObject.cpp")] + [os.path.join(DBOW2, "DUtils", "Random.cpp"), os.path.join(DBOW2, "DUtils", "Timestamp.cpp")]
     subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + os.path.join(ROOT, "include", "orb_slam3_amd"), "-I" + os.path.join(ROOT, "include"),
                     "-I" + os.path.join(ROOT, "oracle", "opencv_shim"), "-I" + os.path.join(ROOT, "oracle", "boost_shim"), "-I" + DBOW2,
                     os.path.join(ROOT, "tests", "cpp", "vocabulary_facade_test.cpp")] + srcs +
-                   ["-L" + libdir, "-lorbx_emu", "-Wl,-rpath," + libdir, "-lpthread", "-o", str(exe)], check=True)
+                   ["-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-lpthread", "-o", str(exe)], check=True)
     r = subprocess.run([str(exe), str(voc), "900"], capture_output=True, text=True)
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
 
@@ -120,10 +120,10 @@ def test_facade_headers_link_from_several_translation_units(tmp_path, emu_lib):
     inc = '#include "ORBextractor.h"\n#include "ORBmatcher.h"\n' + ('#include "ORBVocabulary.h"\n' if voc else "")
     (tmp_path / "a.cpp").write_text(inc + "int fa() { ORB_SLAM3::ORBmatcher m(0.7f, true); const int& r = ORB_SLAM3::ORBmatcher::TH_LOW; return r; }\n")
     (tmp_path / "b.cpp").write_text(inc + "int fa();\nint main() { const int& r = ORB_SLAM3::ORBmatcher::TH_HIGH; return fa() + r + ORB_SLAM3::ORBmatcher::HISTO_LENGTH == 180 ? 0 : 1; }\n")
-    libdir = os.path.join(ROOT, "tests", "emu")
+    libdir, libname = ol.emu_link()
     cmd = ["g++", "-std=c++14", "-w", "-I" + os.path.join(ROOT, "include", "orb_slam3_amd"), "-I" + os.path.join(ROOT, "oracle", "opencv_shim")]
     if voc:
         cmd += ["-I" + DBOW2, "-I/root/reference", "-I" + os.path.join(ROOT, "oracle", "boost_shim")]
     exe = tmp_path / "two_tu"
-    subprocess.run(cmd + [str(tmp_path / "a.cpp"), str(tmp_path / "b.cpp"), "-L" + libdir, "-lorbx_emu", "-Wl,-rpath," + libdir, "-lpthread", "-o", str(exe)], check=True)
+    subprocess.run(cmd + [str(tmp_path / "a.cpp"), str(tmp_path / "b.cpp"), "-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-lpthread", "-o", str(exe)], check=True)
     assert subprocess.run([str(exe)]).returncode == 0

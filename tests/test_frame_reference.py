@@ -168,7 +168,7 @@ def _dropin_vs_reference(tmp_path, orbx, cases):
 
 @pytest.mark.skipif(not os.path.exists(DROPIN), reason="oracle/_ref/libref_frame_dropin.so not built (needs /root/reference)")
 def test_reference_frame_on_dropin_extractor_emulated(tmp_path, emu_lib):
-    _dropin_vs_reference(tmp_path, os.path.join(ol.ROOT, "tests", "emu", "liborbx_emu.so"), CASES[2:3])
+    _dropin_vs_reference(tmp_path, ol.emu_lib_path(), CASES[2:3])
 
 
 @pytest.mark.gpu

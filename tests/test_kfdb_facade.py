@@ -42,7 +42,7 @@ def run(exe, path, seed):
 
 @pytest.mark.parametrize("scoring,seed", [(0, 1), (1, 2), (2, 3), (4, 5)])
 def test_kfdb_facade_emulated(emu_lib, tmp_path, scoring, seed):
-    exe = build_driver(tmp_path, os.path.join(ROOT, "tests", "emu"), "orbx_emu")
+    exe = build_driver(tmp_path, *ol.emu_link())
     run(exe, vocabulary(tmp_path, scoring), seed)
 
 

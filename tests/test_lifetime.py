@@ -176,7 +176,7 @@ def test_facade_worlds_leave_nothing_behind(tmp_path, emu_lib):
     facade = os.path.join(ol.ROOT, "oracle", "_ref", "libmw_facade.so")
     if not os.path.exists(facade):
         pytest.skip("oracle/_ref/libmw_facade.so not built (needs /root/reference)")
-    orbx = os.path.join(ol.ROOT, "tests", "emu", "liborbx_emu.so")
+    orbx = ol.emu_lib_path()
     for seed, variant in [(1, "base"), (6, "kb8")]:
         dst = str(tmp_path / ("w_%s.npz" % variant))
         r = subprocess.run([sys.executable, os.path.join(ol.ROOT, "tests", "matcher_world.py"), facade, orbx, str(seed), variant, dst, "twice"], capture_output=True, text=True)

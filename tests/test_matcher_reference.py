@@ -58,7 +58,7 @@ def _compare(tmp_path, orbx, cases, ref=REF, facade=FACADE):
 
 
 def test_matcher_facade_equals_reference_emulated(tmp_path, emu_lib):
-    _compare(tmp_path, os.path.join(ROOT, "tests", "emu", "liborbx_emu.so"), [(1, "base"), (2, "dense"), (3, "hard"), (4, "rig"), (5, "rig"), (6, "kb8"), (7, "kb8")])
+    _compare(tmp_path, ol.emu_lib_path(), [(1, "base"), (2, "dense"), (3, "hard"), (4, "rig"), (5, "rig"), (6, "kb8"), (7, "kb8")])
 
 
 @pytest.mark.gpu
@@ -82,7 +82,7 @@ def test_real_classes_agree_with_standins(tmp_path):
 
 @real
 def test_matcher_facade_equals_reference_real_classes_emulated(tmp_path, emu_lib):
-    _compare(tmp_path, os.path.join(ROOT, "tests", "emu", "liborbx_emu.so"), [(1, "base"), (3, "hard"), (4, "rig"), (6, "kb8")], REF_REAL, FACADE_REAL)
+    _compare(tmp_path, ol.emu_lib_path(), [(1, "base"), (3, "hard"), (4, "rig"), (6, "kb8")], REF_REAL, FACADE_REAL)
 
 
 @real
@@ -94,7 +94,7 @@ def test_matcher_facade_equals_reference_real_classes_gpu(tmp_path, hip_lib):
 def test_matcher_facade_equals_reference_random_parameters_emulated(tmp_path, emu_lib):
     """the same worlds with the methods' parameters (th, nnratio, ORBdist, window, ratioHamming) drawn at random per seed instead of the reference's call-site
     values (variant "fuzz"; tools/soak_world_fuzz.py runs more seeds): Fuse below th = 2.8 is what the fixed values had hidden (round 5)"""
-    orbx = os.path.join(ROOT, "tests", "emu", "liborbx_emu.so")
+    orbx = ol.emu_lib_path()
     for seed in (11, 12, 13):
         a = _run(tmp_path, REF, "", seed, "fuzz", "ref")
         b = _run(tmp_path, FACADE, orbx, seed, "fuzz", "facade")

@@ -176,7 +176,7 @@ def _facade_all(tmp, exe, env):
 
 @pytest.mark.skipif(not os.path.exists(REF_DRIVER), reason="oracle/_ref/facade_driver_ref not built (needs /root/reference)")
 def test_facade_constructs_every_mono_init_extractor_emulated(tmp_path, emu_lib):
-    _facade_all(tmp_path, _facade_exe(tmp_path, os.path.join(ROOT, "tests", "emu"), "orbx_emu"), dict(os.environ, ORBX_EMU_LDS_LIMIT=GFX950_LDS))
+    _facade_all(tmp_path, _facade_exe(tmp_path, *ol.emu_link()), dict(os.environ, ORBX_EMU_LDS_LIMIT=GFX950_LDS))
 
 
 @pytest.mark.gpu

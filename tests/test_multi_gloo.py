@@ -18,7 +18,7 @@ def _worker(rank, world, port, q):
     from orb_slam3_detailed_comments_amd import synth, _lib, multi
     from orb_slam3_detailed_comments_amd.extractor import ORBextractor
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    lib = _lib.OrbxLib(os.path.join(ROOT, "tests", "emu", "liborbx_emu.so"))
+    lib = _lib.OrbxLib(os.environ.get("ORBX_EMU_LIB") or os.path.join(ROOT, "tests", "emu", "liborbx_emu.so"))
     ex = ORBextractor(300, 1.2, 8, 20, 7, lib=lib)
     frames = [synth.corner_field(376, 240, seed=50 + s, nrect=800) for s in range(5)]     # 5 streams over 2 ranks
     mine = multi.process_streams(ex, frames, rank, world)

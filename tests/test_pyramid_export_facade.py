@@ -25,7 +25,7 @@ def _run(tmp_path, libdir, libname, w, h, calls):
 
 
 def test_facade_pyramid_export_emulated(tmp_path, emu_lib):
-    _run(tmp_path, os.path.join(ROOT, "tests", "emu"), "orbx_emu", 376, 240, 5)
+    _run(tmp_path, *ol.emu_link(), 376, 240, 5)
 
 
 @pytest.mark.gpu
