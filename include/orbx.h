@@ -234,6 +234,19 @@ int orbx_debug_quadtree_pool_levels(orbx_extractor* h);                   /* num
  * packed sub, packed xor(a, c), wave inclusive scan / wave sum of a & 0xFFFF, wave minimum of b (per 64 consecutive elements), v_sad_u8, v_mul_u32_u24,
  * the 64-bit wave scan (two words), the 64-bit workgroup scan (two words), the wave OR, v_mul_hi_u32_u24, v_add3_u32 */
 int orbx_debug_simd_selftest(orbx_extractor* h, const uint32_t* a, const uint32_t* b, const uint32_t* c, int n, uint32_t* out);
+/* test hook: the workgroup primitives of the quadtree kernel (csrc/k_quadtree.hip) run by ONE workgroup of `threads` threads (256 or 1024, the two
+ * sizes a tree runs on) on the caller's data, with their arrays laid out as a tree lays them out.  Host buffers.
+ *  ORBX_QT_SELFTEST_SORT: in = n 64-bit keys, out = the n keys after the kernel's model of libstdc++'s std::sort with the comparator
+ *    (a >> 16) < (b >> 16) - the final rounds' order of (count << 32 | x0 << 16 | index).  spill = 0: every array in LDS, n <= 4095; spill = 1: the
+ *    node-pool form (arrays in device memory, 20-bit range positions), n <= 65535.  start, total, mx, my are not used.
+ *  ORBX_QT_SELFTEST_PARTITION4: in = `total` 32-bit keys (x | y << 12 | ..), out = `total` keys + 4 counts.  The span [start, start + n) of `in` is
+ *    partitioned stably into the same span of `out`, children n1|n2|n3|n4 with left = x < mx, top = y < my; out[total .. total + 4) = the four counts.
+ *    `out` comes in filled: its first `total` keys are uploaded first and everything outside the span has to come back unchanged.  start >= 1.
+ *  ORBX_QT_SELFTEST_SCAN: in = n = `threads` 64-bit values, out = the exclusive prefix sum per thread + the total (threads + 1 values). */
+#define ORBX_QT_SELFTEST_SORT 0
+#define ORBX_QT_SELFTEST_PARTITION4 1
+#define ORBX_QT_SELFTEST_SCAN 2
+int orbx_debug_quadtree_selftest(orbx_extractor* h, int op, int spill, int threads, const void* in, int n, int start, int total, int mx, int my, void* out);
 /* what the library holds at this moment, process-wide: out = { device allocations, page-locked host allocations, streams, events }.  The lifetime
  * tests create, use and destroy every kind of handle (extractor, key frames, map points, vocabulary, communicator, caller buffers) and expect the
  * four counts back where they started (tests/test_lifetime.py). */

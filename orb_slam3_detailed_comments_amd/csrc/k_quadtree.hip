@@ -1103,4 +1103,50 @@ __global__ void __launch_bounds__(kQuadtreeThreads) k_quadtree_spill(const Level
                         qt_prof, wide, counter_bytes);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Self-test of the primitives above (orbx_debug_quadtree_selftest): ONE workgroup of blockDim.x threads (256 or 1024, the two values of
+// LevelInfo::qt_threads) runs one of them on the caller's data, so that the tests can feed them the inputs no image produces (std::sort
+// adversaries, spans of any length).  The arrays of the sort are carved in the order quadtree_tree carves them - range lists (its child-count table) |
+// the two expand arrays | flags (its `erased`) - from dynamic LDS, or from the pool (spill) with only the range counters in LDS.
+//  op 0: out[0..n) = in[0..n) after block_sort_libstdcxx<spill>               (64-bit keys; host: quadtree_selftest_sort_bytes)
+//  op 1: block_partition4 with QuadCls{mx, my} of the span [s, s + n) of in[0..total) into out[0..total); out[total..total+4) = the class counts
+//  op 2: out[t] = block_excl_scan_n<u64>(in[t]) over the blockDim.x / 64 waves, out[blockDim.x] = the total
+template <bool kSpill>
+__device__ __forceinline__ void selftest_sort(unsigned char* mem, const unsigned long long* __restrict__ in, unsigned long long* __restrict__ out, int n, int* s_ctr) {
+    typedef typename SortSeg<kSpill>::T SegT;
+    const int tid = (int)threadIdx.x, NT = (int)blockDim.x;
+    const int cap = quadtree_selftest_seg_cap(n);
+    SegT* seg0 = (SegT*)mem;
+    SegT* seg1 = seg0 + cap;
+    unsigned long long* a = (unsigned long long*)(seg1 + cap);
+    unsigned long long* tmp = a + n;
+    uint8_t* flags = (uint8_t*)(tmp + n);
+    for (int i = tid; i < n; i += NT) a[i] = in[i];
+    __syncthreads();
+    block_sort_libstdcxx<kSpill>(a, tmp, n, seg0, seg1, flags, s_ctr, NT);
+    for (int i = tid; i < n; i += NT) out[i] = a[i];
+}
+__global__ void __launch_bounds__(kQuadtreeThreads) k_quadtree_selftest(int op, int spill, const void* __restrict__ in, void* __restrict__ out,
+                                                                        unsigned char* __restrict__ pool, int n, int s, int total, int mx, int my) {
+    ORBX_DYN_SMEM(smem);
+    __shared__ unsigned long long s_scan[20];
+    __shared__ int s_i[80];
+    const int tid = (int)threadIdx.x, NT = (int)blockDim.x;
+    if (op == 0) {
+        if (spill) selftest_sort<true>(pool, (const unsigned long long*)in, (unsigned long long*)out, n, s_i + 66);
+        else selftest_sort<false>(smem, (const unsigned long long*)in, (unsigned long long*)out, n, s_i + 66);
+    } else if (op == 1) {
+        uint32_t* dst = (uint32_t*)out;
+        int cnt[4];
+        QuadCls cls; cls.mx = mx; cls.my = my;
+        block_partition4((const uint32_t*)in, dst, s, n, cls, s_i, cnt, NT == 256 ? 2 : 4);
+        if (tid < 4) dst[total + tid] = (uint32_t)(tid == 0 ? cnt[0] : tid == 1 ? cnt[1] : tid == 2 ? cnt[2] : cnt[3]);
+    } else {
+        unsigned long long tot;
+        const unsigned long long ex = block_excl_scan_n<unsigned long long>(((const unsigned long long*)in)[tid], &tot, s_scan, NT >> 6);
+        ((unsigned long long*)out)[tid] = ex;
+        if (tid == 0) ((unsigned long long*)out)[NT] = tot;
+    }
+}
+
 }  // namespace orbx

@@ -7,8 +7,9 @@
 // (#keys, UL.x).  Nodes that tie on both are permuted in an implementation-defined way, and that
 // permutation decides which nodes are split before the quota is reached and the order of the output
 // keypoints.  The oracle is the reference compiled with libstdc++, so the device quadtree reproduces
-// libstdc++'s permutation exactly.  tests/test_sort_model.py checks this model against std::sort on
-// tie-heavy, sorted, reversed and median-of-3-killer inputs (host build of the same header).
+// libstdc++'s permutation exactly.  tests/test_models.py (tests/cpp/sort_model_test.cpp) checks this model against std::sort on
+// tie-heavy, sorted, reversed and median-of-3-killer inputs (host build of the same header); tests/test_quadtree_primitives.py checks
+// the kernel's parallel form of it (block_sort_libstdcxx, k_quadtree.hip) against std::sort.
 #pragma once
 #ifndef ORBX_HD
 #define ORBX_HD

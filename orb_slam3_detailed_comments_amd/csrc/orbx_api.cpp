@@ -902,6 +902,37 @@ int orbx_debug_simd_selftest(orbx_extractor* h, const uint32_t* a, const uint32_
     return ORBX_OK;
 }
 
+// debug: one workgroup of `threads` threads runs a workgroup primitive of the quadtree (k_quadtree_selftest) on the caller's data
+int orbx_debug_quadtree_selftest(orbx_extractor* h, int op, int spill, int threads, const void* in, int n, int start, int total, int mx, int my, void* out) {
+    if (!h || !in || !out || (threads != 256 && threads != 1024) || (spill != 0 && spill != 1)) return fail(ORBX_E_ARG, "bad arguments (256 or 1024 threads, spill 0 or 1)");
+    size_t in_bytes = 0, out_bytes = 0, pool_bytes = 0, smem = 0;
+    if (op == ORBX_QT_SELFTEST_SORT) {
+        const int nmax = spill ? 65535 : 4095;          // positions of the range lists: 20 bits (and 16-bit scratch) / 12 bits
+        if (n < 0 || n > nmax) return fail(ORBX_E_ARG, "the %s form sorts at most %d keys", spill ? "pool" : "LDS", nmax);
+        in_bytes = out_bytes = (size_t)n * 8;
+        (spill ? pool_bytes : smem) = quadtree_selftest_sort_bytes(n, spill != 0);
+    } else if (op == ORBX_QT_SELFTEST_PARTITION4) {
+        if (n < 1 || start < 1 || total > (1 << 24) || (long long)start + n > (long long)total) return fail(ORBX_E_ARG, "the span [start, start + n) must lie inside [1, total)");
+        in_bytes = (size_t)total * 4; out_bytes = in_bytes + 16;
+    } else if (op == ORBX_QT_SELFTEST_SCAN) {
+        if (n != threads) return fail(ORBX_E_ARG, "the scan takes one value per thread");
+        in_bytes = (size_t)n * 8; out_bytes = in_bytes + 8;
+    } else return fail(ORBX_E_ARG, "no such self-test %d", op);
+    rt::set_device(h->device);
+    if (smem + 2048 > rt::lds_limit(h->device)) return fail(ORBX_E_CAPACITY, "%d keys need %zu bytes of LDS, the device allows %zu", n, smem + 2048, rt::lds_limit(h->device));
+    orbx::DevBuf<uint8_t> d;
+    const size_t off_out = align_up(in_bytes + 8, 256), off_pool = off_out + align_up(out_bytes + 8, 256);
+    if (d.ensure(off_pool + pool_bytes + 256)) return fail(ORBX_E_DEVICE, "allocation failed");
+    // (the partition's destination arrives filled: what lies outside the span has to come back as it went in)
+    int e = in_bytes ? rt::copy_h2d(d.p, in, in_bytes, h->s0) : 0;
+    if (op == ORBX_QT_SELFTEST_PARTITION4) e |= rt::copy_h2d(d.p + off_out, out, in_bytes, h->s0);
+    ORBX_LAUNCH(k_quadtree_selftest, dim3(1, 1, 1), dim3(threads, 1, 1), smem, h->s0, op, spill, (const void*)d.p, (void*)(d.p + off_out), d.p + off_pool, n, start, total, mx, my);
+    if (out_bytes) e |= rt::copy_d2h(out, d.p + off_out, out_bytes, h->s0);
+    if (e || rt::stream_sync(h->s0) || rt::check_launch()) { d.release(); return fail(ORBX_E_DEVICE, "self-test failed: %s", rt::last_error()); }
+    d.release();
+    return ORBX_OK;
+}
+
 int orbx_debug_live_resources(long long out[4]) {
     if (!out) return fail(ORBX_E_ARG, "null out");
     const rt::Live& l = rt::live();

@@ -77,6 +77,12 @@ __global__ void k_quadtree_spill(const LevelInfo* __restrict__ lv, const CellInf
                            int nlevels, int node_cap, int nb_cap, int lut_x, int lut_y, int* __restrict__ status, long long* __restrict__ qt_prof,
                            int wide, int counter_bytes, unsigned char* __restrict__ pool, size_t pool_stride);
 constexpr int kQuadtreeLdsNodes = 4000;     // the LDS form packs positions of its sort ranges in 12 bits: trees with more nodes take the pool form whatever the LDS
+// self-test of the quadtree's workgroup primitives (orbx_debug_quadtree_selftest; k_quadtree.hip): one workgroup of 256 or 1024 threads.
+// The sort's arrays: two range lists of quadtree_selftest_seg_cap(n) entries (4 bytes in the LDS form, 8 in the pool form), two arrays of n keys, n flag bytes.
+ORBX_HD constexpr int quadtree_selftest_seg_cap(int n) { return (n / 8 + 8 + 1) & ~1; }
+ORBX_HD constexpr size_t quadtree_selftest_sort_bytes(int n, bool spill) { return (size_t)quadtree_selftest_seg_cap(n) * 2 * (spill ? 8 : 4) + (size_t)n * 17 + 16; }
+__global__ void k_quadtree_selftest(int op, int spill, const void* __restrict__ in, void* __restrict__ out, unsigned char* __restrict__ pool,
+                                    int n, int s, int total, int mx, int my);
 __global__ void k_layout(const LevelInfo* __restrict__ lv, int nlevels, const uint32_t* __restrict__ lvl_keys,
                          int kp_total_cap, const int* __restrict__ lvl_count, int lap0, int lap1,
                          int* __restrict__ final_idx, int* __restrict__ n_out, int* __restrict__ mono_out,

@@ -230,6 +230,32 @@ class ORBextractor:
         """Number of pyramid levels whose quadtree the last extraction ran in the pool form (orbx_debug_quadtree_pool_levels)."""
         return int(self._lib.L.orbx_debug_quadtree_pool_levels(self._h))
 
+    def debug_quadtree_sort(self, keys, spill, threads):
+        """Test hook: the quadtree kernel's model of std::sort (comparator on key >> 16) applied to 64-bit keys by one workgroup of `threads`
+        threads, in the LDS form (spill = 0, up to 4095 keys) or the node-pool form (spill = 1, up to 65535) (orbx_debug_quadtree_selftest)."""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        out = np.zeros(max(len(keys), 1), np.uint64)
+        self._lib.check(self._lib.L.orbx_debug_quadtree_selftest(self._h, 0, int(spill), int(threads), keys.ctypes.data if len(keys) else out.ctypes.data,
+                                                                 len(keys), 0, 0, 0, 0, out.ctypes.data))
+        return out[:len(keys)]
+
+    def debug_quadtree_partition4(self, src, dst, start, count, mx, my, threads):
+        """Test hook: the workgroup's stable 4-way partition of src[start : start + count] into the same span of a copy of dst (children n1|n2|n3|n4,
+        left = x < mx, top = y < my).  Returns (the destination buffer, the four counts)."""
+        src = np.ascontiguousarray(src, np.uint32)
+        out = np.concatenate([np.ascontiguousarray(dst, np.uint32), np.zeros(4, np.uint32)])
+        assert len(out) == len(src) + 4
+        self._lib.check(self._lib.L.orbx_debug_quadtree_selftest(self._h, 1, 0, int(threads), src.ctypes.data, int(count), int(start), len(src), int(mx), int(my),
+                                                                 out.ctypes.data))
+        return out[:-4], out[-4:].astype(np.int64)
+
+    def debug_quadtree_scan(self, values):
+        """Test hook: the workgroup's exclusive 64-bit prefix sum over len(values) (256 or 1024) threads.  Returns (prefix per thread, total)."""
+        values = np.ascontiguousarray(values, np.uint64)
+        out = np.zeros(len(values) + 1, np.uint64)
+        self._lib.check(self._lib.L.orbx_debug_quadtree_selftest(self._h, 2, 0, len(values), values.ctypes.data, len(values), 0, 0, 0, 0, out.ctypes.data))
+        return out[:-1], int(out[-1])
+
     def graph_replay(self, on=True):
         """Replay the extraction pipeline as one hipGraph (small-batch latency)."""
         self._lib.check(self._lib.L.orbx_set_graph_replay(self._h, int(on)))

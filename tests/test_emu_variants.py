@@ -54,6 +54,14 @@ def test_quadtree_path_mix(tmp_path, presort_max, bigspan, wave_sort_range, big_
         got = ORBextractor(nf, 1.2, 8, 20, 7, lib=lib)(img, None, lap)
         exp = ol.OracleExtractor(nf).extract(img, lap)
         assert got[0] == exp[0] and ol.kps_equal(got[1], exp[1]) and np.array_equal(got[2], exp[2]), name
+        if bigspan == 80:
+            # the same with every level in the node-pool form: quadtree_tree<true> then runs the whole-workgroup partition of the big spans
+            # (its kDeepBig passes, in the full passes and in the final rounds), which the production threshold of 1024 keys keeps out of small images
+            ex = ORBextractor(nf, 1.2, 8, 20, 7, lib=lib)
+            ex.debug_quadtree_lds_nodes(0)
+            got = ex(img, None, lap)
+            assert ex.debug_quadtree_pool_levels() > 0, name
+            assert got[0] == exp[0] and ol.kps_equal(got[1], exp[1]) and np.array_equal(got[2], exp[2]), name + " (node-pool form)"
 
 
 @pytest.mark.parametrize("cap", [200, 600])

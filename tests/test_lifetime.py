@@ -62,6 +62,10 @@ def exercise(lib, big):
     ex.fetch_undistorted()
     prof = (C.c_longlong * 16)()
     lib.L.orbx_debug_quadtree_profile(ex._h, prof)
+    for spill in (0, 1):                                  # the quadtree self-test: a buffer of its own per call, LDS form and pool form
+        ex.debug_quadtree_sort(np.arange(300, dtype=np.uint64)[::-1] << np.uint64(32), spill, 256)
+    ex.debug_quadtree_partition4(np.arange(200, dtype=np.uint32), np.zeros(200, np.uint32), 10, 150, 100, 0, 1024)
+    ex.debug_quadtree_scan(np.ones(256, np.uint64))
     ex.profile(False)
     ex.set_undistort(None)
     M.ORBmatcher.DescriptorDistance(ex, r[0][2][:50], r[1][2][:70])
@@ -105,6 +109,8 @@ def test_failed_calls_hold_nothing(emu_lib):
     kf = C.c_void_p()
     assert lib.L.orbm_keyframe_create(ex._h, None, C.byref(kf)) != 0
     assert lib.L.orbm_points_create(ex._h, None, C.byref(kf)) != 0
+    eight = np.zeros(8, np.uint64)
+    assert lib.L.orbx_debug_quadtree_selftest(ex._h, 0, 0, 256, eight.ctypes.data, 5000, 0, 0, 0, 0, eight.ctypes.data) != 0      # too many keys for the LDS form
     ex.close()
     assert live(lib) == before and mid != before
 
