@@ -755,6 +755,227 @@ public:
         return merged;
     }
 
+    // ---- one point set into MANY key frames: the forward loops of LocalMapping::SearchInNeighbors and LoopClosing::SearchAndFuse in one call ----
+    // The candidate search of a (point, key frame) pair reads nothing that the map surgery between two key frames changes - with one exception, handled
+    // below - so the searches of all key frames run in one orbm_fuse_candidates_batch over device-resident key frames (ImplicitCache) and ONE upload of the
+    // point set; the surgery is then replayed key frame by key frame in vpKFs order and point by point, with the reference's tests (NULL, isBad,
+    // IsInKeyFrame, the point that sits at the keypoint) read at that moment - the body of the loops above.  The exception: MapPoint::Replace ends with
+    // ComputeDistinctiveDescriptors on the surviving point (src/MapPoint.cc:316), so a point of the set that absorbs another one may carry a new descriptor
+    // into the key frames behind; such points are searched again, for those key frames only, before the replay goes on.
+    // The device evaluates MapPoint::PredictScale itself and needs mfMinDistance / mfMaxDistance for it, which the reference's MapPoint keeps protected
+    // (GetMaxDistanceInvariance() = 1.2f * mfMaxDistance cannot be inverted to the bit): give this class access - `friend class ORBmatcher;` in MapPoint.h -
+    // or make the two members public.  Where they cannot be read, and for key frames of a two-camera rig, the calls below run the single-key-frame
+    // overloads one after the other: the same results, without the saving.
+
+    // for (pKFi : vpKFs) { Fuse(pKFi, vpMapPoints, th); if (pKFi->NLeft != -1) Fuse(pKFi, vpMapPoints, true); }   (src/LocalMapping.cc:991-1001)
+    // Returns what those calls return, per key frame (a rig key frame: the sum of its two).
+    template <class KeyFrameT, class MapPointT>
+    std::vector<int> Fuse(const std::vector<KeyFrameT*>& vpKFs, const std::vector<MapPointT*>& vpMapPoints, const float th = 3.0)
+    {
+        const int K = (int)vpKFs.size(), M = (int)vpMapPoints.size();
+        std::vector<int> counts(K, 0);
+        FuseBatch<KeyFrameT, MapPointT> job(vpMapPoints, th, /*chi2*/ true);
+        const bool batched = K > 0 && M > 0 && job.ReadPoints();
+        auto excluded = [&](KeyFrameT* pKF, int i) { MapPointT* p = vpMapPoints[i]; return !p || p->isBad() || p->IsInKeyFrame(pKF); };
+        if (batched) {
+            for (int k = 0; k < K; k++) {
+                KeyFrameT* pKF = vpKFs[k];
+                if (pKF->NLeft != -1) continue;
+                OrbmProjection spec = Spec(pKF->GetPose(), pKF->mpCamera, *pKF, /*IsInImage*/ 1);
+                SpecCentre(spec, pKF->GetCameraCenter());
+                spec.depth_test = 1; spec.distance_test = 1; spec.angle_test = 1; spec.bf = pKF->mbf;
+                job.Add(k, pKF, spec);
+            }
+            job.Search(0, excluded);
+        }
+        for (int k = 0; k < K; k++) {
+            KeyFrameT* pKF = vpKFs[k];
+            const int row = batched ? job.RowOf(k) : -1;
+            if (row < 0) {
+                counts[k] = Fuse(pKF, vpMapPoints, th);
+                // (the call site's own words: its third argument is `th`, so this is a second pass over camera 1 with th = 1 - bRight stays false)
+                if (pKF->NLeft != -1) counts[k] += Fuse(pKF, vpMapPoints, true);
+                if (batched) job.NoteChangedDescriptors();
+                continue;
+            }
+            job.Refresh(row, excluded);
+            const int* best = job.Best(row);
+            for (int i = 0; i < M; i++) {                   // :1494-1520, as in the single call
+                MapPointT* incoming = vpMapPoints[i];
+                if (!incoming || best[i] < 0 || incoming->isBad() || incoming->IsInKeyFrame(pKF)) continue;
+                MapPointT* resident = Attach(pKF, incoming, best[i]);
+                if (resident && !resident->isBad()) {
+                    MapPointT* keep = resident->Observations() > incoming->Observations() ? resident : incoming;
+                    (keep == resident ? incoming : resident)->Replace(keep);
+                    job.NoteChangedDescriptorOf(keep);       // (either of the two may be a point of the set)
+                }
+                counts[k]++;
+            }
+        }
+        return counts;
+    }
+
+    // for (k) { vpReplacePoint.assign(M, NULL); Fuse(vpKFs[k], vScw[k], vpPoints, th, vpReplacePoint); f(k, vpReplacePoint); }   (src/LoopClosing.cc:2712-2745,
+    // :2769-2800: f is what the caller does with vpReplacePoint under the map mutex - pRep->Replace(vpPoints[i]) - before the next key frame is searched)
+    template <class KeyFrameT, class Sim3Vec, class MapPointT, class AfterKeyFrame>
+    std::vector<int> Fuse(const std::vector<KeyFrameT*>& vpKFs, const Sim3Vec& vScw, const std::vector<MapPointT*>& vpPoints, float th, AfterKeyFrame f)
+    {
+        const int K = (int)vpKFs.size(), M = (int)vpPoints.size();
+        std::vector<int> counts(K, 0);
+        typedef Decay<decltype(vpKFs[0]->GetPose())> SE3T;
+        FuseBatch<KeyFrameT, MapPointT> job(vpPoints, th, /*chi2*/ false);
+        const bool batched = K > 0 && M > 0 && job.ReadPoints();
+        auto excluded = [&](KeyFrameT* pKF, int i) { return vpPoints[i]->isBad() || job.Holds(pKF, vpPoints[i]); };
+        if (batched) {
+            for (int k = 0; k < K; k++) {
+                KeyFrameT* pKF = vpKFs[k];
+                if (pKF->NLeft != -1) continue;
+                const SE3T pose = RigidPart<SE3T>(vScw[k]);
+                OrbmProjection spec = Spec(pose, pKF->mpCamera, *pKF, /*IsInImage*/ 1);
+                SpecCentre(spec, pose.inverse().translation());
+                spec.depth_test = 1; spec.distance_test = 1; spec.angle_test = 1;
+                job.Add(k, pKF, spec);
+            }
+            job.Search(0, excluded);
+        }
+        std::vector<MapPointT*> vpReplacePoint;
+        for (int k = 0; k < K; k++) {
+            KeyFrameT* pKF = vpKFs[k];
+            vpReplacePoint.assign(M, static_cast<MapPointT*>(NULL));
+            const int row = batched ? job.RowOf(k) : -1;
+            if (row < 0) {
+                auto Scw = vScw[k];
+                counts[k] = Fuse(pKF, Scw, vpPoints, th, vpReplacePoint);
+            } else {
+                job.Refresh(row, excluded);
+                const int* best = job.Best(row);
+                const std::set<MapPointT*> inKeyFrame = pKF->GetMapPoints();       // at THIS moment: the hooks of the key frames before may have put points here
+                for (int i = 0; i < M; i++) {               // :1640-1656, as in the single call
+                    if (best[i] < 0 || vpPoints[i]->isBad() || inKeyFrame.count(vpPoints[i])) continue;
+                    MapPointT* resident = Attach(pKF, vpPoints[i], best[i]);
+                    if (resident && !resident->isBad()) vpReplacePoint[i] = resident;
+                    counts[k]++;
+                }
+            }
+            f(k, vpReplacePoint);
+            // (what the hook may have changed of the set: the descriptor of a point that took another one's observations)
+            if (batched) for (int i = 0; i < M; i++) if (vpReplacePoint[i] && !vpPoints[i]->isBad()) job.NoteChangedDescriptorOf(vpPoints[i]);
+        }
+        return counts;
+    }
+
+protected:
+    // mfMinDistance / mfMaxDistance of a map point, where this class may read them
+    template <class P> static auto DistanceLimits(P* p, float& mn, float& mx, int) -> decltype((void)(p->mfMinDistance), (void)(p->mfMaxDistance), bool())
+    {
+        mn = p->mfMinDistance; mx = p->mfMaxDistance;
+        return true;
+    }
+    template <class P> static bool DistanceLimits(P*, float&, float&, long) { return false; }
+
+    // The device side of the two calls above: the point set on the host (as uploaded), the batched key frames with their projections, best_idx per (row, point).
+    template <class KeyFrameT, class MapPointT>
+    class FuseBatch
+    {
+    public:
+        FuseBatch(const std::vector<MapPointT*>& pts, float th_, bool chi2_) : points(pts), M((int)pts.size()), th(th_), chi2(chi2_) {}
+        ~FuseBatch() { for (size_t i = 0; i < owned.size(); i++) orbm_keyframe_destroy(owned[i]); }
+        // position, normal, distance limits and descriptor of every point (NULL entries stay zero: they are excluded everywhere); false = limits unreadable
+        bool ReadPoints()
+        {
+            const size_t M1 = M > 0 ? M : 1;
+            pos.assign(3 * M1, 0.f); normal.assign(3 * M1, 0.f); mind.assign(M1, 0.f); maxd.assign(M1, 0.f); desc.assign(32 * M1, 0);
+            for (int i = 0; i < M; i++) {
+                MapPointT* p = points[i];
+                if (!p) continue;
+                if (!DistanceLimits(p, mind[i], maxd[i], 0)) return false;
+                const auto w = p->GetWorldPos(); const auto n = p->GetNormal();
+                for (int c = 0; c < 3; c++) { pos[3 * (size_t)i + c] = w(c); normal[3 * (size_t)i + c] = n(c); }
+                CopyDescriptor(p, &desc[32 * (size_t)i]);
+                where.insert(std::make_pair(p, i));
+            }
+            return true;
+        }
+        // key frame k of the call becomes the next row.  It is served by the thread's ImplicitCache; one whose mFeatVec is still empty is not cached there
+        // (ResidentKeyFrames::Get) and is uploaded for this call alone
+        void Add(int k, KeyFrameT* pKF, const OrbmProjection& spec)
+        {
+            ResidentKeyFrames<KeyFrameT>& cache = ImplicitCache<KeyFrameT>();
+            if (kfs.empty()) cache.Trim();
+            orbm_keyframe* dev = nullptr;
+            if (pKF->N > 0 && pKF->mFeatVec.empty()) {
+                BowStore b; FillBow(*pKF, pKF->N, b);
+                Check(orbm_keyframe_create(SharedHandle(), &b.v, &dev));
+                owned.push_back(dev);
+            } else dev = cache.Get(pKF);
+            if ((int)rowOf.size() <= k) rowOf.resize(k + 1, -1);
+            rowOf[k] = (int)kfs.size();
+            kfs.push_back(pKF);
+            OrbmFuseTarget t; memset(&t, 0, sizeof t);
+            t.kf = dev; t.spec = spec; t.log_scale_factor = pKF->mfLogScaleFactor; t.inv_level_sigma2 = chi2 ? pKF->mvInvLevelSigma2.data() : nullptr;
+            targets.push_back(t);
+        }
+        int RowOf(int k) const { return k < (int)rowOf.size() ? rowOf[k] : -1; }
+        const int* Best(int row) const { return &best[(size_t)row * M]; }
+        // the map points of a key frame at the moment of the question (the Sim3 overload's spAlreadyFound, :1563)
+        bool Holds(KeyFrameT* pKF, MapPointT* p) { if (pKF != heldOf) { held = pKF->GetMapPoints(); heldOf = pKF; } return held.count(p) != 0; }
+        // rows [first, end) x every point: one upload of the set, one orbm_fuse_candidates_batch
+        template <class Excluded> void Search(int first, const Excluded& excluded)
+        {
+            best.assign(kfs.size() * (size_t)(M > 0 ? M : 1), -1);
+            std::vector<int> all(M);
+            for (int i = 0; i < M; i++) all[i] = i;
+            Run(first, all, excluded);
+        }
+        void NoteChangedDescriptor(int i)
+        {
+            uint8_t now[32];
+            CopyDescriptor(points[i], now);
+            if (memcmp(now, &desc[32 * (size_t)i], 32)) { memcpy(&desc[32 * (size_t)i], now, 32); stale.push_back(i); }
+        }
+        // p has come out of a Replace as the survivor: wherever it stands in the set (a point may be listed more than once), its descriptor may be a new one
+        void NoteChangedDescriptorOf(MapPointT* p) { const auto range = where.equal_range(p); for (auto it = range.first; it != range.second; ++it) NoteChangedDescriptor(it->second); }
+        void NoteChangedDescriptors() { for (int i = 0; i < M; i++) if (points[i] && !points[i]->isBad()) NoteChangedDescriptor(i); }
+        // before the replay of `row`: the points whose descriptor has changed since they were searched are searched again in the rows from here on
+        template <class Excluded> void Refresh(int row, const Excluded& excluded)
+        {
+            if (stale.empty()) return;
+            std::sort(stale.begin(), stale.end());
+            stale.erase(std::unique(stale.begin(), stale.end()), stale.end());
+            Run(row, stale, excluded);
+            stale.clear();
+        }
+    private:
+        template <class Excluded> void Run(int first, const std::vector<int>& subset, const Excluded& excluded)
+        {
+            const int rows = (int)kfs.size() - first, n = (int)subset.size();
+            if (rows <= 0 || n == 0) return;
+            std::vector<float> p(3 * (size_t)n), nr(3 * (size_t)n), mn(n), mx(n); std::vector<uint8_t> d(32 * (size_t)n), skip((size_t)rows * n);
+            for (int j = 0; j < n; j++) {
+                const size_t i = (size_t)subset[j];
+                memcpy(&p[3 * (size_t)j], &pos[3 * i], 12); memcpy(&nr[3 * (size_t)j], &normal[3 * i], 12); mn[j] = mind[i]; mx[j] = maxd[i];
+                memcpy(&d[32 * (size_t)j], &desc[32 * i], 32);
+            }
+            heldOf = nullptr;
+            for (int r = 0; r < rows; r++) for (int j = 0; j < n; j++) skip[(size_t)r * n + j] = excluded(kfs[first + r], subset[j]) ? 1 : 0;
+            heldOf = nullptr;
+            OrbmWorldPointView view = {n, p.data(), nr.data(), mn.data(), mx.data(), nullptr, nullptr, d.data()};
+            orbm_points* set = nullptr;
+            Check(orbm_points_create(SharedHandle(), &view, &set));
+            std::vector<int> out((size_t)rows * n, -1);
+            const int rc = orbm_fuse_candidates_batch(SharedHandle(), rows, &targets[first], set, skip.data(), th, chi2 ? 1 : 0, out.data(), nullptr);
+            orbm_points_destroy(set);
+            Check(rc);
+            for (int r = 0; r < rows; r++) for (int j = 0; j < n; j++) best[(size_t)(first + r) * M + subset[j]] = out[(size_t)r * n + j];
+        }
+        const std::vector<MapPointT*>& points; int M; float th; bool chi2;
+        std::vector<float> pos, normal, mind, maxd; std::vector<uint8_t> desc;
+        std::vector<KeyFrameT*> kfs; std::vector<int> rowOf; std::vector<OrbmFuseTarget> targets; std::vector<orbm_keyframe*> owned;
+        std::vector<int> best, stale;
+        std::set<MapPointT*> held; KeyFrameT* heldOf = nullptr;
+        std::multimap<MapPointT*, int> where;
+    };
+
 public:
     // One library handle (HIP streams + device scratch) per calling THREAD: the reference's matchers are stateless and are called
     // concurrently from the Tracking, LocalMapping and LoopClosing threads; with a handle of its own each of them runs

@@ -750,6 +750,35 @@ int orbm_search_by_bow_resident(orbx_extractor* h, int n, orbm_keyframe* const* 
                                 const uint8_t* const* eligible2, float nnratio, int th_inclusive, int check_orientation, int* const* matches12,
                                 int* nmatches);
 
+/* The candidate search of ORBmatcher::Fuse for ONE resident point set against K resident key frames in one launch chain: LocalMapping::SearchInNeighbors
+ * fuses the current key frame's map points into each of its 20-60 neighbours (src/LocalMapping.cc:999-1040), LoopClosing::SearchAndFuse the loop map points
+ * into every key frame of the corrected map (src/LoopClosing.cc:2700-2765).  The search of a (point, key frame) pair reads nothing that the map surgery
+ * between two key frames changes - the point's position, normal, distance limits and descriptor, the key frame's pose, camera, keypoints and mvuRight - so
+ * all K x M searches run at once; what the surgery does change (isBad, IsInKeyFrame, the key frame's map points) the caller tests when it replays the results,
+ * key frame by key frame and point by point, as for the single call.  Target k: `kf` = the resident keypoints / descriptors / mvuRight of ONE camera (for a
+ * camera of a rig: a resident key frame made from that camera's keypoints and descriptor rows; add NLeft to the right camera's indices), `spec` = exactly what
+ * orbm_project_points takes for Fuse (pose, Ow, camera, bounds, tests, bf), log_scale_factor = pKF->mfLogScaleFactor, inv_level_sigma2 = pKF->mvInvLevelSigma2
+ * (as many levels as kf has; read with chi2_gate only).  The device applies the 0.8 / 1.2 of Get*DistanceInvariance to the set's mfMinDistance / mfMaxDistance and
+ * evaluates MapPoint::PredictScale(dist3D, pKF) itself (glibc's logf, float division, ceil, the clamps), with the scale factors and level count of `kf`.  The grid
+ * of a key frame is built from the spec's bounds (src/Frame.cc:190-191) on its first use and kept inside the orbm_keyframe, keyed by those bounds, until
+ * orbm_keyframe_destroy: a covisibility window that comes back pays for it once.
+ * skip: [K][M] bytes, pairs the caller already excludes (NULL = none).  chi2_gate = 1: Fuse(pKF, vpMapPoints, th, bRight); 0: Fuse(pKF, Scw, vpPoints, th, ..).
+ * best_idx[k][i] / best_dist[k][i] (best_dist may be NULL): as orbm_fuse_candidates gives them for target k - the feature the reference would fuse point i with
+ * and its distance, -1 where the pair is skipped, the geometry rejects it or bestDist > TH_LOW; a target without keypoints gives a row of -1.  Blocking.
+ * K == 0 or an empty set: ORBX_OK, nothing is written.  Refused before anything is enqueued (ORBX_E_ARG, the message names the target): null arguments,
+ * K < 0, a key frame or the point set on another device than the handle, chi2_gate without inv_level_sigma2, a key frame without scale levels.
+ * Limits: K <= 65535 and K x M <= 2^28 pairs (ORBX_E_CAPACITY beyond; nothing is truncated).
+ * (declared apart from its typedef like OrbmFrameMap; the Python mirror is checked by tests/test_fuse_batch.py) */
+struct OrbmFuseTarget {
+    const orbm_keyframe* kf;
+    OrbmProjection spec;
+    float log_scale_factor;
+    const float* inv_level_sigma2;
+};
+typedef struct OrbmFuseTarget OrbmFuseTarget;  /* ONE key frame (one camera) a point set is fused into */
+int orbm_fuse_candidates_batch(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const orbm_points* points, const uint8_t* skip /* [K][M] or NULL */,
+                               float th, int chi2_gate, int* best_idx /* [K][M] */, int* best_dist /* [K][M] or NULL */);
+
 /* SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) for a fisheye-rig frame (F.Nleft != -1; src/ORBmatcher.cc:259-493 incl. :343-372, :414-446).
  * K1 / K2 list ALL features by index (camera 1 first: keys = mvKeys followed by mvKeysRight, descriptor rows as stored); nleft2 = F.Nleft.
  * assigned2[j] = feature of K1 whose map point is written to vpMapPointMatches[j], -1 = NULL (after the rotation-consistency pruning). */

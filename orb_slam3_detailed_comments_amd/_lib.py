@@ -33,7 +33,7 @@ SYMBOLS = [
     "orbm_project_points", "orbm_search_by_projection_sim3", "orbm_search_by_projection_keyframe", "orbm_fuse_candidates", "orbm_search_by_sim3", "orbm_distinctive_descriptors",
     "orbm_search_by_projection_mappoints_fisheye", "orbm_search_by_projection_frame_fisheye", "orbm_search_for_triangulation_batch",
     "orbm_search_local_points_rig_batch", "orbm_search_by_projection_lastframe_rig_batch", "orbm_search_rig_batch_fetch",
-    "orbm_search_local_points_batch_maps", "orbm_search_local_points_rig_batch_maps", "orbm_points_count",
+    "orbm_search_local_points_batch_maps", "orbm_search_local_points_rig_batch_maps", "orbm_points_count", "orbm_fuse_candidates_batch",
     "orbv_create", "orbv_load_text", "orbv_destroy", "orbv_words", "orbv_transform", "orbv_transform_extracted", "orbv_fetch", "orbm_search_by_bow_frames_batch",
     "orbv_transform_rig_extracted", "orbm_search_by_bow_rig_batch",
     "orbv_db_create", "orbv_db_destroy", "orbv_db_add", "orbv_db_add_extracted", "orbv_db_erase", "orbv_db_erase_keys", "orbv_db_clear", "orbv_db_size",
@@ -156,6 +156,7 @@ class OrbxLib:
         L.orbm_search_local_points_batch_maps.argtypes = [vp, i, i, vp, vp, vp, i, f, f, i, f, f, i]
         L.orbm_search_local_points_rig_batch_maps.argtypes = [vp, i, vp, i, i, vp, vp, vp, f, f, i, f, f, i]
         L.orbm_points_count.argtypes = [vp]
+        L.orbm_fuse_candidates_batch.argtypes = [vp, i, vp, vp, vp, f, i, vp, vp]
         L.orbm_distinctive_descriptors.argtypes = [vp, vp, vp, i, vp]
         L.orbv_create.argtypes = [vp, i, i, i, i, i, vp, vp, vp, vp, C.POINTER(vp)]
         L.orbv_load_text.argtypes = [vp, C.c_char_p, C.POINTER(vp)]

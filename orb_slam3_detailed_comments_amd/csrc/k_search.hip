@@ -9,6 +9,8 @@
 //                  hold a MapPoint with observations", best / second-best / ratio, rotation histogram) is replayed on the
 //                  host over these lists (orbm_search.cpp), because an assignment made for one map point removes that
 //                  keypoint from the candidate set of every later one (a true sequential dependency).
+//   k_fuse_candidates  the candidate search of ORBmatcher::Fuse (src/ORBmatcher.cc:1325-1660) for one resident point set against many resident key
+//                  frames: one thread per (point, key frame), geometry, PredictScale, window walk, gates, Hamming distance and the minimum in one pass
 //   k_bow_search   inner loops of ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:1045-1323): one wave per
 //                  unmatched feature of KF1 against the features of KF2 in the same vocabulary node.
 #include "orbx_types.h"
@@ -28,14 +30,10 @@ constexpr int kGridCols = 64, kGridRows = 48;   // FRAME_GRID_COLS / FRAME_GRID_
 // kernel is a chain of dependent round trips, not work).
 // Batched form (grid = B frames of an extractor's device-resident outputs): n_per_frame != NULL gives N per frame and frame b's arrays sit at
 // kps + b * frame_stride, cell_of / cell_items + b * frame_stride, cell_start + b * kGridCellStride.
-__global__ void __launch_bounds__(kGridThreads) k_grid_build(const KeyPointRec* __restrict__ kps, int N, GridParams g,
-                                                             int* __restrict__ cell_of, int* __restrict__ cell_start,
-                                                             int* __restrict__ cell_items, const int* __restrict__ n_per_frame, int frame_stride) {
-    if (n_per_frame) {
-        const size_t b = blockIdx.x;
-        N = n_per_frame[b]; kps += b * (size_t)frame_stride; cell_of += b * (size_t)frame_stride; cell_items += b * (size_t)frame_stride;
-        cell_start += b * (size_t)kGridCellStride;
-    }
+// Table form (k_grid_build_kfs, grid = records): the grids of device-resident key frames (orbm_keyframe) - separate allocations, each with its own
+// keypoints, size, grid constants and outputs (GridBuildRec).
+__device__ __forceinline__ void grid_build_body(const KeyPointRec* __restrict__ kps, int N, const GridParams& g, int* __restrict__ cell_of,
+                                                int* __restrict__ cell_start, int* __restrict__ cell_items) {
     __shared__ int s_hist[kGridCols * kGridRows];
     __shared__ int s_chunk[256];
     __shared__ unsigned long long s_scan[20];
@@ -124,6 +122,20 @@ __global__ void __launch_bounds__(kGridThreads) k_grid_build(const KeyPointRec* 
         }
         __syncthreads();
     }
+}
+__global__ void __launch_bounds__(kGridThreads) k_grid_build(const KeyPointRec* __restrict__ kps, int N, GridParams g,
+                                                             int* __restrict__ cell_of, int* __restrict__ cell_start,
+                                                             int* __restrict__ cell_items, const int* __restrict__ n_per_frame, int frame_stride) {
+    if (n_per_frame) {
+        const size_t b = blockIdx.x;
+        N = n_per_frame[b]; kps += b * (size_t)frame_stride; cell_of += b * (size_t)frame_stride; cell_items += b * (size_t)frame_stride;
+        cell_start += b * (size_t)kGridCellStride;
+    }
+    grid_build_body(kps, N, g, cell_of, cell_start, cell_items);
+}
+__global__ void __launch_bounds__(kGridThreads) k_grid_build_kfs(const GridBuildRec* __restrict__ recs) {
+    const GridBuildRec& R = recs[blockIdx.x];                      // by reference: the record stays in global memory (scalar loads)
+    grid_build_body(R.kps, R.N, R.g, R.cell_of, R.cell_start, R.cell_items);
 }
 
 // level filter (with the reference's bCheckLevels quirk, :908), box test (:944) and right-coordinate gate
@@ -343,6 +355,45 @@ __global__ void __launch_bounds__(256) k_frustum_maps(const FrustumParams* __res
 // (Sophus' quaternion action for the transform, Eigen's a0 + (a1 + a2) for norms and dot products; no fused multiply-adds).  Which tests run and how the projection is written differ between the reference's
 // methods; P says which.  Outputs: valid, u, v, ur = u - bf / z, 1 / z, dist (the argument of MapPoint::PredictScale, which stays with the
 // caller's MapPoint).  skip[i] != 0: the caller's own tests (bad, already matched, ...) have rejected the point.
+// (the body, shared with k_fuse_candidates: point (P0, P1, P2) with normal Pn - read with the angle test only - and distance limits [min_inv, max_inv] - compared
+// with the distance test only; P by reference: the kernel argument itself or a record in global memory)
+__device__ __forceinline__ bool project_point(const ProjectParams& P, float P0, float P1, float P2, const float* __restrict__ Pn, float min_inv, float max_inv,
+                                              int debug_flags, float& u, float& v, float& ur, float& invz, float& dist) {
+    bool ok = true;
+    float pc[3];
+    if (debug_flags & 16) se3_act_matrix_form(P.q, P.t, P0, P1, P2, pc);       // test switch: round 3's R * p + t
+    else se3_act(P.q, P.t, P0, P1, P2, pc);                       // Tcw * p3Dw: Sophus' quaternion action (so3.hpp:357-367, se3.hpp:321-324)
+    if (P.second == 1) sim3_act(P.q2, P.s2, P.t2, pc[0], pc[1], pc[2], pc);       // S21 * p3Dc1 (rxso3.hpp:265-273, sim3.hpp:226-229)
+    else if (P.second == 2) se3_act(P.q2, P.t2, pc[0], pc[1], pc[2], pc);         // GetRelativePoseTrl() * x3Dc
+    const float x = pc[0], y = pc[1], z = pc[2];
+    invz = __fdiv_rn(1.0f, z);
+    if (P.depth_test == 1 && z < 0.0f) ok = false;
+    if (P.depth_test == 2 && invz < 0.0f) ok = false;
+    if (ok) {
+        if (P.camera_type == 1) { KB8Cam c; for (int k = 0; k < 8; k++) c.p[k] = P.cam[k]; const float pc[3] = {x, y, z}; float uv[2]; kb8_project(c, pc, uv); u = uv[0]; v = uv[1]; }
+        else if (P.inline_pinhole) {                              // x = X * invz; u = fx * x + cx (the hand-written form, e.g. :656-660)
+            u = __fadd_rn(__fmul_rn(P.cam[0], __fmul_rn(x, invz)), P.cam[2]);
+            v = __fadd_rn(__fmul_rn(P.cam[1], __fmul_rn(y, invz)), P.cam[3]);
+        } else {                                                  // Pinhole::project, src/CameraModels/Pinhole.cpp:61-68
+            u = __fadd_rn(__fdiv_rn(__fmul_rn(P.cam[0], x), z), P.cam[2]);
+            v = __fadd_rn(__fdiv_rn(__fmul_rn(P.cam[1], y), z), P.cam[3]);
+        }
+        if (P.bounds_mode == 0) { if (u < P.min_x || u > P.max_x || v < P.min_y || v > P.max_y) ok = false; }        // Frame: :2003-2006
+        else if (P.bounds_mode == 1 && !(u >= P.min_x && u < P.max_x && v >= P.min_y && v < P.max_y)) ok = false;      // KeyFrame::IsInImage; 2: no image test
+    }
+    if (ok) {
+        ur = __fsub_rn(u, __fmul_rn(P.bf, invz));
+        const float o0 = __fsub_rn(P0, P.Ow[0]), o1 = __fsub_rn(P1, P.Ow[1]), o2 = __fsub_rn(P2, P.Ow[2]);
+        if (P.dist_mode == 0) dist = sqrtf(eig_dot3(o0, o1, o2, o0, o1, o2));        // PO.norm(): Eigen reduction, a0 + (a1 + a2)
+        else dist = sqrtf(eig_dot3(x, y, z, x, y, z));
+        if (P.distance_test && (dist < min_inv || dist > max_inv)) ok = false;
+        if (ok && P.angle_test) {                                 // PO.dot(Pn) < 0.5 * dist3D
+            const float dot = eig_dot3(o0, o1, o2, Pn[0], Pn[1], Pn[2]);
+            if (dot < __fmul_rn(0.5f, dist)) ok = false;
+        }
+    }
+    return ok;
+}
 __global__ void __launch_bounds__(256) k_project_points(ProjectParams P, int M, const float* __restrict__ pos, const float* __restrict__ normal,
                                                         const float* __restrict__ min_inv, const float* __restrict__ max_inv, const uint8_t* __restrict__ skip,
                                                         uint8_t* __restrict__ valid, float* __restrict__ out /* [5][M]: u, v, ur, 1/z, dist */, int debug_flags) {
@@ -350,41 +401,8 @@ __global__ void __launch_bounds__(256) k_project_points(ProjectParams P, int M, 
     if (i >= M) return;
     bool ok = !(skip && skip[i]);
     float u = 0.f, v = 0.f, ur = 0.f, invz = 0.f, dist = 0.f;
-    if (ok) {
-        const float P0 = pos[3 * i], P1 = pos[3 * i + 1], P2 = pos[3 * i + 2];
-        float pc[3];
-        if (debug_flags & 16) se3_act_matrix_form(P.q, P.t, P0, P1, P2, pc);       // test switch: round 3's R * p + t
-        else se3_act(P.q, P.t, P0, P1, P2, pc);                       // Tcw * p3Dw: Sophus' quaternion action (so3.hpp:357-367, se3.hpp:321-324)
-        if (P.second == 1) sim3_act(P.q2, P.s2, P.t2, pc[0], pc[1], pc[2], pc);       // S21 * p3Dc1 (rxso3.hpp:265-273, sim3.hpp:226-229)
-        else if (P.second == 2) se3_act(P.q2, P.t2, pc[0], pc[1], pc[2], pc);         // GetRelativePoseTrl() * x3Dc
-        const float x = pc[0], y = pc[1], z = pc[2];
-        invz = __fdiv_rn(1.0f, z);
-        if (P.depth_test == 1 && z < 0.0f) ok = false;
-        if (P.depth_test == 2 && invz < 0.0f) ok = false;
-        if (ok) {
-            if (P.camera_type == 1) { KB8Cam c; for (int k = 0; k < 8; k++) c.p[k] = P.cam[k]; const float pc[3] = {x, y, z}; float uv[2]; kb8_project(c, pc, uv); u = uv[0]; v = uv[1]; }
-            else if (P.inline_pinhole) {                              // x = X * invz; u = fx * x + cx (the hand-written form, e.g. :656-660)
-                u = __fadd_rn(__fmul_rn(P.cam[0], __fmul_rn(x, invz)), P.cam[2]);
-                v = __fadd_rn(__fmul_rn(P.cam[1], __fmul_rn(y, invz)), P.cam[3]);
-            } else {                                                  // Pinhole::project, src/CameraModels/Pinhole.cpp:61-68
-                u = __fadd_rn(__fdiv_rn(__fmul_rn(P.cam[0], x), z), P.cam[2]);
-                v = __fadd_rn(__fdiv_rn(__fmul_rn(P.cam[1], y), z), P.cam[3]);
-            }
-            if (P.bounds_mode == 0) { if (u < P.min_x || u > P.max_x || v < P.min_y || v > P.max_y) ok = false; }        // Frame: :2003-2006
-            else if (P.bounds_mode == 1 && !(u >= P.min_x && u < P.max_x && v >= P.min_y && v < P.max_y)) ok = false;      // KeyFrame::IsInImage; 2: no image test
-        }
-        if (ok) {
-            ur = __fsub_rn(u, __fmul_rn(P.bf, invz));
-            const float o0 = __fsub_rn(P0, P.Ow[0]), o1 = __fsub_rn(P1, P.Ow[1]), o2 = __fsub_rn(P2, P.Ow[2]);
-            if (P.dist_mode == 0) dist = sqrtf(eig_dot3(o0, o1, o2, o0, o1, o2));        // PO.norm(): Eigen reduction, a0 + (a1 + a2)
-            else dist = sqrtf(eig_dot3(x, y, z, x, y, z));
-            if (P.distance_test && (dist < min_inv[i] || dist > max_inv[i])) ok = false;
-            if (ok && P.angle_test) {                                 // PO.dot(Pn) < 0.5 * dist3D
-                const float dot = eig_dot3(o0, o1, o2, normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]);
-                if (dot < __fmul_rn(0.5f, dist)) ok = false;
-            }
-        }
-    }
+    if (ok) ok = project_point(P, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], normal + 3 * (size_t)i, P.distance_test ? min_inv[i] : 0.0f, P.distance_test ? max_inv[i] : 0.0f,
+                               debug_flags, u, v, ur, invz, dist);
     valid[i] = ok ? 1 : 0;
     const size_t Ms = (size_t)M;
     out[i] = u; out[Ms + i] = v; out[2 * Ms + i] = ur; out[3 * Ms + i] = invz; out[4 * Ms + i] = dist;
@@ -554,6 +572,72 @@ __global__ void __launch_bounds__(256) k_area_search_threads_maps(const AreaQuer
     const size_t o = (size_t)T.offset;
     area_search_threads_body(queries + o, T.desc, T.M, kps + f, u_right + f, fdesc + 4 * f, g, cell_start + b * (size_t)kGridCellStride, cell_items + f, gate_right,
                              pool_counter, pool_cap, q_start + o, q_count + o, entries);
+}
+
+// The candidate search of ORBmatcher::Fuse (src/ORBmatcher.cc:1325-1528 with the chi-square gate, :1543-1660 without) for ONE resident point set
+// against K resident key frames (orbm_fuse_candidates_batch): one THREAD per (point, key frame), grid ((M + 255) / 256, K).  A Fuse window is 4-9
+// grid cells with a handful of keypoints (radius 3-11 px against cells of ~12 x 10 px): a wave per pair would idle 60 lanes, and nothing but the best
+// candidate leaves the thread - no candidate lists, no pool.  Both halves in one kernel: the query of a pair (32 bytes) never travels through memory,
+// and a pair rejected by the geometry costs its thread nothing further.
+//   fuse_query  the head of the reference's loop for one pair: project_point (the body of k_project_points: depth, image, distance and viewing-angle
+//               tests, ur = u - bf / z), then MapPoint::PredictScale(dist3D, pKF) (src/MapPoint.cc:688-709) as k_keyframe_queries evaluates it - glibc's
+//               logf, float division, ceil, the clamps - and the radius th * mvScaleFactors[level] (:1425-1428 / :1615-1618)
+//   fuse_best   KeyFrame::GetFeaturesInArea's window walk in the reference's order (cells ix-major, iy-minor, keypoints in insertion order), per
+//               candidate the level gate (octave < level - 1 || octave > level rejects, :1454 / :1638), the chi-square gate (chi2_accept) when the query
+//               asks for it, the Hamming distance, a strict `<` minimum - the first candidate in reference order wins a tie
+// T[k] is read by reference (blockIdx.y alone forms its address: scalar loads, no private copy of the record).
+__device__ __forceinline__ bool fuse_query(const FuseTargetRec& R, int i, const float* __restrict__ pos, const float* __restrict__ normal, const float* __restrict__ min_d,
+                                           const float* __restrict__ max_d, float th, int chi2_gate, int debug_flags, AreaQuery& A) {
+    const float maxd = max_d[i];
+    float u = 0.f, v = 0.f, ur = 0.f, invz = 0.f, dist = 0.f;
+    // GetMinDistanceInvariance() = 0.8f * mfMinDistance, GetMaxDistanceInvariance() = 1.2f * mfMaxDistance (src/MapPoint.cc:658-671)
+    if (!project_point(R.P, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], normal + 3 * (size_t)i, __fmul_rn(0.8f, min_d[i]), __fmul_rn(1.2f, maxd), debug_flags, u, v, ur,
+                       invz, dist)) return false;
+    const float ratio = __fdiv_rn(maxd, dist);
+    int n = (int)ceilf(__fdiv_rn(glibc_logf_model<false>(ratio), R.log_scale_factor));
+    if (n < 0) n = 0; else if (n >= R.nlevels) n = R.nlevels - 1;
+    A.x = u; A.y = v; A.r = __fmul_rn(th, pick(R.scale_factors, n)); A.ur = ur;
+    A.min_level = n - 1; A.max_level = n; A.active = 1; A.gate = chi2_gate ? 2 : 0;
+    return true;
+}
+__device__ __forceinline__ void fuse_best(const FuseTargetRec& R, const AreaQuery& A, const unsigned long long* __restrict__ dq, int& best_idx, int& best_dist) {
+    const GridParams& g = R.g;
+    const int nMinX = imax(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(A.x, g.min_x), A.r), g.gw_inv)));
+    const int nMaxX = imin(kGridCols - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(A.x, g.min_x), A.r), g.gw_inv)));
+    const int nMinY = imax(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(A.y, g.min_y), A.r), g.gh_inv)));
+    const int nMaxY = imin(kGridRows - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(A.y, g.min_y), A.r), g.gh_inv)));
+    if (nMinX >= kGridCols || nMaxX < 0 || nMinY >= kGridRows || nMaxY < 0 || nMaxX < nMinX || nMaxY < nMinY) return;
+    const unsigned long long d0 = dq[0], d1 = dq[1], d2 = dq[2], d3 = dq[3];
+    for (int ix = nMinX; ix <= nMaxX; ix++) {
+        const int s = R.cell_start[ix * kGridRows + nMinY], e = R.cell_start[ix * kGridRows + nMaxY + 1];        // the cells of one column are consecutive
+        for (int j = s; j < e; j++) {
+            const int idx = R.cell_items[j];
+            const KeyPointRec k = R.kps[idx];
+            if (!area_accept(A, k, idx, true, 0, nullptr)) continue;
+            if (A.gate == 2 && !chi2_accept(A, k, R.ur[idx], g)) continue;
+            const unsigned long long* df = R.desc + 4 * (size_t)idx;
+            const int dist = __popcll(d0 ^ df[0]) + __popcll(d1 ^ df[1]) + __popcll(d2 ^ df[2]) + __popcll(d3 ^ df[3]);
+            if (dist < best_dist) { best_dist = dist; best_idx = idx; }
+        }
+    }
+}
+// skip: [K][M] bytes or NULL (pairs the caller excludes); best_idx / best_dist: [K][M], -1 where the reference would not fuse (best_dist may be NULL)
+__global__ void __launch_bounds__(256) k_fuse_candidates(const FuseTargetRec* __restrict__ T, int M, const float* __restrict__ pos, const float* __restrict__ normal,
+                                                         const float* __restrict__ min_d, const float* __restrict__ max_d, const unsigned long long* __restrict__ qdesc,
+                                                         const uint8_t* __restrict__ skip, float th, int chi2_gate, int th_low, int debug_flags,
+                                                         int* __restrict__ best_idx, int* __restrict__ best_dist) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= M) return;
+    const FuseTargetRec& R = T[blockIdx.y];
+    const size_t o = (size_t)blockIdx.y * (size_t)M + (size_t)i;
+    int bi = -1, bd = 256;                                            // bestDist = 256 (:1443; INT_MAX at :1630 - either is above TH_LOW)
+    if (R.N > 0 && !(skip && skip[o])) {
+        AreaQuery A;
+        if (fuse_query(R, i, pos, normal, min_d, max_d, th, chi2_gate, debug_flags, A)) fuse_best(R, A, qdesc + 4 * (size_t)i, bi, bd);
+    }
+    if (bd > th_low) bi = -1;                                         // bestDist <= TH_LOW (:1505 / :1654)
+    best_idx[o] = bi;
+    if (best_dist) best_dist[o] = bi >= 0 ? bd : -1;
 }
 
 // ORBmatcher::SearchByProjection(Frame, MapPoints) accept loop (src/ORBmatcher.cc:62-166) on the device, one wave per frame of a batch.

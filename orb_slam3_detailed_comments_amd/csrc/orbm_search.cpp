@@ -7,10 +7,12 @@
 //   single-frame searches   GetFeaturesInArea, SearchByProjection(Frame, MapPoints), isInFrustum (one camera and rig), SearchLocalPoints,
 //                           SearchByProjection(Frame, Frame), SearchForTriangulation, SearchByBoW, SearchForInitialization, the projected-point searches
 //                           (Sim3, key frame, Fuse, SearchBySim3), DistinctiveDescriptors, the two-camera (fisheye) forms
-//   resident objects        orbm_points (map points), orbm_keyframe (key frames) and the searches that read them
+//   resident objects        orbm_points (map points), orbm_keyframe (key frames, with the grids the Fuse batch builds for them) and the searches that read them;
+//                           orbm_fuse_candidates_batch (one point set against many key frames) stands with the single Fuse search
 //   batched routes          frames of the last extraction: SearchLocalPoints, SearchByProjection(last frame / key frame), SearchByBoW; one fetch
 //   rig routes              the same for two-camera frames (two handles), fetched through the same core
 // The line numbers in the comments point into the reference's src/ORBmatcher.cc unless another file is named.
+#include <mutex>
 #include "orbx_internal.h"
 
 using namespace orbx;
@@ -1183,13 +1185,20 @@ int orbm_search_by_bow_batch(orbx_extractor* h, int n, const OrbmKeyFrameView* c
 // What the vocabulary-bucket searches read of a key frame (keys, descriptors, mvuRight, mFeatVec) is uploaded once; the searches then move
 // only their call-time state (map point flags, poses) to the device and their result back.  The host keeps the angles for the
 // rotation-consistency histograms and the per-level scales.
+// The bucket grid of a resident key frame (Frame::AssignFeaturesToGrid) for one set of image bounds, built on the first orbm_fuse_candidates_batch that asks for
+// it and kept with the key frame: mem = cell_start [kGridCellStride] | cell_items [N + 1] | cell_of [N + 1].  users: calls in flight that read it (a grid in use
+// is never dropped); built: the kernel that fills it has run (an entry whose call failed before that is dropped by the next lookup).  Key frames are shared
+// between the handles - and threads - of a device, so the lists are only touched under kf_grid_mutex().
+struct KfGrid { float key[4]; int* mem; int users; bool built; };
 struct orbm_keyframe {
     int device = 0, N = 0, fv_nodes = 0, nlevels = 0;
     uint8_t* dmem = nullptr;
     ResidentKF dev;
     std::vector<float> angle;
     float scale[kMaxLevels], sigma2[kMaxLevels];
+    std::vector<KfGrid*> grids;
 };
+static std::mutex& kf_grid_mutex() { static std::mutex m; return m; }
 
 int orbm_keyframe_create(orbx_extractor* h, const OrbmKeyFrameView* K, orbm_keyframe** out) {
     if (!h || !K || !out || K->N < 0 || K->fv_nodes < 0 || (K->N > 0 && (!K->keys_un || !K->desc))) return fail(ORBX_E_ARG, "bad key frame view");
@@ -1236,6 +1245,7 @@ void orbm_keyframe_destroy(orbm_keyframe* kf) {
     if (!kf) return;
     rt::set_device(kf->device);
     rt::dfree(kf->dmem);
+    for (KfGrid* g : kf->grids) { rt::dfree(g->mem); delete g; }
     delete kf;
 }
 
@@ -1738,6 +1748,111 @@ int orbm_fuse_candidates(orbx_extractor* h, const OrbmFrameView* KF, const OrbmP
         best_idx[i] = bestIdx;
         if (best_dist) best_dist[i] = bestIdx >= 0 ? b.dist : -1;
     }
+    return ORBX_OK;
+}
+
+// Fuse's candidate search for one resident point set against K resident key frames.  One upload (the records of the grids to build, the target table, the
+// skip mask), at most two launches (k_grid_build_kfs for the key frames that have no grid for their target's bounds yet, k_fuse_candidates), one download.
+namespace {
+const int kKfGridsKept = 2;             // grids a key frame keeps between calls (a key frame is normally searched with one set of bounds)
+// the grids one call reads: found or made under the mutex, released when the call ends - whichever way
+struct KfGridUse {
+    std::vector<KfGrid*> held;
+    ~KfGridUse() { if (held.empty()) return; std::lock_guard<std::mutex> lk(kf_grid_mutex()); for (KfGrid* g : held) g->users--; }
+};
+// (caller holds the mutex) the grid of kf for `key`; *fresh = it has just been allocated and is still to be built
+KfGrid* kf_grid_for(orbm_keyframe* kf, const float key[4], bool* fresh) {
+    *fresh = false;
+    // (an entry in use that is not built yet was made for an earlier target of THIS call: nobody else gets in while a call that builds holds the mutex)
+    for (KfGrid* g : kf->grids) if ((g->built || g->users > 0) && !memcmp(g->key, key, sizeof g->key)) return g;
+    const bool full = (int)kf->grids.size() >= kKfGridsKept;        // other bounds than before: drop what no call is reading
+    for (size_t i = 0; i < kf->grids.size();) {
+        KfGrid* g = kf->grids[i];
+        if (g->users == 0 && (full || !g->built)) { rt::dfree(g->mem); delete g; kf->grids.erase(kf->grids.begin() + i); } else i++;
+    }
+    int* mem = (int*)rt::dmalloc(sizeof(int) * ((size_t)kGridCellStride + 2 * ((size_t)kf->N + 1)));
+    if (!mem) return nullptr;
+    KfGrid* g = new KfGrid();
+    memcpy(g->key, key, sizeof g->key); g->mem = mem; g->users = 0; g->built = false;
+    kf->grids.push_back(g);
+    *fresh = true;
+    return g;
+}
+}  // namespace
+
+int orbm_fuse_candidates_batch(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const orbm_points* points, const uint8_t* skip, float th, int chi2_gate,
+                               int* best_idx, int* best_dist) {
+    if (!h || !points || K < 0) return fail(ORBX_E_ARG, "null / negative number of targets");
+    if (points->device != h->device) return fail(ORBX_E_ARG, "the map points live on another device than the handle");
+    if (K == 0) return ORBX_OK;
+    if (!targets) return fail(ORBX_E_ARG, "null target table");
+    static_assert(sizeof(ProjectParams) == sizeof(OrbmProjection), "OrbmProjection and ProjectParams describe the same record");
+    for (int k = 0; k < K; k++) {
+        const OrbmFuseTarget& t = targets[k];
+        if (!t.kf) return fail(ORBX_E_ARG, "target %d: null key frame", k);
+        if (t.kf->device != h->device) return fail(ORBX_E_ARG, "target %d: its key frame lives on another device than the handle", k);
+        if (t.kf->nlevels < 1) return fail(ORBX_E_ARG, "target %d: its key frame has no scale levels", k);
+        if (chi2_gate && !t.inv_level_sigma2) return fail(ORBX_E_ARG, "target %d: chi-square gate without mvInvLevelSigma2", k);
+        if (!(t.spec.max_x > t.spec.min_x) || !(t.spec.max_y > t.spec.min_y)) return fail(ORBX_E_ARG, "target %d: empty image bounds", k);
+    }
+    const int M = points->M;
+    if (M == 0) return ORBX_OK;
+    if (!best_idx) return fail(ORBX_E_ARG, "null result array");
+    if (K > 65535 || (size_t)K * (size_t)M > ((size_t)1 << 28)) return fail(ORBX_E_CAPACITY, "%d targets x %d points: at most 65535 targets and 2^28 pairs per call", K, M);
+    rt::set_device(h->device);
+    const size_t pairs = (size_t)K * (size_t)M;
+    std::vector<FuseTargetRec> recs(K);
+    std::vector<GridBuildRec> build;
+    std::vector<KfGrid*> made;
+    KfGridUse use;
+    std::unique_lock<std::mutex> lk(kf_grid_mutex());
+    for (int k = 0; k < K; k++) {
+        const OrbmFuseTarget& t = targets[k];
+        orbm_keyframe* kf = const_cast<orbm_keyframe*>(t.kf);        // (the grid cache is the one part of a resident key frame that a search adds to)
+        FuseTargetRec& R = recs[k]; memset(&R, 0, sizeof R);
+        memcpy(&R.P, &t.spec, sizeof R.P);
+        R.g.min_x = t.spec.min_x; R.g.min_y = t.spec.min_y;
+        R.g.gw_inv = (float)kGridColsHost / (t.spec.max_x - t.spec.min_x); R.g.gh_inv = (float)kGridRowsHost / (t.spec.max_y - t.spec.min_y);      // src/Frame.cc:190-191
+        if (chi2_gate) for (int l = 0; l < kf->nlevels; l++) R.g.inv_sigma2[l] = t.inv_level_sigma2[l];
+        R.kps = kf->dev.kps; R.desc = kf->dev.desc; R.ur = kf->dev.ur;
+        R.N = kf->N; R.nlevels = kf->nlevels; R.log_scale_factor = t.log_scale_factor;
+        for (int l = 0; l < kMaxLevels; l++) R.scale_factors[l] = kf->scale[l];
+        const float key[4] = {R.g.min_x, R.g.min_y, R.g.gw_inv, R.g.gh_inv};
+        bool fresh;
+        KfGrid* G = kf_grid_for(kf, key, &fresh);
+        if (!G) return fail(ORBX_E_DEVICE, "target %d: allocation of its grid failed", k);
+        G->users++; use.held.push_back(G);
+        R.cell_start = G->mem; R.cell_items = G->mem + kGridCellStride;
+        if (fresh) { GridBuildRec b; b.kps = kf->dev.kps; b.cell_of = G->mem + kGridCellStride + kf->N + 1; b.cell_start = G->mem; b.cell_items = G->mem + kGridCellStride; b.N = kf->N; b.g = R.g; build.push_back(b); made.push_back(G); }
+    }
+    // a grid made here is built on this handle's stream: other threads may find it in the list, so they are kept out until this call has waited for the stream
+    if (build.empty()) lk.unlock();
+    Packer pk(h);
+    const size_t pb = pk.add(build.data(), sizeof(GridBuildRec) * build.size()), pt = pk.add(recs.data(), sizeof(FuseTargetRec) * recs.size()),
+                 ps = skip ? pk.add(skip, pairs) : 0;
+    const size_t nout = best_dist ? 2 * pairs : pairs;
+    if (h->d_si[SI_BEST].ensure(nout)) return fail(ORBX_E_DEVICE, "allocation failed (%d targets x %d points)", K, M);
+    if (int e = pk.flush()) return fail(ORBX_E_DEVICE, "%s", upload_error(e));
+    if (!build.empty()) {
+        const dim3 gridb((unsigned)build.size(), 1, 1), blkb(kGridThreads, 1, 1);
+        ORBX_LAUNCH(k_grid_build_kfs, gridb, blkb, 0, h->s0, pk.dev<GridBuildRec>(pb));
+    }
+    int* d_idx = h->d_si[SI_BEST].p; int* d_dist = best_dist ? d_idx + pairs : (int*)nullptr;
+    const dim3 grid((M + 255) / 256, K, 1), blk(256, 1, 1);
+    ORBX_LAUNCH(k_fuse_candidates, grid, blk, 0, h->s0, pk.dev<FuseTargetRec>(pt), M, points->pos, points->normal, points->min_d, points->max_d, points->desc,
+                skip ? pk.dev<uint8_t>(ps) : (const uint8_t*)nullptr, th, chi2_gate, TH_LOW, h->debug_stereo_flags, d_idx, d_dist);
+    // one copy into the handle's page-locked landing area (as fetch_sync), then into the caller's one or two arrays
+    const int* res = d_idx;
+    int e = 0;
+    if (!rt::memory_is_host()) {
+        e = h->h_res.ensure(sizeof(int) * nout + 64);
+        if (!e) e = rt::copy_d2h(h->h_res.p, d_idx, sizeof(int) * nout, h->s0);
+        res = (const int*)h->h_res.p;
+    }
+    if (e || rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "fuse candidate search failed: %s", rt::last_error());
+    for (KfGrid* g : made) g->built = true;                          // (still under the mutex: `made` is empty otherwise)
+    memcpy(best_idx, res, sizeof(int) * pairs);
+    if (best_dist) memcpy(best_dist, res + pairs, sizeof(int) * pairs);
     return ORBX_OK;
 }
 

@@ -133,6 +133,10 @@ constexpr int kGridThreads = 1024;     // workgroup size of k_grid_build (3 grid
 constexpr int kGridCellStride = 64 * 48 + 2;   // ints per frame of the batched cell_start arrays
 __global__ void k_grid_build(const KeyPointRec* __restrict__ kps, int N, GridParams g, int* __restrict__ cell_of,
                              int* __restrict__ cell_start, int* __restrict__ cell_items, const int* __restrict__ n_per_frame, int frame_stride);
+__global__ void k_grid_build_kfs(const GridBuildRec* __restrict__ recs);
+__global__ void k_fuse_candidates(const FuseTargetRec* __restrict__ T, int M, const float* __restrict__ pos, const float* __restrict__ normal, const float* __restrict__ min_d,
+                                  const float* __restrict__ max_d, const unsigned long long* __restrict__ qdesc, const uint8_t* __restrict__ skip, float th, int chi2_gate,
+                                  int th_low, int debug_flags, int* __restrict__ best_idx, int* __restrict__ best_dist);
 constexpr int kAreaWaves = 16;         // queries (waves) per k_area_search workgroup
 __global__ void k_area_search(const AreaQuery* __restrict__ queries, const unsigned long long* __restrict__ qdesc, int Q,
                               const KeyPointRec* __restrict__ kps, const float* __restrict__ u_right,

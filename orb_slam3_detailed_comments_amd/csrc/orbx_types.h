@@ -99,6 +99,15 @@ struct ProjectParams {
 // resident set the frame names, its size, and where the frame's rows start in everything that is laid out by the prefix sums of M_b (call-time flags,
 // queries, track x 5, level, in_view, q_start / q_count)
 struct FrameMapRec { const float *pos, *normal, *min_d, *max_d; const unsigned long long* desc; int M, offset; };
+// one record of k_grid_build_kfs: the grid of one device-resident key frame (orbm_keyframe) for one set of image bounds
+struct GridBuildRec { const KeyPointRec* kps; int* cell_of; int* cell_start; int* cell_items; int N; GridParams g; };
+// one target of orbm_fuse_candidates_batch (k_fuse_candidates): a resident key frame's arrays and the grid built for the target's bounds, the projection of
+// ORBmatcher::Fuse into it (OrbmFuseTarget::spec), what MapPoint::PredictScale reads of the key frame, and mvInvLevelSigma2 in g.inv_sigma2
+struct FuseTargetRec {
+    const KeyPointRec* kps; const unsigned long long* desc; const float* ur; const int* cell_start; const int* cell_items;
+    ProjectParams P; GridParams g;
+    int N, nlevels; float log_scale_factor; float scale_factors[kMaxLevels];
+};
 struct RigRelPose { float q[4], t[3]; };                          // mTrl of a two-camera Frame: unit quaternion coeffs (x, y, z, w), translation
 struct VocSlot { int node_id, child_start, child_cnt, word_id; };   // one vocabulary node; children occupy consecutive slots
 // Key frame database (orbv_db_*): where the BowVectors of queries sit - query q's sorted word ids / values at ids + start[q] (start == nullptr:

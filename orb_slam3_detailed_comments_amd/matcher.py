@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 
 from .sophus import SE3f, Sim3f, as_se3
+from .views import FuseTarget, Projection as _Projection
 
 
 class ORBmatcher:
@@ -196,6 +197,32 @@ class ORBmatcher:
                                                      None if s2 is None else s2.ctypes.data, bi.ctypes.data, bd.ctypes.data))
         return bi, bd
 
+    @staticmethod
+    def FuseCandidatesBatch(ext, kfs, specs, points, th, invLevelSigma2=None, skip=None):
+        """The candidate search of ORBmatcher::Fuse for one resident point set against K resident key frames in one call (orbm_fuse_candidates_batch).
+        kfs[k] = ResidentKeyFrame of target k (one camera), specs[k] = fuse_spec(...) of that key frame, points = ResidentPoints; invLevelSigma2 = one
+        array for every target or a list of K arrays (pKF->mvInvLevelSigma2): given, the chi-square gate of Fuse(pKF, vpMapPoints, th) runs, None = the Sim3
+        overload; skip = [K, M] uint8, pairs the caller already excludes.  Returns (best_idx, best_dist) as [K, M] int32 arrays, -1 where the reference
+        would not fuse."""
+        K, Mp = len(kfs), points.M
+        assert len(specs) == K
+        T = (FuseTarget * max(K, 1))()
+        if invLevelSigma2 is None:
+            s2 = [None] * K
+        elif isinstance(invLevelSigma2, (list, tuple)) and len(invLevelSigma2) == K and np.ndim(invLevelSigma2[0]) == 1:
+            s2 = [np.ascontiguousarray(a, np.float32) for a in invLevelSigma2]
+        else:
+            s2 = [np.ascontiguousarray(invLevelSigma2, np.float32)] * K
+        for k in range(K):
+            T[k].kf = kfs[k]._kf; T[k].spec = specs[k][0]; T[k].log_scale_factor = specs[k][1]
+            T[k].inv_level_sigma2 = None if s2[k] is None else s2[k].ctypes.data
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        assert sk is None or sk.shape == (K, Mp)
+        bi = np.full((K, Mp), -1, np.int32); bd = np.full((K, Mp), -1, np.int32)
+        ext._lib.check(ext._lib.L.orbm_fuse_candidates_batch(ext._h, K, T, points._p, None if sk is None else sk.ctypes.data, float(th), int(invLevelSigma2 is not None),
+                                                           bi.ctypes.data, bd.ctypes.data))
+        return bi, bd
+
     def SearchBySim3(self, ext, kf1, kf2, p1in2, p2in1, th):
         """ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, S12, th), src/ORBmatcher.cc:1689.  Returns (nFound, matches12[N1])."""
         m12 = np.full(kf1.view.N, -1, np.int32); nf = C.c_int()
@@ -358,18 +385,41 @@ def SearchLocalPointsRig(ext, frame2, pose, cam1, cam2, bounds, scale_factors, p
     return cut(tl), cut(tr), assigned[:N], n.value
 
 
-class _Projection(C.Structure):
-    _fields_ = [("q", C.c_float * 4), ("t", C.c_float * 3), ("second", C.c_int), ("q2", C.c_float * 4), ("t2", C.c_float * 3), ("s2", C.c_float), ("Ow", C.c_float * 3),
-                ("dist_mode", C.c_int), ("depth_test", C.c_int), ("camera_type", C.c_int), ("cam", C.c_float * 8), ("inline_pinhole", C.c_int), ("min_x", C.c_float),
-                ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float), ("bounds_mode", C.c_int), ("distance_test", C.c_int), ("angle_test", C.c_int), ("bf", C.c_float)]
-
-
 class _ProjectIn(C.Structure):
     _fields_ = [("M", C.c_int), ("pos", C.c_void_p), ("normal", C.c_void_p), ("min_inv", C.c_void_p), ("max_inv", C.c_void_p), ("skip", C.c_void_p)]
 
 
 class _ProjectOut(C.Structure):
     _fields_ = [("valid", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("ur", C.c_void_p), ("inv_z", C.c_void_p), ("dist", C.c_void_p)]
+
+
+def projection_spec(pose, cam, bounds, Ow=None, second=None, depth_test=1, bounds_mode=0, inline_pinhole=False, dist_mode=0, distance_test=False, angle_test=False, bf=0.0):
+    """OrbmProjection (views.Projection) from a pose (sophus.SE3f or (R, t)), the camera's 4 or 8 parameters and the image bounds; the arguments as ProjectPoints."""
+    S = _Projection()
+    T = as_se3(pose)
+    S.q[:] = [float(v) for v in T.unit_quaternion()]; S.t[:] = [float(v) for v in T.translation()]
+    if isinstance(second, Sim3f):
+        S.second = 1; S.q2[:] = [float(v) for v in second.quaternion()]; S.t2[:] = [float(v) for v in second.translation()]; S.s2 = float(second.scale())
+    elif second is not None:
+        X = as_se3(second)
+        S.second = 2; S.q2[:] = [float(v) for v in X.unit_quaternion()]; S.t2[:] = [float(v) for v in X.translation()]; S.s2 = 1.0
+    if Ow is not None:
+        S.Ow[:] = np.ascontiguousarray(Ow, np.float32).tolist()
+    cam = [float(v) for v in cam]
+    S.camera_type = 1 if len(cam) == 8 else 0; S.cam[:] = cam + [0.0] * (8 - len(cam)); S.inline_pinhole = int(inline_pinhole)
+    S.min_x, S.max_x, S.min_y, S.max_y = [float(v) for v in bounds]
+    S.dist_mode, S.depth_test, S.bounds_mode, S.angle_test, S.bf = int(dist_mode), int(depth_test), int(bounds_mode), int(angle_test), float(bf)
+    S.distance_test = int(bool(distance_test))
+    return S
+
+
+def fuse_spec(pose, cam, bounds, bf, log_scale_factor, Ow=None):
+    """What ORBmatcher::Fuse projects with into one key frame, as FuseCandidatesBatch takes it: (OrbmProjection, mfLogScaleFactor).  pose = pKF->GetPose() (or
+    the rigid part of Scw), Ow = pKF->GetCameraCenter() (default: pose.inverse().translation()), bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY), KeyFrame::IsInImage,
+    depth, distance-range and viewing-angle tests on, ur = u - bf / z."""
+    T = as_se3(pose)
+    Ow = T.inverse().translation() if Ow is None else Ow
+    return projection_spec(T, cam, bounds, Ow, depth_test=1, bounds_mode=1, distance_test=True, angle_test=True, bf=bf), float(log_scale_factor)
 
 
 def ProjectPoints(ext, pose, cam, bounds, pos, normal=None, min_inv=None, max_inv=None, skip=None, Ow=None, second=None, depth_test=1, bounds_mode=0, inline_pinhole=False,
@@ -380,21 +430,7 @@ def ProjectPoints(ext, pose, cam, bounds, pos, normal=None, min_inv=None, max_in
     applied behind the pose.  Returns dict(valid, u, v, ur, inv_z, dist)."""
     f32 = lambda a: np.ascontiguousarray(a, np.float32)
     pos = f32(pos).reshape(-1, 3); M = len(pos)
-    S = _Projection()
-    T = as_se3(pose)
-    S.q[:] = [float(v) for v in T.unit_quaternion()]; S.t[:] = [float(v) for v in T.translation()]
-    if isinstance(second, Sim3f):
-        S.second = 1; S.q2[:] = [float(v) for v in second.quaternion()]; S.t2[:] = [float(v) for v in second.translation()]; S.s2 = float(second.scale())
-    elif second is not None:
-        X = as_se3(second)
-        S.second = 2; S.q2[:] = [float(v) for v in X.unit_quaternion()]; S.t2[:] = [float(v) for v in X.translation()]; S.s2 = 1.0
-    if Ow is not None:
-        S.Ow[:] = f32(Ow).tolist()
-    cam = [float(v) for v in cam]
-    S.camera_type = 1 if len(cam) == 8 else 0; S.cam[:] = cam + [0.0] * (8 - len(cam)); S.inline_pinhole = int(inline_pinhole)
-    S.min_x, S.max_x, S.min_y, S.max_y = [float(v) for v in bounds]
-    S.dist_mode, S.depth_test, S.bounds_mode, S.angle_test, S.bf = int(dist_mode), int(depth_test), int(bounds_mode), int(angle_test), float(bf)
-    S.distance_test = int(min_inv is not None and max_inv is not None)
+    S = projection_spec(pose, cam, bounds, Ow, second, depth_test, bounds_mode, inline_pinhole, dist_mode, min_inv is not None and max_inv is not None, angle_test, bf)
     keep = [pos] + [None if a is None else (f32(a) if i < 3 else np.ascontiguousarray(a, np.uint8)) for i, a in enumerate((normal, min_inv, max_inv, skip))]
     ptr = lambda a: None if a is None else a.ctypes.data
     I = _ProjectIn(M, ptr(keep[0]), ptr(keep[1]), ptr(keep[2]), ptr(keep[3]), ptr(keep[4]))

@@ -1,5 +1,5 @@
 """ctypes mirrors of the read-only structure-of-arrays views in include/orbx.h (OrbmFrameView, OrbmMapPointView,
-OrbmLastFrameView, OrbmKeyFrameView, OrbmProjectedPointView) and helpers that build them from numpy arrays."""
+OrbmLastFrameView, OrbmKeyFrameView, OrbmProjectedPointView, OrbmProjection, OrbmFuseTarget) and helpers that build them from numpy arrays."""
 import ctypes as C
 
 import numpy as np
@@ -41,6 +41,18 @@ class MapPointRightView(C.Structure):
 
 class ProjectedPointView(C.Structure):
     _fields_ = [("M", _i), ("valid", _vp), ("u", _vp), ("v", _vp), ("ur", _vp), ("pred_level", _vp), ("angle", _vp), ("desc", _vp)]
+
+
+class Projection(C.Structure):
+    """OrbmProjection: pose, camera, bounds and tests of the geometry in front of a projection-type search (matcher.projection_spec fills it)"""
+    _fields_ = [("q", _f * 4), ("t", _f * 3), ("second", _i), ("q2", _f * 4), ("t2", _f * 3), ("s2", _f), ("Ow", _f * 3),
+                ("dist_mode", _i), ("depth_test", _i), ("camera_type", _i), ("cam", _f * 8), ("inline_pinhole", _i), ("min_x", _f),
+                ("max_x", _f), ("min_y", _f), ("max_y", _f), ("bounds_mode", _i), ("distance_test", _i), ("angle_test", _i), ("bf", _f)]
+
+
+class FuseTarget(C.Structure):
+    """OrbmFuseTarget: one key frame (one camera) of orbm_fuse_candidates_batch"""
+    _fields_ = [("kf", _vp), ("spec", Projection), ("log_scale_factor", _f), ("inv_level_sigma2", _vp)]
 
 
 def _arr(a, dtype):

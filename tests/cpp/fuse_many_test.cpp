@@ -1,0 +1,313 @@
+// The many-key-frame forms of ORBmatcher::Fuse (include/orb_slam3_amd/ORBmatcher.h) against the single-key-frame forms called in a loop, on two
+// identical mock worlds: world A runs Fuse(pKF, points, th) once per key frame in order, world B runs Fuse(vpKFs, points, th) once; the same for the
+// Sim3 overload with the hook of LoopClosing::SearchAndFuse (pRep->Replace(point) after every key frame).  Return counts, every key frame's final map
+// point table, every point's observations, bad flag and descriptor, and the logs of AddObservation / AddMapPoint / Replace must be identical.
+//
+// The mocks carry the members the facade's Fuse reads, under the reference's names, and their map surgery is real: Replace moves the observations of
+// the replaced point to the surviving one key frame by key frame and recomputes the survivor's distinctive descriptor (as src/MapPoint.cc:260-320,
+// :418-540), AddObservation counts stereo keypoints twice.  The world is built so that the ORDER of the replay matters: points of the set that
+// duplicate each other and points the key frames already hold (Replace in both directions, by observation count), points already in some key frames,
+// NULL and bad points, points whose descriptor only just passes TH_LOW (the descriptor a Replace leaves them with decides in the key frames behind).  Asserted on world A: at least 30 Replace calls, and at least 5 points whose fate in a later key frame was changed by the surgery of
+// an earlier one (made bad, or moved into the key frame).  argv[1] = "se3" | "sim3".
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <random>
+#include <set>
+#include <string>
+#include <vector>
+#include "ORBmatcher.h"
+
+namespace {
+
+struct V3 {
+    float d[3];
+    V3() : d{0, 0, 0} {}
+    V3(float a, float b, float c) : d{a, b, c} {}
+    float operator()(int i) const { return d[i]; }
+    V3 operator/(float s) const { return V3(d[0] / s, d[1] / s, d[2] / s); }
+};
+struct M3 { float m[9]; float operator()(int r, int c) const { return m[3 * r + c]; } };
+struct Quat { float c[4]; float x() const { return c[0]; } float y() const { return c[1]; } float z() const { return c[2]; } float w() const { return c[3]; } };
+
+M3 rot_xyz(float rx, float ry, float rz) {
+    const float cx = std::cos(rx), sx = std::sin(rx), cy = std::cos(ry), sy = std::sin(ry), cz = std::cos(rz), sz = std::sin(rz);
+    return M3{{cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx, sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx, -sy, cy * sx, cy * cx}};
+}
+V3 mul(const M3& R, const V3& p) { return V3(R(0, 0) * p(0) + R(0, 1) * p(1) + R(0, 2) * p(2), R(1, 0) * p(0) + R(1, 1) * p(1) + R(1, 2) * p(2), R(2, 0) * p(0) + R(2, 1) * p(1) + R(2, 2) * p(2)); }
+M3 transpose(const M3& R) { return M3{{R(0, 0), R(1, 0), R(2, 0), R(0, 1), R(1, 1), R(2, 1), R(0, 2), R(1, 2), R(2, 2)}}; }
+
+// a rigid transform held as Sophus holds it: unit quaternion + translation (small rotations only: w > 0)
+struct MockSE3 {
+    M3 R; V3 t; Quat q;
+    MockSE3() : R{{1, 0, 0, 0, 1, 0, 0, 0, 1}}, q{{0, 0, 0, 1}} {}
+    MockSE3(const M3& R_, const V3& t_) : R(R_), t(t_) {
+        const float w = 0.5f * std::sqrt(1.0f + R(0, 0) + R(1, 1) + R(2, 2)), s = 0.25f / w;
+        q = Quat{{(R(2, 1) - R(1, 2)) * s, (R(0, 2) - R(2, 0)) * s, (R(1, 0) - R(0, 1)) * s, w}};
+    }
+    const Quat& unit_quaternion() const { return q; }
+    V3 translation() const { return t; }
+    M3 rotationMatrix() const { return R; }
+    MockSE3 inverse() const { const M3 Rt = transpose(R); const V3 c = mul(Rt, t); return MockSE3(Rt, V3(-c(0), -c(1), -c(2))); }
+};
+struct MockSim3 {            // p' = s R p + t
+    M3 R; V3 t; float s;
+    M3 rotationMatrix() const { return R; }
+    V3 translation() const { return t; }
+    float scale() const { return s; }
+};
+struct MockCamera {
+    float p[4];
+    int GetType() { return 0; }
+    float getParameter(int i) { return p[i]; }
+};
+
+struct MockKeyFrame;
+struct World;
+
+struct MockMapPoint {
+    World* world; int id;
+    V3 pos, normal; float mfMinDistance = 0, mfMaxDistance = 0;
+    bool bad = false; int nObs = 0; cv::Mat desc;
+    std::map<MockKeyFrame*, int> obs;
+    V3 GetWorldPos() { return pos; }
+    V3 GetNormal() { return normal; }
+    float GetMinDistanceInvariance() { return 0.8f * mfMinDistance; }
+    float GetMaxDistanceInvariance() { return 1.2f * mfMaxDistance; }
+    bool isBad() { return bad; }
+    int Observations() { return nObs; }
+    cv::Mat GetDescriptor() { return desc.clone(); }
+    bool IsInKeyFrame(MockKeyFrame* kf) { return obs.count(kf) != 0; }
+    int PredictScale(const float& currentDist, MockKeyFrame* kf);
+    void AddObservation(MockKeyFrame* kf, int idx);
+    void Replace(MockMapPoint* p);
+    void ComputeDistinctiveDescriptors();
+};
+
+struct MockKeyFrame {
+    World* world; long unsigned int mnId = 0; int N = 0, NLeft = -1, mnScaleLevels = 8;
+    std::map<unsigned, std::vector<unsigned> > mFeatVec;
+    std::vector<cv::KeyPoint> mvKeysUn, mvKeys, mvKeysRight; cv::Mat mDescriptors; std::vector<float> mvuRight;
+    MockCamera cam; MockCamera* mpCamera = &cam; MockCamera* mpCamera2 = nullptr;
+    float mnMinX = 0, mnMinY = 0, mnMaxX = 640, mnMaxY = 480, mfGridElementWidthInv = 0.1f, mfGridElementHeightInv = 0.1f, mbf = 40.0f, mfLogScaleFactor = 0;
+    std::vector<float> mvScaleFactors, mvLevelSigma2, mvInvLevelSigma2;
+    MockSE3 pose; std::vector<MockMapPoint*> points;
+    MockSE3 GetPose() { return pose; }
+    V3 GetCameraCenter() { return pose.inverse().translation(); }
+    MockSE3 GetRightPose() { return pose; }                         // (named by the single call's rig branch; never reached: NLeft == -1)
+    V3 GetRightCameraCenter() { return GetCameraCenter(); }
+    MockMapPoint* GetMapPoint(int i) { return points[i]; }
+    std::set<MockMapPoint*> GetMapPoints() { std::set<MockMapPoint*> s; for (MockMapPoint* p : points) if (p && !p->isBad()) s.insert(p); return s; }
+    void AddMapPoint(MockMapPoint* p, int idx);
+    void ReplaceMapPointMatch(int idx, MockMapPoint* p) { points[idx] = p; }
+    void EraseMapPointMatch(int idx) { points[idx] = nullptr; }
+};
+
+struct World {
+    std::vector<std::unique_ptr<MockKeyFrame> > kfs;          // the K targets first, then key frames outside the call (they only hold observations)
+    std::vector<std::unique_ptr<MockMapPoint> > points;
+    std::vector<MockKeyFrame*> targets; std::vector<MockMapPoint*> set;
+    std::vector<std::string> log; int replaces = 0;
+    void note(const char* what, int a, int b, int c) { char s[96]; snprintf(s, sizeof s, "%s %d %d %d", what, a, b, c); log.push_back(s); }
+};
+
+int kf_index(MockKeyFrame* kf) { for (size_t i = 0; i < kf->world->kfs.size(); i++) if (kf->world->kfs[i].get() == kf) return (int)i; return -1; }
+
+int MockMapPoint::PredictScale(const float& currentDist, MockKeyFrame* kf) {          // src/MapPoint.cc:688-709
+    const float ratio = mfMaxDistance / currentDist;
+    int n = (int)std::ceil(std::log(ratio) / kf->mfLogScaleFactor);
+    if (n < 0) n = 0; else if (n >= kf->mnScaleLevels) n = kf->mnScaleLevels - 1;
+    return n;
+}
+void MockMapPoint::AddObservation(MockKeyFrame* kf, int idx) {                         // src/MapPoint.cc:150-180
+    world->note("AddObservation", id, kf_index(kf), idx);
+    if (obs.count(kf)) return;
+    obs[kf] = idx;
+    nObs += (idx < (int)kf->mvuRight.size() && kf->mvuRight[idx] >= 0) ? 2 : 1;
+}
+void MockKeyFrame::AddMapPoint(MockMapPoint* p, int idx) { world->note("AddMapPoint", kf_index(this), p->id, idx); points[idx] = p; }
+void MockMapPoint::Replace(MockMapPoint* p) {                                          // src/MapPoint.cc:260-320
+    world->note("Replace", id, p->id, 0); world->replaces++;
+    if (p == this) return;
+    std::map<MockKeyFrame*, int> mine; mine.swap(obs);
+    bad = true; nObs = 0;
+    // (a std::map keyed by address iterates in an order that differs between two worlds: go by key frame index, which is what decides here)
+    std::map<int, std::pair<MockKeyFrame*, int> > ordered;
+    for (auto& o : mine) ordered[kf_index(o.first)] = std::make_pair(o.first, o.second);
+    for (auto& o : ordered) {
+        MockKeyFrame* kf = o.second.first; const int idx = o.second.second;
+        if (!p->IsInKeyFrame(kf)) { kf->ReplaceMapPointMatch(idx, p); p->AddObservation(kf, idx); }
+        else kf->EraseMapPointMatch(idx);
+    }
+    p->ComputeDistinctiveDescriptors();
+}
+void MockMapPoint::ComputeDistinctiveDescriptors() {                                   // src/MapPoint.cc:418-540: the observation whose median distance to the others is least
+    std::map<int, const unsigned char*> rows;
+    for (auto& o : obs) if (o.second < o.first->mDescriptors.rows) rows[kf_index(o.first)] = o.first->mDescriptors.ptr(o.second);
+    if (rows.empty()) return;
+    std::vector<const unsigned char*> d; for (auto& r : rows) d.push_back(r.second);
+    int best = 0, bestMedian = 1 << 30;
+    for (size_t i = 0; i < d.size(); i++) {
+        std::vector<int> dist;
+        for (size_t j = 0; j < d.size(); j++) { int s = 0; for (int b = 0; b < 32; b++) s += __builtin_popcount(d[i][b] ^ d[j][b]); dist.push_back(s); }
+        std::sort(dist.begin(), dist.end());
+        const int median = dist[(dist.size() - 1) / 2];
+        if (median < bestMedian) { bestMedian = median; best = (int)i; }
+    }
+    cv::Mat m(1, 32, CV_8UC1); memcpy(m.ptr(0), d[best], 32); desc = m;
+}
+
+const int K = 6, M = 400, FEATURES = 520, OUTSIDE = 3;
+
+// One scene = world features seen by all key frames; every key frame observes ~60 % of them (keypoint = projection + noise, descriptor = the feature's with
+// a few bits flipped).  40 % of the features have a map point already, held by some of the key frames that observe the feature.  The point set: new
+// points on features (some features twice: duplicates inside the set), some of the existing points themselves, NULL and bad entries.
+void build(World& W, unsigned seed, int idBase) {
+    std::mt19937 rng(seed);
+    auto uni = [&](float a, float b) { return a + (b - a) * (float)(rng() % 1000003) / 1000003.0f; };
+    const float fx = 517.3f, fy = 516.5f, cx = 318.6f, cy = 255.3f;
+    struct Feature { V3 p; int octave; unsigned char desc[32]; MockMapPoint* owner; };
+    std::vector<Feature> feats(FEATURES);
+    for (auto& f : feats) {
+        const float z = uni(3.0f, 8.0f);
+        f.p = V3((uni(30, 610) - cx) / fx * z, (uni(30, 450) - cy) / fy * z, z); f.octave = (int)(rng() % 8); f.owner = nullptr;
+        for (int b = 0; b < 32; b++) f.desc[b] = (unsigned char)(rng() & 255);
+    }
+    auto flipped = [&](const unsigned char* src, int maxflips) { cv::Mat m(1, 32, CV_8UC1); memcpy(m.ptr(0), src, 32); for (int n = (int)(rng() % (maxflips + 1)); n > 0; n--) m.ptr(0)[rng() % 32] ^= (unsigned char)(1 << (rng() % 8)); return m; };
+    auto new_point = [&](const Feature& f, float jitter) {
+        std::unique_ptr<MockMapPoint> p(new MockMapPoint());
+        p->world = &W; p->id = (int)W.points.size();
+        p->pos = V3(f.p(0) + uni(-jitter, jitter), f.p(1) + uni(-jitter, jitter), f.p(2) + uni(-jitter, jitter));
+        const float dist = std::sqrt(p->pos(0) * p->pos(0) + p->pos(1) * p->pos(1) + p->pos(2) * p->pos(2));
+        p->normal = V3(p->pos(0) / dist, p->pos(1) / dist, p->pos(2) / dist);
+        p->mfMaxDistance = dist * std::pow(1.2f, (float)f.octave + 0.5f); p->mfMinDistance = p->mfMaxDistance / std::pow(1.2f, 7.0f);
+        p->desc = flipped(f.desc, 12);
+        W.points.push_back(std::move(p));
+        return W.points.back().get();
+    };
+    std::vector<std::vector<int> > slotOf(K + OUTSIDE, std::vector<int>(FEATURES, -1));       // keypoint of feature f in key frame k
+    for (int k = 0; k < K + OUTSIDE; k++) {
+        std::unique_ptr<MockKeyFrame> kf(new MockKeyFrame());
+        kf->world = &W; kf->mnId = (long unsigned int)(idBase + k);
+        kf->cam = MockCamera{{fx, fy, cx, cy}};
+        kf->pose = MockSE3(rot_xyz(uni(-0.02f, 0.02f), uni(-0.02f, 0.02f), uni(-0.02f, 0.02f)), V3(uni(-0.1f, 0.1f), uni(-0.1f, 0.1f), uni(-0.1f, 0.1f)));
+        kf->mfGridElementWidthInv = 64.0f / (kf->mnMaxX - kf->mnMinX); kf->mfGridElementHeightInv = 48.0f / (kf->mnMaxY - kf->mnMinY);
+        kf->mfLogScaleFactor = std::log(1.2f);
+        float s = 1.0f;
+        for (int l = 0; l < 8; l++) { kf->mvScaleFactors.push_back(s); kf->mvLevelSigma2.push_back(s * s); kf->mvInvLevelSigma2.push_back(1.0f / (s * s)); s *= 1.2f; }
+        std::vector<unsigned char> rows;
+        for (int f = 0; f < FEATURES; f++) {
+            if (rng() % 10 >= 6) continue;
+            const V3 c = mul(kf->pose.R, feats[f].p);
+            const float X = c(0) + kf->pose.t(0), Y = c(1) + kf->pose.t(1), Z = c(2) + kf->pose.t(2);
+            const float u = fx * X / Z + cx + uni(-0.4f, 0.4f), v = fy * Y / Z + cy + uni(-0.4f, 0.4f);
+            if (u < 5 || u > 635 || v < 5 || v > 475) continue;
+            slotOf[k][f] = (int)kf->mvKeysUn.size();
+            kf->mvKeysUn.push_back(cv::KeyPoint(u, v, 31.0f, uni(0, 360), 50.0f, feats[f].octave));
+            kf->mvuRight.push_back(rng() % 10 < 6 ? u - kf->mbf / Z : -1.0f);
+            const cv::Mat d = flipped(feats[f].desc, 10); rows.insert(rows.end(), d.ptr(0), d.ptr(0) + 32);
+        }
+        kf->N = (int)kf->mvKeysUn.size(); kf->mvKeys = kf->mvKeysUn;
+        kf->mDescriptors = cv::Mat(kf->N, 32, CV_8UC1); memcpy(kf->mDescriptors.ptr(0), rows.data(), rows.size());
+        kf->points.assign(kf->N, nullptr);
+        if (k != K - 1) for (int i = 0; i < kf->N; i++) kf->mFeatVec[(unsigned)(i % 7)].push_back((unsigned)i);      // (the last target has not run ComputeBoW: not cached, uploaded for the call)
+        W.kfs.push_back(std::move(kf));
+        if (k < K) W.targets.push_back(W.kfs.back().get());
+    }
+    auto observe = [&](MockMapPoint* p, int k, int f) {
+        MockKeyFrame* kf = W.kfs[k].get(); const int slot = slotOf[k][f];
+        if (slot < 0 || kf->points[slot] || p->IsInKeyFrame(kf)) return;
+        p->obs[kf] = slot; p->nObs += kf->mvuRight[slot] >= 0 ? 2 : 1; kf->points[slot] = p;
+    };
+    // the map points the key frames hold before the call: a feature's point sits in about half of the key frames that see the feature
+    for (int f = 0; f < FEATURES; f++) {
+        if (rng() % 10 >= 4) continue;
+        MockMapPoint* p = new_point(feats[f], 0.002f); feats[f].owner = p;
+        for (int k = 0; k < K + OUTSIDE; k++) if (rng() % 2) observe(p, k, f);
+        if (p->obs.empty()) for (int k = 0; k < K + OUTSIDE; k++) observe(p, k, f);
+    }
+    // the point set
+    std::vector<int> used;
+    while ((int)W.set.size() < M) {
+        const unsigned kind = rng() % 20;
+        if (kind == 0) { W.set.push_back(nullptr); continue; }
+        int f = (int)(rng() % FEATURES);
+        if (kind <= 4 && !used.empty()) f = used[rng() % used.size()];                    // a second point of the set on the same feature
+        if (kind >= 17 && feats[f].owner) { W.set.push_back(feats[f].owner); continue; }   // a point the key frames hold already
+        MockMapPoint* p = new_point(feats[f], 0.002f);
+        for (int k = K; k < K + OUTSIDE; k++) if (rng() % 2) observe(p, k, f);             // what it has seen so far lies outside the call (the current key frame ...)
+        if (kind == 5) p->bad = true;
+        if (kind == 6 || kind == 7) {                                                      // a descriptor at the edge of TH_LOW: 44-51 bits from the feature's.  Some key frames
+            cv::Mat m(1, 32, CV_8UC1); memcpy(m.ptr(0), feats[f].desc, 32);                 // take it, some do not - until a Replace in one of them gives the point the descriptor of
+            std::set<int> bits; const int n = 44 + (int)(rng() % 8);                       // its observations, which every later key frame takes
+            while ((int)bits.size() < n) bits.insert((int)(rng() % 256));
+            for (int bit : bits) m.ptr(0)[bit >> 3] ^= (unsigned char)(1 << (bit & 7));
+            p->desc = m;
+        }
+        used.push_back(f);
+        W.set.push_back(p);
+    }
+}
+
+std::string dump(World& W, const std::vector<int>& counts) {
+    std::string s;
+    char b[64];
+    for (int c : counts) { snprintf(b, sizeof b, "count %d\n", c); s += b; }
+    for (auto& kf : W.kfs) { s += "kf"; for (MockMapPoint* p : kf->points) { snprintf(b, sizeof b, " %d", p ? p->id : -1); s += b; } s += "\n"; }
+    for (auto& p : W.points) {
+        snprintf(b, sizeof b, "p %d bad %d n %d obs", p->id, (int)p->bad, p->nObs); s += b;
+        std::map<int, int> o; for (auto& e : p->obs) o[kf_index(e.first)] = e.second;
+        for (auto& e : o) { snprintf(b, sizeof b, " %d:%d", e.first, e.second); s += b; }
+        s += " d"; for (int i = 0; i < 32; i++) { snprintf(b, sizeof b, "%02x", p->desc.ptr(0)[i]); s += b; }
+        s += "\n";
+    }
+    for (auto& l : W.log) s += l + "\n";
+    return s;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    const bool sim3 = argc > 1 && !strcmp(argv[1], "sim3");
+    const float th = sim3 ? 4.0f : 3.0f;
+    World A, B;
+    build(A, sim3 ? 91u : 90u, sim3 ? 2000 : 1000); build(B, sim3 ? 91u : 90u, sim3 ? 3000 : 1500);
+    ORB_SLAM3::ORBmatcher matcher(0.8f);
+    if (sim3) for (World* W : {&A, &B}) { std::vector<MockMapPoint*> s; for (MockMapPoint* p : W->set) if (p) s.push_back(p); W->set.swap(s); }      // (vpPoints holds no NULL entries)
+    const int Mset = (int)A.set.size();
+    std::vector<MockSim3> vScw;
+    for (MockKeyFrame* kf : A.targets) { const float s = 1.02f; vScw.push_back(MockSim3{kf->pose.R, V3(kf->pose.t(0) * s, kf->pose.t(1) * s, kf->pose.t(2) * s), s}); }
+    auto hook = [](World& W) { return [&W](int, std::vector<MockMapPoint*>& rep) { for (size_t i = 0; i < rep.size(); i++) if (rep[i]) rep[i]->Replace(W.set[i]); }; };
+
+    // world A: one call per key frame; before each, what the surgery so far has done to the points of the set
+    std::vector<int> countsA;
+    std::vector<char> bad0(Mset, 0); std::set<int> changed;
+    std::vector<std::vector<char> > in0(K, std::vector<char>(Mset, 0));
+    for (int i = 0; i < Mset; i++) if (A.set[i]) { bad0[i] = A.set[i]->bad; for (int k = 0; k < K; k++) in0[k][i] = A.set[i]->IsInKeyFrame(A.targets[k]); }
+    for (int k = 0; k < K; k++) {
+        if (k > 0) for (int i = 0; i < Mset; i++) if (A.set[i] && !bad0[i] && (A.set[i]->bad || (!in0[k][i] && A.set[i]->IsInKeyFrame(A.targets[k])))) changed.insert(i);
+        if (!sim3) countsA.push_back(matcher.Fuse(A.targets[k], A.set, th));
+        else {
+            std::vector<MockMapPoint*> rep(Mset, nullptr);
+            countsA.push_back(matcher.Fuse(A.targets[k], vScw[k], A.set, th, rep));
+            hook(A)(k, rep);
+        }
+    }
+    // world B: one call
+    const std::vector<int> countsB = sim3 ? matcher.Fuse(B.targets, vScw, B.set, th, hook(B)) : matcher.Fuse(B.targets, B.set, th);
+    const std::string a = dump(A, countsA), b = dump(B, countsB);
+    int fused = 0; for (int c : countsA) fused += c;
+    printf("%s: fused %d, Replace calls %d, points whose fate an earlier key frame changed %d, log lines %zu, identical %d\n", sim3 ? "sim3" : "se3", fused, A.replaces,
+           (int)changed.size(), A.log.size(), (int)(a == b));
+    if (a != b) {
+        size_t i = 0; while (i < a.size() && i < b.size() && a[i] == b[i]) i++;
+        const size_t from = a.rfind('\n', i) == std::string::npos ? 0 : a.rfind('\n', i) + 1;
+        printf("first difference:\n  A: %s\n  B: %s\n", a.substr(from, a.find('\n', i) - from).c_str(), b.substr(from, b.find('\n', i) - from).c_str());
+        return 1;
+    }
+    if (A.replaces < 30 || (int)changed.size() < 5 || fused < 200) { printf("the world does not test the replay order\n"); return 1; }
+    return 0;
+}

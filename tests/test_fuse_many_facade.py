@@ -1,0 +1,38 @@
+"""The many-key-frame forms of the facade's Fuse - Fuse(vpKFs, vpMapPoints, th) and Fuse(vpKFs, vScw, vpPoints, th, afterKeyFrame) of
+include/orb_slam3_amd/ORBmatcher.h - against the single-key-frame forms called once per key frame: tests/cpp/fuse_many_test.cpp builds two identical mock
+worlds (6 key frames, one set of 400 points with duplicates, points the key frames hold already, NULL and bad entries; Replace and AddObservation really move
+observations, Replace recomputes the survivor's descriptor), runs the loop on one and the single call on the other, and requires identical return counts, map
+point tables, observations, bad flags, descriptors and call logs - and a world in which the order of the replay decides (>= 30 Replace calls, >= 5 points
+whose fate an earlier key frame changed)."""
+import os
+import subprocess
+
+import pytest
+
+import oracle_lib as ol
+from orb_slam3_detailed_comments_amd import _lib
+
+ROOT = ol.ROOT
+
+
+def _build(tmp_path, libdir, libname):
+    exe = tmp_path / "fuse_many_test"
+    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + os.path.join(ROOT, "include", "orb_slam3_amd"), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
+                    os.path.join(ROOT, "tests", "cpp", "fuse_many_test.cpp"), "-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-lpthread", "-o", str(exe)], check=True)
+    return exe
+
+
+def _run(tmp_path, libdir, libname):
+    exe = _build(tmp_path, libdir, libname)
+    for form in ("se3", "sim3"):
+        r = subprocess.run([str(exe), form], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0 and "identical 1" in r.stdout, form + ": " + r.stdout + r.stderr
+
+
+def test_fuse_many_equals_the_loop_emulated(tmp_path, emu_lib):
+    _run(tmp_path, *ol.emu_link())
+
+
+@pytest.mark.gpu
+def test_fuse_many_equals_the_loop_gpu(tmp_path, hip_lib):
+    _run(tmp_path, os.path.dirname(_lib.HIP_LIB_PATH), "orbx_hip")
