@@ -251,11 +251,10 @@ __global__ void __launch_bounds__(64 * kAreaWaves) k_area_search(const AreaQuery
 // in the reference's fp32 operation order (Eigen >= 3.3 sums a 3-term product coefficient as a0 + (a1 + a2), sophus_action.h; no fused multiply-adds).  Writes the tracking
 // fields the reference stores in the MapPoint (mbTrackInView, mTrackProjX / Y / XR, mTrackDepth, mnTrackScaleLevel, mTrackViewCos) and,
 // when `queries` is given, the window query of ORBmatcher::SearchByProjection(Frame, MapPoints) for that point (src/ORBmatcher.cc:53-82).
-// Batched form: Fbatch != NULL -> blockIdx.y = frame, frame b uses Fbatch[b] and writes at offsets b * M (track: b * 5 * M).
 // F.rig_mode (Frame::isInFrustumChecks, src/Frame.cc:1592-1650, one camera of a two-camera rig; the caller passes that camera's mR, mt, twc
 // and parameters): nothing is stored unless the point passes every test, and the level of a rejected point is -1 (:756-757).
-// (the body takes the frame's parameters by REFERENCE - the kernel argument itself, or the batch's record in global memory: copying one over the
-// other (`F = Fbatch[b]`) made the struct a private variable, 240 bytes of scratch per thread)
+// (the body takes the frame's parameters by REFERENCE - the kernel argument itself, or the batch's record in global memory: a copy of the record
+// (`F = Fb[b]`) made the struct a private variable, 240 bytes of scratch per thread)
 __device__ __forceinline__ void frustum_body(const FrustumParams& F, int i, int M, const float* __restrict__ pos, const float* __restrict__ normal,
                                              const float* __restrict__ min_dist, const float* __restrict__ max_dist, const uint8_t* __restrict__ is_bad,
                                              uint8_t* __restrict__ in_view, float* __restrict__ track, int* __restrict__ scale_level, AreaQuery* __restrict__ queries) {
@@ -321,32 +320,28 @@ __device__ __forceinline__ void frustum_body(const FrustumParams& F, int i, int 
 __global__ void __launch_bounds__(256) k_frustum(FrustumParams F, int M, const float* __restrict__ pos, const float* __restrict__ normal,
                                                  const float* __restrict__ min_dist, const float* __restrict__ max_dist, const uint8_t* __restrict__ is_bad,
                                                  uint8_t* __restrict__ in_view, float* __restrict__ track /* [6][M]: x, y, xr, depth, cos, - */,
-                                                 int* __restrict__ scale_level, AreaQuery* __restrict__ queries, int* __restrict__ zero4,
-                                                 const FrustumParams* __restrict__ Fbatch) {
+                                                 int* __restrict__ scale_level, AreaQuery* __restrict__ queries, int* __restrict__ zero4) {
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (zero4 && i < 4 && blockIdx.y == 0) zero4[i] = 0;          // the pool counter of the window search that follows (saves a fill launch)
+    if (zero4 && i < 4) zero4[i] = 0;                             // the pool counter of the window search that follows (saves a fill launch)
     if (i >= M) return;
-    if (Fbatch) {
-        const size_t b = blockIdx.y;
-        frustum_body(Fbatch[b], i, M, pos, normal, min_dist, max_dist, is_bad, in_view + b * (size_t)M, track + 5 * b * (size_t)M, scale_level + b * (size_t)M,
-                     queries ? queries + b * (size_t)M : queries);
-    } else frustum_body(F, i, M, pos, normal, min_dist, max_dist, is_bad, in_view, track, scale_level, queries);
+    frustum_body(F, i, M, pos, normal, min_dist, max_dist, is_bad, in_view, track, scale_level, queries);
 }
 
-// The batched form for frames that bring their OWN local maps (orbm_search_local_points_batch_maps): blockIdx.y = frame, frame b reads the set
-// maps[b] names and writes at maps[b].offset - its place in everything laid out by the prefix sums of M_b (is_bad, in_view, level, queries;
-// track at 5 x offset).  grid ((max M_b + 255) / 256, B): the blocks beyond a frame's M_b leave at once.  The table entry is the same for the
-// whole block (an address made of blockIdx.y alone): one scalar load, not one per lane.
-__global__ void __launch_bounds__(256) k_frustum_maps(const FrustumParams* __restrict__ Fb, const FrameMapRec* __restrict__ maps, const uint8_t* __restrict__ is_bad,
-                                                      uint8_t* __restrict__ in_view, float* __restrict__ track, int* __restrict__ scale_level,
-                                                      AreaQuery* __restrict__ queries, int* __restrict__ zero4) {
+// The batched form (orbm_search_local_points_batch / _batch_maps): blockIdx.y = frame, frame b uses Fb[b], reads the resident set maps[b] names and
+// writes at maps[b].offset - its place in everything laid out by the prefix sums of M_b (in_view, level, queries; track at 5 x offset); its is_bad
+// row starts at maps[b].flags.  One set for every frame is the table that names it B times: offset = b * M, flags = 0 (the flags are uploaded once).
+// grid ((max M_b + 255) / 256, B): the blocks beyond a frame's M_b leave at once.  The table entry is the same for the whole block (an address made
+// of blockIdx.y alone): one scalar load, not one per lane.
+__global__ void __launch_bounds__(256) k_frustum_batch(const FrustumParams* __restrict__ Fb, const FrameMapRec* __restrict__ maps, const uint8_t* __restrict__ is_bad,
+                                                       uint8_t* __restrict__ in_view, float* __restrict__ track, int* __restrict__ scale_level,
+                                                       AreaQuery* __restrict__ queries, int* __restrict__ zero4) {
     const size_t b = blockIdx.y;
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
     if (zero4 && i < 4 && b == 0) zero4[i] = 0;
     const FrameMapRec T = maps[b];
     if (i >= T.M) return;
     const size_t o = (size_t)T.offset;
-    frustum_body(Fb[b], i, T.M, T.pos, T.normal, T.min_d, T.max_d, is_bad + o, in_view + o, track + 5 * o, scale_level + o, queries + o);
+    frustum_body(Fb[b], i, T.M, T.pos, T.normal, T.min_d, T.max_d, is_bad + T.flags, in_view + o, track + 5 * o, scale_level + o, queries + o);
 }
 
 // The head of the projection-type searches of ORBmatcher (SearchByProjection(Frame, LastFrame) src/ORBmatcher.cc:1993-2010, (Frame, KeyFrame)
@@ -477,6 +472,9 @@ __global__ void __launch_bounds__(256) k_keyframe_queries(const FrustumParams* _
 // reference's order (ix-major, iy-minor, items in insertion order), counts, the workgroup reserves its span of the entry pool with one
 // atomicAdd, and a second walk writes {idx, dist | octave << 16} at the thread's offset.  Same gates as k_area_search.  blockIdx.y = frame.
 // On pool overflow nothing is written and the counts are 0 (the host sees the counter, enlarges the pool and repeats).
+// Frame b's maps[b].M queries sit at maps[b].offset, their descriptors are maps[b].desc: the resident set of a local map, or the frame's rows of a
+// projection batch's upload (M = cap_last, offset = b * cap_last).  grid ((max M_b + 255) / 256, B); a block beyond its frame's M_b leaves before
+// the first barrier.
 // (the body: queries / q_start / q_count / qdesc / the frame's keypoints and grid are THIS frame's, Q its number of queries)
 __device__ __forceinline__ void area_search_threads_body(const AreaQuery* __restrict__ queries, const unsigned long long* __restrict__ qdesc, int Q,
                                                          const KeyPointRec* __restrict__ kps, const float* __restrict__ u_right,
@@ -548,24 +546,11 @@ __device__ __forceinline__ void area_search_threads_body(const AreaQuery* __rest
     }
     if (q < Q) { q_start[q] = fits ? start : 0; q_count[q] = fits ? cnt : 0; }
 }
-__global__ void __launch_bounds__(256) k_area_search_threads(const AreaQuery* __restrict__ queries, const unsigned long long* __restrict__ qdesc, int Q,
+__global__ void __launch_bounds__(256) k_area_search_threads(const AreaQuery* __restrict__ queries, const FrameMapRec* __restrict__ maps,
                                                              const KeyPointRec* __restrict__ kps, const float* __restrict__ u_right,
                                                              const unsigned long long* __restrict__ fdesc, GridParams g, const int* __restrict__ cell_start,
                                                              const int* __restrict__ cell_items, int gate_right, int* __restrict__ pool_counter, int pool_cap,
-                                                             int* __restrict__ q_start, int* __restrict__ q_count, int2* __restrict__ entries, int frame_stride,
-                                                             int qdesc_per_frame) {
-    const size_t b = blockIdx.y, o = b * (size_t)Q, f = b * (size_t)frame_stride;
-    // qdesc_per_frame: every frame brings its own query descriptors (the map points of ITS last frame)
-    area_search_threads_body(queries + o, qdesc_per_frame ? qdesc + 4 * o : qdesc, Q, kps + f, u_right + f, fdesc + 4 * f, g, cell_start + b * (size_t)kGridCellStride,
-                             cell_items + f, gate_right, pool_counter, pool_cap, q_start + o, q_count + o, entries);
-}
-// The same for frames with their own local maps: frame b's M_b queries sit at maps[b].offset, their descriptors are those of the set maps[b] names.
-// grid ((max M_b + 255) / 256, B); a block beyond its frame's M_b leaves before the first barrier.
-__global__ void __launch_bounds__(256) k_area_search_threads_maps(const AreaQuery* __restrict__ queries, const FrameMapRec* __restrict__ maps,
-                                                                  const KeyPointRec* __restrict__ kps, const float* __restrict__ u_right,
-                                                                  const unsigned long long* __restrict__ fdesc, GridParams g, const int* __restrict__ cell_start,
-                                                                  const int* __restrict__ cell_items, int gate_right, int* __restrict__ pool_counter, int pool_cap,
-                                                                  int* __restrict__ q_start, int* __restrict__ q_count, int2* __restrict__ entries, int frame_stride) {
+                                                             int* __restrict__ q_start, int* __restrict__ q_count, int2* __restrict__ entries, int frame_stride) {
     const size_t b = blockIdx.y, f = b * (size_t)frame_stride;
     const FrameMapRec T = maps[b];
     if ((int)(blockIdx.x * 256) >= T.M) return;
@@ -651,20 +636,20 @@ __global__ void __launch_bounds__(256) k_fuse_candidates(const FuseTargetRec* __
 //      candidates), the others repeat from 1 with the new occupancy.  The first pending lane is never dirty, so every round commits.
 // F.mvpMapPoints[idx] = pMP without observations does not occupy; a later point may overwrite it: assignments are merged with atomicMax on
 // the map point index (the sequential last writer is the largest index).
-// occupied0: [B][cap] bytes or NULL; has_obs: [M] or NULL (all observed).  assigned: [B][cap], -1 = untouched; nmatches: [B].
+// Frame b has maps[b].M points; its q_start / q_count rows (LASTFRAME: and last_angle) start at maps[b].offset, its has_obs row at maps[b].flags (one
+// set for every frame: offset = b * M, flags = 0; frames with their own maps: both the prefix sum of M_b; a projection batch: both b * cap_last).
+// occupied0: [B][cap] bytes or NULL; has_obs: NULL = all observed.  assigned: [B][cap], -1 = untouched; nmatches: [B].
 // dynamic LDS: occupancy bitmap ((cap + 31) / 32 words) | claiming lane per keypoint (cap words) | LASTFRAME: one accept event per query (M words).
 // LASTFRAME = the accept loop of SearchByProjection(CurrentFrame, LastFrame) (src/ORBmatcher.cc:2025-2150): the best candidate alone decides
-// (bestDist <= TH_HIGH, no ratio test), has_obs / the query arrays are per frame, and every accepted pair goes into the rotation histogram
+// (bestDist <= TH_HIGH, no ratio test), and every accepted pair goes into the rotation histogram
 // (:2118-2126, ComputeThreeMaxima :2335-2377): after the loop the pairs outside the three fullest bins are taken back (assigned = -2 = reset to
 // NULL, nmatches--) - per accept EVENT, as the reference's rotHist lists are (a keypoint that was given twice has two entries).
-// MAPS = the frames bring their own local maps (k_local_accept_maps): frame b has maps[b].M points, its q_start / q_count / has_obs rows start at
-// maps[b].offset (prefix sums of M_b) instead of b * M.
-template <bool LASTFRAME, bool MAPS = false>
-__device__ __forceinline__ void local_accept_body(int M, int cap, const int* __restrict__ n_per_frame, const int* __restrict__ q_start,
+template <bool LASTFRAME>
+__device__ __forceinline__ void local_accept_body(const FrameMapRec* __restrict__ maps, int cap, const int* __restrict__ n_per_frame, const int* __restrict__ q_start,
                                                   const int* __restrict__ q_count, const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0,
                                                   const uint8_t* __restrict__ has_obs, float nnratio, int th_high, int* __restrict__ assigned,
                                                   int* __restrict__ nmatches, const float* __restrict__ last_angle, const KeyPointRec* __restrict__ cur_kps,
-                                                  int check_ori, const FrameMapRec* __restrict__ maps = nullptr) {
+                                                  int check_ori) {
     int* events = nullptr;
     ORBX_DYN_SMEM(smem);
     const int nwords = (cap + 31) / 32;
@@ -674,13 +659,12 @@ __device__ __forceinline__ void local_accept_body(int M, int cap, const int* __r
     const int lane = lane_id();
     const size_t b = blockIdx.x;
     const int N = n_per_frame[b];
-    if (MAPS) M = maps[b].M;
-    const size_t qo = MAPS ? (size_t)maps[b].offset : b * (size_t)M;
+    const int M = maps[b].M;
+    const size_t qo = (size_t)maps[b].offset;
     q_start += qo; q_count += qo; assigned += b * (size_t)cap;
-    if (MAPS && has_obs) has_obs += qo;
+    if (has_obs) has_obs += maps[b].flags;
     if (LASTFRAME) {
-        if (has_obs) has_obs += b * (size_t)M;
-        last_angle += b * (size_t)M; cur_kps += b * (size_t)cap;
+        last_angle += qo; cur_kps += b * (size_t)cap;
         events = (int*)(s_claim + cap);                               // in LDS: written and read by different lanes of this wave, in program order
         if (lane < 32) s_hist[lane] = 0;
     }
@@ -779,23 +763,17 @@ __device__ __forceinline__ void local_accept_body(int M, int cap, const int* __r
     if (lane == 0) nmatches[b] = nm;
 }
 
-__global__ void __launch_bounds__(64) k_local_accept(int M, int cap, const int* __restrict__ n_per_frame, const int* __restrict__ q_start,
+__global__ void __launch_bounds__(64) k_local_accept(const FrameMapRec* __restrict__ maps, int cap, const int* __restrict__ n_per_frame, const int* __restrict__ q_start,
                                                      const int* __restrict__ q_count, const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0,
                                                      const uint8_t* __restrict__ has_obs, float nnratio, int th_high, int* __restrict__ assigned,
                                                      int* __restrict__ nmatches) {
-    local_accept_body<false>(M, cap, n_per_frame, q_start, q_count, entries, occupied0, has_obs, nnratio, th_high, assigned, nmatches, nullptr, nullptr, 0);
+    local_accept_body<false>(maps, cap, n_per_frame, q_start, q_count, entries, occupied0, has_obs, nnratio, th_high, assigned, nmatches, nullptr, nullptr, 0);
 }
-__global__ void __launch_bounds__(64) k_local_accept_maps(const FrameMapRec* __restrict__ maps, int cap, const int* __restrict__ n_per_frame, const int* __restrict__ q_start,
-                                                          const int* __restrict__ q_count, const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0,
-                                                          const uint8_t* __restrict__ has_obs, float nnratio, int th_high, int* __restrict__ assigned,
-                                                          int* __restrict__ nmatches) {
-    local_accept_body<false, true>(0, cap, n_per_frame, q_start, q_count, entries, occupied0, has_obs, nnratio, th_high, assigned, nmatches, nullptr, nullptr, 0, maps);
-}
-__global__ void __launch_bounds__(64) k_lastframe_accept(int M, int cap, const int* __restrict__ n_per_frame, const int* __restrict__ q_start,
+__global__ void __launch_bounds__(64) k_lastframe_accept(const FrameMapRec* __restrict__ maps, int cap, const int* __restrict__ n_per_frame, const int* __restrict__ q_start,
                                                          const int* __restrict__ q_count, const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0,
                                                          const uint8_t* __restrict__ has_obs, int th_high, int* __restrict__ assigned, int* __restrict__ nmatches,
                                                          const float* __restrict__ last_angle, const KeyPointRec* __restrict__ cur_kps, int check_ori) {
-    local_accept_body<true>(M, cap, n_per_frame, q_start, q_count, entries, occupied0, has_obs, 0.0f, th_high, assigned, nmatches, last_angle, cur_kps, check_ori);
+    local_accept_body<true>(maps, cap, n_per_frame, q_start, q_count, entries, occupied0, has_obs, 0.0f, th_high, assigned, nmatches, last_angle, cur_kps, check_ori);
 }
 
 // ---- two-camera rig frames (Frame::Nleft != -1) in a batch ----
@@ -803,7 +781,8 @@ __global__ void __launch_bounds__(64) k_lastframe_accept(int M, int cap, const i
 // of SearchByProjection(Frame, MapPoints) for B rig frames.  Fb = [B][2]: camera 1 and camera 2 of frame b, both in rig_mode.  Camera 1's query is
 // the one frustum_body writes (the search runs with the right-coordinate gate off: a rig frame has no mvuRight).  Camera 2's (src/ORBmatcher.cc:
 // 170-176): the point is alive (in view of either camera, not far by camera 1's depth, not bad), in camera 2's view with a level; radius
-// RadiusByViewingCos(mTrackViewCosR) WITHOUT th; levels [level - 1, level].  Every output of camera c of frame b sits at b * M (track: b * 5 * M).
+// RadiusByViewingCos(mTrackViewCosR) WITHOUT th; levels [level - 1, level].  Frame b reads the set maps[b] names, its is_bad row at maps[b].flags, and
+// every output of either camera sits at maps[b].offset (track: 5 x offset), as in k_frustum_batch.
 // (the body, point i of a frame: every array is THAT frame's - M rows, track 5 M)
 __device__ __forceinline__ void frustum_rig_body(const FrustumParams& F1, const FrustumParams& F2, int i, int M, const float* __restrict__ pos,
                                                  const float* __restrict__ normal, const float* __restrict__ min_dist, const float* __restrict__ max_dist,
@@ -824,30 +803,16 @@ __device__ __forceinline__ void frustum_rig_body(const FrustumParams& F1, const 
     }
     q2[i] = q;
 }
-__global__ void __launch_bounds__(256) k_frustum_rig(const FrustumParams* __restrict__ Fb, int M, const float* __restrict__ pos, const float* __restrict__ normal,
-                                                     const float* __restrict__ min_dist, const float* __restrict__ max_dist, const uint8_t* __restrict__ is_bad,
+__global__ void __launch_bounds__(256) k_frustum_rig(const FrustumParams* __restrict__ Fb, const FrameMapRec* __restrict__ maps, const uint8_t* __restrict__ is_bad,
                                                      uint8_t* in_view1, uint8_t* in_view2, float* track1, float* track2, int* level1, int* level2,
                                                      AreaQuery* __restrict__ q1, AreaQuery* __restrict__ q2, int* __restrict__ zero4) {
-    const size_t b = blockIdx.y;
-    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (zero4 && i < 4 && b == 0) zero4[i] = 0;
-    if (i >= M) return;
-    const size_t o = b * (size_t)M, ot = 5 * o;
-    frustum_rig_body(Fb[2 * b], Fb[2 * b + 1], i, M, pos, normal, min_dist, max_dist, is_bad, in_view1 + o, in_view2 + o, track1 + ot, track2 + ot, level1 + o, level2 + o,
-                     q1 + o, q2 + o);
-}
-// The same for rig frames with their own local maps (orbm_search_local_points_rig_batch_maps): frame b reads the set maps[b] names and writes at
-// maps[b].offset (track: 5 x offset), as k_frustum_maps does.
-__global__ void __launch_bounds__(256) k_frustum_rig_maps(const FrustumParams* __restrict__ Fb, const FrameMapRec* __restrict__ maps, const uint8_t* __restrict__ is_bad,
-                                                          uint8_t* in_view1, uint8_t* in_view2, float* track1, float* track2, int* level1, int* level2,
-                                                          AreaQuery* __restrict__ q1, AreaQuery* __restrict__ q2, int* __restrict__ zero4) {
     const size_t b = blockIdx.y;
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
     if (zero4 && i < 4 && b == 0) zero4[i] = 0;
     const FrameMapRec T = maps[b];
     if (i >= T.M) return;
     const size_t o = (size_t)T.offset, ot = 5 * o;
-    frustum_rig_body(Fb[2 * b], Fb[2 * b + 1], i, T.M, T.pos, T.normal, T.min_d, T.max_d, is_bad + o, in_view1 + o, in_view2 + o, track1 + ot, track2 + ot, level1 + o,
+    frustum_rig_body(Fb[2 * b], Fb[2 * b + 1], i, T.M, T.pos, T.normal, T.min_d, T.max_d, is_bad + T.flags, in_view1 + o, in_view2 + o, track1 + ot, track2 + ot, level1 + o,
                      level2 + o, q1 + o, q2 + o);
 }
 
@@ -891,17 +856,17 @@ __global__ void __launch_bounds__(256) k_lastframe_queries_rig(const FrustumPara
 // occupied slot).  A lane claims the slots whose occupancy its writes change; it is dirty when an earlier lane of the round claims a candidate of
 // either of its windows; lanes before the first dirty one commit.  The sequential last writer of a slot is the largest point index (atomicMax on
 // assigned); among the lanes committing in one round, the largest lane writing a slot sets its occupancy.
-// occupied0: [B][2 cap] bytes in the joint slot layout or NULL; has_obs: [M] (MapPoints form) or [B][M] (LastFrame form) or NULL; l2r / r2l: [B][cap];
+// Frame b has maps[b].M points; its query rows (LastFrame form: and last_angle) start at maps[b].offset, its has_obs row at maps[b].flags.
+// occupied0: [B][2 cap] bytes in the joint slot layout or NULL; has_obs: NULL = all observed; l2r / r2l: [B][cap];
 // assigned: [B][2 cap]; nmatches: [B].  dynamic LDS: claim word per slot (2 cap words) | occupancy byte per slot (2 cap, 16-byte multiple) | LastFrame:
 // two events per query (2 M words, slot * 32 + bin).
-// MAPS (k_rig_local_accept_maps): frame b has maps[b].M points; its query rows and has_obs start at maps[b].offset.
-template <bool LASTFRAME, bool MAPS = false>
-__device__ __forceinline__ void rig_accept_body(int M, int cap, const int* __restrict__ n1, const int* __restrict__ n2, const int* __restrict__ qs1,
+template <bool LASTFRAME>
+__device__ __forceinline__ void rig_accept_body(const FrameMapRec* __restrict__ maps, int cap, const int* __restrict__ n1, const int* __restrict__ n2, const int* __restrict__ qs1,
                                                 const int* __restrict__ qc1, const int* __restrict__ qs2, const int* __restrict__ qc2,
                                                 const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0, const uint8_t* __restrict__ has_obs,
                                                 const int* __restrict__ l2r, const int* __restrict__ r2l, float nnratio, int th_high, int* __restrict__ assigned,
                                                 int* __restrict__ nmatches, const float* __restrict__ last_angle, const KeyPointRec* __restrict__ kps1,
-                                                const KeyPointRec* __restrict__ kps2, int check_ori, const FrameMapRec* __restrict__ maps = nullptr) {
+                                                const KeyPointRec* __restrict__ kps2, int check_ori) {
     ORBX_DYN_SMEM(smem);
     const int S = 2 * cap;
     unsigned* s_claim = (unsigned*)smem;
@@ -911,13 +876,12 @@ __device__ __forceinline__ void rig_accept_body(int M, int cap, const int* __res
     const int lane = lane_id();
     const size_t b = blockIdx.x;
     const int NL = n1[b], NR = n2[b], NS = NL + NR;
-    if (MAPS) M = maps[b].M;
-    const size_t qo = MAPS ? (size_t)maps[b].offset : b * (size_t)M;
+    const int M = maps[b].M;
+    const size_t qo = (size_t)maps[b].offset;
     qs1 += qo; qc1 += qo; qs2 += qo; qc2 += qo; assigned += b * (size_t)S;
-    if (MAPS && has_obs) has_obs += qo;
+    if (has_obs) has_obs += maps[b].flags;
     if (LASTFRAME) {
-        if (has_obs) has_obs += b * (size_t)M;
-        last_angle += b * (size_t)M; kps1 += b * (size_t)cap; kps2 += b * (size_t)cap;
+        last_angle += qo; kps1 += b * (size_t)cap; kps2 += b * (size_t)cap;
         if (lane < 32) s_hist[lane] = 0;
     } else { l2r += b * (size_t)cap; r2l += b * (size_t)cap; }
     for (int i = lane; i < S; i += 64) {
@@ -1053,27 +1017,20 @@ __device__ __forceinline__ void rig_accept_body(int M, int cap, const int* __res
     if (lane == 0) nmatches[b] = nm;
 }
 
-__global__ void __launch_bounds__(64) k_rig_local_accept(int M, int cap, const int* __restrict__ n1, const int* __restrict__ n2, const int* __restrict__ qs1,
-                                                         const int* __restrict__ qc1, const int* __restrict__ qs2, const int* __restrict__ qc2,
-                                                         const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0, const uint8_t* __restrict__ has_obs,
-                                                         const int* __restrict__ l2r, const int* __restrict__ r2l, float nnratio, int th_high,
-                                                         int* __restrict__ assigned, int* __restrict__ nmatches) {
-    rig_accept_body<false>(M, cap, n1, n2, qs1, qc1, qs2, qc2, entries, occupied0, has_obs, l2r, r2l, nnratio, th_high, assigned, nmatches, nullptr, nullptr, nullptr, 0);
+__global__ void __launch_bounds__(64) k_rig_local_accept(const FrameMapRec* __restrict__ maps, int cap, const int* __restrict__ n1, const int* __restrict__ n2,
+                                                         const int* __restrict__ qs1, const int* __restrict__ qc1, const int* __restrict__ qs2,
+                                                         const int* __restrict__ qc2, const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0,
+                                                         const uint8_t* __restrict__ has_obs, const int* __restrict__ l2r, const int* __restrict__ r2l, float nnratio,
+                                                         int th_high, int* __restrict__ assigned, int* __restrict__ nmatches) {
+    rig_accept_body<false>(maps, cap, n1, n2, qs1, qc1, qs2, qc2, entries, occupied0, has_obs, l2r, r2l, nnratio, th_high, assigned, nmatches, nullptr, nullptr, nullptr, 0);
 }
-__global__ void __launch_bounds__(64) k_rig_local_accept_maps(const FrameMapRec* __restrict__ maps, int cap, const int* __restrict__ n1, const int* __restrict__ n2,
-                                                              const int* __restrict__ qs1, const int* __restrict__ qc1, const int* __restrict__ qs2,
-                                                              const int* __restrict__ qc2, const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0,
-                                                              const uint8_t* __restrict__ has_obs, const int* __restrict__ l2r, const int* __restrict__ r2l, float nnratio,
-                                                              int th_high, int* __restrict__ assigned, int* __restrict__ nmatches) {
-    rig_accept_body<false, true>(0, cap, n1, n2, qs1, qc1, qs2, qc2, entries, occupied0, has_obs, l2r, r2l, nnratio, th_high, assigned, nmatches, nullptr, nullptr, nullptr, 0,
-                                 maps);
-}
-__global__ void __launch_bounds__(64) k_rig_lastframe_accept(int M, int cap, const int* __restrict__ n1, const int* __restrict__ n2, const int* __restrict__ qs1,
-                                                             const int* __restrict__ qc1, const int* __restrict__ qs2, const int* __restrict__ qc2,
-                                                             const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0, const uint8_t* __restrict__ has_obs,
-                                                             int th_high, int* __restrict__ assigned, int* __restrict__ nmatches, const float* __restrict__ last_angle,
-                                                             const KeyPointRec* __restrict__ kps1, const KeyPointRec* __restrict__ kps2, int check_ori) {
-    rig_accept_body<true>(M, cap, n1, n2, qs1, qc1, qs2, qc2, entries, occupied0, has_obs, nullptr, nullptr, 0.0f, th_high, assigned, nmatches, last_angle, kps1, kps2, check_ori);
+__global__ void __launch_bounds__(64) k_rig_lastframe_accept(const FrameMapRec* __restrict__ maps, int cap, const int* __restrict__ n1, const int* __restrict__ n2,
+                                                             const int* __restrict__ qs1, const int* __restrict__ qc1, const int* __restrict__ qs2,
+                                                             const int* __restrict__ qc2, const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0,
+                                                             const uint8_t* __restrict__ has_obs, int th_high, int* __restrict__ assigned, int* __restrict__ nmatches,
+                                                             const float* __restrict__ last_angle, const KeyPointRec* __restrict__ kps1,
+                                                             const KeyPointRec* __restrict__ kps2, int check_ori) {
+    rig_accept_body<true>(maps, cap, n1, n2, qs1, qc1, qs2, qc2, entries, occupied0, has_obs, nullptr, nullptr, 0.0f, th_high, assigned, nmatches, last_angle, kps1, kps2, check_ori);
 }
 
 // Frame::ComputeStereoFromRGBD (src/Frame.cc:1361-1391) for B frames: mvDepth[i] = imDepth.at<float>(v, u) at the (distorted) keypoint, truncated

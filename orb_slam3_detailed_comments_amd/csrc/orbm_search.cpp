@@ -364,8 +364,7 @@ void launch_frustum(orbx_extractor* h, const FrustumParams& F, int M, const floa
                     uint8_t* track, AreaQuery* queries, int* counter) {
     const TrackBlock T(M);
     dim3 grid((M + 255) / 256, 1, 1), blk(256, 1, 1);
-    ORBX_LAUNCH(k_frustum, grid, blk, 0, h->s0, F, M, pos, normal, min_d, max_d, bad, track + T.in_view, (float*)track, (int*)(track + T.level), queries, counter,
-                (const FrustumParams*)nullptr);
+    ORBX_LAUNCH(k_frustum, grid, blk, 0, h->s0, F, M, pos, normal, min_d, max_d, bad, track + T.in_view, (float*)track, (int*)(track + T.level), queries, counter);
 }
 int enqueue_frustum(orbx_extractor* h, const OrbmFrustumView* V, const OrbmWorldPointView* P, float cos_limit, bool with_queries, float th, int far_points, float th_far,
                     FrustumDev* out, const FrustumParams* second = nullptr, FrustumDev* out2 = nullptr) {
@@ -614,50 +613,57 @@ GridParams grid_from_view(const OrbmFrustumView& v) {
 }
 // entries of the candidate pool: what the last batch grew it to, or `expected` for this one; the kernels count entries in an int
 size_t batch_pool(const orbx_extractor* h, size_t expected) { return std::min<size_t>(std::max(h->lp_pool, expected), 0x7fffffff / 2); }
-// The local maps of a batched SearchLocalPoints: ONE resident set and one pair of flag arrays for every frame (maps == nullptr: frame b's scratch rows at
-// b * M), or one OrbmFrameMap per frame (frame b's rows at the prefix sum of M_b, flags uploaded per frame, the table of the k_*_maps kernels in the upload)
+// The local maps of a batched SearchLocalPoints, staged as the table the kernels read (FrameMapRec, orbx_types.h): ONE resident set and one pair of flag
+// arrays for every frame (maps == nullptr: the set B times, frame b's scratch rows at b * M, the flags uploaded once), or one OrbmFrameMap per frame
+// (frame b's rows and flags at the prefix sum of M_b)
 struct BatchMaps {
     const orbm_points* one; const uint8_t *is_bad, *has_obs; const OrbmFrameMap* maps; int B;
     int m_max = 0; size_t rows = 1, flags = 1;     // largest map; scratch rows of the batch; bytes of ONE uploaded flag array
-    std::vector<int> M;                            // per frame (per-frame form)
-    size_t table_bytes() const { return maps ? sizeof(FrameMapRec) * (size_t)B : 0; }
+    std::vector<int> M;                            // per frame
+    size_t table_bytes() const { return sizeof(FrameMapRec) * (size_t)B; }
+    const orbm_points* set(int b) const { return maps ? maps[b].points : one; }
     int plan(int device) {
-        if (!maps) {
-            if (one->device != device) return fail(ORBX_E_ARG, "map points live on another device");
-            m_max = one->M; flags = m_max > 0 ? m_max : 1; rows = (size_t)B * flags;
-            return ORBX_OK;
-        }
+        if (!maps && one->device != device) return fail(ORBX_E_ARG, "map points live on another device");
         size_t sum = 0;
         M.resize(B);
         for (int b = 0; b < B; b++) {
-            const orbm_points* s = maps[b].points;
+            const orbm_points* s = set(b);
             if (s && s->device != device) return fail(ORBX_E_ARG, "frame %d: its map points live on another device", b);
             M[b] = s && s->M > 0 ? s->M : 0; sum += (size_t)M[b]; m_max = std::max(m_max, M[b]);
         }
         if (sum > 0x7fffffff / 32) return fail(ORBX_E_CAPACITY, "%zu map points in one batch", sum);      // (offsets are ints; 5 floats of track per row)
-        rows = flags = sum > 0 ? sum : 1;
+        rows = sum > 0 ? sum : 1;
+        flags = maps ? rows : (size_t)std::max(m_max, 1);
         return ORBX_OK;
     }
+    static void stage_flags(uint8_t* bad, uint8_t* obs, const uint8_t* is_bad, const uint8_t* has_obs, size_t m) {
+        if (is_bad) memcpy(bad, is_bad, m); else memset(bad, 0, m);
+        if (has_obs) memcpy(obs, has_obs, m); else memset(obs, 1, m);
+    }
     void stage(uint8_t* tab, uint8_t* bad, uint8_t* obs) const {
-        if (!maps) {
-            if (is_bad) memcpy(bad, is_bad, flags); else memset(bad, 0, flags);
-            if (has_obs) memcpy(obs, has_obs, flags); else memset(obs, 1, flags);
-            return;
-        }
         FrameMapRec* T = (FrameMapRec*)tab;
         size_t o = 0;
         for (int b = 0; b < B; b++) {
-            const orbm_points* s = maps[b].points; const size_t m = (size_t)M[b];
+            const orbm_points* s = set(b); const size_t m = (size_t)M[b];
             FrameMapRec r; memset(&r, 0, sizeof r);
             if (m) { r.pos = s->pos; r.normal = s->normal; r.min_d = s->min_d; r.max_d = s->max_d; r.desc = s->desc; }
-            r.M = (int)m; r.offset = (int)o;
+            r.M = (int)m; r.offset = (int)o; r.flags = maps ? (int)o : 0;
             T[b] = r;
-            if (maps[b].is_bad) memcpy(bad + o, maps[b].is_bad, m); else memset(bad + o, 0, m);
-            if (maps[b].has_obs) memcpy(obs + o, maps[b].has_obs, m); else memset(obs + o, 1, m);
+            if (maps) stage_flags(bad + o, obs + o, maps[b].is_bad, maps[b].has_obs, m);
             o += m;
         }
+        if (!maps) stage_flags(bad, obs, is_bad, has_obs, (size_t)m_max);
     }
 };
+// the table of a projection batch (LastFrame / KeyFrame points): frame b's M rows of the uploaded descriptors (d_desc: their device address), everything at b * M
+void stage_uniform_table(uint8_t* tab, int B, int M, const unsigned long long* d_desc) {
+    FrameMapRec* T = (FrameMapRec*)tab;
+    for (int b = 0; b < B; b++) {
+        FrameMapRec r; memset(&r, 0, sizeof r);
+        r.desc = d_desc + 4 * (size_t)b * (size_t)M; r.M = M; r.offset = r.flags = b * M;
+        T[b] = r;
+    }
+}
 // the grid of one camera for B frames (k_grid_build: cell_of, cell_start, cell_items)
 struct GridBlock {
     size_t cof, cst, cit;
@@ -697,10 +703,10 @@ int batch_fetch(orbx_extractor* h, size_t slots, const char* what, int* assigned
     const size_t B1 = h->lp_B, M1 = h->lp_M > 0 ? h->lp_M : 0;
     const ResultBlock res(B1, slots);
     const size_t view_off[2] = {h->lp_o_view, h->lp_o_view_r};
-    // mbTrackInView on the device: [B][M], or - frames with their own maps - frame b's M_b bytes at the prefix sum; the caller's rows are M = max M_b apart
+    // mbTrackInView on the device: frame b's M_b bytes at the prefix sum (one set for every frame: [B][M]); the caller's rows are M = max M_b apart
     const std::vector<int>& Mb = h->lp_maps_M;
-    size_t vb = B1 * M1;
-    if (!Mb.empty()) { vb = 0; for (int m : Mb) vb += (size_t)m; }
+    size_t vb = 0;
+    if (fetch_views) for (int m : Mb) vb += (size_t)m;
     uint8_t* hp = h->h_lp_out.p;
     int e = rt::copy_d2h(hp, h->d_lp.p + h->lp_o_counter, res.bytes, h->s0);
     if (fetch_views) for (int v = 0; v < nviews; v++) e |= rt::copy_d2h(hp + al16(res.bytes) + v * vb, h->d_lp.p + view_off[v], vb, h->s0);
@@ -720,7 +726,6 @@ int batch_fetch(orbx_extractor* h, size_t slots, const char* what, int* assigned
     }
     if (fetch_views) for (int v = 0; v < nviews; v++) if (views[v]) {
         const uint8_t* src = hp + al16(res.bytes) + v * vb;
-        if (Mb.empty()) { memcpy(views[v], src, vb); continue; }
         for (size_t b = 0; b < B1; b++) {
             const size_t m = (size_t)Mb[b];
             memcpy(views[v] + b * M1, src, m); memset(views[v] + b * M1 + m, 0, M1 - m);
@@ -752,7 +757,7 @@ int local_points_batch(orbx_extractor* h, int first, int B, const OrbmFrustumVie
     const size_t u_f = u.take(sizeof(FrustumParams) * B1), u_tab = u.take(P.table_bytes()), u_bad = u.take(P.flags), u_obs = u.take(P.flags),
                  u_occ = u.take(occupied ? B1 * C1 : 0), u_total = u.o;
     // device block: upload | uRight of "no stereo" | grid | queries | track | level | in_view | q_start | q_count | result | entry pool
-    // (`rows` of each: B x M, or the sum of the frames' own M_b)
+    // (`rows` of each: the sum of the frames' M_b; B x M for one set)
     Bump d(u_total);
     const size_t o_ur = d.take(use_u_right ? 0 : 4 * B1 * C1);
     const GridBlock G(d, B1, C1);
@@ -785,26 +790,18 @@ int local_points_batch(orbx_extractor* h, int first, int B, const OrbmFrustumVie
     const FrameMapRec* d_tab = (const FrameMapRec*)(dp + u_tab);
     const dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);              // M: of the one set, or the largest of the frames' own
     if (M <= 0) rt::memset_async(d_counter, 0, 16, h->s0);
-    else if (maps) {
-        ORBX_LAUNCH(k_frustum_maps, grid, blk, 0, h->s0, (const FrustumParams*)(dp + u_f), d_tab, (const uint8_t*)(dp + u_bad), dp + o_view, (float*)(dp + o_trk),
+    else {
+        ORBX_LAUNCH(k_frustum_batch, grid, blk, 0, h->s0, (const FrustumParams*)(dp + u_f), d_tab, (const uint8_t*)(dp + u_bad), dp + o_view, (float*)(dp + o_trk),
                     (int*)(dp + o_lvl), (AreaQuery*)(dp + o_q), d_counter);
-        ORBX_LAUNCH(k_area_search_threads_maps, grid, blk, 0, h->s0, (const AreaQuery*)(dp + o_q), d_tab, kps, ur, fdesc, g, (const int*)(dp + G.cst), (const int*)(dp + G.cit), 1,
+        ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, h->s0, (const AreaQuery*)(dp + o_q), d_tab, kps, ur, fdesc, g, (const int*)(dp + G.cst), (const int*)(dp + G.cit), 1,
                     d_counter, (int)pool, (int*)(dp + o_qs), (int*)(dp + o_qc), (int2*)(dp + o_pool), cap);
-    } else {
-        FrustumParams dummy; memset(&dummy, 0, sizeof dummy);
-        ORBX_LAUNCH(k_frustum, grid, blk, 0, h->s0, dummy, M, points->pos, points->normal, points->min_d, points->max_d, (const uint8_t*)(dp + u_bad),
-                    dp + o_view, (float*)(dp + o_trk), (int*)(dp + o_lvl), (AreaQuery*)(dp + o_q), d_counter, (const FrustumParams*)(dp + u_f));
-        ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, h->s0, (const AreaQuery*)(dp + o_q), points->desc, M, kps, ur, fdesc, g, (const int*)(dp + G.cst), (const int*)(dp + G.cit), 1,
-                    d_counter, (int)pool, (int*)(dp + o_qs), (int*)(dp + o_qc), (int2*)(dp + o_pool), cap, 0);
     }
     {
         dim3 grida(B, 1, 1), blka(64, 1, 1);
         const size_t smem = smem_accept;
         const uint8_t* d_occ = occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr;
-        if (maps) ORBX_LAUNCH(k_local_accept_maps, grida, blka, smem, h->s0, d_tab, cap, nper, (const int*)(dp + o_qs), (const int*)(dp + o_qc), (const int2*)(dp + o_pool), d_occ,
-                              (const uint8_t*)(dp + u_obs), nnratio, TH_HIGH, d_assigned, d_nmatch);
-        else ORBX_LAUNCH(k_local_accept, grida, blka, smem, h->s0, M, cap, nper, (const int*)(dp + o_qs), (const int*)(dp + o_qc), (const int2*)(dp + o_pool), d_occ,
-                         (const uint8_t*)(dp + u_obs), nnratio, TH_HIGH, d_assigned, d_nmatch);
+        ORBX_LAUNCH(k_local_accept, grida, blka, smem, h->s0, d_tab, cap, nper, (const int*)(dp + o_qs), (const int*)(dp + o_qc), (const int2*)(dp + o_pool), d_occ,
+                    (const uint8_t*)(dp + u_obs), nnratio, TH_HIGH, d_assigned, d_nmatch);
     }
     if (h->profile) rt::event_record(h->ev_stage[ST_MATCH][1], h->s0);
     if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
@@ -844,9 +841,9 @@ int projection_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView*
     if (smem_accept + 1024 > rt::lds_limit(h->device)) { h->lp_B = 0; return fail(ORBX_E_CAPACITY, "%d keypoints and %d last-frame points per frame need %zu bytes of LDS in the accept kernel", cap, M, smem_accept); }
     h->lp_B = 0;
     if (h->lp_pending) rt::event_sync(h->ev_lp);
-    // upload block: poses | the rows (n_last .. descriptors) | occupancy | a key frame's mfMaxDistance rows
+    // upload block: poses | the table of the frames' rows | the rows (n_last .. descriptors) | occupancy | a key frame's mfMaxDistance rows
     Bump u;
-    const size_t u_f = u.take(sizeof(FrustumParams) * B1);
+    const size_t u_f = u.take(sizeof(FrustumParams) * B1), u_tab = u.take(sizeof(FrameMapRec) * B1);
     const PointRowsUpload U(u, B1, M1);
     const size_t u_occ = u.take(occupied ? B1 * C1 : 0), u_mxd = u.take(keyframe ? 4 * B1 * M1 : 0), u_total = u.o;
     Bump d(u_total);
@@ -866,6 +863,7 @@ int projection_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView*
         Fp[b].forward = forward ? forward[b] != 0 : 0; Fp[b].backward = backward ? backward[b] != 0 : 0; Fp[b].debug_flags = h->debug_stereo_flags;
     }
     U.stage(hp, *last, B1, M1);
+    stage_uniform_table(hp + u_tab, B, M, (const unsigned long long*)(dp + U.u_desc));
     if (keyframe) memcpy(hp + u_mxd, last->max_distance, 4 * B1 * M1);
     if (occupied) memcpy(hp + u_occ, occupied, B1 * C1);
     if (rt::copy_h2d(dp, hp, u_total, h->s0) || rt::event_record(h->ev_lp, h->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
@@ -879,6 +877,7 @@ int projection_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView*
     int* d_counter = (int*)(dp + o_res); int* d_nmatch = (int*)(dp + o_res + res.nmatches); int* d_assigned = (int*)(dp + o_res + res.assigned);
     if (h->profile) rt::event_record(h->ev_stage[ST_MATCH][0], h->s0);
     const dim3 blk(256, 1, 1);
+    const FrameMapRec* d_tab = (const FrameMapRec*)(dp + u_tab);
     {
         dim3 grid(B, 1, 1), blkg(kGridThreads, 1, 1);
         ORBX_LAUNCH(k_grid_build, grid, blkg, 0, h->s0, kps, 0, g, (int*)(dp + G.cof), (int*)(dp + G.cst), (int*)(dp + G.cit), nper, cap);
@@ -889,13 +888,13 @@ int projection_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView*
                                   (const uint8_t*)(dp + U.u_val), (const float*)(dp + U.u_oct), (const float*)(dp + u_mxd), (AreaQuery*)(dp + o_q), d_counter);
         else ORBX_LAUNCH(k_lastframe_queries, grid, blk, 0, h->s0, (const FrustumParams*)(dp + u_f), M, (const int*)(dp + U.u_n), (const float*)(dp + U.u_pos),
                          (const uint8_t*)(dp + U.u_val), (const int*)(dp + U.u_oct), (AreaQuery*)(dp + o_q), d_counter);
-        ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, h->s0, (const AreaQuery*)(dp + o_q), (const unsigned long long*)(dp + U.u_desc), M, kps, ur, fdesc, g, (const int*)(dp + G.cst),
-                    (const int*)(dp + G.cit), keyframe ? 0 : 1, d_counter, (int)pool, (int*)(dp + o_qs), (int*)(dp + o_qc), (int2*)(dp + o_pool), cap, 1);
+        ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, h->s0, (const AreaQuery*)(dp + o_q), d_tab, kps, ur, fdesc, g, (const int*)(dp + G.cst), (const int*)(dp + G.cit),
+                    keyframe ? 0 : 1, d_counter, (int)pool, (int*)(dp + o_qs), (int*)(dp + o_qc), (int2*)(dp + o_pool), cap);
     }
     {
         dim3 grid(B, 1, 1), blka(64, 1, 1);
         const size_t smem = smem_accept;
-        ORBX_LAUNCH(k_lastframe_accept, grid, blka, smem, h->s0, M, cap, nper, (const int*)(dp + o_qs), (const int*)(dp + o_qc), (const int2*)(dp + o_pool),
+        ORBX_LAUNCH(k_lastframe_accept, grid, blka, smem, h->s0, d_tab, cap, nper, (const int*)(dp + o_qs), (const int*)(dp + o_qc), (const int2*)(dp + o_pool),
                     occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr, (const uint8_t*)(dp + U.u_obs), th_accept, d_assigned, d_nmatch,
                     (const float*)(dp + U.u_ang), kps, check_ori);
     }
@@ -2098,11 +2097,11 @@ struct RigBlock {
     }
 };
 // grids of both cameras, then the window searches of both query sets into one entry pool (the right-coordinate gate off: a rig frame has no mvuRight)
-// queries(): the launch that writes both query sets (and zeroes the pool counter).  maps (device) != NULL: the frames bring their own local maps - M is the
-// largest, the query rows and descriptors come from the table
+// queries(): the launch that writes both query sets (and zeroes the pool counter).  maps (device): the table of the frames' query rows and descriptors, M the
+// largest of its M_b
 template <typename Queries>
 void rig_searches(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, int M, const RigBlock& K, uint8_t* dp, const GridParams& g,
-                  const unsigned long long* qdesc, int qdesc_per_frame, const FrameMapRec* maps, size_t pool, const Queries& queries) {
+                  const FrameMapRec* maps, size_t pool, const Queries& queries) {
     const int cap = L->kp_total_cap;
     const KeyPointRec* kps1 = L->d_kps.p + (size_t)lf * cap; const KeyPointRec* kps2 = R->d_kps.p + (size_t)rf * cap;
     int* d_counter = (int*)(dp + K.res);
@@ -2115,17 +2114,10 @@ void rig_searches(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, i
     queries();
     const float* no_ur = (const float*)dp;                       // never read: gate_right = 0
     dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
-    if (maps) {
-        ORBX_LAUNCH(k_area_search_threads_maps, grid, blk, 0, L->s0, (const AreaQuery*)(dp + K.q1), maps, kps1, no_ur, L->d_desc.p + (size_t)lf * cap * 4, g,
-                    (const int*)(dp + K.g1.cst), (const int*)(dp + K.g1.cit), 0, d_counter, (int)pool, (int*)(dp + K.qs1), (int*)(dp + K.qc1), (int2*)(dp + K.pool), cap);
-        ORBX_LAUNCH(k_area_search_threads_maps, grid, blk, 0, L->s0, (const AreaQuery*)(dp + K.q2), maps, kps2, no_ur, R->d_desc.p + (size_t)rf * cap * 4, g,
-                    (const int*)(dp + K.g2.cst), (const int*)(dp + K.g2.cit), 0, d_counter, (int)pool, (int*)(dp + K.qs2), (int*)(dp + K.qc2), (int2*)(dp + K.pool), cap);
-        return;
-    }
-    ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, L->s0, (const AreaQuery*)(dp + K.q1), qdesc, M, kps1, no_ur, L->d_desc.p + (size_t)lf * cap * 4, g,
-                (const int*)(dp + K.g1.cst), (const int*)(dp + K.g1.cit), 0, d_counter, (int)pool, (int*)(dp + K.qs1), (int*)(dp + K.qc1), (int2*)(dp + K.pool), cap, qdesc_per_frame);
-    ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, L->s0, (const AreaQuery*)(dp + K.q2), qdesc, M, kps2, no_ur, R->d_desc.p + (size_t)rf * cap * 4, g,
-                (const int*)(dp + K.g2.cst), (const int*)(dp + K.g2.cit), 0, d_counter, (int)pool, (int*)(dp + K.qs2), (int*)(dp + K.qc2), (int2*)(dp + K.pool), cap, qdesc_per_frame);
+    ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, L->s0, (const AreaQuery*)(dp + K.q1), maps, kps1, no_ur, L->d_desc.p + (size_t)lf * cap * 4, g,
+                (const int*)(dp + K.g1.cst), (const int*)(dp + K.g1.cit), 0, d_counter, (int)pool, (int*)(dp + K.qs1), (int*)(dp + K.qc1), (int2*)(dp + K.pool), cap);
+    ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, L->s0, (const AreaQuery*)(dp + K.q2), maps, kps2, no_ur, R->d_desc.p + (size_t)rf * cap * 4, g,
+                (const int*)(dp + K.g2.cst), (const int*)(dp + K.g2.cit), 0, d_counter, (int)pool, (int*)(dp + K.qs2), (int*)(dp + K.qc2), (int2*)(dp + K.pool), cap);
 }
 size_t rig_accept_lds(int cap, int events) { const size_t S = 2 * (size_t)cap; return 4 * S + al16(S) + 4 * (size_t)events + 64; }
 // orbm_search_local_points_rig_batch (one resident set, `maps` == NULL) and orbm_search_local_points_rig_batch_maps (maps[b] = frame b's own)
@@ -2148,7 +2140,7 @@ int local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf,
     Bump u;
     const size_t u_f = u.take(sizeof(FrustumParams) * 2 * B1), u_tab = u.take(P.table_bytes()), u_bad = u.take(P.flags), u_obs = u.take(P.flags),
                  u_occ = u.take(occupied ? B1 * S1 : 0), u_total = u.o;
-    // behind the common block: per camera track [5 rows] | level [rows] | in_view [rows]   (rows: B x M, or the sum of the frames' own M_b)
+    // behind the common block: per camera track [5 rows] | level [rows] | in_view [rows]   (rows: the sum of the frames' M_b; B x M for one set)
     Bump t;
     const size_t o_trk1 = t.take(20 * rows), o_trk2 = t.take(20 * rows), o_lvl1 = t.take(4 * rows), o_lvl2 = t.take(4 * rows), o_view1 = t.take(rows), o_view2 = t.take(rows);
     const RigBlock K(u_total, B1, rows, C1, t.o);
@@ -2168,27 +2160,20 @@ int local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf,
     L->lp_pending = true;
     if (L != R) { record_done_if_pending(R); rt::stream_wait_event(L->s0, R->ev_done); }
     uint8_t* dx = dp + ox;
-    const FrameMapRec* d_tab = maps ? (const FrameMapRec*)(dp + u_tab) : nullptr;
+    const FrameMapRec* d_tab = (const FrameMapRec*)(dp + u_tab);
     if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][0], L->s0);
-    rig_searches(L, lf, R, rf, B, M, K, dp, grid_from_view(frames[0].left), points ? points->desc : nullptr, 0, d_tab, pool, [&]() {
+    rig_searches(L, lf, R, rf, B, M, K, dp, grid_from_view(frames[0].left), d_tab, pool, [&]() {
         dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
-        if (maps) ORBX_LAUNCH(k_frustum_rig_maps, grid, blk, 0, L->s0, (const FrustumParams*)(dp + u_f), d_tab, (const uint8_t*)(dp + u_bad), dx + o_view1, dx + o_view2,
-                              (float*)(dx + o_trk1), (float*)(dx + o_trk2), (int*)(dx + o_lvl1), (int*)(dx + o_lvl2), (AreaQuery*)(dp + K.q1), (AreaQuery*)(dp + K.q2),
-                              (int*)(dp + K.res));
-        else ORBX_LAUNCH(k_frustum_rig, grid, blk, 0, L->s0, (const FrustumParams*)(dp + u_f), M, points->pos, points->normal, points->min_d, points->max_d,
-                         (const uint8_t*)(dp + u_bad), dx + o_view1, dx + o_view2, (float*)(dx + o_trk1), (float*)(dx + o_trk2), (int*)(dx + o_lvl1), (int*)(dx + o_lvl2),
-                         (AreaQuery*)(dp + K.q1), (AreaQuery*)(dp + K.q2), (int*)(dp + K.res));
+        ORBX_LAUNCH(k_frustum_rig, grid, blk, 0, L->s0, (const FrustumParams*)(dp + u_f), d_tab, (const uint8_t*)(dp + u_bad), dx + o_view1, dx + o_view2,
+                    (float*)(dx + o_trk1), (float*)(dx + o_trk2), (int*)(dx + o_lvl1), (int*)(dx + o_lvl2), (AreaQuery*)(dp + K.q1), (AreaQuery*)(dp + K.q2),
+                    (int*)(dp + K.res));
     });
     {
         dim3 grid(B, 1, 1), blk(64, 1, 1);
         const uint8_t* d_occ = occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr;
-        if (maps) ORBX_LAUNCH(k_rig_local_accept_maps, grid, blk, smem_accept, L->s0, d_tab, cap, (const int*)(L->d_nm.p + lf), (const int*)(R->d_nm.p + rf),
-                              (const int*)(dp + K.qs1), (const int*)(dp + K.qc1), (const int*)(dp + K.qs2), (const int*)(dp + K.qc2), (const int2*)(dp + K.pool), d_occ,
-                              (const uint8_t*)(dp + u_obs), (const int*)L->d_l2r.p, (const int*)L->d_r2l.p, nnratio, TH_HIGH, (int*)(dp + K.res + K.r.assigned),
-                              (int*)(dp + K.res + K.r.nmatches));
-        else ORBX_LAUNCH(k_rig_local_accept, grid, blk, smem_accept, L->s0, M, cap, (const int*)(L->d_nm.p + lf), (const int*)(R->d_nm.p + rf), (const int*)(dp + K.qs1),
-                         (const int*)(dp + K.qc1), (const int*)(dp + K.qs2), (const int*)(dp + K.qc2), (const int2*)(dp + K.pool), d_occ, (const uint8_t*)(dp + u_obs),
-                         (const int*)L->d_l2r.p, (const int*)L->d_r2l.p, nnratio, TH_HIGH, (int*)(dp + K.res + K.r.assigned), (int*)(dp + K.res + K.r.nmatches));
+        ORBX_LAUNCH(k_rig_local_accept, grid, blk, smem_accept, L->s0, d_tab, cap, (const int*)(L->d_nm.p + lf), (const int*)(R->d_nm.p + rf), (const int*)(dp + K.qs1),
+                    (const int*)(dp + K.qc1), (const int*)(dp + K.qs2), (const int*)(dp + K.qc2), (const int2*)(dp + K.pool), d_occ, (const uint8_t*)(dp + u_obs),
+                    (const int*)L->d_l2r.p, (const int*)L->d_r2l.p, nnratio, TH_HIGH, (int*)(dp + K.res + K.r.assigned), (int*)(dp + K.res + K.r.nmatches));
     }
     if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][1], L->s0);
     if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
@@ -2228,9 +2213,9 @@ int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orb
     if (smem_accept + 1024 > rt::lds_limit(L->device))
         return fail(ORBX_E_CAPACITY, "%d keypoints per camera and %d last-frame points per frame need %zu bytes of LDS in the rig accept kernel", cap, M, smem_accept);
     if (L->lp_pending) rt::event_sync(L->ev_lp);
-    // upload: camera-1 parameters per frame | n_last | pos | valid | octave | angle | has_obs | descriptors | occupancy [B][2 cap]
+    // upload: camera-1 parameters per frame | the table of the frames' rows | n_last | pos | valid | octave | angle | has_obs | descriptors | occupancy [B][2 cap]
     Bump u;
-    const size_t u_f = u.take(sizeof(FrustumParams) * B1);
+    const size_t u_f = u.take(sizeof(FrustumParams) * B1), u_tab = u.take(sizeof(FrameMapRec) * B1);
     const PointRowsUpload U(u, B1, M1);
     const size_t u_occ = u.take(occupied ? B1 * S1 : 0), u_total = u.o;
     const RigBlock K(u_total, B1, B1 * M1, C1, 0);
@@ -2245,20 +2230,22 @@ int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orb
         Fp[b].forward = forward ? forward[b] != 0 : 0; Fp[b].backward = backward ? backward[b] != 0 : 0; Fp[b].debug_flags = L->debug_stereo_flags;
     }
     U.stage(hp, last_frame_rows(last), B1, M1);
+    stage_uniform_table(hp + u_tab, B, M, (const unsigned long long*)(dp + U.u_desc));
     if (occupied) memcpy(hp + u_occ, occupied, B1 * S1);
     if (rt::copy_h2d(dp, hp, u_total, L->s0) || rt::event_record(L->ev_lp, L->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
     L->lp_pending = true;
     if (L != R) { record_done_if_pending(R); rt::stream_wait_event(L->s0, R->ev_done); }
     RigRelPose T; memcpy(T.q, trl, sizeof T.q); memcpy(T.t, trl + 4, sizeof T.t);
     if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][0], L->s0);
-    rig_searches(L, lf, R, rf, B, M, K, dp, grid_from_view(cur[0].left), (const unsigned long long*)(dp + U.u_desc), 1, nullptr, pool, [&]() {
+    const FrameMapRec* d_tab = (const FrameMapRec*)(dp + u_tab);
+    rig_searches(L, lf, R, rf, B, M, K, dp, grid_from_view(cur[0].left), d_tab, pool, [&]() {
         dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
         ORBX_LAUNCH(k_lastframe_queries_rig, grid, blk, 0, L->s0, (const FrustumParams*)(dp + u_f), M, (const int*)(dp + U.u_n), (const float*)(dp + U.u_pos),
                     (const uint8_t*)(dp + U.u_val), (const int*)(dp + U.u_oct), T, (AreaQuery*)(dp + K.q1), (AreaQuery*)(dp + K.q2), (int*)(dp + K.res));
     });
     {
         dim3 grid(B, 1, 1), blk(64, 1, 1);
-        ORBX_LAUNCH(k_rig_lastframe_accept, grid, blk, smem_accept, L->s0, M, cap, (const int*)(L->d_nm.p + lf), (const int*)(R->d_nm.p + rf), (const int*)(dp + K.qs1),
+        ORBX_LAUNCH(k_rig_lastframe_accept, grid, blk, smem_accept, L->s0, d_tab, cap, (const int*)(L->d_nm.p + lf), (const int*)(R->d_nm.p + rf), (const int*)(dp + K.qs1),
                     (const int*)(dp + K.qc1), (const int*)(dp + K.qs2), (const int*)(dp + K.qc2), (const int2*)(dp + K.pool),
                     occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr, (const uint8_t*)(dp + U.u_obs), TH_HIGH, (int*)(dp + K.res + K.r.assigned),
                     (int*)(dp + K.res + K.r.nmatches), (const float*)(dp + U.u_ang), (const KeyPointRec*)(L->d_kps.p + (size_t)lf * cap), (const KeyPointRec*)(R->d_kps.p + (size_t)rf * cap),

@@ -127,7 +127,7 @@ struct orbx_extractor {
     // batched SearchLocalPoints (orbm_search_local_points_batch): one device block, one pinned result block, the size of the last enqueue
     orbx::DevBuf<uint8_t> d_lp, d_depth_in; orbx::HostBuf<uint8_t> h_lp_in, h_lp_out;
     size_t lp_pool = 0; int lp_B = 0, lp_M = 0, lp_first = 0; size_t lp_o_counter = 0, lp_o_view = 0; bool lp_pending = false, lp_want_view = false;
-    std::vector<int> lp_maps_M;                      // the pending batch's frames brought their own local maps: M_b per frame, mbTrackInView rows at their prefix sums (empty: one map, [B][lp_M])
+    std::vector<int> lp_maps_M;                      // the pending local-points batch: M_b per frame, mbTrackInView rows at their prefix sums (one set for every frame: all lp_M)
     bool lp_rig = false; size_t lp_o_view_r = 0;     // the pending batch is a rig batch (orbm_search_rig_batch_fetch; [B][2 cap] assignments, mbTrackInViewR)
     // the last orbm_stereo_fisheye with this handle on the left: the right handle, frames and extractions that d_l2r / d_r2l describe (fe_B == 0: none)
     const orbx_extractor* fe_R = nullptr; int fe_lf = 0, fe_rf = 0, fe_B = 0; uint64_t fe_gen_L = 0, fe_gen_R = 0;

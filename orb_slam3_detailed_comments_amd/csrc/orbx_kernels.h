@@ -145,54 +145,38 @@ __global__ void k_area_search(const AreaQuery* __restrict__ queries, const unsig
                               int* __restrict__ q_start, int* __restrict__ q_count, int2* __restrict__ entries);
 __global__ void k_frustum(FrustumParams F, int M, const float* __restrict__ pos, const float* __restrict__ normal, const float* __restrict__ min_dist,
                           const float* __restrict__ max_dist, const uint8_t* __restrict__ is_bad, uint8_t* __restrict__ in_view, float* __restrict__ track,
-                          int* __restrict__ scale_level, AreaQuery* __restrict__ queries, int* __restrict__ zero4, const FrustumParams* __restrict__ Fbatch);
-__global__ void k_frustum_maps(const FrustumParams* __restrict__ Fb, const FrameMapRec* __restrict__ maps, const uint8_t* __restrict__ is_bad, uint8_t* __restrict__ in_view,
-                               float* __restrict__ track, int* __restrict__ scale_level, AreaQuery* __restrict__ queries, int* __restrict__ zero4);
+                          int* __restrict__ scale_level, AreaQuery* __restrict__ queries, int* __restrict__ zero4);
+__global__ void k_frustum_batch(const FrustumParams* __restrict__ Fb, const FrameMapRec* __restrict__ maps, const uint8_t* __restrict__ is_bad, uint8_t* __restrict__ in_view,
+                                float* __restrict__ track, int* __restrict__ scale_level, AreaQuery* __restrict__ queries, int* __restrict__ zero4);
 __global__ void k_project_points(ProjectParams P, int M, const float* __restrict__ pos, const float* __restrict__ normal, const float* __restrict__ min_inv,
                                  const float* __restrict__ max_inv, const uint8_t* __restrict__ skip, uint8_t* __restrict__ valid, float* __restrict__ out, int debug_flags);
-__global__ void k_area_search_threads(const AreaQuery* __restrict__ queries, const unsigned long long* __restrict__ qdesc, int Q,
-                                      const KeyPointRec* __restrict__ kps, const float* __restrict__ u_right,
-                                      const unsigned long long* __restrict__ fdesc, GridParams g, const int* __restrict__ cell_start,
-                                      const int* __restrict__ cell_items, int gate_right, int* __restrict__ pool_counter, int pool_cap,
-                                      int* __restrict__ q_start, int* __restrict__ q_count, int2* __restrict__ entries, int frame_stride, int qdesc_per_frame);
-__global__ void k_area_search_threads_maps(const AreaQuery* __restrict__ queries, const FrameMapRec* __restrict__ maps, const KeyPointRec* __restrict__ kps,
-                                           const float* __restrict__ u_right, const unsigned long long* __restrict__ fdesc, GridParams g,
-                                           const int* __restrict__ cell_start, const int* __restrict__ cell_items, int gate_right, int* __restrict__ pool_counter,
-                                           int pool_cap, int* __restrict__ q_start, int* __restrict__ q_count, int2* __restrict__ entries, int frame_stride);
+__global__ void k_area_search_threads(const AreaQuery* __restrict__ queries, const FrameMapRec* __restrict__ maps, const KeyPointRec* __restrict__ kps,
+                                      const float* __restrict__ u_right, const unsigned long long* __restrict__ fdesc, GridParams g,
+                                      const int* __restrict__ cell_start, const int* __restrict__ cell_items, int gate_right, int* __restrict__ pool_counter,
+                                      int pool_cap, int* __restrict__ q_start, int* __restrict__ q_count, int2* __restrict__ entries, int frame_stride);
 __global__ void k_lastframe_queries(const FrustumParams* __restrict__ Fb, int capL, const int* __restrict__ n_last, const float* __restrict__ pos,
                                     const uint8_t* __restrict__ valid, const int* __restrict__ octave, AreaQuery* __restrict__ queries, int* __restrict__ zero4);
 __global__ void k_keyframe_queries(const FrustumParams* __restrict__ Fb, int capL, const int* __restrict__ n_kf, const float* __restrict__ pos,
                                    const uint8_t* __restrict__ valid, const float* __restrict__ min_dist, const float* __restrict__ max_dist,
                                    AreaQuery* __restrict__ queries, int* __restrict__ zero4);
-__global__ void k_lastframe_accept(int M, int cap, const int* __restrict__ n_per_frame, const int* __restrict__ q_start, const int* __restrict__ q_count,
-                                   const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0, const uint8_t* __restrict__ has_obs, int th_high,
-                                   int* __restrict__ assigned, int* __restrict__ nmatches, const float* __restrict__ last_angle,
-                                   const KeyPointRec* __restrict__ cur_kps, int check_ori);
-__global__ void k_local_accept(int M, int cap, const int* __restrict__ n_per_frame, const int* __restrict__ q_start, const int* __restrict__ q_count,
-                               const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0, const uint8_t* __restrict__ has_obs, float nnratio,
-                               int th_high, int* __restrict__ assigned, int* __restrict__ nmatches);
-__global__ void k_local_accept_maps(const FrameMapRec* __restrict__ maps, int cap, const int* __restrict__ n_per_frame, const int* __restrict__ q_start,
-                                    const int* __restrict__ q_count, const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0,
-                                    const uint8_t* __restrict__ has_obs, float nnratio, int th_high, int* __restrict__ assigned, int* __restrict__ nmatches);
-__global__ void k_frustum_rig_maps(const FrustumParams* __restrict__ Fb, const FrameMapRec* __restrict__ maps, const uint8_t* __restrict__ is_bad, uint8_t* in_view1,
-                                   uint8_t* in_view2, float* track1, float* track2, int* level1, int* level2, AreaQuery* __restrict__ q1, AreaQuery* __restrict__ q2,
-                                   int* __restrict__ zero4);
-__global__ void k_rig_local_accept_maps(const FrameMapRec* __restrict__ maps, int cap, const int* __restrict__ n1, const int* __restrict__ n2, const int* __restrict__ qs1,
-                                        const int* __restrict__ qc1, const int* __restrict__ qs2, const int* __restrict__ qc2, const int2* __restrict__ entries,
-                                        const uint8_t* __restrict__ occupied0, const uint8_t* __restrict__ has_obs, const int* __restrict__ l2r,
-                                        const int* __restrict__ r2l, float nnratio, int th_high, int* __restrict__ assigned, int* __restrict__ nmatches);
-__global__ void k_frustum_rig(const FrustumParams* __restrict__ Fb, int M, const float* __restrict__ pos, const float* __restrict__ normal,
-                              const float* __restrict__ min_dist, const float* __restrict__ max_dist, const uint8_t* __restrict__ is_bad,
-                              uint8_t* in_view1, uint8_t* in_view2, float* track1, float* track2, int* level1, int* level2,
-                              AreaQuery* __restrict__ q1, AreaQuery* __restrict__ q2, int* __restrict__ zero4);
+__global__ void k_lastframe_accept(const FrameMapRec* __restrict__ maps, int cap, const int* __restrict__ n_per_frame, const int* __restrict__ q_start,
+                                   const int* __restrict__ q_count, const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0,
+                                   const uint8_t* __restrict__ has_obs, int th_high, int* __restrict__ assigned, int* __restrict__ nmatches,
+                                   const float* __restrict__ last_angle, const KeyPointRec* __restrict__ cur_kps, int check_ori);
+__global__ void k_local_accept(const FrameMapRec* __restrict__ maps, int cap, const int* __restrict__ n_per_frame, const int* __restrict__ q_start,
+                               const int* __restrict__ q_count, const int2* __restrict__ entries, const uint8_t* __restrict__ occupied0,
+                               const uint8_t* __restrict__ has_obs, float nnratio, int th_high, int* __restrict__ assigned, int* __restrict__ nmatches);
+__global__ void k_frustum_rig(const FrustumParams* __restrict__ Fb, const FrameMapRec* __restrict__ maps, const uint8_t* __restrict__ is_bad, uint8_t* in_view1,
+                              uint8_t* in_view2, float* track1, float* track2, int* level1, int* level2, AreaQuery* __restrict__ q1, AreaQuery* __restrict__ q2,
+                              int* __restrict__ zero4);
 __global__ void k_lastframe_queries_rig(const FrustumParams* __restrict__ Fb, int capL, const int* __restrict__ n_last, const float* __restrict__ pos,
                                         const uint8_t* __restrict__ valid, const int* __restrict__ octave, RigRelPose trl, AreaQuery* q1,
                                         AreaQuery* __restrict__ q2, int* __restrict__ zero4);
-__global__ void k_rig_local_accept(int M, int cap, const int* __restrict__ n1, const int* __restrict__ n2, const int* __restrict__ qs1,
+__global__ void k_rig_local_accept(const FrameMapRec* __restrict__ maps, int cap, const int* __restrict__ n1, const int* __restrict__ n2, const int* __restrict__ qs1,
                                    const int* __restrict__ qc1, const int* __restrict__ qs2, const int* __restrict__ qc2, const int2* __restrict__ entries,
                                    const uint8_t* __restrict__ occupied0, const uint8_t* __restrict__ has_obs, const int* __restrict__ l2r,
                                    const int* __restrict__ r2l, float nnratio, int th_high, int* __restrict__ assigned, int* __restrict__ nmatches);
-__global__ void k_rig_lastframe_accept(int M, int cap, const int* __restrict__ n1, const int* __restrict__ n2, const int* __restrict__ qs1,
+__global__ void k_rig_lastframe_accept(const FrameMapRec* __restrict__ maps, int cap, const int* __restrict__ n1, const int* __restrict__ n2, const int* __restrict__ qs1,
                                        const int* __restrict__ qc1, const int* __restrict__ qs2, const int* __restrict__ qc2, const int2* __restrict__ entries,
                                        const uint8_t* __restrict__ occupied0, const uint8_t* __restrict__ has_obs, int th_high, int* __restrict__ assigned,
                                        int* __restrict__ nmatches, const float* __restrict__ last_angle, const KeyPointRec* __restrict__ kps1,

@@ -95,10 +95,13 @@ struct ProjectParams {
     int distance_test, angle_test;
     float bf;
 };
-// The local map of ONE frame of a batch whose frames bring their own maps (orbm_search_local_points_batch_maps / _rig_batch_maps): the arrays of the
-// resident set the frame names, its size, and where the frame's rows start in everything that is laid out by the prefix sums of M_b (call-time flags,
-// queries, track x 5, level, in_view, q_start / q_count)
-struct FrameMapRec { const float *pos, *normal, *min_d, *max_d; const unsigned long long* desc; int M, offset; };
+// The points ONE frame of a batched tracking search is matched against: the arrays of the resident set it names and its size, where the frame's rows
+// start in everything the batch lays out per point (`offset`: queries, track x 5, level, in_view, q_start / q_count) and where its rows start in the
+// uploaded call-time flags (`flags`: is_bad / has_obs).
+//   one set for every frame (orbm_search_local_points_batch / _rig_batch): the same set B times, offset = b * M, flags = 0 - the flags are uploaded once
+//   frames with their own maps (.._batch_maps): offset = flags = the prefix sum of M_b
+//   projection batches (LastFrame / KeyFrame): desc = the frame's uploaded descriptor rows, M = cap_last, offset = flags = b * cap_last (pos .. max_d unused)
+struct FrameMapRec { const float *pos, *normal, *min_d, *max_d; const unsigned long long* desc; int M, offset, flags; };
 // one record of k_grid_build_kfs: the grid of one device-resident key frame (orbm_keyframe) for one set of image bounds
 struct GridBuildRec { const KeyPointRec* kps; int* cell_of; int* cell_start; int* cell_items; int N; GridParams g; };
 // one target of orbm_fuse_candidates_batch (k_fuse_candidates): a resident key frame's arrays and the grid built for the target's bounds, the projection of

@@ -1,4 +1,4 @@
-"""Batched, device-resident Tracking::SearchLocalPoints (orbm_search_local_points_batch: k_grid_build / k_frustum / k_area_search over B frames,
+"""Batched, device-resident Tracking::SearchLocalPoints (orbm_search_local_points_batch: k_grid_build / k_frustum_batch / k_area_search_threads over B frames,
 k_local_accept = the sequential accept loop of ORBmatcher::SearchByProjection on the device) and Frame::ComputeStereoFromRGBD
 (orbm_stereo_from_depth), against the reference's own Frame.cc + ORBmatcher.cc run once per frame (oracle/_ref/libref_frame.so): stereo
 frames (uRight from the device stereo matcher) and RGB-D frames (uRight from the depth image), several poses, occupied keypoints, map points

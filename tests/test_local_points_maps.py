@@ -1,5 +1,5 @@
 """Batched Tracking::SearchLocalPoints for frames that each bring their OWN local map - independent streams side by side
-(orbm_search_local_points_batch_maps: k_frustum_maps / k_area_search_threads_maps / k_local_accept_maps read frame b's resident set through a
+(orbm_search_local_points_batch_maps: k_frustum_batch / k_area_search_threads / k_local_accept read frame b's resident set through a
 per-frame table; scratch and call-time flags are laid out by the prefix sums of M_b).
 
 Checker: the reference's own Frame.cc + ORBmatcher.cc, called once per frame with THAT frame's map (oracle/_ref/libref_frame.so); where the

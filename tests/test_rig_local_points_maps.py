@@ -1,5 +1,5 @@
 """Batched Tracking::SearchLocalPoints for two-camera (fisheye rig) frames that each bring their OWN local map
-(orbm_search_local_points_rig_batch_maps: k_frustum_rig_maps / k_area_search_threads_maps per camera / k_rig_local_accept_maps read frame b's
+(orbm_search_local_points_rig_batch_maps: k_frustum_rig / k_area_search_threads per camera / k_rig_local_accept read frame b's
 resident set through a per-frame table; scratch and call-time flags laid out by the prefix sums of M_b).
 
 Checker: the reference's own Frame.cc + ORBmatcher.cc (ReferenceRigFrame.search_local_points, oracle/_ref/libref_frame.so), called once per

@@ -1,7 +1,8 @@
 """The batched tracking searches for two-camera (fisheye rig, Frame::Nleft != -1) frames: orbm_search_local_points_rig_batch
 (Tracking::SearchLocalPoints) and orbm_search_by_projection_lastframe_rig_batch (SearchByProjection(CurrentFrame, LastFrame) with its
 camera-2 branch), read where extraction and orbm_stereo_fisheye left the frames, with the two-camera accept loop on the device
-(k_frustum_rig / k_lastframe_queries_rig, k_area_search_threads per camera, k_rig_local_accept / k_rig_lastframe_accept).
+(k_frustum_rig / k_lastframe_queries_rig, k_area_search_threads per camera, k_rig_local_accept / k_rig_lastframe_accept, all behind the per-frame
+table FrameMapRec: one resident set named B times, or the frames' uploaded last-frame rows).
 
 Bar, for every frame of a batch: assignments over both cameras, match counts, mbTrackInView / mbTrackInViewR identical to the reference's own
 Frame.cc + ORBmatcher.cc (oracle/_ref/libref_frame.so: ReferenceRigFrame; the oracle restatement of the LastFrame search) and to the
