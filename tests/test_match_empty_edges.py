@@ -13,6 +13,7 @@ import pytest
 import oracle_lib as ol
 from orb_slam3_detailed_comments_amd import ORBextractor, ComputeStereoMatches, synth
 from orb_slam3_detailed_comments_amd import matcher as M
+from resident_inject import knn2_expected as _knn2         # the numpy 2-NN, shared with tests/test_knn2_constructed.py
 
 W, H, NF = 376, 240, 500
 FX, B = 458.654, 0.110074
@@ -69,23 +70,6 @@ def test_stereo_right_image_without_keypoints_emulated(emu_lib):
 @pytest.mark.gpu
 def test_stereo_right_image_without_keypoints_gpu(hip_lib):
     _check_stereo(hip_lib)
-
-
-def _knn2(q, t):
-    """BFMatcher(NORM_HAMMING).knnMatch(k = 2) + the ratio test: neighbours by (distance, index), -1 where there is none"""
-    nq = len(q)
-    out = dict(idx0=np.full(nq, -1, np.int32), dist0=np.full(nq, -1, np.int32), idx1=np.full(nq, -1, np.int32), dist1=np.full(nq, -1, np.int32),
-               ratio_ok=np.zeros(nq, np.uint8))
-    if len(t) == 0:
-        return out
-    dist = np.unpackbits(q[:, None, :] ^ t[None, :, :], axis=2).sum(2).astype(np.int32)
-    order = np.argsort(dist, axis=1, kind="stable")
-    rows = np.arange(nq)
-    out["idx0"][:] = order[:, 0]; out["dist0"][:] = dist[rows, order[:, 0]]
-    if len(t) > 1:
-        out["idx1"][:] = order[:, 1]; out["dist1"][:] = dist[rows, order[:, 1]]
-        out["ratio_ok"][:] = out["dist0"].astype(np.float32).astype(np.float64) < out["dist1"].astype(np.float32).astype(np.float64) * 0.7
-    return out
 
 
 def _check_fisheye(lib):
