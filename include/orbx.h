@@ -430,6 +430,53 @@ int orbm_search_local_points_batch_maps(orbx_extractor* h, int first, int B, con
                                         float nnratio, int want_in_view);
 int orbm_points_count(const orbm_points* p);     /* M of a resident set (0 for NULL) */
 
+/* The map on the device.  A map point's fields change where LocalMapping / LoopClosing touch it, but the LIST a frame is matched against does
+ * not change slowly: Tracking::TrackLocalMap calls UpdateLocalMap() for every frame, and Tracking::UpdateLocalPoints (src/Tracking.cc:4088-4120)
+ * rebuilds mvpLocalMapPoints from scratch - the local key frames in reverse order, each one's GetMapPointMatches() in feature order, skipping
+ * nulls, points already stamped for this frame and bad points.  An orbm_map keeps the fields the searches read in a store addressed by SLOT (the
+ * caller's id of a MapPoint, 0 .. slots - 1), the map-point matches of key frames as rows of slots, and builds the list of B frames on the
+ * device into ordinary orbm_points sets, in the reference's order (the accept loops depend on it).  Every search that takes an orbm_points
+ * takes such a set unchanged.
+ *   Sets belong to the map: orbm_points_destroy does nothing to them.  Set b stays valid until the next orbm_map_local_points / orbm_map_select
+ * that writes set b, or orbm_map_destroy; a batch that was enqueued on a set and not fetched yet HAS TO BE FETCHED before that set is rebuilt
+ * (the set's memory is reused in place, or freed when it has to grow).  Buffers grow to the sizes seen and are reused: no allocation per build.
+ *   Every call takes a mutex inside the map and waits for its own work on the stream of the handle it was given, so one map may be updated
+ * through LocalMapping's handle and read through Tracking's; any handle of the map's device will do, a handle of another device is ORBX_E_ARG.
+ *   Refusals come before anything is enqueued and leave the map as it was: ORBX_E_ARG for null pointers, negative sizes, slots / rows / sets
+ * out of range and duplicate slots (the message names the frame, row or entry), ORBX_E_CAPACITY for n > kf_row_cap, B > max_sets and the
+ * limits of orbm_map_create (at most 2^28 slots, 65 535 sets, rows of 2^22 features).  Nothing is ever truncated.
+ *   Device memory: 65 * slots (store) + 4 * kf_rows * kf_row_cap (rows) + 8 * max_sets * slots (first-occurrence and seen stamps) bytes at
+ * creation; each set that has been built holds 69 bytes per point of the largest list it has held; one staging block of about
+ * 20 * (rows visited) + 8 * (positions visited) / 256 + 4 * (seen slots) bytes of the largest call.  orbx_debug_live_resources counts all of it. */
+typedef struct orbm_map orbm_map;
+int orbm_map_create(orbx_extractor* h, int slots, int kf_rows, int kf_row_cap, int max_sets, orbm_map** out);
+int orbm_map_destroy(orbx_extractor* h, orbm_map* m);
+/* n distinct slots get the fields the searches read (pos, normal, mfMinDistance, mfMaxDistance, descriptor; view->M == n).
+ * view->is_bad (NULL = 0) is stored; view->has_obs is ignored.  A slot that was never updated is absent: it behaves as bad and is never emitted. */
+int orbm_map_update(orbx_extractor* h, orbm_map* m, int n, const int* slots, const OrbmWorldPointView* view);
+/* MapPoint::SetBadFlag (or its reverse) for n distinct slots; an absent slot stays absent */
+int orbm_map_set_bad(orbx_extractor* h, orbm_map* m, int n, const int* slots, const uint8_t* bad);
+/* GetMapPointMatches() of one key frame: slot of feature i, or -1 */
+int orbm_map_set_keyframe(orbx_extractor* h, orbm_map* m, int row, int n, const int* slots);
+/* Tracking::UpdateLocalPoints for B frames: frame b visits rows kf_rows[kf_start[b] .. kf_start[b+1]) in THAT order (the caller lists
+ * mvpLocalKeyFrames reversed, as the reference walks them).  Position p of the walk keeps its point iff the slot is >= 0, present and not bad
+ * and no earlier position of this frame holds the same slot.  seen_* (may be NULL): the slots frame b already holds (SearchLocalPoints'
+ * first loop, src/Tracking.cc:3983-4003), seen_slots[seen_start[b] .. seen_start[b+1]); duplicates and slots outside the local map are fine.
+ * Result: set b (orbm_map_set), M_out[b] points; orbm_map_set_fetch gives slots[j] = the slot of local point j (the way back from `assigned` to
+ * the MapPoint) and seen[j] = 1 iff that slot is in the frame's seen list - hand it to the searches as is_bad (mnLastFrameSeen ==
+ * mCurrentFrame.mnId, src/Tracking.cc:4015) and leave has_obs NULL (a good point in a key frame's matches has observations).  Blocking. */
+int orbm_map_local_points(orbx_extractor* h, orbm_map* m, int B, const int* kf_start, const int* kf_rows,
+                          const int* seen_start, const int* seen_slots, int* M_out);
+/* an explicit list (the point set of a Fuse: one key frame's good map points) into set b; slots valid and present, duplicates allowed */
+int orbm_map_select(orbx_extractor* h, orbm_map* m, int b, int n, const int* slots);
+const orbm_points* orbm_map_set(orbx_extractor* h, const orbm_map* m, int b);      /* owned by the map; NULL for a set that was never built */
+int orbm_map_set_fetch(orbx_extractor* h, const orbm_map* m, int b, int* slots /*[M_b]*/, uint8_t* seen /*[M_b]*/);
+int orbm_points_fetch(orbx_extractor* h, const orbm_points* p, float* pos, float* normal, float* min_distance, float* max_distance,
+                      uint8_t* desc);   /* any may be NULL; works for every orbm_points */
+/* tests: the stamp value at which the map's epoch of first-occurrence stamps is used up and the stamps are cleared (0 = the default, 2^32 - 1);
+ * a frame that visits more positions than that is ORBX_E_CAPACITY */
+int orbm_map_debug_epoch(orbx_extractor* h, orbm_map* m, int limit);
+
 /* ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (src/ORBmatcher.cc:1950-2184, one camera) - the search of
  * Tracking::TrackWithMotionModel - for a BATCH of frames on the device: current frames = images [first, first + B) of the handle's last
  * extraction (mvKeysUn, mDescriptors, mvuRight as in orbm_search_local_points_batch); cur[b] = pose, camera, bounds, mbf and scale factors of

@@ -13,6 +13,8 @@
 //                  frames: one thread per (point, key frame), geometry, PredictScale, window walk, gates, Hamming distance and the minimum in one pass
 //   k_bow_search   inner loops of ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:1045-1323): one wave per
 //                  unmatched feature of KF1 against the features of KF2 in the same vocabulary node.
+//   k_map_*        the device-resident map (orbm_map): scatter of updated map points into the store, and Tracking::UpdateLocalPoints
+//                  (src/Tracking.cc:4088-4120) for a batch of frames: first occurrence by atomic max, ordered compaction by chunk ballots, field gather
 #include "orbx_types.h"
 #include "orbx_block.h"
 #include "orbx_kernels.h"
@@ -1370,6 +1372,115 @@ __global__ void __launch_bounds__(256) k_bow_dists(const BowItem* __restrict__ i
         }
         out[I.out_off + j] = d;
     }
+}
+
+// ---- the resident map (orbm_map): the store of map-point fields by slot, and Tracking::UpdateLocalPoints (src/Tracking.cc:4088-4120) built from it ----
+// A map point is 64 bytes: the descriptor (4 words of 8 bytes) and 8 floats (position 3 | normal 3 | mfMinDistance | mfMaxDistance).  Scatter and gather
+// give a point to 4 neighbouring threads: thread q moves descriptor word q and floats 2 q, 2 q + 1, so a wave writes 16 whole descriptors side by side.
+__device__ __forceinline__ float map_float_load(const float* pos, const float* normal, const float* min_d, const float* max_d, size_t i, int e) {
+    return e < 3 ? pos[3 * i + e] : e < 6 ? normal[3 * i + (e - 3)] : e == 6 ? min_d[i] : max_d[i];
+}
+__device__ __forceinline__ void map_float_store(float* pos, float* normal, float* min_d, float* max_d, size_t i, int e, float v) {
+    if (e < 3) pos[3 * i + e] = v; else if (e < 6) normal[3 * i + (e - 3)] = v; else if (e == 6) min_d[i] = v; else max_d[i] = v;
+}
+
+// orbm_map_update / orbm_map_set_bad: record r of the staged block goes to slot slots[r] (distinct: the host refuses duplicates, so no two records meet).
+// desc == nullptr: the flag alone, and only where the slot holds a point.  grid (ceil(4 n / 256)), 256 threads
+__global__ void __launch_bounds__(256) k_map_scatter(int n, const int* __restrict__ slots, const unsigned long long* __restrict__ desc, const float* __restrict__ pos,
+                                                     const float* __restrict__ normal, const float* __restrict__ min_d, const float* __restrict__ max_d,
+                                                     const uint8_t* __restrict__ bad, MapStore S) {
+    const int t = (int)(blockIdx.x * 256u + threadIdx.x), r = t >> 2, q = t & 3;
+    if (r >= n) return;
+    const size_t slot = (size_t)slots[r];
+    const uint8_t st = (uint8_t)(kMapPresent | (bad[r] ? kMapBad : 0));
+    if (!desc) {
+        if (q == 0 && (S.state[slot] & kMapPresent)) S.state[slot] = st;
+        return;
+    }
+    S.desc[4 * slot + q] = desc[4 * (size_t)r + q];
+    for (int e = 2 * q; e < 2 * q + 2; e++) map_float_store(S.pos, S.normal, S.min_d, S.max_d, slot, e, map_float_load(pos, normal, min_d, max_d, (size_t)r, e));
+    if (q == 0) S.state[slot] = st;
+}
+
+// The slots frame b already holds (SearchLocalPoints' first loop, src/Tracking.cc:3983-4003) are marked with this call's epoch: every writer of a word
+// stores the same value, so duplicates need no atomic.  grid (ceil(longest list / 256), B), 256 threads
+__global__ void __launch_bounds__(256) k_map_seen(const int* __restrict__ seen_start, const int* __restrict__ seen_slots, unsigned* __restrict__ seen_stamp, int nslots,
+                                                  unsigned mark) {
+    const int b = (int)blockIdx.y, i = seen_start[b] + (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i < seen_start[b + 1]) seen_stamp[(size_t)b * nslots + seen_slots[i]] = mark;
+}
+
+// the slot at entry i of a visited row, or -1 where UpdateLocalPoints passes on (:4101-4105: no map point, or a bad one; a slot never updated counts as bad)
+__device__ __forceinline__ int map_visit(const MapSeg& G, int i, const int* __restrict__ kf_slots, int row_cap, const uint8_t* __restrict__ state) {
+    const int slot = kf_slots[(size_t)G.row * row_cap + i];
+    return slot >= 0 && state[slot] == kMapPresent ? slot : -1;
+}
+
+// First occurrence (mnTrackReferenceForFrame, :4103-4109): position p of a frame's walk offers top - p to the stamp of (frame, slot); the largest offer is
+// the earliest position, whatever order the atomics arrive in.  top = base + (largest position count of the call): this call's offers lie in (base, top],
+// everything an earlier call left is <= base, and the next call starts at base = top - nothing is cleared between calls.
+// grid (visited rows, ceil(longest row / kMapChunk)), kMapChunk threads
+__global__ void __launch_bounds__(kMapChunk) k_map_stamp(const MapSeg* __restrict__ segs, const int* __restrict__ kf_slots, int row_cap, const uint8_t* __restrict__ state,
+                                                         unsigned* __restrict__ stamp, int nslots, unsigned top) {
+    const MapSeg G = segs[blockIdx.x];
+    const int i = (int)(blockIdx.y * (unsigned)kMapChunk + threadIdx.x);
+    if (i >= G.n) return;
+    const int slot = map_visit(G, i, kf_slots, row_cap, state);
+    if (slot >= 0) atomicMax(&stamp[(size_t)G.set * nslots + slot], top - (unsigned)(G.pos0 + i));
+}
+
+// The positions that keep their point, in visiting order: a chunk's survivors are counted with wave ballots (chunk_off == nullptr: chunk_cnt[chunk] is all
+// this pass writes); once k_map_scan has turned the counts into offsets, the same ballots rank each survivor inside its chunk and its slot goes to
+// sets[frame].slots[offset + rank].  No counter is shared between chunks, so the order is the walk's.  Same grid as k_map_stamp
+__global__ void __launch_bounds__(kMapChunk) k_map_compact(const MapSeg* __restrict__ segs, const int* __restrict__ kf_slots, int row_cap, const uint8_t* __restrict__ state,
+                                                           const unsigned* __restrict__ stamp, int nslots, unsigned top, int* __restrict__ chunk_cnt,
+                                                           const int* __restrict__ chunk_off, const MapSetRec* __restrict__ sets) {
+    __shared__ int wave_cnt[kMapChunk / 64];
+    const MapSeg G = segs[blockIdx.x];
+    const int i = (int)(blockIdx.y * (unsigned)kMapChunk + threadIdx.x);
+    if ((int)(blockIdx.y * (unsigned)kMapChunk) >= G.n) return;            // (the whole workgroup: the row is shorter than the longest one)
+    const int slot = i < G.n ? map_visit(G, i, kf_slots, row_cap, state) : -1;
+    const bool keep = slot >= 0 && stamp[(size_t)G.set * nslots + slot] == top - (unsigned)(G.pos0 + i);
+    const unsigned long long bal = __ballot(keep);
+    const int lane = lane_id(), wave = wave_id();
+    if (lane == 0) wave_cnt[wave] = __popcll(bal);
+    __syncthreads();
+    const int chunk = G.chunk0 + (int)blockIdx.y;
+    if (!chunk_off) {
+        if (threadIdx.x == 0) { int c = 0; for (int w = 0; w < kMapChunk / 64; w++) c += wave_cnt[w]; chunk_cnt[chunk] = c; }
+        return;
+    }
+    if (!keep) return;
+    int at = chunk_off[chunk] + __popcll(bal & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; w++) at += wave_cnt[w];
+    sets[G.set].slots[at] = slot;
+}
+
+// exclusive scan of a frame's chunk counts (its chunks are frame_chunk0[b] .. frame_chunk0[b + 1] - 1) and their sum, the size of its local map.
+// grid (B), one wave: a frame has a few hundred chunks
+__global__ void __launch_bounds__(64) k_map_scan(const int* __restrict__ frame_chunk0, const int* __restrict__ chunk_cnt, int* __restrict__ chunk_off, int* __restrict__ M_out) {
+    const int b = (int)blockIdx.x, lane = lane_id(), c1 = frame_chunk0[b + 1];
+    int run = 0;
+    for (int c = frame_chunk0[b]; c < c1; c += 64) {
+        const int i = c + lane, v = i < c1 ? chunk_cnt[i] : 0;
+        int incl = v;
+        for (int d = 1; d < 64; d <<= 1) { const int up = __shfl_up(incl, d); if (lane >= d) incl += up; }
+        if (i < c1) chunk_off[i] = run + incl - v;
+        run += __shfl(incl, 63);
+    }
+    if (lane == 0) M_out[b] = run;
+}
+
+// the fields of every point of the built sets, by slot, and its seen flag (seen_stamp == nullptr: an explicit list, nothing seen).
+// grid (ceil(4 x largest set / 256), sets), 256 threads
+__global__ void __launch_bounds__(256) k_map_gather(const MapSetRec* __restrict__ sets, MapStore S, const unsigned* __restrict__ seen_stamp, int nslots, unsigned base) {
+    const MapSetRec R = sets[blockIdx.y];
+    const int t = (int)(blockIdx.x * 256u + threadIdx.x), j = t >> 2, q = t & 3;
+    if (j >= R.M) return;
+    const size_t slot = (size_t)R.slots[j];
+    R.desc[4 * (size_t)j + q] = S.desc[4 * slot + q];
+    for (int e = 2 * q; e < 2 * q + 2; e++) map_float_store(R.pos, R.normal, R.min_d, R.max_d, (size_t)j, e, map_float_load(S.pos, S.normal, S.min_d, S.max_d, slot, e));
+    if (q == 0) R.seen[j] = seen_stamp ? (uint8_t)(seen_stamp[(size_t)R.set * nslots + slot] > base) : (uint8_t)0;
 }
 
 }  // namespace orbx

@@ -11,6 +11,8 @@
 //                           orbm_fuse_candidates_batch (one point set against many key frames) stands with the single Fuse search
 //   batched routes          frames of the last extraction: SearchLocalPoints, SearchByProjection(last frame / key frame), SearchByBoW; one fetch
 //   rig routes              the same for two-camera frames (two handles), fetched through the same core
+//   resident map            orbm_map: the map-point store by slot, key-frame rows of slots, Tracking::UpdateLocalPoints for a batch of frames built on the
+//                           device into orbm_points sets that every search above takes
 // The line numbers in the comments point into the reference's src/ORBmatcher.cc unless another file is named.
 #include <mutex>
 #include "orbx_internal.h"
@@ -474,6 +476,7 @@ struct orbm_points {
     int device = 0, M = 0;
     uint8_t* dmem = nullptr;
     const unsigned long long* desc = nullptr; const float *pos = nullptr, *normal = nullptr, *min_d = nullptr, *max_d = nullptr;
+    bool map_owned = false;      // a set an orbm_map built: its memory is the map's
 };
 
 int orbm_points_create(orbx_extractor* h, const OrbmWorldPointView* P, orbm_points** out) {
@@ -496,7 +499,7 @@ int orbm_points_create(orbx_extractor* h, const OrbmWorldPointView* P, orbm_poin
 }
 
 void orbm_points_destroy(orbm_points* p) {
-    if (!p) return;
+    if (!p || p->map_owned) return;
     rt::set_device(p->device);
     rt::dfree(p->dmem);
     delete p;
@@ -2263,6 +2266,342 @@ int orbm_search_rig_batch_fetch(orbx_extractor* L, int* assigned, int cap, int* 
     if ((in_view || in_view_r) && !L->lp_want_view) return fail(ORBX_E_ARG, "in_view was not requested at enqueue time");
     uint8_t* const views[2] = {in_view, in_view_r};
     return batch_fetch(L, 2 * (size_t)L->kp_total_cap, "batched rig search", assigned, cap, nmatches, 2, L->lp_want_view && L->lp_M > 0, views);
+}
+
+}  // extern "C"
+
+// ---- the resident map: map points by slot, key-frame rows of slots, Tracking::UpdateLocalPoints on the device -----------------------------------
+// What the searches read of a map point changes where LocalMapping / LoopClosing touch it; WHICH points a frame's local map lists, and in what order,
+// changes every frame (Tracking::UpdateLocalPoints rebuilds mvpLocalMapPoints from scratch, src/Tracking.cc:4088-4120).  So the fields live in a store
+// addressed by slot, GetMapPointMatches() of every key frame is a row of slots, and the list of a frame - rows walked in the caller's order, the first
+// occurrence of every good point kept - is built by the kernels k_map_* into an orbm_points set the map owns.  Every call takes the map's mutex and
+// waits for its own work, so handles of different threads (LocalMapping's, Tracking's) may share a map.
+struct orbm_map {
+    int device = 0, slots = 0, kf_rows = 0, kf_row_cap = 0, max_sets = 0;
+    mutable std::mutex mu;
+    DevBuf<uint8_t> d_store; MapStore S = {};      // [descriptors 32 | pos 12 | normal 12 | min 4 | max 4 | state 1] x slots
+    DevBuf<int> d_kf;                              // [kf_rows][kf_row_cap] slots; the rows' lengths stay on the host
+    DevBuf<unsigned> d_stamp;                      // [max_sets][slots] first-occurrence stamps, then [max_sets][slots] seen stamps
+    std::vector<int> kf_n;
+    std::vector<uint8_t> state, mark;              // host mirror of S.state (what orbm_map_select checks); scratch of the duplicate check
+    // stamps of one build lie in (base, base + its largest position count]; base then moves up, and everything older reads as stale.  At epoch_limit
+    // (orbm_map_debug_epoch: tests lower it) the stamps are cleared and base starts over
+    unsigned base = 0, epoch_limit = 0xFFFFFFFFu;
+    std::vector<orbm_points> sets; std::vector<DevBuf<uint8_t>> set_mem; std::vector<MapSetRec> set_rec; std::vector<uint8_t> built;
+    HostBuf<uint8_t> h_stage; DevBuf<uint8_t> d_stage;      // one call's upload, counts and set table (the mutex makes them the call's own)
+};
+
+namespace {
+int map_call_check(const orbx_extractor* h, const orbm_map* m) {
+    if (!h || !m) return fail(ORBX_E_ARG, "null handle or map");
+    if (h->device != m->device) return fail(ORBX_E_ARG, "the map lives on device %d, the handle on device %d", m->device, h->device);
+    return ORBX_OK;
+}
+int map_stage(orbm_map* m, size_t host_bytes, size_t dev_bytes) {
+    if (m->h_stage.ensure(host_bytes + 16) || m->d_stage.ensure(dev_bytes + 16)) return fail(ORBX_E_DEVICE, "staging allocation failed");
+    return ORBX_OK;
+}
+// set b laid out for M points in memory that only grows: [descriptors | pos | normal | min | max | slots | seen]; the set reads as empty until its build has ended
+int map_lay_set(orbm_map* m, int b, int M) {
+    const size_t M1 = M > 0 ? M : 1;
+    Bump L;
+    const size_t od = L.take(32 * M1), op = L.take(12 * M1), on = L.take(12 * M1), omn = L.take(4 * M1), omx = L.take(4 * M1), osl = L.take(4 * M1), ose = L.take(M1);
+    orbm_points& P = m->sets[b];
+    P.M = 0;
+    if (m->set_mem[b].ensure(L.o)) return fail(ORBX_E_DEVICE, "set %d: allocation for %d points failed", b, M);
+    uint8_t* p = m->set_mem[b].p;
+    MapSetRec& R = m->set_rec[b];
+    R.desc = (unsigned long long*)(p + od); R.pos = (float*)(p + op); R.normal = (float*)(p + on); R.min_d = (float*)(p + omn); R.max_d = (float*)(p + omx);
+    R.slots = (int*)(p + osl); R.seen = p + ose; R.M = M; R.set = b;
+    P.device = m->device; P.dmem = p; P.desc = R.desc; P.pos = R.pos; P.normal = R.normal; P.min_d = R.min_d; P.max_d = R.max_d; P.map_owned = true;
+    m->built[b] = 1;
+    return ORBX_OK;
+}
+// n slots of the map, each once (a parallel scatter must not meet itself)
+int map_distinct_slots(orbm_map* m, int n, const int* slots) {
+    int rc = ORBX_OK, i = 0;
+    for (; i < n; i++) {
+        const int s = slots[i];
+        if (s < 0 || s >= m->slots) { rc = fail(ORBX_E_ARG, "entry %d: slot %d is outside the map's %d slots", i, s, m->slots); break; }
+        if (m->mark[s]) { rc = fail(ORBX_E_ARG, "entry %d: slot %d is listed twice", i, s); break; }
+        m->mark[s] = 1;
+    }
+    for (int k = 0; k < i; k++) m->mark[slots[k]] = 0;
+    return rc;
+}
+// orbm_map_update (P != nullptr) and orbm_map_set_bad: one staged block up, one launch
+int map_scatter(orbx_extractor* h, orbm_map* m, int n, const int* slots, const OrbmWorldPointView* P, const uint8_t* bad) {
+    const size_t N = n;
+    Bump L;
+    const size_t os = L.take(4 * N), ob = L.take(N), od = L.take(P ? 32 * N : 0), op = L.take(P ? 12 * N : 0), on = L.take(P ? 12 * N : 0), omn = L.take(P ? 4 * N : 0),
+                 omx = L.take(P ? 4 * N : 0);
+    if (int rc = map_stage(m, L.o, L.o)) return rc;
+    uint8_t* hp = m->h_stage.p; uint8_t* dp = m->d_stage.p;
+    memcpy(hp + os, slots, 4 * N);
+    if (bad) memcpy(hp + ob, bad, N); else memset(hp + ob, 0, N);
+    if (P) { memcpy(hp + od, P->desc, 32 * N); memcpy(hp + op, P->pos, 12 * N); memcpy(hp + on, P->normal, 12 * N); memcpy(hp + omn, P->min_distance, 4 * N); memcpy(hp + omx, P->max_distance, 4 * N); }
+    if (rt::copy_h2d(dp, hp, L.o, h->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
+    const dim3 grid((unsigned)((4 * N + 255) / 256), 1, 1), blk(256, 1, 1);
+    ORBX_LAUNCH(k_map_scatter, grid, blk, 0, h->s0, n, (const int*)(dp + os), P ? (const unsigned long long*)(dp + od) : (const unsigned long long*)nullptr, (const float*)(dp + op),
+                (const float*)(dp + on), (const float*)(dp + omn), (const float*)(dp + omx), (const uint8_t*)(dp + ob), m->S);
+    if (rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "map update failed: %s", rt::last_error());
+    for (int i = 0; i < n; i++) {
+        const uint8_t st = (uint8_t)(kMapPresent | (bad && bad[i] ? kMapBad : 0));
+        if (P || (m->state[slots[i]] & kMapPresent)) m->state[slots[i]] = st;
+    }
+    return ORBX_OK;
+}
+void map_release(orbm_map* m) {
+    m->d_store.release(); m->d_kf.release(); m->d_stamp.release(); m->h_stage.release(); m->d_stage.release();
+    for (auto& x : m->set_mem) x.release();
+}
+}  // namespace
+
+extern "C" {
+
+int orbm_map_create(orbx_extractor* h, int slots, int kf_rows, int kf_row_cap, int max_sets, orbm_map** out) {
+    if (!h || !out) return fail(ORBX_E_ARG, "null");
+    if (slots < 1 || kf_rows < 0 || kf_row_cap < 0 || max_sets < 1) return fail(ORBX_E_ARG, "a map needs slots >= 1, kf_rows >= 0, kf_row_cap >= 0, max_sets >= 1");
+    if (slots > (1 << 28) || max_sets > 65535 || kf_row_cap > (1 << 22) || (long long)kf_rows * kf_row_cap > (1ll << 30) || (long long)max_sets * slots > (1ll << 31))
+        return fail(ORBX_E_CAPACITY, "at most 2^28 slots, 65535 sets, rows of 2^22, 2^30 row entries and 2^31 (set, slot) pairs");
+    rt::set_device(h->device);
+    orbm_map* m = new orbm_map();
+    m->device = h->device; m->slots = slots; m->kf_rows = kf_rows; m->kf_row_cap = kf_row_cap; m->max_sets = max_sets;
+    const size_t S1 = slots, pairs = (size_t)max_sets * S1;
+    Bump L;
+    const size_t od = L.take(32 * S1), op = L.take(12 * S1), on = L.take(12 * S1), omn = L.take(4 * S1), omx = L.take(4 * S1), ost = L.take(S1);
+    if (m->d_store.ensure(L.o) || m->d_kf.ensure((size_t)kf_rows * kf_row_cap + 1) || m->d_stamp.ensure(2 * pairs) ||
+        rt::memset_async(m->d_store.p, 0, L.o, h->s0) || rt::memset_async(m->d_stamp.p, 0, 2 * pairs * sizeof(unsigned), h->s0) || rt::stream_sync(h->s0)) {
+        map_release(m); delete m;
+        return fail(ORBX_E_DEVICE, "allocation of a map of %d slots, %d x %d row entries and %d sets failed", slots, kf_rows, kf_row_cap, max_sets);
+    }
+    uint8_t* p = m->d_store.p;
+    m->S.desc = (unsigned long long*)(p + od); m->S.pos = (float*)(p + op); m->S.normal = (float*)(p + on); m->S.min_d = (float*)(p + omn); m->S.max_d = (float*)(p + omx);
+    m->S.state = p + ost;
+    m->kf_n.assign(kf_rows, 0); m->state.assign(S1, 0); m->mark.assign(S1, 0);
+    m->sets.resize(max_sets); m->set_mem.resize(max_sets); m->set_rec.resize(max_sets); m->built.assign(max_sets, 0);
+    *out = m;
+    return ORBX_OK;
+}
+
+int orbm_map_destroy(orbx_extractor* /*h*/, orbm_map* m) {
+    if (!m) return ORBX_OK;
+    rt::set_device(m->device);
+    map_release(m);
+    delete m;
+    return ORBX_OK;
+}
+
+int orbm_map_debug_epoch(orbx_extractor* h, orbm_map* m, int limit) {
+    if (int rc = map_call_check(h, m)) return rc;
+    std::lock_guard<std::mutex> lk(m->mu);
+    rt::set_device(h->device);
+    if (rt::memset_async(m->d_stamp.p, 0, 2 * (size_t)m->max_sets * m->slots * sizeof(unsigned), h->s0) || rt::stream_sync(h->s0)) return fail(ORBX_E_DEVICE, "clearing the stamps failed");
+    m->base = 0; m->epoch_limit = limit > 0 ? (unsigned)limit : 0xFFFFFFFFu;
+    return ORBX_OK;
+}
+
+int orbm_map_update(orbx_extractor* h, orbm_map* m, int n, const int* slots, const OrbmWorldPointView* P) {
+    if (int rc = map_call_check(h, m)) return rc;
+    if (n < 0) return fail(ORBX_E_ARG, "negative number of points");
+    if (n == 0) return ORBX_OK;
+    if (!slots || !P || P->M != n || !P->pos || !P->normal || !P->min_distance || !P->max_distance || !P->desc) return fail(ORBX_E_ARG, "bad map point view (M has to be n, every field present)");
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (int rc = map_distinct_slots(m, n, slots)) return rc;
+    rt::set_device(h->device);
+    return map_scatter(h, m, n, slots, P, P->is_bad);
+}
+
+int orbm_map_set_bad(orbx_extractor* h, orbm_map* m, int n, const int* slots, const uint8_t* bad) {
+    if (int rc = map_call_check(h, m)) return rc;
+    if (n < 0) return fail(ORBX_E_ARG, "negative number of points");
+    if (n == 0) return ORBX_OK;
+    if (!slots || !bad) return fail(ORBX_E_ARG, "null");
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (int rc = map_distinct_slots(m, n, slots)) return rc;
+    rt::set_device(h->device);
+    return map_scatter(h, m, n, slots, nullptr, bad);
+}
+
+int orbm_map_set_keyframe(orbx_extractor* h, orbm_map* m, int row, int n, const int* slots) {
+    if (int rc = map_call_check(h, m)) return rc;
+    if (row < 0 || row >= m->kf_rows) return fail(ORBX_E_ARG, "row %d is outside the map's %d key-frame rows", row, m->kf_rows);
+    if (n < 0 || (n > 0 && !slots)) return fail(ORBX_E_ARG, "row %d: null / negative number of features", row);
+    if (n > m->kf_row_cap) return fail(ORBX_E_CAPACITY, "row %d: %d features, the map's rows hold %d", row, n, m->kf_row_cap);
+    for (int i = 0; i < n; i++)
+        if (slots[i] < -1 || slots[i] >= m->slots) return fail(ORBX_E_ARG, "row %d: slot %d of feature %d is outside the map's %d slots", row, slots[i], i, m->slots);
+    std::lock_guard<std::mutex> lk(m->mu);
+    rt::set_device(h->device);
+    if (n > 0) {
+        if (int rc = map_stage(m, 4 * (size_t)n, 0)) return rc;
+        memcpy(m->h_stage.p, slots, 4 * (size_t)n);
+        if (rt::copy_h2d(m->d_kf.p + (size_t)row * m->kf_row_cap, m->h_stage.p, 4 * (size_t)n, h->s0) || rt::stream_sync(h->s0)) return fail(ORBX_E_DEVICE, "row %d: upload failed: %s", row, rt::last_error());
+    }
+    m->kf_n[row] = n;
+    return ORBX_OK;
+}
+
+int orbm_map_local_points(orbx_extractor* h, orbm_map* m, int B, const int* kf_start, const int* kf_rows, const int* seen_start, const int* seen_slots, int* M_out) {
+    if (int rc = map_call_check(h, m)) return rc;
+    if (B < 0) return fail(ORBX_E_ARG, "negative number of frames");
+    if (B == 0) return ORBX_OK;
+    if (!kf_start || !M_out) return fail(ORBX_E_ARG, "null");
+    if (B > m->max_sets) return fail(ORBX_E_CAPACITY, "%d frames, the map has %d sets", B, m->max_sets);
+    std::lock_guard<std::mutex> lk(m->mu);
+    // the walk of every frame as segments (one per visited row) and chunks of kMapChunk positions; everything is checked before anything is enqueued
+    const long long max_positions = std::min<long long>(0x7fffffff, m->epoch_limit);
+    std::vector<MapSeg> segs; std::vector<int> fc0(B + 1); std::vector<long long> P(B);
+    long long nchunks = 0, L = 0; int max_n = 0;
+    if (kf_start[0] < 0) return fail(ORBX_E_ARG, "frame 0: negative kf_start");
+    for (int b = 0; b < B; b++) {
+        if (kf_start[b + 1] < kf_start[b]) return fail(ORBX_E_ARG, "frame %d: kf_start decreases", b);
+        if (kf_start[b + 1] > kf_start[b] && !kf_rows) return fail(ORBX_E_ARG, "frame %d: null row list", b);
+        fc0[b] = (int)nchunks;
+        long long p = 0;
+        for (int k = kf_start[b]; k < kf_start[b + 1]; k++) {
+            const int row = kf_rows[k];
+            if (row < 0 || row >= m->kf_rows) return fail(ORBX_E_ARG, "frame %d: row %d is outside the map's %d key-frame rows", b, row, m->kf_rows);
+            const int n = m->kf_n[row];
+            if (p + n > max_positions) return fail(ORBX_E_CAPACITY, "frame %d visits more than %lld positions", b, max_positions);
+            const MapSeg g = {b, row, n, (int)p, (int)nchunks};
+            segs.push_back(g);
+            p += n; nchunks += (n + kMapChunk - 1) / kMapChunk; max_n = std::max(max_n, n);
+            if (nchunks > (1ll << 30) || segs.size() > ((size_t)1 << 24)) return fail(ORBX_E_CAPACITY, "frame %d: more than 2^30 chunks or 2^24 visited rows in one call", b);
+        }
+        P[b] = p; L = std::max(L, p);
+    }
+    fc0[B] = (int)nchunks;
+    int seen_total = 0, max_seen = 0;
+    if (seen_start) {
+        if (seen_start[0] < 0) return fail(ORBX_E_ARG, "frame 0: negative seen_start");
+        for (int b = 0; b < B; b++) {
+            if (seen_start[b + 1] < seen_start[b]) return fail(ORBX_E_ARG, "frame %d: seen_start decreases", b);
+            if (seen_start[b + 1] > seen_start[b] && !seen_slots) return fail(ORBX_E_ARG, "frame %d: null seen list", b);
+            for (int k = seen_start[b]; k < seen_start[b + 1]; k++)
+                if (seen_slots[k] < 0 || seen_slots[k] >= m->slots) return fail(ORBX_E_ARG, "frame %d: seen slot %d is outside the map's %d slots", b, seen_slots[k], m->slots);
+            max_seen = std::max(max_seen, seen_start[b + 1] - seen_start[b]);
+        }
+        seen_total = seen_start[B];
+    }
+    rt::set_device(h->device);
+    for (int b = 0; b < B; b++) m->sets[b].M = 0;
+    if (L == 0) {                                                   // nothing is visited: every local map is empty
+        for (int b = 0; b < B; b++) { if (int rc = map_lay_set(m, b, 0)) return rc; M_out[b] = 0; }
+        return ORBX_OK;
+    }
+    const size_t nseg = segs.size(), B1 = B;
+    Bump U;
+    const size_t o_seg = U.take(sizeof(MapSeg) * nseg), o_fc0 = U.take(4 * (B1 + 1)), o_ss = U.take(4 * (B1 + 1)), o_sl = U.take(4 * (size_t)seen_total), up = U.o;
+    const size_t o_cnt = U.take(4 * (size_t)nchunks), o_off = U.take(4 * (size_t)nchunks), o_M = U.take(4 * B1), o_tab = U.take(sizeof(MapSetRec) * B1);
+    const size_t h_M = up, h_tab = up + al16(4 * B1);
+    if (int rc = map_stage(m, h_tab + sizeof(MapSetRec) * B1, U.o)) return rc;
+    uint8_t* hp = m->h_stage.p; uint8_t* dp = m->d_stage.p;
+    memcpy(hp + o_seg, segs.data(), sizeof(MapSeg) * nseg); memcpy(hp + o_fc0, fc0.data(), 4 * (B1 + 1));
+    if (max_seen > 0) { memcpy(hp + o_ss, seen_start, 4 * (B1 + 1)); memcpy(hp + o_sl, seen_slots, 4 * (size_t)seen_total); }
+    const size_t pairs = (size_t)m->max_sets * m->slots;
+    unsigned* stamp = m->d_stamp.p; unsigned* seen_stamp = stamp + pairs;
+    if ((long long)m->base + L > (long long)m->epoch_limit) {       // the epoch is used up: clear, start over
+        if (rt::memset_async(stamp, 0, 2 * pairs * sizeof(unsigned), h->s0)) return fail(ORBX_E_DEVICE, "clearing the stamps failed: %s", rt::last_error());
+        m->base = 0;
+    }
+    const unsigned base = m->base, top = base + (unsigned)L;
+    m->base = top;                                                  // (whatever happens from here on, the stamps this call leaves are stale for the next one)
+    if (rt::copy_h2d(dp, hp, up, h->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
+    const MapSeg* d_seg = (const MapSeg*)(dp + o_seg);
+    if (max_seen > 0) {
+        const dim3 grid((max_seen + 255) / 256, B, 1), blk(256, 1, 1);
+        ORBX_LAUNCH(k_map_seen, grid, blk, 0, h->s0, (const int*)(dp + o_ss), (const int*)(dp + o_sl), seen_stamp, m->slots, base + 1u);
+    }
+    const dim3 gridp((unsigned)nseg, (max_n + kMapChunk - 1) / kMapChunk, 1), blkp(kMapChunk, 1, 1), gridb(B, 1, 1), wave(64, 1, 1);
+    ORBX_LAUNCH(k_map_stamp, gridp, blkp, 0, h->s0, d_seg, (const int*)m->d_kf.p, m->kf_row_cap, (const uint8_t*)m->S.state, stamp, m->slots, top);
+    ORBX_LAUNCH(k_map_compact, gridp, blkp, 0, h->s0, d_seg, (const int*)m->d_kf.p, m->kf_row_cap, (const uint8_t*)m->S.state, (const unsigned*)stamp, m->slots, top,
+                (int*)(dp + o_cnt), (const int*)nullptr, (const MapSetRec*)nullptr);
+    ORBX_LAUNCH(k_map_scan, gridb, wave, 0, h->s0, (const int*)(dp + o_fc0), (const int*)(dp + o_cnt), (int*)(dp + o_off), (int*)(dp + o_M));
+    if (rt::copy_d2h(hp + h_M, dp + o_M, 4 * B1, h->s0) || rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "local map build failed: %s", rt::last_error());
+    // the sizes are known: lay the sets out, scatter the kept slots in visiting order, gather the fields
+    const int* Mb = (const int*)(hp + h_M);
+    int m_max = 0;
+    for (int b = 0; b < B; b++) {
+        if (Mb[b] < 0 || Mb[b] > P[b] || Mb[b] > m->slots) return fail(ORBX_E_INTERNAL, "frame %d: %d kept of %lld visited positions", b, Mb[b], P[b]);
+        if (int rc = map_lay_set(m, b, Mb[b])) return rc;
+        m_max = std::max(m_max, Mb[b]);
+    }
+    memcpy(hp + h_tab, m->set_rec.data(), sizeof(MapSetRec) * B1);
+    if (rt::copy_h2d(dp + o_tab, hp + h_tab, sizeof(MapSetRec) * B1, h->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
+    if (m_max > 0) {
+        const MapSetRec* d_tab = (const MapSetRec*)(dp + o_tab);
+        ORBX_LAUNCH(k_map_compact, gridp, blkp, 0, h->s0, d_seg, (const int*)m->d_kf.p, m->kf_row_cap, (const uint8_t*)m->S.state, (const unsigned*)stamp, m->slots, top,
+                    (int*)(dp + o_cnt), (const int*)(dp + o_off), d_tab);
+        const dim3 gridg((unsigned)((4 * (size_t)m_max + 255) / 256), B, 1), blkg(256, 1, 1);
+        ORBX_LAUNCH(k_map_gather, gridg, blkg, 0, h->s0, d_tab, m->S, (const unsigned*)seen_stamp, m->slots, base);
+    }
+    if (rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "local map build failed: %s", rt::last_error());
+    for (int b = 0; b < B; b++) { m->sets[b].M = Mb[b]; M_out[b] = Mb[b]; }
+    return ORBX_OK;
+}
+
+int orbm_map_select(orbx_extractor* h, orbm_map* m, int b, int n, const int* slots) {
+    if (int rc = map_call_check(h, m)) return rc;
+    if (b < 0 || b >= m->max_sets) return fail(ORBX_E_ARG, "set %d: the map has %d sets", b, m->max_sets);
+    if (n < 0 || (n > 0 && !slots)) return fail(ORBX_E_ARG, "set %d: null / negative number of points", b);
+    if (n > (1 << 26)) return fail(ORBX_E_CAPACITY, "set %d: at most 2^26 points in a list", b);
+    std::lock_guard<std::mutex> lk(m->mu);
+    for (int i = 0; i < n; i++) {
+        if (slots[i] < 0 || slots[i] >= m->slots) return fail(ORBX_E_ARG, "set %d: slot %d (entry %d) is outside the map's %d slots", b, slots[i], i, m->slots);
+        if (!(m->state[slots[i]] & kMapPresent)) return fail(ORBX_E_ARG, "set %d: slot %d (entry %d) holds no point", b, slots[i], i);
+    }
+    rt::set_device(h->device);
+    if (int rc = map_lay_set(m, b, n)) return rc;
+    if (n == 0) return ORBX_OK;
+    const size_t o_rec = al16(4 * (size_t)n);
+    if (int rc = map_stage(m, o_rec + sizeof(MapSetRec), sizeof(MapSetRec))) return rc;
+    uint8_t* hp = m->h_stage.p;
+    memcpy(hp, slots, 4 * (size_t)n); memcpy(hp + o_rec, &m->set_rec[b], sizeof(MapSetRec));
+    if (rt::copy_h2d(m->set_rec[b].slots, hp, 4 * (size_t)n, h->s0) || rt::copy_h2d(m->d_stage.p, hp + o_rec, sizeof(MapSetRec), h->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
+    const dim3 grid((unsigned)((4 * (size_t)n + 255) / 256), 1, 1), blk(256, 1, 1);
+    ORBX_LAUNCH(k_map_gather, grid, blk, 0, h->s0, (const MapSetRec*)m->d_stage.p, m->S, (const unsigned*)nullptr, m->slots, 0u);
+    if (rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "set %d: gather failed: %s", b, rt::last_error());
+    m->sets[b].M = n;
+    return ORBX_OK;
+}
+
+const orbm_points* orbm_map_set(orbx_extractor* h, const orbm_map* m, int b) {
+    if (map_call_check(h, m)) return nullptr;
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (b < 0 || b >= m->max_sets || !m->built[b]) { fail(ORBX_E_ARG, "set %d has not been built (the map has %d sets)", b, m->max_sets); return nullptr; }
+    return &m->sets[b];
+}
+
+int orbm_map_set_fetch(orbx_extractor* h, const orbm_map* m, int b, int* slots, uint8_t* seen) {
+    if (int rc = map_call_check(h, m)) return rc;
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (b < 0 || b >= m->max_sets || !m->built[b]) return fail(ORBX_E_ARG, "set %d has not been built (the map has %d sets)", b, m->max_sets);
+    rt::set_device(h->device);
+    const size_t M = m->sets[b].M;
+    if (M == 0) return ORBX_OK;
+    // the slots and the flags lie side by side in the set's block: one copy brings both
+    const uint8_t* src = (const uint8_t*)m->set_rec[b].slots; const size_t o_seen = (size_t)(m->set_rec[b].seen - src), bytes = o_seen + M;
+    const uint8_t* got = src;
+    if (rt::memory_is_host()) { if (rt::stream_sync(h->s0)) return fail(ORBX_E_DEVICE, "set %d: download failed: %s", b, rt::last_error()); }
+    else {
+        if (h->h_res.ensure(bytes + 64) || rt::copy_d2h(h->h_res.p, src, bytes, h->s0) || rt::stream_sync(h->s0)) return fail(ORBX_E_DEVICE, "set %d: download failed: %s", b, rt::last_error());
+        got = h->h_res.p;
+    }
+    if (slots) memcpy(slots, got, 4 * M);
+    if (seen) memcpy(seen, got + o_seen, M);
+    return ORBX_OK;
+}
+
+int orbm_points_fetch(orbx_extractor* h, const orbm_points* p, float* pos, float* normal, float* min_distance, float* max_distance, uint8_t* desc) {
+    if (!h || !p) return fail(ORBX_E_ARG, "null");
+    if (p->device != h->device) return fail(ORBX_E_ARG, "map points live on another device");
+    rt::set_device(h->device);
+    const size_t M = p->M;
+    if (M == 0) return ORBX_OK;
+    if ((pos && fetch_sync(h, pos, p->pos, 12 * M)) || (normal && fetch_sync(h, normal, p->normal, 12 * M)) || (min_distance && fetch_sync(h, min_distance, p->min_d, 4 * M)) ||
+        (max_distance && fetch_sync(h, max_distance, p->max_d, 4 * M)) || (desc && fetch_sync(h, desc, p->desc, 32 * M)))
+        return fail(ORBX_E_DEVICE, "download failed: %s", rt::last_error());
+    return ORBX_OK;
 }
 
 }  // extern "C"

@@ -205,6 +205,18 @@ __global__ void k_bow_rotation_prune_rig(const BowPairRig* __restrict__ pairs, i
 __global__ void k_bow_dists(const BowItem* __restrict__ items, int nitems, const unsigned long long* __restrict__ desc1,
                             const unsigned long long* __restrict__ desc2, const uint8_t* __restrict__ eligible2,
                             const int* __restrict__ feat2, int* __restrict__ out);
+// the resident map (orbm_map): field scatter, and Tracking::UpdateLocalPoints as stamp / count / scan / compact / gather
+__global__ void k_map_scatter(int n, const int* __restrict__ slots, const unsigned long long* __restrict__ desc, const float* __restrict__ pos,
+                              const float* __restrict__ normal, const float* __restrict__ min_d, const float* __restrict__ max_d, const uint8_t* __restrict__ bad,
+                              MapStore S);
+__global__ void k_map_seen(const int* __restrict__ seen_start, const int* __restrict__ seen_slots, unsigned* __restrict__ seen_stamp, int nslots, unsigned mark);
+__global__ void k_map_stamp(const MapSeg* __restrict__ segs, const int* __restrict__ kf_slots, int row_cap, const uint8_t* __restrict__ state,
+                            unsigned* __restrict__ stamp, int nslots, unsigned top);
+__global__ void k_map_compact(const MapSeg* __restrict__ segs, const int* __restrict__ kf_slots, int row_cap, const uint8_t* __restrict__ state,
+                              const unsigned* __restrict__ stamp, int nslots, unsigned top, int* __restrict__ chunk_cnt, const int* __restrict__ chunk_off,
+                              const MapSetRec* __restrict__ sets);
+__global__ void k_map_scan(const int* __restrict__ frame_chunk0, const int* __restrict__ chunk_cnt, int* __restrict__ chunk_off, int* __restrict__ M_out);
+__global__ void k_map_gather(const MapSetRec* __restrict__ sets, MapStore S, const unsigned* __restrict__ seen_stamp, int nslots, unsigned base);
 
 __global__ void k_distinctive(const unsigned long long* __restrict__ desc, const int* __restrict__ start, int P, int* __restrict__ best);
 __global__ void k_voc_descend(const unsigned long long* __restrict__ fdesc, const int* __restrict__ n_feat, int n_fixed, int cap, int B,

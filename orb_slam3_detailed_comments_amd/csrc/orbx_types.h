@@ -102,6 +102,15 @@ struct ProjectParams {
 //   frames with their own maps (.._batch_maps): offset = flags = the prefix sum of M_b
 //   projection batches (LastFrame / KeyFrame): desc = the frame's uploaded descriptor rows, M = cap_last, offset = flags = b * cap_last (pos .. max_d unused)
 struct FrameMapRec { const float *pos, *normal, *min_d, *max_d; const unsigned long long* desc; int M, offset, flags; };
+// The device-resident map (orbm_map): the store of map-point fields by slot; state[slot]: bit 0 = the slot holds a point, bit 1 = that point is bad
+struct MapStore { unsigned long long* desc; float *pos, *normal, *min_d, *max_d; uint8_t* state; };
+constexpr int kMapPresent = 1, kMapBad = 2;
+constexpr int kMapChunk = 256;         // visited positions per workgroup of the local-map build: one chunk, one count
+// one visited key-frame row of a local-map build (Tracking::UpdateLocalPoints): `n` slots of row `row`, which frame `set` visits at positions
+// [pos0, pos0 + n) of its walk; the row's chunks are chunk0 .. chunk0 + ceil(n / kMapChunk) - 1 of the call (numbered frame by frame, in visiting order)
+struct MapSeg { int set, row, n, pos0, chunk0; };
+// one point set the map builds: where its M points go, slot by slot (slots: which store slot point j is; seen: 1 = the slot is in set `set`'s seen list)
+struct MapSetRec { int* slots; uint8_t* seen; unsigned long long* desc; float *pos, *normal, *min_d, *max_d; int M, set; };
 // one record of k_grid_build_kfs: the grid of one device-resident key frame (orbm_keyframe) for one set of image bounds
 struct GridBuildRec { const KeyPointRec* kps; int* cell_of; int* cell_start; int* cell_items; int N; GridParams g; };
 // one target of orbm_fuse_candidates_batch (k_fuse_candidates): a resident key frame's arrays and the grid built for the target's bounds, the projection of

@@ -5,6 +5,7 @@ import ctypes as C
 
 import numpy as np
 
+from ._lib import OrbxError
 from .sophus import SE3f, Sim3f, as_se3
 from .views import FuseTarget, Projection as _Projection
 
@@ -527,6 +528,110 @@ class ResidentPoints:
     def close(self):
         if self._p:
             self._lib.L.orbm_points_destroy(self._p); self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def PointsFetch(ext, points):
+    """(pos [M, 3], normal [M, 3], min_distance [M], max_distance [M], desc [M, 32]) of any resident point set (orbm_points_fetch)."""
+    m = points.M
+    pos = np.zeros((m, 3), np.float32); normal = np.zeros((m, 3), np.float32); mn = np.zeros(m, np.float32); mx = np.zeros(m, np.float32); desc = np.zeros((m, 32), np.uint8)
+    ext._lib.check(ext._lib.L.orbm_points_fetch(ext._h, points._p, pos.ctypes.data, normal.ctypes.data, mn.ctypes.data, mx.ctypes.data, desc.ctypes.data))
+    return pos, normal, mn, mx, desc
+
+
+class _MapSet:
+    """A point set a ResidentMap built: usable wherever a ResidentPoints is (LocalPointsBatch, LocalPointsRigBatch, FuseCandidatesBatch).  It belongs to
+    the map: close() does nothing, and it is valid until the map rebuilds that set."""
+
+    def __init__(self, p, M):
+        self._p, self.M = C.c_void_p(p), M
+
+    def close(self):
+        pass
+
+
+class ResidentMap:
+    """orbm_map: the map on the device.  The fields the searches read live in a store addressed by slot (update / set_bad), the map-point matches of
+    key frames are rows of slots (set_keyframe), and local_points builds Tracking::UpdateLocalPoints (src/Tracking.cc:4088-4120) of B frames on the
+    device into point sets that set(b) hands to the batched searches.  ext: any extractor on the map's device; every method takes `ext=` to run
+    through another handle (LocalMapping's thread updates, Tracking's thread builds)."""
+
+    def __init__(self, ext, slots, kf_rows, kf_row_cap, max_sets):
+        self._lib, self._ext = ext._lib, ext
+        self.slots, self.kf_rows, self.kf_row_cap, self.max_sets = slots, kf_rows, kf_row_cap, max_sets
+        h = C.c_void_p()
+        self._lib.check(self._lib.L.orbm_map_create(ext._h, int(slots), int(kf_rows), int(kf_row_cap), int(max_sets), C.byref(h)))
+        self._m = h
+
+    def _h(self, ext):
+        return (ext or self._ext)._h
+
+    def update(self, slots, pos, normal, min_distance, max_distance, desc, is_bad=None, ext=None):
+        """SetWorldPos / UpdateNormalAndDepth / ComputeDistinctiveDescriptors of the points at `slots` (distinct): every field the searches read"""
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        s = np.ascontiguousarray(slots, np.int32)
+        pos, normal, mn, mx, d = f32(pos).reshape(-1, 3), f32(normal).reshape(-1, 3), f32(min_distance), f32(max_distance), np.ascontiguousarray(desc, np.uint8)
+        bad = None if is_bad is None else np.ascontiguousarray(is_bad, np.uint8)
+        P = _WorldPointView(); P.M = len(pos)
+        P.pos, P.normal, P.min_distance, P.max_distance, P.desc = pos.ctypes.data, normal.ctypes.data, mn.ctypes.data, mx.ctypes.data, d.ctypes.data
+        P.is_bad = None if bad is None else bad.ctypes.data
+        self._lib.check(self._lib.L.orbm_map_update(self._h(ext), self._m, len(s), s.ctypes.data, C.byref(P)))
+
+    def set_bad(self, slots, bad, ext=None):
+        """MapPoint::SetBadFlag for the points at `slots` (distinct)"""
+        s = np.ascontiguousarray(slots, np.int32); b = np.ascontiguousarray(bad, np.uint8)
+        if len(b) != len(s):
+            raise ValueError("%d flags for %d slots" % (len(b), len(s)))
+        self._lib.check(self._lib.L.orbm_map_set_bad(self._h(ext), self._m, len(s), s.ctypes.data, b.ctypes.data))
+
+    def set_keyframe(self, row, slots, ext=None):
+        """GetMapPointMatches() of the key frame kept in `row`: the slot of feature i, or -1"""
+        s = np.ascontiguousarray(slots, np.int32)
+        self._lib.check(self._lib.L.orbm_map_set_keyframe(self._h(ext), self._m, int(row), len(s), s.ctypes.data))
+
+    def local_points(self, rows, seen=None, ext=None):
+        """Tracking::UpdateLocalPoints for B = len(rows) frames: rows[b] = the rows frame b visits, in visiting order (mvpLocalKeyFrames reversed);
+        seen[b] = the slots frame b already holds (or None).  Builds sets 0 .. B - 1, returns M [B]."""
+        B = len(rows)
+        cat = lambda lists: (np.cumsum([0] + [len(r) for r in lists]).astype(np.int32), np.ascontiguousarray(np.concatenate([np.asarray(r, np.int32).ravel() for r in lists] + [np.zeros(0, np.int32)]), np.int32))
+        ks, kr = cat(rows)
+        ss = sl = None
+        if seen is not None:
+            if len(seen) != B:
+                raise ValueError("%d seen lists for %d frames" % (len(seen), B))
+            ss, sl = cat([[] if s is None else s for s in seen])
+        M = np.zeros(max(B, 1), np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._lib.check(self._lib.L.orbm_map_local_points(self._h(ext), self._m, B, ks.ctypes.data, kr.ctypes.data, ptr(ss), ptr(sl), M.ctypes.data))
+        return M[:B]
+
+    def select(self, b, slots, ext=None):
+        """an explicit list of slots (the point set of a Fuse) into set b"""
+        s = np.ascontiguousarray(slots, np.int32)
+        self._lib.check(self._lib.L.orbm_map_select(self._h(ext), self._m, int(b), len(s), s.ctypes.data))
+
+    def set(self, b, ext=None):
+        """set b as the searches take it (valid until the map rebuilds it)"""
+        p = self._lib.L.orbm_map_set(self._h(ext), self._m, int(b))
+        if not p:
+            raise OrbxError(-2, (self._lib.L.orbx_last_error() or b"").decode())
+        return _MapSet(p, self._lib.L.orbm_points_count(C.c_void_p(p)))
+
+    def fetch(self, b, ext=None):
+        """(slots [M_b] int32: the slot of local point j, seen [M_b] uint8: 1 = frame b already holds it - the searches' is_bad)"""
+        m = self.set(b, ext).M
+        slots = np.zeros(m, np.int32); seen = np.zeros(m, np.uint8)
+        self._lib.check(self._lib.L.orbm_map_set_fetch(self._h(ext), self._m, int(b), slots.ctypes.data, seen.ctypes.data))
+        return slots, seen
+
+    def close(self):
+        if self._m:
+            self._lib.L.orbm_map_destroy(self._ext._h, self._m); self._m = None
 
     def __del__(self):
         try:
