@@ -93,7 +93,9 @@ int orbx_extract(orbx_extractor* h, const uint8_t* image, int width, int height,
  * for the orbm_* matchers.  */
 int orbx_extract_batch(orbx_extractor* h, int B, const uint8_t* images, int width, int height, int stride,
                        size_t image_stride, int images_on_device, int lap0, int lap1);
-/* Copy the results of the last batch to the host (blocking).  kps: [B][cap], desc: [B][cap][32], n_out/mono_out: [B]. */
+/* Copy the results of the last batch to the host (blocking).  kps: [B][cap], desc: [B][cap][32], n_out/mono_out: [B].
+ * Waits for the extraction and for its own copies, not for what was queued on the handle behind the extraction: after a batch of more than 32
+ * images the download runs beside a matcher enqueued before this call (orbm_stereo_match, ...), whose own fetch waits for it. */
 int orbx_fetch(orbx_extractor* h, OrbxKeyPoint* kps, uint8_t* desc, int cap, int* n_out, int* mono_out);
 int orbx_sync(orbx_extractor* h);
 

@@ -360,8 +360,9 @@ int configure(orbx_extractor* h, int W, int H, int B) {
         e |= h->d_uRight.ensure(b * cap); e |= h->d_depth.ensure(b * cap); e |= h->d_sad.ensure(b * cap); e |= h->d_nmatch.ensure(b);
         e |= h->d_rowstart.ensure(b * (size_t)((h->H >> kStereoRowShift) + 3)); e |= h->d_rowitems.ensure(b * cap);
         e |= h->d_knn.ensure(4 * b * cap); e |= h->d_ratio.ensure(b * cap);
-        e |= h->h_nm.ensure(3 * b + 4); e |= h->d_qtprof.ensure(32);
+        e |= h->h_nm.ensure(3 * b + 4); e |= h->h_cnt.ensure(2 * b + 4); e |= h->d_qtprof.ensure(32);
         if (e) return fail(ORBX_E_DEVICE, "device allocation failed (batch %d of %dx%d)", B, W, H);
+        h->cnt_gen = 0;                                                     // (h_cnt is a new block: whatever it held is gone, like d_nm)
         rt::memset_async(h->d_status.p, 0, 4 * sizeof(int), h->s0);
         rt::memset_async(h->d_pyr.p, 0, b * h->pyr_stride + 256, h->s0);     // defined row padding for frames written in place (orbx_input_buffer)
         h->maxB = B;
@@ -401,8 +402,9 @@ void enqueue_input(orbx_extractor* h, int B, const uint8_t* d_images, int sw, in
                 lvl0, L0.pitch, h->pyr_stride);
 }
 
-// with_export: the bordered pyramid export forks from s0 behind the pyramid (eager path; a captured graph leaves it out, orbx_extract_batch)
-int enqueue_extract(orbx_extractor* h, int B, const uint8_t* d_images, int src_w, int src_h, int stride, size_t image_stride, int lap0, int lap1, bool with_export) {
+// capturing: s0 is recording a graph (orbx_extract_batch).  The bordered pyramid export, which forks from s0 behind the pyramid, and the record of
+// ev_done are then left out: both belong to the call, not to the graph
+int enqueue_extract(orbx_extractor* h, int B, const uint8_t* d_images, int src_w, int src_h, int stride, size_t image_stride, int lap0, int lap1, bool capturing) {
     const int nl = h->nlevels;
     const dim3 blk2(64, 4, 1), blk1(256, 1, 1);
     // (no fill launches in front of the chain: the quadtree's capacity flag is cleared by k_fast_cells, and the descriptor rows beyond n[b] -
@@ -451,7 +453,7 @@ int enqueue_extract(orbx_extractor* h, int B, const uint8_t* d_images, int src_w
                     (const ResizeTap*)h->d_ytab.p, h->d_pyr.p, h->pyr_stride, lds_pitch, lds_rows);
     }
     stage_end(h, ST_PYRAMID, h->s0);
-    if (with_export && h->exp_edge > 0) { const int rc = export_enqueue(h, B); if (rc) return rc; }
+    if (!capturing && h->exp_edge > 0) { const int rc = export_enqueue(h, B); if (rc) return rc; }
     BlurTaps taps;
     {
         static const int A[7] = {18, 34, 48, 56, 48, 34, 18}, Bt[7] = {18, 34, 49, 55, 49, 34, 18};
@@ -554,7 +556,16 @@ int enqueue_extract(orbx_extractor* h, int B, const uint8_t* d_images, int src_w
         ORBX_LAUNCH(k_undistort, grid, blk1, 0, h->s0, (const KeyPointRec*)h->d_kps.p, (const int*)h->d_nm.p, h->kp_total_cap, h->undist, h->d_kps_un.p);
     }
     stage_end(h, ST_DESCRIBE, h->s0);
-    h->done_lazy = true;                                            // ev_done: recorded by whoever waits for it (record_done_if_pending)
+    // ev_done = "d_kps, d_desc (d_kps_un) and d_nm of this batch are final": nothing behind this point writes them, the matchers only read them.
+    // Large batches record it here, so that it does NOT cover what the caller queues on s0 next, and send the counts block (2 KB, a blit kernel
+    // in s0's own hardware queue) to the host in front of it: orbx_fetch then waits for this event and downloads records and descriptors on s1 while
+    // k_stereo_match runs on s0 (recorded on demand the event would land behind the matcher, and 19 MB of download would wait for 0.8 ms of
+    // kernels that do not touch them).  Small batches keep the on-demand record (orbx_internal.h: the barrier packet costs the next kernel ~6 us,
+    // their download a few us), and so does a capture: a record inside it would become a node of the graph, which no other stream can wait on
+    if (B > ORBX_QT_WIDE_BATCH && !capturing) {
+        const int e = rt::copy_d2h(h->h_cnt.p, h->d_nm.p, sizeof(int) * (2 * h->maxB + 1), h->s0) | rt::event_record(h->ev_done, h->s0);
+        h->done_lazy = false; h->cnt_gen = e ? 0 : h->extract_gen + 1;
+    } else h->done_lazy = true;                                     // recorded by whoever waits for it (record_done_if_pending)
     h->lastB = B; h->extract_gen++; h->ex_undist_gen = h->undist_gen; h->ex_undist_active = h->undist.active != 0;
     if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
     return ORBX_OK;
@@ -606,7 +617,7 @@ void orbx_destroy(orbx_extractor* h) {
     h->d_slots.release(); h->d_candA.release(); h->d_candB.release(); h->d_lvl_keys.release(); h->d_cell_count.release(); h->d_lvl_count.release();
     h->d_final_idx.release(); h->d_status.p = nullptr; h->d_status.n = 0; h->d_nm.release(); h->d_kps.release(); h->d_desc.release();
     h->d_uRight.release(); h->d_depth.release(); h->d_sad.release(); h->d_nmatch.release(); h->d_knn.release(); h->d_ratio.release();
-    h->d_l2r.release(); h->d_r2l.release(); h->d_p3d.release(); h->d_hamA.release(); h->d_hamB.release(); h->d_hamOut.release(); h->h_stage.release(); h->h_nm.release();
+    h->d_l2r.release(); h->d_r2l.release(); h->d_p3d.release(); h->d_hamA.release(); h->d_hamB.release(); h->d_hamOut.release(); h->h_stage.release(); h->h_nm.release(); h->h_cnt.release();
     for (auto& x : h->d_sr) x.release();
     h->h_packA.release(); h->h_packB.release(); h->h_out.release(); h->h_res.release();
     for (auto& x : h->d_si) x.release();
@@ -667,6 +678,10 @@ int orbx_extract_batch(orbx_extractor* h, int B, const uint8_t* images, int widt
         }
         if (geom && C > 1 && h->d_frame.ensure((size_t)B * h->W * h->H * C + 16)) return fail(ORBX_E_DEVICE, "allocation failed");
     }
+    // This batch rewrites d_kps, d_desc and d_nm.  The download of the previous ones (orbx_fetch, on s1) is never still reading them: orbx_fetch
+    // returns only when its copies have landed, so an extraction - with or without a fetch before it - finds s1 idle.  (The blur of this batch is the
+    // next work on s1, behind its fork from s0.)
+    if (h->fetch_pending) return fail(ORBX_E_INTERNAL, "a download of the previous results is still in flight");
     // the previous batch's export may still be reading the pyramid that this one rewrites
     if (h->exp_guard) {
         if (rt::stream_wait_event(h->s0, h->ev_exp_read)) return fail(ORBX_E_DEVICE, "extraction could not be ordered behind the pyramid export: %s", rt::last_error());
@@ -695,7 +710,7 @@ int orbx_extract_batch(orbx_extractor* h, int B, const uint8_t* images, int widt
             if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
             if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
             if (hipStreamBeginCapture(h->s0, hipStreamCaptureModeThreadLocal) != hipSuccess) return fail(ORBX_E_DEVICE, "graph capture failed to start");
-            rc = enqueue_extract(h, B, d_images, width, height, stride, image_stride, lap0, lap1, false);
+            rc = enqueue_extract(h, B, d_images, width, height, stride, image_stride, lap0, lap1, true);
             const hipError_t e = hipStreamEndCapture(h->s0, &h->graph);
             if (rc || e != hipSuccess || hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0) != hipSuccess) {
                 h->graph_exec = nullptr;
@@ -708,13 +723,14 @@ int orbx_extract_batch(orbx_extractor* h, int B, const uint8_t* images, int widt
         // the pyramid export is not part of the graph (its ring slot changes from call to call): it forks from s0 behind the whole replay
         if (h->exp_edge > 0 && (rc = export_enqueue(h, B))) return rc;
         // the records inside the capture belong to the graph; these are the ones other streams can wait on (an upload into the input buffer
-        // waits for ev_import: after a replay that is the end of the whole graph, which is later than needed but never too early)
+        // waits for ev_import: after a replay that is the end of the whole graph, which is later than needed but never too early; ev_done after a
+        // replay is recorded by its first waiter - orbx_fetch before a matcher is queued, or behind it)
         h->import_lazy = true; h->done_lazy = true;
         h->lastB = B; h->extract_gen++; h->ex_undist_gen = h->undist_gen; h->ex_undist_active = h->undist.active != 0;
         return ORBX_OK;
     }
 #endif
-    return enqueue_extract(h, B, d_images, width, height, stride, image_stride, lap0, lap1, true);
+    return enqueue_extract(h, B, d_images, width, height, stride, image_stride, lap0, lap1, false);
 }
 
 int orbx_set_input(orbx_extractor* h, const OrbxInputSpec* spec) {
@@ -754,17 +770,41 @@ int orbx_fetch(orbx_extractor* h, OrbxKeyPoint* kps, uint8_t* desc, int cap, int
     const size_t kb = (size_t)B * tc * sizeof(KeyPointRec), db = (size_t)B * tc * 32;
     const bool direct = (cap == h->kp_total_cap);   // caller's layout == device layout: no staging, no repack
     if (!direct && h->h_stage.ensure(kb + db + 64)) return fail(ORBX_E_DEVICE, "pinned allocation failed");
-    int e = rt::copy_d2h(h->h_nm.p, h->d_nm.p, sizeof(int) * (2 * h->maxB + 1), h->s0);      // counts, mono indices and the status word behind them
-    if (kps) e |= rt::copy_d2h(direct ? (void*)kps : (void*)h->h_stage.p, h->d_kps.p, kb, h->s0);
-    if (desc) e |= rt::copy_d2h(direct ? (void*)desc : (void*)(h->h_stage.p + kb), h->d_desc.p, db, h->s0);
-    if (e || rt::stream_sync(h->s0)) return fail(ORBX_E_DEVICE, "D2H failed: %s", rt::last_error());
-    if (h->profile) orbx_sync(h);
-    if (h->h_nm.p[2 * h->maxB] != 0) return fail(ORBX_E_INTERNAL, "device quadtree capacity check tripped");
+    const int* nm = h->h_nm.p;
+    int e = 0;
+    if (h->cnt_gen == h->extract_gen) {
+        // Large batch: ev_done sits directly behind k_orient_brief and the counts are already on their way (enqueue_extract).  What the caller
+        // has queued on s0 since (k_stereo_match, k_knn2, the local-points batch) only reads d_kps / d_desc, so the two big copies need not wait
+        // for it: they go out on s1, which is idle from the join in front of k_orient_brief to the fork of the next extraction.  (Not s_copy:
+        // it may hold the next batch's upload, and the download would queue behind it.)  The wait for ev_done is the host's: a device-side
+        // wait, or any other packet, in s1's hardware queue stands behind whatever chain of ANOTHER handle shares that queue (twelve streams
+        // on four queues) - the copies then started 3 ms late and the step was 20 % slower than with the copies on s0
+        // (profiles/fetch_overlap/).  Behind a finished stream the copy engine takes them at once.
+        if (rt::event_sync(h->ev_done)) return fail(ORBX_E_DEVICE, "extraction failed: %s", rt::last_error());
+        nm = h->h_cnt.p;
+        h->fetch_pending = true;
+        if (kps) e |= rt::copy_d2h(direct ? (void*)kps : (void*)h->h_stage.p, h->d_kps.p, kb, h->s1);
+        if (desc) e |= rt::copy_d2h(direct ? (void*)desc : (void*)(h->h_stage.p + kb), h->d_desc.p, db, h->s1);
+        // the next orbx_extract_batch of this handle rewrites both buffers: wait here, for s1 - the extraction is complete, the matcher behind it
+        // on s0 need not be (its own fetch waits for s0)
+        const int se = rt::stream_sync(h->s1);
+        h->fetch_pending = se != 0;
+        e |= se;
+    } else {
+        // small batches and replayed graphs: everything on s0, behind whatever is queued there
+        e = rt::copy_d2h(h->h_nm.p, h->d_nm.p, sizeof(int) * (2 * h->maxB + 1), h->s0);      // counts, mono indices and the status word behind them
+        if (kps) e |= rt::copy_d2h(direct ? (void*)kps : (void*)h->h_stage.p, h->d_kps.p, kb, h->s0);
+        if (desc) e |= rt::copy_d2h(direct ? (void*)desc : (void*)(h->h_stage.p + kb), h->d_desc.p, db, h->s0);
+        e |= rt::stream_sync(h->s0);
+    }
+    if (e) return fail(ORBX_E_DEVICE, "D2H failed: %s", rt::last_error());
+    if (h->profile) orbx_sync(h);       // the stage timers read events of both streams (and of the matcher); the download has run beside it by now
+    if (nm[2 * h->maxB] != 0) return fail(ORBX_E_INTERNAL, "device quadtree capacity check tripped");
     int rc = ORBX_OK;
     for (int b = 0; b < B; b++) {
-        const int n = h->h_nm.p[b];
+        const int n = nm[b];
         if (n_out) n_out[b] = n;
-        if (mono_out) mono_out[b] = h->h_nm.p[h->maxB + b];
+        if (mono_out) mono_out[b] = nm[h->maxB + b];
         if (direct) continue;
         if (n > cap) { rc = ORBX_E_CAPACITY; continue; }
         if (kps) memcpy(kps + (size_t)b * cap, h->h_stage.p + (size_t)b * tc * sizeof(KeyPointRec), (size_t)n * sizeof(KeyPointRec));

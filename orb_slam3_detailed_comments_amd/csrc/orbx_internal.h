@@ -94,9 +94,14 @@ struct orbx_extractor {
     orbx::rt::event_t ev_fork = 0, ev_join = 0, ev_done = 0, ev_copy = 0, ev_import = 0;
     bool copy_pending = false;
     // ev_done / ev_import are recorded when somebody is about to wait for them (another handle's stereo search, an input upload on s_copy), not
-    // after every extraction: a record in the middle of a stream is a barrier packet, and the kernel behind it starts ~6 us later - a third of a
-    // FAST launch at one pair per call.  Recorded late they cover more of the stream than needed, never less.
+    // after every small extraction: a record in the middle of a stream is a barrier packet, and the kernel behind it starts ~6 us later - a third
+    // of a FAST launch at one pair per call.  Recorded late they cover more of the stream than needed, never less.  Large batches record both where
+    // they become true (enqueue_extract): ev_done then means "records, descriptors and counts are final", whatever was queued on s0 behind the
+    // extraction, and orbx_fetch, which waits for it, downloads beside a matcher that only reads them.
     bool done_lazy = false, import_lazy = false;
+    bool fetch_pending = false;   // orbx_fetch has copies in flight on s1 (inside that call only: it returns when they have landed; orbx_extract_batch checks)
+    // counts, mono indices and status word of extraction cnt_gen, copied out on s0 directly behind k_orient_brief (large batches: enqueue_extract)
+    orbx::HostBuf<int> h_cnt; uint64_t cnt_gen = 0;
     orbx::rt::event_t ev_stage[ORBX_NSTAGES][2] = {};
     bool profile = false, serial = false, have_streams = false;
     int lastB = 0;
