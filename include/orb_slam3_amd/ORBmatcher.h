@@ -321,6 +321,37 @@ public:
         return n;
     }
 
+    // ---- one point set searched from MANY key frames, each under its own Sim3: LoopClosing's FindMatchesByProjection from the current key frame and the
+    // verification loop of DetectCommonRegionsFromBoW over its covisible key frames (src/LoopClosing.cc:1046-1090, :1168-1268) in one call ----
+    // for (k) n[k] = SearchByProjection(vpKFs[k], vScw[k], vpPoints, vvpMatched[k], th, ratioHamming);
+    // The calls are independent of one another (no map surgery between them), so they run in one orbm_search_by_projection_sim3_batch over device-resident key
+    // frames (ImplicitCache) and ONE upload of the point set; the sequential accept loop of each key frame runs on the device.  Key frames of a two-camera rig,
+    // and MapPoint types whose mfMinDistance / mfMaxDistance cannot be read (see Fuse(vpKFs, ..) below), take the single calls one after the other.
+    template <class KeyFrameT, class Sim3Vec, class MapPointT>
+    std::vector<int> SearchByProjection(const std::vector<KeyFrameT*> &vpKFs, const Sim3Vec &vScw, const std::vector<MapPointT*> &vpPoints,
+                                        std::vector<std::vector<MapPointT*> > &vvpMatched, int th, float ratioHamming=1.0)
+    {
+        std::vector<std::vector<int> > assigned;
+        const std::vector<int> n = SearchBySim3ProjectionMany(vpKFs, vScw, vpPoints, vvpMatched, th, ratioHamming, /*inlineProjection=*/false, assigned);
+        for (size_t k = 0; k < vpKFs.size(); k++)
+            for (size_t idx = 0; idx < vvpMatched[k].size(); idx++) if (assigned[k][idx] >= 0) vvpMatched[k][idx] = vpPoints[assigned[k][idx]];
+        return n;
+    }
+
+    // for (k) n[k] = SearchByProjection(vpKFs[k], vScw[k], vpPoints, vpPointsKFs, vvpMatched[k], vvpMatchedKF[k], th, ratioHamming);
+    template <class KeyFrameT, class Sim3Vec, class MapPointT>
+    std::vector<int> SearchByProjection(const std::vector<KeyFrameT*> &vpKFs, const Sim3Vec &vScw, const std::vector<MapPointT*> &vpPoints,
+                                        const std::vector<KeyFrameT*> &vpPointsKFs, std::vector<std::vector<MapPointT*> > &vvpMatched,
+                                        std::vector<std::vector<KeyFrameT*> > &vvpMatchedKF, int th, float ratioHamming=1.0)
+    {
+        std::vector<std::vector<int> > assigned;
+        const std::vector<int> n = SearchBySim3ProjectionMany(vpKFs, vScw, vpPoints, vvpMatched, th, ratioHamming, /*inlineProjection=*/true, assigned);
+        for (size_t k = 0; k < vpKFs.size(); k++)
+            for (size_t idx = 0; idx < vvpMatched[k].size(); idx++)
+                if (assigned[k][idx] >= 0) { vvpMatched[k][idx] = vpPoints[assigned[k][idx]]; vvpMatchedKF[k][idx] = vpPointsKFs[assigned[k][idx]]; }
+        return n;
+    }
+
     // Search matches between MapPoints in a KeyFrame and ORB in a Frame.
     // Brute force constrained to ORB that belong to the same vocabulary node (at a certain level)
     // Used in Relocalisation and Loop Detection   — src/ORBmatcher.cc:259-493 (one camera)
@@ -945,6 +976,31 @@ protected:
             Run(row, stale, excluded);
             stale.clear();
         }
+        // ORBmatcher::SearchByProjection(pKF, Scw, ..) of every row at once: occupied[row] = vpMatched[idx] != NULL on entry, excluded(row, i) = the caller's
+        // own tests of point i; assigned[row] = per keypoint the point it gets (-1 none), nmatches[row] = the single call's return value
+        template <class Excluded> void SearchSim3(float ratioHamming, const std::vector<std::vector<uint8_t> >& occupied, const Excluded& excluded,
+                                                  std::vector<std::vector<int> >& assigned, std::vector<int>& nmatches)
+        {
+            const int rows = (int)kfs.size();
+            assigned.assign(rows, std::vector<int>()); nmatches.assign(rows, 0);
+            if (rows == 0 || M == 0) return;
+            std::vector<OrbmSim3Target> t(rows); std::vector<uint8_t> skip((size_t)rows * M);
+            int cap = 1;
+            for (int r = 0; r < rows; r++) {
+                memset(&t[r], 0, sizeof t[r]);
+                t[r].kf = targets[r].kf; t[r].spec = targets[r].spec; t[r].log_scale_factor = targets[r].log_scale_factor; t[r].occupied = occupied[r].data();
+                if (kfs[r]->N > cap) cap = kfs[r]->N;
+                for (int i = 0; i < M; i++) skip[(size_t)r * M + i] = excluded(r, i) ? 1 : 0;
+            }
+            OrbmWorldPointView view = {M, pos.data(), normal.data(), mind.data(), maxd.data(), nullptr, nullptr, desc.data()};
+            orbm_points* set = nullptr;
+            Check(orbm_points_create(SharedHandle(), &view, &set));
+            std::vector<int> out((size_t)rows * cap, -1);
+            const int rc = orbm_search_by_projection_sim3_batch(SharedHandle(), rows, t.data(), set, skip.data(), th, ratioHamming, cap, out.data(), nmatches.data());
+            orbm_points_destroy(set);
+            Check(rc);
+            for (int r = 0; r < rows; r++) assigned[r].assign(out.begin() + (size_t)r * cap, out.begin() + (size_t)r * cap + (kfs[r]->N > 0 ? kfs[r]->N : 1));
+        }
     private:
         template <class Excluded> void Run(int first, const std::vector<int>& subset, const Excluded& excluded)
         {
@@ -1174,8 +1230,17 @@ protected:
         s.v.nlevels = (int)K.mvScaleFactors.size(); s.v.scale_factors = K.mvScaleFactors.data(); s.v.level_sigma2 = K.mvLevelSigma2.data();
     }
 
-    // common body of the two SearchByProjection(KeyFrame*, Sim3, ...) overloads; they differ in how the projection is written
+    // what the two SearchByProjection(KeyFrame*, Sim3, ...) overloads project with: pose = the rigid part of Scw; they differ in how the projection is written
     // (:534 GeometricCamera::project, :656-660 inline pinhole arithmetic with pKF->fx ...)
+    template <class KeyFrameT, class SE3T> static OrbmProjection Sim3ProjectionSpec(KeyFrameT* pKF, const SE3T& pose, bool inlineProjection)
+    {
+        OrbmProjection spec = Spec(pose, pKF->mpCamera, *pKF, /*IsInImage*/ 1);
+        if (inlineProjection) { spec.camera_type = 0; spec.cam[0] = pKF->fx; spec.cam[1] = pKF->fy; spec.cam[2] = pKF->cx; spec.cam[3] = pKF->cy; spec.inline_pinhole = 1; }
+        SpecCentre(spec, pose.inverse().translation());
+        spec.depth_test = 1; spec.distance_test = 1; spec.angle_test = 1;
+        return spec;
+    }
+    // common body of the two single-key-frame overloads
     template <class KeyFrameT, class Sim3T, class MapPointT>
     int SearchBySim3Projection(KeyFrameT* pKF, Sim3T &Scw, const std::vector<MapPointT*> &vpPoints, std::vector<MapPointT*> &vpMatched, int th, float ratioHamming,
                                bool inlineProjection, std::vector<int>& assigned)
@@ -1189,10 +1254,7 @@ protected:
             MapPointT* pMP = vpPoints[i];
             if (!pMP->isBad() && !taken.count(pMP)) pts.take(i, pMP, true);
         }
-        OrbmProjection spec = Spec(pose, pKF->mpCamera, *pKF, /*IsInImage*/ 1);
-        if (inlineProjection) { spec.camera_type = 0; spec.cam[0] = pKF->fx; spec.cam[1] = pKF->fy; spec.cam[2] = pKF->cx; spec.cam[3] = pKF->cy; spec.inline_pinhole = 1; }
-        SpecCentre(spec, pose.inverse().translation());
-        spec.depth_test = 1; spec.distance_test = 1; spec.angle_test = 1;
+        const OrbmProjection spec = Sim3ProjectionSpec(pKF, pose, inlineProjection);
         pts.project(spec);
         ProjStore ps(M);
         for (int i = 0; i < M; i++) {
@@ -1209,6 +1271,40 @@ protected:
         int nmatches = 0;
         Check(orbm_search_by_projection_sim3(SharedHandle(), &fs.v, ps.view(), (float)th, ratioHamming, assigned.data(), &nmatches));
         return nmatches;
+    }
+
+    // common body of the two many-key-frame overloads: assigned[k][idx] = the point vvpMatched[k][idx] gets (-1: none), returns the single calls' return values
+    template <class KeyFrameT, class Sim3Vec, class MapPointT>
+    std::vector<int> SearchBySim3ProjectionMany(const std::vector<KeyFrameT*> &vpKFs, const Sim3Vec &vScw, const std::vector<MapPointT*> &vpPoints,
+                                                std::vector<std::vector<MapPointT*> > &vvpMatched, int th, float ratioHamming, bool inlineProjection,
+                                                std::vector<std::vector<int> >& assigned)
+    {
+        const int K = (int)vpKFs.size(), M = (int)vpPoints.size();
+        std::vector<int> counts(K, 0);
+        assigned.assign(K, std::vector<int>());
+        typedef Decay<decltype(vpKFs[0]->GetPose())> SE3T;
+        FuseBatch<KeyFrameT, MapPointT> job(vpPoints, (float)th, /*chi2*/ false);
+        const bool batched = K > 0 && M > 0 && job.ReadPoints();
+        std::vector<std::vector<int> > rowAssigned; std::vector<int> rowCounts;
+        if (batched) {
+            std::vector<std::vector<uint8_t> > occupied; std::vector<std::set<MapPointT*> > taken;
+            for (int k = 0; k < K; k++) {
+                KeyFrameT* pKF = vpKFs[k];
+                const std::vector<MapPointT*>& vpMatched = vvpMatched[k];
+                if (pKF->NLeft != -1 || (int)vpMatched.size() != pKF->N) continue;
+                job.Add(k, pKF, Sim3ProjectionSpec(pKF, RigidPart<SE3T>(vScw[k]), inlineProjection));
+                occupied.push_back(std::vector<uint8_t>(vpMatched.size() > 0 ? vpMatched.size() : 1, 0));
+                for (size_t i = 0; i < vpMatched.size(); i++) occupied.back()[i] = vpMatched[i] != nullptr;
+                taken.push_back(std::set<MapPointT*>(vpMatched.begin(), vpMatched.end()));
+            }
+            job.SearchSim3(ratioHamming, occupied, [&](int row, int i) { MapPointT* p = vpPoints[i]; return !p || p->isBad() || taken[row].count(p) != 0; }, rowAssigned, rowCounts);
+        }
+        for (int k = 0; k < K; k++) {
+            const int row = batched ? job.RowOf(k) : -1;
+            if (row < 0) { auto Scw = vScw[k]; counts[k] = SearchBySim3Projection(vpKFs[k], Scw, vpPoints, vvpMatched[k], th, ratioHamming, inlineProjection, assigned[k]); }
+            else { assigned[k].swap(rowAssigned[row]); counts[k] = rowCounts[row]; }
+        }
+        return counts;
     }
 
     float mfNNratio;

@@ -828,6 +828,33 @@ typedef struct OrbmFuseTarget OrbmFuseTarget;  /* ONE key frame (one camera) a p
 int orbm_fuse_candidates_batch(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const orbm_points* points, const uint8_t* skip /* [K][M] or NULL */,
                                float th, int chi2_gate, int* best_idx /* [K][M] */, int* best_dist /* [K][M] or NULL */);
 
+/* ORBmatcher::SearchByProjection(KeyFrame* pKF, Sim3f& Scw, vpPoints, vpMatched, th, ratioHamming) and the overload that also returns the points' key frames
+ * (src/ORBmatcher.cc:495-606, :608-732) for ONE resident point set searched from K resident key frames, each under its own Sim3, in one call: LoopClosing's
+ * FindMatchesByProjection searches the matched key frame's covisibility window from the current key frame and DetectCommonRegionsFromBoW searches the same set
+ * again from up to five covisible key frames (src/LoopClosing.cc:1046-1090, :1168-1268), for every loop and merge candidate.  The targets are independent of one
+ * another (nothing is written to the map between them); INSIDE a target the reference's loop over the points is sequential - a keypoint occupied on entry or
+ * taken by an earlier point is invisible to every later point, a point whose best distance is above TH_LOW * ratioHamming takes nothing - and the device
+ * reproduces exactly that order.  Target k: `kf` and `spec` as for orbm_fuse_candidates_batch - spec = what orbm_project_points takes for this search: the rigid
+ * part [R | t / s] of Scw, Ow = its inverse's translation, the camera (inline_pinhole = 1 for the :608 overload), KeyFrame::IsInImage bounds, depth_test = 1,
+ * distance_test = 1, angle_test = 1, bf = 0; log_scale_factor = pKF->mfLogScaleFactor; occupied = [kf N] bytes, vpMatched[idx] != NULL on entry (NULL = none).
+ * The device applies the 0.8 / 1.2 of Get*DistanceInvariance and evaluates MapPoint::PredictScale as orbm_fuse_candidates_batch does; the grids are the same
+ * per-key-frame cache.  skip: [K][M] bytes, the caller's own exclusions (isBad(), membership in spAlreadyFound; NULL = none).
+ * assigned[k][idx] (rows of `cap` entries, cap >= the largest N): the index into the point set of the point the reference writes to vpMatched[idx] of target
+ * k, -1 for untouched entries and for the entries from N_k up to cap; nmatches[k]: the reference's return value.  Blocking.
+ * K == 0 or an empty set: ORBX_OK, nothing is written.  Refused before anything is enqueued (ORBX_E_ARG, the message names the target): null arguments, K < 0, a
+ * key frame or the point set on another device than the handle, empty image bounds, a key frame without scale levels, cap below the largest N.
+ * Limits: K <= 65535, K x M <= 2^28 pairs and K x cap <= 2^28 result entries (ORBX_E_CAPACITY beyond; nothing is truncated).
+ * (declared apart from its typedef like OrbmFuseTarget; the Python mirror is checked by tests/test_sim3_projection_batch.py) */
+struct OrbmSim3Target {
+    const orbm_keyframe* kf;
+    OrbmProjection spec;
+    float log_scale_factor;
+    const uint8_t* occupied;
+};
+typedef struct OrbmSim3Target OrbmSim3Target;  /* ONE (key frame, Sim3) a point set is searched from */
+int orbm_search_by_projection_sim3_batch(orbx_extractor* h, int K, const OrbmSim3Target* targets, const orbm_points* points, const uint8_t* skip /* [K][M] or NULL */,
+                                         float th, float ratio_hamming, int cap, int* assigned /* [K][cap] */, int* nmatches /* [K] */);
+
 /* SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) for a fisheye-rig frame (F.Nleft != -1; src/ORBmatcher.cc:259-493 incl. :343-372, :414-446).
  * K1 / K2 list ALL features by index (camera 1 first: keys = mvKeys followed by mvKeysRight, descriptor rows as stored); nleft2 = F.Nleft.
  * assigned2[j] = feature of K1 whose map point is written to vpMapPointMatches[j], -1 = NULL (after the rotation-consistency pruning). */

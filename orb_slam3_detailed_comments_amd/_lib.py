@@ -33,7 +33,7 @@ SYMBOLS = [
     "orbm_project_points", "orbm_search_by_projection_sim3", "orbm_search_by_projection_keyframe", "orbm_fuse_candidates", "orbm_search_by_sim3", "orbm_distinctive_descriptors",
     "orbm_search_by_projection_mappoints_fisheye", "orbm_search_by_projection_frame_fisheye", "orbm_search_for_triangulation_batch",
     "orbm_search_local_points_rig_batch", "orbm_search_by_projection_lastframe_rig_batch", "orbm_search_rig_batch_fetch",
-    "orbm_search_local_points_batch_maps", "orbm_search_local_points_rig_batch_maps", "orbm_points_count", "orbm_fuse_candidates_batch",
+    "orbm_search_local_points_batch_maps", "orbm_search_local_points_rig_batch_maps", "orbm_points_count", "orbm_fuse_candidates_batch", "orbm_search_by_projection_sim3_batch",
     "orbm_map_create", "orbm_map_destroy", "orbm_map_update", "orbm_map_set_bad", "orbm_map_set_keyframe", "orbm_map_local_points", "orbm_map_select", "orbm_map_set",
     "orbm_map_set_fetch", "orbm_points_fetch", "orbm_map_debug_epoch",
     "orbv_create", "orbv_load_text", "orbv_destroy", "orbv_words", "orbv_transform", "orbv_transform_extracted", "orbv_fetch", "orbm_search_by_bow_frames_batch",
@@ -159,6 +159,7 @@ class OrbxLib:
         L.orbm_search_local_points_rig_batch_maps.argtypes = [vp, i, vp, i, i, vp, vp, vp, f, f, i, f, f, i]
         L.orbm_points_count.argtypes = [vp]
         L.orbm_fuse_candidates_batch.argtypes = [vp, i, vp, vp, vp, f, i, vp, vp]
+        L.orbm_search_by_projection_sim3_batch.argtypes = [vp, i, vp, vp, vp, f, f, i, vp, vp]
         L.orbm_map_create.argtypes = [vp, i, i, i, i, C.POINTER(vp)]
         L.orbm_map_destroy.argtypes = [vp, vp]
         L.orbm_map_update.argtypes = [vp, vp, i, vp, vp]

@@ -11,6 +11,8 @@
 //                  keypoint from the candidate set of every later one (a true sequential dependency).
 //   k_fuse_candidates  the candidate search of ORBmatcher::Fuse (src/ORBmatcher.cc:1325-1660) for one resident point set against many resident key
 //                  frames: one thread per (point, key frame), geometry, PredictScale, window walk, gates, Hamming distance and the minimum in one pass
+//   k_sim3_candidates / k_sim3_accept  ORBmatcher::SearchByProjection(pKF, Scw, ..) (src/ORBmatcher.cc:495-732) for one resident point set from many resident
+//                  key frames: the choice of every (point, key frame) against the occupancy on entry, then the sequential accept loop, one wave per key frame
 //   k_bow_search   inner loops of ORBmatcher::SearchForTriangulation (src/ORBmatcher.cc:1045-1323): one wave per
 //                  unmatched feature of KF1 against the features of KF2 in the same vocabulary node.
 //   k_map_*        the device-resident map (orbm_map): scatter of updated map points into the store, and Tracking::UpdateLocalPoints
@@ -587,7 +589,10 @@ __device__ __forceinline__ bool fuse_query(const FuseTargetRec& R, int i, const 
     A.min_level = n - 1; A.max_level = n; A.active = 1; A.gate = chi2_gate ? 2 : 0;
     return true;
 }
-__device__ __forceinline__ void fuse_best(const FuseTargetRec& R, const AreaQuery& A, const unsigned long long* __restrict__ dq, int& best_idx, int& best_dist) {
+// (taken(idx): the keypoint is invisible to this query - ORBmatcher::SearchByProjection(pKF, Scw, ..)'s `if (vpMatched[idx]) continue;`; Fuse has no such test)
+template <class Taken>
+__device__ __forceinline__ void fuse_best_free(const FuseTargetRec& R, const AreaQuery& A, const unsigned long long* __restrict__ dq, const Taken& taken, int& best_idx,
+                                               int& best_dist) {
     const GridParams& g = R.g;
     const int nMinX = imax(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(A.x, g.min_x), A.r), g.gw_inv)));
     const int nMaxX = imin(kGridCols - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(A.x, g.min_x), A.r), g.gw_inv)));
@@ -599,6 +604,7 @@ __device__ __forceinline__ void fuse_best(const FuseTargetRec& R, const AreaQuer
         const int s = R.cell_start[ix * kGridRows + nMinY], e = R.cell_start[ix * kGridRows + nMaxY + 1];        // the cells of one column are consecutive
         for (int j = s; j < e; j++) {
             const int idx = R.cell_items[j];
+            if (taken(idx)) continue;
             const KeyPointRec k = R.kps[idx];
             if (!area_accept(A, k, idx, true, 0, nullptr)) continue;
             if (A.gate == 2 && !chi2_accept(A, k, R.ur[idx], g)) continue;
@@ -607,6 +613,9 @@ __device__ __forceinline__ void fuse_best(const FuseTargetRec& R, const AreaQuer
             if (dist < best_dist) { best_dist = dist; best_idx = idx; }
         }
     }
+}
+__device__ __forceinline__ void fuse_best(const FuseTargetRec& R, const AreaQuery& A, const unsigned long long* __restrict__ dq, int& best_idx, int& best_dist) {
+    fuse_best_free(R, A, dq, [](int) { return false; }, best_idx, best_dist);
 }
 // skip: [K][M] bytes or NULL (pairs the caller excludes); best_idx / best_dist: [K][M], -1 where the reference would not fuse (best_dist may be NULL)
 __global__ void __launch_bounds__(256) k_fuse_candidates(const FuseTargetRec* __restrict__ T, int M, const float* __restrict__ pos, const float* __restrict__ normal,
@@ -625,6 +634,105 @@ __global__ void __launch_bounds__(256) k_fuse_candidates(const FuseTargetRec* __
     if (bd > th_low) bi = -1;                                         // bestDist <= TH_LOW (:1505 / :1654)
     best_idx[o] = bi;
     if (best_dist) best_dist[o] = bi >= 0 ? bd : -1;
+}
+
+// ORBmatcher::SearchByProjection(KeyFrame* pKF, Sim3f& Scw, vpPoints, [vpPointsKFs,] vpMatched, [vpMatchedKF,] th, ratioHamming) (src/ORBmatcher.cc:495-606,
+// :608-732) for ONE resident point set against K resident key frames, each under its own Sim3 (orbm_search_by_projection_sim3_batch).  The head of the
+// reference's loop is Fuse's (fuse_query, no chi-square gate) and so is the window walk (fuse_best_free), but here the loop over the points is sequential:
+// a keypoint that is occupied on entry or taken by an earlier point is invisible to every later one, and a point whose best distance is above
+// TH_LOW * ratioHamming (`int * float`: a float comparison) takes nothing, so a later point can still have that keypoint.
+//   sim3_choice        the keypoint point i takes when the keypoints `taken` names are invisible, or -1.  It is the FIRST minimum of the walk: removing a
+//                      keypoint other than that one never changes it, and removing it can only raise the minimum - a point that takes nothing never will
+//   k_sim3_candidates  one THREAD per (point, key frame), grid ((M + 255) / 256, K): the choice against the occupancy on entry.  Nothing else leaves the thread
+//   k_sim3_accept      one wave per key frame, the occupancy bitmap in LDS: the points in order, 64 at a time, in the optimistic rounds of local_accept_body
+__device__ __forceinline__ bool bit_of(const uint32_t* bits, int i) { return ((bits[i >> 5] >> (i & 31)) & 1u) != 0u; }
+template <class Taken>
+__device__ __forceinline__ int sim3_choice(const FuseTargetRec& R, int i, const float* __restrict__ pos, const float* __restrict__ normal, const float* __restrict__ min_d,
+                                           const float* __restrict__ max_d, const unsigned long long* __restrict__ qdesc, float th, float max_dist, int debug_flags,
+                                           const Taken& taken) {
+    AreaQuery A;
+    int bi = -1, bd = 256;                                            // bestDist = 256 (:582 / :698)
+    if (fuse_query(R, i, pos, normal, min_d, max_d, th, 0, debug_flags, A)) fuse_best_free(R, A, qdesc + 4 * (size_t)i, taken, bi, bd);
+    return (bi >= 0 && (float)bd <= max_dist) ? bi : -1;             // bestDist <= TH_LOW * ratioHamming (:609 / :722)
+}
+// occupied: the uploaded rows of `vpMatched[idx] != NULL` bytes (target k's at T[k].occ_off); skip: [K][M] bytes or NULL; max_dist = TH_LOW * ratioHamming;
+// choice: [K][M]
+__global__ void __launch_bounds__(256) k_sim3_candidates(const Sim3TargetRec* __restrict__ T, int M, const float* __restrict__ pos, const float* __restrict__ normal,
+                                                         const float* __restrict__ min_d, const float* __restrict__ max_d, const unsigned long long* __restrict__ qdesc,
+                                                         const uint8_t* __restrict__ occupied, const uint8_t* __restrict__ skip, float th, float max_dist,
+                                                         int debug_flags, int* __restrict__ choice) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= M) return;
+    const Sim3TargetRec& S = T[blockIdx.y];
+    const size_t o = (size_t)blockIdx.y * (size_t)M + (size_t)i;
+    const uint8_t* occ = S.occ_off >= 0 ? occupied + S.occ_off : (const uint8_t*)nullptr;
+    int c = -1;
+    if (S.F.N > 0 && !(skip && skip[o]))
+        c = sim3_choice(S.F, i, pos, normal, min_d, max_d, qdesc, th, max_dist, debug_flags, [occ](int idx) { return occ && occ[idx]; });
+    choice[o] = c;
+}
+// The accept loop.  Per 64 consecutive points, one per lane, until none is pending:
+//   1. a lane whose choice has been taken since it was made walks its window again against the live bitmap (the query is recomputed: fuse_query is
+//      deterministic, and conflicts are rare) - its choice is then what the sequential loop would pick if every earlier point had been committed;
+//   2. every pending lane claims its keypoint (LDS, minimum lane per slot of a small table keyed by the low bits of the index);
+//   3. a lane is DIRTY if an earlier lane claims its slot: that lane may take the very keypoint (or one that merely shares the slot - the lane then only
+//      waits a round).  A claim on any OTHER keypoint cannot change a first minimum;
+//   4. the lanes before the first dirty one commit, the others repeat from 1.  The first pending lane holds the minimum of its slot: every round commits.
+// assigned: [K][cap], -1 = untouched - every entry is written once: by the lane that commits it, or after the loop (not occupied then, or occupied on entry);
+// dynamic LDS: the occupancy bitmap, (N + 31) / 32 words for the largest N of the call.
+constexpr int kSim3ClaimSlots = 256;
+__global__ void __launch_bounds__(64) k_sim3_accept(const Sim3TargetRec* __restrict__ T, int M, const float* __restrict__ pos, const float* __restrict__ normal,
+                                                    const float* __restrict__ min_d, const float* __restrict__ max_d, const unsigned long long* __restrict__ qdesc,
+                                                    const uint8_t* __restrict__ occupied, float th, float max_dist, int debug_flags, int cap,
+                                                    const int* __restrict__ choice, int* __restrict__ assigned, int* __restrict__ nmatches) {
+    ORBX_DYN_SMEM(smem);
+    uint32_t* s_occ = (uint32_t*)smem;
+    __shared__ unsigned s_claim[kSim3ClaimSlots];
+    const int lane = lane_id();
+    const Sim3TargetRec& S = T[blockIdx.x];
+    const FuseTargetRec& R = S.F;
+    const int N = R.N, nwords = (N + 31) / 32;
+    const uint8_t* occ0 = S.occ_off >= 0 ? occupied + S.occ_off : (const uint8_t*)nullptr;
+    choice += blockIdx.x * (size_t)M; assigned += blockIdx.x * (size_t)cap;
+    for (int w = lane; w < nwords; w += 64) {
+        uint32_t bits = 0;
+        if (occ0) for (int k = 0; k < 32; k++) { const int i = 32 * w + k; if (i < N && occ0[i]) bits |= 1u << k; }
+        s_occ[w] = bits;
+    }
+    for (int i = lane; i < kSim3ClaimSlots; i += 64) s_claim[i] = 0xFFu;
+    ORBX_WAVE_SYNC();
+    int nm = 0;
+    for (int i0 = 0; i0 < M; i0 += 64) {
+        const int qi = i0 + lane;
+        int c = qi < M ? choice[qi] : -1;
+        bool pending = c >= 0;
+        while (__ballot(pending) != 0ull) {
+            // 1. a choice that is gone: again, against the live occupancy
+            if (pending && bit_of(s_occ, c)) {
+                c = sim3_choice(R, qi, pos, normal, min_d, max_d, qdesc, th, max_dist, debug_flags, [s_occ](int idx) { return bit_of(s_occ, idx); });
+                pending = c >= 0;
+            }
+            // 2. claims
+            const unsigned slot = (unsigned)c & (unsigned)(kSim3ClaimSlots - 1);
+            if (pending) atomicMin(&s_claim[slot], (unsigned)lane);
+            ORBX_WAVE_SYNC();
+            // 3. dirty: an earlier lane claims my slot
+            const bool dirty = pending && s_claim[slot] < (unsigned)lane;
+            const unsigned long long dmask = __ballot(dirty);
+            const int first_dirty = dmask ? __ffsll(dmask) - 1 : 64;
+            ORBX_WAVE_SYNC();
+            if (pending) s_claim[slot] = 0xFFu;                         // (every claimer of a slot restores it)
+            ORBX_WAVE_SYNC();
+            // 4. commit the lanes before the first dirty one
+            const bool commit = pending && lane < first_dirty;
+            if (commit) { assigned[c] = qi; atomicOr(&s_occ[c >> 5], 1u << (c & 31)); pending = false; }
+            nm += __popcll(__ballot(commit));
+            ORBX_WAVE_SYNC();
+        }
+    }
+    ORBX_WAVE_SYNC();
+    for (int i = lane; i < cap; i += 64) if (i >= N || (occ0 && occ0[i]) || !bit_of(s_occ, i)) assigned[i] = -1;
+    if (lane == 0) nmatches[blockIdx.x] = nm;
 }
 
 // ORBmatcher::SearchByProjection(Frame, MapPoints) accept loop (src/ORBmatcher.cc:62-166) on the device, one wave per frame of a batch.

@@ -8,7 +8,8 @@
 //                           SearchByProjection(Frame, Frame), SearchForTriangulation, SearchByBoW, SearchForInitialization, the projected-point searches
 //                           (Sim3, key frame, Fuse, SearchBySim3), DistinctiveDescriptors, the two-camera (fisheye) forms
 //   resident objects        orbm_points (map points), orbm_keyframe (key frames, with the grids the Fuse batch builds for them) and the searches that read them;
-//                           orbm_fuse_candidates_batch (one point set against many key frames) stands with the single Fuse search
+//                           orbm_fuse_candidates_batch and orbm_search_by_projection_sim3_batch (one point set against many key frames) stand with the single
+//                           Fuse search
 //   batched routes          frames of the last extraction: SearchLocalPoints, SearchByProjection(last frame / key frame), SearchByBoW; one fetch
 //   rig routes              the same for two-camera frames (two handles), fetched through the same core
 //   resident map            orbm_map: the map-point store by slot, key-frame rows of slots, Tracking::UpdateLocalPoints for a batch of frames built on the
@@ -1780,6 +1781,43 @@ KfGrid* kf_grid_for(orbm_keyframe* kf, const float key[4], bool* fresh) {
     *fresh = true;
     return g;
 }
+// what orbm_fuse_candidates_batch and orbm_search_by_projection_sim3_batch refuse of target k alike
+int batch_target_check(const orbx_extractor* h, int k, const orbm_keyframe* kf, const OrbmProjection& spec) {
+    if (!kf) return fail(ORBX_E_ARG, "target %d: null key frame", k);
+    if (kf->device != h->device) return fail(ORBX_E_ARG, "target %d: its key frame lives on another device than the handle", k);
+    if (kf->nlevels < 1) return fail(ORBX_E_ARG, "target %d: its key frame has no scale levels", k);
+    if (!(spec.max_x > spec.min_x) || !(spec.max_y > spec.min_y)) return fail(ORBX_E_ARG, "target %d: empty image bounds", k);
+    return ORBX_OK;
+}
+// the grids the targets of one call read, found in the key frames' caches or made (`build`: the records k_grid_build_kfs takes for those).  Used under the mutex.
+struct BatchGrids {
+    KfGridUse use; std::vector<GridBuildRec> build; std::vector<KfGrid*> made;
+    // (caller holds the mutex) fills R for one target: the key frame's arrays, the projection, the grid for the spec's bounds; false = the grid's allocation failed
+    bool target(orbm_keyframe* kf, const OrbmProjection& spec, float log_scale_factor, const float* inv_level_sigma2, FuseTargetRec& R) {
+        memset(&R, 0, sizeof R);
+        memcpy(&R.P, &spec, sizeof R.P);
+        R.g.min_x = spec.min_x; R.g.min_y = spec.min_y;
+        R.g.gw_inv = (float)kGridColsHost / (spec.max_x - spec.min_x); R.g.gh_inv = (float)kGridRowsHost / (spec.max_y - spec.min_y);      // src/Frame.cc:190-191
+        if (inv_level_sigma2) for (int l = 0; l < kf->nlevels; l++) R.g.inv_sigma2[l] = inv_level_sigma2[l];
+        R.kps = kf->dev.kps; R.desc = kf->dev.desc; R.ur = kf->dev.ur;
+        R.N = kf->N; R.nlevels = kf->nlevels; R.log_scale_factor = log_scale_factor;
+        for (int l = 0; l < kMaxLevels; l++) R.scale_factors[l] = kf->scale[l];
+        const float key[4] = {R.g.min_x, R.g.min_y, R.g.gw_inv, R.g.gh_inv};
+        bool fresh;
+        KfGrid* G = kf_grid_for(kf, key, &fresh);
+        if (!G) return false;
+        G->users++; use.held.push_back(G);
+        R.cell_start = G->mem; R.cell_items = G->mem + kGridCellStride;
+        if (fresh) { GridBuildRec b; b.kps = kf->dev.kps; b.cell_of = G->mem + kGridCellStride + kf->N + 1; b.cell_start = G->mem; b.cell_items = G->mem + kGridCellStride; b.N = kf->N; b.g = R.g; build.push_back(b); made.push_back(G); }
+        return true;
+    }
+    void launch_builds(orbx_extractor* h, const GridBuildRec* dev) const {
+        if (build.empty()) return;
+        const dim3 gridb((unsigned)build.size(), 1, 1), blkb(kGridThreads, 1, 1);
+        ORBX_LAUNCH(k_grid_build_kfs, gridb, blkb, 0, h->s0, dev);
+    }
+    void built() { for (KfGrid* g : made) g->built = true; }         // (the stream has been waited for; still under the mutex: `made` is empty otherwise)
+};
 }  // namespace
 
 int orbm_fuse_candidates_batch(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const orbm_points* points, const uint8_t* skip, float th, int chi2_gate,
@@ -1791,11 +1829,8 @@ int orbm_fuse_candidates_batch(orbx_extractor* h, int K, const OrbmFuseTarget* t
     static_assert(sizeof(ProjectParams) == sizeof(OrbmProjection), "OrbmProjection and ProjectParams describe the same record");
     for (int k = 0; k < K; k++) {
         const OrbmFuseTarget& t = targets[k];
-        if (!t.kf) return fail(ORBX_E_ARG, "target %d: null key frame", k);
-        if (t.kf->device != h->device) return fail(ORBX_E_ARG, "target %d: its key frame lives on another device than the handle", k);
-        if (t.kf->nlevels < 1) return fail(ORBX_E_ARG, "target %d: its key frame has no scale levels", k);
+        if (int rc = batch_target_check(h, k, t.kf, t.spec)) return rc;
         if (chi2_gate && !t.inv_level_sigma2) return fail(ORBX_E_ARG, "target %d: chi-square gate without mvInvLevelSigma2", k);
-        if (!(t.spec.max_x > t.spec.min_x) || !(t.spec.max_y > t.spec.min_y)) return fail(ORBX_E_ARG, "target %d: empty image bounds", k);
     }
     const int M = points->M;
     if (M == 0) return ORBX_OK;
@@ -1804,41 +1839,23 @@ int orbm_fuse_candidates_batch(orbx_extractor* h, int K, const OrbmFuseTarget* t
     rt::set_device(h->device);
     const size_t pairs = (size_t)K * (size_t)M;
     std::vector<FuseTargetRec> recs(K);
-    std::vector<GridBuildRec> build;
-    std::vector<KfGrid*> made;
-    KfGridUse use;
+    BatchGrids grids;
     std::unique_lock<std::mutex> lk(kf_grid_mutex());
     for (int k = 0; k < K; k++) {
         const OrbmFuseTarget& t = targets[k];
-        orbm_keyframe* kf = const_cast<orbm_keyframe*>(t.kf);        // (the grid cache is the one part of a resident key frame that a search adds to)
-        FuseTargetRec& R = recs[k]; memset(&R, 0, sizeof R);
-        memcpy(&R.P, &t.spec, sizeof R.P);
-        R.g.min_x = t.spec.min_x; R.g.min_y = t.spec.min_y;
-        R.g.gw_inv = (float)kGridColsHost / (t.spec.max_x - t.spec.min_x); R.g.gh_inv = (float)kGridRowsHost / (t.spec.max_y - t.spec.min_y);      // src/Frame.cc:190-191
-        if (chi2_gate) for (int l = 0; l < kf->nlevels; l++) R.g.inv_sigma2[l] = t.inv_level_sigma2[l];
-        R.kps = kf->dev.kps; R.desc = kf->dev.desc; R.ur = kf->dev.ur;
-        R.N = kf->N; R.nlevels = kf->nlevels; R.log_scale_factor = t.log_scale_factor;
-        for (int l = 0; l < kMaxLevels; l++) R.scale_factors[l] = kf->scale[l];
-        const float key[4] = {R.g.min_x, R.g.min_y, R.g.gw_inv, R.g.gh_inv};
-        bool fresh;
-        KfGrid* G = kf_grid_for(kf, key, &fresh);
-        if (!G) return fail(ORBX_E_DEVICE, "target %d: allocation of its grid failed", k);
-        G->users++; use.held.push_back(G);
-        R.cell_start = G->mem; R.cell_items = G->mem + kGridCellStride;
-        if (fresh) { GridBuildRec b; b.kps = kf->dev.kps; b.cell_of = G->mem + kGridCellStride + kf->N + 1; b.cell_start = G->mem; b.cell_items = G->mem + kGridCellStride; b.N = kf->N; b.g = R.g; build.push_back(b); made.push_back(G); }
+        // (the grid cache is the one part of a resident key frame that a search adds to)
+        if (!grids.target(const_cast<orbm_keyframe*>(t.kf), t.spec, t.log_scale_factor, chi2_gate ? t.inv_level_sigma2 : nullptr, recs[k]))
+            return fail(ORBX_E_DEVICE, "target %d: allocation of its grid failed", k);
     }
     // a grid made here is built on this handle's stream: other threads may find it in the list, so they are kept out until this call has waited for the stream
-    if (build.empty()) lk.unlock();
+    if (grids.build.empty()) lk.unlock();
     Packer pk(h);
-    const size_t pb = pk.add(build.data(), sizeof(GridBuildRec) * build.size()), pt = pk.add(recs.data(), sizeof(FuseTargetRec) * recs.size()),
+    const size_t pb = pk.add(grids.build.data(), sizeof(GridBuildRec) * grids.build.size()), pt = pk.add(recs.data(), sizeof(FuseTargetRec) * recs.size()),
                  ps = skip ? pk.add(skip, pairs) : 0;
     const size_t nout = best_dist ? 2 * pairs : pairs;
     if (h->d_si[SI_BEST].ensure(nout)) return fail(ORBX_E_DEVICE, "allocation failed (%d targets x %d points)", K, M);
     if (int e = pk.flush()) return fail(ORBX_E_DEVICE, "%s", upload_error(e));
-    if (!build.empty()) {
-        const dim3 gridb((unsigned)build.size(), 1, 1), blkb(kGridThreads, 1, 1);
-        ORBX_LAUNCH(k_grid_build_kfs, gridb, blkb, 0, h->s0, pk.dev<GridBuildRec>(pb));
-    }
+    grids.launch_builds(h, pk.dev<GridBuildRec>(pb));
     int* d_idx = h->d_si[SI_BEST].p; int* d_dist = best_dist ? d_idx + pairs : (int*)nullptr;
     const dim3 grid((M + 255) / 256, K, 1), blk(256, 1, 1);
     ORBX_LAUNCH(k_fuse_candidates, grid, blk, 0, h->s0, pk.dev<FuseTargetRec>(pt), M, points->pos, points->normal, points->min_d, points->max_d, points->desc,
@@ -1852,9 +1869,72 @@ int orbm_fuse_candidates_batch(orbx_extractor* h, int K, const OrbmFuseTarget* t
         res = (const int*)h->h_res.p;
     }
     if (e || rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "fuse candidate search failed: %s", rt::last_error());
-    for (KfGrid* g : made) g->built = true;                          // (still under the mutex: `made` is empty otherwise)
+    grids.built();
     memcpy(best_idx, res, sizeof(int) * pairs);
     if (best_dist) memcpy(best_dist, res + pairs, sizeof(int) * pairs);
+    return ORBX_OK;
+}
+
+// The Sim3 projection search of one resident point set from K resident key frames.  One upload (the records of the grids to build, the target table, the
+// `occupied` rows, the skip mask), at most three launches (k_grid_build_kfs, k_sim3_candidates, k_sim3_accept), one download of assigned | nmatches.
+int orbm_search_by_projection_sim3_batch(orbx_extractor* h, int K, const OrbmSim3Target* targets, const orbm_points* points, const uint8_t* skip, float th,
+                                         float ratio_hamming, int cap, int* assigned, int* nmatches) {
+    if (!h || !points || K < 0) return fail(ORBX_E_ARG, "null / negative number of targets");
+    if (points->device != h->device) return fail(ORBX_E_ARG, "the map points live on another device than the handle");
+    if (K == 0) return ORBX_OK;
+    if (!targets) return fail(ORBX_E_ARG, "null target table");
+    int n_max = 0;
+    for (int k = 0; k < K; k++) {
+        if (int rc = batch_target_check(h, k, targets[k].kf, targets[k].spec)) return rc;
+        n_max = std::max(n_max, targets[k].kf->N);
+    }
+    if (cap < n_max) return fail(ORBX_E_ARG, "cap %d is below the %d keypoints of the largest key frame", cap, n_max);
+    const int M = points->M;
+    if (M == 0) return ORBX_OK;
+    if (!assigned || !nmatches) return fail(ORBX_E_ARG, "null result array");
+    const size_t lim = (size_t)1 << 28, cap1 = (size_t)std::max(cap, 1);
+    if (K > 65535 || (size_t)K * (size_t)M > lim || (size_t)K * cap1 > lim)
+        return fail(ORBX_E_CAPACITY, "%d targets x %d points (cap %d): at most 65535 targets, 2^28 pairs and 2^28 result entries per call", K, M, cap);
+    rt::set_device(h->device);
+    const size_t pairs = (size_t)K * (size_t)M, nres = (size_t)K * cap1 + (size_t)K;
+    std::vector<Sim3TargetRec> recs(K);
+    std::vector<uint8_t> occ;
+    BatchGrids grids;
+    std::unique_lock<std::mutex> lk(kf_grid_mutex());
+    for (int k = 0; k < K; k++) {
+        const OrbmSim3Target& t = targets[k];
+        if (!grids.target(const_cast<orbm_keyframe*>(t.kf), t.spec, t.log_scale_factor, nullptr, recs[k].F))
+            return fail(ORBX_E_DEVICE, "target %d: allocation of its grid failed", k);
+        recs[k].occ_off = -1;
+        if (t.occupied && t.kf->N > 0) { recs[k].occ_off = (long long)occ.size(); occ.insert(occ.end(), t.occupied, t.occupied + t.kf->N); occ.resize(al16(occ.size()), 0); }
+    }
+    if (grids.build.empty()) lk.unlock();                            // (as in orbm_fuse_candidates_batch)
+    Packer pk(h);
+    const size_t pb = pk.add(grids.build.data(), sizeof(GridBuildRec) * grids.build.size()), pt = pk.add(recs.data(), sizeof(Sim3TargetRec) * recs.size()),
+                 po = pk.add(occ.data(), occ.size()), ps = skip ? pk.add(skip, pairs) : 0;
+    if (h->d_si[SI_BEST].ensure(pairs + nres)) return fail(ORBX_E_DEVICE, "allocation failed (%d targets x %d points, cap %d)", K, M, cap);
+    if (int e = pk.flush()) return fail(ORBX_E_DEVICE, "%s", upload_error(e));
+    grids.launch_builds(h, pk.dev<GridBuildRec>(pb));
+    int* d_choice = h->d_si[SI_BEST].p; int* d_assigned = d_choice + pairs; int* d_nm = d_assigned + (size_t)K * cap1;
+    const Sim3TargetRec* d_tab = pk.dev<Sim3TargetRec>(pt);
+    const float max_dist = (float)TH_LOW * ratio_hamming;            // `TH_LOW * ratioHamming` (:609 / :722): int * float
+    const dim3 grid((M + 255) / 256, K, 1), blk(256, 1, 1), grida(K, 1, 1), blka(64, 1, 1);
+    ORBX_LAUNCH(k_sim3_candidates, grid, blk, 0, h->s0, d_tab, M, points->pos, points->normal, points->min_d, points->max_d, points->desc, pk.dev<uint8_t>(po),
+                skip ? pk.dev<uint8_t>(ps) : (const uint8_t*)nullptr, th, max_dist, h->debug_stereo_flags, d_choice);
+    const size_t smem = al16(4 * (size_t)((n_max + 31) / 32)) + 16;
+    ORBX_LAUNCH(k_sim3_accept, grida, blka, smem, h->s0, d_tab, M, points->pos, points->normal, points->min_d, points->max_d, points->desc, pk.dev<uint8_t>(po), th,
+                max_dist, h->debug_stereo_flags, (int)cap1, (const int*)d_choice, d_assigned, d_nm);
+    const int* res = d_assigned;
+    int e = 0;
+    if (!rt::memory_is_host()) {
+        e = h->h_res.ensure(sizeof(int) * nres + 64);
+        if (!e) e = rt::copy_d2h(h->h_res.p, d_assigned, sizeof(int) * nres, h->s0);
+        res = (const int*)h->h_res.p;
+    }
+    if (e || rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "Sim3 projection search failed: %s", rt::last_error());
+    grids.built();
+    if (cap > 0) memcpy(assigned, res, sizeof(int) * (size_t)K * (size_t)cap);
+    memcpy(nmatches, res + (size_t)K * cap1, sizeof(int) * (size_t)K);
     return ORBX_OK;
 }
 

@@ -137,6 +137,12 @@ __global__ void k_grid_build_kfs(const GridBuildRec* __restrict__ recs);
 __global__ void k_fuse_candidates(const FuseTargetRec* __restrict__ T, int M, const float* __restrict__ pos, const float* __restrict__ normal, const float* __restrict__ min_d,
                                   const float* __restrict__ max_d, const unsigned long long* __restrict__ qdesc, const uint8_t* __restrict__ skip, float th, int chi2_gate,
                                   int th_low, int debug_flags, int* __restrict__ best_idx, int* __restrict__ best_dist);
+__global__ void k_sim3_candidates(const Sim3TargetRec* __restrict__ T, int M, const float* __restrict__ pos, const float* __restrict__ normal, const float* __restrict__ min_d,
+                                  const float* __restrict__ max_d, const unsigned long long* __restrict__ qdesc, const uint8_t* __restrict__ occupied,
+                                  const uint8_t* __restrict__ skip, float th, float max_dist, int debug_flags, int* __restrict__ choice);
+__global__ void k_sim3_accept(const Sim3TargetRec* __restrict__ T, int M, const float* __restrict__ pos, const float* __restrict__ normal, const float* __restrict__ min_d,
+                              const float* __restrict__ max_d, const unsigned long long* __restrict__ qdesc, const uint8_t* __restrict__ occupied, float th, float max_dist,
+                              int debug_flags, int cap, const int* __restrict__ choice, int* __restrict__ assigned, int* __restrict__ nmatches);
 constexpr int kAreaWaves = 16;         // queries (waves) per k_area_search workgroup
 __global__ void k_area_search(const AreaQuery* __restrict__ queries, const unsigned long long* __restrict__ qdesc, int Q,
                               const KeyPointRec* __restrict__ kps, const float* __restrict__ u_right,

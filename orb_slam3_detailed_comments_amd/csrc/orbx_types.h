@@ -120,7 +120,10 @@ struct FuseTargetRec {
     ProjectParams P; GridParams g;
     int N, nlevels; float log_scale_factor; float scale_factors[kMaxLevels];
 };
-struct RigRelPose { float q[4], t[3]; };                          // mTrl of a two-camera Frame: unit quaternion coeffs (x, y, z, w), translation
+// one target of orbm_search_by_projection_sim3_batch (k_sim3_candidates, k_sim3_accept): the Fuse record with no chi-square gate, and where the target's
+// row of `vpMatched[idx] != NULL on entry` bytes starts in the uploaded occupancy block (-1: nothing is occupied)
+struct Sim3TargetRec { FuseTargetRec F; long long occ_off; };
+struct RigRelPose { float q[4], t[3]; };                         // mTrl of a two-camera Frame: unit quaternion coeffs (x, y, z, w), translation
 struct VocSlot { int node_id, child_start, child_cnt, word_id; };   // one vocabulary node; children occupy consecutive slots
 // Key frame database (orbv_db_*): where the BowVectors of queries sit - query q's sorted word ids / values at ids + start[q] (start == nullptr:
 // q * stride), its word count at n[q * n_step] (a host CSR, or the results of the vocabulary transform left on the device)

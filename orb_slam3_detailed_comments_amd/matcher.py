@@ -7,7 +7,7 @@ import numpy as np
 
 from ._lib import OrbxError
 from .sophus import SE3f, Sim3f, as_se3
-from .views import FuseTarget, Projection as _Projection
+from .views import FuseTarget, Sim3Target, Projection as _Projection
 
 
 class ORBmatcher:
@@ -224,6 +224,29 @@ class ORBmatcher:
                                                            bi.ctypes.data, bd.ctypes.data))
         return bi, bd
 
+    @staticmethod
+    def SearchByProjectionSim3Batch(ext, kfs, specs, points, th, ratio_hamming=1.0, occupied=None, skip=None):
+        """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, [vpPointsKFs,] vpMatched, [vpMatchedKF,] th, ratioHamming) for one resident point set searched
+        from K resident key frames in one call (orbm_search_by_projection_sim3_batch).  kfs[k] = ResidentKeyFrame of target k, specs[k] = sim3_spec(...) of its
+        Sim3, points = ResidentPoints; occupied = None or K arrays (or None) of kfs[k].N uint8, vpMatched[idx] != NULL on entry; skip = [K, M] uint8, pairs the
+        caller excludes (isBad, spAlreadyFound).  Returns (assigned [K, cap], nmatches [K]), cap = the largest N: assigned[k, idx] = the point written to
+        vpMatched[idx] of target k, -1 untouched and beyond kfs[k].N."""
+        K, Mp = len(kfs), points.M
+        assert len(specs) == K and (occupied is None or len(occupied) == K)
+        cap = max([kf.N for kf in kfs] + [0])
+        T = (Sim3Target * max(K, 1))()
+        occ = [None if occupied is None or o is None else np.ascontiguousarray(o, np.uint8) for o in (occupied if occupied is not None else [None] * K)]
+        for k in range(K):
+            assert occ[k] is None or occ[k].shape == (kfs[k].N,)
+            T[k].kf = kfs[k]._kf; T[k].spec = specs[k][0]; T[k].log_scale_factor = specs[k][1]
+            T[k].occupied = None if occ[k] is None else occ[k].ctypes.data
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        assert sk is None or sk.shape == (K, Mp)
+        assigned = np.full((K, cap), -1, np.int32); nm = np.zeros(max(K, 1), np.int32)
+        ext._lib.check(ext._lib.L.orbm_search_by_projection_sim3_batch(ext._h, K, T, points._p, None if sk is None else sk.ctypes.data, float(th), float(ratio_hamming),
+                                                                     cap, assigned.ctypes.data, nm.ctypes.data))
+        return assigned, nm[:K]
+
     def SearchBySim3(self, ext, kf1, kf2, p1in2, p2in1, th):
         """ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, S12, th), src/ORBmatcher.cc:1689.  Returns (nFound, matches12[N1])."""
         m12 = np.full(kf1.view.N, -1, np.int32); nf = C.c_int()
@@ -421,6 +444,15 @@ def fuse_spec(pose, cam, bounds, bf, log_scale_factor, Ow=None):
     T = as_se3(pose)
     Ow = T.inverse().translation() if Ow is None else Ow
     return projection_spec(T, cam, bounds, Ow, depth_test=1, bounds_mode=1, distance_test=True, angle_test=True, bf=bf), float(log_scale_factor)
+
+
+def sim3_spec(pose, cam, bounds, log_scale_factor, Ow=None, inline_pinhole=False):
+    """What ORBmatcher::SearchByProjection(pKF, Scw, ...) projects with, as SearchByProjectionSim3Batch takes it: (OrbmProjection, mfLogScaleFactor).  pose = the
+    rigid part [R | t / s] of Scw, Ow = its inverse's translation (the default), bounds = (mnMinX, mnMaxX, mnMinY, mnMaxY), KeyFrame::IsInImage, depth,
+    distance-range and viewing-angle tests on, bf = 0; inline_pinhole: the overload that also returns the points' key frames (src/ORBmatcher.cc:656-660)."""
+    T = as_se3(pose)
+    Ow = T.inverse().translation() if Ow is None else Ow
+    return projection_spec(T, cam, bounds, Ow, depth_test=1, bounds_mode=1, inline_pinhole=inline_pinhole, distance_test=True, angle_test=True, bf=0.0), float(log_scale_factor)
 
 
 def ProjectPoints(ext, pose, cam, bounds, pos, normal=None, min_inv=None, max_inv=None, skip=None, Ow=None, second=None, depth_test=1, bounds_mode=0, inline_pinhole=False,

@@ -1,5 +1,5 @@
 """ctypes mirrors of the read-only structure-of-arrays views in include/orbx.h (OrbmFrameView, OrbmMapPointView,
-OrbmLastFrameView, OrbmKeyFrameView, OrbmProjectedPointView, OrbmProjection, OrbmFuseTarget) and helpers that build them from numpy arrays."""
+OrbmLastFrameView, OrbmKeyFrameView, OrbmProjectedPointView, OrbmProjection, OrbmFuseTarget, OrbmSim3Target) and helpers that build them from numpy arrays."""
 import ctypes as C
 
 import numpy as np
@@ -53,6 +53,11 @@ class Projection(C.Structure):
 class FuseTarget(C.Structure):
     """OrbmFuseTarget: one key frame (one camera) of orbm_fuse_candidates_batch"""
     _fields_ = [("kf", _vp), ("spec", Projection), ("log_scale_factor", _f), ("inv_level_sigma2", _vp)]
+
+
+class Sim3Target(C.Structure):
+    """OrbmSim3Target: one (key frame, Sim3) of orbm_search_by_projection_sim3_batch"""
+    _fields_ = [("kf", _vp), ("spec", Projection), ("log_scale_factor", _f), ("occupied", _vp)]
 
 
 def _arr(a, dtype):
