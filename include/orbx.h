@@ -236,6 +236,13 @@ int orbx_debug_quadtree_pool_levels(orbx_extractor* h);                   /* num
  * packed sub, packed xor(a, c), wave inclusive scan / wave sum of a & 0xFFFF, wave minimum of b (per 64 consecutive elements), v_sad_u8, v_mul_u32_u24,
  * the 64-bit wave scan (two words), the 64-bit workgroup scan (two words), the wave OR, v_mul_hi_u32_u24, v_add3_u32 */
 int orbx_debug_simd_selftest(orbx_extractor* h, const uint32_t* a, const uint32_t* b, const uint32_t* c, int n, uint32_t* out);
+/* test hook: the device build of the bit-exact function models (csrc/glibc_*_model.h, cv::fastAtan2 in csrc/k_describe.hip) evaluated on n inputs,
+ * 1 <= n <= 1 << 26, one thread per element (tests/test_model_sweep.py walks whole float domains with it).  With a == NULL input i is the float whose
+ * bit pattern is start_bits + i (ops 0 .. 4 only); otherwise input i is a[i], with b[i] as the second operand of ops 5 .. 7.  Host buffers.
+ *  op 0 cosf, 1 sinf, 2 logf, 3 tanf, 4 atanf, 5 atan2f(a, b), 6 fastAtan2(a, b) in degrees: out = n results;
+ *  op 7 the steering of a keypoint with the patch moments m01 = a, m10 = b, by the function the descriptor kernel calls:
+ *       out = 3 n floats, out[i] = angle, out[n + i] = cosf(angle * pi / 180), out[2 n + i] = sinf(..). */
+int orbx_debug_model_eval(orbx_extractor* h, int op, uint32_t start_bits, const float* a, const float* b, int n, float* out);
 /* test hook: the workgroup primitives of the quadtree kernel (csrc/k_quadtree.hip) run by ONE workgroup of `threads` threads (256 or 1024, the two
  * sizes a tree runs on) on the caller's data, with their arrays laid out as a tree lays them out.  Host buffers.
  *  ORBX_QT_SELFTEST_SORT: in = n 64-bit keys, out = the n keys after the kernel's model of libstdc++'s std::sort with the comparator

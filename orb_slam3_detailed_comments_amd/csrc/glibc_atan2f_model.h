@@ -5,7 +5,10 @@
 // psi = atan2f(y, x).  atan2f is not correctly rounded, and the device's atan2f differs from glibc's in the last bits for most arguments, which
 // moved projected pixel coordinates by a few ulp (found by the first GPU run of tests/test_local_points_rig.py).  Every operation below is an
 // IEEE single-precision add / multiply / divide (the build uses -ffp-contract=off), so host, emulator and GPU agree.
-// tools/check_atan2f_model.c: atanf for EVERY float, atan2f for 4e9 pairs (all sign / magnitude classes) against the live libm.
+// tools/check_atan2f_model.c: atanf for EVERY float, atan2f for 4e9 pairs (all sign / magnitude classes) against the live libm (a hand-run tool, on
+// the g++ host build).  The DEVICE build is checked by tests/test_model_sweep.py: atanf for all 2^32 bit patterns and atan2f for 2^28 pairs
+// (special values, y = x * 2^k across both exponent cut-offs, x == 1, subnormal quotients, Kannala-Brandt-shaped and random pairs) on the GPU
+// against the live libm; thinned on the emulator build in the CPU suite.
 #pragma once
 #ifndef ORBX_HD
 #define ORBX_HD

@@ -7,7 +7,9 @@
 // log differs from it in about 5 of 1e8 ratios: one wrong mnTrackScaleLevel every few thousand frames of 5000 local points).
 // The model uses IEEE double multiply / add only; `fma` selects the contraction pattern of glibc's FMA build (the x86-64 ifunc variant
 // __logf_fma, which is what runs on every FMA-capable CPU) - tools/check_logf_model.c compares both patterns with the live libm for EVERY
-// positive finite float and reports which one the machine uses; the result is recorded in DESIGN.md.
+// positive finite float and reports which one the machine uses; the result is recorded in DESIGN.md.  That tool is run by hand on the g++ host
+// build; the DEVICE build of glibc_logf_model<false> is checked by tests/test_model_sweep.py: every positive finite float, subnormals included, on
+// the GPU against the live logf, a thinned sweep on the emulator build in the CPU suite.
 #pragma once
 #ifndef ORBX_HD
 #define ORBX_HD

@@ -7,7 +7,9 @@
 // cosf/sinf.  Those are not correctly rounded, so a device libm would differ in the last bit for some
 // angles.  This model uses only IEEE double multiply/add (no FMA needed: verified identical with and
 // without contraction) and was checked EXHAUSTIVELY against the live glibc for all 1,087,373,312 floats
-// in [0, 6.5] (tools/check_sincosf_model.c: 0 mismatches); tests/test_models.py re-checks a sample.
+// in [0, 6.5] (tools/check_sincosf_model.c: 0 mismatches; a hand-run tool, on the g++ host build); tests/test_models.py re-checks a sample of
+// the host build.  The DEVICE build is checked by tests/test_model_sweep.py: every float in [-6.5, 6.5] on the GPU against the live cosf / sinf
+// (the arithmetic is sign-symmetric: the negative half agrees too), a thinned sweep on the emulator build in the CPU suite.
 #pragma once
 #ifndef ORBX_HD
 #define ORBX_HD

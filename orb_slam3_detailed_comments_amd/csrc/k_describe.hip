@@ -11,6 +11,9 @@
 #include "orbx_kernels.h"
 #include "undistort_model.h"
 #include "glibc_sincosf_model.h"
+#include "glibc_logf_model.h"
+#include "glibc_tanf_model.h"
+#include "glibc_atan2f_model.h"
 
 namespace orbx {
 
@@ -38,6 +41,16 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
     if (x < 0) a = __fsub_rn(180.f, a);
     if (y < 0) a = __fsub_rn(360.f, a);
     return a;
+}
+
+// The steering of a keypoint from its patch moments (IC_Angle :91-138, computeOrbDescriptor :155-157): the angle in degrees, and the cos / sin of
+// angle * factorPI that rotate the BRIEF pattern.  One definition for k_orient_brief and for k_model_selftest (op 7), which compares the
+// composition with cv::fastAtan2 and the live cosf / sinf.
+__device__ __forceinline__ void steer_from_moments(float m01, float m10, float* angle, float* a, float* b) {
+    const float ang = fast_atan2_deg(m01, m10);
+    const float factorPI = (float)(3.1415926535897932384626433832795 / 180.f);
+    const float rad = __fmul_rn(ang, factorPI);
+    *angle = ang; *a = glibc_cosf(rad); *b = glibc_sinf(rad);
 }
 
 // grid (B), 256 threads.  The level-ordered keypoint slots of an image (level l owns [kp_off, kp_off + kp_cap), the first lvl_count of them
@@ -236,10 +249,8 @@ __device__ __forceinline__ void orient_brief_impl(const LevelInfo* __restrict__ 
         if (lane == k) { my_m10 = m10; my_m01 = m01; }
     }
     // ---- 2: angle, cos, sin: one keypoint per lane ----
-    const float my_angle = fast_atan2_deg((float)my_m01, (float)my_m10);
-    const float factorPI = (float)(3.1415926535897932384626433832795 / 180.f);
-    const float my_rad = __fmul_rn(my_angle, factorPI);
-    const float my_a = glibc_cosf(my_rad), my_b = glibc_sinf(my_rad);
+    float my_angle, my_a, my_b;
+    steer_from_moments((float)my_m01, (float)my_m10, &my_angle, &my_a, &my_b);
     // ---- 3: steered BRIEF on the blurred level ----
     // this lane's 4 tests (8 pattern points), the same for every keypoint
     float px0[4], py0[4], px1[4], py1[4];
@@ -338,6 +349,36 @@ __global__ void __launch_bounds__(256) k_undistort(const KeyPointRec* __restrict
     undistort_point(U, k.x, k.y, &x, &y);
     k.x = x; k.y = y;
     kps_un[b * (size_t)cap + i] = k;
+}
+
+// Self-test of the bit-exact function models (orbx_debug_model_eval; tests/test_model_sweep.py compares every result with the live libm /
+// cv::fastAtan2's definition): one thread per element, out[i] = op(x, y) with x = a[i] - or, without a, the float whose bit pattern is
+// start_bits + i - and y = b[i].  ops: 0 glibc_cosf, 1 glibc_sinf, 2 glibc_logf_model<false>, 3 glibc_tanf_model, 4 glibc_atanf_model,
+// 5 glibc_atan2f_model(x, y), 6 fast_atan2_deg(x, y), 7 steer_from_moments(m01 = x, m10 = y): out[i] = angle, out[n + i] = cos, out[2 n + i] = sin
+// (kModelSelftestOps in all).  Compiled with the flags of every other kernel; this is an instantiation of its own of the inline functions, not the
+// copy inlined into k_orient_brief, k_frustum or the Kannala-Brandt kernels (without fast-math flags IEEE fixes the arithmetic of both).
+__global__ void __launch_bounds__(256) k_model_selftest(int op, uint32_t start_bits, const float* __restrict__ a, const float* __restrict__ b, int n,
+                                                        float* __restrict__ out) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= n) return;
+    const float x = a != nullptr ? a[i] : at_float(start_bits + (uint32_t)i);
+    const float y = b != nullptr ? b[i] : 0.0f;
+    float r = 0.0f;
+    switch (op) {
+        case 0: r = glibc_cosf(x); break;
+        case 1: r = glibc_sinf(x); break;
+        case 2: r = glibc_logf_model<false>(x); break;
+        case 3: r = glibc_tanf_model(x); break;
+        case 4: r = glibc_atanf_model(x); break;
+        case 5: r = glibc_atan2f_model(x, y); break;
+        case 6: r = fast_atan2_deg(x, y); break;
+        default: {
+            float ca, sa;
+            steer_from_moments(x, y, &r, &ca, &sa);
+            out[(size_t)n + i] = ca; out[2 * (size_t)n + i] = sa;
+        }
+    }
+    out[i] = r;
 }
 
 }  // namespace orbx

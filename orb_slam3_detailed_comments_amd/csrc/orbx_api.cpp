@@ -942,6 +942,27 @@ int orbx_debug_simd_selftest(orbx_extractor* h, const uint32_t* a, const uint32_
     return ORBX_OK;
 }
 
+// debug: a bit-exact function model (k_model_selftest, ops 0 .. 7) evaluated on n inputs - consecutive bit patterns from start_bits (a == NULL) or the
+// caller's operands; out: n results (3 n for op 7: angle, cos, sin)
+int orbx_debug_model_eval(orbx_extractor* h, int op, uint32_t start_bits, const float* a, const float* b, int n, float* out) {
+    if (!h || !out || n <= 0 || n > kModelSelftestMax || op < 0 || op >= kModelSelftestOps) return fail(ORBX_E_ARG, "bad arguments (op 0 .. %d, 1 .. %d elements)", kModelSelftestOps - 1, kModelSelftestMax);
+    if (op >= 5 && (!a || !b)) return fail(ORBX_E_ARG, "op %d takes two operand arrays", op);
+    rt::set_device(h->device);
+    orbx::DevBuf<float> d;
+    const size_t N = (size_t)n, nout = op == 7 ? 3 * N : N, off_a = nout, off_b = nout + (a ? N : 0);
+    if (d.ensure(off_b + (b ? N : 0))) return fail(ORBX_E_DEVICE, "allocation failed");
+    int e = 0;
+    if (a) e |= rt::copy_h2d(d.p + off_a, a, 4 * N, h->s0);
+    if (b) e |= rt::copy_h2d(d.p + off_b, b, 4 * N, h->s0);
+    dim3 grid((n + 255) / 256, 1, 1), blk(256, 1, 1);
+    ORBX_LAUNCH(k_model_selftest, grid, blk, 0, h->s0, op, start_bits, a ? (const float*)(d.p + off_a) : (const float*)nullptr,
+                b ? (const float*)(d.p + off_b) : (const float*)nullptr, n, d.p);
+    e |= rt::copy_d2h(out, d.p, 4 * nout, h->s0);
+    if (e || rt::stream_sync(h->s0) || rt::check_launch()) { d.release(); return fail(ORBX_E_DEVICE, "model self-test failed: %s", rt::last_error()); }
+    d.release();
+    return ORBX_OK;
+}
+
 // debug: one workgroup of `threads` threads runs a workgroup primitive of the quadtree (k_quadtree_selftest) on the caller's data
 int orbx_debug_quadtree_selftest(orbx_extractor* h, int op, int spill, int threads, const void* in, int n, int start, int total, int mx, int my, void* out) {
     if (!h || !in || !out || (threads != 256 && threads != 1024) || (spill != 0 && spill != 1)) return fail(ORBX_E_ARG, "bad arguments (256 or 1024 threads, spill 0 or 1)");

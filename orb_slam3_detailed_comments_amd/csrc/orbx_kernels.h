@@ -52,6 +52,8 @@ constexpr int kResizeRows = 8;         // output rows per k_resize tile (256 col
 constexpr int kBlurRows = ORBX_BLUR_ROWS, kBlurRowsLarge = ORBX_BLUR_ROWS_LARGE;
 constexpr int kSimdSelftestOps = 22;
 __global__ void k_simd_selftest(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, const uint32_t* __restrict__ c, int n, uint32_t* __restrict__ out);
+constexpr int kModelSelftestOps = 8, kModelSelftestMax = 1 << 26;      // orbx_debug_model_eval (k_describe.hip): ops 0 .. 7, elements per call
+__global__ void k_model_selftest(int op, uint32_t start_bits, const float* __restrict__ a, const float* __restrict__ b, int n, float* __restrict__ out);
 __global__ void k_blur(const LevelInfo* __restrict__ lv, int nlevels, const uint8_t* __restrict__ pyr,
                        uint8_t* __restrict__ blur, size_t pyr_stride, BlurTaps taps, BlurTiles tiles);
 __global__ void k_blur_large(const LevelInfo* __restrict__ lv, int nlevels, const uint8_t* __restrict__ pyr,

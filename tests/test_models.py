@@ -1,6 +1,9 @@
-"""Host checks of the two bit-exact models the device code relies on:
-  csrc/libstdcxx_sort_model.h   == libstdc++ std::sort (tie permutation of the quadtree's final rounds)
-  csrc/glibc_sincosf_model.h    == glibc cosf/sinf on [0, 2*pi] (BRIEF steering)"""
+"""Checks of three of the bit-exact models the device code relies on:
+  csrc/libstdcxx_sort_model.h   == libstdc++ std::sort (tie permutation of the quadtree's final rounds), host build
+  csrc/glibc_sincosf_model.h    == glibc cosf/sinf on [0, 2*pi] (BRIEF steering), a sample on the host build
+  csrc/glibc_logf_model.h       == glibc logf through k_frustum's PredictScale (emulator and GPU), and the reference's choice of logf
+The device builds of the libm models (cosf, sinf, logf, tanf, atanf, atan2f) and of cv::fastAtan2 are swept over their whole domains by
+tests/test_model_sweep.py."""
 import ctypes as C
 import os
 import subprocess
