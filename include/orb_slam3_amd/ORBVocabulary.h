@@ -19,7 +19,10 @@ namespace ORB_SLAM3 {
 
 class ORBVocabularyAmd {
 public:
-    // `h` supplies the GPU stream and scratch memory (any extractor handle of the device the vocabulary should live on)
+    // `h` supplies the GPU stream and scratch memory (any extractor handle of the device the vocabulary should live on) and must not be used for anything
+    // else while transforms run.  transform() may then be called from any number of threads at once, as Frame::ComputeBoW (Tracking) and
+    // KeyFrame::ComputeBoW (LocalMapping) call the reference's: each call holds the device vocabulary's lock from its upload to its results
+    // (tests/cpp/shared_objects_threads_test.cpp).  loadFromTextFile and the destructor are not to run beside a transform.
     explicit ORBVocabularyAmd(orbx_extractor* h) : h_(h), v_(nullptr) {}
     ~ORBVocabularyAmd() { if (v_) orbv_destroy(v_); }
     ORBVocabularyAmd(const ORBVocabularyAmd&) = delete;

@@ -881,7 +881,18 @@ int orbm_distinctive_descriptors(orbx_extractor* h, const uint8_t* desc, const i
 
 /* ---- Vocabulary: the consumer right behind the extractor, Frame::ComputeBoW (src/Frame.cc:984-997) ->
  * ORBVocabulary::transform(features, mBowVec, mFeatVec, 4) (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1195).  Produces the
- * FeatureVector CSR that OrbmKeyFrameView (SearchByBoW / SearchForTriangulation) consumes. ---- */
+ * FeatureVector CSR that OrbmKeyFrameView (SearchByBoW / SearchForTriangulation) consumes.
+ *   Threads: one vocabulary serves every handle of its device, from any thread (Frame::ComputeBoW on Tracking's thread and KeyFrame::ComputeBoW on
+ * LocalMapping's share one ORBVocabulary).  It has ONE scratch and ONE set of results; every orbv_* call that touches them, and the two
+ * orbm_search_by_bow_*_batch, hold the vocabulary's lock from start to end.  So:
+ *   - the blocking orbv_transform is safe from any number of threads at once, each with a handle of its own;
+ *   - the split protocol (orbv_transform_extracted / orbv_transform_rig_extracted, later orbv_fetch, orbv_db_add_extracted, orbv_db_query_extracted or
+ *     a search batch) has one client at a time: the results belong to the handle (L of a rig run) and extraction that made them until the NEXT run of any
+ *     kind on the vocabulary, through any handle.  After that the calls that read them return ORBX_E_ARG ("... were overwritten ...") - never another
+ *     run's vectors; transform again.  orbv_fetch right behind a blocking orbv_transform through the same handle keeps working;
+ *   - a run through another handle than the previous split-protocol run waits, on the device, until that run has finished (and on the host when it has to
+ *     grow the scratch); a run through the same handle is ordered by its stream alone.
+ * orbv_destroy must not run beside another call on the same vocabulary. ---- */
 typedef struct orbv_vocabulary orbv_vocabulary;
 
 /* Vocabulary from flat arrays in ORBvoc.txt line order (loadFromTextFile, TemplatedVocabulary.h:1338-1430): entry i describes node

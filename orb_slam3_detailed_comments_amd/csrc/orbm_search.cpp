@@ -1374,6 +1374,7 @@ int orbm_search_by_bow_frames_batch(orbx_extractor* h, const orbv_vocabulary* v,
                                     float nnratio, int check_ori, int* const* matches12, int* nmatches_out) {
     if (!h || !v || B <= 0 || !KFs || !has_mp1 || !matches12) return fail(ORBX_E_ARG, "null");
     VocFrameArrays V;
+    const std::unique_lock<std::mutex> vlk = orbv_lock(v);       // until the matches are down: no other handle's run replaces the FeatureVectors under the kernels
     if (orbv_frame_arrays(v, &V) == 0 && V.rig)
         return fail(ORBX_E_ARG, "the last vocabulary transform was a rig transform (orbv_transform_rig_extracted): search its frames with orbm_search_by_bow_rig_batch");
     if (orbv_frame_arrays(v, &V) || V.handle != (const void*)h || V.first != first || V.lastB != B || V.cap != h->kp_total_cap || first < 0 || first + B > h->lastB)
@@ -1437,6 +1438,7 @@ int orbm_search_by_bow_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, i
                                  int* nmatches_out) {
     if (!L || !R || !v || B <= 0 || P <= 0 || !frame || !KFs || !has_map_point || !assigned) return fail(ORBX_E_ARG, "null");
     VocFrameArrays V;
+    const std::unique_lock<std::mutex> vlk = orbv_lock(v);       // as in orbm_search_by_bow_frames_batch
     if (orbv_frame_arrays(v, &V) || !V.rig)
         return fail(ORBX_E_ARG, "no rig transform: run orbv_transform_rig_extracted(v, L, %d, R, %d, %d, levelsup) first - the rig frames' rows and FeatureVectors are read where it leaves them",
                     lf, rf, B);
@@ -1760,8 +1762,18 @@ namespace {
 const int kKfGridsKept = 2;             // grids a key frame keeps between calls (a key frame is normally searched with one set of bounds)
 // the grids one call reads: found or made under the mutex, released when the call ends - whichever way
 struct KfGridUse {
-    std::vector<KfGrid*> held;
-    ~KfGridUse() { if (held.empty()) return; std::lock_guard<std::mutex> lk(kf_grid_mutex()); for (KfGrid* g : held) g->users--; }
+    std::vector<KfGrid*> held; std::vector<orbm_keyframe*> of;
+    ~KfGridUse() {
+        if (held.empty()) return;
+        std::lock_guard<std::mutex> lk(kf_grid_mutex());
+        for (KfGrid* g : held) g->users--;
+        // kf_grid_for drops nothing that another call is reading, so beside other threads a list grows past kKfGridsKept: back to that, oldest first
+        for (orbm_keyframe* kf : of)
+            for (size_t i = 0; i < kf->grids.size() && (int)kf->grids.size() > kKfGridsKept;) {
+                KfGrid* g = kf->grids[i];
+                if (g->users == 0) { rt::dfree(g->mem); delete g; kf->grids.erase(kf->grids.begin() + i); } else i++;
+            }
+    }
 };
 // (caller holds the mutex) the grid of kf for `key`; *fresh = it has just been allocated and is still to be built
 KfGrid* kf_grid_for(orbm_keyframe* kf, const float key[4], bool* fresh) {
@@ -1806,7 +1818,7 @@ struct BatchGrids {
         bool fresh;
         KfGrid* G = kf_grid_for(kf, key, &fresh);
         if (!G) return false;
-        G->users++; use.held.push_back(G);
+        G->users++; use.held.push_back(G); use.of.push_back(kf);
         R.cell_start = G->mem; R.cell_items = G->mem + kGridCellStride;
         if (fresh) { GridBuildRec b; b.kps = kf->dev.kps; b.cell_of = G->mem + kGridCellStride + kf->N + 1; b.cell_start = G->mem; b.cell_items = G->mem + kGridCellStride; b.N = kf->N; b.g = R.g; build.push_back(b); made.push_back(G); }
         return true;

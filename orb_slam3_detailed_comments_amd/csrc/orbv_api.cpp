@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <deque>
+#include <mutex>
 #include <unordered_map>
 #include "orbx_internal.h"
 
@@ -27,6 +28,14 @@ struct orbv_vocabulary {
     DevBuf<unsigned> d_word, d_node, d_bow_id, d_fv_node, d_fv_feat;
     DevBuf<double> d_wt, d_bow_val;
     DevBuf<int> d_bow_start, d_fv_start, d_nout, d_nfeat;
+    // One vocabulary serves the handles - and threads - of its device (Frame::ComputeBoW on Tracking's, KeyFrame::ComputeBoW on LocalMapping's), but it has
+    // one scratch and one set of results.  mu: every entry point that touches either holds it for the whole call.  owner: the handle whose run made the
+    // results (nullptr: nobody's; orbv_fetch, orbv_db_add_extracted and orbv_db_query_extracted serve no other).  pending: the handle on whose stream a
+    // split-protocol run may still be executing (compared, never dereferenced), ev_pending: recorded behind that run's last kernel by the thread that
+    // enqueued it - another thread never touches the handle's stream, which may be capturing a graph just then.  A run through another handle makes its
+    // own stream wait for the event; a blocking transform ends waited for and records nothing.  orbx_destroy clears both names (orbv_forget_handle).
+    mutable std::mutex mu;
+    const void* owner = nullptr; const void* pending = nullptr; rt::event_t ev_pending = 0;
 };
 
 namespace {
@@ -34,6 +43,23 @@ namespace {
 int norm_of(int scoring) {      // ScoringObject.h:74-89: (mustNormalize, norm) of each scoring class
     switch (scoring) { case 0: return 1; case 1: return 2; case 2: case 3: case 4: return 1; default: return 0; }
 }
+
+std::mutex& registry_mutex() { static std::mutex m; return m; }
+std::vector<orbv_vocabulary*>& registry() { static std::vector<orbv_vocabulary*> r; return r; }
+
+const char* kOverwritten = "the results of this handle's vocabulary transform were overwritten by a later run on the vocabulary: transform again";
+
+// (caller holds v->mu) before a run through h touches the scratch: what another handle's split-protocol run left on its stream comes first.  The scratch may
+// also be freed and reallocated by this run (reserve, d_fdesc.ensure): the host waits when it is about to grow.  The same handle again: stream order, no wait.
+int order_behind_pending(orbv_vocabulary* v, orbx_extractor* h, bool grows) {
+    if (!v->pending || v->pending == (const void*)h) return 0;
+    int e = rt::stream_wait_event(h->s0, v->ev_pending);
+    if (grows) e |= rt::event_sync(v->ev_pending);
+    v->pending = nullptr;
+    return e;
+}
+// fdesc: the rows the run stages in d_fdesc itself (0: it reads an extractor's)
+bool scratch_grows(const orbv_vocabulary* v, int cap, int B, size_t fdesc) { return cap > v->cap || B > v->maxB || (fdesc > 0 && (fdesc > v->d_fdesc.n || !v->d_fdesc.p)); }
 
 int reserve(orbv_vocabulary* v, int cap, int B) {
     if (cap <= v->cap && B <= v->maxB) return 0;
@@ -61,6 +87,7 @@ int check_capacity(const orbx_extractor* h, int cap, int* P) {
 int run(orbv_vocabulary* v, orbx_extractor* h, const unsigned long long* fdesc, const int* n_feat, int n_fixed, int cap, int B, int levelsup) {
     int P = 0;
     if (int rc = check_capacity(h, cap, &P)) return rc;
+    v->lastB = 0; v->owner = nullptr;                       // the earlier results are gone from here on, whoever made them
     if (reserve(v, cap, B)) return fail(ORBX_E_DEVICE, "vocabulary scratch allocation failed");
     const long groups = (long)cap * B;
     dim3 g1((unsigned)((groups * 16 + 255) / 256), 1, 1), blk(256, 1, 1);
@@ -71,7 +98,7 @@ int run(orbv_vocabulary* v, orbx_extractor* h, const unsigned long long* fdesc, 
                 n_feat, n_fixed, cap, P, v->weighting, norm_of(v->scoring), v->d_bow_id.p, v->d_bow_val.p, v->d_bow_start.p, v->d_fv_node.p,
                 v->d_fv_start.p, v->d_fv_feat.p, v->d_nout.p);
     if (rt::check_launch()) return fail(ORBX_E_DEVICE, "vocabulary kernels failed to launch: %s", rt::last_error());
-    v->lastB = B; v->run_cap = cap; v->run_first = -1; v->run_handle = nullptr;
+    v->lastB = B; v->run_cap = cap; v->run_first = -1; v->run_handle = nullptr; v->owner = h;
     v->run_rig = false; v->run_first_r = -1; v->run_handle_r = nullptr;
     return ORBX_OK;
 }
@@ -79,6 +106,15 @@ int run(orbv_vocabulary* v, orbx_extractor* h, const unsigned long long* fdesc, 
 }  // namespace
 
 namespace orbx {
+std::unique_lock<std::mutex> orbv_lock(const orbv_vocabulary* v) { return std::unique_lock<std::mutex>(v->mu); }
+void orbv_forget_handle(const orbx_extractor* h) {
+    std::lock_guard<std::mutex> rk(registry_mutex());
+    for (orbv_vocabulary* v : registry()) {
+        std::lock_guard<std::mutex> lk(v->mu);
+        if (v->pending == (const void*)h) v->pending = nullptr;         // orbx_destroy has waited for the handle's streams
+        if (v->owner == (const void*)h) v->owner = nullptr;
+    }
+}
 int orbv_frame_arrays(const orbv_vocabulary* v, VocFrameArrays* out) {
     if (!v || v->lastB <= 0) return -1;
     out->fv_node = (const uint32_t*)v->d_fv_node.p; out->fv_start = v->d_fv_start.p; out->fv_feat = (const int*)v->d_fv_feat.p; out->nout = v->d_nout.p;
@@ -132,10 +168,11 @@ int orbv_create(orbx_extractor* h, int k, int L, int scoring, int weighting, int
     orbv_vocabulary* v = new orbv_vocabulary();
     v->k = k; v->L = L; v->scoring = scoring; v->weighting = weighting; v->device = h->device;
     v->n_nodes = n_nodes; v->n_words = n_words; v->root_children = (int)children[0].size();
-    int e = v->d_desc.ensure(sdesc.size()) | v->d_slots.ensure(slots.size()) | v->d_weight.ensure(sw.size());
+    int e = v->d_desc.ensure(sdesc.size()) | v->d_slots.ensure(slots.size()) | v->d_weight.ensure(sw.size()) | rt::event_create(&v->ev_pending);
     if (!e) e = rt::copy_h2d(v->d_desc.p, sdesc.data(), sdesc.size() * 8, h->s0) | rt::copy_h2d(v->d_slots.p, slots.data(), slots.size() * sizeof(VocSlot), h->s0) |
                 rt::copy_h2d(v->d_weight.p, sw.data(), sw.size() * 8, h->s0) | rt::stream_sync(h->s0);
     if (e) { orbv_destroy(v); return fail(ORBX_E_DEVICE, "vocabulary upload failed"); }
+    { std::lock_guard<std::mutex> rk(registry_mutex()); registry().push_back(v); }
     *out = v;
     return ORBX_OK;
 }
@@ -172,7 +209,9 @@ int orbv_load_text(orbx_extractor* h, const char* path, orbv_vocabulary** out) {
 
 void orbv_destroy(orbv_vocabulary* v) {
     if (!v) return;
+    { std::lock_guard<std::mutex> rk(registry_mutex()); auto& r = registry(); r.erase(std::remove(r.begin(), r.end(), v), r.end()); }
     rt::set_device(v->device);
+    rt::event_destroy(v->ev_pending);
     v->d_desc.release(); v->d_slots.release(); v->d_weight.release(); v->d_fdesc.release(); v->d_word.release(); v->d_node.release();
     v->d_bow_id.release(); v->d_fv_node.release(); v->d_fv_feat.release(); v->d_wt.release(); v->d_bow_val.release(); v->d_bow_start.release();
     v->d_fv_start.release(); v->d_nout.release(); v->d_nfeat.release();
@@ -187,8 +226,10 @@ int orbv_transform_extracted(orbv_vocabulary* v, orbx_extractor* h, int first, i
     if (first < 0 || B <= 0 || first + B > h->lastB) return fail(ORBX_E_ARG, "images [%d, %d) are not in the last batch of %d", first, first + B, h->lastB);
     rt::set_device(h->device);
     const int cap = h->kp_total_cap;
+    std::lock_guard<std::mutex> lk(v->mu);
+    if (order_behind_pending(v, h, scratch_grows(v, cap, B, 0))) return fail(ORBX_E_DEVICE, "waiting for the vocabulary's previous run failed: %s", rt::last_error());
     const int rc = run(v, h, (const unsigned long long*)(h->d_desc.p + (size_t)first * cap * 4), (const int*)(h->d_nm.p + first), 0, cap, B, levelsup);
-    if (rc == ORBX_OK) { v->run_first = first; v->run_handle = h; v->run_extract_gen = h->extract_gen; }
+    if (rc == ORBX_OK) { v->run_first = first; v->run_handle = h; v->run_extract_gen = h->extract_gen; rt::event_record(v->ev_pending, h->s0); v->pending = h; }
     return rc;
 }
 
@@ -205,8 +246,10 @@ int orbv_transform_rig_extracted(orbv_vocabulary* v, orbx_extractor* L, int lf, 
     rt::set_device(L->device);
     const int cap = L->kp_total_cap, cap2 = 2 * cap;
     int P = 0;
+    std::lock_guard<std::mutex> lk(v->mu);
     if (int rc = check_capacity(L, cap2, &P)) return rc;                 // refused before the gather overwrites the rows of an earlier rig run
-    v->lastB = 0; v->run_rig = false; v->run_handle = nullptr; v->run_handle_r = nullptr;
+    if (order_behind_pending(v, L, scratch_grows(v, cap2, B, (size_t)B * cap2 * 4))) return fail(ORBX_E_DEVICE, "waiting for the vocabulary's previous run failed: %s", rt::last_error());
+    v->lastB = 0; v->run_rig = false; v->run_handle = nullptr; v->run_handle_r = nullptr; v->owner = nullptr;
     if (v->d_fdesc.ensure((size_t)B * cap2 * 4) || reserve(v, cap2, B)) return fail(ORBX_E_DEVICE, "vocabulary scratch allocation failed");
     if (L != R) { record_done_if_pending(R); rt::stream_wait_event(L->s0, R->ev_done); }          // R's extraction runs on R's stream
     dim3 grid((unsigned)((cap2 + 255) / 256), (unsigned)B, 1), blk(256, 1, 1);
@@ -216,13 +259,18 @@ int orbv_transform_rig_extracted(orbv_vocabulary* v, orbx_extractor* L, int lf, 
     if (rc == ORBX_OK) {
         v->run_first = lf; v->run_handle = L; v->run_extract_gen = L->extract_gen;
         v->run_rig = true; v->run_first_r = rf; v->run_handle_r = R; v->run_extract_gen_r = R->extract_gen;
+        rt::event_record(v->ev_pending, L->s0); v->pending = L;
     }
     return rc;
 }
 
-int orbv_fetch(orbv_vocabulary* v, orbx_extractor* h, int b, uint32_t* word_id, uint32_t* node_id, int n_features, uint32_t* bow_id, double* bow_val,
-               int* n_bow, uint32_t* fv_node, int* fv_start, uint32_t* fv_feat, int* n_fv) {
-    if (!v || !h) return fail(ORBX_E_ARG, "null");
+}  // extern "C"
+
+namespace {
+// (caller holds v->mu) orbv_fetch; h's stream has been waited for when it returns
+int fetch_locked(orbv_vocabulary* v, orbx_extractor* h, int b, uint32_t* word_id, uint32_t* node_id, int n_features, uint32_t* bow_id, double* bow_val,
+                 int* n_bow, uint32_t* fv_node, int* fv_start, uint32_t* fv_feat, int* n_fv) {
+    if (v->lastB > 0 && v->owner != (const void*)h) return fail(ORBX_E_ARG, "%s", kOverwritten);
     if (b < 0 || b >= v->lastB) return fail(ORBX_E_ARG, "image %d is not in the last transformed batch of %d", b, v->lastB);
     rt::set_device(h->device);
     int nout[2] = {0, 0};
@@ -246,7 +294,18 @@ int orbv_fetch(orbv_vocabulary* v, orbx_extractor* h, int b, uint32_t* word_id, 
     if (e) return fail(ORBX_E_DEVICE, "vocabulary fetch failed: %s", rt::last_error());
     if (n_bow) *n_bow = nout[0];
     if (n_fv) *n_fv = nout[1];
+    if (v->pending == (const void*)h) v->pending = nullptr;
     return ORBX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int orbv_fetch(orbv_vocabulary* v, orbx_extractor* h, int b, uint32_t* word_id, uint32_t* node_id, int n_features, uint32_t* bow_id, double* bow_val,
+               int* n_bow, uint32_t* fv_node, int* fv_start, uint32_t* fv_feat, int* n_fv) {
+    if (!v || !h) return fail(ORBX_E_ARG, "null");
+    std::lock_guard<std::mutex> lk(v->mu);
+    return fetch_locked(v, h, b, word_id, node_id, n_features, bow_id, bow_val, n_bow, fv_node, fv_start, fv_feat, n_fv);
 }
 
 int orbv_transform(orbv_vocabulary* v, orbx_extractor* h, const uint8_t* desc, int n, int levelsup, uint32_t* word_id, uint32_t* node_id,
@@ -256,10 +315,12 @@ int orbv_transform(orbv_vocabulary* v, orbx_extractor* h, const uint8_t* desc, i
     if (n > 16384) return fail(ORBX_E_CAPACITY, "more than 16384 features");
     rt::set_device(h->device);
     const int cap = std::max(n, 1);
+    std::lock_guard<std::mutex> lk(v->mu);        // upload, kernels and fetch are one client's: any number of threads may call this on one vocabulary
+    if (order_behind_pending(v, h, scratch_grows(v, cap, 1, (size_t)cap * 4))) return fail(ORBX_E_DEVICE, "waiting for the vocabulary's previous run failed: %s", rt::last_error());
     if (v->d_fdesc.ensure((size_t)cap * 4)) return fail(ORBX_E_DEVICE, "allocation failed");
     if (n > 0 && rt::copy_h2d(v->d_fdesc.p, desc, 32 * (size_t)n, h->s0)) return fail(ORBX_E_DEVICE, "upload failed");
     int rc = run(v, h, v->d_fdesc.p, nullptr, n, cap, 1, levelsup); if (rc) return rc;
-    return orbv_fetch(v, h, 0, word_id, node_id, n, bow_id, bow_val, n_bow, fv_node, fv_start, fv_feat, n_fv);
+    return fetch_locked(v, h, 0, word_id, node_id, n, bow_id, bow_val, n_bow, fv_node, fv_start, fv_feat, n_fv);
 }
 
 }  // extern "C"
@@ -480,8 +541,9 @@ int orbv_db_add_extracted(orbv_database* db, uint64_t key, orbx_extractor* h, in
     if (!db || !h) return fail(ORBX_E_ARG, "null");
     orbv_vocabulary* v = db->voc;
     if (h->device != db->device) return fail(ORBX_E_ARG, "extractor and database live on different devices");
+    std::lock_guard<std::mutex> lk(v->mu);
+    if (v->lastB > 0 && v->owner != (const void*)h) return fail(ORBX_E_ARG, "%s", kOverwritten);
     if (b < 0 || b >= v->lastB) return fail(ORBX_E_ARG, "image %d is not in the last transformed batch of %d", b, v->lastB);
-    if (v->run_handle && v->run_handle != (const void*)h) return fail(ORBX_E_ARG, "the last vocabulary transform ran on another extractor handle");
     rt::set_device(db->device);
     int n = 0;
     if (rt::copy_d2h(&n, v->d_nout.p + 2 * b, sizeof n, h->s0) || rt::stream_sync(h->s0)) return fail(ORBX_E_DEVICE, "fetch failed: %s", rt::last_error());
@@ -490,6 +552,7 @@ int orbv_db_add_extracted(orbv_database* db, uint64_t key, orbx_extractor* h, in
     if (n > 0 && (rt::copy_d2h(id.data(), v->d_bow_id.p + off, 4 * (size_t)n, h->s0) || rt::copy_d2h(val.data(), v->d_bow_val.p + off, 8 * (size_t)n, h->s0) ||
                   rt::stream_sync(h->s0)))
         return fail(ORBX_E_DEVICE, "fetch failed: %s", rt::last_error());
+    if (v->pending == (const void*)h) v->pending = nullptr;
     return db_add_host(db, key, id.data(), val.data(), n);
 }
 
@@ -553,12 +616,14 @@ int orbv_db_query_extracted(orbv_database* db, orbx_extractor* h, int first, int
     if (!db || !h || Q <= 0 || cap < 0 || (x_start && !x_keys && x_start[Q] > 0)) return fail(ORBX_E_ARG, "null");
     orbv_vocabulary* v = db->voc;
     if (h->device != db->device) return fail(ORBX_E_ARG, "extractor and database live on different devices");
+    std::lock_guard<std::mutex> lk(v->mu);         // held until db_run has read the BowVectors where the transform left them
+    if (v->lastB > 0 && v->owner != (const void*)h) return fail(ORBX_E_ARG, "%s", kOverwritten);
     if (first < 0 || first + Q > v->lastB) return fail(ORBX_E_ARG, "images [%d, %d) are not in the last transformed batch of %d", first, first + Q, v->lastB);
-    if (v->run_handle && v->run_handle != (const void*)h) return fail(ORBX_E_ARG, "the last vocabulary transform ran on another extractor handle");
     if (x_start) for (int q = 0; q < Q; q++) if (x_start[q + 1] < x_start[q] || x_start[0] != 0) return fail(ORBX_E_ARG, "x_start must run from 0 and not descend");
     rt::set_device(db->device);
     if (db_sync(db)) return ORBX_E_DEVICE;
     if (rt::stream_sync(h->s0)) return fail(ORBX_E_DEVICE, "vocabulary transform failed: %s", rt::last_error());   // the BowVectors are written on h's stream
+    if (v->pending == (const void*)h) v->pending = nullptr;
     const int cap_v = v->run_cap;
     KfdbQuerySet qs = {v->d_bow_id.p + (size_t)first * cap_v, v->d_bow_val.p + (size_t)first * cap_v, nullptr, cap_v, v->d_nout.p + 2 * first, 2};
     return db_run(db, Q, qs, cap_v, x_start, x_keys, score_all, cap, keys, words, scored, score, n_out, min_common);

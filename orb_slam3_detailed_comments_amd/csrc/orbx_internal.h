@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 #include "../../include/orbx.h"
@@ -53,7 +54,12 @@ struct VocFrameArrays {
 };
 }  // namespace orbx
 struct orbv_vocabulary;
-namespace orbx { int orbv_frame_arrays(const orbv_vocabulary* v, VocFrameArrays* out); }
+struct orbx_extractor;
+namespace orbx {
+int orbv_frame_arrays(const orbv_vocabulary* v, VocFrameArrays* out);      // under orbv_lock(v), held for as long as the arrays are read
+std::unique_lock<std::mutex> orbv_lock(const orbv_vocabulary* v);          // the vocabulary's mutex: its scratch and results are one client's at a time
+void orbv_forget_handle(const orbx_extractor* h);                          // orbx_destroy: no vocabulary names the handle any more
+}
 
 struct orbx_extractor {
     // ---- reference constructor state (src/ORBextractor.cc:468-571) ----

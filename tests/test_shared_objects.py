@@ -1,0 +1,309 @@
+"""Device objects that ORB-SLAM3's threads share: one ORBVocabulary (Frame::ComputeBoW on Tracking's thread, KeyFrame::ComputeBoW on LocalMapping's),
+resident key frames that several threads search.  Everywhere else in the suite each thread has objects of its own.
+
+a. three threads, three handles, one vocabulary: every blocking transform equals the reference's DBoW2 byte for byte (tests/shared_objects_runner.py,
+   in a child process: without the vocabulary's lock the process dies in the allocator); a variant grows the scratch under contention.
+b. two handles on one thread, the interleavings of the split protocol (orbv_transform_extracted ... orbv_fetch): a run through another handle is ordered
+   behind the previous handle's, and results that another run has replaced are refused (ORBX_E_ARG), never handed out as somebody else's vectors.
+c. the C++ facade: one ORBVocabularyAmd, three std::threads (tests/cpp/shared_objects_threads_test.cpp).
+d. resident key frames and one point set searched by three threads through their own handles.
+e. one orbm_map: a writer thread and two reader threads, each with its own handle.
+(f, the KeyFrameDatabase facade used by three threads, is the last section of tests/cpp/kfdb_facade_test.cpp, run by tests/test_kfdb_facade.py.)
+
+Expectations: oracle/_ref/libref_dbow2.so (the reference's own DBoW2) for vectors and scores, oracle_lib's restatements for match rows."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import kfdb_world as kw
+import oracle_lib as ol
+import vocab_scenes as vs
+from orb_slam3_detailed_comments_amd import _lib, synth, views
+from orb_slam3_detailed_comments_amd import matcher as M
+from orb_slam3_detailed_comments_amd._lib import OrbxError, KP_DTYPE
+from orb_slam3_detailed_comments_amd.extractor import ORBextractor
+from orb_slam3_detailed_comments_amd.vocabulary import ORBVocabulary, KeyFrameDatabase
+
+ROOT = ol.ROOT
+E_ARG = -2
+DBOW2 = os.path.join(ROOT, "oracle", "_ref", "libref_dbow2.so")
+needs_dbow2 = pytest.mark.skipif(not os.path.exists(DBOW2), reason="oracle/_ref/libref_dbow2.so not built (needs the reference's DBoW2)")
+EMU_CALLS = 30          # per thread: without the lock the child aborted in 6 of 6 runs at this count
+GPU_CALLS = 10
+
+
+def run_child(lib_path, tmp_path, scenario, calls):
+    """the threaded part, in a process of its own: an abort there is a failed test here"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "shared_objects_runner.py"), lib_path, ROOT, str(tmp_path), scenario, str(calls)],
+                       capture_output=True, text=True, timeout=600)
+    lines = r.stdout.strip().splitlines()
+    print(r.stdout[-2000:])
+    assert r.returncode == 0 and lines and lines[-1].startswith("DONE"), "%s: exit status %d\n%s\n%s" % (scenario, r.returncode, r.stdout[-1500:], r.stderr[-1500:])
+    done = lines[-1].split()
+    assert int(done[3]) == 0 and int(done[1]) >= 3 * calls, lines[-1]
+
+
+# ---- a. one vocabulary, three threads ----
+@needs_dbow2
+@pytest.mark.parametrize("scenario", ["vocabulary", "vocabulary_grow"])
+def test_vocabulary_shared_by_threads_emulated(emu_lib, tmp_path, scenario):
+    run_child(ol.emu_lib_path(), tmp_path, scenario, EMU_CALLS)
+
+
+@needs_dbow2
+@pytest.mark.gpu
+@pytest.mark.parametrize("scenario", ["vocabulary", "vocabulary_grow"])
+def test_vocabulary_shared_by_threads_gpu(hip_lib, tmp_path, scenario):
+    run_child(_lib.HIP_LIB_PATH, tmp_path, scenario, GPU_CALLS)
+
+
+# ---- b. two handles, one thread ----
+def _same(r, exp, what):
+    bi, bv, fn, fs, ff = exp
+    assert np.array_equal(r.bow_id, bi) and r.bow_val.tobytes() == bv.tobytes(), "BowVector, " + what
+    assert np.array_equal(r.fv_node, fn) and np.array_equal(r.fv_start, fs) and np.array_equal(r.fv_feat, ff), "FeatureVector, " + what
+
+
+def _refused(call, what):
+    with pytest.raises(OrbxError) as err:
+        call()
+    assert err.value.code == E_ARG and "overwritten" in str(err.value), "%s: %s" % (what, err.value)
+
+
+class TwoHandles:
+    """handles A and B (300 features, 320 x 240), one vocabulary made through A, the reference's DBoW2 on the same file, a key frame database holding the
+    reference's vectors of six descriptor sets"""
+    LEVELSUP = 2
+
+    def __init__(self, lib, tmp_path):
+        self.A = ORBextractor(300, 1.2, 8, 20, 7, lib=lib); self.B = ORBextractor(300, 1.2, 8, 20, 7, lib=lib)
+        rng = np.random.default_rng(17)
+        header, parent, leaf, desc, weight = vs.make_vocabulary(rng, 8, 3)
+        path = tmp_path / "voc_two_handles.txt"
+        vs.write_text(path, header, parent, leaf, desc, weight)
+        self.ref = ol.RefVocabulary(path); self.score = kw.ref_scorer(path)
+        self.voc = ORBVocabulary.from_arrays(self.A, *header, parent, leaf, desc, weight)
+        self.voc_B = ORBVocabulary(self.B, self.voc._v)                    # the same orbv_vocabulary, its blocking transform through B
+        self.voc_B.close = lambda: None                                    # (self.voc destroys it)
+        self.imgs_A = np.stack([synth.corner_field(320, 240, seed=s, nrect=700) for s in (1, 2)])
+        self.imgs_B = np.stack([synth.corner_field(320, 240, seed=s, nrect=700) for s in (3, 4)])
+        self.res_B = self.B.extract_batch(self.imgs_B)
+        self.q_B = self.res_B[0][2]                                        # the rows B transforms: a frame's descriptors, on the host
+        self.exp_B = self.ref.transform(self.q_B, self.LEVELSUP)
+        assert len(self.q_B) > 200
+        self.db = KeyFrameDatabase(self.voc, self.A); self.restated = kw.RestatedDB(self.voc.size()); self.bow_of = {}
+        for i in range(6):
+            b = self.ref.transform(vs.descriptors_near(rng, desc, 250), self.LEVELSUP)[:2]
+            self.add(1000 + i, b)
+        self.next_key = 2000
+
+    def add(self, key, bow):
+        self.db.add(key, *bow); self.restated.add(key, *bow); self.bow_of[key] = bow
+
+    def enqueue_and_transform_A(self, rig):
+        """A's extraction and its transform, enqueued without a wait"""
+        self.A.enqueue(self.imgs_A)
+        if rig:
+            self.voc.transform_rig_extracted(self.A, 0, self.A, 1, 1, self.LEVELSUP)      # camera 1 = image 0, camera 2 = image 1: one rig frame
+        else:
+            self.voc.transform_extracted(self.A, 0, 2, self.LEVELSUP)
+
+    def transform_A_again(self, rig):
+        if rig:
+            self.voc.transform_rig_extracted(self.A, 0, self.A, 1, 1, self.LEVELSUP)
+        else:
+            self.voc.transform_extracted(self.A, 0, 2, self.LEVELSUP)
+
+    def frames_A(self, res_A, rig):
+        """the rows of every frame the transform of A covers"""
+        return [np.concatenate([res_A[0][2], res_A[1][2]])] if rig else [res_A[0][2], res_A[1][2]]
+
+    def check_A_results(self, res_A, rig):
+        """orbv_fetch, orbv_db_add_extracted and orbv_db_query_extracted through A give the reference's vectors of A's frames"""
+        frames = self.frames_A(res_A, rig)
+        exps = [self.ref.transform(d, self.LEVELSUP) for d in frames]
+        for b, d in enumerate(frames):
+            assert len(exps[b][0]) > 20
+            _same(self.voc.fetch(self.A, b, len(d)), exps[b], "A's frame %d" % b)
+        got = self.db.query_extracted(self.A, 0, len(frames), score_all=False)
+        for b in range(len(frames)):
+            qb = exps[b][:2]
+            assert len(got[b]["keys"]) > 0
+            kw.check_query(got[b], self.restated.query(qb[0]), self.bow_of, qb, self.score, "query_extracted, A's frame %d" % b)
+        keys = []
+        for b in range(len(frames)):                                       # the records read in place must be the reference's vectors: a host query sees them as such
+            self.db.add_extracted(self.next_key, self.A, b); self.restated.add(self.next_key, *exps[b][:2]); self.bow_of[self.next_key] = exps[b][:2]
+            keys.append(self.next_key); self.next_key += 1
+        for b in range(len(frames)):
+            qb = exps[b][:2]
+            r = self.db.query([qb], score_all=False)[0]
+            assert keys[b] in r["keys"].tolist()
+            kw.check_query(r, self.restated.query(qb[0]), self.bow_of, qb, self.score, "after add_extracted, A's frame %d" % b)
+
+    def close(self):
+        self.db.close(); self.voc.close(); self.A.close(); self.B.close()
+
+
+def check_interleavings(lib, tmp_path):
+    W = TwoHandles(lib, tmp_path)
+    for rig in (False, True):                                              # (i), (ii)
+        W.enqueue_and_transform_A(rig)
+        r_B = W.voc_B.transform(W.q_B, W.LEVELSUP)                         # B's kernels write the scratch A's are still using unless they are ordered behind them
+        res_A = W.A.fetch()
+        _same(r_B, W.exp_B, "B's blocking transform behind A's enqueued one (rig %d)" % rig)
+        _refused(lambda: W.voc.fetch(W.A, 0, len(res_A[0][2])), "orbv_fetch through A after B's run")
+        _refused(lambda: W.db.add_extracted(77, W.A, 0), "orbv_db_add_extracted through A after B's run")
+        _refused(lambda: W.db.query_extracted(W.A, 0, 1), "orbv_db_query_extracted through A after B's run")
+        assert W.db.size() == len(W.bow_of)
+        W.transform_A_again(rig)
+        W.check_A_results(res_A, rig)
+    # (iv) what one handle could do before, it still can: a blocking transform, then its fetch; a split transform fetched twice
+    r = W.voc.transform(W.q_B, W.LEVELSUP)
+    _same(r, W.exp_B, "blocking transform through A")
+    _same(W.voc.fetch(W.A, 0, len(W.q_B)), W.exp_B, "orbv_fetch behind a blocking transform of the same handle")
+    res_A = W.A.extract_batch(W.imgs_A)
+    W.voc.transform_extracted(W.A, 0, 2, W.LEVELSUP)
+    for _ in range(2):
+        for b in range(2):
+            _same(W.voc.fetch(W.A, b, len(res_A[b][2])), W.ref.transform(res_A[b][2], W.LEVELSUP), "second fetch of frame %d" % b)
+    W.close()
+
+
+def _kp(k):
+    out = np.zeros(len(k), KP_DTYPE)
+    for f in ("x", "y", "size", "angle", "response", "octave", "class_id"):
+        out[f] = k[f]
+    return out
+
+
+def check_search_after_other_handles_run(lib, tmp_path):
+    """(iii) A transform_extracted, B transform_extracted, then orbm_search_by_bow_frames_batch through both: A's FeatureVectors are gone and it is refused,
+    B's rows equal the oracle's SearchByBoW(pKF, F) on the reference DBoW2's FeatureVectors"""
+    W = TwoHandles(lib, tmp_path)
+    rng = np.random.default_rng(23)
+    sfs = W.B.GetScaleFactors()
+    res_A = W.A.extract_batch(W.imgs_A)
+    kfs_A, kfs_B, mps, kviews = [], [], [], []
+    for b in range(2):                                                     # key frame b: frame b of B seen again with descriptor noise and a turned image
+        k, d = W.res_B[b][1], W.res_B[b][2]
+        src = rng.choice(len(k), int(0.8 * len(k)), replace=False)
+        kk = _kp(k[src]); kk["angle"] = np.mod(kk["angle"] + 25.0 + rng.normal(0, 3.0, len(src)), 360.0).astype(np.float32)
+        dk = d[src].copy()
+        for i in range(len(src)):
+            for bit in rng.choice(256, int(rng.integers(0, 50)), replace=False):
+                dk[i, bit >> 3] ^= np.uint8(1 << (bit & 7))
+        fv = W.ref.transform(dk, W.LEVELSUP)
+        has_mp = (rng.uniform(size=len(src)) < 0.85).astype(np.uint8)
+        kv = views.key_frame_view(kk, dk, sfs, sfs * sfs, fv[2], fv[3], fv[4], None, has_mp)
+        kviews.append(kv); mps.append(has_mp)
+        kfs_A.append(M.ResidentKeyFrame(W.A, kv)); kfs_B.append(M.ResidentKeyFrame(W.B, kv))
+    W.voc.transform_extracted(W.A, 0, 2, W.LEVELSUP)
+    W.voc.transform_extracted(W.B, 0, 2, W.LEVELSUP)
+    m = M.ORBmatcher(0.7, True)
+    with pytest.raises(OrbxError) as err:
+        m.SearchByBoWFramesBatch(W.A, W.voc, kfs_A, mps)
+    assert err.value.code == E_ARG
+    got = m.SearchByBoWFramesBatch(W.B, W.voc, kfs_B, mps)
+    total = 0
+    for b in range(2):
+        k, d = W.res_B[b][1], W.res_B[b][2]
+        fv = W.ref.transform(d, W.LEVELSUP)
+        fview = views.key_frame_view(_kp(k), d, sfs, sfs * sfs, fv[2], fv[3], fv[4], None, None)
+        n, m12 = ol.oracle_search_by_bow(kviews[b], fview, 0.7, True, True)
+        assert got[b][0] == n and np.array_equal(got[b][1], m12), "frame %d of B: %d matches, the oracle has %d" % (b, got[b][0], n)
+        total += n
+    assert total > 60
+    assert len(res_A[0][1]) > 100
+    for kf in kfs_A + kfs_B:
+        kf.close()
+    W.close()
+
+
+@needs_dbow2
+def test_vocabulary_two_handles_interleaved_emulated(emu_lib, tmp_path):
+    check_interleavings(emu_lib, tmp_path)
+
+
+@needs_dbow2
+@pytest.mark.gpu
+def test_vocabulary_two_handles_interleaved_gpu(hip_lib, tmp_path):
+    check_interleavings(hip_lib, tmp_path)
+
+
+@needs_dbow2
+def test_bow_search_after_another_handles_transform_emulated(emu_lib, tmp_path):
+    check_search_after_other_handles_run(emu_lib, tmp_path)
+
+
+@needs_dbow2
+@pytest.mark.gpu
+def test_bow_search_after_another_handles_transform_gpu(hip_lib, tmp_path):
+    check_search_after_other_handles_run(hip_lib, tmp_path)
+
+
+# ---- c. the C++ facade: one ORBVocabularyAmd, three std::threads ----
+# what ORBVocabulary.h needs of DBoW2 (Thirdparty/DBoW2 is part of ORB-SLAM3's tree, not of this one): the two result types, stated here for the test binary
+DBOW2_TYPES = {
+    "BowVector.h": "#pragma once\n#include <map>\nnamespace DBoW2 { typedef unsigned int WordId; typedef double WordValue; typedef unsigned int NodeId;\n"
+                   "class BowVector : public std::map<WordId, WordValue> {}; }\n",
+    "FeatureVector.h": '#pragma once\n#include <map>\n#include <vector>\n#include "BowVector.h"\n'
+                       "namespace DBoW2 { class FeatureVector : public std::map<NodeId, std::vector<unsigned int> > {}; }\n",
+}
+
+
+def run_facade_threads(tmp_path, libdir, libname, calls):
+    inc = tmp_path / "dbow2_types" / "DBoW2"
+    inc.mkdir(parents=True)
+    for name, text in DBOW2_TYPES.items():
+        (inc / name).write_text(text)
+    ref = os.path.join(ROOT, "oracle", "_ref")
+    exe = tmp_path / "shared_objects_threads_test"
+    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + os.path.join(ROOT, "include", "orb_slam3_amd"), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
+                    "-I" + str(inc.parent), os.path.join(ROOT, "tests", "cpp", "shared_objects_threads_test.cpp"), "-L" + libdir, "-l" + libname, DBOW2,
+                    "-Wl,-rpath," + libdir, "-Wl,-rpath," + ref, "-lpthread", "-o", str(exe)], check=True)
+    rng = np.random.default_rng(6)
+    header, parent, leaf, desc, weight = vs.make_vocabulary(rng, 6, 5)    # levelsup 4 of 5 levels: the FeatureVector's nodes are the root's children
+    path = tmp_path / "voc_facade.txt"
+    vs.write_text(path, header, parent, leaf, desc, weight)
+    r = subprocess.run([str(exe), str(path), str(calls)], capture_output=True, text=True, timeout=600)
+    print(r.stdout[-2000:])
+    assert r.returncode == 0 and "calls=%d failures=0" % (3 * calls) in r.stdout, "exit status %d\n%s\n%s" % (r.returncode, r.stdout[-1500:], r.stderr[-1500:])
+
+
+@needs_dbow2
+def test_vocabulary_facade_shared_by_threads_emulated(emu_lib, tmp_path):
+    run_facade_threads(tmp_path, *ol.emu_link(), EMU_CALLS)
+
+
+@needs_dbow2
+@pytest.mark.gpu
+def test_vocabulary_facade_shared_by_threads_gpu(hip_lib, tmp_path):
+    run_facade_threads(tmp_path, os.path.dirname(_lib.HIP_LIB_PATH), "orbx_hip", GPU_CALLS)
+
+
+# ---- d. resident key frames and one point set, three threads ----
+def test_resident_keyframes_shared_by_threads_emulated(emu_lib, tmp_path):
+    run_child(ol.emu_lib_path(), tmp_path, "keyframes", 12)         # every thread meets every bounds variant four times in each of the two batch calls
+
+
+@pytest.mark.gpu
+def test_resident_keyframes_shared_by_threads_gpu(hip_lib, tmp_path):
+    run_child(_lib.HIP_LIB_PATH, tmp_path, "keyframes", 12)
+
+
+# ---- e. one map: a writer and two readers ----
+needs_reference_frame = pytest.mark.skipif(ol.reference_frame_lib() is None, reason="oracle/_ref/libref_frame.so is not built")
+
+
+@needs_reference_frame
+def test_map_with_a_writer_and_two_readers_emulated(emu_lib, tmp_path):
+    run_child(ol.emu_lib_path(), tmp_path, "map", 6)
+
+
+@needs_reference_frame
+@pytest.mark.gpu
+def test_map_with_a_writer_and_two_readers_gpu(hip_lib, tmp_path):
+    run_child(_lib.HIP_LIB_PATH, tmp_path, "map", 6)
