@@ -651,6 +651,12 @@ __device__ __forceinline__ void quadtree_tree(unsigned char* smem, unsigned char
     // instruction per thread, and the search is ~50 of them per key - profiles/r04/quadtree_gather_key_parallel_variant.patch.txt.)
     int lgt = 0;
     while (lgt < 6 && (L.cell_count << (lgt + 1)) <= NT) lgt++;
+    // Four waves per tree (large batches, several trees on a CU): at least four lanes per cell, also where the level then takes trips of 64 cells.
+    // With one lane per cell every load and store of a wave touches 64 cache lines (a cell's slots are 1.4 KB apart, its keys ~180 B), and the
+    // trees of a CU share one L1: at 128 images the gather of a level-0 tree fell from 40 to 27 us and the stage from 0.120 to 0.105 ms
+    // (profiles/quadtree_gather).  Eight lanes per cell gain nothing more, sixteen lose it to the trips.  The wide form keeps its own choice
+    // (two lanes per cell at 752 x 480): alone on its CU it measures the same either way.
+    if (!wide && lgt < 2) lgt = 2;
     const int tpc = 1 << lgt, sub = tid & (tpc - 1), cpt = NT >> lgt;          // lanes per cell, lane within the cell, cells per trip
     const bool one_trip = L.cell_count <= cpt;
     // number of keys first: it decides the counter width and the segment length
