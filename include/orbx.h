@@ -879,6 +879,23 @@ int orbm_search_for_initialization(orbx_extractor* h, const OrbmFrameView* F1, c
  * ties); -1 for a point without descriptors. */
 int orbm_distinctive_descriptors(orbx_extractor* h, const uint8_t* desc, const int* start, int P, int* best);
 
+/* The same choice with the observations NAMED instead of copied: observation o is row obs_feat[o] of the descriptors of resident key frame
+ * kfs[obs_kf[o]] (for a rig key frame the view lists the left camera's features first, so the reference's rightIndex is used as it is).  Point p owns
+ * observations [obs_start[p], obs_start[p+1]), in the order the reference pushes them into vDescriptors (its std::map iteration, left index before
+ * right index, bad key frames left out by the caller).  best[p] as above (-1: no observations); best_desc row p = the chosen descriptor (untouched for
+ * -1; may be NULL).  With map and slots given and slots[p] >= 0 the chosen descriptor also overwrites the descriptor of that slot in the map's store,
+ * on the device; a point with best[p] == -1 leaves its slot as it is (the reference returns before assigning mDescriptor), no other field of any slot
+ * changes, and sets built earlier keep what they hold (as after orbm_map_update).  New points call with map = NULL or slot -1 and make their first
+ * orbm_map_update with the descriptor from best_desc.
+ *   Refused before anything is enqueued, the store untouched, the message naming the point or observation: ORBX_E_ARG for null / negative arguments,
+ * obs_start decreasing, obs_kf outside [0, nkf), a null key frame, obs_feat outside its key frame's features, a key frame or the map on another device
+ * than h, a slot outside the map or holding no point, two points writing one slot; ORBX_E_CAPACITY for more than 1024 observations of one point (nothing
+ * is truncated).  P == 0 is ORBX_OK.  Takes the map's mutex like every orbm_map_* call; blocking, on h's stream; staged through h's reused buffers. */
+int orbm_distinctive_descriptors_resident(orbx_extractor* h, int nkf, orbm_keyframe* const* kfs, int P, const int* obs_start /*[P+1]*/,
+                                          const int* obs_kf /*[total]*/, const int* obs_feat /*[total]*/, orbm_map* map /* may be NULL */,
+                                          const int* slots /*[P], may be NULL; -1 = do not write this point*/, int* best /*[P]*/,
+                                          uint8_t* best_desc /*[P][32], may be NULL*/);
+
 /* ---- Vocabulary: the consumer right behind the extractor, Frame::ComputeBoW (src/Frame.cc:984-997) ->
  * ORBVocabulary::transform(features, mBowVec, mFeatVec, 4) (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1127-1195).  Produces the
  * FeatureVector CSR that OrbmKeyFrameView (SearchByBoW / SearchForTriangulation) consumes.

@@ -30,7 +30,7 @@ SYMBOLS = [
     "orbm_hamming_matrix", "orbm_stereo_match", "orbm_stereo_fetch", "orbm_knn2", "orbm_knn2_fetch", "orbm_stereo_fisheye", "orbm_stereo_fisheye_fetch", "orbm_search_for_triangulation_kb8", "orbm_is_in_frustum", "orbm_is_in_frustum_rig", "orbm_search_local_points_fisheye", "orbm_search_local_points",
     "orbm_get_features_in_area", "orbm_search_by_projection_mappoints", "orbm_search_by_projection_frame",
     "orbm_search_for_triangulation", "orbm_search_by_bow", "orbm_search_by_bow_batch", "orbm_keyframe_create", "orbm_points_create", "orbm_points_destroy", "orbm_search_local_points_resident", "orbm_stereo_from_depth", "orbm_search_local_points_batch", "orbm_search_local_points_fetch", "orbm_search_by_projection_lastframe_batch", "orbm_search_by_projection_keyframe_batch", "orbm_keyframe_destroy", "orbm_search_for_triangulation_resident", "orbm_search_for_triangulation_resident_kb8", "orbm_search_by_bow_resident", "orbm_search_by_bow_fisheye", "orbm_search_for_initialization", "orbm_area_search_batch",
-    "orbm_project_points", "orbm_search_by_projection_sim3", "orbm_search_by_projection_keyframe", "orbm_fuse_candidates", "orbm_search_by_sim3", "orbm_distinctive_descriptors",
+    "orbm_project_points", "orbm_search_by_projection_sim3", "orbm_search_by_projection_keyframe", "orbm_fuse_candidates", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_distinctive_descriptors_resident",
     "orbm_search_by_projection_mappoints_fisheye", "orbm_search_by_projection_frame_fisheye", "orbm_search_for_triangulation_batch",
     "orbm_search_local_points_rig_batch", "orbm_search_by_projection_lastframe_rig_batch", "orbm_search_rig_batch_fetch",
     "orbm_search_local_points_batch_maps", "orbm_search_local_points_rig_batch_maps", "orbm_points_count", "orbm_fuse_candidates_batch", "orbm_search_by_projection_sim3_batch",
@@ -173,6 +173,7 @@ class OrbxLib:
         L.orbm_points_fetch.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         L.orbm_map_debug_epoch.argtypes = [vp, vp, i]
         L.orbm_distinctive_descriptors.argtypes = [vp, vp, vp, i, vp]
+        L.orbm_distinctive_descriptors_resident.argtypes = [vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
         L.orbv_create.argtypes = [vp, i, i, i, i, i, vp, vp, vp, vp, C.POINTER(vp)]
         L.orbv_load_text.argtypes = [vp, C.c_char_p, C.POINTER(vp)]
         L.orbv_destroy.argtypes = [vp]; L.orbv_destroy.restype = None

@@ -449,4 +449,97 @@ __global__ void __launch_bounds__(256) k_distinctive(const unsigned long long* _
     if (lane == 0) best[p] = bestIdx;
 }
 
+// The same choice for map points whose observations are rows of device-resident key frames (orbm_distinctive_descriptors_resident): observation o of
+// the call is row obs_feat[o] of key frame obs_kf[o], whose descriptors start at kf_desc[obs_kf[o]]; record r = first + (wave of the grid) owns entries
+// [start, start + n) and gets best[r] and best_desc[4 r ..]; with a store address the chosen descriptor also goes into the map's store.  Every
+// descriptor is read from global memory once.  The median of row i is the smallest v with #{j : d(i, j) <= v} > rank: the distances stay in
+// registers, a count is the popcount of a ballot (scalar), and v is found by bisection of [0, 256] - at most nine counts.  Row i only wins when its
+// median is below the best so far (strict `<`, :511), i.e. when #{d <= best - 1} > rank: one count settles every row that does not win.
+//   register form (kLds == false, n <= 64; grid ceil(count / 4) x 256 threads, no LDS): one wave per point, lane j holds column j in four 64-bit
+//     registers, row i comes out of lane i through readlane into scalar registers
+//   LDS form (kLds == true, n <= 1024; grid count x 64 threads, 32 * (largest n) bytes of dynamic LDS): one single-wave workgroup per point, the
+//     descriptors staged word-major (word k of column j at cols[k * n + j]: a lane's column reads are consecutive, row i is a broadcast), lane j
+//     covers columns j, j + 64, ..; a count sums the ballots of the chunks
+template <bool kLds>
+__device__ __forceinline__ void distinctive_point(const DistinctiveRec R, int r, const unsigned long long* const* __restrict__ kf_desc,
+                                                  const int* __restrict__ obs_kf, const int* __restrict__ obs_feat, int* __restrict__ best,
+                                                  unsigned long long* __restrict__ best_desc, unsigned long long* cols) {
+    constexpr int kChunks = kLds ? kDistinctiveMax / 64 : 1, kNever = 0x7fff;
+    const int lane = lane_id(), N = R.n, rank = (N - 1) >> 1;                   // (size_t)(0.5 * (N - 1))
+    unsigned long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+    if (kLds) {
+        for (int j = lane; j < N; j += 64) {
+            const unsigned long long* dj = kf_desc[obs_kf[R.start + j]] + 4 * (size_t)obs_feat[R.start + j];
+            cols[j] = dj[0]; cols[N + j] = dj[1]; cols[2 * N + j] = dj[2]; cols[3 * N + j] = dj[3];
+        }
+        __syncthreads();
+    } else if (lane < N) {
+        const unsigned long long* dj = kf_desc[obs_kf[R.start + lane]] + 4 * (size_t)obs_feat[R.start + lane];
+        c0 = dj[0]; c1 = dj[1]; c2 = dj[2]; c3 = dj[3];
+    }
+    int bestMedian = 257, bestIdx = 0;
+    for (int i = 0; i < N; i++) {
+        unsigned long long a0, a1, a2, a3;
+        int d[kChunks];
+        if (kLds) {
+            a0 = cols[i]; a1 = cols[N + i]; a2 = cols[2 * N + i]; a3 = cols[3 * N + i];
+#pragma unroll
+            for (int c = 0; c < kChunks; c++) {
+                if (c * 64 < N) {
+                    const int j = c * 64 + lane, jj = imin(j, N - 1);
+                    const int dist = __popcll(a0 ^ cols[jj]) + __popcll(a1 ^ cols[N + jj]) + __popcll(a2 ^ cols[2 * N + jj]) + __popcll(a3 ^ cols[3 * N + jj]);
+                    d[c] = dist + (j < N ? 0 : kNever);                    // (a lane without a column in this chunk never counts)
+                }
+            }
+        } else {
+            a0 = (unsigned long long)readlane_i64((long long)c0, i); a1 = (unsigned long long)readlane_i64((long long)c1, i);
+            a2 = (unsigned long long)readlane_i64((long long)c2, i); a3 = (unsigned long long)readlane_i64((long long)c3, i);
+            d[0] = __popcll(a0 ^ c0) + __popcll(a1 ^ c1) + __popcll(a2 ^ c2) + __popcll(a3 ^ c3) + (lane < N ? 0 : kNever);      // (a lane without a column never counts)
+        }
+        auto count_le = [&](int v) {                                            // #{j < N : d(i, j) <= v}, the same in every lane
+            int n = 0;
+#pragma unroll
+            for (int c = 0; c < kChunks; c++)
+                if (c * 64 < N) n += __popcll(ORBX_BALLOT(d[c] <= v));
+            return n;
+        };
+        if (count_le(bestMedian - 1) > rank) {                                  // median_i < bestMedian (the first row: every distance is <= 256)
+            int lo = 0, hi = bestMedian - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (count_le(mid) > rank) hi = mid; else lo = mid + 1;
+            }
+            bestMedian = lo; bestIdx = i;
+        }
+    }
+    if (kLds) {
+        if (lane < 4) {
+            const unsigned long long v = cols[lane * N + bestIdx];
+            best_desc[4 * (size_t)r + lane] = v;
+            if (R.store) R.store[lane] = v;
+        }
+    } else if (lane == bestIdx) {
+        unsigned long long* o = best_desc + 4 * (size_t)r;
+        o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
+        if (R.store) { R.store[0] = c0; R.store[1] = c1; R.store[2] = c2; R.store[3] = c3; }
+    }
+    if (lane == 0) best[r] = bestIdx;
+}
+
+// (two instantiations, so that the register form does not carry the registers of the LDS form's sixteen chunks: 15 against 116 VGPRs)
+template <bool kLds>
+__global__ void __launch_bounds__(256) k_distinctive_resident(const DistinctiveRec* __restrict__ recs, int first, int count,
+                                                              const unsigned long long* const* __restrict__ kf_desc, const int* __restrict__ obs_kf,
+                                                              const int* __restrict__ obs_feat, int* __restrict__ best, unsigned long long* __restrict__ best_desc) {
+    ORBX_DYN_SMEM(smem);
+    const int k = (int)blockIdx.x * (int)(blockDim.x >> 6) + ORBX_UNIFORM(wave_id());      // (wave-uniform: the record and the row loop stay scalar)
+    if (k >= count) return;
+    const int r = first + k;
+    distinctive_point<kLds>(recs[r], r, kf_desc, obs_kf, obs_feat, best, best_desc, kLds ? (unsigned long long*)smem : nullptr);
+}
+template __global__ void k_distinctive_resident<false>(const DistinctiveRec* __restrict__, int, int, const unsigned long long* const* __restrict__, const int* __restrict__,
+                                                       const int* __restrict__, int* __restrict__, unsigned long long* __restrict__);
+template __global__ void k_distinctive_resident<true>(const DistinctiveRec* __restrict__, int, int, const unsigned long long* const* __restrict__, const int* __restrict__,
+                                                      const int* __restrict__, int* __restrict__, unsigned long long* __restrict__);
+
 }  // namespace orbx

@@ -2696,4 +2696,99 @@ int orbm_points_fetch(orbx_extractor* h, const orbm_points* p, float* pos, float
     return ORBX_OK;
 }
 
+// MapPoint::ComputeDistinctiveDescriptors on observations that are rows of resident key frames, the winner written into the map's store.  One upload
+// (key-frame table | obs_kf | obs_feat | point records), one launch per form that has points (k_distinctive_resident: <= 64 observations in registers,
+// more through the LDS), one download of best | best_desc.  Everything is checked before anything is enqueued.
+int orbm_distinctive_descriptors_resident(orbx_extractor* h, int nkf, orbm_keyframe* const* kfs, int P, const int* obs_start, const int* obs_kf, const int* obs_feat,
+                                          orbm_map* map, const int* slots, int* best, uint8_t* best_desc) {
+    if (!h || nkf < 0 || P < 0) return fail(ORBX_E_ARG, "null handle / negative number of key frames or points");
+    if (map && map->device != h->device) return fail(ORBX_E_ARG, "the map lives on device %d, the handle on device %d", map->device, h->device);
+    if (P == 0) return ORBX_OK;
+    if (!obs_start || !best) return fail(ORBX_E_ARG, "null obs_start / best");
+    for (int p = 0; p < P; p++) {
+        if (obs_start[p] < 0 || obs_start[p + 1] < obs_start[p]) return fail(ORBX_E_ARG, "point %d: obs_start[] must be non-negative and non-decreasing", p);
+        if (obs_start[p + 1] - obs_start[p] > kDistinctiveMax)
+            return fail(ORBX_E_CAPACITY, "point %d: %d observations, a point may have %d", p, obs_start[p + 1] - obs_start[p], kDistinctiveMax);
+    }
+    const int o0 = obs_start[0], total = obs_start[P] - o0;
+    if (total > 0 && (!kfs || !obs_kf || !obs_feat)) return fail(ORBX_E_ARG, "null key-frame or observation table");
+    for (int p = 0; p < P; p++)
+        for (int o = obs_start[p]; o < obs_start[p + 1]; o++) {
+            const int k = obs_kf[o];
+            if (k < 0 || k >= nkf) return fail(ORBX_E_ARG, "observation %d (point %d): key frame %d is outside the call's %d key frames", o, p, k, nkf);
+            const orbm_keyframe* kf = kfs[k];
+            if (!kf) return fail(ORBX_E_ARG, "observation %d (point %d): key frame %d is null", o, p, k);
+            if (kf->device != h->device) return fail(ORBX_E_ARG, "observation %d (point %d): key frame %d lives on device %d, the handle on device %d", o, p, k, kf->device, h->device);
+            if (obs_feat[o] < 0 || obs_feat[o] >= kf->N) return fail(ORBX_E_ARG, "observation %d (point %d): feature %d is outside the %d features of key frame %d", o, p, obs_feat[o], kf->N, k);
+        }
+    const bool writes = map && slots;
+    std::unique_lock<std::mutex> lk;
+    if (map) lk = std::unique_lock<std::mutex>(map->mu);
+    if (writes) {                                                    // slots inside the map, holding a point, each once (-1: the point writes nothing)
+        int rc = ORBX_OK, p = 0;
+        for (; p < P && !rc; p++) {
+            const int s = slots[p];
+            if (s == -1) continue;
+            if (s < 0 || s >= map->slots) rc = fail(ORBX_E_ARG, "point %d: slot %d is outside the map's %d slots", p, s, map->slots);
+            else if (!(map->state[s] & kMapPresent)) rc = fail(ORBX_E_ARG, "point %d: slot %d holds no point", p, s);
+            else if (map->mark[s]) rc = fail(ORBX_E_ARG, "point %d: slot %d is written twice in this call", p, s);
+            else map->mark[s] = 1;
+        }
+        for (int q = 0; q < p; q++) if (slots[q] >= 0 && slots[q] < map->slots) map->mark[slots[q]] = 0;
+        if (rc) return rc;
+    }
+    // the launch lists: the points of the register form, then those of the LDS form; a point without observations is in neither (best = -1, :473)
+    std::vector<DistinctiveRec> recs; std::vector<int> point_of;
+    recs.reserve(P); point_of.reserve(P);
+    int largest = 0, n_reg = 0;
+    for (int form = 0; form < 2; form++) {
+        for (int p = 0; p < P; p++) {
+            const int n = obs_start[p + 1] - obs_start[p];
+            if (n == 0 || (n > kDistinctiveRegMax) != (form == 1)) continue;
+            recs.push_back({writes && slots[p] >= 0 ? map->S.desc + 4 * (size_t)slots[p] : nullptr, obs_start[p] - o0, n});
+            point_of.push_back(p);
+            largest = std::max(largest, n);
+        }
+        if (form == 0) n_reg = (int)recs.size();
+    }
+    for (int p = 0; p < P; p++) best[p] = -1;
+    const int n_rec = (int)recs.size(), n_lds = n_rec - n_reg;
+    if (n_rec == 0) return ORBX_OK;
+    rt::set_device(h->device);
+    std::vector<const unsigned long long*> table(nkf);
+    for (int k = 0; k < nkf; k++) table[k] = kfs[k] ? kfs[k]->dev.desc : nullptr;
+    Packer pk(h);
+    const size_t pt = pk.add(table.data(), sizeof(table[0]) * table.size()), pok = pk.add(obs_kf + o0, sizeof(int) * (size_t)total),
+                 pof = pk.add(obs_feat + o0, sizeof(int) * (size_t)total), pr = pk.add(recs.data(), sizeof(DistinctiveRec) * recs.size()),
+                 pout = pk.room((4 + 32) * (size_t)n_rec);                      // best_desc [n_rec][4], then best [n_rec]
+    if (int e = pk.flush()) return fail(ORBX_E_DEVICE, "%s", upload_error(e));
+    unsigned long long* d_desc = pk.out<unsigned long long>(pout); int* d_best = (int*)(d_desc + 4 * (size_t)n_rec);
+    const DistinctiveRec* d_recs = pk.dev<DistinctiveRec>(pr);
+    const unsigned long long* const* d_table = pk.dev<const unsigned long long*>(pt);
+    if (n_reg > 0) {
+        const dim3 grid((n_reg + 3) / 4, 1, 1), blk(256, 1, 1);
+        ORBX_LAUNCH(k_distinctive_resident<false>, grid, blk, 0, h->s0, d_recs, 0, n_reg, d_table, pk.dev<int>(pok), pk.dev<int>(pof), d_best, d_desc);
+    }
+    if (n_lds > 0) {
+        const dim3 grid(n_lds, 1, 1), blk(64, 1, 1);
+        ORBX_LAUNCH(k_distinctive_resident<true>, grid, blk, 32 * (size_t)largest, h->s0, d_recs, n_reg, n_lds, d_table, pk.dev<int>(pok), pk.dev<int>(pof), d_best, d_desc);
+    }
+    const size_t o_best = 32 * (size_t)n_rec, bytes = o_best + 4 * (size_t)n_rec;
+    const uint8_t* res = (const uint8_t*)d_desc;
+    int e = 0;
+    if (!rt::memory_is_host()) {                                                // (without best_desc only the indices come down)
+        const size_t from = best_desc ? 0 : o_best;
+        e = h->h_res.ensure(bytes + 64);
+        if (!e) e = rt::copy_d2h(h->h_res.p + from, res + from, bytes - from, h->s0);
+        res = h->h_res.p;
+    }
+    if (e || rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "distinctive-descriptor kernel failed: %s", rt::last_error());
+    const int* got = (const int*)(res + o_best);
+    for (int r = 0; r < n_rec; r++) {
+        best[point_of[r]] = got[r];
+        if (best_desc) memcpy(best_desc + 32 * (size_t)point_of[r], res + 32 * (size_t)r, 32);
+    }
+    return ORBX_OK;
+}
+
 }  // extern "C"

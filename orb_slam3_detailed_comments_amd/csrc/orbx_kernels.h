@@ -227,6 +227,10 @@ __global__ void k_map_scan(const int* __restrict__ frame_chunk0, const int* __re
 __global__ void k_map_gather(const MapSetRec* __restrict__ sets, MapStore S, const unsigned* __restrict__ seen_stamp, int nslots, unsigned base);
 
 __global__ void k_distinctive(const unsigned long long* __restrict__ desc, const int* __restrict__ start, int P, int* __restrict__ best);
+template <bool kLds>        // instantiated for both forms in k_match.hip
+__global__ void k_distinctive_resident(const DistinctiveRec* __restrict__ recs, int first, int count,
+                                       const unsigned long long* const* __restrict__ kf_desc, const int* __restrict__ obs_kf, const int* __restrict__ obs_feat,
+                                       int* __restrict__ best, unsigned long long* __restrict__ best_desc);
 __global__ void k_voc_descend(const unsigned long long* __restrict__ fdesc, const int* __restrict__ n_feat, int n_fixed, int cap, int B,
                               const unsigned long long* __restrict__ slot_desc, const VocSlot* __restrict__ slots,
                               const double* __restrict__ slot_weight, int root_children, int nid_level, unsigned* __restrict__ out_word,

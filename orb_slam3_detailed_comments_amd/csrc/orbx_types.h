@@ -111,6 +111,10 @@ constexpr int kMapChunk = 256;         // visited positions per workgroup of the
 struct MapSeg { int set, row, n, pos0, chunk0; };
 // one point set the map builds: where its M points go, slot by slot (slots: which store slot point j is; seen: 1 = the slot is in set `set`'s seen list)
 struct MapSetRec { int* slots; uint8_t* seen; unsigned long long* desc; float *pos, *normal, *min_d, *max_d; int M, set; };
+// one map point of orbm_distinctive_descriptors_resident (k_distinctive_resident): its observations are entries [start, start + n) of the call's
+// observation table (n >= 1: points without observations are not launched); store: the descriptor of its slot in the map's store (nullptr: not written)
+struct DistinctiveRec { unsigned long long* store; int start, n; };
+constexpr int kDistinctiveRegMax = 64, kDistinctiveMax = 1024;      // most observations of the register form (one per lane) and of a point at all
 // one record of k_grid_build_kfs: the grid of one device-resident key frame (orbm_keyframe) for one set of image bounds
 struct GridBuildRec { const KeyPointRec* kps; int* cell_of; int* cell_start; int* cell_items; int N; GridParams g; };
 // one target of orbm_fuse_candidates_batch (k_fuse_candidates): a resident key frame's arrays and the grid built for the target's bounds, the projection of

@@ -993,3 +993,26 @@ def ComputeDistinctiveDescriptors(ext, desc, start):
     best = np.full(max(P, 1), -1, np.int32)
     ext._lib.check(ext._lib.L.orbm_distinctive_descriptors(ext._h, d.ctypes.data if len(d) else None, st.ctypes.data, P, best.ctypes.data))
     return best[:P]
+
+
+def ComputeDistinctiveDescriptorsResident(ext, kfs, obs_start, obs_kf, obs_feat, resident_map=None, slots=None, want_desc=False):
+    """MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:438) on observations named by (resident key frame, feature): point p owns observations
+    [obs_start[p], obs_start[p+1]), observation o is row obs_feat[o] of ResidentKeyFrame kfs[obs_kf[o]].  With a ResidentMap and slots [P] the chosen
+    descriptor overwrites the descriptor of slot slots[p] in the map's store on the device (-1: this point writes nothing).
+    Returns best[P] (-1: point without observations), or (best, desc [P, 32]) with want_desc - rows of points without observations stay zero."""
+    st = np.ascontiguousarray(obs_start, np.int32); ok = np.ascontiguousarray(obs_kf, np.int32); of = np.ascontiguousarray(obs_feat, np.int32)
+    P = len(st) - 1
+    if P > 0 and (len(ok) < st[-1] or len(of) < st[-1]):
+        raise ValueError("obs_start names %d observations, obs_kf / obs_feat hold %d / %d" % (st[-1], len(ok), len(of)))
+    table = (C.c_void_p * max(len(kfs), 1))(*[k._kf for k in kfs])
+    sl = None
+    if slots is not None:
+        sl = np.ascontiguousarray(slots, np.int32)
+        if len(sl) != P:
+            raise ValueError("%d slots for %d points" % (len(sl), P))
+    best = np.full(max(P, 1), -1, np.int32)
+    desc = np.zeros((max(P, 1), 32), np.uint8) if want_desc else None
+    ptr = lambda a: None if a is None else a.ctypes.data
+    ext._lib.check(ext._lib.L.orbm_distinctive_descriptors_resident(ext._h, len(kfs), table, P, st.ctypes.data, ok.ctypes.data, of.ctypes.data,
+                                                                    resident_map._m if resident_map is not None else None, ptr(sl), best.ctypes.data, ptr(desc)))
+    return (best[:P], desc[:P]) if want_desc else best[:P]
