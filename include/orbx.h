@@ -231,6 +231,12 @@ int orbx_debug_quadtree_profile(orbx_extractor* h, long long out[16]);   /* phas
  * the largest value is 4 000.  Bit-identical outputs. */
 int orbx_debug_quadtree_lds_nodes(orbx_extractor* h, int max_nodes);
 int orbx_debug_quadtree_pool_levels(orbx_extractor* h);                   /* number of levels (0 .. n-1) the last extraction ran in the pool form */
+/* test hook: the quadtree moves a level's keys into sorted order only when it divides a node at or below the depth of its up-front counting sort.
+ * on != 0: every tree sorts right after the gather, as before that change (A/B runs).  Bit-identical outputs. */
+int orbx_debug_quadtree_eager(orbx_extractor* h, int on);
+/* per_level[0 .. levels-1] of image image_index of the last extraction: why the level's tree sorted its keys - 0 never, 1 first needed in a full pass,
+ * 2 first needed in a final round, 3 at once (the switch above, or a level outside the lazy form's limits) */
+int orbx_debug_quadtree_sorted(orbx_extractor* h, int image_index, int* per_level);
 /* test hook: the byte / packed-16-bit instruction wrappers of the kernels (csrc/orbx_simd.h) applied to n operand triples (n a multiple of 256);
  * out = 22 x n results in the order mul24, mul24 (forced), v_perm_b32, v_alignbyte_b32, v_dot4_u32_u8, v_dot2_u32_u16, packed max3, packed min3,
  * packed sub, packed xor(a, c), wave inclusive scan / wave sum of a & 0xFFFF, wave minimum of b (per 64 consecutive elements), v_sad_u8, v_mul_u32_u24,

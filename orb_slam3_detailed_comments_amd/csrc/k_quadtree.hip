@@ -10,7 +10,9 @@
 //   * a node's keys are a contiguous span of a key buffer, children laid out n1|n2|n3|n4.  ONE stable counting sort by
 //     (root, first D child digits) up front puts every node of depth <= D in that state at once (D <= 5, <= 1024 buckets,
 //     bucket code = xpart[x] + ypart[y] from two LDS tables); dividing such a node is a difference of bucket offsets.
-//     Deeper nodes are divided by *stable* 4-way partitions of their span (wave ballots; whole workgroup for huge spans);
+//     Deeper nodes are divided by *stable* 4-way partitions of their span (wave ballots; whole workgroup for huge spans).
+//     The sort's offsets are computed up front; its keys are moved only when the first deeper node is about to be divided - a tree that never
+//     gets there (every tree of the reference's settings) picks its keypoints from a per-bucket winner table the gather fills;
 //   * "first max response wins" (:1028-1053) refers to vKeys order = FAST emission order, which is a function of the key
 //     (cell row, cell column, y, x) and is recomputed in the final selection;
 //   * bNoMore <=> span length 1;
@@ -494,19 +496,15 @@ __device__ __forceinline__ void solo_full_pass(const QNode* __restrict__ cur, QN
     if (lane == 0) { res[0] = T; res[1] = E; res[2] = K; res[3] = overflow; }
 }
 
-// The up-front stable counting sort of a level's keys (bufB -> bufA) by bucket code = xpart[x] + ypart[y]: the keys are cut into nseg
-// contiguous segments of `seg` keys (whole 64-key chunks), wave w < nseg owns segment w.  counts[w][b] (CT = uint16_t when the level has
+// The up-front stable counting sort of a level's keys (bufB -> bufA) by bucket code = xpart[x] + ypart[y], in two parts.  The keys are cut into
+// nseg contiguous segments of `seg` keys (whole 64-key chunks), wave w < nseg owns segment w.  counts[w][b] (CT = uint16_t when the level has
 // < 65536 keys, else uint32_t with fewer segments in the same LDS) comes in as the segment's histogram - counted by the gather with LDS
-// atomics, the order of the counts does not matter - and becomes the number of keys of bucket b in the segments before w, i.e. the wave's
-// cursor relative to bucket_start[b].  The scatter finds the lanes of a 64-key chunk that share a bucket with a bit-wise match (ballots):
-// rank inside the group = number of lower lanes in it.
+// atomics, the order of the counts does not matter.
+// Part 1, the offsets: bucket_start[] from the totals, and counts[w][b] becomes the number of keys of bucket b in the segments before w, i.e.
+// the wave's cursor relative to bucket_start[b].  Every division above the presort depth needs no more than this.
 template <typename CT>
-__device__ __forceinline__ void presort_keys(const uint32_t* __restrict__ bufB, uint32_t* __restrict__ bufA, int n, int NB, int nseg, int seg, CT* counts,
-                                             int* bucket_start, const uint16_t* xpart, const uint16_t* ypart, unsigned long long* s_scan, int NT) {
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int beg = imin(n, wave * seg), end = wave < nseg ? imin(n, beg + seg) : beg;
-    CT* mycount = counts + (wave < nseg ? wave : 0) * NB;
-    const unsigned long long lt = (1ull << lane) - 1ull;
+__device__ __forceinline__ void presort_offsets(int NB, int nseg, CT* counts, int* bucket_start, unsigned long long* s_scan, int NT) {
+    const int tid = (int)threadIdx.x;
     __syncthreads();                                               // the histogram (counted by the gather) is complete
     // exclusive scan over buckets of the totals
     int run = 0;
@@ -522,6 +520,18 @@ __device__ __forceinline__ void presort_keys(const uint32_t* __restrict__ bufB, 
     }
     if (tid == 0) bucket_start[NB] = run;
     __syncthreads();
+}
+// Part 2, the scatter: the key movement, run only by a tree that divides a node at or below the presort depth (or at once: the eager switch).
+// It needs bufB, the cursors and the code tables as part 1 left them.  The lanes of a 64-key chunk that share a bucket are found with a
+// bit-wise match (ballots): rank inside the group = number of lower lanes in it.  All threads of the tree must call; ends with a barrier.
+// (A function of its own, not inlined: the tree has three places that may call it, and inlined there it cost the whole kernel 7 VGPRs.)
+template <typename CT>
+__device__ __attribute__((noinline)) void presort_scatter(const uint32_t* __restrict__ bufB, uint32_t* __restrict__ bufA, int n, int NB, int nseg, int seg, CT* counts,
+                                                const int* bucket_start, const uint16_t* xpart, const uint16_t* ypart) {
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int beg = imin(n, wave * seg), end = wave < nseg ? imin(n, beg + seg) : beg;
+    CT* mycount = counts + (wave < nseg ? wave : 0) * NB;
+    const unsigned long long lt = (1ull << lane) - 1ull;
     // stable scatter: same match; rank inside the group = number of lower lanes in it
     // (the keys of the next four chunks are requested before the ballots of the current four: the chunks of a segment depend on each other
     // through the cursors, so nothing else hides the L2 latency of a wave's three or four trips)
@@ -554,6 +564,7 @@ __device__ __forceinline__ void presort_keys(const uint32_t* __restrict__ bufB, 
             ORBX_WAVE_SYNC();
         }
     }
+    __syncthreads();
 }
 
 // One tree = one workgroup: kQuadtreeThreads threads of which the first L.qt_threads (256 or 1024, by the size of the level) work on the level
@@ -574,7 +585,8 @@ __device__ __forceinline__ void quadtree_tree(unsigned char* smem, unsigned char
                                               uint32_t* __restrict__ candA, uint32_t* __restrict__ candB, size_t cand_stride,
                                               uint32_t* __restrict__ lvl_keys, int kp_total_cap,
                                               int* __restrict__ lvl_count, int nlevels, int node_cap, int nb_cap, int lut_x, int lut_y,
-                                              int* __restrict__ status, long long* __restrict__ qt_prof, int wide, int counter_bytes) {
+                                              int* __restrict__ status, long long* __restrict__ qt_prof, int wide, int counter_bytes,
+                                              int* __restrict__ qt_sorted, int eager) {
     __shared__ unsigned long long s_scan[20];
     __shared__ int s_i[80];
     int* s_part = s_i;                                  // block_partition4: 4 counts per wave
@@ -599,7 +611,8 @@ __device__ __forceinline__ void quadtree_tree(unsigned char* smem, unsigned char
     QT_STAMP(0)
     if (tid == 0) *s_kinds = 0;
     // carve: nodes[2][cap] (24 B) | childcnt[cap][4] (u32) | expand[2][cap] (u64) | erased[cap] (u8) - from LDS, or from this tree's slice of the
-    // node pool (kSpill) - then, always in LDS: bucket_start[nb+1] | counts (counter_bytes per bucket: u16 or u32 per segment) | code LUTs
+    // node pool (kSpill) - then, always in LDS: bucket_start[nb+1] | counts (counter_bytes per bucket: u16 or u32 per segment) | [best[nb], wide
+    // form] | code LUTs
     unsigned char* node_mem = kSpill ? pool : smem;
     QNode* nodes0 = (QNode*)node_mem;
     QNode* nodes1 = nodes0 + node_cap;
@@ -609,7 +622,11 @@ __device__ __forceinline__ void quadtree_tree(unsigned char* smem, unsigned char
     uint8_t* erased = (uint8_t*)(exp1 + node_cap);
     int* bucket_start = kSpill ? (int*)smem : (int*)(smem + (((size_t)node_cap * 81 + 15) & ~(size_t)15));
     int* counts = bucket_start + (nb_cap + 2);
-    uint16_t* xpart = (uint16_t*)(counts + (size_t)(counter_bytes >> 2) * nb_cap);     // bucket code = xpart[x] + ypart[y]
+    // best[bucket]: the bucket's winner of the final selection, (response << 24) | (0xFFFFFF - position in bufB), 0 = empty bucket.  The wide form
+    // (32 counter bytes per bucket, all of them used by 16 waves) has a table of its own behind the counters; the four-wave form with 16-bit
+    // counters uses 4 segments x 2 of its 16 counter bytes and keeps the table in the other half.
+    uint32_t* best = (uint32_t*)counts + (counter_bytes == 32 ? 8 : 2) * (size_t)nb_cap;
+    uint16_t* xpart = (uint16_t*)(counts + (size_t)((counter_bytes >> 2) + (counter_bytes == 32 ? 1 : 0)) * nb_cap);     // bucket code = xpart[x] + ypart[y]
     uint16_t* ypart = xpart + lut_x;
     const int D = L.presort_depth, NBr = 1 << (2 * D), NB = L.nini * NBr;     // buckets per root / in total
     uint32_t* bufA = candA + (size_t)b * cand_stride + L.cand_off;
@@ -679,7 +696,14 @@ __device__ __forceinline__ void quadtree_tree(unsigned char* smem, unsigned char
     const bool narrow_counters = n <= kPresortU16Max;
     const int nseg = narrow_counters ? imin(NW, counter_bytes >> 1) : imin(NW, counter_bytes >> 2);
     const int seg = ((n + 64 * nseg - 1) / (64 * nseg)) << 6;     // keys per sort segment (whole 64-key chunks)
+    // Lazy sort: the keys stay where the gather put them (bufB, vKeys order) until a node at or below the presort depth has to be divided - at
+    // the reference's settings no tree of the stereo, mono or RGB-D inputs ever does (profiles/quadtree_lazy_sort).  The selection of a tree that
+    // never sorted reads each bucket's winner from best[].  Not lazy: the eager switch (orbx_debug_quadtree_eager), a level whose positions do
+    // not fit 24 bits, and a four-wave tree with 32-bit counters (no room for best[]).
+    const bool lazy = !eager && n < (1 << 24) && (counter_bytes == 32 || narrow_counters);
+    int sorted = 0;                    // block-uniform: 0 = keys still in bufB, else why they were sorted (1 full pass, 2 final round, 3 eager)
     for (int i = tid; i < (narrow_counters ? (nseg * NB + 1) >> 1 : nseg * NB); i += NT) counts[i] = 0;
+    if (lazy) for (int i = tid; i < NB; i += NT) best[i] = 0;
     __syncthreads();
     {
         int run = 0;
@@ -698,9 +722,11 @@ __device__ __forceinline__ void quadtree_tree(unsigned char* smem, unsigned char
                 int sidx = (pos + sub) / seg, send = (sidx + 1) * seg;       // segment of this lane's first key, and where it ends
                 auto count_key = [&](uint32_t key, int p) {
                     while (p >= send) { sidx++; send += seg; }
-                    const int slot = sidx * NB + (int)xpart[key_x(key)] + (int)ypart[key_y(key)];
+                    const int code = (int)xpart[key_x(key)] + (int)ypart[key_y(key)], slot = sidx * NB + code;
                     if (narrow_counters) atomicAdd((unsigned*)counts + (slot >> 1), 1u << (16 * (slot & 1)));
                     else atomicAdd(counts + slot, 1);
+                    // p is the key's place in vKeys order, so of two keys of one response the earlier one is the larger word (:1028-1053)
+                    if (lazy) atomicMax(best + code, (key & 0xFF000000u) | (0xFFFFFFu - (uint32_t)p));
                 };
                 // (16-byte accesses - four keys per load and store - change nothing: what this loop waits for is the LDS pipe, 12 k table reads
                 // and atomics per level-0 tree)
@@ -720,9 +746,17 @@ __device__ __forceinline__ void quadtree_tree(unsigned char* smem, unsigned char
     // ---- roots + first D tree levels in ONE stable counting sort (bufB -> bufA) --------------------------------------
     // After the sort every node of depth <= D is a contiguous span, its children are laid out n1|n2|n3|n4 and keys keep
     // their vKeys order inside a bucket (stable), which is exactly the state D partition passes would have produced.
-    if (narrow_counters) presort_keys<uint16_t>(bufB, bufA, n, NB, nseg, seg, (uint16_t*)counts, bucket_start, xpart, ypart, s_scan, NT);
-    else presort_keys<uint32_t>(bufB, bufA, n, NB, nseg, seg, (uint32_t*)counts, bucket_start, xpart, ypart, s_scan, NT);
-    __syncthreads();
+    // Only the offsets are computed here: node records name their spans in buffer A from now on, but the keys are moved there (sort_keys) when
+    // the first node of depth >= D is about to be divided, and not at all if none is.  Until then nothing writes bufB, the cursors or the tables.
+    // (Stamps 1 and 2 bracket the offsets, the eager scatter if the switch is on, and the root records.)
+    if (narrow_counters) presort_offsets<uint16_t>(NB, nseg, (uint16_t*)counts, bucket_start, s_scan, NT);
+    else presort_offsets<uint32_t>(NB, nseg, (uint32_t*)counts, bucket_start, s_scan, NT);
+    auto sort_keys = [&](int why) {        // block-uniform call
+        if (narrow_counters) presort_scatter<uint16_t>(bufB, bufA, n, NB, nseg, seg, (uint16_t*)counts, bucket_start, xpart, ypart);
+        else presort_scatter<uint32_t>(bufB, bufA, n, NB, nseg, seg, (uint32_t*)counts, bucket_start, xpart, ypart);
+        sorted = why;
+    };
+    if (!lazy) sort_keys(3);
     int nnodes = 0;
     for (int r = 0; r < L.nini; r++) {
         const int s0 = bucket_start[r * NBr], c = bucket_start[(r + 1) * NBr] - s0;
@@ -779,6 +813,7 @@ __device__ __forceinline__ void quadtree_tree(unsigned char* smem, unsigned char
         }
         __syncthreads();
         const int kinds = *s_kinds;
+        if (kinds && !sorted) sort_keys(1);
         if (kinds & kDeepBig) {
             for (int i = 0; i < nnodes; i++) {
                 const QNode nd = cur[i];
@@ -906,6 +941,7 @@ __device__ __forceinline__ void quadtree_tree(unsigned char* smem, unsigned char
                 }
                 __syncthreads();
                 const int kinds = *s_kinds;
+                if (kinds && !sorted) sort_keys(2);
                 if (kinds & kDeepBig) {
                     for (int j = 0; j < nexp; j++) {           // (rare) spans too big for one wave
                         const int idx = (int)(expc[j] & 0xFFFF);
@@ -1033,6 +1069,7 @@ __device__ __forceinline__ void quadtree_tree(unsigned char* smem, unsigned char
     QT_STAMP(8)
     // ---- result (:1028-1053): per node, the first key with the largest response ----
     uint32_t* outk = lvl_keys + (size_t)b * kp_total_cap + L.kp_off;
+    if (tid == 0) qt_sorted[(size_t)b * nlevels + level] = sorted;
     if (overflow || nnodes > L.kp_cap) {
         if (tid == 0) { atomicOr(status, 1); lvl_count[(size_t)b * nlevels + level] = 0; }
         return;
@@ -1046,6 +1083,22 @@ __device__ __forceinline__ void quadtree_tree(unsigned char* smem, unsigned char
     int lgl = 0;
     while (lgl < 4 && (nnodes << (lgl + 1)) <= NT) lgl++;
     const int lpn = 1 << lgl;
+    if (!sorted) {
+        // Never sorted: every node has depth <= D - a deeper node can only be the child of a division at depth >= D, and the first of those
+        // sorts - so it is the bucket range [code << 2(D - d), (code + 1) << 2(D - d)) and its winner the largest word of best[] there: both
+        // orderings (largest response, then earliest in vKeys order) are associative.  The key itself is still where the gather put it.
+        for (int i0 = 0; i0 < nnodes; i0 += NT >> lgl) {
+            const int i = i0 + (tid >> lgl), r = tid & (lpn - 1);
+            uint32_t w = 0;
+            if (i < nnodes) {
+                const QNode nd = cur[i];
+                const int sh = 2 * (D - (int)nd.depth), hi = (int)((nd.code + 1u) << sh);
+                for (int bk = (int)(nd.code << sh) + r; bk < hi; bk += lpn) { const uint32_t v = best[bk]; w = v > w ? v : w; }
+            }
+            for (int d = 1; d < lpn; d <<= 1) { const uint32_t o = __shfl_xor(w, d); w = o > w ? o : w; }
+            if (i < nnodes && r == 0) outk[i] = w ? bufB[0xFFFFFFu - (w & 0xFFFFFFu)] : 0u;       // (w != 0: a node holds at least one key)
+        }
+    } else
     for (int i0 = 0; i0 < nnodes; i0 += NT >> lgl) {
         const int i = i0 + (tid >> lgl), r = tid & (lpn - 1);
         uint32_t best = 0; int bs = -1; unsigned long long bo = ~0ull;
@@ -1087,10 +1140,11 @@ __global__ void __launch_bounds__(kQuadtreeThreads) k_quadtree(const LevelInfo* 
                                                   uint32_t* __restrict__ candA, uint32_t* __restrict__ candB, size_t cand_stride,
                                                   uint32_t* __restrict__ lvl_keys, int kp_total_cap,
                                                   int* __restrict__ lvl_count, int nlevels, int node_cap, int nb_cap, int lut_x, int lut_y,
-                                                  int* __restrict__ status, long long* __restrict__ qt_prof, int wide, int counter_bytes, int level0) {
+                                                  int* __restrict__ status, long long* __restrict__ qt_prof, int wide, int counter_bytes, int level0,
+                                                  int* __restrict__ qt_sorted, int eager) {
     ORBX_DYN_SMEM(smem);
     quadtree_tree<false>(smem, nullptr, (int)blockIdx.y + level0, (int)blockIdx.x, lv, cells, ncells, cell_count, slots, slots_stride, candA, candB, cand_stride,
-                         lvl_keys, kp_total_cap, lvl_count, nlevels, node_cap, nb_cap, lut_x, lut_y, status, qt_prof, wide, counter_bytes);
+                         lvl_keys, kp_total_cap, lvl_count, nlevels, node_cap, nb_cap, lut_x, lut_y, status, qt_prof, wide, counter_bytes, qt_sorted, eager);
 }
 // The levels whose node lists do not fit the LDS: levels 0 .. gridDim.y - 1, tree (b, level) works in pool + (b * gridDim.y + level) * pool_stride.
 // Dynamic LDS: the tables only.
@@ -1102,11 +1156,11 @@ __global__ void __launch_bounds__(kQuadtreeThreads) k_quadtree_spill(const Level
                                                   uint32_t* __restrict__ lvl_keys, int kp_total_cap,
                                                   int* __restrict__ lvl_count, int nlevels, int node_cap, int nb_cap, int lut_x, int lut_y,
                                                   int* __restrict__ status, long long* __restrict__ qt_prof, int wide, int counter_bytes,
-                                                  unsigned char* __restrict__ pool, size_t pool_stride) {
+                                                  unsigned char* __restrict__ pool, size_t pool_stride, int* __restrict__ qt_sorted, int eager) {
     ORBX_DYN_SMEM(smem);
     quadtree_tree<true>(smem, pool + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * pool_stride, (int)blockIdx.y, (int)blockIdx.x, lv, cells, ncells, cell_count,
                         slots, slots_stride, candA, candB, cand_stride, lvl_keys, kp_total_cap, lvl_count, nlevels, node_cap, nb_cap, lut_x, lut_y, status,
-                        qt_prof, wide, counter_bytes);
+                        qt_prof, wide, counter_bytes, qt_sorted, eager);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -132,13 +132,14 @@ void pyramid_spans(const orbx_extractor* h, bool columns, std::vector<PyrSpan>& 
 }
 
 // How the quadtree stage is launched (k_quadtree.hip).  A tree's node arrays take 81 bytes per node; beside them the bucket offsets, the per-segment
-// bucket counters (counter_bytes per bucket) and the two coordinate tables of the level.  Levels first_lds .. nlevels-1 run in the LDS form with
+// bucket counters (counter_bytes per bucket), the buckets' winners (4 bytes per bucket; the four-wave form, 16 counter bytes, keeps them in the half of
+// its counters that 16-bit counts leave unused) and the two coordinate tables of the level.  Levels first_lds .. nlevels-1 run in the LDS form with
 // node_cap_lds nodes each; levels 0 .. first_lds-1 (the big quotas of a 5 x nFeatures extractor) keep their node arrays in the global pool.
 struct QuadtreePlan { int first_lds, node_cap_lds, lut_x, lut_y; size_t smem_lds, smem_spill, pool_stride; };
 QuadtreePlan quadtree_plan(const orbx_extractor* h, int counter_bytes) {
     QuadtreePlan p;
     p.lut_x = (int)align_up((size_t)h->lv[0].bw + 1, 8); p.lut_y = (int)align_up((size_t)h->lv[0].bh + 1, 8);       // level 0 is the largest
-    const size_t tables = (size_t)(h->nb_cap + 2) * 4 + (size_t)counter_bytes * h->nb_cap + 2 * (size_t)(p.lut_x + p.lut_y) + 64;
+    const size_t tables = (size_t)(h->nb_cap + 2) * 4 + (size_t)(counter_bytes + (counter_bytes == 32 ? 4 : 0)) * h->nb_cap + 2 * (size_t)(p.lut_x + p.lut_y) + 64;
     const size_t limit = rt::lds_limit(h->device);
     p.first_lds = h->nlevels; p.node_cap_lds = 0; p.smem_lds = 0;
     int cap = 0;
@@ -350,7 +351,7 @@ int configure(orbx_extractor* h, int W, int H, int B) {
         int e = 0;
         e |= h->d_pyr.ensure(b * h->pyr_stride + 256); e |= h->d_blur.ensure(b * h->pyr_stride + 256);
         e |= h->d_slots.ensure(b * h->cand_stride + 4); e |= h->d_candA.ensure(b * h->cand_stride + 4); e |= h->d_candB.ensure(b * h->cand_stride + 4);
-        e |= h->d_cell_count.ensure(b * h->ncells); e |= h->d_lvl_count.ensure(b * h->nlevels);
+        e |= h->d_cell_count.ensure(b * h->ncells); e |= h->d_lvl_count.ensure(b * h->nlevels); e |= h->d_qtsorted.ensure(b * h->nlevels);
         e |= h->d_lvl_keys.ensure(b * cap); e |= h->d_final_idx.ensure(b * cap);
         // counts [b] | mono indices [b] | status word (4 ints): one block, so that orbx_fetch brings all three back in one copy; d_status is a
         // view of its tail (never allocated or freed by itself)
@@ -521,13 +522,13 @@ int enqueue_extract(orbx_extractor* h, int B, const uint8_t* d_images, int src_w
             ORBX_LAUNCH(k_quadtree_spill, dim3(B, qp.first_lds, 1), blkq, qp.smem_spill, h->s0, (const LevelInfo*)h->d_lv.p, (const CellInfo*)h->d_cells.p, h->ncells,
                         (const int*)h->d_cell_count.p, (const uint32_t*)h->d_slots.p, h->cand_stride, h->d_candA.p, h->d_candB.p, h->cand_stride,
                         h->d_lvl_keys.p, h->kp_total_cap, h->d_lvl_count.p, nl, h->node_cap, h->nb_cap, qp.lut_x, qp.lut_y, h->d_status.p,
-                        prof, wide, counter_bytes, h->d_qtpool.p, qp.pool_stride);
+                        prof, wide, counter_bytes, h->d_qtpool.p, qp.pool_stride, h->d_qtsorted.p, h->qt_eager);
         }
         if (qp.first_lds < nl)
             ORBX_LAUNCH(k_quadtree, dim3(B, nl - qp.first_lds, 1), blkq, qp.smem_lds, h->s0, (const LevelInfo*)h->d_lv.p, (const CellInfo*)h->d_cells.p, h->ncells,
                         (const int*)h->d_cell_count.p, (const uint32_t*)h->d_slots.p, h->cand_stride, h->d_candA.p, h->d_candB.p, h->cand_stride,
                         h->d_lvl_keys.p, h->kp_total_cap, h->d_lvl_count.p, nl, qp.node_cap_lds, h->nb_cap, qp.lut_x, qp.lut_y, h->d_status.p,
-                        prof, wide, counter_bytes, qp.first_lds);
+                        prof, wide, counter_bytes, qp.first_lds, h->d_qtsorted.p, h->qt_eager);
     }
     stage_end(h, ST_QUADTREE, h->s0);
     stage_begin(h, ST_LAYOUT, h->s0);
@@ -615,7 +616,7 @@ void orbx_destroy(orbx_extractor* h) {
     }
     orbv_forget_handle(h);      // (its vocabulary work has been waited for above)
     h->d_lv.release(); h->d_cells.release(); h->d_xtab.release(); h->d_ytab.release(); h->d_xspan.release(); h->d_yspan.release(); h->d_pyr.release(); h->d_blur.release(); h->d_stage.release();
-    h->d_slots.release(); h->d_candA.release(); h->d_candB.release(); h->d_lvl_keys.release(); h->d_cell_count.release(); h->d_lvl_count.release();
+    h->d_slots.release(); h->d_candA.release(); h->d_candB.release(); h->d_lvl_keys.release(); h->d_cell_count.release(); h->d_lvl_count.release(); h->d_qtsorted.release();
     h->d_final_idx.release(); h->d_status.p = nullptr; h->d_status.n = 0; h->d_nm.release(); h->d_kps.release(); h->d_desc.release();
     h->d_uRight.release(); h->d_depth.release(); h->d_sad.release(); h->d_nmatch.release(); h->d_knn.release(); h->d_ratio.release();
     h->d_l2r.release(); h->d_r2l.release(); h->d_p3d.release(); h->d_hamA.release(); h->d_hamB.release(); h->d_hamOut.release(); h->h_stage.release(); h->h_nm.release(); h->h_cnt.release();
@@ -1112,6 +1113,23 @@ int orbx_debug_quadtree_lds_nodes(orbx_extractor* h, int max_nodes) {
     if (!h || max_nodes < 0) return ORBX_E_ARG;
     h->qt_lds_nodes = std::min(max_nodes, kQuadtreeLdsNodes);
     h->g_B = 0;                 // a captured graph holds the launches of the old plan
+    return ORBX_OK;
+}
+
+// debug: every tree moves its keys into sorted order right after the gather, as the kernel did before the sort became lazy (A/B runs, parity)
+int orbx_debug_quadtree_eager(orbx_extractor* h, int on) {
+    if (!h) return ORBX_E_ARG;
+    h->qt_eager = on != 0;
+    h->g_B = 0;                 // a captured graph holds the launches with the old flag
+    return ORBX_OK;
+}
+// debug: per level of image b of the last extraction, why its tree sorted its keys: 0 never, 1 a full pass met a node at or below the presort
+// depth, 2 a final round did, 3 at once (the eager switch, or a level the lazy form does not take)
+int orbx_debug_quadtree_sorted(orbx_extractor* h, int b, int* per_level) {
+    if (!h || !per_level || b < 0 || b >= h->lastB || !h->d_qtsorted.p) return fail(ORBX_E_ARG, "bad probe");
+    rt::set_device(h->device);
+    if (rt::stream_sync(h->s0) || rt::copy_d2h(per_level, h->d_qtsorted.p + (size_t)b * h->nlevels, sizeof(int) * h->nlevels, h->s0) || rt::stream_sync(h->s0))
+        return fail(ORBX_E_DEVICE, "probe failed: %s", rt::last_error());
     return ORBX_OK;
 }
 

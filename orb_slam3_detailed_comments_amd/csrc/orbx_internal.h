@@ -121,6 +121,9 @@ struct orbx_extractor {
     size_t area_pool = 0, area_last_total = 0;
     orbx::DevBuf<int> d_si[8];
     orbx::DevBuf<long long> d_qtprof;
+    // per (image, level): why the tree moved its keys into sorted order (0 = never; k_quadtree.hip, orbx_debug_quadtree_sorted); qt_eager = every
+    // tree sorts at once (orbx_debug_quadtree_eager)
+    orbx::DevBuf<int> d_qtsorted; int qt_eager = 0;
     // k_quadtree_spill: node pool of the levels whose quadtree does not fit the LDS (orbx_api.cpp: quadtree_plan); qt_lds_nodes = largest tree the LDS form
     // is given (orbx_debug_quadtree_lds_nodes: tests lower it to run small cases through the pool form)
     orbx::DevBuf<uint8_t> d_qtpool; int qt_lds_nodes = orbx::kQuadtreeLdsNodes, cfg_qt_lds_nodes = 0, qt_pool_levels = 0;      // qt_pool_levels: levels the last extraction ran in the pool form

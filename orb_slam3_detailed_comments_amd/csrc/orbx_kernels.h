@@ -70,14 +70,14 @@ __global__ void k_quadtree(const LevelInfo* __restrict__ lv, const CellInfo* __r
                            uint32_t* __restrict__ candA, uint32_t* __restrict__ candB, size_t cand_stride,
                            uint32_t* __restrict__ lvl_keys, int kp_total_cap, int* __restrict__ lvl_count,
                            int nlevels, int node_cap, int nb_cap, int lut_x, int lut_y, int* __restrict__ status, long long* __restrict__ qt_prof,
-                           int wide, int counter_bytes, int level0);
+                           int wide, int counter_bytes, int level0, int* __restrict__ qt_sorted, int eager);
 // levels whose node lists exceed the LDS (the 5 x nFeatures extractor of the monocular initialisation): node arrays in a global pool
 __global__ void k_quadtree_spill(const LevelInfo* __restrict__ lv, const CellInfo* __restrict__ cells, int ncells,
                            const int* __restrict__ cell_count, const uint32_t* __restrict__ slots, size_t slots_stride,
                            uint32_t* __restrict__ candA, uint32_t* __restrict__ candB, size_t cand_stride,
                            uint32_t* __restrict__ lvl_keys, int kp_total_cap, int* __restrict__ lvl_count,
                            int nlevels, int node_cap, int nb_cap, int lut_x, int lut_y, int* __restrict__ status, long long* __restrict__ qt_prof,
-                           int wide, int counter_bytes, unsigned char* __restrict__ pool, size_t pool_stride);
+                           int wide, int counter_bytes, unsigned char* __restrict__ pool, size_t pool_stride, int* __restrict__ qt_sorted, int eager);
 constexpr int kQuadtreeLdsNodes = 4000;     // the LDS form packs positions of its sort ranges in 12 bits: trees with more nodes take the pool form whatever the LDS
 // self-test of the quadtree's workgroup primitives (orbx_debug_quadtree_selftest; k_quadtree.hip): one workgroup of 256 or 1024 threads.
 // The sort's arrays: two range lists of quadtree_selftest_seg_cap(n) entries (4 bytes in the LDS form, 8 in the pool form), two arrays of n keys, n flag bytes.

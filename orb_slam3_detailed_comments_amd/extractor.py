@@ -230,6 +230,18 @@ class ORBextractor:
         """Number of pyramid levels whose quadtree the last extraction ran in the pool form (orbx_debug_quadtree_pool_levels)."""
         return int(self._lib.L.orbx_debug_quadtree_pool_levels(self._h))
 
+    def debug_quadtree_eager(self, on):
+        """Test hook: every quadtree sorts its keys right after the gather instead of when a deep division first needs them
+        (orbx_debug_quadtree_eager).  Bit-identical outputs."""
+        self._lib.check(self._lib.L.orbx_debug_quadtree_eager(self._h, 1 if on else 0))
+
+    def debug_quadtree_sorted(self, b=0):
+        """Per level of image b of the last extraction: 0 = the tree never sorted its keys, 1 = first needed in a full pass, 2 = in a final
+        round, 3 = sorted at once (orbx_debug_quadtree_sorted)."""
+        out = np.zeros(self.nlevels, np.int32)
+        self._lib.check(self._lib.L.orbx_debug_quadtree_sorted(self._h, int(b), out.ctypes.data))
+        return out
+
     def debug_quadtree_sort(self, keys, spill, threads):
         """Test hook: the quadtree kernel's model of std::sort (comparator on key >> 16) applied to 64-bit keys by one workgroup of `threads`
         threads, in the LDS form (spill = 0, up to 4095 keys) or the node-pool form (spill = 1, up to 65535) (orbx_debug_quadtree_selftest)."""
