@@ -95,6 +95,19 @@ public:
             m[pKF] = e;
             return r;
         }
+        // Enters a key frame that was made ON THE DEVICE (orbm_keyframe_create_extracted / _rig_extracted: Tracking::CreateNewKeyFrame for a frame whose
+        // features never left the GPU) under the tag Get computes for pKF, so that a later search naming pKF uploads nothing.  The cache owns `dev` from here
+        // on and destroys the entry it replaces.  The tag holds mFeatVec.size(): a key frame adopted before ComputeBoW has run on the host object is
+        // rebuilt by the first Get after it, as an entry made by Get would be.  `dev` must live on this thread's device (Device()).
+        void Adopt(KeyFrameT* pKF, orbm_keyframe* dev)
+        {
+            if (device != Device()) { Clear(); device = Device(); }
+            const Tag tag = {(long long)pKF->mnId, (long long)pKF->N, (long long)pKF->mFeatVec.size(), Fingerprint(pKF)};
+            auto it = m.find(pKF);
+            if (it != m.end()) { if (it->second.dev != dev) orbm_keyframe_destroy(it->second.dev); m.erase(it); }
+            Entry e; e.dev = dev; e.tag = tag; e.stamp = ++clock;
+            m[pKF] = e;
+        }
         void Erase(KeyFrameT* pKF) { auto it = m.find(pKF); if (it != m.end()) { orbm_keyframe_destroy(it->second.dev); m.erase(it); } }
         void Clear() { for (auto& e : m) orbm_keyframe_destroy(e.second.dev); m.clear(); if (transient) { orbm_keyframe_destroy(transient); transient = nullptr; } }
         size_t size() const { return m.size(); }
@@ -153,6 +166,7 @@ public:
         if (c.Capacity() == 0) c.SetCapacity((size_t)kImplicitCacheEntries);
         return c;
     }
+    template <class KeyFrameT> static void AdoptImplicit(KeyFrameT* pKF, orbm_keyframe* dev) { ImplicitCache<KeyFrameT>().Adopt(pKF, dev); }     // ResidentKeyFrames::Adopt for the calling thread's cache
     template <class KeyFrameT> static void EraseImplicit(KeyFrameT* pKF) { ImplicitCache<KeyFrameT>().Erase(pKF); }
     template <class KeyFrameT> static void ClearImplicit() { ImplicitCache<KeyFrameT>().Clear(); }
     template <class KeyFrameT> static void SetImplicitCapacity(size_t n) { ImplicitCache<KeyFrameT>().SetCapacity(n ? n : 1); }

@@ -943,6 +943,32 @@ int orbv_transform_extracted(orbv_vocabulary* v, orbx_extractor* h, int first, i
 int orbv_fetch(orbv_vocabulary* v, orbx_extractor* h, int b, uint32_t* word_id, uint32_t* node_id, int n_features, uint32_t* bow_id, double* bow_val,
                int* n_bow, uint32_t* fv_node, int* fv_start, uint32_t* fv_feat, int* n_fv);
 
+/* Resident key frames made ON THE DEVICE from frames of the handle's last extraction (Tracking::CreateNewKeyFrame for frames that never left the
+ * device): out[j] = a key frame of image frames[j] - mvKeysUn (undistorted when the extraction ran with orbx_set_undistort), its descriptor rows,
+ * mvuRight = the results of orbm_stereo_match / orbm_stereo_from_depth for that image when use_u_right != 0 (they must cover it, on this extraction), else
+ * every entry -1, the FeatureVector where the last orbv_transform_extracted(v, h, first, B, levelsup) left it (frames[j] in [first, first + B)), the
+ * handle's scale and sigma tables.  v == NULL: key frames without a FeatureVector (fv_nodes = 0) of any image of the last extraction - what Fuse, the
+ * Sim3 projection batch and the per-camera key frames of a rig need.  An index may appear more than once; every occurrence is an object of its own.
+ * The key frames are copies with the device layout of orbm_keyframe_create: the next extraction, the vocabulary's next run and orbx_destroy of the
+ * handle leave them intact, every resident search takes them through any handle of the device, orbm_keyframe_destroy frees them.  One small block (the
+ * frames' sizes) and the keypoint angles come down, nothing goes up but the table of the call.  Blocking.  n == 0: ORBX_OK, nothing is written.
+ * Refused before anything is enqueued (ORBX_E_ARG; no object is left behind, out is untouched): null arguments, n < 0, nothing extracted yet, an
+ * index outside the extraction or outside the transform's range, a transform of another handle or extraction or one whose results were overwritten,
+ * a rig transform, orbx_set_undistort since the extraction, the vocabulary on another device, use_u_right without stereo results for the image. */
+int orbm_keyframe_create_extracted(orbx_extractor* h, const orbv_vocabulary* v, int n, const int* frames /*[n]*/, int use_u_right,
+                                   orbm_keyframe** out /*[n]*/);
+/* The same for rig frames, in the layout orbm_search_for_triangulation_resident_kb8 and orbm_search_by_bow_rig_batch expect: mvKeys of camera 1
+ * (not undistorted) followed by mvKeysRight, the joined descriptor rows and the FeatureVector of the last
+ * orbv_transform_rig_extracted(v, L, lf, R, rf, B, levelsup), no u_right.  frames[j] in [0, B) names a rig frame as orbm_search_by_bow_rig_batch
+ * does.  v is required; a one-camera transform is refused. */
+int orbm_keyframe_create_rig_extracted(orbx_extractor* L, int lf, orbx_extractor* R, int rf, const orbv_vocabulary* v, int n,
+                                       const int* frames /*[n]*/, orbm_keyframe** out /*[n]*/);
+/* Reads a resident key frame back, however it was made.  Any pointer may be NULL; capacities: keys_un, desc (32 B rows), u_right and node_of_feat N,
+ * fv_node fv_nodes, fv_start fv_nodes + 1, fv_feat fv_start[fv_nodes] entries (at most N) - a first call with only N / fv_nodes gives the sizes.
+ * node_of_feat[f] = index of the node that holds feature f, -1 for a feature in none.  Blocking. */
+int orbm_keyframe_fetch(orbx_extractor* h, const orbm_keyframe* kf, int* N, int* fv_nodes, OrbxKeyPoint* keys_un, uint8_t* desc, float* u_right,
+                        uint32_t* fv_node, int* fv_start, uint32_t* fv_feat, int* node_of_feat);
+
 /* ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vpMapPointMatches) (src/ORBmatcher.cc:259-493; Tracking::TrackReferenceKeyFrame
  * src/Tracking.cc:3183, Relocalization :4371) for a BATCH of frames on the device: frame b = image first + b of h's last extraction, whose
  * FeatureVector is read where orbv_transform_extracted(v, h, first, B, levelsup) left it (call that first, on the same images); KFs[b] = the

@@ -29,7 +29,7 @@ SYMBOLS = [
     "orbx_profile_get", "orbx_stage_name", "orbx_debug_candidates", "orbx_debug_level_keys", "orbx_debug_quadtree_profile", "orbx_set_host_wait", "orbx_debug_quadtree_lds_nodes", "orbx_debug_quadtree_pool_levels", "orbx_debug_quadtree_eager", "orbx_debug_quadtree_sorted", "orbx_debug_simd_selftest", "orbx_debug_model_eval", "orbx_debug_quadtree_selftest", "orbx_debug_stereo_flags", "orbx_debug_live_resources",
     "orbm_hamming_matrix", "orbm_stereo_match", "orbm_stereo_fetch", "orbm_knn2", "orbm_knn2_fetch", "orbm_stereo_fisheye", "orbm_stereo_fisheye_fetch", "orbm_search_for_triangulation_kb8", "orbm_is_in_frustum", "orbm_is_in_frustum_rig", "orbm_search_local_points_fisheye", "orbm_search_local_points",
     "orbm_get_features_in_area", "orbm_search_by_projection_mappoints", "orbm_search_by_projection_frame",
-    "orbm_search_for_triangulation", "orbm_search_by_bow", "orbm_search_by_bow_batch", "orbm_keyframe_create", "orbm_points_create", "orbm_points_destroy", "orbm_search_local_points_resident", "orbm_stereo_from_depth", "orbm_search_local_points_batch", "orbm_search_local_points_fetch", "orbm_search_by_projection_lastframe_batch", "orbm_search_by_projection_keyframe_batch", "orbm_keyframe_destroy", "orbm_search_for_triangulation_resident", "orbm_search_for_triangulation_resident_kb8", "orbm_search_by_bow_resident", "orbm_search_by_bow_fisheye", "orbm_search_for_initialization", "orbm_area_search_batch",
+    "orbm_search_for_triangulation", "orbm_search_by_bow", "orbm_search_by_bow_batch", "orbm_keyframe_create", "orbm_points_create", "orbm_points_destroy", "orbm_search_local_points_resident", "orbm_stereo_from_depth", "orbm_search_local_points_batch", "orbm_search_local_points_fetch", "orbm_search_by_projection_lastframe_batch", "orbm_search_by_projection_keyframe_batch", "orbm_keyframe_destroy", "orbm_keyframe_create_extracted", "orbm_keyframe_create_rig_extracted", "orbm_keyframe_fetch", "orbm_search_for_triangulation_resident", "orbm_search_for_triangulation_resident_kb8", "orbm_search_by_bow_resident", "orbm_search_by_bow_fisheye", "orbm_search_for_initialization", "orbm_area_search_batch",
     "orbm_project_points", "orbm_search_by_projection_sim3", "orbm_search_by_projection_keyframe", "orbm_fuse_candidates", "orbm_search_by_sim3", "orbm_distinctive_descriptors", "orbm_distinctive_descriptors_resident",
     "orbm_search_by_projection_mappoints_fisheye", "orbm_search_by_projection_frame_fisheye", "orbm_search_for_triangulation_batch",
     "orbm_search_local_points_rig_batch", "orbm_search_by_projection_lastframe_rig_batch", "orbm_search_rig_batch_fetch",
@@ -142,6 +142,9 @@ class OrbxLib:
         L.orbm_search_by_projection_lastframe_batch.argtypes = [vp, i, i, vp, vp, f, vp, vp, i, vp, i]
         L.orbm_search_by_projection_keyframe_batch.argtypes = [vp, i, i, vp, vp, f, i, i, vp]
         L.orbm_keyframe_destroy.argtypes = [vp]; L.orbm_keyframe_destroy.restype = None
+        L.orbm_keyframe_create_extracted.argtypes = [vp, vp, i, vp, i, vp]
+        L.orbm_keyframe_create_rig_extracted.argtypes = [vp, i, vp, i, vp, i, vp, vp]
+        L.orbm_keyframe_fetch.argtypes = [vp, vp, ip, ip, vp, vp, vp, vp, vp, vp, vp]
         L.orbm_search_for_triangulation_resident.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, i, i, i, vp, vp]
         L.orbm_search_for_triangulation_resident_kb8.argtypes = [vp, vp, vp, i, vp, vp, vp, vp, i, i, i, vp, vp]
         L.orbm_search_by_bow_resident.argtypes = [vp, i, vp, vp, vp, vp, f, i, i, vp, vp]

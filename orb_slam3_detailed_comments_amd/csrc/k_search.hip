@@ -1591,4 +1591,60 @@ __global__ void __launch_bounds__(256) k_map_gather(const MapSetRec* __restrict_
     if (q == 0) R.seen[j] = seen_stamp ? (uint8_t)(seen_stamp[(size_t)R.set * nslots + slot] > base) : (uint8_t)0;
 }
 
+// ---- key frames made from extracted frames (orbm_keyframe_create_extracted / _rig_extracted) ----------------------------------------------------
+// What the host must know of every frame before it can allocate: out[3 j ..] = features, FeatureVector nodes, FeatureVector entries of record j
+// (the counts are clamped to what the arrays can hold; the host refuses a FeatureVector that does not fit its frame).  grid (ceil(n / 64)), 64 threads
+__global__ void __launch_bounds__(64) k_keyframe_counts(const KfSnapRec* __restrict__ recs, int n, int* __restrict__ out) {
+    const int j = (int)(blockIdx.x * 64u + threadIdx.x);
+    if (j >= n) return;
+    const KfSnapRec R = recs[j];
+    const int N = imin(*R.n_l, R.cap) + (R.kps_r ? imin(*R.n_r, R.cap) : 0);
+    const int rows = R.kps_r ? 2 * R.cap : R.cap;                  // per-frame stride of the transform's arrays
+    int nn = 0, nf = 0;
+    if (R.node_id) { nn = imin(*R.fv_nodes, rows); if (nn < 0) nn = 0; nf = R.fv_start[nn]; }
+    out[3 * j] = N; out[3 * j + 1] = nn; out[3 * j + 2] = nf;
+}
+
+// The copy: every section of the key frames' blocks in one launch.  grid (chunks, n), 256 threads; the workgroups of a key frame stride over each section.
+// Keypoint records are 28 B and a frame's rows start at a multiple of 28 B: they move as flat dwords (camera 2's of a rig frame behind camera 1's);
+// descriptor rows are 32 B at 32 B multiples on both sides: two 16 B accesses per row; uRight, node ids, offsets and feature indices start at
+// dword multiples in the source: dwords.  node_of_feat is the inverse of the CSR with -1 for the features in no node: filling and scattering must not
+// overlap, so the first workgroup of a key frame does both around a barrier (a few thousand entries) and the other workgroups never touch that section.
+// The entry behind the node ids and behind the feature indices (the sections hold one more than they need) is written as 0.
+__global__ void __launch_bounds__(256) k_keyframe_snapshot(const KfSnapRec* __restrict__ recs) {
+    const KfSnapRec R = recs[blockIdx.y];
+    const int t0 = (int)(blockIdx.x * 256u + threadIdx.x), step = (int)(gridDim.x * 256u);
+    const int N = R.N, N1 = N > 0 ? N : 1, nn = R.nn, nf = R.nf;
+    const int nl = R.kps_r ? imin(imin(*R.n_l, R.cap), N) : N;
+    {
+        uint32_t* d = (uint32_t*)R.dst;
+        const uint32_t *s1 = (const uint32_t*)R.kps, *s2 = (const uint32_t*)R.kps_r;
+        for (int i = t0; i < 7 * N; i += step) d[i] = i < 7 * nl ? s1[i] : s2[i - 7 * nl];
+        for (int i = t0; i < N; i += step) R.angle[i] = i < nl ? R.kps[i].angle : R.kps_r[i - nl].angle;
+    }
+    {
+        const int4* s = (const int4*)R.desc; int4* d = (int4*)(R.dst + R.o_desc);
+        for (int i = t0; i < 2 * N; i += step) d[i] = s[i];
+    }
+    {
+        float* d = (float*)(R.dst + R.o_ur);
+        for (int i = t0; i < N1; i += step) d[i] = (R.ur && i < N) ? R.ur[i] : -1.0f;
+    }
+    {
+        uint32_t* dn = (uint32_t*)(R.dst + R.o_nid); int* ds = (int*)(R.dst + R.o_st); int* df = (int*)(R.dst + R.o_ft);
+        for (int i = t0; i <= nn; i += step) { dn[i] = i < nn ? R.node_id[i] : 0u; ds[i] = nn > 0 ? R.fv_start[i] : 0; }
+        for (int i = t0; i <= nf; i += step) df[i] = i < nf ? R.fv_feat[i] : 0;
+    }
+    if (blockIdx.x != 0) return;
+    int* nof = (int*)(R.dst + R.o_nof);
+    for (int i = (int)threadIdx.x; i < N1; i += 256) nof[i] = -1;
+    __syncthreads();
+    for (int k = (int)threadIdx.x; k < nf; k += 256) {
+        int lo = 0, hi = nn;                                        // the node a with fv_start[a] <= k < fv_start[a + 1]
+        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (R.fv_start[mid] <= k) lo = mid; else hi = mid; }
+        const int f = R.fv_feat[k];
+        if ((unsigned)f < (unsigned)N) nof[f] = lo;
+    }
+}
+
 }  // namespace orbx

@@ -591,7 +591,9 @@ int orbm_stereo_from_depth(orbx_extractor* h, int first, int B, const float* dep
     ORBX_LAUNCH(k_stereo_from_depth, grid, blk, 0, h->s0, (const KeyPointRec*)(h->d_kps.p + (size_t)first * cap),
                 h->ex_undist_active ? (const KeyPointRec*)(h->d_kps_un.p + (size_t)first * cap) : (const KeyPointRec*)nullptr, (const int*)(h->d_nm.p + first), cap,
                 d_depth, stride, image_stride, h->W, h->H, mbf, h->d_uRight.p, h->d_depth.p, h->d_nmatch.p);
+    h->ur_B = 0;
     if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
+    h->ur_first = first; h->ur_B = B; h->ur_gen = h->extract_gen;
     return ORBX_OK;
 }
 
@@ -1250,6 +1252,164 @@ void orbm_keyframe_destroy(orbm_keyframe* kf) {
     rt::dfree(kf->dmem);
     for (KfGrid* g : kf->grids) { rt::dfree(g->mem); delete g; }
     delete kf;
+}
+
+// ---- key frames made on the device from frames of the last extraction ----
+// recs name where each frame and its FeatureVector sit (source pointers and cap filled in by the entry points, which have refused everything they can
+// refuse by then).  k_keyframe_counts tells the host the sizes - one small block down -, the blocks are allocated with the layout of orbm_keyframe_create,
+// k_keyframe_snapshot fills all of them in one launch, and the angles come down for the host's copy.  rowcap: most features of one frame.  Blocking.
+static int keyframes_from_records(orbx_extractor* h, const char* entry, std::vector<KfSnapRec>& recs, int rowcap, orbm_keyframe** out) {
+    const int n = (int)recs.size();
+    Packer pk(h);
+    const size_t pr = pk.add(recs.data(), sizeof(KfSnapRec) * recs.size()), pc = pk.room(12 * (size_t)n), pa = pk.room(4 * (size_t)n * rowcap);
+    if (int e = pk.flush()) return fail(ORBX_E_DEVICE, "%s: %s", entry, upload_error(e));
+    ORBX_LAUNCH(k_keyframe_counts, dim3((n + 63) / 64, 1, 1), dim3(64, 1, 1), 0, h->s0, pk.dev<KfSnapRec>(pr), n, pk.out<int>(pc));
+    std::vector<int> cnt(3 * (size_t)n);
+    if (fetch_sync(h, cnt.data(), pk.dev<int>(pc), 12 * (size_t)n) || rt::check_launch()) return fail(ORBX_E_DEVICE, "%s: reading the frames' sizes failed: %s", entry, rt::last_error());
+    int nmax = 1; size_t atotal = 0;
+    for (int j = 0; j < n; j++) {
+        const int N = cnt[3 * j], nn = cnt[3 * j + 1], nf = cnt[3 * j + 2];
+        if (N < 0 || N > rowcap || N >= 65535) return fail(ORBX_E_CAPACITY, "%s: key frame %d would have %d features", entry, j, N);
+        if (nn < 0 || nf < nn || nf > N) return fail(ORBX_E_INTERNAL, "%s: key frame %d: a FeatureVector of %d nodes and %d entries does not fit %d features", entry, j, nn, nf, N);
+    }
+    std::vector<orbm_keyframe*> made(n, nullptr);
+    auto drop = [&]() { for (orbm_keyframe* kf : made) if (kf) { rt::dfree(kf->dmem); delete kf; } };
+    for (int j = 0; j < n; j++) {
+        const int N = cnt[3 * j], N1 = std::max(N, 1), nn = cnt[3 * j + 1], nf = cnt[3 * j + 2];
+        const size_t okp = 0, odesc = okp + al16(sizeof(KeyPointRec) * (size_t)N1), our = odesc + al16(32 * (size_t)N1), onid = our + al16(4 * (size_t)N1),
+                     ost = onid + al16(4 * (size_t)(nn + 1)), oft = ost + al16(4 * (size_t)(nn + 1)), onof = oft + al16(4 * (size_t)(nf + 1)),
+                     total = onof + al16(4 * (size_t)N1);
+        orbm_keyframe* kf = made[j] = new orbm_keyframe();
+        kf->device = h->device; kf->N = N; kf->fv_nodes = nn; kf->nlevels = h->nlevels;
+        kf->dmem = (uint8_t*)rt::dmalloc(total);
+        if (!kf->dmem) { drop(); return fail(ORBX_E_DEVICE, "%s: allocating key frame %d failed", entry, j); }
+        kf->dev.kps = (const KeyPointRec*)(kf->dmem + okp); kf->dev.desc = (const unsigned long long*)(kf->dmem + odesc); kf->dev.ur = (const float*)(kf->dmem + our);
+        kf->dev.node_id = (const uint32_t*)(kf->dmem + onid); kf->dev.fv_start = (const int*)(kf->dmem + ost); kf->dev.fv_feat = (const int*)(kf->dmem + oft);
+        kf->dev.node_of_feat = (const int*)(kf->dmem + onof); kf->dev.N = N; kf->dev.fv_nodes = nn;
+        for (int l = 0; l < kMaxLevels; l++) { kf->scale[l] = l < h->nlevels ? h->scale[l] : 1.0f; kf->sigma2[l] = l < h->nlevels ? h->sigma2[l] : 1.0f; }
+        KfSnapRec& R = recs[j];
+        R.dst = kf->dmem; R.angle = pk.out<float>(pa) + atotal;
+        R.o_desc = (unsigned)odesc; R.o_ur = (unsigned)our; R.o_nid = (unsigned)onid; R.o_st = (unsigned)ost; R.o_ft = (unsigned)oft; R.o_nof = (unsigned)onof;
+        R.N = N; R.nn = nn; R.nf = nf;
+        atotal += (size_t)N; nmax = std::max(nmax, N);
+    }
+    if (int e = pk.flush()) { drop(); return fail(ORBX_E_DEVICE, "%s: %s", entry, upload_error(e)); }
+    // a thread moves ~4 dwords of the largest section (7 per keypoint record)
+    const int chunks = std::min(16, std::max(1, (7 * nmax + 1023) / 1024));
+    ORBX_LAUNCH(k_keyframe_snapshot, dim3(chunks, n, 1), dim3(256, 1, 1), 0, h->s0, pk.dev<KfSnapRec>(pr));
+    std::vector<float> angles(std::max<size_t>(atotal, 1));
+    if (fetch_sync(h, angles.data(), pk.dev<float>(pa), 4 * atotal) || rt::check_launch()) { drop(); return fail(ORBX_E_DEVICE, "%s: the copy failed: %s", entry, rt::last_error()); }
+    size_t a0 = 0;
+    for (int j = 0; j < n; j++) {
+        orbm_keyframe* kf = made[j];
+        kf->angle.assign(std::max(kf->N, 1), 0.0f);
+        std::copy(angles.begin() + a0, angles.begin() + a0 + kf->N, kf->angle.begin());
+        a0 += (size_t)kf->N;
+    }
+    for (int j = 0; j < n; j++) out[j] = made[j];
+    return ORBX_OK;
+}
+
+int orbm_keyframe_create_extracted(orbx_extractor* h, const orbv_vocabulary* v, int n, const int* frames, int use_u_right, orbm_keyframe** out) {
+    static const char* const entry = "orbm_keyframe_create_extracted";
+    if (!h || n < 0 || (n > 0 && (!frames || !out))) return fail(ORBX_E_ARG, "%s: null argument or n < 0", entry);
+    if (n == 0) return ORBX_OK;
+    if (n > 65535) return fail(ORBX_E_CAPACITY, "%s: at most 65535 key frames per call", entry);
+    if (h->lastB <= 0) return fail(ORBX_E_ARG, "%s: the handle has not extracted anything yet", entry);
+    if (undistort_stale(h)) return fail(ORBX_E_ARG, "%s: orbx_set_undistort was called after the last extraction: extract again before making key frames of its frames", entry);
+    VocFrameArrays V; memset(&V, 0, sizeof V);
+    std::unique_lock<std::mutex> vlk;
+    int lo = 0, hi = h->lastB;                                   // the images a key frame may be made of
+    if (v) {
+        vlk = orbv_lock(v);                                      // until the copy has run: no other handle's run replaces the FeatureVectors under the kernel
+        if (orbv_frame_arrays(v, &V)) return fail(ORBX_E_ARG, "%s: run orbv_transform_extracted(v, h, first, B, levelsup) on this extraction first: the FeatureVectors are read where it leaves them", entry);
+        if (V.device != h->device) return fail(ORBX_E_ARG, "%s: vocabulary and extractor live on different devices", entry);
+        if (V.rig) return fail(ORBX_E_ARG, "%s: the last vocabulary transform was a rig transform (orbv_transform_rig_extracted): make its key frames with orbm_keyframe_create_rig_extracted", entry);
+        if (V.handle != (const void*)h || V.cap != h->kp_total_cap || V.first < 0 || V.first + V.lastB > h->lastB)
+            return fail(ORBX_E_ARG, "%s: the vocabulary's last transform did not run on this handle, or its results were overwritten: run orbv_transform_extracted on this extraction", entry);
+        if (V.extract_gen != h->extract_gen)
+            return fail(ORBX_E_ARG, "%s: the handle has extracted another batch since orbv_transform_extracted ran: its FeatureVectors index the keypoints of the previous batch - transform again", entry);
+        lo = V.first; hi = V.first + V.lastB;
+    }
+    for (int j = 0; j < n; j++) {
+        if (frames[j] < lo || frames[j] >= hi)
+            return fail(ORBX_E_ARG, v ? "%s: key frame %d names image %d, the vocabulary transform covers [%d, %d)" : "%s: key frame %d names image %d, the last extraction holds [%d, %d)", entry, j, frames[j], lo, hi);
+        if (use_u_right && (h->ur_B <= 0 || h->ur_gen != h->extract_gen || frames[j] < h->ur_first || frames[j] >= h->ur_first + h->ur_B))
+            return fail(ORBX_E_ARG, "%s: use_u_right, but image %d has no results of orbm_stereo_match / orbm_stereo_from_depth on this extraction", entry, frames[j]);
+    }
+    rt::set_device(h->device);
+    const int cap = h->kp_total_cap;
+    std::vector<KfSnapRec> recs(n);
+    for (int j = 0; j < n; j++) {
+        const size_t f = (size_t)frames[j];
+        KfSnapRec& R = recs[j]; memset(&R, 0, sizeof R);
+        R.kps = (h->ex_undist_active ? h->d_kps_un.p : h->d_kps.p) + f * cap;                        // mvKeysUn
+        R.n_l = h->d_nm.p + f; R.desc = h->d_desc.p + f * cap * 4; R.cap = cap;
+        if (use_u_right) R.ur = h->d_uRight.p + (f - (size_t)h->ur_first) * cap;
+        if (v) {
+            const size_t b = f - (size_t)V.first;
+            R.node_id = V.fv_node + b * cap; R.fv_start = V.fv_start + b * (cap + 1); R.fv_feat = V.fv_feat + b * cap; R.fv_nodes = V.nout + 2 * b + 1;
+        }
+    }
+    return keyframes_from_records(h, entry, recs, cap, out);
+}
+
+int orbm_keyframe_create_rig_extracted(orbx_extractor* L, int lf, orbx_extractor* R, int rf, const orbv_vocabulary* v, int n, const int* frames, orbm_keyframe** out) {
+    static const char* const entry = "orbm_keyframe_create_rig_extracted";
+    if (!L || !R || !v || n < 0 || (n > 0 && (!frames || !out))) return fail(ORBX_E_ARG, "%s: null argument or n < 0", entry);
+    if (n == 0) return ORBX_OK;
+    if (n > 65535) return fail(ORBX_E_CAPACITY, "%s: at most 65535 key frames per call", entry);
+    if (L->lastB <= 0 || R->lastB <= 0) return fail(ORBX_E_ARG, "%s: a handle has not extracted anything yet", entry);
+    VocFrameArrays V;
+    const std::unique_lock<std::mutex> vlk = orbv_lock(v);       // as in orbm_keyframe_create_extracted
+    if (orbv_frame_arrays(v, &V) || !V.rig)
+        return fail(ORBX_E_ARG, "%s: no rig transform: run orbv_transform_rig_extracted(v, L, %d, R, %d, B, levelsup) first - the rig frames' rows and FeatureVectors are read where it leaves them", entry, lf, rf);
+    if (V.handle != (const void*)L || V.handle_r != (const void*)R || V.first != lf || V.first_r != rf)
+        return fail(ORBX_E_ARG, "%s: the last rig transform covered other handles or frames (left %d, right %d, %d frames)", entry, V.first, V.first_r, V.lastB);
+    if (V.extract_gen != L->extract_gen || V.extract_gen_r != R->extract_gen)
+        return fail(ORBX_E_ARG, "%s: a handle has extracted since orbv_transform_rig_extracted ran: its FeatureVectors index the keypoints of the previous batch - transform again", entry);
+    if (V.device != L->device || R->device != L->device) return fail(ORBX_E_ARG, "%s: vocabulary and extractors live on different devices", entry);
+    const int cap = L->kp_total_cap, S = V.cap, B = V.lastB;
+    if (S != 2 * cap || R->kp_total_cap != cap || lf < 0 || rf < 0 || lf + B > L->lastB || rf + B > R->lastB) return fail(ORBX_E_ARG, "%s: the rig transform does not match the handles' extractions", entry);
+    for (int j = 0; j < n; j++)
+        if (frames[j] < 0 || frames[j] >= B) return fail(ORBX_E_ARG, "%s: key frame %d names frame %d, the rig transform holds %d", entry, j, frames[j], B);
+    rt::set_device(L->device);
+    if (L != R) { record_done_if_pending(R); rt::stream_wait_event(L->s0, R->ev_done); }          // R's extraction runs on R's stream
+    std::vector<KfSnapRec> recs(n);
+    for (int j = 0; j < n; j++) {
+        const size_t b = (size_t)frames[j];
+        KfSnapRec& Q = recs[j]; memset(&Q, 0, sizeof Q);
+        Q.kps = L->d_kps.p + ((size_t)lf + b) * cap; Q.kps_r = R->d_kps.p + ((size_t)rf + b) * cap;   // mvKeys, mvKeysRight
+        Q.n_l = L->d_nm.p + lf + b; Q.n_r = R->d_nm.p + rf + b; Q.cap = cap;
+        Q.desc = V.desc + b * S * 4;
+        Q.node_id = V.fv_node + b * S; Q.fv_start = V.fv_start + b * (S + 1); Q.fv_feat = V.fv_feat + b * S; Q.fv_nodes = V.nout + 2 * b + 1;
+    }
+    return keyframes_from_records(L, entry, recs, S, out);
+}
+
+int orbm_keyframe_fetch(orbx_extractor* h, const orbm_keyframe* kf, int* N, int* fv_nodes, OrbxKeyPoint* keys_un, uint8_t* desc, float* u_right, uint32_t* fv_node,
+                        int* fv_start, uint32_t* fv_feat, int* node_of_feat) {
+    if (!h || !kf) return fail(ORBX_E_ARG, "orbm_keyframe_fetch: null handle or key frame");
+    if (kf->device != h->device) return fail(ORBX_E_ARG, "orbm_keyframe_fetch: the key frame lives on another device");
+    rt::set_device(h->device);
+    if (N) *N = kf->N;
+    if (fv_nodes) *fv_nodes = kf->fv_nodes;
+    const size_t n = (size_t)kf->N, nn = (size_t)kf->fv_nodes;
+    // the sections are contiguous: everything from the keypoints to the feature indices' end comes down in one copy
+    const uint8_t* base = kf->dmem;
+    const size_t o_st = (const uint8_t*)kf->dev.fv_start - base, o_ft = (const uint8_t*)kf->dev.fv_feat - base, o_nof = (const uint8_t*)kf->dev.node_of_feat - base;
+    const size_t total = o_nof + 4 * std::max<size_t>(n, 1);
+    std::vector<uint8_t> img(total);
+    if (fetch_sync(h, img.data(), base, total)) return fail(ORBX_E_DEVICE, "orbm_keyframe_fetch: D2H failed: %s", rt::last_error());
+    if (keys_un && n) memcpy(keys_un, img.data(), sizeof(KeyPointRec) * n);
+    if (desc && n) memcpy(desc, img.data() + ((const uint8_t*)kf->dev.desc - base), 32 * n);
+    if (u_right && n) memcpy(u_right, img.data() + ((const uint8_t*)kf->dev.ur - base), 4 * n);
+    if (fv_node && nn) memcpy(fv_node, img.data() + ((const uint8_t*)kf->dev.node_id - base), 4 * nn);
+    const int* st = (const int*)(img.data() + o_st);
+    if (fv_start) memcpy(fv_start, st, 4 * (nn + 1));
+    if (fv_feat && nn && st[nn] > 0) memcpy(fv_feat, img.data() + o_ft, 4 * (size_t)st[nn]);
+    if (node_of_feat && n) memcpy(node_of_feat, img.data() + o_nof, 4 * n);
+    return ORBX_OK;
 }
 
 // rotation-consistency pruning shared by the resident searches: m12 entries outside the three strongest bins of the angle-difference

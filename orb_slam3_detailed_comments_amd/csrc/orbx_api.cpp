@@ -1225,7 +1225,9 @@ int orbm_stereo_match(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int 
     ORBX_LAUNCH(k_stereo_median, grid2, blk, 0, L->s0, (const int*)(L->d_nm.p + lf), cap, L->d_uRight.p, L->d_depth.p,
                 (const int*)L->d_sad.p, L->d_nmatch.p);
     if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][1], L->s0);
+    L->ur_B = 0;
     if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
+    L->ur_first = lf; L->ur_B = B; L->ur_gen = L->extract_gen;
     return ORBX_OK;
 }
 

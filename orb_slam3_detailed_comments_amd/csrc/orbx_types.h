@@ -162,6 +162,19 @@ struct BowPairResident { ResidentKF k1, k2; int mp1_off, elig2_off; const int* k
 // one pair of orbm_search_by_bow_rig_batch: m.k2 = rig frame (descriptors and FeatureVector of the rig transform, m.k2.kps = camera 1's keypoints),
 // kps_r = camera 2's keypoints, nleft = Nleft on the device
 struct BowPairRig { BowPairResident m; const KeyPointRec* kps_r; const int* nleft; };
+// one key frame of orbm_keyframe_create_extracted / _rig_extracted (k_keyframe_counts, k_keyframe_snapshot): where a frame of the last extraction and its
+// FeatureVector sit on the device, and the block of the new key frame.  kps / n_l: the frame's (camera 1's) keypoints and their count; kps_r / n_r: camera 2's
+// of a rig frame (nullptr: one camera); desc: its descriptor rows (a rig's: the joined rows of the rig transform); ur: nullptr = every entry -1;
+// node_id == nullptr: no FeatureVector, else fv_nodes names its node count.  dst: the sections of ResidentKF at the o_* byte offsets (kps at 0);
+// N / nn / nf: features, nodes and FeatureVector entries as k_keyframe_counts reported them; angle: the keypoints' angles, packed, for the host's copy.
+struct KfSnapRec {
+    const KeyPointRec *kps, *kps_r; const int *n_l, *n_r;
+    const unsigned long long* desc; const float* ur;
+    const uint32_t* node_id; const int* fv_start; const int* fv_feat; const int* fv_nodes;
+    uint8_t* dst; float* angle;
+    unsigned o_desc, o_ur, o_nid, o_st, o_ft, o_nof;
+    int N, nn, nf, cap;
+};
 struct KB8StereoParams {                     // Frame::ComputeStereoFishEyeMatches (src/Frame.cc:1530-1587)
     float cam1[8], cam2[8];                  // mpCamera, mpCamera2
     float R12[9], t12[3];                    // mRlr, mtlr

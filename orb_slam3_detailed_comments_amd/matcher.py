@@ -272,6 +272,66 @@ class ResidentKeyFrame:
         self._lib.check(self._lib.L.orbm_keyframe_create(ext._h, kf_view.ref(), C.byref(h)))
         self._kf = h
 
+    @classmethod
+    def _adopt(cls, lib, handle, ext):
+        kf = cls.__new__(cls)
+        kf._lib = lib; kf._kf = C.c_void_p(handle)
+        n = C.c_int()
+        try:
+            lib.check(lib.L.orbm_keyframe_fetch(ext._h, kf._kf, C.byref(n), None, None, None, None, None, None, None, None))
+        except Exception:
+            kf.close()
+            raise
+        kf.N = n.value
+        return kf
+
+    @classmethod
+    def from_extracted(cls, ext, voc, frames, use_u_right=False):
+        """orbm_keyframe_create_extracted: resident key frames made on the device from images `frames` of ext's last extraction - mvKeysUn, descriptor rows,
+        mvuRight of the last stereo matcher / depth call (use_u_right; else -1) and the FeatureVector where the last voc.transform_extracted left it
+        (voc = None: key frames without a FeatureVector).  Returns a list, one object per entry of `frames`."""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        out = (C.c_void_p * max(len(fr), 1))()
+        ext._lib.check(ext._lib.L.orbm_keyframe_create_extracted(ext._h, voc._v if voc is not None else None, len(fr), fr.ctypes.data, int(bool(use_u_right)), out))
+        return cls._adopt_all(ext, out, len(fr))
+
+    @classmethod
+    def from_rig_extracted(cls, exL, lf, exR, rf, voc, frames):
+        """orbm_keyframe_create_rig_extracted: rig key frames (mvKeys followed by mvKeysRight, the joined rows, no mvuRight) of rig frames `frames` of the
+        last voc.transform_rig_extracted(exL, lf, exR, rf, B, levelsup).  Returns a list."""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        out = (C.c_void_p * max(len(fr), 1))()
+        exL._lib.check(exL._lib.L.orbm_keyframe_create_rig_extracted(exL._h, int(lf), exR._h, int(rf), voc._v if voc is not None else None, len(fr), fr.ctypes.data, out))
+        return cls._adopt_all(exL, out, len(fr))
+
+    @classmethod
+    def _adopt_all(cls, ext, out, n):
+        kfs = []
+        try:
+            for j in range(n):
+                kfs.append(cls._adopt(ext._lib, out[j], ext))
+        except Exception:
+            for j in range(len(kfs) + 1, n):
+                ext._lib.L.orbm_keyframe_destroy(C.c_void_p(out[j]))
+            raise
+        return kfs
+
+    def fetch(self, ext):
+        """orbm_keyframe_fetch: dict of numpy arrays - keys_un [N] (views.KP_DTYPE), desc [N, 32], u_right [N], fv_node [nodes], fv_start [nodes + 1],
+        fv_feat [fv_start[-1]], node_of_feat [N]."""
+        from .views import KP_DTYPE
+        L = self._lib
+        n, nn = C.c_int(), C.c_int()
+        L.check(L.L.orbm_keyframe_fetch(ext._h, self._kf, C.byref(n), C.byref(nn), None, None, None, None, None, None, None))
+        N, nodes = n.value, nn.value
+        r = dict(keys_un=np.zeros(N, KP_DTYPE), desc=np.zeros((N, 32), np.uint8), u_right=np.zeros(N, np.float32), fv_node=np.zeros(nodes, np.uint32),
+                 fv_start=np.zeros(nodes + 1, np.int32), node_of_feat=np.zeros(N, np.int32))
+        L.check(L.L.orbm_keyframe_fetch(ext._h, self._kf, None, None, r["keys_un"].ctypes.data, r["desc"].ctypes.data, r["u_right"].ctypes.data, r["fv_node"].ctypes.data,
+                                        r["fv_start"].ctypes.data, None, r["node_of_feat"].ctypes.data))
+        r["fv_feat"] = np.zeros(int(r["fv_start"][nodes]), np.uint32)
+        L.check(L.L.orbm_keyframe_fetch(ext._h, self._kf, None, None, None, None, None, None, None, r["fv_feat"].ctypes.data, None))
+        return r
+
     def close(self):
         if self._kf:
             self._lib.L.orbm_keyframe_destroy(self._kf); self._kf = None
