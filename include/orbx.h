@@ -979,6 +979,60 @@ int orbm_keyframe_fetch(orbx_extractor* h, const orbm_keyframe* kf, int* N, int*
 int orbm_search_by_bow_frames_batch(orbx_extractor* h, const orbv_vocabulary* v, int first, int B, orbm_keyframe* const* KFs,
                                     const uint8_t* const* has_map_point, float nnratio, int check_orientation, int* const* matches12, int* nmatches);
 
+/* The tracking searches fed from the resident map.  A caller that keeps its map in an orbm_map names the points of the three searches around
+ * SearchLocalPoints by SLOT or by key-frame ROW, and the device gathers the fields (k_map_rows_gather, k_map_row_flags) into the block the host-fed
+ * calls upload - everything behind that gather is the host-fed call's own code, so results, the fetch calls, the one pending batch per handle and the
+ * candidate-pool protocol (ORBX_E_CAPACITY from the fetch, then enqueue again) are those of orbm_search_by_projection_lastframe_batch,
+ * .._lastframe_rig_batch, .._keyframe_batch and orbm_search_by_bow_frames_batch.  "The slot holds a point" (orbm_map_update has written it) stands for
+ * pMP != NULL; a slot that holds nothing counts as no map point.
+ *   Last frame (TrackWithMotionModel; src/ORBmatcher.cc:1981-1983 tests pMP and mvbOutlier[i] only): row i of frame b is used iff i < n[b],
+ * slots[b][i] >= 0, the slot holds a point and outlier[b][i] is 0.  The slot's BAD FLAG IS NOT READ: the reference does not call isBad() here and
+ * orbm_map_set_bad leaves the fields in place.  Position and descriptor come from the store; octave, angle and has_obs stay host rows - they belong to
+ * the last frame's keypoints and to the tracker (a temporal point of UpdateLastFrame gets a slot by orbm_map_update like any point, with has_obs = 0).
+ * A slot may appear many times in a row.
+ *   Key frame (Relocalization; :2218-2220): row i is used iff i is below the length of row[b], its slot is >= 0 and holds a point that is NOT bad, and
+ * found[b][i] is 0.  Position, mfMinDistance, mfMaxDistance and descriptor come from the store, the angle from keypoint i of kfs[b]
+ * (pKF->mvKeysUn[i].angle); the row's length and kfs[b]'s N have to be equal.  assigned indexes the row.
+ *   BoW (TrackReferenceKeyFrame, Relocalization): has_map_point[b][i] = the key-frame rule without `found`, for row rows[b] and key frame KFs[b].
+ *   The map: results equal a gather at the moment of the call, whatever any handle does to the map afterwards.  Each call takes the map's mutex,
+ * enqueues upload and gather, waits on the host for an event recorded right behind the gather - for that only, not for the search - and releases the
+ * mutex; the search stays asynchronous.  orbm_search_by_bow_frames_batch_map is blocking as its host-fed form and holds the vocabulary's lock and the
+ * map's mutex, taken in that order.  The key frames kfs[b] / KFs[b] are read by the gather too and may be destroyed once the call has returned
+ * (projection forms; the BoW search has ended by then).
+ *   Refusals come before anything is enqueued, leave nothing to fetch and name frame and entry: ORBX_E_ARG for a null map, last, kf, rows or KFs, a
+ * map on another device than the handle, n[b] outside [0, cap_last], a used slot below -1 or at or above the map's slots, a row outside the map or
+ * never set (orbm_map_set_keyframe), a row length other than kfs[b]'s N, found != NULL with cap_found below a used row's length, and everything the
+ * host-fed calls refuse; ORBX_E_CAPACITY as theirs (LDS of the accept kernel: cap_last, or the longest row).  Device memory: the handle's batch
+ * block as for the host-fed calls (the gathered rows take the place of the uploaded ones); orbx_debug_live_resources counts it.
+ * (The structs are declared apart from their typedefs like OrbmFrameMap; their Python mirrors are checked by tests/test_map_rows_projection.py.) */
+struct OrbmLastFrameSlots {            /* LastFrame.mvpMapPoints as slots of an orbm_map */
+    int cap_last;                      /* entries per frame in the arrays below */
+    const int* n;                      /* [B] LastFrame.N */
+    const int* slots;                  /* [B][cap_last] slot of mvpMapPoints[i], -1 = NULL */
+    const uint8_t* outlier;            /* [B][cap_last] LastFrame.mvbOutlier[i] (NULL = none) */
+    const int* octave;                 /* [B][cap_last] as OrbmLastFrameBatch */
+    const float* angle;                /* [B][cap_last] as OrbmLastFrameBatch */
+    const uint8_t* has_obs;            /* [B][cap_last] (NULL = all observed) */
+};
+typedef struct OrbmLastFrameSlots OrbmLastFrameSlots;
+int orbm_search_by_projection_lastframe_batch_map(orbx_extractor* h, int first, int B, const OrbmFrustumView* cur, orbm_map* map,
+                                                  const OrbmLastFrameSlots* last, float th, const uint8_t* forward, const uint8_t* backward,
+                                                  int check_orientation, const uint8_t* occupied, int use_u_right);
+int orbm_search_by_projection_lastframe_rig_batch_map(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* cur,
+                                                      const float* trl, orbm_map* map, const OrbmLastFrameSlots* last, float th,
+                                                      const uint8_t* forward, const uint8_t* backward, int check_orientation, const uint8_t* occupied);
+struct OrbmKeyFrameRows {              /* the candidate key frame of each frame, by its place in the map */
+    const int* row;                    /* [B] the key frame's row (orbm_map_set_keyframe) */
+    orbm_keyframe* const* kfs;         /* [B] the same key frame, resident: pKF->mvKeysUn[i].angle is read from it */
+    int cap_found;                     /* entries per frame of `found` */
+    const uint8_t* found;              /* [B][cap_found] sAlreadyFound.count(vpMPs[i]) (NULL = none found) */
+};
+typedef struct OrbmKeyFrameRows OrbmKeyFrameRows;
+int orbm_search_by_projection_keyframe_batch_map(orbx_extractor* h, int first, int B, const OrbmFrustumView* cur, orbm_map* map,
+                                                 const OrbmKeyFrameRows* kf, float th, int orb_dist, int check_orientation, const uint8_t* occupied);
+int orbm_search_by_bow_frames_batch_map(orbx_extractor* h, const orbv_vocabulary* v, int first, int B, orbm_keyframe* const* KFs, orbm_map* map,
+                                        const int* rows /*[B]*/, float nnratio, int check_orientation, int* const* matches12, int* nmatches);
+
 /* Frame::ComputeBoW for B fisheye-rig frames (Nleft != -1, src/Frame.cc:984-997 over the rig Frame's mDescriptors, :1514): frame b = left image
  * lf + b of L's last extraction (camera 1: features [0, Nleft)) followed by right image rf + b of R's (camera 2: features [Nleft, Nleft + Nright)),
  * transformed as ONE set of Nleft + Nright rows - BowVector and FeatureVector equal to transform() on the joined rows.  L == R is allowed (lf = 0,

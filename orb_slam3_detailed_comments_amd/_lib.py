@@ -36,6 +36,8 @@ SYMBOLS = [
     "orbm_search_local_points_batch_maps", "orbm_search_local_points_rig_batch_maps", "orbm_points_count", "orbm_fuse_candidates_batch", "orbm_search_by_projection_sim3_batch",
     "orbm_map_create", "orbm_map_destroy", "orbm_map_update", "orbm_map_set_bad", "orbm_map_set_keyframe", "orbm_map_local_points", "orbm_map_select", "orbm_map_set",
     "orbm_map_set_fetch", "orbm_points_fetch", "orbm_map_debug_epoch",
+    "orbm_search_by_projection_lastframe_batch_map", "orbm_search_by_projection_lastframe_rig_batch_map", "orbm_search_by_projection_keyframe_batch_map",
+    "orbm_search_by_bow_frames_batch_map",
     "orbv_create", "orbv_load_text", "orbv_destroy", "orbv_words", "orbv_transform", "orbv_transform_extracted", "orbv_fetch", "orbm_search_by_bow_frames_batch",
     "orbv_transform_rig_extracted", "orbm_search_by_bow_rig_batch",
     "orbv_db_create", "orbv_db_destroy", "orbv_db_add", "orbv_db_add_extracted", "orbv_db_erase", "orbv_db_erase_keys", "orbv_db_clear", "orbv_db_size",
@@ -187,6 +189,10 @@ class OrbxLib:
         L.orbv_transform_extracted.argtypes = [vp, vp, i, i, i]
         L.orbv_fetch.argtypes = [vp, vp, i, vp, vp, i, vp, vp, ip, vp, vp, vp, ip]
         L.orbm_search_by_bow_frames_batch.argtypes = [vp, vp, i, i, vp, vp, f, i, vp, vp]
+        L.orbm_search_by_projection_lastframe_batch_map.argtypes = [vp, i, i, vp, vp, vp, f, vp, vp, i, vp, i]
+        L.orbm_search_by_projection_lastframe_rig_batch_map.argtypes = [vp, i, vp, i, i, vp, vp, vp, vp, f, vp, vp, i, vp]
+        L.orbm_search_by_projection_keyframe_batch_map.argtypes = [vp, i, i, vp, vp, vp, f, i, i, vp]
+        L.orbm_search_by_bow_frames_batch_map.argtypes = [vp, vp, i, i, vp, vp, vp, f, i, vp, vp]
         L.orbv_transform_rig_extracted.argtypes = [vp, vp, i, vp, i, i, i]
         L.orbm_search_by_bow_rig_batch.argtypes = [vp, i, vp, i, i, vp, i, vp, vp, vp, f, i, vp, vp]
         u64 = C.c_uint64

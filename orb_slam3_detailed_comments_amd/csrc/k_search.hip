@@ -1591,6 +1591,47 @@ __global__ void __launch_bounds__(256) k_map_gather(const MapSetRec* __restrict_
     if (q == 0) R.seen[j] = seen_stamp ? (uint8_t)(seen_stamp[(size_t)R.set * nslots + slot] > base) : (uint8_t)0;
 }
 
+// ---- the rows of a projection batch read from the map (orbm_search_by_projection_lastframe_batch_map / _keyframe_batch_map) ------------------------
+// Writes what the host-fed calls upload - valid, position, descriptor and, in the key-frame form, mfMinDistance, mfMaxDistance and the key frame's keypoint
+// angle - for row i of frame b, so the query, window-search and accept kernels read the same block either way.  The row's slot is slots[b][i] (last frame:
+// LastFrame.mvpMapPoints as slots, rows == nullptr) or entry i of the key frame's row in the map (rows[b].slots).  The row is valid iff i < n[b], the slot is
+// >= 0 and holds a point, the caller's flag excluded[b][i] (mvbOutlier / sAlreadyFound) is 0 and - key-frame form only, src/ORBmatcher.cc:2218-2220 against
+// :1981-1983 - the point is not bad.  Rows that are not valid are written as zeros.  Four lanes per row as k_map_gather: lane q moves descriptor word q
+// and two of the floats {x y | z min | max angle}, lane 3 the valid byte.  grid (ceil(4 cap / 256), B), 256 threads
+__global__ void __launch_bounds__(256) k_map_rows_gather(MapStore S, int cap, const int* __restrict__ n, const int* __restrict__ slots, const MapRowRec* __restrict__ rows,
+                                                         const uint8_t* __restrict__ excluded, uint8_t* __restrict__ valid, float* __restrict__ pos,
+                                                         unsigned long long* __restrict__ desc, float* __restrict__ min_d, float* __restrict__ max_d,
+                                                         float* __restrict__ angle) {
+    const int t = (int)(blockIdx.x * 256u + threadIdx.x), i = t >> 2, q = t & 3;
+    if (i >= cap) return;
+    const size_t b = blockIdx.y, o = b * (size_t)cap + (size_t)i;
+    const bool inside = i < n[b];
+    int slot = -1;
+    if (inside) slot = rows ? rows[b].slots[i] : slots[o];
+    bool ok = false;
+    if (slot >= 0) {
+        const uint8_t st = S.state[slot];
+        ok = (st & kMapPresent) && !(rows && (st & kMapBad)) && !excluded[o];
+    }
+    const size_t s = ok ? (size_t)slot : 0;
+    desc[4 * o + q] = ok ? S.desc[4 * s + q] : 0ull;
+    if (q == 0) { pos[3 * o] = ok ? S.pos[3 * s] : 0.0f; pos[3 * o + 1] = ok ? S.pos[3 * s + 1] : 0.0f; }
+    else if (q == 1) { pos[3 * o + 2] = ok ? S.pos[3 * s + 2] : 0.0f; if (rows) min_d[o] = ok ? S.min_d[s] : 0.0f; }
+    else if (q == 2) { if (rows) { max_d[o] = ok ? S.max_d[s] : 0.0f; angle[o] = inside ? rows[b].kps[i].angle : 0.0f; } }
+    else valid[o] = (uint8_t)ok;
+}
+
+// has_map_point of orbm_search_by_bow_frames_batch_map (!pMP || pMP->isBad(), src/ORBmatcher.cc:306-312): flags[off + i] = entry i of the key frame's row is
+// a slot that holds a point which is not bad.  grid (ceil(longest row / 256), B), 256 threads
+__global__ void __launch_bounds__(256) k_map_row_flags(const int* __restrict__ kf_slots, int row_cap, const uint8_t* __restrict__ state,
+                                                       const MapRowFlagRec* __restrict__ recs, uint8_t* __restrict__ flags) {
+    const MapRowFlagRec R = recs[blockIdx.y];
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= R.n) return;
+    const int slot = kf_slots[(size_t)R.row * row_cap + i];
+    flags[(size_t)R.off + i] = (uint8_t)(slot >= 0 && state[slot] == kMapPresent);
+}
+
 // ---- key frames made from extracted frames (orbm_keyframe_create_extracted / _rig_extracted) ----------------------------------------------------
 // What the host must know of every frame before it can allocate: out[3 j ..] = features, FeatureVector nodes, FeatureVector entries of record j
 // (the counts are clamped to what the arrays can hold; the host refuses a FeatureVector that does not fit its frame).  grid (ceil(n / 64)), 64 threads

@@ -688,21 +688,66 @@ struct PointRows {
 PointRows last_frame_rows(const OrbmLastFrameBatch* last) {
     return {last->cap_last, last->n, last->pos, last->valid, last->octave, last->angle, last->has_obs, last->desc, nullptr, nullptr};
 }
-// their place in the upload block, n_last | pos | valid | octave | angle | has_obs | descriptors, and the copy into the staging buffer
+// The same rows named by their place in an orbm_map (the .._batch_map calls): the fields come from the store, gathered on the device.  Last frame: slots
+// [B][cap] (LastFrame.mvpMapPoints), the PointRows carries n, octave, angle and has_obs.  Key frame: recs[b] = the key frame's row of slots and its resident
+// keypoints (device addresses), the PointRows carries n = the rows' lengths.  excluded: mvbOutlier / sAlreadyFound, rows `excluded_stride` apart (nullptr = none)
+struct MapRows { MapStore S; const int* slots; const MapRowRec* recs; const uint8_t* excluded; size_t excluded_stride; };
+// their place in the device block and the copy into the staging buffer.  Host-fed rows go up whole: n_last | pos | valid | octave | angle | has_obs |
+// descriptors.  Map-fed rows (src): n_last | excluded | has_obs | slots, octave, angle (last frame) or the row records (key frame) go up, and
+// device_rows() lays pos, valid, descriptors and a key frame's distance limits and angles out BEHIND the upload, where gather() writes them
 struct PointRowsUpload {
-    size_t u_n, u_pos, u_val, u_oct, u_ang, u_obs, u_desc;
-    PointRowsUpload(Bump& u, size_t B1, size_t M1) {
-        u_n = u.take(4 * B1); u_pos = u.take(12 * B1 * M1); u_val = u.take(B1 * M1); u_oct = u.take(4 * B1 * M1); u_ang = u.take(4 * B1 * M1); u_obs = u.take(B1 * M1);
-        u_desc = u.take(32 * B1 * M1);
+    size_t u_n, u_pos = 0, u_val = 0, u_oct = 0, u_ang = 0, u_obs, u_desc = 0, u_mxd = 0, u_exc = 0, u_src = 0;
+    const MapRows* src; bool keyframe;
+    PointRowsUpload(Bump& u, size_t B1, size_t M1, const MapRows* from_map = nullptr, bool kf = false) : src(from_map), keyframe(kf) {
+        u_n = u.take(4 * B1);
+        if (!src) {
+            u_pos = u.take(12 * B1 * M1); u_val = u.take(B1 * M1); u_oct = u.take(4 * B1 * M1); u_ang = u.take(4 * B1 * M1); u_obs = u.take(B1 * M1);
+            u_desc = u.take(32 * B1 * M1);
+            return;
+        }
+        u_exc = u.take(B1 * M1); u_obs = u.take(B1 * M1);
+        if (keyframe) u_src = u.take(sizeof(MapRowRec) * B1);
+        else { u_src = u.take(4 * B1 * M1); u_oct = u.take(4 * B1 * M1); u_ang = u.take(4 * B1 * M1); }
+    }
+    void device_rows(Bump& d, size_t B1, size_t M1) {
+        if (!src) return;
+        u_pos = d.take(12 * B1 * M1); u_val = d.take(B1 * M1); u_desc = d.take(32 * B1 * M1);
+        if (keyframe) { u_oct = d.take(4 * B1 * M1); u_mxd = d.take(4 * B1 * M1); u_ang = d.take(4 * B1 * M1); }
     }
     void stage(uint8_t* hp, const PointRows& last, size_t B1, size_t M1) const {
-        memcpy(hp + u_n, last.n, 4 * B1); memcpy(hp + u_pos, last.pos, 12 * B1 * M1); memcpy(hp + u_val, last.valid, B1 * M1);
-        if (last.octave) memcpy(hp + u_oct, last.octave, 4 * B1 * M1); else memcpy(hp + u_oct, last.min_distance, 4 * B1 * M1);      // (a key frame's octave rows carry mfMinDistance)
-        memcpy(hp + u_ang, last.angle, 4 * B1 * M1);
+        memcpy(hp + u_n, last.n, 4 * B1);
         if (last.has_obs) memcpy(hp + u_obs, last.has_obs, B1 * M1); else memset(hp + u_obs, 1, B1 * M1);
-        memcpy(hp + u_desc, last.desc, 32 * B1 * M1);
+        if (!src) {
+            memcpy(hp + u_pos, last.pos, 12 * B1 * M1); memcpy(hp + u_val, last.valid, B1 * M1);
+            if (last.octave) memcpy(hp + u_oct, last.octave, 4 * B1 * M1); else memcpy(hp + u_oct, last.min_distance, 4 * B1 * M1);      // (a key frame's octave rows carry mfMinDistance)
+            memcpy(hp + u_ang, last.angle, 4 * B1 * M1);
+            memcpy(hp + u_desc, last.desc, 32 * B1 * M1);
+            return;
+        }
+        memset(hp + u_exc, 0, B1 * M1);
+        if (src->excluded) for (size_t b = 0; b < B1; b++) memcpy(hp + u_exc + b * M1, src->excluded + b * src->excluded_stride, (size_t)last.n[b]);
+        if (keyframe) memcpy(hp + u_src, src->recs, sizeof(MapRowRec) * B1);
+        else { memcpy(hp + u_src, src->slots, 4 * B1 * M1); memcpy(hp + u_oct, last.octave, 4 * B1 * M1); memcpy(hp + u_ang, last.angle, 4 * B1 * M1); }
+    }
+    // map-fed rows: k_map_rows_gather behind the upload, on the same stream
+    void gather(rt::stream_t s, uint8_t* dp, int B, int M) const {
+        const dim3 grid((unsigned)((4 * (size_t)M + 255) / 256), B, 1), blk(256, 1, 1);
+        ORBX_LAUNCH(k_map_rows_gather, grid, blk, 0, s, src->S, M, (const int*)(dp + u_n), keyframe ? (const int*)nullptr : (const int*)(dp + u_src),
+                    keyframe ? (const MapRowRec*)(dp + u_src) : (const MapRowRec*)nullptr, (const uint8_t*)(dp + u_exc), dp + u_val, (float*)(dp + u_pos),
+                    (unsigned long long*)(dp + u_desc), (float*)(dp + u_oct), (float*)(dp + u_mxd), (float*)(dp + u_ang));
     }
 };
+// Upload and, for map-fed rows, the gather: the event of the handle's staging block is recorded behind both, and a map-fed call waits for it on the host -
+// once it has passed, the batch holds copies of everything it reads of the map, so the caller may release the map's mutex while the search still runs
+int upload_rows(orbx_extractor* h, const PointRowsUpload& U, size_t u_total, int B, int M) {
+    uint8_t* hp = h->h_lp_in.p; uint8_t* dp = h->d_lp.p;
+    if (rt::copy_h2d(dp, hp, u_total, h->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
+    if (U.src) U.gather(h->s0, dp, B, M);
+    if (rt::event_record(h->ev_lp, h->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
+    h->lp_pending = true;
+    if (U.src && (rt::event_sync(h->ev_lp) || rt::check_launch())) return fail(ORBX_E_DEVICE, "gathering the rows from the map failed: %s", rt::last_error());
+    return ORBX_OK;
+}
 // the fetch of the handle's pending batch: `slots` assignments per frame, `nviews` mbTrackInView arrays (fetched when fetch_views says so)
 int batch_fetch(orbx_extractor* h, size_t slots, const char* what, int* assigned, int cap, int* nmatches, int nviews, bool fetch_views, uint8_t* const* views) {
     rt::set_device(h->device);
@@ -833,9 +878,10 @@ int orbm_search_local_points_batch_maps(orbx_extractor* h, int first, int B, con
 int orbm_points_count(const orbm_points* p) { return p ? p->M : 0; }
 
 namespace {
-// SearchByProjection(CurrentFrame, LastFrame) (keyframe = false) or (CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (keyframe = true) for B frames
+// SearchByProjection(CurrentFrame, LastFrame) (keyframe = false) or (CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (keyframe = true) for B frames.
+// src == nullptr: the rows are the caller's arrays; else they are read from the map (the caller holds its mutex until this returns)
 int projection_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView* cur, const PointRows* last, float th, const uint8_t* forward, const uint8_t* backward,
-                     int check_ori, const uint8_t* occupied, int use_u_right, bool keyframe, int th_accept) {
+                     int check_ori, const uint8_t* occupied, int use_u_right, bool keyframe, int th_accept, const MapRows* src = nullptr) {
     const int M = last->cap;
     if (int rc = frames_check(cur, sizeof *cur, B)) return rc;
     for (int b = 0; b < B; b++) if (last->n[b] < 0 || last->n[b] > M) return fail(ORBX_E_ARG, "frame %d: %d points in %d rows", b, last->n[b], M);
@@ -850,9 +896,11 @@ int projection_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView*
     // upload block: poses | the table of the frames' rows | the rows (n_last .. descriptors) | occupancy | a key frame's mfMaxDistance rows
     Bump u;
     const size_t u_f = u.take(sizeof(FrustumParams) * B1), u_tab = u.take(sizeof(FrameMapRec) * B1);
-    const PointRowsUpload U(u, B1, M1);
-    const size_t u_occ = u.take(occupied ? B1 * C1 : 0), u_mxd = u.take(keyframe ? 4 * B1 * M1 : 0), u_total = u.o;
+    PointRowsUpload U(u, B1, M1, src, keyframe);
+    const size_t u_occ = u.take(occupied ? B1 * C1 : 0), u_mxd_up = u.take(keyframe && !src ? 4 * B1 * M1 : 0), u_total = u.o;
     Bump d(u_total);
+    U.device_rows(d, B1, M1);
+    const size_t u_mxd = src ? U.u_mxd : u_mxd_up;
     const size_t o_ur = d.take(use_u_right ? 0 : 4 * B1 * C1);
     const GridBlock G(d, B1, C1);
     const size_t o_q = d.take(sizeof(AreaQuery) * B1 * M1), o_qs = d.take(4 * B1 * M1), o_qc = d.take(4 * B1 * M1);
@@ -870,10 +918,9 @@ int projection_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView*
     }
     U.stage(hp, *last, B1, M1);
     stage_uniform_table(hp + u_tab, B, M, (const unsigned long long*)(dp + U.u_desc));
-    if (keyframe) memcpy(hp + u_mxd, last->max_distance, 4 * B1 * M1);
+    if (keyframe && !src) memcpy(hp + u_mxd, last->max_distance, 4 * B1 * M1);
     if (occupied) memcpy(hp + u_occ, occupied, B1 * C1);
-    if (rt::copy_h2d(dp, hp, u_total, h->s0) || rt::event_record(h->ev_lp, h->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
-    h->lp_pending = true;
+    if (int rc = upload_rows(h, U, u_total, B, M)) return rc;
     const KeyPointRec* kps = (h->ex_undist_active ? h->d_kps_un.p : h->d_kps.p) + (size_t)first * cap;
     const unsigned long long* fdesc = h->d_desc.p + (size_t)first * cap * 4;
     const int* nper = h->d_nm.p + first;
@@ -1529,12 +1576,13 @@ int orbm_search_by_bow_resident(orbx_extractor* h, int n, orbm_keyframe* const* 
 // ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vpMapPointMatches) (src/ORBmatcher.cc:259-493) for the frames of a batch: frame b of the last
 // extraction (its FeatureVector where orbv_transform_extracted left it) against the resident key frame KFs[b].  Two launches for the whole batch:
 // k_bow_match_resident (the accept loop per vocabulary node) and k_bow_rotation_prune (histogram, three maxima, resets, counts) - nothing but the
-// call-time flags goes up, nothing but the matches comes down.
-int orbm_search_by_bow_frames_batch(orbx_extractor* h, const orbv_vocabulary* v, int first, int B, orbm_keyframe* const* KFs, const uint8_t* const* has_mp1,
-                                    float nnratio, int check_ori, int* const* matches12, int* nmatches_out) {
-    if (!h || !v || B <= 0 || !KFs || !has_mp1 || !matches12) return fail(ORBX_E_ARG, "null");
+// call-time flags goes up, nothing but the matches comes down.  The caller holds the vocabulary's lock until the matches are down: no other handle's run
+// replaces the FeatureVectors under the kernels.  The flags are the caller's arrays (has_mp1) or, with from_map, filled on the device from the key
+// frames' rows in a map (k_map_row_flags) whose mutex the caller holds as well.
+struct BowMapFlags { const int* kf_slots; int row_cap; const uint8_t* state; const int* rows; };
+static int bow_frames_batch_locked(orbx_extractor* h, const orbv_vocabulary* v, int first, int B, orbm_keyframe* const* KFs, const uint8_t* const* has_mp1,
+                                   const BowMapFlags* from_map, float nnratio, int check_ori, int* const* matches12, int* nmatches_out) {
     VocFrameArrays V;
-    const std::unique_lock<std::mutex> vlk = orbv_lock(v);       // until the matches are down: no other handle's run replaces the FeatureVectors under the kernels
     if (orbv_frame_arrays(v, &V) == 0 && V.rig)
         return fail(ORBX_E_ARG, "the last vocabulary transform was a rig transform (orbv_transform_rig_extracted): search its frames with orbm_search_by_bow_rig_batch");
     if (orbv_frame_arrays(v, &V) || V.handle != (const void*)h || V.first != first || V.lastB != B || V.cap != h->kp_total_cap || first < 0 || first + B > h->lastB)
@@ -1559,15 +1607,25 @@ int orbm_search_by_bow_frames_batch(orbx_extractor* h, const orbv_vocabulary* v,
         P.k2.node_of_feat = nullptr; P.k2.N = cap; P.k2.fv_nodes = 0;
         P.k2_nodes_dev = V.nout + 2 * b + 1;
         P.mp1_off = -1; P.elig2_off = -1;
-        if (has_mp1[b] && K1->N > 0) { P.mp1_off = (int)ftotal; ftotal += al16((size_t)K1->N); }
+        if ((from_map || has_mp1[b]) && K1->N > 0) { P.mp1_off = (int)ftotal; ftotal += al16((size_t)K1->N); }
         N1cap = std::max(N1cap, K1->N); maxnodes = std::max(maxnodes, K1->fv_nodes);
     }
-    std::vector<uint8_t> flags(std::max<size_t>(ftotal, 16), 0);
-    for (int b = 0; b < B; b++) if (pairs[b].mp1_off >= 0) memcpy(&flags[pairs[b].mp1_off], has_mp1[b], (size_t)KFs[b]->N);
+    std::vector<uint8_t> flags(from_map ? 0 : std::max<size_t>(ftotal, 16), 0);
+    std::vector<MapRowFlagRec> recs(from_map ? B : 0);
+    for (int b = 0; b < B; b++) {
+        if (from_map) recs[b] = {from_map->rows[b], pairs[b].mp1_off >= 0 ? KFs[b]->N : 0, std::max(pairs[b].mp1_off, 0)};
+        else if (pairs[b].mp1_off >= 0) memcpy(&flags[pairs[b].mp1_off], has_mp1[b], (size_t)KFs[b]->N);
+    }
     Packer pk(h);
-    const size_t pf = pk.add(flags.data(), flags.size()), pp = pk.add(pairs.data(), sizeof(BowPairResident) * pairs.size());
+    size_t pf, pp, pr = 0;
+    if (from_map) { pp = pk.add(pairs.data(), sizeof(BowPairResident) * pairs.size()); pr = pk.add(recs.data(), sizeof(MapRowFlagRec) * recs.size()); pf = pk.room(std::max<size_t>(ftotal, 16)); }
+    else { pf = pk.add(flags.data(), flags.size()); pp = pk.add(pairs.data(), sizeof(BowPairResident) * pairs.size()); }
     const size_t nout = (size_t)B * N1cap, ntot = nout + 4 + (size_t)B;            // matches | status | nmatches
     if (pk.flush() || h->d_si[SI_BEST].ensure(ntot)) return fail(ORBX_E_DEVICE, "upload/allocation failed");
+    if (from_map && ftotal > 0) {
+        dim3 gridf((N1cap + 255) / 256, B, 1), blkf(256, 1, 1);
+        ORBX_LAUNCH(k_map_row_flags, gridf, blkf, 0, h->s0, from_map->kf_slots, from_map->row_cap, from_map->state, pk.dev<MapRowFlagRec>(pr), pk.out<uint8_t>(pf));
+    }
     if (rt::memset_async(h->d_si[SI_BEST].p, 0xFF, sizeof(int) * nout, h->s0) || rt::memset_async(h->d_si[SI_BEST].p + nout, 0, sizeof(int) * (4 + (size_t)B), h->s0))
         return fail(ORBX_E_DEVICE, "memset failed");
     if (h->profile) rt::event_record(h->ev_stage[ST_MATCH][0], h->s0);
@@ -1587,6 +1645,13 @@ int orbm_search_by_bow_frames_batch(orbx_extractor* h, const orbv_vocabulary* v,
         if (nmatches_out) nmatches_out[b] = res[nout + 4 + b];
     }
     return ORBX_OK;
+}
+
+int orbm_search_by_bow_frames_batch(orbx_extractor* h, const orbv_vocabulary* v, int first, int B, orbm_keyframe* const* KFs, const uint8_t* const* has_mp1,
+                                    float nnratio, int check_ori, int* const* matches12, int* nmatches_out) {
+    if (!h || !v || B <= 0 || !KFs || !has_mp1 || !matches12) return fail(ORBX_E_ARG, "null");
+    const std::unique_lock<std::mutex> vlk = orbv_lock(v);
+    return bow_frames_batch_locked(h, v, first, B, KFs, has_mp1, nullptr, nnratio, check_ori, matches12, nmatches_out);
 }
 
 // SearchByBoW(pKF, F) for rig frames (F.Nleft != -1, src/ORBmatcher.cc:259-493 incl. :343-372 and :414-446), P (frame, key frame) pairs: rig frame
@@ -2452,15 +2517,13 @@ int orbm_search_local_points_rig_batch_maps(orbx_extractor* L, int lf, orbx_extr
     return local_points_rig_batch(L, lf, R, rf, B, frames, nullptr, nullptr, nullptr, maps, occupied, cos_limit, th, far_points, th_far, nnratio, want_in_view);
 }
 
-int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* cur, const float* trl,
-                                                  const OrbmLastFrameBatch* last, float th, const uint8_t* forward, const uint8_t* backward, int check_ori,
-                                                  const uint8_t* occupied) {
-    if (L) { L->lp_B = 0; L->lp_rig = false; }
-    if (!L || !cur || !trl || !last) return fail(ORBX_E_ARG, "null");
-    if (last->cap_last <= 0 || !last->n || !last->pos || !last->valid || !last->octave || !last->angle || !last->desc) return fail(ORBX_E_ARG, "bad last-frame batch");
+// orbm_search_by_projection_lastframe_rig_batch (src == nullptr: the rows are the caller's arrays) and .._rig_batch_map (the rows are read from the map,
+// whose mutex the caller holds until this returns); L is not null and has no batch to fetch any more
+static int lastframe_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* cur, const float* trl, const PointRows* last,
+                               const MapRows* src, float th, const uint8_t* forward, const uint8_t* backward, int check_ori, const uint8_t* occupied) {
     int rc = rig_pair_check(L, lf, R, rf, B); if (rc) return rc;
     if ((rc = frames_check(&cur[0].left, sizeof *cur, B))) return rc;
-    const int M = last->cap_last, cap = L->kp_total_cap;
+    const int M = last->cap, cap = L->kp_total_cap;
     for (int b = 0; b < B; b++) if (last->n[b] < 0 || last->n[b] > M) return fail(ORBX_E_ARG, "frame %d: %d points in %d rows", b, last->n[b], M);
     rt::set_device(L->device);
     const size_t B1 = B, M1 = M, C1 = cap, S1 = 2 * C1;
@@ -2471,9 +2534,12 @@ int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orb
     // upload: camera-1 parameters per frame | the table of the frames' rows | n_last | pos | valid | octave | angle | has_obs | descriptors | occupancy [B][2 cap]
     Bump u;
     const size_t u_f = u.take(sizeof(FrustumParams) * B1), u_tab = u.take(sizeof(FrameMapRec) * B1);
-    const PointRowsUpload U(u, B1, M1);
-    const size_t u_occ = u.take(occupied ? B1 * S1 : 0), u_total = u.o;
-    const RigBlock K(u_total, B1, B1 * M1, C1, 0);
+    PointRowsUpload U(u, B1, M1, src, false);
+    const size_t u_occ = u.take(occupied ? B1 * S1 : 0);
+    Bump behind(u.o);
+    U.device_rows(behind, B1, M1);                              // (map-fed: the gathered rows between the upload and the rig block)
+    const size_t u_total = u.o;
+    const RigBlock K(behind.o, B1, B1 * M1, C1, 0);
     const size_t pool = batch_pool(L, B1 * M1 * 32 + 4096);                    // th = 7 .. 15 px windows, two cameras
     if (L->d_lp.ensure(K.pool + pool * 8 + 64) || L->h_lp_in.ensure(u_total + 16) || L->h_lp_out.ensure(al16(K.r.bytes) + 64))
         return fail(ORBX_E_DEVICE, "allocation failed (batched rig last-frame search, %d frames x %d points)", B, M);
@@ -2484,11 +2550,10 @@ int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orb
         fill_frustum_params(&cur[b].left, 0.0f, th, 0, 0.0f, &Fp[b]);
         Fp[b].forward = forward ? forward[b] != 0 : 0; Fp[b].backward = backward ? backward[b] != 0 : 0; Fp[b].debug_flags = L->debug_stereo_flags;
     }
-    U.stage(hp, last_frame_rows(last), B1, M1);
+    U.stage(hp, *last, B1, M1);
     stage_uniform_table(hp + u_tab, B, M, (const unsigned long long*)(dp + U.u_desc));
     if (occupied) memcpy(hp + u_occ, occupied, B1 * S1);
-    if (rt::copy_h2d(dp, hp, u_total, L->s0) || rt::event_record(L->ev_lp, L->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
-    L->lp_pending = true;
+    if ((rc = upload_rows(L, U, u_total, B, M))) return rc;
     if (L != R) { record_done_if_pending(R); rt::stream_wait_event(L->s0, R->ev_done); }
     RigRelPose T; memcpy(T.q, trl, sizeof T.q); memcpy(T.t, trl + 4, sizeof T.t);
     if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][0], L->s0);
@@ -2512,6 +2577,16 @@ int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orb
     return ORBX_OK;
 }
 
+int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* cur, const float* trl,
+                                                  const OrbmLastFrameBatch* last, float th, const uint8_t* forward, const uint8_t* backward, int check_ori,
+                                                  const uint8_t* occupied) {
+    if (L) { L->lp_B = 0; L->lp_rig = false; }
+    if (!L || !cur || !trl || !last) return fail(ORBX_E_ARG, "null");
+    if (last->cap_last <= 0 || !last->n || !last->pos || !last->valid || !last->octave || !last->angle || !last->desc) return fail(ORBX_E_ARG, "bad last-frame batch");
+    const PointRows rows = last_frame_rows(last);
+    return lastframe_rig_batch(L, lf, R, rf, B, cur, trl, &rows, nullptr, th, forward, backward, check_ori, occupied);
+}
+
 int orbm_search_rig_batch_fetch(orbx_extractor* L, int* assigned, int cap, int* nmatches, uint8_t* in_view, uint8_t* in_view_r) {
     if (!L || L->lp_B <= 0 || !L->lp_rig) return fail(ORBX_E_ARG, "no batched rig search is pending");
     if (assigned && cap < 2 * L->kp_total_cap) return fail(ORBX_E_ARG, "assigned rows need %d entries (2 x orbx_max_keypoints)", 2 * L->kp_total_cap);
@@ -2527,14 +2602,18 @@ int orbm_search_rig_batch_fetch(orbx_extractor* L, int* assigned, int cap, int* 
 // changes every frame (Tracking::UpdateLocalPoints rebuilds mvpLocalMapPoints from scratch, src/Tracking.cc:4088-4120).  So the fields live in a store
 // addressed by slot, GetMapPointMatches() of every key frame is a row of slots, and the list of a frame - rows walked in the caller's order, the first
 // occurrence of every good point kept - is built by the kernels k_map_* into an orbm_points set the map owns.  Every call takes the map's mutex and
-// waits for its own work, so handles of different threads (LocalMapping's, Tracking's) may share a map.
+// waits for its own work, so handles of different threads (LocalMapping's, Tracking's) may share a map.  The searches that read their rows from the map
+// (the .._batch_map calls at the end of this file) hold the mutex until the event behind their gather has passed and leave the rest of the search running:
+// what they read of the map is copied by then.
+// Lock order: a call that needs the vocabulary's lock (orbv_lock) and a map's mutex takes the vocabulary's FIRST (orbm_search_by_bow_frames_batch_map is
+// the only one); no call holds two maps' mutexes, and kf_grid_mutex() is never held together with either.
 struct orbm_map {
     int device = 0, slots = 0, kf_rows = 0, kf_row_cap = 0, max_sets = 0;
     mutable std::mutex mu;
     DevBuf<uint8_t> d_store; MapStore S = {};      // [descriptors 32 | pos 12 | normal 12 | min 4 | max 4 | state 1] x slots
     DevBuf<int> d_kf;                              // [kf_rows][kf_row_cap] slots; the rows' lengths stay on the host
     DevBuf<unsigned> d_stamp;                      // [max_sets][slots] first-occurrence stamps, then [max_sets][slots] seen stamps
-    std::vector<int> kf_n;
+    std::vector<int> kf_n; std::vector<uint8_t> kf_set;     // (kf_set: orbm_map_set_keyframe has written the row)
     std::vector<uint8_t> state, mark;              // host mirror of S.state (what orbm_map_select checks); scratch of the duplicate check
     // stamps of one build lie in (base, base + its largest position count]; base then moves up, and everything older reads as stale.  At epoch_limit
     // (orbm_map_debug_epoch: tests lower it) the stamps are cleared and base starts over
@@ -2630,7 +2709,7 @@ int orbm_map_create(orbx_extractor* h, int slots, int kf_rows, int kf_row_cap, i
     uint8_t* p = m->d_store.p;
     m->S.desc = (unsigned long long*)(p + od); m->S.pos = (float*)(p + op); m->S.normal = (float*)(p + on); m->S.min_d = (float*)(p + omn); m->S.max_d = (float*)(p + omx);
     m->S.state = p + ost;
-    m->kf_n.assign(kf_rows, 0); m->state.assign(S1, 0); m->mark.assign(S1, 0);
+    m->kf_n.assign(kf_rows, 0); m->kf_set.assign(kf_rows, 0); m->state.assign(S1, 0); m->mark.assign(S1, 0);
     m->sets.resize(max_sets); m->set_mem.resize(max_sets); m->set_rec.resize(max_sets); m->built.assign(max_sets, 0);
     *out = m;
     return ORBX_OK;
@@ -2689,7 +2768,7 @@ int orbm_map_set_keyframe(orbx_extractor* h, orbm_map* m, int row, int n, const 
         memcpy(m->h_stage.p, slots, 4 * (size_t)n);
         if (rt::copy_h2d(m->d_kf.p + (size_t)row * m->kf_row_cap, m->h_stage.p, 4 * (size_t)n, h->s0) || rt::stream_sync(h->s0)) return fail(ORBX_E_DEVICE, "row %d: upload failed: %s", row, rt::last_error());
     }
-    m->kf_n[row] = n;
+    m->kf_n[row] = n; m->kf_set[row] = 1;
     return ORBX_OK;
 }
 
@@ -2949,6 +3028,100 @@ int orbm_distinctive_descriptors_resident(orbx_extractor* h, int nkf, orbm_keyfr
         if (best_desc) memcpy(best_desc + 32 * (size_t)point_of[r], res + 32 * (size_t)r, 32);
     }
     return ORBX_OK;
+}
+
+}  // extern "C"
+
+// ---- the tracking searches that name their points by slot or by key-frame row of an orbm_map (include/orbx.h) ----
+// Each checks everything it can refuse, takes the map's mutex, and runs the host-fed call's own code with rows that k_map_rows_gather / k_map_row_flags
+// write on the device.
+namespace {
+int map_search_check(const orbx_extractor* h, const orbm_map* m) {
+    if (h->device != m->device) return fail(ORBX_E_ARG, "the map lives on device %d, the handle on device %d", m->device, h->device);
+    return ORBX_OK;
+}
+// LastFrame.mvpMapPoints as slots: n[b] rows of frame b are used, each -1 or a slot of the map (whether it holds a point is the device's to read)
+int last_slots_check(const orbm_map* m, int B, const OrbmLastFrameSlots* last) {
+    if (last->cap_last <= 0 || !last->n || !last->slots || !last->octave || !last->angle) return fail(ORBX_E_ARG, "bad last-frame batch (cap_last, n, slots, octave and angle are required)");
+    for (int b = 0; b < B; b++) {
+        if (last->n[b] < 0 || last->n[b] > last->cap_last) return fail(ORBX_E_ARG, "frame %d: %d points in %d rows", b, last->n[b], last->cap_last);
+        const int* s = last->slots + (size_t)b * last->cap_last;
+        for (int i = 0; i < last->n[b]; i++)
+            if (s[i] < -1 || s[i] >= m->slots) return fail(ORBX_E_ARG, "frame %d, entry %d: slot %d is outside the map's %d slots", b, i, s[i], m->slots);
+    }
+    return ORBX_OK;
+}
+PointRows last_slot_rows(const OrbmLastFrameSlots* last) { return {last->cap_last, last->n, nullptr, nullptr, last->octave, last->angle, last->has_obs, nullptr, nullptr, nullptr}; }
+// the key frame of frame b by its row: set, and as long as the resident key frame it is paired with; *n = its length
+int map_row_check(const orbx_extractor* h, const orbm_map* m, int b, int row, const orbm_keyframe* K, int* n) {
+    if (row < 0 || row >= m->kf_rows) return fail(ORBX_E_ARG, "frame %d: row %d is outside the map's %d key-frame rows", b, row, m->kf_rows);
+    if (!m->kf_set[row]) return fail(ORBX_E_ARG, "frame %d: row %d was never set (orbm_map_set_keyframe)", b, row);
+    if (!K) return fail(ORBX_E_ARG, "frame %d: null key frame", b);
+    if (K->device != h->device) return fail(ORBX_E_ARG, "frame %d: the key frame lives on another device", b);
+    if (K->N != m->kf_n[row]) return fail(ORBX_E_ARG, "frame %d: row %d holds %d entries, its key frame %d features", b, row, m->kf_n[row], K->N);
+    *n = K->N;
+    return ORBX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int orbm_search_by_projection_lastframe_batch_map(orbx_extractor* h, int first, int B, const OrbmFrustumView* cur, orbm_map* map, const OrbmLastFrameSlots* last, float th,
+                                                  const uint8_t* forward, const uint8_t* backward, int check_ori, const uint8_t* occupied, int use_u_right) {
+    if (h) { h->lp_B = 0; h->lp_rig = false; }
+    if (!h || !cur || !map || !last || B <= 0 || first < 0 || first + B > h->lastB) return fail(ORBX_E_ARG, "bad frame range / null");
+    if (int rc = map_search_check(h, map)) return rc;
+    if (int rc = last_slots_check(map, B, last)) return rc;
+    std::lock_guard<std::mutex> lk(map->mu);
+    const MapRows src = {map->S, last->slots, nullptr, last->outlier, (size_t)last->cap_last};
+    const PointRows R = last_slot_rows(last);
+    return projection_batch(h, first, B, cur, &R, th, forward, backward, check_ori, occupied, use_u_right, false, TH_HIGH, &src);
+}
+
+int orbm_search_by_projection_lastframe_rig_batch_map(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* cur, const float* trl,
+                                                      orbm_map* map, const OrbmLastFrameSlots* last, float th, const uint8_t* forward, const uint8_t* backward,
+                                                      int check_ori, const uint8_t* occupied) {
+    if (L) { L->lp_B = 0; L->lp_rig = false; }
+    if (!L || !R || !cur || !trl || !map || !last || B <= 0) return fail(ORBX_E_ARG, "null");
+    if (int rc = map_search_check(L, map)) return rc;
+    if (int rc = last_slots_check(map, B, last)) return rc;
+    std::lock_guard<std::mutex> lk(map->mu);
+    const MapRows src = {map->S, last->slots, nullptr, last->outlier, (size_t)last->cap_last};
+    const PointRows rows = last_slot_rows(last);
+    return lastframe_rig_batch(L, lf, R, rf, B, cur, trl, &rows, &src, th, forward, backward, check_ori, occupied);
+}
+
+int orbm_search_by_projection_keyframe_batch_map(orbx_extractor* h, int first, int B, const OrbmFrustumView* cur, orbm_map* map, const OrbmKeyFrameRows* kf, float th,
+                                                 int orb_dist, int check_ori, const uint8_t* occupied) {
+    if (h) { h->lp_B = 0; h->lp_rig = false; }
+    if (!h || !cur || !map || !kf || B <= 0 || first < 0 || first + B > h->lastB) return fail(ORBX_E_ARG, "bad frame range / null");
+    if (!kf->row || !kf->kfs) return fail(ORBX_E_ARG, "bad key-frame batch (row and kfs are required)");
+    if (orb_dist < 0 || orb_dist > 256) return fail(ORBX_E_ARG, "ORBdist out of range");
+    if (int rc = map_search_check(h, map)) return rc;
+    std::lock_guard<std::mutex> lk(map->mu);
+    std::vector<int> n(B); std::vector<MapRowRec> recs(B);
+    int M = 1;
+    for (int b = 0; b < B; b++) {
+        if (int rc = map_row_check(h, map, b, kf->row[b], kf->kfs[b], &n[b])) return rc;
+        if (kf->found && kf->cap_found < n[b]) return fail(ORBX_E_ARG, "frame %d: cap_found is %d, row %d holds %d entries", b, kf->cap_found, kf->row[b], n[b]);
+        recs[b] = {map->d_kf.p + (size_t)kf->row[b] * map->kf_row_cap, kf->kfs[b]->dev.kps};
+        M = std::max(M, n[b]);
+    }
+    // (has_obs = all, no right-coordinate gate: as orbm_search_by_projection_keyframe_batch)
+    const MapRows src = {map->S, nullptr, recs.data(), kf->found, (size_t)(kf->cap_found > 0 ? kf->cap_found : 0)};
+    const PointRows R = {M, n.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return projection_batch(h, first, B, cur, &R, th, nullptr, nullptr, check_ori, occupied, /*use_u_right*/ 0, true, orb_dist, &src);
+}
+
+int orbm_search_by_bow_frames_batch_map(orbx_extractor* h, const orbv_vocabulary* v, int first, int B, orbm_keyframe* const* KFs, orbm_map* map, const int* rows,
+                                        float nnratio, int check_ori, int* const* matches12, int* nmatches_out) {
+    if (!h || !v || B <= 0 || !KFs || !map || !rows || !matches12) return fail(ORBX_E_ARG, "null");
+    if (int rc = map_search_check(h, map)) return rc;
+    const std::unique_lock<std::mutex> vlk = orbv_lock(v);      // the vocabulary's lock first, then the map's mutex (see struct orbm_map)
+    std::lock_guard<std::mutex> lk(map->mu);                     // the call is blocking: both are held until the matches are down
+    for (int b = 0; b < B; b++) { int n; if (int rc = map_row_check(h, map, b, rows[b], KFs[b], &n)) return rc; }
+    const BowMapFlags F = {map->d_kf.p, map->kf_row_cap, map->S.state, rows};
+    return bow_frames_batch_locked(h, v, first, B, KFs, nullptr, &F, nnratio, check_ori, matches12, nmatches_out);
 }
 
 }  // extern "C"

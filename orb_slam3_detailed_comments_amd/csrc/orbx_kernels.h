@@ -227,6 +227,12 @@ __global__ void k_map_compact(const MapSeg* __restrict__ segs, const int* __rest
                               const MapSetRec* __restrict__ sets);
 __global__ void k_map_scan(const int* __restrict__ frame_chunk0, const int* __restrict__ chunk_cnt, int* __restrict__ chunk_off, int* __restrict__ M_out);
 __global__ void k_map_gather(const MapSetRec* __restrict__ sets, MapStore S, const unsigned* __restrict__ seen_stamp, int nslots, unsigned base);
+// the rows of a projection batch (LastFrame / KeyFrame points) and the flags of a BoW batch, read from the map by slot
+__global__ void k_map_rows_gather(MapStore S, int cap, const int* __restrict__ n, const int* __restrict__ slots, const MapRowRec* __restrict__ rows,
+                                  const uint8_t* __restrict__ excluded, uint8_t* __restrict__ valid, float* __restrict__ pos, unsigned long long* __restrict__ desc,
+                                  float* __restrict__ min_d, float* __restrict__ max_d, float* __restrict__ angle);
+__global__ void k_map_row_flags(const int* __restrict__ kf_slots, int row_cap, const uint8_t* __restrict__ state, const MapRowFlagRec* __restrict__ recs,
+                                uint8_t* __restrict__ flags);
 
 __global__ void k_distinctive(const unsigned long long* __restrict__ desc, const int* __restrict__ start, int P, int* __restrict__ best);
 template <bool kLds>        // instantiated for both forms in k_match.hip

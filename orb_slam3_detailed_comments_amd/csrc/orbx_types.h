@@ -111,6 +111,10 @@ constexpr int kMapChunk = 256;         // visited positions per workgroup of the
 struct MapSeg { int set, row, n, pos0, chunk0; };
 // one point set the map builds: where its M points go, slot by slot (slots: which store slot point j is; seen: 1 = the slot is in set `set`'s seen list)
 struct MapSetRec { int* slots; uint8_t* seen; unsigned long long* desc; float *pos, *normal, *min_d, *max_d; int M, set; };
+// the rows of one frame of a map-fed projection batch (k_map_rows_gather), key-frame form: the key frame's row of slots in the map and the keypoints of
+// the same key frame, resident (pKF->mvKeysUn[i].angle is read); n: the row's length.  flag record of k_map_row_flags: {row, n, offset into the flag block}
+struct MapRowRec { const int* slots; const KeyPointRec* kps; };
+struct MapRowFlagRec { int row, n, off; };
 // one map point of orbm_distinctive_descriptors_resident (k_distinctive_resident): its observations are entries [start, start + n) of the call's
 // observation table (n >= 1: points without observations are not launched); store: the descriptor of its slot in the map's store (nullptr: not written)
 struct DistinctiveRec { unsigned long long* store; int start, n; };

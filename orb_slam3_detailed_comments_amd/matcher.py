@@ -103,17 +103,28 @@ class ORBmatcher:
         ext._lib.check(ext._lib.L.orbm_search_by_bow_resident(ext._h, n, p1, q1, p2, q2, self.mfNNratio, int(frame_version), int(self.mbCheckOrientation), po, nm.ctypes.data))
         return [(int(nm[p]), outs[p][:kf1s[p].N]) for p in range(n)]
 
-    def SearchByBoWFramesBatch(self, ext, voc, kfs, mps, first=0):
+    def SearchByBoWFramesBatch(self, ext, voc, kfs, mps, first=0, resident_map=None, rows=None):
         """ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) for the frames [first, first + len(kfs)) of ext's last extraction on the device
         (orbm_search_by_bow_frames_batch): voc = the ORBVocabulary whose transform_extracted(ext, first, B, levelsup) has run on these frames, kfs[b] = the
         ResidentKeyFrame frame b is searched against, mps[b] = uint8 flags "feature of kfs[b] has a good map point".  Returns [(nmatches, matches12)]
-        with matches12[i] = frame feature matched to key-frame feature i or -1."""
+        with matches12[i] = frame feature matched to key-frame feature i or -1.
+        resident_map, rows (mps = None): the flags are read on the device from rows[b], the row of kfs[b] in the ResidentMap - an entry counts iff its
+        slot is >= 0 and holds a point that is not bad (orbm_search_by_bow_frames_batch_map)."""
         B = len(kfs)
         p1 = (C.c_void_p * max(B, 1))(*[k._kf for k in kfs])
-        a1 = [np.ascontiguousarray(m, np.uint8) for m in mps]
-        q1 = (C.c_void_p * max(B, 1))(*[m.ctypes.data for m in a1])
         outs = [np.full(max(k.N, 1), -1, np.int32) for k in kfs]
         po = (C.c_void_p * max(B, 1))(*[o.ctypes.data for o in outs]); nm = np.zeros(max(B, 1), np.int32)
+        if resident_map is not None or rows is not None:
+            if resident_map is None or rows is None or mps is not None:
+                raise ValueError("the map-fed form takes resident_map and rows, and mps = None")
+            r = np.ascontiguousarray(rows, np.int32)
+            if len(r) != B:
+                raise ValueError("%d rows for %d key frames" % (len(r), B))
+            ext._lib.check(ext._lib.L.orbm_search_by_bow_frames_batch_map(ext._h, voc._v, int(first), B, p1, resident_map._m, r.ctypes.data, self.mfNNratio,
+                                                                          int(self.mbCheckOrientation), po, nm.ctypes.data))
+            return [(int(nm[b]), outs[b][:kfs[b].N]) for b in range(B)]
+        a1 = [np.ascontiguousarray(m, np.uint8) for m in mps]
+        q1 = (C.c_void_p * max(B, 1))(*[m.ctypes.data for m in a1])
         ext._lib.check(ext._lib.L.orbm_search_by_bow_frames_batch(ext._h, voc._v, int(first), B, p1, q1, self.mfNNratio, int(self.mbCheckOrientation), po, nm.ctypes.data))
         return [(int(nm[b]), outs[b][:kfs[b].N]) for b in range(B)]
 
@@ -571,6 +582,19 @@ class LastFrameBatch:
         L.check(L.L.orbm_search_by_projection_lastframe_batch(self.ext._h, int(first), self.B, self.views, C.byref(lb), float(th), ptr(k[7]), ptr(k[8]), int(bool(check_orientation)),
                                                               ptr(k[9]), int(bool(use_u_right))))
 
+    def enqueue_slots(self, resident_map, n, slots, outlier, octave, angle, has_obs, th, forward=None, backward=None, check_orientation=True, occupied=None, use_u_right=True,
+                      first=0):
+        """The same search with the last frame's map points named by slot of a ResidentMap (orbm_search_by_projection_lastframe_batch_map): slots
+        [B, cap_last] (-1 = no map point), outlier [B, cap_last] or None; position and descriptor are gathered from the map on the device (a slot's bad
+        flag is not read).  octave, angle, has_obs and everything else as enqueue()."""
+        self._again = lambda: self.enqueue_slots(resident_map, n, slots, outlier, octave, angle, has_obs, th, forward, backward, check_orientation, occupied, use_u_right, first)
+        lb, k = _last_frame_slots(n, slots, outlier, octave, angle, has_obs, forward, backward, occupied)
+        self._keep = k
+        ptr = lambda a: None if a is None else a.ctypes.data
+        L = self.ext._lib
+        L.check(L.L.orbm_search_by_projection_lastframe_batch_map(self.ext._h, int(first), self.B, self.views, resident_map._m, C.byref(lb), float(th), ptr(k[6]), ptr(k[7]),
+                                                                  int(bool(check_orientation)), ptr(k[8]), int(bool(use_u_right))))
+
     def fetch(self):
         L = self.ext._lib
         rc = L.L.orbm_search_local_points_fetch(self.ext._h, self.assigned.ctypes.data, self.cap, self.nm.ctypes.data, None)
@@ -579,6 +603,24 @@ class LastFrameBatch:
             rc = L.L.orbm_search_local_points_fetch(self.ext._h, self.assigned.ctypes.data, self.cap, self.nm.ctypes.data, None)
         L.check(rc)
         return self.assigned, self.nm
+
+
+class _LastFrameSlots(C.Structure):
+    _fields_ = [("cap_last", C.c_int), ("n", C.c_void_p), ("slots", C.c_void_p), ("outlier", C.c_void_p), ("octave", C.c_void_p), ("angle", C.c_void_p), ("has_obs", C.c_void_p)]
+
+
+class _KeyFrameRows(C.Structure):
+    _fields_ = [("row", C.c_void_p), ("kfs", C.c_void_p), ("cap_found", C.c_int), ("found", C.c_void_p)]
+
+
+def _last_frame_slots(n, slots, outlier, octave, angle, has_obs, forward, backward, occupied):
+    """(OrbmLastFrameSlots, the arrays it points into followed by forward, backward, occupied)"""
+    u8 = lambda a: None if a is None else np.ascontiguousarray(a, np.uint8)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    slots = np.ascontiguousarray(slots, np.int32)
+    k = (np.ascontiguousarray(n, np.int32), slots, u8(outlier), np.ascontiguousarray(octave, np.int32), np.ascontiguousarray(angle, np.float32), u8(has_obs), u8(forward), u8(backward),
+         u8(occupied))
+    return _LastFrameSlots(slots.shape[1], ptr(k[0]), ptr(k[1]), ptr(k[2]), ptr(k[3]), ptr(k[4]), ptr(k[5])), k
 
 
 class _KeyFramePointBatch(C.Structure):
@@ -602,6 +644,24 @@ class KeyFrameBatch(LastFrameBatch):
         kb = _KeyFramePointBatch(capK, ptr(k[0]), ptr(k[1]), ptr(k[2]), ptr(k[3]), ptr(k[4]), ptr(k[5]), ptr(k[6]))
         L = self.ext._lib
         L.check(L.L.orbm_search_by_projection_keyframe_batch(self.ext._h, int(first), self.B, self.views, C.byref(kb), float(th), int(orb_dist), int(bool(check_orientation)), ptr(k[7])))
+
+    def enqueue_rows(self, resident_map, rows, kfs, found, th, orb_dist, check_orientation=True, occupied=None, first=0):
+        """The same search with each frame's candidate key frame named by its row in a ResidentMap (orbm_search_by_projection_keyframe_batch_map): rows [B],
+        kfs[b] = the same key frame as a ResidentKeyFrame (its keypoint angles are read), found [B, cap_found] uint8 (sAlreadyFound) or None.  Position,
+        distance limits and descriptor are gathered from the map on the device; an entry counts iff its slot holds a point that is not bad and is not
+        found.  assigned indexes the row."""
+        self._again = lambda: self.enqueue_rows(resident_map, rows, kfs, found, th, orb_dist, check_orientation, occupied, first)
+        u8 = lambda a: None if a is None else np.ascontiguousarray(a, np.uint8)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        r, fnd, occ = np.ascontiguousarray(rows, np.int32), u8(found), u8(occupied)
+        if len(r) != self.B or len(kfs) != self.B:
+            raise ValueError("%d rows and %d key frames for %d frames" % (len(r), len(kfs), self.B))
+        pk = (C.c_void_p * self.B)(*[k._kf for k in kfs])
+        self._keep = (r, pk, fnd, occ)
+        kr = _KeyFrameRows(ptr(r), C.cast(pk, C.c_void_p), 0 if fnd is None else fnd.shape[1], ptr(fnd))
+        L = self.ext._lib
+        L.check(L.L.orbm_search_by_projection_keyframe_batch_map(self.ext._h, int(first), self.B, self.views, resident_map._m, C.byref(kr), float(th), int(orb_dist),
+                                                                 int(bool(check_orientation)), ptr(occ)))
 
 
 class ResidentPoints:
@@ -964,6 +1024,17 @@ class LastFrameRigBatch:
         L = self.ext._lib
         L.check(L.L.orbm_search_by_projection_lastframe_rig_batch(self.ext._h, self.lf, self.right._h, self.rf, self.B, self.views, self.trl.ctypes.data, C.byref(lb),
                                                                   float(th), ptr(k[7]), ptr(k[8]), int(bool(check_orientation)), ptr(k[9])))
+
+    def enqueue_slots(self, resident_map, n, slots, outlier, octave, angle, has_obs, th, forward=None, backward=None, check_orientation=True, occupied=None):
+        """The same search with the last frame's map points named by slot of a ResidentMap (orbm_search_by_projection_lastframe_rig_batch_map); the
+        arguments as LastFrameBatch.enqueue_slots."""
+        self._again = lambda: self.enqueue_slots(resident_map, n, slots, outlier, octave, angle, has_obs, th, forward, backward, check_orientation, occupied)
+        lb, k = _last_frame_slots(n, slots, outlier, octave, angle, has_obs, forward, backward, occupied)
+        self._keep = k
+        ptr = lambda a: None if a is None else a.ctypes.data
+        L = self.ext._lib
+        L.check(L.L.orbm_search_by_projection_lastframe_rig_batch_map(self.ext._h, self.lf, self.right._h, self.rf, self.B, self.views, self.trl.ctypes.data, resident_map._m,
+                                                                      C.byref(lb), float(th), ptr(k[6]), ptr(k[7]), int(bool(check_orientation)), ptr(k[8])))
 
     def fetch(self):
         L = self.ext._lib
