@@ -735,6 +735,59 @@ __global__ void __launch_bounds__(64) k_sim3_accept(const Sim3TargetRec* __restr
     if (lane == 0) nmatches[blockIdx.x] = nm;
 }
 
+// ---- reference logic that the accept loops and the BoW pruning share ----
+// The best and the second best of one candidate window, as the strict `<` tests of the reference leave them (the FIRST candidate with the smallest distance;
+// the second best is the smallest among the others).  k1 / k2: keys (dist << 16 | position in the window), 0xFFFFFFFF = none; e1 / e2: the entries' packed
+// dist | level << 16; idx: keypoint of the best.  16 bits hold every position and keypoint index: a query's candidates are distinct keypoints of one frame, and
+// a frame has fewer than 65535 (kp_total_cap, refused in orbx_api.cpp: configure)
+struct BestTwo {
+    unsigned k1, k2; int e1, e2, idx;
+    __device__ __forceinline__ bool any() const { return k1 != 0xFFFFFFFFu; }
+};
+// the reference's four variables of a window with a best (any()); no second best: bestDist2 = 256, bestLevel2 = -1
+struct BestTwoLevels { int bestDist, bestLevel, bestDist2, bestLevel2; };
+__device__ __forceinline__ BestTwoLevels unpack(const BestTwo& r) {
+    const bool second = r.k2 != 0xFFFFFFFFu;
+    return {r.e1 & 0xFFFF, r.e1 >> 16, second ? (r.e2 & 0xFFFF) : 256, second ? (r.e2 >> 16) : -1};
+}
+// occupied(keypoint): the candidate is skipped (F.mvpMapPoints[idx] holds a point with observations)
+template <typename Occupied>
+__device__ __forceinline__ BestTwo best_two_scan(const int2* __restrict__ entries, int st, int cnt, const Occupied& occupied) {
+    BestTwo r = {0xFFFFFFFFu, 0xFFFFFFFFu, 0, 0, -1};
+    for (int k = 0; k < cnt; k++) {
+        const int2 e = entries[st + k];
+        if (occupied(e.x)) continue;
+        const unsigned key = ((unsigned)(e.y & 0xFFFF) << 16) | (unsigned)k;
+        if (key < r.k1) { r.k2 = r.k1; r.e2 = r.e1; r.k1 = key; r.e1 = e.y; r.idx = e.x; } else if (key < r.k2) { r.k2 = key; r.e2 = e.y; }
+    }
+    return r;
+}
+// rot = angle1 - angle2 [+ 360], bin = round(rot / 30) (src/ORBmatcher.cc:2118-2125 and :396-412; the reference's 1 / HISTO_LENGTH factor)
+__device__ __forceinline__ int rot_bin(float angle1, float angle2) {
+    float rot = __fsub_rn(angle1, angle2);
+    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
+    const int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
+    return bin == 30 ? 0 : bin;
+}
+// ComputeThreeMaxima (src/ORBmatcher.cc:2335-2377) over the 30 bin sizes, every lane alike: the three fullest bins, the second / third only while they
+// hold at least 10 % of the first (-1: dropped)
+struct ThreeMaxima {
+    int ind1, ind2, ind3;
+    __device__ __forceinline__ bool keeps(int bin) const { return bin == ind1 || bin == ind2 || bin == ind3; }
+};
+__device__ __forceinline__ ThreeMaxima three_maxima(const int* s_hist) {
+    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+    for (int i = 0; i < 30; i++) {
+        const int sz = s_hist[i];
+        if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
+        else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
+        else if (sz > max3) { max3 = sz; ind3 = i; }
+    }
+    if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
+    else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
+    return {ind1, ind2, ind3};
+}
+
 // ORBmatcher::SearchByProjection(Frame, MapPoints) accept loop (src/ORBmatcher.cc:62-166) on the device, one wave per frame of a batch.
 // The loop is sequential over the map points: a keypoint that has received a map point WITH observations is skipped by every later point.
 // Conflicts are rare, so the wave works on 64 consecutive map points at a time, one per lane, optimistically:
@@ -794,24 +847,13 @@ __device__ __forceinline__ void local_accept_body(const FrameMapRec* __restrict_
         if (LASTFRAME && qi < M) events[qi] = -1;
         while (__ballot(pending) != 0ull) {
             // 1. decision against the current occupancy
-            // keys (dist << 16 | position), packed dist | level << 16 of both, index of the best.  16 bits hold every position and keypoint index: a
-            // query's candidates are distinct keypoints of one frame, and a frame has fewer than 65535 (kp_total_cap, refused in orbx_api.cpp: configure)
-            unsigned k1 = 0xFFFFFFFFu, k2 = 0xFFFFFFFFu; int e1 = 0, e2 = 0, idx1 = -1;
-            if (pending) {
-                for (int k = 0; k < cnt; k++) {
-                    const int2 e = entries[st + k];
-                    if ((s_occ[e.x >> 5] >> (e.x & 31)) & 1u) continue;
-                    const unsigned key = ((unsigned)(e.y & 0xFFFF) << 16) | (unsigned)k;
-                    if (key < k1) { k2 = k1; e2 = e1; k1 = key; e1 = e.y; idx1 = e.x; } else if (key < k2) { k2 = key; e2 = e.y; }
-                }
-            }
+            const BestTwo best = best_two_scan(entries, st, pending ? cnt : 0, [&](int i) { return ((s_occ[i >> 5] >> (i & 31)) & 1u) != 0; });
+            const int idx1 = best.idx;
             bool accept = false;
-            if (pending && k1 != 0xFFFFFFFFu) {
-                const int bestDist = e1 & 0xFFFF, bestLevel = e1 >> 16;
-                int bestDist2 = 256, bestLevel2 = -1;
-                if (k2 != 0xFFFFFFFFu) { bestDist2 = e2 & 0xFFFF; bestLevel2 = e2 >> 16; }
+            if (pending && best.any()) {
+                const BestTwoLevels t = unpack(best);
                 // :146-166  bestDist <= TH_HIGH, and not (bestLevel == bestLevel2 && bestDist > mfNNratio * bestDist2);  LastFrame (:2103): bestDist <= TH_HIGH
-                accept = bestDist <= th_high && (LASTFRAME || !(bestLevel == bestLevel2 && (float)bestDist > __fmul_rn(nnratio, (float)bestDist2)));
+                accept = t.bestDist <= th_high && (LASTFRAME || !(t.bestLevel == t.bestLevel2 && (float)t.bestDist > __fmul_rn(nnratio, (float)t.bestDist2)));
             }
             // 2. claims that occupy
             const bool claims = accept && obs;
@@ -835,11 +877,8 @@ __device__ __forceinline__ void local_accept_body(const FrameMapRec* __restrict_
             if (commit && accept) {
                 atomicMax(&assigned[idx1], qi);
                 if (obs) atomicOr(&s_occ[idx1 >> 5], 1u << (idx1 & 31));
-                if (LASTFRAME && check_ori) {                          // rot = angle(last) - angle(current), bin = round(rot / 30) (:2118-2125, the reference's 1 / HISTO_LENGTH factor)
-                    float rot = __fsub_rn(last_angle[qi], cur_kps[idx1].angle);
-                    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                    int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-                    if (bin == 30) bin = 0;
+                if (LASTFRAME && check_ori) {                          // angle(last) - angle(current) (:2118-2125)
+                    const int bin = rot_bin(last_angle[qi], cur_kps[idx1].angle);
                     atomicAdd(&s_hist[bin & 31], 1);
                     events[qi] = idx1 | (bin << 16);
                 }
@@ -851,22 +890,12 @@ __device__ __forceinline__ void local_accept_body(const FrameMapRec* __restrict_
     }
     if (LASTFRAME && check_ori) {
         ORBX_WAVE_SYNC();
-        // ComputeThreeMaxima (src/ORBmatcher.cc:2335-2377) over the 30 bin sizes, every lane alike
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < 30; i++) {
-            const int sz = s_hist[i];
-            if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
-            else if (sz > max3) { max3 = sz; ind3 = i; }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
+        const ThreeMaxima top = three_maxima(s_hist);
         int taken_back = 0;
         for (int qi = lane; qi < M; qi += 64) {
             const int ev = events[qi];
             if (ev < 0) continue;
-            const int bin = ev >> 16;
-            if (bin != ind1 && bin != ind2 && bin != ind3) { assigned[ev & 0xFFFF] = -2; taken_back++; }
+            if (!top.keeps(ev >> 16)) { assigned[ev & 0xFFFF] = -2; taken_back++; }
         }
         nm -= wave_sum(taken_back);
     }
@@ -1011,37 +1040,23 @@ __device__ __forceinline__ void rig_accept_body(const FrameMapRec* __restrict__ 
             int w0 = -1, w1 = -1, w2 = -1, w3 = -1;
             if (pending) {
                 bool end = false;
-                unsigned k1 = 0xFFFFFFFFu, k2 = 0xFFFFFFFFu; int e1 = 0, e2 = 0, best = -1;
-                for (int k = 0; k < c1; k++) {
-                    const int2 e = entries[st1 + k];
-                    if (s_occ[e.x]) continue;
-                    const unsigned key = ((unsigned)(e.y & 0xFFFF) << 16) | (unsigned)k;
-                    if (key < k1) { k2 = k1; e2 = e1; k1 = key; e1 = e.y; best = e.x; } else if (key < k2) { k2 = key; e2 = e.y; }
-                }
-                if (k1 != 0xFFFFFFFFu && (e1 & 0xFFFF) <= th_high) {
-                    const int bestDist = e1 & 0xFFFF, bestLevel = e1 >> 16;
-                    const int bestDist2 = k2 != 0xFFFFFFFFu ? (e2 & 0xFFFF) : 256, bestLevel2 = k2 != 0xFFFFFFFFu ? (e2 >> 16) : -1;
-                    if (!LASTFRAME && bestLevel == bestLevel2 && (float)bestDist > __fmul_rn(nnratio, (float)bestDist2)) end = true;
+                const BestTwo best1 = best_two_scan(entries, st1, c1, [&](int i) { return s_occ[i] != 0; });
+                const BestTwoLevels t1 = unpack(best1);
+                if (best1.any() && t1.bestDist <= th_high) {
+                    if (!LASTFRAME && t1.bestLevel == t1.bestLevel2 && (float)t1.bestDist > __fmul_rn(nnratio, (float)t1.bestDist2)) end = true;
                     else {
-                        w0 = best;
-                        if (!LASTFRAME) { const int j = l2r[best]; if ((unsigned)j < (unsigned)NR) w1 = NL + j; }
+                        w0 = best1.idx;
+                        if (!LASTFRAME) { const int j = l2r[best1.idx]; if ((unsigned)j < (unsigned)NR) w1 = NL + j; }
                     }
                 }
                 if (!end && c2 > 0) {
-                    k1 = 0xFFFFFFFFu; k2 = 0xFFFFFFFFu; e1 = 0; e2 = 0; best = -1;
-                    for (int k = 0; k < c2; k++) {
-                        const int2 e = entries[st2 + k];
-                        const int s = NL + e.x;
-                        if (s == w1 ? obs : s_occ[s] != 0) continue;
-                        const unsigned key = ((unsigned)(e.y & 0xFFFF) << 16) | (unsigned)k;
-                        if (key < k1) { k2 = k1; e2 = e1; k1 = key; e1 = e.y; best = e.x; } else if (key < k2) { k2 = key; e2 = e.y; }
-                    }
-                    if (k1 != 0xFFFFFFFFu && (e1 & 0xFFFF) <= th_high) {
-                        const int bestDist = e1 & 0xFFFF, bestLevel = e1 >> 16;
-                        const int bestDist2 = k2 != 0xFFFFFFFFu ? (e2 & 0xFFFF) : 256, bestLevel2 = k2 != 0xFFFFFFFFu ? (e2 >> 16) : -1;
-                        if (LASTFRAME || !(bestLevel == bestLevel2 && (float)bestDist > __fmul_rn(nnratio, (float)bestDist2))) {
-                            w2 = NL + best;
-                            if (!LASTFRAME) { const int j = r2l[best]; if ((unsigned)j < (unsigned)NL) w3 = j; }
+                    // (this point's own partner write counts as the occupancy it leaves)
+                    const BestTwo best2 = best_two_scan(entries, st2, c2, [&](int i) { const int s = NL + i; return s == w1 ? obs : s_occ[s] != 0; });
+                    const BestTwoLevels t2 = unpack(best2);
+                    if (best2.any() && t2.bestDist <= th_high) {
+                        if (LASTFRAME || !(t2.bestLevel == t2.bestLevel2 && (float)t2.bestDist > __fmul_rn(nnratio, (float)t2.bestDist2))) {
+                            w2 = NL + best2.idx;
+                            if (!LASTFRAME) { const int j = r2l[best2.idx]; if ((unsigned)j < (unsigned)NL) w3 = j; }
                         }
                     }
                 }
@@ -1084,15 +1099,12 @@ __device__ __forceinline__ void rig_accept_body(const FrameMapRec* __restrict__ 
             if (commit) {
 #pragma unroll
                 for (int k = 0; k < 4; k++) if (ws[k] >= 0) s_claim[ws[k]] = 0xFFu;
-                if (LASTFRAME && check_ori) {                          // rot = angle(last) - angle(current), bin = round(rot / 30) (:2118-2125)
+                if (LASTFRAME && check_ori) {                          // angle(last) - angle(current) (:2118-2125)
 #pragma unroll
                     for (int c = 0; c < 2; c++) {
                         const int s = c == 0 ? w0 : w2;
                         if (s < 0) continue;
-                        float rot = __fsub_rn(last_angle[qi], c == 0 ? kps1[s].angle : kps2[s - NL].angle);
-                        if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                        int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-                        if (bin == 30) bin = 0;
+                        const int bin = rot_bin(last_angle[qi], c == 0 ? kps1[s].angle : kps2[s - NL].angle);
                         atomicAdd(&s_hist[bin & 31], 1);
                         events[2 * qi + c] = s * 32 + (bin & 31);
                     }
@@ -1105,22 +1117,12 @@ __device__ __forceinline__ void rig_accept_body(const FrameMapRec* __restrict__ 
     }
     if (LASTFRAME && check_ori) {
         ORBX_WAVE_SYNC();
-        // ComputeThreeMaxima (src/ORBmatcher.cc:2335-2377) over the 30 bin sizes, every lane alike
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < 30; i++) {
-            const int sz = s_hist[i];
-            if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
-            else if (sz > max3) { max3 = sz; ind3 = i; }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
+        const ThreeMaxima top = three_maxima(s_hist);
         int taken_back = 0;
         for (int e = lane; e < 2 * M; e += 64) {
             const int ev = events[e];
             if (ev < 0) continue;
-            const int bin = ev & 31;
-            if (bin != ind1 && bin != ind2 && bin != ind3) { assigned[ev >> 5] = -2; taken_back++; }
+            if (!top.keeps(ev & 31)) { assigned[ev >> 5] = -2; taken_back++; }
         }
         nm -= wave_sum(taken_back);
     }
@@ -1393,29 +1395,14 @@ __device__ __forceinline__ int bow_prune_body(int* __restrict__ m, int n, int ch
     }
     ORBX_WAVE_SYNC();
     if (check_ori) {
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < 30; i++) {
-            const int sz = s_hist[i];
-            if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (sz > max2) { max3 = max2; max2 = sz; ind3 = ind2; ind2 = i; }
-            else if (sz > max3) { max3 = sz; ind3 = i; }
-        }
-        if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-        else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;
+        const ThreeMaxima top = three_maxima(s_hist);
         for (int i = lane; i < n; i += 64) {
             const int j = m[i];
             if (j < 0) continue;
-            const int bin = bin_of(i, j);
-            if (bin != ind1 && bin != ind2 && bin != ind3) { m[i] = -1; nm--; }
+            if (!top.keeps(bin_of(i, j))) { m[i] = -1; nm--; }
         }
     }
     return wave_sum(nm);
-}
-__device__ __forceinline__ int bow_rot_bin(float angle1, float angle2) {
-    float rot = __fsub_rn(angle1, angle2);
-    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-    const int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-    return bin == 30 ? 0 : bin;
 }
 
 // m12 as written by k_bow_match_resident; nmatches[p] = matches left
@@ -1425,7 +1412,7 @@ __global__ void __launch_bounds__(64) k_bow_rotation_prune(const BowPairResident
     const int p = (int)blockIdx.x;
     const BowPairResident& B = pairs[p];
     const int nm = bow_prune_body(m12 + (size_t)p * N1cap, B.k1.N, check_ori, s_hist,
-                                  [&](int i, int j) { return bow_rot_bin(B.k1.kps[i].angle, B.k2.kps[j].angle); });
+                                  [&](int i, int j) { return rot_bin(B.k1.kps[i].angle, B.k2.kps[j].angle); });
     if (lane_id() == 0) nmatches[p] = nm;
 }
 
@@ -1438,7 +1425,7 @@ __global__ void __launch_bounds__(64) k_bow_rotation_prune_rig(const BowPairRig*
     const BowPairRig& R = pairs[p];
     const int nleft = *R.nleft;
     const int nm = bow_prune_body(assigned + (size_t)p * S, S, check_ori, s_hist, [&](int j, int i) {
-        return bow_rot_bin(R.m.k1.kps[i].angle, j < nleft ? R.m.k2.kps[j].angle : R.kps_r[j - nleft].angle);
+        return rot_bin(R.m.k1.kps[i].angle, j < nleft ? R.m.k2.kps[j].angle : R.kps_r[j - nleft].angle);
     });
     if (lane_id() == 0) nmatches[p] = nm;
 }

@@ -680,6 +680,29 @@ struct ResultBlock {
     size_t nmatches, assigned, bytes;
     ResultBlock(size_t B1, size_t slots) : nmatches(16), assigned(16 + al16(4 * B1)), bytes(assigned + 4 * B1 * slots) {}
 };
+
+// ---- the frame of a batched enqueue.  Each of the four (local_points_batch, projection_batch, local_points_rig_batch, lastframe_rig_batch) keeps what is its
+// own - the checks of its arguments, its LDS formula, the rows it uploads, its query launch and its accept launch - around these steps, in this order:
+//   batch_clear      the first line of every entry point: a new enqueue - accepted or refused - ends the previous batch, so a refused call leaves nothing to fetch
+//   every refusal    BEFORE anything is enqueued into the shared block
+//   batch_reserve    waits for the staging block of the previous enqueue, makes room for this one
+//   batch_upload     the staging block goes up (map-fed rows: and are gathered); ev_lp is recorded behind it
+//   camera_searches / rig_searches     grids, the caller's query launch, the window searches into the entry pool
+//   batch_finish     behind the caller's accept launch: the record of the pending batch is assigned, whole
+void batch_clear(orbx_extractor* h) { if (h) h->batch = PendingBatch(); }
+// room for the device block (`pool` candidate entries behind o_pool), u_total bytes of staging and out_bytes of results; false: an allocation failed
+bool batch_reserve(orbx_extractor* h, size_t o_pool, size_t pool, size_t u_total, size_t out_bytes) {
+    if (h->lp_pending) rt::event_sync(h->ev_lp);                // the staging block of the previous enqueue has been consumed
+    if (h->d_lp.ensure(o_pool + pool * 8 + 64) || h->h_lp_in.ensure(u_total + 16) || h->h_lp_out.ensure(out_bytes + 64)) return false;
+    h->lp_pool = pool;
+    return true;
+}
+int batch_finish(orbx_extractor* h, const PendingBatch& enqueued) {
+    if (h->profile) rt::event_record(h->ev_stage[ST_MATCH][1], h->s0);
+    if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
+    h->batch = enqueued;
+    return ORBX_OK;
+}
 // one record per frame of map points seen from somewhere else: the LastFrame's (octave of its keypoint, has_obs) or a key frame's (distance limits)
 struct PointRows {
     int cap; const int* n; const float* pos; const uint8_t* valid; const int* octave; const float* angle; const uint8_t* has_obs; const uint8_t* desc;
@@ -737,35 +760,36 @@ struct PointRowsUpload {
                     (unsigned long long*)(dp + u_desc), (float*)(dp + u_oct), (float*)(dp + u_mxd), (float*)(dp + u_ang));
     }
 };
-// Upload and, for map-fed rows, the gather: the event of the handle's staging block is recorded behind both, and a map-fed call waits for it on the host -
-// once it has passed, the batch holds copies of everything it reads of the map, so the caller may release the map's mutex while the search still runs
-int upload_rows(orbx_extractor* h, const PointRowsUpload& U, size_t u_total, int B, int M) {
+// The staging block goes up; rows that come from the map (U with a src; nullptr: the batch uploads no such rows) are gathered behind it.  The event of the
+// staging block is recorded behind both, and a map-fed call waits for it on the host - once it has passed, the batch holds copies of everything it reads of
+// the map, so the caller may release the map's mutex while the search still runs
+int batch_upload(orbx_extractor* h, size_t u_total, const PointRowsUpload* U, int B, int M) {
     uint8_t* hp = h->h_lp_in.p; uint8_t* dp = h->d_lp.p;
+    const bool map_fed = U && U->src;
     if (rt::copy_h2d(dp, hp, u_total, h->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
-    if (U.src) U.gather(h->s0, dp, B, M);
+    if (map_fed) U->gather(h->s0, dp, B, M);
     if (rt::event_record(h->ev_lp, h->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
     h->lp_pending = true;
-    if (U.src && (rt::event_sync(h->ev_lp) || rt::check_launch())) return fail(ORBX_E_DEVICE, "gathering the rows from the map failed: %s", rt::last_error());
+    if (map_fed && (rt::event_sync(h->ev_lp) || rt::check_launch())) return fail(ORBX_E_DEVICE, "gathering the rows from the map failed: %s", rt::last_error());
     return ORBX_OK;
 }
 // the fetch of the handle's pending batch: `slots` assignments per frame, `nviews` mbTrackInView arrays (fetched when fetch_views says so)
 int batch_fetch(orbx_extractor* h, size_t slots, const char* what, int* assigned, int cap, int* nmatches, int nviews, bool fetch_views, uint8_t* const* views) {
     rt::set_device(h->device);
-    const size_t B1 = h->lp_B, M1 = h->lp_M > 0 ? h->lp_M : 0;
+    const PendingBatch& P = h->batch;
+    const size_t B1 = P.B, M1 = P.M > 0 ? P.M : 0;
     const ResultBlock res(B1, slots);
-    const size_t view_off[2] = {h->lp_o_view, h->lp_o_view_r};
     // mbTrackInView on the device: frame b's M_b bytes at the prefix sum (one set for every frame: [B][M]); the caller's rows are M = max M_b apart
-    const std::vector<int>& Mb = h->lp_maps_M;
     size_t vb = 0;
-    if (fetch_views) for (int m : Mb) vb += (size_t)m;
+    if (fetch_views) for (size_t b = 0; b < B1; b++) vb += (size_t)P.m(b);
     uint8_t* hp = h->h_lp_out.p;
-    int e = rt::copy_d2h(hp, h->d_lp.p + h->lp_o_counter, res.bytes, h->s0);
-    if (fetch_views) for (int v = 0; v < nviews; v++) e |= rt::copy_d2h(hp + al16(res.bytes) + v * vb, h->d_lp.p + view_off[v], vb, h->s0);
+    int e = rt::copy_d2h(hp, h->d_lp.p + P.o_result, res.bytes, h->s0);
+    if (fetch_views) for (int v = 0; v < nviews; v++) e |= rt::copy_d2h(hp + al16(res.bytes) + v * vb, h->d_lp.p + P.o_view[v], vb, h->s0);
     if (e || rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "%s failed: %s", what, rt::last_error());
     h->lp_pending = false;
     if (h->profile) h->stage_ms[ST_MATCH] = rt::event_elapsed_ms(h->ev_stage[ST_MATCH][0], h->ev_stage[ST_MATCH][1]);
     const int total = *(const int*)hp;
-    if (h->lp_M > 0 && (size_t)total > h->lp_pool) {                // the candidate pool was too small: the caller enqueues again (the pool has grown)
+    if (P.M > 0 && (size_t)total > h->lp_pool) {                    // the candidate pool was too small: the caller enqueues again (the pool has grown)
         h->lp_pool = (size_t)total + (size_t)total / 8 + 4096;
         return fail(ORBX_E_CAPACITY, "candidate pool overflow (%d entries): enqueue the search again, the pool has been enlarged", total);
     }
@@ -778,18 +802,54 @@ int batch_fetch(orbx_extractor* h, size_t slots, const char* what, int* assigned
     if (fetch_views) for (int v = 0; v < nviews; v++) if (views[v]) {
         const uint8_t* src = hp + al16(res.bytes) + v * vb;
         for (size_t b = 0; b < B1; b++) {
-            const size_t m = (size_t)Mb[b];
+            const size_t m = (size_t)P.m(b);
             memcpy(views[v] + b * M1, src, m); memset(views[v] + b * M1 + m, 0, M1 - m);
             src += m;
         }
     }
     return ORBX_OK;
 }
+// the device block of a one-camera batch behind the upload (and the rows gathered from a map): uRight of "no stereo" | grid | queries | `extra` bytes of the
+// caller's | q_start | q_count | result | entry pool
+struct CameraBlock {
+    Bump d; size_t ur; GridBlock g; size_t q, extra, qs, qc; ResultBlock r; size_t res, pool;
+    CameraBlock(size_t o, size_t B1, size_t rows, size_t C1, bool no_u_right, size_t extra_bytes)         // rows: query rows of the whole batch
+        : d(o), ur(d.take(no_u_right ? 4 * B1 * C1 : 0)), g(d, B1, C1), r(B1, C1) {
+        q = d.take(sizeof(AreaQuery) * rows); extra = d.take(extra_bytes); qs = d.take(4 * rows); qc = d.take(4 * rows);
+        res = d.take(r.bytes); pool = d.o;
+    }
+};
+// frames [first, first + B) of the handle's last extraction: mvKeysUn, descriptors, counts
+struct FrameRange { const KeyPointRec* kps; const unsigned long long* desc; const int* n; };
+FrameRange frame_range(const orbx_extractor* h, int first) {
+    const size_t o = (size_t)first * h->kp_total_cap;
+    return {(h->ex_undist_active ? h->d_kps_un.p : h->d_kps.p) + o, h->d_desc.p + o * 4, h->d_nm.p + first};
+}
+// the grid of the frames, then the window searches of the query set into the entry pool.  queries(): the launch that writes the queries (and zeroes the pool
+// counter).  maps (device): the table of the frames' query rows and descriptors, M the largest of its M_b.  gate_right: the window search applies the
+// right-coordinate gate, against mvuRight of the extraction or, without use_u_right, against "no stereo"
+template <typename Queries>
+void camera_searches(orbx_extractor* h, const FrameRange& F, int B, int M, const CameraBlock& K, uint8_t* dp, const GridParams& g, const FrameMapRec* maps, size_t pool,
+                     int use_u_right, int gate_right, const Queries& queries) {
+    const int cap = h->kp_total_cap;
+    const float* ur = h->d_uRight.p;
+    if (!use_u_right) { rt::memset_async(dp + K.ur, 0xBF, 4 * (size_t)B * cap, h->s0); ur = (const float*)(dp + K.ur); }   // 0xBFBFBFBF = -1.498...: a negative uRight = monocular keypoint
+    int* d_counter = (int*)(dp + K.res);
+    if (h->profile) rt::event_record(h->ev_stage[ST_MATCH][0], h->s0);
+    {
+        dim3 grid(B, 1, 1), blkg(kGridThreads, 1, 1);
+        ORBX_LAUNCH(k_grid_build, grid, blkg, 0, h->s0, F.kps, 0, g, (int*)(dp + K.g.cof), (int*)(dp + K.g.cst), (int*)(dp + K.g.cit), F.n, cap);
+    }
+    if (M <= 0) { rt::memset_async(d_counter, 0, 16, h->s0); return; }
+    queries();
+    const dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);              // M: of the one set, or the largest of the frames' own
+    ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, h->s0, (const AreaQuery*)(dp + K.q), maps, F.kps, ur, F.desc, g, (const int*)(dp + K.g.cst), (const int*)(dp + K.g.cit),
+                gate_right, d_counter, (int)pool, (int*)(dp + K.qs), (int*)(dp + K.qc), (int2*)(dp + K.pool), cap);
+}
 // orbm_search_local_points_batch (one resident set, `maps` == NULL) and orbm_search_local_points_batch_maps (maps[b] = frame b's own)
 int local_points_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView* frames, const orbm_points* points, const uint8_t* is_bad, const uint8_t* has_obs,
                        const OrbmFrameMap* maps, const uint8_t* occupied, int use_u_right, float cos_limit, float th, int far_points, float th_far, float nnratio,
                        int want_in_view) {
-    if (h) { h->lp_B = 0; h->lp_rig = false; }     // a new enqueue - accepted or refused - ends the previous batch: a refused call leaves nothing to fetch
     if (!h || !frames || (!points && !maps) || B <= 0 || first < 0 || first + B > h->lastB) return fail(ORBX_E_ARG, "bad frame range / null");
     BatchMaps P{points, is_bad, has_obs, maps, B};
     if (int rc = P.plan(h->device)) return rc;
@@ -798,66 +858,39 @@ int local_points_batch(orbx_extractor* h, int first, int B, const OrbmFrustumVie
     rt::set_device(h->device);
     const int M = P.m_max, cap = h->kp_total_cap;
     const size_t B1 = B, C1 = cap, rows = P.rows;
-    // every refusal comes BEFORE anything is enqueued into the shared block, and leaves no batch to fetch
     const size_t smem_accept = 4 * (size_t)((cap + 31) / 32) + 4 * (size_t)cap + 64;
-    if (smem_accept + 1024 > rt::lds_limit(h->device)) { h->lp_B = 0; return fail(ORBX_E_CAPACITY, "%d keypoints per frame need %zu bytes of LDS in the accept kernel", cap, smem_accept); }
-    h->lp_B = 0;                                                // the block is about to be overwritten: a previous, unfetched batch is gone
-    if (h->lp_pending) { rt::event_sync(h->ev_lp); }            // the staging block of the previous enqueue has been consumed
+    if (smem_accept + 1024 > rt::lds_limit(h->device)) return fail(ORBX_E_CAPACITY, "%d keypoints per frame need %zu bytes of LDS in the accept kernel", cap, smem_accept);
     // upload block: poses | the table of per-frame maps | bad flags | has-observation flags | occupancy
     Bump u;
     const size_t u_f = u.take(sizeof(FrustumParams) * B1), u_tab = u.take(P.table_bytes()), u_bad = u.take(P.flags), u_obs = u.take(P.flags),
                  u_occ = u.take(occupied ? B1 * C1 : 0), u_total = u.o;
-    // device block: upload | uRight of "no stereo" | grid | queries | track | level | in_view | q_start | q_count | result | entry pool
-    // (`rows` of each: the sum of the frames' M_b; B x M for one set)
-    Bump d(u_total);
-    const size_t o_ur = d.take(use_u_right ? 0 : 4 * B1 * C1);
-    const GridBlock G(d, B1, C1);
-    const size_t o_q = d.take(sizeof(AreaQuery) * rows), o_trk = d.take(20 * rows), o_lvl = d.take(4 * rows), o_view = d.take(rows), o_qs = d.take(4 * rows), o_qc = d.take(4 * rows);
-    const ResultBlock res(B1, C1);
-    const size_t o_res = d.take(res.bytes), o_pool = d.o;
+    // between the queries and their CSR: track [5 rows] | level [rows] | in_view [rows]   (rows: the sum of the frames' M_b; B x M for one set)
+    Bump t;
+    const size_t o_trk = t.take(20 * rows), o_lvl = t.take(4 * rows), o_view = t.take(rows);
+    const CameraBlock K(u_total, B1, rows, C1, !use_u_right, t.o);
     const size_t pool = batch_pool(h, rows * 6 + 4096);
-    if (h->d_lp.ensure(o_pool + pool * 8 + 64) || h->h_lp_in.ensure(u_total + 16) || h->h_lp_out.ensure(al16(res.bytes) + (want_in_view ? rows : 0) + 64))
+    if (!batch_reserve(h, K.pool, pool, u_total, al16(K.r.bytes) + (want_in_view ? rows : 0)))
         return fail(ORBX_E_DEVICE, "allocation failed (batched local point search, %d frames, %zu points)", B, rows);
-    h->lp_pool = pool;
-    uint8_t* hp = h->h_lp_in.p; uint8_t* dp = h->d_lp.p;
+    uint8_t* hp = h->h_lp_in.p; uint8_t* dp = h->d_lp.p; uint8_t* dx = dp + K.extra;
     FrustumParams* Fp = (FrustumParams*)(hp + u_f);
     for (int b = 0; b < B; b++) fill_frustum_params(&frames[b], cos_limit, th, far_points, th_far, &Fp[b]);
     P.stage(hp + u_tab, hp + u_bad, hp + u_obs);
     if (occupied) memcpy(hp + u_occ, occupied, B1 * C1);
-    if (rt::copy_h2d(dp, hp, u_total, h->s0) || rt::event_record(h->ev_lp, h->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
-    h->lp_pending = true;
-    const KeyPointRec* kps = (h->ex_undist_active ? h->d_kps_un.p : h->d_kps.p) + (size_t)first * cap;     // mvKeysUn
-    const unsigned long long* fdesc = h->d_desc.p + (size_t)first * cap * 4;
-    const int* nper = h->d_nm.p + first;
-    const float* ur = h->d_uRight.p;
-    if (!use_u_right) { rt::memset_async(dp + o_ur, 0xBF, 4 * B1 * C1, h->s0); ur = (const float*)(dp + o_ur); }   // 0xBFBFBFBF = -1.498...: a negative uRight = monocular keypoint
-    const GridParams g = grid_from_view(frames[0]);
-    int* d_counter = (int*)(dp + o_res); int* d_nmatch = (int*)(dp + o_res + res.nmatches); int* d_assigned = (int*)(dp + o_res + res.assigned);
-    if (h->profile) rt::event_record(h->ev_stage[ST_MATCH][0], h->s0);
-    {
-        dim3 grid(B, 1, 1), blkg(kGridThreads, 1, 1);
-        ORBX_LAUNCH(k_grid_build, grid, blkg, 0, h->s0, kps, 0, g, (int*)(dp + G.cof), (int*)(dp + G.cst), (int*)(dp + G.cit), nper, cap);
-    }
+    if (int rc = batch_upload(h, u_total, nullptr, B, M)) return rc;
+    const FrameRange F = frame_range(h, first);
     const FrameMapRec* d_tab = (const FrameMapRec*)(dp + u_tab);
-    const dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);              // M: of the one set, or the largest of the frames' own
-    if (M <= 0) rt::memset_async(d_counter, 0, 16, h->s0);
-    else {
-        ORBX_LAUNCH(k_frustum_batch, grid, blk, 0, h->s0, (const FrustumParams*)(dp + u_f), d_tab, (const uint8_t*)(dp + u_bad), dp + o_view, (float*)(dp + o_trk),
-                    (int*)(dp + o_lvl), (AreaQuery*)(dp + o_q), d_counter);
-        ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, h->s0, (const AreaQuery*)(dp + o_q), d_tab, kps, ur, fdesc, g, (const int*)(dp + G.cst), (const int*)(dp + G.cit), 1,
-                    d_counter, (int)pool, (int*)(dp + o_qs), (int*)(dp + o_qc), (int2*)(dp + o_pool), cap);
-    }
+    camera_searches(h, F, B, M, K, dp, grid_from_view(frames[0]), d_tab, pool, use_u_right, 1, [&]() {
+        const dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
+        ORBX_LAUNCH(k_frustum_batch, grid, blk, 0, h->s0, (const FrustumParams*)(dp + u_f), d_tab, (const uint8_t*)(dp + u_bad), dx + o_view, (float*)(dx + o_trk),
+                    (int*)(dx + o_lvl), (AreaQuery*)(dp + K.q), (int*)(dp + K.res));
+    });
     {
         dim3 grida(B, 1, 1), blka(64, 1, 1);
-        const size_t smem = smem_accept;
         const uint8_t* d_occ = occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr;
-        ORBX_LAUNCH(k_local_accept, grida, blka, smem, h->s0, d_tab, cap, nper, (const int*)(dp + o_qs), (const int*)(dp + o_qc), (const int2*)(dp + o_pool), d_occ,
-                    (const uint8_t*)(dp + u_obs), nnratio, TH_HIGH, d_assigned, d_nmatch);
+        ORBX_LAUNCH(k_local_accept, grida, blka, smem_accept, h->s0, d_tab, cap, F.n, (const int*)(dp + K.qs), (const int*)(dp + K.qc), (const int2*)(dp + K.pool), d_occ,
+                    (const uint8_t*)(dp + u_obs), nnratio, TH_HIGH, (int*)(dp + K.res + K.r.assigned), (int*)(dp + K.res + K.r.nmatches));
     }
-    if (h->profile) rt::event_record(h->ev_stage[ST_MATCH][1], h->s0);
-    if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
-    h->lp_B = B; h->lp_M = M; h->lp_first = first; h->lp_o_counter = o_res; h->lp_o_view = o_view; h->lp_want_view = want_in_view != 0; h->lp_maps_M = P.M;
-    return ORBX_OK;
+    return batch_finish(h, {B, M, P.M, K.res, {K.extra + o_view, 0}, want_in_view != 0, false});
 }
 }  // namespace
 extern "C" {
@@ -865,13 +898,14 @@ extern "C" {
 int orbm_search_local_points_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView* frames, const orbm_points* points, const uint8_t* is_bad,
                                    const uint8_t* has_obs, const uint8_t* occupied, int use_u_right, float cos_limit, float th, int far_points, float th_far,
                                    float nnratio, int want_in_view) {
-    if (h && !points) { h->lp_B = 0; h->lp_rig = false; return fail(ORBX_E_ARG, "bad frame range / null"); }
+    batch_clear(h);
     return local_points_batch(h, first, B, frames, points, is_bad, has_obs, nullptr, occupied, use_u_right, cos_limit, th, far_points, th_far, nnratio, want_in_view);
 }
 
 int orbm_search_local_points_batch_maps(orbx_extractor* h, int first, int B, const OrbmFrustumView* frames, const OrbmFrameMap* maps, const uint8_t* occupied,
                                         int use_u_right, float cos_limit, float th, int far_points, float th_far, float nnratio, int want_in_view) {
-    if (h && !maps) { h->lp_B = 0; h->lp_rig = false; return fail(ORBX_E_ARG, "null table of per-frame maps"); }
+    batch_clear(h);
+    if (h && !maps) return fail(ORBX_E_ARG, "null table of per-frame maps");
     return local_points_batch(h, first, B, frames, nullptr, nullptr, nullptr, maps, occupied, use_u_right, cos_limit, th, far_points, th_far, nnratio, want_in_view);
 }
 
@@ -879,7 +913,8 @@ int orbm_points_count(const orbm_points* p) { return p ? p->M : 0; }
 
 namespace {
 // SearchByProjection(CurrentFrame, LastFrame) (keyframe = false) or (CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (keyframe = true) for B frames.
-// src == nullptr: the rows are the caller's arrays; else they are read from the map (the caller holds its mutex until this returns)
+// src == nullptr: the rows are the caller's arrays; else they are read from the map (the caller holds its mutex until this returns).  The entry points have
+// checked their own arguments (h among them) and cleared the pending batch
 int projection_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView* cur, const PointRows* last, float th, const uint8_t* forward, const uint8_t* backward,
                      int check_ori, const uint8_t* occupied, int use_u_right, bool keyframe, int th_accept, const MapRows* src = nullptr) {
     const int M = last->cap;
@@ -890,26 +925,19 @@ int projection_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView*
     const int cap = h->kp_total_cap;
     const size_t B1 = B, M1 = M, C1 = cap;
     const size_t smem_accept = 4 * (size_t)((cap + 31) / 32) + 4 * (size_t)cap + 4 * (size_t)M + 64;          // grows with cap_last: checked before anything is enqueued
-    if (smem_accept + 1024 > rt::lds_limit(h->device)) { h->lp_B = 0; return fail(ORBX_E_CAPACITY, "%d keypoints and %d last-frame points per frame need %zu bytes of LDS in the accept kernel", cap, M, smem_accept); }
-    h->lp_B = 0;
-    if (h->lp_pending) rt::event_sync(h->ev_lp);
+    if (smem_accept + 1024 > rt::lds_limit(h->device)) return fail(ORBX_E_CAPACITY, "%d keypoints and %d last-frame points per frame need %zu bytes of LDS in the accept kernel", cap, M, smem_accept);
     // upload block: poses | the table of the frames' rows | the rows (n_last .. descriptors) | occupancy | a key frame's mfMaxDistance rows
     Bump u;
     const size_t u_f = u.take(sizeof(FrustumParams) * B1), u_tab = u.take(sizeof(FrameMapRec) * B1);
     PointRowsUpload U(u, B1, M1, src, keyframe);
     const size_t u_occ = u.take(occupied ? B1 * C1 : 0), u_mxd_up = u.take(keyframe && !src ? 4 * B1 * M1 : 0), u_total = u.o;
-    Bump d(u_total);
-    U.device_rows(d, B1, M1);
+    Bump behind(u_total);
+    U.device_rows(behind, B1, M1);                              // (map-fed: the gathered rows between the upload and the camera block)
     const size_t u_mxd = src ? U.u_mxd : u_mxd_up;
-    const size_t o_ur = d.take(use_u_right ? 0 : 4 * B1 * C1);
-    const GridBlock G(d, B1, C1);
-    const size_t o_q = d.take(sizeof(AreaQuery) * B1 * M1), o_qs = d.take(4 * B1 * M1), o_qc = d.take(4 * B1 * M1);
-    const ResultBlock res(B1, C1);
-    const size_t o_res = d.take(res.bytes), o_pool = d.o;
+    const CameraBlock K(behind.o, B1, B1 * M1, C1, !use_u_right, 0);
     const size_t pool = batch_pool(h, B1 * M1 * 16 + 4096);                     // th = 7 .. 15 px windows: a dozen candidates per point
-    if (h->d_lp.ensure(o_pool + pool * 8 + 64) || h->h_lp_in.ensure(u_total + 16) || h->h_lp_out.ensure(al16(res.bytes) + 64))
+    if (!batch_reserve(h, K.pool, pool, u_total, al16(K.r.bytes)))
         return fail(ORBX_E_DEVICE, "allocation failed (batched last-frame search, %d frames x %d points)", B, M);
-    h->lp_pool = pool;
     uint8_t* hp = h->h_lp_in.p; uint8_t* dp = h->d_lp.p;
     FrustumParams* Fp = (FrustumParams*)(hp + u_f);
     for (int b = 0; b < B; b++) {
@@ -920,47 +948,29 @@ int projection_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView*
     stage_uniform_table(hp + u_tab, B, M, (const unsigned long long*)(dp + U.u_desc));
     if (keyframe && !src) memcpy(hp + u_mxd, last->max_distance, 4 * B1 * M1);
     if (occupied) memcpy(hp + u_occ, occupied, B1 * C1);
-    if (int rc = upload_rows(h, U, u_total, B, M)) return rc;
-    const KeyPointRec* kps = (h->ex_undist_active ? h->d_kps_un.p : h->d_kps.p) + (size_t)first * cap;
-    const unsigned long long* fdesc = h->d_desc.p + (size_t)first * cap * 4;
-    const int* nper = h->d_nm.p + first;
-    const float* ur = h->d_uRight.p;
-    if (!use_u_right) { rt::memset_async(dp + o_ur, 0xBF, 4 * B1 * C1, h->s0); ur = (const float*)(dp + o_ur); }
-    const GridParams g = grid_from_view(cur[0]);
-    int* d_counter = (int*)(dp + o_res); int* d_nmatch = (int*)(dp + o_res + res.nmatches); int* d_assigned = (int*)(dp + o_res + res.assigned);
-    if (h->profile) rt::event_record(h->ev_stage[ST_MATCH][0], h->s0);
-    const dim3 blk(256, 1, 1);
+    if (int rc = batch_upload(h, u_total, &U, B, M)) return rc;
+    const FrameRange F = frame_range(h, first);
     const FrameMapRec* d_tab = (const FrameMapRec*)(dp + u_tab);
-    {
-        dim3 grid(B, 1, 1), blkg(kGridThreads, 1, 1);
-        ORBX_LAUNCH(k_grid_build, grid, blkg, 0, h->s0, kps, 0, g, (int*)(dp + G.cof), (int*)(dp + G.cst), (int*)(dp + G.cit), nper, cap);
-    }
-    {
-        dim3 grid((M + 255) / 256, B, 1);
+    camera_searches(h, F, B, M, K, dp, grid_from_view(cur[0]), d_tab, pool, use_u_right, keyframe ? 0 : 1, [&]() {
+        const dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
         if (keyframe) ORBX_LAUNCH(k_keyframe_queries, grid, blk, 0, h->s0, (const FrustumParams*)(dp + u_f), M, (const int*)(dp + U.u_n), (const float*)(dp + U.u_pos),
-                                  (const uint8_t*)(dp + U.u_val), (const float*)(dp + U.u_oct), (const float*)(dp + u_mxd), (AreaQuery*)(dp + o_q), d_counter);
+                                  (const uint8_t*)(dp + U.u_val), (const float*)(dp + U.u_oct), (const float*)(dp + u_mxd), (AreaQuery*)(dp + K.q), (int*)(dp + K.res));
         else ORBX_LAUNCH(k_lastframe_queries, grid, blk, 0, h->s0, (const FrustumParams*)(dp + u_f), M, (const int*)(dp + U.u_n), (const float*)(dp + U.u_pos),
-                         (const uint8_t*)(dp + U.u_val), (const int*)(dp + U.u_oct), (AreaQuery*)(dp + o_q), d_counter);
-        ORBX_LAUNCH(k_area_search_threads, grid, blk, 0, h->s0, (const AreaQuery*)(dp + o_q), d_tab, kps, ur, fdesc, g, (const int*)(dp + G.cst), (const int*)(dp + G.cit),
-                    keyframe ? 0 : 1, d_counter, (int)pool, (int*)(dp + o_qs), (int*)(dp + o_qc), (int2*)(dp + o_pool), cap);
-    }
+                         (const uint8_t*)(dp + U.u_val), (const int*)(dp + U.u_oct), (AreaQuery*)(dp + K.q), (int*)(dp + K.res));
+    });
     {
         dim3 grid(B, 1, 1), blka(64, 1, 1);
-        const size_t smem = smem_accept;
-        ORBX_LAUNCH(k_lastframe_accept, grid, blka, smem, h->s0, d_tab, cap, nper, (const int*)(dp + o_qs), (const int*)(dp + o_qc), (const int2*)(dp + o_pool),
-                    occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr, (const uint8_t*)(dp + U.u_obs), th_accept, d_assigned, d_nmatch,
-                    (const float*)(dp + U.u_ang), kps, check_ori);
+        ORBX_LAUNCH(k_lastframe_accept, grid, blka, smem_accept, h->s0, d_tab, cap, F.n, (const int*)(dp + K.qs), (const int*)(dp + K.qc), (const int2*)(dp + K.pool),
+                    occupied ? (const uint8_t*)(dp + u_occ) : (const uint8_t*)nullptr, (const uint8_t*)(dp + U.u_obs), th_accept, (int*)(dp + K.res + K.r.assigned),
+                    (int*)(dp + K.res + K.r.nmatches), (const float*)(dp + U.u_ang), F.kps, check_ori);
     }
-    if (h->profile) rt::event_record(h->ev_stage[ST_MATCH][1], h->s0);
-    if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
-    h->lp_B = B; h->lp_M = M; h->lp_first = first; h->lp_o_counter = o_res; h->lp_o_view = 0; h->lp_want_view = false;
-    return ORBX_OK;
+    return batch_finish(h, {B, M, {}, K.res, {0, 0}, false, false});
 }
 }  // namespace
 
 int orbm_search_by_projection_lastframe_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView* cur, const OrbmLastFrameBatch* last, float th,
                                               const uint8_t* forward, const uint8_t* backward, int check_ori, const uint8_t* occupied, int use_u_right) {
-    if (h) { h->lp_B = 0; h->lp_rig = false; }
+    batch_clear(h);
     if (!h || !cur || !last || B <= 0 || first < 0 || first + B > h->lastB) return fail(ORBX_E_ARG, "bad frame range / null");
     if (last->cap_last <= 0 || !last->n || !last->pos || !last->valid || !last->octave || !last->angle || !last->desc) return fail(ORBX_E_ARG, "bad last-frame batch");
     const PointRows R = last_frame_rows(last);
@@ -969,7 +979,7 @@ int orbm_search_by_projection_lastframe_batch(orbx_extractor* h, int first, int 
 
 int orbm_search_by_projection_keyframe_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView* cur, const OrbmKeyFramePointBatch* kf, float th, int orb_dist,
                                              int check_ori, const uint8_t* occupied) {
-    if (h) { h->lp_B = 0; h->lp_rig = false; }
+    batch_clear(h);
     if (!h || !cur || !kf || B <= 0 || first < 0 || first + B > h->lastB) return fail(ORBX_E_ARG, "bad frame range / null");
     if (kf->cap_kf <= 0 || !kf->n || !kf->pos || !kf->valid || !kf->min_distance || !kf->max_distance || !kf->angle || !kf->desc) return fail(ORBX_E_ARG, "bad key-frame batch");
     if (orb_dist < 0 || orb_dist > 256) return fail(ORBX_E_ARG, "ORBdist out of range");
@@ -979,10 +989,10 @@ int orbm_search_by_projection_keyframe_batch(orbx_extractor* h, int first, int B
 }
 
 int orbm_search_local_points_fetch(orbx_extractor* h, int* assigned, int cap, int* nmatches, uint8_t* in_view) {
-    if (!h || h->lp_B <= 0) return fail(ORBX_E_ARG, "no batched local point search is pending");
-    if (h->lp_rig) return fail(ORBX_E_ARG, "the pending batch is a rig batch: fetch it with orbm_search_rig_batch_fetch");
+    if (!h || h->batch.B <= 0) return fail(ORBX_E_ARG, "no batched local point search is pending");
+    if (h->batch.rig) return fail(ORBX_E_ARG, "the pending batch is a rig batch: fetch it with orbm_search_rig_batch_fetch");
     if (assigned && cap < h->kp_total_cap) return fail(ORBX_E_CAPACITY, "assigned rows need %d entries", h->kp_total_cap);
-    const bool fetch_view = in_view && h->lp_want_view && h->lp_M > 0;
+    const bool fetch_view = in_view && h->batch.want_view && h->batch.M > 0;
     const int rc = batch_fetch(h, h->kp_total_cap, "batched local point search", assigned, cap, nmatches, 1, fetch_view, &in_view);
     if (rc) return rc;
     if (in_view && !fetch_view) return fail(ORBX_E_ARG, "in_view was not requested at enqueue time");
@@ -2425,6 +2435,8 @@ void rig_searches(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, i
     const int cap = L->kp_total_cap;
     const KeyPointRec* kps1 = L->d_kps.p + (size_t)lf * cap; const KeyPointRec* kps2 = R->d_kps.p + (size_t)rf * cap;
     int* d_counter = (int*)(dp + K.res);
+    if (L != R) { record_done_if_pending(R); rt::stream_wait_event(L->s0, R->ev_done); }      // the right handle's extraction, before L's stream reads its frames
+    if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][0], L->s0);
     {
         dim3 grid(B, 1, 1), blkg(kGridThreads, 1, 1);
         ORBX_LAUNCH(k_grid_build, grid, blkg, 0, L->s0, kps1, 0, g, (int*)(dp + K.g1.cof), (int*)(dp + K.g1.cst), (int*)(dp + K.g1.cit), (const int*)(L->d_nm.p + lf), cap);
@@ -2444,7 +2456,6 @@ size_t rig_accept_lds(int cap, int events) { const size_t S = 2 * (size_t)cap; r
 int local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* frames, const orbm_points* points,
                            const uint8_t* is_bad, const uint8_t* has_obs, const OrbmFrameMap* maps, const uint8_t* occupied, float cos_limit, float th, int far_points,
                            float th_far, float nnratio, int want_in_view) {
-    if (L) { L->lp_B = 0; L->lp_rig = false; }                     // a new enqueue ends the previous batch; a refused one leaves nothing to fetch
     if (!L || !frames || (!points && !maps)) return fail(ORBX_E_ARG, "null");
     int rc = rig_pair_check(L, lf, R, rf, B); if (rc) return rc;
     if ((rc = frames_check(&frames[0].left, sizeof *frames, B))) return rc;
@@ -2455,7 +2466,6 @@ int local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf,
     const size_t B1 = B, C1 = cap, S1 = 2 * C1, rows = P.rows;
     const size_t smem_accept = rig_accept_lds(cap, 0);
     if (smem_accept + 1024 > rt::lds_limit(L->device)) return fail(ORBX_E_CAPACITY, "%d keypoints per camera need %zu bytes of LDS in the rig accept kernel", cap, smem_accept);
-    if (L->lp_pending) rt::event_sync(L->ev_lp);               // the staging block of the previous enqueue has been consumed
     // upload: [camera 1, camera 2] parameters per frame | the table of per-frame maps | bad flags | has-observation flags | occupancy [B][2 cap]
     Bump u;
     const size_t u_f = u.take(sizeof(FrustumParams) * 2 * B1), u_tab = u.take(P.table_bytes()), u_bad = u.take(P.flags), u_obs = u.take(P.flags),
@@ -2464,11 +2474,10 @@ int local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf,
     Bump t;
     const size_t o_trk1 = t.take(20 * rows), o_trk2 = t.take(20 * rows), o_lvl1 = t.take(4 * rows), o_lvl2 = t.take(4 * rows), o_view1 = t.take(rows), o_view2 = t.take(rows);
     const RigBlock K(u_total, B1, rows, C1, t.o);
-    const size_t ox = K.extra, pool = batch_pool(L, rows * 12 + 4096);
-    if (L->d_lp.ensure(K.pool + pool * 8 + 64) || L->h_lp_in.ensure(u_total + 16) || L->h_lp_out.ensure(al16(K.r.bytes) + (want_in_view ? 2 * rows : 0) + 64))
+    const size_t pool = batch_pool(L, rows * 12 + 4096);
+    if (!batch_reserve(L, K.pool, pool, u_total, al16(K.r.bytes) + (want_in_view ? 2 * rows : 0)))
         return fail(ORBX_E_DEVICE, "allocation failed (batched rig local point search, %d frames, %zu points)", B, rows);
-    L->lp_pool = pool;
-    uint8_t* hp = L->h_lp_in.p; uint8_t* dp = L->d_lp.p;
+    uint8_t* hp = L->h_lp_in.p; uint8_t* dp = L->d_lp.p; uint8_t* dx = dp + K.extra;
     FrustumParams* Fp = (FrustumParams*)(hp + u_f);
     for (int b = 0; b < B; b++) {
         fill_frustum_params(&frames[b].left, cos_limit, th, far_points, th_far, &Fp[2 * b]); Fp[2 * b].rig_mode = 1;
@@ -2476,12 +2485,8 @@ int local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf,
     }
     P.stage(hp + u_tab, hp + u_bad, hp + u_obs);
     if (occupied) memcpy(hp + u_occ, occupied, B1 * S1);
-    if (rt::copy_h2d(dp, hp, u_total, L->s0) || rt::event_record(L->ev_lp, L->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
-    L->lp_pending = true;
-    if (L != R) { record_done_if_pending(R); rt::stream_wait_event(L->s0, R->ev_done); }
-    uint8_t* dx = dp + ox;
+    if ((rc = batch_upload(L, u_total, nullptr, B, M))) return rc;
     const FrameMapRec* d_tab = (const FrameMapRec*)(dp + u_tab);
-    if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][0], L->s0);
     rig_searches(L, lf, R, rf, B, M, K, dp, grid_from_view(frames[0].left), d_tab, pool, [&]() {
         dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
         ORBX_LAUNCH(k_frustum_rig, grid, blk, 0, L->s0, (const FrustumParams*)(dp + u_f), d_tab, (const uint8_t*)(dp + u_bad), dx + o_view1, dx + o_view2,
@@ -2495,11 +2500,7 @@ int local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf,
                     (const int*)(dp + K.qc1), (const int*)(dp + K.qs2), (const int*)(dp + K.qc2), (const int2*)(dp + K.pool), d_occ, (const uint8_t*)(dp + u_obs),
                     (const int*)L->d_l2r.p, (const int*)L->d_r2l.p, nnratio, TH_HIGH, (int*)(dp + K.res + K.r.assigned), (int*)(dp + K.res + K.r.nmatches));
     }
-    if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][1], L->s0);
-    if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
-    L->lp_B = B; L->lp_M = M; L->lp_first = lf; L->lp_o_counter = K.res; L->lp_o_view = ox + o_view1; L->lp_o_view_r = ox + o_view2;
-    L->lp_want_view = want_in_view != 0; L->lp_rig = true; L->lp_maps_M = P.M;
-    return ORBX_OK;
+    return batch_finish(L, {B, M, P.M, K.res, {K.extra + o_view1, K.extra + o_view2}, want_in_view != 0, true});
 }
 }  // namespace
 extern "C" {
@@ -2507,18 +2508,19 @@ extern "C" {
 int orbm_search_local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* frames, const orbm_points* points,
                                        const uint8_t* is_bad, const uint8_t* has_obs, const uint8_t* occupied, float cos_limit, float th, int far_points,
                                        float th_far, float nnratio, int want_in_view) {
-    if (L && !points) { L->lp_B = 0; L->lp_rig = false; return fail(ORBX_E_ARG, "null"); }
+    batch_clear(L);
     return local_points_rig_batch(L, lf, R, rf, B, frames, points, is_bad, has_obs, nullptr, occupied, cos_limit, th, far_points, th_far, nnratio, want_in_view);
 }
 
 int orbm_search_local_points_rig_batch_maps(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* frames, const OrbmFrameMap* maps,
                                             const uint8_t* occupied, float cos_limit, float th, int far_points, float th_far, float nnratio, int want_in_view) {
-    if (L && !maps) { L->lp_B = 0; L->lp_rig = false; return fail(ORBX_E_ARG, "null table of per-frame maps"); }
+    batch_clear(L);
+    if (L && !maps) return fail(ORBX_E_ARG, "null table of per-frame maps");
     return local_points_rig_batch(L, lf, R, rf, B, frames, nullptr, nullptr, nullptr, maps, occupied, cos_limit, th, far_points, th_far, nnratio, want_in_view);
 }
 
 // orbm_search_by_projection_lastframe_rig_batch (src == nullptr: the rows are the caller's arrays) and .._rig_batch_map (the rows are read from the map,
-// whose mutex the caller holds until this returns); L is not null and has no batch to fetch any more
+// whose mutex the caller holds until this returns).  The entry points have checked their own arguments (L among them) and cleared the pending batch
 static int lastframe_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* cur, const float* trl, const PointRows* last,
                                const MapRows* src, float th, const uint8_t* forward, const uint8_t* backward, int check_ori, const uint8_t* occupied) {
     int rc = rig_pair_check(L, lf, R, rf, B); if (rc) return rc;
@@ -2530,20 +2532,17 @@ static int lastframe_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int
     const size_t smem_accept = rig_accept_lds(cap, 2 * M);     // grows with cap_last: checked before anything is enqueued
     if (smem_accept + 1024 > rt::lds_limit(L->device))
         return fail(ORBX_E_CAPACITY, "%d keypoints per camera and %d last-frame points per frame need %zu bytes of LDS in the rig accept kernel", cap, M, smem_accept);
-    if (L->lp_pending) rt::event_sync(L->ev_lp);
     // upload: camera-1 parameters per frame | the table of the frames' rows | n_last | pos | valid | octave | angle | has_obs | descriptors | occupancy [B][2 cap]
     Bump u;
     const size_t u_f = u.take(sizeof(FrustumParams) * B1), u_tab = u.take(sizeof(FrameMapRec) * B1);
     PointRowsUpload U(u, B1, M1, src, false);
-    const size_t u_occ = u.take(occupied ? B1 * S1 : 0);
-    Bump behind(u.o);
+    const size_t u_occ = u.take(occupied ? B1 * S1 : 0), u_total = u.o;
+    Bump behind(u_total);
     U.device_rows(behind, B1, M1);                              // (map-fed: the gathered rows between the upload and the rig block)
-    const size_t u_total = u.o;
     const RigBlock K(behind.o, B1, B1 * M1, C1, 0);
     const size_t pool = batch_pool(L, B1 * M1 * 32 + 4096);                    // th = 7 .. 15 px windows, two cameras
-    if (L->d_lp.ensure(K.pool + pool * 8 + 64) || L->h_lp_in.ensure(u_total + 16) || L->h_lp_out.ensure(al16(K.r.bytes) + 64))
+    if (!batch_reserve(L, K.pool, pool, u_total, al16(K.r.bytes)))
         return fail(ORBX_E_DEVICE, "allocation failed (batched rig last-frame search, %d frames x %d points)", B, M);
-    L->lp_pool = pool;
     uint8_t* hp = L->h_lp_in.p; uint8_t* dp = L->d_lp.p;
     FrustumParams* Fp = (FrustumParams*)(hp + u_f);
     for (int b = 0; b < B; b++) {
@@ -2553,10 +2552,8 @@ static int lastframe_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int
     U.stage(hp, *last, B1, M1);
     stage_uniform_table(hp + u_tab, B, M, (const unsigned long long*)(dp + U.u_desc));
     if (occupied) memcpy(hp + u_occ, occupied, B1 * S1);
-    if ((rc = upload_rows(L, U, u_total, B, M))) return rc;
-    if (L != R) { record_done_if_pending(R); rt::stream_wait_event(L->s0, R->ev_done); }
+    if ((rc = batch_upload(L, u_total, &U, B, M))) return rc;
     RigRelPose T; memcpy(T.q, trl, sizeof T.q); memcpy(T.t, trl + 4, sizeof T.t);
-    if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][0], L->s0);
     const FrameMapRec* d_tab = (const FrameMapRec*)(dp + u_tab);
     rig_searches(L, lf, R, rf, B, M, K, dp, grid_from_view(cur[0].left), d_tab, pool, [&]() {
         dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
@@ -2571,16 +2568,13 @@ static int lastframe_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int
                     (int*)(dp + K.res + K.r.nmatches), (const float*)(dp + U.u_ang), (const KeyPointRec*)(L->d_kps.p + (size_t)lf * cap), (const KeyPointRec*)(R->d_kps.p + (size_t)rf * cap),
                     check_ori);
     }
-    if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][1], L->s0);
-    if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
-    L->lp_B = B; L->lp_M = M; L->lp_first = lf; L->lp_o_counter = K.res; L->lp_o_view = 0; L->lp_o_view_r = 0; L->lp_want_view = false; L->lp_rig = true;
-    return ORBX_OK;
+    return batch_finish(L, {B, M, {}, K.res, {0, 0}, false, true});
 }
 
 int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* cur, const float* trl,
                                                   const OrbmLastFrameBatch* last, float th, const uint8_t* forward, const uint8_t* backward, int check_ori,
                                                   const uint8_t* occupied) {
-    if (L) { L->lp_B = 0; L->lp_rig = false; }
+    batch_clear(L);
     if (!L || !cur || !trl || !last) return fail(ORBX_E_ARG, "null");
     if (last->cap_last <= 0 || !last->n || !last->pos || !last->valid || !last->octave || !last->angle || !last->desc) return fail(ORBX_E_ARG, "bad last-frame batch");
     const PointRows rows = last_frame_rows(last);
@@ -2588,11 +2582,11 @@ int orbm_search_by_projection_lastframe_rig_batch(orbx_extractor* L, int lf, orb
 }
 
 int orbm_search_rig_batch_fetch(orbx_extractor* L, int* assigned, int cap, int* nmatches, uint8_t* in_view, uint8_t* in_view_r) {
-    if (!L || L->lp_B <= 0 || !L->lp_rig) return fail(ORBX_E_ARG, "no batched rig search is pending");
+    if (!L || L->batch.B <= 0 || !L->batch.rig) return fail(ORBX_E_ARG, "no batched rig search is pending");
     if (assigned && cap < 2 * L->kp_total_cap) return fail(ORBX_E_ARG, "assigned rows need %d entries (2 x orbx_max_keypoints)", 2 * L->kp_total_cap);
-    if ((in_view || in_view_r) && !L->lp_want_view) return fail(ORBX_E_ARG, "in_view was not requested at enqueue time");
+    if ((in_view || in_view_r) && !L->batch.want_view) return fail(ORBX_E_ARG, "in_view was not requested at enqueue time");
     uint8_t* const views[2] = {in_view, in_view_r};
-    return batch_fetch(L, 2 * (size_t)L->kp_total_cap, "batched rig search", assigned, cap, nmatches, 2, L->lp_want_view && L->lp_M > 0, views);
+    return batch_fetch(L, 2 * (size_t)L->kp_total_cap, "batched rig search", assigned, cap, nmatches, 2, L->batch.want_view && L->batch.M > 0, views);
 }
 
 }  // extern "C"
@@ -3068,7 +3062,7 @@ extern "C" {
 
 int orbm_search_by_projection_lastframe_batch_map(orbx_extractor* h, int first, int B, const OrbmFrustumView* cur, orbm_map* map, const OrbmLastFrameSlots* last, float th,
                                                   const uint8_t* forward, const uint8_t* backward, int check_ori, const uint8_t* occupied, int use_u_right) {
-    if (h) { h->lp_B = 0; h->lp_rig = false; }
+    batch_clear(h);
     if (!h || !cur || !map || !last || B <= 0 || first < 0 || first + B > h->lastB) return fail(ORBX_E_ARG, "bad frame range / null");
     if (int rc = map_search_check(h, map)) return rc;
     if (int rc = last_slots_check(map, B, last)) return rc;
@@ -3081,7 +3075,7 @@ int orbm_search_by_projection_lastframe_batch_map(orbx_extractor* h, int first, 
 int orbm_search_by_projection_lastframe_rig_batch_map(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* cur, const float* trl,
                                                       orbm_map* map, const OrbmLastFrameSlots* last, float th, const uint8_t* forward, const uint8_t* backward,
                                                       int check_ori, const uint8_t* occupied) {
-    if (L) { L->lp_B = 0; L->lp_rig = false; }
+    batch_clear(L);
     if (!L || !R || !cur || !trl || !map || !last || B <= 0) return fail(ORBX_E_ARG, "null");
     if (int rc = map_search_check(L, map)) return rc;
     if (int rc = last_slots_check(map, B, last)) return rc;
@@ -3093,7 +3087,7 @@ int orbm_search_by_projection_lastframe_rig_batch_map(orbx_extractor* L, int lf,
 
 int orbm_search_by_projection_keyframe_batch_map(orbx_extractor* h, int first, int B, const OrbmFrustumView* cur, orbm_map* map, const OrbmKeyFrameRows* kf, float th,
                                                  int orb_dist, int check_ori, const uint8_t* occupied) {
-    if (h) { h->lp_B = 0; h->lp_rig = false; }
+    batch_clear(h);
     if (!h || !cur || !map || !kf || B <= 0 || first < 0 || first + B > h->lastB) return fail(ORBX_E_ARG, "bad frame range / null");
     if (!kf->row || !kf->kfs) return fail(ORBX_E_ARG, "bad key-frame batch (row and kfs are required)");
     if (orb_dist < 0 || orb_dist > 256) return fail(ORBX_E_ARG, "ORBdist out of range");

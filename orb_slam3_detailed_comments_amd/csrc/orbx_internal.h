@@ -59,6 +59,17 @@ namespace orbx {
 int orbv_frame_arrays(const orbv_vocabulary* v, VocFrameArrays* out);      // under orbv_lock(v), held for as long as the arrays are read
 std::unique_lock<std::mutex> orbv_lock(const orbv_vocabulary* v);          // the vocabulary's mutex: its scratch and results are one client's at a time
 void orbv_forget_handle(const orbx_extractor* h);                          // orbx_destroy: no vocabulary names the handle any more
+
+// The one batched tracking search of a handle that waits for its fetch (orbm_search_local_points_fetch, or orbm_search_rig_batch_fetch when rig).  Every
+// enqueue, accepted or refused, ends the previous batch: it clears the record before its first check (batch_clear, orbm_search.cpp) and assigns it whole
+// behind its last launch (batch_finish), so a refused call leaves nothing to fetch and an accepted one sets every field
+struct PendingBatch {
+    int B = 0, M = 0;                            // frames (0: nothing is pending); the largest M_b
+    std::vector<int> M_b;                        // map points per frame; empty: M for every frame
+    size_t o_result = 0, o_view[2] = {0, 0};     // in d_lp: the ResultBlock; mbTrackInView and (rig) mbTrackInViewR, frame b's row at the prefix sum of M_b
+    bool want_view = false, rig = false;         // the views were asked for at enqueue time; a rig batch: [B][2 cap] assignments
+    int m(size_t b) const { return M_b.empty() ? M : M_b[b]; }
+};
 }
 
 struct orbx_extractor {
@@ -141,11 +152,11 @@ struct orbx_extractor {
     bool in_active = false; int in_channels = 1, in_rgb = 1, in_gray_variant = 0, in_geometry = 0, in_out_w = 0, in_out_h = 0, in_tap_w = 0, in_tap_h = 0;
     orbx::DevBuf<float> d_mapx, d_mapy; orbx::DevBuf<orbx::ResizeTap> d_in_xt, d_in_yt; orbx::DevBuf<uint8_t> d_frame;
     orbx::DevBuf<int> d_rowstart, d_rowitems;   // row index of every image's keypoints for the stereo search (k_layout -> k_stereo_match)
-    // batched SearchLocalPoints (orbm_search_local_points_batch): one device block, one pinned result block, the size of the last enqueue
+    // the batched tracking searches (orbm_search_local_points_batch and its kin): one device block, one pinned staging block, one pinned result block
     orbx::DevBuf<uint8_t> d_lp, d_depth_in; orbx::HostBuf<uint8_t> h_lp_in, h_lp_out;
-    size_t lp_pool = 0; int lp_B = 0, lp_M = 0, lp_first = 0; size_t lp_o_counter = 0, lp_o_view = 0; bool lp_pending = false, lp_want_view = false;
-    std::vector<int> lp_maps_M;                      // the pending local-points batch: M_b per frame, mbTrackInView rows at their prefix sums (one set for every frame: all lp_M)
-    bool lp_rig = false; size_t lp_o_view_r = 0;     // the pending batch is a rig batch (orbm_search_rig_batch_fetch; [B][2 cap] assignments, mbTrackInViewR)
+    // these outlive a batch: the entries the candidate pool has grown to; ev_lp (the staging block's upload) has been recorded and nobody has waited for it
+    size_t lp_pool = 0; bool lp_pending = false;
+    orbx::PendingBatch batch;
     // the last orbm_stereo_fisheye with this handle on the left: the right handle, frames and extractions that d_l2r / d_r2l describe (fe_B == 0: none)
     const orbx_extractor* fe_R = nullptr; int fe_lf = 0, fe_rf = 0, fe_B = 0; uint64_t fe_gen_L = 0, fe_gen_R = 0;
     orbx::rt::event_t ev_lp = 0;
