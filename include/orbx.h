@@ -419,7 +419,7 @@ int orbm_stereo_from_depth(orbx_extractor* h, int first, int B, const float* dep
  * received a point is skipped by every later point) runs on the device, one wave per frame.  Asynchronous; orbm_search_local_points_fetch
  * returns assigned [B][cap] (index of the map point written to F.mvpMapPoints[i], -1 = untouched), the reference's return value per frame
  * and - when requested here - mbTrackInView [B][M].  ORBX_E_CAPACITY from the fetch = the candidate pool was too small for this scene: it has
- * been enlarged, enqueue the same call again. */
+ * been enlarged, enqueue the same call again (the refused fetch writes nothing and ends the batch: nothing is pending until then). */
 int orbm_search_local_points_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView* frames, const orbm_points* points,
                                    const uint8_t* is_bad, const uint8_t* has_obs, const uint8_t* occupied, int use_u_right,
                                    float viewing_cos_limit, float th, int far_points, float th_far, float nnratio, int want_in_view);

@@ -791,6 +791,7 @@ int batch_fetch(orbx_extractor* h, size_t slots, const char* what, int* assigned
     const int total = *(const int*)hp;
     if (P.M > 0 && (size_t)total > h->lp_pool) {                    // the candidate pool was too small: the caller enqueues again (the pool has grown)
         h->lp_pool = (size_t)total + (size_t)total / 8 + 4096;
+        batch_clear(h);                                             // its entries were never written: a second fetch, now under the larger lp_pool, would pass them off as results
         return fail(ORBX_E_CAPACITY, "candidate pool overflow (%d entries): enqueue the search again, the pool has been enlarged", total);
     }
     if (nmatches) memcpy(nmatches, hp + res.nmatches, 4 * B1);

@@ -107,12 +107,12 @@ def test_bow_frames_batch_gpu(hip_lib):
     _run(hip_lib, 752, 480, 1200, 8)
 
 
-def test_bow_frames_batch_edge_cases(emu_lib):
+def _edge_cases(lib):
     """Empty and ragged inputs of orbm_search_by_bow_frames_batch: a frame without keypoints (flat image), a key frame none of whose features carries a
     map point, an empty key frame, a key frame whose vocabulary nodes the frame does not have; one key frame serving several frames."""
     rng = np.random.default_rng(5)
     w, h, nf = 376, 240, 400
-    ex = ORBextractor(nf, 1.2, 8, 20, 7, lib=emu_lib)
+    ex = ORBextractor(nf, 1.2, 8, 20, 7, lib=lib)
     imgs = np.stack([np.full((h, w), 90, np.uint8), synth.corner_field(w, h, seed=31, nrect=900), synth.corner_field(w, h, seed=31, nrect=900),
                      synth.corner_field(w, h, seed=32, nrect=900)])
     res = ex.extract_batch(imgs)
@@ -152,3 +152,12 @@ def test_bow_frames_batch_edge_cases(emu_lib):
     again = m.SearchByBoWFramesBatch(ex, voc, [full, full, full, empty], [np.ones(full.N, np.uint8), np.zeros(full.N, np.uint8), np.ones(full.N, np.uint8), np.zeros(1, np.uint8)])
     assert again[3][0] == 0 and again[2][0] > 0.5 * full.N               # frame 2 is the key frame's own image again
     full.close(); empty.close(); voc.close(); ex.close()
+
+
+def test_bow_frames_batch_edge_cases(emu_lib):
+    _edge_cases(emu_lib)
+
+
+@pytest.mark.gpu
+def test_bow_frames_batch_edge_cases_gpu(hip_lib):
+    _edge_cases(hip_lib)

@@ -41,10 +41,12 @@ def test_kfdb_kl_refused(emu_lib, tmp_path):
     with pytest.raises(OrbxError) as e:
         KeyFrameDatabase(voc, ex)
     assert e.value.code == ORBX_E_ARG and "KL" in str(e.value)
+    voc.close(); ex.close()                 # (the caught exception keeps this frame, and with it the handles, until the next collection)
 
 
-def test_kfdb_edge_cases_emulated(emu_lib, tmp_path):
-    ex, voc, db, score, desc, rng = make(emu_lib, tmp_path, 0)
+def kfdb_edge_cases(lib, tmp_path):
+    """duplicate adds, erases of middle / absent / last keys, exclusions, an empty query and one that shares nothing, capacity overflow, clearMap, clear"""
+    ex, voc, db, score, desc, rng = make(lib, tmp_path, 0)
     nw = voc.size()
     ref = kw.RestatedDB(nw)
     a = (np.array([1, 5, 9, 20], np.uint32), np.array([0.1, 0.2, 0.3, 0.4]))
@@ -93,11 +95,16 @@ def test_kfdb_edge_cases_emulated(emu_lib, tmp_path):
         db.add(9, np.array([3, 2], np.uint32), np.array([0.5, 0.5]))
     with pytest.raises(OrbxError):
         db.add(9, np.array([nw], np.uint32), np.array([0.5]))
+    db.close(); voc.close(); ex.close()     # (the caught exceptions keep this frame, and with it the handles, until the next collection)
 
 
-def test_kfdb_min_common_every_max_emulated(emu_lib, tmp_path):
+def test_kfdb_edge_cases_emulated(emu_lib, tmp_path):
+    kfdb_edge_cases(emu_lib, tmp_path)
+
+
+def kfdb_min_common_every_max(lib, tmp_path):
     """minCommonWords = (int)(maxCommonWords * 0.8f) for every maximum 1 .. 5000: a key added m times shares m words with a one-word query"""
-    ex, voc, db, score, desc, rng = make(emu_lib, tmp_path, 0)
+    ex, voc, db, score, desc, rng = make(lib, tmp_path, 0)
     # one key per m would need 12.5 M adds; instead a key with m words and a query of those m words
     ids = np.arange(min(voc.size(), 5000), dtype=np.uint32)
     assert len(ids) >= 900
@@ -117,6 +124,10 @@ def test_kfdb_min_common_every_max_emulated(emu_lib, tmp_path):
             db.add(2, *one); added += 1
         r = db.query([one])[0]
         assert r["words"].tolist() == [m] and r["min_common"] == int(np.float32(m) * np.float32(0.8)), m
+
+
+def test_kfdb_min_common_every_max_emulated(emu_lib, tmp_path):
+    kfdb_min_common_every_max(emu_lib, tmp_path)
 
 
 def test_kfdb_extracted_emulated(emu_lib, tmp_path):
@@ -144,6 +155,7 @@ def test_kfdb_extracted_emulated(emu_lib, tmp_path):
         assert got[q]["score"].tobytes() == host[q]["score"].tobytes()
     with pytest.raises(OrbxError):
         db.query_extracted(ex, 2, 3)
+    db.close(); voc.close(); ex.close()
 
 
 def test_kfdb_numpy_restatement_emulated(emu_lib, tmp_path):

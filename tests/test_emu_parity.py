@@ -139,9 +139,9 @@ def test_golden_fixture(emu_lib):
     assert mono == int(g["mono_b"]) and k.tobytes() == g["kps_b"].tobytes() and np.array_equal(d, g["desc_b"])
 
 
-def test_handle_reuse_across_sizes_and_batches(emu_lib):
+def _handle_reuse_case(lib):
     """One handle, changing resolution and batch size between calls: tables and device buffers are rebuilt transparently."""
-    ex = ORBextractor(300, 1.2, 8, 20, 7, lib=emu_lib)
+    ex = ORBextractor(300, 1.2, 8, 20, 7, lib=lib)
     a = synth.corner_field(376, 240, seed=40, nrect=800); b = synth.corner_field(320, 300, seed=41, nrect=800)
     ra1 = ex(a)
     rb = ex.extract_batch(np.stack([b, b[::-1].copy(), b]))
@@ -156,16 +156,20 @@ def test_handle_reuse_across_sizes_and_batches(emu_lib):
     cap = ex.max_keypoints()
     from orb_slam3_detailed_comments_amd._lib import KP_DTYPE
     kps = np.zeros(cap, KP_DTYPE); desc = np.zeros((cap, 32), np.uint8); n = C.c_int(); m = C.c_int()
-    emu_lib.check(emu_lib.L.orbx_extract(ex._h, roi.ctypes.data, 376, 240, 500, 0, 0, kps.ctypes.data, desc.ctypes.data, cap, C.byref(n), C.byref(m)))
+    lib.check(lib.L.orbx_extract(ex._h, roi.ctypes.data, 376, 240, 500, 0, 0, kps.ctypes.data, desc.ctypes.data, cap, C.byref(n), C.byref(m)))
     assert m.value == ra1[0] and ol.kps_equal(kps[:n.value], ra1[1]) and np.array_equal(desc[:n.value], ra1[2])
 
 
-def test_unusual_pyramids_with_stereo(emu_lib):
+def test_handle_reuse_across_sizes_and_batches(emu_lib):
+    _handle_reuse_case(emu_lib)
+
+
+def _unusual_pyramids_case(lib):
     """Pyramids the reference accepts but nobody ships: 11 levels (stereo row bands up to 25 rows tall), 3 levels at scale 2, one level."""
     from orb_slam3_detailed_comments_amd import matcher as M
     L, R = synth.stereo_pair(752, 480, seed=3)
     for (nf, sf, nl) in [(800, 1.2, 11), (300, 2.0, 3), (2000, 1.3, 1)]:
-        ex = ORBextractor(nf, sf, nl, 20, 7, lib=emu_lib)
+        ex = ORBextractor(nf, sf, nl, 20, 7, lib=lib)
         res = ex.extract_batch(np.stack([L, R]), (0, 0))
         oL = ol.OracleExtractor(nf, sf, nl, 20, 7); oR = ol.OracleExtractor(nf, sf, nl, 20, 7)
         eL = oL.extract(L); eR = oR.extract(R)
@@ -178,15 +182,26 @@ def test_unusual_pyramids_with_stereo(emu_lib):
         assert no > 20
 
 
-@pytest.mark.parametrize("ini,mn", [(0, 0), (1, 1), (20, 0), (7, 20), (2, 1), (130, 128), (254, 1), (255, 255), (90, 89)])
-def test_extreme_fast_thresholds(emu_lib, ini, mn):
+def test_unusual_pyramids_with_stereo(emu_lib):
+    _unusual_pyramids_case(emu_lib)
+
+
+EXTREME_THRESHOLDS = [(0, 0), (1, 1), (20, 0), (7, 20), (2, 1), (130, 128), (254, 1), (255, 255), (90, 89)]
+
+
+def _extreme_fast_thresholds_case(lib, ini, mn):
     """thresholds at the ends of the byte range, minTh above iniTh, threshold 0 (every pixel takes both polarities in k_fast_cells) - against the
     oracle and the reference build"""
     for img in (synth.uniform_noise(200, 180, seed=77), synth.corner_field(260, 200, seed=78, nrect=300)):
-        got = ORBextractor(200, 1.2, 4, ini, mn, lib=emu_lib)(img)
+        got = ORBextractor(200, 1.2, 4, ini, mn, lib=lib)(img)
         assert _same(got, ol.OracleExtractor(200, 1.2, 4, ini, mn, 0).extract(img)), (ini, mn)
         if ol.reference() is not None:
             assert _same(got, ol.ReferenceExtractor(200, 1.2, 4, ini, mn, 0).extract(img)), (ini, mn)
+
+
+@pytest.mark.parametrize("ini,mn", EXTREME_THRESHOLDS)
+def test_extreme_fast_thresholds(emu_lib, ini, mn):
+    _extreme_fast_thresholds_case(emu_lib, ini, mn)
 
 
 def _zero_copy_case(lib, w, h, nf):

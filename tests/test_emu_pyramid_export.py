@@ -51,21 +51,29 @@ def test_edge_wider_than_the_smallest_level(emu_lib):
     ex.close()
 
 
-def test_other_scale_and_levels(emu_lib):
+def other_scale_and_levels(lib):
     """scale 2.0 (two levels: what a 376 x 240 image takes down to its 35-px cell grid), 1.5 with four and a single level (no pyramid at all)."""
     for scale, nl in ((2.0, 2), (1.5, 4), (1.2, 1)):
-        ex = _ex(emu_lib, 300, scale=scale, nlevels=nl, edge=40)
+        ex = _ex(lib, 300, scale=scale, nlevels=nl, edge=40)
         ex.extract_batch(np.stack([synth.corner_field(376, 240, seed=s, nrect=600) for s in (1, 2)]))
         pc.check_export(ex, 2, 40)
         ex.close()
 
 
-@pytest.mark.parametrize("depth", [1, 2, 3])
-def test_ring_keeps_depth_minus_one_older_exports(emu_lib, depth):
-    ex = _ex(emu_lib, depth=depth)
+def test_other_scale_and_levels(emu_lib):
+    other_scale_and_levels(emu_lib)
+
+
+def ring_keeps_older_exports(lib, depth):
+    ex = _ex(lib, depth=depth)
     seq = [np.stack([synth.corner_field(376, 240, seed=10 * k + b, nrect=700) for b in range(2)]) for k in range(depth + 3)]
     pc.ring_check(ex, seq, 19, depth, 2)
     ex.close()
+
+
+@pytest.mark.parametrize("depth", [1, 2, 3])
+def test_ring_keeps_depth_minus_one_older_exports(emu_lib, depth):
+    ring_keeps_older_exports(emu_lib, depth)
 
 
 def test_stale_or_out_of_range_image_is_refused(emu_lib):
@@ -103,8 +111,8 @@ def test_bad_settings_are_refused(emu_lib):
     ex.close()
 
 
-def test_toggle_reconfigure_and_batch_growth(emu_lib):
-    ex = _ex(emu_lib)
+def toggle_reconfigure_and_batch_growth(lib):
+    ex = _ex(lib)
     a = np.stack([synth.corner_field(376, 240, seed=s, nrect=700) for s in (1, 2)])
     ex.extract_batch(a); pc.check_export(ex, 2, 19)
     ex.pyramid_export(0); ex.extract_batch(a)
@@ -117,10 +125,14 @@ def test_toggle_reconfigure_and_batch_growth(emu_lib):
     ex.close()
 
 
-def test_input_pre_step_and_on_device_frames(emu_lib):
+def test_toggle_reconfigure_and_batch_growth(emu_lib):
+    toggle_reconfigure_and_batch_growth(emu_lib)
+
+
+def input_pre_step_and_on_device_frames(lib):
     rng = np.random.default_rng(3)
     # colour frames resized by the input pre-step
-    ex = _ex(emu_lib)
+    ex = _ex(lib)
     ex.set_input(channels=3, rgb=False, resize=(376, 240))
     col = np.stack([np.repeat(synth.corner_field(400, 260, seed=s, nrect=700)[:, :, None], 3, axis=2) for s in (1, 2)])
     col = np.clip(col.astype(np.int16) + rng.integers(-3, 4, col.shape), 0, 255).astype(np.uint8)
@@ -131,7 +143,7 @@ def test_input_pre_step_and_on_device_frames(emu_lib):
     ex.extract_batch(np.stack([synth.corner_field(376, 240, seed=s, nrect=700) for s in (3, 4)])); pc.check_export(ex, 2, 19)
     ex.close()
     # frames written straight into level 0 (orbx_input_buffer / on_device = 1)
-    ex = _ex(emu_lib)
+    ex = _ex(lib)
     imgs = np.stack([synth.corner_field(376, 240, seed=s, nrect=700) for s in (5, 6, 7)])
     p, shape, st, ist = ex.input_upload(imgs)
     ex.enqueue(None, device_ptr=p, shape=shape, stride=st, image_stride=ist); ex.fetch()
@@ -139,6 +151,10 @@ def test_input_pre_step_and_on_device_frames(emu_lib):
     for b in range(3):
         assert np.array_equal(exp[b][0][19:-19, 19:-19], imgs[b])
     ex.close()
+
+
+def test_input_pre_step_and_on_device_frames(emu_lib):
+    input_pre_step_and_on_device_frames(emu_lib)
 
 
 def test_live_resources_return_to_zero(emu_lib):
@@ -165,30 +181,38 @@ def test_live_resources_return_to_zero(emu_lib):
     assert np.array_equal(pc.live(emu_lib), base)
 
 
-def test_export_off_by_default_allocates_nothing(emu_lib):
+def export_off_by_default_allocates_nothing(lib):
     """The default (export off): no stream, event or buffer of the export, and nothing to hand out."""
-    base = pc.live(emu_lib)
-    ex = _ex(emu_lib, edge=0)
+    base = pc.live(lib)
+    ex = _ex(lib, edge=0)
     img = np.stack([synth.corner_field(376, 240, seed=s, nrect=700) for s in (1, 2)])
     ex.extract_batch(img)
-    plain = pc.live(emu_lib) - base
-    assert emu_lib.L.orbx_pyramid_exported(ex._h, 0, None, None, None, None, None) != 0
+    plain = pc.live(lib) - base
+    assert lib.L.orbx_pyramid_exported(ex._h, 0, None, None, None, None, None) != 0
     ex.close()
-    ex = _ex(emu_lib, edge=19)
+    ex = _ex(lib, edge=19)
     ex.extract_batch(img)
-    exporting = pc.live(emu_lib) - base
+    exporting = pc.live(lib) - base
     ex.close()
     assert exporting[0] == plain[0] + 1 and exporting[1] == plain[1] + 2       # device staging, two pinned slots
     assert exporting[2] == plain[2] + 1 and exporting[3] == plain[3] + 4
 
 
-def test_exported_arrays_are_views_of_the_slot(emu_lib):
-    ex = _ex(emu_lib)
+def test_export_off_by_default_allocates_nothing(emu_lib):
+    export_off_by_default_allocates_nothing(emu_lib)
+
+
+def exported_arrays_are_views_of_the_slot(lib):
+    ex = _ex(lib)
     ex.extract_batch(synth.corner_field(376, 240, seed=1, nrect=700)[None])
     v = ex.exported_pyramid(0)
     base = C.c_void_p(); off = np.zeros(8, np.uint64); step = np.zeros(8, np.int32)
-    emu_lib.check(emu_lib.L.orbx_pyramid_exported(ex._h, 0, C.byref(base), off.ctypes.data, step.ctypes.data, None, None))
+    lib.check(lib.L.orbx_pyramid_exported(ex._h, 0, C.byref(base), off.ctypes.data, step.ctypes.data, None, None))
     for l in range(8):
         assert v[l].ctypes.data == base.value + int(off[l]) and v[l].strides == (int(step[l]), 1)
         assert int(off[l]) % 64 == 0 and int(step[l]) % 16 == 0
     ex.close()
+
+
+def test_exported_arrays_are_views_of_the_slot(emu_lib):
+    exported_arrays_are_views_of_the_slot(emu_lib)

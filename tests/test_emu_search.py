@@ -169,9 +169,10 @@ def test_guided_searches_emulated(emu_lib):
     run_all(emu_lib, 480, 360, 500, 1500, seeds=(0, 1))
 
 
-def test_degenerate_views(emu_lib):
+def degenerate_views(lib):
+    """no map point in view, and an empty frame: searches whose window launch has nothing to do"""
     from orb_slam3_detailed_comments_amd import views
-    ex = ORBextractor(500, 1.2, 8, 20, 7, lib=emu_lib)
+    ex = ORBextractor(500, 1.2, 8, 20, 7, lib=lib)
     rng = np.random.default_rng(9)
     img = synth.corner_field(376, 240, seed=10, nrect=800)
     fv, k, d, u, scales = sc.frame_from_image(img, 300, rng, with_uright=False)
@@ -184,6 +185,10 @@ def test_degenerate_views(emu_lib):
     mps2 = sc.map_points_for_frame(k, d, None, scales, 100, rng, 376, 240)
     n, a = M.ORBmatcher(0.8).SearchByProjection(ex, empty, mps2, 3.0)
     assert n == 0 and len(a) == 0
+
+
+def test_degenerate_views(emu_lib):
+    degenerate_views(emu_lib)
 
 
 def concurrent_matchers(lib, w, h, nf, M_points):

@@ -9,6 +9,7 @@ import pytest
 import kfdb_world as kw
 import vocab_scenes as vs
 from kfdb_world import make, run_world
+from test_emu_kfdb import kfdb_edge_cases, kfdb_min_common_every_max
 from orb_slam3_detailed_comments_amd import synth
 from orb_slam3_detailed_comments_amd.extractor import ORBextractor
 from orb_slam3_detailed_comments_amd.vocabulary import ORBVocabulary, KeyFrameDatabase
@@ -24,6 +25,14 @@ def test_kfdb_world_gpu(hip_lib, tmp_path, scoring):
 @pytest.mark.parametrize("scoring", [2, 0, 1, 4])
 def test_kfdb_raw_vectors_with_zeros_gpu(hip_lib, tmp_path, scoring):
     run_world(None, tmp_path, scoring, n_kf=60, zeros=0.3, normalise=False)
+
+
+def test_kfdb_edge_cases_gpu(hip_lib, tmp_path):
+    kfdb_edge_cases(hip_lib, tmp_path)
+
+
+def test_kfdb_min_common_every_max_gpu(hip_lib, tmp_path):
+    kfdb_min_common_every_max(hip_lib, tmp_path)
 
 
 def test_kfdb_scale_gpu(hip_lib, tmp_path):

@@ -12,6 +12,7 @@ from cases import FULL_CASES, SMALL_CASES, LARGE_CASES, EUROC_BF, EUROC_B
 from orb_slam3_detailed_comments_amd import synth
 from orb_slam3_detailed_comments_amd.extractor import ORBextractor
 from orb_slam3_detailed_comments_amd import matcher as M
+from test_emu_parity import EXTREME_THRESHOLDS, _extreme_fast_thresholds_case, _handle_reuse_case, _unusual_pyramids_case
 
 pytestmark = pytest.mark.gpu
 
@@ -234,3 +235,17 @@ def test_row_ends_of_every_width(hip_lib):
             assert np.array_equal(ex.pyramid_level(l, blurred=True), o.level_image(l, blurred=True)), "width %d blur level %d" % (width, l)
         assert _same(got, exp), width
         ex.close()
+
+
+def test_handle_reuse_across_sizes_and_batches(hip_lib):
+    _handle_reuse_case(hip_lib)
+
+
+def test_unusual_pyramids_with_stereo(hip_lib):
+    _unusual_pyramids_case(hip_lib)
+
+
+@pytest.mark.parametrize("ini,mn", EXTREME_THRESHOLDS)
+def test_extreme_fast_thresholds(hip_lib, ini, mn):
+    """the byte-range ends on the device's own instructions: SDWA survivor ballots, v_mbcnt lane ranks, packed binary16 min3 / max3 scores"""
+    _extreme_fast_thresholds_case(hip_lib, ini, mn)

@@ -13,6 +13,7 @@ import oracle_lib as ol
 import pyramid_export_check as pc
 from orb_slam3_detailed_comments_amd import synth, _lib
 from orb_slam3_detailed_comments_amd.extractor import ORBextractor
+from test_emu_pyramid_export import (export_off_by_default_allocates_nothing, exported_arrays_are_views_of_the_slot, input_pre_step_and_on_device_frames, other_scale_and_levels, ring_keeps_older_exports, toggle_reconfigure_and_batch_growth)
 
 pytestmark = pytest.mark.gpu
 
@@ -83,3 +84,28 @@ def test_gpu_reference_frame_repeat_on_dropin(hip_lib):
     left, right = synth.stereo_pair(752, 480, seed=100)
     n, _, m_ref, _, _ = ol.reference_frame_repeat(left, right, 0.0)
     assert n == 1 and got["matches"] == m_ref and m_ref > 100, (got, m_ref)
+
+
+def test_gpu_other_scale_and_levels(hip_lib):
+    other_scale_and_levels(hip_lib)
+
+
+@pytest.mark.parametrize("depth", [1, 2, 3])
+def test_gpu_ring_keeps_depth_minus_one_older_exports(hip_lib, depth):
+    ring_keeps_older_exports(hip_lib, depth)
+
+
+def test_gpu_toggle_reconfigure_and_batch_growth(hip_lib):
+    toggle_reconfigure_and_batch_growth(hip_lib)
+
+
+def test_gpu_input_pre_step_and_on_device_frames(hip_lib):
+    input_pre_step_and_on_device_frames(hip_lib)
+
+
+def test_gpu_export_off_by_default_allocates_nothing(hip_lib):
+    export_off_by_default_allocates_nothing(hip_lib)
+
+
+def test_gpu_exported_arrays_are_views_of_the_slot(hip_lib):
+    exported_arrays_are_views_of_the_slot(hip_lib)

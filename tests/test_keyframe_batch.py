@@ -101,7 +101,7 @@ def test_keyframe_batch_gpu(hip_lib):
     _run(hip_lib, 752, 480, 1200, 16)
 
 
-def test_keyframe_batch_edge_cases(emu_lib):
+def _edge_cases(lib):
     """Ragged and empty inputs of orbm_search_by_projection_keyframe_batch: a frame without key-frame points, a frame whose points are all invalid, a frame
     whose points all project outside the image, one frame alone, rows longer than any frame uses; bad arguments are refused before anything runs."""
     from orb_slam3_detailed_comments_amd import OrbxError
@@ -109,7 +109,7 @@ def test_keyframe_batch_edge_cases(emu_lib):
     rng = np.random.default_rng(11)
     pairs = [synth.stereo_pair(w, h, seed=880 + b, nrect=800) for b in range(B)]
     refs = [ol.ReferenceFrame(l, r, nf, fx=FX, fy=FY, cx=CX, cy=CY, bf=BF) for l, r in pairs]
-    ex = ORBextractor(nf, 1.2, 8, 20, 7, lib=emu_lib)
+    ex = ORBextractor(nf, 1.2, 8, 20, 7, lib=lib)
     res = ex.extract_batch(np.stack([l for l, _ in pairs] + [r for _, r in pairs]))
     sfs = ex.GetScaleFactors(); cap = ex.max_keypoints()
     cam, bounds = (FX, FY, CX, CY), (0.0, float(w), 0.0, float(h))
@@ -148,3 +148,12 @@ def test_keyframe_batch_edge_cases(emu_lib):
     with pytest.raises(OrbxError):
         one.fetch()                                                                                                                  # a refused call leaves nothing to fetch
     ex.close()
+
+
+def test_keyframe_batch_edge_cases(emu_lib):
+    _edge_cases(emu_lib)
+
+
+@pytest.mark.gpu
+def test_keyframe_batch_edge_cases_gpu(hip_lib):
+    _edge_cases(hip_lib)

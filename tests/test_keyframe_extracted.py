@@ -500,11 +500,20 @@ def test_lifetime_gpu(hip_lib):
 
 
 # ---- 7. the C++ facade: ResidentKeyFrames::Adopt / ORBmatcher::AdoptImplicit -------------------------------------------------------------------
-def test_facade_adopt(emu_lib, tmp_path):
+def _facade_adopt(tmp_path, libdir, libname):
     src = os.path.join(ol.ROOT, "tests", "cpp", "keyframe_adopt_probe.cpp")
     exe = tmp_path / "keyframe_adopt_probe"
-    emu = os.path.join(ol.ROOT, "tests", "emu")
     subprocess.run(["g++", "-O1", "-std=c++17", "-I" + os.path.join(ol.ROOT, "oracle", "opencv_shim"),
-                    "-I" + os.path.join(ol.ROOT, "include"), src, "-o", str(exe), "-L" + emu, "-lorbx_emu", "-Wl,-rpath," + emu, "-lpthread"], check=True)
+                    "-I" + os.path.join(ol.ROOT, "include"), src, "-o", str(exe), "-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-lpthread"], check=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "ADOPT OK" in r.stdout, r.stdout + r.stderr
+
+
+def test_facade_adopt(emu_lib, tmp_path):
+    _facade_adopt(tmp_path, *ol.emu_link())
+
+
+@pytest.mark.gpu
+def test_facade_adopt_gpu(hip_lib, tmp_path):
+    from orb_slam3_detailed_comments_amd import _lib
+    _facade_adopt(tmp_path, os.path.dirname(_lib.HIP_LIB_PATH), "orbx_hip")

@@ -171,8 +171,8 @@ def test_every_buffer_member_is_released_in_destroy():
     assert total > 60
 
 
-def test_facade_worlds_leave_nothing_behind(tmp_path, emu_lib):
-    """The header-only facade (include/orb_slam3_amd/ORBmatcher.h) over the emulator library: worlds of key frames, frames and map points are
+def _facade_worlds(tmp_path, orbx):
+    """The header-only facade (include/orb_slam3_amd/ORBmatcher.h) over the library `orbx`: worlds of key frames, frames and map points are
     built, searched through all thirteen methods (the implicit resident cache included) and destroyed twice in one process (three times under
     AddressSanitizer: profiles/r05_final/sanitizers.txt)."""
     import os
@@ -182,7 +182,6 @@ def test_facade_worlds_leave_nothing_behind(tmp_path, emu_lib):
     facade = os.path.join(ol.ROOT, "oracle", "_ref", "libmw_facade.so")
     if not os.path.exists(facade):
         pytest.skip("oracle/_ref/libmw_facade.so not built (needs /root/reference)")
-    orbx = ol.emu_lib_path()
     for seed, variant in [(1, "base"), (6, "kb8")]:
         dst = str(tmp_path / ("w_%s.npz" % variant))
         r = subprocess.run([sys.executable, os.path.join(ol.ROOT, "tests", "matcher_world.py"), facade, orbx, str(seed), variant, dst, "twice"], capture_output=True, text=True)
@@ -191,13 +190,23 @@ def test_facade_worlds_leave_nothing_behind(tmp_path, emu_lib):
         assert z["live_first"][2] >= 3 and np.array_equal(z["live_first"], z["live_again"]), (variant, z["live_first"], z["live_again"])
 
 
-def test_many_host_threads_with_their_own_handles(emu_lib):
+def test_facade_worlds_leave_nothing_behind(tmp_path, emu_lib):
+    import oracle_lib as ol
+    _facade_worlds(tmp_path, ol.emu_lib_path())
+
+
+@pytest.mark.gpu
+def test_facade_worlds_leave_nothing_behind_gpu(tmp_path, hip_lib):
+    from orb_slam3_detailed_comments_amd import _lib
+    _facade_worlds(tmp_path, _lib.HIP_LIB_PATH)
+
+
+def _many_host_threads(lib):
     """Eight host threads, each with its own extractor handle, extract, associate and search at the same time (the documented threading model: a handle belongs
     to one thread at a time; the library's shared state - error strings, the runtime's counters, the emulator's worker pool - has to cope); every thread gets
     exactly what a serial run gets, and nothing stays behind."""
     import threading
     import search_scenes as sc
-    lib = emu_lib
     before = live(lib)
     NT, ITER = 8, 3
     pairs = [synth.stereo_pair(376, 240, seed=40 + i, nrect=800) for i in range(NT)]
@@ -227,3 +236,12 @@ def test_many_host_threads_with_their_own_handles(emu_lib):
     assert errs == [] and exp[0][0][3] > 50 and exp[0][0][4] > 20
     del exp
     assert live(lib) == before
+
+
+def test_many_host_threads_with_their_own_handles(emu_lib):
+    _many_host_threads(emu_lib)
+
+
+@pytest.mark.gpu
+def test_many_host_threads_with_their_own_handles_gpu(hip_lib):
+    _many_host_threads(hip_lib)

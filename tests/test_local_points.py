@@ -89,7 +89,7 @@ def test_local_points_emulated(emu_lib):
     _check(emu_lib, (3,), npts=1500)
 
 
-def test_single_frame_candidate_pool_overflow_is_retried(emu_lib):
+def _single_frame_pool_overflow(lib):
     """The first window search of a handle gets a candidate pool of Q * 48 + 1024 entries; a search that finds more has to enlarge the pool and run
     again (the batched routes: test_local_points_batch.py::test_candidate_pool_overflow_is_retried).  Whole-image windows on fresh handles: once through
     orbm_area_search_batch, once through orbm_search_local_points (host points and resident points), results against the oracles as above."""
@@ -97,7 +97,7 @@ def test_single_frame_candidate_pool_overflow_is_retried(emu_lib):
     w, h, nf, Q = 752, 480, 1200, 32
     L, R = synth.stereo_pair(w, h, seed=11)
     F = ol.ReferenceFrame(L, R, nf, fx=FX, fy=FY, cx=CX, cy=CY, bf=BF)
-    ex = ORBextractor(nf, 1.2, 8, 20, 7, lib=emu_lib)
+    ex = ORBextractor(nf, 1.2, 8, 20, 7, lib=lib)
     (_, kL, dL), _ = ex.extract_batch(np.stack([L, R]))
     u, _, _ = ComputeStereoMatches(ex, ex, BF, F.mb, 0, 1, 1)
     assert kL.tobytes() == F.keys.tobytes() and F.N >= 200
@@ -125,7 +125,7 @@ def test_single_frame_candidate_pool_overflow_is_retried(emu_lib):
     total = sum(int(((octave >= l - 1) & (octave <= l)).sum()) for l in lvl)          # candidates: the keypoints of levels [l - 1, l]
     assert total > npts * 48 + 1024, "the scene does not overflow the initial pool (%d candidates)" % total
     for resident in (False, True):
-        ex2 = ORBextractor(nf, 1.2, 8, 20, 7, lib=emu_lib)                            # a handle that has not searched yet
+        ex2 = ORBextractor(nf, 1.2, 8, 20, 7, lib=lib)                            # a handle that has not searched yet
         rp = M.ResidentPoints(ex2, pos, normal, mind, maxd, desc) if resident else None
         tr, asg, n = M.SearchLocalPoints(ex2, fv, Rcw, tcw, (FX, FY, CX, CY), (0.0, float(w), 0.0, float(h)), BF, sfs, pos, normal, mind, maxd, bad, obs, desc,
                                          0.5, th, False, 9.0, 0.8, resident=rp)
@@ -141,6 +141,15 @@ def test_single_frame_candidate_pool_overflow_is_retried(emu_lib):
             rp.close()
         ex2.close()
     ex.close()
+
+
+def test_single_frame_candidate_pool_overflow_is_retried(emu_lib):
+    _single_frame_pool_overflow(emu_lib)
+
+
+@pytest.mark.gpu
+def test_single_frame_candidate_pool_overflow_is_retried_gpu(hip_lib):
+    _single_frame_pool_overflow(hip_lib)
 
 
 @pytest.mark.gpu

@@ -164,7 +164,7 @@ def test_local_points_large_batch_gpu(hip_lib):
     _large_batch(hip_lib, 640, 480, 1000, 48, 5000, 12)
 
 
-def test_candidate_pool_overflow_is_retried(emu_lib):
+def _pool_overflow(lib):
     """a search window so wide that the candidate pool of a fresh handle overflows: the fetch reports ORBX_E_CAPACITY once (the pool is enlarged),
     the wrapper runs the batch again, and the results are those of the single-frame call"""
     import ctypes as C
@@ -172,7 +172,7 @@ def test_candidate_pool_overflow_is_retried(emu_lib):
     w, h, nf, npts = 320, 240, 300, 400
     rng = np.random.default_rng(11)
     imgs = np.stack([synth.corner_field(w, h, seed=40 + b, nrect=700) for b in range(2)])
-    ex = ORBextractor(nf, 1.2, 8, 20, 7, lib=emu_lib)
+    ex = ORBextractor(nf, 1.2, 8, 20, 7, lib=lib)
     res = ex.extract_batch(imgs)
     k, d = res[0][1], res[0][2]
     src = rng.integers(0, len(k), npts); z = rng.uniform(1, 6, npts)
@@ -186,8 +186,11 @@ def test_candidate_pool_overflow_is_retried(emu_lib):
     poses = [(np.eye(3, dtype=np.float32), np.zeros(3, np.float32))] * 2
     lp.set_poses(poses)
     lp.enqueue(0, use_u_right=False, th=30.0)
-    rc = emu_lib.L.orbm_search_local_points_fetch(ex._h, lp.assigned.ctypes.data, lp.cap, lp.nm.ctypes.data, None)
+    lp.assigned[:] = -77; lp.nm[:] = -77
+    rc = lib.L.orbm_search_local_points_fetch(ex._h, lp.assigned.ctypes.data, lp.cap, lp.nm.ctypes.data, None)
     assert rc == -4                                         # ORBX_E_CAPACITY: tens of thousands of candidates against a pool sized for six per point
+    assert (lp.assigned == -77).all() and (lp.nm == -77).all(), "the refused fetch wrote into the caller's buffers"
+    assert lib.L.orbm_search_local_points_fetch(ex._h, lp.assigned.ctypes.data, lp.cap, lp.nm.ctypes.data, None) == -2 and (lp.assigned == -77).all(), "the overflowed batch can be fetched again: its entries were never written"
     lp.enqueue(0, use_u_right=False, th=30.0)
     asg, nm, _ = lp.fetch()
     for b in range(2):
@@ -196,3 +199,12 @@ def test_candidate_pool_overflow_is_retried(emu_lib):
         assert nm[b] == ref_n and np.array_equal(asg[b, :len(res[b][1])], ref_as)
     assert nm[0] > 50
     rp.close(); ex.close()
+
+
+def test_candidate_pool_overflow_is_retried(emu_lib):
+    _pool_overflow(emu_lib)
+
+
+@pytest.mark.gpu
+def test_candidate_pool_overflow_is_retried_gpu(hip_lib):
+    _pool_overflow(hip_lib)

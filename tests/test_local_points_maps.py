@@ -264,16 +264,19 @@ def test_in_view_layout_gpu(hip_lib):
     _in_view_layout(hip_lib)
 
 
-def test_pool_overflow_with_ragged_maps(emu_lib):
+def _pool_overflow(lib):
     """windows so wide that the candidate pool of a fresh handle (sized from the sum of the M_b) overflows: one ORBX_E_CAPACITY from the fetch, then
     the re-enqueued batch equals the single-frame calls"""
-    W = World(emu_lib, EMU_SHAPE)
+    W = World(lib, EMU_SHAPE)
     try:
         lp = W.batch()
         lp.enqueue(0, use_u_right=False, th=30.0)
-        assert emu_lib.L.orbm_search_local_points_fetch(W.ex._h, lp.assigned.ctypes.data, lp.cap, lp.nm.ctypes.data, None) == E_CAPACITY
+        lp.assigned[:] = -77; lp.nm[:] = -77
+        assert lib.L.orbm_search_local_points_fetch(W.ex._h, lp.assigned.ctypes.data, lp.cap, lp.nm.ctypes.data, None) == E_CAPACITY
+        assert (lp.assigned == -77).all() and (lp.nm == -77).all(), "the refused fetch wrote into the caller's buffers"
+        assert lib.L.orbm_search_local_points_fetch(W.ex._h, lp.assigned.ctypes.data, lp.cap, lp.nm.ctypes.data, None) == -2 and (lp.assigned == -77).all(), "the overflowed batch can be fetched again: its entries were never written"
         lp.enqueue(0, use_u_right=False, th=30.0)
-        assert emu_lib.L.orbm_search_local_points_fetch(W.ex._h, lp.assigned.ctypes.data, lp.cap, lp.nm.ctypes.data, None) == 0
+        assert lib.L.orbm_search_local_points_fetch(W.ex._h, lp.assigned.ctypes.data, lp.cap, lp.nm.ctypes.data, None) == 0
         for b, m in enumerate(W.maps):
             if m is None:
                 assert lp.nm[b] == 0 and (lp.assigned[b] == -1).all()
@@ -283,6 +286,15 @@ def test_pool_overflow_with_ragged_maps(emu_lib):
         assert lp.nm[0] > 50
     finally:
         W.close()
+
+
+def test_pool_overflow_with_ragged_maps(emu_lib):
+    _pool_overflow(emu_lib)
+
+
+@pytest.mark.gpu
+def test_pool_overflow_with_ragged_maps_gpu(hip_lib):
+    _pool_overflow(hip_lib)
 
 
 def _live(lib):

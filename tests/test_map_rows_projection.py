@@ -14,6 +14,7 @@ library is called the reference alone shows that the scene is a test: enough mat
 Isolation: a batch is enqueued, a second handle overwrites every used slot, flips the bad flags and rewrites the rows, and the fetch still returns the
 reference's result on the original data; the next enqueue sees the new data."""
 import ctypes as C
+import gc
 
 import numpy as np
 import pytest
@@ -473,6 +474,7 @@ def test_lastframe_rig_slots_gpu(hip_lib):
 # ---- refusals, resources, mirrors ----------------------------------------------------------------------------------------------------------------------
 
 def _live(lib):
+    gc.collect()                        # handles of earlier tests that only a collection frees (a caught exception's traceback keeps its frame) are not this test's
     a = (C.c_longlong * 4)()
     lib.check(lib.L.orbx_debug_live_resources(a))
     return list(a)

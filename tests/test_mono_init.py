@@ -118,16 +118,25 @@ def test_pool_form_forced_emulated(emu_lib, name, factory, nf, lap):
     _forced_case(emu_lib, factory, nf, lap, 0)
 
 
-def test_pool_form_mixed_launch_emulated(emu_lib):
+def _mixed_launch(lib):
     """levels 0-2 in the pool, the rest in LDS (two launches), 1 image and 34 images (the narrow counters of the large-batch form)"""
     img = synth.corner_field(376, 240, seed=10, nrect=800)
     other = synth.uniform_noise(376, 240, seed=3)
-    ex = ORBextractor(500, 1.2, 8, 20, 7, lib=emu_lib)
+    ex = ORBextractor(500, 1.2, 8, 20, 7, lib=lib)
     ex.debug_quadtree_lds_nodes(85)                            # quotas 109, 91, 75, ...: kp_cap + 8 = 120, 102, 86 | 74 ...
     exp, expo = _expected(500, 1.2, 8, 20, 7, img, (0, 0)), _expected(500, 1.2, 8, 20, 7, other, (0, 0))
     assert _same(ex(img), exp) and ex.debug_quadtree_pool_levels() == 3
     got = ex.extract_batch(np.stack([img] * 17 + [other] * 17))
     assert _same(got[0], exp) and _same(got[16], exp) and _same(got[17], expo) and _same(got[33], expo)
+
+
+def test_pool_form_mixed_launch_emulated(emu_lib):
+    _mixed_launch(emu_lib)
+
+
+@pytest.mark.gpu
+def test_pool_form_mixed_launch_gpu(hip_lib):
+    _mixed_launch(hip_lib)
 
 
 @pytest.mark.gpu

@@ -288,12 +288,12 @@ def test_rig_bow_two_handles_emulated(emu_lib, tmp_path):
     _run(emu_lib, tmp_path, 376, 376, 500, (40, 300), 3, 2, True, VOC_EMU[:1], seed=1, projection=False)
 
 
-def test_rig_bow_empty_camera_emulated(emu_lib, tmp_path):
+def _empty_camera(lib, tmp_path):
     """a rig frame one of whose cameras found no keypoints (a flat image): the transform and the search still give the joined rows' answer"""
     w = h = 320
     pairs = [_fisheye_pair(80 + b, w, h) for b in range(2)]
     flat = np.full((h, w), 90, np.uint8)
-    ex = ORBextractor(400, 1.2, 8, 20, 7, lib=emu_lib)
+    ex = ORBextractor(400, 1.2, 8, 20, 7, lib=lib)
     res = ex.extract_batch(np.stack([pairs[0][0], flat, pairs[0][1], pairs[1][1]]), (0, w - 1))       # frame 1: camera 1 empty
     try:
         assert len(res[1][1]) == 0 and len(res[3][1]) > 50
@@ -322,6 +322,15 @@ def test_rig_bow_empty_camera_emulated(emu_lib, tmp_path):
         kf.close(); voc.close()
     finally:
         ex.close()
+
+
+def test_rig_bow_empty_camera_emulated(emu_lib, tmp_path):
+    _empty_camera(emu_lib, tmp_path)
+
+
+@pytest.mark.gpu
+def test_rig_bow_empty_camera_gpu(hip_lib, tmp_path):
+    _empty_camera(hip_lib, tmp_path)
 
 
 def _live(lib):

@@ -259,14 +259,17 @@ def test_rig_in_view_layout_gpu(hip_lib):
     _in_view_layout(hip_lib)
 
 
-def test_rig_pool_overflow_with_ragged_maps(emu_lib):
+def _pool_overflow(lib):
     """th = 30 on a fresh handle: one ORBX_E_CAPACITY from the fetch (the pool, sized from the sum of the M_b, is enlarged), then the re-enqueued
     batch equals the single-frame calls"""
-    W = World(emu_lib, EMU_SHAPE)
+    W = World(lib, EMU_SHAPE)
     try:
         lp = W.batch()
         lp.enqueue(th=30.0)
+        lp.assigned[:] = -77; lp.nm[:] = -77
         assert lp._fetch() == E_CAPACITY
+        assert (lp.assigned == -77).all() and (lp.nm == -77).all(), "the refused fetch wrote into the caller's buffers"
+        assert lp._fetch() == -2 and (lp.assigned == -77).all(), "the overflowed batch can be fetched again: its entries were never written"
         lp.enqueue(th=30.0)
         assert lp._fetch() == 0
         for b, m in enumerate(W.maps):
@@ -277,6 +280,15 @@ def test_rig_pool_overflow_with_ragged_maps(emu_lib):
         assert lp.nm[0] > 50
     finally:
         W.close()
+
+
+def test_rig_pool_overflow_with_ragged_maps(emu_lib):
+    _pool_overflow(emu_lib)
+
+
+@pytest.mark.gpu
+def test_rig_pool_overflow_with_ragged_maps_gpu(hip_lib):
+    _pool_overflow(hip_lib)
 
 
 def _refusals(lib, two_devices):
