@@ -28,13 +28,17 @@ __global__ void __launch_bounds__(256) k_hamming_matrix(const unsigned long long
 }
 
 // grid (ceil(cap/4), B); one wave per left keypoint.
-// kpsL/descL/nL: left extractor outputs (stride cap); same for right; pyrL/pyrR: raw pyramids; bucket_start / bucket_items: the row index
-// of the right keypoints (k_layout).
+// kpsL/descL/nL: left extractor outputs (stride cap); descR/nR: the right one's; pyrL/pyrR: raw pyramids; bucket_start: the row buckets of the
+// right keypoints (k_layout); auxR: their search records in bucket order (k_orient_brief) - a run of buckets is a contiguous run of records.
+// A wave's life is a chain of memory round trips, so every trip carries all the loads whose addresses are known by then: the left descriptor, the
+// level and the bucket bounds go with one another, a trip of the search is the records of 128 candidates and then their descriptors (a lane
+// whose candidate fails the band / octave / column tests reads the left descriptor again instead: an address, not a branch, so that the two
+// candidates of a lane share the trip), and the SAD rows of all three row groups are requested together.
 __global__ void __launch_bounds__(256) k_stereo_match(const LevelInfo* __restrict__ lv,
                                                       const KeyPointRec* __restrict__ kpsL, const unsigned long long* __restrict__ descL, const int* __restrict__ nL,
-                                                      const KeyPointRec* __restrict__ kpsR, const unsigned long long* __restrict__ descR,
+                                                      const unsigned long long* __restrict__ descR,
                                                       const int4* __restrict__ auxR, const int* __restrict__ nR,
-                                                      const int* __restrict__ bucket_start, const int* __restrict__ bucket_items, int nb, int lookback,
+                                                      const int* __restrict__ bucket_start, int nb, int lookback,
                                                       int cap, const uint8_t* __restrict__ pyrL, const uint8_t* __restrict__ pyrR, size_t pyr_stride,
                                                       StereoParams P, float* __restrict__ uRight, float* __restrict__ depth, int* __restrict__ sad) {
     const int b = (int)blockIdx.y, lane = lane_id();
@@ -43,97 +47,111 @@ __global__ void __launch_bounds__(256) k_stereo_match(const LevelInfo* __restric
     const size_t o = (size_t)b * cap + iL;
     if (iL >= nL[b]) { if (lane == 0) { uRight[o] = -1.0f; depth[o] = -1.0f; sad[o] = -1; } return; }
     const KeyPointRec kL = kpsL[o];
-    const int levelL = kL.octave;
+    const int levelL = ORBX_UNIFORM(kL.octave);          // (the same in every lane: the level's layout below stays in scalar registers)
     const float uL = kL.x, vL = kL.y;
     const float maxD = __fdiv_rn(P.mbf, P.mb);
     const float minU = __fsub_rn(uL, maxD), maxU = uL;
     float out_u = -1.0f, out_d = -1.0f; int out_sad = -1;
     const int rowL = __float2int_rz(vL);
     const int nr = nR[b];
+    const LevelInfo& Lv = lv[levelL];
+    const float sf = Lv.inv_scale, Lscale = Lv.scale;
+    const int Lw = Lv.w, Lhh = Lv.h, Lpitch = Lv.pitch, Loff = Lv.off;
     // key = distance << 16 | iR.  The reference starts from bestDist = TH_HIGH, bestIdxR = 0 and replaces on a strictly smaller distance
     // while it walks vRowIndices[vL] in ascending iR (src/Frame.cc:1195-1226): the winner is the smallest key below TH_HIGH << 16.
     unsigned best = (unsigned)P.th_high << 16;
+    int best_x = 0;                                       // x bits of the candidate that holds `best`
     if (!(maxU < 0)) {
         const unsigned long long* dl = descL + 4 * o;
         const unsigned long long d0 = dl[0], d1 = dl[1], d2 = dl[2], d3 = dl[3];
-        const int4* ar = auxR + (size_t)b * cap;          // {first row, last row, x bits, octave}: one coalesced 16-B load per candidate
+        const int4* ar = auxR + (size_t)b * cap;          // {first row, last row, x bits, octave | iR << kAuxIndexShift}: one coalesced 16-B load per candidate
         // candidates: right keypoints whose band starts in rows [rowL - lookback, rowL] (lookback >= the tallest band), i.e. a
         // contiguous run of row buckets; the exact band / octave / column tests follow
         const int* bs = bucket_start + (size_t)b * (nb + 1);
-        const int* items = bucket_items + (size_t)b * cap;
         const int jbeg = bs[imin(imax(rowL - lookback, 0) >> kStereoRowShift, nb - 1)], jend = bs[imin(imax(rowL, 0) >> kStereoRowShift, nb - 1) + 1];
-        // one candidate: exact band / octave / column tests, then the (distance, index) key
-        auto visit = [&](int iR, const int4& a) {
-            if (rowL < a.x || rowL > a.y) return;
-            if (a.w < levelL - 1 || a.w > levelL + 1) return;
+        // one candidate: the exact band / octave / column tests ..
+        auto gate = [&](const int4& a) {
+            const int oct = a.w & ((1 << kAuxIndexShift) - 1);
             const float xr = __int_as_float(a.z);
-            if (xr >= minU && xr <= maxU) {
-                const unsigned long long* dr = descR + 4 * ((size_t)b * cap + iR);
-                const int dist = __popcll(d0 ^ dr[0]) + __popcll(d1 ^ dr[1]) + __popcll(d2 ^ dr[2]) + __popcll(d3 ^ dr[3]);
-                const unsigned cand = ((unsigned)dist << 16) | (unsigned)iR;
-                // full-key compare: lowest distance, then lowest iR, whatever the visiting order.  (Test switch bit 1 = the
-                // distance-only compare this kernel had in round 1, kept so that the tie tests can show they would catch it.)
-                if ((P.debug_flags & 2) ? dist < (int)(best >> 16) : cand < best) best = cand;
-            }
+            return rowL >= a.x && rowL <= a.y && oct >= levelL - 1 && oct <= levelL + 1 && xr >= minU && xr <= maxU;
+        };
+        // .. and the (distance, index) key of one that passed them
+        auto take = [&](const int4& a, const unsigned long long* dr) {
+            const int dist = __popcll(d0 ^ dr[0]) + __popcll(d1 ^ dr[1]) + __popcll(d2 ^ dr[2]) + __popcll(d3 ^ dr[3]);
+            const unsigned cand = ((unsigned)dist << 16) | (unsigned)(a.w >> kAuxIndexShift);
+            // full-key compare: lowest distance, then lowest iR, whatever the visiting order.  (Test switch bit 1 = the
+            // distance-only compare this kernel had in round 1, kept so that the tie tests can show they would catch it.)
+            if ((P.debug_flags & 2) ? dist < (int)(best >> 16) : cand < best) { best = cand; best_x = a.z; }
         };
         if (P.debug_flags & 4) {
             // test switch: every lane walks ALL candidates, last to first - every tie then meets in one lane, the higher position first
-            for (int j = jend - 1; j >= jbeg; j--) { const int iR = items[j]; visit(iR, ar[iR]); }
+            for (int j = jend - 1; j >= jbeg; j--) {
+                const int4 a = ar[j];
+                if (gate(a)) take(a, descR + 4 * ((size_t)b * cap + (a.w >> kAuxIndexShift)));
+            }
         } else
         for (int base = jbeg; base < jend; base += 128) { // 2 right keypoints per lane per trip, their loads in flight together
-            int4 a[2]; int idx[2];
+            int4 a[2];
 #pragma unroll
             for (int u = 0; u < 2; u++) {
-                int j = base + 64 * u + lane;
+                const int j = base + 64 * u + lane;
                 const bool in = j < jend;
-                if (P.debug_flags & 1) j = jend - 1 - (j - jbeg);    // test switch: visit the candidates in the opposite order
-                idx[u] = in ? items[j] : -1;
+                int jj = in ? j : jend - 1;                              // (a lane without a candidate repeats the last one's load and drops it)
+                if (P.debug_flags & 1) jj = jend - 1 - (jj - jbeg);      // test switch: visit the candidates in the opposite order
+                a[u] = ar[jj];
+                if (!in) { a[u].x = 1; a[u].y = 0; }                     // empty band
             }
+            bool pass[2];
+            unsigned long long r[2][4];
 #pragma unroll
             for (int u = 0; u < 2; u++) {
-                if (idx[u] >= 0) a[u] = ar[idx[u]]; else { a[u].x = 1; a[u].y = 0; a[u].z = 0; a[u].w = 0; }   // empty band
+                pass[u] = gate(a[u]);
+                const unsigned long long* dr = pass[u] ? descR + 4 * ((size_t)b * cap + (a[u].w >> kAuxIndexShift)) : dl;
+#pragma unroll
+                for (int w = 0; w < 4; w++) r[u][w] = dr[w];
             }
 #pragma unroll
-            for (int u = 0; u < 2; u++) visit(idx[u], a[u]);
+            for (int u = 0; u < 2; u++) if (pass[u]) take(a[u], r[u]);
         }
     }
+    const unsigned mine = best;
     best = wave_min_u32(best);   // lowest distance, then lowest right index == sequential first-min
     const int bestDist = (int)(best >> 16);
     if (bestDist < P.th_orb && nr > 0) {
-        const int bestIdxR = (int)(best & 0xFFFFu);
-        const float uR0 = kpsR[(size_t)b * cap + bestIdxR].x;
-        const LevelInfo Lv = lv[levelL];
-        const float sf = Lv.inv_scale;
+        // the winner's x is in the record its lane read (below TH_HIGH the key is a candidate's: some lane holds it)
+        const float uR0 = __int_as_float(ORBX_READLANE(best_x, __ffsll(__ballot(mine == best)) - 1));
         const float scaleduL = roundf(__fmul_rn(kL.x, sf)), scaledvL = roundf(__fmul_rn(kL.y, sf));
         const float scaleduR0 = roundf(__fmul_rn(uR0, sf));
         const int w = 5, Lh = 5;
         const float iniu = scaleduR0 + (float)(Lh - w), endu = scaleduR0 + (float)(Lh + w + 1);
         const int cu = (int)scaleduL, cv = (int)scaledvL, cr = (int)scaleduR0;
         // the reference only guards iniu/endu (:1265); the extra clause keeps every read inside the level
-        const bool inb = cv - w >= 0 && cv + w < Lv.h && cu - w >= 0 && cu + w < Lv.w && cr - Lh - w >= 0 && cr + Lh + w < Lv.w;
-        if (!(iniu < 0 || endu >= (float)Lv.w) && inb) {
-            const uint8_t* IL = pyrL + (size_t)b * pyr_stride + Lv.off;
-            const uint8_t* IR = pyrR + (size_t)b * pyr_stride + Lv.off;
+        const bool inb = cv - w >= 0 && cv + w < Lhh && cu - w >= 0 && cu + w < Lw && cr - Lh - w >= 0 && cr + Lh + w < Lw;
+        if (!(iniu < 0 || endu >= (float)Lw) && inb) {
+            const uint8_t* IL = pyrL + (size_t)b * pyr_stride + Loff;
+            const uint8_t* IR = pyrR + (size_t)b * pyr_stride + Loff;
             // SAD of the 11 x 11 left window against the right window at the 11 shifts (:1270-1290).  Lane = (row group g = lane >> 4, shift
             // k = lane & 15 < 11) sums rows g, g + 4, g + 8 for its shift: a row is 11 bytes = three dwords at columns 0, 4 and 7 (the third
             // overlaps the second by one byte, which is masked on both sides: no byte outside the windows is read), three v_sad_u8 per row.
             // The four row groups are added across the lanes k, k + 16, k + 32, k + 48; the first minimum over k (:1283 keeps a strictly
             // smaller SAD while k ascends) is the smallest key sad << 4 | k.
-            const int g = lane >> 4, k = lane & 15;
-            uint32_t acc = 0;
-            if (k < 11) {
+            // All 18 loads of a lane go out before the first is used: a lane without a row (g + 8 = 11) or a shift (k >= 11) reads the last
+            // row / shift of the window instead and drops the sum.
+            const int g = lane >> 4, k = lane & 15, kk = imin(k, 10);
+            uint32_t l0[3], l1[3], l2[3], r0[3], r1[3], r2[3];
 #pragma unroll
-                for (int t = 0; t < 3; t++) {
-                    const int row = g + 4 * t;
-                    if (row < 11) {
-                        const int rofs = __mul24(cv - w + row, Lv.pitch);                             // rows and pitches are far below 2^23
-                        const uint8_t* lp = IL + (uint32_t)(rofs + (cu - w));
-                        const uint8_t* rp = IR + (uint32_t)(rofs + (cr - w - Lh + k));
-                        const uint32_t l0 = load_u32_any(lp), l1 = load_u32_any(lp + 4), l2 = load_u32_any(lp + 7) & 0xFFFFFF00u;
-                        const uint32_t r0 = load_u32_any(rp), r1 = load_u32_any(rp + 4), r2 = load_u32_any(rp + 7) & 0xFFFFFF00u;
-                        acc = sad4_u8(l0, r0, sad4_u8(l1, r1, sad4_u8(l2, r2, acc)));
-                    }
-                }
+            for (int t = 0; t < 3; t++) {
+                const int rofs = __mul24(cv - w + imin(g + 4 * t, 10), Lpitch);                   // rows and pitches are far below 2^23
+                const uint8_t* lp = IL + (uint32_t)(rofs + (cu - w));
+                const uint8_t* rp = IR + (uint32_t)(rofs + (cr - w - Lh + kk));
+                l0[t] = load_u32_any(lp); l1[t] = load_u32_any(lp + 4); l2[t] = load_u32_any(lp + 7);
+                r0[t] = load_u32_any(rp); r1[t] = load_u32_any(rp + 4); r2[t] = load_u32_any(rp + 7);
+            }
+            uint32_t acc = 0;
+#pragma unroll
+            for (int t = 0; t < 3; t++) {
+                const uint32_t s = sad4_u8(l0[t], r0[t], sad4_u8(l1[t], r1[t], sad4_u8(l2[t] & 0xFFFFFF00u, r2[t] & 0xFFFFFF00u, 0u)));
+                if (g + 4 * t < 11 && k < 11) acc += s;
             }
             acc += __shfl_xor(acc, 16);
             acc += __shfl_xor(acc, 32);
@@ -144,7 +162,7 @@ __global__ void __launch_bounds__(256) k_stereo_match(const LevelInfo* __restric
                 const float deltaR = __fdiv_rn(__fsub_rn(dist1, dist3),
                                                __fmul_rn(2.0f, __fsub_rn(__fadd_rn(dist1, dist3), __fmul_rn(2.0f, dist2))));
                 if (!(deltaR < -1 || deltaR > 1)) {
-                    float bestuR = __fmul_rn(Lv.scale, __fadd_rn(__fadd_rn(scaleduR0, (float)bestinc), deltaR));
+                    float bestuR = __fmul_rn(Lscale, __fadd_rn(__fadd_rn(scaleduR0, (float)bestinc), deltaR));
                     float disparity = __fsub_rn(uL, bestuR);
                     if (disparity >= 0 && disparity < maxD) {
                         if (disparity <= 0) { disparity = 0.01f; bestuR = (float)((double)uL - 0.01); }

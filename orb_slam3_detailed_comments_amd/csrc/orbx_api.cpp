@@ -359,7 +359,7 @@ int configure(orbx_extractor* h, int W, int H, int B) {
         h->d_status.p = h->d_nm.p ? h->d_nm.p + 2 * b : nullptr; h->d_status.n = h->d_nm.p ? 4 : 0;
         e |= h->d_kps.ensure(b * cap); e |= h->d_desc.ensure(b * cap * 4); e |= h->d_aux.ensure(b * cap * 4);
         e |= h->d_uRight.ensure(b * cap); e |= h->d_depth.ensure(b * cap); e |= h->d_sad.ensure(b * cap); e |= h->d_nmatch.ensure(b);
-        e |= h->d_rowstart.ensure(b * (size_t)((h->H >> kStereoRowShift) + 3)); e |= h->d_rowitems.ensure(b * cap);
+        e |= h->d_rowstart.ensure(b * (size_t)((h->H >> kStereoRowShift) + 3)); e |= h->d_rowpos.ensure(b * cap);
         e |= h->d_knn.ensure(4 * b * cap); e |= h->d_ratio.ensure(b * cap);
         e |= h->h_nm.ensure(3 * b + 4); e |= h->h_cnt.ensure(2 * b + 4); e |= h->d_qtprof.ensure(32);
         if (e) return fail(ORBX_E_DEVICE, "device allocation failed (batch %d of %dx%d)", B, W, H);
@@ -535,7 +535,7 @@ int enqueue_extract(orbx_extractor* h, int B, const uint8_t* d_images, int src_w
     {
         dim3 grid(B, 1, 1);
         ORBX_LAUNCH(k_layout, grid, blk1, 2 * (size_t)(nb_rows + 1) * sizeof(int), h->s0, (const LevelInfo*)h->d_lv.p, nl, (const uint32_t*)h->d_lvl_keys.p, h->kp_total_cap,
-                    (const int*)h->d_lvl_count.p, lap0, lap1, h->d_final_idx.p, h->d_nm.p, h->d_nm.p + h->maxB, nb_rows, h->d_rowstart.p, h->d_rowitems.p);
+                    (const int*)h->d_lvl_count.p, lap0, lap1, h->d_final_idx.p, h->d_nm.p, h->d_nm.p + h->maxB, nb_rows, h->d_rowstart.p, h->d_rowpos.p);
     }
     stage_end(h, ST_LAYOUT, h->s0);
     if (!one_launch) rt::stream_wait_event(h->s0, h->ev_join);
@@ -547,10 +547,10 @@ int enqueue_extract(orbx_extractor* h, int B, const uint8_t* d_images, int src_w
         dim3 grid(gpi * 8 * ((B + 7) / 8), 1, 1);                  // an image's workgroups on one XCD (k_orient_brief)
         if (small) ORBX_LAUNCH(k_orient_brief_small, grid, blk1, 0, h->s0, (const LevelInfo*)h->d_lv.p, nl, (const uint8_t*)h->d_pyr.p, (const uint8_t*)h->d_blur.p,
                     h->pyr_stride, (const uint32_t*)h->d_lvl_keys.p, h->kp_total_cap, (const int*)h->d_lvl_count.p, (const int*)h->d_final_idx.p,
-                    h->umax, h->d_kps.p, h->d_desc.p, (int4*)h->d_aux.p, B, gpi);
+                    (const int*)h->d_rowpos.p, h->umax, h->d_kps.p, h->d_desc.p, (int4*)h->d_aux.p, B, gpi);
         else ORBX_LAUNCH(k_orient_brief, grid, blk1, 0, h->s0, (const LevelInfo*)h->d_lv.p, nl, (const uint8_t*)h->d_pyr.p, (const uint8_t*)h->d_blur.p,
                     h->pyr_stride, (const uint32_t*)h->d_lvl_keys.p, h->kp_total_cap, (const int*)h->d_lvl_count.p, (const int*)h->d_final_idx.p,
-                    h->umax, h->d_kps.p, h->d_desc.p, (int4*)h->d_aux.p, B, gpi);
+                    (const int*)h->d_rowpos.p, h->umax, h->d_kps.p, h->d_desc.p, (int4*)h->d_aux.p, B, gpi);
     }
     if (h->undist.active) {                                         // mvKeysUn (Frame::UndistortKeyPoints)
         dim3 grid((h->kp_total_cap + 255) / 256, B, 1);
@@ -625,7 +625,7 @@ void orbx_destroy(orbx_extractor* h) {
     for (auto& x : h->d_si) x.release();
     h->d_kps_un.release();
     h->d_lp.release(); h->d_depth_in.release(); h->h_lp_in.release(); h->h_lp_out.release();
-    h->d_aux.release(); h->d_qtprof.release(); h->d_qtpool.release(); h->d_rowstart.release(); h->d_rowitems.release();
+    h->d_aux.release(); h->d_qtprof.release(); h->d_qtpool.release(); h->d_rowstart.release(); h->d_rowpos.release();
     h->d_mapx.release(); h->d_mapy.release(); h->d_in_xt.release(); h->d_in_yt.release(); h->d_frame.release();
     h->d_exp.release(); for (auto& x : h->h_exp) x.release();     // (export_release above gave them back already)
     delete h;
@@ -1217,9 +1217,9 @@ int orbm_stereo_match(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int 
     const int lookback = (int)std::ceil(4.0f * R->scale[R->nlevels - 1]) + 2;     // tallest band: 2 * (2 * scale) + rounding
     ORBX_LAUNCH(k_stereo_match, grid, blk, 0, L->s0, (const LevelInfo*)L->d_lv.p,
                 (const KeyPointRec*)(L->d_kps.p + (size_t)lf * cap), (const unsigned long long*)(L->d_desc.p + (size_t)lf * cap * 4), (const int*)(L->d_nm.p + lf),
-                (const KeyPointRec*)(R->d_kps.p + (size_t)rf * cap), (const unsigned long long*)(R->d_desc.p + (size_t)rf * cap * 4),
+                (const unsigned long long*)(R->d_desc.p + (size_t)rf * cap * 4),
                 (const int4*)(R->d_aux.p + (size_t)rf * cap * 4), (const int*)(R->d_nm.p + rf),
-                (const int*)(R->d_rowstart.p + (size_t)rf * (nb + 1)), (const int*)(R->d_rowitems.p + (size_t)rf * cap), nb, lookback, cap, (const uint8_t*)(L->d_pyr.p + (size_t)lf * L->pyr_stride), (const uint8_t*)(R->d_pyr.p + (size_t)rf * R->pyr_stride), L->pyr_stride,
+                (const int*)(R->d_rowstart.p + (size_t)rf * (nb + 1)), nb, lookback, cap, (const uint8_t*)(L->d_pyr.p + (size_t)lf * L->pyr_stride), (const uint8_t*)(R->d_pyr.p + (size_t)rf * R->pyr_stride), L->pyr_stride,
                 P, L->d_uRight.p, L->d_depth.p, L->d_sad.p);
     dim3 grid2(B, 1, 1);
     ORBX_LAUNCH(k_stereo_median, grid2, blk, 0, L->s0, (const int*)(L->d_nm.p + lf), cap, L->d_uRight.p, L->d_depth.p,

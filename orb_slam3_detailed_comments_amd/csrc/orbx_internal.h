@@ -151,7 +151,7 @@ struct orbx_extractor {
     // input pre-step (orbx_set_input): channels / colour order / grey coefficients / geometry, device maps or taps, intermediate frame
     bool in_active = false; int in_channels = 1, in_rgb = 1, in_gray_variant = 0, in_geometry = 0, in_out_w = 0, in_out_h = 0, in_tap_w = 0, in_tap_h = 0;
     orbx::DevBuf<float> d_mapx, d_mapy; orbx::DevBuf<orbx::ResizeTap> d_in_xt, d_in_yt; orbx::DevBuf<uint8_t> d_frame;
-    orbx::DevBuf<int> d_rowstart, d_rowitems;   // row index of every image's keypoints for the stereo search (k_layout -> k_stereo_match)
+    orbx::DevBuf<int> d_rowstart, d_rowpos;     // row buckets of every image's keypoints for the stereo search (k_layout -> k_stereo_match) and every slot's place in their order (-> k_orient_brief)
     // the batched tracking searches (orbm_search_local_points_batch and its kin): one device block, one pinned staging block, one pinned result block
     orbx::DevBuf<uint8_t> d_lp, d_depth_in; orbx::HostBuf<uint8_t> h_lp_in, h_lp_out;
     // these outlive a batch: the entries the candidate pool has grown to; ev_lp (the staging block's upload) has been recorded and nobody has waited for it
@@ -165,7 +165,7 @@ struct orbx_extractor {
     // the model the LAST EXTRACTION ran with: d_kps_un holds that batch's mvKeysUn (or nothing when it ran without a model).  Consumers read these,
     // not the live `undist` - orbx_set_undistort between an extraction and a search would otherwise point them at stale or unallocated keypoints
     int ex_undist_gen = 0; bool ex_undist_active = false;
-    orbx::DevBuf<int> d_aux;     // int4 per keypoint: stereo row band / x / octave (k_orient_brief -> k_stereo_match)
+    orbx::DevBuf<int> d_aux;     // int4 per keypoint, in bucket order: stereo row band / x / octave | output index (k_orient_brief -> k_stereo_match)
     // bordered pyramid export (orbx_set_pyramid_export; nothing of it exists while exp_edge == 0).  k_frame_pyramid writes the framed levels of a batch
     // into d_exp on s_exp, forked from s0 when the pyramid is complete; one D2H copy moves them into ring slot exp_count % exp_depth.  exp_slot: the
     // slot of the last extraction (-1: it exported nothing that is still valid), exp_B its batch

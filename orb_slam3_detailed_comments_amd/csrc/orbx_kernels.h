@@ -88,23 +88,26 @@ __global__ void k_quadtree_selftest(int op, int spill, const void* __restrict__ 
 __global__ void k_layout(const LevelInfo* __restrict__ lv, int nlevels, const uint32_t* __restrict__ lvl_keys,
                          int kp_total_cap, const int* __restrict__ lvl_count, int lap0, int lap1,
                          int* __restrict__ final_idx, int* __restrict__ n_out, int* __restrict__ mono_out,
-                         int nb, int* __restrict__ row_start, int* __restrict__ row_items);
+                         int nb, int* __restrict__ row_start, int* __restrict__ row_pos);
 #ifndef ORBX_STEREO_ROW_SHIFT
 #define ORBX_STEREO_ROW_SHIFT 3
 #endif
 constexpr int kStereoRowShift = ORBX_STEREO_ROW_SHIFT;   // k_layout / k_stereo_match: right keypoints are bucketed by (first row of their band) >> shift
-constexpr int kKpPerWaveDecl = 8;      // must equal kKpPerWave in k_describe.hip
+// search record of a keypoint (k_orient_brief -> k_stereo_match), stored at the keypoint's place in the bucket order: {first row, last row of its
+// candidate band, x bits, octave | output index << kAuxIndexShift} (octave < kMaxLevels, index < 65535)
+constexpr int kAuxIndexShift = 8;
+constexpr int kKpPerWaveDecl = 8;     // must equal kKpPerWave in k_describe.hip
 constexpr int kKpPerWaveSmallDecl = 2; // keypoints per wave of k_orient_brief_small
 __global__ void k_orient_brief(const LevelInfo* __restrict__ lv, int nlevels, const uint8_t* __restrict__ pyr,
                                const uint8_t* __restrict__ blur, size_t pyr_stride,
                                const uint32_t* __restrict__ lvl_keys, int kp_total_cap,
-                               const int* __restrict__ lvl_count, const int* __restrict__ final_idx, UmaxTab umax,
+                               const int* __restrict__ lvl_count, const int* __restrict__ final_idx, const int* __restrict__ row_pos, UmaxTab umax,
                                KeyPointRec* __restrict__ out_kps, unsigned long long* __restrict__ out_desc, int4* __restrict__ out_aux,
                                int B, int groups_per_image);
 __global__ void k_orient_brief_small(const LevelInfo* __restrict__ lv, int nlevels, const uint8_t* __restrict__ pyr,
                                const uint8_t* __restrict__ blur, size_t pyr_stride,
                                const uint32_t* __restrict__ lvl_keys, int kp_total_cap,
-                               const int* __restrict__ lvl_count, const int* __restrict__ final_idx, UmaxTab umax,
+                               const int* __restrict__ lvl_count, const int* __restrict__ final_idx, const int* __restrict__ row_pos, UmaxTab umax,
                                KeyPointRec* __restrict__ out_kps, unsigned long long* __restrict__ out_desc, int4* __restrict__ out_aux,
                                int B, int groups_per_image);
 __global__ void k_undistort(const KeyPointRec* __restrict__ kps, const int* __restrict__ n_per_frame, int cap, UndistortParams U, KeyPointRec* __restrict__ kps_un);
@@ -112,9 +115,9 @@ __global__ void k_hamming_matrix(const unsigned long long* __restrict__ A, int n
                                  const unsigned long long* __restrict__ Bm, int nb, int* __restrict__ out);
 __global__ void k_stereo_match(const LevelInfo* __restrict__ lv, const KeyPointRec* __restrict__ kpsL,
                                const unsigned long long* __restrict__ descL, const int* __restrict__ nL,
-                               const KeyPointRec* __restrict__ kpsR, const unsigned long long* __restrict__ descR,
+                               const unsigned long long* __restrict__ descR,
                                const int4* __restrict__ auxR, const int* __restrict__ nR, const int* __restrict__ bucket_start,
-                               const int* __restrict__ bucket_items, int nb, int lookback, int cap, const uint8_t* __restrict__ pyrL,
+                               int nb, int lookback, int cap, const uint8_t* __restrict__ pyrL,
                                const uint8_t* __restrict__ pyrR, size_t pyr_stride, StereoParams P,
                                float* __restrict__ uRight, float* __restrict__ depth, int* __restrict__ sad);
 __global__ void k_stereo_median(const int* __restrict__ nL, int cap, float* __restrict__ uRight,
