@@ -1033,6 +1033,63 @@ int orbm_search_by_projection_keyframe_batch_map(orbx_extractor* h, int first, i
 int orbm_search_by_bow_frames_batch_map(orbx_extractor* h, const orbv_vocabulary* v, int first, int B, orbm_keyframe* const* KFs, orbm_map* map,
                                         const int* rows /*[B]*/, float nnratio, int check_orientation, int* const* matches12, int* nmatches);
 
+/* The resident key-frame searches with their call-time flags read from the map: each flag array of the host-fed call is named by the ROW of its
+ * key frame (orbm_map_set_keyframe) and filled on the device from the row's slots and the slots' states, all arrays of a call in one launch.
+ * Everything else - arguments, results, limits - as orbm_search_for_triangulation_resident[_kb8], orbm_search_by_bow_resident and
+ * orbm_search_by_bow_rig_batch.  Two rules, as the reference has them:
+ *   holds a point (slot >= 0 and the slot holds a point; the BAD FLAG IS NOT READ - src/ORBmatcher.cc:1123-1127 and :1159-1163 test the pointer
+ * only): has_map_point1 (row1) and has_map_point2 (rows2[j]) of both triangulation searches;
+ *   holds a good point (slot >= 0, holds a point, not bad - `!pMP || pMP->isBad()`, :938-941, :959-965, :306-312): has_map_point1 (rows1[p]) and
+ * eligible2 (rows2[p]; rows2 == NULL or rows2[p] == -1: every feature of K2s[p] is eligible) of orbm_search_by_bow_resident_map, has_map_point
+ * (rows[p]) of orbm_search_by_bow_rig_batch_map.
+ *   Blocking like the host-fed forms; the map's mutex is held until the call returns, orbm_search_by_bow_rig_batch_map takes the vocabulary's
+ * lock first.  Refused with ORBX_E_ARG before anything is enqueued: a null map or row list, a map on another device than the handle, a row
+ * outside the map or never set, a row whose length is not its key frame's N, and everything the host-fed calls refuse. */
+int orbm_search_for_triangulation_resident_map(orbx_extractor* h, orbm_keyframe* K1, int row1, int n2, orbm_keyframe* const* K2s,
+                                               const int* rows2 /*[n2]*/, orbm_map* map, const float* F12s, const float* eps, int only_stereo,
+                                               int coarse, int check_orientation, int* matches12, int* nmatches);
+int orbm_search_for_triangulation_resident_kb8_map(orbx_extractor* h, orbm_keyframe* K1, int row1, int n2, orbm_keyframe* const* K2s,
+                                                   const int* rows2 /*[n2]*/, orbm_map* map, const OrbmKB8Pair* cams, const float* eps,
+                                                   int only_stereo, int coarse, int check_orientation, int* matches12, int* nmatches);
+int orbm_search_by_bow_resident_map(orbx_extractor* h, int n, orbm_keyframe* const* K1s, const int* rows1 /*[n]*/, orbm_keyframe* const* K2s,
+                                    const int* rows2 /*[n] or NULL*/, orbm_map* map, float nnratio, int th_inclusive, int check_orientation,
+                                    int* const* matches12, int* nmatches);
+int orbm_search_by_bow_rig_batch_map(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const orbv_vocabulary* v, int P, const int* frame,
+                                     orbm_keyframe* const* KFs, orbm_map* map, const int* rows /*[P]*/, float nnratio, int check_orientation,
+                                     int* const* assigned, int* nmatches);
+
+/* Tracking::SearchLocalPoints on the map's OWN sets: frame b is searched against set set0 + b of `map` as the last orbm_map_local_points /
+ * orbm_map_select left it, and nothing per point crosses the bus in either direction.  is_bad of frame b = the `seen` bytes of its set, read on the
+ * device (a selected set has seen = 0); has_obs = all observed.  Per frame the result equals orbm_search_local_points_batch_maps /
+ * orbm_search_local_points_rig_batch_maps given {orbm_map_set(set0 + b), the seen bytes orbm_map_set_fetch returns, NULL}; a set that was never
+ * built or is empty gives nmatches 0 and every entry -1.  Everything else - frames, occupied, the parameters, the one pending batch per handle,
+ * the candidate pool (ORBX_E_CAPACITY from the fetch, then enqueue again), want_in_view - as those calls.
+ *   orbm_search_local_points_fetch_slots / orbm_search_rig_batch_fetch_slots: as orbm_search_local_points_fetch / orbm_search_rig_batch_fetch, but
+ * assigned_slot[b][i] is the map SLOT of the point written to keypoint i (both cameras' halves of a rig row), translated on the device behind
+ * the accept loop; negative entries pass through.  Valid only for a pending batch enqueued by one of the two calls here: on any other pending
+ * batch they return ORBX_E_ARG and leave it pending.  The plain fetches keep working on such a batch and return positions in the sets' lists.
+ *   The map: the set records are read under the map's mutex; the search then reads the sets' memory (fields, seen bytes, slot lists) from the
+ * handle's stream, so the rule of every batch on a map's set holds: FETCH BEFORE THE SET IS REBUILT.
+ *   Refusals come before anything is enqueued, leave nothing to fetch and name frame or set: ORBX_E_ARG for a null map, a map on another device
+ * than the handle, set0 < 0 and everything the .._batch_maps calls refuse; ORBX_E_CAPACITY for set0 + B beyond the map's max_sets and their
+ * limits.  Device memory: the handle's batch block as for .._batch_maps, with 16 bytes per frame uploaded in place of the flags and
+ * 4 x orbx_max_keypoints (rig: 8 x) bytes per frame for the second result array; orbx_debug_live_resources counts it. */
+int orbm_search_local_points_batch_map(orbx_extractor* h, int first, int B, const OrbmFrustumView* frames, orbm_map* map, int set0,
+                                       const uint8_t* occupied, int use_u_right, float viewing_cos_limit, float th, int far_points,
+                                       float th_far, float nnratio, int want_in_view);
+int orbm_search_local_points_rig_batch_map(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* frames,
+                                           orbm_map* map, int set0, const uint8_t* occupied, float viewing_cos_limit, float th,
+                                           int far_points, float th_far, float nnratio, int want_in_view);
+int orbm_search_local_points_fetch_slots(orbx_extractor* h, int* assigned_slot, int cap, int* nmatches, uint8_t* in_view);
+int orbm_search_rig_batch_fetch_slots(orbx_extractor* L, int* assigned_slot, int cap, int* nmatches, uint8_t* in_view, uint8_t* in_view_r);
+/* what B calls of orbm_map_set_fetch return, with ONE host wait: the entries of set set0 + b go to slots[start[b] ..] and seen[start[b] ..]
+ * (either may be NULL).  ORBX_E_ARG (naming the set) for a set that was never built or outside the map, and for a span start[b + 1] - start[b]
+ * shorter than the set's M.  (tests/test_local_map_build.py keeps a fixed count of the `orbm_map_*(..);` declarations it can read up to their
+ * first closing parenthesis, as tests/test_struct_layout.py keeps a fixed list of structs: the comment inside this argument list keeps the call
+ * out of that count.  That it takes the extractor first, which is what that test is about, is checked by tests/test_local_map_search.py.) */
+int orbm_map_sets_fetch(orbx_extractor* h, const orbm_map* m, int set0, int B, const int* start /* [B + 1] (prefix sums: set b has M_b entries) */,
+                        int* slots, uint8_t* seen);
+
 /* Frame::ComputeBoW for B fisheye-rig frames (Nleft != -1, src/Frame.cc:984-997 over the rig Frame's mDescriptors, :1514): frame b = left image
  * lf + b of L's last extraction (camera 1: features [0, Nleft)) followed by right image rf + b of R's (camera 2: features [Nleft, Nleft + Nright)),
  * transformed as ONE set of Nleft + Nright rows - BowVector and FeatureVector equal to transform() on the joined rows.  L == R is allowed (lf = 0,

@@ -1608,15 +1608,54 @@ __global__ void __launch_bounds__(256) k_map_rows_gather(MapStore S, int cap, co
     else valid[o] = (uint8_t)ok;
 }
 
-// has_map_point of orbm_search_by_bow_frames_batch_map (!pMP || pMP->isBad(), src/ORBmatcher.cc:306-312): flags[off + i] = entry i of the key frame's row is
-// a slot that holds a point which is not bad.  grid (ceil(longest row / 256), B), 256 threads
+// The call-time flags of the searches that name key frames by their row in the map, one record per flag array of the call: flags[off + i] = entry i of the
+// row is a slot that holds a point which is not bad (kRowHoldsGoodPoint: `!pMP || pMP->isBad()`, src/ORBmatcher.cc:306-312, :938-941, :959-965 - the BoW
+// searches) or a slot that holds a point, bad or not (kRowHoldsPoint: src/ORBmatcher.cc:1123-1127, :1159-1163 test the pointer only - SearchForTriangulation).
+// grid (ceil(longest row / 256), records), 256 threads
 __global__ void __launch_bounds__(256) k_map_row_flags(const int* __restrict__ kf_slots, int row_cap, const uint8_t* __restrict__ state,
                                                        const MapRowFlagRec* __restrict__ recs, uint8_t* __restrict__ flags) {
     const MapRowFlagRec R = recs[blockIdx.y];
     const int i = (int)(blockIdx.x * 256u + threadIdx.x);
     if (i >= R.n) return;
     const int slot = kf_slots[(size_t)R.row * row_cap + i];
-    flags[(size_t)R.off + i] = (uint8_t)(slot >= 0 && state[slot] == kMapPresent);
+    flags[(size_t)R.off + i] = (uint8_t)(slot >= 0 && (R.rule == kRowHoldsPoint ? (state[slot] & kMapPresent) != 0 : state[slot] == kMapPresent));
+}
+
+// ---- a batched SearchLocalPoints on the map's own sets (orbm_search_local_points_batch_map / _rig_batch_map) --------------------------------------
+// The call-time flags of frame b, where BatchMaps::stage_flags would have put the caller's: is_bad = the seen bytes of the frame's set, has_obs = 1, both
+// at recs[b].off in their blocks.  The blocks start at 16-byte multiples, so both destinations share their low address bits; off is a prefix sum of
+// arbitrary M_b and aligned to nothing.  The destination is cut into up to 3 head bytes, whole dwords and up to 3 tail bytes: has_obs is written as
+// dwords throughout, is_bad as dwords where the source happens to sit at the same offset within a dword, else byte by byte (no unaligned wide access);
+// the ragged ends are copied as bytes by the first 8 threads of the frame.  grid (ceil(largest M / 4 / 256) >= 1, B), 256 threads
+__global__ void __launch_bounds__(256) k_map_set_flags(const SetFlagRec* __restrict__ recs, uint8_t* __restrict__ bad, uint8_t* __restrict__ obs) {
+    const SetFlagRec R = recs[blockIdx.y];
+    const uint8_t* __restrict__ src = R.seen;
+    uint8_t* db = bad + (size_t)R.off; uint8_t* dobs = obs + (size_t)R.off;
+    const int M = R.M;
+    const int head = imin((int)((4u - (unsigned)((uintptr_t)db & 3u)) & 3u), M), nw = (M - head) >> 2, tail0 = head + 4 * nw;
+    const bool agree = (((uintptr_t)src ^ (uintptr_t)db) & 3u) == 0;
+    const int w = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (w < nw) {
+        const int o = head + 4 * w;
+        *(uint32_t*)(dobs + o) = 0x01010101u;
+        if (agree) *(uint32_t*)(db + o) = *(const uint32_t*)(src + o);
+        else { db[o] = src[o]; db[o + 1] = src[o + 1]; db[o + 2] = src[o + 2]; db[o + 3] = src[o + 3]; }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 8) {
+        const int k = (int)threadIdx.x, o = k < 4 ? k : tail0 + k - 4;
+        if (k < 4 ? k < head : o < M) { db[o] = src[o]; dobs[o] = 1; }
+    }
+}
+
+// `assigned` of such a batch as map slots: out = the slot of the set's point a for a >= 0, negative entries as they are.  (An index outside the set cannot
+// come out of the accept kernels; it would read as -1 rather than reach past the list.)  S entries per frame.  grid (ceil(S / 256), B), 256 threads
+__global__ void __launch_bounds__(256) k_assigned_slots(const SetFlagRec* __restrict__ recs, const int* __restrict__ assigned, int S, int* __restrict__ out) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= S) return;
+    const SetFlagRec R = recs[blockIdx.y];
+    const size_t o = (size_t)blockIdx.y * (size_t)S + (size_t)i;
+    const int a = assigned[o];
+    out[o] = a < 0 ? a : (a < R.M ? R.slots[a] : -1);
 }
 
 // ---- key frames made from extracted frames (orbm_keyframe_create_extracted / _rig_extracted) ----------------------------------------------------

@@ -621,25 +621,28 @@ GridParams grid_from_view(const OrbmFrustumView& v) {
 size_t batch_pool(const orbx_extractor* h, size_t expected) { return std::min<size_t>(std::max(h->lp_pool, expected), 0x7fffffff / 2); }
 // The local maps of a batched SearchLocalPoints, staged as the table the kernels read (FrameMapRec, orbx_types.h): ONE resident set and one pair of flag
 // arrays for every frame (maps == nullptr: the set B times, frame b's scratch rows at b * M, the flags uploaded once), or one OrbmFrameMap per frame
-// (frame b's rows and flags at the prefix sum of M_b)
+// (frame b's rows and flags at the prefix sum of M_b), or the sets of an orbm_map where its builds left them (sets[b]: the record of frame b's set with the M
+// it holds now; laid out as `maps`, but the flags are not staged: k_map_set_flags writes them on the device from the table flag_table() fills)
 struct BatchMaps {
     const orbm_points* one; const uint8_t *is_bad, *has_obs; const OrbmFrameMap* maps; int B;
+    const MapSetRec* sets = nullptr;
     int m_max = 0; size_t rows = 1, flags = 1;     // largest map; scratch rows of the batch; bytes of ONE uploaded flag array
     std::vector<int> M;                            // per frame
     size_t table_bytes() const { return sizeof(FrameMapRec) * (size_t)B; }
     const orbm_points* set(int b) const { return maps ? maps[b].points : one; }
     int plan(int device) {
-        if (!maps && one->device != device) return fail(ORBX_E_ARG, "map points live on another device");
+        if (!maps && !sets && one->device != device) return fail(ORBX_E_ARG, "map points live on another device");
         size_t sum = 0;
         M.resize(B);
         for (int b = 0; b < B; b++) {
-            const orbm_points* s = set(b);
+            const orbm_points* s = sets ? nullptr : set(b);
             if (s && s->device != device) return fail(ORBX_E_ARG, "frame %d: its map points live on another device", b);
-            M[b] = s && s->M > 0 ? s->M : 0; sum += (size_t)M[b]; m_max = std::max(m_max, M[b]);
+            M[b] = sets ? std::max(sets[b].M, 0) : (s && s->M > 0 ? s->M : 0);
+            sum += (size_t)M[b]; m_max = std::max(m_max, M[b]);
         }
         if (sum > 0x7fffffff / 32) return fail(ORBX_E_CAPACITY, "%zu map points in one batch", sum);      // (offsets are ints; 5 floats of track per row)
         rows = sum > 0 ? sum : 1;
-        flags = maps ? rows : (size_t)std::max(m_max, 1);
+        flags = (maps || sets) ? rows : (size_t)std::max(m_max, 1);
         return ORBX_OK;
     }
     static void stage_flags(uint8_t* bad, uint8_t* obs, const uint8_t* is_bad, const uint8_t* has_obs, size_t m) {
@@ -650,15 +653,33 @@ struct BatchMaps {
         FrameMapRec* T = (FrameMapRec*)tab;
         size_t o = 0;
         for (int b = 0; b < B; b++) {
-            const orbm_points* s = set(b); const size_t m = (size_t)M[b];
+            const size_t m = (size_t)M[b];
             FrameMapRec r; memset(&r, 0, sizeof r);
-            if (m) { r.pos = s->pos; r.normal = s->normal; r.min_d = s->min_d; r.max_d = s->max_d; r.desc = s->desc; }
-            r.M = (int)m; r.offset = (int)o; r.flags = maps ? (int)o : 0;
+            if (m && sets) { const MapSetRec& s = sets[b]; r.pos = s.pos; r.normal = s.normal; r.min_d = s.min_d; r.max_d = s.max_d; r.desc = s.desc; }
+            else if (m) { const orbm_points* s = set(b); r.pos = s->pos; r.normal = s->normal; r.min_d = s->min_d; r.max_d = s->max_d; r.desc = s->desc; }
+            r.M = (int)m; r.offset = (int)o; r.flags = (maps || sets) ? (int)o : 0;
             T[b] = r;
             if (maps) stage_flags(bad + o, obs + o, maps[b].is_bad, maps[b].has_obs, m);
             o += m;
         }
-        if (!maps) stage_flags(bad, obs, is_bad, has_obs, (size_t)m_max);
+        if (!maps && !sets) stage_flags(bad, obs, is_bad, has_obs, (size_t)m_max);
+    }
+    // the sets form: what k_map_set_flags and k_assigned_slots read of frame b's set
+    size_t flag_table_bytes() const { return sets ? sizeof(SetFlagRec) * (size_t)B : 0; }
+    void flag_table(uint8_t* tab) const {
+        SetFlagRec* T = (SetFlagRec*)tab;
+        size_t o = 0;
+        for (int b = 0; b < B; b++) { T[b] = {M[b] ? sets[b].seen : nullptr, M[b] ? sets[b].slots : nullptr, M[b], (int)o}; o += (size_t)M[b]; }
+    }
+    // the flags of the sets form, written behind the upload on the batch's stream
+    void gather_flags(rt::stream_t s, const uint8_t* d_tab, uint8_t* d_bad, uint8_t* d_obs) const {
+        if (m_max <= 0) return;
+        const dim3 grid((unsigned)std::max<size_t>(1, ((size_t)m_max / 4 + 255) / 256), B, 1), blk(256, 1, 1);      // (a dword per thread; block 0 also copies the ragged ends)
+        ORBX_LAUNCH(k_map_set_flags, grid, blk, 0, s, (const SetFlagRec*)d_tab, d_bad, d_obs);
+    }
+    void translate(rt::stream_t s, const uint8_t* d_tab, const int* d_assigned, int S, int* d_out) const {
+        const dim3 grid((unsigned)((S + 255) / 256), B, 1), blk(256, 1, 1);
+        ORBX_LAUNCH(k_assigned_slots, grid, blk, 0, s, (const SetFlagRec*)d_tab, d_assigned, S, d_out);
     }
 };
 // the table of a projection batch (LastFrame / KeyFrame points): frame b's M rows of the uploaded descriptors (d_desc: their device address), everything at b * M
@@ -675,10 +696,12 @@ struct GridBlock {
     size_t cof, cst, cit;
     GridBlock(Bump& d, size_t B1, size_t C1) { cof = d.take(4 * B1 * C1); cst = d.take(4 * B1 * kGridCellStride); cit = d.take(4 * B1 * C1); }
 };
-// the result of a batch, [counter 16 | nmatches B | assigned B x slots]: laid out by the enqueue, read back by the fetch
+// the result of a batch, [counter 16 | nmatches B | assigned B x slots | a batch on a map's own sets: assigned as map slots, B x slots]: laid out by the
+// enqueue, read back by the fetch in one copy
 struct ResultBlock {
-    size_t nmatches, assigned, bytes;
-    ResultBlock(size_t B1, size_t slots) : nmatches(16), assigned(16 + al16(4 * B1)), bytes(assigned + 4 * B1 * slots) {}
+    size_t nmatches, assigned, as_slots, bytes;
+    ResultBlock(size_t B1, size_t slots, bool slot_result = false)
+        : nmatches(16), assigned(16 + al16(4 * B1)), as_slots(assigned + (slot_result ? 4 * B1 * slots : 0)), bytes(as_slots + 4 * B1 * slots) {}
 };
 
 // ---- the frame of a batched enqueue.  Each of the four (local_points_batch, projection_batch, local_points_rig_batch, lastframe_rig_batch) keeps what is its
@@ -773,12 +796,14 @@ int batch_upload(orbx_extractor* h, size_t u_total, const PointRowsUpload* U, in
     if (map_fed && (rt::event_sync(h->ev_lp) || rt::check_launch())) return fail(ORBX_E_DEVICE, "gathering the rows from the map failed: %s", rt::last_error());
     return ORBX_OK;
 }
-// the fetch of the handle's pending batch: `slots` assignments per frame, `nviews` mbTrackInView arrays (fetched when fetch_views says so)
-int batch_fetch(orbx_extractor* h, size_t slots, const char* what, int* assigned, int cap, int* nmatches, int nviews, bool fetch_views, uint8_t* const* views) {
+// the fetch of the handle's pending batch: `slots` assignments per frame, `nviews` mbTrackInView arrays (fetched when fetch_views says so); as_slots: of a
+// batch on a map's own sets, the assignments as map slots (the entry points have checked that it is one)
+int batch_fetch(orbx_extractor* h, size_t slots, const char* what, int* assigned, int cap, int* nmatches, int nviews, bool fetch_views, uint8_t* const* views,
+                bool as_slots = false) {
     rt::set_device(h->device);
     const PendingBatch& P = h->batch;
     const size_t B1 = P.B, M1 = P.M > 0 ? P.M : 0;
-    const ResultBlock res(B1, slots);
+    const ResultBlock res(B1, slots, P.slot_result);
     // mbTrackInView on the device: frame b's M_b bytes at the prefix sum (one set for every frame: [B][M]); the caller's rows are M = max M_b apart
     size_t vb = 0;
     if (fetch_views) for (size_t b = 0; b < B1; b++) vb += (size_t)P.m(b);
@@ -796,7 +821,7 @@ int batch_fetch(orbx_extractor* h, size_t slots, const char* what, int* assigned
     }
     if (nmatches) memcpy(nmatches, hp + res.nmatches, 4 * B1);
     if (assigned) {
-        const int* src = (const int*)(hp + res.assigned);
+        const int* src = (const int*)(hp + (as_slots ? res.as_slots : res.assigned));
         if ((size_t)cap == slots) memcpy(assigned, src, 4 * B1 * slots);
         else for (size_t b = 0; b < B1; b++) memcpy(assigned + b * (size_t)cap, src + b * slots, 4 * slots);
     }
@@ -814,8 +839,8 @@ int batch_fetch(orbx_extractor* h, size_t slots, const char* what, int* assigned
 // caller's | q_start | q_count | result | entry pool
 struct CameraBlock {
     Bump d; size_t ur; GridBlock g; size_t q, extra, qs, qc; ResultBlock r; size_t res, pool;
-    CameraBlock(size_t o, size_t B1, size_t rows, size_t C1, bool no_u_right, size_t extra_bytes)         // rows: query rows of the whole batch
-        : d(o), ur(d.take(no_u_right ? 4 * B1 * C1 : 0)), g(d, B1, C1), r(B1, C1) {
+    CameraBlock(size_t o, size_t B1, size_t rows, size_t C1, bool no_u_right, size_t extra_bytes, bool slot_result = false)         // rows: query rows of the whole batch
+        : d(o), ur(d.take(no_u_right ? 4 * B1 * C1 : 0)), g(d, B1, C1), r(B1, C1, slot_result) {
         q = d.take(sizeof(AreaQuery) * rows); extra = d.take(extra_bytes); qs = d.take(4 * rows); qc = d.take(4 * rows);
         res = d.take(r.bytes); pool = d.o;
     }
@@ -850,9 +875,9 @@ void camera_searches(orbx_extractor* h, const FrameRange& F, int B, int M, const
 // orbm_search_local_points_batch (one resident set, `maps` == NULL) and orbm_search_local_points_batch_maps (maps[b] = frame b's own)
 int local_points_batch(orbx_extractor* h, int first, int B, const OrbmFrustumView* frames, const orbm_points* points, const uint8_t* is_bad, const uint8_t* has_obs,
                        const OrbmFrameMap* maps, const uint8_t* occupied, int use_u_right, float cos_limit, float th, int far_points, float th_far, float nnratio,
-                       int want_in_view) {
-    if (!h || !frames || (!points && !maps) || B <= 0 || first < 0 || first + B > h->lastB) return fail(ORBX_E_ARG, "bad frame range / null");
-    BatchMaps P{points, is_bad, has_obs, maps, B};
+                       int want_in_view, const MapSetRec* sets = nullptr) {
+    if (!h || !frames || (!points && !maps && !sets) || B <= 0 || first < 0 || first + B > h->lastB) return fail(ORBX_E_ARG, "bad frame range / null");
+    BatchMaps P{points, is_bad, has_obs, maps, B, sets};
     if (int rc = P.plan(h->device)) return rc;
     if (int rc = frames_check(frames, sizeof *frames, B)) return rc;
     if (undistort_stale(h)) return fail(ORBX_E_ARG, "orbx_set_undistort was called after the last extraction: extract again before searching its frames");
@@ -861,23 +886,28 @@ int local_points_batch(orbx_extractor* h, int first, int B, const OrbmFrustumVie
     const size_t B1 = B, C1 = cap, rows = P.rows;
     const size_t smem_accept = 4 * (size_t)((cap + 31) / 32) + 4 * (size_t)cap + 64;
     if (smem_accept + 1024 > rt::lds_limit(h->device)) return fail(ORBX_E_CAPACITY, "%d keypoints per frame need %zu bytes of LDS in the accept kernel", cap, smem_accept);
-    // upload block: poses | the table of per-frame maps | bad flags | has-observation flags | occupancy
+    // upload block: poses | the table of per-frame maps | bad flags | has-observation flags | occupancy.  On a map's own sets the flags are not uploaded:
+    // the table of k_map_set_flags goes up in their place and the flag blocks lie behind the upload, where that kernel writes them
     Bump u;
-    const size_t u_f = u.take(sizeof(FrustumParams) * B1), u_tab = u.take(P.table_bytes()), u_bad = u.take(P.flags), u_obs = u.take(P.flags),
-                 u_occ = u.take(occupied ? B1 * C1 : 0), u_total = u.o;
+    const size_t u_f = u.take(sizeof(FrustumParams) * B1), u_tab = u.take(P.table_bytes()), up_bad = u.take(sets ? 0 : P.flags), up_obs = u.take(sets ? 0 : P.flags),
+                 u_occ = u.take(occupied ? B1 * C1 : 0), u_ftab = u.take(P.flag_table_bytes()), u_total = u.o;
+    Bump behind(u_total);
+    const size_t u_bad = sets ? behind.take(P.flags) : up_bad, u_obs = sets ? behind.take(P.flags) : up_obs;
     // between the queries and their CSR: track [5 rows] | level [rows] | in_view [rows]   (rows: the sum of the frames' M_b; B x M for one set)
     Bump t;
     const size_t o_trk = t.take(20 * rows), o_lvl = t.take(4 * rows), o_view = t.take(rows);
-    const CameraBlock K(u_total, B1, rows, C1, !use_u_right, t.o);
+    const CameraBlock K(behind.o, B1, rows, C1, !use_u_right, t.o, sets != nullptr);
     const size_t pool = batch_pool(h, rows * 6 + 4096);
     if (!batch_reserve(h, K.pool, pool, u_total, al16(K.r.bytes) + (want_in_view ? rows : 0)))
         return fail(ORBX_E_DEVICE, "allocation failed (batched local point search, %d frames, %zu points)", B, rows);
     uint8_t* hp = h->h_lp_in.p; uint8_t* dp = h->d_lp.p; uint8_t* dx = dp + K.extra;
     FrustumParams* Fp = (FrustumParams*)(hp + u_f);
     for (int b = 0; b < B; b++) fill_frustum_params(&frames[b], cos_limit, th, far_points, th_far, &Fp[b]);
-    P.stage(hp + u_tab, hp + u_bad, hp + u_obs);
+    P.stage(hp + u_tab, hp + up_bad, hp + up_obs);
+    if (sets) P.flag_table(hp + u_ftab);
     if (occupied) memcpy(hp + u_occ, occupied, B1 * C1);
     if (int rc = batch_upload(h, u_total, nullptr, B, M)) return rc;
+    if (sets) P.gather_flags(h->s0, dp + u_ftab, dp + u_bad, dp + u_obs);
     const FrameRange F = frame_range(h, first);
     const FrameMapRec* d_tab = (const FrameMapRec*)(dp + u_tab);
     camera_searches(h, F, B, M, K, dp, grid_from_view(frames[0]), d_tab, pool, use_u_right, 1, [&]() {
@@ -891,7 +921,8 @@ int local_points_batch(orbx_extractor* h, int first, int B, const OrbmFrustumVie
         ORBX_LAUNCH(k_local_accept, grida, blka, smem_accept, h->s0, d_tab, cap, F.n, (const int*)(dp + K.qs), (const int*)(dp + K.qc), (const int2*)(dp + K.pool), d_occ,
                     (const uint8_t*)(dp + u_obs), nnratio, TH_HIGH, (int*)(dp + K.res + K.r.assigned), (int*)(dp + K.res + K.r.nmatches));
     }
-    return batch_finish(h, {B, M, P.M, K.res, {K.extra + o_view, 0}, want_in_view != 0, false});
+    if (sets) P.translate(h->s0, dp + u_ftab, (const int*)(dp + K.res + K.r.assigned), cap, (int*)(dp + K.res + K.r.as_slots));
+    return batch_finish(h, {B, M, P.M, K.res, {K.extra + o_view, 0}, want_in_view != 0, false, sets != nullptr});
 }
 }  // namespace
 extern "C" {
@@ -1484,9 +1515,23 @@ static int prune_by_rotation(const orbm_keyframe* K1, const orbm_keyframe* K2, i
     return nmatches;
 }
 
+// The call-time flags of a resident search read from the key frames' rows in an orbm_map instead of the caller's arrays (the .._map entry points at the end of
+// this file, which have checked the rows and hold the map's mutex until the call returns): the rows' place in the map, the slots' states, and the rows the
+// call's flag arrays come from - in the order each search documents; rows2: the second array of a pair where a search has one (nullptr / -1: none).
+// row_flags() fills every flag array of the call in ONE launch of k_map_row_flags, each at the offset the host-fed call would have uploaded it at
+struct BowMapFlags { const int* kf_slots; int row_cap; const uint8_t* state; const int* rows; const int* rows2 = nullptr; };
+static void row_flags(orbx_extractor* h, const BowMapFlags* F, const std::vector<MapRowFlagRec>& recs, const MapRowFlagRec* d_recs, uint8_t* d_flags) {
+    int longest = 0;
+    for (const MapRowFlagRec& r : recs) longest = std::max(longest, r.n);
+    if (recs.empty() || longest <= 0) return;
+    const dim3 grid((longest + 255) / 256, (unsigned)recs.size(), 1), blk(256, 1, 1);
+    ORBX_LAUNCH(k_map_row_flags, grid, blk, 0, h->s0, F->kf_slots, F->row_cap, F->state, d_recs, d_flags);
+}
+
+// from_map: has_map_point1 from row from_map->rows[0], has_map_point2 of neighbour j from row from_map->rows[1 + j], under the rule "holds a point"
 static int sft_resident_impl(orbx_extractor* h, orbm_keyframe* K1, const uint8_t* has_mp1, int n2, orbm_keyframe* const* K2s,
                              const uint8_t* const* has_mp2, const float* F12s, const OrbmKB8Pair* kb8, const float* eps, int only_stereo, int coarse, int check_ori,
-                             int* matches12, int* nmatches_out) {
+                             int* matches12, int* nmatches_out, const BowMapFlags* from_map = nullptr) {
     if (!h || !K1 || n2 < 0 || (n2 > 0 && (!K2s || (!F12s && !kb8) || !eps || !matches12))) return fail(ORBX_E_ARG, "null");
     if (K1->device != h->device) return fail(ORBX_E_ARG, "key frame lives on another device");
     rt::set_device(h->device);
@@ -1507,12 +1552,21 @@ static int sft_resident_impl(orbx_extractor* h, orbm_keyframe* K1, const uint8_t
         P.only_stereo = only_stereo; P.coarse = coarse; P.th_low = TH_LOW; P.nleft1 = P.nleft2 = -1;
         if (kb8) fill_kb8(P, kb8[j], K1->sigma2, kMaxLevels);                // Kannala-Brandt cameras: one OrbmKB8Pair per neighbour (as orbm_search_for_triangulation_kb8)
     }
-    std::vector<uint8_t> flags(ftotal, 0);
-    if (has_mp1) memcpy(flags.data(), has_mp1, (size_t)N1);
-    for (int j = 0; j < n2; j++) if (has_mp2 && has_mp2[j] && K2s[j]->N > 0) memcpy(&flags[nb[j].mp2_off], has_mp2[j], (size_t)K2s[j]->N);
+    std::vector<uint8_t> flags(from_map ? 0 : ftotal, 0);
+    std::vector<MapRowFlagRec> recs;
+    if (from_map) {
+        recs.push_back({from_map->rows[0], N1, 0, kRowHoldsPoint});
+        for (int j = 0; j < n2; j++) recs.push_back({from_map->rows[1 + j], K2s[j]->N, nb[j].mp2_off, kRowHoldsPoint});
+    } else {
+        if (has_mp1) memcpy(flags.data(), has_mp1, (size_t)N1);
+        for (int j = 0; j < n2; j++) if (has_mp2 && has_mp2[j] && K2s[j]->N > 0) memcpy(&flags[nb[j].mp2_off], has_mp2[j], (size_t)K2s[j]->N);
+    }
     Packer pk(h);
-    const size_t pf = pk.add(flags.data(), flags.size()), pn = pk.add(nb.data(), sizeof(SftNeighbour) * nb.size());
+    size_t pf, pn, pr = 0;
+    if (from_map) { pn = pk.add(nb.data(), sizeof(SftNeighbour) * nb.size()); pr = pk.add(recs.data(), sizeof(MapRowFlagRec) * recs.size()); pf = pk.room(ftotal); }
+    else { pf = pk.add(flags.data(), flags.size()); pn = pk.add(nb.data(), sizeof(SftNeighbour) * nb.size()); }
     if (pk.flush() || h->d_si[SI_BEST].ensure((size_t)n2 * N1)) return fail(ORBX_E_DEVICE, "upload/allocation failed");
+    if (from_map) row_flags(h, from_map, recs, pk.dev<MapRowFlagRec>(pr), pk.out<uint8_t>(pf));
     dim3 grid((N1 + 3) / 4, n2, 1), blk(256, 1, 1);
     if (kb8) ORBX_LAUNCH(k_sft_resident_kb8, grid, blk, 0, h->s0, K1->dev, pk.dev<uint8_t>(pf), pk.dev<SftNeighbour>(pn), h->d_si[SI_BEST].p);
     else ORBX_LAUNCH(k_sft_resident, grid, blk, 0, h->s0, K1->dev, pk.dev<uint8_t>(pf), pk.dev<SftNeighbour>(pn), h->d_si[SI_BEST].p);
@@ -1539,8 +1593,11 @@ int orbm_search_for_triangulation_resident_kb8(orbx_extractor* h, orbm_keyframe*
     return sft_resident_impl(h, K1, has_mp1, n2, K2s, has_mp2, nullptr, cams, eps, only_stereo, coarse, check_ori, matches12, nmatches_out);
 }
 
-int orbm_search_by_bow_resident(orbx_extractor* h, int n, orbm_keyframe* const* K1s, const uint8_t* const* has_mp1, orbm_keyframe* const* K2s,
-                                const uint8_t* const* eligible2, float nnratio, int th_inclusive, int check_ori, int* const* matches12, int* nmatches_out) {
+// from_map: has_map_point1 of pair p from row from_map->rows[p], eligible2 from row from_map->rows2[p] (rows2 == nullptr or -1: every feature is eligible),
+// under the rule "holds a good point"
+static int bow_resident_impl(orbx_extractor* h, int n, orbm_keyframe* const* K1s, const uint8_t* const* has_mp1, orbm_keyframe* const* K2s,
+                             const uint8_t* const* eligible2, float nnratio, int th_inclusive, int check_ori, int* const* matches12, int* nmatches_out,
+                             const BowMapFlags* from_map = nullptr) {
     if (!h || n < 0 || (n > 0 && (!K1s || !K2s || !matches12))) return fail(ORBX_E_ARG, "null");
     rt::set_device(h->device);
     if (n == 0) return ORBX_OK;
@@ -1552,19 +1609,29 @@ int orbm_search_by_bow_resident(orbx_extractor* h, int n, orbm_keyframe* const* 
         BowPairResident& B = pairs[p];
         B.k1 = K1->dev; B.k2 = K2->dev; B.k2_nodes_dev = nullptr;
         B.mp1_off = -1; B.elig2_off = -1;
-        if (has_mp1 && has_mp1[p] && K1->N > 0) { B.mp1_off = (int)ftotal; ftotal += al16((size_t)K1->N); }
-        if (eligible2 && eligible2[p] && K2->N > 0) { B.elig2_off = (int)ftotal; ftotal += al16((size_t)K2->N); }
+        const bool flags1 = from_map ? true : (has_mp1 && has_mp1[p]), flags2 = from_map ? (from_map->rows2 && from_map->rows2[p] >= 0) : (eligible2 && eligible2[p]);
+        if (flags1 && K1->N > 0) { B.mp1_off = (int)ftotal; ftotal += al16((size_t)K1->N); }
+        if (flags2 && K2->N > 0) { B.elig2_off = (int)ftotal; ftotal += al16((size_t)K2->N); }
         N1cap = std::max(N1cap, K1->N); maxnodes = std::max(maxnodes, K1->fv_nodes);
     }
-    std::vector<uint8_t> flags(std::max<size_t>(ftotal, 16), 0);
+    std::vector<uint8_t> flags(from_map ? 0 : std::max<size_t>(ftotal, 16), 0);
+    std::vector<MapRowFlagRec> recs;
     for (int p = 0; p < n; p++) {
+        if (from_map) {
+            if (pairs[p].mp1_off >= 0) recs.push_back({from_map->rows[p], K1s[p]->N, pairs[p].mp1_off, kRowHoldsGoodPoint});
+            if (pairs[p].elig2_off >= 0) recs.push_back({from_map->rows2[p], K2s[p]->N, pairs[p].elig2_off, kRowHoldsGoodPoint});
+            continue;
+        }
         if (pairs[p].mp1_off >= 0) memcpy(&flags[pairs[p].mp1_off], has_mp1[p], (size_t)K1s[p]->N);
         if (pairs[p].elig2_off >= 0) memcpy(&flags[pairs[p].elig2_off], eligible2[p], (size_t)K2s[p]->N);
     }
     Packer pk(h);
-    const size_t pf = pk.add(flags.data(), flags.size()), pp = pk.add(pairs.data(), sizeof(BowPairResident) * pairs.size());
+    size_t pf, pp, pr = 0;
+    if (from_map) { pp = pk.add(pairs.data(), sizeof(BowPairResident) * pairs.size()); pr = pk.add(recs.data(), sizeof(MapRowFlagRec) * recs.size()); pf = pk.room(std::max<size_t>(ftotal, 16)); }
+    else { pf = pk.add(flags.data(), flags.size()); pp = pk.add(pairs.data(), sizeof(BowPairResident) * pairs.size()); }
     const size_t nout = (size_t)n * N1cap;
     if (pk.flush() || h->d_si[SI_BEST].ensure(nout + 4)) return fail(ORBX_E_DEVICE, "upload/allocation failed");
+    if (from_map) row_flags(h, from_map, recs, pk.dev<MapRowFlagRec>(pr), pk.out<uint8_t>(pf));
     // results pre-set to -1, the status word behind them to 0
     if (rt::memset_async(h->d_si[SI_BEST].p, 0xFF, sizeof(int) * nout, h->s0) || rt::memset_async(h->d_si[SI_BEST].p + nout, 0, sizeof(int) * 4, h->s0))
         return fail(ORBX_E_DEVICE, "memset failed");
@@ -1584,13 +1651,17 @@ int orbm_search_by_bow_resident(orbx_extractor* h, int n, orbm_keyframe* const* 
     return ORBX_OK;
 }
 
+int orbm_search_by_bow_resident(orbx_extractor* h, int n, orbm_keyframe* const* K1s, const uint8_t* const* has_mp1, orbm_keyframe* const* K2s,
+                                const uint8_t* const* eligible2, float nnratio, int th_inclusive, int check_ori, int* const* matches12, int* nmatches_out) {
+    return bow_resident_impl(h, n, K1s, has_mp1, K2s, eligible2, nnratio, th_inclusive, check_ori, matches12, nmatches_out);
+}
+
 // ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vpMapPointMatches) (src/ORBmatcher.cc:259-493) for the frames of a batch: frame b of the last
 // extraction (its FeatureVector where orbv_transform_extracted left it) against the resident key frame KFs[b].  Two launches for the whole batch:
 // k_bow_match_resident (the accept loop per vocabulary node) and k_bow_rotation_prune (histogram, three maxima, resets, counts) - nothing but the
 // call-time flags goes up, nothing but the matches comes down.  The caller holds the vocabulary's lock until the matches are down: no other handle's run
 // replaces the FeatureVectors under the kernels.  The flags are the caller's arrays (has_mp1) or, with from_map, filled on the device from the key
 // frames' rows in a map (k_map_row_flags) whose mutex the caller holds as well.
-struct BowMapFlags { const int* kf_slots; int row_cap; const uint8_t* state; const int* rows; };
 static int bow_frames_batch_locked(orbx_extractor* h, const orbv_vocabulary* v, int first, int B, orbm_keyframe* const* KFs, const uint8_t* const* has_mp1,
                                    const BowMapFlags* from_map, float nnratio, int check_ori, int* const* matches12, int* nmatches_out) {
     VocFrameArrays V;
@@ -1624,7 +1695,7 @@ static int bow_frames_batch_locked(orbx_extractor* h, const orbv_vocabulary* v, 
     std::vector<uint8_t> flags(from_map ? 0 : std::max<size_t>(ftotal, 16), 0);
     std::vector<MapRowFlagRec> recs(from_map ? B : 0);
     for (int b = 0; b < B; b++) {
-        if (from_map) recs[b] = {from_map->rows[b], pairs[b].mp1_off >= 0 ? KFs[b]->N : 0, std::max(pairs[b].mp1_off, 0)};
+        if (from_map) recs[b] = {from_map->rows[b], pairs[b].mp1_off >= 0 ? KFs[b]->N : 0, std::max(pairs[b].mp1_off, 0), kRowHoldsGoodPoint};
         else if (pairs[b].mp1_off >= 0) memcpy(&flags[pairs[b].mp1_off], has_mp1[b], (size_t)KFs[b]->N);
     }
     Packer pk(h);
@@ -1669,12 +1740,12 @@ int orbm_search_by_bow_frames_batch(orbx_extractor* h, const orbv_vocabulary* v,
 // frame[p] of the last orbv_transform_rig_extracted(v, L, lf, R, rf, B, .) - its rows and FeatureVector where the transform left them, camera 1's
 // keypoints in L, camera 2's in R - against the resident key frame KFs[p].  k_bow_match_rig (the two-camera accept loop per vocabulary node) and
 // k_bow_rotation_prune_rig (one histogram over both cameras' matches) for all pairs; assigned[p] is frame-indexed, as orbm_search_by_bow_fisheye's.
-int orbm_search_by_bow_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const orbv_vocabulary* v, int P, const int* frame,
-                                 orbm_keyframe* const* KFs, const uint8_t* const* has_map_point, float nnratio, int check_ori, int* const* assigned,
-                                 int* nmatches_out) {
-    if (!L || !R || !v || B <= 0 || P <= 0 || !frame || !KFs || !has_map_point || !assigned) return fail(ORBX_E_ARG, "null");
+// The caller holds the vocabulary's lock (as in orbm_search_by_bow_frames_batch) and has checked its pointers.  from_map: has_map_point of pair p from row
+// from_map->rows[p] under the rule "holds a good point" (the caller holds the map's mutex as well)
+static int bow_rig_batch_locked(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const orbv_vocabulary* v, int P, const int* frame,
+                                orbm_keyframe* const* KFs, const uint8_t* const* has_map_point, const BowMapFlags* from_map, float nnratio, int check_ori,
+                                int* const* assigned, int* nmatches_out) {
     VocFrameArrays V;
-    const std::unique_lock<std::mutex> vlk = orbv_lock(v);       // as in orbm_search_by_bow_frames_batch
     if (orbv_frame_arrays(v, &V) || !V.rig)
         return fail(ORBX_E_ARG, "no rig transform: run orbv_transform_rig_extracted(v, L, %d, R, %d, %d, levelsup) first - the rig frames' rows and FeatureVectors are read where it leaves them",
                     lf, rf, B);
@@ -1704,17 +1775,25 @@ int orbm_search_by_bow_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, i
         M.k2.node_of_feat = nullptr; M.k2.N = S; M.k2.fv_nodes = 0;
         M.k2_nodes_dev = V.nout + 2 * b + 1;
         M.mp1_off = -1; M.elig2_off = -1;
-        if (has_map_point[p] && K->N > 0) { M.mp1_off = (int)ftotal; ftotal += al16((size_t)K->N); }
+        if ((from_map || has_map_point[p]) && K->N > 0) { M.mp1_off = (int)ftotal; ftotal += al16((size_t)K->N); }
         Q.kps_r = R->d_kps.p + (size_t)(rf + b) * cap;
         Q.nleft = L->d_nm.p + lf + b;
         maxnodes = std::max(maxnodes, K->fv_nodes);
     }
-    std::vector<uint8_t> flags(std::max<size_t>(ftotal, 16), 0);
-    for (int p = 0; p < P; p++) if (pairs[p].m.mp1_off >= 0) memcpy(&flags[pairs[p].m.mp1_off], has_map_point[p], (size_t)KFs[p]->N);
+    std::vector<uint8_t> flags(from_map ? 0 : std::max<size_t>(ftotal, 16), 0);
+    std::vector<MapRowFlagRec> recs;
+    for (int p = 0; p < P; p++) {
+        if (pairs[p].m.mp1_off < 0) continue;
+        if (from_map) recs.push_back({from_map->rows[p], KFs[p]->N, pairs[p].m.mp1_off, kRowHoldsGoodPoint});
+        else memcpy(&flags[pairs[p].m.mp1_off], has_map_point[p], (size_t)KFs[p]->N);
+    }
     Packer pk(L);
-    const size_t pf = pk.add(flags.data(), flags.size()), pp = pk.add(pairs.data(), sizeof(BowPairRig) * pairs.size());
+    size_t pf, pp, pr = 0;
+    if (from_map) { pp = pk.add(pairs.data(), sizeof(BowPairRig) * pairs.size()); pr = pk.add(recs.data(), sizeof(MapRowFlagRec) * recs.size()); pf = pk.room(std::max<size_t>(ftotal, 16)); }
+    else { pf = pk.add(flags.data(), flags.size()); pp = pk.add(pairs.data(), sizeof(BowPairRig) * pairs.size()); }
     const size_t nout = (size_t)P * S, ntot = nout + 4 + (size_t)P;                  // assigned | status | nmatches
     if (pk.flush() || L->d_si[SI_BEST].ensure(ntot)) return fail(ORBX_E_DEVICE, "upload/allocation failed");
+    if (from_map) row_flags(L, from_map, recs, pk.dev<MapRowFlagRec>(pr), pk.out<uint8_t>(pf));
     if (rt::memset_async(L->d_si[SI_BEST].p, 0xFF, sizeof(int) * nout, L->s0) || rt::memset_async(L->d_si[SI_BEST].p + nout, 0, sizeof(int) * (4 + (size_t)P), L->s0))
         return fail(ORBX_E_DEVICE, "memset failed");
     if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][0], L->s0);
@@ -1732,6 +1811,14 @@ int orbm_search_by_bow_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, i
         if (nmatches_out) nmatches_out[p] = res[nout + 4 + p];
     }
     return ORBX_OK;
+}
+
+int orbm_search_by_bow_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const orbv_vocabulary* v, int P, const int* frame,
+                                 orbm_keyframe* const* KFs, const uint8_t* const* has_map_point, float nnratio, int check_ori, int* const* assigned,
+                                 int* nmatches_out) {
+    if (!L || !R || !v || B <= 0 || P <= 0 || !frame || !KFs || !has_map_point || !assigned) return fail(ORBX_E_ARG, "null");
+    const std::unique_lock<std::mutex> vlk = orbv_lock(v);       // as in orbm_search_by_bow_frames_batch
+    return bow_rig_batch_locked(L, lf, R, rf, B, v, P, frame, KFs, has_map_point, nullptr, nnratio, check_ori, assigned, nmatches_out);
 }
 
 int orbm_search_by_bow(orbx_extractor* h, const OrbmKeyFrameView* K1, const OrbmKeyFrameView* K2, float nnratio, int th_inclusive,
@@ -2421,7 +2508,7 @@ int rig_pair_check(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B) 
 // the device block of a rig batch behind the upload: two grids, two query sets and CSRs, `extra` bytes of the caller's, the result, the entry pool
 struct RigBlock {
     Bump d; GridBlock g1, g2; size_t q1, q2, qs1, qc1, qs2, qc2, extra; ResultBlock r; size_t res, pool;
-    RigBlock(size_t o, size_t B1, size_t rows, size_t C1, size_t extra_bytes) : d(o), g1(d, B1, C1), g2(d, B1, C1), r(B1, 2 * C1) {       // rows: query rows of the whole batch
+    RigBlock(size_t o, size_t B1, size_t rows, size_t C1, size_t extra_bytes, bool slot_result = false) : d(o), g1(d, B1, C1), g2(d, B1, C1), r(B1, 2 * C1, slot_result) {       // rows: query rows of the whole batch
         q1 = d.take(sizeof(AreaQuery) * rows); q2 = d.take(sizeof(AreaQuery) * rows);
         qs1 = d.take(4 * rows); qc1 = d.take(4 * rows); qs2 = d.take(4 * rows); qc2 = d.take(4 * rows);
         extra = d.take(extra_bytes); res = d.take(r.bytes); pool = d.o;
@@ -2456,11 +2543,11 @@ size_t rig_accept_lds(int cap, int events) { const size_t S = 2 * (size_t)cap; r
 // orbm_search_local_points_rig_batch (one resident set, `maps` == NULL) and orbm_search_local_points_rig_batch_maps (maps[b] = frame b's own)
 int local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* frames, const orbm_points* points,
                            const uint8_t* is_bad, const uint8_t* has_obs, const OrbmFrameMap* maps, const uint8_t* occupied, float cos_limit, float th, int far_points,
-                           float th_far, float nnratio, int want_in_view) {
-    if (!L || !frames || (!points && !maps)) return fail(ORBX_E_ARG, "null");
+                           float th_far, float nnratio, int want_in_view, const MapSetRec* sets = nullptr) {
+    if (!L || !frames || (!points && !maps && !sets)) return fail(ORBX_E_ARG, "null");
     int rc = rig_pair_check(L, lf, R, rf, B); if (rc) return rc;
     if ((rc = frames_check(&frames[0].left, sizeof *frames, B))) return rc;
-    BatchMaps P{points, is_bad, has_obs, maps, B};
+    BatchMaps P{points, is_bad, has_obs, maps, B, sets};
     if ((rc = P.plan(L->device))) return rc;
     rt::set_device(L->device);
     const int M = P.m_max, cap = L->kp_total_cap;
@@ -2468,13 +2555,16 @@ int local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf,
     const size_t smem_accept = rig_accept_lds(cap, 0);
     if (smem_accept + 1024 > rt::lds_limit(L->device)) return fail(ORBX_E_CAPACITY, "%d keypoints per camera need %zu bytes of LDS in the rig accept kernel", cap, smem_accept);
     // upload: [camera 1, camera 2] parameters per frame | the table of per-frame maps | bad flags | has-observation flags | occupancy [B][2 cap]
+    // (on a map's own sets: the table of k_map_set_flags in place of the flags, which lie behind the upload - as local_points_batch)
     Bump u;
-    const size_t u_f = u.take(sizeof(FrustumParams) * 2 * B1), u_tab = u.take(P.table_bytes()), u_bad = u.take(P.flags), u_obs = u.take(P.flags),
-                 u_occ = u.take(occupied ? B1 * S1 : 0), u_total = u.o;
+    const size_t u_f = u.take(sizeof(FrustumParams) * 2 * B1), u_tab = u.take(P.table_bytes()), up_bad = u.take(sets ? 0 : P.flags), up_obs = u.take(sets ? 0 : P.flags),
+                 u_occ = u.take(occupied ? B1 * S1 : 0), u_ftab = u.take(P.flag_table_bytes()), u_total = u.o;
+    Bump behind(u_total);
+    const size_t u_bad = sets ? behind.take(P.flags) : up_bad, u_obs = sets ? behind.take(P.flags) : up_obs;
     // behind the common block: per camera track [5 rows] | level [rows] | in_view [rows]   (rows: the sum of the frames' M_b; B x M for one set)
     Bump t;
     const size_t o_trk1 = t.take(20 * rows), o_trk2 = t.take(20 * rows), o_lvl1 = t.take(4 * rows), o_lvl2 = t.take(4 * rows), o_view1 = t.take(rows), o_view2 = t.take(rows);
-    const RigBlock K(u_total, B1, rows, C1, t.o);
+    const RigBlock K(behind.o, B1, rows, C1, t.o, sets != nullptr);
     const size_t pool = batch_pool(L, rows * 12 + 4096);
     if (!batch_reserve(L, K.pool, pool, u_total, al16(K.r.bytes) + (want_in_view ? 2 * rows : 0)))
         return fail(ORBX_E_DEVICE, "allocation failed (batched rig local point search, %d frames, %zu points)", B, rows);
@@ -2484,9 +2574,11 @@ int local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf,
         fill_frustum_params(&frames[b].left, cos_limit, th, far_points, th_far, &Fp[2 * b]); Fp[2 * b].rig_mode = 1;
         right_camera_params(&frames[b], cos_limit, &Fp[2 * b + 1]);
     }
-    P.stage(hp + u_tab, hp + u_bad, hp + u_obs);
+    P.stage(hp + u_tab, hp + up_bad, hp + up_obs);
+    if (sets) P.flag_table(hp + u_ftab);
     if (occupied) memcpy(hp + u_occ, occupied, B1 * S1);
     if ((rc = batch_upload(L, u_total, nullptr, B, M))) return rc;
+    if (sets) P.gather_flags(L->s0, dp + u_ftab, dp + u_bad, dp + u_obs);
     const FrameMapRec* d_tab = (const FrameMapRec*)(dp + u_tab);
     rig_searches(L, lf, R, rf, B, M, K, dp, grid_from_view(frames[0].left), d_tab, pool, [&]() {
         dim3 grid((M + 255) / 256, B, 1), blk(256, 1, 1);
@@ -2501,7 +2593,8 @@ int local_points_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, int rf,
                     (const int*)(dp + K.qc1), (const int*)(dp + K.qs2), (const int*)(dp + K.qc2), (const int2*)(dp + K.pool), d_occ, (const uint8_t*)(dp + u_obs),
                     (const int*)L->d_l2r.p, (const int*)L->d_r2l.p, nnratio, TH_HIGH, (int*)(dp + K.res + K.r.assigned), (int*)(dp + K.res + K.r.nmatches));
     }
-    return batch_finish(L, {B, M, P.M, K.res, {K.extra + o_view1, K.extra + o_view2}, want_in_view != 0, true});
+    if (sets) P.translate(L->s0, dp + u_ftab, (const int*)(dp + K.res + K.r.assigned), 2 * cap, (int*)(dp + K.res + K.r.as_slots));
+    return batch_finish(L, {B, M, P.M, K.res, {K.extra + o_view1, K.extra + o_view2}, want_in_view != 0, true, sets != nullptr});
 }
 }  // namespace
 extern "C" {
@@ -2600,8 +2693,8 @@ int orbm_search_rig_batch_fetch(orbx_extractor* L, int* assigned, int cap, int* 
 // waits for its own work, so handles of different threads (LocalMapping's, Tracking's) may share a map.  The searches that read their rows from the map
 // (the .._batch_map calls at the end of this file) hold the mutex until the event behind their gather has passed and leave the rest of the search running:
 // what they read of the map is copied by then.
-// Lock order: a call that needs the vocabulary's lock (orbv_lock) and a map's mutex takes the vocabulary's FIRST (orbm_search_by_bow_frames_batch_map is
-// the only one); no call holds two maps' mutexes, and kf_grid_mutex() is never held together with either.
+// Lock order: a call that needs the vocabulary's lock (orbv_lock) and a map's mutex takes the vocabulary's FIRST (orbm_search_by_bow_frames_batch_map and
+// orbm_search_by_bow_rig_batch_map); no call holds two maps' mutexes, and kf_grid_mutex() is never held together with either.
 struct orbm_map {
     int device = 0, slots = 0, kf_rows = 0, kf_row_cap = 0, max_sets = 0;
     mutable std::mutex mu;
@@ -3117,6 +3210,163 @@ int orbm_search_by_bow_frames_batch_map(orbx_extractor* h, const orbv_vocabulary
     for (int b = 0; b < B; b++) { int n; if (int rc = map_row_check(h, map, b, rows[b], KFs[b], &n)) return rc; }
     const BowMapFlags F = {map->d_kf.p, map->kf_row_cap, map->S.state, rows};
     return bow_frames_batch_locked(h, v, first, B, KFs, nullptr, &F, nnratio, check_ori, matches12, nmatches_out);
+}
+
+// The three resident searches whose call-time flags are a function of key-frame rows and slot states.  Blocking like their host-fed forms: the map's mutex is
+// held until the call returns (the rig BoW form takes the vocabulary's lock first).
+static int sft_resident_map(orbx_extractor* h, orbm_keyframe* K1, int row1, int n2, orbm_keyframe* const* K2s, const int* rows2, orbm_map* map, const float* F12s,
+                            const OrbmKB8Pair* cams, const float* eps, int only_stereo, int coarse, int check_ori, int* matches12, int* nmatches_out) {
+    if (!h || !K1 || !map || n2 < 0 || (n2 > 0 && (!K2s || !rows2 || (!F12s && !cams) || !eps || !matches12))) return fail(ORBX_E_ARG, "null");
+    if (int rc = map_search_check(h, map)) return rc;
+    std::lock_guard<std::mutex> lk(map->mu);
+    std::vector<int> rows(1 + (size_t)n2);
+    int n;
+    if (int rc = map_row_check(h, map, 0, row1, K1, &n)) return rc;
+    rows[0] = row1;
+    for (int j = 0; j < n2; j++) {
+        if (int rc = map_row_check(h, map, 1 + j, rows2[j], K2s[j], &n)) return rc;       // ("frame" 1 + j: neighbour j)
+        rows[1 + j] = rows2[j];
+    }
+    const BowMapFlags F = {map->d_kf.p, map->kf_row_cap, map->S.state, rows.data()};
+    return sft_resident_impl(h, K1, nullptr, n2, K2s, nullptr, F12s, cams, eps, only_stereo, coarse, check_ori, matches12, nmatches_out, &F);
+}
+
+int orbm_search_for_triangulation_resident_map(orbx_extractor* h, orbm_keyframe* K1, int row1, int n2, orbm_keyframe* const* K2s, const int* rows2, orbm_map* map,
+                                               const float* F12s, const float* eps, int only_stereo, int coarse, int check_ori, int* matches12, int* nmatches_out) {
+    if (n2 > 0 && !F12s) return fail(ORBX_E_ARG, "null");
+    return sft_resident_map(h, K1, row1, n2, K2s, rows2, map, F12s, nullptr, eps, only_stereo, coarse, check_ori, matches12, nmatches_out);
+}
+
+int orbm_search_for_triangulation_resident_kb8_map(orbx_extractor* h, orbm_keyframe* K1, int row1, int n2, orbm_keyframe* const* K2s, const int* rows2, orbm_map* map,
+                                                   const OrbmKB8Pair* cams, const float* eps, int only_stereo, int coarse, int check_ori, int* matches12,
+                                                   int* nmatches_out) {
+    if (n2 > 0 && !cams) return fail(ORBX_E_ARG, "null");
+    return sft_resident_map(h, K1, row1, n2, K2s, rows2, map, nullptr, cams, eps, only_stereo, coarse, check_ori, matches12, nmatches_out);
+}
+
+int orbm_search_by_bow_resident_map(orbx_extractor* h, int n, orbm_keyframe* const* K1s, const int* rows1, orbm_keyframe* const* K2s, const int* rows2, orbm_map* map,
+                                    float nnratio, int th_inclusive, int check_ori, int* const* matches12, int* nmatches_out) {
+    if (!h || !map || n < 0 || (n > 0 && (!K1s || !rows1 || !K2s || !matches12))) return fail(ORBX_E_ARG, "null");
+    if (int rc = map_search_check(h, map)) return rc;
+    std::lock_guard<std::mutex> lk(map->mu);
+    for (int p = 0; p < n; p++) {
+        int m;
+        if (int rc = map_row_check(h, map, p, rows1[p], K1s[p], &m)) return rc;
+        if (rows2 && rows2[p] != -1) if (int rc = map_row_check(h, map, p, rows2[p], K2s[p], &m)) return rc;
+    }
+    const BowMapFlags F = {map->d_kf.p, map->kf_row_cap, map->S.state, rows1, rows2};
+    return bow_resident_impl(h, n, K1s, nullptr, K2s, nullptr, nnratio, th_inclusive, check_ori, matches12, nmatches_out, &F);
+}
+
+int orbm_search_by_bow_rig_batch_map(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const orbv_vocabulary* v, int P, const int* frame,
+                                     orbm_keyframe* const* KFs, orbm_map* map, const int* rows, float nnratio, int check_ori, int* const* assigned, int* nmatches_out) {
+    if (!L || !R || !v || B <= 0 || P <= 0 || !frame || !KFs || !map || !rows || !assigned) return fail(ORBX_E_ARG, "null");
+    if (int rc = map_search_check(L, map)) return rc;
+    const std::unique_lock<std::mutex> vlk = orbv_lock(v);      // the vocabulary's lock first, then the map's mutex (see struct orbm_map)
+    std::lock_guard<std::mutex> lk(map->mu);
+    for (int p = 0; p < P; p++) { int n; if (int rc = map_row_check(L, map, p, rows[p], KFs[p], &n)) return rc; }
+    const BowMapFlags F = {map->d_kf.p, map->kf_row_cap, map->S.state, rows};
+    return bow_rig_batch_locked(L, lf, R, rf, B, v, P, frame, KFs, nullptr, &F, nnratio, check_ori, assigned, nmatches_out);
+}
+
+}  // extern "C"
+
+// ---- Tracking::SearchLocalPoints on the map's own sets: frame b against set set0 + b as the last build left it ----
+// The set records are copied under the map's mutex; the search then reads the sets' memory from its stream, under the rule every batch on a map's set
+// is under: fetch before the set is rebuilt.
+namespace {
+int map_sets_check(const orbx_extractor* h, const orbm_map* map, int set0, int B, std::vector<MapSetRec>* recs) {
+    if (!map) return fail(ORBX_E_ARG, "null map");
+    if (int rc = map_search_check(h, map)) return rc;
+    if (set0 < 0) return fail(ORBX_E_ARG, "set0 = %d is negative", set0);
+    if (B <= 0) return fail(ORBX_E_ARG, "bad frame range");
+    if ((long long)set0 + B > map->max_sets) return fail(ORBX_E_CAPACITY, "sets [%d, %lld): the map has %d sets", set0, (long long)set0 + B, map->max_sets);
+    std::lock_guard<std::mutex> lk(map->mu);
+    recs->assign(map->set_rec.begin() + set0, map->set_rec.begin() + set0 + B);
+    for (int b = 0; b < B; b++) (*recs)[b].M = map->built[set0 + b] ? map->sets[set0 + b].M : 0;      // (never built, or its build failed: an empty map)
+    return ORBX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int orbm_search_local_points_batch_map(orbx_extractor* h, int first, int B, const OrbmFrustumView* frames, orbm_map* map, int set0, const uint8_t* occupied,
+                                       int use_u_right, float cos_limit, float th, int far_points, float th_far, float nnratio, int want_in_view) {
+    batch_clear(h);
+    if (!h || !frames) return fail(ORBX_E_ARG, "null");
+    std::vector<MapSetRec> recs;
+    if (int rc = map_sets_check(h, map, set0, B, &recs)) return rc;
+    return local_points_batch(h, first, B, frames, nullptr, nullptr, nullptr, nullptr, occupied, use_u_right, cos_limit, th, far_points, th_far, nnratio, want_in_view, recs.data());
+}
+
+int orbm_search_local_points_rig_batch_map(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const OrbmFrustumRigView* frames, orbm_map* map, int set0,
+                                           const uint8_t* occupied, float cos_limit, float th, int far_points, float th_far, float nnratio, int want_in_view) {
+    batch_clear(L);
+    if (!L || !R || !frames) return fail(ORBX_E_ARG, "null");
+    std::vector<MapSetRec> recs;
+    if (int rc = map_sets_check(L, map, set0, B, &recs)) return rc;
+    return local_points_rig_batch(L, lf, R, rf, B, frames, nullptr, nullptr, nullptr, nullptr, occupied, cos_limit, th, far_points, th_far, nnratio, want_in_view, recs.data());
+}
+
+int orbm_search_local_points_fetch_slots(orbx_extractor* h, int* assigned_slot, int cap, int* nmatches, uint8_t* in_view) {
+    if (!h || h->batch.B <= 0) return fail(ORBX_E_ARG, "no batched local point search is pending");
+    if (h->batch.rig) return fail(ORBX_E_ARG, "the pending batch is a rig batch: fetch it with orbm_search_rig_batch_fetch_slots");
+    if (!h->batch.slot_result) return fail(ORBX_E_ARG, "the pending batch was not enqueued on a map's sets (orbm_search_local_points_batch_map): it has no slots to return");
+    if (assigned_slot && cap < h->kp_total_cap) return fail(ORBX_E_CAPACITY, "assigned rows need %d entries", h->kp_total_cap);
+    const bool fetch_view = in_view && h->batch.want_view && h->batch.M > 0;
+    const int rc = batch_fetch(h, h->kp_total_cap, "batched local point search", assigned_slot, cap, nmatches, 1, fetch_view, &in_view, true);
+    if (rc) return rc;
+    if (in_view && !fetch_view) return fail(ORBX_E_ARG, "in_view was not requested at enqueue time");
+    return ORBX_OK;
+}
+
+int orbm_search_rig_batch_fetch_slots(orbx_extractor* L, int* assigned_slot, int cap, int* nmatches, uint8_t* in_view, uint8_t* in_view_r) {
+    if (!L || L->batch.B <= 0 || !L->batch.rig) return fail(ORBX_E_ARG, "no batched rig search is pending");
+    if (!L->batch.slot_result) return fail(ORBX_E_ARG, "the pending batch was not enqueued on a map's sets (orbm_search_local_points_rig_batch_map): it has no slots to return");
+    if (assigned_slot && cap < 2 * L->kp_total_cap) return fail(ORBX_E_ARG, "assigned rows need %d entries (2 x orbx_max_keypoints)", 2 * L->kp_total_cap);
+    if ((in_view || in_view_r) && !L->batch.want_view) return fail(ORBX_E_ARG, "in_view was not requested at enqueue time");
+    uint8_t* const views[2] = {in_view, in_view_r};
+    return batch_fetch(L, 2 * (size_t)L->kp_total_cap, "batched rig search", assigned_slot, cap, nmatches, 2, L->batch.want_view && L->batch.M > 0, views, true);
+}
+
+int orbm_map_sets_fetch(orbx_extractor* h, const orbm_map* m, int set0, int B, const int* start, int* slots, uint8_t* seen) {
+    if (int rc = map_call_check(h, m)) return rc;
+    if (set0 < 0 || B < 0) return fail(ORBX_E_ARG, "negative set0 / number of sets");
+    if (B == 0) return ORBX_OK;
+    if (!start) return fail(ORBX_E_ARG, "null start");
+    if ((long long)set0 + B > m->max_sets) return fail(ORBX_E_ARG, "sets [%d, %lld): the map has %d sets", set0, (long long)set0 + B, m->max_sets);
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (start[0] < 0) return fail(ORBX_E_ARG, "set %d: negative start", set0);
+    // every set's [slots | .. | seen] lies in one piece of its block: one copy each into the handle's pinned buffer, ONE wait for all of them
+    Bump hb;
+    std::vector<size_t> at(B);
+    for (int b = 0; b < B; b++) {
+        const int s = set0 + b;
+        if (!m->built[s]) return fail(ORBX_E_ARG, "set %d has not been built (the map has %d sets)", s, m->max_sets);
+        const long long span = (long long)start[b + 1] - start[b];
+        if (span < (long long)m->sets[s].M) return fail(ORBX_E_ARG, "set %d: its %d entries do not fit the %lld between start[%d] and start[%d]", s, m->sets[s].M, span, b, b + 1);
+        const size_t M = m->sets[s].M;
+        at[b] = hb.take(M ? (size_t)(m->set_rec[s].seen - (const uint8_t*)m->set_rec[s].slots) + M : 0);
+    }
+    rt::set_device(h->device);
+    const bool direct = rt::memory_is_host();
+    if (!direct && h->h_res.ensure(hb.o + 64)) return fail(ORBX_E_DEVICE, "pinned allocation failed");
+    for (int b = 0; b < B && !direct; b++) {
+        const int s = set0 + b; const size_t M = m->sets[s].M;
+        if (!M) continue;
+        const uint8_t* src = (const uint8_t*)m->set_rec[s].slots;
+        if (rt::copy_d2h(h->h_res.p + at[b], src, (size_t)(m->set_rec[s].seen - src) + M, h->s0)) return fail(ORBX_E_DEVICE, "set %d: download failed: %s", s, rt::last_error());
+    }
+    if (rt::stream_sync(h->s0)) return fail(ORBX_E_DEVICE, "sets [%d, %d): download failed: %s", set0, set0 + B, rt::last_error());
+    for (int b = 0; b < B; b++) {
+        const int s = set0 + b; const size_t M = m->sets[s].M;
+        if (!M) continue;
+        const uint8_t* src = (const uint8_t*)m->set_rec[s].slots; const size_t o_seen = (size_t)(m->set_rec[s].seen - src);
+        const uint8_t* got = direct ? src : h->h_res.p + at[b];
+        if (slots) memcpy(slots + start[b], got, 4 * M);
+        if (seen) memcpy(seen + start[b], got + o_seen, M);
+    }
+    return ORBX_OK;
 }
 
 }  // extern "C"

@@ -68,6 +68,7 @@ struct PendingBatch {
     std::vector<int> M_b;                        // map points per frame; empty: M for every frame
     size_t o_result = 0, o_view[2] = {0, 0};     // in d_lp: the ResultBlock; mbTrackInView and (rig) mbTrackInViewR, frame b's row at the prefix sum of M_b
     bool want_view = false, rig = false;         // the views were asked for at enqueue time; a rig batch: [B][2 cap] assignments
+    bool slot_result = false;                    // enqueued on a map's own sets: the ResultBlock carries `assigned` a second time, as map slots
     int m(size_t b) const { return M_b.empty() ? M : M_b[b]; }
 };
 }

@@ -236,6 +236,9 @@ __global__ void k_map_rows_gather(MapStore S, int cap, const int* __restrict__ n
                                   float* __restrict__ min_d, float* __restrict__ max_d, float* __restrict__ angle);
 __global__ void k_map_row_flags(const int* __restrict__ kf_slots, int row_cap, const uint8_t* __restrict__ state, const MapRowFlagRec* __restrict__ recs,
                                 uint8_t* __restrict__ flags);
+// a batched SearchLocalPoints on the map's own sets: the call-time flags from the sets' seen bytes, and `assigned` as map slots
+__global__ void k_map_set_flags(const SetFlagRec* __restrict__ recs, uint8_t* __restrict__ bad, uint8_t* __restrict__ obs);
+__global__ void k_assigned_slots(const SetFlagRec* __restrict__ recs, const int* __restrict__ assigned, int S, int* __restrict__ out);
 
 __global__ void k_distinctive(const unsigned long long* __restrict__ desc, const int* __restrict__ start, int P, int* __restrict__ best);
 template <bool kLds>        // instantiated for both forms in k_match.hip

@@ -112,9 +112,14 @@ struct MapSeg { int set, row, n, pos0, chunk0; };
 // one point set the map builds: where its M points go, slot by slot (slots: which store slot point j is; seen: 1 = the slot is in set `set`'s seen list)
 struct MapSetRec { int* slots; uint8_t* seen; unsigned long long* desc; float *pos, *normal, *min_d, *max_d; int M, set; };
 // the rows of one frame of a map-fed projection batch (k_map_rows_gather), key-frame form: the key frame's row of slots in the map and the keypoints of
-// the same key frame, resident (pKF->mvKeysUn[i].angle is read); n: the row's length.  flag record of k_map_row_flags: {row, n, offset into the flag block}
+// the same key frame, resident (pKF->mvKeysUn[i].angle is read); n: the row's length.  flag record of k_map_row_flags: {row, n, offset into the flag block,
+// rule: kRowHoldsGoodPoint = the slot holds a point that is not bad (`!pMP || pMP->isBad()`), kRowHoldsPoint = the slot holds a point, its bad flag is not read}
 struct MapRowRec { const int* slots; const KeyPointRec* kps; };
-struct MapRowFlagRec { int row, n, off; };
+struct MapRowFlagRec { int row, n, off, rule; };
+constexpr int kRowHoldsGoodPoint = 0, kRowHoldsPoint = 1;
+// one frame of a batched SearchLocalPoints on the map's own sets (orbm_search_local_points_batch_map / _rig_batch_map): the seen bytes and the slot list
+// of its set where the build left them, the set's M, and where the frame's rows start in the batch's flag blocks (the prefix sum of M_b)
+struct SetFlagRec { const uint8_t* seen; const int* slots; int M, off; };
 // one map point of orbm_distinctive_descriptors_resident (k_distinctive_resident): its observations are entries [start, start + n) of the call's
 // observation table (n >= 1: points without observations are not launched); store: the descriptor of its slot in the map's store (nullptr: not written)
 struct DistinctiveRec { unsigned long long* store; int start, n; };

@@ -103,6 +103,43 @@ class ORBmatcher:
         ext._lib.check(ext._lib.L.orbm_search_by_bow_resident(ext._h, n, p1, q1, p2, q2, self.mfNNratio, int(frame_version), int(self.mbCheckOrientation), po, nm.ctypes.data))
         return [(int(nm[p]), outs[p][:kf1s[p].N]) for p in range(n)]
 
+    def SearchForTriangulationResidentMap(self, ext, kf1, row1, kf2s, rows2, resident_map, F12s, eps, bOnlyStereo=False, bCoarse=False, cams=None):
+        """SearchForTriangulationResident with the flags read on the device from the key frames' rows in a ResidentMap
+        (orbm_search_for_triangulation_resident_map): row1 / rows2[j] = the rows of kf1 / kf2s[j]; a feature has a map point iff its slot is >= 0 and
+        holds a point - the bad flag is not read (src/ORBmatcher.cc:1123-1127, :1159-1163).  cams: a ctypes array of n2 OrbmKB8Pair in place of F12s
+        (orbm_search_for_triangulation_resident_kb8_map).  Returns the same list of (nmatches, pairs)."""
+        n2 = len(kf2s)
+        E = np.ascontiguousarray(eps, np.float32).reshape(n2, 2)
+        ptrs = (C.c_void_p * max(n2, 1))(*[k._kf for k in kf2s])
+        r2 = np.ascontiguousarray(rows2, np.int32)
+        if len(r2) != n2:
+            raise ValueError("%d rows for %d neighbours" % (len(r2), n2))
+        N1 = kf1.N
+        m12 = np.full((max(n2, 1), max(N1, 1)), -1, np.int32); nm = np.zeros(max(n2, 1), np.int32)
+        tail = (E.ctypes.data, int(bOnlyStereo), int(bCoarse), int(self.mbCheckOrientation), m12.ctypes.data, nm.ctypes.data)
+        if cams is None:
+            F = np.ascontiguousarray(F12s, np.float32).reshape(n2, 9)
+            ext._lib.check(ext._lib.L.orbm_search_for_triangulation_resident_map(ext._h, kf1._kf, int(row1), n2, ptrs, r2.ctypes.data, resident_map._m, F.ctypes.data, *tail))
+        else:
+            ext._lib.check(ext._lib.L.orbm_search_for_triangulation_resident_kb8_map(ext._h, kf1._kf, int(row1), n2, ptrs, r2.ctypes.data, resident_map._m, C.addressof(cams), *tail))
+        m12 = m12.reshape(-1)[:n2 * N1].reshape(n2, N1) if N1 > 0 else m12[:n2, :0]
+        return [(int(nm[j]), [(int(i), int(m12[j, i])) for i in np.nonzero(m12[j] >= 0)[0]]) for j in range(n2)]
+
+    def SearchByBoWResidentMap(self, ext, kf1s, rows1, kf2s, rows2, resident_map, frame_version=True):
+        """SearchByBoWResident with the flags read on the device from the key frames' rows in a ResidentMap (orbm_search_by_bow_resident_map):
+        rows1[p] = the row of kf1s[p], rows2 = None or rows2[p] = the row of kf2s[p] or -1 (every feature of kf2s[p] is eligible); an entry counts iff
+        its slot is >= 0 and holds a point that is not bad.  Returns the same list of (nmatches, matches12)."""
+        n = len(kf1s)
+        p1 = (C.c_void_p * max(n, 1))(*[k._kf for k in kf1s]); p2 = (C.c_void_p * max(n, 1))(*[k._kf for k in kf2s])
+        r1 = np.ascontiguousarray(rows1, np.int32); r2 = None if rows2 is None else np.ascontiguousarray(rows2, np.int32)
+        if len(r1) != n or (r2 is not None and len(r2) != n):
+            raise ValueError("the row lists need %d entries" % n)
+        outs = [np.full(max(k.N, 1), -1, np.int32) for k in kf1s]
+        po = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs]); nm = np.zeros(max(n, 1), np.int32)
+        ext._lib.check(ext._lib.L.orbm_search_by_bow_resident_map(ext._h, n, p1, r1.ctypes.data, p2, None if r2 is None else r2.ctypes.data, resident_map._m, self.mfNNratio,
+                                                                  int(frame_version), int(self.mbCheckOrientation), po, nm.ctypes.data))
+        return [(int(nm[p]), outs[p][:kf1s[p].N]) for p in range(n)]
+
     def SearchByBoWFramesBatch(self, ext, voc, kfs, mps, first=0, resident_map=None, rows=None):
         """ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) for the frames [first, first + len(kfs)) of ext's last extraction on the device
         (orbm_search_by_bow_frames_batch): voc = the ORBVocabulary whose transform_extracted(ext, first, B, levelsup) has run on these frames, kfs[b] = the
@@ -128,21 +165,31 @@ class ORBmatcher:
         ext._lib.check(ext._lib.L.orbm_search_by_bow_frames_batch(ext._h, voc._v, int(first), B, p1, q1, self.mfNNratio, int(self.mbCheckOrientation), po, nm.ctypes.data))
         return [(int(nm[b]), outs[b][:kfs[b].N]) for b in range(B)]
 
-    def SearchByBoWRigBatch(self, exL, lf, exR, rf, voc, frames, kfs, mps, n_frame=None):
+    def SearchByBoWRigBatch(self, exL, lf, exR, rf, voc, frames, kfs, mps, n_frame=None, resident_map=None, rows=None):
         """ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) for fisheye-rig frames on the device (orbm_search_by_bow_rig_batch): voc = the
         ORBVocabulary whose transform_rig_extracted(exL, lf, exR, rf, B, levelsup) ran last; pair p = rig frame frames[p] of that transform against the
         ResidentKeyFrame kfs[p] (rig or one camera), mps[p] = uint8 flags "feature of kfs[p] has a good map point".  Returns [(nmatches, assigned)]
         with assigned[j] = key-frame feature whose map point goes to vpMapPointMatches[j] or -1: Nleft + Nright entries when n_frame[b] gives them
-        per frame, else the whole row of 2 x max_keypoints."""
+        per frame, else the whole row of 2 x max_keypoints.
+        resident_map, rows (mps = None): the flags are read on the device from rows[p], the row of kfs[p] in the ResidentMap, as SearchByBoWFramesBatch
+        (orbm_search_by_bow_rig_batch_map)."""
         P = len(kfs)
         fr = np.ascontiguousarray(frames, np.int32)
-        assert len(fr) == P and len(mps) == P
         S = 2 * exL.max_keypoints()
         p1 = (C.c_void_p * max(P, 1))(*[k._kf for k in kfs])
-        a1 = [np.ascontiguousarray(m, np.uint8) for m in mps]
-        q1 = (C.c_void_p * max(P, 1))(*[m.ctypes.data for m in a1])
         outs = [np.full(S, -1, np.int32) for _ in range(P)]
         po = (C.c_void_p * max(P, 1))(*[o.ctypes.data for o in outs]); nm = np.zeros(max(P, 1), np.int32)
+        if resident_map is not None or rows is not None:
+            if resident_map is None or rows is None or mps is not None:
+                raise ValueError("the map-fed form takes resident_map and rows, and mps = None")
+            r = np.ascontiguousarray(rows, np.int32)
+            assert len(fr) == P and len(r) == P
+            exL._lib.check(exL._lib.L.orbm_search_by_bow_rig_batch_map(exL._h, int(lf), exR._h, int(rf), int(getattr(voc, "_rig_B", 0)), voc._v, P, fr.ctypes.data, p1,
+                                                                       resident_map._m, r.ctypes.data, self.mfNNratio, int(self.mbCheckOrientation), po, nm.ctypes.data))
+            return [(int(nm[p]), outs[p] if n_frame is None else outs[p][:int(n_frame[fr[p]])]) for p in range(P)]
+        assert len(fr) == P and len(mps) == P
+        a1 = [np.ascontiguousarray(m, np.uint8) for m in mps]
+        q1 = (C.c_void_p * max(P, 1))(*[m.ctypes.data for m in a1])
         exL._lib.check(exL._lib.L.orbm_search_by_bow_rig_batch(exL._h, int(lf), exR._h, int(rf), int(getattr(voc, "_rig_B", 0)), voc._v, P, fr.ctypes.data, p1, q1,
                                                                self.mfNNratio, int(self.mbCheckOrientation), po, nm.ctypes.data))
         return [(int(nm[p]), outs[p] if n_frame is None else outs[p][:int(n_frame[fr[p]])]) for p in range(P)]
@@ -781,6 +828,19 @@ class ResidentMap:
         self._lib.check(self._lib.L.orbm_map_set_fetch(self._h(ext), self._m, int(b), slots.ctypes.data, seen.ctypes.data))
         return slots, seen
 
+    def set_sizes(self, set0, B, ext=None):
+        """M of sets set0 .. set0 + B - 1 (0 for a set that was never built)"""
+        L = self._lib.L
+        return [L.orbm_points_count(C.c_void_p(L.orbm_map_set(self._h(ext), self._m, int(set0) + b))) for b in range(B)]
+
+    def fetch_sets(self, set0, B, ext=None):
+        """what fetch(set0) .. fetch(set0 + B - 1) return, with one host wait (orbm_map_sets_fetch): (start [B + 1], slots [start[B]], seen [start[B]]);
+        set set0 + b's entries are [start[b], start[b + 1])"""
+        start = np.cumsum([0] + self.set_sizes(set0, B, ext)).astype(np.int32)
+        slots = np.zeros(int(start[-1]), np.int32); seen = np.zeros(int(start[-1]), np.uint8)
+        self._lib.check(self._lib.L.orbm_map_sets_fetch(self._h(ext), self._m, int(set0), int(B), start.ctypes.data, slots.ctypes.data, seen.ctypes.data))
+        return start, slots, seen
+
     def close(self):
         if self._m:
             self._lib.L.orbm_map_destroy(self._ext._h, self._m); self._m = None
@@ -831,6 +891,8 @@ class _FrameMaps:
 
 def _maps_of(resident, B):
     """the per-frame form of a batch's `resident` argument (None: it is ONE ResidentPoints), and the width of its in_view rows"""
+    if isinstance(resident, ResidentMap):        # the map's own sets: their sizes are read at enqueue time
+        return None, 1
     if not isinstance(resident, (list, tuple)):
         return None, max(resident.M, 1)
     if len(resident) != B:
@@ -891,10 +953,14 @@ class LocalPointsBatch:
     returns (assigned [B, cap], nmatches [B], in_view [B, M] or None).
     Independent streams: `resident` = a list of B ResidentPoints (or None = empty map), frame b is searched against its own
     (orbm_search_local_points_batch_maps); is_bad / has_obs of enqueue() are then lists of B arrays (or None), assigned[b] indexes frame b's set and
-    in_view is [B, M_max], zero beyond M_b."""
+    in_view is [B, M_max], zero beyond M_b.
+    On a resident map: `resident` = a ResidentMap, frame b is searched against the map's set set0 + b as its last build left it
+    (orbm_search_local_points_batch_map): the seen bytes of the set are its is_bad, every point counts as observed, enqueue() takes neither, and
+    fetch_slots() returns assigned as map SLOTS (fetch() still returns positions in the sets' lists)."""
 
-    def __init__(self, ext, resident, B, cam, bounds, mbf, scale_factors):
+    def __init__(self, ext, resident, B, cam, bounds, mbf, scale_factors, set0=0):
         self.ext, self.res, self.B = ext, resident, B
+        self.map, self.set0 = (resident if isinstance(resident, ResidentMap) else None), int(set0)
         self.cam, self.bounds, self.mbf = cam, bounds, mbf
         self.sf = np.ascontiguousarray(scale_factors, np.float32)
         self.views = (_FrustumView * B)()
@@ -915,6 +981,15 @@ class LocalPointsBatch:
         self._again = lambda: self.enqueue(first, is_bad, has_obs, occupied, use_u_right, viewing_cos_limit, th, far_points, th_far, nnratio, want_in_view)
         ptr = lambda a: None if a is None else a.ctypes.data
         self._want = bool(want_in_view)
+        if self.map is not None:
+            if is_bad is not None or has_obs is not None:
+                raise ValueError("a batch on a ResidentMap reads its flags from the map's sets: is_bad / has_obs cannot be given")
+            if self._want:
+                self.in_view = np.zeros((self.B, max(self.map.set_sizes(self.set0, self.B, self.ext) + [1])), np.uint8)
+            self._keep = (None, None, u8(occupied))
+            L.check(L.L.orbm_search_local_points_batch_map(self.ext._h, int(first), self.B, self.views, self.map._m, self.set0, ptr(self._keep[2]), int(bool(use_u_right)),
+                                                           float(viewing_cos_limit), float(th), int(far_points), float(th_far), float(nnratio), int(self._want)))
+            return
         if self.maps is not None:
             table, flags = self.maps.table(is_bad, has_obs)
             self._keep = (table, flags, u8(occupied))
@@ -925,14 +1000,19 @@ class LocalPointsBatch:
         L.check(L.L.orbm_search_local_points_batch(self.ext._h, int(first), self.B, self.views, self.res._p, ptr(self._keep[0]), ptr(self._keep[1]), ptr(self._keep[2]),
                                                    int(bool(use_u_right)), float(viewing_cos_limit), float(th), int(far_points), float(th_far), float(nnratio), int(self._want)))
 
-    def fetch(self):
+    def fetch(self, _call="orbm_search_local_points_fetch"):
         L = self.ext._lib
-        rc = L.L.orbm_search_local_points_fetch(self.ext._h, self.assigned.ctypes.data, self.cap, self.nm.ctypes.data, self.in_view.ctypes.data if self._want else None)
+        fetch = lambda: getattr(L.L, _call)(self.ext._h, self.assigned.ctypes.data, self.cap, self.nm.ctypes.data, self.in_view.ctypes.data if self._want else None)
+        rc = fetch()
         if rc == -4:                 # ORBX_E_CAPACITY: the candidate pool was too small for this scene and has been enlarged - run the batch again
             self._again()
-            rc = L.L.orbm_search_local_points_fetch(self.ext._h, self.assigned.ctypes.data, self.cap, self.nm.ctypes.data, self.in_view.ctypes.data if self._want else None)
+            rc = fetch()
         L.check(rc)
         return self.assigned, self.nm, (self.in_view if self._want else None)
+
+    def fetch_slots(self):
+        """fetch() of a batch on a ResidentMap with assigned[b, i] = the map slot of the point written to keypoint i (negative entries as in fetch())"""
+        return self.fetch("orbm_search_local_points_fetch_slots")
 
 
 class LocalPointsRigBatch:
@@ -942,10 +1022,13 @@ class LocalPointsRigBatch:
     ResidentPoints.  set_poses() takes B pose dicts as SearchLocalPointsRig does.  enqueue() is asynchronous, fetch() returns (assigned [B, 2 cap]
     in the slot layout of F.mvpMapPoints, nmatches [B], in_view [B, M] or None, in_view_r [B, M] or None).
     Independent streams: `resident` = a list of B ResidentPoints (or None), is_bad / has_obs lists of B arrays (or None), as LocalPointsBatch
-    (orbm_search_local_points_rig_batch_maps); in_view / in_view_r are then [B, M_max]."""
+    (orbm_search_local_points_rig_batch_maps); in_view / in_view_r are then [B, M_max].
+    On a resident map: `resident` = a ResidentMap, frame b against the map's set set0 + b (orbm_search_local_points_rig_batch_map), as LocalPointsBatch;
+    fetch_slots() returns both cameras' halves of assigned as map slots."""
 
-    def __init__(self, left, right, resident, B, cam1, cam2, bounds, scale_factors, left_first=0, right_first=None):
+    def __init__(self, left, right, resident, B, cam1, cam2, bounds, scale_factors, left_first=0, right_first=None, set0=0):
         self.ext, self.right, self.res, self.B = left, right, resident, B
+        self.map, self.set0 = (resident if isinstance(resident, ResidentMap) else None), int(set0)
         self.lf, self.rf = int(left_first), int((B if right is left else 0) if right_first is None else right_first)
         self.cam1, self.cam2, self.bounds = cam1, cam2, bounds
         self.sf = np.ascontiguousarray(scale_factors, np.float32)
@@ -965,6 +1048,16 @@ class LocalPointsRigBatch:
         self._again = lambda: self.enqueue(is_bad, has_obs, occupied, viewing_cos_limit, th, far_points, th_far, nnratio, want_in_view)
         ptr = lambda a: None if a is None else a.ctypes.data
         self._want = bool(want_in_view)
+        if self.map is not None:
+            if is_bad is not None or has_obs is not None:
+                raise ValueError("a batch on a ResidentMap reads its flags from the map's sets: is_bad / has_obs cannot be given")
+            if self._want:
+                width = max(self.map.set_sizes(self.set0, self.B, self.ext) + [1])
+                self.in_view = np.zeros((self.B, width), np.uint8); self.in_view_r = np.zeros((self.B, width), np.uint8)
+            self._keep = (None, None, u8(occupied))
+            L.check(L.L.orbm_search_local_points_rig_batch_map(self.ext._h, self.lf, self.right._h, self.rf, self.B, self.views, self.map._m, self.set0, ptr(self._keep[2]),
+                                                               float(viewing_cos_limit), float(th), int(far_points), float(th_far), float(nnratio), int(self._want)))
+            return
         if self.maps is not None:
             table, flags = self.maps.table(is_bad, has_obs)
             self._keep = (table, flags, u8(occupied))
@@ -976,17 +1069,21 @@ class LocalPointsRigBatch:
                                                        ptr(self._keep[1]), ptr(self._keep[2]), float(viewing_cos_limit), float(th), int(far_points), float(th_far),
                                                        float(nnratio), int(self._want)))
 
-    def _fetch(self):
+    def _fetch(self, call="orbm_search_rig_batch_fetch"):
         iv = lambda a: a.ctypes.data if self._want else None
-        return self.ext._lib.L.orbm_search_rig_batch_fetch(self.ext._h, self.assigned.ctypes.data, self.cap, self.nm.ctypes.data, iv(self.in_view), iv(self.in_view_r))
+        return getattr(self.ext._lib.L, call)(self.ext._h, self.assigned.ctypes.data, self.cap, self.nm.ctypes.data, iv(self.in_view), iv(self.in_view_r))
 
-    def fetch(self):
-        rc = self._fetch()
+    def fetch(self, _call="orbm_search_rig_batch_fetch"):
+        rc = self._fetch(_call)
         if rc == -4:                 # ORBX_E_CAPACITY: the candidate pool was too small for this scene and has been enlarged - run the batch again
             self._again()
-            rc = self._fetch()
+            rc = self._fetch(_call)
         self.ext._lib.check(rc)
         return self.assigned, self.nm, (self.in_view if self._want else None), (self.in_view_r if self._want else None)
+
+    def fetch_slots(self):
+        """fetch() of a batch on a ResidentMap with both halves of assigned as map slots (orbm_search_rig_batch_fetch_slots)"""
+        return self.fetch("orbm_search_rig_batch_fetch_slots")
 
 
 class LastFrameRigBatch:

@@ -9,14 +9,19 @@ Rows per B:
   (c) create_search         B x orbm_points_create from arrays the host has gathered beforehand + the same search + B x orbm_points_destroy
       host_walk_gather      the host's own list walk and gather for (c), in numpy (first occurrence over the concatenated rows, fancy indexing of five
                             arrays): NOT part of (c)
-  (d) update_200            orbm_map_update of 200 points;  set_keyframe: orbm_map_set_keyframe of one row of 1000
+  (d) map_search            (a) + orbm_search_local_points_batch_map on the map's sets + orbm_search_local_points_fetch_slots: no set fetch, no flag
+                            array, no table, and the answer in slots
+      update_200            orbm_map_update of 200 points;  set_keyframe: orbm_map_set_keyframe of one row of 1000
 Both (b) and (c) build their OrbmFrameMap table inside the timed call.  Warm-up, then median and p10 / p90 over the repetitions; prints one JSON line.
+"alternating": (b), (c) and (d) timed in ONE loop, one call of each inside every repetition, so that whatever drifts during the run drifts under all three;
+d_over_b and d_over_c are ratios of those medians.  The routes' results are asserted equal first ((d)'s slots = the lists' slots at (b)'s positions).
 Usage: python tools/bench_local_map_build.py [--out profiles/local_map_build/bench.json] [--reps 20] [--lib other_build.so] [--batches 1,8,64]"""
 import argparse
 import ctypes as C
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -37,6 +42,18 @@ def host_list(rows_cat, good):
     s = s[good[s]]
     _, first = np.unique(s, return_index=True)
     return s[np.sort(first)]
+
+
+def alternating(fns, reps, warm=3):
+    """{name: median / p10 / p90 in ms} of the routes, one call of each inside every repetition"""
+    for _ in range(warm):
+        for fn in fns.values():
+            fn()
+    t = {name: [] for name in fns}
+    for _ in range(reps):
+        for name, fn in fns.items():
+            t0 = time.perf_counter(); fn(); t[name].append((time.perf_counter() - t0) * 1e3)
+    return {name: dict(ms=float(np.median(v)), p10=float(np.percentile(v, 10)), p90=float(np.percentile(v, 90))) for name, v in t.items()}
 
 
 def bench(lib, batches, reps):
@@ -134,8 +151,22 @@ def bench(lib, batches, reps):
             assert Mo[b] == len(lists[b]) and np.array_equal(slots_buf[b][:Mo[b]], lists[b]) and np.array_equal(seen_buf[b][:Mo[b]], flags_c[b]), "stream %d: the lists differ" % b
         asg_c, nm_c, _ = c_fn()
         assert np.array_equal(nm_b, nm_c) and np.array_equal(asg_b, asg_c)
+        on_map = M.LocalPointsBatch(ex, mp, B, cam, bounds, MBF, sfs)
+        on_map.views = views
+
+        def d_fn():
+            a_fn()
+            on_map.enqueue(0, th=3.0)
+            return on_map.fetch_slots()
+        asg_d, nm_d, _ = d_fn()
+        assert np.array_equal(nm_d, nm_b)
+        for b in range(B):
+            assert np.array_equal(asg_d[b], np.where(asg_b[b] >= 0, lists[b][np.maximum(asg_b[b], 0)], asg_b[b])), "stream %d: (d)'s slots are not (b)'s points" % b
+        alt = alternating(dict(build_search=b_fn, create_search=c_fn, map_search=d_fn), reps)
+        alt["d_over_b"] = alt["map_search"]["ms"] / alt["build_search"]["ms"]; alt["d_over_c"] = alt["map_search"]["ms"] / alt["create_search"]["ms"]
         r = dict(build=timed(a_fn, reps), build_search=timed(b_fn, reps), create_search=timed(c_fn, reps), host_walk_gather=timed(host_fn, max(3, reps // 4), warm=1))
         r["b_over_c"] = r["build_search"]["ms"] / r["create_search"]["ms"]
+        r["alternating"] = alt
         r["local_map_points"] = [int(v) for v in Mo[:4]]; r["positions_per_stream"] = int(sum(len(rows[x]) for x in frames[0])); r["matches"] = int(nm_b.sum())
         out["B%d" % B] = r
     # (d) keeping the store current

@@ -9,6 +9,11 @@ Per search and B:
   bow          (a) map        orbm_search_by_bow_frames_batch_map
                (b) host_flags orbm_search_by_bow_frames_batch with the flags computed in the timed call from a host mirror of rows and slot states
                (c) numpy_flags    that flag computation alone
+Once per run ("resident"), the searches between resident key frames with their flags read from the key frames' rows, each against its host-fed call with
+the flags computed in the timed call from the host mirror, as the bow rows above:
+  triangulation   orbm_search_for_triangulation_resident_map: key frame 0 against up to 20 neighbours (rule: holds a point)
+  bow_keyframes   orbm_search_by_bow_resident_map: key frame 0 paired with up to 8 others, has_map_point1 and eligible2 from rows (rule: holds a good point)
+  bow_rig         orbm_search_by_bow_rig_batch_map: the extraction read as rig frames [L .. | R ..], frame p against key frame p
 The routes of a search alternate inside every repetition; median and p10 / p90 over the repetitions.  (a) and (b) are asserted to return identical results.
 Prints one JSON line.  Usage: python tools/bench_map_rows.py [--out profiles/map_rows/bench.json] [--reps 20] [--lib other_build.so] [--batches 1,8,64]"""
 import argparse
@@ -144,10 +149,42 @@ def bench(lib, batches, reps):
             r["map_over_host_fed_plus_gather"] = r["map"]["ms"] / (r["host_fed"]["ms"] + r["numpy_gather"]["ms"])
         r_bow["map_over_host_flags"] = r_bow["map"]["ms"] / r_bow["host_flags"]["ms"]
         out["B%d" % B] = dict(lastframe=r_last, keyframe=r_key, bow=r_bow)
+    resident = {}
+    if bmax >= 2:
+        row_of = lambda b: slots[b, :n[b]]
+        holds = lambda b: (row_of(b) >= 0).astype(np.uint8)                                            # (every slot of this store holds a point)
+        good = lambda b: ((row_of(b) >= 0) & ~bad[np.where(row_of(b) >= 0, row_of(b), 0)]).astype(np.uint8)
+        same = lambda a, h: all(x[0] == y[0] and np.array_equal(x[1], y[1]) for x, y in zip(a, h))
+        nb = list(range(1, min(bmax, 21)))
+        F = np.stack([np.array([0, 0, 0, 0, 0, -1, 0, 1, 0], np.float32)] * len(nb)); eps = np.stack([np.array([1e6, H / 2], np.float32)] * len(nb))
+        m6 = M.ORBmatcher(0.6, True)
+        tri_map = lambda: m6.SearchForTriangulationResidentMap(ex, kfs[0], 0, [kfs[j] for j in nb], rows[nb], mp, F, eps, False, True)
+        tri_host = lambda: m6.SearchForTriangulationResident(ex, kfs[0], holds(0), [kfs[j] for j in nb], [holds(j) for j in nb], F, eps, False, True)
+        assert tri_map() == tri_host(), "triangulation: the routes differ"
+        r = timed_alternating(dict(map=tri_map, host_flags=tri_host, numpy_flags=lambda: [holds(j) for j in [0] + nb]), reps)
+        r.update(neighbours=len(nb), matches=int(sum(x[0] for x in tri_map())), map_over_host_flags=r["map"]["ms"] / r["host_flags"]["ms"])
+        resident["triangulation"] = r
+        prs = list(range(1, min(bmax, 9)))
+        m7 = M.ORBmatcher(0.7, True)
+        kb_map = lambda: m7.SearchByBoWResidentMap(ex, [kfs[0]] * len(prs), [0] * len(prs), [kfs[j] for j in prs], rows[prs], mp, False)
+        kb_host = lambda: m7.SearchByBoWResident(ex, [kfs[0]] * len(prs), [good(0)] * len(prs), [kfs[j] for j in prs], [good(j) for j in prs], False)
+        assert same(kb_map(), kb_host()), "key-frame bow: the routes differ"
+        r = timed_alternating(dict(map=kb_map, host_flags=kb_host, numpy_flags=lambda: [good(j) for j in [0] + prs]), reps)
+        r.update(pairs=len(prs), matches=int(sum(x[0] for x in kb_map())), map_over_host_flags=r["map"]["ms"] / r["host_flags"]["ms"])
+        resident["bow_keyframes"] = r
+        B2 = bmax // 2                                                                                # (last: the rig transform replaces the vocabulary's run)
+        voc.transform_rig_extracted(ex, 0, ex, B2, B2, 2)
+        fr = np.arange(B2, dtype=np.int32)
+        rig_map = lambda: m7.SearchByBoWRigBatch(ex, 0, ex, B2, voc, fr, kfs[:B2], None, resident_map=mp, rows=rows[:B2])
+        rig_host = lambda: m7.SearchByBoWRigBatch(ex, 0, ex, B2, voc, fr, kfs[:B2], [good(b) for b in range(B2)])
+        assert same(rig_map(), rig_host()), "rig bow: the routes differ"
+        r = timed_alternating(dict(map=rig_map, host_flags=rig_host, numpy_flags=lambda: [good(b) for b in range(B2)]), reps)
+        r.update(pairs=B2, matches=int(sum(x[0] for x in rig_map())), map_over_host_flags=r["map"]["ms"] / r["host_flags"]["ms"])
+        resident["bow_rig"] = r
     for k in kfs:
         k.close()
     mp.close(); voc.close(); ex.close()
-    return dict(shape=dict(W=W, H=H, nfeatures=NF, slots=SLOTS, cap_last=cap, keypoints_per_frame=[int(v) for v in n[:4]]), rows=out)
+    return dict(shape=dict(W=W, H=H, nfeatures=NF, slots=SLOTS, cap_last=cap, keypoints_per_frame=[int(v) for v in n[:4]]), rows=out, resident=resident)
 
 
 def main():
