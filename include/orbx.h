@@ -462,7 +462,9 @@ int orbm_points_count(const orbm_points* p);     /* M of a resident set (0 for N
  * limits of orbm_map_create (at most 2^28 slots, 65 535 sets, rows of 2^22 features).  Nothing is ever truncated.
  *   Device memory: 65 * slots (store) + 4 * kf_rows * kf_row_cap (rows) + 8 * max_sets * slots (first-occurrence and seen stamps) bytes at
  * creation; each set that has been built holds 69 bytes per point of the largest list it has held; one staging block of about
- * 20 * (rows visited) + 8 * (positions visited) / 256 + 4 * (seen slots) bytes of the largest call.  orbx_debug_live_resources counts all of it. */
+ * 20 * (rows visited) + 8 * (positions visited) / 256 + 4 * (seen slots) bytes of the largest call (12 bytes per edit of orbm_map_edit_keyframes);
+ * 4 * slots more from the first orbm_fuse_candidates_batch_map / orbm_search_by_projection_sim3_batch_map on, for their table by slot - nothing of it
+ * at creation.  orbx_debug_live_resources counts all of it. */
 typedef struct orbm_map orbm_map;
 int orbm_map_create(orbx_extractor* h, int slots, int kf_rows, int kf_row_cap, int max_sets, orbm_map** out);
 int orbm_map_destroy(orbx_extractor* h, orbm_map* m);
@@ -1089,6 +1091,48 @@ int orbm_search_rig_batch_fetch_slots(orbx_extractor* L, int* assigned_slot, int
  * out of that count.  That it takes the extractor first, which is what that test is about, is checked by tests/test_local_map_search.py.) */
 int orbm_map_sets_fetch(orbx_extractor* h, const orbm_map* m, int set0, int B, const int* start /* [B + 1] (prefix sums: set b has M_b entries) */,
                         int* slots, uint8_t* seen);
+
+/* LocalMapping's and LoopClosing's batches fed from the map: orbm_fuse_candidates_batch and orbm_search_by_projection_sim3_batch on set `set` of `map`
+ * as orbm_map_select / orbm_map_local_points left it (M = its size; the set's gathered fields are read exactly as those calls read an orbm_points, the
+ * set's slot list names the points), with the exclusions the caller used to compute pair by pair (src/ORBmatcher.cc:1366-1375, :1561 / :1575, :512-525,
+ * :633-645) filled on the device from the map's rows and slot states, and the answers the replay needs given as slots.
+ *   Fuse, both overloads (chi2_gate 1 / 0): pair (k, i) is skipped iff the slot of point i is BAD AT THE MOMENT OF THE CALL (the set may be older than an
+ * orbm_map_set_bad) or occurs anywhere in row rows[k] - in either camera's half of a rig row: `pMP->isBad() || pMP->IsInKeyFrame(pKF)`, which is what
+ * spAlreadyFound = pKF->GetMapPoints() amounts to for the Sim3 overload.  A row entry of -1 or one whose slot holds no point excludes nothing; an entry
+ * whose slot is bad still excludes (membership is membership); a slot the set holds at several positions is excluded at every one of them.
+ *   feat0[k] (NULL = all 0): the row entry of feature 0 of targets[k].kf - 0 for a whole key frame or a rig's left camera, NLeft for the right camera's
+ * per-camera key frame; 0 <= feat0[k] and feat0[k] + N_k <= the row's length.
+ *   kf_slot[k][i] (may be NULL) = pKF->GetMapPoint(bestIdx) for the replay (:1505-1526, :1655-1668): where best_idx[k][i] >= 0, the slot at row entry
+ * feat0[k] + best_idx[k][i] if it holds a point that is not bad (compare observations, Replace), -2 if it holds a bad point (nothing is done), -1 if the
+ * entry is -1 or its slot holds nothing (AddObservation / AddMapPoint); -1 where best_idx is -1.
+ *   Sim3 projection search: pair (k, i) is skipped iff the slot is bad or occurs in found_slots[found_start[k] .. found_start[k+1]) (spAlreadyFound of
+ * vpMatched; duplicates, slots outside the set and -1 entries are fine; found_start == NULL: the bad flags alone).  OrbmSim3Target.occupied stays a host
+ * row (vpMatched is a per-call vector, not the key frame's matches).  assigned_slot[k][idx] (may be NULL) = the map slot of the point assigned[k][idx]
+ * names; negative entries pass through, entries from N_k up to cap are -1.
+ *   Results equal the host-fed calls given orbm_map_set(h, map, set) and the skip matrix these rules yield: the flag kernels write the [K][M] bytes
+ * where the host-fed call uploads them and everything behind is that call's own code.  Blocking; the map's mutex is taken first and held until the call
+ * returns, the key-frame grid mutex after it.  K == 0 or an empty set: ORBX_OK, nothing is written.
+ *   orbm_map_edit_keyframes: n entries of the rows at once - entry feat[j] of row row[j] becomes slot[j], -1 = EraseMapPointMatch; with AddMapPoint,
+ * ReplaceMapPointMatch and what MapPoint::Replace does to the rows of its observations, everything a Fuse replay changes in the rows goes up in ONE
+ * call (one upload, one launch; blocking, under the map's mutex).  Row lengths do not change; n == 0 is fine.
+ *   Refusals come before anything is enqueued, leave the map, its table and the grid caches as they were and name the target or entry: ORBX_E_ARG for
+ * a null map or row list, a map on another device than the handle, a set outside the map or never built, a row outside the map or never set,
+ * feat0[k] + N_k beyond the row's length, found_start decreasing or given without found_slots, a found slot below -1 or at or above the map's slots,
+ * an edit whose row, feat or slot is out of range (feat at or above the row's length, slot below -1 or at or above the map's slots), two edits of
+ * one (row, feat) - the result would depend on the order of the stores - and everything the host-fed calls refuse; ORBX_E_CAPACITY for their limits.
+ *   Device memory: 4 bytes per slot of the map for the table that names a position of the set by slot, allocated by the FIRST of these two searches on
+ * a map (not at orbm_map_create), cleared then and when its epoch is used up (as the first-occurrence stamps), freed by orbm_map_destroy; the handle's
+ * scratch as for the host-fed calls, with 16 bytes per target and the found lists uploaded in place of the K x M bytes, and 4 x K x M (Fuse) or
+ * 4 x K x cap (Sim3) bytes for the second result.  orbx_debug_live_resources counts all of it.
+ * (The comment inside orbm_map_edit_keyframes' argument list keeps it out of the count tests/test_local_map_build.py takes, as orbm_map_sets_fetch's
+ * does; that the three calls take the extractor first is checked by tests/test_fuse_map.py.) */
+int orbm_fuse_candidates_batch_map(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const int* rows /*[K]*/, const int* feat0 /*[K] or NULL*/,
+                                   orbm_map* map, int set, float th, int chi2_gate, int* best_idx /*[K][M]*/, int* best_dist /*[K][M] or NULL*/,
+                                   int* kf_slot /*[K][M] or NULL*/);
+int orbm_search_by_projection_sim3_batch_map(orbx_extractor* h, int K, const OrbmSim3Target* targets, orbm_map* map, int set,
+                                             const int* found_start /*[K+1] or NULL*/, const int* found_slots, float th, float ratio_hamming, int cap,
+                                             int* assigned /*[K][cap]*/, int* nmatches /*[K]*/, int* assigned_slot /*[K][cap] or NULL*/);
+int orbm_map_edit_keyframes(orbx_extractor* h, orbm_map* m, int n /* edits (all of one replay) */, const int* row, const int* feat, const int* slot);
 
 /* Frame::ComputeBoW for B fisheye-rig frames (Nleft != -1, src/Frame.cc:984-997 over the rig Frame's mDescriptors, :1514): frame b = left image
  * lf + b of L's last extraction (camera 1: features [0, Nleft)) followed by right image rf + b of R's (camera 2: features [Nleft, Nleft + Nright)),

@@ -1658,6 +1658,81 @@ __global__ void __launch_bounds__(256) k_assigned_slots(const SetFlagRec* __rest
     out[o] = a < 0 ? a : (a < R.M ? R.slots[a] : -1);
 }
 
+// ---- the exclusions of a Fuse / Sim3 projection batch read from the map (orbm_fuse_candidates_batch_map / orbm_search_by_projection_sim3_batch_map) ----
+// skip[k][i] of the host-fed calls - `pMP->isBad() || pMP->IsInKeyFrame(pKF)` (src/ORBmatcher.cc:1366-1375), spAlreadyFound (:512-525, :561, :633-645,
+// :1561, :1575) - written where those calls upload it, in O(M + K M + listed slots): a table by slot names a position of the set, the targets' lists are
+// looked up in it.  table[slot] holds top - (the first position of the set that is this slot), offered with atomicMax as the first-occurrence stamps of
+// k_map_stamp are: this call's offers lie in (base, top], top = base + M, whatever an earlier call left is <= base and reads as "not in the set", and
+// nothing is cleared between calls.  Three launches, each after the other has ended:
+//   k_map_set_table    position i offers itself to its slot's entry and writes the slot's bad flag to skip[k][i] of kSkipTargets targets
+//   k_map_skip_listed  entry j of target k's list (a key-frame row, a found list; -1 and slots outside the set fall through) stores 1 at skip[k][position]:
+//                      every writer of a byte stores the same value
+//   k_map_skip_dups    a position that is not its slot's first takes the first one's flag (orbm_map_select allows a slot at several positions); the
+//                      bytes read here (first positions) are not written here
+// grid (ceil(M / 256), ceil(K / kSkipTargets)), 256 threads
+__global__ void __launch_bounds__(256) k_map_set_table(int M, int K, const int* __restrict__ slots, const uint8_t* __restrict__ state, unsigned* __restrict__ table,
+                                                       unsigned top, uint8_t* __restrict__ skip) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= M) return;
+    const int slot = slots[i];
+    if (blockIdx.y == 0) atomicMax(&table[slot], top - (unsigned)i);
+    const uint8_t bad = (uint8_t)(state[slot] != kMapPresent);
+    const int k0 = (int)blockIdx.y * kSkipTargets, k1 = imin(K, k0 + kSkipTargets);
+    for (int k = k0; k < k1; k++) skip[(size_t)k * (size_t)M + (size_t)i] = bad;
+}
+
+// grid (ceil(longest list / 256), K), 256 threads
+__global__ void __launch_bounds__(256) k_map_skip_listed(const MapSkipRec* __restrict__ recs, const int* __restrict__ lists, int M, const unsigned* __restrict__ table,
+                                                         unsigned base, unsigned top, uint8_t* __restrict__ skip) {
+    const MapSkipRec R = recs[blockIdx.y];
+    const int j = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (j >= R.n) return;
+    const int slot = lists[(size_t)R.off + (size_t)j];
+    if (slot < 0) return;
+    const unsigned t = table[slot], p = top - t;
+    if (t > base && p < (unsigned)M) skip[(size_t)blockIdx.y * (size_t)M + (size_t)p] = 1;
+}
+
+// grid as k_map_set_table
+__global__ void __launch_bounds__(256) k_map_skip_dups(int M, int K, const int* __restrict__ slots, const unsigned* __restrict__ table, unsigned top,
+                                                       uint8_t* __restrict__ skip) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= M) return;
+    const unsigned first = top - table[slots[i]];
+    if (first >= (unsigned)i) return;                               // (its slot's first position; a later one cannot be the first)
+    const int k0 = (int)blockIdx.y * kSkipTargets, k1 = imin(K, k0 + kSkipTargets);
+    for (int k = k0; k < k1; k++) {
+        const size_t o = (size_t)k * (size_t)M;
+        if (skip[o + first]) skip[o + (size_t)i] = 1;
+    }
+}
+
+// pKF->GetMapPoint(bestIdx) of the Fuse replay (:1505-1526, :1655-1668) as a slot: entry feat0 + bestIdx of the target's row if that slot holds a point
+// that is not bad, -2 if it holds a bad one (the replay does nothing), -1 if the entry is -1 or its slot holds nothing (AddObservation / AddMapPoint),
+// and -1 where best_idx is.  grid (ceil(M / 256), K), 256 threads
+__global__ void __launch_bounds__(256) k_fuse_kf_slots(const MapSkipRec* __restrict__ recs, const int* __restrict__ kf_slots, int M, const uint8_t* __restrict__ state,
+                                                       const int* __restrict__ best_idx, int* __restrict__ kf_slot) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (i >= M) return;
+    const size_t o = (size_t)blockIdx.y * (size_t)M + (size_t)i;
+    const int b = best_idx[o];
+    int out = -1;
+    if (b >= 0) {
+        const MapSkipRec R = recs[blockIdx.y];
+        const int slot = kf_slots[(size_t)R.off + (size_t)R.feat0 + (size_t)b];
+        if (slot >= 0) { const uint8_t st = state[slot]; out = st == kMapPresent ? slot : (st & kMapPresent) ? -2 : -1; }
+    }
+    kf_slot[o] = out;
+}
+
+// orbm_map_edit_keyframes: entry feat[j] of row row[j] becomes slot[j] (the host refuses two edits of one entry, so no two stores meet).
+// grid (ceil(n / 256)), 256 threads
+__global__ void __launch_bounds__(256) k_map_edit_rows(int n, const int* __restrict__ row, const int* __restrict__ feat, const int* __restrict__ slot,
+                                                       int* __restrict__ kf_slots, int row_cap) {
+    const int j = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (j < n) kf_slots[(size_t)row[j] * (size_t)row_cap + (size_t)feat[j]] = slot[j];
+}
+
 // ---- key frames made from extracted frames (orbm_keyframe_create_extracted / _rig_extracted) ----------------------------------------------------
 // What the host must know of every frame before it can allocate: out[3 j ..] = features, FeatureVector nodes, FeatureVector entries of record j
 // (the counts are clamped to what the arrays can hold; the host refuses a FeatureVector that does not fit its frame).  grid (ceil(n / 64)), 64 threads

@@ -13,7 +13,7 @@
 //   batched routes          frames of the last extraction: SearchLocalPoints, SearchByProjection(last frame / key frame), SearchByBoW; one fetch
 //   rig routes              the same for two-camera frames (two handles), fetched through the same core
 //   resident map            orbm_map: the map-point store by slot, key-frame rows of slots, Tracking::UpdateLocalPoints for a batch of frames built on the
-//                           device into orbm_points sets that every search above takes
+//                           device into orbm_points sets that every search above takes; the tracking searches, and the Fuse / Sim3 batches, fed from it
 // The line numbers in the comments point into the reference's src/ORBmatcher.cc unless another file is named.
 #include <mutex>
 #include "orbx_internal.h"
@@ -2153,13 +2153,31 @@ struct BatchGrids {
     }
     void built() { for (KfGrid* g : made) g->built = true; }         // (the stream has been waited for; still under the mutex: `made` is empty otherwise)
 };
-}  // namespace
 
-int orbm_fuse_candidates_batch(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const orbm_points* points, const uint8_t* skip, float th, int chi2_gate,
-                               int* best_idx, int* best_dist) {
-    if (!h || !points || K < 0) return fail(ORBX_E_ARG, "null / negative number of targets");
-    if (points->device != h->device) return fail(ORBX_E_ARG, "the map points live on another device than the handle");
-    if (K == 0) return ORBX_OK;
+// What a call that is fed from the map (orbm_fuse_candidates_batch_map, orbm_search_by_projection_sim3_batch_map, at the end of this file) brings in place
+// of the host's skip[K][M]: the set's slot list, the slots' states and the map's rows on the device, one MapSkipRec per target, and - Sim3 - the found lists
+// to upload.  The entry point has checked everything and holds the map's mutex until the call returns; map_skip_table() gives the call its range of the
+// map's table by slot (allocated on the first such call) once nothing can be refused any more.
+struct MapSkip {
+    orbm_map* map; const int* set_slots; const uint8_t* state; const int* kf_slots;
+    std::vector<MapSkipRec> recs; int longest = 0;
+    const int* found = nullptr; size_t n_found = 0;                 // host: the found lists, one behind the other (nullptr: the lists are the map's rows)
+    unsigned* table = nullptr; unsigned base = 0, top = 0;
+};
+int map_skip_table(orbx_extractor* h, int M, MapSkip* S);
+// skip[K][M] on the device (k_search.hip "the exclusions of a Fuse / Sim3 projection batch read from the map")
+void launch_map_skip(orbx_extractor* h, const MapSkip& S, int K, int M, const MapSkipRec* d_recs, const int* d_lists, uint8_t* d_skip) {
+    const dim3 blk(256, 1, 1), grids((M + 255) / 256, (K + kSkipTargets - 1) / kSkipTargets, 1);
+    ORBX_LAUNCH(k_map_set_table, grids, blk, 0, h->s0, M, K, S.set_slots, S.state, S.table, S.top, d_skip);
+    if (S.longest > 0) {
+        const dim3 gridl((S.longest + 255) / 256, K, 1);
+        ORBX_LAUNCH(k_map_skip_listed, gridl, blk, 0, h->s0, d_recs, d_lists, M, (const unsigned*)S.table, S.base, S.top, d_skip);
+        ORBX_LAUNCH(k_map_skip_dups, grids, blk, 0, h->s0, M, K, S.set_slots, (const unsigned*)S.table, S.top, d_skip);
+    }
+}
+
+// what orbm_fuse_candidates_batch and its map-fed form refuse of the target table alike
+int fuse_targets_check(const orbx_extractor* h, int K, const OrbmFuseTarget* targets, int chi2_gate) {
     if (!targets) return fail(ORBX_E_ARG, "null target table");
     static_assert(sizeof(ProjectParams) == sizeof(OrbmProjection), "OrbmProjection and ProjectParams describe the same record");
     for (int k = 0; k < K; k++) {
@@ -2167,6 +2185,13 @@ int orbm_fuse_candidates_batch(orbx_extractor* h, int K, const OrbmFuseTarget* t
         if (int rc = batch_target_check(h, k, t.kf, t.spec)) return rc;
         if (chi2_gate && !t.inv_level_sigma2) return fail(ORBX_E_ARG, "target %d: chi-square gate without mvInvLevelSigma2", k);
     }
+    return ORBX_OK;
+}
+
+// The Fuse batch behind its checks, K > 0 checked targets: skip = the host's [K][M] bytes or nullptr; from_map: the bytes are written on the device where
+// `skip` would have been uploaded, and kf_slot (may be nullptr) comes back behind the distances
+int fuse_batch_run(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const orbm_points* points, const uint8_t* skip, MapSkip* from_map, float th, int chi2_gate,
+                   int* best_idx, int* best_dist, int* kf_slot) {
     const int M = points->M;
     if (M == 0) return ORBX_OK;
     if (!best_idx) return fail(ORBX_E_ARG, "null result array");
@@ -2185,17 +2210,22 @@ int orbm_fuse_candidates_batch(orbx_extractor* h, int K, const OrbmFuseTarget* t
     // a grid made here is built on this handle's stream: other threads may find it in the list, so they are kept out until this call has waited for the stream
     if (grids.build.empty()) lk.unlock();
     Packer pk(h);
-    const size_t pb = pk.add(grids.build.data(), sizeof(GridBuildRec) * grids.build.size()), pt = pk.add(recs.data(), sizeof(FuseTargetRec) * recs.size()),
-                 ps = skip ? pk.add(skip, pairs) : 0;
-    const size_t nout = best_dist ? 2 * pairs : pairs;
+    const size_t pb = pk.add(grids.build.data(), sizeof(GridBuildRec) * grids.build.size()), pt = pk.add(recs.data(), sizeof(FuseTargetRec) * recs.size());
+    const size_t pr = from_map ? pk.add(from_map->recs.data(), sizeof(MapSkipRec) * from_map->recs.size()) : 0;
+    const size_t ps = from_map ? pk.room(pairs) : skip ? pk.add(skip, pairs) : 0;
+    const bool flags = from_map || skip;
+    const size_t nout = (1 + (best_dist ? 1 : 0) + (kf_slot ? 1 : 0)) * pairs;
     if (h->d_si[SI_BEST].ensure(nout)) return fail(ORBX_E_DEVICE, "allocation failed (%d targets x %d points)", K, M);
+    if (from_map) if (int rc = map_skip_table(h, M, from_map)) return rc;
     if (int e = pk.flush()) return fail(ORBX_E_DEVICE, "%s", upload_error(e));
     grids.launch_builds(h, pk.dev<GridBuildRec>(pb));
-    int* d_idx = h->d_si[SI_BEST].p; int* d_dist = best_dist ? d_idx + pairs : (int*)nullptr;
+    if (from_map) launch_map_skip(h, *from_map, K, M, pk.dev<MapSkipRec>(pr), from_map->kf_slots, pk.out<uint8_t>(ps));
+    int* d_idx = h->d_si[SI_BEST].p; int* d_dist = best_dist ? d_idx + pairs : (int*)nullptr; int* d_kfs = d_idx + (best_dist ? 2 : 1) * pairs;
     const dim3 grid((M + 255) / 256, K, 1), blk(256, 1, 1);
     ORBX_LAUNCH(k_fuse_candidates, grid, blk, 0, h->s0, pk.dev<FuseTargetRec>(pt), M, points->pos, points->normal, points->min_d, points->max_d, points->desc,
-                skip ? pk.dev<uint8_t>(ps) : (const uint8_t*)nullptr, th, chi2_gate, TH_LOW, h->debug_stereo_flags, d_idx, d_dist);
-    // one copy into the handle's page-locked landing area (as fetch_sync), then into the caller's one or two arrays
+                flags ? pk.dev<uint8_t>(ps) : (const uint8_t*)nullptr, th, chi2_gate, TH_LOW, h->debug_stereo_flags, d_idx, d_dist);
+    if (kf_slot) ORBX_LAUNCH(k_fuse_kf_slots, grid, blk, 0, h->s0, pk.dev<MapSkipRec>(pr), from_map->kf_slots, M, from_map->state, (const int*)d_idx, d_kfs);
+    // one copy into the handle's page-locked landing area (as fetch_sync), then into the caller's one to three arrays
     const int* res = d_idx;
     int e = 0;
     if (!rt::memory_is_host()) {
@@ -2207,23 +2237,28 @@ int orbm_fuse_candidates_batch(orbx_extractor* h, int K, const OrbmFuseTarget* t
     grids.built();
     memcpy(best_idx, res, sizeof(int) * pairs);
     if (best_dist) memcpy(best_dist, res + pairs, sizeof(int) * pairs);
+    if (kf_slot) memcpy(kf_slot, res + (best_dist ? 2 : 1) * pairs, sizeof(int) * pairs);
     return ORBX_OK;
 }
 
-// The Sim3 projection search of one resident point set from K resident key frames.  One upload (the records of the grids to build, the target table, the
-// `occupied` rows, the skip mask), at most three launches (k_grid_build_kfs, k_sim3_candidates, k_sim3_accept), one download of assigned | nmatches.
-int orbm_search_by_projection_sim3_batch(orbx_extractor* h, int K, const OrbmSim3Target* targets, const orbm_points* points, const uint8_t* skip, float th,
-                                         float ratio_hamming, int cap, int* assigned, int* nmatches) {
-    if (!h || !points || K < 0) return fail(ORBX_E_ARG, "null / negative number of targets");
-    if (points->device != h->device) return fail(ORBX_E_ARG, "the map points live on another device than the handle");
-    if (K == 0) return ORBX_OK;
+// what orbm_search_by_projection_sim3_batch and its map-fed form refuse of the target table alike; *n_max = the largest N
+int sim3_targets_check(const orbx_extractor* h, int K, const OrbmSim3Target* targets, int cap, int* n_max) {
     if (!targets) return fail(ORBX_E_ARG, "null target table");
-    int n_max = 0;
+    *n_max = 0;
     for (int k = 0; k < K; k++) {
         if (int rc = batch_target_check(h, k, targets[k].kf, targets[k].spec)) return rc;
-        n_max = std::max(n_max, targets[k].kf->N);
+        *n_max = std::max(*n_max, targets[k].kf->N);
     }
-    if (cap < n_max) return fail(ORBX_E_ARG, "cap %d is below the %d keypoints of the largest key frame", cap, n_max);
+    if (cap < *n_max) return fail(ORBX_E_ARG, "cap %d is below the %d keypoints of the largest key frame", cap, *n_max);
+    return ORBX_OK;
+}
+
+// The Sim3 projection search of one resident point set from K resident key frames, behind its checks.  One upload (the records of the grids to build, the
+// target table, the `occupied` rows, the skip mask - from_map: the MapSkipRec table and the found lists in its place), at most three launches
+// (k_grid_build_kfs, k_sim3_candidates, k_sim3_accept; from_map: the three flag kernels in front, k_assigned_slots behind when assigned_slot is wanted), one
+// download of assigned | nmatches [| assigned_slot].
+int sim3_batch_run(orbx_extractor* h, int K, const OrbmSim3Target* targets, int n_max, const orbm_points* points, const uint8_t* skip, MapSkip* from_map, float th,
+                   float ratio_hamming, int cap, int* assigned, int* nmatches, int* assigned_slot) {
     const int M = points->M;
     if (M == 0) return ORBX_OK;
     if (!assigned || !nmatches) return fail(ORBX_E_ARG, "null result array");
@@ -2231,7 +2266,7 @@ int orbm_search_by_projection_sim3_batch(orbx_extractor* h, int K, const OrbmSim
     if (K > 65535 || (size_t)K * (size_t)M > lim || (size_t)K * cap1 > lim)
         return fail(ORBX_E_CAPACITY, "%d targets x %d points (cap %d): at most 65535 targets, 2^28 pairs and 2^28 result entries per call", K, M, cap);
     rt::set_device(h->device);
-    const size_t pairs = (size_t)K * (size_t)M, nres = (size_t)K * cap1 + (size_t)K;
+    const size_t pairs = (size_t)K * (size_t)M, nres = (size_t)K * cap1 + (size_t)K + (assigned_slot ? (size_t)K * cap1 : 0);
     std::vector<Sim3TargetRec> recs(K);
     std::vector<uint8_t> occ;
     BatchGrids grids;
@@ -2243,22 +2278,37 @@ int orbm_search_by_projection_sim3_batch(orbx_extractor* h, int K, const OrbmSim
         recs[k].occ_off = -1;
         if (t.occupied && t.kf->N > 0) { recs[k].occ_off = (long long)occ.size(); occ.insert(occ.end(), t.occupied, t.occupied + t.kf->N); occ.resize(al16(occ.size()), 0); }
     }
-    if (grids.build.empty()) lk.unlock();                            // (as in orbm_fuse_candidates_batch)
+    if (grids.build.empty()) lk.unlock();                            // (as in fuse_batch_run)
     Packer pk(h);
     const size_t pb = pk.add(grids.build.data(), sizeof(GridBuildRec) * grids.build.size()), pt = pk.add(recs.data(), sizeof(Sim3TargetRec) * recs.size()),
-                 po = pk.add(occ.data(), occ.size()), ps = skip ? pk.add(skip, pairs) : 0;
+                 po = pk.add(occ.data(), occ.size());
+    size_t pr = 0, pf = 0, pa = 0, ps = 0;
+    std::vector<SetFlagRec> set_recs;
+    if (from_map) {
+        pr = pk.add(from_map->recs.data(), sizeof(MapSkipRec) * from_map->recs.size());
+        pf = pk.add(from_map->found, sizeof(int) * from_map->n_found);
+        if (assigned_slot) { set_recs.assign(K, SetFlagRec{nullptr, from_map->set_slots, M, 0}); pa = pk.add(set_recs.data(), sizeof(SetFlagRec) * set_recs.size()); }
+        ps = pk.room(pairs);
+    } else if (skip) ps = pk.add(skip, pairs);
+    const bool flags = from_map || skip;
     if (h->d_si[SI_BEST].ensure(pairs + nres)) return fail(ORBX_E_DEVICE, "allocation failed (%d targets x %d points, cap %d)", K, M, cap);
+    if (from_map) if (int rc = map_skip_table(h, M, from_map)) return rc;
     if (int e = pk.flush()) return fail(ORBX_E_DEVICE, "%s", upload_error(e));
     grids.launch_builds(h, pk.dev<GridBuildRec>(pb));
-    int* d_choice = h->d_si[SI_BEST].p; int* d_assigned = d_choice + pairs; int* d_nm = d_assigned + (size_t)K * cap1;
+    if (from_map) launch_map_skip(h, *from_map, K, M, pk.dev<MapSkipRec>(pr), pk.dev<int>(pf), pk.out<uint8_t>(ps));
+    int* d_choice = h->d_si[SI_BEST].p; int* d_assigned = d_choice + pairs; int* d_nm = d_assigned + (size_t)K * cap1; int* d_aslot = d_nm + K;
     const Sim3TargetRec* d_tab = pk.dev<Sim3TargetRec>(pt);
     const float max_dist = (float)TH_LOW * ratio_hamming;            // `TH_LOW * ratioHamming` (:609 / :722): int * float
     const dim3 grid((M + 255) / 256, K, 1), blk(256, 1, 1), grida(K, 1, 1), blka(64, 1, 1);
     ORBX_LAUNCH(k_sim3_candidates, grid, blk, 0, h->s0, d_tab, M, points->pos, points->normal, points->min_d, points->max_d, points->desc, pk.dev<uint8_t>(po),
-                skip ? pk.dev<uint8_t>(ps) : (const uint8_t*)nullptr, th, max_dist, h->debug_stereo_flags, d_choice);
+                flags ? pk.dev<uint8_t>(ps) : (const uint8_t*)nullptr, th, max_dist, h->debug_stereo_flags, d_choice);
     const size_t smem = al16(4 * (size_t)((n_max + 31) / 32)) + 16;
     ORBX_LAUNCH(k_sim3_accept, grida, blka, smem, h->s0, d_tab, M, points->pos, points->normal, points->min_d, points->max_d, points->desc, pk.dev<uint8_t>(po), th,
                 max_dist, h->debug_stereo_flags, (int)cap1, (const int*)d_choice, d_assigned, d_nm);
+    if (assigned_slot) {
+        const dim3 grids((unsigned)((cap1 + 255) / 256), K, 1);
+        ORBX_LAUNCH(k_assigned_slots, grids, blk, 0, h->s0, pk.dev<SetFlagRec>(pa), (const int*)d_assigned, (int)cap1, d_aslot);
+    }
     const int* res = d_assigned;
     int e = 0;
     if (!rt::memory_is_host()) {
@@ -2270,7 +2320,28 @@ int orbm_search_by_projection_sim3_batch(orbx_extractor* h, int K, const OrbmSim
     grids.built();
     if (cap > 0) memcpy(assigned, res, sizeof(int) * (size_t)K * (size_t)cap);
     memcpy(nmatches, res + (size_t)K * cap1, sizeof(int) * (size_t)K);
+    if (assigned_slot && cap > 0) memcpy(assigned_slot, res + (size_t)K * cap1 + (size_t)K, sizeof(int) * (size_t)K * (size_t)cap);
     return ORBX_OK;
+}
+}  // namespace
+
+int orbm_fuse_candidates_batch(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const orbm_points* points, const uint8_t* skip, float th, int chi2_gate,
+                               int* best_idx, int* best_dist) {
+    if (!h || !points || K < 0) return fail(ORBX_E_ARG, "null / negative number of targets");
+    if (points->device != h->device) return fail(ORBX_E_ARG, "the map points live on another device than the handle");
+    if (K == 0) return ORBX_OK;
+    if (int rc = fuse_targets_check(h, K, targets, chi2_gate)) return rc;
+    return fuse_batch_run(h, K, targets, points, skip, nullptr, th, chi2_gate, best_idx, best_dist, nullptr);
+}
+
+int orbm_search_by_projection_sim3_batch(orbx_extractor* h, int K, const OrbmSim3Target* targets, const orbm_points* points, const uint8_t* skip, float th,
+                                         float ratio_hamming, int cap, int* assigned, int* nmatches) {
+    if (!h || !points || K < 0) return fail(ORBX_E_ARG, "null / negative number of targets");
+    if (points->device != h->device) return fail(ORBX_E_ARG, "the map points live on another device than the handle");
+    if (K == 0) return ORBX_OK;
+    int n_max = 0;
+    if (int rc = sim3_targets_check(h, K, targets, cap, &n_max)) return rc;
+    return sim3_batch_run(h, K, targets, n_max, points, skip, nullptr, th, ratio_hamming, cap, assigned, nmatches, nullptr);
 }
 
 int orbm_search_by_sim3(orbx_extractor* h, const OrbmFrameView* KF1, const OrbmFrameView* KF2, const OrbmProjectedPointView* P1in2,
@@ -2694,7 +2765,8 @@ int orbm_search_rig_batch_fetch(orbx_extractor* L, int* assigned, int cap, int* 
 // (the .._batch_map calls at the end of this file) hold the mutex until the event behind their gather has passed and leave the rest of the search running:
 // what they read of the map is copied by then.
 // Lock order: a call that needs the vocabulary's lock (orbv_lock) and a map's mutex takes the vocabulary's FIRST (orbm_search_by_bow_frames_batch_map and
-// orbm_search_by_bow_rig_batch_map); no call holds two maps' mutexes, and kf_grid_mutex() is never held together with either.
+// orbm_search_by_bow_rig_batch_map); no call holds two maps' mutexes.  kf_grid_mutex() is taken AFTER a map's mutex where both are needed
+// (orbm_fuse_candidates_batch_map, orbm_search_by_projection_sim3_batch_map), never the other way round, and never together with the vocabulary's.
 struct orbm_map {
     int device = 0, slots = 0, kf_rows = 0, kf_row_cap = 0, max_sets = 0;
     mutable std::mutex mu;
@@ -2706,6 +2778,9 @@ struct orbm_map {
     // stamps of one build lie in (base, base + its largest position count]; base then moves up, and everything older reads as stale.  At epoch_limit
     // (orbm_map_debug_epoch: tests lower it) the stamps are cleared and base starts over
     unsigned base = 0, epoch_limit = 0xFFFFFFFFu;
+    // [slots] "which position of the set is this slot" of the Fuse / Sim3 batches fed from the map (k_map_set_table), allocated by the first of them; a
+    // call's entries lie in (tbase, tbase + M] and tbase then moves up, as `base` does (the same epoch_limit; map_skip_table)
+    DevBuf<unsigned> d_table; unsigned tbase = 0;
     std::vector<orbm_points> sets; std::vector<DevBuf<uint8_t>> set_mem; std::vector<MapSetRec> set_rec; std::vector<uint8_t> built;
     HostBuf<uint8_t> h_stage; DevBuf<uint8_t> d_stage;      // one call's upload, counts and set table (the mutex makes them the call's own)
 };
@@ -2771,7 +2846,7 @@ int map_scatter(orbx_extractor* h, orbm_map* m, int n, const int* slots, const O
     return ORBX_OK;
 }
 void map_release(orbm_map* m) {
-    m->d_store.release(); m->d_kf.release(); m->d_stamp.release(); m->h_stage.release(); m->d_stage.release();
+    m->d_store.release(); m->d_kf.release(); m->d_stamp.release(); m->d_table.release(); m->h_stage.release(); m->d_stage.release();
     for (auto& x : m->set_mem) x.release();
 }
 }  // namespace
@@ -2815,8 +2890,10 @@ int orbm_map_debug_epoch(orbx_extractor* h, orbm_map* m, int limit) {
     if (int rc = map_call_check(h, m)) return rc;
     std::lock_guard<std::mutex> lk(m->mu);
     rt::set_device(h->device);
-    if (rt::memset_async(m->d_stamp.p, 0, 2 * (size_t)m->max_sets * m->slots * sizeof(unsigned), h->s0) || rt::stream_sync(h->s0)) return fail(ORBX_E_DEVICE, "clearing the stamps failed");
-    m->base = 0; m->epoch_limit = limit > 0 ? (unsigned)limit : 0xFFFFFFFFu;
+    if (rt::memset_async(m->d_stamp.p, 0, 2 * (size_t)m->max_sets * m->slots * sizeof(unsigned), h->s0) ||
+        (m->d_table.p && rt::memset_async(m->d_table.p, 0, (size_t)m->slots * sizeof(unsigned), h->s0)) || rt::stream_sync(h->s0))
+        return fail(ORBX_E_DEVICE, "clearing the stamps failed");
+    m->base = 0; m->tbase = 0; m->epoch_limit = limit > 0 ? (unsigned)limit : 0xFFFFFFFFu;
     return ORBX_OK;
 }
 
@@ -3267,6 +3344,125 @@ int orbm_search_by_bow_rig_batch_map(orbx_extractor* L, int lf, orbx_extractor* 
     for (int p = 0; p < P; p++) { int n; if (int rc = map_row_check(L, map, p, rows[p], KFs[p], &n)) return rc; }
     const BowMapFlags F = {map->d_kf.p, map->kf_row_cap, map->S.state, rows};
     return bow_rig_batch_locked(L, lf, R, rf, B, v, P, frame, KFs, nullptr, &F, nnratio, check_ori, assigned, nmatches_out);
+}
+
+}  // extern "C"
+
+// ---- LocalMapping's and LoopClosing's batches on a set of the map: exclusions by row or found list, answers in slots, the replay's row changes as one edit ----
+// Blocking like their host-fed forms.  The map's mutex is taken first and held until the call returns (so the set cannot be rebuilt under the search), the
+// key-frame grid mutex inside fuse_batch_run / sim3_batch_run after it.
+namespace {
+// the call's range of the map's table by slot: allocated and cleared by the first call that needs it, cleared again only when the epoch is used up
+int map_skip_table(orbx_extractor* h, int M, MapSkip* S) {
+    orbm_map* m = S->map;
+    const size_t bytes = (size_t)m->slots * sizeof(unsigned);
+    if (!m->d_table.p) {
+        if (m->d_table.ensure((size_t)m->slots) || rt::memset_async(m->d_table.p, 0, bytes, h->s0)) {
+            m->d_table.release();
+            return fail(ORBX_E_DEVICE, "allocation of the map's table of %d slots failed", m->slots);
+        }
+        m->tbase = 0;
+    } else if ((long long)m->tbase + M > (long long)m->epoch_limit) {
+        if (rt::memset_async(m->d_table.p, 0, bytes, h->s0)) return fail(ORBX_E_DEVICE, "clearing the map's table failed: %s", rt::last_error());
+        m->tbase = 0;
+    }
+    S->table = m->d_table.p; S->base = m->tbase; S->top = m->tbase + (unsigned)M;
+    m->tbase = S->top;                                              // (whatever happens from here on, what this call leaves in the table is stale for the next one)
+    return ORBX_OK;
+}
+// (caller holds the map's mutex) set `set` as a search takes it
+int map_built_set_check(const orbm_map* m, int set) {
+    if (set < 0 || set >= m->max_sets || !m->built[set]) return fail(ORBX_E_ARG, "set %d has not been built (the map has %d sets)", set, m->max_sets);
+    return ORBX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int orbm_fuse_candidates_batch_map(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const int* rows, const int* feat0, orbm_map* map, int set, float th,
+                                   int chi2_gate, int* best_idx, int* best_dist, int* kf_slot) {
+    if (!h || K < 0) return fail(ORBX_E_ARG, "null / negative number of targets");
+    if (!map || !rows) return fail(ORBX_E_ARG, "null map or row list");
+    if (int rc = map_search_check(h, map)) return rc;
+    std::lock_guard<std::mutex> lk(map->mu);
+    if (int rc = map_built_set_check(map, set)) return rc;
+    if (K == 0) return ORBX_OK;
+    if (int rc = fuse_targets_check(h, K, targets, chi2_gate)) return rc;
+    MapSkip S;
+    S.map = map; S.set_slots = map->set_rec[set].slots; S.state = map->S.state; S.kf_slots = map->d_kf.p;
+    S.recs.resize(K);
+    for (int k = 0; k < K; k++) {
+        const int row = rows[k], f0 = feat0 ? feat0[k] : 0, N = targets[k].kf->N;
+        if (row < 0 || row >= map->kf_rows) return fail(ORBX_E_ARG, "target %d: row %d is outside the map's %d key-frame rows", k, row, map->kf_rows);
+        if (!map->kf_set[row]) return fail(ORBX_E_ARG, "target %d: row %d was never set (orbm_map_set_keyframe)", k, row);
+        const int n = map->kf_n[row];
+        if (f0 < 0 || (long long)f0 + N > n) return fail(ORBX_E_ARG, "target %d: features [%d, %lld) lie outside row %d of %d entries", k, f0, (long long)f0 + N, row, n);
+        S.recs[k] = {(long long)row * map->kf_row_cap, n, f0};
+        S.longest = std::max(S.longest, n);
+    }
+    return fuse_batch_run(h, K, targets, &map->sets[set], nullptr, &S, th, chi2_gate, best_idx, best_dist, kf_slot);
+}
+
+int orbm_search_by_projection_sim3_batch_map(orbx_extractor* h, int K, const OrbmSim3Target* targets, orbm_map* map, int set, const int* found_start,
+                                             const int* found_slots, float th, float ratio_hamming, int cap, int* assigned, int* nmatches, int* assigned_slot) {
+    if (!h || K < 0) return fail(ORBX_E_ARG, "null / negative number of targets");
+    if (!map) return fail(ORBX_E_ARG, "null map");
+    if (int rc = map_search_check(h, map)) return rc;
+    std::lock_guard<std::mutex> lk(map->mu);
+    if (int rc = map_built_set_check(map, set)) return rc;
+    if (found_start && !found_slots) return fail(ORBX_E_ARG, "found_start without found_slots");
+    if (K == 0) return ORBX_OK;
+    int n_max = 0;
+    if (int rc = sim3_targets_check(h, K, targets, cap, &n_max)) return rc;
+    MapSkip S;
+    S.map = map; S.set_slots = map->set_rec[set].slots; S.state = map->S.state; S.kf_slots = map->d_kf.p;
+    S.recs.assign(K, MapSkipRec{0, 0, 0});
+    if (found_start) {
+        if (found_start[0] < 0) return fail(ORBX_E_ARG, "target 0: negative found_start");
+        for (int k = 0; k < K; k++) {
+            if (found_start[k + 1] < found_start[k]) return fail(ORBX_E_ARG, "target %d: found_start decreases", k);
+            for (int j = found_start[k]; j < found_start[k + 1]; j++)
+                if (found_slots[j] < -1 || found_slots[j] >= map->slots)
+                    return fail(ORBX_E_ARG, "target %d, entry %d: found slot %d is outside the map's %d slots", k, j - found_start[k], found_slots[j], map->slots);
+            S.recs[k] = {(long long)found_start[k] - found_start[0], found_start[k + 1] - found_start[k], 0};
+            S.longest = std::max(S.longest, S.recs[k].n);
+        }
+        S.found = found_slots + found_start[0]; S.n_found = (size_t)(found_start[K] - found_start[0]);
+    }
+    return sim3_batch_run(h, K, targets, n_max, &map->sets[set], nullptr, &S, th, ratio_hamming, cap, assigned, nmatches, assigned_slot);
+}
+
+int orbm_map_edit_keyframes(orbx_extractor* h, orbm_map* m, int n, const int* row, const int* feat, const int* slot) {
+    if (int rc = map_call_check(h, m)) return rc;
+    if (n < 0) return fail(ORBX_E_ARG, "negative number of edits");
+    if (n == 0) return ORBX_OK;
+    if (!row || !feat || !slot) return fail(ORBX_E_ARG, "null");
+    if (n > (1 << 26)) return fail(ORBX_E_CAPACITY, "at most 2^26 edits in a call");
+    std::lock_guard<std::mutex> lk(m->mu);
+    std::vector<std::pair<unsigned long long, int>> keys(n);
+    for (int j = 0; j < n; j++) {
+        if (row[j] < 0 || row[j] >= m->kf_rows) return fail(ORBX_E_ARG, "edit %d: row %d is outside the map's %d key-frame rows", j, row[j], m->kf_rows);
+        if (feat[j] < 0 || feat[j] >= m->kf_n[row[j]]) return fail(ORBX_E_ARG, "edit %d: feature %d is outside row %d of %d entries", j, feat[j], row[j], m->kf_n[row[j]]);
+        if (slot[j] < -1 || slot[j] >= m->slots) return fail(ORBX_E_ARG, "edit %d: slot %d is outside the map's %d slots", j, slot[j], m->slots);
+        keys[j] = {((unsigned long long)(unsigned)row[j] << 32) | (unsigned)feat[j], j};
+    }
+    // two edits of one entry: the result would be whichever store comes last
+    std::sort(keys.begin(), keys.end());
+    for (int j = 1; j < n; j++)
+        if (keys[j].first == keys[j - 1].first)
+            return fail(ORBX_E_ARG, "edit %d: feature %d of row %d is edited twice (edit %d as well)", keys[j].second, feat[keys[j].second], row[keys[j].second], keys[j - 1].second);
+    rt::set_device(h->device);
+    const size_t N = n;
+    Bump L;
+    const size_t o_row = L.take(4 * N), o_feat = L.take(4 * N), o_slot = L.take(4 * N);
+    if (int rc = map_stage(m, L.o, L.o)) return rc;
+    uint8_t* hp = m->h_stage.p; uint8_t* dp = m->d_stage.p;
+    memcpy(hp + o_row, row, 4 * N); memcpy(hp + o_feat, feat, 4 * N); memcpy(hp + o_slot, slot, 4 * N);
+    if (rt::copy_h2d(dp, hp, L.o, h->s0)) return fail(ORBX_E_DEVICE, "upload failed: %s", rt::last_error());
+    const dim3 grid((unsigned)((N + 255) / 256), 1, 1), blk(256, 1, 1);
+    ORBX_LAUNCH(k_map_edit_rows, grid, blk, 0, h->s0, n, (const int*)(dp + o_row), (const int*)(dp + o_feat), (const int*)(dp + o_slot), m->d_kf.p, m->kf_row_cap);
+    if (rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "key-frame row edit failed: %s", rt::last_error());
+    return ORBX_OK;
 }
 
 }  // extern "C"

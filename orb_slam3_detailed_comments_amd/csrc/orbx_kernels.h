@@ -239,6 +239,17 @@ __global__ void k_map_row_flags(const int* __restrict__ kf_slots, int row_cap, c
 // a batched SearchLocalPoints on the map's own sets: the call-time flags from the sets' seen bytes, and `assigned` as map slots
 __global__ void k_map_set_flags(const SetFlagRec* __restrict__ recs, uint8_t* __restrict__ bad, uint8_t* __restrict__ obs);
 __global__ void k_assigned_slots(const SetFlagRec* __restrict__ recs, const int* __restrict__ assigned, int S, int* __restrict__ out);
+// a Fuse / Sim3 projection batch fed from the map: skip[K][M] from the slots' bad flags and the targets' rows or found lists, the replay's GetMapPoint as
+// slots, and the replay's row changes as one sparse edit
+__global__ void k_map_set_table(int M, int K, const int* __restrict__ slots, const uint8_t* __restrict__ state, unsigned* __restrict__ table, unsigned top,
+                                uint8_t* __restrict__ skip);
+__global__ void k_map_skip_listed(const MapSkipRec* __restrict__ recs, const int* __restrict__ lists, int M, const unsigned* __restrict__ table, unsigned base,
+                                  unsigned top, uint8_t* __restrict__ skip);
+__global__ void k_map_skip_dups(int M, int K, const int* __restrict__ slots, const unsigned* __restrict__ table, unsigned top, uint8_t* __restrict__ skip);
+__global__ void k_fuse_kf_slots(const MapSkipRec* __restrict__ recs, const int* __restrict__ kf_slots, int M, const uint8_t* __restrict__ state,
+                                const int* __restrict__ best_idx, int* __restrict__ kf_slot);
+__global__ void k_map_edit_rows(int n, const int* __restrict__ row, const int* __restrict__ feat, const int* __restrict__ slot, int* __restrict__ kf_slots,
+                                int row_cap);
 
 __global__ void k_distinctive(const unsigned long long* __restrict__ desc, const int* __restrict__ start, int P, int* __restrict__ best);
 template <bool kLds>        // instantiated for both forms in k_match.hip

@@ -120,6 +120,11 @@ constexpr int kRowHoldsGoodPoint = 0, kRowHoldsPoint = 1;
 // one frame of a batched SearchLocalPoints on the map's own sets (orbm_search_local_points_batch_map / _rig_batch_map): the seen bytes and the slot list
 // of its set where the build left them, the set's M, and where the frame's rows start in the batch's flag blocks (the prefix sum of M_b)
 struct SetFlagRec { const uint8_t* seen; const int* slots; int M, off; };
+// one target of a Fuse / Sim3 projection batch fed from the map (orbm_fuse_candidates_batch_map / orbm_search_by_projection_sim3_batch_map): the n slots
+// that exclude a point of the set from this target start at entry `off` of the call's list block - the map's rows (Fuse: the whole row of the target's key
+// frame, off = row * kf_row_cap) or the uploaded found lists (Sim3); feat0: the row entry of the target's feature 0 (k_fuse_kf_slots reads off + feat0 + bestIdx)
+struct MapSkipRec { long long off; int n, feat0; };
+constexpr int kSkipTargets = 16;       // targets one thread of k_map_set_table / k_map_skip_dups writes the flag of its position for
 // one map point of orbm_distinctive_descriptors_resident (k_distinctive_resident): its observations are entries [start, start + n) of the call's
 // observation table (n >= 1: points without observations are not launched); store: the descriptor of its slot in the map's store (nullptr: not written)
 struct DistinctiveRec { unsigned long long* store; int start, n; };

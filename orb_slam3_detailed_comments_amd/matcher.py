@@ -305,6 +305,57 @@ class ORBmatcher:
                                                                      cap, assigned.ctypes.data, nm.ctypes.data))
         return assigned, nm[:K]
 
+    @staticmethod
+    def FuseCandidatesBatchMap(ext, kfs, specs, resident_map, set, rows, th, invLevelSigma2=None, feat0=None, want_kf_slot=False):
+        """FuseCandidatesBatch on set `set` of a ResidentMap (orbm_fuse_candidates_batch_map): the pairs `pMP->isBad() || pMP->IsInKeyFrame(pKF)` excludes
+        are found on the device from row rows[k] of target k and the slots' states at the moment of the call.  feat0 = None or K row entries of the
+        targets' feature 0 (NLeft for a rig's right camera).  Returns (best_idx, best_dist) as [K, M] int32 arrays and, with want_kf_slot, kf_slot [K, M]:
+        pKF->GetMapPoint(bestIdx) as a slot, -2 for a bad point, -1 for none."""
+        K, Mp = len(kfs), resident_map.set(set, ext).M
+        assert len(specs) == K and len(rows) == K and (feat0 is None or len(feat0) == K)
+        T = (FuseTarget * max(K, 1))()
+        if invLevelSigma2 is None:
+            s2 = [None] * K
+        elif isinstance(invLevelSigma2, (list, tuple)) and len(invLevelSigma2) == K and np.ndim(invLevelSigma2[0]) == 1:
+            s2 = [np.ascontiguousarray(a, np.float32) for a in invLevelSigma2]
+        else:
+            s2 = [np.ascontiguousarray(invLevelSigma2, np.float32)] * K
+        for k in range(K):
+            T[k].kf = kfs[k]._kf; T[k].spec = specs[k][0]; T[k].log_scale_factor = specs[k][1]
+            T[k].inv_level_sigma2 = None if s2[k] is None else s2[k].ctypes.data
+        r = np.ascontiguousarray(np.asarray(rows, np.int32).reshape(-1), np.int32) if K else np.zeros(1, np.int32)
+        f0 = None if feat0 is None else np.ascontiguousarray(np.asarray(feat0, np.int32).reshape(-1), np.int32)
+        bi = np.full((K, Mp), -1, np.int32); bd = np.full((K, Mp), -1, np.int32); ks = np.full((K, Mp), -1, np.int32) if want_kf_slot else None
+        ext._lib.check(ext._lib.L.orbm_fuse_candidates_batch_map(ext._h, K, T, r.ctypes.data, None if f0 is None or K == 0 else f0.ctypes.data, resident_map._m, int(set),
+                                                               float(th), int(invLevelSigma2 is not None), bi.ctypes.data, bd.ctypes.data,
+                                                               None if ks is None else ks.ctypes.data))
+        return (bi, bd, ks) if want_kf_slot else (bi, bd)
+
+    @staticmethod
+    def SearchByProjectionSim3BatchMap(ext, kfs, specs, resident_map, set, th, ratio_hamming=1.0, occupied=None, found=None, want_slots=False):
+        """SearchByProjectionSim3Batch on set `set` of a ResidentMap (orbm_search_by_projection_sim3_batch_map): a point is skipped for target k iff its
+        slot is bad at the moment of the call or listed in found[k] (spAlreadyFound as slots; found = None or K arrays, duplicates / -1 / slots outside the
+        set are fine).  Returns (assigned [K, cap], nmatches [K]) and, with want_slots, assigned_slot [K, cap]: the map slot of every assigned point."""
+        K, Mp = len(kfs), resident_map.set(set, ext).M
+        assert len(specs) == K and (occupied is None or len(occupied) == K) and (found is None or len(found) == K)
+        cap = max([kf.N for kf in kfs] + [0])
+        T = (Sim3Target * max(K, 1))()
+        occ = [None if occupied is None or o is None else np.ascontiguousarray(o, np.uint8) for o in (occupied if occupied is not None else [None] * K)]
+        for k in range(K):
+            assert occ[k] is None or occ[k].shape == (kfs[k].N,)
+            T[k].kf = kfs[k]._kf; T[k].spec = specs[k][0]; T[k].log_scale_factor = specs[k][1]
+            T[k].occupied = None if occ[k] is None else occ[k].ctypes.data
+        fs = fl = None
+        if found is not None:
+            lists = [np.zeros(0, np.int32) if a is None else np.asarray(a, np.int32).reshape(-1) for a in found]
+            fs = np.cumsum([0] + [len(a) for a in lists]).astype(np.int32)
+            fl = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, np.int32)]), np.int32)
+        assigned = np.full((K, cap), -1, np.int32); nm = np.zeros(max(K, 1), np.int32); aslot = np.full((K, cap), -1, np.int32) if want_slots else None
+        ext._lib.check(ext._lib.L.orbm_search_by_projection_sim3_batch_map(ext._h, K, T, resident_map._m, int(set), None if fs is None else fs.ctypes.data,
+                                                                         None if fl is None else fl.ctypes.data, float(th), float(ratio_hamming), cap,
+                                                                         assigned.ctypes.data, nm.ctypes.data, None if aslot is None else aslot.ctypes.data))
+        return (assigned, nm[:K], aslot) if want_slots else (assigned, nm[:K])
+
     def SearchBySim3(self, ext, kf1, kf2, p1in2, p2in1, th):
         """ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, S12, th), src/ORBmatcher.cc:1689.  Returns (nFound, matches12[N1])."""
         m12 = np.full(kf1.view.N, -1, np.int32); nf = C.c_int()
@@ -792,6 +843,14 @@ class ResidentMap:
         """GetMapPointMatches() of the key frame kept in `row`: the slot of feature i, or -1"""
         s = np.ascontiguousarray(slots, np.int32)
         self._lib.check(self._lib.L.orbm_map_set_keyframe(self._h(ext), self._m, int(row), len(s), s.ctypes.data))
+
+    def edit_keyframes(self, rows, feats, slots, ext=None):
+        """entry feats[j] of row rows[j] becomes slots[j] (-1 = EraseMapPointMatch): AddMapPoint / ReplaceMapPointMatch / MapPoint::Replace of a whole Fuse
+        replay in one call (orbm_map_edit_keyframes); no (row, feat) twice"""
+        r, f, s = (np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1), np.int32) for a in (rows, feats, slots))
+        if not len(r) == len(f) == len(s):
+            raise ValueError("%d rows, %d features, %d slots" % (len(r), len(f), len(s)))
+        self._lib.check(self._lib.L.orbm_map_edit_keyframes(self._h(ext), self._m, len(r), r.ctypes.data, f.ctypes.data, s.ctypes.data))
 
     def local_points(self, rows, seen=None, ext=None):
         """Tracking::UpdateLocalPoints for B = len(rows) frames: rows[b] = the rows frame b visits, in visiting order (mvpLocalKeyFrames reversed);
