@@ -50,7 +50,8 @@ def restated_stereo(kL, dL, kR, dR, pyrL, pyrR, mbf, mb):
             rows[yi].append(iR)
     bitsL = np.unpackbits(dL, axis=1).astype(np.int16); bitsR = np.unpackbits(dR, axis=1).astype(np.int16)
     minD, maxD = f32(0), f32(mbf) / f32(mb)
-    entered = dict(clamp=0, negative=0, too_far=0, delta=0, max_abs_delta=0.0)
+    # (at_maxd / one_float_below / one_float_above: the disparity, where it reaches the range test, equals maxD / its neighbour floats - tests/test_stereo_disparity_range.py)
+    entered = dict(clamp=0, negative=0, too_far=0, delta=0, max_abs_delta=0.0, at_maxd=0, one_float_below=0, one_float_above=0, at_maxd_delta_zero=0)
     dist_idx = []
     for iL in range(N):
         lvl = int(kL["octave"][iL]); uL = f32(kL["x"][iL]); vL = f32(kL["y"][iL])
@@ -93,6 +94,8 @@ def restated_stereo(kL, dL, kR, dR, pyrL, pyrR, mbf, mb):
         if not disparity >= minD:
             entered["negative"] += 1
             continue
+        entered["at_maxd"] += int(disparity == maxD); entered["at_maxd_delta_zero"] += int(disparity == maxD and delta == 0)
+        entered["one_float_below"] += int(disparity == np.nextafter(maxD, f32(0))); entered["one_float_above"] += int(disparity == np.nextafter(maxD, f32(np.inf)))
         if not disparity < maxD:
             entered["too_far"] += 1
             continue

@@ -15,6 +15,7 @@ CONFIGS = [  # (k, L, scoring, weighting, ragged, min_leaf_level, levelsups)
     (4, 5, 2, 2, False, 1, (2,)),              # CHI_SQUARE (L1), IDF: addIfNotExist
     (3, 6, 0, 3, True, 4, (2,)),               # ragged tree, leaves at levels >= 4 = L - levelsup; BINARY
     (20, 2, 0, 0, False, 1, (1,)),             # more children than lanes in a group
+    (5, 3, 5, 1, False, 1, (1,)),              # DOT_PRODUCT with TF: the one other weighting whose unnormalised values are divided by the vector size
 ]
 
 

@@ -9,7 +9,9 @@ inputs hold pairs whose shifted pixel is the LAST float the host model still acc
 flips one of them.  Expected l2r, r2l and n are replayed in numpy from the host depths: accept when z > 1e-4, the largest left index wins a right keypoint.
 
 Rigs: the TUM-VI pair of tests/test_kb8.py, and a 2 mm rig without rotation: with TUM-VI's tz = 1 mm and 2.7 degrees of pitch no point that both cameras see
-inside the theta_d clamp has 0 < z <= 1e-4 (z2 > 0 needs 0.0469 y + z > 1.05e-3, the clamp z >= |y| / 72), so the acceptance threshold itself is exercised on the small rig.
+inside the theta_d clamp has 0 < z <= 1e-4 (z2 > 0 needs 0.0469 y + z > 1.05e-3, the clamp z >= |y| / 72), so the acceptance threshold itself is exercised on the small rig:
+depths either side of 1e-4, and pairs searched among neighbouring float pixels until the host model's depth is float(1e-4) EXACTLY (refused: the comparison is strict),
+the float above it (accepted) and the float below.
 
 Rejection codes of the host model: -1 parallax below the gate, -2 z1 <= 0, -3 z2 <= 0, -4 / -5 the chi-square gate in camera 1 / 2."""
 import ctypes as C
@@ -189,6 +191,7 @@ class Scene:
         z, p = triangulate(self.rig, np.stack([kL["x"][i], kL["y"][i]], 1), np.stack([kR["x"][j], kR["y"][j]], 1), self.sigma2[kL["octave"][i]], self.sigma2[kR["octave"][j]])
         self.match = np.full(cap, -1, np.int32); self.match[i] = j                 # per left keypoint: the right keypoint the ratio test hands to the triangulation
         self.code = np.full(cap, 0, np.int32)                                  # per left keypoint: 1 accepted, -1 .. -5 rejected by that gate, -6 depth <= 1e-4, 0 no ratio match
+        self.model_z = np.full(cap, np.nan, np.float32); self.model_z[i] = z    # per left keypoint: what the host model returned (depth or rejection code)
         n_acc = 0
         for a, b, zz, pp in zip(i, j, z, p):                                  # ascending left index: the last writer of r2l[j] is the largest
             if zz > f32(0.0001):
@@ -213,6 +216,40 @@ def _grid_pixels(cam):
         for deg in (45.0, 135.0, 225.0, 315.0, 10.0, 100.0, 190.0, 280.0, 80.0, 170.0, 260.0, 350.0):           # every quadrant of psi, near both ends of each
             px.append((cx + f32(r * np.cos(np.radians(deg))), cy + f32(r * np.sin(np.radians(deg)))))
     return np.array(px, np.float32)
+
+
+def _float_steps(v, ks):
+    out = np.zeros(len(ks), np.float32)
+    for n, k in enumerate(ks):
+        x = f32(v)
+        for _ in range(abs(int(k))):
+            x = np.nextafter(x, f32(np.inf) if k > 0 else f32(-np.inf))
+        out[n] = x
+    return out
+
+
+def _pairs_at_depth(rig, sigma2, targets, want=2, seed=1):
+    """Pixel pairs (octave 0 on both sides) whose depth by the host model is EXACTLY one of `targets`: points near 1e-4 on rays like those of the small-rig frame, then the
+    121 x 121 neighbouring floats of (left v, right u) - some 5 000 to 9 000 distinct depths within 1e-7 of the point's - searched for the values.  {target: (uv1, uv2)}"""
+    rng = np.random.default_rng(seed)
+    ks = np.arange(-60, 61)
+    found = {f32(t): ([], []) for t in targets}
+    for _ in range(200):
+        if all(len(v[0]) >= want for v in found.values()):
+            break
+        z0 = np.array([1e-4 * (1 + rng.uniform(-1e-3, 1e-3))])
+        X = np.stack([rng.uniform(0.0005, 0.002) * z0 / 1e-4, rng.uniform(0.002, 0.004) * z0 / 1e-4, z0], 1)
+        u1 = _project64(rig["cam1"], X).astype(np.float32); u2 = _right_pixels(rig, X)
+        xs = _float_steps(u2[0, 0], ks); ys = _float_steps(u1[0, 1], ks)
+        A = np.zeros((len(ks) ** 2, 2), np.float32); B = np.zeros_like(A)
+        A[:, 0] = u1[0, 0]; A[:, 1] = np.repeat(ys, len(ks)); B[:, 0] = np.tile(xs, len(ks)); B[:, 1] = u2[0, 1]
+        z, _ = triangulate(rig, A, B, np.full(len(A), sigma2[0]), np.full(len(A), sigma2[0]))
+        for t, (l, r) in found.items():
+            hit = np.flatnonzero(z == t)
+            if len(hit) and len(l) < want:
+                l.append(A[hit[0]].copy()); r.append(B[hit[0]].copy())
+    assert all(len(v[0]) >= want for v in found.values()), {float(t): len(v[0]) for t, v in found.items()}
+    return {t: (np.array(l), np.array(r)) for t, (l, r) in found.items()}
 
 
 def build_scenes(sigma2, cap):
@@ -289,6 +326,10 @@ def build_scenes(sigma2, cap):
     X = np.stack([np.full(len(zs), 0.001) * zs / 1e-4, 0.003 * zs / 1e-4, zs], 1)                                 # rays 88.6 degrees off the axis, inside the clamp
     u1 = _project64(small["cam1"], X).astype(np.float32)
     s3.add_pairs(u1, _right_pixels(small, X), 0, 0)
+    # .. and ON it: `depth > 0.0001f` (src/Frame.cc:1573) refuses float(1e-4) itself and takes the next float
+    th = f32(0.0001)
+    for uv1, uv2 in _pairs_at_depth(small, sigma2, (th, np.nextafter(th, f32(1)), np.nextafter(th, f32(0)))).values():
+        s3.add_pairs(uv1, uv2, 0, 0)
     s3.add_unmatched(5, 5)
     s3.finish(cap)
     empty = Scene(small, sigma2, 0, 0, 5).finish(cap)
@@ -329,6 +370,10 @@ def _check_construction(groups):
         assert count(s2, c) >= 8
     assert s2.exp["n"] == 0 and (s2.exp["r2l"] == -1).all() and (s2.exp["depth"] == -1).all()
     assert count(s3, -6) >= 3 and count(s3, 1) >= 3, "depths on both sides of 1e-4"
+    th = f32(0.0001)
+    on, above, below = s3.model_z == th, s3.model_z == np.nextafter(th, f32(1)), s3.model_z == np.nextafter(th, f32(0))
+    assert on.sum() >= 2 and above.sum() >= 2 and below.sum() >= 2, "depths of exactly float(1e-4) and its two neighbours: %d, %d, %d" % (on.sum(), above.sum(), below.sum())
+    assert (s3.code[on] == -6).all() and (s3.code[below] == -6).all() and (s3.code[above] == 1).all()
     acc = np.flatnonzero(s0.code == 1)
     assert {(int(a), int(b)) for a, b in zip(s0.kL["octave"][acc], s0.kR["octave"][s0.match[acc]])} >= {(a, b) for a in range(8) for b in range(8)}   # sigma2 is picked per side
 

@@ -1,0 +1,266 @@
+"""The mutants of tools/emu_mutants.py: (id, file in csrc, old text that occurs EXACTLY ONCE in that file, new text, CPU test files, intent[, note]).
+
+Only decisions are mutated: a relational boundary, one clause of a compound gate removed or negated, a rank or threshold constant off by one, a tie broken the other
+way, a gate's constant replaced by a neighbour.  Never address arithmetic, loop bounds over memory, launch geometry, synchronisation or the lines under the
+debug_flags test switches: the emulator runs inside the test process, and a mutant must not be able to index outside its arrays.  That also keeps out the clauses
+whose only purpose is to keep reads inside an array (`inb` of k_stereo_match, the `q < cap` tests) and the gates in front of a readlane / an index (`bestinc == -Lh`
+may be moved inwards, not removed).
+
+`note`: the reason why a mutant that survives is no gap in the suite - it computes the same on every input (equivalent), or no input that the library accepts reaches the
+value where it differs.  A survivor without a note is a missing test.  Ids are stable: add at the end of a file's block, never renumber."""
+
+STEREO = ["test_stereo_constructed_descriptors.py", "test_branch_edges_stereo.py", "test_stereo_ties.py", "test_stereo_chain.py", "test_match_empty_edges.py",
+          "test_stereo_disparity_range.py"]
+KNN = ["test_knn2_constructed.py", "test_match_empty_edges.py", "test_kb8_stereo_constructed.py", "test_kb8.py"]
+KB8 = ["test_kb8_stereo_constructed.py", "test_kb8.py", "test_match_empty_edges.py"]
+DISTINCTIVE = ["test_distinctive_resident.py", "test_emu_mappoint.py"]
+
+MUTANTS = []
+
+
+def M(id, file, old, new, tests, intent, note=None, more=()):
+    """more: further (old, new) pairs of the same mutant, each old text unique too - for a decision that is written at two places (a tie order packed into a key and unpacked again)"""
+    MUTANTS.append(dict(id=id, file=file, old=old, new=new, tests=list(tests), intent=intent, note=note, more=list(more)))
+
+
+# ---- k_match.hip ---------------------------------------------------------------------------------------------------------------------------------------------
+F = "k_match.hip"
+DELTA = ("equivalent: bestinc is the FIRST minimum of the eleven SADs and not at either end, so dist1 > dist2 <= dist3 and |dist1 - dist3| <= dist1 + dist3 - 2 dist2, "
+         "i.e. |deltaR| <= 0.5 (integers below 2^15: every operation before the division is exact); the gate is never entered (tests/test_branch_edges_stereo.py asserts the bound)")
+# k_stereo_match: gate
+M(1, F, "return rowL >= a.x &&", "return rowL > a.x &&", STEREO, "stereo gate: first row of the band exclusive")
+M(2, F, "&& rowL <= a.y &&", "&& rowL < a.y &&", STEREO, "stereo gate: last row of the band exclusive")
+M(3, F, "oct >= levelL - 1 &&", "oct > levelL - 1 &&", STEREO, "stereo gate: the octave below refused")
+M(4, F, "oct <= levelL + 1 &&", "oct < levelL + 1 &&", STEREO, "stereo gate: the octave above refused")
+M(5, F, "xr >= minU && xr <= maxU;", "xr > minU && xr <= maxU;", STEREO, "stereo gate: x == minU refused")
+M(6, F, "xr >= minU && xr <= maxU;", "xr >= minU && xr < maxU;", STEREO, "stereo gate: x == maxU refused")
+M(7, F, "oct >= levelL - 1 && oct <= levelL + 1 && ", "", STEREO, "stereo gate: the octave clause removed")
+# :120
+M(8, F, "bestDist < P.th_orb && nr > 0", "bestDist <= P.th_orb && nr > 0", STEREO, "stereo: distance th_orb goes on to the refinement")
+M(9, F, "bestDist < P.th_orb && nr > 0", "bestDist < P.th_orb", STEREO, "stereo: the nr > 0 clause removed",
+  "equivalent: without right keypoints every bucket is empty (jbeg == jend), best stays TH_HIGH << 16 and bestDist = TH_HIGH is not below th_orb")
+M(10, F, "P.th_high << 16;", "(P.th_high + 1) << 16;", STEREO, "stereo: a candidate at TH_HIGH replaces the start value",
+   "equivalent in the output: a winner at distance TH_HIGH is not below th_orb and ends as -1 like no winner.  Precondition th_orb <= th_high: both are set in one place, "
+   "orbm_stereo_match (csrc/orbx_api.cpp: P.th_high = 100, P.th_orb = (100 + 50) / 2, ORBmatcher::TH_HIGH / TH_LOW), and no entry point takes either")
+# :130
+M(11, F, "endu >= (float)Lw", "endu > (float)Lw", STEREO, "stereo: endu == level width accepted",
+   "unreachable: endu == Lw needs a right keypoint whose x, rounded at the LEFT keypoint's level, is Lw - 11.  orbm_stereo_match reads the right keypoints' x only from "
+   "the search records that the right extraction wrote (d_aux: no entry point returns or takes its address, tests/resident_inject.py), and the extractor keeps a keypoint "
+   "of level m at x <= w_m - 17 of its level; with |m - levelL| <= 1 that is at most Lw - 17 / 1.2 + rounding = Lw - 13 at the left keypoint's level.  "
+   "The reference's answer at the boundary is pinned on the oracle by tests/test_stereo_disparity_range.py::test_oracle_window_guard_at_the_level_border")
+M(12, F, "!(iniu < 0 ||", "!(iniu <= 0 ||", STEREO, "stereo: iniu == 0 refused",
+   "equivalent: iniu == 0 means cr == 0, and the `inb` clause cr - Lh - w >= 0 already refuses it")
+# :160 - :168
+M(13, F, "bestinc == -Lh ||", "bestinc == -Lh + 1 ||", STEREO, "stereo: the second shift counts as the window's end")
+M(14, F, "|| bestinc == Lh))", "|| bestinc == Lh - 1))", STEREO, "stereo: the last shift but one counts as the window's end")
+M(15, F, "deltaR < -1 ||", "deltaR <= -1 ||", STEREO, "stereo: deltaR == -1 refused", DELTA)
+M(16, F, "|| deltaR > 1))", "|| deltaR >= 1))", STEREO, "stereo: deltaR == 1 refused", DELTA)
+M(17, F, "disparity >= 0 && disparity < maxD", "disparity > 0 && disparity < maxD", STEREO, "stereo: disparity 0 refused instead of clamped")
+M(18, F, "disparity >= 0 && disparity < maxD", "disparity >= 0 && disparity <= maxD", STEREO, "stereo: disparity == maxD accepted")
+M(19, F, "if (disparity <= 0) {", "if (disparity < 0) {", STEREO, "stereo: disparity 0 not clamped to 0.01")
+M(20, F, "disparity >= 0 && disparity < maxD", "disparity < maxD", STEREO, "stereo: the disparity >= 0 clause removed")
+# k_stereo_median
+M(21, F, "if (!((float)s < thDist))", "if ((float)s > thDist)", STEREO, "median: SAD == thDist kept")
+M(22, F, "pass ? s_med[2] : cnt / 2;", "pass ? s_med[2] : (cnt - 1) / 2;", STEREO, "median: rank (cnt - 1) / 2")
+M(23, F, "if (s >= 0) {", "if (s > 0) {", STEREO, "median: a match with SAD 0 neither kept nor erased")
+M(24, F, "if (s >= 0 && (pass == 0", "if (s > 0 && (pass == 0", STEREO, "median: SAD 0 left out of the median")
+M(25, F, "1.5f * 1.4f", "1.5f * 1.5f", STEREO, "median: factor 2.25 instead of 2.1")
+# k_knn2 / k_knn2_mfma
+M(26, F, "\n        ratio_ok[o] = (i1 >= 0 && (double)(float)dd0 < ", "\n        ratio_ok[o] = (i1 >= 0 && (double)(float)dd0 <= ", KNN, "knn2: ratio test inclusive")
+M(27, F, "\n            ratio_ok[o] = (i1 >= 0 && (double)(float)dd0 < ", "\n            ratio_ok[o] = (i1 >= 0 && (double)(float)dd0 <= ", KNN, "knn2_mfma: ratio test inclusive")
+M(28, F, "\n        ratio_ok[o] = (i1 >= 0 && ", "\n        ratio_ok[o] = (", KNN, "knn2: a query without second neighbour passes the ratio test")
+M(29, F, "\n            ratio_ok[o] = (i1 >= 0 && ", "\n            ratio_ok[o] = (", KNN, "knn2_mfma: a query without second neighbour passes the ratio test")
+M(30, F, "(int)(b0 >> 16), dd1 = i1 < 0 ?", "(int)(b0 >> 16), dd1 = i1 <= 0 ?", KNN, "knn2: second neighbour 0 reported without distance")
+M(31, F, "(int)(k0 >> 16), dd1 = i1 < 0 ?", "(int)(k0 >> 16), dd1 = i1 <= 0 ?", KNN, "knn2_mfma: second neighbour 0 reported without distance")
+M(32, F, "if ((int)(key & 0xFFFFu) >= nT) key", "if ((int)(key & 0xFFFFu) > nT) key", KNN, "knn2_mfma: the row behind the train set is a neighbour")
+# (ids 33 and 34, `q >= nQ` -> `q > nQ` in k_knn2 and k_knn2_mfma, are not in the list: the mutant reads - k_knn2 - or writes - both - the row behind the query set, which lies
+# inside the arrays only because they are sized to the capacity.  The line is covered from the other side: tests/test_match_empty_edges.py checks the -1 rows behind the set.)
+M(35, F, "if (k0 == b0) k0 = k1;", "if (k0 != b0) k0 = k1;", KNN, "knn2: the runner-up exposed by the wrong lanes")
+# k_kb8_stereo
+M(36, F, "if (z > 0.0001f) {", "if (z > 0.0f) {", KB8, "kb8 stereo: depth gate 0 instead of 1e-4")
+M(37, F, "if (z > 0.0001f) {", "if (z >= 0.0001f) {", KB8, "kb8 stereo: depth gate inclusive")
+M(38, F, "i < nL[b] && q >= 0 && ratio_ok", "i < nL[b] && q > 0 && ratio_ok", KB8, "kb8 stereo: the first lapping keypoint left out")
+M(39, F, "atomicMax(&r2l[", "atomicMin(&r2l[", KB8, "kb8 stereo: the smallest left index wins mvRightToLeftMatch")
+# k_distinctive, distinctive_point
+M(40, F, "const int rank = (N - 1) >> 1;", "const int rank = N >> 1;", DISTINCTIVE, "distinctive: rank N / 2")
+M(41, F, "if (median < bestMedian) {", "if (median <= bestMedian) {", DISTINCTIVE, "distinctive: the last of equal medians wins")
+M(42, F, "median < 0 && rank < before + c[t]", "median < 0 && rank <= before + c[t]", DISTINCTIVE, "distinctive: the bin before the rank's")
+M(43, F, "N = R.n, rank = (N - 1) >> 1;", "N = R.n, rank = N >> 1;", DISTINCTIVE, "distinctive (resident): rank N / 2")
+M(44, F, "if (count_le(bestMedian - 1) > rank) {", "if (count_le(bestMedian) > rank) {", DISTINCTIVE, "distinctive (resident): the last of equal medians wins")
+M(45, F, "if (count_le(mid) > rank) hi = mid;", "if (count_le(mid) >= rank) hi = mid;", DISTINCTIVE, "distinctive (resident): bisection one rank low")
+M(46, F, "ORBX_BALLOT(d[c] <= v)", "ORBX_BALLOT(d[c] < v)", DISTINCTIVE, "distinctive (resident): count of distances below v, not up to v",
+  note="equivalent: with `<` the bisection returns median + 1 for every row and the winner test `count(bestMedian - 1) > rank` becomes median_i < median_best again - bestMedian is off by one consistently and never leaves the function (a median of 256, which the start value 257 would not admit, loses to no row and leaves bestIdx = 0 as the reference does)")
+
+# ---- k_search.hip --------------------------------------------------------------------------------------------------------------------------------------------
+F = "k_search.hip"
+LOCAL = ["test_branch_edges_search.py", "test_emu_search.py", "test_local_points.py", "test_local_points_batch.py", "test_local_points_maps.py", "test_local_map_search.py",
+         "test_search_gates.py"]
+PROJ = ["test_lastframe_batch.py", "test_keyframe_batch.py", "test_map_rows_projection.py", "test_branch_edges_rotation.py", "test_emu_search.py", "test_branch_edges_search.py",
+        "test_search_gates.py", "test_lastframe_gates.py"]
+RIG = ["test_rig_tracking_batch.py", "test_local_points_rig.py", "test_rig_local_points_maps.py", "test_search_gates.py"]
+FUSE = ["test_fuse_batch.py", "test_fuse_map.py", "test_emu_search.py", "test_search_gates.py", "test_projection_gates.py"]
+SIM3 = ["test_sim3_projection_batch.py", "test_sim3_map.py", "test_emu_search.py", "test_search_gates.py"]
+BOW = ["test_branch_edges_triangulation.py", "test_emu_search.py", "test_bow_frames_batch.py", "test_map_rows_bow.py", "test_branch_edges_rotation.py", "test_rig_bow_batch.py",
+       "test_keyframe_search_gates.py"]
+MAP = ["test_map_rows_resident.py", "test_map_rows_bow.py", "test_map_rows_projection.py", "test_local_map_build.py", "test_fuse_map.py", "test_sim3_map.py", "test_local_map_search.py",
+       "test_map_state_gates.py"]
+# area_accept
+M(100, F, "if (k.octave < A.min_level) return false;", "if (k.octave <= A.min_level) return false;", LOCAL + PROJ[:2], "area: the lowest level of the window refused")
+M(101, F, "A.max_level >= 0 && k.octave > A.max_level", "A.max_level >= 0 && k.octave >= A.max_level", LOCAL + PROJ[:2], "area: the highest level of the window refused")
+M(102, F, "if (A.max_level >= 0 && k.octave", "if (A.max_level > 0 && k.octave", LOCAL + PROJ[:2], "area: max level 0 means no upper limit")
+M(103, F, "fabsf(__fsub_rn(k.x, A.x)) < A.r &&", "fabsf(__fsub_rn(k.x, A.x)) <= A.r &&", LOCAL, "area: |dx| == r inside the box")
+M(104, F, "fabsf(__fsub_rn(k.y, A.y)) < A.r))", "fabsf(__fsub_rn(k.y, A.y)) <= A.r))", LOCAL, "area: |dy| == r inside the box")
+M(105, F, "if (ur > 0 && fabsf(__fsub_rn(A.ur, ur)) > A.r)", "if (ur >= 0 && fabsf(__fsub_rn(A.ur, ur)) > A.r)", LOCAL + PROJ[:1], "area: a right coordinate of exactly 0 is gated")
+M(106, F, "if (ur > 0 && fabsf(__fsub_rn(A.ur, ur)) > A.r)", "if (ur > 0 && fabsf(__fsub_rn(A.ur, ur)) >= A.r)", LOCAL + PROJ[:1], "area: right-coordinate error == r refused")
+M(107, F, "if (ur > 0 && fabsf(__fsub_rn(A.ur, ur)) > A.r)", "if (fabsf(__fsub_rn(A.ur, ur)) > A.r)", LOCAL + PROJ[:1], "area: the ur > 0 clause removed (monocular keypoints gated)")
+M(108, F, "if (gate_right && A.gate == 1) {", "if (gate_right) {", FUSE + LOCAL[:2], "area: Fuse's queries take the right-coordinate radius test")
+# chi2_accept
+M(110, F, "(double)__fmul_rn(e2, inv) > 7.8);", "(double)__fmul_rn(e2, inv) > 5.99);", FUSE, "chi2: the stereo keypoints judged by the monocular bound")
+M(111, F, "(double)__fmul_rn(e2, inv) > 5.99);", "(double)__fmul_rn(e2, inv) > 7.8);", FUSE, "chi2: the monocular keypoints judged by the stereo bound")
+M(112, F, "(double)__fmul_rn(e2, inv) > 7.8);", "(double)__fmul_rn(e2, inv) >= 7.8);", FUSE, "chi2: stereo bound inclusive",
+  "equivalent: the left side is a float widened to double and 7.8 is no float (nor is 5.99), so the two never compare equal")
+M(113, F, "(double)__fmul_rn(e2, inv) > 5.99);", "(double)__fmul_rn(e2, inv) >= 5.99);", FUSE, "chi2: monocular bound inclusive",
+  "equivalent: the left side is a float widened to double and 5.99 is no float, so the two never compare equal")
+M(114, F, "    if (ur >= 0) {\n        const float er", "    if (ur > 0) {\n        const float er", FUSE, "chi2: a right coordinate of exactly 0 counts as monocular")
+# frustum_body (+ rig form)
+M(120, F, "if (z < 0.0f) ok = false;", "if (z <= 0.0f) ok = false;", LOCAL, "frustum: depth exactly 0 refused",
+  note="no defined expectation: a point with z == 0 and x or y != 0 projects to +-inf and fails the image test either way; only the camera centre itself (x = y = z = 0, u = v = NaN) passes, and there the reference goes on to MapPoint::PredictScale with a distance of 0 - `(int)ceil(log(inf) / ..)`, an undefined conversion that gcc and the device answer differently")
+M(121, F, "if (uu < F.min_x || uu > F.max_x) ok = false;", "if (uu <= F.min_x || uu > F.max_x) ok = false;", LOCAL, "frustum: u == mnMinX outside")
+M(122, F, "if (uu < F.min_x || uu > F.max_x) ok = false;", "if (uu < F.min_x || uu >= F.max_x) ok = false;", LOCAL, "frustum: u == mnMaxX outside")
+M(123, F, "(vv < F.min_y || vv > F.max_y)) ok = false;", "(vv <= F.min_y || vv > F.max_y)) ok = false;", LOCAL, "frustum: v == mnMinY outside")
+M(124, F, "(vv < F.min_y || vv > F.max_y)) ok = false;", "(vv < F.min_y || vv >= F.max_y)) ok = false;", LOCAL, "frustum: v == mnMaxY outside")
+M(125, F, "if (dist < minDistance || dist > maxDistance) ok = false;", "if (dist <= minDistance || dist > maxDistance) ok = false;", LOCAL, "frustum: distance == 0.8 min refused")
+M(126, F, "if (dist < minDistance || dist > maxDistance) ok = false;", "if (dist < minDistance || dist >= maxDistance) ok = false;", LOCAL, "frustum: distance == 1.2 max refused")
+M(127, F, "if (vcos < F.cos_limit) ok = false;", "if (vcos <= F.cos_limit) ok = false;", LOCAL, "frustum: viewing cosine == limit refused")
+M(128, F, "!(F.far_points && depth > F.th_far)", "!(F.far_points && depth >= F.th_far)", LOCAL, "local points: depth == thFarPoints is far")
+M(129, F, "float r = (double)vcos > 0.998 ? 2.5f : 4.0f;", "float r = (double)vcos >= 0.998 ? 2.5f : 4.0f;", LOCAL, "RadiusByViewingCos inclusive",
+  "equivalent: vcos is a float widened to double and 0.998 is no float, so the two never compare equal")
+M(130, F, "float r = (double)vcos > 0.998 ? 2.5f : 4.0f;", "float r = (double)vcos > 0.99 ? 2.5f : 4.0f;", LOCAL, "RadiusByViewingCos: 0.99 for 0.998")
+M(131, F, "float r = (double)vcos > 0.998 ? 2.5f : 4.0f;", "float r = vcos > 0.998f ? 2.5f : 4.0f;", LOCAL, "RadiusByViewingCos compared in float")
+M(132, F, "q.min_level = lvl - 1; q.max_level = lvl; q.active = 1; q.gate = 1;", "q.min_level = lvl; q.max_level = lvl; q.active = 1; q.gate = 1;", LOCAL, "local points: the level below the predicted one refused")
+M(133, F, "if (F.th != 1.0f) r = __fmul_rn(r, F.th);", "r = __fmul_rn(r, F.th);", LOCAL, "local points: the radius always multiplied by th",
+  "equivalent: r * 1.0f == r for every float r")
+M(134, F, "const float r = (double)track2[4 * Ms + i] > 0.998 ? 2.5f : 4.0f;", "const float r = (double)track2[4 * Ms + i] > 0.99 ? 2.5f : 4.0f;", RIG, "rig camera 2: 0.99 for 0.998")
+M(135, F, "track1[3 * Ms + i] > F1.th_far)", "track1[3 * Ms + i] >= F1.th_far)", RIG, "rig: depth == thFarPoints is far")
+M(136, F, "const bool alive = (inl || inr) &&", "const bool alive = inl &&", RIG, "rig: a point seen by camera 2 alone is dropped")
+M(137, F, "q.min_level = lvl - 1; q.max_level = lvl; q.active = 1;\n", "q.min_level = lvl; q.max_level = lvl; q.active = 1;\n", RIG, "rig camera 2: the level below the predicted one refused")
+# project_point
+M(140, F, "if (P.depth_test == 1 && z < 0.0f) ok = false;", "if (P.depth_test == 1 && z <= 0.0f) ok = false;", FUSE + SIM3, "projection: depth exactly 0 refused (z test)",
+  note="no defined expectation: a point with z == 0 and x or y != 0 projects to +-inf and fails the image test either way; only the camera centre itself (x = y = z = 0, u = v = NaN) passes, and there the reference goes on to MapPoint::PredictScale with a distance of 0 - `(int)ceil(log(inf) / ..)`, an undefined conversion that gcc and the device answer differently")
+M(141, F, "if (P.depth_test == 2 && invz < 0.0f) ok = false;", "if (P.depth_test == 2 && invz <= 0.0f) ok = false;", FUSE + SIM3 + PROJ[:2], "projection: 1 / z == 0 refused")
+M(142, F, "if (u < P.min_x || u > P.max_x || v < P.min_y || v > P.max_y) ok = false; }", "if (u <= P.min_x || u >= P.max_x || v <= P.min_y || v >= P.max_y) ok = false; }", FUSE + SIM3 + PROJ[:2], "projection (Frame bounds): the border is outside")
+M(143, F, "!(u >= P.min_x && u < P.max_x && v >= P.min_y && v < P.max_y)", "!(u > P.min_x && u < P.max_x && v > P.min_y && v < P.max_y)", FUSE + SIM3, "projection (IsInImage): the lower border is outside")
+M(144, F, "!(u >= P.min_x && u < P.max_x && v >= P.min_y && v < P.max_y)", "!(u >= P.min_x && u <= P.max_x && v >= P.min_y && v <= P.max_y)", FUSE + SIM3, "projection (IsInImage): the upper border is inside")
+M(145, F, "if (P.distance_test && (dist < min_inv || dist > max_inv)) ok = false;", "if (P.distance_test && (dist <= min_inv || dist > max_inv)) ok = false;", FUSE + SIM3, "projection: distance == lower limit refused")
+M(146, F, "if (P.distance_test && (dist < min_inv || dist > max_inv)) ok = false;", "if (P.distance_test && (dist < min_inv || dist >= max_inv)) ok = false;", FUSE + SIM3, "projection: distance == upper limit refused")
+M(147, F, "if (dot < __fmul_rn(0.5f, dist)) ok = false;", "if (dot <= __fmul_rn(0.5f, dist)) ok = false;", FUSE + SIM3, "projection: viewing angle of exactly 60 degrees refused")
+M(148, F, "if (dot < __fmul_rn(0.5f, dist)) ok = false;", "if (dot < __fmul_rn(0.6f, dist)) ok = false;", FUSE + SIM3, "projection: viewing-angle bound 0.6 for 0.5")
+# projection_queries_body
+M(150, F, "(!(invz < 0.0f) && oct >= 0 && oct < F.nlevels)", "(!(invz <= 0.0f) && oct >= 0 && oct < F.nlevels)", PROJ, "last frame: 1 / z == 0 refused")
+M(151, F, "if (!(u < F.min_x || u > F.max_x || v < F.min_y || v > F.max_y)) {", "if (!(u <= F.min_x || u >= F.max_x || v <= F.min_y || v >= F.max_y)) {", PROJ, "last frame / key frame: the image border is outside")
+M(152, F, "if (!(dist3D < minDistance || dist3D > maxDistance)) {", "if (!(dist3D <= minDistance || dist3D > maxDistance)) {", PROJ, "key frame: distance == 0.8 min refused")
+M(153, F, "if (!(dist3D < minDistance || dist3D > maxDistance)) {", "if (!(dist3D < minDistance || dist3D >= maxDistance)) {", PROJ, "key frame: distance == 1.2 max refused")
+M(154, F, "q.min_level = n - 1; q.max_level = n + 1; q.active = 1; q.gate = 0;", "q.min_level = n - 1; q.max_level = n; q.active = 1; q.gate = 0;", PROJ, "key frame: the level above the predicted one refused")
+M(155, F, "if (F.forward) { q.min_level = oct; q.max_level = -1; }", "if (F.forward) { q.min_level = oct + 1; q.max_level = -1; }", PROJ, "last frame, forward: the keypoint's own octave refused")
+M(156, F, "else if (F.backward) { q.min_level = 0; q.max_level = oct; }", "else if (F.backward) { q.min_level = 0; q.max_level = oct - 1; }", PROJ, "last frame, backward: the keypoint's own octave refused")
+M(157, F, "else { q.min_level = oct - 1; q.max_level = oct + 1; }", "else { q.min_level = oct; q.max_level = oct + 1; }", PROJ, "last frame: the octave below refused")
+# fuse_query, fuse_best_free, k_fuse_candidates, sim3_choice
+M(160, F, "A.min_level = n - 1; A.max_level = n; A.active = 1; A.gate = chi2_gate ? 2 : 0;", "A.min_level = n; A.max_level = n; A.active = 1; A.gate = chi2_gate ? 2 : 0;", FUSE + SIM3, "Fuse / Sim3: the level below the predicted one refused")
+M(161, F, "A.min_level = n - 1; A.max_level = n; A.active = 1; A.gate = chi2_gate ? 2 : 0;", "A.min_level = n - 1; A.max_level = n + 1; A.active = 1; A.gate = chi2_gate ? 2 : 0;", FUSE + SIM3, "Fuse / Sim3: the level above the predicted one admitted")
+M(162, F, "if (dist < best_dist) { best_dist = dist; best_idx = idx; }", "if (dist <= best_dist) { best_dist = dist; best_idx = idx; }", FUSE + SIM3, "Fuse / Sim3: the last of equal distances wins")
+M(163, F, "if (bd > th_low) bi = -1;", "if (bd >= th_low) bi = -1;", FUSE, "Fuse: bestDist == TH_LOW refused")
+M(164, F, "return (bi >= 0 && (float)bd <= max_dist) ? bi : -1;", "return (bi >= 0 && (float)bd < max_dist) ? bi : -1;", SIM3, "Sim3: bestDist == TH_LOW * ratioHamming refused")
+M(165, F, "if (A.gate == 2 && !chi2_accept(A, k, R.ur[idx], g)) continue;", "", FUSE, "Fuse: the chi-square gate removed")
+# accept bodies: local, last frame, rig
+M(170, F, "accept = t.bestDist <= th_high && (LASTFRAME ||", "accept = t.bestDist < th_high && (LASTFRAME ||", LOCAL + PROJ[:2], "accept: bestDist == TH_HIGH refused")
+M(171, F, "!(t.bestLevel == t.bestLevel2 && (float)t.bestDist > __fmul_rn(nnratio, (float)t.bestDist2)));", "!(t.bestLevel == t.bestLevel2 && (float)t.bestDist >= __fmul_rn(nnratio, (float)t.bestDist2)));", LOCAL, "accept: bestDist == mfNNratio * bestDist2 refused")
+M(172, F, "!(t.bestLevel == t.bestLevel2 && (float)t.bestDist > __fmul_rn(nnratio, (float)t.bestDist2)));", "!((float)t.bestDist > __fmul_rn(nnratio, (float)t.bestDist2)));", LOCAL, "accept: the ratio test without the level-equality clause")
+M(173, F, "const bool claims = accept && obs;", "const bool claims = accept;", LOCAL, "accept: a point without observations occupies its keypoint",
+  "equivalent in the output: `claims` only makes later lanes of the round wait (dirty); what they then decide is read from s_occ, which takes the point's has_obs two lines below")
+M(174, F, "if (obs) atomicOr(&s_occ[idx1 >> 5], 1u << (idx1 & 31));", "atomicOr(&s_occ[idx1 >> 5], 1u << (idx1 & 31));", LOCAL, "accept: a point without observations occupies its keypoint")
+M(175, F, "if (best1.any() && t1.bestDist <= th_high) {", "if (best1.any() && t1.bestDist < th_high) {", RIG, "rig accept, camera 1: bestDist == TH_HIGH refused")
+M(176, F, "if (best2.any() && t2.bestDist <= th_high) {", "if (best2.any() && t2.bestDist < th_high) {", RIG, "rig accept, camera 2: bestDist == TH_HIGH refused")
+M(177, F, "if (!LASTFRAME && t1.bestLevel == t1.bestLevel2 && (float)t1.bestDist > __fmul_rn(nnratio, (float)t1.bestDist2)) end = true;",
+  "if (!LASTFRAME && t1.bestLevel == t1.bestLevel2 && (float)t1.bestDist >= __fmul_rn(nnratio, (float)t1.bestDist2)) end = true;", RIG, "rig accept, camera 1: ratio test inclusive")
+M(178, F, "if (LASTFRAME || !(t2.bestLevel == t2.bestLevel2 && (float)t2.bestDist > __fmul_rn(nnratio, (float)t2.bestDist2))) {",
+  "if (LASTFRAME || !(t2.bestLevel == t2.bestLevel2 && (float)t2.bestDist >= __fmul_rn(nnratio, (float)t2.bestDist2))) {", RIG, "rig accept, camera 2: ratio test inclusive")
+M(179, F, "if (!LASTFRAME && t1.bestLevel == t1.bestLevel2 && (float)t1.bestDist >", "if (!LASTFRAME && (float)t1.bestDist >", RIG, "rig accept, camera 1: the ratio test without the level-equality clause")
+M(180, F, "if (!end && c2 > 0) {", "if (c2 > 0) {", RIG, "rig accept: camera 2 searched after a ratio-test rejection of camera 1")
+# the rotation histogram
+M(185, F, "if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);", "if (rot <= 0.0f) rot = __fadd_rn(rot, 360.0f);", PROJ + BOW[:3] + ["test_keyframe_search_gates.py"], "rotation: a difference of exactly 0 becomes 360 (bin 12 instead of bin 0)")
+M(186, F, "return bin == 30 ? 0 : bin;", "return bin == 29 ? 0 : bin;", PROJ + BOW[:3], "rotation: bin 29 folded onto bin 0",
+  note="equivalent: rot lies in [0, 360) and the factor is 1 / 30, so bin = round(rot / 30) is at most 12 (the reference's HISTO_LENGTH quirk); neither 29 nor 30 ever occurs")
+M(187, F, "if ((float)max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }", "if ((float)max2 <= __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }", PROJ + BOW[:3], "three maxima: a second bin of exactly 10 % dropped")
+M(188, F, "else if ((float)max3 < __fmul_rn(0.1f, (float)max1)) ind3 = -1;", "else if ((float)max3 <= __fmul_rn(0.1f, (float)max1)) ind3 = -1;", PROJ + BOW[:3], "three maxima: a third bin of exactly 10 % dropped")
+M(189, F, "if (sz > max1) { max3 = max2;", "if (sz >= max1) { max3 = max2;", PROJ + BOW[:3], "three maxima: the last of equal bins is the first maximum")
+# bow_search_core (SearchForTriangulation), k_sft_*
+M(190, F, "const bool stereo2 = ur2[idx2] >= 0;", "const bool stereo2 = ur2[idx2] > 0;", BOW, "triangulation search: a right coordinate of exactly 0 counts as monocular")
+M(191, F, "if (P.only_stereo && !stereo2) continue;", "", BOW, "triangulation search: the only_stereo gate on KF2 removed")
+M(192, F, "if (dist > P.th_low) continue;", "if (dist >= P.th_low) continue;", BOW, "triangulation search: distance == TH_LOW refused")
+M(193, F, "< __fmul_rn(100.f, P.scale2[k2.octave])) continue;", "<= __fmul_rn(100.f, P.scale2[k2.octave])) continue;", BOW, "triangulation search: epipole distance == bound refused")
+M(194, F, "if (!stereo1 && !stereo2 && !(KB8 && P.nleft1 >= 0)) {", "if (!stereo1 && !(KB8 && P.nleft1 >= 0)) {", BOW, "triangulation search: epipole test for stereo keypoints of KF2")
+M(195, F, "if (!(z > 0.0001f)) continue;", "if (!(z > 0.0f)) continue;", BOW, "triangulation search (KB8): depth gate 0 for 1e-4")
+M(196, F, "if (!((double)dsqr < 3.84 * (double)P.sigma2_2[k2.octave])) continue;", "if (!((double)dsqr <= 3.84 * (double)P.sigma2_2[k2.octave])) continue;", BOW, "triangulation search: epipolar distance == bound accepted")
+M(197, F, "if (!((double)dsqr < 3.84 * (double)P.sigma2_2[k2.octave])) continue;", "if (!((double)dsqr < 5.99 * (double)P.sigma2_2[k2.octave])) continue;", BOW, "triangulation search: 5.99 for 3.84")
+M(198, F, "((unsigned)dist << 16) | (unsigned)(0xFFFF - j);", "((unsigned)dist << 16) | (unsigned)j;", BOW, "triangulation search: the first of equal distances wins",
+  more=[("feat2[0xFFFF - (int)(best & 0xFFFF)];", "feat2[(int)(best & 0xFFFF)];")])
+M(199, F, "if (a >= 0 && !flags[idx1] && !(S.P.only_stereo && !stereo1)) {", "if (a >= 0 && !flags[idx1]) {", BOW, "triangulation search (resident): the only_stereo gate on KF1 removed")
+M(200, F, "const bool stereo1 = k1.ur[idx1] >= 0;", "const bool stereo1 = k1.ur[idx1] > 0;", BOW, "triangulation search (resident): KF1 right coordinate of exactly 0 counts as monocular")
+# bow_match_node, bow_prune_body
+M(205, F, "const bool pass = th_inclusive ? bestDist1 <= th_low : bestDist1 < th_low;", "const bool pass = th_inclusive ? bestDist1 < th_low : bestDist1 <= th_low;", BOW, "SearchByBoW: the TH_LOW comparisons of the two forms swapped")
+M(206, F, "if (pass && (float)bestDist1 < __fmul_rn(nnratio, (float)bestDist2)) {", "if (pass && (float)bestDist1 <= __fmul_rn(nnratio, (float)bestDist2)) {", BOW, "SearchByBoW: ratio test inclusive")
+M(207, F, "if ((int)(mr >> 16) <= th_low) {", "if ((int)(mr >> 16) < th_low) {", BOW, "SearchByBoW (rig): camera 2's best == TH_LOW refused")
+M(208, F, "if (RIG && pass) {", "if (RIG) {", BOW, "SearchByBoW (rig): camera 2 considered though camera 1's best failed TH_LOW")
+M(209, F, "if (!mp1[idx1]) continue;", "", BOW, "SearchByBoW: features of K1 without a good map point searched")
+M(210, F, "if (el2 && !el2[idx2]) continue;", "", BOW, "SearchByBoW: ineligible features of K2 are candidates")
+M(211, F, "if (!top.keeps(bin_of(i, j))) { m[i] = -1; nm--; }", "if (top.keeps(bin_of(i, j))) { m[i] = -1; nm--; }", BOW, "rotation pruning negated")
+# the resident map's state tests
+M(220, F, "return slot >= 0 && state[slot] == kMapPresent ? slot : -1;", "return slot >= 0 && (state[slot] & kMapPresent) ? slot : -1;", MAP, "map_visit: a bad point is visited")
+M(221, F, "ok = (st & kMapPresent) && !(rows && (st & kMapBad)) && !excluded[o];", "ok = (st & kMapPresent) && !(st & kMapBad) && !excluded[o];", MAP + PROJ[:2], "rows gather: the last-frame form refuses bad points too")
+M(222, F, "ok = (st & kMapPresent) && !(rows && (st & kMapBad)) && !excluded[o];", "ok = (st & kMapPresent) && !excluded[o];", MAP + PROJ[:2], "rows gather: the key-frame form admits bad points")
+M(223, F, "ok = (st & kMapPresent) && !(rows && (st & kMapBad)) && !excluded[o];", "ok = (st & kMapPresent) && !(rows && (st & kMapBad));", MAP + PROJ[:2], "rows gather: the caller's exclusion flag ignored")
+M(224, F, "(R.rule == kRowHoldsPoint ? (state[slot] & kMapPresent) != 0 : state[slot] == kMapPresent)", "(R.rule == kRowHoldsPoint ? state[slot] == kMapPresent : state[slot] == kMapPresent)", MAP + BOW[:1], "row flags: kRowHoldsPoint refuses bad points")
+M(225, F, "(R.rule == kRowHoldsPoint ? (state[slot] & kMapPresent) != 0 : state[slot] == kMapPresent)", "(R.rule == kRowHoldsPoint ? (state[slot] & kMapPresent) != 0 : (state[slot] & kMapPresent) != 0)", MAP + BOW[:1], "row flags: kRowHoldsGoodPoint admits bad points")
+M(226, F, "out = st == kMapPresent ? slot : (st & kMapPresent) ? -2 : -1;", "out = (st & kMapPresent) ? slot : -1;", MAP + FUSE[:2], "fuse kf slots: a bad point in the key frame is fused with")
+M(227, F, "out = st == kMapPresent ? slot : (st & kMapPresent) ? -2 : -1;", "out = st == kMapPresent ? slot : -1;", MAP + FUSE[:2], "fuse kf slots: a bad point in the key frame reads as an empty entry")
+M(228, F, "const uint8_t bad = (uint8_t)(state[slot] != kMapPresent);", "const uint8_t bad = (uint8_t)((state[slot] & kMapPresent) == 0);", MAP + FUSE[:2] + SIM3[:2], "set table: a bad point is not skipped")
+M(229, F, "if (q == 0 && (S.state[slot] & kMapPresent)) S.state[slot] = st;", "if (q == 0) S.state[slot] = st;", MAP, "set_bad: a slot that holds nothing becomes present")
+M(230, F, "if (t > base && p < (unsigned)M) skip", "if (t >= base && p < (unsigned)M) skip", MAP + FUSE[:2] + SIM3[:2], "skip listed: a stamp of an earlier call counts as in the set",
+  note="equivalent: top = base + M, so a stamp t == base gives the position p = top - t = M, and the clause p < M beside it refuses exactly that value")
+# k_stereo_from_depth
+M(235, F, "if (d > 0) {\n                const float xu", "if (d >= 0) {\n                const float xu", ["test_local_points_batch.py", "test_emu_search.py", "test_frame_reference.py"], "RGB-D: depth 0 is a measurement")
+
+# ---- k_vocab.hip ---------------------------------------------------------------------------------------------------------------------------------------------
+F = "k_vocab.hip"
+VOC = ["test_emu_vocab.py", "test_emu_kfdb.py"]
+M(300, F, "key = ((unsigned)dist << 8) | (unsigned)c;", "key = ((unsigned)dist << 8) | (unsigned)(255 - c);", VOC, "descend: the last child of equal distances wins",
+  more=[("slot = cs + (int)(best & 0xFFu);", "slot = cs + 255 - (int)(best & 0xFFu);")])
+M(301, F, "if (i < n && wt_[i] > 0) {", "if (i < n && wt_[i] >= 0) {", VOC, "assemble: stopped words (weight 0) enter the vectors")
+M(302, F, "if (weighting <= 1) for (int t = s + 1;", "if (weighting < 1) for (int t = s + 1;", VOC, "assemble: TF counts a word once")
+M(303, F, "if (weighting <= 1) for (int t = s + 1;", "if (weighting <= 2) for (int t = s + 1;", VOC, "assemble: IDF adds the weight per feature")
+M(304, F, "if (weighting <= 1 && norm == 0 && nu > 0) {", "if (weighting < 1 && norm == 0 && nu > 0) {", VOC, "assemble: TF without normalisation not divided by the word count")
+M(305, F, "if (weighting <= 1 && norm == 0 && nu > 0) {", "if (weighting <= 1 && nu > 0) {", VOC, "assemble: divided by the word count although normalised")
+M(306, F, "if (norm == 1) for (int u = 0; u < nu; u++) acc = acc + fabs(", "if (norm == 2) for (int u = 0; u < nu; u++) acc = acc + fabs(", VOC, "assemble: L1 and L2 norms swapped")
+M(307, F, "if (nv > 0.0) for", "if (nv >= 0.0) for", VOC, "assemble: a zero norm divides",
+  "equivalent: every value is a sum of weights > 0 (stopped words are filtered above), so nv == 0 only when nu == 0, and then the loop is empty")
+M(310, F, "if (qw[mid] < w) lo = mid + 1; else hi = mid;", "if (qw[mid] <= w) lo = mid + 1; else hi = mid;", VOC, "kfdb: the word search steps over an equal id")
+M(311, F, "const int minc = (int)((float)mx * 0.8f);", "const int minc = (int)((float)mx * 0.7f);", VOC, "kfdb: minCommonWords 0.7 of the maximum")
+M(312, F, "const int sc = (score_all || v > minc) ? 1 : 0;", "const int sc = (score_all || v >= minc) ? 1 : 0;", VOC, "kfdb: minCommonWords inclusive")
+M(313, F, "if (j < lane) rank++; else if (j > lane) last = false;", "if (j > lane) rank++; else if (j < lane) last = false;", VOC, "kfdb: records of equal first position in reverse order")
+M(314, F, "if (sv != 0.0) t = __dmul_rn(vi, wi) / sv; else hit = 0;", "if (sv == 0.0) t = __dmul_rn(vi, wi) / sv; else hit = 0;", VOC, "kfdb chi-square: the zero test negated")
+M(315, F, "score = acc >= 1.0 ? 1.0 :", "score = acc > 1.0 ? 1.0 :", VOC, "kfdb L2: clamp exclusive",
+  "equivalent: at acc == 1.0 the other arm gives 1.0 - sqrt(1.0 - 1.0) = 1.0 as well")
+M(316, F, "if (scoring == 0) score = -acc / 2.0;", "if (scoring == 5) score = -acc / 2.0;", VOC, "kfdb: the L1 finisher on the dot product instead")
+M(317, F, "else if (scoring == 1) score = acc >= 1.0", "else if (scoring == 5) score = acc >= 1.0", VOC, "kfdb: the L2 finisher on the dot product instead")
+M(318, F, "else if (scoring == 2) score = __dmul_rn(2.0, acc);", "else if (scoring == 5) score = __dmul_rn(2.0, acc);", VOC, "kfdb: the chi-square finisher on the dot product instead")
+
+# ---- k_describe.hip: k_layout and fast_atan2_deg ------------------------------------------------------------------------------------------------------------
+# (bucket_of's imin / imax clamp an index into the row histogram: address arithmetic, not mutated)
+F = "k_describe.hip"
+LAYOUT = ["test_emu_parity.py", "test_emu_fuzz.py", "test_knn2_constructed.py"]
+ATAN = ["test_model_sweep.py", "test_models.py", "test_orient_chain.py"]
+M(400, F, "xf >= (float)lap0 && xf <= (float)lap1;", "xf > (float)lap0 && xf <= (float)lap1;", LAYOUT, "layout: x == lapping begin is monocular")
+M(401, F, "xf >= (float)lap0 && xf <= (float)lap1;", "xf >= (float)lap0 && xf < (float)lap1;", LAYOUT, "layout: x == lapping end is monocular")
+M(402, F, "if (x < 0) a = __fsub_rn(180.f, a);", "if (x <= 0) a = __fsub_rn(180.f, a);", ATAN, "fastAtan2: x == 0 mirrored (differs at x = y = 0 only: 180 for 0)")
+M(403, F, "if (y < 0) a = __fsub_rn(360.f, a);", "if (y <= 0) a = __fsub_rn(360.f, a);", ATAN, "fastAtan2: y == 0 gives 360 - a")
+M(404, F, "if (ax >= ay) {", "if (ax > ay) {", ATAN, "fastAtan2: |x| == |y| takes the 90 - a branch")
