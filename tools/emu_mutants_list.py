@@ -1,4 +1,4 @@
-"""The mutants of tools/emu_mutants.py: (id, file in csrc, old text that occurs EXACTLY ONCE in that file, new text, CPU test files, intent[, note]).
+"""The mutants of tools/emu_mutants.py: (id, file in csrc, old text that occurs EXACTLY ONCE in that file, new text, CPU test files or node ids, intent[, note][, defines]).
 
 Only decisions are mutated: a relational boundary, one clause of a compound gate removed or negated, a rank or threshold constant off by one, a tie broken the other
 way, a gate's constant replaced by a neighbour.  Never address arithmetic, loop bounds over memory, launch geometry, synchronisation or the lines under the
@@ -18,9 +18,11 @@ DISTINCTIVE = ["test_distinctive_resident.py", "test_emu_mappoint.py"]
 MUTANTS = []
 
 
-def M(id, file, old, new, tests, intent, note=None, more=()):
-    """more: further (old, new) pairs of the same mutant, each old text unique too - for a decision that is written at two places (a tie order packed into a key and unpacked again)"""
-    MUTANTS.append(dict(id=id, file=file, old=old, new=new, tests=list(tests), intent=intent, note=note, more=list(more)))
+def M(id, file, old, new, tests, intent, note=None, more=(), defines=()):
+    """more: further (old, new) pairs of the same mutant, each old text unique too - for a decision that is written at two places (a tie order packed into a key and unpacked again)
+    defines: compiler switches the mutant's whole library is built with (the variants of tests/test_emu_variants.py), for decisions the default build reaches only on huge inputs
+    tests: file names, or pytest node ids where the whole file takes minutes on the emulator; cheapest first"""
+    MUTANTS.append(dict(id=id, file=file, old=old, new=new, tests=list(tests), intent=intent, note=note, more=list(more), defines=list(defines)))
 
 
 # ---- k_match.hip ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -264,3 +266,208 @@ M(401, F, "xf >= (float)lap0 && xf <= (float)lap1;", "xf >= (float)lap0 && xf < 
 M(402, F, "if (x < 0) a = __fsub_rn(180.f, a);", "if (x <= 0) a = __fsub_rn(180.f, a);", ATAN, "fastAtan2: x == 0 mirrored (differs at x = y = 0 only: 180 for 0)")
 M(403, F, "if (y < 0) a = __fsub_rn(360.f, a);", "if (y <= 0) a = __fsub_rn(360.f, a);", ATAN, "fastAtan2: y == 0 gives 360 - a")
 M(404, F, "if (ax >= ay) {", "if (ax > ay) {", ATAN, "fastAtan2: |x| == |y| takes the 90 - a branch")
+
+
+# ==== the extraction half: k_describe (rest), k_fast, k_quadtree, k_image, blur_body.h, k_input and the host tables of orbx_api.cpp ================================
+# These kernels write into arrays sized from the decisions themselves, so the safety rule is stricter: no mutant may let a kernel emit more items into a
+# fixed-capacity array than the array was sized for (profiles/emu_mutants_extract/README.md, "What is not in the list", names every line left out for that).
+# The whole of tests/test_emu_parity.py takes minutes on the emulator (its 4127-pixel cases): the groups name the small cases by node id, the new constructed
+# tests first.
+NEW = "test_extract_decisions.py"
+SMALL = ["test_emu_parity.py::test_extractor_stagewise_and_final[%s]" % c for c in
+         ("small_376x240_n500", "small_lap_partial", "small_noise", "small_threshold_fallback", "small_280x260_wide_cells", "min_239x239_noise_n1000")]
+EXTRACT = [NEW] + SMALL + ["test_emu_parity.py::test_extreme_fast_thresholds", "test_emu_parity.py::test_other_parameters_and_gauss_variant", "test_emu_fuzz.py"]
+IMAGE = EXTRACT + ["test_emu_parity.py::test_pyramid_one_launch_emulated", "test_emu_parity.py::test_row_ends_of_every_width", "test_emu_pyramid_export.py"]
+DESCRIBE = EXTRACT + ["test_orient_chain.py"]
+DESCRIBE_STEREO = DESCRIBE + ["test_emu_parity.py::test_batch_and_stereo_and_knn", "test_stereo_chain.py"]
+INPUT = ["test_emu_input.py"]
+LOOSER = ("equivalent in the output: the quick test of phase A only chooses which pixels phase B scores; phase B (fast_score_pk) decides exactly and writes a score "
+          "only where it is positive, so a looser quick test lists more pixels and changes no score; a list that fills sooner gives the corner list up, and the "
+          "list-free NMS (C', D') computes the same set from the same score tile")
+
+# ---- k_describe.hip: k_orient_brief and the rest of k_layout -------------------------------------------------------------------------------------------------------
+F = "k_describe.hip"
+M(405, F, "au <= kHalfPatch && au <= um[trip];", "au <= kHalfPatch && au < um[trip];", DESCRIBE, "IC_Angle: the disc's rim columns (|u| == umax[|v|]) left out")
+M(406, F, "const bool on = av <= kHalfPatch &&", "const bool on = av < kHalfPatch &&", DESCRIBE, "IC_Angle: rows v = +-15 left out")
+M(407, F, "(uint32_t)(u + 16) << (8 * j)", "(uint32_t)(u + 17) << (8 * j)", DESCRIBE, "IC_Angle: column weight biased by 17 against the correction by 16")
+M(408, F, "int m10 = (int)du - 16 * ds;", "int m10 = (int)du - 15 * ds;", DESCRIBE, "IC_Angle: bias correction 15 * sum")
+M(409, F, "m01 += mul24(-kHalfPatch + 8 * trip + r8, s);", "m01 += mul24(kHalfPatch - 8 * trip - r8, s);", DESCRIBE, "IC_Angle: sign of m01's row weight")
+M(410, F, "ORBX_BALLOT(t0v[r] < t1v[r]);", "ORBX_BALLOT(t0v[r] <= t1v[r]);", DESCRIBE, "BRIEF: equal samples set the bit")
+M(411, F, "__fadd_rn(__fmul_rn(px0[r], bb), __fmul_rn(py0[r], a))", "__fsub_rn(__fmul_rn(px0[r], bb), __fmul_rn(py0[r], a))", DESCRIBE, "BRIEF: sign in the first point's row")
+M(412, F, "__fsub_rn(__fmul_rn(px0[r], a), __fmul_rn(py0[r], bb))", "__fadd_rn(__fmul_rn(px0[r], a), __fmul_rn(py0[r], bb))", DESCRIBE, "BRIEF: sign in the first point's column")
+M(413, F, "__fadd_rn(__fmul_rn(px1[r], bb), __fmul_rn(py1[r], a))", "__fsub_rn(__fmul_rn(px1[r], bb), __fmul_rn(py1[r], a))", DESCRIBE, "BRIEF: sign in the second point's row")
+M(414, F, "__fsub_rn(__fmul_rn(px1[r], a), __fmul_rn(py1[r], bb))", "__fadd_rn(__fmul_rn(px1[r], a), __fmul_rn(py1[r], bb))", DESCRIBE, "BRIEF: sign in the second point's column")
+M(415, F, "if (lvl[k] != 0) xf = __fmul_rn(xf, s_scale[lvl[k]]);", "if (lvl[k] > 1) xf = __fmul_rn(xf, s_scale[lvl[k]]);", DESCRIBE, "layout: level 1's x not scaled for the lapping test")
+M(416, F, "if (my_level != 0) { xf = __fmul_rn(xf, my_scale);", "if (my_level > 1) { xf = __fmul_rn(xf, my_scale);", DESCRIBE, "records: level 1 not scaled")
+M(417, F, "if (l != 0) yf = __fmul_rn(yf, s_scale[l]);", "if (l > 1) yf = __fmul_rn(yf, s_scale[l]);", DESCRIBE_STEREO, "row index: level 1's band from the unscaled y")
+M(418, F, "aux.x = (int)floorf(__fsub_rn(yf, r));", "aux.x = (int)ceilf(__fsub_rn(yf, r));", DESCRIBE_STEREO, "stereo band: first row rounded up")
+M(419, F, "aux.y = (int)ceilf(__fadd_rn(yf, r));", "aux.y = (int)floorf(__fadd_rn(yf, r));", DESCRIBE_STEREO, "stereo band: last row rounded down")
+M(420, F, "fin[k] = lapf[k] ? total - 1 - pl : pm;", "fin[k] = lapf[k] ? pm : total - 1 - pl;", DESCRIBE, "layout: lapping keypoints from the front, monocular ones from the back")
+M(421, F, "if (lvl[k] != 0) xf = __fmul_rn(xf, s_scale[lvl[k]]);", "xf = __fmul_rn(xf, s_scale[lvl[k]]);", DESCRIBE, "layout: level 0 scaled as well",
+  "equivalent: the scale of level 0 is 1.0f (init_tables, csrc/orbx_api.cpp: h->scale[0] = 1.0f) and x * 1.0f == x for every float")
+# (the band's half-height 2 * scale is written twice: the record's band and the row index's first row.  Only narrower bands are mutated: the matcher's look-back
+# over the row buckets is sized for 2 * scale by the host - orbm_stereo_match, `lookback` - and a wider band is not covered by that size argument)
+M(422, F, "const float r = __fmul_rn(2.0f, my_scale);", "const float r = __fmul_rn(1.0f, my_scale);", DESCRIBE_STEREO, "stereo band: half-height 1 * scale in the records")
+M(423, F, "__fsub_rn(yf, __fmul_rn(2.0f, s_scale[l]))", "__fsub_rn(yf, __fmul_rn(1.0f, s_scale[l]))", DESCRIBE_STEREO, "row index: first row from a half-height of 1 * scale")
+
+# ---- k_fast.hip ----------------------------------------------------------------------------------------------------------------------------------------------------
+F = "k_fast.hip"
+CAP = ("-DORBX_FAST_LIST_CAP=200",)
+M(500, F, "sA = mA > t0 ? mA - 1 : 0;", "sA = mA >= t0 ? mA - 1 : 0;", EXTRACT, "FAST score: arc difference == t is a corner (entry A)")
+M(501, F, "sB = mB > t0 ? mB - 1 : 0;", "sB = mB >= t0 ? mB - 1 : 0;", EXTRACT, "FAST score: arc difference == t is a corner (entry B)")
+M(502, F, "sA = mA > t0 ? mA - 1 : 0;", "sA = mA > t0 + 1 ? mA - 1 : 0;", EXTRACT, "FAST score: arc difference == t + 1 is no corner (entry A)")
+M(503, F, "sB = mB > t0 ? mB - 1 : 0;", "sB = mB > t0 + 1 ? mB - 1 : 0;", EXTRACT, "FAST score: arc difference == t + 1 is no corner (entry B)")
+M(504, F, "sA = mA > t0 ? mA - 1 : 0;", "sA = mA > t0 ? mA : 0;", EXTRACT, "FAST score: the arc difference itself (entry A)")
+M(505, F, "sB = mB > t0 ? mB - 1 : 0;", "sB = mB > t0 ? mB : 0;", EXTRACT, "FAST score: the arc difference itself (entry B)")
+M(506, F, "const int td = (t0 + 1) >> 1;", "const int td = (t0 + 2) >> 1;", EXTRACT, "quick test: td one higher for even thresholds (stricter)")
+M(507, F, "Cd = (uint32_t)(td - 1) * 0x01010101u,", "Cd = (uint32_t)td * 0x01010101u,", EXTRACT, "quick test: dark bound V - td instead of V - td + 1 (stricter)")
+M(508, F, "Tb = (uint32_t)td * 0x01010101u;", "Tb = (uint32_t)(td + 1) * 0x01010101u;", EXTRACT, "quick test: bright bound V + td + 1 (stricter)")
+M(509, F, "Tb = (uint32_t)td * 0x01010101u;", "Tb = (uint32_t)(td - 1) * 0x01010101u;", EXTRACT, "quick test: bright bound V + td - 1 (looser)", LOOSER + " (t0 >= 1 in this branch, so td - 1 >= 0)")
+M(510, F, "const uint32_t Qd = x & (mx - (mx >> 7));", "const uint32_t Qd = x & kL7;", EXTRACT, "quick test: max(V - td + 1, 0) without the saturation at 0",
+  "equivalent in the output: where V - td + 1 < 0 the byte of x is 128 + V - td + 1 in 1..127, so the mutant compares the ring with a bound above 0 where the kernel "
+  "compares with 0 (every ring pixel `not dark`, SD = 0); a pixel with v - t0 < 0 has no dark corner, and what the mutant lists in addition phase B scores 0.  " + LOOSER)
+M(511, F, "const uint32_t Pb = y ^ (y & (my - (my >> 7)));", "const uint32_t Pb = y;", EXTRACT, "quick test: min(V + td, 128) without the saturation at 128")
+M(512, F, "if (t0 >= 1) {", "if (t0 >= 2) {", EXTRACT, "quick test: threshold 1 takes the score-everything branch", LOOSER)
+M(513, F, "if (t0 >= 1) {", "if (t0 >= 0) {", EXTRACT, "quick test: threshold 0 goes through the byte arithmetic (td = 0)")
+for _i, (_a, _b) in enumerate((("q0", "q4"), ("q1", "q5"), ("q2", "q6"), ("q3", "q7"))):
+    M(514 + _i, F, "((%s - Qd) & (%s - Qd))" % (_a, _b), "((%s - Qd) | (%s - Qd))" % (_a, _b), EXTRACT, "quick test, dark: pair (%s, %s) needs BOTH ring pixels dark (stricter)" % (_a, _b))
+    M(518 + _i, F, "((%s - Pb) | (%s - Pb))" % (_a, _b), "((%s - Pb) & (%s - Pb))" % (_a, _b), EXTRACT, "quick test, bright: pair (%s, %s) needs BOTH ring pixels bright (stricter)" % (_a, _b))
+M(522, F, " | ((q3 - Qd) & (q7 - Qd));", ";", EXTRACT, "quick test, dark: the pair (6, 14) dropped (looser)", LOOSER)
+M(523, F, " & ((q3 - Pb) | (q7 - Pb));", ";", EXTRACT, "quick test, bright: the pair (6, 14) dropped (looser)", LOOSER)
+M(524, F, "const uint32_t ANY = SD | SB, BOTH = SD & SB;", "const uint32_t ANY = SD | SB, BOTH = 0u;", EXTRACT, "dual polarity: no second (dark) entry for a pixel listed for both")
+M(525, F, "((SB & (0x80u << (8 * j))) ? kEntBright : 0)", "((SD & (0x80u << (8 * j))) ? 0 : kEntBright)", EXTRACT, "dual polarity: the first entry of a pixel listed for both is dark too")
+M(526, F, "list[cnt + lanes_below(bald[j])] = (uint16_t)(toff + j);", "list[cnt + lanes_below(bald[j])] = (uint16_t)((toff + j) | kEntBright);", EXTRACT, "dual polarity: the second entry is bright too")
+M(527, F, "if (sA > 0) sc[oA] = (uint8_t)sA;", "if (sA >= 0) sc[oA] = (uint8_t)sA;", EXTRACT, "score tile: a zero score overwrites the other polarity's (entry A)")
+M(528, F, "if (hasB && sB > 0) sc[oB] = (uint8_t)sB;", "if (hasB && sB >= 0) sc[oB] = (uint8_t)sB;", EXTRACT, "score tile: a zero score overwrites the other polarity's (entry B)")
+M(529, F, "if (hasB && sB > 0) sc[oB] = (uint8_t)sB;", "if (sB > 0) sc[oB] = (uint8_t)sB;", EXTRACT, "score tile: the hasB clause removed",
+  "equivalent: without a second entry eB = eA (the line above), so sB == sA and oB == oA: the same byte is written twice")
+# NMS strictness, one neighbour at a time: `c[n] - 1` makes the comparison with that neighbour >= and leaves the seven others strict.  Of two adjacent pixels one
+# still sees the other through a strict comparison, so no two adjacent pixels survive and the count stays within ((iw + 1) / 2) * ((ih + 1) / 2), the cell's slots;
+# a score-0 pixel of the list-free path still has seven neighbours >= 0 and does not survive.
+_NB = (("c[-wp - 1]", "upper left"), ("c[-wp]", "upper"), ("c[-wp + 1]", "upper right"), ("c[-1]", "left"), ("c[1]", "right"), ("c[wp - 1]", "lower left"), ("c[wp]", "lower"),
+       ("c[wp + 1]", "lower right"))
+_M0 = "const int m0 = imax(imax((int)c[-wp - 1], (int)c[-wp]), imax((int)c[-wp + 1], (int)c[-1]));"
+_M1 = "const int m1 = imax(imax((int)c[1], (int)c[wp - 1]), imax((int)c[wp], (int)c[wp + 1]));"
+for _i, (_n, _w) in enumerate(_NB):
+    _line = _M0 if _i < 4 else _M1
+    _mut = _line.replace("(int)%s" % _n, "(int)%s - 1" % _n)
+    if _i < 4:
+        M(530 + _i, F, "zero frame\n            " + _line, "zero frame\n            " + _mut, EXTRACT, "NMS (corner list): a tie with the %s neighbour survives" % _w)
+        M(540 + _i, F, "const int s = c[0];\n            " + _line, "const int s = c[0];\n            " + _mut, EXTRACT, "NMS (list-free): a tie with the %s neighbour survives" % _w, defines=CAP)
+    else:
+        M(530 + _i, F, _line + "\n            if (s > imax(m0, m1)) atomicOr", _mut + "\n            if (s > imax(m0, m1)) atomicOr", EXTRACT, "NMS (corner list): a tie with the %s neighbour survives" % _w)
+        M(540 + _i, F, _line + "\n            kf[o]", _mut + "\n            kf[o]", EXTRACT, "NMS (list-free): a tie with the %s neighbour survives" % _w, defines=CAP)
+M(550, F, "const int t0 = pass == 0 ? iniTh : minTh;", "const int t0 = pass == 0 ? iniTh : iniTh;", EXTRACT, "second run: at iniTh again")
+M(551, F, "const int t0 = pass == 0 ? iniTh : minTh;", "const int t0 = pass == 0 ? iniTh : minTh + 1;", EXTRACT, "second run: at minTh + 1")
+M(552, F, "if (base > 0 || pass == 1 || minTh >= iniTh) break;", "if (base > 0 || pass == 1 || minTh > iniTh) break;", EXTRACT, "second run: also when minTh == iniTh",
+  "equivalent: the second run only happens for base == 0, and at the same threshold it computes the same empty set again")
+M(553, F, "if (base > 0 || pass == 1 || minTh >= iniTh) break;", "if (base > 0 || pass == 1) break;", EXTRACT, "second run: the minTh >= iniTh clause removed (a higher minTh is run)",
+  "equivalent: a strict 3x3 maximum with score >= minTh > iniTh is one with score >= iniTh too, so a cell that is empty at iniTh is empty at every higher threshold")
+M(554, F, "if (wpr <= kFastPitch) fast_cell<kFastPitch>", "if (wpr < kFastPitch) fast_cell<kFastPitch>", EXTRACT, "window of exactly kFastPitch bytes takes the variable-pitch form",
+  "equivalent: at wpr == kFastPitch the variable pitch wp = wpr is kFastPitch too; both forms lay the same tile out and the host sizes it with that pitch (configure, csrc/orbx_api.cpp: wp = gx1 - gx0 <= kFastPitch ? ..)")
+M(555, F, "if (cnt + trip > list_cap) {                         // wave-uniform", "if (cnt + trip >= list_cap) {                         // wave-uniform", EXTRACT,
+  "list flush: one trip earlier", "equivalent in the output: when the pending survivors are scored does not change their scores", defines=CAP)
+M(556, F, "if (cnt + trip > list_cap) { corners_listed = false;", "if (cnt + trip >= list_cap) { corners_listed = false;", EXTRACT, "list overflow: given up when the trip fits exactly",
+  "equivalent in the output: the list-free NMS and compaction (C', D') compute the same set in the same row-major order from the same score tile", defines=CAP)
+
+# ---- k_quadtree.hip ------------------------------------------------------------------------------------------------------------------------------------------------
+F = "k_quadtree.hip"
+QT = EXTRACT + ["test_quadtree_primitives.py", "test_quadtree_gather.py", "test_quadtree_lazy_sort.py"]
+M(600, F, "else if (nnodes + nexp * 3 > N) {", "else if (nnodes + nexp * 3 >= N) {", QT, "quadtree: the final rounds begin when a full pass could reach exactly N")
+# The child a key falls into (DivideNode :651-661) is spelled once per partition form.  Every mutant below changes count AND placement of one form together (one
+# classification feeds both, or both texts are edited), so the keys stay inside the node's span; the forms that the default build reaches only on big dense
+# levels are built with ORBX_PRESORT_MAX=1 (every division below depth 1 moves its keys: spans of thousands of keys on a 320 x 256 noise image)
+DEEP = ("-DORBX_PRESORT_MAX=1",)
+_CLS = "const bool left = key_x(key) < mx, top = key_y(key) < my;"
+M(601, F, _CLS + "\n        return left", _CLS.replace("< mx", "<= mx") + "\n        return left", QT, "workgroup partition: a key on the dividing column goes left", defines=DEEP)
+M(602, F, _CLS + "\n        return left", _CLS.replace("< my", "<= my") + "\n        return left", QT, "workgroup partition: a key on the dividing row goes up", defines=DEEP)
+_C4 = "const bool left = key_x(key[u]) < mx, top = key_y(key[u]) < my;"
+M(603, F, _C4, _C4.replace("< mx", "<= mx"), QT, "one-wave partition (<= 256 keys): a key on the dividing column goes left", defines=DEEP)
+M(604, F, _C4, _C4.replace("< my", "<= my"), QT, "one-wave partition (<= 256 keys): a key on the dividing row goes up", defines=DEEP)
+_W1 = "const uint32_t key = src[s + i0 + lane];\n            " + _CLS
+_W2 = "\n            key = src[s + i0 + lane];\n            " + _CLS
+M(605, F, _W1, _W1.replace("< mx", "<= mx"), QT, "one-wave partition (> 256 keys): a key on the dividing column goes left", more=[(_W2, _W2.replace("< mx", "<= mx"))], defines=DEEP)
+M(606, F, _W1, _W1.replace("< my", "<= my"), QT, "one-wave partition (> 256 keys): a key on the dividing row goes up", more=[(_W2, _W2.replace("< my", "<= my"))], defines=DEEP)
+M(607, F, "const bool left = x < mx;", "const bool left = x <= mx;", QT, "presort: a key on a dividing column goes left (bucket table)")
+M(608, F, "const bool top = y < my;", "const bool top = y <= my;", QT, "presort: a key on a dividing row goes up (bucket table)")
+M(609, F, "if (ds > 0 || ko < bo) { best = key[u];", "if (ds > 0 || ko > bo) { best = key[u];", QT, "final selection: of equal responses the LAST in vKeys order wins (per lane)")
+M(610, F, "if (os > bs || (os == bs && oo < bo)) {", "if (os > bs || (os == bs && oo > bo)) {", QT, "final selection: of equal responses the LAST in vKeys order wins (between lanes)")
+M(611, F, "if (ds < 0) continue;", "if (ds <= 0) continue;", QT, "final selection: of equal responses the first in buffer order wins, not the first in vKeys order")
+M(612, F, "const uint32_t v = best[bk]; w = v > w ? v : w;", "const uint32_t v = best[bk]; w = (v > w) == (w != 0u) ? w : v;", QT, "final selection, never-sorted tree: the smallest bucket word wins")
+
+# ---- libstdcxx_sort_model.h: the pieces k_quadtree.hip runs (median of three, heap fallback; block_sort_libstdcxx has its own range loop) -----------------------------
+# Only ties are turned: `!less(b, a)` for `less(a, b)` differs from it on equal keys alone, so the pick is still A median of the three and the unguarded partition
+# keeps both its sentinels; the heap's loops are bounded by indices, not by comparisons.  What stays out is in the README, line by line.
+F = "libstdcxx_sort_model.h"
+SORT = ["test_quadtree_primitives.py"] + EXTRACT
+M(650, F, "if (less(a[ia], a[ib])) {", "if (!less(a[ib], a[ia])) {", SORT, "median of three: a == b takes the a < b branch")
+M(651, F, "if (less(a[ib], a[ic])) pick = ib;", "if (!less(a[ic], a[ib])) pick = ib;", SORT, "median of three (a < b): b == c picks b, not c")
+M(652, F, "else if (less(a[ia], a[ic])) pick = ic;", "else if (!less(a[ic], a[ia])) pick = ic;", SORT, "median of three (a < b, c <= b): a == c picks c, not a")
+M(653, F, "} else if (less(a[ia], a[ic])) pick = ia;", "} else if (!less(a[ic], a[ia])) pick = ia;", SORT, "median of three (a >= b): a == c picks a")
+M(654, F, "else if (less(a[ib], a[ic])) pick = ic;", "else if (!less(a[ic], a[ib])) pick = ic;", SORT, "median of three (a >= b, a >= c): b == c picks c, not b")
+M(655, F, "if (less(a[first + child], a[first + (child - 1)])) child--;", "if (!less(a[first + (child - 1)], a[first + child])) child--;", SORT, "heap fallback: of equal children the left one goes up")
+M(656, F, "while (hole > top && less(a[first + parent], value)) {", "while (hole > top && !less(value, a[first + parent])) {", SORT, "heap fallback: a value rises past an equal parent")
+
+# ---- k_image.hip ---------------------------------------------------------------------------------------------------------------------------------------------------
+F = "k_image.hip"
+_V = "int v = ((mul24_forced(b0, h0 >> 4) >> 16) + (mul24_forced(b1, h1 >> 4) >> 16) + 2) >> 2;"
+_V1 = _V.replace("+ 2) >> 2", "+ 1) >> 2")
+M(700, F, "a1[k]);\n                " + _V, "a1[k]);\n                " + _V1, IMAGE, "k_resize: rounding term 1")
+M(701, F, "a1);\n                " + _V, "a1);\n                " + _V1, IMAGE, "k_pyramid_fused: rounding term 1")
+M(702, F, "mulhi_u24_uniform(b1, Hc[k]), 2u);", "mulhi_u24_uniform(b1, Hc[k]), 1u);", IMAGE, "k_resize_rows: rounding term 1")
+M(704, F, "a1[k]);\n                " + _V + "\n                v = imin(imax(v, 0), 255);", "a1[k]);\n                " + _V + "\n                v = imin(imax(v, 0), 254);", IMAGE, "k_resize: clamp at 254")
+M(705, F, "a1);\n                " + _V + "\n                v = imin(imax(v, 0), 255);", "a1);\n                " + _V + "\n                v = imin(imax(v, 0), 254);", IMAGE, "k_pyramid_fused: clamp at 254")
+M(706, F, "H[k] = dot2_u16(byte_perm(w.hi, w.lo, sel[k]), wgt[k], 0u) & ~15u;", "H[k] = dot2_u16(byte_perm(w.hi, w.lo, sel[k]), wgt[k], 0u) & ~7u;", IMAGE, "k_resize_rows: the horizontal sum keeps bit 3")
+M(707, F, "p = p < 0 ? -p : 2 * len - 2 - p;", "p = p < 0 ? -p - 1 : 2 * len - 2 - p;", IMAGE, "framed export: left / upper border mirrors with the edge pixel repeated (REFLECT)")
+M(708, F, "p = p < 0 ? -p : 2 * len - 2 - p;", "p = p < 0 ? -p : 2 * len - 1 - p;", IMAGE, "framed export: right / lower border mirrors with the edge pixel repeated (REFLECT)")
+M(709, F, "a1[k]);\n                " + _V, "a1[k]);\n                " + _V.replace("h0 >> 4", "h0 >> 5"), IMAGE, "k_resize: the upper row's horizontal sum shifted by 5")
+M(710, F, "a1[k]);\n                " + _V, "a1[k]);\n                " + _V.replace("h1 >> 4) >> 16", "h1 >> 4) >> 17"), IMAGE, "k_resize: the lower row's product shifted by 17")
+M(711, F, "a1);\n                " + _V, "a1);\n                " + _V.replace("h0 >> 4", "h0 >> 5"), IMAGE, "k_pyramid_fused: the upper row's horizontal sum shifted by 5")
+M(712, F, "a1);\n                " + _V, "a1);\n                " + _V.replace("h1 >> 4) >> 16", "h1 >> 4) >> 17"), IMAGE, "k_pyramid_fused: the lower row's product shifted by 17")
+M(713, F, "b1 = (uint32_t)(ty.w >> 16) << 12;", "b1 = (uint32_t)(ty.w >> 16) << 11;", IMAGE, "k_resize_rows: the lower row's weight scaled by 2^11 (its product shifted by 17)")
+
+# ---- blur_body.h (included by k_image.hip and k_fast.hip) ----------------------------------------------------------------------------------------------------------
+F = "blur_body.h"
+M(750, F, "if (col < 0) col = -col;", "if (col < 0) col = -col - 1;", IMAGE, "blur: left border mirrors with the edge column repeated")
+M(751, F, "if (col >= L.w) col = 2 * L.w - 2 - col;", "if (col >= L.w) col = 2 * L.w - 1 - col;", IMAGE, "blur: right border mirrors with the edge column repeated")
+M(752, F, "if (y < 0) y = -y;", "if (y < 0) y = -y - 1;", IMAGE, "blur: upper border mirrors with the edge row repeated")
+M(753, F, "if (y >= L.h) y = 2 * L.h - 2 - y;", "if (y >= L.h) y = 2 * L.h - 1 - y;", IMAGE, "blur: lower border mirrors with the edge row repeated")
+M(754, F, "dot2_u16(Q[3][j], Ke3, 32768u)", "dot2_u16(Q[3][j], Ke3, 32767u)", IMAGE, "blur: rounding term 32767 (even rows)")
+M(755, F, "dot2_u16(Q[3][j], Ko3, 32768u)", "dot2_u16(Q[3][j], Ko3, 32767u)", IMAGE, "blur: rounding term 32767 (odd rows)")
+M(756, F, "const bool exact256 = 2 * (k0 + k1 + k2) + k3 <= 256;", "const bool exact256 = 2 * (k0 + k1 + k2) + k3 < 256;", IMAGE, "blur: taps that sum to 256 take the shift-and-clamp form",
+  "equivalent: with taps that sum to 256 the accumulator is at most 255 * 65536 + 32768, so `>> 16` is byte 2 and the clamp at 255 never acts: both forms give the same bytes")
+M(757, F, "const bool exact256 = 2 * (k0 + k1 + k2) + k3 <= 256;", "const bool exact256 = 2 * (k0 + k1 + k2) + k3 <= 257;", IMAGE, "blur: taps that sum to 257 take the byte-permute form (no clamp)")
+M(758, F, "ve = ve > 255u ? 255u : ve;", "ve = ve > 255u ? 254u : ve;", IMAGE, "blur: the clamp of the 257 taps gives 254 (even rows)")
+M(759, F, "uint32_t ve = ae[j] >> 16, vo = ao[j] >> 16;", "uint32_t ve = ae[j] >> 15, vo = ao[j] >> 16;", IMAGE, "blur, 257 taps: even rows shifted by 15 (then clamped)")
+M(760, F, "oe = byte_perm(ae[1], ae[0], 0x0c0c0602u)", "oe = byte_perm(ae[1], ae[0], 0x0c0c0501u)", IMAGE, "blur, 256 taps: byte 1 of the accumulators of columns 0 and 1, a shift by 8 (even rows)")
+
+# ---- k_input.hip ---------------------------------------------------------------------------------------------------------------------------------------------------
+F = "k_input.hip"
+M(800, F, "+ p11 * w11 + (1 << 14)) >> 15;", "+ p11 * w11 + (1 << 14) - 1) >> 15;", INPUT, "remap: rounding term one less")
+M(801, F, "+ ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;", "+ ((b1 * (h1 >> 4)) >> 16) + 1) >> 2;", INPUT, "input resize: rounding term 1")
+M(802, F, "const int half = 1 << (shift - 1);", "const int half = (1 << (shift - 1)) - 1;", INPUT, "grey: rounding term one less")
+M(803, F, "r = byte_at(3 * j + ridx);", "r = byte_at(3 * j + 2 - ridx);", INPUT, "grey, 3 channels: red read from the blue channel")
+M(804, F, "r = (int)((q >> (8 * ridx)) & 0xFFu);", "r = (int)((q >> (8 * (2 - ridx))) & 0xFFu);", INPUT, "grey, 4 channels: red read from the blue channel")
+M(805, F, "(int)q[ridx] * ry", "(int)q[2 - ridx] * ry", INPUT, "grey, partial group: red read from the blue channel")
+M(806, F, "fsx = __float2int_rn(__fmul_rn(mx, 32.0f))", "fsx = (int)floorf(__fmul_rn(mx, 32.0f))", INPUT, "remap: x fixed point truncated instead of rounded")
+M(807, F, "fsy = __float2int_rn(__fmul_rn(my, 32.0f))", "fsy = (int)floorf(__fmul_rn(my, 32.0f))", INPUT, "remap: y fixed point truncated instead of rounded")
+M(808, F, "(((b0 * (h0 >> 4)) >> 16)", "(((b0 * (h0 >> 5)) >> 16)", INPUT, "input resize: the upper row's horizontal sum shifted by 5")
+
+# ---- orbx_api.cpp: the host tables that feed the extraction kernels ------------------------------------------------------------------------------------------------
+F = "orbx_api.cpp"
+TABLES = EXTRACT + ["test_abi.py"]
+M(900, F, "h->quota[l] = round_half_even_f(want);", "h->quota[l] = (int)want;", TABLES, "feature quota per level truncated instead of rounded")
+M(901, F, "std::max(h->nfeatures - sum, 0);", "std::max(h->nfeatures - sum - 1, 0);", TABLES, "feature quota: the last level gets one less than the remainder")
+M(902, F, "if (iniX >= maxBX - 6) continue;", "if (iniX > maxBX - 6) continue;", TABLES, "cell table: a column that starts at maxBX - 6 is kept",
+  "equivalent: such a cell has x0 = iniX + 3 = maxBX - 3 = x1, an empty interior; it takes no slot ((iw + 1) / 2 = 0) and fast_block writes the count 0 for it "
+  "(csrc/k_fast.hip: ci.x1 - ci.x0 <= 0), and the candidate lists are read cell by cell")
+M(903, F, "L.wcell = (int)ceil(width / L.ncols);", "L.wcell = (int)floor(width / L.ncols);", TABLES, "cell table: cell width rounded down")
+M(904, F, "L.hcell = (int)ceil(height / L.nrows);", "L.hcell = (int)floor(height / L.nrows);", TABLES, "cell table: cell height rounded down")
+M(905, F, "um[v] = round_half_even_d(sqrt(hp2 - v * v));", "um[v] = (int)sqrt(hp2 - v * v);", TABLES, "umax: half-widths truncated instead of rounded")
+M(906, F, "L.w = round_half_even_f((float)W * h->inv_scale[l]);", "L.w = (int)((float)W * h->inv_scale[l]);", TABLES, "level width truncated instead of rounded")
+M(907, F, "a1 = round_half_even_f(f * 2048.f);", "a1 = (int)(f * 2048.f);", TABLES + ["test_emu_input.py"], "resize taps: the second weight truncated instead of rounded")
+M(908, F, "L.patch = (int)(31 * h->scale[l]);", "L.patch = (int)(31 * h->scale[l] + 0.5f);", TABLES, "keypoint size rounded instead of truncated")
+M(909, F, "h->sigma2[i] = h->scale[i] * h->scale[i];", "h->sigma2[i] = h->scale[i];", TABLES, "level sigma2 table: the scale itself")
+M(910, F, "h->scale[i] = (float)(h->scale[i - 1] * h->scaleFactor);", "h->scale[i] = (float)pow((double)h->scaleFactor, (double)i);", TABLES, "scale table: the power, not the running product")
+M(911, F, "h->inv_scale[i] = 1.0f / h->scale[i];", "h->inv_scale[i] = (float)pow(1.0 / (double)h->scaleFactor, (double)i);", TABLES, "inverse scale table: the power of the inverse factor, not the inverse of the scale")
+M(912, F, "h->inv_sigma2[i] = 1.0f / h->sigma2[i];", "h->inv_sigma2[i] = h->inv_scale[i] * h->inv_scale[i];", TABLES, "inverse sigma2 table: the square of the inverse scale")
