@@ -964,7 +964,7 @@ protected:
         const int* Best(int row) const { return &best[(size_t)row * M]; }
         // the map points of a key frame at the moment of the question (the Sim3 overload's spAlreadyFound, :1563)
         bool Holds(KeyFrameT* pKF, MapPointT* p) { if (pKF != heldOf) { held = pKF->GetMapPoints(); heldOf = pKF; } return held.count(p) != 0; }
-        // rows [first, end) x every point: one upload of the set, one orbm_fuse_candidates_batch
+        // rows [first, end) x every point: one upload of the set, one orbm_fuse_pairs_batch
         template <class Excluded> void Search(int first, const Excluded& excluded)
         {
             best.assign(kfs.size() * (size_t)(M > 0 ? M : 1), -1);
@@ -1032,11 +1032,18 @@ protected:
             OrbmWorldPointView view = {n, p.data(), nr.data(), mn.data(), mx.data(), nullptr, nullptr, d.data()};
             orbm_points* set = nullptr;
             Check(orbm_points_create(SharedHandle(), &view, &set));
-            std::vector<int> out((size_t)rows * n, -1);
-            const int rc = orbm_fuse_candidates_batch(SharedHandle(), rows, &targets[first], set, skip.data(), th, chi2 ? 1 : 0, out.data(), nullptr);
+            // the matched pairs alone come down (a few per cent of rows x n); cap = every pair, so the call never has to be repeated: host memory only
+            const size_t pairs = std::min((size_t)rows * (size_t)n, (size_t)1 << 28);           // (beyond that the call refuses)
+            std::vector<int> start((size_t)rows + 1, 0), point(pairs), feat(pairs);
+            const int rc = orbm_fuse_pairs_batch(SharedHandle(), rows, &targets[first], set, skip.data(), th, chi2 ? 1 : 0, (int)pairs, start.data(), point.data(),
+                                                 feat.data(), nullptr);
             orbm_points_destroy(set);
             Check(rc);
-            for (int r = 0; r < rows; r++) for (int j = 0; j < n; j++) best[(size_t)(first + r) * M + subset[j]] = out[(size_t)r * n + j];
+            for (int r = 0; r < rows; r++) {
+                int* row = &best[(size_t)(first + r) * M];
+                for (int j = 0; j < n; j++) row[subset[j]] = -1;
+                for (int e = start[r]; e < start[r + 1]; e++) row[subset[point[e]]] = feat[e];
+            }
         }
         const std::vector<MapPointT*>& points; int M; float th; bool chi2;
         std::vector<float> pos, normal, mind, maxd; std::vector<uint8_t> desc;

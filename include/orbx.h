@@ -843,6 +843,25 @@ typedef struct OrbmFuseTarget OrbmFuseTarget;  /* ONE key frame (one camera) a p
 int orbm_fuse_candidates_batch(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const orbm_points* points, const uint8_t* skip /* [K][M] or NULL */,
                                float th, int chi2_gate, int* best_idx /* [K][M] */, int* best_dist /* [K][M] or NULL */);
 
+/* The same search, answered with the matched pairs alone: the replay reads only the pairs with best_idx >= 0, a few per cent of K x M at LoopClosing's
+ * shapes, and the dense arrays are most of what the dense call brings down.  The list holds EXACTLY the pairs (k, i) for which orbm_fuse_candidates_batch
+ * with the same arguments gives best_idx[k][i] >= 0 (the search kernels are that call's; the list is compacted from its dense result on the device),
+ * ordered by k, then by i - the order the replay visits them in (src/ORBmatcher.cc:1494-1520, :1640-1656).  Target k owns entries [start[k], start[k+1]),
+ * start[0] = 0; entry e: point[e] = i (the position in the set), feat[e] = best_idx[k][i], dist[e] = best_dist[k][i] (dist may be NULL).  A target without
+ * keypoints has an empty span.
+ *   Capacity: `cap` = the entries point / feat / dist have room for.  start[0 .. K] is written whenever the call returns ORBX_OK or ORBX_E_CAPACITY.  If
+ * start[K] > cap the call returns ORBX_E_CAPACITY and point / feat / dist are untouched - nothing is truncated; call again with cap >= start[K]
+ * (cap = K x M always suffices; device memory grows with min(cap, K x M) records, so a tight cap is the cheaper one).  K == 0 or an empty set: ORBX_OK,
+ * start all zero, nothing else written.
+ *   Blocking.  `start` comes down first and, in the same copy, as many entries as a quarter more than the handle's previous such call found (at least
+ * 1024): a list that short costs one wait for the stream, a longer one a second copy of exactly the entries still missing.
+ *   Refusals, limits, locking and the grid cache are orbm_fuse_candidates_batch's; refused as well (ORBX_E_ARG, before anything is enqueued): cap < 0, a
+ * null start, a null point or feat with cap > 0.  Device memory: the handle's reused scratch (the dense result stays on the device, plus 8 bytes per
+ * 256 positions of a target and the records), counted by orbx_debug_live_resources. */
+int orbm_fuse_pairs_batch(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const orbm_points* points, const uint8_t* skip /* [K][M] or NULL */,
+                          float th, int chi2_gate, int cap, int* start /* [K+1] */, int* point /* [cap] */, int* feat /* [cap] */,
+                          int* dist /* [cap] or NULL */);
+
 /* ORBmatcher::SearchByProjection(KeyFrame* pKF, Sim3f& Scw, vpPoints, vpMatched, th, ratioHamming) and the overload that also returns the points' key frames
  * (src/ORBmatcher.cc:495-606, :608-732) for ONE resident point set searched from K resident key frames, each under its own Sim3, in one call: LoopClosing's
  * FindMatchesByProjection searches the matched key frame's covisibility window from the current key frame and DetectCommonRegionsFromBoW searches the same set
@@ -1124,11 +1143,18 @@ int orbm_map_sets_fetch(orbx_extractor* h, const orbm_map* m, int set0, int B, c
  * a map (not at orbm_map_create), cleared then and when its epoch is used up (as the first-occurrence stamps), freed by orbm_map_destroy; the handle's
  * scratch as for the host-fed calls, with 16 bytes per target and the found lists uploaded in place of the K x M bytes, and 4 x K x M (Fuse) or
  * 4 x K x cap (Sim3) bytes for the second result.  orbx_debug_live_resources counts all of it.
+ *   orbm_fuse_pairs_batch_map: orbm_fuse_pairs_batch on the set, i.e. the pairs with best_idx >= 0 of orbm_fuse_candidates_batch_map with the same
+ * arguments, in the same order and under the same capacity rule (start always, every other array untouched on ORBX_E_CAPACITY), with two more optional
+ * arrays per entry: point_slot[e] = the map slot of set position point[e] (what orbm_map_set_fetch returns for it) and kf_slot[e] = the dense call's
+ * kf_slot[k][i] - slot / -1 / -2 as above, evaluated for the listed pairs only: the dense third array and its launch are not needed.
  * (The comment inside orbm_map_edit_keyframes' argument list keeps it out of the count tests/test_local_map_build.py takes, as orbm_map_sets_fetch's
  * does; that the three calls take the extractor first is checked by tests/test_fuse_map.py.) */
 int orbm_fuse_candidates_batch_map(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const int* rows /*[K]*/, const int* feat0 /*[K] or NULL*/,
                                    orbm_map* map, int set, float th, int chi2_gate, int* best_idx /*[K][M]*/, int* best_dist /*[K][M] or NULL*/,
                                    int* kf_slot /*[K][M] or NULL*/);
+int orbm_fuse_pairs_batch_map(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const int* rows /*[K]*/, const int* feat0 /*[K] or NULL*/,
+                              orbm_map* map, int set, float th, int chi2_gate, int cap, int* start /*[K+1]*/, int* point /*[cap]*/, int* feat /*[cap]*/,
+                              int* dist /*[cap] or NULL*/, int* point_slot /*[cap] or NULL*/, int* kf_slot /*[cap] or NULL*/);
 int orbm_search_by_projection_sim3_batch_map(orbx_extractor* h, int K, const OrbmSim3Target* targets, orbm_map* map, int set,
                                              const int* found_start /*[K+1] or NULL*/, const int* found_slots, float th, float ratio_hamming, int cap,
                                              int* assigned /*[K][cap]*/, int* nmatches /*[K]*/, int* assigned_slot /*[K][cap] or NULL*/);

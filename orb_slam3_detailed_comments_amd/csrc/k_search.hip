@@ -1725,6 +1725,82 @@ __global__ void __launch_bounds__(256) k_fuse_kf_slots(const MapSkipRec* __restr
     kf_slot[o] = out;
 }
 
+// ---- the matched pairs of a Fuse batch as one list (orbm_fuse_pairs_batch / orbm_fuse_pairs_batch_map) --------------------------------------------
+// Behind k_fuse_candidates, on its dense best_idx[K][M]: the pairs with best_idx >= 0, target by target and inside a target by position - the order the
+// replay visits them in.  As the local-map build compacts (k_map_compact / k_map_scan): a chunk is kPairChunk positions of one target, chunk c of target k is
+// number k * gridDim.x + c, so the order of the numbers is the order of the list; its pairs are counted with wave ballots, the counts are scanned, and the
+// same ballots rank each pair inside its chunk.  No cursor is shared, so the order does not depend on which workgroup runs first.
+//   k_fuse_pairs (chunk_off == nullptr)   chunk_cnt[chunk], nothing else
+//   k_fuse_pair_scan_tiles                a tile is kPairTile chunks, one wave: chunk_off = exclusive scan inside the tile, tile_sum = the tile's pairs
+//   k_fuse_pair_scan_sums                 tile_off = exclusive scan of tile_sum, tile_off[ntiles] = all pairs; one workgroup, a run of tiles per thread
+//   k_fuse_pairs (chunk_off != nullptr)   start[k] = the offset of target k's first chunk, start[K] = all pairs; if they fit in cap, the record of every pair
+
+// pKF->GetMapPoint(feat) of the replay for one pair, by the rule of k_fuse_kf_slots: the slot, -2 for a bad point, -1 for no point
+__device__ __forceinline__ int fuse_pair_kf_slot(const MapSkipRec& R, const int* __restrict__ kf_slots, const uint8_t* __restrict__ state, int feat) {
+    const int slot = kf_slots[(size_t)R.off + (size_t)R.feat0 + (size_t)feat];
+    if (slot < 0) return -1;
+    const uint8_t st = state[slot];
+    if (!(st & kMapPresent)) return -1;
+    return (st & kMapBad) ? -2 : slot;
+}
+
+// grid (ceil(M / kPairChunk), K), kPairChunk threads.  A record is O.fields ints: position, feature, then what the caller asked for (FusePairOut)
+__global__ void __launch_bounds__(kPairChunk) k_fuse_pairs(int M, const int* __restrict__ best_idx, const int* __restrict__ best_dist, int* __restrict__ chunk_cnt,
+                                                           const int* __restrict__ chunk_off, const int* __restrict__ tile_off, int ntiles, int cap,
+                                                           int* __restrict__ start, const MapSkipRec* __restrict__ recs, const int* __restrict__ kf_slots,
+                                                           const uint8_t* __restrict__ state, const int* __restrict__ set_slots, FusePairOut O) {
+    __shared__ int wave_cnt[kPairChunk / 64];
+    const int k = (int)blockIdx.y, i = (int)(blockIdx.x * (unsigned)kPairChunk + threadIdx.x);
+    const size_t o = (size_t)k * (size_t)M + (size_t)i;
+    const int feat = i < M ? best_idx[o] : -1;
+    const bool keep = feat >= 0;
+    const unsigned long long bal = __ballot(keep);
+    const int lane = lane_id(), wave = wave_id();
+    if (lane == 0) wave_cnt[wave] = __popcll(bal);
+    __syncthreads();
+    const int chunk = k * (int)gridDim.x + (int)blockIdx.x;
+    if (!chunk_off) {
+        if (threadIdx.x == 0) { int c = 0; for (int w = 0; w < kPairChunk / 64; w++) c += wave_cnt[w]; chunk_cnt[chunk] = c; }
+        return;
+    }
+    const int at0 = tile_off[chunk / kPairTile] + chunk_off[chunk], total = tile_off[ntiles];
+    if (threadIdx.x == 0) {
+        if (blockIdx.x == 0) start[k] = at0;
+        if (chunk == 0) start[gridDim.y] = total;
+    }
+    if (!keep || total > cap) return;                               // (nothing is truncated: a list that does not fit is not written at all)
+    int at = at0 + __popcll(bal & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; w++) at += wave_cnt[w];
+    if (at >= total) return;                                        // (cannot happen: the offsets are the scan of these counts; it keeps the store inside the list)
+    int* __restrict__ r = O.rec + (size_t)at * (size_t)O.fields;
+    r[0] = i; r[1] = feat;
+    if (O.dist >= 0) r[O.dist] = best_dist[o];
+    if (O.point_slot >= 0) r[O.point_slot] = set_slots[i];
+    if (O.kf_slot >= 0) r[O.kf_slot] = fuse_pair_kf_slot(recs[k], kf_slots, state, feat);
+}
+
+// grid (ceil(n / 256)), 256 threads: four tiles
+__global__ void __launch_bounds__(256) k_fuse_pair_scan_tiles(int n, const int* __restrict__ chunk_cnt, int* __restrict__ chunk_off, int* __restrict__ tile_sum) {
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x), lane = lane_id();
+    const int v = i < n ? chunk_cnt[i] : 0;
+    const int incl = wave_incl_scan(v);
+    if (i < n) chunk_off[i] = incl - v;
+    if (lane == 63 && i - 63 < n) tile_sum[i / kPairTile] = incl;
+}
+
+// one workgroup of 256 threads: thread t sums tiles [t R, (t + 1) R), R = ceil(ntiles / 256) (at most 2^20 + 65535 chunks in a call: R <= 69), the sums are
+// scanned over the workgroup, and each thread writes its run
+__global__ void __launch_bounds__(256) k_fuse_pair_scan_sums(int ntiles, const int* __restrict__ tile_sum, int* __restrict__ tile_off) {
+    __shared__ int scratch[17];
+    const int R = (ntiles + 255) / 256, j0 = (int)threadIdx.x * R, j1 = imin(ntiles, j0 + R);
+    int s = 0;
+    for (int j = j0; j < j1; j++) s += tile_sum[j];
+    int total;
+    int run = block_excl_scan(s, &total, scratch);
+    for (int j = j0; j < j1; j++) { run += tile_sum[j]; tile_off[j] = run - tile_sum[j]; }
+    if (threadIdx.x == 0) tile_off[ntiles] = total;
+}
+
 // orbm_map_edit_keyframes: entry feat[j] of row row[j] becomes slot[j] (the host refuses two edits of one entry, so no two stores meet).
 // grid (ceil(n / 256)), 256 threads
 __global__ void __launch_bounds__(256) k_map_edit_rows(int n, const int* __restrict__ row, const int* __restrict__ feat, const int* __restrict__ slot,

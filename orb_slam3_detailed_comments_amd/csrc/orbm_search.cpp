@@ -2188,13 +2188,91 @@ int fuse_targets_check(const orbx_extractor* h, int K, const OrbmFuseTarget* tar
     return ORBX_OK;
 }
 
+// The compacted form of the Fuse batch's answer (orbm_fuse_pairs_batch / orbm_fuse_pairs_batch_map): the caller's arrays, and where everything lies in the
+// handle's d_si[SI_BEST], in ints: the dense best_idx [and best_dist] of the search, the chunk counts and offsets, the tile sums and offsets
+// (k_search.hip "the matched pairs of a Fuse batch as one list"), and - one behind the other, so that one copy brings both - start[K + 1] and the records
+struct FusePairsWanted { int cap; int* start; int* point; int* feat; int* dist; int* point_slot; int* kf_slot; };
+struct FusePairsLayout {
+    size_t nch = 0, ntiles = 0, dcap = 0, o_cnt = 0, o_off = 0, o_tsum = 0, o_toff = 0, o_start = 0, o_rec = 0, ints = 0;
+    int fields = 0, f_dist = -1, f_pslot = -1, f_kfs = -1;
+    FusePairsLayout() {}
+    FusePairsLayout(const FusePairsWanted& W, int K, int M) {
+        const size_t pairs = (size_t)K * (size_t)M;
+        nch = (size_t)K * (size_t)((M + kPairChunk - 1) / kPairChunk); ntiles = (nch + kPairTile - 1) / kPairTile;
+        dcap = std::min((size_t)W.cap, pairs);                      // (a list longer than cap is not written)
+        fields = 2;
+        if (W.dist) f_dist = fields++;
+        if (W.point_slot) f_pslot = fields++;
+        if (W.kf_slot) f_kfs = fields++;
+        o_cnt = (W.dist ? 2 : 1) * pairs; o_off = o_cnt + nch; o_tsum = o_off + nch; o_toff = o_tsum + ntiles; o_start = o_toff + ntiles + 1;
+        o_rec = o_start + (size_t)K + 1; ints = o_rec + dcap * (size_t)fields;
+    }
+};
+// records [r0, r1) of the list, as they came down, into the caller's arrays
+void fuse_pairs_unpack(const FusePairsWanted& W, const FusePairsLayout& L, const int* rec, size_t r0, size_t r1) {
+    for (size_t r = r0; r < r1; r++, rec += L.fields) {
+        W.point[r] = rec[0]; W.feat[r] = rec[1];
+        if (W.dist) W.dist[r] = rec[L.f_dist];
+        if (W.point_slot) W.point_slot[r] = rec[L.f_pslot];
+        if (W.kf_slot) W.kf_slot[r] = rec[L.f_kfs];
+    }
+}
+// Behind k_fuse_candidates on the same stream: count, scan, scatter, and the download.  `start` comes down first and with it, in the same copy, the first
+// `guess` records - a quarter more than the handle's last such call found, at least 1024: a call whose list is that short (LocalMapping's, and every
+// repeat of a call at a steady scene) waits for the stream once, where a second wait costs more than the few KB that may not be needed; only a longer list
+// pays a second copy, of exactly the records that are missing.
+int fuse_pairs_finish(orbx_extractor* h, int K, int M, const FusePairsWanted& W, const FusePairsLayout& L, const MapSkip* from_map, const MapSkipRec* d_recs,
+                      BatchGrids& grids) {
+    int* d = h->d_si[SI_BEST].p;
+    const size_t pairs = (size_t)K * (size_t)M;
+    const dim3 grid((M + kPairChunk - 1) / kPairChunk, K, 1), blk(kPairChunk, 1, 1), gridt((unsigned)((L.nch + 255) / 256), 1, 1), blkt(256, 1, 1), one(1, 1, 1);
+    const FusePairOut O = {d + L.o_rec, L.fields, L.f_dist, L.f_pslot, L.f_kfs};
+    const int* d_dist = W.dist ? d + pairs : (const int*)nullptr;
+    const int* kf_slots = from_map ? from_map->kf_slots : (const int*)nullptr; const uint8_t* state = from_map ? from_map->state : (const uint8_t*)nullptr;
+    const int* set_slots = from_map ? from_map->set_slots : (const int*)nullptr;
+    ORBX_LAUNCH(k_fuse_pairs, grid, blk, 0, h->s0, M, (const int*)d, d_dist, d + L.o_cnt, (const int*)nullptr, (const int*)nullptr, (int)L.ntiles, W.cap, d + L.o_start,
+                d_recs, kf_slots, state, set_slots, O);
+    ORBX_LAUNCH(k_fuse_pair_scan_tiles, gridt, blkt, 0, h->s0, (int)L.nch, (const int*)(d + L.o_cnt), d + L.o_off, d + L.o_tsum);
+    ORBX_LAUNCH(k_fuse_pair_scan_sums, one, blkt, 0, h->s0, (int)L.ntiles, (const int*)(d + L.o_tsum), d + L.o_toff);
+    ORBX_LAUNCH(k_fuse_pairs, grid, blk, 0, h->s0, M, (const int*)d, d_dist, d + L.o_cnt, (const int*)(d + L.o_off), (const int*)(d + L.o_toff), (int)L.ntiles, W.cap,
+                d + L.o_start, d_recs, kf_slots, state, set_slots, O);
+    const size_t guess = std::min(L.dcap, std::max<size_t>(h->fuse_pairs_last + h->fuse_pairs_last / 4 + 256, 1024)), head = (size_t)K + 1;
+    const bool direct = rt::memory_is_host();
+    const int* res = d + L.o_start;
+    int e = 0;
+    if (!direct) {
+        e = h->h_res.ensure(sizeof(int) * (head + guess * L.fields) + 64);
+        if (!e) e = rt::copy_d2h(h->h_res.p, d + L.o_start, sizeof(int) * (head + guess * L.fields), h->s0);
+        res = (const int*)h->h_res.p;
+    }
+    if (e || rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "fuse pair search failed: %s", rt::last_error());
+    grids.built();
+    memcpy(W.start, res, sizeof(int) * head);
+    const size_t total = (size_t)W.start[K];
+    if (total > (size_t)W.cap) return fail(ORBX_E_CAPACITY, "%zu pairs do not fit in cap = %d", total, W.cap);
+    h->fuse_pairs_last = total;
+    fuse_pairs_unpack(W, L, res + head, 0, std::min(total, guess));
+    if (total > guess) {
+        const int* rest = d + L.o_rec + guess * L.fields;
+        if (!direct) {
+            const size_t bytes = sizeof(int) * (total - guess) * L.fields;
+            if (h->h_res.ensure(bytes + 64) || rt::copy_d2h(h->h_res.p, rest, bytes, h->s0) || rt::stream_sync(h->s0))
+                return fail(ORBX_E_DEVICE, "fuse pair download failed: %s", rt::last_error());
+            rest = (const int*)h->h_res.p;
+        }
+        fuse_pairs_unpack(W, L, rest, guess, total);
+    }
+    return ORBX_OK;
+}
+
 // The Fuse batch behind its checks, K > 0 checked targets: skip = the host's [K][M] bytes or nullptr; from_map: the bytes are written on the device where
-// `skip` would have been uploaded, and kf_slot (may be nullptr) comes back behind the distances
+// `skip` would have been uploaded, and kf_slot (may be nullptr) comes back behind the distances.  want: the pair-list forms - the dense result stays on the
+// device and fuse_pairs_finish takes over behind the search (best_idx, best_dist and kf_slot are not read then)
 int fuse_batch_run(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const orbm_points* points, const uint8_t* skip, MapSkip* from_map, float th, int chi2_gate,
-                   int* best_idx, int* best_dist, int* kf_slot) {
+                   int* best_idx, int* best_dist, int* kf_slot, const FusePairsWanted* want = nullptr) {
     const int M = points->M;
-    if (M == 0) return ORBX_OK;
-    if (!best_idx) return fail(ORBX_E_ARG, "null result array");
+    if (M == 0) { if (want) std::fill(want->start, want->start + K + 1, 0); return ORBX_OK; }
+    if (!want && !best_idx) return fail(ORBX_E_ARG, "null result array");
     if (K > 65535 || (size_t)K * (size_t)M > ((size_t)1 << 28)) return fail(ORBX_E_CAPACITY, "%d targets x %d points: at most 65535 targets and 2^28 pairs per call", K, M);
     rt::set_device(h->device);
     const size_t pairs = (size_t)K * (size_t)M;
@@ -2214,16 +2292,18 @@ int fuse_batch_run(orbx_extractor* h, int K, const OrbmFuseTarget* targets, cons
     const size_t pr = from_map ? pk.add(from_map->recs.data(), sizeof(MapSkipRec) * from_map->recs.size()) : 0;
     const size_t ps = from_map ? pk.room(pairs) : skip ? pk.add(skip, pairs) : 0;
     const bool flags = from_map || skip;
-    const size_t nout = (1 + (best_dist ? 1 : 0) + (kf_slot ? 1 : 0)) * pairs;
+    const FusePairsLayout PL = want ? FusePairsLayout(*want, K, M) : FusePairsLayout();
+    const size_t nout = want ? PL.ints : (1 + (best_dist ? 1 : 0) + (kf_slot ? 1 : 0)) * pairs;
     if (h->d_si[SI_BEST].ensure(nout)) return fail(ORBX_E_DEVICE, "allocation failed (%d targets x %d points)", K, M);
     if (from_map) if (int rc = map_skip_table(h, M, from_map)) return rc;
     if (int e = pk.flush()) return fail(ORBX_E_DEVICE, "%s", upload_error(e));
     grids.launch_builds(h, pk.dev<GridBuildRec>(pb));
     if (from_map) launch_map_skip(h, *from_map, K, M, pk.dev<MapSkipRec>(pr), from_map->kf_slots, pk.out<uint8_t>(ps));
-    int* d_idx = h->d_si[SI_BEST].p; int* d_dist = best_dist ? d_idx + pairs : (int*)nullptr; int* d_kfs = d_idx + (best_dist ? 2 : 1) * pairs;
+    int* d_idx = h->d_si[SI_BEST].p; int* d_dist = (want ? want->dist : best_dist) ? d_idx + pairs : (int*)nullptr; int* d_kfs = d_idx + (best_dist ? 2 : 1) * pairs;
     const dim3 grid((M + 255) / 256, K, 1), blk(256, 1, 1);
     ORBX_LAUNCH(k_fuse_candidates, grid, blk, 0, h->s0, pk.dev<FuseTargetRec>(pt), M, points->pos, points->normal, points->min_d, points->max_d, points->desc,
                 flags ? pk.dev<uint8_t>(ps) : (const uint8_t*)nullptr, th, chi2_gate, TH_LOW, h->debug_stereo_flags, d_idx, d_dist);
+    if (want) return fuse_pairs_finish(h, K, M, *want, PL, from_map, from_map ? pk.dev<MapSkipRec>(pr) : (const MapSkipRec*)nullptr, grids);
     if (kf_slot) ORBX_LAUNCH(k_fuse_kf_slots, grid, blk, 0, h->s0, pk.dev<MapSkipRec>(pr), from_map->kf_slots, M, from_map->state, (const int*)d_idx, d_kfs);
     // one copy into the handle's page-locked landing area (as fetch_sync), then into the caller's one to three arrays
     const int* res = d_idx;
@@ -2238,6 +2318,14 @@ int fuse_batch_run(orbx_extractor* h, int K, const OrbmFuseTarget* targets, cons
     memcpy(best_idx, res, sizeof(int) * pairs);
     if (best_dist) memcpy(best_dist, res + pairs, sizeof(int) * pairs);
     if (kf_slot) memcpy(kf_slot, res + (best_dist ? 2 : 1) * pairs, sizeof(int) * pairs);
+    return ORBX_OK;
+}
+
+// what the pair-list forms refuse of their own arguments
+int fuse_pairs_check(int cap, const int* start, const int* point, const int* feat) {
+    if (cap < 0) return fail(ORBX_E_ARG, "negative cap");
+    if (!start) return fail(ORBX_E_ARG, "null start array");
+    if (cap > 0 && (!point || !feat)) return fail(ORBX_E_ARG, "null point or feat array with cap = %d", cap);
     return ORBX_OK;
 }
 
@@ -2332,6 +2420,17 @@ int orbm_fuse_candidates_batch(orbx_extractor* h, int K, const OrbmFuseTarget* t
     if (K == 0) return ORBX_OK;
     if (int rc = fuse_targets_check(h, K, targets, chi2_gate)) return rc;
     return fuse_batch_run(h, K, targets, points, skip, nullptr, th, chi2_gate, best_idx, best_dist, nullptr);
+}
+
+int orbm_fuse_pairs_batch(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const orbm_points* points, const uint8_t* skip, float th, int chi2_gate, int cap,
+                          int* start, int* point, int* feat, int* dist) {
+    if (!h || !points || K < 0) return fail(ORBX_E_ARG, "null / negative number of targets");
+    if (points->device != h->device) return fail(ORBX_E_ARG, "the map points live on another device than the handle");
+    if (int rc = fuse_pairs_check(cap, start, point, feat)) return rc;
+    if (K == 0) { start[0] = 0; return ORBX_OK; }
+    if (int rc = fuse_targets_check(h, K, targets, chi2_gate)) return rc;
+    const FusePairsWanted W = {cap, start, point, feat, dist, nullptr, nullptr};
+    return fuse_batch_run(h, K, targets, points, skip, nullptr, th, chi2_gate, nullptr, nullptr, nullptr, &W);
 }
 
 int orbm_search_by_projection_sim3_batch(orbx_extractor* h, int K, const OrbmSim3Target* targets, const orbm_points* points, const uint8_t* skip, float th,
@@ -3375,18 +3474,16 @@ int map_built_set_check(const orbm_map* m, int set) {
     if (set < 0 || set >= m->max_sets || !m->built[set]) return fail(ORBX_E_ARG, "set %d has not been built (the map has %d sets)", set, m->max_sets);
     return ORBX_OK;
 }
-}  // namespace
-
-extern "C" {
-
-int orbm_fuse_candidates_batch_map(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const int* rows, const int* feat0, orbm_map* map, int set, float th,
-                                   int chi2_gate, int* best_idx, int* best_dist, int* kf_slot) {
+// (caller holds nothing) both forms of the Fuse batch on a set of the map: want == nullptr the dense one
+int fuse_map_run(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const int* rows, const int* feat0, orbm_map* map, int set, float th, int chi2_gate,
+                 int* best_idx, int* best_dist, int* kf_slot, const FusePairsWanted* want) {
     if (!h || K < 0) return fail(ORBX_E_ARG, "null / negative number of targets");
     if (!map || !rows) return fail(ORBX_E_ARG, "null map or row list");
     if (int rc = map_search_check(h, map)) return rc;
+    if (want) if (int rc = fuse_pairs_check(want->cap, want->start, want->point, want->feat)) return rc;
     std::lock_guard<std::mutex> lk(map->mu);
     if (int rc = map_built_set_check(map, set)) return rc;
-    if (K == 0) return ORBX_OK;
+    if (K == 0) { if (want) want->start[0] = 0; return ORBX_OK; }
     if (int rc = fuse_targets_check(h, K, targets, chi2_gate)) return rc;
     MapSkip S;
     S.map = map; S.set_slots = map->set_rec[set].slots; S.state = map->S.state; S.kf_slots = map->d_kf.p;
@@ -3400,7 +3497,21 @@ int orbm_fuse_candidates_batch_map(orbx_extractor* h, int K, const OrbmFuseTarge
         S.recs[k] = {(long long)row * map->kf_row_cap, n, f0};
         S.longest = std::max(S.longest, n);
     }
-    return fuse_batch_run(h, K, targets, &map->sets[set], nullptr, &S, th, chi2_gate, best_idx, best_dist, kf_slot);
+    return fuse_batch_run(h, K, targets, &map->sets[set], nullptr, &S, th, chi2_gate, best_idx, best_dist, kf_slot, want);
+}
+}  // namespace
+
+extern "C" {
+
+int orbm_fuse_candidates_batch_map(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const int* rows, const int* feat0, orbm_map* map, int set, float th,
+                                   int chi2_gate, int* best_idx, int* best_dist, int* kf_slot) {
+    return fuse_map_run(h, K, targets, rows, feat0, map, set, th, chi2_gate, best_idx, best_dist, kf_slot, nullptr);
+}
+
+int orbm_fuse_pairs_batch_map(orbx_extractor* h, int K, const OrbmFuseTarget* targets, const int* rows, const int* feat0, orbm_map* map, int set, float th,
+                              int chi2_gate, int cap, int* start, int* point, int* feat, int* dist, int* point_slot, int* kf_slot) {
+    const FusePairsWanted W = {cap, start, point, feat, dist, point_slot, kf_slot};
+    return fuse_map_run(h, K, targets, rows, feat0, map, set, th, chi2_gate, nullptr, nullptr, nullptr, &W);
 }
 
 int orbm_search_by_projection_sim3_batch_map(orbx_extractor* h, int K, const OrbmSim3Target* targets, orbm_map* map, int set, const int* found_start,

@@ -134,6 +134,7 @@ struct orbx_extractor {
     orbx::HostBuf<uint8_t> h_packA, h_packB, h_out;      // pinned staging of the window searches (frame, queries, results)
     orbx::HostBuf<uint8_t> h_res;                        // pinned landing area of results that end in caller (pageable) memory: orbx::fetch_sync
     size_t area_pool = 0, area_last_total = 0;
+    size_t fuse_pairs_last = 0;                  // pairs the last orbm_fuse_pairs_batch[_map] found: the next call's guess of what to fetch with `start`
     orbx::DevBuf<int> d_si[8];
     orbx::DevBuf<long long> d_qtprof;
     // per (image, level): why the tree moved its keys into sorted order (0 = never; k_quadtree.hip, orbx_debug_quadtree_sorted); qt_eager = every

@@ -248,6 +248,12 @@ __global__ void k_map_skip_listed(const MapSkipRec* __restrict__ recs, const int
 __global__ void k_map_skip_dups(int M, int K, const int* __restrict__ slots, const unsigned* __restrict__ table, unsigned top, uint8_t* __restrict__ skip);
 __global__ void k_fuse_kf_slots(const MapSkipRec* __restrict__ recs, const int* __restrict__ kf_slots, int M, const uint8_t* __restrict__ state,
                                 const int* __restrict__ best_idx, int* __restrict__ kf_slot);
+// the matched pairs of a Fuse batch as one list in the replay's order: count per chunk, scan (tiles, then their sums), scatter
+__global__ void k_fuse_pairs(int M, const int* __restrict__ best_idx, const int* __restrict__ best_dist, int* __restrict__ chunk_cnt, const int* __restrict__ chunk_off,
+                             const int* __restrict__ tile_off, int ntiles, int cap, int* __restrict__ start, const MapSkipRec* __restrict__ recs,
+                             const int* __restrict__ kf_slots, const uint8_t* __restrict__ state, const int* __restrict__ set_slots, FusePairOut O);
+__global__ void k_fuse_pair_scan_tiles(int n, const int* __restrict__ chunk_cnt, int* __restrict__ chunk_off, int* __restrict__ tile_sum);
+__global__ void k_fuse_pair_scan_sums(int ntiles, const int* __restrict__ tile_sum, int* __restrict__ tile_off);
 __global__ void k_map_edit_rows(int n, const int* __restrict__ row, const int* __restrict__ feat, const int* __restrict__ slot, int* __restrict__ kf_slots,
                                 int row_cap);
 

@@ -125,6 +125,11 @@ struct SetFlagRec { const uint8_t* seen; const int* slots; int M, off; };
 // frame, off = row * kf_row_cap) or the uploaded found lists (Sim3); feat0: the row entry of the target's feature 0 (k_fuse_kf_slots reads off + feat0 + bestIdx)
 struct MapSkipRec { long long off; int n, feat0; };
 constexpr int kSkipTargets = 16;       // targets one thread of k_map_set_table / k_map_skip_dups writes the flag of its position for
+// the compacted pair list of a Fuse batch (k_fuse_pairs): a chunk is kPairChunk positions of one target (one workgroup, one count), a tile kPairTile chunks
+// (one wave of the scan).  The list is records of `fields` ints - {position, feature} and then best_dist, the position's map slot, pKF->GetMapPoint(feature)
+// as a slot, each at the index named here or -1 = not asked for
+constexpr int kPairChunk = 256, kPairTile = 64;
+struct FusePairOut { int* rec; int fields, dist, point_slot, kf_slot; };
 // one map point of orbm_distinctive_descriptors_resident (k_distinctive_resident): its observations are entries [start, start + n) of the call's
 // observation table (n >= 1: points without observations are not launched); store: the descriptor of its slot in the map's store (nullptr: not written)
 struct DistinctiveRec { unsigned long long* store; int start, n; };

@@ -332,6 +332,69 @@ class ORBmatcher:
         return (bi, bd, ks) if want_kf_slot else (bi, bd)
 
     @staticmethod
+    def _fuse_targets(kfs, specs, invLevelSigma2):
+        """the OrbmFuseTarget table of the pair-list calls (and what keeps its arrays alive), as FuseCandidatesBatch fills it"""
+        K = len(kfs)
+        assert len(specs) == K
+        T = (FuseTarget * max(K, 1))()
+        if invLevelSigma2 is None:
+            s2 = [None] * K
+        elif isinstance(invLevelSigma2, (list, tuple)) and len(invLevelSigma2) == K and np.ndim(invLevelSigma2[0]) == 1:
+            s2 = [np.ascontiguousarray(a, np.float32) for a in invLevelSigma2]
+        else:
+            s2 = [np.ascontiguousarray(invLevelSigma2, np.float32)] * K
+        for k in range(K):
+            T[k].kf = kfs[k]._kf; T[k].spec = specs[k][0]; T[k].log_scale_factor = specs[k][1]
+            T[k].inv_level_sigma2 = None if s2[k] is None else s2[k].ctypes.data
+        return T, s2
+
+    @staticmethod
+    def _fuse_pairs(lib, K, Mp, cap, wanted, call):
+        """call(cap, start, pointers) -> rc with a guessed capacity (an eighth of the pairs, at least 1024) unless the caller names one; ORBX_E_CAPACITY with
+        start[K] > cap is answered by ONE more call with cap = start[K].  wanted[j]: array j is asked for (None in its place otherwise).  Returns
+        (start, *arrays) trimmed to start[K]."""
+        start = np.zeros(K + 1, np.int32)
+        guess = min(K * Mp, max(1024, K * Mp // 8)) if cap is None else int(cap)
+        for attempt in range(2):
+            arrays = [np.full(max(guess, 1), -1, np.int32) if w else None for w in wanted]
+            rc = call(guess, start, [None if a is None else a.ctypes.data for a in arrays])
+            if rc != -4 or attempt == 1 or guess < 0 or int(start[K]) <= guess:      # -4 = ORBX_E_CAPACITY (past a limit of the call: start stays zero, no retry)
+                break
+            guess = int(start[K])
+        lib.check(rc)
+        n = int(start[K])
+        return (start,) + tuple(None if a is None else a[:n] for a in arrays)
+
+    @staticmethod
+    def FuseCandidatesPairsBatch(ext, kfs, specs, points, th, invLevelSigma2=None, skip=None, cap=None, want_dist=True):
+        """FuseCandidatesBatch answered with the matched pairs alone (orbm_fuse_pairs_batch): the pairs with best_idx >= 0, ordered by target, then by
+        position.  Returns (start [K + 1], point, feat, dist): target k owns entries start[k] .. start[k + 1] - 1, entry e fuses set position point[e] with
+        feature feat[e] at distance dist[e] (None without want_dist).  cap = None: the wrapper guesses a capacity; either way it calls once more with
+        start[K] if the list is longer."""
+        K, Mp = len(kfs), points.M
+        T, keep = ORBmatcher._fuse_targets(kfs, specs, invLevelSigma2)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        assert sk is None or sk.shape == (K, Mp)
+        L = ext._lib.L
+        return ORBmatcher._fuse_pairs(ext._lib, K, Mp, cap, (True, True, want_dist), lambda c, start, a: L.orbm_fuse_pairs_batch(
+            ext._h, K, T, points._p, None if sk is None else sk.ctypes.data, float(th), int(invLevelSigma2 is not None), c, start.ctypes.data, *a))
+
+    @staticmethod
+    def FuseCandidatesPairsBatchMap(ext, kfs, specs, resident_map, set, rows, th, invLevelSigma2=None, feat0=None, cap=None, want_dist=True, want_slots=True):
+        """FuseCandidatesBatchMap answered with the matched pairs alone (orbm_fuse_pairs_batch_map).  Returns (start, point, feat, dist, point_slot, kf_slot):
+        as FuseCandidatesPairsBatch, with point_slot[e] = the map slot of set position point[e] and kf_slot[e] = pKF->GetMapPoint(feat[e]) as a slot, -2
+        for a bad point, -1 for none (both None without want_slots)."""
+        K, Mp = len(kfs), resident_map.set(set, ext).M
+        assert len(rows) == K and (feat0 is None or len(feat0) == K)
+        T, keep = ORBmatcher._fuse_targets(kfs, specs, invLevelSigma2)
+        r = np.ascontiguousarray(np.asarray(rows, np.int32).reshape(-1), np.int32) if K else np.zeros(1, np.int32)
+        f0 = None if feat0 is None else np.ascontiguousarray(np.asarray(feat0, np.int32).reshape(-1), np.int32)
+        L = ext._lib.L
+        return ORBmatcher._fuse_pairs(ext._lib, K, Mp, cap, (True, True, want_dist, want_slots, want_slots), lambda c, start, a: L.orbm_fuse_pairs_batch_map(
+            ext._h, K, T, r.ctypes.data, None if f0 is None or K == 0 else f0.ctypes.data, resident_map._m, int(set), float(th), int(invLevelSigma2 is not None), c,
+            start.ctypes.data, *a))
+
+    @staticmethod
     def SearchByProjectionSim3BatchMap(ext, kfs, specs, resident_map, set, th, ratio_hamming=1.0, occupied=None, found=None, want_slots=False):
         """SearchByProjectionSim3Batch on set `set` of a ResidentMap (orbm_search_by_projection_sim3_batch_map): a point is skipped for target k iff its
         slot is bad at the moment of the call or listed in found[k] (spAlreadyFound as slots; found = None or K arrays, duplicates / -1 / slots outside the

@@ -231,6 +231,24 @@ M(230, F, "if (t > base && p < (unsigned)M) skip", "if (t >= base && p < (unsign
   note="equivalent: top = base + M, so a stamp t == base gives the position p = top - t = M, and the clause p < M beside it refuses exactly that value")
 # k_stereo_from_depth
 M(235, F, "if (d > 0) {\n                const float xu", "if (d >= 0) {\n                const float xu", ["test_local_points_batch.py", "test_emu_search.py", "test_frame_reference.py"], "RGB-D: depth 0 is a measurement")
+# the compacted pair list of a Fuse batch: k_fuse_pairs, k_fuse_pair_scan_tiles, k_fuse_pair_scan_sums, fuse_pair_kf_slot
+# (`total > cap` is not mutated towards writing: the records of a list longer than cap would lie behind the array.  `at >= total` only keeps a store inside the list.)
+PAIRS = ["test_fuse_pairs.py"]
+M(240, F, "const bool keep = feat >= 0;", "const bool keep = feat > 0;", PAIRS, "fuse pairs: a pair with feature 0 is left out")
+M(241, F, "int at = at0 + __popcll(bal & ((1ull << lane) - 1ull));", "int at = at0 + __popcll(bal & ((2ull << lane) - 1ull));", PAIRS, "fuse pairs: the rank inside a wave counts the lane itself")
+M(242, F, "for (int w = 0; w < wave; w++) at += wave_cnt[w];\n    if (at >= total)", "for (int w = 0; w <= wave; w++) at += wave_cnt[w];\n    if (at >= total)", PAIRS,
+  "fuse pairs: the rank inside a chunk counts the lane's own wave")
+M(243, F, "if (!keep || total > cap) return;", "if (!keep || total >= cap) return;", PAIRS, "fuse pairs: a list of exactly cap entries is not written")
+M(244, F, "if (i < n) chunk_off[i] = incl - v;", "if (i < n) chunk_off[i] = incl;", PAIRS, "fuse pair scan: chunk offsets inclusive")
+M(245, F, "tile_off[j] = run - tile_sum[j]; }", "tile_off[j] = run; }", PAIRS, "fuse pair scan: tile offsets inclusive")
+M(246, F, "if (slot < 0) return -1;\n    const uint8_t st = state[slot];\n    if (!(st & kMapPresent)) return -1;", "if (slot < 0) return -2;\n    const uint8_t st = state[slot];\n    if (!(st & kMapPresent)) return -1;",
+  PAIRS, "fuse pair kf slot: an empty row entry reads as a bad point")
+M(247, F, "if (!(st & kMapPresent)) return -1;\n    return (st & kMapBad)", "if (!(st & kMapPresent)) return -2;\n    return (st & kMapBad)", PAIRS, "fuse pair kf slot: a slot that holds nothing reads as a bad point")
+M(248, F, "if (!(st & kMapPresent)) return -1;\n    return (st & kMapBad)", "if (!(st & kMapPresent)) return slot;\n    return (st & kMapBad)", PAIRS, "fuse pair kf slot: a slot that holds nothing is fused with")
+M(249, F, "return (st & kMapBad) ? -2 : slot;", "return slot;", PAIRS, "fuse pair kf slot: a bad point in the key frame is fused with")
+M(250, F, "return (st & kMapBad) ? -2 : slot;", "return (st & kMapBad) ? -1 : slot;", PAIRS, "fuse pair kf slot: a bad point in the key frame reads as an empty entry")
+M(251, F, "if (blockIdx.x == 0) start[k] = at0;\n        if (chunk == 0) start[gridDim.y] = total;", "if (blockIdx.x == 0) start[k] = at0;\n        if (chunk == 0) start[gridDim.y] = total - 1;", PAIRS,
+  "fuse pairs: start[K] one short of the list")
 
 # ---- k_vocab.hip ---------------------------------------------------------------------------------------------------------------------------------------------
 F = "k_vocab.hip"
