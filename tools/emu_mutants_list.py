@@ -489,3 +489,224 @@ M(909, F, "h->sigma2[i] = h->scale[i] * h->scale[i];", "h->sigma2[i] = h->scale[
 M(910, F, "h->scale[i] = (float)(h->scale[i - 1] * h->scaleFactor);", "h->scale[i] = (float)pow((double)h->scaleFactor, (double)i);", TABLES, "scale table: the power, not the running product")
 M(911, F, "h->inv_scale[i] = 1.0f / h->scale[i];", "h->inv_scale[i] = (float)pow(1.0 / (double)h->scaleFactor, (double)i);", TABLES, "inverse scale table: the power of the inverse factor, not the inverse of the scale")
 M(912, F, "h->inv_sigma2[i] = 1.0f / h->sigma2[i];", "h->inv_sigma2[i] = h->inv_scale[i] * h->inv_scale[i];", TABLES, "inverse sigma2 table: the square of the inverse scale")
+
+# ---- orbm_search.cpp: the host replays of the single-frame ORBmatcher entries (ids from 1000) -------------------------------------------------------------------
+# The kernels hand back ordered candidate lists; the reference's accept loop is replayed over them on the host.  Host code runs inside the test process like an emulated
+# kernel, so the safety rule is the same: no sizes, Packer / Bump / ensure offsets, loop bounds or launch geometry; no guard in front of an index or a write
+# (`b.idx >= 0`, `best[k] < 0`, `ltr != -1`, `rtl != -1`, `m12[i] < 0`, `matches12[i1] >= 0` of the prev update, `nleft2 > K2->N`, `N >= 65535`, `it.cnt2 > 0xFFFF`,
+# `l < kMaxLevels`, `lvl != -1 && lvl >= 0 && lvl < F->right.nlevels`) removed - the level gates in front of scale_factors[] are only moved inwards; no argument check.
+# `rot < 0` is not removed either (a negative bin would index in front of the histogram): it is moved to `rot < -1`, whose bins stay at 0.
+F = "orbm_search.cpp"
+HG, HR = "test_host_replay_gates.py", "test_host_rotation_gates.py"
+H_MAPPTS = [HG, "test_branch_edges_search.py", "test_emu_search.py", "test_local_points.py", "test_search_gates.py"]
+H_FRAME = [HG, "test_emu_search.py", "test_lastframe_batch.py", "test_batch_table_forms.py"]
+H_SCAN = [HG, "test_emu_search.py", "test_branch_edges_search.py", "test_lastframe_batch.py", "test_branch_edges_windows.py"]
+H_ROT = [HR, "test_branch_edges_rotation.py", "test_emu_search.py", "test_lastframe_batch.py"]
+H_TRI = [HG, "test_branch_edges_triangulation.py", "test_emu_search.py", "test_keyframe_search_gates.py"]
+H_BOW = [HG, "test_emu_search.py", "test_branch_edges_rotation.py", "test_keyframe_search_gates.py", "test_bow_frames_batch.py"]
+H_BOWF = [HG, "test_rig_bow_batch.py"]
+H_INIT = [HG, "test_branch_edges_search.py", "test_emu_search.py"]
+H_PROJ = [HG, "test_emu_search.py", "test_branch_edges_windows.py", "test_lastframe_batch.py", "test_sim3_projection_batch.py"]
+H_FISH = [HG, "test_emu_search.py", "test_rig_tracking_batch.py", "test_local_points_rig.py", "test_search_gates.py"]
+H_RES = [HR, "test_keyframe_search_gates.py", "test_resident_keyframes.py", "test_branch_edges_rotation.py"]
+H_FRUSTUM = ["test_local_points.py", "test_local_points_rig.py", "test_search_gates.py"]
+# scan_best / scan_best2
+M(1000, F, "if (dist < b.dist) { b.dist = dist; b.idx = idx; }", "if (dist <= b.dist) { b.dist = dist; b.idx = idx; }", H_SCAN, "scan_best: the last of equal distances wins")
+M(1001, F, "if (occ && occ[idx + off]) continue;\n        if (dist < b.dist)", "if (dist < b.dist)", H_SCAN, "scan_best: the occupancy skip removed")
+M(1002, F, "if (occ && occ[idx + off]) continue;\n        if (dist < b.dist)", "if (occ && occ[idx]) continue;\n        if (dist < b.dist)", H_FISH, "scan_best: camera 2's occupancy read at camera 1's slots")
+M(1003, F, "if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2", "if (dist <= bestDist) { bestDist2 = bestDist; bestDist = dist; bestLevel2", H_MAPPTS, "scan_best2: the last of equal distances wins")
+M(1004, F, "else if (dist < bestDist2) { bestLevel2 = level;", "else if (dist <= bestDist2) { bestLevel2 = level;", H_MAPPTS, "scan_best2: a candidate as far as the second best gives it its level")
+M(1005, F, "bestLevel2 = bestLevel; bestLevel = level; bestIdx = idx; }", "bestLevel = level; bestIdx = idx; }", H_MAPPTS, "scan_best2: a displaced best does not hand its level to the second")
+M(1006, F, "{ bestDist2 = bestDist; bestDist = dist; bestLevel2", "{ bestDist = dist; bestLevel2", H_MAPPTS, "scan_best2: a displaced best does not hand its distance to the second")
+M(1007, F, "else if (dist < bestDist2) { bestLevel2 = level; bestDist2 = dist; }", "else if (dist < bestDist2) { bestDist2 = dist; }", H_MAPPTS, "scan_best2: the second best's level not recorded")
+M(1008, F, "if (occ && occ[idx + off]) continue;\n        const int dist = c.dist(q, k), level", "const int dist = c.dist(q, k), level", H_MAPPTS, "scan_best2: the occupancy skip removed")
+M(1009, F, "if (occ && occ[idx + off]) continue;\n        const int dist = c.dist(q, k), level", "if (occ && occ[idx]) continue;\n        const int dist = c.dist(q, k), level", H_FISH,
+  "scan_best2: camera 2's occupancy read at camera 1's slots")
+# replay_mappoints
+M(1010, F, "if (b.bestDist <= TH_HIGH) {\n            if (b.bestLevel == b.bestLevel2 && b.bestDist > nnratio * b.bestDist2) continue;",
+  "if (b.bestDist < TH_HIGH) {\n            if (b.bestLevel == b.bestLevel2 && b.bestDist > nnratio * b.bestDist2) continue;", H_MAPPTS, "replay_mappoints: a best distance of TH_HIGH refused")
+M(1011, F, "b.bestDist > nnratio * b.bestDist2) continue;\n            if (b.bestLevel !=", "b.bestDist >= nnratio * b.bestDist2) continue;\n            if (b.bestLevel !=", H_MAPPTS,
+  "replay_mappoints: bestDist == nnratio * bestDist2 refused")
+M(1012, F, "if (b.bestLevel == b.bestLevel2 && b.bestDist > nnratio * b.bestDist2) continue;\n            if (b.bestLevel !=",
+  "if (b.bestDist > nnratio * b.bestDist2) continue;\n            if (b.bestLevel !=", H_MAPPTS, "replay_mappoints: the ratio test also between different levels")
+M(1013, F, "|| b.bestDist <= nnratio * b.bestDist2) {\n                assigned[b.bestIdx] = i;\n                occ[b.bestIdx] = has_obs",
+  "|| b.bestDist < nnratio * b.bestDist2) {\n                assigned[b.bestIdx] = i;\n                occ[b.bestIdx] = has_obs", H_MAPPTS, "replay_mappoints: the second `if` strict (bestDist == nnratio * bestDist2 on equal levels refused there)")
+M(1014, F, "occ[b.bestIdx] = has_obs ? has_obs[i] : 1;", "occ[b.bestIdx] = 1;", H_MAPPTS, "replay_mappoints: a point without observations occupies its keypoint")
+# orbm_search_by_projection_mappoints: the skip tests and the window
+M(1015, F, "if (!P->in_view[i]) continue;\n        if (far_points", "if (far_points", H_MAPPTS, "SearchByProjection(MapPoints): the mbTrackInView skip removed")
+M(1016, F, "P->track_depth[i] > th_far) continue;\n        if (P->is_bad[i]) continue;\n        const int lvl", "P->track_depth[i] >= th_far) continue;\n        if (P->is_bad[i]) continue;\n        const int lvl",
+  H_MAPPTS, "SearchByProjection(MapPoints): depth == thFarPoints is far")
+M(1017, F, "if (P->is_bad[i]) continue;\n        const int lvl", "const int lvl", H_MAPPTS, "SearchByProjection(MapPoints): the isBad skip removed")
+M(1018, F, "q.min_level = lvl - 1; q.max_level = lvl; q.active = 1; q.gate = 1;", "q.min_level = lvl; q.max_level = lvl; q.active = 1; q.gate = 1;", H_MAPPTS,
+  "SearchByProjection(MapPoints): the level below the predicted one refused")
+M(1019, F, "q.min_level = lvl - 1; q.max_level = lvl; q.active = 1; q.gate = 1;", "q.min_level = lvl - 1; q.max_level = lvl + 1; q.active = 1; q.gate = 1;", H_MAPPTS,
+  "SearchByProjection(MapPoints): the level above the predicted one accepted")
+# RotHist
+M(1020, F, "if (rot < 0.0) rot += 360.0f;", "if (rot <= 0.0) rot += 360.0f;", H_ROT, "rot_bin: rot == 0 goes to 360 (bin 12)")
+M(1021, F, "if (rot < 0.0) rot += 360.0f;", "if (rot < -1.0) rot += 360.0f;", H_ROT, "rot_bin: a rot just below 0 is not wrapped (bin 0 for 12)")
+M(1022, F, "if (bin == HISTO_LENGTH) bin = 0;", "if (bin == HISTO_LENGTH - 1) bin = 0;", H_ROT, "rot_bin: bin 29 wraps to 0",
+  "unreachable, like the line itself: the factor is the reference's 1 / HISTO_LENGTH = 1 / 30 (not HISTO_LENGTH / 360), rot lies in [0, 360], so round(rot / 30) is at most 12 - "
+  "neither 29 nor 30 is ever a bin (tests/test_host_rotation_gates.py pins the largest bin, 12, on the oracle)")
+M(1023, F, "int bin = (int)round(rot * factor);", "int bin = (int)(rot * factor);", H_ROT, "rot_bin: the bin truncated instead of rounded")
+M(1024, F, "if (s > max1) { max3 = max2;", "if (s >= max1) { max3 = max2;", H_ROT, "three_maxima: the later of two equal strongest bins is first")
+M(1025, F, "else if (s > max2) { max3 = max2;", "else if (s >= max2) { max3 = max2;", H_ROT, "three_maxima: the later of two equal second bins is second")
+M(1026, F, "else if (s > max3) { max3 = s; ind3 = i; }", "else if (s >= max3) { max3 = s; ind3 = i; }", H_ROT, "three_maxima: the later of two equal third bins is third")
+M(1027, F, "if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }", "if (max2 <= 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }", H_ROT, "three_maxima: a second bin of exactly 0.1 max1 dropped")
+M(1028, F, "else if (max3 < 0.1f * (float)max1) { ind3 = -1; }", "else if (max3 <= 0.1f * (float)max1) { ind3 = -1; }", H_ROT, "three_maxima: a third bin of exactly 0.1 max1 dropped")
+M(1029, F, "if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }", "if (max2 < 0.1f * (float)max1) { ind2 = -1; }", H_ROT, "three_maxima: the third bin survives a weak second")
+M(1030, F, "if (i == ind1 || i == ind2 || i == ind3) continue;", "if (i == ind1 || i == ind2) continue;", H_ROT, "prune: the third bin is not spared")
+M(1031, F, "if (i == ind1 || i == ind2 || i == ind3) continue;", "if (i == ind1 || i == ind3) continue;", H_ROT, "prune: the second bin is not spared")
+M(1032, F, "if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }", "if (s > max1) { max2 = max1; max1 = s; ind2 = ind1; ind1 = i; }", H_ROT,
+  "three_maxima: a new strongest bin does not push the second down to third")
+M(1033, F, "else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }", "else if (s > max2) { max2 = s; ind2 = i; }", H_ROT, "three_maxima: a new second bin does not push the old one down to third")
+# orbm_search_by_projection_frame
+M(1040, F, "if (u < Cur->min_x || u > Cur->max_x) continue;", "if (u <= Cur->min_x || u > Cur->max_x) continue;", H_FRAME, "SearchByProjection(Frame): u == mnMinX outside")
+M(1041, F, "if (u < Cur->min_x || u > Cur->max_x) continue;", "if (u < Cur->min_x || u >= Cur->max_x) continue;", H_FRAME, "SearchByProjection(Frame): u == mnMaxX outside")
+M(1042, F, "if (v < Cur->min_y || v > Cur->max_y) continue;", "if (v <= Cur->min_y || v > Cur->max_y) continue;", H_FRAME, "SearchByProjection(Frame): v == mnMinY outside")
+M(1043, F, "if (v < Cur->min_y || v > Cur->max_y) continue;", "if (v < Cur->min_y || v >= Cur->max_y) continue;", H_FRAME, "SearchByProjection(Frame): v == mnMaxY outside")
+M(1044, F, "if (oct < 0 || oct >= Cur->nlevels) continue;", "if (oct <= 0 || oct >= Cur->nlevels) continue;", H_FRAME, "SearchByProjection(Frame): octave 0 refused")
+M(1045, F, "if (oct < 0 || oct >= Cur->nlevels) continue;", "if (oct < 0 || oct >= Cur->nlevels - 1) continue;", H_FRAME, "SearchByProjection(Frame): the last octave refused")
+M(1046, F, "if (forward) { q.min_level = oct; q.max_level = -1; }            // :2018", "if (forward) { q.min_level = oct - 1; q.max_level = -1; }            // :2018", H_FRAME,
+  "SearchByProjection(Frame), forward: the octave below accepted")
+M(1047, F, "\n        else if (backward) { q.min_level = 0; q.max_level = oct; }", "\n        else if (backward) { q.min_level = 0; q.max_level = oct + 1; }", H_FRAME,
+  "SearchByProjection(Frame), backward: the octave above accepted")
+M(1048, F, "\n        else if (backward) { q.min_level = 0; q.max_level = oct; }", "\n        else if (backward) { q.min_level = 1; q.max_level = oct; }", H_FRAME,
+  "SearchByProjection(Frame), backward: octave 0 refused")
+M(1049, F, "\n        else { q.min_level = oct - 1; q.max_level = oct + 1; }", "\n        else { q.min_level = oct; q.max_level = oct + 1; }", H_FRAME, "SearchByProjection(Frame), default: the octave below refused")
+M(1050, F, "\n        else { q.min_level = oct - 1; q.max_level = oct + 1; }", "\n        else { q.min_level = oct - 1; q.max_level = oct; }", H_FRAME, "SearchByProjection(Frame), default: the octave above refused")
+M(1051, F, "if (!Last->valid[i]) continue;\n        const float u = Last->proj_u[i], v = Last->proj_v[i];\n        if (u < Cur->min_x", "const float u = Last->proj_u[i], v = Last->proj_v[i];\n        if (u < Cur->min_x",
+  H_FRAME, "SearchByProjection(Frame): the skip of points without map point / outliers / behind the camera removed")
+M(1052, F, "if (b.dist <= TH_HIGH) {\n            assigned[b.idx] = i;\n            occ[b.idx] = Last->has_obs", "if (b.dist < TH_HIGH) {\n            assigned[b.idx] = i;\n            occ[b.idx] = Last->has_obs",
+  H_FRAME, "SearchByProjection(Frame): a best distance of TH_HIGH refused")
+M(1053, F, "occ[b.idx] = Last->has_obs ? Last->has_obs[i] : 1;", "occ[b.idx] = 1;", H_FRAME, "SearchByProjection(Frame): a point without observations occupies its keypoint")
+_FRAME_PRUNE = "hist.add(Last->angle[i], Cur->keys_un[b.idx].angle, b.idx);\n        }\n    }\n    if (check_ori) hist.prune([&](int idx) { "
+M(1054, F, _FRAME_PRUNE + "assigned[idx] = -2; nmatches--; });", _FRAME_PRUNE + "assigned[idx] = -1; nmatches--; });", H_FRAME + [HR], "SearchByProjection(Frame): the rotation check resets to -1")
+M(1055, F, _FRAME_PRUNE + "assigned[idx] = -2; nmatches--; });", _FRAME_PRUNE + "assigned[idx] = -2; });", H_FRAME + [HR], "SearchByProjection(Frame): the rotation check does not reduce the count")
+M(1056, F, "if (forward) { q.min_level = oct; q.max_level = -1; }            // :2018", "if (forward && !backward) { q.min_level = oct; q.max_level = -1; }            // :2018", H_FRAME,
+  "SearchByProjection(Frame): backward wins when both flags are set")
+# search_for_triangulation_impl
+M(1060, F, "if (K1->has_map_point && K1->has_map_point[idx1]) continue;\n                const bool stereo1", "if (K1->has_map_point && !K1->has_map_point[idx1]) continue;\n                const bool stereo1",
+  H_TRI, "SearchForTriangulation: the features WITH a map point are searched")
+M(1061, F, "K1->u_right[idx1] >= 0;\n                if (only_stereo", "K1->u_right[idx1] > 0;\n                if (only_stereo", H_TRI, "SearchForTriangulation: a right coordinate of exactly 0 is monocular")
+M(1062, F, "if (only_stereo && !stereo1) continue;", "if (!stereo1) continue;", H_TRI, "SearchForTriangulation: monocular features always skipped")
+M(1063, F, "if (only_stereo && !stereo1) continue;", "if (only_stereo && stereo1) continue;", H_TRI, "SearchForTriangulation: bOnlyStereo skips the stereo features")
+M(1064, F, "P.only_stereo = only_stereo; P.coarse = coarse; P.th_low = TH_LOW;\n", "P.only_stereo = only_stereo; P.coarse = coarse; P.th_low = TH_LOW - 1;\n", H_TRI, "SearchForTriangulation: TH_LOW - 1 handed to the kernel")
+# orbm_search_by_bow_batch
+_BOWSKIP = "     // !pMP || pMP->isBad()\n                BowItem it; it.idx1 = base1[p]"
+M(1070, F, "!K1->has_map_point[idx1]) continue;" + _BOWSKIP, "K1->has_map_point[idx1]) continue;" + _BOWSKIP, H_BOW, "SearchByBoW: the features WITHOUT a map point are searched")
+M(1071, F, "if (taken[idx2] || d < 0) continue;", "if (d < 0) continue;", H_BOW, "SearchByBoW: a target taken by an earlier feature is a candidate again")
+M(1072, F, "if (d < bestDist1) { bestDist2 = bestDist1; bestDist1 = d; bestIdx2 = idx2; }", "if (d <= bestDist1) { bestDist2 = bestDist1; bestDist1 = d; bestIdx2 = idx2; }", H_BOW,
+  "SearchByBoW: the last of equal distances wins")
+M(1073, F, "{ bestDist2 = bestDist1; bestDist1 = d; bestIdx2 = idx2; }", "{ bestDist1 = d; bestIdx2 = idx2; }", H_BOW, "SearchByBoW: a displaced best does not become the second best")
+M(1074, F, "(bestDist1 <= TH_LOW) : (bestDist1 < TH_LOW);", "(bestDist1 < TH_LOW) : (bestDist1 < TH_LOW);", H_BOW, "SearchByBoW(KeyFrame, Frame): a best distance of TH_LOW refused")
+M(1075, F, "(bestDist1 <= TH_LOW) : (bestDist1 < TH_LOW);", "(bestDist1 <= TH_LOW) : (bestDist1 <= TH_LOW);", H_BOW, "SearchByBoW(KeyFrame, KeyFrame): a best distance of TH_LOW accepted")
+M(1076, F, "if (pass && static_cast<float>(bestDist1) < nnratio * static_cast<float>(bestDist2)) {", "if (pass && static_cast<float>(bestDist1) <= nnratio * static_cast<float>(bestDist2)) {", H_BOW,
+  "SearchByBoW: bestDist1 == nnratio * bestDist2 accepted")
+M(1077, F, "taken[bestIdx2] = 1;", "taken[bestIdx2] = 0;", H_BOW, "SearchByBoW: a matched target is not marked as taken")
+M(1078, F, "if (taken[idx2] || d < 0) continue;", "if (taken[idx2] || d <= 0) continue;", H_BOW, "SearchByBoW: a target at distance 0 skipped like an ineligible one")
+M(1079, F, "else if (d < bestDist2) bestDist2 = d;\n            }\n            const bool pass", "else if (d <= bestDist2) bestDist2 = d;\n            }\n            const bool pass", H_BOW,
+  "SearchByBoW: second best inclusive", "equivalent: with d == bestDist2 the assignment writes the value that is there")
+# orbm_search_by_bow_fisheye
+M(1080, F, "if (assigned2[idx2] >= 0) continue;", "if (assigned2[idx2] > 0) continue;", H_BOWF, "SearchByBoW, rig frame: a frame feature taken by key-frame feature 0 is a candidate again")
+M(1081, F, "if (idx2 < nleft2) {", "if (idx2 <= nleft2) {", H_BOWF, "SearchByBoW, rig frame: the first feature of camera 2 counts as camera 1's")
+M(1082, F, "if (d < bestDist1) { bestDist2 = bestDist1; bestDist1 = d; bestIdxF = idx2; }", "if (d <= bestDist1) { bestDist2 = bestDist1; bestDist1 = d; bestIdxF = idx2; }", H_BOWF,
+  "SearchByBoW, rig frame: the last of equal camera-1 distances wins")
+M(1083, F, "if (d < bestDist1R) {", "if (d <= bestDist1R) {", H_BOWF, "SearchByBoW, rig frame: the last of equal camera-2 distances wins")
+M(1084, F, "if (bestDist1 <= TH_LOW) {\n                if (static_cast<float>(bestDist1) < nnratio", "if (bestDist1 < TH_LOW) {\n                if (static_cast<float>(bestDist1) < nnratio", H_BOWF,
+  "SearchByBoW, rig frame: a camera-1 best of TH_LOW refused")
+M(1085, F, "< nnratio * static_cast<float>(bestDist2)) {\n                    assigned2[bestIdxF]", "<= nnratio * static_cast<float>(bestDist2)) {\n                    assigned2[bestIdxF]", H_BOWF,
+  "SearchByBoW, rig frame: bestDist1 == nnratio * bestDist2 accepted")
+M(1086, F, "if (bestDist1R <= TH_LOW) {", "if (bestDist1R < TH_LOW) {", H_BOWF, "SearchByBoW, rig frame: a camera-2 best of TH_LOW refused")
+M(1087, F, "if (bestDist1R <= TH_LOW) {", "if (bestDist1R <= TH_LOW && static_cast<float>(bestDist1R) < nnratio * static_cast<float>(bestDist2R)) {", H_BOWF,
+  "SearchByBoW, rig frame: the camera-2 match takes a ratio test")
+M(1088, F, "if (bestDist1 <= TH_LOW) {\n                if (static_cast<float>(bestDist1) < nnratio", "if (bestDist1 <= TH_LOW || bestDist1R <= TH_LOW) {\n                if (static_cast<float>(bestDist1) < nnratio", H_BOWF,
+  "SearchByBoW, rig frame: the camera-2 match is taken without a camera-1 best under TH_LOW")
+M(1089, F, "else if (d < bestDist2) bestDist2 = d;\n                } else {", "else if (d < bestDist2) {}\n                } else {", H_BOWF, "SearchByBoW, rig frame: camera 1's second best only from displaced bests")
+# orbm_search_for_initialization
+M(1090, F, "if (level1 > 0) continue;", "if (level1 > 1) continue;", H_INIT, "SearchForInitialization: level-1 keypoints searched too")
+M(1091, F, "if (matched_dist[i2] <= dist) continue;", "if (matched_dist[i2] < dist) continue;", H_INIT, "SearchForInitialization: a keypoint matched at the same distance is a candidate")
+M(1092, F, "if (matched_dist[i2] <= dist) continue;", "", H_INIT, "SearchForInitialization: the matched-distance skip removed")
+M(1093, F, "if (dist < bestDist) { bestDist2 = bestDist; bestDist = dist; bestIdx2 = i2; }", "if (dist <= bestDist) { bestDist2 = bestDist; bestDist = dist; bestIdx2 = i2; }", H_INIT,
+  "SearchForInitialization: the last of equal distances wins")
+M(1094, F, "if (bestDist <= TH_LOW) {\n            if (bestDist < (float)bestDist2 * nnratio) {", "if (bestDist < TH_LOW) {\n            if (bestDist < (float)bestDist2 * nnratio) {", H_INIT,
+  "SearchForInitialization: a best distance of TH_LOW refused")
+M(1095, F, "if (bestDist < (float)bestDist2 * nnratio) {", "if (bestDist <= (float)bestDist2 * nnratio) {", H_INIT, "SearchForInitialization: bestDist == bestDist2 * nnratio accepted")
+M(1096, F, "{ matches12[matches21[bestIdx2]] = -1; nmatches--; }", "{ matches12[matches21[bestIdx2]] = -1; }", H_INIT, "SearchForInitialization: a displaced match stays in the count")
+M(1097, F, "{ matches12[matches21[bestIdx2]] = -1; nmatches--; }", "{ nmatches--; }", H_INIT, "SearchForInitialization: a displaced match stays in vnMatches12")
+M(1098, F, "if (matches21[bestIdx2] >= 0) {", "if (matches21[bestIdx2] > 0) {", H_INIT, "SearchForInitialization: an earlier match by keypoint 0 is not displaced")
+M(1099, F, "matches21[bestIdx2] = i1; matched_dist[bestIdx2] = bestDist;", "matches21[bestIdx2] = i1;", H_INIT, "SearchForInitialization: the matched distance not recorded")
+M(1100, F, "if (matches12[idx1] >= 0) { matches12[idx1] = -1; nmatches--; }", "{ matches12[idx1] = -1; nmatches--; }", H_INIT + [HR],
+  "SearchForInitialization: the rotation check counts a displaced match down again")
+M(1101, F, "{ bestDist2 = bestDist; bestDist = dist; bestIdx2 = i2; }", "{ bestDist = dist; bestIdx2 = i2; }", H_INIT, "SearchForInitialization: a displaced best does not become the second best")
+# projected_candidates and the four searches on it
+M(1110, F, "if (!P->valid[i]) continue;\n        const int lvl = P->pred_level[i];", "const int lvl = P->pred_level[i];", H_PROJ, "projected_candidates: invalid points searched")
+M(1111, F, "if (lvl < 0 || lvl >= F->nlevels) continue;\n        q.x = P->u[i];", "if (lvl <= 0 || lvl >= F->nlevels) continue;\n        q.x = P->u[i];", H_PROJ, "projected_candidates: predicted level 0 refused")
+M(1112, F, "if (lvl < 0 || lvl >= F->nlevels) continue;\n        q.x = P->u[i];", "if (lvl < 0 || lvl >= F->nlevels - 1) continue;\n        q.x = P->u[i];", H_PROJ, "projected_candidates: the last predicted level refused")
+M(1113, F, "q.min_level = lvl - 1; q.max_level = lvl + hi;", "q.min_level = lvl; q.max_level = lvl + hi;", H_PROJ, "projected_candidates: the level below the predicted one refused")
+M(1114, F, "q.min_level = lvl - 1; q.max_level = lvl + hi;", "q.min_level = lvl - 1; q.max_level = lvl + hi + 1;", H_PROJ, "projected_candidates: one level more above the predicted one")
+M(1120, F, "b.dist <= TH_LOW * ratio_hamming) {", "b.dist < TH_LOW * ratio_hamming) {", H_PROJ, "SearchByProjection(Sim3): a best distance of TH_LOW * ratioHamming refused")
+M(1121, F, "{ assigned[b.idx] = i; occ[b.idx] = 1; nmatches++; }", "{ assigned[b.idx] = i; occ[b.idx] = 0; nmatches++; }", H_PROJ, "SearchByProjection(Sim3): a matched keypoint stays free")
+M(1122, F, "projected_candidates(h, KF, P, th, 0, 0, nullptr, &qs, &c); if (rc) return rc;\n    const int N = KF->N;", "projected_candidates(h, KF, P, th, 1, 0, nullptr, &qs, &c); if (rc) return rc;\n    const int N = KF->N;",
+  H_PROJ, "SearchByProjection(Sim3): the level above the predicted one accepted")
+M(1125, F, "b.dist <= orb_dist) {", "b.dist < orb_dist) {", H_PROJ, "SearchByProjection(KeyFrame): a best distance of ORBdist refused")
+M(1126, F, "assigned[b.idx] = i; occ[b.idx] = 1; nmatches++;\n", "assigned[b.idx] = i; occ[b.idx] = 0; nmatches++;\n", H_PROJ, "SearchByProjection(KeyFrame): a matched keypoint stays free")
+_KF_PRUNE = "hist.add(P->angle[i], Cur->keys_un[b.idx].angle, b.idx);\n        }\n    }\n    if (check_ori) hist.prune([&](int idx) { "
+M(1127, F, _KF_PRUNE + "assigned[idx] = -2; nmatches--; });", _KF_PRUNE + "assigned[idx] = -1; nmatches--; });", H_PROJ + [HR], "SearchByProjection(KeyFrame): the rotation check resets to -1")
+M(1128, F, "projected_candidates(h, Cur, P, th, 1, 0, nullptr, &qs, &c);", "projected_candidates(h, Cur, P, th, 0, 0, nullptr, &qs, &c);", H_PROJ, "SearchByProjection(KeyFrame): the level above the predicted one refused")
+M(1130, F, "b.dist > TH_LOW ? -1 : b.idx;", "b.dist >= TH_LOW ? -1 : b.idx;", H_PROJ + ["test_projection_gates.py"], "Fuse candidates: a best distance of TH_LOW refused")
+M(1135, F, "if (b.dist <= TH_HIGH) out[i] = b.idx;", "if (b.dist < TH_HIGH) out[i] = b.idx;", H_PROJ, "SearchBySim3: a best distance of TH_HIGH refused")
+M(1136, F, "if (idx2 >= 0 && vnMatch2[idx2] == i1) {", "if (idx2 >= 0) {", H_PROJ, "SearchBySim3: the mutual-agreement test removed")
+# the fisheye replays
+M(1140, F, "if (!inl && !inr) continue;", "if (!inl) continue;", H_FISH, "SearchByProjection(MapPoints), rig: a point only camera 2 sees is skipped")
+M(1141, F, "P->track_depth[i] > th_far) continue;\n        if (P->is_bad[i]) continue;\n        alive[i] = 1;", "P->track_depth[i] >= th_far) continue;\n        if (P->is_bad[i]) continue;\n        alive[i] = 1;",
+  H_FISH, "SearchByProjection(MapPoints), rig: depth == thFarPoints is far")
+M(1142, F, "if (P->is_bad[i]) continue;\n        alive[i] = 1;", "alive[i] = 1;", H_FISH, "SearchByProjection(MapPoints), rig: the isBad skip removed")
+M(1143, F, "const float r = PR->view_cos_r[i] > 0.998 ? 2.5f : 4.0f;", "const float r = PR->view_cos_r[i] > 0.99 ? 2.5f : 4.0f;", H_FISH, "SearchByProjection(MapPoints), rig: camera 2's RadiusByViewingCos at 0.99")
+M(1144, F, "float r = P->view_cos[i] > 0.998 ? 2.5f : 4.0f;\n                if (bFactor) r *= th;\n                AreaQuery& q = ql[i];",
+  "float r = P->view_cos[i] > 0.99 ? 2.5f : 4.0f;\n                if (bFactor) r *= th;\n                AreaQuery& q = ql[i];", H_FISH, "SearchByProjection(MapPoints), rig: camera 1's RadiusByViewingCos at 0.99")
+M(1145, F, "b.bestDist > nnratio * b.bestDist2) skip_right = true;", "b.bestDist > nnratio * b.bestDist2) skip_right = false;", H_FISH,
+  "SearchByProjection(MapPoints), rig: camera 2 is searched after camera 1's ratio test failed")
+M(1146, F, "if (b.bestDist <= TH_HIGH) {\n                if (b.bestLevel == b.bestLevel2 && b.bestDist > nnratio * b.bestDist2) skip_right",
+  "if (b.bestDist < TH_HIGH) {\n                if (b.bestLevel == b.bestLevel2 && b.bestDist > nnratio * b.bestDist2) skip_right", H_FISH, "SearchByProjection(MapPoints), rig: a camera-1 best of TH_HIGH refused")
+M(1147, F, "b.bestDist > nnratio * b.bestDist2) skip_right = true;", "b.bestDist >= nnratio * b.bestDist2) skip_right = true;", H_FISH,
+  "SearchByProjection(MapPoints), rig: camera 1's bestDist == nnratio * bestDist2 refused")
+M(1148, F, "occ[ltr + NL] = obs; nmatches++; }", "occ[ltr + NL] = obs; }", H_FISH, "SearchByProjection(MapPoints), rig: the lapping twin of a camera-1 match is not counted")
+M(1149, F, "if (b.bestDist <= TH_HIGH) {\n                if (b.bestLevel == b.bestLevel2 && b.bestDist > nnratio * b.bestDist2) continue;\n                const int rtl",
+  "if (b.bestDist < TH_HIGH) {\n                if (b.bestLevel == b.bestLevel2 && b.bestDist > nnratio * b.bestDist2) continue;\n                const int rtl", H_FISH,
+  "SearchByProjection(MapPoints), rig: a camera-2 best of TH_HIGH refused")
+M(1150, F, "b.bestDist > nnratio * b.bestDist2) continue;\n                const int rtl", "b.bestDist >= nnratio * b.bestDist2) continue;\n                const int rtl", H_FISH,
+  "SearchByProjection(MapPoints), rig: camera 2's bestDist == nnratio * bestDist2 refused")
+M(1151, F, "if (b.bestLevel == b.bestLevel2 && b.bestDist > nnratio * b.bestDist2) continue;\n                const int rtl", "if (b.bestDist > nnratio * b.bestDist2) continue;\n                const int rtl", H_FISH,
+  "SearchByProjection(MapPoints), rig: camera 2's ratio test also between different levels")
+M(1152, F, "occ[b.bestIdx] = obs;\n                    const int ltr", "occ[b.bestIdx] = 1;\n                    const int ltr", H_FISH, "SearchByProjection(MapPoints), rig: a point without observations occupies its camera-1 keypoint")
+M(1153, F, "occ[rtl] = obs; nmatches++; }", "occ[rtl] = obs; }", H_FISH, "SearchByProjection(MapPoints), rig: the lapping twin of a camera-2 match is not counted")
+M(1154, F, "scan_best2(cr, i, occ.data(), NL);", "scan_best2(cr, i, occ.data(), 0);", H_FISH, "SearchByProjection(MapPoints), rig: camera 2's occupancy read without the Nleft offset")
+M(1155, F, "|| b.bestDist <= nnratio * b.bestDist2) {\n                    assigned[b.bestIdx] = i; occ[b.bestIdx] = obs;", "|| b.bestDist < nnratio * b.bestDist2) {\n                    assigned[b.bestIdx] = i; occ[b.bestIdx] = obs;",
+  H_FISH, "SearchByProjection(MapPoints), rig: camera 1's second `if` strict")
+M(1160, F, "if (u < Cur->left.min_x || u > Cur->left.max_x) continue;", "if (u <= Cur->left.min_x || u > Cur->left.max_x) continue;", H_FISH, "SearchByProjection(Frame), rig: u == mnMinX outside")
+M(1161, F, "if (u < Cur->left.min_x || u > Cur->left.max_x) continue;", "if (u < Cur->left.min_x || u >= Cur->left.max_x) continue;", H_FISH, "SearchByProjection(Frame), rig: u == mnMaxX outside")
+M(1162, F, "if (v < Cur->left.min_y || v > Cur->left.max_y) continue;", "if (v <= Cur->left.min_y || v > Cur->left.max_y) continue;", H_FISH, "SearchByProjection(Frame), rig: v == mnMinY outside")
+M(1163, F, "if (v < Cur->left.min_y || v > Cur->left.max_y) continue;", "if (v < Cur->left.min_y || v >= Cur->left.max_y) continue;", H_FISH, "SearchByProjection(Frame), rig: v == mnMaxY outside")
+M(1164, F, "if (bl.dist <= TH_HIGH) {", "if (bl.dist < TH_HIGH) {", H_FISH, "SearchByProjection(Frame), rig: a camera-1 best of TH_HIGH refused")
+M(1165, F, "if (br.dist <= TH_HIGH) {", "if (br.dist < TH_HIGH) {", H_FISH, "SearchByProjection(Frame), rig: a camera-2 best of TH_HIGH refused")
+M(1166, F, "scan_best(cr, i, occ.data(), NL);", "scan_best(cr, i, occ.data(), 0);", H_FISH, "SearchByProjection(Frame), rig: camera 2's occupancy read without the Nleft offset")
+M(1167, F, "if (!ql[i].active || cl.count[i] == 0) continue;                   // an empty left", "if (!ql[i].active) continue;                   // an empty left", H_FISH,
+  "SearchByProjection(Frame), rig: camera 2 is searched after an empty camera-1 window")
+M(1168, F, "\n            if (forward) { q.min_level = oct; q.max_level = -1; }", "\n            if (forward) { q.min_level = oct - 1; q.max_level = -1; }", H_FISH, "SearchByProjection(Frame), rig, forward: the octave below accepted")
+M(1169, F, "\n            else if (backward) { q.min_level = 0; q.max_level = oct; }", "\n            else if (backward) { q.min_level = 0; q.max_level = oct + 1; }", H_FISH,
+  "SearchByProjection(Frame), rig, backward: the octave above accepted")
+M(1170, F, "\n            else { q.min_level = oct - 1; q.max_level = oct + 1; }", "\n            else { q.min_level = oct; q.max_level = oct + 1; }", H_FISH, "SearchByProjection(Frame), rig, default: the octave below refused")
+M(1171, F, "br.idx + NL);\n        }\n    }\n    if (check_ori) hist.prune([&](int idx) { assigned[idx] = -2;", "br.idx + NL);\n        }\n    }\n    if (check_ori) hist.prune([&](int idx) { assigned[idx] = -1;",
+  H_FISH + [HR], "SearchByProjection(Frame), rig: the rotation check resets to -1")
+M(1172, F, "const uint8_t obs = Last->has_obs ? Last->has_obs[i] : 1;\n        const Best bl", "const uint8_t obs = 1;\n        const Best bl", H_FISH,
+  "SearchByProjection(Frame), rig: a point without observations occupies its keypoints")
+M(1173, F, "\n            else { q.min_level = oct - 1; q.max_level = oct + 1; }", "\n            else { q.min_level = oct - 1; q.max_level = oct; }", H_FISH, "SearchByProjection(Frame), rig, default: the octave above refused")
+# prune_by_rotation, fill_frustum_params, right_camera_params
+M(1180, F, "hist.add(K1->angle[i], K2->angle[m12[i]], i);", "hist.add(K2->angle[m12[i]], K1->angle[i], i);", H_RES, "prune_by_rotation: the angle difference taken the other way round")
+M(1181, F, "m12[idx1] = -1; nmatches--; });\n    return nmatches;", "m12[idx1] = -1; });\n    return nmatches;", H_RES, "prune_by_rotation: the rotation check does not reduce the count")
+M(1185, F, "Fp->kb8 = V->camera_type == 1;", "Fp->kb8 = V->camera_type != 1;", H_FRUSTUM, "fill_frustum_params: the camera models swapped")
+M(1186, F, "R.camera_type = V->camera2_type;", "R.camera_type = V->left.camera_type;", [HG] + H_FRUSTUM[1:], "right_camera_params: camera 2 takes camera 1's model",
+  "no reference answer where it differs: both cameras of a Frame with Nleft != -1 are KannalaBrandt8 in the reference (the two-camera constructor, src/Frame.cc:1432, is called where Tracking holds an mpCamera2, and that is "
+  "only ever a `new KannalaBrandt8`, src/Tracking.cc:1132, beside a fisheye first camera), every rig of the suite and of the reference drivers (oracle/ref_frame_driver.cpp) is such a pair, and with equal models the mutant "
+  "computes the same; a pinhole camera beside a fisheye one would have nothing to be compared with")
+M(1187, F, "Fp->rig_mode = 1;", "Fp->rig_mode = 0;", [HG] + H_FRUSTUM[1:], "right_camera_params: camera 2 judged in the single-camera mode")
