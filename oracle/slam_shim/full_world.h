@@ -8,7 +8,9 @@
 #define ORBX_REAL_MAPPOINT
 #define ORBX_REAL_KEYFRAME
 #define MAP_H
+#ifndef ORBX_REFERENCE_KFDB    // (_ref/libkfdb_ref.so: the reference's own include/KeyFrameDatabase.h and src/KeyFrameDatabase.cc take the stand-in's place)
 #define KEYFRAMEDATABASE_H
+#endif
 #include <algorithm>
 #include <climits>
 #include <fstream>
@@ -29,6 +31,8 @@ public:
     long unsigned int GetId() { return 0; }
     long unsigned int GetInitKFid() { return 0; }
     bool isImuInitialized() { return false; }
+    bool mbBad = false;
+    bool IsBad() { return mbBad; }
     void EraseMapPoint(MapPoint*) {}
     void EraseKeyFrame(KeyFrame*) {}
 #ifdef ORBX_LOCALMAPPING_WORLD     // (localmapping_world.h: what LocalMapping.cc asks of the map, declared only)
@@ -44,6 +48,7 @@ public:
 #endif
 };
 class Frame;
+#ifndef ORBX_REFERENCE_KFDB
 class KeyFrameDatabase {
 public:
     void erase(KeyFrame*) {}
@@ -53,6 +58,7 @@ public:
     void DetectNBestCandidates(KeyFrame* pKF, std::vector<KeyFrame*>& vpLoopCand, std::vector<KeyFrame*>& vpMergeCand, int nNumCandidates);
 #endif
 };
+#endif
 // names used inside the never-instantiated serialize() templates of KeyFrame.h / MapPoint.h
 template <class Archive, class T> void serializeMatrix(Archive&, T&, const unsigned int) {}
 template <class Archive, class T> void serializeSophusSE3(Archive&, T&, const unsigned int) {}

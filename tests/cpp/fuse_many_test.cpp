@@ -93,6 +93,7 @@ struct MockKeyFrame {
     std::vector<cv::KeyPoint> mvKeysUn, mvKeys, mvKeysRight; cv::Mat mDescriptors; std::vector<float> mvuRight;
     MockCamera cam; MockCamera* mpCamera = &cam; MockCamera* mpCamera2 = nullptr;
     float mnMinX = 0, mnMinY = 0, mnMaxX = 640, mnMaxY = 480, mfGridElementWidthInv = 0.1f, mfGridElementHeightInv = 0.1f, mbf = 40.0f, mfLogScaleFactor = 0;
+    float fx = 0, fy = 0, cx = 0, cy = 0;                           // (read by the Sim3 projection searches of tests/cpp/facade_gates_test.cpp)
     std::vector<float> mvScaleFactors, mvLevelSigma2, mvInvLevelSigma2;
     MockSE3 pose; std::vector<MockMapPoint*> points;
     MockSE3 GetPose() { return pose; }
@@ -193,6 +194,7 @@ void build(World& W, unsigned seed, int idBase) {
         std::unique_ptr<MockKeyFrame> kf(new MockKeyFrame());
         kf->world = &W; kf->mnId = (long unsigned int)(idBase + k);
         kf->cam = MockCamera{{fx, fy, cx, cy}};
+        kf->fx = fx; kf->fy = fy; kf->cx = cx; kf->cy = cy;
         kf->pose = MockSE3(rot_xyz(uni(-0.02f, 0.02f), uni(-0.02f, 0.02f), uni(-0.02f, 0.02f)), V3(uni(-0.1f, 0.1f), uni(-0.1f, 0.1f), uni(-0.1f, 0.1f)));
         kf->mfGridElementWidthInv = 64.0f / (kf->mnMaxX - kf->mnMinX); kf->mfGridElementHeightInv = 48.0f / (kf->mnMaxY - kf->mnMinY);
         kf->mfLogScaleFactor = std::log(1.2f);
@@ -270,6 +272,7 @@ std::string dump(World& W, const std::vector<int>& counts) {
 
 }  // namespace
 
+#ifndef FUSE_MANY_TEST_NO_MAIN       // (tests/cpp/facade_gates_test.cpp includes this file for the mock world)
 int main(int argc, char** argv) {
     const bool sim3 = argc > 1 && !strcmp(argv[1], "sim3");
     const float th = sim3 ? 4.0f : 3.0f;
@@ -311,3 +314,4 @@ int main(int argc, char** argv) {
     if (A.replaces < 30 || (int)changed.size() < 5 || fused < 200) { printf("the world does not test the replay order\n"); return 1; }
     return 0;
 }
+#endif

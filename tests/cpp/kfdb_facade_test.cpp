@@ -230,6 +230,7 @@ static void ThreadedSection(const Voc& voc, int nwords, std::mt19937& g) {
     if (orbv_db_size(db.Handle()) != N) { printf("THREADS the writer's key frames are not all gone\n"); g_fail++; }
 }
 
+#ifndef KFDB_FACADE_TEST_NO_MAIN       // (tests/cpp/kfdb_gates_test.cpp includes this file for the mock world and the restatement)
 int main(int argc, char** argv) {
     if (argc < 3) return 2;
     g_ref = ref_voc_load_text(argv[1]);
@@ -293,3 +294,4 @@ int main(int argc, char** argv) {
     orbv_destroy(voc.v);
     return g_fail ? 1 : 0;
 }
+#endif

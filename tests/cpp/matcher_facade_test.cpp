@@ -84,7 +84,8 @@ int main(int argc, char** argv) {
     exL(imL, cv::Mat(), kl2, dl2, lap2); exR(imR, cv::Mat(), kr2, dr2, lap2);
     RF.Nleft = (int)kl2.size(); RF.Nright = (int)kr2.size();
     ORB_SLAM3::ComputeStereoFishEyeMatches(RF, &exL, &exR);
-    int nfish = 0, fish_bad = RF.mnCloseMPs != 0 || (int)RF.mvDepth.size() != RF.Nleft || (int)RF.mvRightToLeftMatch.size() != RF.Nright;
+    int nfish = 0, fish_bad = RF.mnCloseMPs != 0 || (int)RF.mvDepth.size() != RF.Nleft || (int)RF.mvRightToLeftMatch.size() != RF.Nright || (int)RF.mvuRight.size() != RF.Nleft;
+    for (float u : RF.mvuRight) fish_bad |= u != -1.0f;                       // mvuRight = vector<float>(Nleft, -1) (src/Frame.cc:1533)
     for (int i = 0; i < RF.Nleft && !fish_bad; i++) {
         const int j = RF.mvLeftToRightMatch[i];
         if (j < 0) { fish_bad |= RF.mvDepth[i] != -1.0f; continue; }

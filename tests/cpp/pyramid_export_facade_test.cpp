@@ -63,6 +63,22 @@ int main(int argc, char** argv) {
         }
         prev_mats = ex.mvImagePyramid; prev_bytes = got;
     }
+    // SetExportPyramid(false): the call still extracts, and mvImagePyramid keeps the views it held (nothing is exported, nothing is asked for)
+    {
+        ex.SetExportPyramid(false);
+        cv::Mat im(h, w, CV_8UC1, ims[0].data());
+        std::vector<cv::KeyPoint> k2; cv::Mat d2;
+        ex(im, cv::Mat(), k2, d2, lap);
+        if (k2.empty() || d2.rows != (int)k2.size()) { fprintf(stderr, "no features without the export\n"); bad++; }
+        for (int l = 0; l < nl; l++) if (ex.mvImagePyramid[l].data != prev_mats[l].data) { fprintf(stderr, "level %d changed with the export switched off\n", l); bad++; }
+        ex.SetExportPyramid(true);
+        ex(im, cv::Mat(), k2, d2, lap);
+        const uint8_t* base = nullptr; std::vector<size_t> off(nl); std::vector<int> step(nl), lw(nl), lh(nl);
+        if (orbx_pyramid_exported(ex.Handle(), 0, &base, off.data(), step.data(), lw.data(), lh.data()) != ORBX_OK) { fprintf(stderr, "exported: %s\n", orbx_last_error()); return 4; }
+        for (int l = 0; l < nl; l++) if (ex.mvImagePyramid[l].data != base + off[l] + (size_t)E * step[l] + E) { fprintf(stderr, "level %d is no view of the export slot after switching it on again\n", l); bad++; }
+        // an empty image: -1, as the reference (src/ORBextractor.cc:1089-1090)
+        if (ex(cv::Mat(), cv::Mat(), k2, d2, lap) != -1) { fprintf(stderr, "an empty image did not return -1\n"); bad++; }
+    }
     printf("%s: %d calls, %d mismatches\n", bad ? "FAIL" : "ok", calls, bad);
     return bad ? 1 : 0;
 }

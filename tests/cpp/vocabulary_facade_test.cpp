@@ -31,12 +31,27 @@ int main(int argc, char** argv) {
         }
         for (int levelsup = 0; levelsup <= 4; levelsup += 2) {
             DBoW2::BowVector bv1, bv2; DBoW2::FeatureVector fv1, fv2;
+            bv1[0xFFFFF0u] = 1.0; bv2[0xFFFFF0u] = 1.0; fv1[0xFFFFF0u].push_back(1); fv2[0xFFFFF0u].push_back(1);      // transform clears what the vectors held (TemplatedVocabulary.h:1132-1133)
             ref.transform(feats, bv1, fv1, levelsup);
             voc.transform(feats, bv2, fv2, levelsup);
             if (!(static_cast<const std::map<DBoW2::WordId, DBoW2::WordValue>&>(bv1) == bv2)) { fprintf(stderr, "BowVector differs (round %d, levelsup %d)\n", round, levelsup); return 1; }
             if (!(static_cast<const std::map<DBoW2::NodeId, std::vector<unsigned int> >&>(fv1) == fv2)) { fprintf(stderr, "FeatureVector differs (round %d, levelsup %d)\n", round, levelsup); return 1; }
             if (m > 50 && bv1.size() < 10) { fprintf(stderr, "suspiciously small BowVector\n"); return 1; }
         }
+    }
+    // a second load replaces the device vocabulary: after the same transform as before it, nothing more is allocated than there was
+    {
+        std::vector<cv::Mat> feats(n);
+        for (int i = 0; i < n; i++) { feats[i].create(1, 32, CV_8U); for (int b = 0; b < 32; b++) { s = s * 1664525u + 1013904223u; feats[i].data[b] = (unsigned char)(s >> 24); } }
+        DBoW2::BowVector bv1, bv2; DBoW2::FeatureVector fv1, fv2;
+        long long before[4], after[4];
+        voc.transform(feats, bv1, fv1, 4);
+        orbx_debug_live_resources(before);
+        if (!voc.loadFromTextFile(argv[1]) || voc.size() != ref.size()) { fprintf(stderr, "the second loadFromTextFile failed\n"); return 1; }
+        voc.transform(feats, bv2, fv2, 4);
+        orbx_debug_live_resources(after);
+        if (!(static_cast<const std::map<DBoW2::WordId, DBoW2::WordValue>&>(bv1) == bv2) || bv1.empty()) { fprintf(stderr, "BowVector differs after the second load\n"); return 1; }
+        if (after[0] != before[0]) { fprintf(stderr, "a second load left %lld device allocations behind\n", after[0] - before[0]); return 1; }
     }
     orbx_destroy(h);
     printf("ok\n");

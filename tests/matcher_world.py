@@ -514,12 +514,204 @@ def build_and_run_kb8(drv, seed):
     return out
 
 
+def build_and_run_gates(drv, seed):
+    """Hand-built worlds for the decisions the facade takes itself (tests/test_matcher_gates.py holds the expected value of every array written here, case by case):
+    a few key points on a lattice, one map point per case placed so that it projects onto its key point, descriptors at chosen Hamming distances.  Eight key
+    points per frame: the ones under test first, unrelated ones behind them."""
+    rng = np.random.default_rng(1000 + seed)
+    out = {}
+    L = drv.L
+    cam = drv.camera()
+    I3 = np.eye(3, dtype=np.float32)
+    base = rng.integers(0, 256, (64, 32), dtype=np.uint8)                      # descriptor b: the pattern of case b; near(b, k): k bits of it flipped
+
+    def near(b, k):
+        d = base[b].copy()
+        for bit in range(k):
+            d[bit >> 3] ^= np.uint8(1 << (bit & 7))
+        return d
+
+    def world_point(u, v, z, R=I3, t=np.zeros(3)):
+        """the world point that the camera (R, t) sees at pixel (u, v) and depth z"""
+        Xc = np.array([(u - CX) / FX * z, (v - CY) / FY * z, z])
+        return (R.T.astype(np.float64) @ (Xc - t)).astype(np.float32)
+
+    def mappoint(X, level, desc, centre=np.zeros(3), bad=0, n_obs=1, far=1.0):
+        """a point whose PredictScale from `centre` is `level`: mfMaxDistance = dist * 1.2^(level - 0.5); far < 1 pulls the whole range below the distance"""
+        d = float(np.linalg.norm(X - centre)); maxd = d * SCALE ** (level - 0.5) * far
+        return drv.mappoint(X, (X - centre) / d, maxd / SCALE ** (NLEVELS - 1), maxd, desc, bad=bad, n_obs=n_obs)
+
+    def keys_of(spots, octaves):
+        """len(spots) key points under test + unrelated ones in the bottom row of the image, up to eight"""
+        k = np.zeros(8, KP)
+        for i in range(8):
+            k["x"][i], k["y"][i] = spots[i] if i < len(spots) else (40.0 + 90.0 * i, 440.0)
+            k["octave"][i] = octaves[i] if i < len(octaves) else 0
+        k["size"] = 31.0 * SCALE ** k["octave"]; k["response"] = 50.0; k["class_id"] = -1
+        return k
+
+    def descs(cases):
+        return np.stack([cases[i] if i < len(cases) else base[40 + i] for i in range(8)])
+
+    def ids8(ids):
+        return np.array(list(ids) + [-1] * (8 - len(ids)), np.int32)
+
+    def project(X, R, t):
+        Xc = R.astype(np.float64) @ X.astype(np.float64) + t
+        return float(FX * Xc[0] / Xc[2] + CX), float(FY * Xc[1] / Xc[2] + CY)
+
+    # ---- SearchByProjection(CurrentFrame, LastFrame): `towards` / `away` at and beside z == mb, and under bMono ----
+    # the last frame stands at the origin, the current one at (0, 0, -tz): zLastOfCurCentre = -tz exactly (identity rotations).  mb = 0.5.  The last frame's key point has
+    # octave 2; the current frame's key point under the projection has octave 1 (accepted by the default window [1, 3], refused by `towards`: [2, ..)) or octave 3
+    # (accepted by the default window, refused by `away`: [0, 2])
+    half = np.float32(0.5)
+    for name, tz, mono, octave in (("towards_at_mb", -half, 0, 1), ("towards_above_mb", np.nextafter(-half, np.float32(-1)), 0, 1), ("away_at_mb", half, 0, 3),
+                                   ("away_above_mb", np.nextafter(half, np.float32(1)), 0, 3), ("towards_mono", np.float32(-1.0), 1, 1), ("away_mono", np.float32(1.0), 1, 3)):
+        X = world_point(300.0, 200.0, 4.0)
+        p = mappoint(X, 2, near(0, 0))
+        fl = drv.frame(False, keys_of([(300.0, 200.0)], [2]), descs([near(0, 3)]), None, I3, np.zeros(3, np.float32), cam, mb=0.5)
+        drv.set_map_points(False, fl, ids8([p]))
+        t = np.array([0, 0, tz], np.float32)
+        fc = drv.frame(False, keys_of([project(X, I3, t)], [octave]), descs([near(0, 5)]), None, I3, t, cam, mb=0.5)
+        drv.set_map_points(False, fc, ids8([]))
+        n = L.mw_search_by_projection_frame(drv.w, fc, fl, C.c_float(7.0), mono, C.c_float(0.9), 0)
+        got = drv.get_map_points(False, fc, 8)
+        out["gate_lastframe_" + name] = np.concatenate([[n], np.where(got >= 0, got - np.int32(p), -1)])           # per key point: 0 = the point, -1 = nothing
+
+    # ---- SearchByProjection(CurrentFrame, LastFrame) on a rig: camera 2's pixel is GetRelativePoseTrl() * x3Dc through Sophus' SE3 action, (p + w uv) + q x uv ----
+    # Two points (fp32) whose camera-2 x differs in the last place from what the Sim3 action's sum, p + (w uv + q x uv), gives; camera 2's key point stands exactly th = 7
+    # pixels (level 0) to the left of the larger of the two values: inside the window (|dx| < r) for the smaller one only.  Both frames stand at the origin
+    trl2 = (rot(0.0, 0.02, 0.0), np.array([-0.11, 0.0, 0.0], np.float32))
+    camr = drv.camera()
+    for name, Xr, kx, vr in (("inside", [-1.1589839458465576, -0.17403489351272583, 4.550220489501953], 248.3038330078125, 235.63571166992188),      # SE3: 255.30380, the other sum: 255.30383
+                             ("outside", [1.0493049621582031, -0.1697162687778473, 4.439051628112793], 461.6703186035156, 235.4788055419922)):       # SE3: 468.67032, the other sum: 468.67029
+        Xr = np.array(Xr, np.float32)
+        pr2 = mappoint(Xr, 1, near(15, 0))
+        fl = drv.frame(False, keys_of([project(Xr, I3, np.zeros(3))], [0]), np.concatenate([descs([near(15, 3)]), descs([])]), None, I3, np.zeros(3, np.float32), cam, camr, keys_right=keys_of([], []), trl=trl2)
+        drv.set_map_points(False, fl, np.concatenate([ids8([pr2]), ids8([])]))
+        # (camera 1's window must not be empty, or camera 2 is not searched at all, :2040: an unrelated key point stands at camera 1's projection)
+        fc = drv.frame(False, keys_of([project(Xr, I3, np.zeros(3))], [0]), np.concatenate([descs([base[33]]), descs([near(15, 2)])]), None, I3, np.zeros(3, np.float32), cam, camr, keys_right=keys_of([(kx, vr)], [0]), trl=trl2)
+        drv.set_map_points(False, fc, np.full(16, -1, np.int32))
+        n = L.mw_search_by_projection_frame(drv.w, fc, fl, C.c_float(7.0), 0, C.c_float(0.9), 0)
+        got = drv.get_map_points(False, fc, 16)
+        out["gate_lastframe_rig_camera2_window_edge_" + name] = np.concatenate([[n], np.where(got >= 0, got - np.int32(pr2), -1)])
+
+    # ---- SearchByProjection(CurrentFrame, KeyFrame, sAlreadyFound): the distance range ----
+    # point 0 lies inside [0.8 mfMinDistance, 1.2 mfMaxDistance], point 1 beyond 1.2 mfMaxDistance (predicted level 0 there, and a level-0 key point with its descriptor waits)
+    Xs = [world_point(200.0, 150.0, 4.0), world_point(500.0, 150.0, 4.0)]
+    p0 = mappoint(Xs[0], 1, near(1, 0)); p1 = mappoint(Xs[1], 0, near(2, 0), far=0.5)
+    kf = drv.frame(True, keys_of([(200.0, 150.0), (500.0, 150.0)], [1, 0]), descs([near(1, 2), near(2, 2)]), None, I3, np.zeros(3, np.float32), cam)
+    drv.set_map_points(True, kf, ids8([p0, p1]))
+    fr = drv.frame(False, keys_of([(200.0, 150.0), (500.0, 150.0)], [1, 0]), descs([near(1, 4), near(2, 4)]), None, I3, np.zeros(3, np.float32), cam)
+    drv.set_map_points(False, fr, ids8([]))
+    n = L.mw_search_by_projection_keyframe(drv.w, fr, kf, None, 0, C.c_float(10.0), 100, C.c_float(0.9), 0)
+    got = drv.get_map_points(False, fr, 8)
+    out["gate_keyframe_distance_range"] = np.concatenate([[n], np.where(got >= 0, got - np.int32(p0), -1)])
+
+    # ---- SearchByProjection(KeyFrame, Sim3, ..): a point that vpMatched holds already takes no part; the pose is [R | t / s] ----
+    # Scw = (s = 2, R = I, t = (1, 0, 0)): the camera stands at t / s = (0.5, 0, 0) from the origin.  Key point 0 holds q0 on entry; q0 projects onto key point 1, whose
+    # descriptor is q0's: it must stay free.  q1 projects onto key point 2 and is matched.  (With t not divided by s, q1 would fall 54 pixels beside its key point.)
+    ts = np.array([0.5, 0.0, 0.0]); centre = -ts
+    q0 = mappoint(world_point(300.0, 250.0, 4.0, I3, ts), 1, near(3, 0), centre=centre); q1 = mappoint(world_point(450.0, 250.0, 4.0, I3, ts), 1, near(4, 0), centre=centre)
+    for with_kfs in (0, 1):
+        ks = drv.frame(True, keys_of([(100.0, 100.0), (300.0, 250.0), (450.0, 250.0)], [1, 1, 1]), descs([near(5, 0), near(3, 2), near(4, 2)]), None, I3, np.zeros(3, np.float32), cam)
+        matched = ids8([q0]); mkf = np.full(8, -1, np.int32); pts = np.array([q0, q1], np.int32); pkf = np.array([ks, ks], np.int32)
+        n = L.mw_search_by_projection_sim3(drv.w, ks, C.c_float(2.0), _p(I3), _p((ts * 2.0).astype(np.float32)), _p(pts), 2, _p(pkf), with_kfs, _p(matched), _p(mkf), 3, C.c_float(1.0))
+        out["gate_sim3_taken_and_rigid_part_%d" % with_kfs] = np.concatenate([[n], np.where(matched >= 0, matched - np.int32(q0), -1), np.where(mkf >= 0, mkf - np.int32(ks), -1)])
+
+    # ---- the two Sim3 overloads project differently: GeometricCamera::project against fx * (X / Z) + cx written out ----
+    # a Kannala-Brandt key frame: the first overload projects with the camera model (key point 0 stands there), the second with the pinhole arithmetic of pKF->fx, ..
+    # (key point 1 stands there, ten pixels further out); each must take its own
+    P8 = np.array([FX * 0.62, FY * 0.62, CX, CY, 0.0035, 0.0007, -0.0020, 0.0002], np.float32)
+    L.mw_add_camera_kb8.restype = C.c_int
+    ck = L.mw_add_camera_kb8(drv.w, _p(P8))
+    Xk = np.array([2.0, 0.5, 4.0], np.float32)
+    uk, vk = kb8_project(P8.astype(np.float64), Xk[None].astype(np.float64)); up, vp = float(P8[0]) * 2.0 / 4.0 + CX, float(P8[1]) * 0.5 / 4.0 + CY
+    qk = mappoint(Xk, 1, near(6, 0))
+    for with_kfs in (0, 1):
+        kk = drv.frame(True, keys_of([(float(uk[0]), float(vk[0])), (up, vp)], [1, 1]), descs([near(6, 2), near(6, 2)]), None, I3, np.zeros(3, np.float32), ck)
+        matched = ids8([]); mkf = np.full(8, -1, np.int32); pts = np.array([qk], np.int32); pkf = np.array([kk], np.int32)
+        n = L.mw_search_by_projection_sim3(drv.w, kk, C.c_float(1.0), _p(I3), _p(np.zeros(3, np.float32)), _p(pts), 1, _p(pkf), with_kfs, _p(matched), _p(mkf), 3, C.c_float(1.0))
+        out["gate_sim3_projection_form_%d" % with_kfs] = np.concatenate([[n], np.where(matched >= 0, matched - np.int32(qk), -1)])
+
+    # ... and on a pinhole key frame the two forms differ in the last place: fx * X / Z + cx against fx * (X * (1 / Z)) + cx.  Two points (fp32, y = 0) for which exactly
+    # one of the forms gives u = 752 = mnMaxX, outside the image (IsInImage: u < mnMaxX), and the other the float below it; the key point waits 6.5 pixels inside (the last half cell
+    # of the key frame's grid holds no key point: KeyFrame::PosInGrid rounds), th = 6 reaches it on level 1
+    edge = [np.array([3.4779205322265625, 0.0, 3.9354944229125977], np.float32),      # divided: 752 (out), multiplied by 1 / Z: 751.99994 (in)
+            np.array([3.736060857772827, 0.0, 4.227597236633301], np.float32)]        # divided: 751.99994 (in), multiplied: 752 (out)
+    ke = drv.frame(True, keys_of([(745.5, CY)], [1]), descs([near(14, 2)]), None, I3, np.zeros(3, np.float32), cam)
+    for which, Xe in enumerate(edge):
+        qe = mappoint(Xe, 1, near(14, 0))
+        for with_kfs in (0, 1):
+            matched = ids8([]); mkf = np.full(8, -1, np.int32); pts = np.array([qe], np.int32); pkf = np.array([ke], np.int32)
+            n = L.mw_search_by_projection_sim3(drv.w, ke, C.c_float(1.0), _p(I3), _p(np.zeros(3, np.float32)), _p(pts), 1, _p(pkf), with_kfs, _p(matched), _p(mkf), 6, C.c_float(1.0))
+            out["gate_sim3_image_edge_point%d_%d" % (which, with_kfs)] = np.concatenate([[n], np.where(matched >= 0, matched - np.int32(qe), -1)])
+
+    # ---- SearchByBoW(KeyFrame, KeyFrame): a bad point of the SECOND key frame is no candidate ----
+    # feature 0 of key frame 1 and features 0, 1 of key frame 2 share node 5; feature 0 of key frame 2 is 10 bits away but its point is bad, feature 1 is 30 bits away
+    b0 = mappoint(world_point(100.0, 100.0, 4.0), 1, near(7, 0)); bb = mappoint(world_point(200.0, 100.0, 4.0), 1, near(7, 0), bad=1); bg = mappoint(world_point(300.0, 100.0, 4.0), 1, near(7, 0))
+    nodes = np.array([5, 5, 9, 10, 11, 12, 13, 14])
+    k1 = drv.frame(True, keys_of([(100.0, 100.0)], [1]), descs([near(7, 0)]), None, I3, np.zeros(3, np.float32), cam)
+    drv.set_map_points(True, k1, ids8([b0])); drv.set_feat_vec(True, k1, nodes)
+    k2 = drv.frame(True, keys_of([(200.0, 100.0), (300.0, 100.0)], [1, 1]), descs([near(7, 10), near(7, 30)]), None, I3, np.zeros(3, np.float32), cam)
+    drv.set_map_points(True, k2, ids8([bb, bg])); drv.set_feat_vec(True, k2, nodes)
+    o = np.full(8, -1, np.int32)
+    n = L.mw_search_by_bow_keyframes(drv.w, k1, k2, _p(o), C.c_float(0.8), 0)
+    out["gate_bow_keyframes_bad_point_of_the_second"] = np.concatenate([[n], np.where(o >= 0, o - np.int32(b0), -1)])
+
+    # ---- SearchBySim3: points that have a partner on entry take no part, on either side ----
+    # both key frames at the origin, S12 = identity: a point is seen at the same pixel by both.  Pixels A, B, C.  Key frame 1: feature 0 at A holds a0, feature 1 at C holds a1,
+    # feature 2 at B holds a2.  Key frame 2: feature 0 at B holds b0, feature 1 at C holds b1, feature 3 at A holds b3.  On entry vpMatches12[0] = b0.
+    #   a1 and b1 find each other's key point: matched.
+    #   a0 (paired) is not searched: b3 finds feature 0 of key frame 1, but nothing points back.  b0 (paired, at feature 0 of key frame 2) is not searched: a2 finds feature 0
+    #   of key frame 2, but nothing points back.
+    A, B_, C_ = (150.0, 300.0), (350.0, 300.0), (550.0, 300.0)
+    XA, XB, XC = world_point(*A, 4.0), world_point(*B_, 4.0), world_point(*C_, 4.0)
+    a0, a1, a2 = mappoint(XA, 1, near(8, 0)), mappoint(XC, 1, near(9, 0)), mappoint(XB, 1, near(10, 0))
+    b0, b1, b3 = mappoint(XB, 1, near(10, 1)), mappoint(XC, 1, near(9, 1)), mappoint(XA, 1, near(8, 1))
+    s1 = drv.frame(True, keys_of([A, C_, B_], [1, 1, 1]), descs([near(8, 2), near(9, 2), near(10, 2)]), None, I3, np.zeros(3, np.float32), cam)
+    drv.set_map_points(True, s1, ids8([a0, a1, a2]))
+    s2 = drv.frame(True, keys_of([B_, C_, (600.0, 400.0), A], [1, 1, 1, 1]), descs([near(10, 3), near(9, 3), base[30], near(8, 3)]), None, I3, np.zeros(3, np.float32), cam)
+    drv.set_map_points(True, s2, ids8([b0, b1, -1, b3]))
+    m12 = ids8([b0])
+    n = L.mw_search_by_sim3(drv.w, s1, s2, _p(m12), C.c_float(1.0), _p(I3), _p(np.zeros(3, np.float32)), C.c_float(7.5))
+    out["gate_sim3_paired_points"] = np.concatenate([[n], np.where(m12 >= 0, m12 - np.int32(b0), -1)])
+
+    # ---- Fuse: a point listed twice, and the viewing-angle test ----
+    # feature 0 holds r (5 observations); p (1 observation) lies where r lies, with r's descriptor, and stands TWICE in the set: the first entry is replaced by r and is bad
+    # when the loop reaches the second.  p2 faces away from the camera (its normal points along the viewing ray): not fused, though feature 1 is free and fits
+    XD, XE = world_point(200.0, 380.0, 4.0), world_point(420.0, 380.0, 4.0)
+    r = mappoint(XD, 1, near(11, 0), n_obs=5); p = mappoint(XD, 1, near(11, 1), n_obs=1)
+    dE = float(np.linalg.norm(XE)); maxE = dE * SCALE ** 0.5
+    p2 = drv.mappoint(XE, -XE / dE, maxE / SCALE ** (NLEVELS - 1), maxE, near(12, 0), bad=0, n_obs=1)
+    kfu = drv.frame(True, keys_of([(200.0, 380.0), (420.0, 380.0)], [1, 1]), descs([near(11, 2), near(12, 2)]), None, I3, np.zeros(3, np.float32), cam)
+    drv.set_map_points(True, kfu, ids8([r]))
+    cand = np.array([p, p, p2], np.int32)
+    n = L.mw_fuse(drv.w, kfu, _p(cand), len(cand), C.c_float(3.0), 0)
+    held = drv.get_map_points(True, kfu, 8); sp = drv.mappoint_state(p, kfu)
+    out["gate_fuse_listed_twice_and_angle"] = np.concatenate([[n], np.where(held >= 0, held - np.int32(r), -1), [sp[0], sp[2] - np.int32(r)]])
+
+    # ---- Fuse on a rig key frame, camera 1: the distance is measured from camera 1's centre ----
+    # camera 2 stands 2 m beside camera 1.  The point is 5 m from camera 1 and 6.4 m from camera 2; 1.2 mfMaxDistance = 5.5 m
+    trl = (I3, np.array([-2.0, 0.0, 0.0], np.float32))
+    cam2 = drv.camera()
+    XR = np.array([-3.0, 0.0, 4.0], np.float32); uR_, vR_ = project(XR, I3, np.zeros(3))
+    pr = drv.mappoint(XR, XR / 5.0, 5.5 / 1.2 / SCALE ** (NLEVELS - 1), 5.5 / 1.2, near(13, 0), bad=0, n_obs=1)
+    kr_ = drv.frame(True, keys_of([(uR_, vR_)], [0]), np.concatenate([descs([near(13, 2)]), descs([])]), None, I3, np.zeros(3, np.float32), cam, cam2, keys_right=keys_of([], []), trl=trl)
+    drv.set_map_points(True, kr_, np.full(16, -1, np.int32))
+    cand = np.array([pr], np.int32)
+    n = L.mw_fuse(drv.w, kr_, _p(cand), 1, C.c_float(3.0), 0)
+    held = drv.get_map_points(True, kr_, 16)
+    out["gate_fuse_rig_camera1_centre"] = np.concatenate([[n], np.where(held >= 0, held - np.int32(pr), -1)])
+    return out
+
+
 if __name__ == "__main__":
     drv_path, orbx_path, seed, variant, dst = sys.argv[1], sys.argv[2], int(sys.argv[3]), sys.argv[4], sys.argv[5]
     d = Driver(drv_path, orbx_path or None)
     if variant in ("fuzz", "rigfuzz", "kb8fuzz"):
         FUZZ = np.random.default_rng(50000 + seed); variant = {"fuzz": "base", "rigfuzz": "rig", "kb8fuzz": "kb8"}[variant]
-    res = build_and_run_rig(d, seed) if variant == "rig" else build_and_run_kb8(d, seed) if variant == "kb8" else build_and_run(d, seed, variant)
+    res = build_and_run_rig(d, seed) if variant == "rig" else build_and_run_kb8(d, seed) if variant == "kb8" else build_and_run_gates(d, seed) if variant == "gates" else build_and_run(d, seed, variant)
     extra = {}
     d.close()
     if len(sys.argv) > 6 and sys.argv[6] == "twice" and orbx_path:

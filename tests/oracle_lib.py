@@ -23,6 +23,22 @@ def emu_link():
     return d, f[3:-3]
 
 
+def include_root():
+    """<repo>/include, or ORBX_FACADE_INCLUDE: a copy of it with one facade header edited (tools/emu_mutants.py, the mutants from 2000)"""
+    return os.path.abspath(os.environ.get("ORBX_FACADE_INCLUDE") or os.path.join(ROOT, "include"))
+
+
+def facade_include():
+    """the directory of the drop-in headers (ORBmatcher.h, KeyFrameDatabase.h, ORBextractor.h, ORBVocabulary.h) that the facade tests compile against"""
+    return os.path.join(include_root(), "orb_slam3_amd")
+
+
+def mw_facade_lib(full=False):
+    """the matcher world over the drop-in ORBmatcher.h: oracle/_ref/libmw_facade.so (full: libmw_facade_full.so, over the reference's own Frame / KeyFrame /
+    MapPoint), or ORBX_MW_FACADE_LIB / ORBX_MW_FACADE_FULL_LIB: the same recipe of oracle/Makefile run on edited headers (tools/emu_mutants.py)"""
+    return os.environ.get("ORBX_MW_FACADE_FULL_LIB" if full else "ORBX_MW_FACADE_LIB") or os.path.join(ROOT, "oracle", "_ref", "libmw_facade_full.so" if full else "libmw_facade.so")
+
+
 def build():
     subprocess.run(["make", "-j8", "-C", ORACLE_DIR, "-s"], check=True, stdout=subprocess.DEVNULL)
 

@@ -69,7 +69,7 @@ def test_dropin_headers_refuse_to_follow_the_reference_headers(tmp_path):
     for name, guard in (("ORBextractor.h", "ORBEXTRACTOR_H"), ("ORBmatcher.h", "ORBMATCHER_H")):
         src = tmp_path / ("t_" + name + ".cpp")
         src.write_text("#define %s\n#include \"%s\"\nint main() { return 0; }\n" % (guard, name))
-        r = subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-I" + os.path.join(ol.ROOT, "include", "orb_slam3_amd"), "-I" + os.path.join(ol.ROOT, "oracle", "opencv_shim"), str(src)],
+        r = subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-I" + ol.facade_include(), "-I" + os.path.join(ol.ROOT, "oracle", "opencv_shim"), str(src)],
                            capture_output=True, text=True)
         assert r.returncode != 0 and "was included before the drop-in" in r.stderr, r.stderr[-500:]
 
@@ -101,6 +101,6 @@ def test_replaced_header_recipe_of_the_integration_guide(tmp_path):
     (inc / "ORBextractor.h").write_bytes(open(os.path.join(ol.ROOT, "include", "orb_slam3_amd", "ORBextractor.h"), "rb").read())
     (inc / "KeyFrameLike.h").write_text('#include "ORBextractor.h"\nstruct KeyFrameLike { ORB_SLAM3::ORBextractor* mpExtractor; };\n')      # what KeyFrame.h:27 does
     (src / "t.cpp").write_text('#include "KeyFrameLike.h"\n#include "ORBextractor.h"\nint main() { return sizeof(KeyFrameLike) > 0 ? 0 : 1; }\n')
-    r = subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-I" + str(inc), "-I" + os.path.join(ol.ROOT, "include", "orb_slam3_amd"),
+    r = subprocess.run(["g++", "-std=c++14", "-fsyntax-only", "-I" + str(inc), "-I" + ol.facade_include(),
                         "-I" + os.path.join(ol.ROOT, "oracle", "opencv_shim"), str(src / "t.cpp")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-800:]

@@ -19,7 +19,7 @@ def _run_pair(tmp_path, libdir, libname, extra_env=None):
     img = synth.corner_field(376, 240, seed=10, nrect=800)
     raw = tmp_path / "im.raw"; raw.write_bytes(img.tobytes())
     exe = tmp_path / "facade_driver_ours"
-    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + os.path.join(ROOT, "include", "orb_slam3_amd"), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
+    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + ol.facade_include(), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
                     os.path.join(ROOT, "tests", "cpp", "facade_driver.cpp"), "-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-o", str(exe)], check=True)
     for lap in ((0, 0), (100, 250)):
         a, b = tmp_path / "ref.bin", tmp_path / "ours.bin"
@@ -47,7 +47,7 @@ def _run_matcher_facade(tmp_path, libdir, libname):
     (tmp_path / "l.raw").write_bytes(L.tobytes()); (tmp_path / "r.raw").write_bytes(R.tobytes())
     ol.oracle()
     exe = tmp_path / "matcher_facade_test"
-    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + os.path.join(ROOT, "include", "orb_slam3_amd"), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
+    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + ol.facade_include(), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
                     os.path.join(ROOT, "tests", "cpp", "matcher_facade_test.cpp"), "-L" + libdir, "-l" + libname, "-L" + os.path.join(ROOT, "oracle"), "-lorb_oracle",
                     "-Wl,-rpath," + libdir, "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-lpthread", "-o", str(exe)], check=True)
     r = subprocess.run([str(exe), str(tmp_path / "l.raw"), str(tmp_path / "r.raw"), "376", "240"], capture_output=True, text=True)
@@ -59,7 +59,7 @@ def _run_matcher_threads(tmp_path, libdir, libname):
     L, _ = synth.stereo_pair(376, 240, seed=21, nrect=800)
     (tmp_path / "t.raw").write_bytes(L.tobytes())
     exe = tmp_path / "matcher_threads_test"
-    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + os.path.join(ROOT, "include", "orb_slam3_amd"), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
+    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + ol.facade_include(), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
                     os.path.join(ROOT, "tests", "cpp", "matcher_threads_test.cpp"), "-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-lpthread", "-o", str(exe)], check=True)
     r = subprocess.run([str(exe), str(tmp_path / "t.raw"), "376", "240"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
@@ -105,7 +105,7 @@ def test_vocabulary_facade_emulated(tmp_path, emu_lib):
     exe = tmp_path / "vocabulary_facade_test"
     libdir, libname = ol.emu_link()
     srcs = [os.path.join(DBOW2, "DBoW2", f) for f in ("FORB.cpp", "BowVector.cpp", "FeatureVector.cpp", "ScoringObject.cpp")] + [os.path.join(DBOW2, "DUtils", "Random.cpp"), os.path.join(DBOW2, "DUtils", "Timestamp.cpp")]
-    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + os.path.join(ROOT, "include", "orb_slam3_amd"), "-I" + os.path.join(ROOT, "include"),
+    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + ol.facade_include(), "-I" + ol.include_root(),
                     "-I" + os.path.join(ROOT, "oracle", "opencv_shim"), "-I" + os.path.join(ROOT, "oracle", "boost_shim"), "-I" + DBOW2,
                     os.path.join(ROOT, "tests", "cpp", "vocabulary_facade_test.cpp")] + srcs +
                    ["-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-lpthread", "-o", str(exe)], check=True)
@@ -121,7 +121,7 @@ def test_facade_headers_link_from_several_translation_units(tmp_path, emu_lib):
     (tmp_path / "a.cpp").write_text(inc + "int fa() { ORB_SLAM3::ORBmatcher m(0.7f, true); const int& r = ORB_SLAM3::ORBmatcher::TH_LOW; return r; }\n")
     (tmp_path / "b.cpp").write_text(inc + "int fa();\nint main() { const int& r = ORB_SLAM3::ORBmatcher::TH_HIGH; return fa() + r + ORB_SLAM3::ORBmatcher::HISTO_LENGTH == 180 ? 0 : 1; }\n")
     libdir, libname = ol.emu_link()
-    cmd = ["g++", "-std=c++14", "-w", "-I" + os.path.join(ROOT, "include", "orb_slam3_amd"), "-I" + os.path.join(ROOT, "oracle", "opencv_shim")]
+    cmd = ["g++", "-std=c++14", "-w", "-I" + ol.facade_include(), "-I" + os.path.join(ROOT, "oracle", "opencv_shim")]
     if voc:
         cmd += ["-I" + DBOW2, "-I/root/reference", "-I" + os.path.join(ROOT, "oracle", "boost_shim")]
     exe = tmp_path / "two_tu"

@@ -17,7 +17,7 @@ ROOT = ol.ROOT
 
 def _build(tmp_path, libdir, libname):
     exe = tmp_path / "fuse_many_test"
-    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + os.path.join(ROOT, "include", "orb_slam3_amd"), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
+    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + ol.facade_include(), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
                     os.path.join(ROOT, "tests", "cpp", "fuse_many_test.cpp"), "-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-lpthread", "-o", str(exe)], check=True)
     return exe
 

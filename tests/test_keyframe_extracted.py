@@ -504,7 +504,7 @@ def _facade_adopt(tmp_path, libdir, libname):
     src = os.path.join(ol.ROOT, "tests", "cpp", "keyframe_adopt_probe.cpp")
     exe = tmp_path / "keyframe_adopt_probe"
     subprocess.run(["g++", "-O1", "-std=c++17", "-I" + os.path.join(ol.ROOT, "oracle", "opencv_shim"),
-                    "-I" + os.path.join(ol.ROOT, "include"), src, "-o", str(exe), "-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-lpthread"], check=True)
+                    "-I" + ol.include_root(), src, "-o", str(exe), "-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-lpthread"], check=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "ADOPT OK" in r.stdout, r.stdout + r.stderr
 

@@ -20,7 +20,7 @@ def build_driver(tmp_path, libdir, libname):
     if ol.reference_dbow2() is None:
         pytest.skip("oracle/_ref/libref_dbow2.so not built")
     exe = tmp_path / "kfdb_facade_test"
-    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + os.path.join(ROOT, "include", "orb_slam3_amd"), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
+    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + ol.facade_include(), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
                     os.path.join(ROOT, "tests", "cpp", "kfdb_facade_test.cpp"), "-L" + libdir, "-l" + libname, os.path.join(REF, "libref_dbow2.so"),
                     "-Wl,-rpath," + libdir, "-Wl,-rpath," + REF, "-lpthread", "-o", str(exe)], check=True)
     return exe

@@ -179,7 +179,7 @@ def _facade_worlds(tmp_path, orbx):
     import subprocess
     import sys
     import oracle_lib as ol
-    facade = os.path.join(ol.ROOT, "oracle", "_ref", "libmw_facade.so")
+    facade = ol.mw_facade_lib()
     if not os.path.exists(facade):
         pytest.skip("oracle/_ref/libmw_facade.so not built (needs /root/reference)")
     for seed, variant in [(1, "base"), (6, "kb8")]:

@@ -21,12 +21,12 @@ from orb_slam3_detailed_comments_amd import _lib
 
 ROOT = ol.ROOT
 REF = os.path.join(ROOT, "oracle", "_ref", "libmw_ref.so")
-FACADE = os.path.join(ROOT, "oracle", "_ref", "libmw_facade.so")
+FACADE = ol.mw_facade_lib()
 # the same driver over the reference's OWN Frame, KeyFrame and MapPoint classes (Frame.cc / KeyFrame.cc / MapPoint.cc linked in, and in the
 # facade build compiled against the drop-in ORBmatcher.h); only Map, KeyFrameDatabase, the IMU types, the camera and the Eigen / Sophus algebra
 # are stand-ins there
 REF_REAL = os.path.join(ROOT, "oracle", "_ref", "libmw_ref_full.so")
-FACADE_REAL = os.path.join(ROOT, "oracle", "_ref", "libmw_facade_full.so")
+FACADE_REAL = ol.mw_facade_lib(full=True)
 RUNNER = os.path.join(ROOT, "tests", "matcher_world.py")
 pytestmark = pytest.mark.skipif(not (os.path.exists(REF) and os.path.exists(FACADE)), reason="oracle/_ref/libmw_*.so not built (needs /root/reference)")
 

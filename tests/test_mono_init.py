@@ -165,7 +165,7 @@ def test_pool_form_batches_gpu(hip_lib):
 # ---- the C++ facade: ORBextractor(5 * nFeatures, ...) for every settings file, against the reference build of the same driver ----
 def _facade_exe(tmp, libdir, libname):
     exe = tmp / "facade_driver_ours"
-    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + os.path.join(ROOT, "include", "orb_slam3_amd"), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
+    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + ol.facade_include(), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
                     os.path.join(ROOT, "tests", "cpp", "facade_driver.cpp"), "-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-o", str(exe)], check=True)
     return exe
 

@@ -17,7 +17,7 @@ def _run(tmp_path, libdir, libname, w, h, calls):
         img = synth.corner_field(w, h, seed=30 + s, nrect=800 if w < 500 else 3000) if s < 2 else synth.natural(w, h, seed=30 + s)
         p = tmp_path / ("im%d.raw" % s); p.write_bytes(img.tobytes()); raws.append(str(p))
     exe = tmp_path / "pyramid_export_facade_test"
-    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + os.path.join(ROOT, "include", "orb_slam3_amd"), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
+    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + ol.facade_include(), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
                     os.path.join(ROOT, "tests", "cpp", "pyramid_export_facade_test.cpp"), "-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-lpthread",
                     "-o", str(exe)], check=True)
     r = subprocess.run([str(exe), str(w), str(h), str(calls)] + raws, capture_output=True, text=True, timeout=900)

@@ -261,7 +261,7 @@ def run_facade_threads(tmp_path, libdir, libname, calls):
         (inc / name).write_text(text)
     ref = os.path.join(ROOT, "oracle", "_ref")
     exe = tmp_path / "shared_objects_threads_test"
-    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + os.path.join(ROOT, "include", "orb_slam3_amd"), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
+    subprocess.run(["g++", "-std=c++14", "-O1", "-w", "-I" + ol.facade_include(), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
                     "-I" + str(inc.parent), os.path.join(ROOT, "tests", "cpp", "shared_objects_threads_test.cpp"), "-L" + libdir, "-l" + libname, DBOW2,
                     "-Wl,-rpath," + libdir, "-Wl,-rpath," + ref, "-lpthread", "-o", str(exe)], check=True)
     rng = np.random.default_rng(6)

@@ -18,7 +18,7 @@ ROOT = ol.ROOT
 def _build(tmp_path, libdir, libname, hidden):
     exe = tmp_path / ("sim3_many_test_hidden" if hidden else "sim3_many_test")
     subprocess.run(["g++", "-std=c++14", "-O1", "-w"] + (["-DHIDE_DISTANCE_LIMITS"] if hidden else []) +
-                   ["-I" + os.path.join(ROOT, "include", "orb_slam3_amd"), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
+                   ["-I" + ol.facade_include(), "-I" + os.path.join(ROOT, "oracle", "opencv_shim"),
                     os.path.join(ROOT, "tests", "cpp", "sim3_many_test.cpp"), "-L" + libdir, "-l" + libname, "-Wl,-rpath," + libdir, "-lpthread", "-o", str(exe)], check=True)
     return exe
 

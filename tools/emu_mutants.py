@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Would a test notice a kernel line deciding wrongly?  A mutation pass over the DECISIONS of the kernels (match / search / vocabulary: ids below 405; extraction - FAST,
 quadtree, pyramid, blur, orientation and BRIEF, input stage - and the host tables of orbx_api.cpp that feed it: ids from 405) and of the host replays of the single-frame
-matcher entries in orbm_search.cpp (ids from 1000: host code is a translation unit of the emulator library like any kernel file), on the CPU SIMT emulator only.
+matcher entries in orbm_search.cpp (ids from 1000: host code is a translation unit of the emulator library like any kernel file), on the CPU SIMT emulator only - and over the
+drop-in facade headers of include/orb_slam3_amd (ids from 2000), which are compiled into the test drivers, not into the library.
 
 For every mutant of tools/emu_mutants_list.py: copy csrc to a temporary directory (the tree is never edited), replace the mutant's old text - which must occur exactly
 once in its file, so that the list cannot rot silently when a kernel is edited - by its new text, build the emulator library from the copy with the flags of
@@ -14,12 +15,18 @@ A mutant may carry `defines` (("-DORBX_FAST_LIST_CAP=200",): the switches of tes
 them - for decisions that the default build reaches only on very large or very dense images.  Its test files must take the `emu_lib` fixture (tests/test_emu_variants.py builds
 its own libraries from the tree and would not see the mutant).  A test may be named as a file or as a pytest node id (`test_x.py::test_y`, `test_x.py::test_y[case]`) where the
 whole file takes minutes on the emulator; files are run in the order given, cheapest first, and the run stops at the first failure.
+A mutant whose file is named from the repository root (include/orb_slam3_amd/ORBmatcher.h) is a header's: a copy of include/ takes the edit, the emulator library stays the
+unmutated one of tests/emu (built once per pass), oracle/_ref/libmw_facade.so - and libmw_facade_full.so where the mutant's group names a test that loads it - is built from the
+copy into the temporary directory by the recipe of oracle/Makefile (FACADE_INC, FACADE_OUT), and the tests run with ORBX_FACADE_INCLUDE / ORBX_MW_FACADE_LIB /
+ORBX_MW_FACADE_FULL_LIB naming them (tests/oracle_lib.py: facade_include, include_root, mw_facade_lib).  tests/test_callers_compile.py reads objects made from the real headers
+and is refused in such a mutant's group.
 crashed: pytest, or one of its workers, ended on a signal (a negative return status, "worker .. crashed").  That is no kill: a mutant that can index outside its arrays is a
 defect of the LIST (it breaks the list's safety rule), and the pass fails on it.
 
     python tools/emu_mutants.py                       every mutant -> profiles/emu_mutants/results_after.jsonl
     python tools/emu_mutants.py --only k_match        the mutants of files whose name contains k_match (comma-separated list)
     python tools/emu_mutants.py --only orbm_search    the host replays (profiles/emu_mutants_host/: --out / --carry / --base name that directory's files)
+    python tools/emu_mutants.py --only include/       the facade headers (profiles/emu_mutants_facade/)
     python tools/emu_mutants.py --ids 3,4             by id
     python tools/emu_mutants.py --without test_x.py   leave test files out (how results_before.jsonl was made: without the tests that the pass itself added)
     python tools/emu_mutants.py --carry before.jsonl  take the kills of an earlier pass as they are and run only what survived it
@@ -45,6 +52,30 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 CSRC = os.path.join(ROOT, "orb_slam3_detailed_comments_amd", "csrc")
 EMU = os.path.join(ROOT, "tests", "emu")
+INCLUDE = os.path.join(ROOT, "include")
+ORACLE = os.path.join(ROOT, "oracle")
+# the tests that load oracle/_ref/libmw_facade.so (tests/oracle_lib.py::mw_facade_lib) - and, of these, what loads libmw_facade_full.so: the `real` tests of
+# tests/test_matcher_reference.py (a mutant's group names them by node id, or the whole file)
+MW_TESTS = ("test_matcher_reference.py", "test_lifetime.py", "test_matcher_gates.py")
+MW_FULL_NODES = ("real",)
+
+
+def is_facade(m):
+    """a mutant of a drop-in header: its file is named from the repository root (include/orb_slam3_amd/ORBmatcher.h), not inside csrc"""
+    return m["file"].startswith("include/")
+
+
+def source_path(m):
+    return os.path.join(ROOT, m["file"]) if is_facade(m) else os.path.join(CSRC, m["file"])
+
+
+def needs_mw(files, full=False):
+    """does one of the test files / node ids load the matcher-world facade library (full: the one over the reference's own Frame / KeyFrame / MapPoint)"""
+    for f in files:
+        name, _, node = f.partition("::")
+        if name in MW_TESTS and (not full or (name == "test_matcher_reference.py" and (not node or any(w in node for w in MW_FULL_NODES)))):
+            return True
+    return False
 
 
 def emu_sources():
@@ -113,9 +144,25 @@ def same_mutant(r, m):
     return r["edits"] == [list(e) for e in edits(m)] if "edits" in r else r.get("edits_sha") == edits_sha(m)
 
 
+def tests_sha(files):
+    """what a survivor of a header's mutant survived: the contents of its test files and of everything they compile or run (tests/cpp, the world runner, the helpers) -
+    a check strengthened INSIDE an existing driver changes it, which the list of file names alone would not show"""
+    h = hashlib.sha1()
+    names = sorted({f.split("::")[0] for f in files}) + ["matcher_world.py", "oracle_lib.py"] + sorted("cpp/" + n for n in os.listdir(os.path.join(ROOT, "tests", "cpp")))
+    for n in names:
+        h.update(n.encode()); h.update(open(os.path.join(ROOT, "tests", n), "rb").read())
+    return h.hexdigest()[:12]
+
+
 def stands(r, m, without):
-    """a kill of an earlier run stands; a survivor's verdict stands only if the very same test files would run now"""
-    return same_mutant(r, m) and (r["verdict"] == "killed" or (r["verdict"] == "survived" and r.get("tests") == test_files(m, without)))
+    """a kill of an earlier run stands; a survivor's verdict stands only if the very same test files would run now - for a header's mutant (ids from 2000) with the very
+    same contents (tests_sha: a record without one is run again)"""
+    if not same_mutant(r, m):
+        return False
+    if r["verdict"] == "killed":
+        return True
+    files = test_files(m, without)
+    return r["verdict"] == "survived" and r.get("tests") == files and (not is_facade(m) or r.get("tests_sha") == tests_sha(files))
 
 
 def apply_mutant(m, src_dir):
@@ -150,8 +197,74 @@ def crashed(rc, out):
     return (isinstance(rc, int) and (rc < 0 or rc >= 128)) or re.search(r"crashed while running|Fatal Python error|node down: Not properly terminated", out) is not None
 
 
+def run_tests(rec, m, d, files, env, timeout):
+    """the mutant's test files under `env`; the verdict goes into rec"""
+    t1 = time.time()
+    cmd = [sys.executable, "-m", "pytest"] + [os.path.join("tests", f) for f in files] + ["-m", "not gpu", "-x", "-q", "-rfE", "-p", "no:cacheprovider", "--basetemp=" + os.path.join(d, "pytest")]
+    try:
+        r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
+        out, rc = r.stdout + r.stderr, r.returncode
+    except subprocess.TimeoutExpired as e:
+        out, rc = (e.stdout or b"").decode(errors="replace") if isinstance(e.stdout, bytes) else (e.stdout or ""), "timeout"
+    rec["test_s"] = round(time.time() - t1, 1)
+    if rc == 0:
+        rec.update(verdict="survived", tests=files)             # (what it survived: --carry runs it again when the files change)
+    elif rc == 5:
+        rec.update(verdict="refused", detail="no test collected from %s" % files)
+    elif crashed(rc, out):                                      # no kill: the mutant broke the list's safety rule
+        rec.update(verdict="crashed", first_failing_test=(first_failure(out) or "").strip("'\"") or None, detail=out[-300:])
+    elif rc == "timeout":                                       # a verdict of its own: a hang is noticed, but no test says what is wrong
+        rec.update(verdict="timeout", detail="the tests did not end within %d s" % timeout)
+    else:
+        rec.update(verdict="killed", first_failing_test=first_failure(out))
+        if rec["first_failing_test"] is None:
+            rec["detail"] = out[-300:]
+    return rec
+
+
+def run_facade_mutant(m, work, without, timeout):
+    """a mutant of a header under include/orb_slam3_amd: a copy of include/ with the edit, the matcher-world facade libraries built from the copy by the recipe of
+    oracle/Makefile where the mutant's tests load them, and the tests pointed at both (tests/oracle_lib.py: ORBX_FACADE_INCLUDE, ORBX_MW_FACADE_LIB,
+    ORBX_MW_FACADE_FULL_LIB).  The emulator library is the unmutated one of tests/emu (built once per pass, in main)."""
+    rec = dict(id=m["id"], file=m["file"], intent=m["intent"], edits_sha=edits_sha(m))
+    d = os.path.join(work, "m%03d" % m["id"])
+    inc = os.path.join(d, "include")
+    shutil.copytree(INCLUDE, inc)
+    t0 = time.time()
+    try:
+        apply_mutant(dict(m, file=os.path.relpath(m["file"], "include")), inc)
+    except ValueError as e:
+        rec.update(verdict="refused", detail=str(e))
+        shutil.rmtree(d, ignore_errors=True)
+        return rec
+    files = test_files(m, without)
+    if not files:
+        rec.update(verdict="refused", detail="none of the mutant's test files is left: %s" % m["tests"])
+        shutil.rmtree(d, ignore_errors=True)
+        return rec
+    env = dict(os.environ, ORBX_FACADE_INCLUDE=inc)
+    env.pop("ORBX_EMU_LIB", None)
+    targets = [("libmw_facade.so", "ORBX_MW_FACADE_LIB")] * needs_mw(files) + [("libmw_facade_full.so", "ORBX_MW_FACADE_FULL_LIB")] * needs_mw(files, full=True)
+    if targets:
+        r = subprocess.run(["make", "-C", ORACLE, "-j2", "FACADE_INC=" + inc, "FACADE_OUT=" + d] + [os.path.join(d, t) for t, _ in targets], capture_output=True, text=True)
+        if r.returncode:
+            rec.update(verdict="build_error", detail=r.stderr[-400:], build_s=round(time.time() - t0, 1))
+            shutil.rmtree(d, ignore_errors=True)
+            return rec
+        for t, var in targets:
+            env[var] = os.path.join(d, t)
+    rec["build_s"] = round(time.time() - t0, 1)
+    run_tests(rec, m, d, files, env, timeout)
+    if rec["verdict"] == "survived":
+        rec["tests_sha"] = tests_sha(files)
+    shutil.rmtree(d, ignore_errors=True)
+    return rec
+
+
 def run_mutant(m, base, work, without, timeout):
     """build and test one mutant; base: the copy of csrc, the unmutated objects beside it (base_objects)"""
+    if is_facade(m):
+        return run_facade_mutant(m, work, without, timeout)
     # (a record is small: note and texts are the list's, which a record only has to be matched against - edits_sha; the first pass's records hold them in full)
     rec = dict(id=m["id"], file=m["file"], intent=m["intent"], edits_sha=edits_sha(m))
     defines = tuple(m.get("defines") or ())
@@ -192,27 +305,7 @@ def run_mutant(m, base, work, without, timeout):
         rec.update(verdict="refused", detail="none of the mutant's test files is left: %s" % m["tests"])
         shutil.rmtree(d, ignore_errors=True)
         return rec
-    t1 = time.time()
-    env = dict(os.environ, ORBX_EMU_LIB=so)
-    cmd = [sys.executable, "-m", "pytest"] + [os.path.join("tests", f) for f in files] + ["-m", "not gpu", "-x", "-q", "-rfE", "-p", "no:cacheprovider", "--basetemp=" + os.path.join(d, "pytest")]
-    try:
-        r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
-        out, rc = r.stdout + r.stderr, r.returncode
-    except subprocess.TimeoutExpired as e:
-        out, rc = (e.stdout or b"").decode(errors="replace") if isinstance(e.stdout, bytes) else (e.stdout or ""), "timeout"
-    rec["test_s"] = round(time.time() - t1, 1)
-    if rc == 0:
-        rec.update(verdict="survived", tests=files)             # (what it survived: --carry runs it again when the files change)
-    elif rc == 5:
-        rec.update(verdict="refused", detail="no test collected from %s" % files)
-    elif crashed(rc, out):                                      # no kill: the mutant broke the list's safety rule
-        rec.update(verdict="crashed", first_failing_test=(first_failure(out) or "").strip("'\"") or None, detail=out[-300:])
-    elif rc == "timeout":                                       # a verdict of its own: a hang is noticed, but no test says what is wrong
-        rec.update(verdict="timeout", detail="the tests did not end within %d s" % timeout)
-    else:
-        rec.update(verdict="killed", first_failing_test=first_failure(out))
-        if rec["first_failing_test"] is None:
-            rec["detail"] = out[-300:]
+    run_tests(rec, m, d, files, dict(os.environ, ORBX_EMU_LIB=so), timeout)
     shutil.rmtree(d, ignore_errors=True)
     return rec
 
@@ -266,13 +359,15 @@ def main():
     assert len(set(ids)) == len(ids), "duplicate mutant ids"
     bad = 0
     for m in MUTANTS:                                           # the whole list is verified, whatever is selected
-        text = open(os.path.join(CSRC, m["file"])).read()
+        text = open(source_path(m)).read()
         for old, _ in edits(m):
             if text.count(old) != 1:
                 print("mutant %d (%s): the old text occurs %d times, must be exactly once: %r" % (m["id"], m["file"], text.count(old), old))
                 bad += 1
         if not m["tests"]:
             print("mutant %d names no test file" % m["id"]); bad += 1
+        if is_facade(m) and any(t.startswith("test_callers_compile.py") for t in m["tests"]):   # (it reads objects made from the real headers at build time)
+            print("mutant %d: tests/test_callers_compile.py cannot see a mutated header" % m["id"]); bad += 1
     if bad:
         return 2
     if a.check:
@@ -317,8 +412,11 @@ def main():
             subprocess.run(["make", "-C", EMU, "-s"], check=True)   # (the emu_lib fixture builds the default library before it looks at ORBX_EMU_LIB: not while the workers start)
             base = os.path.join(work, "base")
             shutil.copytree(CSRC, base)
-            base_objects(base, ())
-            print("unmutated objects: %.0f s" % (time.time() - t_pass))
+            if not all(is_facade(m) for m in todo):
+                base_objects(base, ())
+                print("unmutated objects: %.0f s" % (time.time() - t_pass))
+            if any(is_facade(m) for m in todo):                 # the oracle's libraries (the reference builds among them) before the workers ask for them
+                subprocess.run(["make", "-C", ORACLE, "-j8", "-s"], check=True, stdout=subprocess.DEVNULL)
 
         def one(m):
             r = run_mutant(m, base, work, without, a.timeout)

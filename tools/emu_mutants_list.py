@@ -1,4 +1,4 @@
-"""The mutants of tools/emu_mutants.py: (id, file in csrc, old text that occurs EXACTLY ONCE in that file, new text, CPU test files or node ids, intent[, note][, defines]).
+"""The mutants of tools/emu_mutants.py: (id, file in csrc - or, from the repository root, a header under include/orb_slam3_amd -, old text that occurs EXACTLY ONCE in that file, new text, CPU test files or node ids, intent[, note][, defines]).
 
 Only decisions are mutated: a relational boundary, one clause of a compound gate removed or negated, a rank or threshold constant off by one, a tie broken the other
 way, a gate's constant replaced by a neighbour.  Never address arithmetic, loop bounds over memory, launch geometry, synchronisation or the lines under the
@@ -710,3 +710,311 @@ M(1186, F, "R.camera_type = V->camera2_type;", "R.camera_type = V->left.camera_t
   "only ever a `new KannalaBrandt8`, src/Tracking.cc:1132, beside a fisheye first camera), every rig of the suite and of the reference drivers (oracle/ref_frame_driver.cpp) is such a pair, and with equal models the mutant "
   "computes the same; a pinhole camera beside a fisheye one would have nothing to be compared with")
 M(1187, F, "Fp->rig_mode = 1;", "Fp->rig_mode = 0;", [HG] + H_FRUSTUM[1:], "right_camera_params: camera 2 judged in the single-camera mode")
+
+# ---- the drop-in facade headers (ids from 2000) -----------------------------------------------------------------------------------------------------------------
+# A file named from the repository root (include/orb_slam3_amd/...): the tool edits a copy of include/, builds oracle/_ref/libmw_facade*.so from the copy where the
+# mutant's tests load them, and leaves the emulator library alone.  tests/test_callers_compile.py never stands in a group: it reads objects made from the real headers.
+# The safety rule is the host code's - a mutant runs inside the test drivers, on the emulator, in host memory:
+#   no sizes, no `M > 0 ? M : 1` buffers, no loop bounds;
+#   no guard removed in front of an index or a dereference (`!pMP`, `!incoming`, `!p`, `points[i] &&`, `best[i] < 0`, `m12[i] >= 0`, `assigned[i] >= 0`,
+#   `j >= 0 && j < n[1]`, `row < 0`, `k < (int)rowOf.size()`, `it == mAdds.end()`, `v_ == nullptr ||`, `(int)vpMatched.size() != pKF->N`, `mpCamera2 &&` in front of
+#   mpCamera2->, `u_right = nullptr` under mpCamera2: a rig's mvuRight holds Nleft values and the device would read N);
+#   no Check(...) removed; nothing that destroys a device object twice or uses one after its destroy (Adopt's `dev != dev` test may only be mutated towards a leak,
+#   the transient rule only towards caching, FuseBatch::Add's own upload of a key frame without BoW not at all: through Get it would be the transient, destroyed by
+#   the next Get of the same call).  A mutant that leaks is allowed: the library's live count shows it.  `crashed` fails the pass.
+FH = "include/orb_slam3_amd/ORBmatcher.h"
+FG = "test_facade_gates.py"                                           # the new files: the mock-type driver (cache, FuseBatch, Fuse) and the constructed database
+KG = "test_kfdb_gates.py"
+MG = "test_matcher_gates.py"                                          # ... and the hand-built `gates` worlds of tests/matcher_world.py, through the reference and the facade
+MOCK = "test_facade.py::test_matcher_facade_emulated"
+MWREF = "test_matcher_reference.py::test_matcher_facade_equals_reference_emulated"
+MWFUZZ = "test_matcher_reference.py::test_matcher_facade_equals_reference_random_parameters_emulated"
+F_MW = [MG, FG, MOCK, MWREF, MWFUZZ]
+F_FUSE = [MG, FG, "test_fuse_many_facade.py", MOCK, MWREF]
+F_SIM3 = [MG, FG, "test_sim3_many_facade.py", MWREF]
+F_CACHE = [FG, "test_keyframe_extracted.py::test_facade_adopt", "test_fuse_many_facade.py", MOCK, "test_shared_objects.py::test_resident_keyframes_shared_by_threads_emulated",
+           "test_lifetime.py::test_facade_worlds_leave_nothing_behind", MWREF]
+F_KFDB = [KG, "test_kfdb_facade.py"]
+F_EXTRACT = ["test_facade.py::test_facade_dropin_emulated", "test_pyramid_export_facade.py", "test_mono_init.py::test_facade_constructs_every_mono_init_extractor_emulated"]
+F_VOC = ["test_facade.py::test_vocabulary_facade_emulated", "test_shared_objects.py::test_vocabulary_facade_shared_by_threads_emulated"]
+TWICE = ("equivalent: Fuse tests the point twice on purpose - the head only chooses what is projected, and the replay loop reads isBad / IsInKeyFrame again before anything is written; "
+         "a point that the head lets through wrongly is projected, searched and then skipped there")
+ROUTE = "equivalent in the result: the condition only chooses between the resident and the uploaded form of the same search, which tests/test_resident_keyframes.py holds equal"
+# SearchByProjection(Frame, MapPoints)
+M(2000, FH, "hasObs[i] = p->Observations() > 0;", "hasObs[i] = p->Observations() >= 0;", F_MW, "SearchByProjection(MapPoints): a point without observations counts as observed")
+M(2001, FH, "bad[i] = p->isBad(); hasObs[i]", "bad[i] = 0; hasObs[i]", F_MW, "SearchByProjection(MapPoints): isBad not read")
+M(2002, FH, "inViewR[i] = p->mbTrackInViewR;", "inViewR[i] = p->mbTrackInView;", F_MW, "SearchByProjection(MapPoints), rig: camera 2 takes camera 1's mbTrackInView")
+M(2003, FH, "FillFrame(F, fs, OccupiedWithObservations);", "FillFrame(F, fs, OccupiedAny);", F_MW, "SearchByProjection(MapPoints): a keypoint with an unobserved point is occupied")
+M(2004, FH, "FillRig(F, rs, OccupiedWithObservations);", "FillRig(F, rs, OccupiedAny);", F_MW, "SearchByProjection(MapPoints), rig: a keypoint with an unobserved point is occupied")
+# SearchByProjection(Frame, LastFrame)
+M(2010, FH, "zLastOfCurCentre > CurrentFrame.mb, away", "zLastOfCurCentre >= CurrentFrame.mb, away", F_MW, "SearchByProjection(LastFrame): z == mb is `towards`")
+M(2011, FH, "-zLastOfCurCentre > CurrentFrame.mb;", "-zLastOfCurCentre >= CurrentFrame.mb;", F_MW, "SearchByProjection(LastFrame): -z == mb is `away`")
+M(2012, FH, "towards = !bMono && zLastOfCurCentre", "towards = zLastOfCurCentre", F_MW, "SearchByProjection(LastFrame): bMono does not switch `towards` off")
+M(2013, FH, "away = !bMono && -zLastOfCurCentre", "away = -zLastOfCurCentre", F_MW, "SearchByProjection(LastFrame): bMono does not switch `away` off")
+M(2014, FH, "if (!pMP || LastFrame.mvbOutlier[i]) continue;", "if (!pMP) continue;", F_MW, "SearchByProjection(LastFrame): outliers are searched")
+M(2015, FH, "seen[i] = pMP->Observations() > 0;", "seen[i] = 1;", F_MW, "SearchByProjection(LastFrame): a point without observations occupies its keypoint")
+M(2016, FH, "FillFrame(CurrentFrame, fs, OccupiedWithObservations);", "FillFrame(CurrentFrame, fs, OccupiedAny);", F_MW, "SearchByProjection(LastFrame): a keypoint with an unobserved point is occupied")
+M(2017, FH, "FillRig(CurrentFrame, rs, OccupiedWithObservations);", "FillRig(CurrentFrame, rs, OccupiedAny);", F_MW, "SearchByProjection(LastFrame), rig: a keypoint with an unobserved point is occupied")
+M(2018, FH, "CurrentFrame.mvpMapPoints[i] = LastFrame.mvpMapPoints[assigned[i]];\n            else if (assigned[i] == -2) CurrentFrame.mvpMapPoints[i] = nullptr;",
+  "CurrentFrame.mvpMapPoints[i] = LastFrame.mvpMapPoints[assigned[i]];", F_MW, "SearchByProjection(LastFrame): a match that the rotation check removes leaves the keypoint's old point")
+M(2019, FH, "right.depth_test = 0; right.bounds_mode = 2;", "right.depth_test = 2; right.bounds_mode = 2;", F_MW, "SearchByProjection(LastFrame), rig: camera 2's projection takes a depth test")
+M(2020, FH, "spec.depth_test = 2;                                  // 1 / z < 0 rejects", "spec.depth_test = 1;                                  // 1 / z < 0 rejects", F_MW,
+  "SearchByProjection(LastFrame): the depth test of the other methods (z <= 0)")
+# SearchByProjection(Frame, KeyFrame, sAlreadyFound)
+M(2025, FH, "if (pMP && !pMP->isBad() && !sAlreadyFound.count(pMP)) pts.take(i, pMP, false);", "if (pMP && !sAlreadyFound.count(pMP)) pts.take(i, pMP, false);", F_MW,
+  "SearchByProjection(KeyFrame): bad points are searched")
+M(2026, FH, "if (pMP && !pMP->isBad() && !sAlreadyFound.count(pMP)) pts.take(i, pMP, false);", "if (pMP && !pMP->isBad()) pts.take(i, pMP, false);", F_MW,
+  "SearchByProjection(KeyFrame): points already found are searched")
+M(2027, FH, "FillFrame(CurrentFrame, fs, OccupiedAny);", "FillFrame(CurrentFrame, fs, OccupiedWithObservations);", F_MW, "SearchByProjection(KeyFrame): a keypoint with an unobserved point is free")
+M(2028, FH, "CurrentFrame.mvpMapPoints[i] = kfPoints[assigned[i]];\n            else if (assigned[i] == -2) CurrentFrame.mvpMapPoints[i] = nullptr;", "CurrentFrame.mvpMapPoints[i] = kfPoints[assigned[i]];", F_MW,
+  "SearchByProjection(KeyFrame): the -2 -> nullptr write-back removed",
+  "equivalent: under OccupiedAny only a keypoint that was NULL on entry can be matched, so a match that the rotation check removes (-2) leaves what was there, NULL, with or without the line")
+M(2029, FH, "spec.distance_test = 1;                               // no depth test", "spec.distance_test = 0;                               // no depth test", F_MW,
+  "SearchByProjection(KeyFrame): the distance-range test switched off")
+# the Sim3 projection searches, single and many
+M(2030, FH, "if (!pMP->isBad() && !taken.count(pMP)) pts.take(i, pMP, true);", "if (!taken.count(pMP)) pts.take(i, pMP, true);", F_SIM3 + [MWFUZZ], "SearchByProjection(Sim3): bad points are searched")
+M(2031, FH, "if (!pMP->isBad() && !taken.count(pMP)) pts.take(i, pMP, true);", "if (!pMP->isBad()) pts.take(i, pMP, true);", F_SIM3 + [MWFUZZ], "SearchByProjection(Sim3): points already matched are searched")
+M(2033, FH, "for (int i = 0; i < N; i++) fs.occ[i] = vpMatched[i] != nullptr;", "for (int i = 0; i < N; i++) fs.occ[i] = 0;", F_SIM3 + [MWFUZZ], "SearchByProjection(Sim3): matched keypoints are free")
+M(2034, FH, "if (inlineProjection) { spec.camera_type = 0;", "if (!inlineProjection) { spec.camera_type = 0;", F_SIM3 + [MWFUZZ], "Sim3ProjectionSpec: the two overloads' projections swapped")
+M(2035, FH, "spec.inline_pinhole = 1; }", "spec.inline_pinhole = 0; }", F_SIM3 + [MWFUZZ], "Sim3ProjectionSpec: the inline form projects like GeometricCamera::project")
+M(2036, FH, "spec.depth_test = 1; spec.distance_test = 1; spec.angle_test = 1;\n        return spec;", "spec.depth_test = 1; spec.distance_test = 1; spec.angle_test = 0;\n        return spec;", F_SIM3 + [MWFUZZ],
+  "Sim3ProjectionSpec: the viewing-angle test switched off")
+M(2037, FH, "return SE3T(S.rotationMatrix(), S.translation() / S.scale());", "return SE3T(S.rotationMatrix(), S.translation());", F_SIM3 + F_FUSE[1:], "RigidPart: the translation is not divided by the scale")
+M(2038, FH, "{ vpMatched[idx] = vpPoints[assigned[idx]]; vpMatchedKF[idx] = vpPointsKFs[assigned[idx]]; }", "{ vpMatched[idx] = vpPoints[assigned[idx]]; }", F_SIM3 + [MWFUZZ],
+  "SearchByProjection(Sim3, vpPointsKFs): vpMatchedKF not written")
+M(2039, FH, "if (pKF->NLeft != -1 || (int)vpMatched.size() != pKF->N) continue;", "if ((int)vpMatched.size() != pKF->N) continue;", F_SIM3, "SearchByProjection(Sim3), many: a rig key frame takes the batched route")
+M(2040, FH, "return !p || p->isBad() || taken[row].count(p) != 0; }", "return !p || taken[row].count(p) != 0; }", F_SIM3, "SearchByProjection(Sim3), many: bad points are searched")
+M(2041, FH, "return !p || p->isBad() || taken[row].count(p) != 0; }", "return !p || p->isBad(); }", F_SIM3, "SearchByProjection(Sim3), many: points already matched are searched")
+M(2042, FH, "occupied.back()[i] = vpMatched[i] != nullptr;", "occupied.back()[i] = 0;", F_SIM3, "SearchByProjection(Sim3), many: matched keypoints are free")
+M(2043, FH, "s.s2 = x.scale(); s.second = 1;", "s.s2 = x.scale(); s.second = 2;", F_MW, "SecondQuaternion: a Sim3 applied as an SE3")
+M(2044, FH, "s.s2 = 1.0f; s.second = 2;", "s.s2 = 1.0f; s.second = 1;", F_MW, "SecondQuaternion: an SE3 applied as a Sim3")
+# SearchByBoW
+M(2045, FH, "if (F.Nleft == -1 && !pKF->mpCamera2 && !pKF->mFeatVec.empty()) {", "if (F.Nleft == -1 && !pKF->mpCamera2) {", F_MW + F_CACHE[1:2], "SearchByBoW(KeyFrame, Frame): a key frame without BoW takes the resident route", ROUTE)
+M(2046, FH, "if (F.Nleft == -1 && !pKF->mpCamera2 && !pKF->mFeatVec.empty()) {", "if (!pKF->mpCamera2 && !pKF->mFeatVec.empty()) {", F_MW, "SearchByBoW(KeyFrame, Frame): a rig frame takes the resident route")
+M(2047, FH, "if (F.Nleft == -1 && !pKF->mpCamera2 && !pKF->mFeatVec.empty()) {", "if (F.Nleft == -1 && !pKF->mFeatVec.empty()) {", F_MW, "SearchByBoW(KeyFrame, Frame): a rig key frame takes the resident route")
+M(2048, FH, "k1.present[i] = vpMapPointsKF[i] && !vpMapPointsKF[i]->isBad();", "k1.present[i] = vpMapPointsKF[i] != nullptr;", F_MW, "SearchByBoW(KeyFrame, Frame), uploaded form: bad points take part")
+M(2049, FH, "good[i][j] = mps[i][j] && !mps[i][j]->isBad();", "good[i][j] = mps[i][j] != nullptr;", F_MW, "SearchByBoW(KeyFrame, Frame), resident form: bad points take part")
+M(2051, FH, "const size_t lim1 = pKF1->NLeft != -1 ?", "const size_t lim1 = pKF1->NLeft == -1 ?", F_MW, "SearchByBoW(KeyFrame, KeyFrame): camera 2's features of key frame 1 take part")
+M(2052, FH, "lim2 = pKF2->NLeft != -1 ?", "lim2 = pKF2->NLeft == -1 ?", F_MW, "SearchByBoW(KeyFrame, KeyFrame): camera 2's features of key frame 2 take part")
+M(2053, FH, "k1.present[i] = vpMapPoints1[i] && !vpMapPoints1[i]->isBad();", "k1.present[i] = vpMapPoints1[i] != nullptr;", F_MW, "SearchByBoW(KeyFrame, KeyFrame): bad points of key frame 1 take part")
+M(2054, FH, "k2.present[i] = vpMapPoints2[i] && !vpMapPoints2[i]->isBad();", "k2.present[i] = vpMapPoints2[i] != nullptr;", F_MW, "SearchByBoW(KeyFrame, KeyFrame): bad points of key frame 2 take part")
+M(2055, FH, "&k1.v, &k2.v, mfNNratio, 1, mbCheckOrientation, m12.data(), &nmatches));", "&k1.v, &k2.v, mfNNratio, 0, mbCheckOrientation, m12.data(), &nmatches));", F_MW,
+  "SearchByBoW(KeyFrame, Frame), uploaded form: the key-frame pair's threshold (< TH_LOW)")
+M(2056, FH, "&k1.v, &k2.v, mfNNratio, 0, mbCheckOrientation, m12.data(), &nmatches));", "&k1.v, &k2.v, mfNNratio, 1, mbCheckOrientation, m12.data(), &nmatches));", F_MW,
+  "SearchByBoW(KeyFrame, KeyFrame): the frame form's threshold (<= TH_LOW)")
+M(2057, FH, "k2.data(), nullptr, mfNNratio, 1, mbCheckOrientation, m12p.data(), counts.data());", "k2.data(), nullptr, mfNNratio, 0, mbCheckOrientation, m12p.data(), counts.data());", F_MW,
+  "SearchByBoW(KeyFrame, Frame), resident form: the key-frame pair's threshold (< TH_LOW)")
+M(2058, FH, "{ vnMatches12[i] = m12[i]; vbPrevMatched[i].x = prev[2 * i]; vbPrevMatched[i].y = prev[2 * i + 1]; }", "{ vnMatches12[i] = m12[i]; }", F_MW, "SearchForInitialization: vbPrevMatched not written back")
+# SearchForTriangulation
+M(2060, FH, "if (pKF1->N > 0 && !pKF1->mFeatVec.empty() && !pKF2->mFeatVec.empty()) {", "if (pKF1->N > 0 && !pKF1->mFeatVec.empty()) {", F_MW, "SearchForTriangulation: a second key frame without BoW takes the resident route", ROUTE)
+M(2061, FH, "mp1[i] = pKF1->GetMapPoint(i) != nullptr;", "mp1[i] = 0;", F_MW, "SearchForTriangulation, resident form: features of key frame 1 with a point are searched")
+M(2062, FH, "mp2[j][i] = pKF2->GetMapPoint(i) != nullptr;", "mp2[j][i] = 0;", F_MW, "SearchForTriangulation, resident form: features of key frame 2 with a point are candidates")
+M(2064, FH, "kb.nleft1 = rig ? pKF1->NLeft : -1;", "kb.nleft1 = -1;", F_MW, "FillKB8Pair: key frame 1 of a rig pair judged as one camera")
+M(2065, FH, "put(0, T1w * Tw2); put(1, T1w * Twr2);", "put(0, T1w * Tw2); put(1, T1w * Tw2);", F_MW, "FillKB8Pair: Tlr takes the left-left transform")
+M(2067, FH, "if (pKF1->NLeft != -1) FillAllKeys(*pKF1, pKF1->NLeft, pKF1->N, k1);", "", F_MW, "SearchForTriangulation, fisheye, uploaded form: a rig key frame's keypoints from mvKeysUn")
+M(2068, FH, "if (pKF->NLeft != -1) FillAllKeys(*pKF, pKF->NLeft, pKF->N, k);      // a rig", "     // a rig", F_MW + F_CACHE[4:6], "ResidentKeyFrames::Get: a rig key frame's keypoints from mvKeysUn")
+# SearchBySim3
+M(2070, FH, "if (!partner) continue;\n            paired[0][i] = 1;", "if (!partner) continue;", F_MW, "SearchBySim3: a point of key frame 1 that has a partner is searched")
+M(2071, FH, "if (j >= 0 && j < n[1]) paired[1][j] = 1;", "if (j >= 0 && j < n[1]) paired[1][j] = 0;", F_MW, "SearchBySim3: the partner in key frame 2 is searched")
+M(2072, FH, "if (pMP && !paired[side][i] && !pMP->isBad()) pts.take(i, pMP, false);", "if (pMP && !pMP->isBad()) pts.take(i, pMP, false);", F_MW, "SearchBySim3: paired points are searched")
+M(2073, FH, "if (pMP && !paired[side][i] && !pMP->isBad()) pts.take(i, pMP, false);", "if (pMP && !paired[side][i]) pts.take(i, pMP, false);", F_MW, "SearchBySim3: bad points are searched")
+M(2074, FH, "const Sim3T across[2] = {S12.inverse(), S12};", "const Sim3T across[2] = {S12, S12.inverse()};", F_MW, "SearchBySim3: the two directions' transforms swapped")
+M(2075, FH, "spec.depth_test = 1; spec.dist_mode = 1; spec.distance_test = 1;", "spec.depth_test = 1; spec.dist_mode = 0; spec.distance_test = 1;", F_MW, "SearchBySim3: the range from the camera centre instead of |p_c|")
+# Fuse, one key frame
+M(2080, FH, "if (pMP && !pMP->isBad() && !pMP->IsInKeyFrame(pKF)) pts.take(i, pMP, true);", "if (pMP && !pMP->IsInKeyFrame(pKF)) pts.take(i, pMP, true);", F_FUSE, "Fuse, head: bad points are projected", TWICE)
+M(2081, FH, "if (pMP && !pMP->isBad() && !pMP->IsInKeyFrame(pKF)) pts.take(i, pMP, true);", "if (pMP && !pMP->isBad()) pts.take(i, pMP, true);", F_FUSE, "Fuse, head: points of the key frame are projected", TWICE)
+M(2082, FH, "if (!incoming || !ps.valid[i] || best[i] < 0 || incoming->isBad() || incoming->IsInKeyFrame(pKF)) continue;",
+  "if (!incoming || !ps.valid[i] || best[i] < 0 || incoming->IsInKeyFrame(pKF)) continue;", F_FUSE, "Fuse, replay: a point that an earlier merge made bad is merged")
+M(2083, FH, "if (!incoming || !ps.valid[i] || best[i] < 0 || incoming->isBad() || incoming->IsInKeyFrame(pKF)) continue;",
+  "if (!incoming || !ps.valid[i] || best[i] < 0 || incoming->isBad()) continue;", F_FUSE, "Fuse, replay: a point that an earlier merge put into the key frame is merged")
+M(2084, FH, "resident->Observations() > incoming->Observations() ? resident : incoming;\n                (keep == resident ? incoming : resident)->Replace(keep);\n            }\n            merged++;",
+  "resident->Observations() >= incoming->Observations() ? resident : incoming;\n                (keep == resident ? incoming : resident)->Replace(keep);\n            }\n            merged++;", F_FUSE,
+  "Fuse: with equal observations the resident point survives")
+M(2085, FH, "if (resident && !resident->isBad()) {           // two points for one keypoint", "if (resident) {           // two points for one keypoint", F_FUSE, "Fuse: a bad resident point is merged with")
+M(2086, FH, "if (best[i] >= 0) best[i] += pKF->NLeft;", "if (best[i] >= 0) best[i] += 0;", F_FUSE, "Fuse(bRight): the keypoint index without + NLeft")
+M(2087, FH, "bRight ? Spec(pKF->GetRightPose(), pKF->mpCamera2,", "bRight ? Spec(pKF->GetPose(), pKF->mpCamera2,", F_FUSE, "Fuse(bRight): camera 1's pose")
+M(2088, FH, "if (bRight) SpecCentre(spec, pKF->GetRightCameraCenter()); else", "if (!bRight) SpecCentre(spec, pKF->GetRightCameraCenter()); else", F_FUSE, "Fuse: the two cameras' centres swapped")
+M(2089, FH, "spec.angle_test = 1; spec.bf = pKF->mbf;\n        pts.project(spec);", "spec.angle_test = 0; spec.bf = pKF->mbf;\n        pts.project(spec);", F_FUSE, "Fuse: the viewing-angle test switched off")
+M(2090, FH, "ps.view(), th, 1, pKF->mvInvLevelSigma2.data(), best.data(), nullptr));", "ps.view(), th, 0, pKF->mvInvLevelSigma2.data(), best.data(), nullptr));", F_FUSE, "Fuse: the chi-square gate switched off")
+M(2091, FH, "if (!there) { point->AddObservation(kf, slot); kf->AddMapPoint(point, slot); }", "if (!there) { kf->AddMapPoint(point, slot); }", F_FUSE, "Attach: AddObservation dropped")
+M(2092, FH, "if (!there) { point->AddObservation(kf, slot); kf->AddMapPoint(point, slot); }", "if (!there) { point->AddObservation(kf, slot); }", F_FUSE, "Attach: AddMapPoint dropped")
+M(2093, FH, "if (!pMP->isBad() && !inKeyFrame.count(pMP)) pts.take(i, pMP, true);", "if (!inKeyFrame.count(pMP)) pts.take(i, pMP, true);", F_FUSE, "Fuse(Sim3), head: bad points are projected")
+M(2094, FH, "if (!pMP->isBad() && !inKeyFrame.count(pMP)) pts.take(i, pMP, true);", "if (!pMP->isBad()) pts.take(i, pMP, true);", F_FUSE, "Fuse(Sim3), head: points of the key frame are projected")
+M(2095, FH, "if (!ps.valid[i] || best[i] < 0 || vpPoints[i]->isBad()) continue;", "if (!ps.valid[i] || best[i] < 0) continue;", F_FUSE, "Fuse(Sim3), replay: the isBad test removed",
+  "equivalent: the head lets only points through that are not bad, ps.valid is 0 for every other, and nothing between head and replay of this overload changes a point's state "
+  "(Attach adds an observation; Replace is the caller's, after the call)")
+M(2096, FH, "if (resident && !resident->isBad()) vpReplacePoint[i] = resident;\n            merged++;", "if (resident) vpReplacePoint[i] = resident;\n            merged++;", F_FUSE, "Fuse(Sim3): a bad resident point is reported")
+# (2093 and 2095 are the two places of ONE test: each alone is equivalent because the other still stands.  2097 takes both away)
+M(2097, FH, "if (!pMP->isBad() && !inKeyFrame.count(pMP)) pts.take(i, pMP, true);", "if (!inKeyFrame.count(pMP)) pts.take(i, pMP, true);", F_FUSE, "Fuse(Sim3): isBad tested at neither place",
+  more=[("if (!ps.valid[i] || best[i] < 0 || vpPoints[i]->isBad()) continue;", "if (!ps.valid[i] || best[i] < 0) continue;")])
+# Fuse, many key frames
+M(2100, FH, "return !p || p->isBad() || p->IsInKeyFrame(pKF); };", "return !p || p->IsInKeyFrame(pKF); };", F_FUSE, "Fuse, many: bad points are searched", TWICE)
+M(2101, FH, "return !p || p->isBad() || p->IsInKeyFrame(pKF); };", "return !p || p->isBad(); };", F_FUSE, "Fuse, many: points of the key frame are searched", TWICE)
+M(2102, FH, "if (pKF->NLeft != -1) continue;\n                OrbmProjection spec = Spec(pKF->GetPose(), pKF->mpCamera, *pKF, /*IsInImage*/ 1);",
+  "OrbmProjection spec = Spec(pKF->GetPose(), pKF->mpCamera, *pKF, /*IsInImage*/ 1);", F_FUSE, "Fuse, many: a rig key frame takes the batched route")
+M(2103, FH, "if (pKF->NLeft != -1) counts[k] += Fuse(pKF, vpMapPoints, true);", "", F_FUSE, "Fuse, many: a rig key frame's second pass dropped")
+M(2104, FH, "if (pKF->NLeft != -1) counts[k] += Fuse(pKF, vpMapPoints, true);", "if (pKF->NLeft != -1) counts[k] += Fuse(pKF, vpMapPoints, th, true);", F_FUSE,
+  "Fuse, many: a rig key frame's second pass searches camera 2 (the reference's call site passes `true` as th)")
+M(2105, FH, "if (batched) job.NoteChangedDescriptors();", "", F_FUSE, "Fuse, many: no refresh behind a key frame that took the unbatched route")
+M(2106, FH, "if (!incoming || best[i] < 0 || incoming->isBad() || incoming->IsInKeyFrame(pKF)) continue;", "if (!incoming || best[i] < 0 || incoming->IsInKeyFrame(pKF)) continue;", F_FUSE,
+  "Fuse, many, replay: a point that an earlier merge made bad is merged")
+M(2107, FH, "if (!incoming || best[i] < 0 || incoming->isBad() || incoming->IsInKeyFrame(pKF)) continue;", "if (!incoming || best[i] < 0 || incoming->isBad()) continue;", F_FUSE,
+  "Fuse, many, replay: a point that an earlier merge put into the key frame is merged")
+M(2108, FH, "resident->Observations() > incoming->Observations() ? resident : incoming;\n                    (keep == resident ? incoming : resident)->Replace(keep);\n                    job.NoteChangedDescriptorOf(keep);",
+  "resident->Observations() >= incoming->Observations() ? resident : incoming;\n                    (keep == resident ? incoming : resident)->Replace(keep);\n                    job.NoteChangedDescriptorOf(keep);", F_FUSE,
+  "Fuse, many: with equal observations the resident point survives")
+M(2109, FH, "job.NoteChangedDescriptorOf(keep);       // (either", ";       // (either", F_FUSE, "Fuse, many: the survivor of a Replace is not searched again")
+M(2110, FH, "job.Refresh(row, excluded);\n            const int* best = job.Best(row);", "const int* best = job.Best(row);", F_FUSE, "Fuse, many: no Refresh in front of a key frame's replay")
+M(2111, FH, "if (resident && !resident->isBad()) {\n                    MapPointT* keep", "if (resident) {\n                    MapPointT* keep", F_FUSE, "Fuse, many: a bad resident point is merged with")
+M(2112, FH, "return vpPoints[i]->isBad() || job.Holds(pKF, vpPoints[i]); };", "return job.Holds(pKF, vpPoints[i]); };", F_FUSE, "Fuse(Sim3), many: bad points are searched",
+  "equivalent: the replay loop of this overload tests vpPoints[i]->isBad() again before anything is written, and a bad point's search result is read nowhere else")
+M(2113, FH, "return vpPoints[i]->isBad() || job.Holds(pKF, vpPoints[i]); };", "return vpPoints[i]->isBad(); };", F_FUSE, "Fuse(Sim3), many: points of the key frame are searched",
+  "equivalent: the replay loop reads pKF->GetMapPoints() at its own moment, which holds whatever Holds held, and skips those points")
+M(2114, FH, "job.Refresh(row, excluded);\n                const int* best = job.Best(row);", "const int* best = job.Best(row);", F_FUSE, "Fuse(Sim3), many: no Refresh in front of a key frame's replay")
+M(2115, FH, "if (best[i] < 0 || vpPoints[i]->isBad() || inKeyFrame.count(vpPoints[i])) continue;", "if (best[i] < 0 || inKeyFrame.count(vpPoints[i])) continue;", F_FUSE,
+  "Fuse(Sim3), many, replay: a point that an earlier hook made bad is attached")
+M(2116, FH, "if (best[i] < 0 || vpPoints[i]->isBad() || inKeyFrame.count(vpPoints[i])) continue;", "if (best[i] < 0 || vpPoints[i]->isBad()) continue;", F_FUSE,
+  "Fuse(Sim3), many, replay: a point that an earlier hook put into the key frame is attached")
+M(2117, FH, "if (resident && !resident->isBad()) vpReplacePoint[i] = resident;\n                    counts[k]++;", "if (resident) vpReplacePoint[i] = resident;\n                    counts[k]++;", F_FUSE,
+  "Fuse(Sim3), many: a bad resident point is reported")
+M(2118, FH, "if (batched) for (int i = 0; i < M; i++) if (vpReplacePoint[i] && !vpPoints[i]->isBad()) job.NoteChangedDescriptorOf(vpPoints[i]);", "", F_FUSE,
+  "Fuse(Sim3), many: what the hook changed is not searched again")
+M(2119, FH, "if (pKF->NLeft != -1) continue;\n                const SE3T pose = RigidPart<SE3T>(vScw[k]);", "const SE3T pose = RigidPart<SE3T>(vScw[k]);", F_FUSE, "Fuse(Sim3), many: a rig key frame takes the batched route")
+# FuseBatch
+M(2121, FH, "heldOf = nullptr;\n            OrbmWorldPointView view = {n,", "OrbmWorldPointView view = {n,", F_FUSE, "FuseBatch::Run: the held set of the last key frame stays valid after the exclusion loop")
+M(2122, FH, "heldOf = nullptr;\n            for (int r = 0; r < rows; r++) for (int j = 0; j < n; j++) skip", "for (int r = 0; r < rows; r++) for (int j = 0; j < n; j++) skip", F_FUSE,
+  "FuseBatch::Run: the held set is not forgotten in front of the exclusion loop")
+# (2121 and 2122 are likewise a pair: either reset alone forgets the held set between two runs.  2123 takes both away)
+M(2123, FH, "heldOf = nullptr;\n            OrbmWorldPointView view = {n,", "OrbmWorldPointView view = {n,", F_FUSE, "FuseBatch::Run: the held set is never forgotten",
+  more=[("heldOf = nullptr;\n            for (int r = 0; r < rows; r++) for (int j = 0; j < n; j++) skip", "for (int r = 0; r < rows; r++) for (int j = 0; j < n; j++) skip")])
+M(2124, FH, "{ memcpy(&desc[32 * (size_t)i], now, 32); stale.push_back(i); }", "{ stale.push_back(i); }", F_FUSE, "FuseBatch::NoteChangedDescriptor: the new descriptor is not kept")
+M(2125, FH, "{ memcpy(&desc[32 * (size_t)i], now, 32); stale.push_back(i); }", "{ memcpy(&desc[32 * (size_t)i], now, 32); }", F_FUSE, "FuseBatch::NoteChangedDescriptor: the point is not marked stale")
+M(2126, FH, "if (points[i] && !points[i]->isBad()) NoteChangedDescriptor(i); }", "if (points[i]) NoteChangedDescriptor(i); }", F_FUSE, "FuseBatch::NoteChangedDescriptors: bad points are compared too",
+  "equivalent: a bad point is excluded by every later search and replay (`excluded`, the replay's own isBad), so whether its row is searched again changes nothing that is read")
+M(2128, FH, "for (int j = 0; j < n; j++) row[subset[j]] = -1;", "", F_FUSE, "FuseBatch::Run: a point searched again keeps its old candidate when the new search finds none")
+M(2129, FH, "for (auto it = range.first; it != range.second; ++it) NoteChangedDescriptor(it->second);", "if (range.first != range.second) NoteChangedDescriptor(range.first->second);", F_FUSE,
+  "FuseBatch::NoteChangedDescriptorOf: only the first place of a point listed twice")
+# ResidentKeyFrames
+M(2140, FH, "return id == o.id && n == o.n && nodes == o.nodes && print == o.print; }", "return n == o.n && nodes == o.nodes && print == o.print; }", F_CACHE, "ResidentKeyFrames::Tag: mnId not compared")
+M(2141, FH, "return id == o.id && n == o.n && nodes == o.nodes && print == o.print; }", "return id == o.id && nodes == o.nodes && print == o.print; }", F_CACHE, "ResidentKeyFrames::Tag: N not compared")
+M(2142, FH, "return id == o.id && n == o.n && nodes == o.nodes && print == o.print; }", "return id == o.id && n == o.n && print == o.print; }", F_CACHE, "ResidentKeyFrames::Tag: the size of mFeatVec not compared")
+M(2143, FH, "return id == o.id && n == o.n && nodes == o.nodes && print == o.print; }", "return id == o.id && n == o.n && nodes == o.nodes; }", F_CACHE, "ResidentKeyFrames::Tag: the fingerprint not compared")
+M(2144, FH, "if (pKF->N > 0 && pKF->mFeatVec.empty()) { transient = r; return r; }", "", F_CACHE, "ResidentKeyFrames::Get: a key frame without BoW is cached")
+M(2145, FH, "if (transient) { orbm_keyframe_destroy(transient); transient = nullptr; }\n            BowStore k;", "BowStore k;", F_CACHE, "ResidentKeyFrames::Get: the previous transient entry is not released (a leak)")
+M(2146, FH, "if (device != Device()) { Clear(); device = Device(); }\n            const Tag tag = {(long long)pKF->mnId, (long long)pKF->N, (long long)pKF->mFeatVec.size(), Fingerprint(pKF)};\n            auto it = m.find(pKF);\n            if (it != m.end()) {\n                if",
+  "if (device != Device()) { device = Device(); }\n            const Tag tag = {(long long)pKF->mnId, (long long)pKF->N, (long long)pKF->mFeatVec.size(), Fingerprint(pKF)};\n            auto it = m.find(pKF);\n            if (it != m.end()) {\n                if",
+  F_CACHE, "ResidentKeyFrames::Get: the cache survives a change of device")
+M(2148, FH, "{ it->second.stamp = ++clock; return it->second.dev; }", "{ return it->second.dev; }", F_CACHE, "ResidentKeyFrames::Get: a hit does not renew the entry's age")
+M(2149, FH, "if (capacity == 0 || m.size() <= capacity) return;", "if (capacity == 0 || m.size() < capacity) return;", F_CACHE, "ResidentKeyFrames::Trim: a cache of exactly `capacity` entries is trimmed")
+M(2150, FH, "m.size() - capacity + capacity / 8;", "m.size() - capacity + capacity / 9;", F_CACHE, "ResidentKeyFrames::Trim: capacity / 9 below the bound")
+M(2151, FH, "byAge.begin() + (drop < byAge.size() ? drop : byAge.size() - 1), byAge.end());", "byAge.begin() + (drop < byAge.size() ? drop - 1 : byAge.size() - 1), byAge.end());", F_CACHE,
+  "ResidentKeyFrames::Trim: nth_element at drop - 1",
+  "equivalent: drop >= 1 here; with the nth element at index drop - 1 the entries in front of it are not younger than it, so [0, drop) is the same set of the `drop` oldest entries (stamps are unique)")
+M(2152, FH, "std::nth_element(byAge.begin(), byAge.begin() + (drop < byAge.size() ? drop : byAge.size() - 1), byAge.end());", "", F_CACHE, "ResidentKeyFrames::Trim: entries dropped in address order, not by age")
+M(2154, FH, "if (it->second.dev != dev) orbm_keyframe_destroy(it->second.dev);", "", F_CACHE, "ResidentKeyFrames::Adopt: the entry it replaces is not destroyed (a leak)")
+M(2156, FH, "SetCapacity(n ? n : 1); }", "SetCapacity(n); }", F_CACHE, "SetImplicitCapacity(0) sets 0, which the next ImplicitCache() turns into 256")
+M(2157, FH, "if (c.Capacity() == 0) c.SetCapacity((size_t)kImplicitCacheEntries);", "", F_CACHE, "ImplicitCache: unbounded")
+M(2158, FH, "if (capacity == 0 || m.size() <= capacity) return;", "if (m.size() <= capacity) return;", F_CACHE, "ResidentKeyFrames::Trim: capacity 0 empties the cache")
+# occupancy
+M(2165, FH, "F.mvpMapPoints[first + i]->Observations() > 0;", "F.mvpMapPoints[first + i]->Observations() >= 0;", F_MW, "FillOccupancy: a point without observations occupies under OccupiedWithObservations")
+M(2166, FH, "FillOccupancy(F, NL, NR, occ, s.r.occ);", "FillOccupancy(F, 0, NR, occ, s.r.occ);", F_MW, "FillRig: camera 2's occupancy read at camera 1's slots")
+# the stereo free functions
+F_TAIL = [FG, MOCK]
+M(2170, FH, "F.mvuRight = std::vector<float>(F.Nleft, -1);", "F.mvuRight = std::vector<float>(F.Nleft, 0);", F_TAIL, "ComputeStereoFishEyeMatches: mvuRight reset to 0")
+M(2171, FH, "F.mnCloseMPs = 0;", "", F_TAIL, "ComputeStereoFishEyeMatches: mnCloseMPs not reset")
+M(2172, FH, "if (l2r[i] >= 0) F.mvStereo3Dpoints[i] =", "if (l2r[i] > 0) F.mvStereo3Dpoints[i] =", F_TAIL, "ComputeStereoFishEyeMatches: a match with right keypoint 0 gets no 3-D point")
+M(2173, FH, "F.mvRightToLeftMatch.assign(r2l.begin(), r2l.begin() + F.Nright);", "F.mvRightToLeftMatch.assign(l2r.begin(), l2r.begin() + F.Nright);", F_TAIL, "ComputeStereoFishEyeMatches: mvRightToLeftMatch from the left table")
+
+FK = "include/orb_slam3_amd/KeyFrameDatabase.h"
+M(2200, FK, "e.n++;", "e.n = 1;", F_KFDB, "add: a second add of the same key frame is not counted")
+M(2201, FK, "if (--it->second.n == 0) mAdds.erase(it);", "mAdds.erase(it);", F_KFDB, "erase: the first erase forgets a key frame that was added twice")
+M(2202, FK, "if (--it->second.n == 0) mAdds.erase(it);", "if (--it->second.n <= 1) mAdds.erase(it);", F_KFDB, "erase: a key frame with one surviving add is forgotten")
+M(2203, FK, "if (it->second.mapOf(it->first) == (const void*)pMap)", "if (it->second.mapOf(it->first) != (const void*)pMap)", F_KFDB, "clearMap: the other maps' key frames are erased")
+M(2204, FK, "if (pKFi->mnRelocQuery != F->mnId) { pKFi->mnRelocWords = 0;", "if (pKFi->mnRelocQuery != F->mnId) {", F_KFDB, "reloc: the word counter is not reset")
+M(2205, FK, "pKFi->mnRelocQuery = F->mnId; lKFsSharingWords.push_back(pKFi); }\n            else repeat = true;", "pKFi->mnRelocQuery = F->mnId; lKFsSharingWords.push_back(pKFi); }", F_KFDB, "reloc: a repeat query id is not noticed")
+M(2206, FK, "if (k->mnRelocWords > maxCommonWords) maxCommonWords = k->mnRelocWords;\n        int minCommonWords = maxCommonWords * 0.8f;", "if (k->mnRelocWords > maxCommonWords) maxCommonWords = k->mnRelocWords;\n        int minCommonWords = maxCommonWords * 0.7f;", F_KFDB, "reloc: 0.7f of the most common words")
+M(2207, FK, "if (pKFi->mnRelocWords > minCommonWords) {", "if (pKFi->mnRelocWords >= minCommonWords) {", F_KFDB, "reloc: exactly minCommonWords is enough")
+M(2208, FK, "if (pKF2->mnRelocQuery != F->mnId) continue;", "", F_KFDB, "reloc: a neighbour that this query did not stamp adds its old score")
+M(2209, FK, "accScore += pKF2->mRelocScore;", "", F_KFDB, "reloc: the neighbours' scores are not accumulated")
+M(2210, FK, "if (pKF2->mRelocScore > bestScore) { pBestKF = pKF2;", "if (pKF2->mRelocScore >= bestScore) { pBestKF = pKF2;", F_KFDB, "reloc: a neighbour with the same score becomes the group's key frame")
+M(2211, FK, "{ pBestKF = pKF2; bestScore = pKF2->mRelocScore; }", "{ pBestKF = pKF2; }", F_KFDB, "reloc: the best score of the group is not raised")
+M(2212, FK, "if (accScore > bestAccScore) bestAccScore = accScore;\n        }\n        float minScoreToRetain = 0.75f * bestAccScore;", "if (accScore < bestAccScore) bestAccScore = accScore;\n        }\n        float minScoreToRetain = 0.75f * bestAccScore;", F_KFDB,
+  "reloc: the best accumulated score is never raised")
+M(2213, FK, "float minScoreToRetain = 0.75f * bestAccScore;", "float minScoreToRetain = 0.8f * bestAccScore;", F_KFDB, "reloc: 0.8f of the best accumulated score")
+M(2214, FK, "if (si > minScoreToRetain) {", "if (si >= minScoreToRetain) {", F_KFDB, "reloc: exactly 0.75f of the best accumulated score is enough")
+M(2215, FK, "if (pKFi->GetMap() != pMap) continue;", "", F_KFDB, "reloc: candidates of other maps are returned")
+M(2216, FK, "if (!spAlreadyAddedKF.count(pKFi)) { vpRelocCandidates.push_back(pKFi);", "{ vpRelocCandidates.push_back(pKFi);", F_KFDB, "reloc: a key frame that leads two groups is returned twice")
+M(2217, FK, "if (repeat) { Query(bow, excluded, all, 1); src = &all; }", "", F_KFDB, "Scores: no rescoring after a repeat query id")
+M(2220, FK, "if (pKFi->mnPlaceRecognitionQuery != pKF->mnId) { pKFi->mnPlaceRecognitionWords = 0;", "if (pKFi->mnPlaceRecognitionQuery != pKF->mnId) {", F_KFDB, "nbest: the word counter is not reset")
+M(2221, FK, "if (c->mnPlaceRecognitionQuery != pKF->mnId) c->mnPlaceRecognitionWords = 1;", "if (c->mnPlaceRecognitionQuery != pKF->mnId) c->mnPlaceRecognitionWords = shared;", F_KFDB,
+  "nbest: a connected key frame's counter holds its shared words, not the reference's single 1")
+M(2222, FK, "else c->mnPlaceRecognitionWords += shared;", "else c->mnPlaceRecognitionWords += 1;", F_KFDB, "nbest: a connected key frame stamped earlier counts one word")
+M(2223, FK, "SharedWords(pKF->mBowVec, c->mBowVec) * it->second.n;", "SharedWords(pKF->mBowVec, c->mBowVec);", F_KFDB, "nbest: a connected key frame that was added twice counts its words once")
+M(2224, FK, "if (shared == 0) continue;", "", F_KFDB, "nbest: a connected key frame without shared words gets the 1")
+M(2225, FK, "if (k->mnPlaceRecognitionWords > maxCommonWords) maxCommonWords = k->mnPlaceRecognitionWords;\n        int minCommonWords = maxCommonWords * 0.8f;",
+  "if (k->mnPlaceRecognitionWords > maxCommonWords) maxCommonWords = k->mnPlaceRecognitionWords;\n        int minCommonWords = maxCommonWords * 0.7f;", F_KFDB, "nbest: 0.7f of the most common words")
+M(2226, FK, "if (pKFi->mnPlaceRecognitionWords > minCommonWords) {", "if (pKFi->mnPlaceRecognitionWords >= minCommonWords) {", F_KFDB, "nbest: exactly minCommonWords is enough")
+M(2227, FK, "if (pKF2->mnPlaceRecognitionQuery != pKF->mnId) continue;", "", F_KFDB, "nbest: a neighbour that this query did not stamp adds its old score")
+M(2228, FK, "if (pKF2->mPlaceRecognitionScore > bestScore) { pBestKF = pKF2;", "if (pKF2->mPlaceRecognitionScore >= bestScore) { pBestKF = pKF2;", F_KFDB, "nbest: a neighbour with the same score becomes the group's key frame")
+M(2230, FK, "lAccScoreAndMatch.sort([]", "lAccScoreAndMatch.reverse(); lAccScoreAndMatch.sort([]", F_KFDB, "nbest: equal accumulated scores in the reverse order of the list")
+M(2231, FK, "while (i < lAccScoreAndMatch.size() && ((int)vpLoopCand.size() < nNumCandidates || (int)vpMergeCand.size() < nNumCandidates)) {",
+  "while (i < lAccScoreAndMatch.size() && ((int)vpLoopCand.size() < nNumCandidates && (int)vpMergeCand.size() < nNumCandidates)) {", F_KFDB, "nbest: the walk ends when ONE of the lists is full")
+M(2232, FK, "if (pKF->GetMap() == pKFi->GetMap() && (int)vpLoopCand.size() < nNumCandidates) vpLoopCand.push_back(pKFi);", "if (pKF->GetMap() == pKFi->GetMap() && (int)vpLoopCand.size() <= nNumCandidates) vpLoopCand.push_back(pKFi);", F_KFDB,
+  "nbest: one loop candidate more than asked")
+M(2233, FK, "(int)vpMergeCand.size() < nNumCandidates && !pKFi->GetMap()->IsBad()) vpMergeCand.push_back(pKFi);", "(int)vpMergeCand.size() <= nNumCandidates && !pKFi->GetMap()->IsBad()) vpMergeCand.push_back(pKFi);", F_KFDB,
+  "nbest: one merge candidate more than asked")
+M(2234, FK, " && !pKFi->GetMap()->IsBad()) vpMergeCand.push_back(pKFi);", ") vpMergeCand.push_back(pKFi);", F_KFDB, "nbest: a key frame of a bad map is a merge candidate")
+M(2235, FK, "else if (pKF->GetMap() != pKFi->GetMap() && (int)vpMergeCand.size()", "else if ((int)vpMergeCand.size()", F_KFDB, "nbest: a key frame of the query's map beyond the loop list's end becomes a merge candidate")
+M(2236, FK, "if (!spAlreadyAddedKF.count(pKFi)) {\n                if (pKF->GetMap()", "{\n                if (pKF->GetMap()", F_KFDB, "nbest: a key frame that leads two groups is listed twice")
+M(2237, FK, "for (KeyFrameT* k : spConnectedKF) excluded.push_back(Key(k));", "", F_KFDB, "nbest: connected key frames are not excluded from the query")
+M(2238, FK, "pKFi->mnPlaceRecognitionQuery = pKF->mnId; lKFsSharingWords.push_back(pKFi); }\n            else repeat = true;", "pKFi->mnPlaceRecognitionQuery = pKF->mnId; lKFsSharingWords.push_back(pKFi); }", F_KFDB,
+  "nbest: a repeat query id is not noticed")
+
+FX = "include/orb_slam3_amd/ORBextractor.h"
+M(2260, FX, "attempt < 2 && rc == ORBX_E_CAPACITY; attempt++)", "attempt < 1 && rc == ORBX_E_CAPACITY; attempt++)", F_EXTRACT, "ORBextractor: no second attempt after ORBX_E_CAPACITY")
+M(2261, FX, "const int c = attempt == 0 ? cap : std::max(orbx_max_keypoints(mpHandle), n);", "const int c = cap;", F_EXTRACT, "ORBextractor: the second attempt with the first one's capacity")
+M(2263, FX, "b ? EDGE : 0, RING)", "EDGE, RING)", F_EXTRACT, "SetExportPyramid(false) leaves the device export on")
+M(2264, FX, "mbExportPyramid = b;", "", F_EXTRACT, "SetExportPyramid: the flag is not kept")
+M(2265, FX, "if(_image.empty())\n            return -1;", "if(_image.empty())\n            return 0;", F_EXTRACT, "ORBextractor: an empty image returns 0")
+
+FV = "include/orb_slam3_amd/ORBVocabulary.h"
+M(2280, FV, "v.clear(); fv.clear();", "", F_VOC, "ORBVocabularyAmd::transform: the output vectors are not cleared")
+M(2281, FV, "if (v_) { orbv_destroy(v_); v_ = nullptr; }\n        return", "return", F_VOC, "ORBVocabularyAmd::loadFromTextFile: a second load leaks the first vocabulary")
+
+# notes of the facade block, written after its pass (profiles/emu_mutants_facade/README.md): kept in one place because most of them argue from the same few facts
+_SAME_RIG = ("no reference answer where it differs: the condition is reached with a frame and a key frame of different kinds (a rig frame against a one-camera key frame, or the "
+             "other way round), which the reference never pairs - Tracking builds frames and key frames from one System, all with or all without mpCamera2 (src/Tracking.cc:1132, "
+             "src/KeyFrame.cc:56-77 copies the frame's cameras) - and for two of one kind the other clauses of the line decide alone")
+_FACADE_NOTES = {
+    2019: "no accepted input reaches the difference: camera 2's projection of a point that camera 1 accepted is rejected by the added test only when the point lies BEHIND camera 2 "
+          "(1 / z < 0 after GetRelativePoseTrl()); the Kannala-Brandt model puts such a point at a radius of more than fx * pi / 2 from the principal point (theta > pi / 2, "
+          "csrc/kb8_model.h), outside every key point of an image that is narrower than that on each side of it - and the reference only builds rigs of Kannala-Brandt cameras "
+          "(src/Tracking.cc:1132), whose frames lie inside that radius (752 x 480 at fx = 190 .. 435 in every rig of the suite)",
+    2020: "equivalent but for z = -0.0f: depth_test 1 rejects z < 0, depth_test 2 rejects 1 / z < 0 (csrc/k_search.hip project_point), the same set for every other float "
+          "(1 / z of a negative denormal is -inf); at -0 the reference's own u = fx * x * (1 / z) is an infinity or NaN that it converts to cell indices (src/Frame.cc:720-745): "
+          "there is no defined answer to be compared with",
+    2046: _SAME_RIG, 2047: _SAME_RIG,
+    2055: "unreachable: the one-camera uploaded form is entered only when the first line of the method did not take the resident route, i.e. with pKF->mFeatVec empty (a rig goes to the "
+          "fisheye call below it); without vocabulary nodes on the key frame's side there is no node pair, nothing is compared and the threshold is never read",
+    2067: "unreachable: SearchForTriangulationFisheye is entered only when the resident route was not taken, i.e. when N == 0 or one of the two mFeatVec is empty; without common "
+          "vocabulary nodes no pair of features is compared and the key points are never read",
+    2093: "one of a redundant pair: the replay loop of this overload tests vpPoints[i]->isBad() again before anything is written; a bad point that the head lets through is "
+          "projected, searched and skipped there.  2095 is the other place; the pair as a whole is mutant 2097, which takes both tests away",
+    2121: "one of a redundant pair: Holds is called from the exclusion loop of Run alone, and 2122's reset in front of the loop still forgets the held set between two runs "
+          "(the hooks that change a key frame's points run between them).  The pair as a whole is mutant 2123, which takes both resets away",
+    2122: "the other of the redundant pair of 2121: the reset behind the loop has already forgotten the set when the next Run begins.  Both together: 2123",
+    2123: "equivalent in the result: between two runs the set a key frame holds only grows by points that are not bad (a point leaves a key frame only by being replaced, and "
+          "is bad from then on - excluded by the clause in front of Holds), and a point that has entered since is searched in vain: the replay loop reads "
+          "pKF->GetMapPoints() at its own moment and skips it (the argument of 2113, where Holds goes altogether)",
+    2260: "unreachable: ORBX_E_CAPACITY of orbx_extract needs n > cap, and the first attempt's cap is orbx_max_keypoints() >= the sum over the levels of quota + 3 - before the "
+          "geometry is known that very sum (csrc/orbx_api.cpp:653-657), afterwards kp_total_cap, which is larger (:283) -, while a level never returns more than quota + 3 key points "
+          "(`a full pass never overshoots the quota, a final-round split adds at most 3`, :282); the second attempt exists for a library whose bound changes, not for this one",
+    2261: "unreachable, as 2260: the second attempt is never made",
+    2263: "equivalent in every output: SetExportPyramid(false) clears mbExportPyramid, so operator() never asks for the exported levels; whether the device goes on writing them "
+          "into its export slot is invisible to the caller (tests/cpp/pyramid_export_facade_test.cpp requires mvImagePyramid to keep its views) - it costs the time the switch "
+          "was added to save, which tools/bench_dropin_frame.py measures",
+}
+for _m in MUTANTS:
+    if _m["id"] in _FACADE_NOTES:
+        assert not _m["note"], _m["id"]
+        _m["note"] = _FACADE_NOTES[_m["id"]]
