@@ -1160,6 +1160,44 @@ int orbm_search_by_projection_sim3_batch_map(orbx_extractor* h, int K, const Orb
                                              int* assigned /*[K][cap]*/, int* nmatches /*[K]*/, int* assigned_slot /*[K][cap] or NULL*/);
 int orbm_map_edit_keyframes(orbx_extractor* h, orbm_map* m, int n /* edits (all of one replay) */, const int* row, const int* feat, const int* slot);
 
+/* The stereo map points a key frame is born with, made ON THE DEVICE MAP: the second half of Tracking::CreateNewKeyFrame (src/Tracking.cc:3868-3960;
+ * orbm_keyframe_create_extracted is its first half) and the same loop of Tracking::UpdateLastFrame (:3264-3341), for B frames of h's last extraction.
+ * Read where they are: mvKeysUn and the descriptor rows of the extraction, mvDepth of orbm_stereo_match / orbm_stereo_from_depth, the handle's scale table.
+ *   Selection: the features with mvDepth[i] > 0, ordered as std::sort orders pair<float, int> (by depth, equal depths by index); the loop visits them in
+ * that order, counts every entry it visits and ends behind the first entry j with depth_j > th_depth && j + 1 > max_points.  processed[b] = entries
+ * visited; a visited entry whose keeps byte is 0 creates a point: created[b] of them, feat[b][j] = feature of the j-th, slot[b][j] = free_slots[j].
+ *   Per created point, in the reference's fp32 statements: Frame::UnprojectStereo (src/Frame.cc:1396-1409; x3D = mRwc * x3Dc + mOw as Eigen sums it),
+ * then mode 1 = MapPoint(Pos, pMap, pFrame, idxF) (src/MapPoint.cc:90-128): normal = (Pos - Ow) / |Pos - Ow|, mfMaxDistance = |Pos - Ow| *
+ * mvScaleFactors[octave], mfMinDistance = mfMaxDistance / mvScaleFactors[nLevels - 1], descriptor = row i; mode 0 = MapPoint(Pos, pKF, pMap) +
+ * AddObservation + ComputeDistinctiveDescriptors + UpdateNormalAndDepth (:567-642) for a point with ONE observation: the same but normal =
+ * (0 + normali / |normali|) / 1, i.e. a component -0 becomes +0.  The five fields go into the store at the slot, present and not bad, as orbm_map_update
+ * leaves a slot; with row >= 0 the slot also becomes entry i of that row (KeyFrame::AddMapPoint; a row shorter than the image so far - never set, or
+ * set for fewer features - is lengthened to the image's N with -1).  No other slot, no other row entry and no set built earlier changes.
+ *   Two phases: one workgroup per frame sorts the keys `depth bits << 32 | index` in LDS, cuts the prefix and ranks the creating entries; the 8 B bytes
+ * of counts come down; then ORBX_E_CAPACITY - with created / processed filled for every frame, nothing truncated, nothing written to the store or the rows
+ * - if a frame creates more points than its nfree or than cap, or has more features with a positive depth than the LDS sort holds: 16 384 keys of 8 bytes
+ * = 128 KB of gfx950's 160 KB of LDS per workgroup (such a frame reports created = -1, processed = that count).  Otherwise the second phase writes.
+ *   Blocking; takes the map's mutex; runs on h's stream behind the extraction and the depth producer; staged through h's reused buffers.  The images'
+ * feature counts come down first when a frame names a row or brings keeps (both are N long).  B == 0: ORBX_OK.  ORBX_E_ARG, before any launch, the
+ * message naming the frame: null arguments (feat / slot may be NULL with cap == 0), B < 0, max_points < 0, cap < 0, a mode other than 0 or 1, nothing
+ * extracted yet, `frame` outside the extraction, no depth results for that image on this extraction, orbx_set_undistort since the extraction, a map on
+ * another device, `row` outside the map or an image with more features than kf_row_cap, a free slot outside the map, a slot twice in the call, a row twice.
+ *   Rig frames (Nleft != -1: Frame::UnprojectStereoFishEye, the second row entry through mvLeftToRightMatch) are out of scope: they stay on the host
+ * route (orbm_map_update + orbm_map_edit_keyframes), and depths left by orbm_stereo_fisheye are refused.
+ * (The struct is declared apart from its typedef, as OrbmFrameMap is; its Python mirror is checked by tests/test_stereo_points.py.) */
+struct OrbmStereoPointsFrame {
+    int frame;                             /* image of h's last extraction whose mvKeysUn / mvDepth are read (stereo: the left image) */
+    float Rwc[9], Ow[3];                   /* Frame::mRwc (row-major) and Frame::mOw as Frame::UpdatePoseMatrices left them; mode 0: Ow is also pKF->GetCameraCenter() */
+    const uint8_t* keeps;                  /* [N of that image] 1 = mvpMapPoints[i] != NULL && Observations() >= 1 (the feature keeps its point); NULL = none keeps one */
+    const int* free_slots; int nfree;      /* slots the caller gives to new points: the j-th point CREATED (in the loop's order) takes free_slots[j] */
+    int row;                               /* >= 0: KeyFrame::AddMapPoint - the slot is written at feature i of that row of the map; -1: no row */
+};
+typedef struct OrbmStereoPointsFrame OrbmStereoPointsFrame;
+int orbm_map_stereo_points(orbx_extractor* h, orbm_map* m, int B, const OrbmStereoPointsFrame* frames /*[B]*/,
+                           const float* cam /* [6]: cx, cy, invfx, invfy (as Frame holds them), 2 spare */, float th_depth, int max_points /* 100 */,
+                           int mode /* 0 key-frame points, 1 temporal points */, int* created /*[B]*/, int* processed /*[B]*/, int cap,
+                           int* feat /*[B][cap]*/, int* slot /*[B][cap]*/);
+
 /* Frame::ComputeBoW for B fisheye-rig frames (Nleft != -1, src/Frame.cc:984-997 over the rig Frame's mDescriptors, :1514): frame b = left image
  * lf + b of L's last extraction (camera 1: features [0, Nleft)) followed by right image rf + b of R's (camera 2: features [Nleft, Nleft + Nright)),
  * transformed as ONE set of Nleft + Nright rows - BowVector and FeatureVector equal to transform() on the joined rows.  L == R is allowed (lf = 0,

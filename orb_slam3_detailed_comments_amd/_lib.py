@@ -42,6 +42,7 @@ SYMBOLS = [
     "orbm_map_sets_fetch",
     "orbm_search_for_triangulation_resident_map", "orbm_search_for_triangulation_resident_kb8_map", "orbm_search_by_bow_resident_map", "orbm_search_by_bow_rig_batch_map",
     "orbm_fuse_candidates_batch_map", "orbm_search_by_projection_sim3_batch_map", "orbm_map_edit_keyframes", "orbm_fuse_pairs_batch", "orbm_fuse_pairs_batch_map",
+    "orbm_map_stereo_points",
     "orbv_create", "orbv_load_text", "orbv_destroy", "orbv_words", "orbv_transform", "orbv_transform_extracted", "orbv_fetch", "orbm_search_by_bow_frames_batch",
     "orbv_transform_rig_extracted", "orbm_search_by_bow_rig_batch",
     "orbv_db_create", "orbv_db_destroy", "orbv_db_add", "orbv_db_add_extracted", "orbv_db_erase", "orbv_db_erase_keys", "orbv_db_clear", "orbv_db_size",
@@ -211,6 +212,7 @@ class OrbxLib:
         L.orbm_fuse_pairs_batch_map.argtypes = [vp, i, vp, vp, vp, vp, i, f, i, i, vp, vp, vp, vp, vp, vp]
         L.orbm_search_by_projection_sim3_batch_map.argtypes = [vp, i, vp, vp, i, vp, vp, f, f, i, vp, vp, vp]
         L.orbm_map_edit_keyframes.argtypes = [vp, vp, i, vp, vp, vp]
+        L.orbm_map_stereo_points.argtypes = [vp, vp, i, vp, vp, f, i, i, vp, vp, i, vp, vp]
         L.orbv_transform_rig_extracted.argtypes = [vp, vp, i, vp, i, i, i]
         L.orbm_search_by_bow_rig_batch.argtypes = [vp, i, vp, i, i, vp, i, vp, vp, vp, f, i, vp, vp]
         u64 = C.c_uint64

@@ -1809,6 +1809,129 @@ __global__ void __launch_bounds__(256) k_map_edit_rows(int n, const int* __restr
     if (j < n) kf_slots[(size_t)row[j] * (size_t)row_cap + (size_t)feat[j]] = slot[j];
 }
 
+// ---- the stereo map points a key frame is born with (orbm_map_stereo_points) ----------------------------------------------------------------------
+// Tracking::CreateNewKeyFrame (src/Tracking.cc:3868-3960) and Tracking::UpdateLastFrame (:3264-3341) sort the features with a positive depth by
+// (depth, index), walk the sorted list and stop behind the first entry that is farther than mThDepth once more than `max_points` entries were visited; an
+// entry whose feature keeps its map point is visited and counted, every other one gets a new point.
+constexpr int kStereoSelectThreads = 256;
+// Where the flagged threads of a workgroup stand among themselves, in thread order: wave ballots rank a lane inside its wave, the waves' counts are summed
+// in LDS (wave_cnt: one int per wave).  Every thread calls; two barriers.  No counter is shared, so the order is the threads'.
+__device__ __forceinline__ int block_ballot_rank(bool flag, int* total, int* wave_cnt) {
+    const unsigned long long bal = __ballot(flag);
+    const int lane = lane_id(), wave = wave_id();
+    if (lane == 0) wave_cnt[wave] = __popcll(bal);
+    __syncthreads();
+    int at = __popcll(bal & ((1ull << lane) - 1ull)), tot = 0;
+    for (int w = 0; w < kStereoSelectThreads / 64; w++) { const int c = wave_cnt[w]; if (w < wave) at += c; tot += c; }
+    __syncthreads();
+    *total = tot;
+    return at;
+}
+
+// Phase 1, one workgroup per frame: the candidates (mvDepth[i] > 0) become keys `depth bits << 32 | i` in LDS - positive floats order as their bit
+// patterns, so the keys order as std::sort orders pair<float, int>, a total order -, a bitonic network sorts them (padded to a power of two with keys
+// above every real one), the stop rule cuts the prefix, and the entries that create a point are ranked in list order.  counts[2 b] = points created,
+// counts[2 b + 1] = entries processed; feat_all[b * cap + j] = feature of the j-th created point.  More candidates than the sort has room for
+// (P.sort_cap keys of dynamic LDS): counts = {-1, candidates}, nothing else is written.  grid (B), kStereoSelectThreads threads, 8 * P.sort_cap bytes
+__global__ void __launch_bounds__(kStereoSelectThreads) k_map_stereo_select(const StereoPointsRec* __restrict__ recs, StereoPointsParams P,
+                                                                            const uint8_t* __restrict__ keeps_all, int* __restrict__ feat_all,
+                                                                            int* __restrict__ counts) {
+    ORBX_DYN_SMEM(smem);
+    unsigned long long* keys = (unsigned long long*)smem;
+    __shared__ int wave_cnt[kStereoSelectThreads / 64];
+    __shared__ unsigned wave_stop[kStereoSelectThreads / 64];
+    const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const StereoPointsRec& R = recs[b];
+    const int N = imax(0, imin(*R.n, P.cap));
+    int nc = 0;
+    for (int base = 0; base < N; base += kStereoSelectThreads) {
+        const int i = base + tid;
+        const float d = i < N ? R.depth[i] : 0.0f;
+        const bool cand = d > 0.0f;                                  // `if(z>0)`, :3880 / :3274
+        int tot;
+        const int at = nc + block_ballot_rank(cand, &tot, wave_cnt);
+        if (cand && at < P.sort_cap) keys[at] = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(unsigned)i;
+        nc += tot;
+    }
+    if (nc > P.sort_cap) {
+        if (tid == 0) { counts[2 * b] = -1; counts[2 * b + 1] = nc; }
+        return;
+    }
+    int P2 = 1;
+    while (P2 < nc) P2 <<= 1;
+    for (int i = nc + tid; i < P2; i += kStereoSelectThreads) keys[i] = ~0ull;
+    __syncthreads();
+    for (int k = 2; k <= P2; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (P2 >> 1); t += kStereoSelectThreads) {
+                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+                const unsigned long long a = keys[lo], c = keys[hi];
+                if ((a > c) == ((lo & k) == 0)) { keys[lo] = c; keys[hi] = a; }
+            }
+            __syncthreads();
+        }
+    // the loop ends behind the first entry j with depth_j > mThDepth && nPoints > max_points, nPoints = j + 1 (:3951-3955 / :3333-3337)
+    unsigned stop = (unsigned)nc;
+    for (int j = tid; j < nc; j += kStereoSelectThreads)
+        if (__uint_as_float((unsigned)(keys[j] >> 32)) > P.th_depth && j + 1 > P.max_points) { stop = (unsigned)(j + 1); break; }
+    stop = wave_min_u32(stop);
+    if (lane_id() == 0) wave_stop[wave_id()] = stop;
+    __syncthreads();
+    for (int w = 0; w < kStereoSelectThreads / 64; w++) stop = wave_stop[w] < stop ? wave_stop[w] : stop;
+    const int processed = (int)stop;
+    const uint8_t* __restrict__ keeps = R.keeps_off >= 0 ? keeps_all + R.keeps_off : nullptr;
+    int* __restrict__ feat = feat_all + (size_t)b * (size_t)P.cap;
+    int created = 0;
+    for (int base = 0; base < processed; base += kStereoSelectThreads) {
+        const int j = base + tid;
+        const int f = j < processed ? (int)(unsigned)(keys[j] & 0xFFFFFFFFull) : 0;
+        const bool create = j < processed && !(keeps && keeps[f]);
+        int tot;
+        const int at = created + block_ballot_rank(create, &tot, wave_cnt);
+        if (create) feat[at] = f;                                    // (at < processed <= N <= P.cap)
+        created += tot;
+    }
+    if (tid == 0) { counts[2 * b] = created; counts[2 * b + 1] = processed; }
+}
+
+// Phase 2: the j-th created point of frame b goes to slot free_all[free_off + j].  Frame::UnprojectStereo (src/Frame.cc:1396-1409), then the fields as
+// MapPoint(Pos, pMap, pFrame, idxF) computes them (P.mode 1, src/MapPoint.cc:90-128, Nleft == -1) or as MapPoint(Pos, pKF, pMap) + AddObservation +
+// UpdateNormalAndDepth leave them for a point with one observation (P.mode 0, :567-642: normal = (0 + normali / |normali|) / 1, which turns a -0 into
+// +0) - in the reference's fp32 statements, unfused; the matrix product as Eigen sums it (sophus_action.h).  Four lanes per point as k_map_scatter: all
+// four compute the point, lane q stores two of the eight floats, lanes 0 and 1 move the descriptor row in two 16-byte accesses, lane 0 marks the slot
+// present and not bad, lane 2 enters the slot in the row, lane 3 lists the feature in the call's compacted output (its frame's part starts at the sum of
+// the earlier frames' counts).  The host has refused duplicate slots and rows, so no two stores meet.  grid (ceil(4 x most points / 256), B), 256 threads
+__global__ void __launch_bounds__(256) k_map_stereo_write(const StereoPointsRec* __restrict__ recs, StereoPointsParams P, const int* __restrict__ free_all,
+                                                          const int* __restrict__ feat_all, const int* __restrict__ counts, MapStore S,
+                                                          int* __restrict__ kf_slots, int row_cap, int* __restrict__ out_feat) {
+    const int b = (int)blockIdx.y;
+    const StereoPointsRec& R = recs[b];
+    const int t = (int)(blockIdx.x * 256u + threadIdx.x), j = t >> 2, q = t & 3;
+    int before = 0;
+    for (int k = lane_id(); k < b; k += 64) before += counts[2 * k];
+    before = wave_sum(before);
+    if (j >= counts[2 * b]) return;
+    const int i = feat_all[(size_t)b * (size_t)P.cap + (size_t)j];
+    const size_t slot = (size_t)free_all[R.free_off + j];
+    const KeyPointRec* __restrict__ kp = R.kps + i;
+    const float z = R.depth[i], u = kp->x, v = kp->y;
+    const float x = __fmul_rn(__fmul_rn(__fsub_rn(u, P.cx), z), P.invfx), y = __fmul_rn(__fmul_rn(__fsub_rn(v, P.cy), z), P.invfy);
+    float pos[3];
+    eig_rt3(R.Rwc, R.Ow, x, y, z, pos);                              // x3D = mRwc * x3Dc + mOw
+    const float o0 = __fsub_rn(pos[0], R.Ow[0]), o1 = __fsub_rn(pos[1], R.Ow[1]), o2 = __fsub_rn(pos[2], R.Ow[2]);
+    const float dist = sqrtf(eig_dot3(o0, o1, o2, o0, o1, o2));
+    float n0 = __fdiv_rn(o0, dist), n1 = __fdiv_rn(o1, dist), n2 = __fdiv_rn(o2, dist);
+    if (P.mode == 0) {
+        n0 = __fdiv_rn(__fadd_rn(0.0f, n0), 1.0f); n1 = __fdiv_rn(__fadd_rn(0.0f, n1), 1.0f); n2 = __fdiv_rn(__fadd_rn(0.0f, n2), 1.0f);
+    }
+    const float max_d = __fmul_rn(dist, pick(P.scale, kp->octave)), min_d = __fdiv_rn(max_d, P.scale_top);
+    if (q < 2) ((int4*)S.desc)[2 * slot + (size_t)q] = ((const int4*)R.desc)[2 * (size_t)i + (size_t)q];
+    if (q == 0) { S.pos[3 * slot] = pos[0]; S.pos[3 * slot + 1] = pos[1]; S.state[slot] = (uint8_t)kMapPresent; }
+    else if (q == 1) { S.pos[3 * slot + 2] = pos[2]; S.normal[3 * slot] = n0; }
+    else if (q == 2) { S.normal[3 * slot + 1] = n1; S.normal[3 * slot + 2] = n2; if (R.row >= 0) kf_slots[(size_t)R.row * (size_t)row_cap + (size_t)i] = (int)slot; }
+    else { S.min_d[slot] = min_d; S.max_d[slot] = max_d; out_feat[before + j] = i; }
+}
+
 // ---- key frames made from extracted frames (orbm_keyframe_create_extracted / _rig_extracted) ----------------------------------------------------
 // What the host must know of every frame before it can allocate: out[3 j ..] = features, FeatureVector nodes, FeatureVector entries of record j
 // (the counts are clamped to what the arrays can hold; the host refuses a FeatureVector that does not fit its frame).  grid (ceil(n / 64)), 64 threads

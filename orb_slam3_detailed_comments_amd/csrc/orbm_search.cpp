@@ -593,7 +593,7 @@ int orbm_stereo_from_depth(orbx_extractor* h, int first, int B, const float* dep
                 d_depth, stride, image_stride, h->W, h->H, mbf, h->d_uRight.p, h->d_depth.p, h->d_nmatch.p);
     h->ur_B = 0;
     if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
-    h->ur_first = first; h->ur_B = B; h->ur_gen = h->extract_gen;
+    h->ur_first = first; h->ur_B = B; h->ur_gen = h->extract_gen; h->depth_is_rig = false;
     return ORBX_OK;
 }
 
@@ -3573,6 +3573,146 @@ int orbm_map_edit_keyframes(orbx_extractor* h, orbm_map* m, int n, const int* ro
     const dim3 grid((unsigned)((N + 255) / 256), 1, 1), blk(256, 1, 1);
     ORBX_LAUNCH(k_map_edit_rows, grid, blk, 0, h->s0, n, (const int*)(dp + o_row), (const int*)(dp + o_feat), (const int*)(dp + o_slot), m->d_kf.p, m->kf_row_cap);
     if (rt::stream_sync(h->s0) || rt::check_launch()) return fail(ORBX_E_DEVICE, "key-frame row edit failed: %s", rt::last_error());
+    return ORBX_OK;
+}
+
+// The second half of Tracking::CreateNewKeyFrame (src/Tracking.cc:3868-3960) and the loop of Tracking::UpdateLastFrame (:3264-3341) for B frames of the
+// last extraction.  Everything that can be refused from the arguments is refused first; then the images' feature counts come down (the `keeps` arrays and
+// the rows are that long), the call's table goes up once, k_map_stereo_select sorts, cuts and ranks, its 8 B bytes of counts come down, and only a call
+// whose every frame fits its free slots and `cap` reaches k_map_stereo_write.
+int orbm_map_stereo_points(orbx_extractor* h, orbm_map* m, int B, const OrbmStereoPointsFrame* frames, const float* cam, float th_depth, int max_points, int mode,
+                           int* created, int* processed, int cap, int* feat, int* slot) {
+    static const char* const entry = "orbm_map_stereo_points";
+    if (int rc = map_call_check(h, m)) return rc;
+    if (B < 0 || max_points < 0 || cap < 0) return fail(ORBX_E_ARG, "%s: B, max_points and cap have to be >= 0", entry);
+    if (mode != 0 && mode != 1) return fail(ORBX_E_ARG, "%s: mode %d (0 = key-frame points, 1 = temporal points)", entry, mode);
+    if (B == 0) return ORBX_OK;
+    if (!frames || !cam || !created || !processed || (cap > 0 && (!feat || !slot))) return fail(ORBX_E_ARG, "%s: null argument", entry);
+    if (B > 65535) return fail(ORBX_E_CAPACITY, "%s: at most 65535 frames per call", entry);
+    if (h->lastB <= 0) return fail(ORBX_E_ARG, "%s: the handle has not extracted anything yet", entry);
+    if (undistort_stale(h)) return fail(ORBX_E_ARG, "%s: orbx_set_undistort was called after the last extraction: extract again before making map points of its frames", entry);
+    if (h->nlevels < 1 || h->nlevels > kMaxLevels) return fail(ORBX_E_ARG, "%s: bad scale levels", entry);
+    size_t nfree_total = 0;
+    bool need_n = false;
+    for (int b = 0; b < B; b++) {
+        const OrbmStereoPointsFrame& F = frames[b];
+        if (F.frame < 0 || F.frame >= h->lastB) return fail(ORBX_E_ARG, "%s: frame %d names image %d, the last extraction holds [0, %d)", entry, b, F.frame, h->lastB);
+        if (h->ur_B <= 0 || h->ur_gen != h->extract_gen || F.frame < h->ur_first || F.frame >= h->ur_first + h->ur_B || h->depth_is_rig)
+            return fail(ORBX_E_ARG, "%s: frame %d: image %d has no depth results of orbm_stereo_match / orbm_stereo_from_depth on this extraction", entry, b, F.frame);
+        if (F.nfree < 0 || (F.nfree > 0 && !F.free_slots)) return fail(ORBX_E_ARG, "%s: frame %d: null / negative free slots", entry, b);
+        if (F.row < -1 || F.row >= m->kf_rows) return fail(ORBX_E_ARG, "%s: frame %d: row %d is outside the map's %d key-frame rows", entry, b, F.row, m->kf_rows);
+        nfree_total += (size_t)F.nfree;
+        need_n = need_n || F.keeps || F.row >= 0;
+    }
+    if (nfree_total > (size_t)0x7fffffff / 8) return fail(ORBX_E_CAPACITY, "%s: %zu free slots in one call", entry, nfree_total);
+    std::lock_guard<std::mutex> lk(m->mu);
+    {   // a slot twice, a row twice: two frames would write one place
+        int rc = ORBX_OK;
+        std::vector<int> rows;
+        int b = 0, k = 0;
+        for (; b < B && !rc; b++) {
+            const OrbmStereoPointsFrame& F = frames[b];
+            for (k = 0; k < F.nfree; k++) {
+                const int s = F.free_slots[k];
+                if (s < 0 || s >= m->slots) { rc = fail(ORBX_E_ARG, "%s: frame %d: free slot %d (entry %d) is outside the map's %d slots", entry, b, s, k, m->slots); break; }
+                if (m->mark[s]) { rc = fail(ORBX_E_ARG, "%s: frame %d: free slot %d (entry %d) is listed twice in this call", entry, b, s, k); break; }
+                m->mark[s] = 1;
+            }
+            if (rc) break;
+            if (F.row >= 0) rows.push_back(F.row);
+        }
+        for (int bb = 0; bb <= b && bb < B; bb++) {
+            const int upto = bb < b ? frames[bb].nfree : k;
+            for (int kk = 0; kk < upto; kk++) m->mark[frames[bb].free_slots[kk]] = 0;
+        }
+        if (rc) return rc;
+        std::sort(rows.begin(), rows.end());
+        for (size_t r = 1; r < rows.size(); r++)
+            if (rows[r] == rows[r - 1]) return fail(ORBX_E_ARG, "%s: row %d is named by two frames", entry, rows[r]);
+    }
+    rt::set_device(h->device);
+    const int kcap = h->kp_total_cap;
+    // N of the images: `keeps` is that long, and so is the row a frame writes into
+    std::vector<int> nimg((size_t)h->lastB, kcap);
+    if (need_n) {
+        if (fetch_sync(h, nimg.data(), h->d_nm.p, sizeof(int) * (size_t)h->lastB)) return fail(ORBX_E_DEVICE, "%s: reading the images' feature counts failed: %s", entry, rt::last_error());
+        for (int b = 0; b < B; b++) {
+            int& n = nimg[frames[b].frame];
+            n = std::max(0, std::min(n, kcap));
+            if (frames[b].row >= 0 && n > m->kf_row_cap)
+                return fail(ORBX_E_ARG, "%s: frame %d: image %d has %d features, the map's rows hold %d", entry, b, frames[b].frame, n, m->kf_row_cap);
+        }
+    }
+    StereoPointsParams P; memset(&P, 0, sizeof P);
+    P.cx = cam[0]; P.cy = cam[1]; P.invfx = cam[2]; P.invfy = cam[3]; P.th_depth = th_depth; P.max_points = max_points; P.mode = mode;
+    P.nlevels = h->nlevels; P.cap = kcap; P.scale_top = h->scale[h->nlevels - 1];
+    for (int l = 0; l < kMaxLevels; l++) P.scale[l] = l < h->nlevels ? h->scale[l] : 1.0f;
+    P.sort_cap = 2;
+    while (P.sort_cap < kcap && P.sort_cap < kStereoPointsSortMax) P.sort_cap <<= 1;
+    while (P.sort_cap > 2 && (size_t)P.sort_cap * 8 + 1024 > rt::lds_limit(h->device)) P.sort_cap >>= 1;      // (a device with less LDS per workgroup than gfx950)
+    std::vector<StereoPointsRec> recs(B);
+    std::vector<uint8_t> keeps; std::vector<int> fslots; fslots.reserve(nfree_total);
+    size_t out_room = 0;
+    for (int b = 0; b < B; b++) {
+        const OrbmStereoPointsFrame& F = frames[b];
+        const size_t f = (size_t)F.frame;
+        StereoPointsRec& R = recs[b]; memset(&R, 0, sizeof R);
+        R.kps = (h->ex_undist_active ? h->d_kps_un.p : h->d_kps.p) + f * kcap;                      // mvKeysUn
+        R.depth = h->d_depth.p + (f - (size_t)h->ur_first) * kcap; R.desc = h->d_desc.p + f * kcap * 4; R.n = h->d_nm.p + f;
+        R.keeps_off = -1;
+        if (F.keeps) { R.keeps_off = (long long)keeps.size(); keeps.insert(keeps.end(), F.keeps, F.keeps + nimg[f]); }
+        R.free_off = (int)fslots.size(); fslots.insert(fslots.end(), F.free_slots, F.free_slots + F.nfree);
+        R.row = F.row;
+        memcpy(R.Rwc, F.Rwc, sizeof R.Rwc); memcpy(R.Ow, F.Ow, sizeof R.Ow);
+        out_room += (size_t)std::min(std::min(F.nfree, cap), kcap);
+    }
+    Packer pk(h);
+    const size_t pr = pk.add(recs.data(), sizeof(StereoPointsRec) * recs.size()), pf = pk.add(fslots.data(), 4 * fslots.size()), pkeep = pk.add(keeps.data(), keeps.size()),
+                 pc = pk.room(8 * (size_t)B), pfeat = pk.room(4 * (size_t)B * kcap), pout = pk.room(4 * out_room);
+    if (int e = pk.flush()) return fail(ORBX_E_DEVICE, "%s: %s", entry, upload_error(e));
+    ORBX_LAUNCH(k_map_stereo_select, dim3(B, 1, 1), dim3(256, 1, 1), 8 * (size_t)P.sort_cap, h->s0, pk.dev<StereoPointsRec>(pr), P, pk.dev<uint8_t>(pkeep), pk.out<int>(pfeat),
+                pk.out<int>(pc));
+    std::vector<int> cnt(2 * (size_t)B);
+    if (fetch_sync(h, cnt.data(), pk.dev<int>(pc), 8 * (size_t)B) || rt::check_launch()) return fail(ORBX_E_DEVICE, "%s: the selection failed: %s", entry, rt::last_error());
+    int refused = -1, why = 0, most = 0; size_t total = 0;
+    for (int b = 0; b < B; b++) {
+        created[b] = cnt[2 * b]; processed[b] = cnt[2 * b + 1];
+        if (refused >= 0) continue;
+        if (cnt[2 * b] < 0) { refused = b; why = 0; }
+        else if (cnt[2 * b] > frames[b].nfree) { refused = b; why = 1; }
+        else if (cnt[2 * b] > cap) { refused = b; why = 2; }
+        else { most = std::max(most, cnt[2 * b]); total += (size_t)cnt[2 * b]; }
+    }
+    if (refused >= 0) {
+        const int b = refused;
+        if (why == 0) return fail(ORBX_E_CAPACITY, "%s: frame %d: %d features with a positive depth, the sort in LDS holds %d", entry, b, processed[b], P.sort_cap);
+        if (why == 1) return fail(ORBX_E_CAPACITY, "%s: frame %d creates %d points and was given %d free slots", entry, b, created[b], frames[b].nfree);
+        return fail(ORBX_E_CAPACITY, "%s: frame %d creates %d points, cap is %d", entry, b, created[b], cap);
+    }
+    if (most == 0) return ORBX_OK;
+    // a row that is shorter than its image so far (never set, or set for fewer features) reads -1 behind its old end
+    for (int b = 0; b < B; b++) {
+        const int row = frames[b].row, n = nimg[frames[b].frame];
+        if (row >= 0 && m->kf_n[row] < n &&
+            rt::memset_async(m->d_kf.p + (size_t)row * m->kf_row_cap + m->kf_n[row], 0xFF, sizeof(int) * (size_t)(n - m->kf_n[row]), h->s0))
+            return fail(ORBX_E_DEVICE, "%s: frame %d: clearing the end of row %d failed", entry, b, row);
+    }
+    ORBX_LAUNCH(k_map_stereo_write, dim3((unsigned)((4 * (size_t)most + 255) / 256), B, 1), dim3(256, 1, 1), 0, h->s0, pk.dev<StereoPointsRec>(pr), P, pk.dev<int>(pf),
+                pk.dev<int>(pfeat), pk.dev<int>(pc), m->S, m->d_kf.p, m->kf_row_cap, pk.out<int>(pout));
+    std::vector<int> flat(total);
+    const int fe = fetch_sync(h, flat.data(), pk.dev<int>(pout), 4 * total) || rt::check_launch();
+    // (the launch is behind us either way: the host's picture of the map follows what the kernel was told to write)
+    size_t at = 0;
+    for (int b = 0; b < B; b++) {
+        const OrbmStereoPointsFrame& F = frames[b];
+        for (int j = 0; j < created[b]; j++) {
+            feat[(size_t)b * cap + j] = flat[at + j]; slot[(size_t)b * cap + j] = F.free_slots[j];
+            m->state[F.free_slots[j]] = (uint8_t)kMapPresent;
+        }
+        at += (size_t)created[b];
+        if (F.row >= 0) { m->kf_n[F.row] = std::max(m->kf_n[F.row], nimg[F.frame]); m->kf_set[F.row] = 1; }
+    }
+    if (fe) return fail(ORBX_E_DEVICE, "%s: writing the points failed: %s", entry, rt::last_error());
     return ORBX_OK;
 }
 

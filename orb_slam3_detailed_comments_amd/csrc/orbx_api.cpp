@@ -1227,7 +1227,7 @@ int orbm_stereo_match(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int 
     if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][1], L->s0);
     L->ur_B = 0;
     if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
-    L->ur_first = lf; L->ur_B = B; L->ur_gen = L->extract_gen;
+    L->ur_first = lf; L->ur_B = B; L->ur_gen = L->extract_gen; L->depth_is_rig = false;
     return ORBX_OK;
 }
 
@@ -1304,6 +1304,7 @@ int orbm_stereo_fisheye(orbx_extractor* L, int lf, orbx_extractor* R, int rf, in
     if (rt::check_launch()) return fail(ORBX_E_DEVICE, "kernel launch failed: %s", rt::last_error());
     // what the links describe, for the rig batch searches that read them in place (orbm_search_local_points_rig_batch, ..._lastframe_rig_batch)
     L->fe_R = R; L->fe_lf = lf; L->fe_rf = rf; L->fe_B = B; L->fe_gen_L = L->extract_gen; L->fe_gen_R = R->extract_gen;
+    L->depth_is_rig = true;
     return ORBX_OK;
 }
 

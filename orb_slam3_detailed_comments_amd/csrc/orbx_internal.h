@@ -106,6 +106,7 @@ struct orbx_extractor {
     // the last orbm_stereo_match / orbm_stereo_from_depth of this handle: d_uRight holds mvuRight of images [ur_first, ur_first + ur_B) of extraction ur_gen, image
     // ur_first's first (ur_B == 0: none) - orbm_keyframe_create_extracted refuses use_u_right for an image they do not cover
     int ur_first = 0, ur_B = 0; uint64_t ur_gen = 0;
+    bool depth_is_rig = false;    // orbm_stereo_fisheye has written d_depth since (its own layout: orbm_map_stereo_points refuses to read it as mvDepth)
     orbx::DevBuf<int> d_knn; orbx::DevBuf<uint8_t> d_ratio;
     orbx::DevBuf<int> d_l2r, d_r2l; orbx::DevBuf<float> d_p3d;     // fisheye stereo (orbm_stereo_fisheye)
     orbx::DevBuf<unsigned long long> d_hamA, d_hamB; orbx::DevBuf<int> d_hamOut;

@@ -256,6 +256,11 @@ __global__ void k_fuse_pair_scan_tiles(int n, const int* __restrict__ chunk_cnt,
 __global__ void k_fuse_pair_scan_sums(int ntiles, const int* __restrict__ tile_sum, int* __restrict__ tile_off);
 __global__ void k_map_edit_rows(int n, const int* __restrict__ row, const int* __restrict__ feat, const int* __restrict__ slot, int* __restrict__ kf_slots,
                                 int row_cap);
+// orbm_map_stereo_points: the depth-ordered selection of Tracking::CreateNewKeyFrame / UpdateLastFrame per frame, then the new points into the store and rows
+__global__ void k_map_stereo_select(const StereoPointsRec* __restrict__ recs, StereoPointsParams P, const uint8_t* __restrict__ keeps_all, int* __restrict__ feat_all,
+                                    int* __restrict__ counts);
+__global__ void k_map_stereo_write(const StereoPointsRec* __restrict__ recs, StereoPointsParams P, const int* __restrict__ free_all, const int* __restrict__ feat_all,
+                                   const int* __restrict__ counts, MapStore S, int* __restrict__ kf_slots, int row_cap, int* __restrict__ out_feat);
 
 __global__ void k_distinctive(const unsigned long long* __restrict__ desc, const int* __restrict__ start, int P, int* __restrict__ best);
 template <bool kLds>        // instantiated for both forms in k_match.hip

@@ -194,6 +194,20 @@ struct KfSnapRec {
     unsigned o_desc, o_ur, o_nid, o_st, o_ft, o_nof;
     int N, nn, nf, cap;
 };
+// one frame of orbm_map_stereo_points (k_map_stereo_select, k_map_stereo_write): mvKeysUn, mvDepth and the descriptor rows of an image of the last
+// extraction and its feature count where the extractor and the depth producer left them; keeps_off: where the frame's `keeps` bytes start in the call's
+// staged block (-1: no feature keeps a point); free_off: where its free slots start in the staged slot list; the frame's list of created features is
+// feat_all + b * cap (creation order: phase 1 writes it, phase 2 reads it); row: the key-frame row that receives the slots, or -1
+struct StereoPointsRec {
+    const KeyPointRec* kps; const float* depth; const unsigned long long* desc; const int* n;
+    long long keeps_off; int free_off, row;
+    float Rwc[9], Ow[3];
+};
+// what every frame of the call shares: Frame::cx, cy, invfx, invfy, mThDepth, the loop's point count (100), which MapPoint constructor is followed
+// (0: key-frame points, 1: temporal points), mvScaleFactors with its last entry apart (a lane indexes the table by its keypoint's octave), the keypoint
+// capacity of an image and the keys the LDS sort was given room for (a power of two)
+struct StereoPointsParams { float cx, cy, invfx, invfy, th_depth; int max_points, mode, nlevels, cap, sort_cap; float scale_top; float scale[kMaxLevels]; };
+constexpr int kStereoPointsSortMax = 16384;    // keys of 8 bytes: 128 KB of gfx950's 160 KB of LDS, the largest power of two that fits
 struct KB8StereoParams {                     // Frame::ComputeStereoFishEyeMatches (src/Frame.cc:1530-1587)
     float cam1[8], cam2[8];                  // mpCamera, mpCamera2
     float R12[9], t12[3];                    // mRlr, mtlr

@@ -868,6 +868,11 @@ class _MapSet:
         pass
 
 
+class _StereoPointsFrame(C.Structure):      # OrbmStereoPointsFrame
+    _fields_ = [("frame", C.c_int), ("Rwc", C.c_float * 9), ("Ow", C.c_float * 3), ("keeps", C.c_void_p), ("free_slots", C.c_void_p), ("nfree", C.c_int),
+                ("row", C.c_int)]
+
+
 class ResidentMap:
     """orbm_map: the map on the device.  The fields the searches read live in a store addressed by slot (update / set_bad), the map-point matches of
     key frames are rows of slots (set_keyframe), and local_points builds Tracking::UpdateLocalPoints (src/Tracking.cc:4088-4120) of B frames on the
@@ -962,6 +967,38 @@ class ResidentMap:
         slots = np.zeros(int(start[-1]), np.int32); seen = np.zeros(int(start[-1]), np.uint8)
         self._lib.check(self._lib.L.orbm_map_sets_fetch(self._h(ext), self._m, int(set0), int(B), start.ctypes.data, slots.ctypes.data, seen.ctypes.data))
         return start, slots, seen
+
+    def stereo_points(self, frames, cam, th_depth, max_points=100, mode=0, cap=None, ext=None):
+        """The stereo map points of Tracking::CreateNewKeyFrame (mode 0) / Tracking::UpdateLastFrame (mode 1) for B frames of ext's last extraction
+        (orbm_map_stereo_points).  frames: B dicts {frame, Rwc [3, 3], Ow [3], free_slots, keeps (N bytes or None), row (-1 = none)}; cam = (cx, cy,
+        invfx, invfy).  Returns (created [B], processed [B], feat [B, cap], slot [B, cap]); a refusal raises OrbxError with .created / .processed set
+        (what ORBX_E_CAPACITY reports so that the caller can size a second call)."""
+        B = len(frames)
+        tab = (_StereoPointsFrame * max(B, 1))()
+        keep = []
+        for b, f in enumerate(frames):
+            t = tab[b]
+            t.frame = int(f["frame"])
+            t.Rwc[:] = [float(x) for x in np.asarray(f["Rwc"], np.float32).reshape(9)]
+            t.Ow[:] = [float(x) for x in np.asarray(f["Ow"], np.float32).reshape(3)]
+            fs = np.ascontiguousarray(f["free_slots"], np.int32).reshape(-1)
+            k = None if f.get("keeps") is None else np.ascontiguousarray(f["keeps"], np.uint8).reshape(-1)
+            keep += [fs, k]
+            t.keeps = None if k is None else k.ctypes.data
+            t.free_slots = fs.ctypes.data; t.nfree = len(fs)
+            t.row = int(f.get("row", -1))
+        if cap is None:
+            cap = max([len(keep[2 * b]) for b in range(B)] + [0])
+        c = np.zeros(6, np.float32); c[:4] = np.asarray(cam, np.float32).reshape(-1)[:4]
+        created = np.zeros(max(B, 1), np.int32); processed = np.zeros(max(B, 1), np.int32)
+        feat = np.full((max(B, 1), max(cap, 1)), -1, np.int32); slot = np.full((max(B, 1), max(cap, 1)), -1, np.int32)
+        rc = self._lib.L.orbm_map_stereo_points(self._h(ext), self._m, B, tab, c.ctypes.data, float(th_depth), int(max_points), int(mode), created.ctypes.data,
+                                                processed.ctypes.data, int(cap), feat.ctypes.data, slot.ctypes.data)
+        if rc != 0:
+            e = OrbxError(rc, (self._lib.L.orbx_last_error() or b"").decode())
+            e.created, e.processed = created[:B].copy(), processed[:B].copy()
+            raise e
+        return created[:B], processed[:B], feat[:B, :cap], slot[:B, :cap]
 
     def close(self):
         if self._m:
