@@ -2,7 +2,8 @@
 """Would a test notice a kernel line deciding wrongly?  A mutation pass over the DECISIONS of the kernels (match / search / vocabulary: ids below 405; extraction - FAST,
 quadtree, pyramid, blur, orientation and BRIEF, input stage - and the host tables of orbx_api.cpp that feed it: ids from 405) and of the host replays of the single-frame
 matcher entries in orbm_search.cpp (ids from 1000: host code is a translation unit of the emulator library like any kernel file), on the CPU SIMT emulator only - and over the
-drop-in facade headers of include/orb_slam3_amd (ids from 2000), which are compiled into the test drivers, not into the library.
+drop-in facade headers of include/orb_slam3_amd (ids from 2000), which are compiled into the test drivers, not into the library.  Ids from 3000 are the state-carrying code:
+the resident map's kernels and host code (k_map_* of k_search.hip, the map and batch entries of orbm_search.cpp), the resident key frames and the key frame database of orbv_api.cpp.
 
 For every mutant of tools/emu_mutants_list.py: copy csrc to a temporary directory (the tree is never edited), replace the mutant's old text - which must occur exactly
 once in its file, so that the list cannot rot silently when a kernel is edited - by its new text, build the emulator library from the copy with the flags of
@@ -27,6 +28,7 @@ defect of the LIST (it breaks the list's safety rule), and the pass fails on it.
     python tools/emu_mutants.py --only k_match        the mutants of files whose name contains k_match (comma-separated list)
     python tools/emu_mutants.py --only orbm_search    the host replays (profiles/emu_mutants_host/: --out / --carry / --base name that directory's files)
     python tools/emu_mutants.py --only include/       the facade headers (profiles/emu_mutants_facade/)
+    python tools/emu_mutants.py --ids 3000,3001,..    the resident map, key frames and database (profiles/emu_mutants_map/: its README has the whole command)
     python tools/emu_mutants.py --ids 3,4             by id
     python tools/emu_mutants.py --without test_x.py   leave test files out (how results_before.jsonl was made: without the tests that the pass itself added)
     python tools/emu_mutants.py --carry before.jsonl  take the kills of an earlier pass as they are and run only what survived it

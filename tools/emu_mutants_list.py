@@ -1018,3 +1018,182 @@ for _m in MUTANTS:
     if _m["id"] in _FACADE_NOTES:
         assert not _m["note"], _m["id"]
         _m["note"] = _FACADE_NOTES[_m["id"]]
+
+
+# ---- the state-carrying code: the resident map, the resident key frames, the key frame database (ids from 3000) ----------------------------------------------
+# Kernels of k_search.hip / k_vocab.hip that no earlier block touches, the resident-map and batch host code of orbm_search.cpp, and the database of orbv_api.cpp.
+# Not in the list, because the mutant could store outside an array once a test reaches it (the list's safety rule):
+#   k_map_scan's loop bound and its carry `run += __shfl(incl, 63)` (the two pilot mutants), the chunk counts of k_map_compact and every rank moved UP: M_out shrinks or an
+#   offset grows, the host lays the set out for the smaller M, and the scatter of k_map_compact then stores behind it.  The carry is mutated where it only moves stores DOWN
+#   (3010); M_out itself is compared by tests/test_map_scan_tiles.py.
+#   block_ballot_rank counting the lane's own wave (feat[at] behind the frame's row), `head` of k_map_set_flags without its imin (bytes behind the last frame's flags),
+#   the remap of db_compact (a stale record index reads behind `mult`), every `slot >= m->slots` / `row >= m->kf_rows` / `feat >= kf_n` refusal (used as an index).
+F = "k_search.hip"
+M_BUILD = ["test_map_state_gates.py", "test_map_scan_tiles.py", "test_state_gaps.py", "test_local_map_build.py::test_list_emulated", "test_local_map_build.py::test_fields_emulated",
+           "test_local_map_build.py::test_refusals_and_lifetime_emulated", "test_local_map_build.py::test_fuzz_emulated"]
+M_SKIP = ["test_map_set_duplicates.py", "test_fuse_map.py", "test_sim3_map.py", "test_fuse_pairs.py"]
+M_FLAGS = ["test_map_set_flags.py", "test_local_map_search.py", "test_sim3_map.py"]
+M_ROWS = ["test_map_rows_resident.py", "test_map_rows_bow.py", "test_map_rows_projection.py"]
+M_STEREO = ["test_stereo_points.py", "test_state_gaps.py"]
+M_KF = ["test_keyframe_extracted.py", "test_resident_keyframes.py"]
+KFDB = ["test_kfdb_state.py", "test_emu_kfdb.py", "test_kfdb_gates.py", "test_kfdb_reference.py"]
+EARLY = ("equivalent in every output: the clear only comes one call earlier - a cleared table and a base of 0 give what a fresh map gives, which is what "
+         "tests/test_map_scan_tiles.py and tests/test_map_set_duplicates.py require of every call on both sides of the limit")
+# k_map_scatter, k_map_seen, map_visit, k_map_stamp
+M(3000, F, "const uint8_t st = (uint8_t)(kMapPresent | (bad[r] ? kMapBad : 0));\n    if (!desc) {", "const uint8_t st = (uint8_t)(kMapPresent);\n    if (!desc) {", M_BUILD, "map scatter: the bad flag of the staged record ignored")
+M(3001, F, "if (i < seen_start[b + 1]) seen_stamp[", "if (i + 1 < seen_start[b + 1]) seen_stamp[", M_BUILD, "map seen: the last slot of a frame's seen list is not marked")
+M(3002, F, "seen_slots[i]] = mark;", "seen_slots[i]] = mark - 1u;", M_BUILD, "map seen: marked with the previous call's epoch")
+M(3003, F, "return slot >= 0 && state[slot] == kMapPresent ? slot : -1;", "return slot > 0 && state[slot] == kMapPresent ? slot : -1;", M_BUILD, "map_visit: slot 0 is never visited")
+M(3004, F, "if (slot >= 0) atomicMax(&stamp[(size_t)G.set * nslots + slot], top - (unsigned)(G.pos0 + i));", "if (slot >= 0) atomicMax(&stamp[(size_t)G.set * nslots + slot], top - (unsigned)i);", M_BUILD,
+  "map stamp: the position inside the row offered instead of the position in the walk")
+# k_map_compact, k_map_scan, k_map_gather
+M(3006, F, "const int slot = i < G.n ? map_visit(G, i, kf_slots, row_cap, state) : -1;\n    const bool keep", "const int slot = i + 1 < G.n ? map_visit(G, i, kf_slots, row_cap, state) : -1;\n    const bool keep", M_BUILD,
+  "map compact: the last entry of every visited row passed over")
+M(3007, F, "const bool keep = slot >= 0 && stamp[(size_t)G.set * nslots + slot] == top - (unsigned)(G.pos0 + i);", "const bool keep = slot >= 0;", M_BUILD, "map compact: repeats are kept")
+M(3008, F, "for (int w = 0; w < wave; w++) at += wave_cnt[w];\n    sets[G.set].slots[at] = slot;", "for (int w = 0; w < wave - 1; w++) at += wave_cnt[w];\n    sets[G.set].slots[at] = slot;", M_BUILD,
+  "map compact: the rank inside a chunk forgets the wave in front")
+M(3010, F, "if (i < c1) chunk_off[i] = run + incl - v;", "if (i < c1) chunk_off[i] = incl - v;", M_BUILD, "map scan: the offsets of a later tile forget the tiles in front")
+M(3012, F, "(uint8_t)(seen_stamp[(size_t)R.set * nslots + slot] > base)", "(uint8_t)(seen_stamp[(size_t)R.set * nslots + slot] >= base)", M_BUILD, "map gather: a mark of the previous call reads as seen")
+M(3013, F, "> base) : (uint8_t)0;", "> base) : (uint8_t)1;", M_BUILD + M_FLAGS[1:2], "map gather: the points of a selected set read as seen")
+# k_map_rows_gather, k_map_row_flags
+M(3014, F, "if (slot >= 0) {\n        const uint8_t st = S.state[slot];\n        ok =", "if (slot > 0) {\n        const uint8_t st = S.state[slot];\n        ok =", M_ROWS + ["test_state_gaps.py"], "rows gather: slot 0 holds no point")
+M(3015, F, "flags[(size_t)R.off + i] = (uint8_t)(slot >= 0 && ", "flags[(size_t)R.off + i] = (uint8_t)(slot > 0 && ", M_ROWS + ["test_state_gaps.py"], "row flags: slot 0 holds no point")
+# k_map_set_flags, k_assigned_slots
+M(3016, F, "if (k < 4 ? k < head : o < M) { db[o] = src[o]; dobs[o] = 1; }", "if (k < 4 ? k + 1 < head : o < M) { db[o] = src[o]; dobs[o] = 1; }", M_FLAGS, "set flags: the last head byte is not copied")
+M(3017, F, "if (k < 4 ? k < head : o < M) { db[o] = src[o]; dobs[o] = 1; }", "if (k < 4 ? k < head : o + 1 < M) { db[o] = src[o]; dobs[o] = 1; }", M_FLAGS, "set flags: the last tail byte is not copied")
+M(3019, F, "if (k < 4 ? k < head : o < M) { db[o] = src[o]; dobs[o] = 1; }", "if (k < 4 ? k < head : o < M) { db[o] = src[o]; dobs[o] = 0; }", M_FLAGS, "set flags: the ragged ends have no observations")
+M(3020, F, "*(uint32_t*)(dobs + o) = 0x01010101u;", "*(uint32_t*)(dobs + o) = 0x00010101u;", M_FLAGS, "set flags: every fourth point of the dword part has no observations")
+M(3021, F, "db[o + 2] = src[o + 2]; db[o + 3] = src[o + 3]; }", "db[o + 2] = src[o + 2]; db[o + 3] = src[o + 2]; }", M_FLAGS, "set flags: the byte form copies a neighbour's flag")
+M(3022, F, "if (agree) *(uint32_t*)(db + o) = *(const uint32_t*)(src + o);", "if (agree) *(uint32_t*)(db + o) = *(const uint32_t*)(src + o) & 0x00FFFFFFu;", M_FLAGS, "set flags: the dword form drops a flag")
+M(3023, F, "out[o] = a < 0 ? a : (a < R.M ? R.slots[a] : -1);", "out[o] = a < 0 ? -1 : (a < R.M ? R.slots[a] : -1);", M_FLAGS, "assigned slots: every negative entry becomes -1",
+  note="unreachable: the kernel has three callers - local_points_batch and local_points_rig_batch on a map's sets, and sim3_batch_run - and the accept kernels in front of it are the "
+       "MapPoints forms local_accept_body<false> / rig_accept_body<false> and k_sim3_accept, which write an index or -1; the -2 of the rotation check is written under "
+       "`LASTFRAME && check_ori` alone (k_search.hip, both bodies), and the last-frame batches return positions of the last frame's rows, which are never translated")
+M(3024, F, "out[o] = a < 0 ? a : (a < R.M ? R.slots[a] : -1);", "out[o] = a <= 0 ? a : (a < R.M ? R.slots[a] : -1);", M_FLAGS, "assigned slots: the set's point 0 is not translated")
+# k_map_skip_listed, k_map_skip_dups, k_fuse_kf_slots, k_map_edit_rows
+M(3026, F, "if (slot < 0) return;\n    const unsigned t = table[slot], p = top - t;", "if (slot <= 0) return;\n    const unsigned t = table[slot], p = top - t;", M_SKIP, "skip listed: slot 0 in a list excludes nothing")
+M(3027, F, "if (t > base && p < (unsigned)M) skip", "if (t > base && p + 1 < (unsigned)M) skip", M_SKIP, "skip listed: the set's last position is never excluded by a list")
+M(3028, F, "if (first >= (unsigned)i) return; ", "if (first >= (unsigned)i || first == 0u) return; ", M_SKIP, "skip dups: a repeat of the slot at position 0 does not take its flag")
+M(3029, F, "if (first >= (unsigned)i) return; ", "if (first > (unsigned)i) return; ", M_SKIP, "skip dups: a first position copies its own flag",
+  note="equivalent: first == i reads skip[o + i] and stores 1 into the same byte only where it is 1 already")
+M(3030, F, "if (b >= 0) {\n        const MapSkipRec R = recs[blockIdx.y];", "if (b > 0) {\n        const MapSkipRec R = recs[blockIdx.y];", M_SKIP, "fuse kf slots: a match with feature 0 reads as an empty entry")
+M(3031, F, "if (j < n) kf_slots[(size_t)row[j] * (size_t)row_cap + (size_t)feat[j]] = slot[j];", "if (j + 1 < n) kf_slots[(size_t)row[j] * (size_t)row_cap + (size_t)feat[j]] = slot[j];", ["test_state_gaps.py"] + M_SKIP[1:2], "edit rows: the last edit of a call is dropped")
+# k_map_stereo_select, k_map_stereo_write
+M(3033, F, "const bool cand = d > 0.0f; ", "const bool cand = d >= 0.0f; ", M_STEREO, "stereo points: depth 0 is a candidate")
+M(3034, F, "> P.th_depth && j + 1 > P.max_points) {", ">= P.th_depth && j + 1 > P.max_points) {", M_STEREO, "stereo points: depth == mThDepth counts as far")
+M(3035, F, "> P.th_depth && j + 1 > P.max_points) {", "> P.th_depth && j + 1 >= P.max_points) {", M_STEREO, "stereo points: the stop rule fires at nPoints == max_points")
+M(3036, F, "{ stop = (unsigned)(j + 1); break; }", "{ stop = (unsigned)j; break; }", M_STEREO, "stereo points: the walk ends in front of the first far entry")
+M(3037, F, "const bool create = j < processed && !(keeps && keeps[f]);", "const bool create = j < processed;", M_STEREO, "stereo points: a feature that keeps its point gets a new one")
+M(3040, F, "if (P.mode == 0) {\n        n0 =", "if (P.mode != 0) {\n        n0 =", M_STEREO, "stereo points: the normal's pass through UpdateNormalAndDepth belongs to the other mode")
+M(3041, F, "if (R.row >= 0) kf_slots[(size_t)R.row * (size_t)row_cap + (size_t)i] = (int)slot; }", "if (R.row > 0) kf_slots[(size_t)R.row * (size_t)row_cap + (size_t)i] = (int)slot; }", M_STEREO, "stereo points: row 0 is not written")
+# k_keyframe_counts
+M(3042, F, "const int N = imin(*R.n_l, R.cap) + (R.kps_r ? imin(*R.n_r, R.cap) : 0);", "const int N = imin(*R.n_l, R.cap);", M_KF, "key frame counts: camera 2's features are not counted")
+# k_sim3_candidates, k_sim3_accept
+M(3050, F, "if (S.F.N > 0 && !(skip && skip[o]))", "if (S.F.N > 0)", SIM3[:2] + M_SKIP[:1], "Sim3 candidates: the skip mask ignored")
+M(3051, F, "[occ](int idx) { return occ && occ[idx]; }", "[occ](int idx) { return false; }", SIM3[:2], "Sim3 candidates: keypoints occupied on entry are candidates",
+  note="equivalent: k_sim3_candidates only proposes; k_sim3_accept starts its bitmap from the same occupancy on entry (s_occ from occ0) and walks the window again, against that "
+       "bitmap, for every choice whose keypoint is taken in it (`if (pending && bit_of(s_occ, c))`), so a choice that fell on an occupied keypoint is replaced by the choice "
+       "the unmutated kernel makes; it costs the second walk the candidates kernel exists to save")
+M(3052, F, "const bool dirty = pending && s_claim[slot] < (unsigned)lane;", "const bool dirty = false;", SIM3[:2], "Sim3 accept: two points of one round take one keypoint")
+M(3053, F, "if (i >= N || (occ0 && occ0[i]) || !bit_of(s_occ, i)) assigned[i] = -1;", "if (i >= N || !bit_of(s_occ, i)) assigned[i] = -1;", SIM3[:2], "Sim3 accept: a keypoint occupied on entry keeps what the array held")
+# grid_build_body, k_lastframe_queries_rig, wave_find_node, k_bow_dists
+M(3060, F, "if (!(px < 0 || px >= kGridCols || py < 0 || py >= kGridRows)) { myc[k] = px * kGridRows + py;", "if (!(px <= 0 || px >= kGridCols || py < 0 || py >= kGridRows)) { myc[k] = px * kGridRows + py;",
+  ["test_state_gaps.py"] + FUSE[:2] + SIM3[:2] + M_KF, "key-frame grid: the first column of cells holds nothing")
+M(3061, F, "while (j >= 0 && cell_items[st + j] > v)", "while (j >= 0 && cell_items[st + j] < v)", FUSE[:2] + SIM3[:2] + M_KF, "key-frame grid: a cell's items in descending index order")
+M(3062, F, "if (after == 0) s_hist[c] = cur + before + 1;", "if (after == 0) s_hist[c] = cur + before;", FUSE[:2] + SIM3[:2] + M_KF + ["test_emu_search.py"], "key-frame grid, crowded cells: the cursor forgets the chunk's last item")
+M(3065, F, "q.x = u; q.y = v; q.r = A.r; q.min_level = A.min_level; q.max_level = A.max_level; q.active = 1;", "q.x = u; q.y = v; q.r = A.r; q.min_level = A.min_level; q.max_level = -1; q.active = 1;",
+  RIG[:1] + M_ROWS[2:], "last-frame rig queries: camera 2's window has no upper level")
+M(3066, F, "const unsigned long long le = __ballot(pos < lo + len && ids[pos] <= id);", "const unsigned long long le = __ballot(pos < lo + len && ids[pos] < id);", ["test_state_gaps.py"] + BOW, "wave_find_node: a probe that hits the id does not count")
+M(3067, F, "int d = -1;\n        if (eligible2[idx2]) {", "int d = -1;\n        if (!eligible2[idx2]) {", BOW, "bow dists: the eligibility flag negated")
+
+# ---- k_match.hip: how k_distinctive_resident is fed ----
+F = "k_match.hip"
+M(3070, F, "const int r = first + k;\n    distinctive_point<kLds>", "const int r = k;\n    distinctive_point<kLds>", DISTINCTIVE, "distinctive (resident): the second form's launch starts at record 0 again")
+
+# ---- k_vocab.hip ----
+F = "k_vocab.hip"
+M(3080, F, "cnt[(size_t)q * R + r] = c * m;", "cnt[(size_t)q * R + r] = c;", KFDB, "kfdb count: a key added twice counts its words once")
+M(3081, F, "if (p >= 0) { c++; f = (unsigned)p < f ? (unsigned)p : f; }", "if (p >= 0) { c++; f = (unsigned)p; }", KFDB, "kfdb count: a lane keeps its last shared word's position, not its first")
+M(3082, F, "if (tid == 0) start[base] = nvalid;", "if (tid == 0) start[base] = nvalid - 1;", VOC + KFDB[:1], "emit_runs: the last run ends one entry early")
+M(3083, F, "if ((a > b2) == up) { key[t] = b2; key[p] = a; }", "if ((a >= b2) == up) { key[t] = b2; key[p] = a; }", VOC, "bitonic sort: equal keys are exchanged",
+  note="equivalent: a real key carries its feature index in its low 16 bits, so two real keys never compare equal; the only equal keys are the kEmpty padding, and exchanging two equal values changes nothing")
+M(3084, F, "if (i == 0) n_out[b] = nl + nr;", "if (i == 0) n_out[b] = nl;", ["test_rig_bow_batch.py", "test_keyframe_extracted.py"], "rig gather: the feature count forgets camera 2")
+
+# ---- orbm_search.cpp: the resident map's host code ----
+F = "orbm_search.cpp"
+M(3100, F, "if (P || (m->state[slots[i]] & kMapPresent)) m->state[slots[i]] = st;", "", M_BUILD[:5] + M_SKIP[:2], "map scatter: the host mirror of `state` is not updated")
+M(3101, F, "slot[(size_t)b * cap + j] = F.free_slots[j];\n            m->state[F.free_slots[j]] = (uint8_t)kMapPresent;", "slot[(size_t)b * cap + j] = F.free_slots[j];", M_STEREO,
+  "stereo points: the host mirror does not learn of the new points")
+M(3102, F, "for (int k = 0; k < i; k++) m->mark[slots[k]] = 0;", "for (int k = 0; k + 1 < i; k++) m->mark[slots[k]] = 0;", M_BUILD, "distinct slots: the mark of the last checked slot stays set")
+M(3103, F, "if (p + n > max_positions) return fail(", "if (p + n >= max_positions) return fail(", M_BUILD, "local points: a walk of exactly the epoch's length refused")
+M(3104, F, "if ((long long)m->base + L > (long long)m->epoch_limit) {", "if ((long long)m->base + L >= (long long)m->epoch_limit) {", M_BUILD, "local points: the stamps are cleared one build early", note=EARLY)
+M(3105, F, "if (rt::memset_async(stamp, 0, 2 * pairs * sizeof(unsigned), h->s0)) return fail(ORBX_E_DEVICE, \"clearing the stamps failed: %s\", rt::last_error());\n        m->base = 0;", "m->base = 0;", M_BUILD,
+  "local points: at the end of an epoch base starts over and the stamps stay")
+M(3106, F, "m->base = top;  ", "", M_BUILD, "local points: base is not advanced")
+M(3107, F, "seen_stamp, m->slots, base + 1u);", "seen_stamp, m->slots, base);", M_BUILD, "local points: the seen marks carry the previous call's value")
+M(3108, F, "m->built[b] = 1;\n    return ORBX_OK;", "return ORBX_OK;", M_BUILD, "map_lay_set: built[b] is not set")
+M(3109, F, "orbm_points& P = m->sets[b];\n    P.M = 0;", "orbm_points& P = m->sets[b];", M_BUILD + M_SKIP[1:2], "map_lay_set: P.M is left stale")
+M(3110, F, "if (!(m->state[slots[i]] & kMapPresent)) return fail(ORBX_E_ARG, \"set %d: slot %d (entry %d) holds no point\", b, slots[i], i);", "", M_BUILD, "map select: a slot that holds nothing is accepted")
+M(3111, F, "if (span < (long long)m->sets[s].M) return fail(", "if (span <= (long long)m->sets[s].M) return fail(", M_FLAGS[1:2] + ["test_state_gaps.py"], "sets fetch: a span that fits exactly refused")
+M(3112, F, "for (int b = 0; b < B; b++) m->sets[b].M = 0;\n    if (L == 0) {", "if (L == 0) {", M_BUILD, "local points: the sets keep their old size while they are rebuilt",
+  note="one of a redundant pair: map_lay_set sets P.M = 0 for every set the call rebuilds before anything is written into it (mutant 3109 is the other place), and a call refused in front "
+       "of this line must leave the sets as they are (tests/test_map_scan_tiles.py); between this line and map_lay_set only a device failure returns")
+# map_skip_table, fuse_map_run, orbm_map_edit_keyframes
+M(3113, F, "} else if ((long long)m->tbase + M > (long long)m->epoch_limit) {", "} else if ((long long)m->tbase + M >= (long long)m->epoch_limit) {", M_SKIP, "skip table: cleared one call early", note=EARLY)
+M(3114, F, "if (rt::memset_async(m->d_table.p, 0, bytes, h->s0)) return fail(ORBX_E_DEVICE, \"clearing the map's table failed: %s\", rt::last_error());\n        m->tbase = 0;", "m->tbase = 0;", M_SKIP,
+  "skip table: at the end of an epoch tbase starts over and the table stays")
+M(3115, F, "m->tbase = S->top;  ", "", M_SKIP, "skip table: tbase is not advanced")
+M(3116, F, "if (f0 < 0 || (long long)f0 + N > n) return fail(", "if (f0 < 0 || (long long)f0 + N >= n) return fail(", M_SKIP, "fuse on the map: features that end exactly at the row's end refused")
+M(3117, F, "if (keys[j].first == keys[j - 1].first)\n", "if (false)\n", M_SKIP[1:2], "edit key frames: two edits of one entry accepted")
+M(3118, F, "for (int j = 1; j < n; j++)\n        if (keys[j].first == keys[j - 1].first)", "for (int j = 2; j < n; j++)\n        if (keys[j].first == keys[j - 1].first)", M_SKIP[1:2] + ["test_state_gaps.py"],
+  "edit key frames: the two smallest entries are not compared")
+# orbm_map_stereo_points
+M(3120, F, "else if (cnt[2 * b] > frames[b].nfree) { refused = b; why = 1; }", "else if (cnt[2 * b] >= frames[b].nfree) { refused = b; why = 1; }", M_STEREO, "stereo points: exactly as many free slots as points refused")
+M(3121, F, "else if (cnt[2 * b] > cap) { refused = b; why = 2; }", "else if (cnt[2 * b] >= cap) { refused = b; why = 2; }", M_STEREO, "stereo points: exactly cap points refused")
+M(3122, F, "m->kf_n[F.row] = std::max(m->kf_n[F.row], nimg[F.frame]); m->kf_set[F.row] = 1; }", "m->kf_n[F.row] = std::max(m->kf_n[F.row], nimg[F.frame]); }", M_STEREO, "stereo points: the row a frame wrote does not count as set")
+M(3123, F, "if (rows[r] == rows[r - 1]) return fail(ORBX_E_ARG, \"%s: row %d is named by two frames\", entry, rows[r]);", ";", M_STEREO, "stereo points: two frames may write one row")
+
+# ---- orbv_api.cpp: the key frame database ----
+F = "orbv_api.cpp"
+M(3200, F, "if (i > 0 && id[i] <= id[i - 1]) return fail(", "if (i > 0 && id[i] < id[i - 1]) return fail(", KFDB, "kfdb add: a word id twice in one BowVector accepted")
+M(3201, F, "if (it != db->keys.end() && (it->second.n != n || it->second.sum != sum))", "if (it != db->keys.end() && (it->second.n != n))", KFDB, "kfdb add: another BowVector of the same size under a live key accepted")
+M(3202, F, "db->rlive[r] = 0; db->live--; db->dead_words += db->rn[r];", "db->rlive[r] = 0; db->live--;", KFDB, "kfdb erase: the erased words are not counted",
+  note="equivalent in every output: dead_words only decides WHEN db_sync compacts the arena; an erased record carries the multiplicity 0 (db_sync builds `mult` from the keys' surviving records) "
+       "and is passed over by k_kfdb_count whether it has been compacted away or not.  The arena then grows where it would have been compacted; what a compaction does is covered "
+       "from the other side (3203, tests/test_kfdb_state.py)")
+M(3203, F, "db->dead_words = 0; db->up_words = 0; db->meta_dirty = true;\n}", "db->dead_words = 0; db->meta_dirty = true;\n}", KFDB, "kfdb compact: the device keeps the arena prefix of before the compaction")
+M(3205, F, "(size_t)db->dead_words > live_words)) db_compact(db);", "(size_t)db->dead_words >= live_words)) db_compact(db);", KFDB, "kfdb sync: compaction when the erased words EQUAL the live ones",
+  note="equivalent in every output: a compaction keeps the surviving records in add order and changes no result (tests/test_kfdb_state.py queries on both sides of the threshold and requires the model's answer on both)")
+M(3207, F, "mult[kv.second.recs.front()] = (int)kv.second.recs.size();", "mult[kv.second.recs.back()] = (int)kv.second.recs.size();", KFDB, "kfdb sync: the LAST surviving add of a key carries its count")
+M(3208, F, "db_kill(db, it->second.recs.front());\n    it->second.recs.pop_front();", "db_kill(db, it->second.recs.back());\n    it->second.recs.pop_back();", KFDB, "kfdb erase: the latest add of the key goes, not the earliest")
+M(3209, F, "if (it->second.recs.empty()) db->keys.erase(it);\n    return ORBX_OK;", "return ORBX_OK;", KFDB, "kfdb erase: a key without records is remembered with its BowVector")
+M(3210, F, "for (int r : it->second.recs) db_kill(db, r);\n        db->keys.erase(it);", "db_kill(db, it->second.recs.front());\n        db->keys.erase(it);", KFDB, "kfdb erase_keys: only the first add of a key is counted as erased")
+M(3211, F, "db->live = 0; db->dead_words = 0; db->up_words = 0; db->meta_dirty = true;\n    return ORBX_OK;", "db->live = 0; db->dead_words = 0; db->meta_dirty = true;\n    return ORBX_OK;", KFDB,
+  "kfdb clear: the device keeps the arena prefix of before the clear")
+M(3212, F, "!it->second.recs.empty()) xr.push_back(it->second.recs.front());", "!it->second.recs.empty()) xr.push_back(it->second.recs.back());", KFDB, "kfdb query: an exclusion names the key's latest add")
+M(3213, F, "if (n > cap) too_small = 1;", "if (n >= cap) too_small = 1;", KFDB, "kfdb query: a result of exactly cap keys refused")
+# orbm_distinctive_descriptors_resident, keyframes_from_records, map_row_check, fuse_pairs_finish, db_sync's growth
+F = "orbm_search.cpp"
+DIST_RES = ["test_state_gaps.py", "test_distinctive_resident.py"]
+M(3130, F, "if (obs_start[p + 1] - obs_start[p] > kDistinctiveMax)", "if (obs_start[p + 1] - obs_start[p] >= kDistinctiveMax)", DIST_RES, "distinctive (resident): a point with exactly the most observations allowed refused")
+M(3133, F, "for (int q = 0; q < p; q++) if (slots[q] >= 0 && slots[q] < map->slots) map->mark[slots[q]] = 0;", "for (int q = 0; q + 1 < p; q++) if (slots[q] >= 0 && slots[q] < map->slots) map->mark[slots[q]] = 0;", DIST_RES,
+  "distinctive (resident): the mark of the last checked slot stays set")
+M(3134, F, "recs.push_back({writes && slots[p] >= 0 ? map->S.desc", "recs.push_back({writes && slots[p] > 0 ? map->S.desc", DIST_RES, "distinctive (resident): the winner of the point at slot 0 is not written into the map")
+M(3135, F, "if (n == 0 || (n > kDistinctiveRegMax) != (form == 1)) continue;", "if (n == 0 || (n >= kDistinctiveRegMax) != (form == 1)) continue;", DIST_RES, "distinctive (resident): a point of exactly kDistinctiveRegMax observations takes the LDS form",
+  note="equivalent in every output: the two forms of k_distinctive_resident differ in where a point's distance rows are kept (registers up to kDistinctiveRegMax observations, LDS "
+       "beyond - the LDS of the launch is sized by the largest n of the call either way), not in what they compute: the same distinctive_point<kLds> body, the same medians, the same "
+       "first-minimum rule; tests/test_distinctive_resident.py requires its expected choice of points with 63, 64 and 65 observations, on either side of the line")
+M(3141, F, "a0 += (size_t)kf->N;\n    }\n    for (int j = 0; j < n; j++) out[j] = made[j];", "}\n    for (int j = 0; j < n; j++) out[j] = made[j];", M_KF, "key frames from records: every key frame gets the first one's keypoint angles")
+M(3150, F, "if (K->N != m->kf_n[row]) return fail(", "if (K->N > m->kf_n[row]) return fail(", M_ROWS + ["test_state_gaps.py"], "map row check: a row longer than its key frame accepted")
+M(3155, F, "if (total > (size_t)W.cap) return fail(ORBX_E_CAPACITY, \"%zu pairs do not fit in cap = %d\", total, W.cap);", "if (total >= (size_t)W.cap) return fail(ORBX_E_CAPACITY, \"%zu pairs do not fit in cap = %d\", total, W.cap);", PAIRS,
+  "fuse pairs: a list of exactly cap pairs refused")
+F = "orbv_api.cpp"
+M(3217, F, "db->up_words = 0;\n    }\n    if (R > db->d_rn.n) {", "}\n    if (R > db->d_rn.n) {", KFDB, "kfdb sync: a grown arena keeps only the appended tail")
+# check_capacity (the extractor's capacity, at both of its call sites through run()), batch_fetch, an empty set in the pair-list Fuse
+F = "orbv_api.cpp"
+M(3218, F, "if (cap > 16384) return fail(ORBX_E_CAPACITY, \"more than 16384 features per image\");", "if (cap >= 16384) return fail(ORBX_E_CAPACITY, \"more than 16384 features per image\");",
+  ["test_kfdb_state.py", "test_emu_vocab.py", "test_rig_bow_batch.py"], "check_capacity: an extractor of exactly 16384 key points refused")
+F = "orbm_search.cpp"
+M(3156, F, "if (M == 0) { if (want) std::fill(want->start, want->start + K + 1, 0); return ORBX_OK; }", "if (M == 0) { return ORBX_OK; }", PAIRS + M_SKIP[1:2], "fuse pairs: an empty point set leaves `start` as the caller's array held it")
+M(3157, F, "memcpy(views[v] + b * M1, src, m); memset(views[v] + b * M1 + m, 0, M1 - m);", "memcpy(views[v] + b * M1, src, m);", ["test_local_points_maps.py", "test_local_map_search.py", "test_local_map_build.py::test_searches_emulated"],
+  "batch fetch: mbTrackInView behind a frame's own points is not zeroed")
