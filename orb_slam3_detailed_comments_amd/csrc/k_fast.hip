@@ -13,13 +13,15 @@
 //   A     quick rejection of every interior pixel, 4 adjacent pixels per lane in one register (SWAR) in the "H form" (p >> 1) | 0x80 of
 //         every byte (7-bit value + guard bit): one v_sub_u32 compares four ring pixels with four thresholds, opposite ring pairs combine
 //         with v_and/v_or.  The test is a necessary condition of "corner at t0" evaluated at 7-bit precision (derivation at phase A); it lets
-//         the same ~1/3 of the pixels through as the exact pair test.  Survivors go to an UNORDERED list by ballot compaction
-//         (no prefix scan, no per-lane counters).
+//         the same ~1/3 of the pixels through as the exact pair test.  Survivors go to a list in ROW-MAJOR order: a trip's lanes are
+//         (row, dword) ordered, every lane appends its own entries side by side behind those of the lanes below it (chained v_mbcnt over the
+//         four byte ballots: no prefix scan, no per-lane counters).
 //   B     exact cornerScore of the listed pixels, two per lane in packed 16-bit lanes (3-input packed min / max), whenever the list is
-//         full and at the end; pixels with a positive score are compacted, in place, to the corner list at the front of the list.
-//   C     strict 3x3 NMS of the corners on the score tile; survivors set a bit in a row-major bitmap
-//   D     output in bitmap (= row-major = reference) order: popcount, wave prefix sum, bit extraction.
-// Cells with more corners than the list holds (noise) give the corner list up: NMS and compaction then scan the score tile.
+//         full and at the end; pixels with a positive score are compacted, in place and in list order, to the corner list at the front of
+//         the list - which is therefore row-major as well.
+//   C     strict 3x3 NMS of the corners on the score tile, 64 corners per trip in list order; the survivors of a trip are ranked by one
+//         ballot and written to the output at once: row-major = the reference's order by construction, no bitmap and no second pass.
+// Cells with more corners than the list holds (noise) give the corner list up: NMS and compaction then scan the score tile (C', D').
 #include "orbx_types.h"
 #include "orbx_block.h"
 #include "orbx_kernels.h"
@@ -54,12 +56,13 @@ __device__ __forceinline__ void fast_score_pk(const pk2 x[16], pk2 vp, int t0, i
     sB = mB > t0 ? mB - 1 : 0;
 }
 
-// number of set bits of a wave ballot below this lane (v_mbcnt_lo/hi)
-__device__ __forceinline__ int lanes_below(unsigned long long bal) {
+// acc + number of set bits of a wave ballot below this lane (v_mbcnt_lo/hi add their last operand: a chain over several ballots costs
+// nothing beyond the two instructions per ballot)
+__device__ __forceinline__ int lanes_below(unsigned long long bal, int acc = 0) {
 #ifdef ORBX_EMU
-    return __popcll(bal & ((1ull << lane_id()) - 1ull));
+    return acc + __popcll(bal & ((1ull << lane_id()) - 1ull));
 #else
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, (unsigned)acc));
 #endif
 }
 
@@ -97,7 +100,7 @@ __device__ __forceinline__ void fast_cell(const CellInfo ci, const LevelInfo L, 
     // with cornerScore >= t, and a strict 3x3 maximum with score >= t has no neighbour that a lower threshold could add above it, so the
     // first run only needs the pixels that are corners at iniTh: the quick test and the list work at t0 = iniTh (the headline workload:
     // -23 % survivors, -29 % corners against t0 = minTh; every cell has corners at 20), and only a cell that comes out empty is done again
-    // at minTh, window reload included (the bitmaps of phase C have overwritten the tile by then).  Wave-uniform loop.
+    // at minTh, window reload included (the keep flags of phase C' may have overwritten the tile by then).  Wave-uniform loop.
     int cx0 = ci.x0, cx1 = ci.x1, cy0 = ci.y0, cy1 = ci.y1;
     for (int pass = 0;; pass++) {
 #ifndef ORBX_EMU
@@ -111,7 +114,7 @@ __device__ __forceinline__ void fast_cell(const CellInfo ci, const LevelInfo L, 
     const int wp = WPC ? WPC : wpr, wpd = wp >> 2;          // LDS pitch
     const int xo = (cx0 - 3) - gx0;                         // tile column of the window's first pixel (0..3)
     // LDS: 16 bytes of padding (the dword left of a row start is read, never used) | window tile, raw bytes | score tile | survivor / corner
-    // list.  The bitmaps of phases C / D and the keep flags of the list-free NMS live in the window tile, which is dead by then.
+    // list.  The keep flags of the list-free NMS (C') live in the window tile, which is dead by then.
     uint8_t* tile = smem + 16;
     uint8_t* sc = tile + tile_bytes;
     const int sc_bytes = wp * (ih + 2);
@@ -187,7 +190,12 @@ __device__ __forceinline__ void fast_cell(const CellInfo ci, const LevelInfo L, 
     // The list region holds [0, nc) corner entries (score offsets of pixels with a positive score) followed by the pending survivors
     // [pbeg, cnt) of phase A.  ---- B ----  scores the pending entries, two per lane, and compacts the corners among them in place: a trip
     // reads 128 entries and appends at most that many behind entries that have been consumed.  When the corners alone no longer leave room
-    // for a phase-A trip, the corner list is given up (corners_listed = false) and phases C / D scan the score tile instead.
+    // for a phase-A trip, the corner list is given up (corners_listed = false) and phases C' / D' scan the score tile instead.
+    // Order invariant: the pending entries are row-major (phase A), and every one of them lies in a later row than every corner already
+    // listed (a flush happens between two trips of phase A, and a trip covers whole rows).  The compaction is stable - the entries of a trip
+    // are ordered (lane, even before odd); a lane's even entry goes behind the corners of both kinds in the lanes below it, its odd entry
+    // also behind its own even entry - and appends behind the corners already there, so [0, nc) stays row-major across any number of
+    // mid-cell flushes.  Phase C relies on it.
     int nc = 0, pbeg = 0, cnt = 0;
     bool corners_listed = true;
     auto score_pending = [&]() {
@@ -208,10 +216,10 @@ __device__ __forceinline__ void fast_cell(const CellInfo ci, const LevelInfo L, 
             if (corners_listed) {
                 const bool cA = sA > 0, cB = hasB && sB > 0;
                 const unsigned long long balA = ORBX_BALLOT(cA), balB = ORBX_BALLOT(cB);
-                const int nA = __popcll(balA);
-                if (ORBX_IN_BALLOT(balA)) list[nc + lanes_below(balA)] = (uint16_t)oA;
-                if (ORBX_IN_BALLOT(balB)) list[nc + nA + lanes_below(balB)] = (uint16_t)oB;
-                nc += nA + __popcll(balB);
+                int r = nc + lanes_below(balB, lanes_below(balA));      // corners of the lanes below
+                if (ORBX_IN_BALLOT(balA)) list[r++] = (uint16_t)oA;
+                if (ORBX_IN_BALLOT(balB)) list[r] = (uint16_t)oB;
+                nc += __popcll(balA) + __popcll(balB);
             }
         }
         ORBX_WAVE_SYNC();
@@ -271,71 +279,73 @@ __device__ __forceinline__ void fast_cell(const CellInfo ci, const LevelInfo L, 
             }
             const uint32_t ANY = SD | SB, BOTH = SD & SB;
             unsigned long long bal[4], bald[4];
-            int trip = 0;
+            // trip: entries of the whole wave; below: entries of the lanes below this one.  The list order is (row, dword, byte) = row-major: a
+            // lane writes its own entries side by side from cnt + below on.
+            int trip = 0, below = 0;
             // (the appends below are guarded by ORBX_IN_BALLOT(bal[j]), not by a lane predicate: the compiler tested every bit twice otherwise, as
             // and + cmp for the branch and as bfe + cmp for the ballot)
             bal[0] = byte_ballot<0>(ANY); bal[1] = byte_ballot<1>(ANY); bal[2] = byte_ballot<2>(ANY); bal[3] = byte_ballot<3>(ANY);
 #pragma unroll
-            for (int j = 0; j < 4; j++) trip += __popcll(bal[j]);
+            for (int j = 0; j < 4; j++) { trip += __popcll(bal[j]); below = lanes_below(bal[j], below); }
             const bool dups = ORBX_BALLOT(BOTH != 0u) != 0ull;      // a pixel that passes for both polarities gets a second (dark) entry: rare
             if (dups) {
                 bald[0] = byte_ballot<0>(BOTH); bald[1] = byte_ballot<1>(BOTH); bald[2] = byte_ballot<2>(BOTH); bald[3] = byte_ballot<3>(BOTH);
 #pragma unroll
-                for (int j = 0; j < 4; j++) trip += __popcll(bald[j]);
+                for (int j = 0; j < 4; j++) { trip += __popcll(bald[j]); below = lanes_below(bald[j], below); }
             }
             if (cnt + trip > list_cap) {                         // wave-uniform: score what is pending, then append behind the corners
                 score_pending();
                 if (cnt + trip > list_cap) { corners_listed = false; nc = 0; pbeg = cnt = 0; }      // (a trip adds <= 512 <= list_cap entries)
             }
             const int toff = toff_lane + it0 * wp;
+            uint16_t* lp = list + cnt + below;
+            auto first_entry = [&](int j) { return (uint16_t)((toff + j) | ((SB & (0x80u << (8 * j))) ? kEntBright : 0)); };
+            if (!dups) {
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                if (ORBX_IN_BALLOT(bal[j])) list[cnt + lanes_below(bal[j])] = (uint16_t)((toff + j) | ((SB & (0x80u << (8 * j))) ? kEntBright : 0));
-                cnt += __popcll(bal[j]);
-            }
-            if (dups) {
+                for (int j = 0; j < 4; j++)
+                    if (ORBX_IN_BALLOT(bal[j])) *lp++ = first_entry(j);
+            } else {
+                // the second (dark) entry of a pixel directly behind its first: the two stay one pixel's worth of the order
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
-                    if (ORBX_IN_BALLOT(bald[j])) list[cnt + lanes_below(bald[j])] = (uint16_t)(toff + j);
-                    cnt += __popcll(bald[j]);
+                    if (ORBX_IN_BALLOT(bal[j])) *lp++ = first_entry(j);
+                    if (ORBX_IN_BALLOT(bald[j])) *lp++ = (uint16_t)(toff + j);
                 }
             }
+            cnt += trip;
         }
     }
     ORBX_WAVE_SYNC();
     score_pending();
     if (corners_listed) {
-        // ---- C ----  cell-local strict 3x3 NMS of the corners (every listed pixel has a score >= t0); survivors mark their (row-major)
-        // score offset in a bitmap
-        uint32_t* bm = tile32;                                         // bit o: corner at score offset o survived
-        const int nwords = (sc_bytes + 31) >> 5;
-        for (int i = lane; i < nwords; i += kFastThreads) bm[i] = 0u;
-        ORBX_WAVE_SYNC();
-        for (int i = lane; i < nc; i += kFastThreads) {
-            const int o = list[i];
-            const uint8_t* c = sc + o;
-            const int s = c[0];
-            // neighbours outside the cell interior are the zero frame
-            const int m0 = imax(imax((int)c[-wp - 1], (int)c[-wp]), imax((int)c[-wp + 1], (int)c[-1]));
-            const int m1 = imax(imax((int)c[1], (int)c[wp - 1]), imax((int)c[wp], (int)c[wp + 1]));
-            if (s > imax(m0, m1)) atomicOr(&bm[o >> 5], 1u << (o & 31));
-        }
-        ORBX_WAVE_SYNC();
-        // ---- D ----  output in bitmap order = row-major order of the pixels
-        for (int w0 = 0; w0 < nwords; w0 += kFastThreads) {
-            const int w = w0 + lane;
-            uint32_t bits = w < nwords ? bm[w] : 0u;
-            const int c = __popc(bits);
-            const int incl = wave_incl_scan(c);
-            int pos = base + incl - c;
-            while (bits) {
-                const int b = __ffsll((unsigned long long)bits) - 1;
-                bits &= bits - 1u;
-                const int o = 32 * w + b;
-                const int y1 = o / (WPC ? WPC : wp), col = o - y1 * wp;      // score row (interior y + 1), tile column
-                out[pos++] = key_pack(cx0 + (col - (xo + 3)) - kBorder, cy0 + (y1 - 1) - kBorder, (int)sc[o]);
+        // ---- C ----  cell-local strict 3x3 NMS of the corners (every listed pixel has a score >= t0), 64 per trip in list order = row-major
+        // order (the invariant at score_pending); the survivors of a trip go straight to the output, ranked by their ballot
+        // key of the corner at score offset o = y1 * wp + col (y1: score row = interior y + 1, col: tile column): the fields of key_pack do not
+        // overlap and x = kx + col >= 0, so the key is a sum:  kk + o + y1 * (4096 - wp) + (s << 24)
+        const int kk = (cx0 - (xo + 3) - kBorder) + ((cy0 - 1 - kBorder) << 12);
+        // o / WPC == (o * Mp) >> 20 exactly for o < 2^14 (the tile offsets' range) when WPC <= 64: the error o * (Mp * WPC - 2^20) / (2^20 * WPC)
+        // is below o / 2^20 < 1 / 64 <= 1 / WPC
+        static_assert(WPC <= 64, "division by multiplication in phase C");
+        constexpr int Mp = WPC ? (1 << 20) / WPC + 1 : 0;
+        for (int i0 = 0; i0 < nc; i0 += kFastThreads) {
+            const int i = i0 + lane;
+            bool keep = false;
+            int o = 0, s = 0;
+            if (i < nc) {
+                o = list[i];
+                const uint8_t* c = sc + o;
+                s = c[0];
+                // neighbours outside the cell interior are the zero frame
+                const int m0 = imax(imax((int)c[-wp - 1], (int)c[-wp]), imax((int)c[-wp + 1], (int)c[-1]));
+                const int m1 = imax(imax((int)c[1], (int)c[wp - 1]), imax((int)c[wp], (int)c[wp + 1]));
+                keep = s > imax(m0, m1);
             }
-            base += ORBX_READLANE(incl, 63);
+            const unsigned long long bal = ORBX_BALLOT(keep);
+            if (ORBX_IN_BALLOT(bal)) {
+                const int y1 = WPC ? (int)((unsigned)mul24(o, Mp) >> 20) : o / wp;
+                out[base + lanes_below(bal)] = (uint32_t)(kk + o + mul24(y1, 4096 - wp)) + ((uint32_t)s << 24);
+            }
+            base += __popcll(bal);
         }
     } else {
         // ---- C', D' ----  the same over every interior pixel (cells so dense that their corners do not fit the list)
@@ -366,7 +376,7 @@ __device__ __forceinline__ void fast_cell(const CellInfo ci, const LevelInfo L, 
         }
     }
     if (base > 0 || pass == 1 || minTh >= iniTh) break;
-    ORBX_WAVE_SYNC();                                           // the second run reloads the window over the bitmap / keep flags
+    ORBX_WAVE_SYNC();                                           // the second run reloads the window (over the keep flags of C')
     }
     if (lane == 0) *count_out = base;
 }

@@ -354,7 +354,7 @@ M(522, F, " | ((q3 - Qd) & (q7 - Qd));", ";", EXTRACT, "quick test, dark: the pa
 M(523, F, " & ((q3 - Pb) | (q7 - Pb));", ";", EXTRACT, "quick test, bright: the pair (6, 14) dropped (looser)", LOOSER)
 M(524, F, "const uint32_t ANY = SD | SB, BOTH = SD & SB;", "const uint32_t ANY = SD | SB, BOTH = 0u;", EXTRACT, "dual polarity: no second (dark) entry for a pixel listed for both")
 M(525, F, "((SB & (0x80u << (8 * j))) ? kEntBright : 0)", "((SD & (0x80u << (8 * j))) ? 0 : kEntBright)", EXTRACT, "dual polarity: the first entry of a pixel listed for both is dark too")
-M(526, F, "list[cnt + lanes_below(bald[j])] = (uint16_t)(toff + j);", "list[cnt + lanes_below(bald[j])] = (uint16_t)((toff + j) | kEntBright);", EXTRACT, "dual polarity: the second entry is bright too")
+M(526, F, "if (ORBX_IN_BALLOT(bald[j])) *lp++ = (uint16_t)(toff + j);", "if (ORBX_IN_BALLOT(bald[j])) *lp++ = (uint16_t)((toff + j) | kEntBright);", EXTRACT, "dual polarity: the second entry is bright too")
 M(527, F, "if (sA > 0) sc[oA] = (uint8_t)sA;", "if (sA >= 0) sc[oA] = (uint8_t)sA;", EXTRACT, "score tile: a zero score overwrites the other polarity's (entry A)")
 M(528, F, "if (hasB && sB > 0) sc[oB] = (uint8_t)sB;", "if (hasB && sB >= 0) sc[oB] = (uint8_t)sB;", EXTRACT, "score tile: a zero score overwrites the other polarity's (entry B)")
 M(529, F, "if (hasB && sB > 0) sc[oB] = (uint8_t)sB;", "if (sB > 0) sc[oB] = (uint8_t)sB;", EXTRACT, "score tile: the hasB clause removed",
@@ -370,10 +370,10 @@ for _i, (_n, _w) in enumerate(_NB):
     _line = _M0 if _i < 4 else _M1
     _mut = _line.replace("(int)%s" % _n, "(int)%s - 1" % _n)
     if _i < 4:
-        M(530 + _i, F, "zero frame\n            " + _line, "zero frame\n            " + _mut, EXTRACT, "NMS (corner list): a tie with the %s neighbour survives" % _w)
+        M(530 + _i, F, "zero frame\n                " + _line, "zero frame\n                " + _mut, EXTRACT, "NMS (corner list): a tie with the %s neighbour survives" % _w)
         M(540 + _i, F, "const int s = c[0];\n            " + _line, "const int s = c[0];\n            " + _mut, EXTRACT, "NMS (list-free): a tie with the %s neighbour survives" % _w, defines=CAP)
     else:
-        M(530 + _i, F, _line + "\n            if (s > imax(m0, m1)) atomicOr", _mut + "\n            if (s > imax(m0, m1)) atomicOr", EXTRACT, "NMS (corner list): a tie with the %s neighbour survives" % _w)
+        M(530 + _i, F, _line + "\n                keep = s > imax(m0, m1);", _mut + "\n                keep = s > imax(m0, m1);", EXTRACT, "NMS (corner list): a tie with the %s neighbour survives" % _w)
         M(540 + _i, F, _line + "\n            kf[o]", _mut + "\n            kf[o]", EXTRACT, "NMS (list-free): a tie with the %s neighbour survives" % _w, defines=CAP)
 M(550, F, "const int t0 = pass == 0 ? iniTh : minTh;", "const int t0 = pass == 0 ? iniTh : iniTh;", EXTRACT, "second run: at iniTh again")
 M(551, F, "const int t0 = pass == 0 ? iniTh : minTh;", "const int t0 = pass == 0 ? iniTh : minTh + 1;", EXTRACT, "second run: at minTh + 1")
@@ -387,6 +387,21 @@ M(555, F, "if (cnt + trip > list_cap) {                         // wave-uniform"
   "list flush: one trip earlier", "equivalent in the output: when the pending survivors are scored does not change their scores", defines=CAP)
 M(556, F, "if (cnt + trip > list_cap) { corners_listed = false;", "if (cnt + trip >= list_cap) { corners_listed = false;", EXTRACT, "list overflow: given up when the trip fits exactly",
   "equivalent in the output: the list-free NMS and compaction (C', D') compute the same set in the same row-major order from the same score tile", defines=CAP)
+# the ordered lists: phase A appends in (row, dword, byte) order, phase B compacts in place and in order, phase C writes the survivors in list order
+# (tests/test_fast_ordered_lists.py; profiles/fast_ordered_lists/README.md).  Every mutant keeps its writes inside the entries the trip owns (ranks only shrink).
+ORDER = ["test_fast_ordered_lists.py::test_ordered_lists_emulated", "test_fast_ordered_lists.py::test_mid_cell_flush_keeps_the_order"]
+_RANK = "int r = nc + lanes_below(balB, lanes_below(balA));"
+M(560, F, _RANK, "int r = nc + lanes_below(balB);", ORDER, "corner list: the rank without the even corners of the lanes below")
+M(561, F, _RANK, "int r = nc + lanes_below(balA);", ORDER, "corner list: the rank without the odd corners of the lanes below")
+M(562, F, "if (ORBX_IN_BALLOT(balA)) list[r++] = (uint16_t)oA;", "if (ORBX_IN_BALLOT(balA)) list[r] = (uint16_t)oA;", ORDER, "corner list: the odd entry's rank without its own lane's even entry")
+_DUAL = "                    if (ORBX_IN_BALLOT(bal[j])) *lp++ = first_entry(j);\n                    if (ORBX_IN_BALLOT(bald[j])) *lp++ = (uint16_t)(toff + j);\n                }"
+M(563, F, _DUAL, "                    if (ORBX_IN_BALLOT(bal[j])) *lp++ = first_entry(j);\n                }\n                for (int j = 0; j < 4; j++) {\n"
+  "                    if (ORBX_IN_BALLOT(bald[j])) *lp++ = (uint16_t)(toff + j);\n                }", ORDER, "survivor list: a lane's second (dark) entries behind all of its first entries")
+M(564, F, "            base += __popcll(bal);\n        }\n    } else {", "            base = __popcll(bal);\n        }\n    } else {", ORDER, "phase C: `base` does not carry from one trip of 64 corners to the next")
+M(565, F, "mul24(y1, 4096 - wp)", "mul24(y1, 4095 - wp)", ORDER, "phase C: the key's x counts the row once too often")
+# the strict comparison at its new place, all eight neighbours at once (one at a time: 530 - 537).  Run on the constructed cells alone: of two equal neighbours both then
+# survive, and only there is the number of survivors known to stay far below the cell's slots
+M(566, F, "keep = s > imax(m0, m1);", "keep = s >= imax(m0, m1);", ORDER[:1], "phase C: a tie with any neighbour survives")
 
 # ---- k_quadtree.hip ------------------------------------------------------------------------------------------------------------------------------------------------
 F = "k_quadtree.hip"
