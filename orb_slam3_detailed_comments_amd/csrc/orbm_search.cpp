@@ -1515,36 +1515,68 @@ static int prune_by_rotation(const orbm_keyframe* K1, const orbm_keyframe* K2, i
     return nmatches;
 }
 
-// The call-time flags of a resident search read from the key frames' rows in an orbm_map instead of the caller's arrays (the .._map entry points at the end of
-// this file, which have checked the rows and hold the map's mutex until the call returns): the rows' place in the map, the slots' states, and the rows the
-// call's flag arrays come from - in the order each search documents; rows2: the second array of a pair where a search has one (nullptr / -1: none).
-// row_flags() fills every flag array of the call in ONE launch of k_map_row_flags, each at the offset the host-fed call would have uploaded it at
-struct BowMapFlags { const int* kf_slots; int row_cap; const uint8_t* state; const int* rows; const int* rows2 = nullptr; };
-static void row_flags(orbx_extractor* h, const BowMapFlags* F, const std::vector<MapRowFlagRec>& recs, const MapRowFlagRec* d_recs, uint8_t* d_flags) {
-    int longest = 0;
-    for (const MapRowFlagRec& r : recs) longest = std::max(longest, r.n);
-    if (recs.empty() || longest <= 0) return;
-    const dim3 grid((longest + 255) / 256, (unsigned)recs.size(), 1), blk(256, 1, 1);
-    ORBX_LAUNCH(k_map_row_flags, grid, blk, 0, h->s0, F->kf_slots, F->row_cap, F->state, d_recs, d_flags);
-}
+// The call-time flag block of a resident search: every flag array of the call, 16-byte aligned, one behind the other in the order the search documents, and where
+// the arrays come from - the caller's own arrays (host-fed: arrays[list][i], nullptr: none) or the key frames' rows in an orbm_map (map-fed: rows[list][i], -1: none;
+// the .._map entry points at the end of this file have checked the rows and hold the map's mutex until the call returns).  A search has at most two lists of arrays.
+// add() hands out the offsets, pack() puts the block behind the call's records in the one upload - the bytes themselves (host-fed), or the records of
+// k_map_row_flags and room for the block (map-fed: room() has to follow the last add()) - and fill(), after flush(), writes a map-fed block in ONE launch, each
+// array at the offset the host-fed call uploads it at.  The block is never shorter than 16 bytes; what lies between the arrays is not read.
+struct CallFlags {
+    const uint8_t* const* arrays[2]; const int* rows[2];
+    const int* kf_slots; int row_cap; const uint8_t* state;                 // the map's rows and slot states (kf_slots == nullptr: host-fed)
+    struct Piece { const uint8_t* src; int n, off; };
+    std::vector<Piece> pieces; std::vector<MapRowFlagRec> recs; std::vector<uint8_t> bytes;
+    size_t total = 0, pf = 0, pr = 0;
+    CallFlags(const uint8_t* const* a0, const uint8_t* const* a1) : arrays{a0, a1}, rows{nullptr, nullptr}, kf_slots(nullptr), row_cap(0), state(nullptr) {}
+    CallFlags(const int* slots, int cap, const uint8_t* st, const int* r0, const int* r1) : arrays{nullptr, nullptr}, rows{r0, r1}, kf_slots(slots), row_cap(cap), state(st) {}
+    // the offset of array i of a list, n flags long, or -1: no array was passed, or the key frame has no features.  always: the search reads the array
+    // unconditionally - it gets an offset (and at least 16 bytes) even then, all zero where the caller passed none
+    int add(int list, int i, int n, int rule, bool always = false) {
+        const uint8_t* src = arrays[list] ? arrays[list][i] : nullptr;
+        const int row = rows[list] ? rows[list][i] : -1;
+        const bool given = n > 0 && (kf_slots ? row >= 0 : src != nullptr);
+        if (!given && !always) return -1;
+        const int off = (int)total;
+        total += al16((size_t)std::max(n, 1));
+        if (given && kf_slots) recs.push_back({row, n, off, rule});
+        else if (given) pieces.push_back({src, n, off});
+        return off;
+    }
+    void pack(Packer& pk) {
+        const size_t block = std::max<size_t>(total, 16);
+        if (kf_slots) { pr = pk.add(recs.data(), sizeof(MapRowFlagRec) * recs.size()); pf = pk.room(block); return; }
+        bytes.assign(block, 0);
+        for (const Piece& p : pieces) memcpy(&bytes[p.off], p.src, (size_t)p.n);
+        pf = pk.add(bytes.data(), bytes.size());
+    }
+    void fill(orbx_extractor* h, const Packer& pk) const {
+        int longest = 0;
+        for (const MapRowFlagRec& r : recs) longest = std::max(longest, r.n);
+        if (longest <= 0) return;                                            // host-fed, or no array of the call holds a flag
+        const dim3 grid((longest + 255) / 256, (unsigned)recs.size(), 1), blk(256, 1, 1);
+        const int* slots = kf_slots; const int cap = row_cap; const uint8_t* st = state;
+        const MapRowFlagRec* d_recs = pk.dev<MapRowFlagRec>(pr); uint8_t* d_flags = pk.out<uint8_t>(pf);
+        ORBX_LAUNCH(k_map_row_flags, grid, blk, 0, h->s0, slots, cap, st, d_recs, d_flags);
+    }
+    const uint8_t* dev(const Packer& pk) const { return pk.dev<uint8_t>(pf); }
+};
 
-// from_map: has_map_point1 from row from_map->rows[0], has_map_point2 of neighbour j from row from_map->rows[1 + j], under the rule "holds a point"
-static int sft_resident_impl(orbx_extractor* h, orbm_keyframe* K1, const uint8_t* has_mp1, int n2, orbm_keyframe* const* K2s,
-                             const uint8_t* const* has_mp2, const float* F12s, const OrbmKB8Pair* kb8, const float* eps, int only_stereo, int coarse, int check_ori,
-                             int* matches12, int* nmatches_out, const BowMapFlags* from_map = nullptr) {
+// flags: list 0 holds has_map_point1 (one array), list 1 has_map_point2 of neighbour j; from a map under the rule "holds a point"
+static int sft_resident_impl(orbx_extractor* h, orbm_keyframe* K1, CallFlags flags, int n2, orbm_keyframe* const* K2s, const float* F12s, const OrbmKB8Pair* kb8,
+                             const float* eps, int only_stereo, int coarse, int check_ori, int* matches12, int* nmatches_out) {
     if (!h || !K1 || n2 < 0 || (n2 > 0 && (!K2s || (!F12s && !kb8) || !eps || !matches12))) return fail(ORBX_E_ARG, "null");
     if (K1->device != h->device) return fail(ORBX_E_ARG, "key frame lives on another device");
     rt::set_device(h->device);
     const int N1 = K1->N;
     if (n2 == 0 || N1 == 0) { for (int j = 0; j < n2; j++) if (nmatches_out) nmatches_out[j] = 0; return ORBX_OK; }
-    // call-time flags: KF1's map point flags at 0, then each neighbour's
-    size_t ftotal = al16((size_t)N1);
+    // call-time flags: KF1's map point flags at 0, then each neighbour's (the kernel reads them all: an array that was not passed is all zero)
+    flags.add(0, 0, N1, kRowHoldsPoint, true);
     std::vector<SftNeighbour> nb(n2);
     for (int j = 0; j < n2; j++) {
         const orbm_keyframe* K2 = K2s[j];
         if (!K2 || K2->device != h->device) return fail(ORBX_E_ARG, "bad neighbour key frame %d", j);
         SftNeighbour& S = nb[j]; memset(&S, 0, sizeof S);
-        S.k2 = K2->dev; S.mp2_off = (int)ftotal; ftotal += al16((size_t)std::max(K2->N, 1));
+        S.k2 = K2->dev; S.mp2_off = flags.add(1, j, K2->N, kRowHoldsPoint, true);
         BowParams& P = S.P;
         if (F12s) for (int i = 0; i < 9; i++) P.F12[i] = F12s[9 * (size_t)j + i];
         P.ep[0] = eps[2 * (size_t)j]; P.ep[1] = eps[2 * (size_t)j + 1];
@@ -1552,24 +1584,14 @@ static int sft_resident_impl(orbx_extractor* h, orbm_keyframe* K1, const uint8_t
         P.only_stereo = only_stereo; P.coarse = coarse; P.th_low = TH_LOW; P.nleft1 = P.nleft2 = -1;
         if (kb8) fill_kb8(P, kb8[j], K1->sigma2, kMaxLevels);                // Kannala-Brandt cameras: one OrbmKB8Pair per neighbour (as orbm_search_for_triangulation_kb8)
     }
-    std::vector<uint8_t> flags(from_map ? 0 : ftotal, 0);
-    std::vector<MapRowFlagRec> recs;
-    if (from_map) {
-        recs.push_back({from_map->rows[0], N1, 0, kRowHoldsPoint});
-        for (int j = 0; j < n2; j++) recs.push_back({from_map->rows[1 + j], K2s[j]->N, nb[j].mp2_off, kRowHoldsPoint});
-    } else {
-        if (has_mp1) memcpy(flags.data(), has_mp1, (size_t)N1);
-        for (int j = 0; j < n2; j++) if (has_mp2 && has_mp2[j] && K2s[j]->N > 0) memcpy(&flags[nb[j].mp2_off], has_mp2[j], (size_t)K2s[j]->N);
-    }
     Packer pk(h);
-    size_t pf, pn, pr = 0;
-    if (from_map) { pn = pk.add(nb.data(), sizeof(SftNeighbour) * nb.size()); pr = pk.add(recs.data(), sizeof(MapRowFlagRec) * recs.size()); pf = pk.room(ftotal); }
-    else { pf = pk.add(flags.data(), flags.size()); pn = pk.add(nb.data(), sizeof(SftNeighbour) * nb.size()); }
+    const size_t pn = pk.add(nb.data(), sizeof(SftNeighbour) * nb.size());
+    flags.pack(pk);
     if (pk.flush() || h->d_si[SI_BEST].ensure((size_t)n2 * N1)) return fail(ORBX_E_DEVICE, "upload/allocation failed");
-    if (from_map) row_flags(h, from_map, recs, pk.dev<MapRowFlagRec>(pr), pk.out<uint8_t>(pf));
+    flags.fill(h, pk);
     dim3 grid((N1 + 3) / 4, n2, 1), blk(256, 1, 1);
-    if (kb8) ORBX_LAUNCH(k_sft_resident_kb8, grid, blk, 0, h->s0, K1->dev, pk.dev<uint8_t>(pf), pk.dev<SftNeighbour>(pn), h->d_si[SI_BEST].p);
-    else ORBX_LAUNCH(k_sft_resident, grid, blk, 0, h->s0, K1->dev, pk.dev<uint8_t>(pf), pk.dev<SftNeighbour>(pn), h->d_si[SI_BEST].p);
+    if (kb8) ORBX_LAUNCH(k_sft_resident_kb8, grid, blk, 0, h->s0, K1->dev, flags.dev(pk), pk.dev<SftNeighbour>(pn), h->d_si[SI_BEST].p);
+    else ORBX_LAUNCH(k_sft_resident, grid, blk, 0, h->s0, K1->dev, flags.dev(pk), pk.dev<SftNeighbour>(pn), h->d_si[SI_BEST].p);
     if (fetch_sync(h, matches12, h->d_si[SI_BEST].p, sizeof(int) * (size_t)n2 * N1) || rt::check_launch())
         return fail(ORBX_E_DEVICE, "resident triangulation search failed: %s", rt::last_error());
     for (int j = 0; j < n2; j++) {
@@ -1583,68 +1605,77 @@ int orbm_search_for_triangulation_resident(orbx_extractor* h, orbm_keyframe* K1,
                                            const uint8_t* const* has_mp2, const float* F12s, const float* eps, int only_stereo, int coarse, int check_ori,
                                            int* matches12, int* nmatches_out) {
     if (n2 > 0 && !F12s) return fail(ORBX_E_ARG, "null");
-    return sft_resident_impl(h, K1, has_mp1, n2, K2s, has_mp2, F12s, nullptr, eps, only_stereo, coarse, check_ori, matches12, nmatches_out);
+    return sft_resident_impl(h, K1, CallFlags(&has_mp1, has_mp2), n2, K2s, F12s, nullptr, eps, only_stereo, coarse, check_ori, matches12, nmatches_out);
 }
 
 int orbm_search_for_triangulation_resident_kb8(orbx_extractor* h, orbm_keyframe* K1, const uint8_t* has_mp1, int n2, orbm_keyframe* const* K2s,
                                                const uint8_t* const* has_mp2, const OrbmKB8Pair* cams, const float* eps, int only_stereo, int coarse, int check_ori,
                                                int* matches12, int* nmatches_out) {
     if (n2 > 0 && !cams) return fail(ORBX_E_ARG, "null");
-    return sft_resident_impl(h, K1, has_mp1, n2, K2s, has_mp2, nullptr, cams, eps, only_stereo, coarse, check_ori, matches12, nmatches_out);
+    return sft_resident_impl(h, K1, CallFlags(&has_mp1, has_mp2), n2, K2s, nullptr, cams, eps, only_stereo, coarse, check_ori, matches12, nmatches_out);
 }
 
-// from_map: has_map_point1 of pair p from row from_map->rows[p], eligible2 from row from_map->rows2[p] (rows2 == nullptr or -1: every feature is eligible),
-// under the rule "holds a good point"
-static int bow_resident_impl(orbx_extractor* h, int n, orbm_keyframe* const* K1s, const uint8_t* const* has_mp1, orbm_keyframe* const* K2s,
-                             const uint8_t* const* eligible2, float nnratio, int th_inclusive, int check_ori, int* const* matches12, int* nmatches_out,
-                             const BowMapFlags* from_map = nullptr) {
+// The result block of the resident BoW searches in d_si[SI_BEST]: nout results, pre-set to -1 | 4 status words | `extra` counts, both zeroed.  ensure() goes
+// with the upload, clear() in front of the search's launches, fetch() behind them: ONE copy brings the whole block down into res
+struct BowResults {
+    orbx_extractor* h; size_t nout, extra; std::vector<int> res;
+    size_t total() const { return nout + 4 + extra; }
+    int* dev() const { return h->d_si[SI_BEST].p; }
+    int* status() const { return dev() + nout; }
+    int* counts() const { return dev() + nout + 4; }
+    bool ensure() const { return h->d_si[SI_BEST].ensure(total()) != 0; }
+    int clear() const {
+        if (rt::memset_async(dev(), 0xFF, sizeof(int) * nout, h->s0) || rt::memset_async(status(), 0, sizeof(int) * (4 + extra), h->s0)) return fail(ORBX_E_DEVICE, "memset failed");
+        return ORBX_OK;
+    }
+    // search: names the call in a failure's text; k2: what the second side of a pair is, for the refusal of an overfull vocabulary node (status bit 4)
+    int fetch(const char* search, const char* k2) {
+        res.resize(total());
+        if (fetch_sync(h, res.data(), dev(), sizeof(int) * total()) || rt::check_launch()) return fail(ORBX_E_DEVICE, "%s failed: %s", search, rt::last_error());
+        if (res[nout] & 4) return fail(ORBX_E_CAPACITY, "a vocabulary node holds more than 2048 features of one %s", k2);
+        return ORBX_OK;
+    }
+};
+
+// frame b of a vocabulary transform as the second key frame of a BoW pair: its FeatureVector where the transform left it, in rows of `width` entries (the
+// extractor's capacity, twice that for a rig frame); the node count is read on the device (BowPairResident::k2_nodes_dev)
+static ResidentKF frame_as_k2(const VocFrameArrays& V, int b, int width, const KeyPointRec* kps, const unsigned long long* desc) {
+    ResidentKF K; memset(&K, 0, sizeof K);
+    K.kps = kps; K.desc = desc;
+    K.node_id = V.fv_node + (size_t)b * width; K.fv_start = V.fv_start + (size_t)b * (width + 1); K.fv_feat = V.fv_feat + (size_t)b * width;
+    K.N = width;
+    return K;
+}
+
+// flags: list 0 holds has_map_point1 of pair p, list 1 eligible2 (none: every feature is eligible); from a map under the rule "holds a good point"
+static int bow_resident_impl(orbx_extractor* h, int n, orbm_keyframe* const* K1s, orbm_keyframe* const* K2s, CallFlags flags, float nnratio, int th_inclusive,
+                             int check_ori, int* const* matches12, int* nmatches_out) {
     if (!h || n < 0 || (n > 0 && (!K1s || !K2s || !matches12))) return fail(ORBX_E_ARG, "null");
     rt::set_device(h->device);
     if (n == 0) return ORBX_OK;
-    size_t ftotal = 0; int N1cap = 1, maxnodes = 1;
+    int N1cap = 1, maxnodes = 1;
     std::vector<BowPairResident> pairs(n);
     for (int p = 0; p < n; p++) {
         const orbm_keyframe *K1 = K1s[p], *K2 = K2s[p];
         if (!K1 || !K2 || !matches12[p] || K1->device != h->device || K2->device != h->device) return fail(ORBX_E_ARG, "bad key frame pair %d", p);
         BowPairResident& B = pairs[p];
         B.k1 = K1->dev; B.k2 = K2->dev; B.k2_nodes_dev = nullptr;
-        B.mp1_off = -1; B.elig2_off = -1;
-        const bool flags1 = from_map ? true : (has_mp1 && has_mp1[p]), flags2 = from_map ? (from_map->rows2 && from_map->rows2[p] >= 0) : (eligible2 && eligible2[p]);
-        if (flags1 && K1->N > 0) { B.mp1_off = (int)ftotal; ftotal += al16((size_t)K1->N); }
-        if (flags2 && K2->N > 0) { B.elig2_off = (int)ftotal; ftotal += al16((size_t)K2->N); }
+        B.mp1_off = flags.add(0, p, K1->N, kRowHoldsGoodPoint); B.elig2_off = flags.add(1, p, K2->N, kRowHoldsGoodPoint);
         N1cap = std::max(N1cap, K1->N); maxnodes = std::max(maxnodes, K1->fv_nodes);
     }
-    std::vector<uint8_t> flags(from_map ? 0 : std::max<size_t>(ftotal, 16), 0);
-    std::vector<MapRowFlagRec> recs;
-    for (int p = 0; p < n; p++) {
-        if (from_map) {
-            if (pairs[p].mp1_off >= 0) recs.push_back({from_map->rows[p], K1s[p]->N, pairs[p].mp1_off, kRowHoldsGoodPoint});
-            if (pairs[p].elig2_off >= 0) recs.push_back({from_map->rows2[p], K2s[p]->N, pairs[p].elig2_off, kRowHoldsGoodPoint});
-            continue;
-        }
-        if (pairs[p].mp1_off >= 0) memcpy(&flags[pairs[p].mp1_off], has_mp1[p], (size_t)K1s[p]->N);
-        if (pairs[p].elig2_off >= 0) memcpy(&flags[pairs[p].elig2_off], eligible2[p], (size_t)K2s[p]->N);
-    }
     Packer pk(h);
-    size_t pf, pp, pr = 0;
-    if (from_map) { pp = pk.add(pairs.data(), sizeof(BowPairResident) * pairs.size()); pr = pk.add(recs.data(), sizeof(MapRowFlagRec) * recs.size()); pf = pk.room(std::max<size_t>(ftotal, 16)); }
-    else { pf = pk.add(flags.data(), flags.size()); pp = pk.add(pairs.data(), sizeof(BowPairResident) * pairs.size()); }
-    const size_t nout = (size_t)n * N1cap;
-    if (pk.flush() || h->d_si[SI_BEST].ensure(nout + 4)) return fail(ORBX_E_DEVICE, "upload/allocation failed");
-    if (from_map) row_flags(h, from_map, recs, pk.dev<MapRowFlagRec>(pr), pk.out<uint8_t>(pf));
-    // results pre-set to -1, the status word behind them to 0
-    if (rt::memset_async(h->d_si[SI_BEST].p, 0xFF, sizeof(int) * nout, h->s0) || rt::memset_async(h->d_si[SI_BEST].p + nout, 0, sizeof(int) * 4, h->s0))
-        return fail(ORBX_E_DEVICE, "memset failed");
+    const size_t pp = pk.add(pairs.data(), sizeof(BowPairResident) * pairs.size());
+    flags.pack(pk);
+    BowResults R = {h, (size_t)n * N1cap, 0, {}};
+    if (pk.flush() || R.ensure()) return fail(ORBX_E_DEVICE, "upload/allocation failed");
+    flags.fill(h, pk);
+    if (int rc = R.clear()) return rc;
     dim3 grid((maxnodes + 3) / 4, n, 1), blk(256, 1, 1);
-    ORBX_LAUNCH(k_bow_match_resident, grid, blk, 0, h->s0, pk.dev<BowPairResident>(pp), pk.dev<uint8_t>(pf), nnratio, TH_LOW, th_inclusive,
-                h->d_si[SI_BEST].p, N1cap, h->d_si[SI_BEST].p + nout);
-    std::vector<int> res(nout + 4);
-    if (fetch_sync(h, res.data(), h->d_si[SI_BEST].p, sizeof(int) * (nout + 4)) || rt::check_launch())
-        return fail(ORBX_E_DEVICE, "resident bow search failed: %s", rt::last_error());
-    if (res[nout] & 4) return fail(ORBX_E_CAPACITY, "a vocabulary node holds more than 2048 features of one key frame");
+    ORBX_LAUNCH(k_bow_match_resident, grid, blk, 0, h->s0, pk.dev<BowPairResident>(pp), flags.dev(pk), nnratio, TH_LOW, th_inclusive, R.dev(), N1cap, R.status());
+    if (int rc = R.fetch("resident bow search", "key frame")) return rc;
     for (int p = 0; p < n; p++) {
         const int N1 = K1s[p]->N;
-        if (N1 > 0) memcpy(matches12[p], &res[(size_t)p * N1cap], sizeof(int) * (size_t)N1);
+        if (N1 > 0) memcpy(matches12[p], &R.res[(size_t)p * N1cap], sizeof(int) * (size_t)N1);
         const int nm = prune_by_rotation(K1s[p], K2s[p], matches12[p], check_ori != 0);
         if (nmatches_out) nmatches_out[p] = nm;
     }
@@ -1653,17 +1684,17 @@ static int bow_resident_impl(orbx_extractor* h, int n, orbm_keyframe* const* K1s
 
 int orbm_search_by_bow_resident(orbx_extractor* h, int n, orbm_keyframe* const* K1s, const uint8_t* const* has_mp1, orbm_keyframe* const* K2s,
                                 const uint8_t* const* eligible2, float nnratio, int th_inclusive, int check_ori, int* const* matches12, int* nmatches_out) {
-    return bow_resident_impl(h, n, K1s, has_mp1, K2s, eligible2, nnratio, th_inclusive, check_ori, matches12, nmatches_out);
+    return bow_resident_impl(h, n, K1s, K2s, CallFlags(has_mp1, eligible2), nnratio, th_inclusive, check_ori, matches12, nmatches_out);
 }
 
 // ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vpMapPointMatches) (src/ORBmatcher.cc:259-493) for the frames of a batch: frame b of the last
 // extraction (its FeatureVector where orbv_transform_extracted left it) against the resident key frame KFs[b].  Two launches for the whole batch:
 // k_bow_match_resident (the accept loop per vocabulary node) and k_bow_rotation_prune (histogram, three maxima, resets, counts) - nothing but the
 // call-time flags goes up, nothing but the matches comes down.  The caller holds the vocabulary's lock until the matches are down: no other handle's run
-// replaces the FeatureVectors under the kernels.  The flags are the caller's arrays (has_mp1) or, with from_map, filled on the device from the key
-// frames' rows in a map (k_map_row_flags) whose mutex the caller holds as well.
-static int bow_frames_batch_locked(orbx_extractor* h, const orbv_vocabulary* v, int first, int B, orbm_keyframe* const* KFs, const uint8_t* const* has_mp1,
-                                   const BowMapFlags* from_map, float nnratio, int check_ori, int* const* matches12, int* nmatches_out) {
+// replaces the FeatureVectors under the kernels.  flags: list 0 holds has_map_point1 of frame b's key frame - the caller's arrays or, filled on the device,
+// the key frames' rows in a map whose mutex the caller holds as well (rule "holds a good point").
+static int bow_frames_batch_locked(orbx_extractor* h, const orbv_vocabulary* v, int first, int B, orbm_keyframe* const* KFs, CallFlags flags, float nnratio,
+                                   int check_ori, int* const* matches12, int* nmatches_out) {
     VocFrameArrays V;
     if (orbv_frame_arrays(v, &V) == 0 && V.rig)
         return fail(ORBX_E_ARG, "the last vocabulary transform was a rig transform (orbv_transform_rig_extracted): search its frames with orbm_search_by_bow_rig_batch");
@@ -1675,7 +1706,7 @@ static int bow_frames_batch_locked(orbx_extractor* h, const orbv_vocabulary* v, 
     if (undistort_stale(h)) return fail(ORBX_E_ARG, "orbx_set_undistort was called after the last extraction: extract again before searching its frames");
     rt::set_device(h->device);
     const int cap = h->kp_total_cap;
-    size_t ftotal = 0; int N1cap = 1, maxnodes = 1;
+    int N1cap = 1, maxnodes = 1;
     std::vector<BowPairResident> pairs(B);
     for (int b = 0; b < B; b++) {
         const orbm_keyframe* K1 = KFs[b];
@@ -1683,48 +1714,30 @@ static int bow_frames_batch_locked(orbx_extractor* h, const orbv_vocabulary* v, 
         BowPairResident& P = pairs[b];
         memset(&P, 0, sizeof P);
         P.k1 = K1->dev;
-        P.k2.kps = (h->ex_undist_active ? h->d_kps_un.p : h->d_kps.p) + (size_t)(first + b) * cap;          // F.mvKeysUn (the angle is what is read of it)
-        P.k2.desc = h->d_desc.p + (size_t)(first + b) * cap * 4; P.k2.ur = nullptr;
-        P.k2.node_id = V.fv_node + (size_t)b * cap; P.k2.fv_start = V.fv_start + (size_t)b * (cap + 1); P.k2.fv_feat = V.fv_feat + (size_t)b * cap;
-        P.k2.node_of_feat = nullptr; P.k2.N = cap; P.k2.fv_nodes = 0;
+        P.k2 = frame_as_k2(V, b, cap, (h->ex_undist_active ? h->d_kps_un.p : h->d_kps.p) + (size_t)(first + b) * cap,      // F.mvKeysUn (the angle is what is read of it)
+                           h->d_desc.p + (size_t)(first + b) * cap * 4);
         P.k2_nodes_dev = V.nout + 2 * b + 1;
-        P.mp1_off = -1; P.elig2_off = -1;
-        if ((from_map || has_mp1[b]) && K1->N > 0) { P.mp1_off = (int)ftotal; ftotal += al16((size_t)K1->N); }
+        P.mp1_off = flags.add(0, b, K1->N, kRowHoldsGoodPoint); P.elig2_off = -1;
         N1cap = std::max(N1cap, K1->N); maxnodes = std::max(maxnodes, K1->fv_nodes);
     }
-    std::vector<uint8_t> flags(from_map ? 0 : std::max<size_t>(ftotal, 16), 0);
-    std::vector<MapRowFlagRec> recs(from_map ? B : 0);
-    for (int b = 0; b < B; b++) {
-        if (from_map) recs[b] = {from_map->rows[b], pairs[b].mp1_off >= 0 ? KFs[b]->N : 0, std::max(pairs[b].mp1_off, 0), kRowHoldsGoodPoint};
-        else if (pairs[b].mp1_off >= 0) memcpy(&flags[pairs[b].mp1_off], has_mp1[b], (size_t)KFs[b]->N);
-    }
     Packer pk(h);
-    size_t pf, pp, pr = 0;
-    if (from_map) { pp = pk.add(pairs.data(), sizeof(BowPairResident) * pairs.size()); pr = pk.add(recs.data(), sizeof(MapRowFlagRec) * recs.size()); pf = pk.room(std::max<size_t>(ftotal, 16)); }
-    else { pf = pk.add(flags.data(), flags.size()); pp = pk.add(pairs.data(), sizeof(BowPairResident) * pairs.size()); }
-    const size_t nout = (size_t)B * N1cap, ntot = nout + 4 + (size_t)B;            // matches | status | nmatches
-    if (pk.flush() || h->d_si[SI_BEST].ensure(ntot)) return fail(ORBX_E_DEVICE, "upload/allocation failed");
-    if (from_map && ftotal > 0) {
-        dim3 gridf((N1cap + 255) / 256, B, 1), blkf(256, 1, 1);
-        ORBX_LAUNCH(k_map_row_flags, gridf, blkf, 0, h->s0, from_map->kf_slots, from_map->row_cap, from_map->state, pk.dev<MapRowFlagRec>(pr), pk.out<uint8_t>(pf));
-    }
-    if (rt::memset_async(h->d_si[SI_BEST].p, 0xFF, sizeof(int) * nout, h->s0) || rt::memset_async(h->d_si[SI_BEST].p + nout, 0, sizeof(int) * (4 + (size_t)B), h->s0))
-        return fail(ORBX_E_DEVICE, "memset failed");
+    const size_t pp = pk.add(pairs.data(), sizeof(BowPairResident) * pairs.size());
+    flags.pack(pk);
+    BowResults R = {h, (size_t)B * N1cap, (size_t)B, {}};                          // matches | status | nmatches
+    if (pk.flush() || R.ensure()) return fail(ORBX_E_DEVICE, "upload/allocation failed");
+    flags.fill(h, pk);
+    if (int rc = R.clear()) return rc;
     if (h->profile) rt::event_record(h->ev_stage[ST_MATCH][0], h->s0);
     dim3 grid((maxnodes + 3) / 4, B, 1), blk(256, 1, 1);
-    ORBX_LAUNCH(k_bow_match_resident, grid, blk, 0, h->s0, pk.dev<BowPairResident>(pp), pk.dev<uint8_t>(pf), nnratio, TH_LOW, 1, h->d_si[SI_BEST].p, N1cap,
-                h->d_si[SI_BEST].p + nout);
+    ORBX_LAUNCH(k_bow_match_resident, grid, blk, 0, h->s0, pk.dev<BowPairResident>(pp), flags.dev(pk), nnratio, TH_LOW, 1, R.dev(), N1cap, R.status());
     dim3 gridp(B, 1, 1), blkp(64, 1, 1);
-    ORBX_LAUNCH(k_bow_rotation_prune, gridp, blkp, 0, h->s0, pk.dev<BowPairResident>(pp), h->d_si[SI_BEST].p, N1cap, check_ori, h->d_si[SI_BEST].p + nout + 4);
+    ORBX_LAUNCH(k_bow_rotation_prune, gridp, blkp, 0, h->s0, pk.dev<BowPairResident>(pp), R.dev(), N1cap, check_ori, R.counts());
     if (h->profile) rt::event_record(h->ev_stage[ST_MATCH][1], h->s0);
-    std::vector<int> res(ntot);
-    if (fetch_sync(h, res.data(), h->d_si[SI_BEST].p, sizeof(int) * ntot) || rt::check_launch())
-        return fail(ORBX_E_DEVICE, "batched bow search failed: %s", rt::last_error());
-    if (res[nout] & 4) return fail(ORBX_E_CAPACITY, "a vocabulary node holds more than 2048 features of one frame");
+    if (int rc = R.fetch("batched bow search", "frame")) return rc;
     for (int b = 0; b < B; b++) {
         const int N1 = KFs[b]->N;
-        if (N1 > 0) memcpy(matches12[b], &res[(size_t)b * N1cap], sizeof(int) * (size_t)N1);
-        if (nmatches_out) nmatches_out[b] = res[nout + 4 + b];
+        if (N1 > 0) memcpy(matches12[b], &R.res[(size_t)b * N1cap], sizeof(int) * (size_t)N1);
+        if (nmatches_out) nmatches_out[b] = R.res[R.nout + 4 + b];
     }
     return ORBX_OK;
 }
@@ -1733,18 +1746,17 @@ int orbm_search_by_bow_frames_batch(orbx_extractor* h, const orbv_vocabulary* v,
                                     float nnratio, int check_ori, int* const* matches12, int* nmatches_out) {
     if (!h || !v || B <= 0 || !KFs || !has_mp1 || !matches12) return fail(ORBX_E_ARG, "null");
     const std::unique_lock<std::mutex> vlk = orbv_lock(v);
-    return bow_frames_batch_locked(h, v, first, B, KFs, has_mp1, nullptr, nnratio, check_ori, matches12, nmatches_out);
+    return bow_frames_batch_locked(h, v, first, B, KFs, CallFlags(has_mp1, nullptr), nnratio, check_ori, matches12, nmatches_out);
 }
 
 // SearchByBoW(pKF, F) for rig frames (F.Nleft != -1, src/ORBmatcher.cc:259-493 incl. :343-372 and :414-446), P (frame, key frame) pairs: rig frame
 // frame[p] of the last orbv_transform_rig_extracted(v, L, lf, R, rf, B, .) - its rows and FeatureVector where the transform left them, camera 1's
 // keypoints in L, camera 2's in R - against the resident key frame KFs[p].  k_bow_match_rig (the two-camera accept loop per vocabulary node) and
 // k_bow_rotation_prune_rig (one histogram over both cameras' matches) for all pairs; assigned[p] is frame-indexed, as orbm_search_by_bow_fisheye's.
-// The caller holds the vocabulary's lock (as in orbm_search_by_bow_frames_batch) and has checked its pointers.  from_map: has_map_point of pair p from row
-// from_map->rows[p] under the rule "holds a good point" (the caller holds the map's mutex as well)
+// The caller holds the vocabulary's lock (as in orbm_search_by_bow_frames_batch) and has checked its pointers.  flags: list 0 holds has_map_point of pair
+// p's key frame; from a map under the rule "holds a good point" (the caller holds the map's mutex as well)
 static int bow_rig_batch_locked(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const orbv_vocabulary* v, int P, const int* frame,
-                                orbm_keyframe* const* KFs, const uint8_t* const* has_map_point, const BowMapFlags* from_map, float nnratio, int check_ori,
-                                int* const* assigned, int* nmatches_out) {
+                                orbm_keyframe* const* KFs, CallFlags flags, float nnratio, int check_ori, int* const* assigned, int* nmatches_out) {
     VocFrameArrays V;
     if (orbv_frame_arrays(v, &V) || !V.rig)
         return fail(ORBX_E_ARG, "no rig transform: run orbv_transform_rig_extracted(v, L, %d, R, %d, %d, levelsup) first - the rig frames' rows and FeatureVectors are read where it leaves them",
@@ -1757,7 +1769,7 @@ static int bow_rig_batch_locked(orbx_extractor* L, int lf, orbx_extractor* R, in
     const int cap = L->kp_total_cap, S = V.cap;
     if (S != 2 * cap || lf + B > L->lastB || rf + B > R->lastB) return fail(ORBX_E_ARG, "the rig transform does not match the handles' extractions");
     rt::set_device(L->device);
-    size_t ftotal = 0; int maxnodes = 1;
+    int maxnodes = 1;
     std::vector<BowPairRig> pairs(P);
     for (int p = 0; p < P; p++) {
         const int b = frame[p];
@@ -1769,46 +1781,30 @@ static int bow_rig_batch_locked(orbx_extractor* L, int lf, orbx_extractor* R, in
         memset(&Q, 0, sizeof Q);
         BowPairResident& M = Q.m;
         M.k1 = K->dev;
-        M.k2.kps = L->d_kps.p + (size_t)(lf + b) * cap;                                   // mvKeys; camera 2's mvKeysRight below
-        M.k2.desc = V.desc + (size_t)b * S * 4; M.k2.ur = nullptr;
-        M.k2.node_id = V.fv_node + (size_t)b * S; M.k2.fv_start = V.fv_start + (size_t)b * (S + 1); M.k2.fv_feat = V.fv_feat + (size_t)b * S;
-        M.k2.node_of_feat = nullptr; M.k2.N = S; M.k2.fv_nodes = 0;
+        M.k2 = frame_as_k2(V, b, S, L->d_kps.p + (size_t)(lf + b) * cap, V.desc + (size_t)b * S * 4);   // mvKeys; camera 2's mvKeysRight below
         M.k2_nodes_dev = V.nout + 2 * b + 1;
-        M.mp1_off = -1; M.elig2_off = -1;
-        if ((from_map || has_map_point[p]) && K->N > 0) { M.mp1_off = (int)ftotal; ftotal += al16((size_t)K->N); }
+        M.mp1_off = flags.add(0, p, K->N, kRowHoldsGoodPoint); M.elig2_off = -1;
         Q.kps_r = R->d_kps.p + (size_t)(rf + b) * cap;
         Q.nleft = L->d_nm.p + lf + b;
         maxnodes = std::max(maxnodes, K->fv_nodes);
     }
-    std::vector<uint8_t> flags(from_map ? 0 : std::max<size_t>(ftotal, 16), 0);
-    std::vector<MapRowFlagRec> recs;
-    for (int p = 0; p < P; p++) {
-        if (pairs[p].m.mp1_off < 0) continue;
-        if (from_map) recs.push_back({from_map->rows[p], KFs[p]->N, pairs[p].m.mp1_off, kRowHoldsGoodPoint});
-        else memcpy(&flags[pairs[p].m.mp1_off], has_map_point[p], (size_t)KFs[p]->N);
-    }
     Packer pk(L);
-    size_t pf, pp, pr = 0;
-    if (from_map) { pp = pk.add(pairs.data(), sizeof(BowPairRig) * pairs.size()); pr = pk.add(recs.data(), sizeof(MapRowFlagRec) * recs.size()); pf = pk.room(std::max<size_t>(ftotal, 16)); }
-    else { pf = pk.add(flags.data(), flags.size()); pp = pk.add(pairs.data(), sizeof(BowPairRig) * pairs.size()); }
-    const size_t nout = (size_t)P * S, ntot = nout + 4 + (size_t)P;                  // assigned | status | nmatches
-    if (pk.flush() || L->d_si[SI_BEST].ensure(ntot)) return fail(ORBX_E_DEVICE, "upload/allocation failed");
-    if (from_map) row_flags(L, from_map, recs, pk.dev<MapRowFlagRec>(pr), pk.out<uint8_t>(pf));
-    if (rt::memset_async(L->d_si[SI_BEST].p, 0xFF, sizeof(int) * nout, L->s0) || rt::memset_async(L->d_si[SI_BEST].p + nout, 0, sizeof(int) * (4 + (size_t)P), L->s0))
-        return fail(ORBX_E_DEVICE, "memset failed");
+    const size_t pp = pk.add(pairs.data(), sizeof(BowPairRig) * pairs.size());
+    flags.pack(pk);
+    BowResults out = {L, (size_t)P * S, (size_t)P, {}};                             // assigned | status | nmatches
+    if (pk.flush() || out.ensure()) return fail(ORBX_E_DEVICE, "upload/allocation failed");
+    flags.fill(L, pk);
+    if (int rc = out.clear()) return rc;
     if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][0], L->s0);
     dim3 grid((maxnodes + 3) / 4, P, 1), blk(256, 1, 1);
-    ORBX_LAUNCH(k_bow_match_rig, grid, blk, 0, L->s0, pk.dev<BowPairRig>(pp), pk.dev<uint8_t>(pf), nnratio, TH_LOW, L->d_si[SI_BEST].p, S, L->d_si[SI_BEST].p + nout);
+    ORBX_LAUNCH(k_bow_match_rig, grid, blk, 0, L->s0, pk.dev<BowPairRig>(pp), flags.dev(pk), nnratio, TH_LOW, out.dev(), S, out.status());
     dim3 gridp(P, 1, 1), blkp(64, 1, 1);
-    ORBX_LAUNCH(k_bow_rotation_prune_rig, gridp, blkp, 0, L->s0, pk.dev<BowPairRig>(pp), L->d_si[SI_BEST].p, S, check_ori, L->d_si[SI_BEST].p + nout + 4);
+    ORBX_LAUNCH(k_bow_rotation_prune_rig, gridp, blkp, 0, L->s0, pk.dev<BowPairRig>(pp), out.dev(), S, check_ori, out.counts());
     if (L->profile) rt::event_record(L->ev_stage[ST_MATCH][1], L->s0);
-    std::vector<int> res(ntot);
-    if (fetch_sync(L, res.data(), L->d_si[SI_BEST].p, sizeof(int) * ntot) || rt::check_launch())
-        return fail(ORBX_E_DEVICE, "batched rig bow search failed: %s", rt::last_error());
-    if (res[nout] & 4) return fail(ORBX_E_CAPACITY, "a vocabulary node holds more than 2048 features of one rig frame");
+    if (int rc = out.fetch("batched rig bow search", "rig frame")) return rc;
     for (int p = 0; p < P; p++) {
-        memcpy(assigned[p], &res[(size_t)p * S], sizeof(int) * (size_t)S);
-        if (nmatches_out) nmatches_out[p] = res[nout + 4 + p];
+        memcpy(assigned[p], &out.res[(size_t)p * S], sizeof(int) * (size_t)S);
+        if (nmatches_out) nmatches_out[p] = out.res[out.nout + 4 + p];
     }
     return ORBX_OK;
 }
@@ -1818,7 +1814,7 @@ int orbm_search_by_bow_rig_batch(orbx_extractor* L, int lf, orbx_extractor* R, i
                                  int* nmatches_out) {
     if (!L || !R || !v || B <= 0 || P <= 0 || !frame || !KFs || !has_map_point || !assigned) return fail(ORBX_E_ARG, "null");
     const std::unique_lock<std::mutex> vlk = orbv_lock(v);       // as in orbm_search_by_bow_frames_batch
-    return bow_rig_batch_locked(L, lf, R, rf, B, v, P, frame, KFs, has_map_point, nullptr, nnratio, check_ori, assigned, nmatches_out);
+    return bow_rig_batch_locked(L, lf, R, rf, B, v, P, frame, KFs, CallFlags(has_map_point, nullptr), nnratio, check_ori, assigned, nmatches_out);
 }
 
 int orbm_search_by_bow(orbx_extractor* h, const OrbmKeyFrameView* K1, const OrbmKeyFrameView* K2, float nnratio, int th_inclusive,
@@ -3326,6 +3322,8 @@ int map_row_check(const orbx_extractor* h, const orbm_map* m, int b, int row, co
     *n = K->N;
     return ORBX_OK;
 }
+// the call-time flags of a resident search from checked rows of the map: at most two lists of rows, as CallFlags takes the caller's arrays
+CallFlags map_flags(const orbm_map* m, const int* rows0, const int* rows1) { return CallFlags(m->d_kf.p, m->kf_row_cap, m->S.state, rows0, rows1); }
 }  // namespace
 
 extern "C" {
@@ -3384,8 +3382,7 @@ int orbm_search_by_bow_frames_batch_map(orbx_extractor* h, const orbv_vocabulary
     const std::unique_lock<std::mutex> vlk = orbv_lock(v);      // the vocabulary's lock first, then the map's mutex (see struct orbm_map)
     std::lock_guard<std::mutex> lk(map->mu);                     // the call is blocking: both are held until the matches are down
     for (int b = 0; b < B; b++) { int n; if (int rc = map_row_check(h, map, b, rows[b], KFs[b], &n)) return rc; }
-    const BowMapFlags F = {map->d_kf.p, map->kf_row_cap, map->S.state, rows};
-    return bow_frames_batch_locked(h, v, first, B, KFs, nullptr, &F, nnratio, check_ori, matches12, nmatches_out);
+    return bow_frames_batch_locked(h, v, first, B, KFs, map_flags(map, rows, nullptr), nnratio, check_ori, matches12, nmatches_out);
 }
 
 // The three resident searches whose call-time flags are a function of key-frame rows and slot states.  Blocking like their host-fed forms: the map's mutex is
@@ -3395,16 +3392,11 @@ static int sft_resident_map(orbx_extractor* h, orbm_keyframe* K1, int row1, int 
     if (!h || !K1 || !map || n2 < 0 || (n2 > 0 && (!K2s || !rows2 || (!F12s && !cams) || !eps || !matches12))) return fail(ORBX_E_ARG, "null");
     if (int rc = map_search_check(h, map)) return rc;
     std::lock_guard<std::mutex> lk(map->mu);
-    std::vector<int> rows(1 + (size_t)n2);
     int n;
     if (int rc = map_row_check(h, map, 0, row1, K1, &n)) return rc;
-    rows[0] = row1;
-    for (int j = 0; j < n2; j++) {
+    for (int j = 0; j < n2; j++)
         if (int rc = map_row_check(h, map, 1 + j, rows2[j], K2s[j], &n)) return rc;       // ("frame" 1 + j: neighbour j)
-        rows[1 + j] = rows2[j];
-    }
-    const BowMapFlags F = {map->d_kf.p, map->kf_row_cap, map->S.state, rows.data()};
-    return sft_resident_impl(h, K1, nullptr, n2, K2s, nullptr, F12s, cams, eps, only_stereo, coarse, check_ori, matches12, nmatches_out, &F);
+    return sft_resident_impl(h, K1, map_flags(map, &row1, rows2), n2, K2s, F12s, cams, eps, only_stereo, coarse, check_ori, matches12, nmatches_out);
 }
 
 int orbm_search_for_triangulation_resident_map(orbx_extractor* h, orbm_keyframe* K1, int row1, int n2, orbm_keyframe* const* K2s, const int* rows2, orbm_map* map,
@@ -3430,8 +3422,7 @@ int orbm_search_by_bow_resident_map(orbx_extractor* h, int n, orbm_keyframe* con
         if (int rc = map_row_check(h, map, p, rows1[p], K1s[p], &m)) return rc;
         if (rows2 && rows2[p] != -1) if (int rc = map_row_check(h, map, p, rows2[p], K2s[p], &m)) return rc;
     }
-    const BowMapFlags F = {map->d_kf.p, map->kf_row_cap, map->S.state, rows1, rows2};
-    return bow_resident_impl(h, n, K1s, nullptr, K2s, nullptr, nnratio, th_inclusive, check_ori, matches12, nmatches_out, &F);
+    return bow_resident_impl(h, n, K1s, K2s, map_flags(map, rows1, rows2), nnratio, th_inclusive, check_ori, matches12, nmatches_out);
 }
 
 int orbm_search_by_bow_rig_batch_map(orbx_extractor* L, int lf, orbx_extractor* R, int rf, int B, const orbv_vocabulary* v, int P, const int* frame,
@@ -3441,8 +3432,7 @@ int orbm_search_by_bow_rig_batch_map(orbx_extractor* L, int lf, orbx_extractor* 
     const std::unique_lock<std::mutex> vlk = orbv_lock(v);      // the vocabulary's lock first, then the map's mutex (see struct orbm_map)
     std::lock_guard<std::mutex> lk(map->mu);
     for (int p = 0; p < P; p++) { int n; if (int rc = map_row_check(L, map, p, rows[p], KFs[p], &n)) return rc; }
-    const BowMapFlags F = {map->d_kf.p, map->kf_row_cap, map->S.state, rows};
-    return bow_rig_batch_locked(L, lf, R, rf, B, v, P, frame, KFs, nullptr, &F, nnratio, check_ori, assigned, nmatches_out);
+    return bow_rig_batch_locked(L, lf, R, rf, B, v, P, frame, KFs, map_flags(map, rows, nullptr), nnratio, check_ori, assigned, nmatches_out);
 }
 
 }  // extern "C"

@@ -10,6 +10,36 @@ from .sophus import SE3f, Sim3f, as_se3
 from .views import FuseTarget, Sim3Target, Projection as _Projection
 
 
+def _ptrs(items, n=None):
+    """A C array of n pointers (default: one per item), never of length 0, that starts with the items (None: a null pointer)."""
+    items = list(items)
+    return (C.c_void_p * max(len(items) if n is None else n, 1))(*items)
+
+
+def _flag_ptrs(flags, n, optional=False):
+    """The call-time flag arrays of n key frames as (uint8 arrays - to be kept alive over the call -, their C array of pointers); optional: None passes as a
+    null pointer."""
+    arrays = [None if optional and m is None else np.ascontiguousarray(m, np.uint8) for m in flags]
+    return arrays, _ptrs((None if m is None else m.ctypes.data for m in arrays), n)
+
+
+def _match_rows(kfs):
+    """One row of matches per key frame, pre-set to -1, the rows' C array of pointers and the match counts."""
+    outs = [np.full(max(k.N, 1), -1, np.int32) for k in kfs]
+    return outs, _ptrs(o.ctypes.data for o in outs), np.zeros(max(len(kfs), 1), np.int32)
+
+
+def _matched_rows(nm, outs, kfs):
+    """[(nmatches, matches12[N1])] per key frame from what _match_rows laid out."""
+    return [(int(nm[p]), outs[p][:k.N]) for p, k in enumerate(kfs)]
+
+
+def _neighbour_pairs(nm, m12, n2, N1):
+    """[(nmatches, [(i1, i2)...])] per neighbour from the (n2, N1) block a resident triangulation search filled."""
+    m12 = m12.reshape(-1)[:n2 * N1].reshape(n2, N1) if N1 > 0 else m12[:n2, :0]
+    return [(int(nm[j]), [(int(i), int(m12[j, i])) for i in np.nonzero(m12[j] >= 0)[0]]) for j in range(n2)]
+
+
 class ORBmatcher:
     TH_LOW, TH_HIGH, HISTO_LENGTH = 50, 100, 30   # src/ORBmatcher.cc:35-37
 
@@ -79,29 +109,25 @@ class ORBmatcher:
         none).  Returns the same list of (nmatches, pairs)."""
         n2 = len(kf2s)
         F = np.ascontiguousarray(F12s, np.float32).reshape(n2, 9); E = np.ascontiguousarray(eps, np.float32).reshape(n2, 2)
-        ptrs = (C.c_void_p * max(n2, 1))(*[k._kf for k in kf2s])
+        ptrs = _ptrs(k._kf for k in kf2s)
         m1 = None if mp1 is None else np.ascontiguousarray(mp1, np.uint8)
-        m2 = [None if m is None else np.ascontiguousarray(m, np.uint8) for m in mp2s]
-        pm2 = (C.c_void_p * max(n2, 1))(*[None if m is None else m.ctypes.data for m in m2])
+        m2, pm2 = _flag_ptrs(mp2s, n2, optional=True)
         N1 = kf1.N
         m12 = np.full((max(n2, 1), max(N1, 1)), -1, np.int32); nm = np.zeros(max(n2, 1), np.int32)
         ext._lib.check(ext._lib.L.orbm_search_for_triangulation_resident(ext._h, kf1._kf, None if m1 is None else m1.ctypes.data, n2, ptrs, pm2, F.ctypes.data,
                                                                        E.ctypes.data, int(bOnlyStereo), int(bCoarse), int(self.mbCheckOrientation), m12.ctypes.data,
                                                                        nm.ctypes.data))
-        m12 = m12.reshape(-1)[:n2 * N1].reshape(n2, N1) if N1 > 0 else m12[:n2, :0]
-        return [(int(nm[j]), [(int(i), int(m12[j, i])) for i in np.nonzero(m12[j] >= 0)[0]]) for j in range(n2)]
+        return _neighbour_pairs(nm, m12, n2, N1)
 
     def SearchByBoWResident(self, ext, kf1s, mp1s, kf2s, elig2s, frame_version=True):
         """SearchByBoWBatch over ResidentKeyFrame objects: mp1s[p] = uint8 flags "feature of kf1s[p] has a good map point", elig2s[p] = flags of the
         features of kf2s[p] that may be matched (None = all).  Returns the same list of (nmatches, matches12)."""
         n = len(kf1s)
-        p1 = (C.c_void_p * max(n, 1))(*[k._kf for k in kf1s]); p2 = (C.c_void_p * max(n, 1))(*[k._kf for k in kf2s])
-        a1 = [None if m is None else np.ascontiguousarray(m, np.uint8) for m in mp1s]; a2 = [None if m is None else np.ascontiguousarray(m, np.uint8) for m in elig2s]
-        q1 = (C.c_void_p * max(n, 1))(*[None if m is None else m.ctypes.data for m in a1]); q2 = (C.c_void_p * max(n, 1))(*[None if m is None else m.ctypes.data for m in a2])
-        outs = [np.full(max(k.N, 1), -1, np.int32) for k in kf1s]
-        po = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs]); nm = np.zeros(max(n, 1), np.int32)
+        p1 = _ptrs(k._kf for k in kf1s); p2 = _ptrs(k._kf for k in kf2s)
+        a1, q1 = _flag_ptrs(mp1s, n, optional=True); a2, q2 = _flag_ptrs(elig2s, n, optional=True)
+        outs, po, nm = _match_rows(kf1s)
         ext._lib.check(ext._lib.L.orbm_search_by_bow_resident(ext._h, n, p1, q1, p2, q2, self.mfNNratio, int(frame_version), int(self.mbCheckOrientation), po, nm.ctypes.data))
-        return [(int(nm[p]), outs[p][:kf1s[p].N]) for p in range(n)]
+        return _matched_rows(nm, outs, kf1s)
 
     def SearchForTriangulationResidentMap(self, ext, kf1, row1, kf2s, rows2, resident_map, F12s, eps, bOnlyStereo=False, bCoarse=False, cams=None):
         """SearchForTriangulationResident with the flags read on the device from the key frames' rows in a ResidentMap
@@ -110,7 +136,7 @@ class ORBmatcher:
         (orbm_search_for_triangulation_resident_kb8_map).  Returns the same list of (nmatches, pairs)."""
         n2 = len(kf2s)
         E = np.ascontiguousarray(eps, np.float32).reshape(n2, 2)
-        ptrs = (C.c_void_p * max(n2, 1))(*[k._kf for k in kf2s])
+        ptrs = _ptrs(k._kf for k in kf2s)
         r2 = np.ascontiguousarray(rows2, np.int32)
         if len(r2) != n2:
             raise ValueError("%d rows for %d neighbours" % (len(r2), n2))
@@ -122,23 +148,21 @@ class ORBmatcher:
             ext._lib.check(ext._lib.L.orbm_search_for_triangulation_resident_map(ext._h, kf1._kf, int(row1), n2, ptrs, r2.ctypes.data, resident_map._m, F.ctypes.data, *tail))
         else:
             ext._lib.check(ext._lib.L.orbm_search_for_triangulation_resident_kb8_map(ext._h, kf1._kf, int(row1), n2, ptrs, r2.ctypes.data, resident_map._m, C.addressof(cams), *tail))
-        m12 = m12.reshape(-1)[:n2 * N1].reshape(n2, N1) if N1 > 0 else m12[:n2, :0]
-        return [(int(nm[j]), [(int(i), int(m12[j, i])) for i in np.nonzero(m12[j] >= 0)[0]]) for j in range(n2)]
+        return _neighbour_pairs(nm, m12, n2, N1)
 
     def SearchByBoWResidentMap(self, ext, kf1s, rows1, kf2s, rows2, resident_map, frame_version=True):
         """SearchByBoWResident with the flags read on the device from the key frames' rows in a ResidentMap (orbm_search_by_bow_resident_map):
         rows1[p] = the row of kf1s[p], rows2 = None or rows2[p] = the row of kf2s[p] or -1 (every feature of kf2s[p] is eligible); an entry counts iff
         its slot is >= 0 and holds a point that is not bad.  Returns the same list of (nmatches, matches12)."""
         n = len(kf1s)
-        p1 = (C.c_void_p * max(n, 1))(*[k._kf for k in kf1s]); p2 = (C.c_void_p * max(n, 1))(*[k._kf for k in kf2s])
+        p1 = _ptrs(k._kf for k in kf1s); p2 = _ptrs(k._kf for k in kf2s)
         r1 = np.ascontiguousarray(rows1, np.int32); r2 = None if rows2 is None else np.ascontiguousarray(rows2, np.int32)
         if len(r1) != n or (r2 is not None and len(r2) != n):
             raise ValueError("the row lists need %d entries" % n)
-        outs = [np.full(max(k.N, 1), -1, np.int32) for k in kf1s]
-        po = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs]); nm = np.zeros(max(n, 1), np.int32)
+        outs, po, nm = _match_rows(kf1s)
         ext._lib.check(ext._lib.L.orbm_search_by_bow_resident_map(ext._h, n, p1, r1.ctypes.data, p2, None if r2 is None else r2.ctypes.data, resident_map._m, self.mfNNratio,
                                                                   int(frame_version), int(self.mbCheckOrientation), po, nm.ctypes.data))
-        return [(int(nm[p]), outs[p][:kf1s[p].N]) for p in range(n)]
+        return _matched_rows(nm, outs, kf1s)
 
     def SearchByBoWFramesBatch(self, ext, voc, kfs, mps, first=0, resident_map=None, rows=None):
         """ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) for the frames [first, first + len(kfs)) of ext's last extraction on the device
@@ -148,9 +172,8 @@ class ORBmatcher:
         resident_map, rows (mps = None): the flags are read on the device from rows[b], the row of kfs[b] in the ResidentMap - an entry counts iff its
         slot is >= 0 and holds a point that is not bad (orbm_search_by_bow_frames_batch_map)."""
         B = len(kfs)
-        p1 = (C.c_void_p * max(B, 1))(*[k._kf for k in kfs])
-        outs = [np.full(max(k.N, 1), -1, np.int32) for k in kfs]
-        po = (C.c_void_p * max(B, 1))(*[o.ctypes.data for o in outs]); nm = np.zeros(max(B, 1), np.int32)
+        p1 = _ptrs(k._kf for k in kfs)
+        outs, po, nm = _match_rows(kfs)
         if resident_map is not None or rows is not None:
             if resident_map is None or rows is None or mps is not None:
                 raise ValueError("the map-fed form takes resident_map and rows, and mps = None")
@@ -159,11 +182,10 @@ class ORBmatcher:
                 raise ValueError("%d rows for %d key frames" % (len(r), B))
             ext._lib.check(ext._lib.L.orbm_search_by_bow_frames_batch_map(ext._h, voc._v, int(first), B, p1, resident_map._m, r.ctypes.data, self.mfNNratio,
                                                                           int(self.mbCheckOrientation), po, nm.ctypes.data))
-            return [(int(nm[b]), outs[b][:kfs[b].N]) for b in range(B)]
-        a1 = [np.ascontiguousarray(m, np.uint8) for m in mps]
-        q1 = (C.c_void_p * max(B, 1))(*[m.ctypes.data for m in a1])
-        ext._lib.check(ext._lib.L.orbm_search_by_bow_frames_batch(ext._h, voc._v, int(first), B, p1, q1, self.mfNNratio, int(self.mbCheckOrientation), po, nm.ctypes.data))
-        return [(int(nm[b]), outs[b][:kfs[b].N]) for b in range(B)]
+        else:
+            a1, q1 = _flag_ptrs(mps, B)
+            ext._lib.check(ext._lib.L.orbm_search_by_bow_frames_batch(ext._h, voc._v, int(first), B, p1, q1, self.mfNNratio, int(self.mbCheckOrientation), po, nm.ctypes.data))
+        return _matched_rows(nm, outs, kfs)
 
     def SearchByBoWRigBatch(self, exL, lf, exR, rf, voc, frames, kfs, mps, n_frame=None, resident_map=None, rows=None):
         """ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) for fisheye-rig frames on the device (orbm_search_by_bow_rig_batch): voc = the
@@ -176,22 +198,23 @@ class ORBmatcher:
         P = len(kfs)
         fr = np.ascontiguousarray(frames, np.int32)
         S = 2 * exL.max_keypoints()
-        p1 = (C.c_void_p * max(P, 1))(*[k._kf for k in kfs])
+        p1 = _ptrs(k._kf for k in kfs)
         outs = [np.full(S, -1, np.int32) for _ in range(P)]
-        po = (C.c_void_p * max(P, 1))(*[o.ctypes.data for o in outs]); nm = np.zeros(max(P, 1), np.int32)
+        po = _ptrs(o.ctypes.data for o in outs); nm = np.zeros(max(P, 1), np.int32)
+
+        def search(entry, *flags):                   # the two entry points differ in their flag arguments alone
+            exL._lib.check(entry(exL._h, int(lf), exR._h, int(rf), int(getattr(voc, "_rig_B", 0)), voc._v, P, fr.ctypes.data, p1, *flags, self.mfNNratio,
+                                 int(self.mbCheckOrientation), po, nm.ctypes.data))
         if resident_map is not None or rows is not None:
             if resident_map is None or rows is None or mps is not None:
                 raise ValueError("the map-fed form takes resident_map and rows, and mps = None")
             r = np.ascontiguousarray(rows, np.int32)
             assert len(fr) == P and len(r) == P
-            exL._lib.check(exL._lib.L.orbm_search_by_bow_rig_batch_map(exL._h, int(lf), exR._h, int(rf), int(getattr(voc, "_rig_B", 0)), voc._v, P, fr.ctypes.data, p1,
-                                                                       resident_map._m, r.ctypes.data, self.mfNNratio, int(self.mbCheckOrientation), po, nm.ctypes.data))
-            return [(int(nm[p]), outs[p] if n_frame is None else outs[p][:int(n_frame[fr[p]])]) for p in range(P)]
-        assert len(fr) == P and len(mps) == P
-        a1 = [np.ascontiguousarray(m, np.uint8) for m in mps]
-        q1 = (C.c_void_p * max(P, 1))(*[m.ctypes.data for m in a1])
-        exL._lib.check(exL._lib.L.orbm_search_by_bow_rig_batch(exL._h, int(lf), exR._h, int(rf), int(getattr(voc, "_rig_B", 0)), voc._v, P, fr.ctypes.data, p1, q1,
-                                                               self.mfNNratio, int(self.mbCheckOrientation), po, nm.ctypes.data))
+            search(exL._lib.L.orbm_search_by_bow_rig_batch_map, resident_map._m, r.ctypes.data)
+        else:
+            assert len(fr) == P and len(mps) == P
+            a1, q1 = _flag_ptrs(mps, P)
+            search(exL._lib.L.orbm_search_by_bow_rig_batch, q1)
         return [(int(nm[p]), outs[p] if n_frame is None else outs[p][:int(n_frame[fr[p]])]) for p in range(P)]
 
     def SearchByBoWFisheye(self, ext, kf, frame, nleft):
